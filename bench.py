@@ -32,6 +32,17 @@ that IS HBM-bound (the queue build: bytes from the same counter passes over its 
 `presented_frame` (N = 1) times the frame the reference presents: five images at 4 spp with the shipped LTC
 tables, four a-trous rounds, combine.  `cpu_baseline` is the CPU oracle (a scalar C++ port, oracle/)
 timed on the host cores on a bounded sample of the same workload — reported, not a target.
+
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, the line.  Everything else it can
+measure or check — roofline / roofline_secondary / frame_hbm, the one-frame-at-a-time pass (--isolated-frames), the
+presented frame (--present-frames), the CPU baseline, --verify and the final assembled-vs-unsharded check of N > 1 —
+runs only with --full (those keys are null in a plain line):
+
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full
+
+--dump-outputs DIR writes, after the timed steps, what the timed path computed in its last step (rank 0's assembled
+framebuffer, and the HDR accumulation when --accumulate > 1) as DIR/<name>.npy in float32, so that two builds can be
+compared output for output: the inputs (scene, cameras, seeds) depend on the arguments only.
 """
 import argparse
 import json
@@ -206,6 +217,31 @@ def build_setup(args, scenes, np):
         args.workload = "obj:" + os.path.basename(args.obj)
         return setup
     return getattr(scenes, WORKLOADS[args.workload])(W, H)
+
+
+DUMP_BUDGET_BYTES = 60_000_000        # --dump-outputs: the arrays in all (headers included, below 64 MB)
+
+
+def rgba8_channels(fb):
+    """a packed RGBA8 framebuffer (rows x width uint32) as rows x width x 4 channel values (R, G, B, A)"""
+    import numpy as np
+    return np.ascontiguousarray(fb).view(np.uint8).reshape(fb.shape[0], fb.shape[1], 4)
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: arrays (name -> rows x width x channels) as d/<name>.npy in float32.  Over DUMP_BUDGET_BYTES in all, the same
+    fixed, seeded sample of pixels is taken from every array (pixels x channels), and d/pixel_index.npy holds their row-major indices."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float32) for k, v in arrays.items()}
+    npix = next(iter(arrays.values())).shape[0] * next(iter(arrays.values())).shape[1]
+    if sum(a.nbytes for a in arrays.values()) > DUMP_BUDGET_BYTES:
+        per_pixel = sum(a.nbytes for a in arrays.values()) // npix + 8
+        idx = np.sort(np.random.default_rng(0).choice(npix, DUMP_BUDGET_BYTES // per_pixel, replace=False))
+        arrays = {k: a.reshape(npix, -1)[idx] for k, a in arrays.items()}
+        arrays["pixel_index"] = idx.astype(np.float64)
+    for k, a in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), a)
 
 
 FIRST_EXCHANGE_TIMEOUT_MS = 60000        # watchdog of the verified first exchange (RTR_MGPU_TIMEOUT_MS, if set, wins)
@@ -475,11 +511,15 @@ def run_inproc(args, K, plan):
     sync_all()
     elapsed = time.perf_counter() - t0
 
-    # the assembled frame of the last step against the same frame rendered unsharded on device 0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"framebuffer_rgba8": rgba8_channels(mg.download(last_slot[0]))})
+    # the assembled frame of the last step against the same frame rendered unsharded on device 0 (--full)
     last_i = args.warmup + args.steps - 1
-    for j in range(K):
-        api.render(scene, cams.camera(last_i), cams.info(last_i, j if K > 1 else None), params(0, j=j), whole)
-    bad = int((mg.download(last_slot[0]) != whole.download()).sum())
+    bad = None
+    if args.full:
+        for j in range(K):
+            api.render(scene, cams.camera(last_i), cams.info(last_i, j if K > 1 else None), params(0, j=j), whole)
+        bad = int((mg.download(last_slot[0]) != whole.download()).sum())
     info = A.rtr_mgpu_info()
     A.mgpu_lib().rtr_mgpu_get_info(mg.h, C.byref(info))          # after the run: with the host time of the ranks' threads
     host_frames = max(int(info.enqueuedFrames) - int(info0.enqueuedFrames), 1)
@@ -511,7 +551,7 @@ def run_inproc(args, K, plan):
                  # host time of the slowest rank's thread per frame it enqueued (stream waits, the launch, RCCL calls, event records): the
                  # ranks' threads run side by side, so this — not its sum over ranks — is what must stay below a shard's GPU time
                  "host_enqueue_ms_per_frame": round(host_ms, 4), "of_which_inside_rccl_calls": round(host_rccl_ms, 4)},
-        "verify": {"assembled_vs_unsharded_pixels_differing": bad, "frame": last_i},
+        "verify": {"assembled_vs_unsharded_pixels_differing": bad, "frame": last_i} if args.full else None, "full": args.full,
         "rehearsal": ("the %d ranks share ONE GPU (RTR_MGPU_TEST_SHARED_DEVICE=1; rcclVersion 99999 = tests/fake_rccl, a same-device double of RCCL): "
                       "the rate is one GPU's, time-sliced — not a scaling point" % N) if plan.get("shared_device") else None,
         "roofline": None, "roofline_note": "the roofline block is reported for the one-GPU run of the same workload (N = 1 line)",
@@ -559,14 +599,20 @@ def main():
     ap.add_argument("--config", type=int, default=0, choices=[0, 1, 2, 3, 4, 5],
                     help="shortcut for a BASELINE.json config: 1 cornell 256x256 (the reference's CPU-runnable case), 2 cornell 1080p, 3 bunny_class 1080p 4 spp, 4 (default) sponza_class 1080p, "
                          "5 sponza_class 4K x16 accumulated")
-    ap.add_argument("--isolated-frames", type=int, default=10,
-                    help="after the timed region, render this many frames ONE AT A TIME to report per-kernel durations free of "
-                         "cross-frame overlap (0 = skip; profiles/run_rocprof.sh skips it so rocprof's averages cover the timed launches only)")
-    ap.add_argument("--present-frames", type=int, default=20,
-                    help="after the timed region (N=1), time this many PRESENTED frames of the same scene as the reference's frame loop makes them "
+    ap.add_argument("--isolated-frames", type=int, default=None,
+                    help="with --full: after the timed region, render this many frames ONE AT A TIME to report per-kernel durations free of "
+                         "cross-frame overlap (default 10; 0 = skip; profiles/run_rocprof.sh skips it so rocprof's averages cover the timed launches only)")
+    ap.add_argument("--present-frames", type=int, default=None,
+                    help="with --full: after the timed region (N=1), time this many PRESENTED frames of the same scene as the reference's frame loop makes them "
                          "(application.cppm:391-457): ray-gen of all five images at 4 spp with the shipped LTC tables, four a-trous rounds on the "
-                         "sampled pair, combine -> FINAL; reported as `presented_frame` (0 = skip)")
-    ap.add_argument("--verify", action="store_true", help="after timing, check the assembled frame against the oracle on a row sample")
+                         "sampled pair, combine -> FINAL; reported as `presented_frame` (default 20; 0 = skip)")
+    ap.add_argument("--verify", action="store_true", help="with --full: after timing, check the assembled frame against the oracle on a row sample")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, measure and check everything else: roofline blocks, the one-frame-at-a-time pass, the presented frame, "
+                         "the CPU baseline (unless --no-cpu-baseline), --verify, and N > 1's assembled frame against an unsharded render")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float32; at most 64 MB in all, "
+                         "a fixed seeded sample of pixels beyond that)")
     ap.add_argument("--obj", default=None, metavar="PATH",
                     help="render a real asset instead of the procedural stand-in (SURVEY 8d: 'real bunny.obj / sponza.obj accepted if present'): "
                          "an OBJ file with its MTL / textures beside it; the camera looks at the centre of its bounds from --obj-view, one area light "
@@ -579,6 +625,12 @@ def main():
                          "touched the GPU, and relays its JSON line and return code")
     ap.add_argument("--print-launch", action="store_true", help="print, as one JSON line, how this invocation would be run, and exit")
     args = ap.parse_args()
+    if not args.full:
+        asked = [o for o, v in (("--isolated-frames", args.isolated_frames), ("--present-frames", args.present_frames), ("--verify", args.verify)) if v]
+        if asked:
+            ap.error(", ".join(asked) + ": measured or checked only with --full")
+    args.isolated_frames = (10 if args.full else 0) if args.isolated_frames is None else args.isolated_frames
+    args.present_frames = (20 if args.full else 0) if args.present_frames is None else args.present_frames
 
     if args.config == 1:
         args.workload, args.width, args.height = "cornell", 256, 256
@@ -966,6 +1018,17 @@ def main():
         tt = torch.tensor([elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if args.dump_outputs and rank == 0:
+        # the last timed step's frame, before anything below renders into a frame object again
+        b = last_buf[0]
+        if not dist_on:
+            fb = locals_[b].cpu().numpy().view(np.uint32)
+        else:
+            fb = mg.download(b) if use_lib else fulls[b].cpu().numpy().view(np.uint32)
+        outs = {"framebuffer_rgba8": rgba8_channels(fb)}
+        if K > 1 and not dist_on:
+            outs["hdr"] = frames[b].download(A.IMAGE_HDR)
+        dump_outputs(args.dump_outputs, outs)
 
     # After the timed region: the same frames ONE AT A TIME, so every kernel has the GPU to itself.  With several frames in
     # flight a launch's HIP-event bracket also contains the time it queued behind / shared CUs with the neighbouring frames'
@@ -1039,7 +1102,7 @@ def main():
         trace_rays = sched["shadow_rays"] * (args.steps if own_launch else 1)     # shadow rays those launches traced (counting form, mean of the timed frames)
         trace_bytes = trace_bytes_mean * (args.steps if own_launch else 1)
         roofline, roofline2, frame_hbm = None, None, None
-        if pipeline_used == 2 and trace_ms > 0:
+        if args.full and pipeline_used == 2 and trace_ms > 0:        # the roofline blocks: --full only
             rev = A.hip_lib().rtr_kernel_revision().decode()
             pmc, pmc_note, pmc_key, pmc_file = None, None, None, None
             # The counter totals are NOT measured by this process (rocprofv3 has to wrap it): they are committed passes of this command
@@ -1173,7 +1236,7 @@ def main():
                 frame_hbm = {"bytes_per_frame": int(fb) if fb else None, "per_kernel_per_launch": {kk: int((vv["read_bytes"] + vv["write_bytes"]) * scale) for kk, vv in pmc["kernels"].items()},
                              "gbps_at_ms_per_step": round(fb / (ms_per_step * 1e-3) / 1e9, 1), "frac_of_hbm_peak": round(fb / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
                              "scope": "sum of the frame's four kernels' HBM bytes (committed counter passes, scaled by rays) over this run's frame time"} if fb else None
-        elif trace_ms == 0 and kern["primary"] > 0:
+        elif args.full and trace_ms == 0 and kern["primary"] > 0:
             mk_ms = kern["primary"] / n
             achieved = alg_bytes_mean / (mk_ms * 1e-3) / 1e9
             roofline = {"bound": "hbm", "kernel": "k_megakernel", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
@@ -1212,13 +1275,14 @@ def main():
             "roofline_secondary": roofline2,
             "frame_hbm": frame_hbm,
             "presented_frame": presented,
+            "full": args.full,
         }
 
     # ---- reported CPU baseline (rank 0, N=1 only): the oracle on a bounded sample --------------------------
     if rank == 0 and emu:
         out["emulated_rank_of"] = emu
         out["config"]["workload"] += f" [single-GPU rehearsal of ONE rank of {emu}: shard 0 only, no gather; value = this rank's rays/s]"
-    if rank == 0 and not dist_on and not emu and not args.no_cpu_baseline:
+    if rank == 0 and not dist_on and not emu and args.full and not args.no_cpu_baseline:
         from oracle import oracle_py as O
         threads = min(os.cpu_count() or 1, 16)
         bvh = scene.export_bvh()
@@ -1253,15 +1317,17 @@ def main():
         out["cpu_baseline"] = None
     elif rank == 0:
         out["cpu_baseline"] = None
-        # N > 1: the assembled frame of the last step must equal the same frame rendered unsharded on this GPU
-        last_i = args.warmup + args.steps - 1
-        whole = api.Frame(ctx, W, H, images)
-        render_step(whole, last_i, [params(0, 0, 1, j=j) for j in range(K)], False)
-        torch.cuda.synchronize()
-        assembled = mg.download(last_buf[0]) if use_lib else fulls[last_buf[0]].cpu().numpy().view(np.uint32)
-        bad = int((assembled != whole.download()).sum())
-        out["verify"] = {"assembled_vs_unsharded_pixels_differing": bad, "frame": last_i,
-                         "gather": "librtr_mgpu.so: grouped ncclSend / ncclRecv to rank 0 on a communication stream + k_deinterleave" if use_lib else "torch.distributed gather (rehearsal backend)"}
+        # N > 1 (--full): the assembled frame of the last step must equal the same frame rendered unsharded on this GPU
+        out["verify"] = None
+        if args.full:
+            last_i = args.warmup + args.steps - 1
+            whole = api.Frame(ctx, W, H, images)
+            render_step(whole, last_i, [params(0, 0, 1, j=j) for j in range(K)], False)
+            torch.cuda.synchronize()
+            assembled = mg.download(last_buf[0]) if use_lib else fulls[last_buf[0]].cpu().numpy().view(np.uint32)
+            bad = int((assembled != whole.download()).sum())
+            out["verify"] = {"assembled_vs_unsharded_pixels_differing": bad, "frame": last_i,
+                             "gather": "librtr_mgpu.so: grouped ncclSend / ncclRecv to rank 0 on a communication stream + k_deinterleave" if use_lib else "torch.distributed gather (rehearsal backend)"}
         if use_lib:
             out["rccl"] = {"nranks": int(mg.info.nranks), "nlocal": int(mg.info.nlocal), "version": int(mg.info.rcclVersion),
                            "first_exchange_verified": rccl0["first_exchange_verified"], "first_exchange_ms": rccl0["first_exchange_ms"],

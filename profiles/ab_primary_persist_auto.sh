@@ -10,8 +10,8 @@ for l in sys.stdin:
 "; }
 for rep in 1 2; do
 for m in 0 2; do
-  RTR_PRIMARY_PERSIST=$m python3 bench.py --steps 16 --warmup 4 --present-frames 10 2>/dev/null | show "[config 4 default + presented] persist=$m"
-  RTR_PRIMARY_PERSIST=$m python3 bench.py --config 3 --batch 1 --frames-in-flight 4 --steps 40 --warmup 8 --present-frames 0 2>/dev/null | show "[config 3, one frame per launch, 4 in flight] persist=$m"
-  RTR_PRIMARY_PERSIST=$m python3 bench.py --config 3 --batch 1 --frames-in-flight 1 --steps 40 --warmup 8 --present-frames 0 2>/dev/null | show "[config 3, one frame per launch, 1 in flight] persist=$m"
-  RTR_PRIMARY_PERSIST=$m python3 bench.py --config 5 --steps 3 --warmup 1 --present-frames 0 2>/dev/null | show "[config 5] persist=$m"
+  RTR_PRIMARY_PERSIST=$m python3 bench.py --full --steps 16 --warmup 4 --present-frames 10 2>/dev/null | show "[config 4 default + presented] persist=$m"
+  RTR_PRIMARY_PERSIST=$m python3 bench.py --full --config 3 --batch 1 --frames-in-flight 4 --steps 40 --warmup 8 --present-frames 0 2>/dev/null | show "[config 3, one frame per launch, 4 in flight] persist=$m"
+  RTR_PRIMARY_PERSIST=$m python3 bench.py --full --config 3 --batch 1 --frames-in-flight 1 --steps 40 --warmup 8 --present-frames 0 2>/dev/null | show "[config 3, one frame per launch, 1 in flight] persist=$m"
+  RTR_PRIMARY_PERSIST=$m python3 bench.py --full --config 5 --steps 3 --warmup 1 --present-frames 0 2>/dev/null | show "[config 5] persist=$m"
 done; done

@@ -8,5 +8,5 @@ for l in sys.stdin:
         j=json.loads(l); print('$1', 'ms/frame', j['ms_per_step'], j['value'], (j.get('kernels_ms_in_flight_event_brackets') or {}), (j.get('verify') or {}))
 "; }
 for rep in 1 2 3; do for a in 0 1; do
-  RTR_QUEUE_AFFINITY=$a python3 bench.py --steps 96 --warmup 32 --present-frames 0 --isolated-frames 0 --verify 2>/dev/null | show "[affinity $a]"
+  RTR_QUEUE_AFFINITY=$a python3 bench.py --full --steps 96 --warmup 32 --present-frames 0 --isolated-frames 0 --verify 2>/dev/null | show "[affinity $a]"
 done; done

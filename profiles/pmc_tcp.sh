@@ -7,7 +7,7 @@ OUT=$REPO/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 -L > "$OUT/counters_available.txt" 2>&1 || true
-BENCH="python3 $REPO/bench.py --steps 5 --warmup 1 --no-cpu-baseline --frames-in-flight 1 $@"
+BENCH="python3 $REPO/bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --frames-in-flight 1 $@"
 timeout -k 10 170 rocprofv3 --kernel-trace --pmc TCP_TOTAL_CACHE_ACCESSES_sum TCP_TCC_READ_REQ_sum TCP_TOTAL_ACCESSES_sum TCP_PENDING_STALL_CYCLES_sum --output-format csv -d "$OUT/pmc_tcp1" -- $BENCH > "$OUT/bench_pmc_tcp1.log" 2> "$OUT/rocprof_pmc_tcp1.log" || echo "tcp1 failed"
 # (round 1: a pass with TA_BUSY_avr / TA_TA_BUSY_sum / TA_ADDR_STALLED_BY_TC_CYCLES_sum / TA_DATA_STALLED_BY_TC_CYCLES_sum aborted inside
 #  rocprofv3 and the bench process then hung until the run's limit; its output was not kept.  Round 3 met the same abort with its

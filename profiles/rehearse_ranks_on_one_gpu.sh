@@ -3,8 +3,8 @@
 # of `python bench.py --gpus N` and a measure of what the exchange machinery costs (the rate is one GPU's, time-sliced by N ranks).
 cd ${GRAFT_REPO_ROOT:-.}
 for n in 1 2 4 8; do
-  if [ $n = 1 ]; then python3 bench.py --steps 96 --warmup 16 --present-frames 0 --no-cpu-baseline --isolated-frames 0 2>/dev/null
-  else LD_PRELOAD=$PWD/tests/fake_rccl/libfake_rccl.so RTR_MGPU_TEST_SHARED_DEVICE=1 python3 bench.py --gpus $n --steps 96 --warmup 32 2>/dev/null; fi | python3 -c "
+  if [ $n = 1 ]; then python3 bench.py --full --steps 96 --warmup 16 --present-frames 0 --no-cpu-baseline --isolated-frames 0 2>/dev/null
+  else LD_PRELOAD=$PWD/tests/fake_rccl/libfake_rccl.so RTR_MGPU_TEST_SHARED_DEVICE=1 python3 bench.py --full --gpus $n --steps 96 --warmup 32 2>/dev/null; fi | python3 -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):
@@ -13,7 +13,7 @@ for l in sys.stdin:
 done
 # the same with sixteen shards per launch given explicitly (round 3's launches): what ONE exchange per launch does to the ranks' host time
 for n in 4 8; do
-  LD_PRELOAD=$PWD/tests/fake_rccl/libfake_rccl.so RTR_MGPU_TEST_SHARED_DEVICE=1 python3 bench.py --gpus $n --steps 96 --warmup 32 --batch 16 2>/dev/null | python3 -c "
+  LD_PRELOAD=$PWD/tests/fake_rccl/libfake_rccl.so RTR_MGPU_TEST_SHARED_DEVICE=1 python3 bench.py --full --gpus $n --steps 96 --warmup 32 --batch 16 2>/dev/null | python3 -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):

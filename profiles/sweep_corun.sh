@@ -5,7 +5,7 @@
 cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out/r04
 L=gpurun_out/r04/sweep_corun.log; : > $L
-run() { w=$1; b=$2; f=$3; RTR_TRACE_WGS_PER_CU=$w python3 bench.py --steps 96 --warmup 16 --batch $b --frames-in-flight $f --isolated-frames 2 --no-cpu-baseline --present-frames 0 2>/dev/null | python3 -c "
+run() { w=$1; b=$2; f=$3; RTR_TRACE_WGS_PER_CU=$w python3 bench.py --full --steps 96 --warmup 16 --batch $b --frames-in-flight $f --isolated-frames 2 --no-cpu-baseline --present-frames 0 2>/dev/null | python3 -c "
 import sys,json
 j=json.loads([l for l in sys.stdin if l.startswith('{')][-1])
 print('trace_wgs_per_cu $w frames/launch $b frame objects $f | ms/frame', j['ms_per_step'], '| Mrays/s', j['value'], '| latency', j.get('frame_latency_ms'), '| kernels in flight', j.get('kernels_ms_in_flight_event_brackets') or j.get('kernels_ms'))" | tee -a $L; }

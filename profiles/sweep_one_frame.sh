@@ -1,6 +1,6 @@
 #!/bin/bash
 # A frame rendered ALONE (one launch per frame, joined before the next): run-time knobs of the any-hit kernel once more, for this case only.
-run() { env "$@" python3 bench.py --steps 24 --warmup 6 --batch 1 --frames-in-flight 1 --isolated-frames 24 --no-cpu-baseline --present-frames 0 2>/dev/null | python3 -c "
+run() { env "$@" python3 bench.py --full --steps 24 --warmup 6 --batch 1 --frames-in-flight 1 --isolated-frames 24 --no-cpu-baseline --present-frames 0 2>/dev/null | python3 -c "
 import sys,json
 j=json.loads([l for l in sys.stdin if l.startswith('{')][-1])
 print('$*', '| one frame at a time', j['one_frame_at_a_time']['ms_per_step'], '| ms/step', j['ms_per_step'], '| kernels', j['kernels_ms'])"; }

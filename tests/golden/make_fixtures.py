@@ -11,6 +11,9 @@ place where /root/reference and oracle/_ref exist):  python tests/golden/make_fi
   cornell_256_oracle.npz  oracle (brute force, no BVH) render of Cornell 256x256 1spp: the 5 ray-gen images
                           + HDR — a regression pin of the oracle itself (parity is otherwise UNPINNED: the
                           reference ships no golden image)
+  ref_ltc_tables.bin      the reference's two 64x64 RGBA32F LTC tables (external/LUT/ltc_matrix.h, dumped by
+                          oracle/_ref/ltc_dump) as 2 x 16384 little-endian floats: what tests/test_ltc_tables.py
+                          and tests/test_host_scene.py compare the shipped tables with
 """
 import hashlib
 import json
@@ -84,9 +87,19 @@ def image_hashes():
     print("image_stb_hashes.json:", len(out), "files")
 
 
+def ltc_tables():
+    """5) the reference's LTC tables, as the reference uploads them (oracle/_ref/ltc_dump) -> tests/golden/ref_ltc_tables.bin"""
+    raw = subprocess.run([os.path.join(ROOT, "oracle", "_ref", "ltc_dump")], check=True, capture_output=True).stdout
+    assert len(raw) == 2 * 16384 * 4
+    open(os.path.join(HERE, "ref_ltc_tables.bin"), "wb").write(raw)
+    print("ref_ltc_tables.bin:", len(raw), "bytes")
+
+
 def main():
     if len(sys.argv) > 1 and sys.argv[1] == "images":
         return image_hashes()
+    if len(sys.argv) > 1 and sys.argv[1] == "ltc":
+        return ltc_tables()
     from realtimeraytracer_amd import _abi as A
     from realtimeraytracer_amd import scenes
     from oracle import oracle_py as O
@@ -123,6 +136,7 @@ def main():
                         counters=np.array([r.stats.numRays, r.stats.numPrimaryRays, r.stats.numShadowRays, r.stats.numHits,
                                            r.stats.numLightFetches, r.stats.numLightTriFetches], dtype=np.uint64))
     image_hashes()
+    ltc_tables()
     print("fixtures written to", HERE)
 
 

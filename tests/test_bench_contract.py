@@ -1,5 +1,6 @@
 """bench.py is what the driver runs: its one JSON line must keep the contract (metric / value / roofline / cpu_baseline ...), the
-presented-frame object, the real-asset option and the N > 1 code path (one rank through librtr_mgpu.so and real RCCL)."""
+presented-frame object, the real-asset option and the N > 1 code path (one rank through librtr_mgpu.so and real RCCL).  A plain run
+measures the headline only; what else it can measure or check runs with --full."""
 import json
 import os
 import subprocess
@@ -24,7 +25,7 @@ def _bench(args, env=None, timeout=600):
 
 
 def test_bench_line_keeps_the_contract(scene_cache):
-    d = _bench(["--steps", "12", "--warmup", "2", "--width", "640", "--height", "360", "--present-frames", "2", "--verify"],
+    d = _bench(["--steps", "12", "--warmup", "2", "--width", "640", "--height", "360", "--present-frames", "2", "--verify", "--full"],
                env={"RTR_SCENE_CACHE": str(scene_cache)})
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config",
               "roofline", "cpu_baseline", "presented_frame"):
@@ -60,15 +61,44 @@ def test_bench_line_keeps_the_contract(scene_cache):
     assert p["spp"] == 4 and p["images"] == 5 and p["denoise_iterations"] == 4 and p["ms_per_frame"] > 0
 
 
+def test_plain_bench_line_and_its_dumped_outputs(scene_cache, gpu_ctx, oracle, tmp_path):
+    """Without --full the line carries the headline and none of the extra measurements; --dump-outputs writes the framebuffer of the
+    last timed step, which is the frame the CPU oracle renders for that step's camera and seed."""
+    import numpy as np
+    import bench
+    from realtimeraytracer_amd import _abi as A
+    from realtimeraytracer_amd import api
+    W, H, steps, warmup = 320, 184, 6, 2
+    d = _bench(["--steps", str(steps), "--warmup", str(warmup), "--width", str(W), "--height", str(H), "--dump-outputs", str(tmp_path)],
+               env={"RTR_SCENE_CACHE": str(scene_cache)})
+    assert d["full"] is False and d["steps"] == steps and d["warmup"] == warmup and d["ms_per_step"] > 0 and d["value"] > 0
+    assert d["unit"] == "Mrays/s" and d["higher_is_better"] is True and d["dtype"] == "f32" and d["timed_launches"] == [steps]
+    assert abs(d["ms_per_step"] * d["value"] * 1e3 / d["config"]["rays_per_frame"] - 1.0) < 0.02
+    for k in ("roofline", "roofline_secondary", "frame_hbm", "cpu_baseline", "presented_frame", "one_frame_at_a_time"):
+        assert d[k] is None, k
+    assert sorted(os.listdir(tmp_path)) == ["framebuffer_rgba8.npy"]
+    got = np.load(tmp_path / "framebuffer_rgba8.npy")
+    assert got.shape == (H, W, 4) and got.dtype == np.float32
+    setup = scenes.sponza_class(W, H)
+    cams = bench.CameraSource(setup, "path")
+    last = warmup + steps - 1
+    scene = api.Scene(gpu_ctx, setup.desc)
+    p = api.make_params(W, H, spp=1, shadow_rays=3, images=A.IMAGES_FRAMEBUFFER)
+    ref = oracle.render(setup.desc, cams.camera(last), cams.info(last), p, bvh=scene.export_bvh(), threads=8)
+    scene.close()
+    want = ref.images[A.IMAGE_SHADOWED].view(np.uint8).reshape(H, W, 4).astype(np.float32)
+    assert np.array_equal(got, want), int((got != want).any(axis=2).sum())
+
+
 def test_bench_renders_a_real_asset(scene_cache):
     obj, _ = scenes.write_cornell(scene_cache)
-    d = _bench(["--obj", obj, "--obj-view", "0.0,0.0,-1.9", "--steps", "6", "--warmup", "2", "--width", "320", "--height", "184", "--no-cpu-baseline", "--isolated-frames", "2"])
+    d = _bench(["--obj", obj, "--obj-view", "0.0,0.0,-1.9", "--steps", "6", "--warmup", "2", "--width", "320", "--height", "184", "--no-cpu-baseline", "--isolated-frames", "2", "--full"])
     assert d["data"].startswith("file ") and d["config"]["workload"].startswith("obj:") and d["value"] > 0
     assert d["config"]["primary_rays_per_frame"] == 320 * 184 and d["config"]["rays_per_frame"] > 320 * 184       # something was hit and lit
 
 
 def test_bench_multi_rank_path_with_one_rank_through_rccl(scene_cache):
-    d = _bench(["--steps", "10", "--warmup", "2", "--width", "640", "--height", "360", "--isolated-frames", "2"],
+    d = _bench(["--steps", "10", "--warmup", "2", "--width", "640", "--height", "360", "--isolated-frames", "2", "--full"],
                env={"RTR_BENCH_FORCE_DIST": "1", "RTR_SCENE_CACHE": str(scene_cache), "MASTER_PORT": "29577"})
     assert d["verify"]["assembled_vs_unsharded_pixels_differing"] == 0 and "librtr_mgpu.so" in d["verify"]["gather"]
     assert d["cpu_baseline"] is None and d["presented_frame"] is None and d["value"] > 0
@@ -80,7 +110,7 @@ def test_bench_multi_rank_path_with_one_rank_through_rccl(scene_cache):
 def test_bench_in_process_multi_gpu_path_with_one_rank(scene_cache):
     """`python bench.py --gpus N` started plainly drives the N devices from one process through rtr_mgpu_create; here that code path
     with N = 1 (RTR_BENCH_FORCE_INPROC) and the shard sent to itself through RCCL."""
-    d = _bench(["--steps", "10", "--warmup", "2", "--width", "640", "--height", "360"],
+    d = _bench(["--steps", "10", "--warmup", "2", "--width", "640", "--height", "360", "--full"],
                env={"RTR_BENCH_FORCE_INPROC": "1", "RTR_MGPU_SELF_EXCHANGE": "1", "RTR_SCENE_CACHE": str(scene_cache)})
     assert d["verify"]["assembled_vs_unsharded_pixels_differing"] == 0 and d["n_gpus"] == 1 and d["value"] > 0
     assert d["rccl"]["nranks"] == 1 and d["rccl"]["nlocal"] == 1 and "rtr_mgpu_create " in d["rccl"]["launch"] + " "
@@ -107,7 +137,7 @@ def test_bench_gpus_4_started_plainly_with_the_ranks_sharing_one_gpu(scene_cache
     assembled frame of the last step equals the unsharded one."""
     fake = os.path.join(ROOT, "tests", "fake_rccl", "libfake_rccl.so")
     assert os.path.exists(fake), "run __graft_entry__.build()"
-    d = _bench(["--gpus", "4", "--steps", "24", "--warmup", "8", "--width", "640", "--height", "360"],
+    d = _bench(["--gpus", "4", "--steps", "24", "--warmup", "8", "--width", "640", "--height", "360", "--full"],
                env={"RTR_SCENE_CACHE": str(scene_cache), "LD_PRELOAD": fake, "RTR_MGPU_TEST_SHARED_DEVICE": "1"})
     assert d["n_gpus"] == 4 and d["scaling"] == "strong" and d["value"] > 100 and d["rehearsal"] and "share ONE GPU" in d["rehearsal"]
     r = d["rccl"]
@@ -134,7 +164,7 @@ def test_bench_gpus_n_start_is_verified_and_a_wrong_exchange_stops_the_run(scene
     fake = os.path.join(ROOT, "tests", "fake_rccl", "libfake_rccl.so")
     base = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", RTR_SCENE_CACHE=str(scene_cache), LD_PRELOAD=fake, RTR_MGPU_TEST_SHARED_DEVICE="1")
     base.pop("WORLD_SIZE", None); base.pop("RTR_MGPU_GROUP_PER_SLOT", None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "3", "--steps", "6", "--warmup", "2", "--width", "320", "--height", "200"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "3", "--steps", "6", "--warmup", "2", "--width", "320", "--height", "200", "--full"]
 
     def line(r):
         return json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

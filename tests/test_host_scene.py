@@ -143,15 +143,12 @@ def test_missing_textures_are_refused_loudly(scene_cache):
 
 
 def test_reference_ltc_tables_known_answers_and_analytic_image(oracle, scene_cache):
-    """Where the reference tree exists: its real LTC tables (external/LUT/ltc_matrix.h, dumped by oracle/_ref/ltc_dump —
-    the data itself is not committed) satisfy SURVEY Appendix B and drive the oracle's analytic (LTC) image to a finite,
-    non-trivial result with BVH == brute force.  Elsewhere the synthetic stand-ins of scenes.synthetic_ltc() are used."""
+    """The reference's real LTC tables (external/LUT/ltc_matrix.h, dumped by oracle/_ref/ltc_dump into the fixture
+    tests/golden/ref_ltc_tables.bin) satisfy SURVEY Appendix B and drive the oracle's analytic (LTC) image to a finite,
+    non-trivial result with BVH == brute force."""
     import os
-    import subprocess
-    tool = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", "ltc_dump")
-    if not os.path.exists(tool):
-        pytest.skip("reference tree absent: oracle/_ref/ltc_dump not built")
-    a = np.frombuffer(subprocess.run([tool], check=True, capture_output=True).stdout, np.float32)
+    gold = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_ltc_tables.bin")
+    a = np.fromfile(gold, dtype="<f4").astype(np.float32)
     assert a.size == 2 * 16384
     l1, l2 = a[:16384].reshape(64, 64, 4).copy(), a[16384:].reshape(64, 64, 4).copy()
     assert l1.reshape(-1)[3] == np.float32(2e-05) and l2.reshape(-1)[:4].tolist() == [1.0, 0.0, 0.0, 0.0]

@@ -320,12 +320,23 @@ int  rtr_frame_wait(rtr_frame* frame);
  * reading the pair the ping-pong flag points at.  The frame must own images 0-7 and hold a full (unsharded) frame
  * rendered with RTR_IMAGES_RAYGEN5.  Synchronous. */
 int  rtr_denoise_combine(rtr_frame* frame, int iterations);
+/* The same checks, launches and ping-pong, ENQUEUED on the stream of the frame's context and not waited for: it comes behind a
+ * render of the frame on that stream and behind an rtr_render_batch_async launch that rendered it on another frame's stream, and a
+ * later batch comes behind it — all without a host join.  rtr_frame_wait joins.  With two frames on two contexts, the post passes of
+ * frame n run while frame n+1 is rendered (the frame the reference presents, two in flight). */
+int  rtr_denoise_combine_async(rtr_frame* frame, int iterations);
 
 /* Rank-0 step after the RCCL gather: `gathered` holds shardCount blocks of (localRows x width)
  * RGBA8 pixels in rank order; writes the de-interleaved (height x width) image to `dst`.
  * Both are device pointers; ENQUEUED on the ctx stream (asynchronous; synchronise the stream to read). */
 int  rtr_deinterleave_bands(rtr_ctx* ctx, const void* gathered, void* dst, uint32_t width, uint32_t height,
                             uint32_t bandRows, uint32_t shardCount);
+/* The same for several images in ONE launch (librtr_mgpu.so's present mode): `gathered` holds shardCount blocks, each of numImages
+ * planes of (localRows x width) RGBA8 pixels — [shard][image][localRow][x], localRows = rtr_shard_rows(height, bandRows, shardCount) —
+ * and image i is de-interleaved into dst[i] (height x width).  Same band -> shard map as rtr_deinterleave_bands.  ENQUEUED on the ctx
+ * stream.  RTR_ERR_INVALID_ARGUMENT for 0 or more than 8 images, a null pointer, or a bandRows that is not a multiple of 8 (0 -> 8). */
+int  rtr_deinterleave_images(rtr_ctx* ctx, const void* gathered, uint32_t numImages, void* const* dst, uint32_t width,
+                             uint32_t height, uint32_t bandRows, uint32_t shardCount);
 
 /* ---- errors --------------------------------------------------------------------------- */
 const char* rtr_last_error(void);

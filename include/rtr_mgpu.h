@@ -56,6 +56,16 @@ int  rtr_mgpu_scene_create(rtr_mgpu* m, const rtr_scene_desc* desc);
 /* the launch's transfers as one RCCL group PER SLOT instead of one group for the launch (the fallback; also set for every launch of a
  * handle made while RTR_MGPU_GROUP_PER_SLOT=1 is in the environment) */
 #define RTR_MGPU_GROUP_PER_SLOT 2
+/* PRESENT mode: the frame the reference presents (five ray-gen images, a-trous rounds, combine; src/app/application.cppm:391-445)
+ * instead of the raw shadowed image.  Needs params->images == RTR_IMAGES_RAYGEN5 (RTR_ERR_INVALID_ARGUMENT otherwise; HDR / accumulate:
+ * RTR_ERR_UNSUPPORTED; with RTR_MGPU_NO_EXCHANGE: RTR_ERR_INVALID_ARGUMENT) and a bandRows that is a multiple of 8.  The denoise taps
+ * reach 20 rows, across the bands of other ranks, so no rank can denoise its own shard: every rank renders its five images into ONE
+ * shard buffer of five planes (ANALYTIC, SHADOWED, UNSHADOWED, NORMAL, POSITION: ascending binding order), which travels as one send
+ * of 5 x shardBytes; rank 0, on its communication stream, de-interleaves the five planes into a whole frame with all 8 images
+ * (rtr_deinterleave_images), runs rtr_denoise_combine_async on it (rtr_mgpu_set_denoise_iterations rounds), then records the slot's
+ * exchange event — so the post passes of frame n run under the ray-gen of frame n+1.  rtr_mgpu_frame_download of a present slot is
+ * RTR_IMAGE_FINAL; rtr_mgpu_image_download gives any of images 0-7.  A slot that changes mode is re-created, as on a new extent. */
+#define RTR_MGPU_PRESENT 4
 int  rtr_mgpu_render_async(rtr_mgpu* m, int slot, const RtrCameraData* camera, const RtrSceneInfo* sceneInfo, const rtr_render_params* params, int flags);
 /* n frames into n distinct slots with ONE launch of the pipeline per rank (rtr_render_batch_async: a 1/N shard of a 1-spp frame is
  * too little work per launch — one rank of eight renders a frame in 0.39 ms one launch per frame and in 0.35 ms four per launch) and
@@ -67,10 +77,17 @@ int  rtr_mgpu_wait(rtr_mgpu* m, int slot);
 /* rtr_mgpu_render_async + rtr_mgpu_wait on slot 0. */
 int  rtr_mgpu_render(rtr_mgpu* m, const RtrCameraData* camera, const RtrSceneInfo* sceneInfo, const rtr_render_params* params);
 
-/* The assembled frame (height x width RGBA8, bytes B,G,R,255) of a waited-for slot; only where rank 0 is local
- * (RTR_ERR_INVALID_ARGUMENT elsewhere). */
+/* The assembled frame (height x width RGBA8, bytes B,G,R,255) of a waited-for slot — the shadowed image, or RTR_IMAGE_FINAL of a
+ * present slot; only where rank 0 is local (RTR_ERR_INVALID_ARGUMENT elsewhere). */
 int  rtr_mgpu_frame_download(rtr_mgpu* m, int slot, void* dst, size_t bytes);
 int  rtr_mgpu_frame_device_ptr(rtr_mgpu* m, int slot, void** devicePtr, size_t* bytes);
+/* Image `which` (0-7, height x width RGBA8) of a waited-for PRESENT slot, on rank 0 only: the state rtr_denoise_combine leaves the
+ * whole frame in (the sampled and denoised pairs after the ping-pong, FINAL, and the analytic / normal / position images as rendered).
+ * RTR_ERR_INVALID_ARGUMENT for a slot that was not rendered with RTR_MGPU_PRESENT. */
+int  rtr_mgpu_image_download(rtr_mgpu* m, int slot, int which, void* dst, size_t bytes);
+int  rtr_mgpu_image_device_ptr(rtr_mgpu* m, int slot, int which, void** devicePtr, size_t* bytes);
+/* a-trous rounds of the present passes of later launches: 0-64, default the reference's NUM_DENOISING_ITERATIONS = 4 */
+int  rtr_mgpu_set_denoise_iterations(rtr_mgpu* m, int iterations);
 /* Per-kernel times of a local rank's shard render of a waited-for slot (rtr_frame_get_stats of its frame). */
 int  rtr_mgpu_frame_stats(rtr_mgpu* m, int slot, int localRank, rtr_frame_stats* out);
 /* This rank's own shard (rtr_shard_rows x width) of a waited-for slot: localRank indexes the ranks of this process. */
@@ -109,6 +126,9 @@ int  rtr_mgpu_get_info(const rtr_mgpu* m, rtr_mgpu_info* out);
  *            lands at (= shardBytes * peer);  SEND: byte offset in the local shard (0)
  *   bytes    RENDER / RECV / SEND: shardBytes = rtr_shard_rows(height, bandRows, nranks) * width * 4;
  *            DEINTERLEAVE: width * height * 4 (the assembled frame)
+ *            present plans (RTR_MGPU_PRESENT): a rank's shard is five planes, so RENDER / RECV / SEND bytes are 5 x shardBytes and a
+ *            RECV lands at peer x 5 x shardBytes; DEINTERLEAVE bytes are 5 x width x height x 4 (five images of the whole frame); and
+ *            rank 0 has one PRESENT per slot (bytes width x height x 4: the presented image) right after that slot's DEINTERLEAVE
  *   buffer   which buffer offset / bytes refer to
  *   event    WAIT / RECORD: which of the slot's two events */
 typedef enum rtr_mgpu_op_kind {
@@ -119,7 +139,8 @@ typedef enum rtr_mgpu_op_kind {
     RTR_MGPU_OP_RECV = 5,          /* ncclRecv(gather + offset, bytes, from peer) */
     RTR_MGPU_OP_SEND = 6,          /* ncclSend(local + offset, bytes, to peer) */
     RTR_MGPU_OP_GROUP_END = 7,     /* ncclGroupEnd */
-    RTR_MGPU_OP_DEINTERLEAVE = 8   /* rank 0: gather buffer (nranks shards) -> assembled frame (k_deinterleave) */
+    RTR_MGPU_OP_DEINTERLEAVE = 8,  /* rank 0: gather buffer (nranks shards) -> assembled frame (k_deinterleave; k_deinterleave_images in present plans) */
+    RTR_MGPU_OP_PRESENT = 9        /* rank 0, present plans: rtr_denoise_combine_async of the assembled frame, before the slot's COMM_DONE record */
 } rtr_mgpu_op_kind;
 typedef enum rtr_mgpu_stream { RTR_MGPU_STREAM_RENDER = 0, RTR_MGPU_STREAM_COMM = 1 } rtr_mgpu_stream;
 typedef enum rtr_mgpu_buffer { RTR_MGPU_BUF_NONE = 0, RTR_MGPU_BUF_LOCAL = 1, RTR_MGPU_BUF_GATHER = 2, RTR_MGPU_BUF_SELF_SRC = 3, RTR_MGPU_BUF_FULL = 4 } rtr_mgpu_buffer;
@@ -134,24 +155,26 @@ typedef struct rtr_mgpu_op {
     uint64_t offset;
     uint64_t bytes;
 } rtr_mgpu_op;
-#define RTR_MGPU_PLAN_MAX_OPS 32     /* 8 + (nranks - 1) operations on rank 0; nranks <= RTR_MGPU_MAX_RANKS */
+#define RTR_MGPU_PLAN_MAX_OPS 32     /* 8 + (nranks - 1) operations on rank 0 (one more in a present plan); nranks <= RTR_MGPU_MAX_RANKS */
 #define RTR_MGPU_MAX_RANKS 16
-/* Fills ops[0 .. *numOps) for `rank` of `nranks`.  flags: RTR_MGPU_NO_EXCHANGE (render only); selfExchange != 0 with nranks == 1:
+/* Fills ops[0 .. *numOps) for `rank` of `nranks`.  flags: RTR_MGPU_NO_EXCHANGE (render only), RTR_MGPU_PRESENT (present plan; refused
+ * together with RTR_MGPU_NO_EXCHANGE), RTR_MGPU_GROUP_PER_SLOT; selfExchange != 0 with nranks == 1:
  * the one rank sends its shard to itself through the communicator (test hook).  RTR_ERR_INVALID_ARGUMENT on a bad rank / extent or
  * when maxOps is too small. */
 int  rtr_mgpu_plan(int rank, int nranks, uint32_t width, uint32_t height, uint32_t bandRows, int flags, int selfExchange,
                    rtr_mgpu_op* ops, int maxOps, int* numOps);
 /* The plan of a launch of `nslots` frames (rtr_mgpu_render_batch_async; nslots = 1 is rtr_mgpu_plan): the WAITs of every slot, ONE
  * RENDER (slot 0 leads), one render -> communication edge, ONE group holding every slot's transfers in slot order — on rank 0 the
- * (nranks - 1) receives of slot 0, then of slot 1 ...; on the others one send per slot — then a DEINTERLEAVE and a RECORD per slot.
- * At most RTR_MGPU_BATCH_PLAN_MAX_OPS operations. */
+ * (nranks - 1) receives of slot 0, then of slot 1 ...; on the others one send per slot — then a DEINTERLEAVE (+ a PRESENT in a present
+ * plan) per slot and a RECORD per slot.  At most RTR_MGPU_BATCH_PLAN_MAX_OPS operations (a present plan included). */
 #define RTR_MGPU_BATCH_PLAN_MAX_OPS (6 + RTR_MAX_BATCH * (5 + RTR_MGPU_MAX_RANKS))
 int  rtr_mgpu_plan_batch(int rank, int nranks, uint32_t width, uint32_t height, uint32_t bandRows, int flags, int selfExchange, int nslots,
                          rtr_mgpu_op* ops, int maxOps, int* numOps);
 
 /* Watchdog of rtr_mgpu_wait: a slot whose exchange has not finished after this many milliseconds is given up — every local
  * communicator is aborted (ncclCommAbort releases peers blocked in a send / recv that will never be matched), the handle refuses
- * further renders and rtr_mgpu_wait returns RTR_ERR_HIP with the stage it was waiting in.  Default 120000, from the environment
+ * further renders and rtr_mgpu_wait returns RTR_ERR_HIP with the stage it was waiting in (rtr_deinterleave_images and
+ * rtr_denoise_combine_async among them in present mode).  Default 120000, from the environment
  * variable RTR_MGPU_TIMEOUT_MS at creation; 0 = wait for ever. */
 int  rtr_mgpu_set_timeout_ms(rtr_mgpu* m, uint32_t ms);
 

@@ -162,6 +162,8 @@ RTR_SYMBOLS = {
     "rtr_frame_wait": (C.c_int, [VP]),
     "rtr_deinterleave_bands": (C.c_int, [VP, VP, VP, u32, u32, u32, u32]),
     "rtr_denoise_combine": (C.c_int, [VP, C.c_int]),
+    "rtr_denoise_combine_async": (C.c_int, [VP, C.c_int]),
+    "rtr_deinterleave_images": (C.c_int, [VP, VP, u32, P(VP), u32, u32, u32, u32]),
     "rtr_last_error": (C.c_char_p, []),
     "rtr_status_string": (C.c_char_p, [C.c_int]),
     "rtr_abi_version": (C.c_int, []),
@@ -223,6 +225,7 @@ class rtr_mgpu_op(C.Structure):
 
 
 MGPU_OP_WAIT, MGPU_OP_RENDER, MGPU_OP_RECORD, MGPU_OP_GROUP_START, MGPU_OP_RECV, MGPU_OP_SEND, MGPU_OP_GROUP_END, MGPU_OP_DEINTERLEAVE = range(1, 9)
+MGPU_OP_PRESENT = 9
 MGPU_STREAM_RENDER, MGPU_STREAM_COMM = 0, 1
 MGPU_BUF_NONE, MGPU_BUF_LOCAL, MGPU_BUF_GATHER, MGPU_BUF_SELF_SRC, MGPU_BUF_FULL = range(5)
 MGPU_EV_NONE, MGPU_EV_RENDER_DONE, MGPU_EV_COMM_DONE = range(3)
@@ -237,6 +240,8 @@ MGPU_ID_BYTES = 128
 MGPU_MAX_SLOTS = 64
 MGPU_NO_EXCHANGE = 1
 MGPU_GROUP_PER_SLOT = 2
+MGPU_PRESENT = 4
+MGPU_PRESENT_PLANES = (IMAGE_ANALYTIC, IMAGE_SHADOWED, IMAGE_UNSHADOWED, IMAGE_NORMAL, IMAGE_POSITION)     # a present shard's planes, in order
 
 # every entry point include/rtr_mgpu.h declares
 MGPU_SYMBOLS = {
@@ -258,6 +263,9 @@ MGPU_SYMBOLS = {
     "rtr_mgpu_plan_batch": (C.c_int, [C.c_int, C.c_int, u32, u32, u32, C.c_int, C.c_int, C.c_int, P(rtr_mgpu_op), C.c_int, P(C.c_int)]),
     "rtr_mgpu_set_timeout_ms": (C.c_int, [VP, u32]),
     "rtr_mgpu_last_error": (C.c_char_p, []),
+    "rtr_mgpu_image_download": (C.c_int, [VP, C.c_int, C.c_int, VP, C.c_size_t]),
+    "rtr_mgpu_image_device_ptr": (C.c_int, [VP, C.c_int, C.c_int, P(VP), P(C.c_size_t)]),
+    "rtr_mgpu_set_denoise_iterations": (C.c_int, [VP, C.c_int]),
 }
 
 

@@ -146,6 +146,11 @@ class Frame:
         """reference frame loop tail (application.cppm:391-445): 4 x a-trous on both sampled images, then combine."""
         _check(self.lib.rtr_denoise_combine(self.h, iterations), "rtr_denoise_combine")
 
+    def denoise_combine_async(self, iterations=4):
+        """the same passes enqueued on the frame's context stream (behind a render or a batch launch that wrote the frame), not
+        waited for: wait() joins, and the next frame's render on another context runs under them"""
+        _check(self.lib.rtr_denoise_combine_async(self.h, iterations), "rtr_denoise_combine_async")
+
     def wait(self):
         _check(self.lib.rtr_frame_wait(self.h), "rtr_frame_wait")
 
@@ -209,6 +214,13 @@ def render_batch_limit(scene, params, num_area_lights):
 def deinterleave_bands(ctx, gathered_ptr, dst_ptr, width, height, band_rows, shard_count):
     _check(ctx.lib.rtr_deinterleave_bands(ctx.h, A.VP(gathered_ptr), A.VP(dst_ptr), width, height, band_rows, shard_count),
            "rtr_deinterleave_bands")
+
+
+def deinterleave_images(ctx, gathered_ptr, dst_ptrs, width, height, band_rows, shard_count):
+    """rtr_deinterleave_images: [shard][image][local row][x] gather buffer -> len(dst_ptrs) whole images, one launch, on the ctx stream"""
+    n = len(dst_ptrs)
+    arr = (A.VP * max(n, 1))(*[A.VP(p) for p in dst_ptrs])
+    _check(ctx.lib.rtr_deinterleave_images(ctx.h, A.VP(gathered_ptr), n, arr, width, height, band_rows, shard_count), "rtr_deinterleave_images")
 
 
 def host_build_bvh(desc):

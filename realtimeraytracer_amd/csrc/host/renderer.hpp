@@ -58,6 +58,9 @@ public:
     rtr_frame_stats stats() const { rtr_frame_stats s; check(rtr_frame_get_stats(h_, &s), "rtr_frame_get_stats"); return s; }
     // the passes after the ray-gen dispatch in the reference's frame loop (application.cppm:391-445): a-trous rounds, then combine
     void denoise_combine(int iterations) { check(rtr_denoise_combine(h_, iterations), "rtr_denoise_combine"); }
+    // the same passes enqueued on the frame's context stream, not waited for (wait() joins): the next frame renders under them
+    void denoise_combine_async(int iterations) { check(rtr_denoise_combine_async(h_, iterations), "rtr_denoise_combine_async"); }
+    void wait() { check(rtr_frame_wait(h_), "rtr_frame_wait"); }
     uint32_t width() const { return width_; }
     uint32_t rows() const { return rows_; }
 private:

@@ -16,4 +16,11 @@ hipError_t launch_denoise_pair(const uint32_t* inA, uint32_t* outA, const uint32
 hipError_t launch_combine(const uint32_t* analytic, const uint32_t* shadowed, const uint32_t* unshadowed, uint32_t* finalImage,
                           uint32_t width, uint32_t height, hipStream_t stream);
 
+/* Rank-0 step of the multi-GPU present mode: `gathered` holds shardCount blocks, each of numImages planes of (localRows x width)
+ * RGBA8 pixels ([shard][image][localRow][x]); writes numImages (<= kMaxDeinterleaveImages) de-interleaved (height x width) images
+ * to dst[0 .. numImages), with the band -> shard map of k_deinterleave (band b -> shard b % shardCount). */
+constexpr uint32_t kMaxDeinterleaveImages = 8;
+hipError_t launch_deinterleave_images(const uint32_t* gathered, uint32_t* const* dst, uint32_t numImages, uint32_t width, uint32_t height,
+                                      uint32_t bandRows, uint32_t shardCount, uint32_t localRows, hipStream_t stream);
+
 }  // namespace rtrdev

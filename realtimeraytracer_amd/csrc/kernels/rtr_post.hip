@@ -149,6 +149,51 @@ __global__ __launch_bounds__(256) void k_combine(const uint32_t* __restrict__ an
     }
 }
 
+/* ---- de-interleave of several images after the multi-GPU gather ----------------------------------------------------------------
+ * Pure data movement (2 x images x width x height x 4 bytes): one workgroup per output row of one image, the row copied whole from its
+ * shard's plane.  16-byte loads and stores when every row starts on a 16-byte boundary (width a multiple of 4 and 16-byte aligned
+ * pointers), 4-byte ones otherwise.  Padding rows of a shard (past the frame's last band) are never read. */
+struct DeinterleaveArgs {
+    const uint32_t* gathered;
+    uint32_t* dst[kMaxDeinterleaveImages];
+    uint32_t width, height, bandRows, shardCount, localRows, numImages;
+};
+
+template <bool VEC16>
+__global__ __launch_bounds__(256) void k_deinterleave_images(const DeinterleaveArgs a) {
+    const uint32_t img = blockIdx.x / a.height, y = blockIdx.x - img * a.height;         /* image-major: row y of image img */
+    const uint32_t band = y / a.bandRows, r = y - band * a.bandRows;
+    const uint32_t shard = band % a.shardCount, lb = band / a.shardCount;
+    const size_t srcRow = ((size_t)shard * a.numImages + img) * a.localRows + (size_t)lb * a.bandRows + r;
+    const uint32_t* src = a.gathered + srcRow * a.width;
+    uint32_t* dst = a.dst[img] + (size_t)y * a.width;
+    if (VEC16) {
+        const uint4* s4 = reinterpret_cast<const uint4*>(src);
+        uint4* d4 = reinterpret_cast<uint4*>(dst);
+        for (uint32_t i = threadIdx.x; i < (a.width >> 2); i += 256u) d4[i] = s4[i];
+    } else {
+        for (uint32_t i = threadIdx.x; i < a.width; i += 256u) dst[i] = src[i];
+    }
+}
+
+hipError_t launch_deinterleave_images(const uint32_t* gathered, uint32_t* const* dst, uint32_t numImages, uint32_t width, uint32_t height,
+                                      uint32_t bandRows, uint32_t shardCount, uint32_t localRows, hipStream_t stream) {
+    if (numImages == 0 || numImages > kMaxDeinterleaveImages || width == 0 || height == 0 || bandRows == 0 || shardCount == 0) return hipErrorInvalidValue;
+    if ((uint64_t)numImages * height > 0x7fffffffull) return hipErrorInvalidValue;
+    DeinterleaveArgs a;
+    a.gathered = gathered;
+    bool aligned = (width & 3u) == 0u && ((uintptr_t)gathered & 15u) == 0u;
+    for (uint32_t i = 0; i < kMaxDeinterleaveImages; ++i) {
+        a.dst[i] = i < numImages ? dst[i] : nullptr;
+        if (i < numImages) aligned = aligned && ((uintptr_t)dst[i] & 15u) == 0u;
+    }
+    a.width = width; a.height = height; a.bandRows = bandRows; a.shardCount = shardCount; a.localRows = localRows; a.numImages = numImages;
+    const dim3 grid(numImages * height);
+    if (aligned) hipLaunchKernelGGL((k_deinterleave_images<true>), grid, dim3(256), 0, stream, a);
+    else hipLaunchKernelGGL((k_deinterleave_images<false>), grid, dim3(256), 0, stream, a);
+    return hipGetLastError();
+}
+
 hipError_t launch_denoise_pair(const uint32_t* inA, uint32_t* outA, const uint32_t* inB, uint32_t* outB, const uint32_t* normal,
                                const uint32_t* position, uint32_t width, uint32_t height, int step_width, float c_phi, float n_phi,
                                float p_phi, hipStream_t stream) {

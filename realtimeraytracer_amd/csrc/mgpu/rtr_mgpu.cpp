@@ -67,12 +67,18 @@ private:
     std::thread th_;
 };
 
+/* present mode (RTR_MGPU_PRESENT): the five ray-gen images of a shard as five planes of ONE buffer, in ascending binding order */
+const int kPresentPlanes[5] = {RTR_IMAGE_ANALYTIC, RTR_IMAGE_SHADOWED, RTR_IMAGE_UNSHADOWED, RTR_IMAGE_NORMAL, RTR_IMAGE_POSITION};
+constexpr uint32_t kPresentPlaneCount = 5;
+
 struct Slot {
     rtr_frame* frame = nullptr;
-    uint32_t* gathered = nullptr;     /* rank 0: nranks x rows x width */
-    uint32_t* full = nullptr;         /* rank 0: height x width */
+    uint32_t* gathered = nullptr;     /* rank 0: nranks x planes x rows x width (planes = 5 in present mode, else 1) */
+    uint32_t* full = nullptr;         /* rank 0, framebuffer mode: height x width */
+    rtr_frame* present = nullptr;     /* rank 0, present mode: the whole frame with all 8 images, on the communication context */
+    uint32_t* planes = nullptr;       /* ranks > 0, present mode: this rank's five-plane shard */
     uint32_t* selfSrc = nullptr;      /* one-rank self-exchange test hook: the shard is rendered here and sent to `gathered` */
-    void* local = nullptr;            /* this rank's shard (device pointer of the frame's image) */
+    void* local = nullptr;            /* this rank's shard: the frame's image, or the first of its five planes in present mode */
     hipEvent_t evRender = nullptr, evComm = nullptr;
     uint32_t width = 0, height = 0, rows = 0, bandRows = 0, images = 0;
     bool commPending = false;         /* evComm has been recorded at least once */
@@ -86,7 +92,7 @@ struct Rank {
      * cannot fill the GPU, so frames in flight on separate streams are where most of the strong scaling comes from */
     rtr_ctx* ctx[RTR_MGPU_MAX_SLOTS] = {};
     hipStream_t renderStream[RTR_MGPU_MAX_SLOTS] = {};
-    rtr_ctx* commCtx = nullptr;       /* one more context whose stream is the communication stream (RCCL ops, k_deinterleave) */
+    rtr_ctx* commCtx = nullptr;       /* one more context whose stream is the communication stream (RCCL ops, k_deinterleave, present passes) */
     hipStream_t commStream = nullptr;
     rtr_scene* scene = nullptr;
     ncclComm_t comm = nullptr;        /* written when the rank is made and in destroy_rank (after its worker has joined), read by the worker in between */
@@ -112,6 +118,7 @@ struct rtr_mgpu {
     std::atomic<bool> aborted{false};               /* the communicators were aborted: the handle only waits for / frees things now; workers issue no further RCCL call */
     uint32_t timeoutMs = 120000;
     int planFlags = 0;                /* OR-ed into every launch's flags (RTR_MGPU_GROUP_PER_SLOT=1 in the environment at creation) */
+    int denoiseIterations = 4;        /* a-trous rounds of the present passes (rtr_mgpu_set_denoise_iterations; the reference's 4) */
     std::vector<std::unique_ptr<Rank>> ranks;       /* the local ones */
 };
 
@@ -120,31 +127,40 @@ namespace {
 void release_slot(Rank& r, Slot& s) {
     (void)hipSetDevice(r.device);
     if (s.frame) rtr_frame_destroy(s.frame);
+    if (s.present) rtr_frame_destroy(s.present);
     if (s.gathered) (void)hipFree(s.gathered);
     if (s.full) (void)hipFree(s.full);
+    if (s.planes) (void)hipFree(s.planes);
     if (s.selfSrc) (void)hipFree(s.selfSrc);
     if (s.evRender) (void)hipEventDestroy(s.evRender);
     if (s.evComm) (void)hipEventDestroy(s.evComm);
     /* device resources only: `pending` / `inFlight` belong to the caller's thread (this may run on the rank's worker) */
-    s.frame = nullptr; s.gathered = nullptr; s.full = nullptr; s.selfSrc = nullptr; s.local = nullptr;
+    s.frame = nullptr; s.present = nullptr; s.gathered = nullptr; s.full = nullptr; s.planes = nullptr; s.selfSrc = nullptr; s.local = nullptr;
     s.evRender = nullptr; s.evComm = nullptr; s.width = s.height = s.rows = s.bandRows = s.images = 0; s.commPending = false;
 }
 
-bool slot_matches(const rtr_mgpu* m, const Slot& s, const rtr_render_params& p) {
+/* what a slot renders in a launch with these flags: the five ray-gen images in present mode, else the framebuffer (+ HDR) */
+uint32_t slot_images(const rtr_render_params& p, int flags) {
+    return (flags & RTR_MGPU_PRESENT) ? RTR_IMAGES_RAYGEN5 : (RTR_IMAGES_FRAMEBUFFER | (p.images & RTR_IMG_BIT(RTR_IMAGE_HDR)));
+}
+
+bool slot_matches(const rtr_mgpu* m, const Slot& s, const rtr_render_params& p, int flags) {
     const uint32_t band = p.bandRows ? p.bandRows : 8u;
     const uint32_t rows = rtr_shard_rows(p.height, band, (uint32_t)m->nranks);
-    const uint32_t images = RTR_IMAGES_FRAMEBUFFER | (p.images & RTR_IMG_BIT(RTR_IMAGE_HDR));
+    const uint32_t images = slot_images(p, flags);
     return s.frame && s.width == p.width && s.height == p.height && s.rows == rows && s.bandRows == band && s.images == images;
 }
 
-/* (re)creates the slot's frame and, on rank 0, the gather / full-frame buffers for this extent.  Everything of a frame that can
+/* (re)creates the slot's frame and, on rank 0, the gather / full-frame buffers for this extent and mode (a slot that switches
+ * between the framebuffer and the present mode is re-created like one that changes its extent).  Everything of a frame that can
  * fail for lack of memory happens here, BEFORE any rank posts a send or a receive (rtr_mgpu_render_async joins this phase on all
  * local ranks first): a rank that fails later than that would leave its peers' receives unmatched. */
-int prepare_slot(rtr_mgpu* m, Rank& r, Slot& s, const rtr_render_params& p, std::string& err) {
-    if (slot_matches(m, s, p)) return RTR_OK;
+int prepare_slot(rtr_mgpu* m, Rank& r, Slot& s, const rtr_render_params& p, int flags, std::string& err) {
+    if (slot_matches(m, s, p, flags)) return RTR_OK;
     const uint32_t band = p.bandRows ? p.bandRows : 8u;
     const uint32_t rows = rtr_shard_rows(p.height, band, (uint32_t)m->nranks);
-    const uint32_t images = RTR_IMAGES_FRAMEBUFFER | (p.images & RTR_IMG_BIT(RTR_IMAGE_HDR));
+    const uint32_t images = slot_images(p, flags);
+    const bool present = images == RTR_IMAGES_RAYGEN5;
     r.stage = "prepare_slot";
     /* the slot's previous frame may still be running (its join only covered the host-side enqueue) */
     W_HIP(hipSetDevice(r.device));
@@ -152,26 +168,40 @@ int prepare_slot(rtr_mgpu* m, Rank& r, Slot& s, const rtr_render_params& p, std:
     W_HIP(hipStreamSynchronize(r.renderStream[sl]));
     W_HIP(hipStreamSynchronize(r.commStream));
     release_slot(r, s);
-    W_RTR(rtr_frame_create(r.ctx[sl], p.width, rows, images, &s.frame));
+    /* present mode: the frame's five images are bound to the planes of one shard buffer below (the frame owns a framebuffer only) */
+    W_RTR(rtr_frame_create(r.ctx[sl], p.width, rows, present ? RTR_IMAGES_FRAMEBUFFER : images, &s.frame));
     W_HIP(hipEventCreateWithFlags(&s.evRender, hipEventDisableTiming));
     W_HIP(hipEventCreateWithFlags(&s.evComm, hipEventDisableTiming));
     const size_t shardBytes = (size_t)rows * p.width * 4;
+    const size_t unit = shardBytes * (present ? kPresentPlaneCount : 1u);      /* what one rank contributes to the gather buffer */
+    char* base = nullptr;                                                        /* where this rank's shard is rendered */
     if (r.rank == 0) {
-        W_HIP(hipMalloc((void**)&s.gathered, shardBytes * (size_t)m->nranks));
-        W_HIP(hipMemsetAsync(s.gathered, 0, shardBytes * (size_t)m->nranks, r.commStream));
-        W_HIP(hipMalloc((void**)&s.full, (size_t)p.width * p.height * 4));
+        W_HIP(hipMalloc((void**)&s.gathered, unit * (size_t)m->nranks));
+        W_HIP(hipMemsetAsync(s.gathered, 0, unit * (size_t)m->nranks, r.commStream));
+        if (present) W_RTR(rtr_frame_create(r.commCtx, p.width, p.height, 0xffu, &s.present));
+        else W_HIP(hipMalloc((void**)&s.full, (size_t)p.width * p.height * 4));
         if (m->selfExchange && m->nranks == 1) {
-            W_HIP(hipMalloc((void**)&s.selfSrc, shardBytes));
-            W_HIP(hipMemsetAsync(s.selfSrc, 0, shardBytes, r.commStream));
-            W_RTR(rtr_frame_bind_external(s.frame, RTR_IMAGE_SHADOWED, s.selfSrc, shardBytes));
+            W_HIP(hipMalloc((void**)&s.selfSrc, unit));
+            W_HIP(hipMemsetAsync(s.selfSrc, 0, unit, r.commStream));
+            base = reinterpret_cast<char*>(s.selfSrc);
         } else {
-            /* rank 0 renders straight into its place in the gather buffer: no copy of its own shard */
-            W_RTR(rtr_frame_bind_external(s.frame, RTR_IMAGE_SHADOWED, s.gathered, shardBytes));
+            base = reinterpret_cast<char*>(s.gathered);          /* rank 0 renders straight into its place in the gather buffer: no copy of its own shard */
         }
         W_HIP(hipStreamSynchronize(r.commStream));
+    } else if (present) {
+        W_HIP(hipMalloc((void**)&s.planes, unit));
+        W_HIP(hipMemsetAsync(s.planes, 0, unit, r.commStream));
+        W_HIP(hipStreamSynchronize(r.commStream));
+        base = reinterpret_cast<char*>(s.planes);
     }
-    size_t bytes = 0;
-    W_RTR(rtr_frame_device_ptr(s.frame, RTR_IMAGE_SHADOWED, &s.local, &bytes));
+    if (present) {
+        for (uint32_t k = 0; k < kPresentPlaneCount; ++k) W_RTR(rtr_frame_bind_external(s.frame, kPresentPlanes[k], base + k * shardBytes, shardBytes));
+        s.local = base;
+    } else {
+        if (base) W_RTR(rtr_frame_bind_external(s.frame, RTR_IMAGE_SHADOWED, base, shardBytes));
+        size_t bytes = 0;
+        W_RTR(rtr_frame_device_ptr(s.frame, RTR_IMAGE_SHADOWED, &s.local, &bytes));
+    }
     s.width = p.width; s.height = p.height; s.rows = rows; s.bandRows = band; s.images = images;
     r.stage = "idle";
     return RTR_OK;
@@ -185,8 +215,12 @@ int prepare_slot(rtr_mgpu* m, Rank& r, Slot& s, const rtr_render_params& p, std:
 #define RTR_MGPU_TEST_WRONG_PLACE_ONE_GROUP 0x20000000
 int make_plan(int rank, int nranks, uint32_t width, uint32_t height, uint32_t bandRows, int flags, int selfExchange, int nslots, std::vector<rtr_mgpu_op>& ops) {
     if (nranks < 1 || nranks > RTR_MGPU_MAX_RANKS || rank < 0 || rank >= nranks || width == 0 || height == 0 || nslots < 1 || nslots > RTR_MAX_BATCH) return RTR_ERR_INVALID_ARGUMENT;
+    const bool present = (flags & RTR_MGPU_PRESENT) != 0;
+    if (present && (flags & RTR_MGPU_NO_EXCHANGE)) return RTR_ERR_INVALID_ARGUMENT;       /* the present passes need the whole frame */
     if (bandRows == 0) bandRows = 8;
-    const uint64_t shardBytes = (uint64_t)rtr_shard_rows(height, bandRows, (uint32_t)nranks) * width * 4u;
+    /* a rank's contribution: its shard of the framebuffer, or in present mode the five planes of its five ray-gen images */
+    const uint64_t shardBytes = (uint64_t)rtr_shard_rows(height, bandRows, (uint32_t)nranks) * width * 4u * (present ? kPresentPlaneCount : 1u);
+    const uint64_t frameBytes = (uint64_t)width * height * 4u;
     const bool self = selfExchange && nranks == 1;
     auto op = [&](int kind, int stream, int slot, int peer, int buffer, int event, uint64_t offset, uint64_t bytes) {
         rtr_mgpu_op o; memset(&o, 0, sizeof o);
@@ -230,7 +264,12 @@ int make_plan(int rank, int nranks, uint32_t width, uint32_t height, uint32_t ba
         }
         if (!perSlot) op(RTR_MGPU_OP_GROUP_END, RTR_MGPU_STREAM_COMM, 0, -1, RTR_MGPU_BUF_NONE, RTR_MGPU_EV_NONE, 0, 0);
     }
-    if (rank == 0) for (int j = 0; j < nslots; ++j) op(RTR_MGPU_OP_DEINTERLEAVE, RTR_MGPU_STREAM_COMM, j, -1, RTR_MGPU_BUF_FULL, RTR_MGPU_EV_NONE, 0, (uint64_t)width * height * 4u);     /* one rank: a plain copy */
+    if (rank == 0)
+        for (int j = 0; j < nslots; ++j) {
+            op(RTR_MGPU_OP_DEINTERLEAVE, RTR_MGPU_STREAM_COMM, j, -1, RTR_MGPU_BUF_FULL, RTR_MGPU_EV_NONE, 0, frameBytes * (present ? kPresentPlaneCount : 1u));     /* one rank: a plain copy */
+            /* the denoise + combine of the slot's whole frame, on the communication stream: it runs under the next launch's ray-gen */
+            if (present) op(RTR_MGPU_OP_PRESENT, RTR_MGPU_STREAM_COMM, j, -1, RTR_MGPU_BUF_FULL, RTR_MGPU_EV_NONE, 0, frameBytes);
+        }
     for (int j = 0; j < nslots; ++j) op(RTR_MGPU_OP_RECORD, RTR_MGPU_STREAM_COMM, j, -1, RTR_MGPU_BUF_NONE, RTR_MGPU_EV_COMM_DONE, 0, 0);
     return RTR_OK;
 }
@@ -242,6 +281,7 @@ struct BatchJob {                     /* what one call renders: n frames into n 
     RtrSceneInfo infos[RTR_MAX_BATCH];
     rtr_render_params p;
     int flags = 0;
+    int iterations = 4;               /* a-trous rounds of a present launch */
 };
 
 /* Carries the launch's plan out on this rank's streams; the slots are prepared (prepare_slot) before this runs.  A plain walk over
@@ -255,7 +295,7 @@ int enqueue(rtr_mgpu* m, Rank& r, const BatchJob& job, std::string& err) {
     W_HIP(hipSetDevice(r.device));
     if (!r.scene) { err = "no scene: call rtr_mgpu_scene_create first"; return RTR_ERR_INVALID_ARGUMENT; }
     rtr_render_params p = job.p;
-    for (int j = 0; j < job.n; ++j) if (!slot_matches(m, r.slots[job.slots[j]], p)) { err = "internal: slot not prepared for this extent"; return RTR_ERR_INVALID_ARGUMENT; }
+    for (int j = 0; j < job.n; ++j) if (!slot_matches(m, r.slots[job.slots[j]], p, job.flags)) { err = "internal: slot not prepared for this extent"; return RTR_ERR_INVALID_ARGUMENT; }
     std::vector<rtr_mgpu_op> ops;
     if (make_plan(r.rank, m->nranks, p.width, p.height, p.bandRows, job.flags, m->selfExchange ? 1 : 0, job.n, ops) != RTR_OK) { err = "internal: no plan for this rank / extent"; return RTR_ERR_INVALID_ARGUMENT; }
     hipStream_t renderStream = r.renderStream[job.slots[0]];
@@ -323,10 +363,28 @@ int enqueue(rtr_mgpu* m, Rank& r, const BatchJob& job, std::string& err) {
                 r.rcclNs += (unsigned long long)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
                 break;
             }
-            case RTR_MGPU_OP_DEINTERLEAVE:
-                r.stage = "rtr_deinterleave_bands";
-                c = rtr_deinterleave_bands(r.commCtx, s.gathered, s.full, s.width, s.height, s.bandRows, (uint32_t)m->nranks);
-                if (c != RTR_OK) err = std::string("rtr_deinterleave_bands: ") + rtr_last_error();
+            case RTR_MGPU_OP_DEINTERLEAVE: {
+                const uint64_t frameBytes = (uint64_t)s.width * s.height * 4u;
+                if (s.present && o.bytes == frameBytes * kPresentPlaneCount) {      /* present mode: five planes -> images 0, 1, 2, 6, 7 of the whole frame */
+                    r.stage = "rtr_deinterleave_images";
+                    void* dst[kPresentPlaneCount];
+                    for (uint32_t k = 0; k < kPresentPlaneCount && c == RTR_OK; ++k) c = rtr_frame_device_ptr(s.present, kPresentPlanes[k], &dst[k], nullptr);
+                    if (c == RTR_OK) c = rtr_deinterleave_images(r.commCtx, s.gathered, kPresentPlaneCount, dst, s.width, s.height, s.bandRows, (uint32_t)m->nranks);
+                    if (c != RTR_OK) err = std::string("rtr_deinterleave_images: ") + rtr_last_error();
+                } else if (s.full && o.bytes == frameBytes) {
+                    r.stage = "rtr_deinterleave_bands";
+                    c = rtr_deinterleave_bands(r.commCtx, s.gathered, s.full, s.width, s.height, s.bandRows, (uint32_t)m->nranks);
+                    if (c != RTR_OK) err = std::string("rtr_deinterleave_bands: ") + rtr_last_error();
+                } else {
+                    err = "internal: the plan's de-interleave does not match the slot's mode"; c = RTR_ERR_INVALID_ARGUMENT;
+                }
+                break;
+            }
+            case RTR_MGPU_OP_PRESENT:                /* rank 0: the reference's post passes over the assembled frame, not waited for */
+                r.stage = "rtr_denoise_combine_async";
+                if (!s.present) { err = "internal: a present operation on a slot without a present frame"; c = RTR_ERR_INVALID_ARGUMENT; break; }
+                c = rtr_denoise_combine_async(s.present, job.iterations);
+                if (c != RTR_OK) err = std::string("rtr_denoise_combine_async: ") + rtr_last_error();
                 break;
             default: err = "internal: unknown operation in the plan"; c = RTR_ERR_INVALID_ARGUMENT; break;
         }
@@ -608,8 +666,15 @@ int rtr_mgpu_render_batch_async(rtr_mgpu* m, const int* slots, int n, const RtrC
         for (int k = 0; k < j; ++k) if (slots[k] == slots[j]) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_mgpu_render_batch_async: slot %d given twice", slots[j]);
     }
     if (p->width == 0 || p->height == 0) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_mgpu_render_async: empty frame");
-    if (p->images & ~(RTR_IMAGES_FRAMEBUFFER | RTR_IMG_BIT(RTR_IMAGE_HDR))) return fail(RTR_ERR_UNSUPPORTED, "rtr_mgpu_render_async: only the RGBA8 framebuffer (RTR_IMAGE_SHADOWED) is gathered; RTR_IMAGE_HDR may be added for accumulation");
-    if (p->accumulate && !(p->images & RTR_IMG_BIT(RTR_IMAGE_HDR))) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_mgpu_render_async: accumulate needs RTR_IMAGE_HDR in params->images");
+    if (flags & RTR_MGPU_PRESENT) {
+        if (flags & RTR_MGPU_NO_EXCHANGE) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_mgpu_render_async: RTR_MGPU_PRESENT needs the exchange (the present passes read the whole frame); not with RTR_MGPU_NO_EXCHANGE");
+        if ((p->images & RTR_IMG_BIT(RTR_IMAGE_HDR)) || p->accumulate) return fail(RTR_ERR_UNSUPPORTED, "rtr_mgpu_render_async: RTR_MGPU_PRESENT renders one frame's five ray-gen images; HDR accumulation is not supported with it");
+        if (p->images != RTR_IMAGES_RAYGEN5) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_mgpu_render_async: RTR_MGPU_PRESENT needs params->images == RTR_IMAGES_RAYGEN5 (0x%x), got 0x%x", RTR_IMAGES_RAYGEN5, p->images);
+        if ((p->bandRows ? p->bandRows : 8u) % 8u) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_mgpu_render_async: RTR_MGPU_PRESENT needs bandRows a multiple of 8, got %u", p->bandRows);
+    } else {
+        if (p->images & ~(RTR_IMAGES_FRAMEBUFFER | RTR_IMG_BIT(RTR_IMAGE_HDR))) return fail(RTR_ERR_UNSUPPORTED, "rtr_mgpu_render_async: only the RGBA8 framebuffer (RTR_IMAGE_SHADOWED) is gathered; RTR_IMAGE_HDR may be added for accumulation (or RTR_MGPU_PRESENT with RTR_IMAGES_RAYGEN5)");
+        if (p->accumulate && !(p->images & RTR_IMG_BIT(RTR_IMAGE_HDR))) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_mgpu_render_async: accumulate needs RTR_IMAGE_HDR in params->images");
+    }
     for (auto& rp : m->ranks) if (!rp->scene) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_mgpu_render_async: no scene: call rtr_mgpu_scene_create first");
     /* consecutive calls on a slot are ordered by its render stream; only an enqueue still running on a worker forbids the next call */
     for (int j = 0; j < n; ++j)
@@ -624,14 +689,14 @@ int rtr_mgpu_render_batch_async(rtr_mgpu* m, const int* slots, int n, const RtrC
      * that dropped out after its peers had posted theirs would leave them waiting for ever.  In steady state (the slots already have
      * this extent) this is a comparison on the caller's thread. */
     bool prepared = true;
-    for (int j = 0; j < n; ++j) for (auto& rp : m->ranks) prepared = prepared && slot_matches(m, rp->slots[slots[j]], *p);
+    for (int j = 0; j < n; ++j) for (auto& rp : m->ranks) prepared = prepared && slot_matches(m, rp->slots[slots[j]], *p, flags);
     if (!prepared) {
         std::vector<std::future<int>> fs;
         std::vector<int> sl(slots, slots + n);
         for (auto& rp : m->ranks) {
             Rank* r = rp.get(); const rtr_render_params pp = *p;
-            fs.push_back(r->worker->submit([m, r, sl, pp](std::string& err) -> int {
-                for (int s1 : sl) { const int c = prepare_slot(m, *r, r->slots[s1], pp, err); if (c != RTR_OK) return c; }
+            fs.push_back(r->worker->submit([m, r, sl, pp, flags](std::string& err) -> int {
+                for (int s1 : sl) { const int c = prepare_slot(m, *r, r->slots[s1], pp, flags, err); if (c != RTR_OK) return c; }
                 return RTR_OK;
             }));
         }
@@ -641,7 +706,7 @@ int rtr_mgpu_render_batch_async(rtr_mgpu* m, const int* slots, int n, const RtrC
     }
     /* Phase 2 — the plan, rank by rank, each on its own thread */
     BatchJob job;
-    job.n = n; job.p = *p; job.flags = flags | m->planFlags;
+    job.n = n; job.p = *p; job.flags = flags | m->planFlags; job.iterations = m->denoiseIterations;
     for (int j = 0; j < n; ++j) { job.slots[j] = slots[j]; job.cams[j] = cams[j]; job.infos[j] = infos[j]; }
     for (auto& rp : m->ranks) {
         Rank* r = rp.get();
@@ -745,8 +810,43 @@ int rtr_mgpu_frame_device_ptr(rtr_mgpu* m, int slot, void** ptr, size_t* bytes) 
     Slot& s = r->slots[slot];
     /* a worker may be re-creating the slot's buffers right now */
     if (s.inFlight) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_mgpu_frame_device_ptr: slot %d is in flight; rtr_mgpu_wait it first", slot);
+    if (s.present) {                                   /* present mode: the presented image */
+        if (rtr_frame_device_ptr(s.present, RTR_IMAGE_FINAL, ptr, bytes) != RTR_OK) return fail(RTR_ERR_HIP, "rtr_mgpu_frame_device_ptr: %s", rtr_last_error());
+        return RTR_OK;
+    }
     if (!s.full) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_mgpu_frame_device_ptr: slot %d has not been rendered", slot);
     *ptr = s.full; if (bytes) *bytes = (size_t)s.width * s.height * 4;
+    return RTR_OK;
+}
+
+int rtr_mgpu_image_device_ptr(rtr_mgpu* m, int slot, int which, void** ptr, size_t* bytes) {
+    if (!m || !ptr) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_mgpu_image_device_ptr: null argument");
+    if (slot < 0 || slot >= m->framesInFlight) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_mgpu_image_device_ptr: slot %d not in [0,%d)", slot, m->framesInFlight);
+    if (which < 0 || which > 7) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_mgpu_image_device_ptr: image %d not in [0,7]", which);
+    Rank* r = rank0_of(m);
+    if (!r) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_mgpu_image_device_ptr: rank 0 is not in this process");
+    Slot& s = r->slots[slot];
+    if (s.inFlight) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_mgpu_image_device_ptr: slot %d is in flight; rtr_mgpu_wait it first", slot);
+    if (!s.present) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_mgpu_image_device_ptr: slot %d was not rendered with RTR_MGPU_PRESENT", slot);
+    if (rtr_frame_device_ptr(s.present, which, ptr, bytes) != RTR_OK) return fail(RTR_ERR_HIP, "rtr_mgpu_image_device_ptr: %s", rtr_last_error());
+    return RTR_OK;
+}
+
+int rtr_mgpu_image_download(rtr_mgpu* m, int slot, int which, void* dst, size_t bytes) {
+    if (!dst) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_mgpu_image_download: null destination");
+    void* src = nullptr; size_t need = 0;
+    int rc = rtr_mgpu_image_device_ptr(m, slot, which, &src, &need);
+    if (rc != RTR_OK) return rc;
+    if (bytes != need) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_mgpu_image_download: %zu bytes given, the image is %zu", bytes, need);
+    Rank* r = rank0_of(m);
+    if (hipSetDevice(r->device) != hipSuccess || hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) != hipSuccess) return fail(RTR_ERR_HIP, "rtr_mgpu_image_download: copy failed");
+    return RTR_OK;
+}
+
+int rtr_mgpu_set_denoise_iterations(rtr_mgpu* m, int iterations) {
+    if (!m) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_mgpu_set_denoise_iterations: null");
+    if (iterations < 0 || iterations > 64) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_mgpu_set_denoise_iterations: %d rounds, 0 to 64", iterations);
+    m->denoiseIterations = iterations;
     return RTR_OK;
 }
 
@@ -777,7 +877,9 @@ int rtr_mgpu_shard_download(rtr_mgpu* m, int slot, int localRank, void* dst, siz
     if (!s.frame || s.inFlight) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_mgpu_shard_download: slot %d not rendered or still in flight", slot);
     const size_t need = (size_t)s.rows * s.width * 4;
     if (bytes != need) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_mgpu_shard_download: %zu bytes given, the shard is %zu", bytes, need);
-    if (hipSetDevice(r.device) != hipSuccess || hipMemcpy(dst, s.local, bytes, hipMemcpyDeviceToHost) != hipSuccess) return fail(RTR_ERR_HIP, "rtr_mgpu_shard_download: copy failed");
+    void* src = nullptr;                               /* the shadowed image (in present mode the second of the shard's planes) */
+    if (rtr_frame_device_ptr(s.frame, RTR_IMAGE_SHADOWED, &src, nullptr) != RTR_OK) return fail(RTR_ERR_HIP, "rtr_mgpu_shard_download: %s", rtr_last_error());
+    if (hipSetDevice(r.device) != hipSuccess || hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) != hipSuccess) return fail(RTR_ERR_HIP, "rtr_mgpu_shard_download: copy failed");
     return RTR_OK;
 }
 

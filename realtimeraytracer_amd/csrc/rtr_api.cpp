@@ -1323,11 +1323,13 @@ int rtr_frame_get_stats(const rtr_frame* f, rtr_frame_stats* out) {
     return RTR_OK;
 }
 
-int rtr_denoise_combine(rtr_frame* f, int iterations) {
-    if (!f) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_denoise_combine: null frame");
-    if (iterations < 0 || iterations > 64) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_denoise_combine: iterations %d", iterations);
+/* the checks, launches and ping-pong of rtr_denoise_combine, enqueued on the frame's context stream (behind a batch launch that wrote
+ * the frame on another stream, and ahead of a later one: order_on_own_stream) */
+static int enqueue_denoise_combine(rtr_frame* f, int iterations, const char* who) {
+    if (!f) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: null frame", who);
+    if (iterations < 0 || iterations > 64) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: iterations %d", who, iterations);
     for (int i = 0; i < 8; ++i)
-        if (!f->image_ptr(i)) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_denoise_combine: the frame lacks image %d (create it with all of images 0-7)", i);
+        if (!f->image_ptr(i)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: the frame lacks image %d (create it with all of images 0-7)", who, i);
     HIP_TRY(hipSetDevice(f->ctx->device));
     { const int rc = order_on_own_stream(f); if (rc != RTR_OK) return rc; }
     hipStream_t st = f->ctx->stream;
@@ -1349,8 +1351,18 @@ int rtr_denoise_combine(rtr_frame* f, int iterations) {
     hipError_t e = rtrdev::launch_combine(f->image_ptr(RTR_IMAGE_ANALYTIC), denoisingOutput == 0 ? sh : dsh, denoisingOutput == 0 ? un : dun,
                                           f->image_ptr(RTR_IMAGE_FINAL), f->width, f->rows, st);
     if (e != hipSuccess) return fail(RTR_ERR_HIP, "combine launch: %s", hipGetErrorString(e));
-    HIP_TRY(hipStreamSynchronize(st));
     return RTR_OK;
+}
+
+int rtr_denoise_combine(rtr_frame* f, int iterations) {
+    const int rc = enqueue_denoise_combine(f, iterations, "rtr_denoise_combine");
+    if (rc != RTR_OK) return rc;
+    HIP_TRY(hipStreamSynchronize(f->ctx->stream));
+    return RTR_OK;
+}
+
+int rtr_denoise_combine_async(rtr_frame* f, int iterations) {
+    return enqueue_denoise_combine(f, iterations, "rtr_denoise_combine_async");     /* rtr_frame_wait joins */
 }
 
 int rtr_deinterleave_bands(rtr_ctx* ctx, const void* gathered, void* dst, uint32_t width, uint32_t height, uint32_t bandRows, uint32_t shardCount) {
@@ -1362,6 +1374,23 @@ int rtr_deinterleave_bands(rtr_ctx* ctx, const void* gathered, void* dst, uint32
     hipError_t e = rtrdev::launch_deinterleave((const uint32_t*)gathered, (uint32_t*)dst, width, height, bandRows, shardCount, localRows, ctx->stream);
     if (e != hipSuccess) return fail(RTR_ERR_HIP, "deinterleave launch: %s", hipGetErrorString(e));
     return RTR_OK;   /* enqueued on the ctx stream; the caller synchronises (stream order is enough for a following copy) */
+}
+
+int rtr_deinterleave_images(rtr_ctx* ctx, const void* gathered, uint32_t numImages, void* const* dst, uint32_t width, uint32_t height,
+                            uint32_t bandRows, uint32_t shardCount) {
+    if (!ctx || !gathered || !dst || width == 0 || height == 0) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_deinterleave_images: bad argument");
+    if (numImages == 0 || numImages > rtrdev::kMaxDeinterleaveImages) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_deinterleave_images: %u images, 1 to %u", numImages, rtrdev::kMaxDeinterleaveImages);
+    for (uint32_t i = 0; i < numImages; ++i) if (!dst[i]) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_deinterleave_images: destination %u is null", i);
+    if (bandRows == 0) bandRows = 8;
+    if (bandRows % 8u) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_deinterleave_images: bandRows %u is not a multiple of 8", bandRows);
+    if (shardCount == 0) shardCount = 1;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const uint32_t localRows = rtr_shard_rows(height, bandRows, shardCount);
+    uint32_t* d[rtrdev::kMaxDeinterleaveImages];
+    for (uint32_t i = 0; i < numImages; ++i) d[i] = static_cast<uint32_t*>(dst[i]);
+    hipError_t e = rtrdev::launch_deinterleave_images(static_cast<const uint32_t*>(gathered), d, numImages, width, height, bandRows, shardCount, localRows, ctx->stream);
+    if (e != hipSuccess) return fail(RTR_ERR_HIP, "deinterleave launch: %s", hipGetErrorString(e));
+    return RTR_OK;   /* enqueued on the ctx stream, like rtr_deinterleave_bands */
 }
 
 }  // extern "C"

@@ -75,6 +75,7 @@ class MultiGpu:
         self.info = A.rtr_mgpu_info()
         self._check(self.lib.rtr_mgpu_get_info(self.h, C.byref(self.info)), "rtr_mgpu_get_info")
         self._extent = {}            # per slot: (height, width, band rows) of the last render
+        self._present = {}           # per slot: rendered in present mode (RTR_MGPU_PRESENT)
 
     @staticmethod
     def unique_id():
@@ -107,20 +108,33 @@ class MultiGpu:
         import ctypes as C
         self._check(self.lib.rtr_mgpu_scene_create(self.h, C.byref(desc)), "rtr_mgpu_scene_create")
 
-    def render_async(self, slot, camera, scene_info, params, exchange=True):
-        import ctypes as C
-        self._check(self.lib.rtr_mgpu_render_async(self.h, slot, C.byref(camera), C.byref(scene_info), C.byref(params), 0 if exchange else 1), "rtr_mgpu_render_async")
-        self._extent[slot] = (params.height, params.width, params.bandRows or 8)
+    @staticmethod
+    def _flags(exchange, present):
+        from . import _abi as A
+        return (0 if exchange else A.MGPU_NO_EXCHANGE) | (A.MGPU_PRESENT if present else 0)
 
-    def render_batch_async(self, slots, cameras, scene_infos, params, exchange=True):
+    def render_async(self, slot, camera, scene_info, params, exchange=True, present=False):
+        """present=True: RTR_MGPU_PRESENT — params.images must be IMAGES_RAYGEN5; rank 0 assembles the five images and runs the
+        denoise + combine passes on its communication stream, download(slot) is then the presented (FINAL) image"""
+        import ctypes as C
+        self._check(self.lib.rtr_mgpu_render_async(self.h, slot, C.byref(camera), C.byref(scene_info), C.byref(params), self._flags(exchange, present)), "rtr_mgpu_render_async")
+        self._extent[slot] = (params.height, params.width, params.bandRows or 8)
+        self._present[slot] = bool(present)
+
+    def render_batch_async(self, slots, cameras, scene_infos, params, exchange=True, present=False):
         """rtr_mgpu_render_batch_async: len(slots) frames with one launch of the pipeline per rank, then every slot's exchange"""
         import ctypes as C
         from . import _abi as A
         n = len(slots)
         self._check(self.lib.rtr_mgpu_render_batch_async(self.h, (C.c_int * n)(*slots), n, (A.RtrCameraData * n)(*cameras), (A.RtrSceneInfo * n)(*scene_infos),
-                                                         C.byref(params), 0 if exchange else 1), "rtr_mgpu_render_batch_async")
+                                                         C.byref(params), self._flags(exchange, present)), "rtr_mgpu_render_batch_async")
         for s1 in slots:
             self._extent[s1] = (params.height, params.width, params.bandRows or 8)
+            self._present[s1] = bool(present)
+
+    def set_denoise_iterations(self, n):
+        """a-trous rounds of the present passes of later launches (0-64; default 4)"""
+        self._check(self.lib.rtr_mgpu_set_denoise_iterations(self.h, int(n)), "rtr_mgpu_set_denoise_iterations")
 
     def wait(self, slot):
         self._check(self.lib.rtr_mgpu_wait(self.h, slot), "rtr_mgpu_wait")
@@ -129,10 +143,15 @@ class MultiGpu:
         self.render_async(0, camera, scene_info, params)
         self.wait(0)
 
-    def download(self, slot=0):
+    def download(self, slot=0, which=None):
+        """the assembled frame of a waited-for slot (the presented FINAL image of a present slot); which = 0-7: that image of a
+        present slot (rtr_mgpu_image_download)"""
         H, W, _ = self._extent[slot]
         out = np.zeros((H, W), np.uint32)
-        self._check(self.lib.rtr_mgpu_frame_download(self.h, slot, out.ctypes.data, out.nbytes), "rtr_mgpu_frame_download")
+        if which is None:
+            self._check(self.lib.rtr_mgpu_frame_download(self.h, slot, out.ctypes.data, out.nbytes), "rtr_mgpu_frame_download")
+        else:
+            self._check(self.lib.rtr_mgpu_image_download(self.h, slot, int(which), out.ctypes.data, out.nbytes), "rtr_mgpu_image_download")
         return out
 
     def download_shard(self, slot=0, local_rank=0):

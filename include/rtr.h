@@ -338,6 +338,50 @@ int  rtr_deinterleave_bands(rtr_ctx* ctx, const void* gathered, void* dst, uint3
 int  rtr_deinterleave_images(rtr_ctx* ctx, const void* gathered, uint32_t numImages, void* const* dst, uint32_t width,
                              uint32_t height, uint32_t bandRows, uint32_t shardCount);
 
+/* ---- ray queries ---------------------------------------------------------------------- */
+/* The traversal of the renderer for rays the CALLER makes: what traceRayEXT does for raygen.rgen, without the fixed shaders.
+ * Flags (bit mask):
+ *   RTR_QUERY_CLOSEST  the closest hit: the (t, customIndex, primitiveId)-minimal one with tmin < t < tmax — gl_RayFlagsNoneEXT
+ *                      (reference src/shaders/raygen.rgen:99-107, the camera rays: tmin 0.001, tmax 10000).  Writes hits[].
+ *   RTR_QUERY_ANY      terminate on the first accepted hit and report only whether there is one (occluded[] = 1, else 0) —
+ *                      gl_RayFlagsTerminateOnFirstHitEXT | gl_RayFlagsSkipClosestHitShaderEXT (raygen.rgen:226-231, :299-303, the
+ *                      shadow rays).  Which triangle the walk meets first depends on the walk, so no hit record is defined.
+ *   RTR_QUERY_OPAQUE   skip the opacity-map test (opacity.rahit:31-64) as gl_RayFlagsOpaqueEXT does; without it alpha-tested
+ *                      geometry is treated exactly as the renderer treats it. */
+#define RTR_QUERY_CLOSEST 0u
+#define RTR_QUERY_ANY     1u
+#define RTR_QUERY_OPAQUE  2u
+
+typedef struct rtr_query_stats {
+    /* exact work counters of the query (the counting form of the kernels), counted as rtr_frame_stats counts the renderer's camera
+     * rays: a ray that outgrew the 16-entry LDS stack and was walked again over the BVH2 counts once, its two walks both */
+    uint64_t numRays;
+    uint64_t numNodeVisits;
+    uint64_t numTriTests;
+    uint64_t numAlphaTests;
+    uint64_t tailRays;         /* rays walked again by the tail kernel */
+    float    ms;               /* the query's kernels, HIP events on the context stream */
+    uint32_t _pad;
+} rtr_query_stats;
+
+/* numRays rays[] against `scene`, results in hits[] (RTR_QUERY_CLOSEST) or occluded[] (RTR_QUERY_ANY).  rays, hits and occluded are
+ * DEVICE pointers (torch tensors, hipMalloc), 16-B aligned; the pointer the mode does not use may be NULL and is not touched.  The work
+ * is ENQUEUED on ctx's stream (rtr_ctx_set_stream) and not waited for; the scene may belong to another context of the same device, as
+ * in rtr_render_async.  A ray with !(tmax > tmin), or whose origin or direction is not finite or whose direction is zero, is a miss.
+ * numRays == 0 does nothing.  RTR_ERR_INVALID_ARGUMENT (with a message) for a null pointer the mode needs, a pointer that is not
+ * 16-B aligned, unknown flag bits or a scene on another device.  The context keeps a small scratch area for the rays that need a deeper
+ * stack (bounded, whatever numRays is); calls on one context are ordered on its stream. */
+int  rtr_trace_rays_async(rtr_ctx* ctx, const rtr_scene* scene, const RtrRay* rays, uint32_t numRays, uint32_t flags,
+                          RtrHit* hits, uint8_t* occluded);
+/* The same, then joins ctx's stream (only that stream).  stats (may be NULL): run the counting form of the kernels and fill it. */
+int  rtr_trace_rays(rtr_ctx* ctx, const rtr_scene* scene, const RtrRay* rays, uint32_t numRays, uint32_t flags,
+                    RtrHit* hits, uint8_t* occluded, rtr_query_stats* stats);
+/* Writes to the device array out[] the width * height * spp camera rays the renderer traces for `camera` (raygen.rgen:83-107:
+ * jittered direction through the viewport, tmin 0.001, tmax 10000): ray k = (py * width + px) * spp + i.  ENQUEUED on ctx's stream.
+ * Callers generate, edit and trace camera rays this way; traced with RTR_QUERY_CLOSEST they give the renderer's primary hits.
+ * RTR_ERR_INVALID_ARGUMENT for a null or unaligned pointer, a zero extent or more than 2^32 - 1 rays. */
+int  rtr_camera_rays_async(rtr_ctx* ctx, const RtrCameraData* camera, uint32_t width, uint32_t height, uint32_t spp, RtrRay* out);
+
 /* ---- errors --------------------------------------------------------------------------- */
 const char* rtr_last_error(void);
 const char* rtr_status_string(int status);

@@ -168,6 +168,23 @@ typedef struct RtrBvhTri {
     float    e2[3]; uint32_t flags;      /* bit0: alpha-tested (any-hit needed) */
 } RtrBvhTri;
 
+/* ---- ray queries (rtr_trace_rays): one caller-supplied ray and its closest hit ---------------------------------------------
+ * What traceRayEXT takes (origin, tMin, direction, tMax: reference src/shaders/raygen.rgen:99-107) and what its hit shader reads
+ * (gl_HitTEXT, the barycentrics of hitAttributeEXT, gl_InstanceCustomIndexEXT, gl_PrimitiveID: closesthit.rchit:45-56), 32 B each
+ * so that a lane moves its record as two 16-B accesses.  The direction need not be normalised; t is in its units. */
+typedef struct RtrRay {
+    float origin[3];    float tmin;
+    float direction[3]; float tmax;
+} RtrRay;
+
+/* A miss: customIndex = primitiveId = 0xffffffff, t = the ray's tmax, u = v = 0.  _reserved is written as 0. */
+typedef struct RtrHit {
+    float    t, u, v;
+    uint32_t customIndex;
+    uint32_t primitiveId;
+    uint32_t _reserved[3];
+} RtrHit;
+
 #ifdef __cplusplus
 }
 #endif
@@ -183,6 +200,8 @@ static_assert(sizeof(RtrBvhNode) == 32, "BVH node must be 32 B");
 static_assert(sizeof(RtrBvhGrid) == 32, "BVH grid record must be 32 B");
 static_assert(sizeof(RtrBvhTri) == 48, "BVH triangle must be 48 B");
 static_assert(sizeof(RtrWideNode) == 64, "wide node must be 64 B");
+static_assert(sizeof(RtrRay) == 32, "ray must be 32 B");
+static_assert(sizeof(RtrHit) == 32, "hit must be 32 B");
 #endif
 
 #endif /* RTR_TYPES_H */

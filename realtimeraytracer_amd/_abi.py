@@ -63,6 +63,14 @@ class RtrWideNode(C.Structure):
     _fields_ = [("plane", (u32 * 3) * 4), ("child", i32 * 4)]
 
 
+class RtrRay(C.Structure):
+    _fields_ = [("origin", f32 * 3), ("tmin", f32), ("direction", f32 * 3), ("tmax", f32)]
+
+
+class RtrHit(C.Structure):
+    _fields_ = [("t", f32), ("u", f32), ("v", f32), ("customIndex", u32), ("primitiveId", u32), ("_reserved", u32 * 3)]
+
+
 class rtr_texture(C.Structure):
     _fields_ = [("pixels", C.POINTER(C.c_uint8)), ("width", u32), ("height", u32), ("channels", u32), ("_pad", u32)]
 
@@ -104,9 +112,15 @@ class rtr_frame_stats(C.Structure):
                 ("shadowTraceClockMinMHz", f32), ("shadowTraceClockMaxMHz", f32)]
 
 
+class rtr_query_stats(C.Structure):
+    _fields_ = [("numRays", u64), ("numNodeVisits", u64), ("numTriTests", u64), ("numAlphaTests", u64), ("tailRays", u64),
+                ("ms", f32), ("_pad", u32)]
+
+
 assert C.sizeof(RtrVertex) == 48 and C.sizeof(RtrCameraData) == 64 and C.sizeof(RtrSceneInfo) == 32
 assert C.sizeof(RtrObjectInfo) == 80 and C.sizeof(RtrAreaLightInfo) == 96
 assert C.sizeof(RtrBvhNode) == 32 and C.sizeof(RtrBvhGrid) == 32 and C.sizeof(RtrBvhTri) == 48 and C.sizeof(RtrWideNode) == 64
+assert C.sizeof(RtrRay) == 32 and C.sizeof(RtrHit) == 32 and C.sizeof(rtr_query_stats) == 48
 
 # enum rtr_image
 IMAGE_ANALYTIC, IMAGE_SHADOWED, IMAGE_UNSHADOWED = 0, 1, 2
@@ -122,6 +136,7 @@ IMAGES_FRAMEBUFFER = IMG_BIT(IMAGE_SHADOWED)
 IMAGES_RAYGEN5 = IMG_BIT(0) | IMG_BIT(1) | IMG_BIT(2) | IMG_BIT(6) | IMG_BIT(7)
 IMAGES_DENOISE = IMG_BIT(3) | IMG_BIT(4) | IMG_BIT(5)
 BUILD_HOST_SAH, BUILD_DEVICE_LBVH = 0, 1
+QUERY_CLOSEST, QUERY_ANY, QUERY_OPAQUE = 0, 1, 2
 
 P = C.POINTER
 VP = C.c_void_p
@@ -169,6 +184,9 @@ RTR_SYMBOLS = {
     "rtr_abi_version": (C.c_int, []),
     "rtr_kernel_revision": (C.c_char_p, []),
     "rtr_check_scene_limits": (C.c_int, [C.c_uint64, C.c_uint64]),
+    "rtr_trace_rays_async": (C.c_int, [VP, VP, VP, u32, u32, VP, VP]),
+    "rtr_trace_rays": (C.c_int, [VP, VP, VP, u32, u32, VP, VP, P(rtr_query_stats)]),
+    "rtr_camera_rays_async": (C.c_int, [VP, P(RtrCameraData), u32, u32, u32, VP]),
 }
 
 RTRH_SYMBOLS = {

@@ -25,6 +25,7 @@ class Context:
     def __init__(self, device=0, test_hooks=False):
         """test_hooks: everything made from this context goes through librtr_hip_test.so (the product's sources + the test switches)"""
         self.lib = A.hip_lib_with_hooks() if test_hooks else A.hip_lib()
+        self.device = int(device)
         self.h = A.VP()
         _check(self.lib.rtr_ctx_create(device, C.byref(self.h)), "rtr_ctx_create")
 
@@ -38,6 +39,12 @@ class Context:
 
     def set_stream(self, stream_ptr):
         _check(self.lib.rtr_ctx_set_stream(self.h, A.VP(stream_ptr) if stream_ptr else None), "rtr_ctx_set_stream")
+
+    def get_stream(self):
+        """the hipStream_t (as an int) this context's work is enqueued on"""
+        p = A.VP()
+        _check(self.lib.rtr_ctx_get_stream(self.h, C.byref(p)), "rtr_ctx_get_stream")
+        return p.value or 0
 
     def device_name(self):
         buf = C.create_string_buffer(256)
@@ -247,4 +254,102 @@ def host_build_bvh_wide(desc):
     out = BvhExport((nodes, tris, st.grid))
     out.wide = wide
     out.stats = st
+    return out
+
+
+# ---- ray queries (rtr_trace_rays, rtr_camera_rays_async) ----------------------------------------------------------------------------
+class QueryResult:
+    """What trace_rays gives back.  Closest hit: t, u, v (float32), custom_index, primitive_id (int32, -1 for a miss; t = the ray's tmax
+    then).  Any hit: occluded (uint8, 1 = occluded).  The other fields are None.  stats: rtr_query_stats of the counting form, or None."""
+    t = u = v = custom_index = primitive_id = occluded = stats = None
+
+
+def _torch():
+    import torch
+    return torch
+
+
+def _join_ctx_stream(ctx, torch, dev):
+    """torch's current stream waits for what the context's stream holds (a no-op when they are one stream)"""
+    cs = ctx.get_stream()
+    cur = torch.cuda.current_stream(dev)
+    if cs != cur.cuda_stream:
+        torch.cuda.ExternalStream(cs, device=dev).synchronize()
+
+
+def trace_rays(scene, rays, any_hit=False, opaque=False, collect_stats=False, ctx=None, asynchronous=False):
+    """rtr_trace_rays: rays is a contiguous float32 (N, 8) tensor on the context's device — rows are RtrRay (origin, tmin, direction,
+    tmax) — whose results come back as device tensors without a copy, or a numpy array, which is copied to the device and whose results
+    come back as numpy.  any_hit: occlusion only (RTR_QUERY_ANY); opaque: no opacity-map test (RTR_QUERY_OPAQUE).  ctx: the context whose
+    stream carries the work (default: the scene's).  asynchronous: enqueue and return (rtr_trace_rays_async); the context must then be
+    on torch's current stream (ctx.set_stream), so that the results are ordered for torch without a join.  collect_stats: the counting
+    form, synchronous.  Wrong shape, dtype, device or layout raises ValueError before anything is launched."""
+    torch = _torch()
+    ctx = ctx or scene.ctx
+    dev = torch.device("cuda", ctx.device)
+    as_numpy = isinstance(rays, np.ndarray)
+    if as_numpy:
+        if rays.dtype != np.float32 or rays.ndim != 2 or rays.shape[1] != 8:
+            raise ValueError(f"trace_rays: rays must be float32 (N, 8), got {rays.dtype} {rays.shape}")
+        r = torch.from_numpy(np.ascontiguousarray(rays)).to(dev)
+    elif isinstance(rays, torch.Tensor):
+        if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8:
+            raise ValueError(f"trace_rays: rays must be float32 (N, 8), got {rays.dtype} {tuple(rays.shape)}")
+        if rays.device != dev:
+            raise ValueError(f"trace_rays: rays live on {rays.device}, the context on {dev}")
+        if not rays.is_contiguous():
+            raise ValueError("trace_rays: rays must be contiguous")
+        r = rays
+    else:
+        raise ValueError(f"trace_rays: rays must be a torch tensor or a numpy array, got {type(rays).__name__}")
+    if asynchronous and collect_stats:
+        raise ValueError("trace_rays: collect_stats needs the synchronous form")
+    if asynchronous and ctx.get_stream() != torch.cuda.current_stream(dev).cuda_stream:
+        raise ValueError("trace_rays: an asynchronous query needs the context on torch's current stream (ctx.set_stream)")
+    n = int(r.shape[0])
+    flags = (A.QUERY_ANY if any_hit else A.QUERY_CLOSEST) | (A.QUERY_OPAQUE if opaque else 0)
+    hits = occ = None
+    if any_hit:
+        occ = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)[:n]
+    else:
+        hits = torch.empty((n, 8), dtype=torch.int32, device=dev)
+    if not asynchronous and ctx.get_stream() != torch.cuda.current_stream(dev).cuda_stream:
+        torch.cuda.current_stream(dev).synchronize()        # the rays (and the outputs' memory) are ready for the context's stream
+    hp = A.VP(hits.data_ptr()) if hits is not None and n else None
+    op = A.VP(occ.data_ptr()) if occ is not None and n else None
+    rp = A.VP(r.data_ptr()) if n else None
+    out = QueryResult()
+    if asynchronous:
+        _check(ctx.lib.rtr_trace_rays_async(ctx.h, scene.h, rp, n, flags, hp, op), "rtr_trace_rays_async")
+    else:
+        st = A.rtr_query_stats() if collect_stats else None
+        _check(ctx.lib.rtr_trace_rays(ctx.h, scene.h, rp, n, flags, hp, op, C.byref(st) if st is not None else None), "rtr_trace_rays")
+        out.stats = st
+    if any_hit:
+        out.occluded = occ
+    else:
+        f = hits.view(torch.float32)
+        out.t, out.u, out.v = f[:, 0], f[:, 1], f[:, 2]
+        out.custom_index, out.primitive_id = hits[:, 3], hits[:, 4]
+    if as_numpy:
+        for k in ("t", "u", "v", "custom_index", "primitive_id", "occluded"):
+            x = getattr(out, k)
+            if x is not None:
+                setattr(out, k, x.cpu().numpy())
+    out._keep = (r, hits, occ)           # an asynchronous query's buffers stay alive with its result
+    return out
+
+
+def camera_rays(ctx, camera, width, height, spp=1):
+    """rtr_camera_rays_async: the (width * height * spp, 8) float32 device tensor of the camera rays the renderer traces for `camera`,
+    row k = (py * width + px) * spp + i; ready for torch's current stream when it returns."""
+    torch = _torch()
+    dev = torch.device("cuda", ctx.device)
+    n = int(width) * int(height) * int(spp)
+    out = torch.empty((max(n, 1), 8), dtype=torch.float32, device=dev)[:n]
+    if ctx.get_stream() != torch.cuda.current_stream(dev).cuda_stream:
+        torch.cuda.current_stream(dev).synchronize()        # the tensor's memory is free for the context's stream
+    _check(ctx.lib.rtr_camera_rays_async(ctx.h, C.byref(camera), int(width), int(height), int(spp), A.VP(out.data_ptr()) if n else None),
+           "rtr_camera_rays_async")
+    _join_ctx_stream(ctx, torch, dev)
     return out

@@ -72,4 +72,16 @@ inline void render(const Scene& scene, const RtrCameraData& cam, const RtrSceneI
     check(rtr_render(scene.get(), &cam, &info, &p, frame.get()), "rtr_render");
 }
 
+// ray queries: rays, hits and occluded are DEVICE arrays (include/rtr.h: rtr_trace_rays); flags RTR_QUERY_ANY | RTR_QUERY_OPAQUE.
+// Synchronous: returns when the results are in place (stats, if given, from the counting form).
+inline void trace_rays(const Context& ctx, const Scene& scene, const RtrRay* rays, uint32_t numRays, uint32_t flags, RtrHit* hits,
+                       uint8_t* occluded, rtr_query_stats* stats = nullptr) {
+    check(rtr_trace_rays(ctx.get(), scene.get(), rays, numRays, flags, hits, occluded, stats), "rtr_trace_rays");
+}
+
+// the width * height * spp camera rays the renderer traces for `cam`, written to the device array `out` (enqueued on ctx's stream)
+inline void camera_rays(const Context& ctx, const RtrCameraData& cam, uint32_t width, uint32_t height, uint32_t spp, RtrRay* out) {
+    check(rtr_camera_rays_async(ctx.get(), &cam, width, height, spp, out), "rtr_camera_rays_async");
+}
+
 }  // namespace rtr

@@ -238,8 +238,13 @@ __device__ __forceinline__ uint32_t ray_octant(const DeviceScene& sc, rtr_v3 o, 
 /* LIMIT > 0: the stack holds only LIMIT entries; a ray that needs more is abandoned with best.custom = RTR_STACK_OVERFLOW (the
  * caller re-traces it with a full-depth stack), so the common case can run with a small LDS footprint. */
 #define RTR_STACK_OVERFLOW 0xfffffffeu
-/* OCT 0..7: every lane that calls has these direction signs (slab_oct); 8 = any. */
-template <bool ANY, bool STATS, int BLOCK, int LIMIT = 0, int OCT = 8>
+/* OCT 0..7: every lane that calls has these direction signs (slab_oct); 8 = any.  ALPHA = false: no opacity-map test, every
+ * candidate is accepted (the ray queries' RTR_QUERY_OPAQUE, gl_RayFlagsOpaqueEXT).
+ * FLAT_TAKE: the closest-hit rule written without short-circuit branches.  In the ray-query kernels the branchy form was miscompiled on
+ * exact ties in t: a candidate that won on (customIndex, primitiveId) got its t, u, v stored but the ids of the hit it replaced stayed
+ * (the compiler merged the two ids into one 64-bit value and carried the old pair along the tie path).  The renderer's kernels are
+ * compiled correctly with the branchy form and keep it. */
+template <bool ANY, bool STATS, int BLOCK, int LIMIT = 0, int OCT = 8, bool ALPHA = true, bool FLAT_TAKE = false>
 __device__ __forceinline__ bool trace(const DeviceScene& sc, int32_t* __restrict__ stack,
                                       rtr_v3 o, rtr_v3 d, float tmin, float tmax, HitRec& best, LocalStats& st) {
     if (STATS) { st.rays++; if (ANY) st.shadow++; else st.primary++; }
@@ -301,9 +306,13 @@ __device__ __forceinline__ bool trace(const DeviceScene& sc, int32_t* __restrict
                 if (rtr_mt_intersect(o, d, f4xyz(q0), f4xyz(q1), f4xyz(q2), tmin, &t, &u, &v)) {
                     if (t < tmax) {
                         const uint32_t cu = __float_as_uint(q0.w), pr = __float_as_uint(q1.w);
-                        if ((__float_as_uint(q2.w) & 1u) && !alpha_pass<STATS>(sc, cu, pr, u, v, st)) continue;
+                        if (ALPHA && (__float_as_uint(q2.w) & 1u) && !alpha_pass<STATS>(sc, cu, pr, u, v, st)) continue;
                         bool take;
-                        if (!found) take = true;
+                        if (FLAT_TAKE) {
+                            /* the same rule, evaluated without short-circuit branches (see FLAT_TAKE above) */
+                            const bool idLess = (cu < best.custom) | ((cu == best.custom) & (pr < best.prim));
+                            take = !found | (t < best.t) | ((t == best.t) & idLess);
+                        } else if (!found) take = true;
                         else take = t < best.t || (t == best.t && (cu < best.custom || (cu == best.custom && pr < best.prim)));
                         if (take) {
                             found = true; best.t = t; best.u = u; best.v = v; best.custom = cu; best.prim = pr; best.leaf = cur;

@@ -1,0 +1,30 @@
+/* rtr_query.h — host-callable launchers of the ray-query kernels (kernels/rtr_query.hip; internal to librtr_hip.so). */
+#pragma once
+#include <hip/hip_runtime.h>
+#include "rtr_kernels.h"
+
+namespace rtrdev {
+
+/* Entries of a context's redo list: the rays of one query that outgrew the 16-entry LDS stack.  Past it the tail kernel finds them by
+ * their sentinel in the outputs instead, so the scratch does not grow with the number of rays. */
+constexpr uint32_t kQueryRedoCap = 1u << 16;
+constexpr uint32_t kQueryRedoWord = 0;       /* word of the control block: rays appended to the redo list (may exceed its capacity) */
+constexpr uint32_t kQueryCtrlWords = 16;
+
+struct QueryArgs {
+    const float4* rays;          /* RtrRay as 2 x float4: {origin, tmin} {direction, tmax} */
+    float4* hits;                /* RtrHit as 2 x float4 (closest hit), or null */
+    uint8_t* occluded;           /* any hit: 1 = occluded, or null */
+    uint32_t n;
+    uint32_t redoCap;            /* entries of redoList the query may use */
+    uint32_t* ctrl;              /* kQueryCtrlWords words, zeroed before the launch */
+    uint32_t* redoList;
+    int32_t* spill;              /* kSpillInts: the tail kernel's full-depth stacks */
+};
+
+/* flags: RTR_QUERY_ANY | RTR_QUERY_OPAQUE (validated by the caller).  stats: the counting form, counters added there (zeroed by the caller). */
+hipError_t launch_query(const DeviceScene& sc, const QueryArgs& qa, uint32_t flags, Counters* stats, hipStream_t stream);
+/* width * height * spp camera rays of raygen.rgen:83-107, ray k = (py * width + px) * spp + i (< 2^32, checked by the caller) */
+hipError_t launch_camera_rays(const RtrCameraData& cam, uint32_t width, uint32_t height, uint32_t spp, float4* out, hipStream_t stream);
+
+}  // namespace rtrdev

@@ -1,0 +1,159 @@
+/* rtr_query.hip — ray queries: the renderer's BVH2 walk for rays the caller supplies (include/rtr.h: rtr_trace_rays).
+ *
+ * What traceRayEXT does for the reference's ray-gen shader, without the fixed shaders: closest hit (gl_RayFlagsNoneEXT, the camera
+ * rays of raygen.rgen:99-107) or terminate-on-first-hit (the shadow rays of raygen.rgen:226-231, :299-303), with or without the
+ * opacity-map any-hit test.  The walk is trace() of rtr_device.h, the one the camera-ray kernel k_primary runs, so a camera ray
+ * (rtr_camera_rays_async) traced here gets the renderer's primary hit bit for bit and is counted as the renderer counts it:
+ *   k_query       one ray per lane, one-wave workgroups (RTR_PRIMARY_BLOCK, what k_primary measured best), 16-entry interleaved
+ *                 LDS stack; a wave whose rays share their direction signs runs the octant form of the slab test.  A ray that
+ *                 needs more stack is abandoned: its output gets a sentinel and it is appended to a bounded redo list, one atomic
+ *                 per wave (ballot + mbcnt prefix);
+ *   k_query_tail  walks those rays again with a full-depth stack in global memory (as k_primary_tail does); if the redo list
+ *                 overflowed it finds them by their sentinel in the outputs.
+ * Compiled with the library's flags (-ffp-contract=off): the numerical contract of include/rtr_math.h.
+ */
+#include "rtr_query.h"
+#include "../../../include/rtr.h"
+
+namespace rtrdev {
+
+#ifndef RTR_PRIMARY_BLOCK
+#define RTR_PRIMARY_BLOCK 64
+#endif
+constexpr int kQueryBlock = RTR_PRIMARY_BLOCK;
+static_assert(kQueryBlock % 64 == 0 && kQueryBlock >= 64 && kQueryBlock <= 1024, "RTR_PRIMARY_BLOCK: a multiple of 64");
+constexpr int kQueryTailBlock = 256;
+constexpr int kQueryTailBlocks = 64;         /* the spill area holds 64 entries for each of these 64 x 256 lanes */
+static_assert((size_t)64 * kQueryTailBlocks * kQueryTailBlock == kSpillInts, "the tail kernel's stacks fill the spill area");
+constexpr uint8_t kOccludedRedo = 0xffu;     /* sentinel of an abandoned any-hit ray (its hit record's sentinel: customIndex = RTR_STACK_OVERFLOW) */
+
+/* ray k: two 16-B loads.  false: a degenerate ray (origin or direction not finite, or a zero direction), which is a miss */
+__device__ __forceinline__ bool query_ray(const float4* __restrict__ rays, uint32_t k, rtr_v3& o, rtr_v3& d, float& tmin, float& tmax) {
+    const float4 a = rays[2 * (size_t)k], b = rays[2 * (size_t)k + 1];
+    o = rtr_mk(a.x, a.y, a.z); tmin = a.w;
+    d = rtr_mk(b.x, b.y, b.z); tmax = b.w;
+    const bool finite = __builtin_isfinite(a.x) && __builtin_isfinite(a.y) && __builtin_isfinite(a.z) &&
+                        __builtin_isfinite(b.x) && __builtin_isfinite(b.y) && __builtin_isfinite(b.z);
+    return finite && (b.x != 0.0f || b.y != 0.0f || b.z != 0.0f);
+}
+
+/* RtrHit as two 16-B stores: {t, u, v, customIndex} {primitiveId, 0, 0, 0} */
+__device__ __forceinline__ void query_store_hit(float4* __restrict__ hits, uint32_t k, const HitRec& h) {
+    hits[2 * (size_t)k] = make_float4(h.t, h.u, h.v, __uint_as_float(h.custom));
+    hits[2 * (size_t)k + 1] = make_float4(__uint_as_float(h.prim), 0.0f, 0.0f, 0.0f);
+}
+
+template <bool ANY, bool ALPHA, bool STATS>
+__global__ __launch_bounds__(kQueryBlock) void k_query(DeviceScene sc, QueryArgs qa, Counters* stats) {
+    __shared__ int32_t s_stack[16 * kQueryBlock];
+    int32_t* stack = s_stack + threadIdx.x;
+    const uint32_t k = blockIdx.x * kQueryBlock + threadIdx.x;
+    if (k >= qa.n) return;
+    LocalStats st;
+    rtr_v3 o, d;
+    float tmin, tmax;
+    const bool ok = query_ray(qa.rays, k, o, d, tmin, tmax);
+    const float limit = ok ? tmax : tmin;                 /* a degenerate ray walks nothing (!(limit > tmin)) but is counted like any other */
+    HitRec h;
+    if (STATS) trace<ANY, true, kQueryBlock, 16, 8, ALPHA, true>(sc, stack, o, d, tmin, limit, h, st);
+    else {
+        /* as in k_primary: the traversal compiled for the wave's direction signs when all its rays share them */
+        const uint32_t oct = ray_octant(sc, o, d);
+        const uint32_t woct = (uint32_t)__builtin_amdgcn_readfirstlane((int)oct);
+        switch (__ballot(oct != woct) != 0ull ? 8u : woct) {
+            case 0: trace<ANY, false, kQueryBlock, 16, 0, ALPHA, true>(sc, stack, o, d, tmin, limit, h, st); break;
+            case 1: trace<ANY, false, kQueryBlock, 16, 1, ALPHA, true>(sc, stack, o, d, tmin, limit, h, st); break;
+            case 2: trace<ANY, false, kQueryBlock, 16, 2, ALPHA, true>(sc, stack, o, d, tmin, limit, h, st); break;
+            case 3: trace<ANY, false, kQueryBlock, 16, 3, ALPHA, true>(sc, stack, o, d, tmin, limit, h, st); break;
+            case 4: trace<ANY, false, kQueryBlock, 16, 4, ALPHA, true>(sc, stack, o, d, tmin, limit, h, st); break;
+            case 5: trace<ANY, false, kQueryBlock, 16, 5, ALPHA, true>(sc, stack, o, d, tmin, limit, h, st); break;
+            case 6: trace<ANY, false, kQueryBlock, 16, 6, ALPHA, true>(sc, stack, o, d, tmin, limit, h, st); break;
+            case 7: trace<ANY, false, kQueryBlock, 16, 7, ALPHA, true>(sc, stack, o, d, tmin, limit, h, st); break;
+            default: trace<ANY, false, kQueryBlock, 16, 8, ALPHA, true>(sc, stack, o, d, tmin, limit, h, st); break;
+        }
+    }
+    /* the walk's outcome is read from the record alone (as k_primary reads it), not from trace()'s return value */
+    const bool over = h.custom == RTR_STACK_OVERFLOW, found = h.custom != RTR_MISS && !over;
+    if (!ok) h.t = tmax;                                  /* a miss reports the ray's own tmax */
+    if (ANY) qa.occluded[k] = over ? kOccludedRedo : (found ? 1u : 0u);
+    else query_store_hit(qa.hits, k, h);                  /* an abandoned ray's record carries customIndex = RTR_STACK_OVERFLOW */
+    /* the abandoned rays of the wave take consecutive entries of the redo list: one atomic per wave */
+    const unsigned long long m = __ballot(over);
+    if (m != 0ull) {
+        const uint32_t prefix = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+        uint32_t base = 0;
+        if (over && prefix == 0u) base = atomicAdd(qa.ctrl + kQueryRedoWord, (uint32_t)__popcll(m));
+        base = (uint32_t)__builtin_amdgcn_readlane((int)base, __ffsll((long long)m) - 1);
+        if (over && base + prefix < qa.redoCap) qa.redoList[base + prefix] = k;
+    }
+    if (STATS) st.flush(stats);
+}
+
+/* The rays k_query abandoned, walked from the root with a full-depth stack in global memory (no LDS, so it can always run).  From the
+ * redo list, or — when more rays were abandoned than the list holds — from a scan of the outputs for their sentinel.  STATS: the
+ * counting form (the ray itself was counted by k_query; this walk's visits and tests are added to it). */
+template <bool ANY, bool ALPHA, bool STATS>
+__global__ __launch_bounds__(kQueryTailBlock) void k_query_tail(DeviceScene sc, QueryArgs qa, Counters* stats) {
+    const uint32_t count = qa.ctrl[kQueryRedoWord];
+    if (count == 0u) return;
+    const bool scan = count > qa.redoCap;
+    const uint64_t m = scan ? qa.n : count;
+    int32_t* stack = qa.spill + blockIdx.x * kQueryTailBlock + threadIdx.x;
+    LocalStats st;
+    for (uint64_t j = (uint64_t)blockIdx.x * kQueryTailBlock + threadIdx.x; j < m; j += (uint64_t)gridDim.x * kQueryTailBlock) {
+        uint32_t k = (uint32_t)j;
+        if (!scan) k = qa.redoList[j];
+        else if (ANY ? qa.occluded[k] != kOccludedRedo : __float_as_uint(qa.hits[2 * (size_t)k].w) != RTR_STACK_OVERFLOW) continue;
+        rtr_v3 o, d;
+        float tmin, tmax;
+        query_ray(qa.rays, k, o, d, tmin, tmax);          /* an abandoned ray is never degenerate: it walked past 16 stacked nodes */
+        HitRec h;
+        trace<ANY, STATS, kQueryTailBlocks * kQueryTailBlock, 0, 8, ALPHA, true>(sc, stack, o, d, tmin, tmax, h, st);
+        const bool found = h.custom != RTR_MISS;
+        if (STATS) { st.rays--; if (ANY) st.shadow--; else st.primary--; }
+        if (ANY) qa.occluded[k] = found ? 1u : 0u;
+        else query_store_hit(qa.hits, k, h);
+    }
+    if (STATS) st.flush(stats);
+}
+
+template <bool ANY, bool ALPHA, bool STATS>
+static hipError_t query_t(const DeviceScene& sc, const QueryArgs& qa, Counters* stats, hipStream_t s) {
+    const uint32_t blocks = (uint32_t)(((uint64_t)qa.n + kQueryBlock - 1) / kQueryBlock);
+    hipLaunchKernelGGL((k_query<ANY, ALPHA, STATS>), dim3(blocks), dim3(kQueryBlock), 0, s, sc, qa, stats);
+    hipLaunchKernelGGL((k_query_tail<ANY, ALPHA, STATS>), dim3(kQueryTailBlocks), dim3(kQueryTailBlock), 0, s, sc, qa, stats);
+    return hipGetLastError();
+}
+
+template <bool ANY, bool ALPHA>
+static hipError_t query_s(const DeviceScene& sc, const QueryArgs& qa, Counters* stats, hipStream_t s) {
+    return stats ? query_t<ANY, ALPHA, true>(sc, qa, stats, s) : query_t<ANY, ALPHA, false>(sc, qa, stats, s);
+}
+
+hipError_t launch_query(const DeviceScene& sc, const QueryArgs& qa, uint32_t flags, Counters* stats, hipStream_t s) {
+    const bool any = (flags & RTR_QUERY_ANY) != 0u, alpha = (flags & RTR_QUERY_OPAQUE) == 0u;
+    if (any) return alpha ? query_s<true, true>(sc, qa, stats, s) : query_s<true, false>(sc, qa, stats, s);
+    return alpha ? query_s<false, true>(sc, qa, stats, s) : query_s<false, false>(sc, qa, stats, s);
+}
+
+/* one lane per pixel-sample: the camera ray k_primary traces for it (primary_dir, tmin 0.001, tmax 10000) */
+constexpr int kCameraRaysBlock = 256;
+__global__ __launch_bounds__(kCameraRaysBlock) void k_camera_rays(RenderArgs ra, uint32_t n, float4* __restrict__ out) {
+    const uint32_t k = blockIdx.x * kCameraRaysBlock + threadIdx.x;
+    if (k >= n) return;
+    const uint32_t i = k % ra.spp, pix = k / ra.spp;
+    const uint32_t px = pix % ra.width, py = pix / ra.width;
+    const rtr_v3 d = primary_dir(ra, px, py, i);
+    out[2 * (size_t)k] = make_float4(ra.cam.position[0], ra.cam.position[1], ra.cam.position[2], 0.001f);
+    out[2 * (size_t)k + 1] = make_float4(d.x, d.y, d.z, 10000.0f);
+}
+
+hipError_t launch_camera_rays(const RtrCameraData& cam, uint32_t width, uint32_t height, uint32_t spp, float4* out, hipStream_t s) {
+    RenderArgs ra{};
+    ra.cam = cam; ra.width = width; ra.height = height; ra.spp = spp;
+    const uint32_t n = width * height * spp;
+    hipLaunchKernelGGL(k_camera_rays, dim3((uint32_t)(((uint64_t)n + kCameraRaysBlock - 1) / kCameraRaysBlock)), dim3(kCameraRaysBlock), 0, s, ra, n, out);
+    return hipGetLastError();
+}
+
+}  // namespace rtrdev

@@ -8,6 +8,7 @@
 #include "kernels/rtr_kernels.h"
 #include "kernels/rtr_post.h"
 #include "kernels/rtr_bvh.h"
+#include "kernels/rtr_query.h"
 
 #include <hip/hip_runtime.h>
 
@@ -79,10 +80,20 @@ struct rtr_ctx {
     int children = 0;
     bool destroyed = false;
     rtrdev::Tunables tun;                /* run-time tunables of the staged pipeline: environment at creation, rtr_ctx_set_tunable afterwards */
+    /* ray queries (rtr_trace_rays): the tail kernel's scratch — control block, redo list (kQueryRedoCap entries), full-depth stacks —
+     * and the counters of the counting form.  Allocated by the first query and reused by every later one: its size does not depend on
+     * the number of rays.  qEv: around the query's kernels (timing, and what a query enqueued on another stream waits for). */
+    DevBuf<uint32_t> qCtrl, qRedo;
+    DevBuf<int32_t> qSpill;
+    DevBuf<Counters> qCounters;
+    hipEvent_t qEv[2] = {nullptr, nullptr};
+    hipStream_t qLastStream = nullptr;   /* the stream the last query was enqueued on */
 };
 
 static void ctx_free(rtr_ctx* c) {
     (void)hipSetDevice(c->device);
+    if (c->qLastStream) (void)hipEventSynchronize(c->qEv[1]);      /* the scratch below is freed with the context */
+    for (hipEvent_t e : c->qEv) if (e) (void)hipEventDestroy(e);
     if (c->ownStream && c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -1391,6 +1402,87 @@ int rtr_deinterleave_images(rtr_ctx* ctx, const void* gathered, uint32_t numImag
     hipError_t e = rtrdev::launch_deinterleave_images(static_cast<const uint32_t*>(gathered), d, numImages, width, height, bandRows, shardCount, localRows, ctx->stream);
     if (e != hipSuccess) return fail(RTR_ERR_HIP, "deinterleave launch: %s", hipGetErrorString(e));
     return RTR_OK;   /* enqueued on the ctx stream, like rtr_deinterleave_bands */
+}
+
+/* ---- ray queries ---------------------------------------------------------------------------- */
+static bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+
+/* the checks and launches of rtr_trace_rays[_async], enqueued on the context's stream; count: the counting form */
+static int enqueue_query(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, uint32_t n, uint32_t flags, RtrHit* hits, uint8_t* occluded,
+                         bool count, const char* who) {
+    if (!c || !s) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: null context or scene", who);
+    if (flags & ~(RTR_QUERY_ANY | RTR_QUERY_OPAQUE)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: unknown flag bits 0x%x", who, flags & ~(RTR_QUERY_ANY | RTR_QUERY_OPAQUE));
+    if (s->ctx->device != c->device) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: the scene lives on device %d, the context on device %d", who, s->ctx->device, c->device);
+    if (n == 0) return RTR_OK;
+    const bool any = (flags & RTR_QUERY_ANY) != 0u;
+    if (!rays) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: rays is null", who);
+    if (!aligned16(rays)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: rays is not 16-B aligned", who);
+    if (!any && !hits) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: a closest-hit query needs hits", who);
+    if (!any && !aligned16(hits)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: hits is not 16-B aligned", who);
+    if (any && !occluded) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: an any-hit query (RTR_QUERY_ANY) needs occluded", who);
+    if (any && !aligned16(occluded)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: occluded is not 16-B aligned", who);
+    HIP_TRY(hipSetDevice(c->device));
+    if (!c->qCtrl.p) {
+        HIP_TRY(c->qCtrl.alloc(rtrdev::kQueryCtrlWords));
+        HIP_TRY(c->qRedo.alloc(rtrdev::kQueryRedoCap));
+        HIP_TRY(c->qSpill.alloc(rtrdev::kSpillInts));
+        HIP_TRY(c->qCounters.alloc(1));
+        for (hipEvent_t& e : c->qEv) HIP_TRY(hipEventCreate(&e));
+    }
+    uint32_t redoCap = rtrdev::kQueryRedoCap;
+#ifdef RTR_TEST_HOOKS
+    if (const char* e = getenv("RTR_QUERY_REDO_CAP")) { const uint64_t v = strtoull(e, nullptr, 10); if (v >= 1 && v < redoCap) redoCap = (uint32_t)v; }   /* a list short enough to overflow */
+#endif
+    hipStream_t st = c->stream;
+    /* the scratch is the context's: a query enqueued on another stream than the last one (rtr_ctx_set_stream) comes behind it */
+    if (c->qLastStream && c->qLastStream != st) HIP_TRY(hipStreamWaitEvent(st, c->qEv[1], 0));
+    HIP_TRY(hipMemsetAsync(c->qCtrl.p, 0, rtrdev::kQueryCtrlWords * sizeof(uint32_t), st));
+    if (count) HIP_TRY(hipMemsetAsync(c->qCounters.p, 0, sizeof(Counters), st));
+    HIP_TRY(hipEventRecord(c->qEv[0], st));
+    rtrdev::QueryArgs qa{};
+    qa.rays = reinterpret_cast<const float4*>(rays); qa.hits = reinterpret_cast<float4*>(hits); qa.occluded = occluded; qa.n = n;
+    qa.redoCap = redoCap; qa.ctrl = c->qCtrl.p; qa.redoList = c->qRedo.p; qa.spill = c->qSpill.p;
+    const hipError_t e = rtrdev::launch_query(s->dev, qa, flags, count ? c->qCounters.p : nullptr, st);
+    if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: kernel launch: %s", who, hipGetErrorString(e));
+    HIP_TRY(hipEventRecord(c->qEv[1], st));
+    c->qLastStream = st;
+    return RTR_OK;
+}
+
+int rtr_trace_rays_async(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, uint32_t n, uint32_t flags, RtrHit* hits, uint8_t* occluded) {
+    return enqueue_query(c, s, rays, n, flags, hits, occluded, false, "rtr_trace_rays_async");
+}
+
+int rtr_trace_rays(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, uint32_t n, uint32_t flags, RtrHit* hits, uint8_t* occluded, rtr_query_stats* stats) {
+    const int rc = enqueue_query(c, s, rays, n, flags, hits, occluded, stats != nullptr, "rtr_trace_rays");
+    if (rc != RTR_OK) return rc;
+    if (stats) memset(stats, 0, sizeof *stats);
+    if (n == 0) return RTR_OK;
+    hipStream_t st = c->stream;
+    if (stats) {      /* copies on the context's stream: the call joins that stream only */
+        Counters h;
+        uint32_t ctrl[rtrdev::kQueryCtrlWords];
+        HIP_TRY(hipMemcpyAsync(&h, c->qCounters.p, sizeof h, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(ctrl, c->qCtrl.p, sizeof ctrl, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        stats->numRays = h.rays; stats->numNodeVisits = h.nodes; stats->numTriTests = h.tris; stats->numAlphaTests = h.alphaTests;
+        stats->tailRays = ctrl[rtrdev::kQueryRedoWord];
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, c->qEv[0], c->qEv[1]));
+        stats->ms = ms;
+    } else HIP_TRY(hipStreamSynchronize(st));
+    return RTR_OK;
+}
+
+int rtr_camera_rays_async(rtr_ctx* c, const RtrCameraData* cam, uint32_t width, uint32_t height, uint32_t spp, RtrRay* out) {
+    if (!c || !cam || !out) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_camera_rays_async: null argument");
+    if (!aligned16(out)) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_camera_rays_async: out is not 16-B aligned");
+    if (width == 0 || height == 0 || spp == 0) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_camera_rays_async: extent %ux%u x %u spp", width, height, spp);
+    if ((uint64_t)width * height * spp > 0xffffffffull) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_camera_rays_async: %ux%u x %u spp is more than 2^32 - 1 rays", width, height, spp);
+    HIP_TRY(hipSetDevice(c->device));
+    const hipError_t e = rtrdev::launch_camera_rays(*cam, width, height, spp, reinterpret_cast<float4*>(out), c->stream);
+    if (e != hipSuccess) return fail(RTR_ERR_HIP, "rtr_camera_rays_async: kernel launch: %s", hipGetErrorString(e));
+    return RTR_OK;
 }
 
 }  // extern "C"

@@ -1,0 +1,464 @@
+"""Ray queries (rtr_trace_rays, rtr_camera_rays_async) on the device, against the CPU oracle: camera rays give the renderer's primary
+hits bit for bit, random rays the brute-force closest hit (oracle_mt over the exported triangle records, (t, customIndex, primitiveId)
+rule), occlusion agrees with the closest hit, deep rays take the tail kernel, and the counting form counts as the renderer does."""
+import ctypes as C
+import os
+import shutil
+
+import numpy as np
+import pytest
+import torch
+
+from realtimeraytracer_amd import _abi as A
+from realtimeraytracer_amd import api, host, scenes
+
+pytestmark = pytest.mark.gpu
+
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+MISS = 0xffffffff
+F3 = A.f32 * 3
+
+
+def _u32(x):
+    return np.asarray(x).astype(np.int64) & 0xffffffff
+
+
+def _tri_table(bvh):
+    """the exported triangle records as (n, 12) uint32 / float32 views"""
+    raw = np.frombuffer(bvh[1], dtype=np.uint32).reshape(-1, 12).copy()
+    return raw, raw.view(np.float32)
+
+
+def brute_force(oracle, bvh, rays, opaque=True):
+    """closest hit of each ray over every triangle record: oracle_mt (the kernels' Moeller-Trumbore) and t < tmax, the minimum over
+    (t, customIndex, primitiveId).  Only for scenes without alpha-tested geometry, or with opaque=True."""
+    raw, flt = _tri_table(bvh)
+    assert opaque or not (raw[:, 11] & 1).any()
+    L = oracle.lib()
+    tris = [(F3(*flt[j, 0:3]), F3(*flt[j, 4:7]), F3(*flt[j, 8:11]), int(raw[j, 3]), int(raw[j, 7])) for j in range(len(raw))]
+    n = len(rays)
+    t = np.zeros(n, np.float32); u = np.zeros(n, np.float32); v = np.zeros(n, np.float32)
+    cu = np.full(n, MISS, np.int64); pr = np.full(n, MISS, np.int64)
+    tuv = (A.f32 * 3)()
+    for k in range(n):
+        r = rays[k]
+        o, d, tmin, tmax = F3(*r[0:3]), F3(*r[4:7]), r[3], r[7]
+        t[k] = tmax
+        if not (tmax > tmin) or not np.isfinite(r[[0, 1, 2, 4, 5, 6]]).all() or not r[4:7].any():
+            continue
+        best = None
+        for v0, e1, e2, c, p in tris:
+            if L.oracle_mt(o, d, v0, e1, e2, float(tmin), tuv) and np.float32(tuv[0]) < tmax:
+                key = (np.float32(tuv[0]), c, p)
+                if best is None or key < best[0]:
+                    best = (key, np.float32(tuv[1]), np.float32(tuv[2]))
+        if best is not None:
+            (t[k], cu[k], pr[k]), u[k], v[k] = best[0], best[1], best[2]
+    return t, u, v, cu, pr
+
+
+def _np(x):
+    return x.cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+
+
+def assert_hits(res, exp, what):
+    t, u, v, cu, pr = exp
+    got = (_np(res.t), _np(res.u), _np(res.v), _u32(_np(res.custom_index)), _u32(_np(res.primitive_id)))
+    for name, g, e in zip(("t", "u", "v", "customIndex", "primitiveId"), got, (t, u, v, _u32(cu), _u32(pr))):
+        if g.dtype == np.float32:
+            bad = g.view(np.uint32) != np.asarray(e, np.float32).view(np.uint32)
+        else:
+            bad = g != e
+        if bad.any():
+            k = np.nonzero(bad)[0][:5]
+            raise AssertionError(f"{what}: {int(bad.sum())} of {len(g)} rays differ in {name}; first {k.tolist()}: gpu {g[k].tolist()} expected {np.asarray(e)[k].tolist()}")
+
+
+def random_rays(lo, hi, n, seed, tmax_scale):
+    rng = np.random.default_rng(seed)
+    lo, hi = np.asarray(lo, np.float64), np.asarray(hi, np.float64)
+    ext = hi - lo
+    o = lo + ext * rng.uniform(-0.2, 1.2, (n, 3))
+    d = rng.normal(size=(n, 3))
+    d /= np.linalg.norm(d, axis=1, keepdims=True)
+    tmin = rng.choice(np.array([0.0, 0.001, 0.5], np.float32), n)
+    tmax = rng.choice(np.array([10000.0, np.inf], np.float32), n).astype(np.float64)
+    part = rng.uniform(0, 1, n)
+    tmax = np.where(part < 0.3, rng.uniform(0.0, 1.0, n) * tmax_scale, tmax)         # short rays
+    tmax = np.where(part > 0.95, tmin - rng.uniform(0, 1, n), tmax)                   # tmax < tmin
+    tmax = np.where((part > 0.9) & (part <= 0.95), tmin, tmax)                         # tmax == tmin
+    r = np.zeros((n, 8), np.float32)
+    r[:, 0:3], r[:, 3], r[:, 4:7], r[:, 7] = o, tmin, d, tmax
+    return r
+
+
+def oracle_camera_hits(oracle, s, w, h, spp, bvh):
+    p = api.make_params(w, h, spp=spp)
+    t, u, v, cu, pr = oracle.primary_hits(s.desc, s.camera, p, bvh=bvh, threads=16)
+    return np.where(cu == MISS, np.float32(10000.0), t), u, v, cu.astype(np.int64), pr.astype(np.int64)
+
+
+# ---- 1. camera rays = the oracle's primary hits --------------------------------------------------------------------------------------
+@pytest.mark.parametrize("case", ["cornell_brute", "textured_room", "sponza_mixed"])
+def test_camera_rays_equal_the_oracle(gpu_ctx, oracle, scene_cache, case):
+    if case == "cornell_brute":
+        s, w, h, spp = scenes.cornell_box(256, 256), 256, 256, 2
+    elif case == "textured_room":
+        s, w, h, spp = scenes.textured_room(320, 200), 320, 200, 1
+    else:
+        s, w, h, spp = scenes.sponza_mixed(320, 180), 320, 180, 1
+    scene = api.Scene(gpu_ctx, s.desc)
+    rays = api.camera_rays(gpu_ctx, s.camera, w, h, spp)
+    assert rays.shape == (w * h * spp, 8) and rays.dtype == torch.float32
+    r = api.trace_rays(scene, rays)
+    exp = oracle_camera_hits(oracle, s, w, h, spp, None if case == "cornell_brute" else scene.export_bvh())
+    assert_hits(r, exp, case)
+    assert (np.asarray(exp[3]) != MISS).mean() > 0.3
+    rn = rays.cpu().numpy()
+    assert (rn[:, 3] == np.float32(0.001)).all() and (rn[:, 7] == np.float32(10000.0)).all()
+    assert (rn[:, 0:3] == np.array(s.camera.position[:], np.float32)).all()
+
+
+# ---- 2. random rays = brute force -------------------------------------------------------------------------------------------------
+def _features_setup(tmp_path):
+    for f in ("features.obj", "features.mtl"):
+        shutil.copy(os.path.join(GOLD, f), tmp_path / f)
+    os.makedirs(tmp_path / "textures", exist_ok=True)
+    for n in ("albedo", "spec", "metal", "alpha"):
+        scenes.write_png(str(tmp_path / "textures" / f"{n}.png"), np.full((4, 4, 3), 200, np.uint8))
+    cwd = os.getcwd()
+    os.chdir(tmp_path)
+    try:
+        hs = host.HostScene()
+        hs.addObjMtlPair("features.obj", "")
+        hs.setSky((0.5, 0.7, 1.0))
+        hs.build()
+    finally:
+        os.chdir(cwd)
+    return hs
+
+
+@pytest.mark.parametrize("case", ["cornell", "features_opaque"])
+def test_random_rays_equal_brute_force(gpu_ctx, oracle, scene_cache, tmp_path, case):
+    if case == "cornell":
+        hs, keep = None, scenes.cornell_box(64, 64)
+        desc, opaque = keep.desc, False
+    else:
+        hs = _features_setup(tmp_path)
+        desc, opaque = hs.desc, True
+    scene = api.Scene(gpu_ctx, desc)
+    st = scene.stats()
+    bvh = scene.export_bvh()
+    if not opaque:
+        assert not (np.frombuffer(bvh[1], dtype=np.uint32).reshape(-1, 12)[:, 11] & 1).any()
+    diag = float(np.linalg.norm(np.array(st.boundsMax[:]) - np.array(st.boundsMin[:])))
+    rays = random_rays(st.boundsMin[:], st.boundsMax[:], 3000, seed=7, tmax_scale=diag)
+    exp = brute_force(oracle, bvh, rays, opaque=True)
+    res = api.trace_rays(scene, rays, opaque=opaque)           # numpy in, numpy out
+    assert isinstance(res.t, np.ndarray)
+    assert_hits(res, exp, case)
+    found = exp[3] != MISS
+    assert 0.02 < found.mean() < 0.98
+    occ = api.trace_rays(scene, rays, any_hit=True, opaque=opaque).occluded
+    assert (occ == found).all()
+
+
+# ---- 3. minimality on a large scene ---------------------------------------------------------------------------------------------
+def test_minimality_on_sponza_class(gpu_ctx, oracle, scene_cache):
+    s = scenes.sponza_class(64, 64)
+    scene = api.Scene(gpu_ctx, s.desc)
+    st = scene.stats()
+    rays = random_rays(st.boundsMin[:], st.boundsMax[:], 1 << 20, seed=11, tmax_scale=3000.0)
+    rt = torch.from_numpy(rays).cuda()
+    r = api.trace_rays(scene, rt)
+    t = r.t.cpu().numpy(); cu = _u32(r.custom_index.cpu().numpy()); pr = _u32(r.primitive_id.cpu().numpy())
+    hit = cu != MISS
+    assert hit.mean() > 0.3
+    idx = np.nonzero(hit)[0]
+    below = rays[idx].copy(); below[:, 7] = t[idx]
+    at = rays[idx].copy(); at[:, 7] = np.nextafter(t[idx], np.float32(np.inf))
+    occ_below = api.trace_rays(scene, torch.from_numpy(below).cuda(), any_hit=True).occluded.cpu().numpy()
+    occ_at = api.trace_rays(scene, torch.from_numpy(at).cuda(), any_hit=True).occluded.cpu().numpy()
+    assert int(occ_below.sum()) == 0, "a hit nearer than the closest one"
+    assert occ_at.all(), f"{int((occ_at == 0).sum())} closest hits not found again with tmax just past them"
+    # the returned triangle gives exactly t*, u, v
+    raw, flt = _tri_table(scene.export_bvh())
+    keys = (raw[:, 3].astype(np.uint64) << np.uint64(32)) | raw[:, 7].astype(np.uint64)
+    order = np.argsort(keys)
+    L = oracle.lib()
+    u = r.u.cpu().numpy(); v = r.v.cpu().numpy()
+    tuv = (A.f32 * 3)()
+    for k in np.random.default_rng(3).choice(idx, 10000, replace=False):
+        key = (np.uint64(cu[k]) << np.uint64(32)) | np.uint64(pr[k])
+        j = order[np.searchsorted(keys, key, sorter=order)]
+        assert keys[j] == key
+        ry = rays[k]
+        assert L.oracle_mt(F3(*ry[0:3]), F3(*ry[4:7]), F3(*flt[j, 0:3]), F3(*flt[j, 4:7]), F3(*flt[j, 8:11]), float(ry[3]), tuv)
+        assert (np.float32(tuv[0]), np.float32(tuv[1]), np.float32(tuv[2])) == (t[k], u[k], v[k]), k
+
+
+# ---- 4. occlusion agrees with the closest hit --------------------------------------------------------------------------------------
+def test_any_hit_agrees_with_closest_hit_on_alpha_tested_geometry(gpu_ctx, scene_cache):
+    s = scenes.textured_room(160, 100)
+    scene = api.Scene(gpu_ctx, s.desc)
+    raw = np.frombuffer(scene.export_bvh()[1], dtype=np.uint32).reshape(-1, 12)
+    assert (raw[:, 11] & 1).any(), "the scene must hold alpha-tested triangles"
+    st = scene.stats()
+    rays = torch.cat([api.camera_rays(gpu_ctx, s.camera, 160, 100, 2),
+                      torch.from_numpy(random_rays(st.boundsMin[:], st.boundsMax[:], 200000, seed=5, tmax_scale=50.0)).cuda()])
+    closest = {}
+    for opaque in (False, True):
+        c = api.trace_rays(scene, rays, opaque=opaque)
+        a = api.trace_rays(scene, rays, any_hit=True, opaque=opaque)
+        found = (c.custom_index != -1).to(torch.uint8)
+        assert torch.equal(a.occluded, found), f"opaque={opaque}: {int((a.occluded != found).sum())} rays"
+        closest[opaque] = c
+    differ = closest[False].custom_index != closest[True].custom_index
+    assert int(differ.sum()) > 0, "skipping the opacity map must change some hits"
+    assert bool((closest[True].t <= closest[False].t).all())
+
+
+# ---- 5. deep rays ---------------------------------------------------------------------------------------------------------------
+def _deep_scene(ctx):
+    """the squeezed row of tests/test_gpu_parity.py (2^19 triangles 0.01 apart) whose camera rays, looking down its length from its
+    head, keep one pending far child per level of the ~20-level tree"""
+    N = 1 << 19
+    x = np.arange(N, dtype=np.float32) * np.float32(0.01)
+    tri = np.stack([np.stack([x, np.full(N, -1.0, np.float32), np.full(N, -0.3, np.float32)], 1),
+                    np.stack([x + np.float32(0.006), np.full(N, -1.0, np.float32), np.zeros(N, np.float32)], 1),
+                    np.stack([x, np.full(N, -1.0, np.float32), np.full(N, 0.3, np.float32)], 1)], 1).reshape(-1, 3)
+    wall = np.array([[N * 0.01 + 1.0, -4.0, -4.0], [N * 0.01 + 1.0, 4.0, -4.0], [N * 0.01 + 1.0, 0.0, 4.0]], np.float32)
+    verts = np.concatenate([wall, tri])
+    V = np.zeros((len(verts), 12), np.float32)
+    V[:, :3] = verts
+    idx = np.concatenate([np.array([0, 1, 2], np.uint32), np.arange(3 * N, dtype=np.uint32)])
+    meshes = (A.RtrMesh * 2)()
+    for m, (vo, io, vc, ic) in zip(meshes, [(0, 0, 3, 3), (3, 3, 3 * N, 3 * N)]):
+        m.vertexOffset, m.indexOffset, m.vertexCount, m.indexCount, m.isOpaque = vo, io, vc, ic, 1
+    inst = (A.RtrInstance * 2)()
+    for i, (mi, ci) in zip(inst, [(0, 0), (1, 1)]):
+        i.meshIndex, i.customIndex = mi, ci
+        for k, val in enumerate((1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0)):
+            i.transform[k] = float(val)
+    objs = (A.RtrObjectInfo * 2)()
+    for o, (vo, io) in zip(objs, [(0, 0), (3, 3)]):
+        o.vertexOffset, o.indexOffset = vo, io
+        o.color[0] = o.color[1] = o.color[2] = 0.8
+    d = A.rtr_scene_desc()
+    d.vertices = V.ctypes.data_as(C.POINTER(A.RtrVertex)); d.numVertices = len(V)
+    d.indices = idx.ctypes.data_as(C.POINTER(A.u32)); d.numIndices = len(idx)
+    d.meshes, d.numMeshes = meshes, 2
+    d.instances, d.numInstances = inst, 2
+    d.objects, d.numObjects = objs, 2
+    d.skyColor[0] = d.skyColor[1] = d.skyColor[2] = 0.5
+    keep = (V, idx, meshes, inst, objs)
+    scene = api.Scene(ctx, d)
+    assert scene.stats().maxDepth > 16
+    end = float(N) * 0.01
+    cam = host.Camera(0.004, (-30.0, -0.995, 0.0), (0.8 * end, -1.0, 0.0), (0.0, 1.0, 0.0), 16, 8).getGPUData()
+    return d, keep, scene, cam
+
+
+def test_deep_rays_take_the_tail_kernel(gpu_ctx, oracle):
+    d, keep, scene, cam = _deep_scene(gpu_ctx)
+    W, H, S = 16, 8, 2
+    rays = api.camera_rays(gpu_ctx, cam, W, H, S)
+    r = api.trace_rays(scene, rays, collect_stats=True)
+    assert r.stats.tailRays > 0 and r.stats.numRays == W * H * S
+    p = api.make_params(W, H, spp=S)
+    t, u, v, cu, pr = oracle.primary_hits(d, cam, p, bvh=None, threads=16)            # brute force
+    exp = (np.where(cu == MISS, np.float32(10000.0), t), u, v, cu.astype(np.int64), pr.astype(np.int64))
+    assert_hits(r, exp, "deep rays")
+    timed = api.trace_rays(scene, rays)
+    assert_hits(timed, exp, "deep rays, timed form")
+    occ = api.trace_rays(scene, rays, any_hit=True).occluded.cpu().numpy()
+    assert (occ == (cu != MISS)).all()
+    # a redo list of 4 entries: the tail kernel finds the abandoned rays by their sentinel (RTR_QUERY_REDO_CAP: librtr_hip_test.so only)
+    os.environ["RTR_QUERY_REDO_CAP"] = "4"
+    try:
+        hctx = api.Context(0, test_hooks=True)
+        hscene = api.Scene(hctx, d)
+        hr = api.trace_rays(hscene, rays, collect_stats=True)
+        assert hr.stats.tailRays > 4
+        assert_hits(hr, exp, "deep rays, redo list overflowed")
+        assert_hits(api.trace_rays(hscene, rays), exp, "deep rays, redo list overflowed, timed form")
+        hocc = api.trace_rays(hscene, rays, any_hit=True).occluded.cpu().numpy()
+        assert (hocc == occ).all()
+        hscene.close(); hctx.close()
+    finally:
+        del os.environ["RTR_QUERY_REDO_CAP"]
+
+
+# ---- 6. counters = the camera-ray share of a counting render -----------------------------------------------------------------------
+@pytest.mark.parametrize("case", ["cornell", "deep"])
+def test_counters_equal_the_renderers_camera_rays(gpu_ctx, oracle, scene_cache, case):
+    for name in ("primary_persist", "primary_packet", "primary_wide"):
+        assert gpu_ctx.get_tunable(name) == 0
+    if case == "cornell":
+        s = scenes.cornell_box(96, 64)
+        desc, cam, info, W, H, S = s.desc, s.camera, s.scene_info(0), 96, 64, 2
+        scene, keep = api.Scene(gpu_ctx, desc), None
+    else:
+        desc, keep, scene, cam = _deep_scene(gpu_ctx)
+        info, W, H, S = host.scene_info(0, 0, (-30.0, -0.995, 0.0)), 16, 8, 2
+    p = api.make_params(W, H, spp=S, collect_stats=1, pipeline=2)
+    frame = api.Frame(gpu_ctx, W, H)
+    api.render(scene, cam, info, p, frame)
+    g = frame.stats()
+    q = api.trace_rays(scene, api.camera_rays(gpu_ctx, cam, W, H, S), collect_stats=True).stats
+    assert q.numRays == g.numPrimaryRays == W * H * S
+    assert q.numNodeVisits == g.numNodeVisits - g.numShadowNodeVisits
+    assert q.numTriTests == g.numTriTests - g.numShadowTriTests
+    assert q.tailRays == g.primaryTailRays
+    assert (q.tailRays > 0) == (case == "deep")
+    ref = oracle.render(desc, cam, info, p, bvh=scene.export_bvh(), threads=16)
+    assert q.numNodeVisits == ref.stats.numNodeVisits - ref.stats.numShadowNodeVisits
+    assert q.numTriTests == ref.stats.numTriTests - ref.stats.numShadowTriTests
+    assert q.tailRays == ref.stats.primaryTailRays
+    assert q.ms > 0.0
+
+
+# ---- 7. dynamic scenes ----------------------------------------------------------------------------------------------------------
+def test_queries_see_moved_instances(gpu_ctx, oracle, scene_cache):
+    s = scenes.cornell_box(64, 64)
+    scene = api.Scene(gpu_ctx, s.desc)
+    st = scene.stats()
+    rays = random_rays(st.boundsMin[:], st.boundsMax[:], 1500, seed=21, tmax_scale=1500.0)
+    before = api.trace_rays(scene, rays)
+    inst = [A.RtrInstance.from_buffer_copy(s.desc.instances[i]) for i in range(s.desc.numInstances)]
+    for k, i in enumerate(inst):
+        if i.customIndex >= s.num_lights:
+            i.transform[3] += 40.0 * (k % 3)
+            i.transform[7] -= 25.0 * (k % 2)
+    scene.update_instances(inst)
+    after = api.trace_rays(scene, rays)
+    assert_hits(after, brute_force(oracle, scene.export_bvh(), rays), "after update_instances")
+    assert (after.t != before.t).any()
+
+
+# ---- 8. plumbing ----------------------------------------------------------------------------------------------------------------
+def test_asynchronous_queries_on_torchs_stream(scene_cache):
+    s = scenes.cornell_box(128, 128)
+    ctx = api.Context(0)
+    scene = api.Scene(ctx, s.desc)
+    ref = api.trace_rays(scene, api.camera_rays(ctx, s.camera, 128, 128, 1))
+    refo = api.trace_rays(scene, api.camera_rays(ctx, s.camera, 128, 128, 1), any_hit=True).occluded.clone()
+    stream = torch.cuda.Stream()
+    with torch.cuda.stream(stream):
+        ctx.set_stream(stream.cuda_stream)
+        rays = api.camera_rays(ctx, s.camera, 128, 128, 1)
+        rays = rays * 1.0                                     # torch work on the stream between the two calls
+        r = api.trace_rays(scene, rays, asynchronous=True)
+        o = api.trace_rays(scene, rays, any_hit=True, asynchronous=True)
+        t = r.t * 1.0                                         # consumed on the same stream, no host join in between
+        stream.synchronize()
+        assert torch.equal(t, ref.t) and torch.equal(r.custom_index, ref.custom_index) and torch.equal(r.primitive_id, ref.primitive_id)
+        assert torch.equal(o.occluded, refo)
+        with pytest.raises(ValueError):
+            api.trace_rays(scene, rays, asynchronous=True, collect_stats=True)
+        ctx.set_stream(None)
+    with pytest.raises(ValueError):
+        api.trace_rays(scene, rays, asynchronous=True)        # the context is no longer on torch's current stream
+    scene.close(); ctx.close()
+
+
+def test_launch_larger_than_the_redo_list(gpu_ctx, scene_cache):
+    s = scenes.cornell_box(64, 64)
+    scene = api.Scene(gpu_ctx, s.desc)
+    st = scene.stats()
+    rays = torch.from_numpy(random_rays(st.boundsMin[:], st.boundsMax[:], 300000, seed=9, tmax_scale=1500.0)).cuda()
+    whole = api.trace_rays(scene, rays)
+    for lo in range(0, 300000, 50000):
+        part = api.trace_rays(scene, rays[lo:lo + 50000])
+        for f in ("t", "u", "v", "custom_index", "primitive_id"):
+            assert torch.equal(getattr(whole, f)[lo:lo + 50000], getattr(part, f)), f
+
+
+def test_degenerate_rays_are_misses(gpu_ctx, scene_cache):
+    s = scenes.cornell_box(64, 64)
+    scene = api.Scene(gpu_ctx, s.desc)
+    nan, inf = np.float32(np.nan), np.float32(np.inf)
+    base = [278.0, 273.0, -800.0, 0.001, 0.0, 0.0, 1.0, 10000.0]       # this one hits the back wall
+    bad = [[nan, 273.0, -800.0, 0.001, 0.0, 0.0, 1.0, 10000.0], [278.0, 273.0, -800.0, 0.001, nan, 0.0, 1.0, 10000.0],
+           [278.0, 273.0, -800.0, 0.001, 0.0, 0.0, 0.0, 10000.0], [278.0, 273.0, -800.0, 0.001, 0.0, 0.0, inf, 10000.0],
+           [278.0, 273.0, -inf, 0.001, 0.0, 0.0, 1.0, 10000.0], [278.0, 273.0, -800.0, 0.001, 0.0, 0.0, 1.0, nan],
+           [278.0, 273.0, -800.0, nan, 0.0, 0.0, 1.0, 10000.0], [278.0, 273.0, -800.0, 5.0, 0.0, 0.0, 1.0, 5.0]]
+    rays = np.array([base] + bad, np.float32)
+    r = api.trace_rays(scene, torch.from_numpy(rays).cuda())
+    ci = r.custom_index.cpu().numpy()
+    assert ci[0] != -1
+    assert (ci[1:] == -1).all() and (r.primitive_id.cpu().numpy()[1:] == -1).all()
+    assert (r.u.cpu().numpy()[1:] == 0).all() and (r.v.cpu().numpy()[1:] == 0).all()
+    assert (r.t.cpu().numpy()[1:].view(np.uint32) == rays[1:, 7].view(np.uint32)).all()      # t = the ray's tmax
+    assert (r._keep[1][:, 5:8].cpu().numpy() == 0).all()                                      # reserved words
+    occ = api.trace_rays(scene, torch.from_numpy(rays).cuda(), any_hit=True).occluded.cpu().numpy()
+    assert occ[0] == 1 and (occ[1:] == 0).all()
+
+
+def test_invalid_arguments(gpu_ctx, scene_cache):
+    s = scenes.cornell_box(64, 64)
+    scene = api.Scene(gpu_ctx, s.desc)
+    lib, ctx = gpu_ctx.lib, gpu_ctx.h
+    rays = api.camera_rays(gpu_ctx, s.camera, 8, 8, 1)
+    hits = torch.empty((64, 8), dtype=torch.int32, device="cuda")
+    occ = torch.empty(64 + 16, dtype=torch.uint8, device="cuda")
+    rp, hp, op = A.VP(rays.data_ptr()), A.VP(hits.data_ptr()), A.VP(occ.data_ptr())
+    INVALID = -1
+    assert lib.rtr_trace_rays(ctx, scene.h, None, 64, 0, hp, None, None) == INVALID                     # no rays
+    assert lib.rtr_trace_rays(ctx, scene.h, rp, 64, 0, None, op, None) == INVALID                       # closest hit without hits
+    assert lib.rtr_trace_rays(ctx, scene.h, rp, 64, A.QUERY_ANY, hp, None, None) == INVALID             # any hit without occluded
+    assert lib.rtr_trace_rays(ctx, scene.h, A.VP(rays.data_ptr() + 4), 64, 0, hp, None, None) == INVALID
+    assert lib.rtr_trace_rays(ctx, scene.h, rp, 64, 0, A.VP(hits.data_ptr() + 8), None, None) == INVALID
+    assert lib.rtr_trace_rays(ctx, scene.h, rp, 64, A.QUERY_ANY, None, A.VP(occ.data_ptr() + 1), None) == INVALID
+    assert lib.rtr_trace_rays_async(ctx, scene.h, rp, 64, 4, hp, None) == INVALID                       # unknown flag bit
+    assert b"flag" in lib.rtr_last_error()
+    assert lib.rtr_trace_rays_async(None, scene.h, rp, 64, 0, hp, None) == INVALID
+    assert lib.rtr_camera_rays_async(ctx, C.byref(s.camera), 8, 8, 1, A.VP(rays.data_ptr() + 4)) == INVALID
+    assert lib.rtr_camera_rays_async(ctx, C.byref(s.camera), 0, 8, 1, rp) == INVALID
+    assert lib.rtr_camera_rays_async(ctx, C.byref(s.camera), 65536, 65536, 1, rp) == INVALID
+    assert lib.rtr_trace_rays(ctx, scene.h, None, 0, 0, None, None, None) == 0                          # no rays: nothing to do
+    if torch.cuda.device_count() > 1:
+        other = api.Context(1)
+        assert lib.rtr_trace_rays(other.h, scene.h, rp, 64, 0, hp, None, None) == INVALID               # scene on another device
+        other.close()
+    # the Python layer refuses before anything is launched
+    for bad in (rays[:, :7].contiguous(), rays.double(), rays.cpu(), rays.t().contiguous().t(), rays[:, 0]):
+        with pytest.raises(ValueError):
+            api.trace_rays(scene, bad)
+    with pytest.raises(ValueError):
+        api.trace_rays(scene, rays.cpu().numpy().astype(np.float64))
+
+
+# ---- exact ties in t ------------------------------------------------------------------------------------------------------------
+def test_exact_ties_keep_the_smallest_ids_with_their_own_barycentrics(gpu_ctx, oracle):
+    """Every hit is a tie: one quad instanced twice at the same place (customIndex 0 and 1), split along a diagonal the rays also hit.
+    The record must be one triangle's, whole: the (t, customIndex, primitiveId)-smallest, with its own u, v."""
+    V = np.zeros((4, 12), np.float32)
+    V[:, :3] = [[-1, -1, 0], [1, -1, 0], [1, 1, 0], [-1, 1, 0]]
+    idx = np.array([0, 1, 2, 0, 2, 3], np.uint32)
+    meshes = (A.RtrMesh * 1)()
+    meshes[0].vertexCount, meshes[0].indexCount, meshes[0].isOpaque = 4, 6, 1
+    inst = (A.RtrInstance * 2)()
+    for c in range(2):
+        inst[c].meshIndex, inst[c].customIndex = 0, c
+        for k, val in enumerate((1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0)):
+            inst[c].transform[k] = float(val)
+    objs = (A.RtrObjectInfo * 2)()
+    d = A.rtr_scene_desc()
+    d.vertices = V.ctypes.data_as(C.POINTER(A.RtrVertex)); d.numVertices = 4
+    d.indices = idx.ctypes.data_as(C.POINTER(A.u32)); d.numIndices = 6
+    d.meshes, d.numMeshes = meshes, 1
+    d.instances, d.numInstances = inst, 2
+    d.objects, d.numObjects = objs, 2
+    scene = api.Scene(gpu_ctx, d)
+    rng = np.random.default_rng(17)
+    n = 4096
+    target = rng.uniform(-0.9, 0.9, (n, 2)).astype(np.float32)
+    target[: n // 4, 1] = target[: n // 4, 0]                    # on the shared diagonal: four triangles tie
+    rays = np.zeros((n, 8), np.float32)
+    rays[:, 0:2], rays[:, 2], rays[:, 3] = rng.uniform(-0.5, 0.5, (n, 2)), -5.0, 0.0
+    rays[:, 4:6], rays[:, 6], rays[:, 7] = target - rays[:, 0:2], 5.0, 10000.0
+    res = api.trace_rays(scene, torch.from_numpy(rays).cuda())
+    assert_hits(res, brute_force(oracle, scene.export_bvh(), rays), "ties")
+    ci = _np(res.custom_index)
+    assert ((ci == 0) | (ci == -1)).all() and (ci == 0).mean() > 0.9      # Moeller-Trumbore is not watertight: a ray exactly on an edge may miss both sides

@@ -382,6 +382,17 @@ int  rtr_trace_rays(rtr_ctx* ctx, const rtr_scene* scene, const RtrRay* rays, ui
  * RTR_ERR_INVALID_ARGUMENT for a null or unaligned pointer, a zero extent or more than 2^32 - 1 rays. */
 int  rtr_camera_rays_async(rtr_ctx* ctx, const RtrCameraData* camera, uint32_t width, uint32_t height, uint32_t spp, RtrRay* out);
 
+/* What the closest-hit shader computes for numRays hits[] of rays[] (a closest-hit query's results, or hits of the caller's own): out[k]
+ * is the RtrSurface of hits[k], by the renderer's own surface fetch (closesthit.rchit:53-106, raygen.rgen:110-121, miss.rmiss:15-27),
+ * with the scene's current instance transforms.  rays[k] gives the direction the normal is turned against and the miss looks up.
+ * rays, hits and out are DEVICE pointers, 16-B aligned.  The work is ENQUEUED on ctx's stream; the scene may belong to another context
+ * of the same device.  numRays == 0 does nothing.  A hit whose ids are out of range gives RTR_SURFACE_INVALID and reads nothing there.
+ * RTR_ERR_INVALID_ARGUMENT (with a message) for a null or unaligned pointer or a scene on another device. */
+int  rtr_hit_surfaces_async(rtr_ctx* ctx, const rtr_scene* scene, const RtrRay* rays, const RtrHit* hits, uint32_t numRays,
+                            RtrSurface* out);
+/* The same, then joins ctx's stream (only that stream). */
+int  rtr_hit_surfaces(rtr_ctx* ctx, const rtr_scene* scene, const RtrRay* rays, const RtrHit* hits, uint32_t numRays, RtrSurface* out);
+
 /* ---- errors --------------------------------------------------------------------------- */
 const char* rtr_last_error(void);
 const char* rtr_status_string(int status);

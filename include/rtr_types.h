@@ -185,6 +185,31 @@ typedef struct RtrHit {
     uint32_t _reserved[3];
 } RtrHit;
 
+/* ---- hit surfaces (rtr_hit_surfaces): what the closest-hit shader computes for one RtrHit ----------------------------------
+ * closesthit.rchit:53-106 for an object, and the light-hit and miss rules of raygen.rgen:110-121 / miss.rmiss:15-27.  80 B, so a lane
+ * writes its record as five 16-B stores.  Per kind:
+ *   RTR_SURFACE_OBJECT   position, normal, color (linear), roughness, metallic: the renderer's hit point, shading normal (with its
+ *                        geometric fallback, turned against the ray), colour and material; uv: the interpolated texture coordinate;
+ *                        geomNormal: normalize(nmat * normalize(cross(p1 - p0, p2 - p0))), as wound, never turned.
+ *                        objectIndex = customIndex - numLights (the ObjectInfo row).
+ *   RTR_SURFACE_LIGHT    color: the light's colour; position: (u, v) over the light triangle's world-space corners; normal = geomNormal:
+ *                        that triangle's unit normal; the other floats 0.  objectIndex = the light index.
+ *   RTR_SURFACE_MISS     color: the sky radiance in the ray's direction (HDRI or the constant sky); every other float 0.
+ *   RTR_SURFACE_INVALID  a customIndex that is neither, or a primitiveId past the instance's (light's) triangles: every float 0.
+ * objectIndex is 0xffffffff for MISS and INVALID; _reserved is written as 0. */
+#define RTR_SURFACE_MISS    0u
+#define RTR_SURFACE_OBJECT  1u
+#define RTR_SURFACE_LIGHT   2u
+#define RTR_SURFACE_INVALID 3u
+
+typedef struct RtrSurface {
+    float    position[3];   uint32_t kind;
+    float    normal[3];     uint32_t objectIndex;
+    float    geomNormal[3]; float    metallic;
+    float    color[3];      float    roughness;
+    float    uv[2];         uint32_t _reserved[2];
+} RtrSurface;
+
 #ifdef __cplusplus
 }
 #endif
@@ -202,6 +227,7 @@ static_assert(sizeof(RtrBvhTri) == 48, "BVH triangle must be 48 B");
 static_assert(sizeof(RtrWideNode) == 64, "wide node must be 64 B");
 static_assert(sizeof(RtrRay) == 32, "ray must be 32 B");
 static_assert(sizeof(RtrHit) == 32, "hit must be 32 B");
+static_assert(sizeof(RtrSurface) == 80, "surface must be 80 B");
 #endif
 
 #endif /* RTR_TYPES_H */

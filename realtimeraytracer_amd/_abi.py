@@ -71,6 +71,11 @@ class RtrHit(C.Structure):
     _fields_ = [("t", f32), ("u", f32), ("v", f32), ("customIndex", u32), ("primitiveId", u32), ("_reserved", u32 * 3)]
 
 
+class RtrSurface(C.Structure):
+    _fields_ = [("position", f32 * 3), ("kind", u32), ("normal", f32 * 3), ("objectIndex", u32), ("geomNormal", f32 * 3), ("metallic", f32),
+                ("color", f32 * 3), ("roughness", f32), ("uv", f32 * 2), ("_reserved", u32 * 2)]
+
+
 class rtr_texture(C.Structure):
     _fields_ = [("pixels", C.POINTER(C.c_uint8)), ("width", u32), ("height", u32), ("channels", u32), ("_pad", u32)]
 
@@ -121,6 +126,7 @@ assert C.sizeof(RtrVertex) == 48 and C.sizeof(RtrCameraData) == 64 and C.sizeof(
 assert C.sizeof(RtrObjectInfo) == 80 and C.sizeof(RtrAreaLightInfo) == 96
 assert C.sizeof(RtrBvhNode) == 32 and C.sizeof(RtrBvhGrid) == 32 and C.sizeof(RtrBvhTri) == 48 and C.sizeof(RtrWideNode) == 64
 assert C.sizeof(RtrRay) == 32 and C.sizeof(RtrHit) == 32 and C.sizeof(rtr_query_stats) == 48
+assert C.sizeof(RtrSurface) == 80
 
 # enum rtr_image
 IMAGE_ANALYTIC, IMAGE_SHADOWED, IMAGE_UNSHADOWED = 0, 1, 2
@@ -137,6 +143,7 @@ IMAGES_RAYGEN5 = IMG_BIT(0) | IMG_BIT(1) | IMG_BIT(2) | IMG_BIT(6) | IMG_BIT(7)
 IMAGES_DENOISE = IMG_BIT(3) | IMG_BIT(4) | IMG_BIT(5)
 BUILD_HOST_SAH, BUILD_DEVICE_LBVH = 0, 1
 QUERY_CLOSEST, QUERY_ANY, QUERY_OPAQUE = 0, 1, 2
+SURFACE_MISS, SURFACE_OBJECT, SURFACE_LIGHT, SURFACE_INVALID = 0, 1, 2, 3
 
 P = C.POINTER
 VP = C.c_void_p
@@ -187,6 +194,8 @@ RTR_SYMBOLS = {
     "rtr_trace_rays_async": (C.c_int, [VP, VP, VP, u32, u32, VP, VP]),
     "rtr_trace_rays": (C.c_int, [VP, VP, VP, u32, u32, VP, VP, P(rtr_query_stats)]),
     "rtr_camera_rays_async": (C.c_int, [VP, P(RtrCameraData), u32, u32, u32, VP]),
+    "rtr_hit_surfaces_async": (C.c_int, [VP, VP, VP, VP, u32, VP]),
+    "rtr_hit_surfaces": (C.c_int, [VP, VP, VP, VP, u32, VP]),
 }
 
 RTRH_SYMBOLS = {

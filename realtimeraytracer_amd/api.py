@@ -260,8 +260,9 @@ def host_build_bvh_wide(desc):
 # ---- ray queries (rtr_trace_rays, rtr_camera_rays_async) ----------------------------------------------------------------------------
 class QueryResult:
     """What trace_rays gives back.  Closest hit: t, u, v (float32), custom_index, primitive_id (int32, -1 for a miss; t = the ray's tmax
-    then).  Any hit: occluded (uint8, 1 = occluded).  The other fields are None.  stats: rtr_query_stats of the counting form, or None."""
-    t = u = v = custom_index = primitive_id = occluded = stats = None
+    then).  Any hit: occluded (uint8, 1 = occluded).  The other fields are None.  stats: rtr_query_stats of the counting form, or None.
+    hits: the closest-hit records themselves, an (N, 8) int32 array of RtrHit (what hit_surfaces takes), or None."""
+    t = u = v = custom_index = primitive_id = occluded = stats = hits = None
 
 
 def _torch():
@@ -331,8 +332,9 @@ def trace_rays(scene, rays, any_hit=False, opaque=False, collect_stats=False, ct
         f = hits.view(torch.float32)
         out.t, out.u, out.v = f[:, 0], f[:, 1], f[:, 2]
         out.custom_index, out.primitive_id = hits[:, 3], hits[:, 4]
+        out.hits = hits
     if as_numpy:
-        for k in ("t", "u", "v", "custom_index", "primitive_id", "occluded"):
+        for k in ("t", "u", "v", "custom_index", "primitive_id", "occluded", "hits"):
             x = getattr(out, k)
             if x is not None:
                 setattr(out, k, x.cpu().numpy())
@@ -353,3 +355,67 @@ def camera_rays(ctx, camera, width, height, spp=1):
            "rtr_camera_rays_async")
     _join_ctx_stream(ctx, torch, dev)
     return out
+
+
+class SurfaceResult:
+    """What hit_surfaces gives back: views into one (N, 20) array of RtrSurface records (raw, float32).  position, normal, geom_normal,
+    color (N, 3) and roughness, metallic (N,) and uv (N, 2) are float32; kind (A.SURFACE_*) and object_index (the ObjectInfo row of an
+    object, the light index of a light, -1 otherwise) are int32."""
+    raw = position = normal = geom_normal = color = roughness = metallic = uv = kind = object_index = None
+
+
+def _device_array(torch, x, dtype, np_dtype, name, dev, who):
+    """an (N, 8) array of 32-bit words on dev: a device tensor as it is (checked), a numpy array copied there"""
+    if isinstance(x, np.ndarray):
+        if x.dtype != np_dtype or x.ndim != 2 or x.shape[1] != 8:
+            raise ValueError(f"{who}: {name} must be {np.dtype(np_dtype)} (N, 8), got {x.dtype} {x.shape}")
+        return torch.from_numpy(np.ascontiguousarray(x)).to(dev), True
+    if isinstance(x, torch.Tensor):
+        if x.dtype != dtype or x.dim() != 2 or x.shape[1] != 8:
+            raise ValueError(f"{who}: {name} must be {dtype} (N, 8), got {x.dtype} {tuple(x.shape)}")
+        if x.device != dev:
+            raise ValueError(f"{who}: {name} live on {x.device}, the context on {dev}")
+        if not x.is_contiguous():
+            raise ValueError(f"{who}: {name} must be contiguous")
+        return x, False
+    raise ValueError(f"{who}: {name} must be a torch tensor or a numpy array, got {type(x).__name__}")
+
+
+def hit_surfaces(scene, rays, hits, ctx=None, asynchronous=False):
+    """rtr_hit_surfaces: what the closest-hit shader computes for each hit.  rays: as trace_rays takes them (float32 (N, 8)); hits: the
+    QueryResult of a closest-hit trace_rays or its (N, 8) int32 RtrHit records.  Device tensors give device results without a copy; numpy
+    in gives numpy out (both must then be numpy).  ctx and asynchronous as in trace_rays: an asynchronous call needs the context on
+    torch's current stream.  Wrong shape, dtype, device, layout or a length mismatch raises ValueError before anything is launched."""
+    torch = _torch()
+    ctx = ctx or scene.ctx
+    dev = torch.device("cuda", ctx.device)
+    if isinstance(hits, QueryResult):
+        if hits.hits is None:
+            raise ValueError("hit_surfaces: the QueryResult holds no hit records (an any-hit query)")
+        hits = hits.hits
+    r, rn = _device_array(torch, rays, torch.float32, np.float32, "rays", dev, "hit_surfaces")
+    h, hn = _device_array(torch, hits, torch.int32, np.int32, "hits", dev, "hit_surfaces")
+    if rn != hn:
+        raise ValueError("hit_surfaces: rays and hits must both be numpy arrays or both be tensors")
+    if r.shape[0] != h.shape[0]:
+        raise ValueError(f"hit_surfaces: {r.shape[0]} rays but {h.shape[0]} hits")
+    if asynchronous and ctx.get_stream() != torch.cuda.current_stream(dev).cuda_stream:
+        raise ValueError("hit_surfaces: an asynchronous call needs the context on torch's current stream (ctx.set_stream)")
+    n = int(r.shape[0])
+    out = torch.empty((n, 20), dtype=torch.float32, device=dev)
+    if not asynchronous and ctx.get_stream() != torch.cuda.current_stream(dev).cuda_stream:
+        torch.cuda.current_stream(dev).synchronize()        # the inputs (and the output's memory) are ready for the context's stream
+    args = (A.VP(r.data_ptr()), A.VP(h.data_ptr()), n, A.VP(out.data_ptr())) if n else (None, None, 0, None)
+    if asynchronous:
+        _check(ctx.lib.rtr_hit_surfaces_async(ctx.h, scene.h, *args), "rtr_hit_surfaces_async")
+    else:
+        _check(ctx.lib.rtr_hit_surfaces(ctx.h, scene.h, *args), "rtr_hit_surfaces")
+    raw = out.cpu().numpy() if rn else out
+    words = raw.view(np.int32) if rn else raw.view(torch.int32)
+    res = SurfaceResult()
+    res.raw = raw
+    res.position, res.normal, res.geom_normal, res.color = raw[:, 0:3], raw[:, 4:7], raw[:, 8:11], raw[:, 12:15]
+    res.metallic, res.roughness, res.uv = raw[:, 11], raw[:, 15], raw[:, 16:18]
+    res.kind, res.object_index = words[:, 3], words[:, 7]
+    res._keep = (r, h)                   # an asynchronous call's inputs stay alive with its result
+    return res

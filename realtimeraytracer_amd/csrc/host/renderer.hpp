@@ -84,4 +84,10 @@ inline void camera_rays(const Context& ctx, const RtrCameraData& cam, uint32_t w
     check(rtr_camera_rays_async(ctx.get(), &cam, width, height, spp, out), "rtr_camera_rays_async");
 }
 
+// what the closest-hit shader computes for hits[k] of rays[k] (include/rtr.h: rtr_hit_surfaces); all DEVICE arrays.
+// Synchronous: returns when out[] is in place.
+inline void hit_surfaces(const Context& ctx, const Scene& scene, const RtrRay* rays, const RtrHit* hits, uint32_t numRays, RtrSurface* out) {
+    check(rtr_hit_surfaces(ctx.get(), scene.get(), rays, hits, numRays, out), "rtr_hit_surfaces");
+}
+
 }  // namespace rtr

@@ -1772,7 +1772,8 @@ __global__ __launch_bounds__(kBlock) void k_deinterleave(const uint32_t* __restr
     }
 }
 
-/* One lane per light: the world-space corners, area, pdf and unit normal of its triangles (read by light_loops in every pixel). */
+/* One lane per light: the world-space corners, area, pdf and unit normal of its triangles (read by light_loops in every pixel).  Record
+ * first[l] + ti is triangle ti of the light's index range: a light's records are in primitiveId order (rtr_hit_surfaces relies on it). */
 __global__ __launch_bounds__(64) void k_light_tris(const RtrAreaLightInfo* __restrict__ lights, const RtrVertex* __restrict__ vertices,
                                                    const uint32_t* __restrict__ indices, const uint32_t* __restrict__ first,
                                                    uint32_t numLights, float4* __restrict__ out) {

@@ -22,9 +22,22 @@ struct QueryArgs {
     int32_t* spill;              /* kSpillInts: the tail kernel's full-depth stacks */
 };
 
+/* Arguments of the hit-surface kernel (rtr_hit_surfaces).  The triangle counts live here, not in DeviceScene, which every other kernel
+ * takes by value. */
+struct SurfaceArgs {
+    const float4* rays;          /* RtrRay as 2 x float4: {origin, tmin} {direction, tmax} */
+    const float4* hits;          /* RtrHit as 2 x float4: {t, u, v, customIndex} {primitiveId, -, -, -} */
+    float4* out;                 /* RtrSurface as 5 x float4 */
+    const uint32_t* triCount;    /* per customIndex: the triangles of the light (customIndex < numLights) or of the instance's mesh */
+    uint32_t numInstances;       /* entries of triCount */
+    uint32_t n;
+};
+
 /* flags: RTR_QUERY_ANY | RTR_QUERY_OPAQUE (validated by the caller).  stats: the counting form, counters added there (zeroed by the caller). */
 hipError_t launch_query(const DeviceScene& sc, const QueryArgs& qa, uint32_t flags, Counters* stats, hipStream_t stream);
 /* width * height * spp camera rays of raygen.rgen:83-107, ray k = (py * width + px) * spp + i (< 2^32, checked by the caller) */
 hipError_t launch_camera_rays(const RtrCameraData& cam, uint32_t width, uint32_t height, uint32_t spp, float4* out, hipStream_t stream);
+/* one RtrSurface per hit: the renderer's surface fetch (fetch_surface) for caller hits */
+hipError_t launch_hit_surfaces(const DeviceScene& sc, const SurfaceArgs& sa, hipStream_t stream);
 
 }  // namespace rtrdev

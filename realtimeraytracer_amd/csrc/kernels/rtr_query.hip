@@ -10,6 +10,7 @@
  *                 per wave (ballot + mbcnt prefix);
  *   k_query_tail  walks those rays again with a full-depth stack in global memory (as k_primary_tail does); if the redo list
  *                 overflowed it finds them by their sentinel in the outputs.
+ * k_hit_surfaces (rtr_hit_surfaces) takes the hits further: the surface the closest-hit shader computes for each, by fetch_surface().
  * Compiled with the library's flags (-ffp-contract=off): the numerical contract of include/rtr_math.h.
  */
 #include "rtr_query.h"
@@ -153,6 +154,72 @@ hipError_t launch_camera_rays(const RtrCameraData& cam, uint32_t width, uint32_t
     ra.cam = cam; ra.width = width; ra.height = height; ra.spp = spp;
     const uint32_t n = width * height * spp;
     hipLaunchKernelGGL(k_camera_rays, dim3((uint32_t)(((uint64_t)n + kCameraRaysBlock - 1) / kCameraRaysBlock)), dim3(kCameraRaysBlock), 0, s, ra, n, out);
+    return hipGetLastError();
+}
+
+/* One lane per hit: what the closest-hit shader computes for it (rtr_hit_surfaces).  The surface is fetch_surface<true>'s, the one the
+ * renderer shades with, called without the LTC lookups (wantAnalytic = false): hit point, shading normal, linear colour and material
+ * for an object; the light's colour at a light hit and the sky radiance at a miss, read from the Accum it adds them to.  uv and the
+ * geometric normal come next to it, in the same rtr_math.h forms.  Ids out of range are INVALID and read nothing of the scene. */
+constexpr int kSurfaceBlock = 256;
+__global__ __launch_bounds__(kSurfaceBlock) void k_hit_surfaces(DeviceScene sc, SurfaceArgs sa) {
+    const uint32_t k = blockIdx.x * kSurfaceBlock + threadIdx.x;
+    if (k >= sa.n) return;
+    const float4 rb = sa.rays[2 * (size_t)k + 1];                                   /* {direction, tmax}: the origin is not needed */
+    const float4 ha = sa.hits[2 * (size_t)k], hb = sa.hits[2 * (size_t)k + 1];
+    HitRec h;
+    h.t = ha.x; h.u = ha.y; h.v = ha.z; h.custom = __float_as_uint(ha.w); h.prim = __float_as_uint(hb.x); h.leaf = 0;
+    const rtr_v3 dir = f4xyz(rb);
+    uint32_t kind = RTR_SURFACE_INVALID, index = 0xffffffffu;
+    if (h.custom == RTR_MISS) kind = RTR_SURFACE_MISS;
+    else if (h.custom < sa.numInstances && h.prim < sa.triCount[h.custom]) {
+        kind = h.custom < sc.numLights ? RTR_SURFACE_LIGHT : RTR_SURFACE_OBJECT;
+        index = h.custom < sc.numLights ? h.custom : h.custom - sc.numLights;
+    }
+    const rtr_v3 zero = rtr_mk(0, 0, 0);
+    rtr_v3 position = zero, normal = zero, geomNormal = zero, color = zero;
+    float metallic = 0.0f, roughness = 0.0f, uu = 0.0f, vv = 0.0f;
+    if (kind != RTR_SURFACE_INVALID) {
+        RenderArgs ra{};                     /* fetch_surface reads only the camera position, for a view vector this kernel does not output */
+        Accum acc;
+        acc.analytic = acc.shadowed = acc.unshadowed = acc.avgNormal = acc.avgPosition = zero;
+        Surface sf;
+        LocalStats st;
+        fetch_surface<true, false>(sc, ra, h, dir, false, acc, sf, st);
+        const float b0 = 1.0f - h.u - h.v, b1 = h.u, b2 = h.v;
+        if (kind == RTR_SURFACE_OBJECT) {
+            position = sf.hitPoint; normal = sf.hitNormal; color = sf.color; metallic = sf.metallic; roughness = sf.roughness;
+            const RtrObjectInfo* oi = sc.objects + index;
+            const uint32_t vOff = oi->vertexOffset, iOff = oi->indexOffset;
+            const float4* va = reinterpret_cast<const float4*>(sc.vertices + (sc.indices[3u * h.prim + 0u + iOff] + vOff));
+            const float4* vb = reinterpret_cast<const float4*>(sc.vertices + (sc.indices[3u * h.prim + 1u + iOff] + vOff));
+            const float4* vc = reinterpret_cast<const float4*>(sc.vertices + (sc.indices[3u * h.prim + 2u + iOff] + vOff));
+            const rtr_v3 p0 = f4xyz(va[0]), p1 = f4xyz(vb[0]), p2 = f4xyz(vc[0]);
+            const rtr_v3 g = rtr_cross(rtr_sub(p1, p0), rtr_sub(p2, p0));
+            geomNormal = rtr_normalize(rtr_mul33(sc.nmats + 12u * h.custom, rtr_normalize(g)));
+            const float4 ta = va[2], tb = vb[2], tc = vc[2];                       /* uv in floats 8,9 of the 48-B vertex */
+            uu = rtr_fma(tc.x, b2, rtr_fma(tb.x, b1, ta.x * b0));
+            vv = rtr_fma(tc.y, b2, rtr_fma(tb.y, b1, ta.y * b0));
+        } else {
+            color = acc.shadowed;                                                    /* the sky at a miss, the light's colour at a light */
+            if (kind == RTR_SURFACE_LIGHT) {
+                /* k_light_tris writes light l's records at lightTriFirst[l] + primitiveId (triangle ti of the light's index range) */
+                const float4* rec = sc.lightTris + (size_t)(sc.lightTriFirst[index] + h.prim) * kLightTriRecord;
+                position = rtr_madd(rtr_madd(rtr_scale(f4xyz(rec[0]), b0), f4xyz(rec[1]), b1), f4xyz(rec[2]), b2);
+                normal = geomNormal = f4xyz(rec[3]);
+            }
+        }
+    }
+    float4* o = sa.out + 5 * (size_t)k;
+    o[0] = make_float4(position.x, position.y, position.z, __uint_as_float(kind));
+    o[1] = make_float4(normal.x, normal.y, normal.z, __uint_as_float(index));
+    o[2] = make_float4(geomNormal.x, geomNormal.y, geomNormal.z, metallic);
+    o[3] = make_float4(color.x, color.y, color.z, roughness);
+    o[4] = make_float4(uu, vv, 0.0f, 0.0f);
+}
+
+hipError_t launch_hit_surfaces(const DeviceScene& sc, const SurfaceArgs& sa, hipStream_t s) {
+    hipLaunchKernelGGL(k_hit_surfaces, dim3((uint32_t)(((uint64_t)sa.n + kSurfaceBlock - 1) / kSurfaceBlock)), dim3(kSurfaceBlock), 0, s, sc, sa);
     return hipGetLastError();
 }
 

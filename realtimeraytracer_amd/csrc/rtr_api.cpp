@@ -120,6 +120,8 @@ struct rtr_scene {
     DevBuf<RtrAreaLightInfo> lights;
     DevBuf<float4> lightTris;            /* 4 x float4 per light triangle (rtrdev::launch_light_tris) */
     DevBuf<uint32_t> lightTriFirst;      /* first record of light l */
+    DevBuf<uint32_t> triCount;           /* per customIndex: triangles of the light or of the instance's mesh (rtr_hit_surfaces' range check) */
+    uint32_t numInstances = 0;
     DevBuf<float> xforms, nmats, ltc1, ltc2;
     std::vector<DevBuf<uint8_t>> texPixels;
     DevBuf<uint8_t> hdriPixels;
@@ -631,6 +633,13 @@ static int scene_create_impl(rtr_ctx* ctx, const rtr_scene_desc* d, const rtr_sc
         for (uint32_t l = 0; l < d->numLights; ++l) { first[l] = total; total += d->lights[l].numTriangles; }
         chk(s->lightTriFirst.upload(first.data(), first.size(), st));
         chk(s->lightTris.alloc((size_t)total * rtrdev::kLightTriRecord));
+        /* what a hit's primitiveId may be, per customIndex: a light's records or its instance's mesh triangles */
+        std::vector<uint32_t> count(d->numInstances);
+        for (uint32_t i = 0; i < d->numInstances; ++i) {
+            const RtrInstance& in = d->instances[i];
+            count[in.customIndex] = in.customIndex < d->numLights ? d->lights[in.customIndex].numTriangles : d->meshes[in.meshIndex].indexCount / 3u;
+        }
+        chk(s->triCount.upload(count.data(), count.size(), st));
     }
     chk(s->xforms.upload(xforms.data(), xforms.size(), st));
     chk(s->nmats.upload(nmats.data(), nmats.size(), st));
@@ -658,7 +667,7 @@ static int scene_create_impl(rtr_ctx* ctx, const rtr_scene_desc* d, const rtr_sc
         delete s; ctx_release_child(ctx);
         return fail(e == hipErrorOutOfMemory ? RTR_ERR_OUT_OF_MEMORY : RTR_ERR_HIP, "scene upload: %s", hipGetErrorString(e));
     }
-    s->numLights = d->numLights; s->numObjects = d->numObjects; s->numVertices = d->numVertices; s->numIndices = d->numIndices;
+    s->numLights = d->numLights; s->numObjects = d->numObjects; s->numInstances = d->numInstances; s->numVertices = d->numVertices; s->numIndices = d->numIndices;
     if (d->numLights) s->hostLights.assign(d->lights, d->lights + d->numLights);
     if (d->numInstances) s->hostInstances.assign(d->instances, d->instances + d->numInstances);
     if (d->numMeshes) s->hostMeshes.assign(d->meshes, d->meshes + d->numMeshes);
@@ -1471,6 +1480,34 @@ int rtr_trace_rays(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, uint32_t 
         HIP_TRY(hipEventElapsedTime(&ms, c->qEv[0], c->qEv[1]));
         stats->ms = ms;
     } else HIP_TRY(hipStreamSynchronize(st));
+    return RTR_OK;
+}
+
+/* the checks and the launch of rtr_hit_surfaces[_async], enqueued on the context's stream */
+static int enqueue_surfaces(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, uint32_t n, RtrSurface* out, const char* who) {
+    if (!c || !s) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: null context or scene", who);
+    if (s->ctx->device != c->device) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: the scene lives on device %d, the context on device %d", who, s->ctx->device, c->device);
+    if (n == 0) return RTR_OK;
+    if (!rays || !hits || !out) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: %s is null", who, !rays ? "rays" : (!hits ? "hits" : "out"));
+    if (!aligned16(rays) || !aligned16(hits) || !aligned16(out))
+        return fail(RTR_ERR_INVALID_ARGUMENT, "%s: %s is not 16-B aligned", who, !aligned16(rays) ? "rays" : (!aligned16(hits) ? "hits" : "out"));
+    HIP_TRY(hipSetDevice(c->device));
+    rtrdev::SurfaceArgs sa{};
+    sa.rays = reinterpret_cast<const float4*>(rays); sa.hits = reinterpret_cast<const float4*>(hits); sa.out = reinterpret_cast<float4*>(out);
+    sa.triCount = s->triCount.p; sa.numInstances = s->numInstances; sa.n = n;
+    const hipError_t e = rtrdev::launch_hit_surfaces(s->dev, sa, c->stream);
+    if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: kernel launch: %s", who, hipGetErrorString(e));
+    return RTR_OK;
+}
+
+int rtr_hit_surfaces_async(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, uint32_t n, RtrSurface* out) {
+    return enqueue_surfaces(c, s, rays, hits, n, out, "rtr_hit_surfaces_async");
+}
+
+int rtr_hit_surfaces(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, uint32_t n, RtrSurface* out) {
+    const int rc = enqueue_surfaces(c, s, rays, hits, n, out, "rtr_hit_surfaces");
+    if (rc != RTR_OK || n == 0) return rc;
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return RTR_OK;
 }
 

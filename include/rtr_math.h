@@ -299,8 +299,9 @@ RTR_HD uint32_t rtr_quant_hi(float v, float origin, float scale) {
 /* Per-ray constants of the quantised slab test: t(q) = q * ga + gb with ga = scale * idir, gb = (origin - o) * idir.
  * Same operation count per plane as the fp32 form (one fma) once q is converted.  Rounding: |t(q) - t_exact| corresponds
  * to moving the plane by at most ~(2 extent + 3 |origin - o| + |o + t d|) * 2^-24, far inside the builder's outward
- * padding of 2^-18 * max|coordinate| (ray origins up to ~8 scene sizes away), so the test stays conservative with
- * respect to rtr_mt_intersect's t exactly as rtr_slab was. */
+ * padding of 2^-18 * max|coordinate| while this bound alone covers it (ray origins up to ~8 scene sizes away), so the test
+ * stays conservative with respect to rtr_mt_intersect's t exactly as rtr_slab was.  Farther origins are not excluded: the
+ * queries of tests/test_gpu_conditioning.py start from 1 to 1000 scene sizes away and equal the brute force hit for hit. */
 RTR_HD void rtr_ray_grid(rtr_v3 o, rtr_v3 idir, const float* origin, const float* scale, rtr_v3* ga, rtr_v3* gb) {
     ga->x = scale[0] * idir.x; ga->y = scale[1] * idir.y; ga->z = scale[2] * idir.z;
     gb->x = (origin[0] - o.x) * idir.x; gb->y = (origin[1] - o.y) * idir.y; gb->z = (origin[2] - o.z) * idir.z;

@@ -297,3 +297,62 @@ class Witness:
         a = np.nan_to_num(a, nan=0.0)
         q = np.rint(np.power(a, 1 / 2.2) * 255.0).astype(np.uint32)
         return q[:, 2] | (q[:, 1] << 8) | (q[:, 0] << 16) | np.uint32(0xff000000)
+
+
+# ---- ray / triangle for caller-supplied rays (the BVH conditioning tests) ----------------------------------------------------------
+EPS_T = 2.0 ** -24          # fp32 unit roundoff
+
+
+def ray_hits(v0, v1, v2, rays, chunk=1 << 21):
+    """Closest hit of every RtrRay row (origin, tmin, direction, tmax) over the triangles (v0, v1, v2: (T, 3) float64 corners), by the
+    intersect.rint rules (|det| >= 1e-5, 0 <= u <= 1, v >= 0, u + v <= 1, tmin < t < tmax; ties to the lower index) in float64.
+
+    An fp32 evaluation of the same test can decide differently only near one of its boundaries.  For each ray and triangle the margin
+    is 1e-6 in barycentrics plus the error bound of an fp32 evaluation, 8 eps |o - v0| max(|e1|, |e2|) / |det| (the cancellation in
+    s = o - v0 grows with the distance of the origin and shrinks with the angle of incidence); a triangle whose barycentrics, det, or t
+    against tmin / tmax lie within their margins is 'near'.  Returns (index or -1, t, u, v, t margin, ambiguous, ties) per ray: ambiguous
+    rays are those with a near triangle (or non-finite input); ties counts the hits within the t margin of the closest one."""
+    e1, e2 = v1 - v0, v2 - v0
+    le = np.maximum(np.linalg.norm(e1, axis=1), np.linalg.norm(e2, axis=1))
+    n = len(rays)
+    best = np.full(n, -1, np.int64)
+    bt, bu, bv, btol = np.full(n, np.inf), np.zeros(n), np.zeros(n), np.zeros(n)
+    amb = np.zeros(n, bool)
+    ties = np.zeros(n, np.int64)
+    r64 = rays.astype(F)
+    step = max(1, chunk // max(len(v0), 1))
+    for lo in range(0, n, step):
+        r = r64[lo:lo + step]
+        o, d, tmin, tmax = r[:, 0:3], r[:, 4:7], r[:, 3], r[:, 7]
+        h = np.cross(d[:, None, :], e2[None, :, :])
+        a = np.einsum("tk,rtk->rt", e1, h)
+        s = o[:, None, :] - v0[None, :, :]
+        with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+            f = 1.0 / a
+            u = f * np.einsum("rtk,rtk->rt", s, h)
+            q = np.cross(s, e1[None, :, :])
+            v = f * np.einsum("rk,rtk->rt", d, q)
+            t = f * np.einsum("tk,rtk->rt", e2, q)
+            ls = np.linalg.norm(s, axis=2)
+            m = 1e-6 + 8 * EPS_T * ls * le[None, :] / np.abs(a)                      # barycentric margin
+            tt = np.abs(t) * 1e-5 + 8 * EPS_T * ls * le[None, :] ** 2 / np.abs(a)    # t margin
+            ma = 8 * EPS_T * np.linalg.norm(e1, axis=1)[None, :] * np.linalg.norm(h, axis=2)
+            strict = ((np.abs(a) >= 1e-5 + ma) & (u >= m) & (u <= 1 - m) & (v >= m) & (u + v <= 1 - m) & (t > tmin[:, None] + tt)
+                      & (t < tmax[:, None] - tt))
+            loose = ((np.abs(a) >= 1e-5 - ma) & (u >= -m) & (u <= 1 + m) & (v >= -m) & (u + v <= 1 + m) & (t > tmin[:, None] - tt)
+                     & (t < tmax[:, None] + tt))
+        live = np.isfinite(r[:, :7]).all(1) & (d != 0).any(1)
+        near = (loose & ~strict).any(1)
+        ts = np.where(strict, t, np.inf)
+        k = np.argmin(ts, axis=1)
+        rows = np.arange(len(r))
+        tk = ts[rows, k]
+        hit = np.isfinite(tk)
+        with np.errstate(invalid="ignore"):
+            close = (strict & (np.abs(t - tk[:, None]) <= tt[rows, k][:, None] + tt)).sum(1)
+        best[lo:lo + step] = np.where(hit, k, -1)
+        bt[lo:lo + step], bu[lo:lo + step], bv[lo:lo + step] = tk, u[rows, k], v[rows, k]
+        btol[lo:lo + step] = np.where(hit, tt[rows, k], 0.0)
+        amb[lo:lo + step] = near | ~live
+        ties[lo:lo + step] = close
+    return best, bt, bu, bv, btol, amb, ties

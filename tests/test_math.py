@@ -81,15 +81,24 @@ def test_unorm8_unpack_without_division_is_exact(oracle):
 def test_division_by_a_known_divisor_is_the_ieee_quotient(oracle):
     """rtr_div_by (a * fl(1/b) corrected twice by its exact remainder: what the denoise kernel issues instead of the division
     sequence) against a / b for EVERY float a of either sign with 2^-40 <= |a| <= 16 — the squared distances of UNORM8 vectors and
-    their quotients lie inside — for the divisors the pass uses (the phis, step^2 = 1, 4, 9, 16) and a few others; and at zero."""
+    their quotients lie inside — for the divisors the pass uses: the phis and EVERY step^2 the API can issue, (i + 1)^2 for i < 64
+    (rtr_denoise_combine accepts iterations <= 64), and a few others; and at zero."""
     import numpy as np
+    from concurrent.futures import ThreadPoolExecutor
     L = oracle.lib()
 
     def bits(x):
         return int(np.float32(x).view(np.uint32))
-    for b in (0.001, 1.0, 4.0, 9.0, 16.0, 25.0, 0.37):
-        assert L.oracle_div_by_mismatches(b, bits(2.0 ** -40), bits(16.0)) == 0, b
-        assert L.oracle_div_by_mismatches(b, 0, 0) == 0, b
+    # the smallest non-zero squared UNORM8 distance over the largest divisor stays above the range's lower end, the largest below its top
+    assert np.float32(1.0 / 255.0) ** 2 / np.float32(64 ** 2) > np.float32(2.0 ** -40)
+    assert 4 * np.float32(1.0) ** 2 <= 16.0                 # four channels, each at most 1 apart
+    divisors = [0.001, 0.37] + [float((i + 1) ** 2) for i in range(64)]
+
+    def bad(b):
+        return L.oracle_div_by_mismatches(b, bits(2.0 ** -40), bits(16.0)) + L.oracle_div_by_mismatches(b, 0, 0)
+    with ThreadPoolExecutor(8) as pool:                     # ctypes releases the GIL: 66 sweeps of 2 x 3.7e8 floats
+        for b, n in zip(divisors, pool.map(bad, divisors)):
+            assert n == 0, (b, n)
 
 
 def test_moeller_trumbore_edge_cases(oracle):

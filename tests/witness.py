@@ -5,17 +5,26 @@ forms, the same expression order.  That is what makes bit-exact parity testable,
 header would be invisible to every parity test.  This module restates the path a SECOND time with nothing in common:
 numpy, float64, libm (np.power, np.arctan2, ...), its own ray-triangle test, brute force over all triangles (no BVH), its own
 texture sampler and tone map, written from the shader text (reference src/shaders/raygen.rgen, closesthit.rchit, miss.rmiss,
-opacity.rahit, cook-torrance.glsl, raycommon.glsl) and the C-ABI scene description alone.
+opacity.rahit, cook-torrance.glsl, raycommon.glsl, LTC.glsl) and the C-ABI scene description alone.
 
-It cannot be bit-exact against fp32 code; tests/test_witness.py holds the oracle within 1e-5 relative on the HDR radiance and
-+-1 LSB on the RGBA8 bytes, on a sample of pixels, and allows the handful of pixels where a discrete decision (hit / miss at a
-silhouette, occluded / visible at a shadow edge, r1 + r2 > 1 fold) flips between fp32 and fp64.
+Covered: all five ray-gen images (Witness.render_all) — shadowed; unshadowed (the same sum, visibility 1); normal and position
+(normalize(avg), avg * POSITION_SCALE, packed without a tone map); analytic (bilinear look-up of the two 64 x 64 x 4 LTC tables with
+the sampler's repeat addressing, tangent frame, inverse transform from t1, the edge integrals with the shader's rational fit, the
+clipped-sphere look-up in ltc2.w, one- / two-sided lights, the Fresnel mix from t2, x 5).  The passes behind the ray-gen dispatch
+(a-trous, combine) have a witness of their own, tests/post_witness.py.
+
+It cannot be bit-exact against fp32 code; tests/test_witness.py holds the oracle to it by measured bounds (median relative error of
+the HDR radiance 1e-7, all but a handful of 20000 pixels byte-equal in every image), and allows the handful of pixels where a discrete
+decision (hit / miss at a silhouette, occluded / visible at a shadow edge, r1 + r2 > 1 fold) flips between fp32 and fp64.  Values the
+shader holds in fp32 and then amplifies are taken at fp32: the PCG floats, the fold's sum, and the pixel's world position (render_all).
 """
 import ctypes as C
 
 import numpy as np
 
 F = np.float64
+A_ANALYTIC, A_SHADOWED, A_UNSHADOWED, A_NORMAL, A_POSITION = 0, 1, 2, 6, 7      # rtr_image numbers (include/rtr.h)
+POSITION_SCALE = 1.0                                                             # raygen.rgen:10
 
 
 def _arr(ptr, n, dtype, width):
@@ -63,6 +72,8 @@ class Witness:
             tx = d.hdri.contents
             px = np.frombuffer(C.cast(tx.pixels, C.POINTER(C.c_uint8 * (tx.width * tx.height * tx.channels))).contents, dtype=np.uint8)
             self.hdri = px.reshape(tx.height, tx.width, tx.channels).astype(F) / 255.0
+        tab = lambda p: np.ctypeslib.as_array(p, (64, 64, 4)).astype(F) if p else None     # noqa: E731  texSamplers[0], [1]: [v][u][rgba]
+        self.ltc1, self.ltc2 = tab(d.ltc1), tab(d.ltc2)
         self.sky = np.power(np.array([d.skyColor[0], d.skyColor[1], d.skyColor[2]], F), 2.2)
         # world-space triangle soup in (instance, primitive) order + what the hit shader needs per triangle
         V0, V1, V2, cust, prim, alpha = [], [], [], [], [], []
@@ -178,19 +189,34 @@ class Witness:
     # ---- raygen.rgen for a set of pixels -------------------------------------------------------------------------------------
     def render(self, camera, info, params, xs, ys):
         """Returns (hdr (n,3) float64: pre-tonemap shadowed radiance, rgba8 (n,) uint32 packed B,G,R,255) for pixels (xs, ys)."""
+        r = self.render_all(camera, info, params, xs, ys, analytic=False)
+        return r["hdr"][A_SHADOWED], r["rgba8"][A_SHADOWED]
+
+    def render_all(self, camera, info, params, xs, ys, analytic=True):
+        """The five ray-gen images for pixels (xs, ys), keyed by rtr_image number (0 analytic, 1 shadowed, 2 unshadowed, 6 normal,
+        7 position): {"hdr": float64 (n, 3) values before the pack — radiance before the tone map for 0 / 1 / 2, normalize(avg) and
+        avg * POSITION_SCALE for 6 / 7 — and "rgba8": (n,) uint32 packed B,G,R,255}.  analytic needs the scene's LTC tables."""
         xs, ys = np.asarray(xs, np.int64), np.asarray(ys, np.int64)
         n = len(xs)
         cam = np.array(camera.position[:3], F)
         TL, dH, dV = (np.array(a[:3], F) for a in (camera.topLeftViewportCorner, camera.horizontalViewportDelta, camera.verticalViewportDelta))
-        shadowed = np.zeros((n, 3), F)
+        acc = {w: np.zeros((n, 3), F) for w in (A_ANALYTIC, A_SHADOWED, A_UNSHADOWED, A_NORMAL, A_POSITION)}
         ux, uy = xs.astype(np.uint32), ys.astype(np.uint32)
         for i in range(params.spp):
             with np.errstate(over="ignore"):
                 jx, jy = pcg(ux + np.uint32(i)), pcg(ux + np.uint32(i) * np.uint32(322))     # raygen.rgen:83: both seeds use x only
             pw = TL + dH * (xs + jx - 0.5)[:, None] + dV * (ys + jy - 0.5)[:, None]
+            # raygen.rgen:86-89 holds pixelWorldPos in an fp32 variable, one unit in front of a camera that stands hundreds of units from the
+            # origin, and :92 subtracts the camera from it: the variable's representation error (half an ulp of 278, 1.5e-5) becomes a
+            # relative error of 1.5e-5 in the direction, 0.02 units on a wall 1370 units away.  The ray the shader traces is defined by that
+            # fp32 value, so the witness rounds the exact position to fp32 ONCE (nearest: no expression order is copied) and goes on in
+            # float64.  Without it every fp32 evaluation of the shader traces rays this witness does not, and the position image — raw
+            # coordinates as UNORM8, 1 LSB = 0.004 units — differed from the oracle's on 0.87 % of the Cornell box's pixels, by up to 4 LSB;
+            # with it, on none of 3000 (tests/test_witness.py::test_five_images_normal_and_position).
+            pw = pw.astype(np.float32).astype(F)
             rd = normalize(pw - cam)
             hit, k, t, bu, bv = self.closest(np.broadcast_to(cam, (n, 3)), rd, 10000.0)
-            # miss.rmiss:15-27
+            # miss.rmiss:15-27; raygen.rgen:110-121: a miss or a light adds its colour to all three and skips the G-buffer sums
             miss = ~hit
             if miss.any():
                 sky = np.broadcast_to(self.sky, (miss.sum(), 3))
@@ -199,21 +225,33 @@ class Witness:
                     hu = np.arctan2(dd[:, 2], dd[:, 0]) / (2 * 3.14159265) + 0.5
                     hv = 1.0 - np.arccos(np.clip(dd[:, 1], -1, 1)) / 3.14159265
                     sky = np.power(self.sample(self.hdri, hu, hv)[:, :3], 2.2)
-                shadowed[miss] += sky
+                for w in (A_ANALYTIC, A_SHADOWED, A_UNSHADOWED):
+                    acc[w][miss] += sky
             cu = self.cust[k]
             islight = hit & (cu < self.numLights)
             for li in np.unique(cu[islight]):
-                shadowed[islight & (cu == li)] += np.array(self.lights[li].color[:3], F)
+                for w in (A_ANALYTIC, A_SHADOWED, A_UNSHADOWED):
+                    acc[w][islight & (cu == li)] += np.array(self.lights[li].color[:3], F)
             surf = np.nonzero(hit & (cu >= self.numLights))[0]
             if len(surf) == 0:
                 continue
-            shadowed[surf] += self._shade(surf, xs, ys, cam, rd, k, bu, bv, info, params)
-        shadowed /= params.spp
-        return shadowed, self.pack(shadowed)
+            sh, un, an, N, P = self._shade(surf, xs, ys, cam, rd, k, bu, bv, info, params, analytic)
+            acc[A_SHADOWED][surf] += sh; acc[A_UNSHADOWED][surf] += un; acc[A_ANALYTIC][surf] += an
+            acc[A_NORMAL][surf] += N; acc[A_POSITION][surf] += P                      # raygen.rgen:132-133
+        for w in acc:
+            acc[w] /= params.spp
+        with np.errstate(invalid="ignore", divide="ignore"):
+            acc[A_NORMAL] = normalize(acc[A_NORMAL])                                    # raygen.rgen:359; 0 / 0 where no sample hit a surface
+        acc[A_POSITION] = acc[A_POSITION] * POSITION_SCALE
+        rgba = {w: self.pack(acc[w]) for w in (A_ANALYTIC, A_SHADOWED, A_UNSHADOWED)}
+        rgba.update({w: self.pack_unorm(acc[w]) for w in (A_NORMAL, A_POSITION)})
+        if not analytic:
+            del acc[A_ANALYTIC], rgba[A_ANALYTIC]
+        return {"hdr": acc, "rgba8": rgba}
 
-    def _shade(self, rows, xs, ys, cam, rd, k, bu, bv, info, params):
+    def _shade(self, rows, xs, ys, cam, rd, k, bu, bv, info, params, analytic):
         m = len(rows)
-        out = np.zeros((m, 3), F)
+        out = np.zeros((m, 3), F); out_un = np.zeros((m, 3), F); out_an = np.zeros((m, 3), F)
         kk, u, v = k[rows], bu[rows], bv[rows]
         b0 = 1 - u - v
         P = np.zeros((m, 3), F); N = np.zeros((m, 3), F)
@@ -249,6 +287,12 @@ class Witness:
         so = P + N * 0.01
         px, py = xs[rows].astype(np.uint32), ys[rows].astype(np.uint32)
         ns_ = params.numShadowRays
+        if analytic:                                                                    # raygen.rgen:140-157
+            mdiff = (1 - metallic)[:, None] * color
+            dotnv = np.clip(np.sum(N * V, 1), 0.0, 1.0)
+            lu, lv = rough * self.LUT_SCALE + self.LUT_BIAS, np.sqrt(1.0 - dotnv) * self.LUT_SCALE + self.LUT_BIAS
+            t1, t2 = self.sample(self.ltc1, lu, lv), self.sample(self.ltc2, lu, lv)
+            fresnel = mspec * t2[:, 0:1] + (1 - mspec) * t2[:, 1:2]                     # :280
         for li in range(info.numAreaLights):                                            # raygen.rgen:165-285
             L = self.lights[li]
             T = np.array(L.transform[:], F).reshape(4, 4).T                             # column-major mat4
@@ -261,7 +305,7 @@ class Witness:
                 pdf = 1.0 / (area * 0.7)
                 ln = ln / np.sqrt(ln @ ln)
                 front = np.ones(m, bool) if L.isTwoSided else ((P - Pl[0]) @ ln >= 0)
-                acc = np.zeros((m, 3), F)
+                acc = np.zeros((m, 3), F); acc_un = np.zeros((m, 3), F)
                 for s in range(ns_):
                     with np.errstate(over="ignore"):
                         seed = np.uint32(s) + px * np.uint32(733) + py * np.uint32(1933) + np.uint32(info.frame)
@@ -277,7 +321,16 @@ class Witness:
                     B, ndl = self.brdf(N, V, ld, color, metallic, rough, mspec, 0.1, 0.1)
                     Lr = lcol[None, :] * (L.intensity * ndl / (dist * dist) * 10.0)[:, None]
                     acc += vis[:, None] * B * Lr / pdf
+                    acc_un += B * Lr / pdf                                              # :270: the same sum, visibility 1
                 out += np.where(front[:, None], acc / ns_, 0.0)
+                out_un += np.where(front[:, None], acc_un / ns_, 0.0)
+                if analytic:                                                            # :277-283; `continue` at :196 skips it with the samples
+                    two = bool(L.isTwoSided)
+                    with np.errstate(invalid="ignore", divide="ignore"):
+                        diffuse = self.ltc_evaluate(N, V, P, None, Pl, ln, two)
+                        spec = self.ltc_evaluate(N, V, P, t1, Pl, ln, two)
+                    a = lcol[None, :] * L.intensity * (spec[:, None] * fresnel + mdiff * diffuse[:, None]) * 5.0
+                    out_an += np.where(front[:, None], a, 0.0)
         dl = np.array([-1.0, 1.0, -0.5], F); dl /= np.sqrt(dl @ dl)                    # raygen.rgen:289-338
         lit = N @ dl > 0
         if lit.any():
@@ -285,8 +338,58 @@ class Witness:
             dd = np.broadcast_to(dl, (len(r), 3))
             vis = ~self.occluded(so[r], dd, np.full(len(r), 10000.0))
             B, ndl = self.brdf(N[r], V[r], dd, color[r], metallic[r], rough[r], mspec[r], 5.0, 0.0001)
-            out[r] += vis[:, None] * B * (np.array([1.0, 1.0, 0.5], F) * 0.2)[None, :] * (ndl * 20.0)[:, None]
+            d = B * (np.array([1.0, 1.0, 0.5], F) * 0.2)[None, :] * (ndl * 20.0)[:, None]
+            out[r] += vis[:, None] * d
+            out_un[r] += d; out_an[r] += d                                              # :337-338
+        return out, out_un, out_an, N, P
+
+    # ---- LTC.glsl, raygen.rgen:65-67 -----------------------------------------------------------------------------------------
+    LUT_SIZE = 64.0
+    LUT_SCALE = (LUT_SIZE - 1.0) / LUT_SIZE
+    LUT_BIAS = 0.5 / LUT_SIZE
+    EDGE_A0 = 0.8543985                                                                 # class attributes so that a test can mutate its copy
+    SWAP_T1_ZW = False
+    FLIP_BEHIND = True
+
+    def integrate_edge(self, v1, v2):
+        """LTC.glsl:2-15.  The rational fit of theta / sin(theta) is the operation, not an approximation of it."""
+        x = np.sum(v1 * v2, 1)
+        y = np.abs(x)
+        a = self.EDGE_A0 + (0.4965155 + 0.0145206 * y) * y
+        b = 3.4175940 + (4.1616724 + y) * y
+        v = a / b
+        ts = np.where(x > 0.0, v, 0.5 / np.sqrt(np.maximum(1.0 - x * x, 1e-7)) - v)
+        return np.cross(v1, v2) * ts[:, None]
+
+    def ltc_evaluate(self, N, V, P, t1, points, light_normal, two_sided):
+        """LTC.glsl:17-72; t1 = None is mat3(1).  Returns the scalar every component of Lo_i holds."""
+        T1 = normalize(V - N * np.sum(V * N, 1)[:, None])
+        T2 = np.cross(N, T1)
+        Ls = []
+        for k in range(3):
+            w = points[k][None, :] - P
+            q = np.stack([np.sum(T1 * w, 1), np.sum(T2 * w, 1), np.sum(N * w, 1)], 1)   # transpose(mat3(T1, T2, N)) * w
+            if t1 is not None:                                                          # mat3(vec3(t1.x, 0, t1.y), vec3(0, 1, 0), vec3(t1.z, 0, t1.w)): columns
+                c2x, c2z = (t1[:, 3], t1[:, 2]) if self.SWAP_T1_ZW else (t1[:, 2], t1[:, 3])
+                q = np.stack([t1[:, 0] * q[:, 0] + c2x * q[:, 2], q[:, 1], t1[:, 1] * q[:, 0] + c2z * q[:, 2]], 1)
+            Ls.append(normalize(q))
+        behind = (points[0][None, :] - P) @ light_normal < 0.0
+        vsum = self.integrate_edge(Ls[0], Ls[1]) + self.integrate_edge(Ls[1], Ls[2]) + self.integrate_edge(Ls[2], Ls[0])
+        ln = np.sqrt(np.sum(vsum * vsum, 1))
+        z = vsum[:, 2] / ln
+        if self.FLIP_BEHIND:
+            z = np.where(behind, -z, z)
+        scale = self.sample(self.ltc2, (z * 0.5 + 0.5) * self.LUT_SCALE + self.LUT_BIAS, ln * self.LUT_SCALE + self.LUT_BIAS)[:, 3]
+        out = ln * scale
+        if not two_sided:
+            out = np.where(behind, out, 0.0)
         return out
+
+    @staticmethod
+    def pack_unorm(c):
+        """imageStore(vec4(v.b, v.g, v.r, 1)) into rgba8 without a tone map (raygen.rgen:363-364): clamp, round to nearest; NaN stores 0"""
+        q = np.rint(np.clip(np.nan_to_num(np.asarray(c, F), nan=0.0), 0, 1) * 255.0).astype(np.uint32)
+        return q[:, 2] | (q[:, 1] << 8) | (q[:, 0] << 16) | np.uint32(0xff000000)
 
     @staticmethod
     def pack(c):

@@ -393,6 +393,65 @@ int  rtr_hit_surfaces_async(rtr_ctx* ctx, const rtr_scene* scene, const RtrRay* 
 /* The same, then joins ctx's stream (only that stream). */
 int  rtr_hit_surfaces(rtr_ctx* ctx, const rtr_scene* scene, const RtrRay* rays, const RtrHit* hits, uint32_t numRays, RtrSurface* out);
 
+/* ---- direct lighting for ray-query hits ----------------------------------------------------------------------------------
+ * What the ray-gen shader does AFTER the closest hit (raygen.rgen:165-338, :345-357), in the stages the renderer itself runs it in:
+ *   rtr_light_rays   the shadow rays of each hit        (the area-light samples of :206-231, the directional light of :299-303)
+ *   rtr_trace_rays   RTR_QUERY_ANY answers them         (the caller's launch: any of the stages can be replaced)
+ *   rtr_shade_hits   the Cook-Torrance sums, the LTC term, sky and light hits
+ *   rtr_tonemap_pack ACES + sRGB + B,G,R,255
+ * camera rays -> closest hit -> these four reproduce rtr_render's images from public parts: at 1 sample per pixel bit for bit (with
+ * more, the renderer adds all samples of a pixel into ONE running sum before it divides, which per-hit outputs cannot restate; and
+ * divergence D6 of DESIGN.md section 4 holds here as there).
+ * Every hit owns Q = numShadowRays * (triangles of the first numAreaLights lights) + 1 SLOTS, whether or not a ray is sent for them:
+ * sample s of triangle ti of light l is slot (T_l + ti) * numShadowRays + s, T_l = the triangles of the lights before l; the
+ * directional light is slot Q - 1. */
+#define RTR_LIGHT_SHADOWED   1u   /* always produced */
+#define RTR_LIGHT_UNSHADOWED 2u
+#define RTR_LIGHT_ANALYTIC   4u   /* needs the scene's LTC tables */
+
+typedef struct rtr_light_params {
+    uint32_t numAreaLights;   /* SceneInfo.numAreaLights: the first lights of the scene that are sampled */
+    uint32_t numShadowRays;   /* NUM_SHADOW_RAYS (reference: 3) */
+    uint32_t frame;           /* SceneInfo.frame: enters every sample seed */
+    uint32_t width, spp;      /* hit k belongs to pixel ((k / spp) % width, (k / spp) / width): rtr_camera_rays_async's order.  Used when seeds == NULL */
+    uint32_t outputs;         /* RTR_LIGHT_SHADOWED (always produced) | RTR_LIGHT_UNSHADOWED | RTR_LIGHT_ANALYTIC */
+    uint32_t _pad[2];
+} rtr_light_params;           /* 32 bytes */
+
+/* Q for these params: pure arithmetic on the scene's light table, no device is touched.  RTR_ERR_INVALID_ARGUMENT for a null pointer,
+ * numAreaLights above the scene's lights, numShadowRays == 0 (or above 1024, rtr_render's limit), or a Q past 32 bits. */
+int  rtr_light_slots(const rtr_scene* scene, const rtr_light_params* params, uint32_t* slotsPerHit);
+/* For hit k of numHits, writes Q RtrRay at outRays[k * Q ... k * Q + Q): exactly the shadow rays the shader sends for that surface point —
+ * origin hitPoint + 0.01 * hitNormal, normalised direction, tmin 0.001, tmax = distance - 0.5 (10000 for the directional light).  A slot
+ * whose ray the shader does not send — a one-sided light triangle facing away, the directional light behind the surface, a hit that is a
+ * miss, a light or has ids out of range — gets the NULL RAY, eight zero floats, which rtr_trace_rays answers "not occluded" without a walk.
+ * seeds: device array of numHits uint32, or NULL.  The seed of sample s is s + base_k + frame (32-bit words), base_k = seeds[k], or
+ * px * 733 + py * 1933 of the pixel params->width / spp give: camera-ray callers pass NULL and get the renderer's seeds.  The view
+ * vector is normalize(rays[k].origin - hitPoint), for a camera ray the shader's cameraPosition - hitPoint.
+ * rays, hits, outRays: DEVICE pointers, 16-B aligned; seeds 4-B aligned.  ENQUEUED on ctx's stream; the scene may belong to another
+ * context of the same device.  numHits == 0 does nothing.  RTR_ERR_INVALID_ARGUMENT (with a message) for a null or misaligned pointer,
+ * a scene on another device, params rtr_light_slots refuses, width or spp == 0 with seeds == NULL, or numHits * Q past 32 bits. */
+int  rtr_light_rays_async(rtr_ctx* ctx, const rtr_scene* scene, const RtrRay* rays, const RtrHit* hits, uint32_t numHits,
+                          const rtr_light_params* params, const uint32_t* seeds, RtrRay* outRays);
+/* out[k] = the RtrRadiance of hit k: one primary sample's contribution — the sky at a miss and the light's colour at a light hit in every
+ * sum asked for, the light loops at an object, zeros and RTR_SURFACE_INVALID for ids out of range.  occluded: the numHits * Q bytes an
+ * RTR_QUERY_ANY query of rtr_light_rays' rays returned (no alignment asked); bytes of null slots are not read.  Sums not in
+ * params->outputs are written as zeros and their work is skipped under the renderer's rule: an occluded sample's BRDF is evaluated only
+ * when the unshadowed sum is wanted.  RTR_LIGHT_ANALYTIC on a scene without LTC tables: RTR_ERR_UNSUPPORTED.  out: 16-B aligned.
+ * Otherwise as rtr_light_rays_async, with the same rays, hits, params and seeds. */
+int  rtr_shade_hits_async(rtr_ctx* ctx, const rtr_scene* scene, const RtrRay* rays, const RtrHit* hits, uint32_t numHits,
+                          const rtr_light_params* params, const uint32_t* seeds, const uint8_t* occluded, RtrRadiance* out);
+/* outBGRA8[k] = the tone-mapped, packed pixel (raygen.rgen:345-357) of the three floats at (char*)radiance + k * strideBytes: a column of
+ * RtrRadiance (stride 48), an RGBA float image (16), packed float3 (12).  strideBytes: a multiple of 4, >= 12; both pointers 4-B
+ * aligned DEVICE pointers.  ENQUEUED on ctx's stream. */
+int  rtr_tonemap_pack_async(rtr_ctx* ctx, const float* radiance, uint32_t strideBytes, uint32_t numValues, uint32_t* outBGRA8);
+/* The same three, then join ctx's stream (only that stream). */
+int  rtr_light_rays(rtr_ctx* ctx, const rtr_scene* scene, const RtrRay* rays, const RtrHit* hits, uint32_t numHits,
+                    const rtr_light_params* params, const uint32_t* seeds, RtrRay* outRays);
+int  rtr_shade_hits(rtr_ctx* ctx, const rtr_scene* scene, const RtrRay* rays, const RtrHit* hits, uint32_t numHits,
+                    const rtr_light_params* params, const uint32_t* seeds, const uint8_t* occluded, RtrRadiance* out);
+int  rtr_tonemap_pack(rtr_ctx* ctx, const float* radiance, uint32_t strideBytes, uint32_t numValues, uint32_t* outBGRA8);
+
 /* ---- errors --------------------------------------------------------------------------- */
 const char* rtr_last_error(void);
 const char* rtr_status_string(int status);

@@ -210,6 +210,16 @@ typedef struct RtrSurface {
     float    uv[2];         uint32_t _reserved[2];
 } RtrSurface;
 
+/* ---- direct lighting (rtr_shade_hits): one primary sample's contribution, as the ray-gen shader forms it -------------------
+ * The three sums of raygen.rgen:165-338 for one RtrHit — shadowed (what the framebuffer shows), unshadowed (every sample counted as
+ * visible) and analytic (the LTC term) — before the division by the samples per pixel and the tone map.  48 B, three 16-B stores.
+ * kind: the RTR_SURFACE_* of the hit.  A sum that was not asked for (rtr_light_params.outputs) is written as zeros; _r0, _r1 as 0. */
+typedef struct RtrRadiance {
+    float    shadowed[3];   uint32_t kind;
+    float    unshadowed[3]; uint32_t _r0;
+    float    analytic[3];   uint32_t _r1;
+} RtrRadiance;
+
 #ifdef __cplusplus
 }
 #endif
@@ -228,6 +238,7 @@ static_assert(sizeof(RtrWideNode) == 64, "wide node must be 64 B");
 static_assert(sizeof(RtrRay) == 32, "ray must be 32 B");
 static_assert(sizeof(RtrHit) == 32, "hit must be 32 B");
 static_assert(sizeof(RtrSurface) == 80, "surface must be 80 B");
+static_assert(sizeof(RtrRadiance) == 48, "radiance must be 48 B");
 #endif
 
 #endif /* RTR_TYPES_H */

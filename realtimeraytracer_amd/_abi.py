@@ -76,6 +76,15 @@ class RtrSurface(C.Structure):
                 ("color", f32 * 3), ("roughness", f32), ("uv", f32 * 2), ("_reserved", u32 * 2)]
 
 
+class RtrRadiance(C.Structure):
+    _fields_ = [("shadowed", f32 * 3), ("kind", u32), ("unshadowed", f32 * 3), ("_r0", u32), ("analytic", f32 * 3), ("_r1", u32)]
+
+
+class rtr_light_params(C.Structure):
+    _fields_ = [("numAreaLights", u32), ("numShadowRays", u32), ("frame", u32), ("width", u32), ("spp", u32), ("outputs", u32),
+                ("_pad", u32 * 2)]
+
+
 class rtr_texture(C.Structure):
     _fields_ = [("pixels", C.POINTER(C.c_uint8)), ("width", u32), ("height", u32), ("channels", u32), ("_pad", u32)]
 
@@ -127,6 +136,7 @@ assert C.sizeof(RtrObjectInfo) == 80 and C.sizeof(RtrAreaLightInfo) == 96
 assert C.sizeof(RtrBvhNode) == 32 and C.sizeof(RtrBvhGrid) == 32 and C.sizeof(RtrBvhTri) == 48 and C.sizeof(RtrWideNode) == 64
 assert C.sizeof(RtrRay) == 32 and C.sizeof(RtrHit) == 32 and C.sizeof(rtr_query_stats) == 48
 assert C.sizeof(RtrSurface) == 80
+assert C.sizeof(RtrRadiance) == 48 and C.sizeof(rtr_light_params) == 32
 
 # enum rtr_image
 IMAGE_ANALYTIC, IMAGE_SHADOWED, IMAGE_UNSHADOWED = 0, 1, 2
@@ -144,6 +154,7 @@ IMAGES_DENOISE = IMG_BIT(3) | IMG_BIT(4) | IMG_BIT(5)
 BUILD_HOST_SAH, BUILD_DEVICE_LBVH = 0, 1
 QUERY_CLOSEST, QUERY_ANY, QUERY_OPAQUE = 0, 1, 2
 SURFACE_MISS, SURFACE_OBJECT, SURFACE_LIGHT, SURFACE_INVALID = 0, 1, 2, 3
+LIGHT_SHADOWED, LIGHT_UNSHADOWED, LIGHT_ANALYTIC = 1, 2, 4
 
 P = C.POINTER
 VP = C.c_void_p
@@ -196,6 +207,13 @@ RTR_SYMBOLS = {
     "rtr_camera_rays_async": (C.c_int, [VP, P(RtrCameraData), u32, u32, u32, VP]),
     "rtr_hit_surfaces_async": (C.c_int, [VP, VP, VP, VP, u32, VP]),
     "rtr_hit_surfaces": (C.c_int, [VP, VP, VP, VP, u32, VP]),
+    "rtr_light_slots": (C.c_int, [VP, P(rtr_light_params), P(u32)]),
+    "rtr_light_rays_async": (C.c_int, [VP, VP, VP, VP, u32, P(rtr_light_params), VP, VP]),
+    "rtr_light_rays": (C.c_int, [VP, VP, VP, VP, u32, P(rtr_light_params), VP, VP]),
+    "rtr_shade_hits_async": (C.c_int, [VP, VP, VP, VP, u32, P(rtr_light_params), VP, VP, VP]),
+    "rtr_shade_hits": (C.c_int, [VP, VP, VP, VP, u32, P(rtr_light_params), VP, VP, VP]),
+    "rtr_tonemap_pack_async": (C.c_int, [VP, VP, u32, u32, VP]),
+    "rtr_tonemap_pack": (C.c_int, [VP, VP, u32, u32, VP]),
 }
 
 RTRH_SYMBOLS = {

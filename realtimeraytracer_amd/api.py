@@ -419,3 +419,183 @@ def hit_surfaces(scene, rays, hits, ctx=None, asynchronous=False):
     res.kind, res.object_index = words[:, 3], words[:, 7]
     res._keep = (r, h)                   # an asynchronous call's inputs stay alive with its result
     return res
+
+
+# ---- direct lighting for ray-query hits (rtr_light_rays, rtr_shade_hits, rtr_tonemap_pack) ----------------------------------------
+class RadianceResult:
+    """What shade_hits and direct_light give back: views into one (N, 12) array of RtrRadiance records (raw, float32).  shadowed,
+    unshadowed, analytic (N, 3) float32 — a sum that was not asked for is zeros — and kind (A.SURFACE_*) int32."""
+    raw = shadowed = unshadowed = analytic = kind = None
+
+
+def make_light_params(num_area_lights, shadow_rays=3, frame=0, width=0, spp=1, outputs=A.LIGHT_SHADOWED):
+    """rtr_light_params.  width / spp say which pixel a hit belongs to (camera_rays' order) and matter only without explicit seeds"""
+    return A.rtr_light_params(int(num_area_lights), int(shadow_rays), int(frame) & 0xffffffff, int(width), int(spp), int(outputs))
+
+
+def light_slots(scene, params):
+    """rtr_light_slots: Q, the slots (light rays, visibility bytes) every hit owns for these params"""
+    q = C.c_uint32(0)
+    _check(scene.lib.rtr_light_slots(scene.h, C.byref(params), C.byref(q)), "rtr_light_slots")
+    return int(q.value)
+
+
+def _light_inputs(torch, scene, rays, hits, seeds, ctx, who, asynchronous):
+    """the checked device arrays of light_rays / shade_hits: (rays, hits, seeds or None, numpy in?)"""
+    dev = torch.device("cuda", ctx.device)
+    if isinstance(hits, QueryResult):
+        if hits.hits is None:
+            raise ValueError(f"{who}: the QueryResult holds no hit records (an any-hit query)")
+        hits = hits.hits
+    r, rn = _device_array(torch, rays, torch.float32, np.float32, "rays", dev, who)
+    h, hn = _device_array(torch, hits, torch.int32, np.int32, "hits", dev, who)
+    if rn != hn:
+        raise ValueError(f"{who}: rays and hits must both be numpy arrays or both be tensors")
+    if r.shape[0] != h.shape[0]:
+        raise ValueError(f"{who}: {r.shape[0]} rays but {h.shape[0]} hits")
+    sd = None
+    if seeds is not None:
+        if isinstance(seeds, np.ndarray):
+            if seeds.dtype not in (np.uint32, np.int32) or seeds.ndim != 1:
+                raise ValueError(f"{who}: seeds must be 32-bit integers (N,), got {seeds.dtype} {seeds.shape}")
+            sd = torch.from_numpy(np.ascontiguousarray(seeds).view(np.int32)).to(dev)
+        elif isinstance(seeds, torch.Tensor):
+            if seeds.dtype != torch.int32 or seeds.dim() != 1 or seeds.device != dev or not seeds.is_contiguous():
+                raise ValueError(f"{who}: seeds must be a contiguous int32 (N,) tensor on {dev}")
+            sd = seeds
+        else:
+            raise ValueError(f"{who}: seeds must be a torch tensor or a numpy array, got {type(seeds).__name__}")
+        if sd.shape[0] != r.shape[0]:
+            raise ValueError(f"{who}: {r.shape[0]} rays but {sd.shape[0]} seeds")
+    if asynchronous and ctx.get_stream() != torch.cuda.current_stream(dev).cuda_stream:
+        raise ValueError(f"{who}: an asynchronous call needs the context on torch's current stream (ctx.set_stream)")
+    return r, h, sd, rn
+
+
+def light_rays(scene, rays, hits, params, seeds=None, ctx=None, asynchronous=False):
+    """rtr_light_rays: the shadow rays the ray-gen shader sends for each hit, as an (N * Q, 8) float32 array of RtrRay (Q =
+    light_slots(scene, params)); hit k's rays are rows k * Q ... k * Q + Q, a slot without a ray holds eight zeros.  rays, hits as
+    hit_surfaces takes them; seeds: int32 (N,) bases of the sample seeds, default the pixel's (params.width, params.spp).  Device
+    tensors in give a device tensor out, numpy in gives numpy out; ctx and asynchronous as in trace_rays."""
+    torch = _torch()
+    ctx = ctx or scene.ctx
+    dev = torch.device("cuda", ctx.device)
+    r, h, sd, as_numpy = _light_inputs(torch, scene, rays, hits, seeds, ctx, "light_rays", asynchronous)
+    n, q = int(r.shape[0]), light_slots(scene, params)
+    if n * q > 0xffffffff:
+        raise ValueError(f"light_rays: {n} hits x {q} slots do not fit 32 bits")
+    out = torch.empty((n * q, 8), dtype=torch.float32, device=dev)
+    if not asynchronous and ctx.get_stream() != torch.cuda.current_stream(dev).cuda_stream:
+        torch.cuda.current_stream(dev).synchronize()        # the inputs (and the output's memory) are ready for the context's stream
+    fn = ctx.lib.rtr_light_rays_async if asynchronous else ctx.lib.rtr_light_rays
+    if n:
+        _check(fn(ctx.h, scene.h, A.VP(r.data_ptr()), A.VP(h.data_ptr()), n, C.byref(params), A.VP(sd.data_ptr()) if sd is not None else None,
+                  A.VP(out.data_ptr())), "rtr_light_rays")
+    else:
+        _check(fn(ctx.h, scene.h, None, None, 0, C.byref(params), None, None), "rtr_light_rays")
+    if as_numpy:
+        return out.cpu().numpy()
+    out._keep = (r, h, sd)               # an asynchronous call's inputs stay alive with its result
+    return out
+
+
+def shade_hits(scene, rays, hits, params, occluded, seeds=None, ctx=None, asynchronous=False):
+    """rtr_shade_hits: one primary sample's contribution for each hit -> RadianceResult.  occluded: the (N * Q,) uint8 answers of
+    trace_rays(any_hit=True) for light_rays' rays (or the QueryResult itself), with the same rays, hits, params and seeds."""
+    torch = _torch()
+    ctx = ctx or scene.ctx
+    dev = torch.device("cuda", ctx.device)
+    r, h, sd, as_numpy = _light_inputs(torch, scene, rays, hits, seeds, ctx, "shade_hits", asynchronous)
+    if isinstance(occluded, QueryResult):
+        if occluded.occluded is None:
+            raise ValueError("shade_hits: the QueryResult holds no visibility bytes (a closest-hit query)")
+        occluded = occluded.occluded
+    n, q = int(r.shape[0]), light_slots(scene, params)
+    if isinstance(occluded, np.ndarray):
+        if not as_numpy or occluded.dtype != np.uint8 or occluded.shape != (n * q,):
+            raise ValueError(f"shade_hits: occluded must be uint8 ({n * q},), numpy like the rays; got {occluded.dtype} {occluded.shape}")
+        oc = torch.from_numpy(np.ascontiguousarray(occluded)).to(dev)
+    elif isinstance(occluded, torch.Tensor):
+        if as_numpy or occluded.dtype != torch.uint8 or tuple(occluded.shape) != (n * q,) or occluded.device != dev or not occluded.is_contiguous():
+            raise ValueError(f"shade_hits: occluded must be a contiguous uint8 ({n * q},) tensor on {dev}, like the rays")
+        oc = occluded
+    else:
+        raise ValueError(f"shade_hits: occluded must be a torch tensor or a numpy array, got {type(occluded).__name__}")
+    out = torch.empty((n, 12), dtype=torch.float32, device=dev)
+    if not asynchronous and ctx.get_stream() != torch.cuda.current_stream(dev).cuda_stream:
+        torch.cuda.current_stream(dev).synchronize()
+    fn = ctx.lib.rtr_shade_hits_async if asynchronous else ctx.lib.rtr_shade_hits
+    if n:
+        _check(fn(ctx.h, scene.h, A.VP(r.data_ptr()), A.VP(h.data_ptr()), n, C.byref(params), A.VP(sd.data_ptr()) if sd is not None else None,
+                  A.VP(oc.data_ptr()), A.VP(out.data_ptr())), "rtr_shade_hits")
+    else:
+        _check(fn(ctx.h, scene.h, None, None, 0, C.byref(params), None, None, None), "rtr_shade_hits")
+    res = _radiance_result(out.cpu().numpy() if as_numpy else out, as_numpy, torch)
+    res._keep = (r, h, sd, oc)
+    return res
+
+
+def _radiance_result(raw, as_numpy, torch):
+    res = RadianceResult()
+    words = raw.view(np.int32) if as_numpy else raw.view(torch.int32)
+    res.raw = raw
+    res.shadowed, res.unshadowed, res.analytic, res.kind = raw[:, 0:3], raw[:, 4:7], raw[:, 8:11], words[:, 3]
+    return res
+
+
+def tonemap_pack(ctx, radiance, asynchronous=False):
+    """rtr_tonemap_pack: the tone-mapped BGRA8 pixel (ACES, sRGB; uint32 as Frame.download gives them, here int32 (N,) on the device) of
+    each row of radiance, a float32 (N, >= 3) array whose first three columns are used and whose rows may be a view into wider records
+    (RadianceResult.shadowed, an HDR image reshaped to (N, 4)).  numpy in gives numpy (uint32) out."""
+    torch = _torch()
+    dev = torch.device("cuda", ctx.device)
+    as_numpy = isinstance(radiance, np.ndarray)
+    x = torch.from_numpy(np.ascontiguousarray(radiance, dtype=np.float32)).to(dev) if as_numpy else radiance
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.dim() != 2 or x.shape[1] < 3 or x.device != dev:
+        raise ValueError(f"tonemap_pack: radiance must be float32 (N, >= 3) on {dev}")
+    n = int(x.shape[0])
+    if n and (x.stride(1) != 1 or x.stride(0) < 3):
+        raise ValueError("tonemap_pack: the three floats of a row must be adjacent")
+    if asynchronous and ctx.get_stream() != torch.cuda.current_stream(dev).cuda_stream:
+        raise ValueError("tonemap_pack: an asynchronous call needs the context on torch's current stream (ctx.set_stream)")
+    out = torch.empty(n, dtype=torch.int32, device=dev)
+    if not asynchronous and ctx.get_stream() != torch.cuda.current_stream(dev).cuda_stream:
+        torch.cuda.current_stream(dev).synchronize()
+    fn = ctx.lib.rtr_tonemap_pack_async if asynchronous else ctx.lib.rtr_tonemap_pack
+    if n:
+        _check(fn(ctx.h, A.VP(x.data_ptr()), 4 * int(x.stride(0)), n, A.VP(out.data_ptr())), "rtr_tonemap_pack")
+    if as_numpy:
+        return out.cpu().numpy().view(np.uint32)
+    out._keep = x
+    return out
+
+
+def direct_light(scene, rays, hits=None, params=None, seeds=None, ctx=None, max_ray_bytes=256 << 20):
+    """The composed stage: closest hit (when hits is None) -> light_rays -> trace_rays(any_hit=True) -> shade_hits, in chunks of hits
+    so that a chunk's light rays (n * Q * 32 bytes) stay within max_ray_bytes — a 1080p frame at Q = 7 would be 464 MB of rays at once.
+    Chunks do not change the result.  rays: a float32 (N, 8) device tensor; hits: a QueryResult, (N, 8) int32 records, or None;
+    params: make_light_params(...).  Returns a RadianceResult on the device."""
+    torch = _torch()
+    ctx = ctx or scene.ctx
+    if params is None:
+        raise ValueError("direct_light: params (make_light_params) are needed")
+    if not isinstance(rays, torch.Tensor):
+        raise ValueError("direct_light: rays must be a device tensor")
+    if hits is None:
+        hits = trace_rays(scene, rays, ctx=ctx)
+    if isinstance(hits, QueryResult):
+        hits = hits.hits
+    n, q = int(rays.shape[0]), light_slots(scene, params)
+    chunk = max(1, int(max_ray_bytes) // (32 * q))
+    out =torch.empty((n, 12), dtype=torch.float32, device=rays.device)
+    for a in range(0, n, chunk):
+        b = min(n, a + chunk)
+        sd = seeds[a:b] if seeds is not None else None
+        if sd is None and a:             # the pixel of hit k is (k // spp) % width, (k // spp) // width: a later chunk carries its seeds
+            k = torch.arange(a, b, device=rays.device, dtype=torch.int64) // int(params.spp)
+            sd = ((k % int(params.width)) * 733 + (k // int(params.width)) * 1933).to(torch.int32)      # wraps to 32 bits as the kernel's words do
+        r, h = rays[a:b], hits[a:b]
+        lr = light_rays(scene, r, h, params, seeds=sd, ctx=ctx)
+        occ = trace_rays(scene, lr, any_hit=True, ctx=ctx).occluded
+        out[a:b] = shade_hits(scene, r, h, params, occ, seeds=sd, ctx=ctx).raw
+    return _radiance_result(out, False, torch)

@@ -623,7 +623,11 @@ __device__ __forceinline__ rtr_v3 light_sample_pos(const rtr_v3* P, uint32_t s, 
 
 /* The light loops of raygen.rgen:165-338 for one shaded surface point.  Policy::occluded(origin, dir, tmax, rawDir, intoSurface) (rawDir: dir before normalisation, only its signs are meaningful; intoSurface: dot(hitNormal, rawDir) < 0) answers the
  * shadow query; Policy::kShade == false (counting / emitting the queries) skips the BRDF arithmetic but keeps the exact
- * sequence of queries. */
+ * sequence of queries.  Policy::slots_at(first) is told, ahead of the queries of a light triangle that is not culled, the FIXED slot of
+ * its first sample — (lightTriFirst[li] + ti) * numShadowRays, include/rtr.h: rtr_light_slots — and kDirectionalSlot ahead of the
+ * directional light's query.  The renderer's policies number their queries as they come and leave it empty; the ray-query stage
+ * (kernels/rtr_query.hip), whose slots do not depend on which triangles were culled, takes its place from it. */
+constexpr uint32_t kDirectionalSlot = 0xffffffffu;
 #ifndef RTR_INTO_EXPR
 #define RTR_INTO_EXPR (rtr_dot(hitNormal, lightVec) < 0.0f)
 #endif
@@ -663,6 +667,7 @@ __device__ __forceinline__ void light_loops(const DeviceScene& sc, const RenderA
                 if (rtr_dot(lightNormal, rtr_sub(hitPoint, P[0])) < 0.0f) continue;
             }
             rtr_v3 shadowedSample = rtr_mk(0, 0, 0), unshadowedSample = rtr_mk(0, 0, 0);
+            pol.slots_at((sc.lightTriFirst[li] + ti) * ra.numShadowRays);
             for (uint32_t s = 0; s < ra.numShadowRays; ++s) {                             /* :206 */
                 const rtr_v3 lightSamplePos = light_sample_pos(P, s, px, py, ra.info.frame);
                 const rtr_v3 lightVec = rtr_sub(lightSamplePos, hitPoint);
@@ -701,6 +706,7 @@ __device__ __forceinline__ void light_loops(const DeviceScene& sc, const RenderA
     /* directional light, raygen.rgen:289-338 */
     const rtr_v3 directLightDir = directional_light_dir();
     if (rtr_dot(hitNormal, directLightDir) <= 0.0f) return;
+    pol.slots_at(kDirectionalSlot);
     const bool occ = pol.occluded(shadowOrigin, directLightDir, 10000.0f, directLightDir, false);
     if (Policy::kShade && (wantUnshadowed || wantAnalytic || !occ)) {
         const float currShadow = occ ? 0.0f : 1.0f;

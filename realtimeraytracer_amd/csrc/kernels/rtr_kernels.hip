@@ -34,6 +34,7 @@ constexpr int kBlock = 256;
 template <bool STATS, int STACK>
 struct InlinePolicy {
     static constexpr bool kShade = true;
+    __device__ __forceinline__ void slots_at(uint32_t) {}
     const DeviceScene& sc; int32_t* stack; LocalStats& st;
     __device__ __forceinline__ bool occluded(rtr_v3 o, rtr_v3 d, float tmax, rtr_v3, bool) {
         HitRec h;
@@ -98,12 +99,14 @@ __device__ __forceinline__ void queue_store(const RayQueue& q, size_t idx, rtr_v
  * pixels aimed at the same light triangle / sample index. */
 struct CountPolicy {
     static constexpr bool kShade = false;
+    __device__ __forceinline__ void slots_at(uint32_t) {}
     uint32_t n;
     __device__ __forceinline__ bool occluded(rtr_v3, rtr_v3, float, rtr_v3, bool) { ++n; return false; }
 };
 
 struct EmitPolicy {
     static constexpr bool kShade = false;
+    __device__ __forceinline__ void slots_at(uint32_t) {}
     typedef volatile __attribute__((address_space(3))) uint32_t* lds_word;     /* keeps the access a ds_read/ds_write, not a flat_load */
     /* slot: where this query's visibility byte lives.  The bytes are laid out in PLANES — query j of pixel-sample k at
      * j * slotStride + k (slotStride = all pixel-sample slots of the frame) — so the 64 results a traversal wave holds (the same
@@ -140,6 +143,7 @@ __device__ __forceinline__ uint32_t vis_mask32(const uint8_t* __restrict__ vis, 
 
 struct LookupPolicy {
     static constexpr bool kShade = true;
+    __device__ __forceinline__ void slots_at(uint32_t) {}
     const uint8_t* vis; uint32_t slot, slotStride;
     uint32_t mask, j;                        /* vis_mask32 of this pixel-sample; queries answered so far */
     __device__ __forceinline__ bool occluded(rtr_v3, rtr_v3, float, rtr_v3, bool) {
@@ -160,6 +164,7 @@ __device__ __forceinline__ uint32_t raw_octant(rtr_v3 r) {
 
 struct CountOctPolicy {
     static constexpr bool kShade = false;
+    __device__ __forceinline__ void slots_at(uint32_t) {}
     unsigned long long lo, hi;                 /* eight 16-bit counters: octants 0-3, 4-7 */
     __device__ __forceinline__ void add(uint32_t oct, uint32_t n) {
         const unsigned long long v = (unsigned long long)n << ((oct & 3u) * 16u);
@@ -170,6 +175,7 @@ struct CountOctPolicy {
 
 struct EmitOctPolicy {
     static constexpr bool kShade = false;
+    __device__ __forceinline__ void slots_at(uint32_t) {}
     typedef volatile __attribute__((address_space(3))) uint32_t* lds_word;
     RayQueue queue; lds_word run; uint32_t slot, nt;         /* run[o]: next queue index of this wave's part of the octant-o run; slot as in EmitPolicy */
     __device__ __forceinline__ bool occluded(rtr_v3, rtr_v3 d, float tmax, rtr_v3 raw, bool into) {

@@ -33,11 +33,35 @@ struct SurfaceArgs {
     uint32_t n;
 };
 
+/* Arguments of the direct-lighting kernels (rtr_light_rays, rtr_shade_hits): rtr_light_params and the slots per hit the host derived
+ * from the scene's light table (rtr_light_slots). */
+struct LightArgs {
+    const float4* rays;          /* RtrRay as 2 x float4 */
+    const float4* hits;          /* RtrHit as 2 x float4 */
+    const uint32_t* seeds;       /* per hit: the base of its sample seeds, or null (then the pixel's: px * 733 + py * 1933) */
+    const uint32_t* triCount;    /* as SurfaceArgs */
+    uint32_t numInstances;
+    uint32_t n;
+    uint32_t slots;              /* Q: numShadowRays x the triangles of the first numAreaLights lights, + 1 */
+    uint32_t numAreaLights, numShadowRays, frame, width, spp;
+    uint32_t outputs;            /* RTR_LIGHT_* mask (shade) */
+    uint32_t direct;             /* light rays: 1 = the unstaged form of the kernel whatever the slot count (the test build's switch) */
+    float4* outRays;             /* light rays: n * slots RtrRay */
+    const uint8_t* occluded;     /* shade: n * slots visibility bytes */
+    float4* out;                 /* shade: RtrRadiance as 3 x float4 */
+};
+
 /* flags: RTR_QUERY_ANY | RTR_QUERY_OPAQUE (validated by the caller).  stats: the counting form, counters added there (zeroed by the caller). */
 hipError_t launch_query(const DeviceScene& sc, const QueryArgs& qa, uint32_t flags, Counters* stats, hipStream_t stream);
 /* width * height * spp camera rays of raygen.rgen:83-107, ray k = (py * width + px) * spp + i (< 2^32, checked by the caller) */
 hipError_t launch_camera_rays(const RtrCameraData& cam, uint32_t width, uint32_t height, uint32_t spp, float4* out, hipStream_t stream);
 /* one RtrSurface per hit: the renderer's surface fetch (fetch_surface) for caller hits */
 hipError_t launch_hit_surfaces(const DeviceScene& sc, const SurfaceArgs& sa, hipStream_t stream);
+/* the shadow rays raygen.rgen:206-231 and :299-303 send for each hit, at fixed slots; a slot whose ray is not sent holds the null ray */
+hipError_t launch_light_rays(const DeviceScene& sc, const LightArgs& la, hipStream_t stream);
+/* one RtrRadiance per hit: shade_sample with the visibility bytes of those slots */
+hipError_t launch_shade_hits(const DeviceScene& sc, const LightArgs& la, hipStream_t stream);
+/* tonemap_pack of n float3 read strideWords floats apart */
+hipError_t launch_tonemap_pack(const float* radiance, uint32_t strideWords, uint32_t n, uint32_t* out, hipStream_t stream);
 
 }  // namespace rtrdev

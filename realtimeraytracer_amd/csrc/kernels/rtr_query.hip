@@ -11,6 +11,8 @@
  *   k_query_tail  walks those rays again with a full-depth stack in global memory (as k_primary_tail does); if the redo list
  *                 overflowed it finds them by their sentinel in the outputs.
  * k_hit_surfaces (rtr_hit_surfaces) takes the hits further: the surface the closest-hit shader computes for each, by fetch_surface().
+ * k_light_rays / k_shade_hits / k_tonemap_pack (rtr_light_rays, rtr_shade_hits, rtr_tonemap_pack) take them to the framebuffer: what the
+ * ray-gen shader does after the closest hit, by the renderer's own light_loops() with every query at a fixed slot of its hit.
  * Compiled with the library's flags (-ffp-contract=off): the numerical contract of include/rtr_math.h.
  */
 #include "rtr_query.h"
@@ -220,6 +222,175 @@ __global__ __launch_bounds__(kSurfaceBlock) void k_hit_surfaces(DeviceScene sc, 
 
 hipError_t launch_hit_surfaces(const DeviceScene& sc, const SurfaceArgs& sa, hipStream_t s) {
     hipLaunchKernelGGL(k_hit_surfaces, dim3((uint32_t)(((uint64_t)sa.n + kSurfaceBlock - 1) / kSurfaceBlock)), dim3(kSurfaceBlock), 0, s, sc, sa);
+    return hipGetLastError();
+}
+
+/* ---- direct lighting for caller hits (rtr_light_rays, rtr_shade_hits, rtr_tonemap_pack) ------------------------------------------------
+ * What raygen.rgen:110-338 does with a closest hit, cut where the renderer's staged pipeline cuts it: the shadow rays of a hit, and —
+ * once the caller has had them answered (rtr_trace_rays, RTR_QUERY_ANY) — the sums.  Both kernels run light_loops(), the loops
+ * k_shadow_gen_oct and k_resolve run, with a policy that takes each query's place from slots_at(): hit k owns la.slots (Q) consecutive
+ * slots, sample s of light triangle T_l + ti at (T_l + ti) * numShadowRays + s, the directional light last (include/rtr.h). */
+typedef float rtr_q4 __attribute__((ext_vector_type(4)));
+
+/* What a hit is, as k_hit_surfaces decides it; the hit record, the ray's direction and the RenderArgs the device functions read:
+ * the view vector's origin (the ray's), numAreaLights, numShadowRays and the frame word.  light_sample_pos forms a sample's seed as
+ * s + px * 733 + py * 1933 + frame in 32-bit words, so handing it px = py = 0 and frame + base gives the seed s + base + frame of
+ * include/rtr.h whatever base is: the caller's seeds[k], or the pixel's px * 733 + py * 1933 (the renderer's seed for a camera ray). */
+__device__ __forceinline__ uint32_t light_hit(const DeviceScene& sc, const LightArgs& la, uint32_t k, HitRec& h, rtr_v3& dir, RenderArgs& ra) {
+    const float4 ro = la.rays[2 * (size_t)k], rb = la.rays[2 * (size_t)k + 1];
+    const float4 ha = la.hits[2 * (size_t)k], hb = la.hits[2 * (size_t)k + 1];
+    h.t = ha.x; h.u = ha.y; h.v = ha.z; h.custom = __float_as_uint(ha.w); h.prim = __float_as_uint(hb.x); h.leaf = 0;
+    dir = f4xyz(rb);
+    uint32_t base;
+    if (la.seeds) base = la.seeds[k];
+    else { const uint32_t pix = k / la.spp; base = (pix % la.width) * 733u + (pix / la.width) * 1933u; }
+    ra.cam.position[0] = ro.x; ra.cam.position[1] = ro.y; ra.cam.position[2] = ro.z;
+    ra.info.numAreaLights = la.numAreaLights; ra.info.frame = la.frame + base;
+    ra.numShadowRays = la.numShadowRays; ra.spp = 1u;
+    if (h.custom == RTR_MISS) return RTR_SURFACE_MISS;
+    if (h.custom < la.numInstances && h.prim < la.triCount[h.custom]) return h.custom < sc.numLights ? RTR_SURFACE_LIGHT : RTR_SURFACE_OBJECT;
+    return RTR_SURFACE_INVALID;
+}
+
+/* the query's ray into its slot of the hit's row: {origin, tmin 0.001} {direction, tmax}, two 16-B stores (LDS or global) */
+template <class Row>
+struct RayEmitPolicy {
+    static constexpr bool kShade = false;
+    Row row; uint32_t slot, last;
+    __device__ __forceinline__ void slots_at(uint32_t first) { slot = first == kDirectionalSlot ? last : first; }
+    __device__ __forceinline__ bool occluded(rtr_v3 o, rtr_v3 d, float tmax, rtr_v3, bool) {
+        row[2u * slot] = rtr_q4{o.x, o.y, o.z, 0.001f};
+        row[2u * slot + 1u] = rtr_q4{d.x, d.y, d.z, tmax};
+        ++slot;
+        return false;
+    }
+};
+
+/* One lane per hit, one wave per workgroup.  A hit's Q rays are 32 B apiece and 32 Q bytes from the next lane's: stored where the light
+ * loops make them, every store instruction of the wave touches 64 different cache lines, half of each.  STAGED (Q <= kLightStagedSlots):
+ * the wave's rays are made in LDS — lane l's row at l * (2 Q + 1) 16-B pieces: the odd pitch spreads the eight lanes a ds_write_b128
+ * serves together over eight different 16-B bank slots, where the dense pitch 2 Q puts them all on one whenever Q is a multiple of 4 —
+ * pre-filled with zeros, which ARE the null rays of the slots the loops skip; then the wave stores its contiguous 64 * Q * 32-byte block
+ * with lane i on the i-th consecutive 16-B piece, 1 KiB per store instruction, every line written whole.  !STAGED is the form it was
+ * compared with and the one left for light tables whose rows outgrow a workgroup's 64 KiB of LDS: zeros and rays stored straight from
+ * the loops at the 32 Q-byte lane stride.  (The pre-fill cannot be a memset ahead of the kernel in either form without writing the
+ * buffer twice.)  Both forms write the same bytes; tests/test_gpu_direct_light.py runs both against one another.  Measured on the bench
+ * frame's camera hits (1920x1080, Q = 13, 863 MB of rays): staged 0.277 ms (3.1 TB/s written), direct 0.596 ms
+ * (profiles/direct_light_rate.py, profiles/direct_light/). */
+constexpr int kLightRaysBlock = 64;
+constexpr uint32_t kLightStagedSlots = 31;       /* 64 lanes x (2 * 31 + 1) pieces x 16 B = 63 KiB */
+template <bool STAGED>
+__global__ __launch_bounds__(kLightRaysBlock) void k_light_rays(DeviceScene sc, LightArgs la) {
+    extern __shared__ rtr_q4 s_stage[];
+    typedef __attribute__((address_space(3))) rtr_q4* lds_q4;      /* keeps the accesses ds_read / ds_write */
+    const lds_q4 stage = (lds_q4)s_stage;
+    const uint32_t lane = threadIdx.x;
+    const uint64_t k0 = (uint64_t)blockIdx.x * kLightRaysBlock;
+    const bool live = k0 + lane < la.n;
+    const uint32_t k = (uint32_t)(k0 + lane);
+    const uint32_t Q = la.slots, pieces = 2u * Q, pitch = pieces + 1u;
+    rtr_q4* __restrict__ out = reinterpret_cast<rtr_q4*>(la.outRays) + k0 * pieces;          /* the wave's block */
+    const rtr_q4 zero = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (STAGED) {
+        for (uint32_t i = lane; i < kLightRaysBlock * pitch; i += kLightRaysBlock) stage[i] = zero;
+        __syncthreads();
+    } else if (live) {
+        for (uint32_t j = 0; j < pieces; ++j) out[(size_t)lane * pieces + j] = zero;
+    }
+    if (live) {
+        HitRec h;
+        rtr_v3 dir;
+        RenderArgs ra{};
+        if (light_hit(sc, la, k, h, dir, ra) == RTR_SURFACE_OBJECT) {
+            Accum acc;
+            Surface sf;
+            LocalStats st;
+            fetch_surface<false, false>(sc, ra, h, dir, false, acc, sf, st);
+            if (STAGED) {
+                RayEmitPolicy<lds_q4> pol{stage + lane * pitch, 0u, Q - 1u};
+                light_loops<RayEmitPolicy<lds_q4>, false>(sc, ra, 0u, 0u, sf, 0u, acc, pol, st);
+            } else {
+                RayEmitPolicy<rtr_q4*> pol{out + (size_t)lane * pieces, 0u, Q - 1u};
+                light_loops<RayEmitPolicy<rtr_q4*>, false>(sc, ra, 0u, 0u, sf, 0u, acc, pol, st);
+            }
+        }
+    }
+    if (STAGED) {
+        __syncthreads();
+        const uint64_t left = la.n - k0;
+        const uint32_t total = (uint32_t)(left < (uint64_t)kLightRaysBlock ? left : (uint64_t)kLightRaysBlock) * pieces;
+        /* piece p of the block belongs to row p / pieces: kept as (row, rest) and stepped by 64 pieces, one division per lane */
+        const uint32_t stepRow = (uint32_t)kLightRaysBlock / pieces, stepRest = (uint32_t)kLightRaysBlock % pieces;
+        uint32_t row = lane / pieces, rest = lane % pieces;
+        for (uint32_t p = lane; p < total; p += kLightRaysBlock) {
+            out[p] = stage[row * pitch + rest];
+            row += stepRow; rest += stepRest;
+            if (rest >= pieces) { rest -= pieces; ++row; }
+        }
+    }
+}
+
+hipError_t launch_light_rays(const DeviceScene& sc, const LightArgs& la, hipStream_t s) {
+    const uint32_t blocks = (uint32_t)(((uint64_t)la.n + kLightRaysBlock - 1) / kLightRaysBlock);
+    if (la.slots <= kLightStagedSlots && !la.direct) {
+        const size_t lds = (size_t)kLightRaysBlock * (2u * la.slots + 1u) * sizeof(rtr_q4);
+        hipLaunchKernelGGL(k_light_rays<true>, dim3(blocks), dim3(kLightRaysBlock), lds, s, sc, la);
+    } else hipLaunchKernelGGL(k_light_rays<false>, dim3(blocks), dim3(kLightRaysBlock), 0, s, sc, la);
+    return hipGetLastError();
+}
+
+/* the visibility byte of the query's slot (the caller's RTR_QUERY_ANY answers for the rays k_light_rays made) */
+struct SlotLookupPolicy {
+    static constexpr bool kShade = true;
+    const uint8_t* occ; uint32_t slot, last;
+    __device__ __forceinline__ void slots_at(uint32_t first) { slot = first == kDirectionalSlot ? last : first; }
+    __device__ __forceinline__ bool occluded(rtr_v3, rtr_v3, float, rtr_v3, bool) { return occ[slot++] != 0; }
+};
+
+/* One lane per hit: shade_sample() — fetch_surface<true> and the light loops, as k_resolve calls them for one sample of a pixel — into
+ * a zeroed Accum; `want` is the renderer's (bit 0 analytic, bit 1 unshadowed), so the same work is skipped under the same rule.  A sum
+ * that was not asked for is written as zeros. */
+constexpr int kShadeBlock = 256;
+__global__ __launch_bounds__(kShadeBlock) void k_shade_hits(DeviceScene sc, LightArgs la) {
+    const uint32_t k = blockIdx.x * kShadeBlock + threadIdx.x;
+    if (k >= la.n) return;
+    HitRec h;
+    rtr_v3 dir;
+    RenderArgs ra{};
+    const uint32_t kind = light_hit(sc, la, k, h, dir, ra);
+    const bool wantUnshadowed = (la.outputs & RTR_LIGHT_UNSHADOWED) != 0u, wantAnalytic = (la.outputs & RTR_LIGHT_ANALYTIC) != 0u;
+    const rtr_v3 zero = rtr_mk(0, 0, 0);
+    Accum acc;
+    acc.analytic = acc.shadowed = acc.unshadowed = acc.avgNormal = acc.avgPosition = zero;
+    if (kind != RTR_SURFACE_INVALID) {
+        LocalStats st;
+        SlotLookupPolicy pol{la.occluded + (size_t)k * la.slots, 0u, la.slots - 1u};
+        shade_sample<SlotLookupPolicy, false>(sc, ra, 0u, 0u, h, dir, (wantAnalytic ? 1u : 0u) | (wantUnshadowed ? 2u : 0u), acc, pol, st);
+    }
+    if (!wantUnshadowed) acc.unshadowed = zero;
+    if (!wantAnalytic) acc.analytic = zero;
+    float4* o = la.out + 3 * (size_t)k;
+    o[0] = make_float4(acc.shadowed.x, acc.shadowed.y, acc.shadowed.z, __uint_as_float(kind));
+    o[1] = make_float4(acc.unshadowed.x, acc.unshadowed.y, acc.unshadowed.z, 0.0f);
+    o[2] = make_float4(acc.analytic.x, acc.analytic.y, acc.analytic.z, 0.0f);
+}
+
+hipError_t launch_shade_hits(const DeviceScene& sc, const LightArgs& la, hipStream_t s) {
+    hipLaunchKernelGGL(k_shade_hits, dim3((uint32_t)(((uint64_t)la.n + kShadeBlock - 1) / kShadeBlock)), dim3(kShadeBlock), 0, s, sc, la);
+    return hipGetLastError();
+}
+
+/* one lane per value: raygen.rgen:345-357 (ACES, sRGB, bytes B, G, R, 255) of the three floats at radiance + k * strideWords */
+constexpr int kTonemapBlock = 256;
+__global__ __launch_bounds__(kTonemapBlock) void k_tonemap_pack(const float* __restrict__ radiance, uint32_t strideWords, uint32_t n, uint32_t* __restrict__ out) {
+    const uint32_t k = blockIdx.x * kTonemapBlock + threadIdx.x;
+    if (k >= n) return;
+    const float* r = radiance + (size_t)k * strideWords;
+    out[k] = tonemap_pack(rtr_mk(r[0], r[1], r[2]));
+}
+
+hipError_t launch_tonemap_pack(const float* radiance, uint32_t strideWords, uint32_t n, uint32_t* out, hipStream_t s) {
+    hipLaunchKernelGGL(k_tonemap_pack, dim3((uint32_t)(((uint64_t)n + kTonemapBlock - 1) / kTonemapBlock)), dim3(kTonemapBlock), 0, s, radiance, strideWords, n, out);
     return hipGetLastError();
 }
 

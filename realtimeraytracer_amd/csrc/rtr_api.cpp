@@ -1522,4 +1522,104 @@ int rtr_camera_rays_async(rtr_ctx* c, const RtrCameraData* cam, uint32_t width, 
     return RTR_OK;
 }
 
+/* ---- direct lighting for ray-query hits -------------------------------------------------------------------------------------- */
+static bool aligned4(const void* p) { return ((uintptr_t)p & 3u) == 0; }
+
+/* Q of rtr_light_slots, from the host copy of the light table (as enqueue_render counts maxRaysPerSample) */
+static int light_slots(const rtr_scene* s, const rtr_light_params* p, uint32_t* q, const char* who) {
+    if (!s || !p) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: null scene or params", who);
+    if (p->numAreaLights > s->numLights) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: numAreaLights %u > scene lights %u", who, p->numAreaLights, s->numLights);
+    if (p->numShadowRays == 0 || p->numShadowRays > 1024) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: numShadowRays %u (1 ... 1024)", who, p->numShadowRays);
+    if (p->outputs & ~(RTR_LIGHT_SHADOWED | RTR_LIGHT_UNSHADOWED | RTR_LIGHT_ANALYTIC)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: unknown output bits 0x%x", who, p->outputs);
+    uint64_t slots = 1;
+    for (uint32_t l = 0; l < p->numAreaLights; ++l) slots += (uint64_t)s->hostLights[l].numTriangles * p->numShadowRays;
+    if (slots > 0xffffffffull) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: %llu slots per hit do not fit 32 bits", who, (unsigned long long)slots);
+    *q = (uint32_t)slots;
+    return RTR_OK;
+}
+
+int rtr_light_slots(const rtr_scene* s, const rtr_light_params* p, uint32_t* slotsPerHit) {
+    if (!slotsPerHit) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_light_slots: slotsPerHit is null");
+    return light_slots(s, p, slotsPerHit, "rtr_light_slots");
+}
+
+/* the checks and the launch of rtr_light_rays[_async] (shade == false) and rtr_shade_hits[_async], enqueued on the context's stream */
+static int enqueue_light(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, uint32_t n, const rtr_light_params* p,
+                         const uint32_t* seeds, RtrRay* outRays, const uint8_t* occluded, RtrRadiance* out, bool shade, const char* who) {
+    if (!c || !s || !p) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: null context, scene or params", who);
+    if (s->ctx->device != c->device) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: the scene lives on device %d, the context on device %d", who, s->ctx->device, c->device);
+    uint32_t slots = 0;
+    const int rc = light_slots(s, p, &slots, who);
+    if (rc != RTR_OK) return rc;
+    if (shade && (p->outputs & RTR_LIGHT_ANALYTIC) && !s->hasLtc) return fail(RTR_ERR_UNSUPPORTED, "%s: RTR_LIGHT_ANALYTIC needs the LTC tables (rtr_scene_desc.ltc1/ltc2)", who);
+    if (n == 0) return RTR_OK;
+    if ((uint64_t)n * slots > 0xffffffffull) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: %u hits x %u slots do not fit 32 bits", who, n, slots);
+    const void* res = shade ? (const void*)out : (const void*)outRays;
+    const char* resName = shade ? "out" : "outRays";
+    if (!rays || !hits || !res) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: %s is null", who, !rays ? "rays" : (!hits ? "hits" : resName));
+    if (shade && !occluded) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: occluded is null", who);
+    if (!aligned16(rays) || !aligned16(hits) || !aligned16(res))
+        return fail(RTR_ERR_INVALID_ARGUMENT, "%s: %s is not 16-B aligned", who, !aligned16(rays) ? "rays" : (!aligned16(hits) ? "hits" : resName));
+    if (seeds && !aligned4(seeds)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: seeds is not 4-B aligned", who);
+    if (!seeds && (p->width == 0 || p->spp == 0)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: width %u, spp %u: without seeds the hits are pixel-samples of a frame", who, p->width, p->spp);
+    HIP_TRY(hipSetDevice(c->device));
+    rtrdev::LightArgs la{};
+    la.rays = reinterpret_cast<const float4*>(rays); la.hits = reinterpret_cast<const float4*>(hits); la.seeds = seeds;
+    la.triCount = s->triCount.p; la.numInstances = s->numInstances; la.n = n; la.slots = slots;
+    la.numAreaLights = p->numAreaLights; la.numShadowRays = p->numShadowRays; la.frame = p->frame; la.width = p->width; la.spp = p->spp;
+    la.outputs = p->outputs;
+    la.outRays = reinterpret_cast<float4*>(outRays); la.occluded = occluded; la.out = reinterpret_cast<float4*>(out);
+#ifdef RTR_TEST_HOOKS
+    if (const char* e = getenv("RTR_LIGHT_RAYS_DIRECT")) la.direct = atoi(e) != 0 ? 1u : 0u;   /* the kernel's unstaged form for a light table that would be staged */
+#endif
+    const hipError_t e = shade ? rtrdev::launch_shade_hits(s->dev, la, c->stream) : rtrdev::launch_light_rays(s->dev, la, c->stream);
+    if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: kernel launch: %s", who, hipGetErrorString(e));
+    return RTR_OK;
+}
+
+int rtr_light_rays_async(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, uint32_t n, const rtr_light_params* p,
+                         const uint32_t* seeds, RtrRay* outRays) {
+    return enqueue_light(c, s, rays, hits, n, p, seeds, outRays, nullptr, nullptr, false, "rtr_light_rays_async");
+}
+
+int rtr_light_rays(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, uint32_t n, const rtr_light_params* p,
+                   const uint32_t* seeds, RtrRay* outRays) {
+    const int rc = enqueue_light(c, s, rays, hits, n, p, seeds, outRays, nullptr, nullptr, false, "rtr_light_rays");
+    if (rc != RTR_OK || n == 0) return rc;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return RTR_OK;
+}
+
+int rtr_shade_hits_async(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, uint32_t n, const rtr_light_params* p,
+                         const uint32_t* seeds, const uint8_t* occluded, RtrRadiance* out) {
+    return enqueue_light(c, s, rays, hits, n, p, seeds, nullptr, occluded, out, true, "rtr_shade_hits_async");
+}
+
+int rtr_shade_hits(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, uint32_t n, const rtr_light_params* p,
+                   const uint32_t* seeds, const uint8_t* occluded, RtrRadiance* out) {
+    const int rc = enqueue_light(c, s, rays, hits, n, p, seeds, nullptr, occluded, out, true, "rtr_shade_hits");
+    if (rc != RTR_OK || n == 0) return rc;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return RTR_OK;
+}
+
+int rtr_tonemap_pack_async(rtr_ctx* c, const float* radiance, uint32_t strideBytes, uint32_t n, uint32_t* out) {
+    if (!c) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_tonemap_pack: null context");
+    if (strideBytes < 12 || (strideBytes & 3u)) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_tonemap_pack: strideBytes %u (a multiple of 4, at least 12)", strideBytes);
+    if (n == 0) return RTR_OK;
+    if (!radiance || !out) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_tonemap_pack: %s is null", !radiance ? "radiance" : "outBGRA8");
+    if (!aligned4(radiance) || !aligned4(out)) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_tonemap_pack: %s is not 4-B aligned", !aligned4(radiance) ? "radiance" : "outBGRA8");
+    HIP_TRY(hipSetDevice(c->device));
+    const hipError_t e = rtrdev::launch_tonemap_pack(radiance, strideBytes / 4u, n, out, c->stream);
+    if (e != hipSuccess) return fail(RTR_ERR_HIP, "rtr_tonemap_pack: kernel launch: %s", hipGetErrorString(e));
+    return RTR_OK;
+}
+
+int rtr_tonemap_pack(rtr_ctx* c, const float* radiance, uint32_t strideBytes, uint32_t n, uint32_t* out) {
+    const int rc = rtr_tonemap_pack_async(c, radiance, strideBytes, n, out);
+    if (rc != RTR_OK || n == 0) return rc;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return RTR_OK;
+}
+
 }  // extern "C"

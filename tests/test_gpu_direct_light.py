@@ -1,0 +1,432 @@
+"""Direct lighting for ray-query hits (rtr_light_rays, rtr_shade_hits, rtr_tonemap_pack) on the device.
+  * camera rays -> closest hit -> light rays -> occlusion -> shade -> tone map IS the renderer: at 1 spp the shadowed sum equals
+    RTR_IMAGE_HDR bit for bit and the three packed images equal the renderer's byte for byte (tolerance 0: the same device functions
+    compiled with the same flags, through other kernels — k_query's BVH2 walk instead of the staged pipeline's queue walk);
+  * the light rays against a float64 restatement (tests/light_witness.py), the sums for rays that are not camera rays against the
+    witness's own shading fed the device's visibility bytes;
+  * properties that need no reference, and the plumbing."""
+import ctypes as C
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from realtimeraytracer_amd import _abi as A
+from realtimeraytracer_amd import api, scenes
+from light_witness import LightWitness, expected_light_rays
+from test_gpu_surfaces import Expect, _hits, random_rays, tri_counts
+
+pytestmark = pytest.mark.gpu
+
+MISS = 0xffffffff
+ALL3 = A.LIGHT_SHADOWED | A.LIGHT_UNSHADOWED | A.LIGHT_ANALYTIC
+ALL5 = A.IMAGES_RAYGEN5 | A.IMG_BIT(A.IMAGE_HDR)
+INVALID, UNSUPPORTED = -1, -4            # RTR_ERR_INVALID_ARGUMENT, RTR_ERR_UNSUPPORTED (include/rtr.h)
+
+
+def _np(x):
+    return x.cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+
+
+def _bits(x):
+    return _np(x).view(np.uint32)
+
+
+def _setup(case, ltc=True):
+    kw = dict(ltc=scenes.shipped_ltc()) if ltc else {}
+    if case == "cornell_box":
+        return scenes.cornell_box(128, 128, **kw), 128, 128
+    return scenes.textured_room(160, 100, **kw), 160, 100
+
+
+def _compose(scene, rays, hits, p, seeds=None):
+    lr = api.light_rays(scene, rays, hits, p, seeds=seeds)
+    occ = api.trace_rays(scene, lr, any_hit=True).occluded
+    return lr, occ, api.shade_hits(scene, rays, hits, p, occ, seeds=seeds)
+
+
+# ---- 1. the composed route is the renderer ---------------------------------------------------------------------------------------
+@pytest.mark.parametrize("case", ["cornell_box", "textured_room"])
+def test_composed_route_equals_the_renderer(gpu_ctx, scene_cache, case):
+    s, w, h = _setup(case)
+    scene = api.Scene(gpu_ctx, s.desc)
+    frame = api.Frame(gpu_ctx, w, h, ALL5)
+    fb = api.Frame(gpu_ctx, w, h, A.IMAGES_FRAMEBUFFER | A.IMG_BIT(A.IMAGE_HDR))
+    rays = api.camera_rays(gpu_ctx, s.camera, w, h, 1)
+    q = api.trace_rays(scene, rays)
+    for f in (0, 5):
+        api.render(scene, s.camera, s.scene_info(f), api.make_params(w, h, spp=1, images=ALL5), frame)
+        p = api.make_light_params(s.num_lights, 3, f, w, 1, ALL3)
+        lr, occ, rad = _compose(scene, rays, q, p)
+        raw = _np(rad.raw)
+        assert np.isfinite(raw[:, [0, 1, 2, 4, 5, 6, 8, 9, 10]]).all()          # divergence D6 (an overflowing occluded sample) is not in play
+        hdr = frame.download(A.IMAGE_HDR).reshape(-1, 4)
+        d = int((_bits(rad.shadowed) != hdr[:, :3].view(np.uint32)).any(1).sum())
+        assert d == 0, f"{case} frame {f}: {d} of {w * h} pixels differ from RTR_IMAGE_HDR"
+        for name, img in (("shadowed", A.IMAGE_SHADOWED), ("unshadowed", A.IMAGE_UNSHADOWED), ("analytic", A.IMAGE_ANALYTIC)):
+            got = _np(api.tonemap_pack(gpu_ctx, getattr(rad, name))).view(np.uint32)
+            d = int((got != frame.download(img).reshape(-1)).sum())
+            assert d == 0, f"{case} frame {f}: {d} of {w * h} pixels differ in the {name} image"
+        # the framebuffer-only form (want = 0): occluded samples' BRDFs skipped on both sides
+        api.render(scene, s.camera, s.scene_info(f), api.make_params(w, h, spp=1, images=A.IMAGES_FRAMEBUFFER | A.IMG_BIT(A.IMAGE_HDR)), fb)
+        only = api.shade_hits(scene, rays, q, api.make_light_params(s.num_lights, 3, f, w, 1, A.LIGHT_SHADOWED), occ)
+        assert (_bits(only.shadowed) == fb.download(A.IMAGE_HDR).reshape(-1, 4)[:, :3].view(np.uint32)).all()
+        assert (_np(api.tonemap_pack(gpu_ctx, only.shadowed)).view(np.uint32) == fb.download(A.IMAGE_SHADOWED).reshape(-1)).all()
+        assert not _np(only.unshadowed).any() and not _np(only.analytic).any()
+    kind = _np(rad.kind)
+    assert (kind == A.SURFACE_OBJECT).mean() > 0.3
+    if case == "cornell_box":              # the one-sided light: object hits above it own null slots
+        Q = api.light_slots(scene, p)
+        null = ~_np(lr).reshape(w * h, Q, 8).any(2)
+        assert (null[kind == A.SURFACE_OBJECT][:, :Q - 1].all(1)).any() and not null[kind == A.SURFACE_OBJECT].all()
+        assert {A.SURFACE_LIGHT, A.SURFACE_MISS} <= set(kind.tolist())
+    else:
+        assert s.desc.hdri and (kind == A.SURFACE_MISS).any()
+
+
+# ---- 2. the light rays are the shader's ----------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("case", ["cornell_box", "textured_room"])
+def test_light_rays_equal_the_float64_restatement(gpu_ctx, scene_cache, case):
+    s, w, h = _setup(case)
+    scene = api.Scene(gpu_ctx, s.desc)
+    rays = api.camera_rays(gpu_ctx, s.camera, w, h, 1)
+    q = api.trace_rays(scene, rays)
+    wit = LightWitness(s.desc)
+    surf = Expect(wit, _np(rays), _np(q.hits))
+    for f in (0, 5):
+        p = api.make_light_params(s.num_lights, 3, f, w, 1)
+        Q = api.light_slots(scene, p)
+        got = _np(api.light_rays(scene, rays, q, p)).reshape(w * h, Q, 8).astype(np.float64)
+        k = np.arange(w * h, dtype=np.uint32)
+        with np.errstate(over="ignore"):
+            base = (k % np.uint32(w)) * np.uint32(733) + (k // np.uint32(w)) * np.uint32(1933)
+        exp = expected_light_rays(wit, surf, base, f, s.num_lights, 3)
+        assert exp.rays.shape == got.shape
+        share = exp.boundary.mean()
+        print(f"{case} frame {f}: {int(exp.boundary.sum())} of {w * h} hits on a decision boundary ({share:.4%})")
+        assert share <= 0.005
+        ok = ~exp.boundary
+        gnull = ~got.any(2)
+        assert (gnull[ok] == exp.null[ok]).all(), f"{case}: {(gnull[ok] != exp.null[ok]).any(1).sum()} hits differ in which slots are null"
+        live = ok[:, None] & ~exp.null
+        assert live.any()
+        err = np.abs(got - exp.rays)
+        for name, cols, bound in (("origin", slice(0, 3), exp.bound_o), ("direction", slice(4, 7), exp.bound_d)):
+            bad = live & (err[:, :, cols].max(2) > bound)
+            assert not bad.any(), f"{case}: {name} of {int(bad.sum())} rays beyond the bound, worst {err[:, :, cols].max(2)[bad].max():.3e}"
+        bad = live & (err[:, :, 7] > exp.bound_t)
+        assert not bad.any(), f"{case}: tmax of {int(bad.sum())} rays beyond the bound"
+        assert (got[live][:, 3] == np.float32(0.001)).all()
+
+
+# ---- 3. shading for rays that are not camera rays ------------------------------------------------------------------------------------
+@pytest.mark.parametrize("case,p99", [("cornell_box", 1e-3), ("textured_room", 1e-2)])
+def test_shading_of_random_rays_equals_the_witness(gpu_ctx, scene_cache, case, p99):
+    s, w, h = _setup(case)
+    scene = api.Scene(gpu_ctx, s.desc)
+    st = scene.stats()
+    n = 20000
+    rays = torch.from_numpy(random_rays(st.boundsMin[:], st.boundsMax[:], n, seed=77)).cuda()
+    seeds = np.random.default_rng(9).integers(0, 2 ** 32, n, dtype=np.uint64).astype(np.uint32)
+    q = api.trace_rays(scene, rays)
+    p = api.make_light_params(s.num_lights, 3, 11, 0, 1, ALL3)
+    lr, occ, rad = _compose(scene, rays, q, p, seeds=torch.from_numpy(seeds.view(np.int32)).cuda())
+    wit = LightWitness(s.desc)
+    Q = api.light_slots(scene, p)
+    want = wit.shade(_np(rays), _np(q.hits), seeds, 11, s.num_lights, 3, _np(occ).reshape(n, Q))
+    kind = _np(rad.kind)
+    assert (kind == want["kind"]).all()
+    assert (kind == A.SURFACE_OBJECT).sum() >= 4000           # enough shaded hits for a 99 % quantile and a 0.5 % share to mean something (the room is open to the sky)
+    for name in ("shadowed", "unshadowed", "analytic"):
+        g, e = _np(getattr(rad, name)).astype(np.float64), want[name]
+        rel = (np.abs(g - e) / np.maximum(np.abs(e), 1e-3)).max(1)
+        print(f"{case} {name}: median {np.median(rel):.2e}, p99 {np.percentile(rel, 99):.2e}, {(rel > 10 * p99).sum()} of {n} beyond 10 x {p99}")
+        assert np.median(rel) <= 5e-5, (name, np.median(rel))
+        assert np.percentile(rel, 99) <= p99, (name, np.percentile(rel, 99))
+        assert (rel > 10 * p99).mean() <= 0.005, (name, (rel > 10 * p99).sum())
+
+
+# ---- 4. properties that need no reference ----------------------------------------------------------------------------------------------
+def test_visibility_bytes_drive_the_shadowed_sum(gpu_ctx, scene_cache):
+    s, w, h = _setup("cornell_box")
+    scene = api.Scene(gpu_ctx, s.desc)
+    rays = api.camera_rays(gpu_ctx, s.camera, w, h, 1)
+    q = api.trace_rays(scene, rays)
+    p = api.make_light_params(s.num_lights, 3, 2, w, 1, ALL3)
+    Q = api.light_slots(scene, p)
+    lr, occ, rad = _compose(scene, rays, q, p)
+    zero = api.shade_hits(scene, rays, q, p, torch.zeros_like(occ))
+    assert (_bits(zero.shadowed) == _bits(zero.unshadowed)).all()
+    assert (_bits(zero.unshadowed) == _bits(rad.unshadowed)).all() and (_bits(zero.analytic) == _bits(rad.analytic)).all()
+    ones = api.shade_hits(scene, rays, q, p, torch.ones_like(occ))
+    live = _np(lr).reshape(w * h, Q, 8).any(2).all(1) & (_np(rad.kind) == A.SURFACE_OBJECT)
+    assert live.sum() > 100 and not _np(ones.shadowed)[live].any()
+    assert (_bits(ones.unshadowed) == _bits(rad.unshadowed)).all()
+    # outputs not asked for are zero, and asking for more does not change the shadowed sum
+    for outs in (A.LIGHT_SHADOWED, A.LIGHT_SHADOWED | A.LIGHT_UNSHADOWED, A.LIGHT_SHADOWED | A.LIGHT_ANALYTIC, 0):
+        r = api.shade_hits(scene, rays, q, api.make_light_params(s.num_lights, 3, 2, w, 1, outs), occ)
+        assert (_bits(r.shadowed) == _bits(rad.shadowed)).all()
+        assert (_bits(r.unshadowed) == (_bits(rad.unshadowed) if outs & A.LIGHT_UNSHADOWED else 0)).all()
+        assert (_bits(r.analytic) == (_bits(rad.analytic) if outs & A.LIGHT_ANALYTIC else 0)).all()
+        assert not _bits(r.raw)[:, [7, 11]].any()
+    # null rays are never occluded
+    null = ~_np(lr).any(1)
+    assert null.any() and not _np(occ)[null].any()
+    every = api.trace_rays(scene, torch.zeros((4096, 8), dtype=torch.float32, device="cuda"), any_hit=True).occluded
+    assert not _np(every).any()
+
+
+def test_misses_lights_and_invalid_hits(gpu_ctx, scene_cache):
+    for case in ("cornell_box", "textured_room"):
+        s, w, h = _setup(case)
+        scene = api.Scene(gpu_ctx, s.desc)
+        counts = tri_counts(LightWitness(s.desc))
+        ninst, obj = len(counts), s.num_lights
+        rows = [(0.0, 0.0, MISS, MISS)] * 40 + [(0.2, 0.3, 0, 0), (0.0, 0.0, 0, counts[0] - 1)] + \
+               [(0.2, 0.2, ninst, 0), (0.2, 0.2, 0xfffffffe, 0), (0.2, 0.2, obj, counts[obj]), (0.2, 0.2, 0, counts[0]), (0.2, 0.2, obj, 0xfffffffe)]
+        hits = _hits(rows)
+        n = len(rows)
+        rng = np.random.default_rng(3)
+        rays = np.zeros((n, 8), np.float32)
+        d = rng.normal(size=(n, 3))
+        rays[:, 4:7], rays[:, 7] = d / np.linalg.norm(d, axis=1, keepdims=True), 10000.0
+        p = api.make_light_params(s.num_lights, 3, 0, 8, 1, ALL3)
+        Q = api.light_slots(scene, p)
+        lr = api.light_rays(scene, rays, hits, p)                      # numpy in, numpy out
+        assert isinstance(lr, np.ndarray) and lr.shape == (n * Q, 8) and not lr.any()
+        rad = api.shade_hits(scene, rays, hits, p, np.ones(n * Q, np.uint8))
+        assert isinstance(rad.raw, np.ndarray)
+        assert rad.kind.tolist() == [A.SURFACE_MISS] * 40 + [A.SURFACE_LIGHT] * 2 + [A.SURFACE_INVALID] * 5
+        surf = api.hit_surfaces(scene, rays, hits)
+        for name in ("shadowed", "unshadowed", "analytic"):
+            x = getattr(rad, name)
+            assert (x[:42].view(np.uint32) == surf.color[:42].view(np.uint32)).all(), name      # the sky / the light's colour
+            assert not x[42:].view(np.uint32).any()
+        assert (rad.shadowed[40:42] == np.array(s.desc.lights[0].color[:3], np.float32)).all()
+        if case == "textured_room":
+            assert len(np.unique(rad.shadowed[:40, 0])) > 10           # the HDRI, per direction
+
+
+def test_seeds_frames_and_light_counts(gpu_ctx, scene_cache):
+    s, w, h = _setup("cornell_box")
+    scene = api.Scene(gpu_ctx, s.desc)
+    rays = api.camera_rays(gpu_ctx, s.camera, w, h, 1)
+    q = api.trace_rays(scene, rays)
+    p = api.make_light_params(s.num_lights, 3, 4, w, 1, ALL3)
+    lr, occ, rad = _compose(scene, rays, q, p)
+    k = torch.arange(w * h, device="cuda", dtype=torch.int64)
+    seeds = ((k % w) * 733 + (k // w) * 1933).to(torch.int32)
+    lr2, occ2, rad2 = _compose(scene, rays, q, api.make_light_params(s.num_lights, 3, 4, 0, 0, ALL3), seeds=seeds)
+    assert torch.equal(lr.view(torch.int32), lr2.view(torch.int32)) and torch.equal(rad.raw.view(torch.int32), rad2.raw.view(torch.int32))
+    # the frame enters the seeds; frame f with seeds + 1 is frame f + 1
+    lr3 = api.light_rays(scene, rays, q, api.make_light_params(s.num_lights, 3, 5, w, 1))
+    assert not torch.equal(lr, lr3)
+    assert torch.equal(lr3, api.light_rays(scene, rays, q, api.make_light_params(s.num_lights, 3, 4, 0, 0), seeds=seeds + 1))
+    # slot arithmetic
+    ntri = sum(s.desc.lights[l].numTriangles for l in range(s.num_lights))
+    assert api.light_slots(scene, p) == 3 * ntri + 1 and api.light_slots(scene, api.make_light_params(s.num_lights, 5)) == 5 * ntri + 1
+    p0 = api.make_light_params(0, 3, 4, w, 1, ALL3)
+    assert api.light_slots(scene, p0) == 1
+    lr0, occ0, rad0 = _compose(scene, rays, q, p0)
+    Q = api.light_slots(scene, p)
+    assert lr0.shape == (w * h, 8) and torch.equal(lr0, lr.reshape(w * h, Q, 8)[:, Q - 1])       # only the directional slot is left
+    for bad in (api.make_light_params(s.num_lights + 1, 3), api.make_light_params(s.num_lights, 0)):
+        with pytest.raises(api.RtrError) as e:
+            api.light_slots(scene, bad)
+        assert e.value.status == INVALID
+
+
+def test_both_forms_of_the_light_ray_kernel_write_the_same_bytes(scene_cache):
+    """the staged kernel (rays made in LDS, stored as one contiguous block per wave) against the direct one, which the test build of
+    the library selects by RTR_LIGHT_RAYS_DIRECT; n is not a multiple of 64, so the last wave is partial"""
+    code = (
+        "import os, sys, torch\n"
+        "sys.path.insert(0, sys.argv[1])\n"
+        "from realtimeraytracer_amd import api, scenes\n"
+        "ctx = api.Context(0, test_hooks=True)\n"
+        "out = []\n"
+        "for s in (scenes.cornell_box(100, 75), scenes.textured_room(100, 75)):\n"
+        "    scene = api.Scene(ctx, s.desc)\n"
+        "    rays = api.camera_rays(ctx, s.camera, 100, 75, 1)[:7475]\n"
+        "    q = api.trace_rays(scene, rays)\n"
+        "    for nsr in (1, 3, 4):\n"
+        "        p = api.make_light_params(s.num_lights, nsr, 1, 100, 1)\n"
+        "        got = []\n"
+        "        for direct in ('0', '1'):\n"
+        "            os.environ['RTR_LIGHT_RAYS_DIRECT'] = direct\n"
+        "            got.append(api.light_rays(scene, rays, q.hits[:7475], p).view(torch.int32).clone())\n"
+        "        assert bool(got[0].any()) and torch.equal(got[0], got[1]), (s.name, nsr)\n"
+        "print('SAME')\n")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, RTR_SCENE_CACHE=scene_cache)
+    r = subprocess.run([sys.executable, "-c", code, root], capture_output=True, text=True, timeout=300, env=env)
+    assert r.returncode == 0 and "SAME" in r.stdout, r.stdout + r.stderr
+
+
+def test_rays_follow_updated_lights(gpu_ctx, scene_cache):
+    s, w, h = _setup("cornell_box")
+    scene = api.Scene(gpu_ctx, s.desc)
+    rays = api.camera_rays(gpu_ctx, s.camera, w, h, 1)
+    q = api.trace_rays(scene, rays)
+    p = api.make_light_params(s.num_lights, 3, 0, w, 1)
+    Q = api.light_slots(scene, p)
+    obj = _np(q.custom_index) >= s.num_lights
+    before = _np(api.light_rays(scene, rays, q, p)).reshape(w * h, Q, 8)
+    assert (~before[obj][:, :Q - 1].any(2)).any()                       # one-sided: some surface points see the light's back
+    # two-sided: every area slot of an object hit is live
+    two = A.RtrAreaLightInfo.from_buffer_copy(bytes(s.host.lightInfos()[0]))
+    two.isTwoSided = 1
+    scene.update_lights([two])
+    after = _np(api.light_rays(scene, rays, q, p)).reshape(w * h, Q, 8)
+    assert after[obj][:, :Q - 1].any(2).all()
+    front = before[:, :Q - 1].any(2)
+    assert (after[:, :Q - 1][front] == before[:, :Q - 1][front]).all()
+    # moved: the light 60 units down (its instance and its info together); the rays end on the new plane
+    moved = A.RtrAreaLightInfo.from_buffer_copy(bytes(two))
+    moved.transform[13] -= 60.0
+    inst = [A.RtrInstance.from_buffer_copy(s.desc.instances[i]) for i in range(s.desc.numInstances)]
+    for i in inst:
+        if i.customIndex == 0:
+            i.transform[7] -= 60.0
+    y0 = np.array(two.transform[:], np.float64).reshape(4, 4).T[1, 3]
+    scene.update_instances(inst, [moved])
+    q2 = api.trace_rays(scene, rays)
+    lr = _np(api.light_rays(scene, rays, q2, p)).reshape(w * h, Q, 8).astype(np.float64)
+    area = lr[_np(q2.custom_index) >= s.num_lights][:, :Q - 1].reshape(-1, 8)
+    end_y = area[:, 1] + area[:, 5] * (area[:, 7] + 0.5)
+    assert np.abs(end_y - (y0 - 60.0)).max() < 0.05, np.abs(end_y - (y0 - 60.0)).max()
+
+
+# ---- 5. plumbing -----------------------------------------------------------------------------------------------------------------------
+def test_plumbing(gpu_ctx, scene_cache):
+    s, w, h = _setup("cornell_box", ltc=False)
+    scene = api.Scene(gpu_ctx, s.desc)
+    lib, ctx = gpu_ctx.lib, gpu_ctx.h
+    rays = api.camera_rays(gpu_ctx, s.camera, 8, 8, 1)
+    q = api.trace_rays(scene, rays)
+    p = api.make_light_params(s.num_lights, 3, 0, 8, 1, A.LIGHT_SHADOWED | A.LIGHT_UNSHADOWED)
+    Q = api.light_slots(scene, p)
+    out_r = torch.full((64 * Q, 8), 7.0, dtype=torch.float32, device="cuda")
+    out_s = torch.full((64, 12), 7.0, dtype=torch.float32, device="cuda")
+    out_t = torch.full((64,), 7, dtype=torch.int32, device="cuda")
+    occ = torch.zeros(64 * Q + 1, dtype=torch.uint8, device="cuda")
+    seeds = torch.zeros(65, dtype=torch.int32, device="cuda")
+    rp, hp, pp = A.VP(rays.data_ptr()), A.VP(q.hits.data_ptr()), C.byref(p)
+    orp, osp, otp, ocp, sdp = (A.VP(x.data_ptr()) for x in (out_r, out_s, out_t, occ, seeds))
+    # n == 0 does nothing, whatever the pointers
+    for fn in (lib.rtr_light_rays, lib.rtr_light_rays_async):
+        assert fn(ctx, scene.h, None, None, 0, pp, None, None) == 0
+    for fn in (lib.rtr_shade_hits, lib.rtr_shade_hits_async):
+        assert fn(ctx, scene.h, None, None, 0, pp, None, None, None) == 0
+    for fn in (lib.rtr_tonemap_pack, lib.rtr_tonemap_pack_async):
+        assert fn(ctx, None, 48, 0, None) == 0
+    assert api.light_rays(scene, rays[:0], q.hits[:0], p).shape == (0, 8)
+    assert api.shade_hits(scene, rays[:0], q.hits[:0], p, occ[:0]).raw.shape == (0, 12)
+    assert api.tonemap_pack(gpu_ctx, out_s[:0]).shape == (0,)
+    # null and misaligned pointers
+    for fn in (lib.rtr_light_rays, lib.rtr_light_rays_async):
+        for a in ((None, hp, orp), (rp, None, orp), (rp, hp, None), (A.VP(rays.data_ptr() + 4), hp, orp), (rp, A.VP(q.hits.data_ptr() + 8), orp),
+                  (rp, hp, A.VP(out_r.data_ptr() + 4))):
+            assert fn(ctx, scene.h, a[0], a[1], 64, pp, None, a[2]) == INVALID
+        assert b"16-B aligned" in lib.rtr_last_error()
+        assert fn(ctx, scene.h, rp, hp, 64, pp, A.VP(seeds.data_ptr() + 2), orp) == INVALID and b"4-B aligned" in lib.rtr_last_error()
+        assert fn(ctx, scene.h, rp, hp, 64, None, None, orp) == INVALID
+        assert fn(None, scene.h, rp, hp, 64, pp, None, orp) == INVALID and fn(ctx, None, rp, hp, 64, pp, None, orp) == INVALID
+        assert fn(ctx, scene.h, rp, hp, 64, C.byref(api.make_light_params(s.num_lights, 3, 0, 0, 1)), None, orp) == INVALID     # no seeds, no width
+    for fn in (lib.rtr_shade_hits, lib.rtr_shade_hits_async):
+        for a in ((None, hp, ocp, osp), (rp, None, ocp, osp), (rp, hp, None, osp), (rp, hp, ocp, None), (rp, hp, ocp, A.VP(out_s.data_ptr() + 8))):
+            assert fn(ctx, scene.h, a[0], a[1], 64, pp, None, a[2], a[3]) == INVALID
+    for fn in (lib.rtr_tonemap_pack, lib.rtr_tonemap_pack_async):
+        for a in ((None, 48, otp), (osp, 48, None), (A.VP(out_s.data_ptr() + 2), 48, otp), (osp, 8, otp), (osp, 14, otp)):
+            assert fn(ctx, a[0], a[1], 64, a[2]) == INVALID
+    # n * Q past 32 bits is refused
+    big = (2 ** 32 - 1) // Q + 1
+    assert lib.rtr_light_rays_async(ctx, scene.h, rp, hp, big, pp, None, orp) == INVALID and b"32 bits" in lib.rtr_last_error()
+    assert lib.rtr_shade_hits_async(ctx, scene.h, rp, hp, big, pp, None, ocp, osp) == INVALID
+    # the analytic sum needs the scene's LTC tables
+    pa = api.make_light_params(s.num_lights, 3, 0, 8, 1, ALL3)
+    rc = lib.rtr_shade_hits(ctx, scene.h, rp, hp, 64, C.byref(pa), None, ocp, osp)
+    assert rc == UNSUPPORTED and b"LTC" in lib.rtr_last_error()
+    torch.cuda.synchronize()
+    assert bool((out_r == 7.0).all()) and bool((out_s == 7.0).all()) and bool((out_t == 7).all())
+    # the calls themselves; an unaligned occluded pointer and offset seeds are fine
+    assert lib.rtr_light_rays(ctx, scene.h, rp, hp, 64, pp, A.VP(seeds.data_ptr() + 4), orp) == 0
+    o1 = api.trace_rays(scene, out_r, any_hit=True).occluded
+    occ[1:] = o1
+    assert lib.rtr_shade_hits(ctx, scene.h, rp, hp, 64, pp, A.VP(seeds.data_ptr() + 4), A.VP(occ.data_ptr() + 1), osp) == 0
+    assert lib.rtr_tonemap_pack(ctx, osp, 48, 64, otp) == 0
+    z = torch.zeros(64, dtype=torch.int32, device="cuda")
+    ref = api.shade_hits(scene, rays, q, p, o1, seeds=z)
+    assert torch.equal(out_r, api.light_rays(scene, rays, q, p, seeds=z)) and torch.equal(out_s.view(torch.int32), ref.raw.view(torch.int32))
+    assert torch.equal(out_t, api.tonemap_pack(gpu_ctx, ref.shadowed))
+    # strides: a packed float3 array and a 16-B-stride image give the same pixels
+    packed = ref.shadowed.contiguous()
+    rgba = torch.cat([packed, torch.ones((64, 1), device="cuda")], 1)
+    assert torch.equal(api.tonemap_pack(gpu_ctx, packed), out_t) and torch.equal(api.tonemap_pack(gpu_ctx, rgba), out_t)
+    # numpy in, numpy out
+    ln = api.light_rays(scene, _np(rays), _np(q.hits), p, seeds=np.zeros(64, np.uint32))
+    assert isinstance(ln, np.ndarray) and (ln.view(np.uint32) == _bits(out_r)).all()
+    sn = api.shade_hits(scene, _np(rays), _np(q.hits), p, _np(o1), seeds=np.zeros(64, np.uint32))
+    assert isinstance(sn.shadowed, np.ndarray) and (sn.raw.view(np.uint32) == _bits(out_s)).all()
+    tn = api.tonemap_pack(gpu_ctx, sn.shadowed)
+    assert isinstance(tn, np.ndarray) and tn.dtype == np.uint32 and (tn == _np(out_t).view(np.uint32)).all()
+    # the Python layer refuses before anything is launched
+    for bad in (lambda: api.light_rays(scene, rays, q.hits[:10], p), lambda: api.light_rays(scene, rays.cpu(), q, p),
+                lambda: api.light_rays(scene, rays, q, p, seeds=z[:10]), lambda: api.light_rays(scene, rays, q, p, seeds=z.float()),
+                lambda: api.shade_hits(scene, rays, q, p, o1[:-1]), lambda: api.shade_hits(scene, rays, q, p, o1.int()),
+                lambda: api.shade_hits(scene, rays, q, p, q), lambda: api.light_rays(scene, rays, api.trace_rays(scene, rays, any_hit=True), p),
+                lambda: api.tonemap_pack(gpu_ctx, ref.shadowed.double()), lambda: api.tonemap_pack(gpu_ctx, ref.raw[:, 0:2])):
+        with pytest.raises(ValueError):
+            bad()
+
+
+def test_five_launches_on_a_caller_stream_without_a_host_join(scene_cache):
+    s, w, h = _setup("cornell_box")
+    ctx = api.Context(0)
+    scene = api.Scene(ctx, s.desc)
+    p = api.make_light_params(s.num_lights, 3, 1, w, 1, ALL3)
+    rays0 = api.camera_rays(ctx, s.camera, w, h, 1)
+    q0 = api.trace_rays(scene, rays0)
+    _, _, ref = _compose(scene, rays0, q0, p)
+    ref_px = api.tonemap_pack(ctx, ref.shadowed).clone()
+    ref_raw = ref.raw.clone()
+    stream = torch.cuda.Stream()
+    with torch.cuda.stream(stream):
+        ctx.set_stream(stream.cuda_stream)
+        rays = api.camera_rays(ctx, s.camera, w, h, 1) * 1.0                 # torch work on the stream between the calls
+        q = api.trace_rays(scene, rays, asynchronous=True)
+        lr = api.light_rays(scene, rays, q, p, asynchronous=True)
+        occ = api.trace_rays(scene, lr, any_hit=True, asynchronous=True)
+        rad = api.shade_hits(scene, rays, q, p, occ, asynchronous=True)
+        px = api.tonemap_pack(ctx, rad.shadowed, asynchronous=True)
+        got_raw, got_px = rad.raw.view(torch.int32) + 0, px + 0              # consumed on the same stream, no host join in between
+        stream.synchronize()
+        assert torch.equal(got_raw, ref_raw.view(torch.int32)) and torch.equal(got_px, ref_px)
+        ctx.set_stream(None)
+    with pytest.raises(ValueError):
+        api.light_rays(scene, rays, q, p, asynchronous=True)                 # the context is no longer on torch's current stream
+    scene.close(); ctx.close()
+
+
+def test_direct_light_in_chunks_equals_one_pass(gpu_ctx, scene_cache):
+    s, w, h = _setup("textured_room")
+    scene = api.Scene(gpu_ctx, s.desc)
+    rays = api.camera_rays(gpu_ctx, s.camera, w, h, 1)[:w * h - 37]
+    n = len(rays)
+    p = api.make_light_params(s.num_lights, 3, 3, w, 1, ALL3)
+    Q = api.light_slots(scene, p)
+    whole = api.direct_light(scene, rays, params=p)
+    _, _, ref = _compose(scene, rays, api.trace_rays(scene, rays), p)
+    assert torch.equal(whole.raw.view(torch.int32), ref.raw.view(torch.int32))
+    chunk = n // 3 - 11                                                      # four chunks, the last one short; not a multiple of the width
+    assert n % chunk and chunk % w and -(-n // chunk) >= 3
+    parts = api.direct_light(scene, rays, params=p, max_ray_bytes=chunk * Q * 32 + 5)
+    assert torch.equal(parts.raw.view(torch.int32), whole.raw.view(torch.int32))
+    seeds = torch.arange(n, device="cuda", dtype=torch.int32) * 7919
+    a = api.direct_light(scene, rays, api.trace_rays(scene, rays), params=p, seeds=seeds)
+    b = api.direct_light(scene, rays, params=p, seeds=seeds, max_ray_bytes=chunk * Q * 32)
+    assert torch.equal(a.raw.view(torch.int32), b.raw.view(torch.int32)) and not torch.equal(a.raw, whole.raw)
+    assert a.shadowed.shape == (n, 3) and a.kind.dtype == torch.int32

@@ -376,6 +376,33 @@ int  rtr_trace_rays_async(rtr_ctx* ctx, const rtr_scene* scene, const RtrRay* ra
 /* The same, then joins ctx's stream (only that stream).  stats (may be NULL): run the counting form of the kernels and fill it. */
 int  rtr_trace_rays(rtr_ctx* ctx, const rtr_scene* scene, const RtrRay* rays, uint32_t numRays, uint32_t flags,
                     RtrHit* hits, uint8_t* occluded, rtr_query_stats* stats);
+/* ---- queued occlusion queries ----
+ * A second way to answer occlusion rays, with the renderer's own any-hit machinery: the rays are binned by direction octant into a
+ * queue of ray indices, persistent waves walk the 4-wide tree and refill their finished lanes from it, and the few rays that need a
+ * deeper stack are finished over the BVH2.  occluded[k] is BYTE FOR BYTE what rtr_trace_rays(..., RTR_QUERY_ANY | the same
+ * RTR_QUERY_OPAQUE bit) writes for the same rays — every k < numRays is written, 0 or 1; a null ray, a ray with !(tmax > tmin) or
+ * with a non-finite origin or direction or a zero direction is 0 and costs no walk; every ray's own tmin is honoured — only the work is
+ * scheduled differently: worth it for long arrays of incoherent rays (the light rays of a frame), not for a handful.
+ * flags: 0 or RTR_QUERY_OPAQUE; RTR_QUERY_ANY is accepted and ignored (the query is any-hit by nature); other bits are refused.
+ * The queue lives in SCRATCH THE CALLER OWNS: rtr_occlusion_scratch_bytes(numRays) bytes of device memory (a multiple of 16, monotone
+ * in numRays; pure arithmetic, no device is touched), 16-B aligned, free for reuse once the query has run; it need not be initialised
+ * and nothing is kept in it between calls.  Beside it the call uses the context's small fixed-size query scratch (the deep stacks and
+ * the counters rtr_trace_rays uses, allocated by the context's first query of either kind); apart from that first use it allocates
+ * nothing and never joins the host.  rays, occluded: DEVICE pointers, 16-B aligned.  ENQUEUED on ctx's stream; calls on one context
+ * are ordered on its stream; the scene may belong to another context of the same device.  numRays == 0 does nothing.
+ * RTR_ERR_INVALID_ARGUMENT (with a message) for a null or misaligned pointer the call needs, a scratch smaller than
+ * rtr_occlusion_scratch_bytes(numRays), unknown flag bits or a scene on another device. */
+int  rtr_occlusion_scratch_bytes(uint32_t numRays, size_t* bytes);
+int  rtr_trace_occlusion_async(rtr_ctx* ctx, const rtr_scene* scene, const RtrRay* rays, uint32_t numRays, uint32_t flags,
+                               void* scratch, size_t scratchBytes, uint8_t* occluded);
+/* The same, then joins ctx's stream (only that stream).  stats (may be NULL): run the counting form of the kernels and fill it:
+ * numRays = the well-formed rays (finite origin and direction, direction not zero), whether their interval is empty or not — what
+ * rtr_frame_stats counts as shadow rays when the rays are rtr_light_rays'; null rays are not counted.  numNodeVisits = 4-wide
+ * record visits + the BVH2 visits of the tailRays rays that were walked again; numTriTests, numAlphaTests: both walks.  For the light
+ * rays of a frame's camera hits these are the renderer's any-hit counters with the tunable trace_own_leaf = 0.  ms: queue build, walk
+ * and tail together. */
+int  rtr_trace_occlusion(rtr_ctx* ctx, const rtr_scene* scene, const RtrRay* rays, uint32_t numRays, uint32_t flags,
+                         void* scratch, size_t scratchBytes, uint8_t* occluded, rtr_query_stats* stats);
 /* Writes to the device array out[] the width * height * spp camera rays the renderer traces for `camera` (raygen.rgen:83-107:
  * jittered direction through the viewport, tmin 0.001, tmax 10000): ray k = (py * width + px) * spp + i.  ENQUEUED on ctx's stream.
  * Callers generate, edit and trace camera rays this way; traced with RTR_QUERY_CLOSEST they give the renderer's primary hits.
@@ -396,7 +423,8 @@ int  rtr_hit_surfaces(rtr_ctx* ctx, const rtr_scene* scene, const RtrRay* rays, 
 /* ---- direct lighting for ray-query hits ----------------------------------------------------------------------------------
  * What the ray-gen shader does AFTER the closest hit (raygen.rgen:165-338, :345-357), in the stages the renderer itself runs it in:
  *   rtr_light_rays   the shadow rays of each hit        (the area-light samples of :206-231, the directional light of :299-303)
- *   rtr_trace_rays   RTR_QUERY_ANY answers them         (the caller's launch: any of the stages can be replaced)
+ *   rtr_trace_rays   RTR_QUERY_ANY answers them         (the caller's launch: any of the stages can be replaced; rtr_trace_occlusion
+ *                                                        gives the same bytes)
  *   rtr_shade_hits   the Cook-Torrance sums, the LTC term, sky and light hits
  *   rtr_tonemap_pack ACES + sRGB + B,G,R,255
  * camera rays -> closest hit -> these four reproduce rtr_render's images from public parts: at 1 sample per pixel bit for bit (with

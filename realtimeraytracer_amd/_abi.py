@@ -204,6 +204,9 @@ RTR_SYMBOLS = {
     "rtr_check_scene_limits": (C.c_int, [C.c_uint64, C.c_uint64]),
     "rtr_trace_rays_async": (C.c_int, [VP, VP, VP, u32, u32, VP, VP]),
     "rtr_trace_rays": (C.c_int, [VP, VP, VP, u32, u32, VP, VP, P(rtr_query_stats)]),
+    "rtr_occlusion_scratch_bytes": (C.c_int, [u32, P(C.c_size_t)]),
+    "rtr_trace_occlusion_async": (C.c_int, [VP, VP, VP, u32, u32, VP, C.c_size_t, VP]),
+    "rtr_trace_occlusion": (C.c_int, [VP, VP, VP, u32, u32, VP, C.c_size_t, VP, P(rtr_query_stats)]),
     "rtr_camera_rays_async": (C.c_int, [VP, P(RtrCameraData), u32, u32, u32, VP]),
     "rtr_hit_surfaces_async": (C.c_int, [VP, VP, VP, VP, u32, VP]),
     "rtr_hit_surfaces": (C.c_int, [VP, VP, VP, VP, u32, VP]),

@@ -342,6 +342,62 @@ def trace_rays(scene, rays, any_hit=False, opaque=False, collect_stats=False, ct
     return out
 
 
+def occlusion_scratch_bytes(lib, n):
+    """rtr_occlusion_scratch_bytes: device scratch a queued occlusion query of n rays needs"""
+    b = C.c_size_t(0)
+    _check(lib.rtr_occlusion_scratch_bytes(int(n), C.byref(b)), "rtr_occlusion_scratch_bytes")
+    return int(b.value)
+
+
+def trace_occlusion(scene, rays, opaque=False, collect_stats=False, ctx=None, asynchronous=False):
+    """rtr_trace_occlusion: the queued occlusion query — the same bytes as trace_rays(any_hit=True), answered by the renderer's any-hit
+    machinery (rays binned by direction octant, persistent waves over the 4-wide tree).  rays, opaque, ctx, asynchronous, collect_stats
+    and the QueryResult (occluded, stats) as in trace_rays.  The query's scratch is a uint8 device tensor kept on the context and grown
+    when a longer ray array comes; queries on one context are ordered on its stream, so they share it."""
+    torch = _torch()
+    ctx = ctx or scene.ctx
+    dev = torch.device("cuda", ctx.device)
+    as_numpy = isinstance(rays, np.ndarray)
+    if as_numpy:
+        if rays.dtype != np.float32 or rays.ndim != 2 or rays.shape[1] != 8:
+            raise ValueError(f"trace_occlusion: rays must be float32 (N, 8), got {rays.dtype} {rays.shape}")
+        r = torch.from_numpy(np.ascontiguousarray(rays)).to(dev)
+    elif isinstance(rays, torch.Tensor):
+        if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8:
+            raise ValueError(f"trace_occlusion: rays must be float32 (N, 8), got {rays.dtype} {tuple(rays.shape)}")
+        if rays.device != dev:
+            raise ValueError(f"trace_occlusion: rays live on {rays.device}, the context on {dev}")
+        if not rays.is_contiguous():
+            raise ValueError("trace_occlusion: rays must be contiguous")
+        r = rays
+    else:
+        raise ValueError(f"trace_occlusion: rays must be a torch tensor or a numpy array, got {type(rays).__name__}")
+    if asynchronous and collect_stats:
+        raise ValueError("trace_occlusion: collect_stats needs the synchronous form")
+    if asynchronous and ctx.get_stream() != torch.cuda.current_stream(dev).cuda_stream:
+        raise ValueError("trace_occlusion: an asynchronous query needs the context on torch's current stream (ctx.set_stream)")
+    n = int(r.shape[0])
+    need = occlusion_scratch_bytes(ctx.lib, n)
+    scratch = getattr(ctx, "_occlusion_scratch", None)
+    if scratch is None or scratch.numel() < need:
+        scratch = ctx._occlusion_scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+    occ = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)[:n]
+    if not asynchronous and ctx.get_stream() != torch.cuda.current_stream(dev).cuda_stream:
+        torch.cuda.current_stream(dev).synchronize()        # the rays (and the outputs' memory) are ready for the context's stream
+    flags = A.QUERY_OPAQUE if opaque else 0
+    args = (A.VP(r.data_ptr()), n, flags, A.VP(scratch.data_ptr()), scratch.numel(), A.VP(occ.data_ptr())) if n else (None, 0, flags, None, 0, None)
+    out = QueryResult()
+    if asynchronous:
+        _check(ctx.lib.rtr_trace_occlusion_async(ctx.h, scene.h, *args), "rtr_trace_occlusion_async")
+    else:
+        st = A.rtr_query_stats() if collect_stats else None
+        _check(ctx.lib.rtr_trace_occlusion(ctx.h, scene.h, *args, C.byref(st) if st is not None else None), "rtr_trace_occlusion")
+        out.stats = st
+    out.occluded = occ.cpu().numpy() if as_numpy else occ
+    out._keep = (r, occ, scratch)        # an asynchronous query's buffers stay alive with its result
+    return out
+
+
 def camera_rays(ctx, camera, width, height, spp=1):
     """rtr_camera_rays_async: the (width * height * spp, 8) float32 device tensor of the camera rays the renderer traces for `camera`,
     row k = (py * width + px) * spp + i; ready for torch's current stream when it returns."""
@@ -570,10 +626,10 @@ def tonemap_pack(ctx, radiance, asynchronous=False):
     return out
 
 
-def direct_light(scene, rays, hits=None, params=None, seeds=None, ctx=None, max_ray_bytes=256 << 20):
+def direct_light(scene, rays, hits=None, params=None, seeds=None, ctx=None, max_ray_bytes=256 << 20, occlusion="dense"):
     """The composed stage: closest hit (when hits is None) -> light_rays -> trace_rays(any_hit=True) -> shade_hits, in chunks of hits
     so that a chunk's light rays (n * Q * 32 bytes) stay within max_ray_bytes — a 1080p frame at Q = 7 would be 464 MB of rays at once.
-    Chunks do not change the result.  rays: a float32 (N, 8) device tensor; hits: a QueryResult, (N, 8) int32 records, or None;
+    Chunks do not change the result.  occlusion: "dense" (trace_rays, the default) or "queued" (trace_occlusion): the same bytes.  rays: a float32 (N, 8) device tensor; hits: a QueryResult, (N, 8) int32 records, or None;
     params: make_light_params(...).  Returns a RadianceResult on the device."""
     torch = _torch()
     ctx = ctx or scene.ctx
@@ -581,6 +637,8 @@ def direct_light(scene, rays, hits=None, params=None, seeds=None, ctx=None, max_
         raise ValueError("direct_light: params (make_light_params) are needed")
     if not isinstance(rays, torch.Tensor):
         raise ValueError("direct_light: rays must be a device tensor")
+    if occlusion not in ("dense", "queued"):
+        raise ValueError(f"direct_light: occlusion must be 'dense' or 'queued', got {occlusion!r}")
     if hits is None:
         hits = trace_rays(scene, rays, ctx=ctx)
     if isinstance(hits, QueryResult):
@@ -596,6 +654,6 @@ def direct_light(scene, rays, hits=None, params=None, seeds=None, ctx=None, max_
             sd = ((k % int(params.width)) * 733 + (k // int(params.width)) * 1933).to(torch.int32)      # wraps to 32 bits as the kernel's words do
         r, h = rays[a:b], hits[a:b]
         lr = light_rays(scene, r, h, params, seeds=sd, ctx=ctx)
-        occ = trace_rays(scene, lr, any_hit=True, ctx=ctx).occluded
+        occ = (trace_occlusion(scene, lr, ctx=ctx) if occlusion == "queued" else trace_rays(scene, lr, any_hit=True, ctx=ctx)).occluded
         out[a:b] = shade_hits(scene, r, h, params, occ, seeds=sd, ctx=ctx).raw
     return _radiance_result(out, False, torch)

@@ -115,6 +115,23 @@ hipError_t launch_megakernel(const DeviceScene& sc, const RenderArgs& ra, const 
 hipError_t launch_wavefront(const DeviceScene& sc, const FrameBatch& batch, const Workspace& ws, const Tunables& tun,
                             int stackEntries, Counters* stats, hipStream_t stream, hipEvent_t* ev, uint32_t numCus);
 
+/* A queued occlusion query over a caller's rays (rtr_trace_occlusion; kernels/rtr_occlusion.hip builds the queue, k_shadow_trace4 in its
+ * CALLER form drains it).  ctrl has the layout of Workspace::queueCount — queued rays, batch cursors, list lengths — and is zeroed,
+ * with overflow[0], before the launch. */
+struct OcclusionArgs {
+    const float4* rays;          /* RtrRay as 2 x float4: {origin, tmin} {direction, tmax} */
+    uint8_t* occluded;           /* one byte per ray, zeroed before the launch: the walk stores the 1s (and the tail's sentinel) */
+    uint32_t n;
+    uint32_t batch;              /* rays per batch of the lists */
+    uint32_t* ctrl;              /* kQueueCtrlWords words */
+    uint32_t* overflow;          /* [0] abandoned rays, then their ray indices (overflowCap entries): what k_query_tail takes as its redo list */
+    uint32_t overflowCap;
+    uint32_t* queue;             /* n ray indices, binned by direction octant */
+    uint2* lists;                /* kQueueLists lists of listStride batches {first queue entry, rays} */
+    uint32_t listStride;
+};
+hipError_t launch_occlusion_walk(const DeviceScene& sc, const OcclusionArgs& oa, const Tunables& tun, bool alpha, Counters* stats, hipStream_t stream, uint32_t numCus);
+
 /* fills DeviceScene::lightTris (4 x float4 per light triangle, light l from first[l]); after create and after light transforms change */
 hipError_t launch_light_tris(const RtrAreaLightInfo* lights, const RtrVertex* vertices, const uint32_t* indices, const uint32_t* first,
                              uint32_t numLights, float4* out, hipStream_t stream);

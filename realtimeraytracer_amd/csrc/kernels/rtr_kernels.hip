@@ -840,10 +840,11 @@ __global__ __launch_bounds__(kBlock) void k_shadow_trace(DeviceScene sc, const R
 
 /* The inner-node loop of k_shadow_trace4, compiled per direction octant (OCT 0..7; 8 = any signs, see slab_oct). */
 /* One any-hit triangle test of the persistent 4-wide kernel: 48-B record through the buffer resource, Moeller-Trumbore, t < tmax,
- * and opacity.rahit on alpha-tested geometry. */
-template <bool STATS>
+ * and opacity.rahit on alpha-tested geometry.  MAY_SKIP_ALPHA (the caller-ray form only): `opaque` — wave-uniform, RTR_QUERY_OPAQUE —
+ * accepts every candidate without that test. */
+template <bool STATS, bool MAY_SKIP_ALPHA = false>
 __device__ __forceinline__ bool tri_any(const DeviceScene& sc, const __amdgpu_buffer_rsrc_t triBuf, const uint32_t tri, const rtr_v3 o, const rtr_v3 d,
-                                        const float tmin, const float tmax, LocalStats& st) {
+                                        const float tmin, const float tmax, LocalStats& st, const bool opaque = false) {
     typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
     const int32_t triOff = (int32_t)(tri * 48u);
     const u32x4 r0 = __builtin_amdgcn_raw_buffer_load_b128(triBuf, triOff, 0, RTR_TRI_AUX);
@@ -854,7 +855,7 @@ __device__ __forceinline__ bool tri_any(const DeviceScene& sc, const __amdgpu_bu
     const float4 q2 = make_float4(__uint_as_float(r2.x), __uint_as_float(r2.y), __uint_as_float(r2.z), __uint_as_float(r2.w));
     float t, u, v;
     if (!(rtr_mt_intersect(o, d, f4xyz(q0), f4xyz(q1), f4xyz(q2), tmin, &t, &u, &v) && t < tmax)) return false;
-    if (__float_as_uint(q2.w) & 1u) return alpha_pass<STATS>(sc, __float_as_uint(q0.w), __float_as_uint(q1.w), u, v, st);
+    if ((__float_as_uint(q2.w) & 1u) && !(MAY_SKIP_ALPHA && opaque)) return alpha_pass<STATS>(sc, __float_as_uint(q0.w), __float_as_uint(q1.w), u, v, st);
     return true;
 }
 
@@ -969,7 +970,12 @@ __device__ __forceinline__ void inner_nodes4(const __amdgpu_buffer_rsrc_t nodeBu
  * tree: the hit child that exits last first (kFarFirst), ties to the lower slot, the others stacked in slot order — whatever the scheduling, the octant
  * form or the queue mode, so the counting form's numbers are the timed form's, and the oracle restates them), per-trip lane counts
  * of the two phases, and a shader-clock stamp pair per wave. */
-template <int STACK, bool LISTS, bool STATS>
+/* CALLER (rtr_trace_occlusion, launch_occlusion_walk below): the same walk for rays the caller supplies.  The queue holds INDICES into an
+ * array of 32-B RtrRay records (queue.slot: the indices, binned by k_occlusion_gen of rtr_occlusion.hip; queue.dt: the rays, two 16-B
+ * pieces each), so the refill gathers origin, direction, tmin and tmax of its ray and the result goes to vis[index]; no ray starts at
+ * a leaf (an RtrRay carries no leaf code), and an abandoned ray leaves the sentinel k_query_tail of rtr_query.hip looks for.  Everything
+ * else — batch lists, refill rule, inner_nodes4, the leaf phase — is the code above and below, not a copy of it. */
+template <int STACK, bool LISTS, bool STATS, bool CALLER = false>
 __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_shadow_trace4(DeviceScene sc, const RayQueue queue,
                                                               const uint32_t* __restrict__ count, uint32_t* nextBatch,
                                                               uint8_t* __restrict__ vis, uint32_t visFill, uint32_t kBatch, uint32_t kRefill,
@@ -1038,7 +1044,7 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(8, 
     rtr_v3 o = rtr_mk(0, 0, 0), d = rtr_mk(0, 0, 0), ga = rtr_mk(0, 0, 0), gb = rtr_mk(0, 0, 0);   /* t(q) = q * ga + gb */
     float tmax = 0.f;
     uint32_t slot = 0, rayIndex = 0, res = kResNone, occ = 0;
-    const float tmin = 0.001f;
+    float tmin = 0.001f;                     /* the renderer's rays all start there; a caller's ray brings its own (CALLER) */
     /* nodes and triangles through buffer resources: the address of a visit is one 32-bit shift, not 64-bit lane arithmetic
      * (2.28 -> 2.17 ms, and 62 -> 47 VGPRs) */
     const __amdgpu_buffer_rsrc_t nodeBuf = __builtin_amdgcn_make_buffer_rsrc((void*)sc.nodes4, 0, 0xffffffff, 0x00020000);
@@ -1060,7 +1066,11 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(8, 
             const uint32_t fill = visFill;
 #endif
             if (cur == kDone && res != kResNone) {
-                if (res == 2u) { const uint32_t at = atomicAdd(overflow, 1u); if (at < overflowCap) overflow[1u + at] = rayIndex; }      /* finished by k_shadow_tail (a full list: it redoes the whole queue) */
+                if (res == 2u) {      /* finished by k_shadow_tail (a full list: it redoes the whole queue) */
+                    const uint32_t at = atomicAdd(overflow, 1u);
+                    if (at < overflowCap) overflow[1u + at] = CALLER ? slot : rayIndex;
+                    if (CALLER) visOut[slot] = 0xffu;      /* k_query_tail's sentinel: past a full list it finds the ray by it */
+                }
                 else { if (res != fill) visOut[slot] = (uint8_t)res; occ += res; }      /* the array was pre-filled with the commoner outcome: only the other one is stored */
                 res = kResNone;
             }
@@ -1114,6 +1124,18 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(8, 
                         rayIndex = batchPos + prefix;
                         bool into = false;                               /* the ray leaves its surface point into the surface: its own triangle's leaf first */
                         int32_t ownLeaf = 0;
+                        if (CALLER) {      /* the ray's index out of the binned queue (streamed), then the ray itself */
+#if RTR_REFILL_LDS
+                            const global_f4 qrays = (global_f4)rc.dt;
+                            const global_u32 qslot = (global_u32)rc.slot;
+                            slot = (octForms & 2u) ? __builtin_nontemporal_load(qslot + rayIndex) : qslot[rayIndex];
+                            const rtr_f4 a = qrays[2 * (size_t)slot], b = qrays[2 * (size_t)slot + 1];
+#else
+                            slot = queue.slot[rayIndex];
+                            const float4 a = queue.dt[2 * (size_t)slot], b = queue.dt[2 * (size_t)slot + 1];
+#endif
+                            o = rtr_mk(a.x, a.y, a.z); tmin = a.w; d = rtr_mk(b.x, b.y, b.z); tmax = b.w;
+                        } else
 #if RTR_REFILL_LDS
                         {   /* queue_load() through the addresses kept in LDS */
                             const global_f4 qdt = (global_f4)rc.dt, qorg = (global_f4)rc.origin;
@@ -1128,9 +1150,11 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(8, 
                             ownLeaf = __float_as_int(og.w);
                         }
 #else
-                        into = (queue.slot[rayIndex] & kRayIntoSurface) != 0u;
-                        queue_load(queue, rayIndex, o, d, tmax, slot, octForms & 2u);
-                        ownLeaf = __float_as_int(queue.origin[slot & queue.slotMask].w);
+                        {
+                            into = (queue.slot[rayIndex] & kRayIntoSurface) != 0u;
+                            queue_load(queue, rayIndex, o, d, tmax, slot, octForms & 2u);
+                            ownLeaf = __float_as_int(queue.origin[slot & queue.slotMask].w);
+                        }
 #endif
                         if (STATS) { st.rays++; st.shadow++; }
                         if (!(tmax > tmin)) {
@@ -1199,7 +1223,7 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(8, 
 #if !RTR_STATS_LEAF_PHASE
                 ws.triIters++; ws.triLanes += (uint32_t)__popcll(m);
 #endif
-                if (go) { st.tris++; st.shadowTris++; hit = tri_any<true>(sc, triBuf, first + i, o, d, tmin, tmax, st); }
+                if (go) { st.tris++; st.shadowTris++; hit = tri_any<true, CALLER>(sc, triBuf, first + i, o, d, tmin, tmax, st, (octForms & 4u) != 0u); }
             }
             if (atLeaf) {
                 if (hit) { res = 1u; cur = kDone; }
@@ -1209,7 +1233,7 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(8, 
             const uint32_t code = (uint32_t)~cur;
             const uint32_t first = code >> 3, cnt = (code & 7u) + 1u;
             bool hit = false;
-            for (uint32_t i = 0; i < cnt && !hit; ++i) hit = tri_any<false>(sc, triBuf, first + i, o, d, tmin, tmax, st);
+            for (uint32_t i = 0; i < cnt && !hit; ++i) hit = tri_any<false, CALLER>(sc, triBuf, first + i, o, d, tmin, tmax, st, (octForms & 4u) != 0u);
             if (hit) { res = 1u; cur = kDone; }
             else { cur = *sp; sp -= kTraceBlock; }                        /* slot 0 holds kDone: an empty stack ends the ray (visible) */
         }
@@ -2008,6 +2032,29 @@ hipError_t launch_wavefront(const DeviceScene& sc, const FrameBatch& fb, const W
         case 64: return wave_t<64>(sc, fb, ws, tun, stats, stream, ev, numCus);
         default: return hipErrorInvalidValue;
     }
+}
+
+/* The any-hit walk over a caller's rays (rtr_trace_occlusion): k_shadow_trace4 in its CALLER form over the index queue and batch lists
+ * k_occlusion_gen built.  Launch shape and tunables are the renderer's: persistent workgroups by the length of the queue, the context's
+ * refill / inner-loop thresholds, octant forms, top of the tree in LDS. */
+hipError_t launch_occlusion_walk(const DeviceScene& sc, const OcclusionArgs& oa, const Tunables& tun, bool alpha, Counters* stats, hipStream_t s, uint32_t numCus) {
+    if (numCus == 0) numCus = 256;
+    if (!sc.nodes4) return hipErrorInvalidValue;
+    RayQueue rq;
+    rq.dt = const_cast<float4*>(oa.rays); rq.slot = oa.queue;
+    uint32_t tblocks = numCus * (tun.trace_wgs_per_cu ? tun.trace_wgs_per_cu : (oa.n >= kBinnedMinRays ? 8u : 6u)) * (uint32_t)kBlock / (uint32_t)kTraceBlock;
+    const uint32_t needed = (uint32_t)(((uint64_t)oa.n + kTraceBlock - 1) / kTraceBlock);
+    if (tblocks > needed) tblocks = needed;
+    if (tblocks == 0) tblocks = 1;
+    const uint32_t kOct = tun.trace_octant_forms | ((tun.queue_nt & 1u) << 1) | (alpha ? 0u : 4u);      /* bit 2: RTR_QUERY_OPAQUE (tri_any) */
+    const uint32_t kTop = tun.trace_top_nodes < kTopNodes ? tun.trace_top_nodes : kTopNodes;
+    const uint32_t top = kTop < sc.numNodes4 ? kTop : sc.numNodes4;
+    uint32_t* const ctrl = oa.ctrl;
+#define RTR_OCC_WALK(STATS) hipLaunchKernelGGL((k_shadow_trace4<RTR_SHADOW_STACK, true, STATS, true>), dim3(tblocks), dim3(kTraceBlock), 0, s, sc, rq, ctrl, ctrl + kBatchCursorWord, \
+        oa.occluded, 0u, oa.batch, tun.trace_refill, tun.trace_inner_min, oa.overflow, oa.overflowCap, kOct, top, oa.lists, oa.listStride, stats, (unsigned long long*)nullptr)
+    if (stats) RTR_OCC_WALK(true); else RTR_OCC_WALK(false);
+#undef RTR_OCC_WALK
+    return hipGetLastError();
 }
 
 hipError_t launch_light_tris(const RtrAreaLightInfo* lights, const RtrVertex* vertices, const uint32_t* indices, const uint32_t* first,

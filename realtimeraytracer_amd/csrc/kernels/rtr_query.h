@@ -53,6 +53,19 @@ struct LightArgs {
 
 /* flags: RTR_QUERY_ANY | RTR_QUERY_OPAQUE (validated by the caller).  stats: the counting form, counters added there (zeroed by the caller). */
 hipError_t launch_query(const DeviceScene& sc, const QueryArgs& qa, uint32_t flags, Counters* stats, hipStream_t stream);
+/* k_query_tail alone, any-hit form: finishes the rays another walk abandoned — qa.ctrl[kQueryRedoWord] of them, their indices in
+ * qa.redoList (or, past qa.redoCap, found by the sentinel in qa.occluded) — over the BVH2 (the queued occlusion query's third stage) */
+hipError_t launch_query_tail_any(const DeviceScene& sc, const QueryArgs& qa, bool alpha, Counters* stats, hipStream_t stream);
+/* The queued occlusion query (rtr_trace_occlusion; kernels/rtr_occlusion.hip): queue build over the rays -> k_shadow_trace4's walk over the
+ * 4-wide tree (launch_occlusion_walk) -> k_query_tail.  spill: kSpillInts. */
+hipError_t launch_occlusion(const DeviceScene& sc, const OcclusionArgs& oa, const Tunables& tun, bool alpha, int32_t* spill, Counters* stats,
+                            hipStream_t stream, uint32_t numCus);
+/* rays one workgroup of the queue build bins: what bounds the batches a launch can append to one list (occlusion_list_stride) */
+constexpr uint32_t kOcclusionGenRays = 4096;
+constexpr uint32_t occlusion_batch(uint32_t n) { return (size_t)n >= ((size_t)100 << 20) ? 512u : 256u; }
+constexpr uint32_t occlusion_list_stride(uint32_t n) {      /* for the shorter batch whatever n is: monotone in n */
+    return (uint32_t)((uint64_t)n / 256u / kQueueRegions + ((uint64_t)n + kOcclusionGenRays - 1) / kOcclusionGenRays + 1u);
+}
 /* width * height * spp camera rays of raygen.rgen:83-107, ray k = (py * width + px) * spp + i (< 2^32, checked by the caller) */
 hipError_t launch_camera_rays(const RtrCameraData& cam, uint32_t width, uint32_t height, uint32_t spp, float4* out, hipStream_t stream);
 /* one RtrSurface per hit: the renderer's surface fetch (fetch_surface) for caller hits */

@@ -139,6 +139,17 @@ hipError_t launch_query(const DeviceScene& sc, const QueryArgs& qa, uint32_t fla
     return alpha ? query_s<false, true>(sc, qa, stats, s) : query_s<false, false>(sc, qa, stats, s);
 }
 
+hipError_t launch_query_tail_any(const DeviceScene& sc, const QueryArgs& qa, bool alpha, Counters* stats, hipStream_t s) {
+    if (alpha) {
+        if (stats) hipLaunchKernelGGL((k_query_tail<true, true, true>), dim3(kQueryTailBlocks), dim3(kQueryTailBlock), 0, s, sc, qa, stats);
+        else hipLaunchKernelGGL((k_query_tail<true, true, false>), dim3(kQueryTailBlocks), dim3(kQueryTailBlock), 0, s, sc, qa, stats);
+    } else {
+        if (stats) hipLaunchKernelGGL((k_query_tail<true, false, true>), dim3(kQueryTailBlocks), dim3(kQueryTailBlock), 0, s, sc, qa, stats);
+        else hipLaunchKernelGGL((k_query_tail<true, false, false>), dim3(kQueryTailBlocks), dim3(kQueryTailBlock), 0, s, sc, qa, stats);
+    }
+    return hipGetLastError();
+}
+
 /* one lane per pixel-sample: the camera ray k_primary traces for it (primary_dir, tmin 0.001, tmax 10000) */
 constexpr int kCameraRaysBlock = 256;
 __global__ __launch_bounds__(kCameraRaysBlock) void k_camera_rays(RenderArgs ra, uint32_t n, float4* __restrict__ out) {

@@ -1416,6 +1416,17 @@ int rtr_deinterleave_images(rtr_ctx* ctx, const void* gathered, uint32_t numImag
 /* ---- ray queries ---------------------------------------------------------------------------- */
 static bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
+/* the context's query scratch, allocated by its first query (the current device is the context's) */
+static int query_scratch(rtr_ctx* c) {
+    if (c->qCtrl.p) return RTR_OK;
+    HIP_TRY(c->qRedo.alloc(rtrdev::kQueryRedoCap));
+    HIP_TRY(c->qSpill.alloc(rtrdev::kSpillInts));
+    HIP_TRY(c->qCounters.alloc(1));
+    for (hipEvent_t& e : c->qEv) HIP_TRY(hipEventCreate(&e));
+    HIP_TRY(c->qCtrl.alloc(rtrdev::kQueryCtrlWords));
+    return RTR_OK;
+}
+
 /* the checks and launches of rtr_trace_rays[_async], enqueued on the context's stream; count: the counting form */
 static int enqueue_query(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, uint32_t n, uint32_t flags, RtrHit* hits, uint8_t* occluded,
                          bool count, const char* who) {
@@ -1431,13 +1442,8 @@ static int enqueue_query(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, uin
     if (any && !occluded) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: an any-hit query (RTR_QUERY_ANY) needs occluded", who);
     if (any && !aligned16(occluded)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: occluded is not 16-B aligned", who);
     HIP_TRY(hipSetDevice(c->device));
-    if (!c->qCtrl.p) {
-        HIP_TRY(c->qCtrl.alloc(rtrdev::kQueryCtrlWords));
-        HIP_TRY(c->qRedo.alloc(rtrdev::kQueryRedoCap));
-        HIP_TRY(c->qSpill.alloc(rtrdev::kSpillInts));
-        HIP_TRY(c->qCounters.alloc(1));
-        for (hipEvent_t& e : c->qEv) HIP_TRY(hipEventCreate(&e));
-    }
+    const int src = query_scratch(c);
+    if (src != RTR_OK) return src;
     uint32_t redoCap = rtrdev::kQueryRedoCap;
 #ifdef RTR_TEST_HOOKS
     if (const char* e = getenv("RTR_QUERY_REDO_CAP")) { const uint64_t v = strtoull(e, nullptr, 10); if (v >= 1 && v < redoCap) redoCap = (uint32_t)v; }   /* a list short enough to overflow */
@@ -1476,6 +1482,93 @@ int rtr_trace_rays(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, uint32_t 
         HIP_TRY(hipStreamSynchronize(st));
         stats->numRays = h.rays; stats->numNodeVisits = h.nodes; stats->numTriTests = h.tris; stats->numAlphaTests = h.alphaTests;
         stats->tailRays = ctrl[rtrdev::kQueryRedoWord];
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, c->qEv[0], c->qEv[1]));
+        stats->ms = ms;
+    } else HIP_TRY(hipStreamSynchronize(st));
+    return RTR_OK;
+}
+
+/* ---- queued occlusion queries (kernels/rtr_occlusion.hip) ---- */
+namespace {
+/* the caller's scratch: control block (zeroed with the count of abandoned rays behind it) | abandoned rays' list | index queue | batch lists */
+struct OcclusionLayout { size_t ctrl, overflow, queue, lists, bytes; uint32_t overflowCap, listStride; };
+size_t up16(size_t x) { return (x + 15u) & ~(size_t)15u; }
+OcclusionLayout occlusion_layout(uint32_t n) {
+    OcclusionLayout l{};
+    l.overflowCap = n < rtrdev::kQueryRedoCap ? n : rtrdev::kQueryRedoCap;
+    l.listStride = rtrdev::occlusion_list_stride(n);
+    l.ctrl = 0;
+    l.overflow = up16(rtrdev::kQueueCtrlWords * sizeof(uint32_t));
+    l.queue = l.overflow + up16(((size_t)l.overflowCap + 1u) * sizeof(uint32_t));
+    l.lists = l.queue + up16((size_t)n * sizeof(uint32_t));
+    l.bytes = l.lists + up16((size_t)rtrdev::kQueueLists * l.listStride * sizeof(uint2));
+    return l;
+}
+}  // namespace
+
+int rtr_occlusion_scratch_bytes(uint32_t numRays, size_t* bytes) {
+    if (!bytes) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_occlusion_scratch_bytes: bytes is null");
+    *bytes = occlusion_layout(numRays).bytes;
+    return RTR_OK;
+}
+
+static int enqueue_occlusion(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, uint32_t n, uint32_t flags, void* scratch, size_t scratchBytes,
+                             uint8_t* occluded, bool count, const char* who) {
+    if (!c || !s) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: null context or scene", who);
+    if (flags & ~(RTR_QUERY_ANY | RTR_QUERY_OPAQUE)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: unknown flag bits 0x%x", who, flags & ~(RTR_QUERY_ANY | RTR_QUERY_OPAQUE));
+    if (s->ctx->device != c->device) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: the scene lives on device %d, the context on device %d", who, s->ctx->device, c->device);
+    if (n == 0) return RTR_OK;
+    if (!rays || !occluded || !scratch) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: %s is null", who, !rays ? "rays" : (!occluded ? "occluded" : "scratch"));
+    if (!aligned16(rays) || !aligned16(occluded) || !aligned16(scratch))
+        return fail(RTR_ERR_INVALID_ARGUMENT, "%s: %s is not 16-B aligned", who, !aligned16(rays) ? "rays" : (!aligned16(occluded) ? "occluded" : "scratch"));
+    const OcclusionLayout l = occlusion_layout(n);
+    if (scratchBytes < l.bytes) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: %zu bytes of scratch, %u rays need %zu (rtr_occlusion_scratch_bytes)", who, scratchBytes, n, l.bytes);
+    HIP_TRY(hipSetDevice(c->device));
+    const int rc = query_scratch(c);
+    if (rc != RTR_OK) return rc;
+    uint32_t overflowCap = l.overflowCap;
+#ifdef RTR_TEST_HOOKS
+    if (const char* e = getenv("RTR_QUERY_REDO_CAP")) { const uint64_t v = strtoull(e, nullptr, 10); if (v >= 1 && v < overflowCap) overflowCap = (uint32_t)v; }   /* a list short enough to overflow */
+#endif
+    hipStream_t st = c->stream;
+    if (c->qLastStream && c->qLastStream != st) HIP_TRY(hipStreamWaitEvent(st, c->qEv[1], 0));      /* the deep stacks and the counters are the context's */
+    char* const base = static_cast<char*>(scratch);
+    HIP_TRY(hipMemsetAsync(base + l.ctrl, 0, l.overflow + 16u, st));       /* the control block and the count of abandoned rays */
+    HIP_TRY(hipMemsetAsync(occluded, 0, n, st));                           /* the walk stores the occluded rays' bytes only */
+    if (count) HIP_TRY(hipMemsetAsync(c->qCounters.p, 0, sizeof(Counters), st));
+    HIP_TRY(hipEventRecord(c->qEv[0], st));
+    rtrdev::OcclusionArgs oa{};
+    oa.rays = reinterpret_cast<const float4*>(rays); oa.occluded = occluded; oa.n = n; oa.batch = rtrdev::occlusion_batch(n);
+    oa.ctrl = reinterpret_cast<uint32_t*>(base + l.ctrl); oa.overflow = reinterpret_cast<uint32_t*>(base + l.overflow); oa.overflowCap = overflowCap;
+    oa.queue = reinterpret_cast<uint32_t*>(base + l.queue); oa.lists = reinterpret_cast<uint2*>(base + l.lists); oa.listStride = l.listStride;
+    const hipError_t e = rtrdev::launch_occlusion(s->dev, oa, c->tun, (flags & RTR_QUERY_OPAQUE) == 0u, c->qSpill.p, count ? c->qCounters.p : nullptr, st,
+                                                  (uint32_t)c->prop.multiProcessorCount);
+    if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: kernel launch: %s", who, hipGetErrorString(e));
+    HIP_TRY(hipEventRecord(c->qEv[1], st));
+    c->qLastStream = st;
+    return RTR_OK;
+}
+
+int rtr_trace_occlusion_async(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, uint32_t n, uint32_t flags, void* scratch, size_t scratchBytes, uint8_t* occluded) {
+    return enqueue_occlusion(c, s, rays, n, flags, scratch, scratchBytes, occluded, false, "rtr_trace_occlusion_async");
+}
+
+int rtr_trace_occlusion(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, uint32_t n, uint32_t flags, void* scratch, size_t scratchBytes, uint8_t* occluded,
+                        rtr_query_stats* stats) {
+    const int rc = enqueue_occlusion(c, s, rays, n, flags, scratch, scratchBytes, occluded, stats != nullptr, "rtr_trace_occlusion");
+    if (rc != RTR_OK) return rc;
+    if (stats) memset(stats, 0, sizeof *stats);
+    if (n == 0) return RTR_OK;
+    hipStream_t st = c->stream;
+    if (stats) {      /* copies on the context's stream: the call joins that stream only */
+        Counters h;
+        uint32_t tail = 0;
+        HIP_TRY(hipMemcpyAsync(&h, c->qCounters.p, sizeof h, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(&tail, static_cast<char*>(scratch) + occlusion_layout(n).overflow, sizeof tail, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        stats->numRays = h.rays; stats->numNodeVisits = h.nodes; stats->numTriTests = h.tris; stats->numAlphaTests = h.alphaTests;
+        stats->tailRays = tail;
         float ms = 0.f;
         HIP_TRY(hipEventElapsedTime(&ms, c->qEv[0], c->qEv[1]));
         stats->ms = ms;

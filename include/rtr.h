@@ -403,6 +403,38 @@ int  rtr_trace_occlusion_async(rtr_ctx* ctx, const rtr_scene* scene, const RtrRa
  * and tail together. */
 int  rtr_trace_occlusion(rtr_ctx* ctx, const rtr_scene* scene, const RtrRay* rays, uint32_t numRays, uint32_t flags,
                          void* scratch, size_t scratchBytes, uint8_t* occluded, rtr_query_stats* stats);
+/* ---- start hints: the renderer's own-leaf rule for the queued query ----
+ * The renderer's any-hit walk starts a shadow ray that leaves its surface point INTO the surface (dot(hitNormal, lightVec) < 0) at the
+ * leaf of the triangle it starts on, the root waiting on the stack: 0.01 above that triangle it nearly always re-enters it, and the leaf
+ * answers without a record visit (the tunable trace_own_leaf).  An RtrRay carries no leaf, so the caller passes it beside the ray.
+ * A HINT is an int32_t.  Negative: a leaf child code as in RtrBvhNode / RtrWideNode — code = ~hint, first = code >> 3, count =
+ * (code & 7) + 1, indexing the leaf-ordered triangle array — and the walk tests that leaf first, then walks from the root.  0: no hint,
+ * the walk starts at the root.  ANYTHING ELSE COUNTS AS 0: a positive value, 0x80000000, a code whose first + count exceeds the scene's
+ * triangle records; no value makes the walk read outside the triangle array.  Any-hit is a pure function of the ray and the triangles, so
+ * a hint — right, wrong or another triangle's — changes the work and never a byte: occluded[] is rtr_trace_rays(RTR_QUERY_ANY)'s.
+ * Hints come from the scene's triangle -> leaf table: for every (customIndex, primitiveId) of the scene the child code of the leaf that
+ * holds that world-space record.  The table is NOT part of rtr_scene_create: THE FIRST CALL of rtr_hit_leaves or rtr_light_rays_hinted
+ * (either form) on a scene ALLOCATES it (4 B per triangle + 4 B per instance) and fills it on ctx's stream, which that one call joins;
+ * every later call, from any context of the device, finds it complete.  It survives rtr_scene_update_instances (a refit keeps topology
+ * and leaf order); a scene made by rtr_scene_create_like makes its own.
+ *
+ * leaves[k] = the table's entry for hits[k] (customIndex, primitiveId): light instances are in the tree, so light hits get theirs; a miss
+ * or ids out of range give 0 and read nothing.  For callers who make their own rays from a hit (transmission, a probe below a surface).
+ * hits (16-B aligned) and leaves (4-B aligned) are DEVICE pointers; ENQUEUED on ctx's stream (apart from the first use, above); the
+ * scene may belong to another context of the same device.  numHits == 0 does nothing.  RTR_ERR_INVALID_ARGUMENT (with a message) for a
+ * null or misaligned pointer or a scene on another device. */
+int  rtr_hit_leaves_async(rtr_ctx* ctx, const rtr_scene* scene, const RtrHit* hits, uint32_t numHits, int32_t* leaves);
+/* The same, then joins ctx's stream (only that stream). */
+int  rtr_hit_leaves(rtr_ctx* ctx, const rtr_scene* scene, const RtrHit* hits, uint32_t numHits, int32_t* leaves);
+/* rtr_trace_occlusion with a start hint per ray: startLeaves is a DEVICE pointer, 4-B aligned, numRays entries, read at the refill beside
+ * the ray it belongs to (the queue build does not look at it); NULL behaves exactly as the unhinted call.  Everything else — flags,
+ * the scratch and its size, occluded[], the rays that need a deeper stack (finished over the BVH2 from the root) — as there.  stats: as
+ * documented for rtr_trace_occlusion; for rtr_light_rays_hinted's rays and hints of a frame's camera hits the counters are the renderer's
+ * any-hit counters with the default trace_own_leaf = 1. */
+int  rtr_trace_occlusion_hinted_async(rtr_ctx* ctx, const rtr_scene* scene, const RtrRay* rays, const int32_t* startLeaves, uint32_t numRays,
+                                      uint32_t flags, void* scratch, size_t scratchBytes, uint8_t* occluded);
+int  rtr_trace_occlusion_hinted(rtr_ctx* ctx, const rtr_scene* scene, const RtrRay* rays, const int32_t* startLeaves, uint32_t numRays,
+                                uint32_t flags, void* scratch, size_t scratchBytes, uint8_t* occluded, rtr_query_stats* stats);
 /* Writes to the device array out[] the width * height * spp camera rays the renderer traces for `camera` (raygen.rgen:83-107:
  * jittered direction through the viewport, tmin 0.001, tmax 10000): ray k = (py * width + px) * spp + i.  ENQUEUED on ctx's stream.
  * Callers generate, edit and trace camera rays this way; traced with RTR_QUERY_CLOSEST they give the renderer's primary hits.
@@ -424,7 +456,8 @@ int  rtr_hit_surfaces(rtr_ctx* ctx, const rtr_scene* scene, const RtrRay* rays, 
  * What the ray-gen shader does AFTER the closest hit (raygen.rgen:165-338, :345-357), in the stages the renderer itself runs it in:
  *   rtr_light_rays   the shadow rays of each hit        (the area-light samples of :206-231, the directional light of :299-303)
  *   rtr_trace_rays   RTR_QUERY_ANY answers them         (the caller's launch: any of the stages can be replaced; rtr_trace_occlusion
- *                                                        gives the same bytes)
+ *                                                        gives the same bytes, and so does rtr_trace_occlusion_hinted with
+ *                                                        rtr_light_rays_hinted's hints: the renderer's own walk, rule for rule)
  *   rtr_shade_hits   the Cook-Torrance sums, the LTC term, sky and light hits
  *   rtr_tonemap_pack ACES + sRGB + B,G,R,255
  * camera rays -> closest hit -> these four reproduce rtr_render's images from public parts: at 1 sample per pixel bit for bit (with
@@ -461,6 +494,14 @@ int  rtr_light_slots(const rtr_scene* scene, const rtr_light_params* params, uin
  * a scene on another device, params rtr_light_slots refuses, width or spp == 0 with seeds == NULL, or numHits * Q past 32 bits. */
 int  rtr_light_rays_async(rtr_ctx* ctx, const rtr_scene* scene, const RtrRay* rays, const RtrHit* hits, uint32_t numHits,
                           const rtr_light_params* params, const uint32_t* seeds, RtrRay* outRays);
+/* rtr_light_rays and the start hints of its rays (rtr_trace_occlusion_hinted): outRays is byte for byte what rtr_light_rays writes, and
+ * outLeaves (DEVICE pointer, 4-B aligned, numHits * Q entries) gets at k * Q + slot the leaf code of hit k's own triangle exactly where
+ * the renderer marks the ray — the slot's ray is sent and dot(hitNormal, lightVec) < 0 with the un-normalised vector to the light sample —
+ * and 0 at every other slot: null slots, the directional light's slot Q - 1, every slot of a hit that is a miss, a light or invalid.
+ * The leaf is looked up in the scene's triangle -> leaf table, whose first use allocates (see rtr_hit_leaves).  Otherwise as
+ * rtr_light_rays_async; RTR_ERR_INVALID_ARGUMENT also for a null or misaligned outLeaves. */
+int  rtr_light_rays_hinted_async(rtr_ctx* ctx, const rtr_scene* scene, const RtrRay* rays, const RtrHit* hits, uint32_t numHits,
+                                 const rtr_light_params* params, const uint32_t* seeds, RtrRay* outRays, int32_t* outLeaves);
 /* out[k] = the RtrRadiance of hit k: one primary sample's contribution — the sky at a miss and the light's colour at a light hit in every
  * sum asked for, the light loops at an object, zeros and RTR_SURFACE_INVALID for ids out of range.  occluded: the numHits * Q bytes an
  * RTR_QUERY_ANY query of rtr_light_rays' rays returned (no alignment asked); bytes of null slots are not read.  Sums not in
@@ -473,9 +514,11 @@ int  rtr_shade_hits_async(rtr_ctx* ctx, const rtr_scene* scene, const RtrRay* ra
  * RtrRadiance (stride 48), an RGBA float image (16), packed float3 (12).  strideBytes: a multiple of 4, >= 12; both pointers 4-B
  * aligned DEVICE pointers.  ENQUEUED on ctx's stream. */
 int  rtr_tonemap_pack_async(rtr_ctx* ctx, const float* radiance, uint32_t strideBytes, uint32_t numValues, uint32_t* outBGRA8);
-/* The same three, then join ctx's stream (only that stream). */
+/* The same four, then join ctx's stream (only that stream). */
 int  rtr_light_rays(rtr_ctx* ctx, const rtr_scene* scene, const RtrRay* rays, const RtrHit* hits, uint32_t numHits,
                     const rtr_light_params* params, const uint32_t* seeds, RtrRay* outRays);
+int  rtr_light_rays_hinted(rtr_ctx* ctx, const rtr_scene* scene, const RtrRay* rays, const RtrHit* hits, uint32_t numHits,
+                           const rtr_light_params* params, const uint32_t* seeds, RtrRay* outRays, int32_t* outLeaves);
 int  rtr_shade_hits(rtr_ctx* ctx, const rtr_scene* scene, const RtrRay* rays, const RtrHit* hits, uint32_t numHits,
                     const rtr_light_params* params, const uint32_t* seeds, const uint8_t* occluded, RtrRadiance* out);
 int  rtr_tonemap_pack(rtr_ctx* ctx, const float* radiance, uint32_t strideBytes, uint32_t numValues, uint32_t* outBGRA8);

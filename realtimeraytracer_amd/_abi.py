@@ -207,12 +207,18 @@ RTR_SYMBOLS = {
     "rtr_occlusion_scratch_bytes": (C.c_int, [u32, P(C.c_size_t)]),
     "rtr_trace_occlusion_async": (C.c_int, [VP, VP, VP, u32, u32, VP, C.c_size_t, VP]),
     "rtr_trace_occlusion": (C.c_int, [VP, VP, VP, u32, u32, VP, C.c_size_t, VP, P(rtr_query_stats)]),
+    "rtr_trace_occlusion_hinted_async": (C.c_int, [VP, VP, VP, VP, u32, u32, VP, C.c_size_t, VP]),
+    "rtr_trace_occlusion_hinted": (C.c_int, [VP, VP, VP, VP, u32, u32, VP, C.c_size_t, VP, P(rtr_query_stats)]),
+    "rtr_hit_leaves_async": (C.c_int, [VP, VP, VP, u32, VP]),
+    "rtr_hit_leaves": (C.c_int, [VP, VP, VP, u32, VP]),
     "rtr_camera_rays_async": (C.c_int, [VP, P(RtrCameraData), u32, u32, u32, VP]),
     "rtr_hit_surfaces_async": (C.c_int, [VP, VP, VP, VP, u32, VP]),
     "rtr_hit_surfaces": (C.c_int, [VP, VP, VP, VP, u32, VP]),
     "rtr_light_slots": (C.c_int, [VP, P(rtr_light_params), P(u32)]),
     "rtr_light_rays_async": (C.c_int, [VP, VP, VP, VP, u32, P(rtr_light_params), VP, VP]),
     "rtr_light_rays": (C.c_int, [VP, VP, VP, VP, u32, P(rtr_light_params), VP, VP]),
+    "rtr_light_rays_hinted_async": (C.c_int, [VP, VP, VP, VP, u32, P(rtr_light_params), VP, VP, VP]),
+    "rtr_light_rays_hinted": (C.c_int, [VP, VP, VP, VP, u32, P(rtr_light_params), VP, VP, VP]),
     "rtr_shade_hits_async": (C.c_int, [VP, VP, VP, VP, u32, P(rtr_light_params), VP, VP, VP]),
     "rtr_shade_hits": (C.c_int, [VP, VP, VP, VP, u32, P(rtr_light_params), VP, VP, VP]),
     "rtr_tonemap_pack_async": (C.c_int, [VP, VP, u32, u32, VP]),

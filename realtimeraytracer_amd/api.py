@@ -349,11 +349,13 @@ def occlusion_scratch_bytes(lib, n):
     return int(b.value)
 
 
-def trace_occlusion(scene, rays, opaque=False, collect_stats=False, ctx=None, asynchronous=False):
+def trace_occlusion(scene, rays, opaque=False, collect_stats=False, ctx=None, asynchronous=False, start_leaves=None):
     """rtr_trace_occlusion: the queued occlusion query — the same bytes as trace_rays(any_hit=True), answered by the renderer's any-hit
     machinery (rays binned by direction octant, persistent waves over the 4-wide tree).  rays, opaque, ctx, asynchronous, collect_stats
     and the QueryResult (occluded, stats) as in trace_rays.  The query's scratch is a uint8 device tensor kept on the context and grown
-    when a longer ray array comes; queries on one context are ordered on its stream, so they share it."""
+    when a longer ray array comes; queries on one context are ordered on its stream, so they share it.
+    start_leaves (rtr_trace_occlusion_hinted): one int32 start hint per ray — light_rays(hints=True)'s or hit_leaves' — as an (N,) int32
+    device tensor or numpy array like the rays; any value is safe and none changes a byte, only the work.  None: the unhinted query."""
     torch = _torch()
     ctx = ctx or scene.ctx
     dev = torch.device("cuda", ctx.device)
@@ -377,6 +379,18 @@ def trace_occlusion(scene, rays, opaque=False, collect_stats=False, ctx=None, as
     if asynchronous and ctx.get_stream() != torch.cuda.current_stream(dev).cuda_stream:
         raise ValueError("trace_occlusion: an asynchronous query needs the context on torch's current stream (ctx.set_stream)")
     n = int(r.shape[0])
+    sl = None
+    if start_leaves is not None:
+        if isinstance(start_leaves, np.ndarray):
+            if not as_numpy or start_leaves.dtype != np.int32 or start_leaves.shape != (n,):
+                raise ValueError(f"trace_occlusion: start_leaves must be int32 ({n},), numpy like the rays; got {start_leaves.dtype} {start_leaves.shape}")
+            sl = torch.from_numpy(np.ascontiguousarray(start_leaves)).to(dev)
+        elif isinstance(start_leaves, torch.Tensor):
+            if as_numpy or start_leaves.dtype != torch.int32 or tuple(start_leaves.shape) != (n,) or start_leaves.device != dev or not start_leaves.is_contiguous():
+                raise ValueError(f"trace_occlusion: start_leaves must be a contiguous int32 ({n},) tensor on {dev}, like the rays")
+            sl = start_leaves
+        else:
+            raise ValueError(f"trace_occlusion: start_leaves must be a torch tensor or a numpy array, got {type(start_leaves).__name__}")
     need = occlusion_scratch_bytes(ctx.lib, n)
     scratch = getattr(ctx, "_occlusion_scratch", None)
     if scratch is None or scratch.numel() < need:
@@ -385,16 +399,25 @@ def trace_occlusion(scene, rays, opaque=False, collect_stats=False, ctx=None, as
     if not asynchronous and ctx.get_stream() != torch.cuda.current_stream(dev).cuda_stream:
         torch.cuda.current_stream(dev).synchronize()        # the rays (and the outputs' memory) are ready for the context's stream
     flags = A.QUERY_OPAQUE if opaque else 0
-    args = (A.VP(r.data_ptr()), n, flags, A.VP(scratch.data_ptr()), scratch.numel(), A.VP(occ.data_ptr())) if n else (None, 0, flags, None, 0, None)
+    args = (n, flags, A.VP(scratch.data_ptr()), scratch.numel(), A.VP(occ.data_ptr())) if n else (0, flags, None, 0, None)
+    rp = A.VP(r.data_ptr()) if n else None
     out = QueryResult()
-    if asynchronous:
-        _check(ctx.lib.rtr_trace_occlusion_async(ctx.h, scene.h, *args), "rtr_trace_occlusion_async")
+    if sl is not None:
+        hp = A.VP(sl.data_ptr()) if n else None
+        if asynchronous:
+            _check(ctx.lib.rtr_trace_occlusion_hinted_async(ctx.h, scene.h, rp, hp, *args), "rtr_trace_occlusion_hinted_async")
+        else:
+            st = A.rtr_query_stats() if collect_stats else None
+            _check(ctx.lib.rtr_trace_occlusion_hinted(ctx.h, scene.h, rp, hp, *args, C.byref(st) if st is not None else None), "rtr_trace_occlusion_hinted")
+            out.stats = st
+    elif asynchronous:
+        _check(ctx.lib.rtr_trace_occlusion_async(ctx.h, scene.h, rp, *args), "rtr_trace_occlusion_async")
     else:
         st = A.rtr_query_stats() if collect_stats else None
-        _check(ctx.lib.rtr_trace_occlusion(ctx.h, scene.h, *args, C.byref(st) if st is not None else None), "rtr_trace_occlusion")
+        _check(ctx.lib.rtr_trace_occlusion(ctx.h, scene.h, rp, *args, C.byref(st) if st is not None else None), "rtr_trace_occlusion")
         out.stats = st
     out.occluded = occ.cpu().numpy() if as_numpy else occ
-    out._keep = (r, occ, scratch)        # an asynchronous query's buffers stay alive with its result
+    out._keep = (r, sl, occ, scratch)    # an asynchronous query's buffers stay alive with its result
     return out
 
 
@@ -477,6 +500,33 @@ def hit_surfaces(scene, rays, hits, ctx=None, asynchronous=False):
     return res
 
 
+def hit_leaves(scene, hits, ctx=None, asynchronous=False):
+    """rtr_hit_leaves: the start hint of each hit — the code of the BVH leaf its triangle sits in, 0 for a miss or ids out of range — as
+    int32 (N,), for rays the caller makes from a hit and hands to trace_occlusion(start_leaves=...).  hits: a closest-hit QueryResult or
+    its (N, 8) int32 RtrHit records; a device tensor gives a device tensor, numpy gives numpy.  The scene's first call builds its
+    triangle -> leaf table.  ctx and asynchronous as in trace_rays."""
+    torch = _torch()
+    ctx = ctx or scene.ctx
+    dev = torch.device("cuda", ctx.device)
+    if isinstance(hits, QueryResult):
+        if hits.hits is None:
+            raise ValueError("hit_leaves: the QueryResult holds no hit records (an any-hit query)")
+        hits = hits.hits
+    h, as_numpy = _device_array(torch, hits, torch.int32, np.int32, "hits", dev, "hit_leaves")
+    if asynchronous and ctx.get_stream() != torch.cuda.current_stream(dev).cuda_stream:
+        raise ValueError("hit_leaves: an asynchronous call needs the context on torch's current stream (ctx.set_stream)")
+    n = int(h.shape[0])
+    out = torch.empty(n, dtype=torch.int32, device=dev)
+    if not asynchronous and ctx.get_stream() != torch.cuda.current_stream(dev).cuda_stream:
+        torch.cuda.current_stream(dev).synchronize()        # the hits (and the output's memory) are ready for the context's stream
+    fn = ctx.lib.rtr_hit_leaves_async if asynchronous else ctx.lib.rtr_hit_leaves
+    _check(fn(ctx.h, scene.h, A.VP(h.data_ptr()) if n else None, n, A.VP(out.data_ptr()) if n else None), "rtr_hit_leaves")
+    if as_numpy:
+        return out.cpu().numpy()
+    out._keep = h                        # an asynchronous call's input stays alive with its result
+    return out
+
+
 # ---- direct lighting for ray-query hits (rtr_light_rays, rtr_shade_hits, rtr_tonemap_pack) ----------------------------------------
 class RadianceResult:
     """What shade_hits and direct_light give back: views into one (N, 12) array of RtrRadiance records (raw, float32).  shadowed,
@@ -528,11 +578,13 @@ def _light_inputs(torch, scene, rays, hits, seeds, ctx, who, asynchronous):
     return r, h, sd, rn
 
 
-def light_rays(scene, rays, hits, params, seeds=None, ctx=None, asynchronous=False):
+def light_rays(scene, rays, hits, params, seeds=None, ctx=None, asynchronous=False, hints=False):
     """rtr_light_rays: the shadow rays the ray-gen shader sends for each hit, as an (N * Q, 8) float32 array of RtrRay (Q =
     light_slots(scene, params)); hit k's rays are rows k * Q ... k * Q + Q, a slot without a ray holds eight zeros.  rays, hits as
     hit_surfaces takes them; seeds: int32 (N,) bases of the sample seeds, default the pixel's (params.width, params.spp).  Device
-    tensors in give a device tensor out, numpy in gives numpy out; ctx and asynchronous as in trace_rays."""
+    tensors in give a device tensor out, numpy in gives numpy out; ctx and asynchronous as in trace_rays.
+    hints=True (rtr_light_rays_hinted): returns (rays, leaves) — the same rays and the int32 (N * Q,) start hints of the queued occlusion
+    query (trace_occlusion(start_leaves=...)): the hit's leaf where the renderer marks the ray as leaving into its surface, else 0."""
     torch = _torch()
     ctx = ctx or scene.ctx
     dev = torch.device("cuda", ctx.device)
@@ -541,18 +593,23 @@ def light_rays(scene, rays, hits, params, seeds=None, ctx=None, asynchronous=Fal
     if n * q > 0xffffffff:
         raise ValueError(f"light_rays: {n} hits x {q} slots do not fit 32 bits")
     out = torch.empty((n * q, 8), dtype=torch.float32, device=dev)
+    leaves = torch.empty(n * q, dtype=torch.int32, device=dev) if hints else None
     if not asynchronous and ctx.get_stream() != torch.cuda.current_stream(dev).cuda_stream:
         torch.cuda.current_stream(dev).synchronize()        # the inputs (and the output's memory) are ready for the context's stream
-    fn = ctx.lib.rtr_light_rays_async if asynchronous else ctx.lib.rtr_light_rays
+    if hints:
+        fn, who = (ctx.lib.rtr_light_rays_hinted_async if asynchronous else ctx.lib.rtr_light_rays_hinted), "rtr_light_rays_hinted"
+        extra = (A.VP(leaves.data_ptr()) if n else None,)
+    else:
+        fn, who, extra = (ctx.lib.rtr_light_rays_async if asynchronous else ctx.lib.rtr_light_rays), "rtr_light_rays", ()
     if n:
         _check(fn(ctx.h, scene.h, A.VP(r.data_ptr()), A.VP(h.data_ptr()), n, C.byref(params), A.VP(sd.data_ptr()) if sd is not None else None,
-                  A.VP(out.data_ptr())), "rtr_light_rays")
+                  A.VP(out.data_ptr()), *extra), who)
     else:
-        _check(fn(ctx.h, scene.h, None, None, 0, C.byref(params), None, None), "rtr_light_rays")
+        _check(fn(ctx.h, scene.h, None, None, 0, C.byref(params), None, None, *extra), who)
     if as_numpy:
-        return out.cpu().numpy()
+        return (out.cpu().numpy(), leaves.cpu().numpy()) if hints else out.cpu().numpy()
     out._keep = (r, h, sd)               # an asynchronous call's inputs stay alive with its result
-    return out
+    return (out, leaves) if hints else out
 
 
 def shade_hits(scene, rays, hits, params, occluded, seeds=None, ctx=None, asynchronous=False):
@@ -629,16 +686,17 @@ def tonemap_pack(ctx, radiance, asynchronous=False):
 def direct_light(scene, rays, hits=None, params=None, seeds=None, ctx=None, max_ray_bytes=256 << 20, occlusion="dense"):
     """The composed stage: closest hit (when hits is None) -> light_rays -> trace_rays(any_hit=True) -> shade_hits, in chunks of hits
     so that a chunk's light rays (n * Q * 32 bytes) stay within max_ray_bytes — a 1080p frame at Q = 7 would be 464 MB of rays at once.
-    Chunks do not change the result.  occlusion: "dense" (trace_rays, the default) or "queued" (trace_occlusion): the same bytes.  rays: a float32 (N, 8) device tensor; hits: a QueryResult, (N, 8) int32 records, or None;
+    Chunks do not change the result.  occlusion: "dense" (trace_rays, the default), "queued" (trace_occlusion) or "queued_own_leaf"
+    (light_rays(hints=True) and trace_occlusion(start_leaves=...): the renderer's own walk, own-leaf rule included): the same bytes.  rays: a float32 (N, 8) device tensor; hits: a QueryResult, (N, 8) int32 records, or None;
     params: make_light_params(...).  Returns a RadianceResult on the device."""
-    torch = _torch()
-    ctx = ctx or scene.ctx
+    if occlusion not in ("dense", "queued", "queued_own_leaf"):
+        raise ValueError(f"direct_light: occlusion must be 'dense', 'queued' or 'queued_own_leaf', got {occlusion!r}")
     if params is None:
         raise ValueError("direct_light: params (make_light_params) are needed")
+    torch = _torch()
+    ctx = ctx or scene.ctx
     if not isinstance(rays, torch.Tensor):
         raise ValueError("direct_light: rays must be a device tensor")
-    if occlusion not in ("dense", "queued"):
-        raise ValueError(f"direct_light: occlusion must be 'dense' or 'queued', got {occlusion!r}")
     if hits is None:
         hits = trace_rays(scene, rays, ctx=ctx)
     if isinstance(hits, QueryResult):
@@ -653,7 +711,11 @@ def direct_light(scene, rays, hits=None, params=None, seeds=None, ctx=None, max_
             k = torch.arange(a, b, device=rays.device, dtype=torch.int64) // int(params.spp)
             sd = ((k % int(params.width)) * 733 + (k // int(params.width)) * 1933).to(torch.int32)      # wraps to 32 bits as the kernel's words do
         r, h = rays[a:b], hits[a:b]
-        lr = light_rays(scene, r, h, params, seeds=sd, ctx=ctx)
-        occ = (trace_occlusion(scene, lr, ctx=ctx) if occlusion == "queued" else trace_rays(scene, lr, any_hit=True, ctx=ctx)).occluded
+        if occlusion == "queued_own_leaf":
+            lr, leaves = light_rays(scene, r, h, params, seeds=sd, ctx=ctx, hints=True)
+            occ = trace_occlusion(scene, lr, ctx=ctx, start_leaves=leaves).occluded
+        else:
+            lr = light_rays(scene, r, h, params, seeds=sd, ctx=ctx)
+            occ = (trace_occlusion(scene, lr, ctx=ctx) if occlusion == "queued" else trace_rays(scene, lr, any_hit=True, ctx=ctx)).occluded
         out[a:b] = shade_hits(scene, r, h, params, occ, seeds=sd, ctx=ctx).raw
     return _radiance_result(out, False, torch)

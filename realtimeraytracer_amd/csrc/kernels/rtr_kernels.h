@@ -129,6 +129,10 @@ struct OcclusionArgs {
     uint32_t* queue;             /* n ray indices, binned by direction octant */
     uint2* lists;                /* kQueueLists lists of listStride batches {first queue entry, rays} */
     uint32_t listStride;
+    /* rtr_trace_occlusion_hinted: per ray the code of the leaf its walk starts at (include/rtr.h: a hint), or null: every walk starts at the
+     * root.  numTris: triangle records of the scene — a code whose triangles would lie past them is no hint. */
+    const int32_t* startLeaves;
+    uint32_t numTris;
 };
 hipError_t launch_occlusion_walk(const DeviceScene& sc, const OcclusionArgs& oa, const Tunables& tun, bool alpha, Counters* stats, hipStream_t stream, uint32_t numCus);
 

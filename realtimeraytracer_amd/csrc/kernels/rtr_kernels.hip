@@ -974,8 +974,13 @@ __device__ __forceinline__ void inner_nodes4(const __amdgpu_buffer_rsrc_t nodeBu
  * array of 32-B RtrRay records (queue.slot: the indices, binned by k_occlusion_gen of rtr_occlusion.hip; queue.dt: the rays, two 16-B
  * pieces each), so the refill gathers origin, direction, tmin and tmax of its ray and the result goes to vis[index]; no ray starts at
  * a leaf (an RtrRay carries no leaf code), and an abandoned ray leaves the sentinel k_query_tail of rtr_query.hip looks for.  Everything
- * else — batch lists, refill rule, inner_nodes4, the leaf phase — is the code above and below, not a copy of it. */
-template <int STACK, bool LISTS, bool STATS, bool CALLER = false>
+ * else — batch lists, refill rule, inner_nodes4, the leaf phase — is the code above and below, not a copy of it.
+ * HINTS (CALLER only; rtr_trace_occlusion_hinted): the caller's rays come with one int32 each (queue.origin: that array; queue.slotMask:
+ * the scene's triangle records), the code of the leaf the walk starts at — the renderer's own-leaf rule for rays that are not its own.
+ * The refill loads it beside the ray and takes it as (into, ownLeaf) when it is a leaf code whose triangles all lie inside the record
+ * array; anything else (0, a positive value, kDone, a code past the records) starts at the root.  An any-hit answer does not depend on
+ * where the walk starts, so a hint changes the work, never a byte.  The forms without HINTS compile to what they were. */
+template <int STACK, bool LISTS, bool STATS, bool CALLER = false, bool HINTS = false>
 __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_shadow_trace4(DeviceScene sc, const RayQueue queue,
                                                               const uint32_t* __restrict__ count, uint32_t* nextBatch,
                                                               uint8_t* __restrict__ vis, uint32_t visFill, uint32_t kBatch, uint32_t kRefill,
@@ -993,6 +998,7 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(8, 
     typedef const __attribute__((address_space(1))) rtr_f4* global_f4;
     typedef const __attribute__((address_space(1))) uint32_t* global_u32;
     typedef __attribute__((address_space(1))) uint8_t* global_u8;
+    typedef const __attribute__((address_space(1))) int32_t* global_i32;
     __shared__ RefillConsts s_rc;
     if (threadIdx.x == 0) {
         const rtr_v3 cw = rtr_wide_centre_world(sc.grid->origin, sc.grid->scale, sc.grid->wideCentreXY, sc.grid->wideCentreZ);
@@ -1135,6 +1141,20 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(8, 
                             const float4 a = queue.dt[2 * (size_t)slot], b = queue.dt[2 * (size_t)slot + 1];
 #endif
                             o = rtr_mk(a.x, a.y, a.z); tmin = a.w; d = rtr_mk(b.x, b.y, b.z); tmax = b.w;
+                            if (HINTS) {       /* read once, like the index: past the caches */
+#if RTR_REFILL_LDS
+                                const global_i32 qhint = (global_i32)rc.origin;
+                                const uint32_t numTris = rc.slotMask;
+                                ownLeaf = (octForms & 2u) ? __builtin_nontemporal_load(qhint + slot) : qhint[slot];
+#else
+                                const uint32_t numTris = queue.slotMask;
+                                ownLeaf = reinterpret_cast<const int32_t*>(queue.origin)[slot];
+#endif
+                                /* first + count <= records, in 32 bits: first < 2^28 whatever the word is.  kDone and kAbandoned have first =
+                                 * 2^28 - 1, past any scene (rtr_check_scene_limits), so a lane can never start on a sentinel */
+                                const uint32_t code = (uint32_t)~ownLeaf;
+                                into = ownLeaf < 0 && (code >> 3) + (code & 7u) + 1u <= numTris;
+                            }
                         } else
 #if RTR_REFILL_LDS
                         {   /* queue_load() through the addresses kept in LDS */
@@ -2042,6 +2062,8 @@ hipError_t launch_occlusion_walk(const DeviceScene& sc, const OcclusionArgs& oa,
     if (!sc.nodes4) return hipErrorInvalidValue;
     RayQueue rq;
     rq.dt = const_cast<float4*>(oa.rays); rq.slot = oa.queue;
+    const bool hinted = oa.startLeaves != nullptr;
+    if (hinted) { rq.origin = reinterpret_cast<float4*>(const_cast<int32_t*>(oa.startLeaves)); rq.slotMask = oa.numTris; }      /* the HINTS form's reading of the two fields */
     uint32_t tblocks = numCus * (tun.trace_wgs_per_cu ? tun.trace_wgs_per_cu : (oa.n >= kBinnedMinRays ? 8u : 6u)) * (uint32_t)kBlock / (uint32_t)kTraceBlock;
     const uint32_t needed = (uint32_t)(((uint64_t)oa.n + kTraceBlock - 1) / kTraceBlock);
     if (tblocks > needed) tblocks = needed;
@@ -2050,9 +2072,10 @@ hipError_t launch_occlusion_walk(const DeviceScene& sc, const OcclusionArgs& oa,
     const uint32_t kTop = tun.trace_top_nodes < kTopNodes ? tun.trace_top_nodes : kTopNodes;
     const uint32_t top = kTop < sc.numNodes4 ? kTop : sc.numNodes4;
     uint32_t* const ctrl = oa.ctrl;
-#define RTR_OCC_WALK(STATS) hipLaunchKernelGGL((k_shadow_trace4<RTR_SHADOW_STACK, true, STATS, true>), dim3(tblocks), dim3(kTraceBlock), 0, s, sc, rq, ctrl, ctrl + kBatchCursorWord, \
+#define RTR_OCC_WALK(STATS, HINTS) hipLaunchKernelGGL((k_shadow_trace4<RTR_SHADOW_STACK, true, STATS, true, HINTS>), dim3(tblocks), dim3(kTraceBlock), 0, s, sc, rq, ctrl, ctrl + kBatchCursorWord, \
         oa.occluded, 0u, oa.batch, tun.trace_refill, tun.trace_inner_min, oa.overflow, oa.overflowCap, kOct, top, oa.lists, oa.listStride, stats, (unsigned long long*)nullptr)
-    if (stats) RTR_OCC_WALK(true); else RTR_OCC_WALK(false);
+    if (hinted) { if (stats) RTR_OCC_WALK(true, true); else RTR_OCC_WALK(false, true); }
+    else { if (stats) RTR_OCC_WALK(true, false); else RTR_OCC_WALK(false, false); }
 #undef RTR_OCC_WALK
     return hipGetLastError();
 }

@@ -47,9 +47,30 @@ struct LightArgs {
     uint32_t outputs;            /* RTR_LIGHT_* mask (shade) */
     uint32_t direct;             /* light rays: 1 = the unstaged form of the kernel whatever the slot count (the test build's switch) */
     float4* outRays;             /* light rays: n * slots RtrRay */
+    int32_t* outLeaves;          /* hinted light rays: n * slots start hints (LeafTable below), or null */
+    const int32_t* leafTable;    /* hinted light rays: the scene's triangle -> leaf table and its per-customIndex bases */
+    const uint32_t* leafBase;
     const uint8_t* occluded;     /* shade: n * slots visibility bytes */
     float4* out;                 /* shade: RtrRadiance as 3 x float4 */
 };
+
+/* The per-scene triangle -> leaf table (rtr_hit_leaves, rtr_light_rays_hinted): entry base[customIndex] + primitiveId, base = the prefix
+ * sum of triCount, is the child code of the BVH2 leaf that holds that world-space record (RtrBvhNode::child: negative); an entry no leaf
+ * wrote stays 0.  A start hint of the queued occlusion query (include/rtr.h). */
+struct LeafArgs {
+    const float4* hits;          /* RtrHit as 2 x float4 */
+    int32_t* leaves;             /* one hint per hit */
+    const uint32_t* triCount;    /* as SurfaceArgs */
+    const uint32_t* base;        /* per customIndex: its first entry of the table */
+    const int32_t* table;
+    uint32_t numInstances;
+    uint32_t n;
+};
+/* fills the table (zeroed by the caller) from the BVH2: nodes as 2 x uint4 apiece, tris as 3 x float4 apiece */
+hipError_t launch_leaf_table(const uint4* nodes, uint32_t numNodes, const float4* tris, uint32_t numTris, const uint32_t* triCount,
+                             const uint32_t* base, uint32_t numInstances, int32_t* table, hipStream_t stream);
+/* leaves[k] = the table entry of hits[k]; 0 for a miss or ids out of range, which read nothing */
+hipError_t launch_hit_leaves(const LeafArgs& a, hipStream_t stream);
 
 /* flags: RTR_QUERY_ANY | RTR_QUERY_OPAQUE (validated by the caller).  stats: the counting form, counters added there (zeroed by the caller). */
 hipError_t launch_query(const DeviceScene& sc, const QueryArgs& qa, uint32_t flags, Counters* stats, hipStream_t stream);
@@ -70,7 +91,8 @@ constexpr uint32_t occlusion_list_stride(uint32_t n) {      /* for the shorter b
 hipError_t launch_camera_rays(const RtrCameraData& cam, uint32_t width, uint32_t height, uint32_t spp, float4* out, hipStream_t stream);
 /* one RtrSurface per hit: the renderer's surface fetch (fetch_surface) for caller hits */
 hipError_t launch_hit_surfaces(const DeviceScene& sc, const SurfaceArgs& sa, hipStream_t stream);
-/* the shadow rays raygen.rgen:206-231 and :299-303 send for each hit, at fixed slots; a slot whose ray is not sent holds the null ray */
+/* the shadow rays raygen.rgen:206-231 and :299-303 send for each hit, at fixed slots; a slot whose ray is not sent holds the null ray.
+ * With la.outLeaves: the same rays and, per slot, the hit's leaf code where the ray leaves into its surface, else 0 */
 hipError_t launch_light_rays(const DeviceScene& sc, const LightArgs& la, hipStream_t stream);
 /* one RtrRadiance per hit: shade_sample with the visibility bytes of those slots */
 hipError_t launch_shade_hits(const DeviceScene& sc, const LightArgs& la, hipStream_t stream);

@@ -236,6 +236,61 @@ hipError_t launch_hit_surfaces(const DeviceScene& sc, const SurfaceArgs& sa, hip
     return hipGetLastError();
 }
 
+/* ---- the triangle -> leaf table (rtr_hit_leaves, rtr_light_rays_hinted) --------------------------------------------------------------
+ * One lane per BVH2 node: each of its two children that is a leaf writes its code at the (customIndex, primitiveId) of its up to 8
+ * records.  A record sits in one leaf, so no entry is written with two values (a scene of a single leaf stores it as both children of
+ * the root: the same value twice); slots of the node array that are not part of a device-built tree hold child codes 0, 0.  The ids are
+ * checked against the table's extent and the leaf against the record array before anything is read or written there: the degenerate
+ * record of an empty scene (customIndex 0xffffffff) writes nothing. */
+constexpr int kLeafTableBlock = 256;
+__global__ __launch_bounds__(kLeafTableBlock) void k_leaf_table(const uint4* __restrict__ nodes, uint32_t numNodes, const float4* __restrict__ tris,
+                                                                uint32_t numTris, const uint32_t* __restrict__ triCount, const uint32_t* __restrict__ base,
+                                                                uint32_t numInstances, int32_t* __restrict__ table) {
+    const uint32_t i = blockIdx.x * kLeafTableBlock + threadIdx.x;
+    if (i >= numNodes) return;
+    const uint4 w = nodes[2 * (size_t)i + 1];                  /* {z planes, child[0], child[1]} */
+    const int32_t child[2] = {(int32_t)w.z, (int32_t)w.w};
+#pragma unroll
+    for (int sl = 0; sl < 2; ++sl) {
+        if (child[sl] >= 0) continue;
+        const uint32_t code = (uint32_t)~child[sl];
+        const uint32_t first = code >> 3, cnt = (code & 7u) + 1u;
+        if (first + cnt > numTris) continue;
+        for (uint32_t j = first; j < first + cnt; ++j) {
+            const uint32_t custom = __float_as_uint(tris[3 * (size_t)j].w), prim = __float_as_uint(tris[3 * (size_t)j + 1].w);
+            if (custom < numInstances && prim < triCount[custom]) table[base[custom] + prim] = child[sl];
+        }
+    }
+}
+
+hipError_t launch_leaf_table(const uint4* nodes, uint32_t numNodes, const float4* tris, uint32_t numTris, const uint32_t* triCount,
+                             const uint32_t* base, uint32_t numInstances, int32_t* table, hipStream_t s) {
+    if (numNodes == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_leaf_table, dim3((numNodes + kLeafTableBlock - 1) / kLeafTableBlock), dim3(kLeafTableBlock), 0, s, nodes, numNodes, tris, numTris,
+                       triCount, base, numInstances, table);
+    return hipGetLastError();
+}
+
+/* the table entry of a hit's ids, or 0 (a miss, RTR_STACK_OVERFLOW and anything else out of range: nothing is read for them) */
+__device__ __forceinline__ int32_t leaf_of(const uint32_t* __restrict__ triCount, const uint32_t* __restrict__ base, const int32_t* __restrict__ table,
+                                           uint32_t numInstances, uint32_t custom, uint32_t prim) {
+    if (custom >= numInstances || prim >= triCount[custom]) return 0;
+    return table[base[custom] + prim];
+}
+
+constexpr int kHitLeavesBlock = 256;
+__global__ __launch_bounds__(kHitLeavesBlock) void k_hit_leaves(LeafArgs a) {
+    const uint32_t k = blockIdx.x * kHitLeavesBlock + threadIdx.x;
+    if (k >= a.n) return;
+    const uint32_t custom = __float_as_uint(a.hits[2 * (size_t)k].w), prim = __float_as_uint(a.hits[2 * (size_t)k + 1].x);
+    a.leaves[k] = leaf_of(a.triCount, a.base, a.table, a.numInstances, custom, prim);
+}
+
+hipError_t launch_hit_leaves(const LeafArgs& a, hipStream_t s) {
+    hipLaunchKernelGGL(k_hit_leaves, dim3((uint32_t)(((uint64_t)a.n + kHitLeavesBlock - 1) / kHitLeavesBlock)), dim3(kHitLeavesBlock), 0, s, a);
+    return hipGetLastError();
+}
+
 /* ---- direct lighting for caller hits (rtr_light_rays, rtr_shade_hits, rtr_tonemap_pack) ------------------------------------------------
  * What raygen.rgen:110-338 does with a closest hit, cut where the renderer's staged pipeline cuts it: the shadow rays of a hit, and —
  * once the caller has had them answered (rtr_trace_rays, RTR_QUERY_ANY) — the sums.  Both kernels run light_loops(), the loops
@@ -277,6 +332,23 @@ struct RayEmitPolicy {
     }
 };
 
+/* RayEmitPolicy and, beside each ray, its start hint for the queued occlusion query (rtr_light_rays_hinted): the leaf of the hit's own
+ * triangle where the ray leaves INTO the surface — light_loops' intoSurface, the mark the renderer's queue build sets — else 0.  The
+ * hints have a row of their own, one word per slot. */
+template <class Row, class HintRow>
+struct RayHintEmitPolicy {
+    static constexpr bool kShade = false;
+    Row row; HintRow hints; int32_t leaf; uint32_t slot, last;
+    __device__ __forceinline__ void slots_at(uint32_t first) { slot = first == kDirectionalSlot ? last : first; }
+    __device__ __forceinline__ bool occluded(rtr_v3 o, rtr_v3 d, float tmax, rtr_v3, bool into) {
+        row[2u * slot] = rtr_q4{o.x, o.y, o.z, 0.001f};
+        row[2u * slot + 1u] = rtr_q4{d.x, d.y, d.z, tmax};
+        hints[slot] = into ? leaf : 0;
+        ++slot;
+        return false;
+    }
+};
+
 /* One lane per hit, one wave per workgroup.  A hit's Q rays are 32 B apiece and 32 Q bytes from the next lane's: stored where the light
  * loops make them, every store instruction of the wave touches 64 different cache lines, half of each.  STAGED (Q <= kLightStagedSlots):
  * the wave's rays are made in LDS — lane l's row at l * (2 Q + 1) 16-B pieces: the odd pitch spreads the eight lanes a ds_write_b128
@@ -287,13 +359,20 @@ struct RayEmitPolicy {
  * the loops at the 32 Q-byte lane stride.  (The pre-fill cannot be a memset ahead of the kernel in either form without writing the
  * buffer twice.)  Both forms write the same bytes; tests/test_gpu_direct_light.py runs both against one another.  Measured on the bench
  * frame's camera hits (1920x1080, Q = 13, 863 MB of rays): staged 0.277 ms (3.1 TB/s written), direct 0.596 ms
- * (profiles/direct_light_rate.py, profiles/direct_light/). */
+ * (profiles/direct_light_rate.py, profiles/direct_light/).
+ * HINTS (rtr_light_rays_hinted): the rays as before and la.outLeaves, one word per slot.  STAGED, the wave's hints are made in LDS behind
+ * the rays — lane l's row at l * (Q | 1) words, zeros first: the 0 of every slot without a mark — and stored as the wave's contiguous
+ * 64 * Q * 4-byte block, lane i on the i-th word, 256 B per store instruction; !STAGED, zeros and hints go straight to the 4 Q-byte lane
+ * stride.  The forms without HINTS compile to what they were. */
 constexpr int kLightRaysBlock = 64;
 constexpr uint32_t kLightStagedSlots = 31;       /* 64 lanes x (2 * 31 + 1) pieces x 16 B = 63 KiB */
-template <bool STAGED>
+constexpr uint32_t kLightStagedLds = 64u << 10;  /* what a workgroup's stage may take: rays, and hints behind them */
+__host__ __device__ constexpr uint32_t light_hint_pitch(uint32_t q) { return q | 1u; }      /* odd, as the rays' pitch: the lanes that write one slot spread over the banks */
+template <bool STAGED, bool HINTS = false>
 __global__ __launch_bounds__(kLightRaysBlock) void k_light_rays(DeviceScene sc, LightArgs la) {
     extern __shared__ rtr_q4 s_stage[];
     typedef __attribute__((address_space(3))) rtr_q4* lds_q4;      /* keeps the accesses ds_read / ds_write */
+    typedef __attribute__((address_space(3))) int32_t* lds_i32;
     const lds_q4 stage = (lds_q4)s_stage;
     const uint32_t lane = threadIdx.x;
     const uint64_t k0 = (uint64_t)blockIdx.x * kLightRaysBlock;
@@ -302,11 +381,16 @@ __global__ __launch_bounds__(kLightRaysBlock) void k_light_rays(DeviceScene sc, 
     const uint32_t Q = la.slots, pieces = 2u * Q, pitch = pieces + 1u;
     rtr_q4* __restrict__ out = reinterpret_cast<rtr_q4*>(la.outRays) + k0 * pieces;          /* the wave's block */
     const rtr_q4 zero = {0.0f, 0.0f, 0.0f, 0.0f};
+    const uint32_t hpitch = light_hint_pitch(Q);
+    const lds_i32 hstage = (lds_i32)(stage + kLightRaysBlock * pitch);                         /* HINTS && STAGED: behind the rays */
+    int32_t* __restrict__ outHints = HINTS ? la.outLeaves + k0 * Q : nullptr;                /* the wave's block */
     if (STAGED) {
         for (uint32_t i = lane; i < kLightRaysBlock * pitch; i += kLightRaysBlock) stage[i] = zero;
+        if (HINTS) for (uint32_t i = lane; i < kLightRaysBlock * hpitch; i += kLightRaysBlock) hstage[i] = 0;
         __syncthreads();
     } else if (live) {
         for (uint32_t j = 0; j < pieces; ++j) out[(size_t)lane * pieces + j] = zero;
+        if (HINTS) for (uint32_t j = 0; j < Q; ++j) outHints[(size_t)lane * Q + j] = 0;
     }
     if (live) {
         HitRec h;
@@ -317,7 +401,16 @@ __global__ __launch_bounds__(kLightRaysBlock) void k_light_rays(DeviceScene sc, 
             Surface sf;
             LocalStats st;
             fetch_surface<false, false>(sc, ra, h, dir, false, acc, sf, st);
-            if (STAGED) {
+            if (HINTS) {
+                const int32_t leaf = leaf_of(la.triCount, la.leafBase, la.leafTable, la.numInstances, h.custom, h.prim);
+                if (STAGED) {
+                    RayHintEmitPolicy<lds_q4, lds_i32> pol{stage + lane * pitch, hstage + lane * hpitch, leaf, 0u, Q - 1u};
+                    light_loops<RayHintEmitPolicy<lds_q4, lds_i32>, false>(sc, ra, 0u, 0u, sf, 0u, acc, pol, st);
+                } else {
+                    RayHintEmitPolicy<rtr_q4*, int32_t*> pol{out + (size_t)lane * pieces, outHints + (size_t)lane * Q, leaf, 0u, Q - 1u};
+                    light_loops<RayHintEmitPolicy<rtr_q4*, int32_t*>, false>(sc, ra, 0u, 0u, sf, 0u, acc, pol, st);
+                }
+            } else if (STAGED) {
                 RayEmitPolicy<lds_q4> pol{stage + lane * pitch, 0u, Q - 1u};
                 light_loops<RayEmitPolicy<lds_q4>, false>(sc, ra, 0u, 0u, sf, 0u, acc, pol, st);
             } else {
@@ -338,12 +431,27 @@ __global__ __launch_bounds__(kLightRaysBlock) void k_light_rays(DeviceScene sc, 
             row += stepRow; rest += stepRest;
             if (rest >= pieces) { rest -= pieces; ++row; }
         }
+        if (HINTS) {      /* the same walk over the hint words: word p belongs to row p / Q */
+            const uint32_t words = total / 2u;
+            const uint32_t hStepRow = (uint32_t)kLightRaysBlock / Q, hStepRest = (uint32_t)kLightRaysBlock % Q;
+            uint32_t hrow = lane / Q, hrest = lane % Q;
+            for (uint32_t p = lane; p < words; p += kLightRaysBlock) {
+                outHints[p] = hstage[hrow * hpitch + hrest];
+                hrow += hStepRow; hrest += hStepRest;
+                if (hrest >= Q) { hrest -= Q; ++hrow; }
+            }
+        }
     }
 }
 
 hipError_t launch_light_rays(const DeviceScene& sc, const LightArgs& la, hipStream_t s) {
     const uint32_t blocks = (uint32_t)(((uint64_t)la.n + kLightRaysBlock - 1) / kLightRaysBlock);
-    if (la.slots <= kLightStagedSlots && !la.direct) {
+    if (la.outLeaves) {      /* staged while rays and hints both fit the stage */
+        const size_t lds = (size_t)kLightRaysBlock * ((2u * (size_t)la.slots + 1u) * sizeof(rtr_q4) + light_hint_pitch(la.slots) * sizeof(int32_t));
+        if (la.slots <= kLightStagedSlots && lds <= kLightStagedLds && !la.direct)
+            hipLaunchKernelGGL((k_light_rays<true, true>), dim3(blocks), dim3(kLightRaysBlock), lds, s, sc, la);
+        else hipLaunchKernelGGL((k_light_rays<false, true>), dim3(blocks), dim3(kLightRaysBlock), 0, s, sc, la);
+    } else if (la.slots <= kLightStagedSlots && !la.direct) {
         const size_t lds = (size_t)kLightRaysBlock * (2u * la.slots + 1u) * sizeof(rtr_q4);
         hipLaunchKernelGGL(k_light_rays<true>, dim3(blocks), dim3(kLightRaysBlock), lds, s, sc, la);
     } else hipLaunchKernelGGL(k_light_rays<false>, dim3(blocks), dim3(kLightRaysBlock), 0, s, sc, la);

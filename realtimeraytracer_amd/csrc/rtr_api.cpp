@@ -122,6 +122,12 @@ struct rtr_scene {
     DevBuf<uint32_t> lightTriFirst;      /* first record of light l */
     DevBuf<uint32_t> triCount;           /* per customIndex: triangles of the light or of the instance's mesh (rtr_hit_surfaces' range check) */
     uint32_t numInstances = 0;
+    /* the triangle -> leaf table (rtr_hit_leaves, rtr_light_rays_hinted): made by the first call that asks for it (ensure_leaf_table), kept
+     * through refits, which keep topology and leaf order.  mutable: the query calls take the scene const */
+    std::vector<uint32_t> hostTriCount;
+    mutable DevBuf<uint32_t> leafBase;   /* per customIndex: prefix sum of triCount */
+    mutable DevBuf<int32_t> leafTable;
+    mutable bool leafReady = false;
     DevBuf<float> xforms, nmats, ltc1, ltc2;
     std::vector<DevBuf<uint8_t>> texPixels;
     DevBuf<uint8_t> hdriPixels;
@@ -640,6 +646,7 @@ static int scene_create_impl(rtr_ctx* ctx, const rtr_scene_desc* d, const rtr_sc
             count[in.customIndex] = in.customIndex < d->numLights ? d->lights[in.customIndex].numTriangles : d->meshes[in.meshIndex].indexCount / 3u;
         }
         chk(s->triCount.upload(count.data(), count.size(), st));
+        s->hostTriCount.swap(count);
     }
     chk(s->xforms.upload(xforms.data(), xforms.size(), st));
     chk(s->nmats.upload(nmats.data(), nmats.size(), st));
@@ -1513,8 +1520,12 @@ int rtr_occlusion_scratch_bytes(uint32_t numRays, size_t* bytes) {
     return RTR_OK;
 }
 
-static int enqueue_occlusion(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, uint32_t n, uint32_t flags, void* scratch, size_t scratchBytes,
-                             uint8_t* occluded, bool count, const char* who) {
+static bool aligned4(const void* p) { return ((uintptr_t)p & 3u) == 0; }
+
+/* startLeaves: the hints of rtr_trace_occlusion_hinted (null: none; the unhinted calls pass null) */
+static int enqueue_occlusion(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const int32_t* startLeaves, uint32_t n, uint32_t flags, void* scratch,
+                             size_t scratchBytes, uint8_t* occluded, bool count, const char* who) {
+    if (n && !aligned4(startLeaves)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: startLeaves is not 4-B aligned", who);
     if (!c || !s) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: null context or scene", who);
     if (flags & ~(RTR_QUERY_ANY | RTR_QUERY_OPAQUE)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: unknown flag bits 0x%x", who, flags & ~(RTR_QUERY_ANY | RTR_QUERY_OPAQUE));
     if (s->ctx->device != c->device) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: the scene lives on device %d, the context on device %d", who, s->ctx->device, c->device);
@@ -1542,6 +1553,7 @@ static int enqueue_occlusion(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays,
     oa.rays = reinterpret_cast<const float4*>(rays); oa.occluded = occluded; oa.n = n; oa.batch = rtrdev::occlusion_batch(n);
     oa.ctrl = reinterpret_cast<uint32_t*>(base + l.ctrl); oa.overflow = reinterpret_cast<uint32_t*>(base + l.overflow); oa.overflowCap = overflowCap;
     oa.queue = reinterpret_cast<uint32_t*>(base + l.queue); oa.lists = reinterpret_cast<uint2*>(base + l.lists); oa.listStride = l.listStride;
+    oa.startLeaves = startLeaves; oa.numTris = (uint32_t)(s->tris.n / 3);          /* a hint is checked against the records the scene holds */
     const hipError_t e = rtrdev::launch_occlusion(s->dev, oa, c->tun, (flags & RTR_QUERY_OPAQUE) == 0u, c->qSpill.p, count ? c->qCounters.p : nullptr, st,
                                                   (uint32_t)c->prop.multiProcessorCount);
     if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: kernel launch: %s", who, hipGetErrorString(e));
@@ -1551,12 +1563,30 @@ static int enqueue_occlusion(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays,
 }
 
 int rtr_trace_occlusion_async(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, uint32_t n, uint32_t flags, void* scratch, size_t scratchBytes, uint8_t* occluded) {
-    return enqueue_occlusion(c, s, rays, n, flags, scratch, scratchBytes, occluded, false, "rtr_trace_occlusion_async");
+    return enqueue_occlusion(c, s, rays, nullptr, n, flags, scratch, scratchBytes, occluded, false, "rtr_trace_occlusion_async");
 }
+
+int rtr_trace_occlusion_hinted_async(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const int32_t* startLeaves, uint32_t n, uint32_t flags, void* scratch,
+                                     size_t scratchBytes, uint8_t* occluded) {
+    return enqueue_occlusion(c, s, rays, startLeaves, n, flags, scratch, scratchBytes, occluded, false, "rtr_trace_occlusion_hinted_async");
+}
+
+static int occlusion_sync(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const int32_t* startLeaves, uint32_t n, uint32_t flags, void* scratch,
+                          size_t scratchBytes, uint8_t* occluded, rtr_query_stats* stats, const char* who);
 
 int rtr_trace_occlusion(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, uint32_t n, uint32_t flags, void* scratch, size_t scratchBytes, uint8_t* occluded,
                         rtr_query_stats* stats) {
-    const int rc = enqueue_occlusion(c, s, rays, n, flags, scratch, scratchBytes, occluded, stats != nullptr, "rtr_trace_occlusion");
+    return occlusion_sync(c, s, rays, nullptr, n, flags, scratch, scratchBytes, occluded, stats, "rtr_trace_occlusion");
+}
+
+int rtr_trace_occlusion_hinted(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const int32_t* startLeaves, uint32_t n, uint32_t flags, void* scratch,
+                               size_t scratchBytes, uint8_t* occluded, rtr_query_stats* stats) {
+    return occlusion_sync(c, s, rays, startLeaves, n, flags, scratch, scratchBytes, occluded, stats, "rtr_trace_occlusion_hinted");
+}
+
+static int occlusion_sync(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const int32_t* startLeaves, uint32_t n, uint32_t flags, void* scratch,
+                          size_t scratchBytes, uint8_t* occluded, rtr_query_stats* stats, const char* who) {
+    const int rc = enqueue_occlusion(c, s, rays, startLeaves, n, flags, scratch, scratchBytes, occluded, stats != nullptr, who);
     if (rc != RTR_OK) return rc;
     if (stats) memset(stats, 0, sizeof *stats);
     if (n == 0) return RTR_OK;
@@ -1604,6 +1634,60 @@ int rtr_hit_surfaces(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const R
     return RTR_OK;
 }
 
+/* ---- start hints: the triangle -> leaf table (kernels/rtr_query.hip: k_leaf_table) ---- */
+/* Made by the first call that needs it, on the calling context's stream (the current device is the scene's), and JOINED before the call
+ * goes on: whichever context of the device asks next finds it complete, without an event to wait for.  rtr_scene_update_instances
+ * keeps it (a refit moves boxes and records, not the leaves they sit in). */
+static int ensure_leaf_table(rtr_ctx* c, const rtr_scene* s, const char* who) {
+    if (s->leafReady) return RTR_OK;
+    std::vector<uint32_t> base(s->hostTriCount.size() + 1, 0u);
+    uint64_t total = 0;
+    for (size_t i = 0; i < s->hostTriCount.size(); ++i) { base[i] = (uint32_t)total; total += s->hostTriCount[i]; }
+    if (total > 0xffffffffull) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: %llu (customIndex, primitiveId) pairs do not fit the leaf table's 32-bit index", who, (unsigned long long)total);
+    hipStream_t st = c->stream;
+    HIP_TRY(s->leafBase.upload(base.data(), base.size(), st));
+    HIP_TRY(s->leafTable.alloc((size_t)total));
+    HIP_TRY(hipMemsetAsync(s->leafTable.p, 0, s->leafTable.n * sizeof(int32_t), st));
+    const hipError_t e = rtrdev::launch_leaf_table(s->nodes.p, (uint32_t)(s->nodes.n / 2), s->tris.p, (uint32_t)(s->tris.n / 3), s->triCount.p, s->leafBase.p,
+                                                   s->numInstances, s->leafTable.p, st);
+    if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: leaf table: %s", who, hipGetErrorString(e));
+    HIP_TRY(hipStreamSynchronize(st));
+    s->leafReady = true;
+    return RTR_OK;
+}
+
+/* the checks and the launch of rtr_hit_leaves[_async].  The pointers are checked first: that needs nothing of the handles */
+static int enqueue_hit_leaves(rtr_ctx* c, const rtr_scene* s, const RtrHit* hits, uint32_t n, int32_t* leaves, const char* who) {
+    if (n) {
+        if (!hits || !leaves) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: %s is null", who, !hits ? "hits" : "leaves");
+        if (!aligned16(hits)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: hits is not 16-B aligned", who);
+        if (!aligned4(leaves)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: leaves is not 4-B aligned", who);
+    }
+    if (!c || !s) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: null context or scene", who);
+    if (s->ctx->device != c->device) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: the scene lives on device %d, the context on device %d", who, s->ctx->device, c->device);
+    if (n == 0) return RTR_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    const int rc = ensure_leaf_table(c, s, who);
+    if (rc != RTR_OK) return rc;
+    rtrdev::LeafArgs a{};
+    a.hits = reinterpret_cast<const float4*>(hits); a.leaves = leaves; a.triCount = s->triCount.p; a.base = s->leafBase.p; a.table = s->leafTable.p;
+    a.numInstances = s->numInstances; a.n = n;
+    const hipError_t e = rtrdev::launch_hit_leaves(a, c->stream);
+    if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: kernel launch: %s", who, hipGetErrorString(e));
+    return RTR_OK;
+}
+
+int rtr_hit_leaves_async(rtr_ctx* c, const rtr_scene* s, const RtrHit* hits, uint32_t n, int32_t* leaves) {
+    return enqueue_hit_leaves(c, s, hits, n, leaves, "rtr_hit_leaves_async");
+}
+
+int rtr_hit_leaves(rtr_ctx* c, const rtr_scene* s, const RtrHit* hits, uint32_t n, int32_t* leaves) {
+    const int rc = enqueue_hit_leaves(c, s, hits, n, leaves, "rtr_hit_leaves");
+    if (rc != RTR_OK || n == 0) return rc;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return RTR_OK;
+}
+
 int rtr_camera_rays_async(rtr_ctx* c, const RtrCameraData* cam, uint32_t width, uint32_t height, uint32_t spp, RtrRay* out) {
     if (!c || !cam || !out) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_camera_rays_async: null argument");
     if (!aligned16(out)) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_camera_rays_async: out is not 16-B aligned");
@@ -1616,7 +1700,6 @@ int rtr_camera_rays_async(rtr_ctx* c, const RtrCameraData* cam, uint32_t width, 
 }
 
 /* ---- direct lighting for ray-query hits -------------------------------------------------------------------------------------- */
-static bool aligned4(const void* p) { return ((uintptr_t)p & 3u) == 0; }
 
 /* Q of rtr_light_slots, from the host copy of the light table (as enqueue_render counts maxRaysPerSample) */
 static int light_slots(const rtr_scene* s, const rtr_light_params* p, uint32_t* q, const char* who) {
@@ -1638,7 +1721,12 @@ int rtr_light_slots(const rtr_scene* s, const rtr_light_params* p, uint32_t* slo
 
 /* the checks and the launch of rtr_light_rays[_async] (shade == false) and rtr_shade_hits[_async], enqueued on the context's stream */
 static int enqueue_light(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, uint32_t n, const rtr_light_params* p,
-                         const uint32_t* seeds, RtrRay* outRays, const uint8_t* occluded, RtrRadiance* out, bool shade, const char* who) {
+                         const uint32_t* seeds, RtrRay* outRays, const uint8_t* occluded, RtrRadiance* out, bool shade, const char* who,
+                         int32_t* outLeaves = nullptr, bool hinted = false) {
+    if (hinted && n) {       /* rtr_light_rays_hinted: its own array is checked first, which needs nothing of the handles */
+        if (!outLeaves) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: outLeaves is null", who);
+        if (!aligned4(outLeaves)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: outLeaves is not 4-B aligned", who);
+    }
     if (!c || !s || !p) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: null context, scene or params", who);
     if (s->ctx->device != c->device) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: the scene lives on device %d, the context on device %d", who, s->ctx->device, c->device);
     uint32_t slots = 0;
@@ -1656,7 +1744,9 @@ static int enqueue_light(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, con
     if (seeds && !aligned4(seeds)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: seeds is not 4-B aligned", who);
     if (!seeds && (p->width == 0 || p->spp == 0)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: width %u, spp %u: without seeds the hits are pixel-samples of a frame", who, p->width, p->spp);
     HIP_TRY(hipSetDevice(c->device));
+    if (hinted) { const int rct = ensure_leaf_table(c, s, who); if (rct != RTR_OK) return rct; }
     rtrdev::LightArgs la{};
+    if (hinted) { la.outLeaves = outLeaves; la.leafTable = s->leafTable.p; la.leafBase = s->leafBase.p; }
     la.rays = reinterpret_cast<const float4*>(rays); la.hits = reinterpret_cast<const float4*>(hits); la.seeds = seeds;
     la.triCount = s->triCount.p; la.numInstances = s->numInstances; la.n = n; la.slots = slots;
     la.numAreaLights = p->numAreaLights; la.numShadowRays = p->numShadowRays; la.frame = p->frame; la.width = p->width; la.spp = p->spp;
@@ -1678,6 +1768,19 @@ int rtr_light_rays_async(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, con
 int rtr_light_rays(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, uint32_t n, const rtr_light_params* p,
                    const uint32_t* seeds, RtrRay* outRays) {
     const int rc = enqueue_light(c, s, rays, hits, n, p, seeds, outRays, nullptr, nullptr, false, "rtr_light_rays");
+    if (rc != RTR_OK || n == 0) return rc;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return RTR_OK;
+}
+
+int rtr_light_rays_hinted_async(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, uint32_t n, const rtr_light_params* p,
+                                const uint32_t* seeds, RtrRay* outRays, int32_t* outLeaves) {
+    return enqueue_light(c, s, rays, hits, n, p, seeds, outRays, nullptr, nullptr, false, "rtr_light_rays_hinted_async", outLeaves, true);
+}
+
+int rtr_light_rays_hinted(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, uint32_t n, const rtr_light_params* p,
+                          const uint32_t* seeds, RtrRay* outRays, int32_t* outLeaves) {
+    const int rc = enqueue_light(c, s, rays, hits, n, p, seeds, outRays, nullptr, nullptr, false, "rtr_light_rays_hinted", outLeaves, true);
     if (rc != RTR_OK || n == 0) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
     return RTR_OK;

@@ -250,6 +250,19 @@ int  rtr_check_scene_limits(uint64_t numTriangles, uint64_t numNodes);
  * other threads or processes must itself keep those from enqueueing new frames of this scene until the call has returned. */
 int  rtr_scene_update_instances(rtr_scene* scene, const RtrInstance* instances, uint32_t numInstances,
                                 const RtrAreaLightInfo* lights, uint32_t numLights);
+/* Instance cull masks: VkAccelerationStructureInstanceKHR::mask (reference src/vulkan/raytracing/tlas.cppm:63, instance.setMask(0xFF): the
+ * only value the reference uses).  masks: a HOST array, one byte per instance, in instance order (rtr_scene_desc::instances); every new
+ * scene — one made by rtr_scene_create_like too — starts with 0xff everywhere.  Only the MASKED ray queries (rtr_trace_rays_masked,
+ * rtr_trace_occlusion_masked) look at the masks: rtr_render and every other entry point IGNORE them and give the bytes they gave before
+ * the call (tested).  The masks live in the triangle records (RtrBvhTri::flags bits 8..15, complemented: rtr_types.h), which a kernel
+ * rewrites; rtr_scene_export_bvh shows them, and a scene that never called the setter exports the records it always did.  They survive
+ * rtr_scene_update_instances.  The setter rewrites a device array that queries read, so it synchronises as the update calls do: it first
+ * JOINS THE WHOLE DEVICE (hipDeviceSynchronize: every query and frame in flight on any stream of this process finishes with the old
+ * masks), rewrites, and returns when the new state is complete; safe to call at any time from the thread that enqueues the work, and a
+ * caller that uses the scene from other threads or processes must itself keep those from enqueueing until the call has returned.
+ * RTR_ERR_INVALID_ARGUMENT for a null pointer or a numInstances that is not the scene's.  The getter returns what was set (0xff if never). */
+int  rtr_scene_set_instance_masks(rtr_scene* scene, const uint8_t* masks, uint32_t numInstances);
+int  rtr_scene_get_instance_masks(const rtr_scene* scene, uint8_t* masks, uint32_t numInstances);
 /* replaces the host-visible LightInfo buffer rewrite (src/app/application.cppm:264-271). */
 int  rtr_scene_update_lights(rtr_scene* scene, const RtrAreaLightInfo* lights, uint32_t numLights);
 
@@ -376,6 +389,22 @@ int  rtr_trace_rays_async(rtr_ctx* ctx, const rtr_scene* scene, const RtrRay* ra
 /* The same, then joins ctx's stream (only that stream).  stats (may be NULL): run the counting form of the kernels and fill it. */
 int  rtr_trace_rays(rtr_ctx* ctx, const rtr_scene* scene, const RtrRay* rays, uint32_t numRays, uint32_t flags,
                     RtrHit* hits, uint8_t* occluded, rtr_query_stats* stats);
+/* ---- cull masks: traceRayEXT's cullMask argument (reference src/shaders/raygen.rgen:102,234,306, always 0xFF there) ----
+ * Vulkan's rule: an instance's triangles exist for a ray iff (instanceMask & rayMask) != 0, with the instance masks of
+ * rtr_scene_set_instance_masks (default 0xff) and the ray's EFFECTIVE mask cullMask & (rayMasks ? rayMasks[k] : 0xff).  cullMask: 8 bits;
+ * higher bits are refused (RTR_ERR_INVALID_ARGUMENT, with a message).  rayMasks: a DEVICE pointer, one byte per ray, no alignment asked,
+ * or NULL: one launch can carry rays of different kinds (bounce rays that skip the emitters beside probe rays that see one layer), as one
+ * Vulkan dispatch does.  A ray whose effective mask is 0 is a miss (t = its tmax) / not occluded and costs no walk.  Everything else is
+ * the unmasked call's: the closest hit is the (t, customIndex, primitiveId)-minimal ACCEPTED hit, RTR_QUERY_ANY / RTR_QUERY_OPAQUE, the
+ * opacity-map test (not run on a masked-out record), tmin / tmax, degenerate rays, pointers, alignment, stream order, numRays == 0, a
+ * scene on another context of the same device.  stats: as rtr_trace_rays; numTriTests counts FETCHED records, so a masked-out record
+ * counts (a box whose triangles are all masked out is still entered: the mask is a filter in the leaves, not a culled subtree).  With
+ * default instance masks, cullMask 0xff and rayMasks NULL, results and every counter equal the unmasked call's.  The unmasked entry
+ * points launch the unmasked forms of the kernels, whose instructions are what they were. */
+int  rtr_trace_rays_masked_async(rtr_ctx* ctx, const rtr_scene* scene, const RtrRay* rays, const uint8_t* rayMasks, uint32_t numRays,
+                                 uint32_t flags, uint32_t cullMask, RtrHit* hits, uint8_t* occluded);
+int  rtr_trace_rays_masked(rtr_ctx* ctx, const rtr_scene* scene, const RtrRay* rays, const uint8_t* rayMasks, uint32_t numRays,
+                           uint32_t flags, uint32_t cullMask, RtrHit* hits, uint8_t* occluded, rtr_query_stats* stats);
 /* ---- queued occlusion queries ----
  * A second way to answer occlusion rays, with the renderer's own any-hit machinery: the rays are binned by direction octant into a
  * queue of ray indices, persistent waves walk the 4-wide tree and refill their finished lanes from it, and the few rays that need a
@@ -435,6 +464,16 @@ int  rtr_trace_occlusion_hinted_async(rtr_ctx* ctx, const rtr_scene* scene, cons
                                       uint32_t flags, void* scratch, size_t scratchBytes, uint8_t* occluded);
 int  rtr_trace_occlusion_hinted(rtr_ctx* ctx, const rtr_scene* scene, const RtrRay* rays, const int32_t* startLeaves, uint32_t numRays,
                                 uint32_t flags, void* scratch, size_t scratchBytes, uint8_t* occluded, rtr_query_stats* stats);
+/* The queued query with a cull mask (see "cull masks" above): rtr_trace_occlusion_hinted — startLeaves == NULL is the unhinted query —
+ * plus rayMasks (DEVICE pointer, one byte per ray, gathered at the refill beside the ray and its hint; or NULL) and cullMask (8 bits,
+ * higher bits refused).  occluded[] is byte for byte rtr_trace_rays_masked(RTR_QUERY_ANY)'s.  A ray whose effective mask is 0 is not
+ * queued: its byte is 0 and stats count it as a ray with an empty interval is counted.  A hinted leaf whose triangles are all masked out
+ * does not stop the ray.  Scratch, flags, pointers, alignment and stream order as rtr_trace_occlusion. */
+int  rtr_trace_occlusion_masked_async(rtr_ctx* ctx, const rtr_scene* scene, const RtrRay* rays, const int32_t* startLeaves, const uint8_t* rayMasks,
+                                      uint32_t numRays, uint32_t flags, uint32_t cullMask, void* scratch, size_t scratchBytes, uint8_t* occluded);
+int  rtr_trace_occlusion_masked(rtr_ctx* ctx, const rtr_scene* scene, const RtrRay* rays, const int32_t* startLeaves, const uint8_t* rayMasks,
+                                uint32_t numRays, uint32_t flags, uint32_t cullMask, void* scratch, size_t scratchBytes, uint8_t* occluded,
+                                rtr_query_stats* stats);
 /* Writes to the device array out[] the width * height * spp camera rays the renderer traces for `camera` (raygen.rgen:83-107:
  * jittered direction through the viewport, tmin 0.001, tmax 10000): ray k = (py * width + px) * spp + i.  ENQUEUED on ctx's stream.
  * Callers generate, edit and trace camera rays this way; traced with RTR_QUERY_CLOSEST they give the renderer's primary hits.

@@ -165,8 +165,14 @@ typedef struct RtrWideNode {
 typedef struct RtrBvhTri {
     float    v0[3]; uint32_t customIndex;
     float    e1[3]; uint32_t primitiveId;
-    float    e2[3]; uint32_t flags;      /* bit0: alpha-tested (any-hit needed) */
+    float    e2[3]; uint32_t flags;      /* bit0: alpha-tested (any-hit needed); bits 8..15: ~instance cull mask (below); others 0 */
 } RtrBvhTri;
+/* Bits 8..15 of RtrBvhTri::flags hold the COMPLEMENT of the 8-bit cull mask of the record's instance (rtr_scene_set_instance_masks;
+ * VkAccelerationStructureInstanceKHR::mask, reference src/vulkan/raytracing/tlas.cppm:63): the default mask 0xff is stored as 0, so the
+ * records of a scene whose masks were never set are what every builder has always written.  The record exists for a ray with the 8-bit
+ * mask m iff ((m << RTR_TRI_MASK_SHIFT) & ~flags) != 0.  Only the masked ray queries read the bits; the renderer reads bit 0 alone. */
+#define RTR_TRI_MASK_SHIFT 8u
+#define RTR_TRI_MASK_BITS  (0xffu << RTR_TRI_MASK_SHIFT)
 
 /* ---- ray queries (rtr_trace_rays): one caller-supplied ray and its closest hit ---------------------------------------------
  * What traceRayEXT takes (origin, tMin, direction, tMax: reference src/shaders/raygen.rgen:99-107) and what its hit shader reads

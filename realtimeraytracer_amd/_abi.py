@@ -178,6 +178,8 @@ RTR_SYMBOLS = {
     "rtr_host_build_bvh_wide": (C.c_int, [P(rtr_scene_desc), P(rtr_scene_stats), VP, C.c_size_t, VP, C.c_size_t, VP, C.c_size_t]),
     "rtr_scene_update_lights": (C.c_int, [VP, P(RtrAreaLightInfo), u32]),
     "rtr_scene_update_instances": (C.c_int, [VP, P(RtrInstance), u32, P(RtrAreaLightInfo), u32]),
+    "rtr_scene_set_instance_masks": (C.c_int, [VP, VP, u32]),
+    "rtr_scene_get_instance_masks": (C.c_int, [VP, VP, u32]),
     "rtr_frame_create": (C.c_int, [VP, u32, u32, u32, P(VP)]),
     "rtr_frame_destroy": (None, [VP]),
     "rtr_frame_bind_external": (C.c_int, [VP, C.c_int, VP, C.c_size_t]),
@@ -204,6 +206,10 @@ RTR_SYMBOLS = {
     "rtr_check_scene_limits": (C.c_int, [C.c_uint64, C.c_uint64]),
     "rtr_trace_rays_async": (C.c_int, [VP, VP, VP, u32, u32, VP, VP]),
     "rtr_trace_rays": (C.c_int, [VP, VP, VP, u32, u32, VP, VP, P(rtr_query_stats)]),
+    "rtr_trace_rays_masked_async": (C.c_int, [VP, VP, VP, VP, u32, u32, u32, VP, VP]),
+    "rtr_trace_rays_masked": (C.c_int, [VP, VP, VP, VP, u32, u32, u32, VP, VP, P(rtr_query_stats)]),
+    "rtr_trace_occlusion_masked_async": (C.c_int, [VP, VP, VP, VP, VP, u32, u32, u32, VP, C.c_size_t, VP]),
+    "rtr_trace_occlusion_masked": (C.c_int, [VP, VP, VP, VP, VP, u32, u32, u32, VP, C.c_size_t, VP, P(rtr_query_stats)]),
     "rtr_occlusion_scratch_bytes": (C.c_int, [u32, P(C.c_size_t)]),
     "rtr_trace_occlusion_async": (C.c_int, [VP, VP, VP, u32, u32, VP, C.c_size_t, VP]),
     "rtr_trace_occlusion": (C.c_int, [VP, VP, VP, u32, u32, VP, C.c_size_t, VP, P(rtr_query_stats)]),

@@ -74,6 +74,7 @@ class Scene:
         """like: a Scene made from the same description whose tree is uploaded instead of built again (rtr_scene_create_like)"""
         self.ctx, self.lib = ctx, ctx.lib
         self.h = A.VP()
+        self._num_instances = int(desc.numInstances)
         if like is None:
             _check(self.lib.rtr_scene_create(ctx.h, C.byref(desc), C.byref(self.h)), "rtr_scene_create")
         else:
@@ -106,6 +107,22 @@ class Scene:
         else:
             larr = (A.RtrAreaLightInfo * len(lights))(*lights)
             _check(self.lib.rtr_scene_update_instances(self.h, arr, len(instances), larr, len(lights)), "rtr_scene_update_instances")
+
+    def set_instance_masks(self, masks):
+        """rtr_scene_set_instance_masks: one 8-bit cull mask per instance, in instance order (array-like of uint8; default 0xff).  Only
+        the masked queries (trace_rays / trace_occlusion with cull_mask or ray_masks) look at them; renders ignore them."""
+        m = np.asarray(masks)
+        if m.ndim != 1 or m.dtype.kind not in "ui" or (m.size and (int(m.min()) < 0 or int(m.max()) > 0xff)):
+            raise ValueError(f"set_instance_masks: masks must be a 1-D array of values 0..255, got {m.dtype} {m.shape}")
+        m = np.ascontiguousarray(m, dtype=np.uint8)
+        _check(self.lib.rtr_scene_set_instance_masks(self.h, m.ctypes.data_as(A.VP) if m.size else None, int(m.size)), "rtr_scene_set_instance_masks")
+
+    def instance_masks(self):
+        """rtr_scene_get_instance_masks: the masks as a uint8 array, in instance order (0xff where never set)"""
+        n = self._num_instances
+        m = np.zeros(n, np.uint8)
+        _check(self.lib.rtr_scene_get_instance_masks(self.h, m.ctypes.data_as(A.VP) if n else None, n), "rtr_scene_get_instance_masks")
+        return m
 
     def update_lights(self, lights):
         arr = (A.RtrAreaLightInfo * len(lights))(*lights)
@@ -278,13 +295,35 @@ def _join_ctx_stream(ctx, torch, dev):
         torch.cuda.ExternalStream(cs, device=dev).synchronize()
 
 
-def trace_rays(scene, rays, any_hit=False, opaque=False, collect_stats=False, ctx=None, asynchronous=False):
+def _cull_mask_args(torch, who, cull_mask, ray_masks, n, dev):
+    """(ray-mask tensor or None, cull mask) of a masked query; cull_mask None -> 0xff.  ray_masks: a contiguous uint8 (N,) tensor on
+    dev, or a numpy array, which is uploaded."""
+    cm = 0xff if cull_mask is None else int(cull_mask)
+    rm = None
+    if ray_masks is not None:
+        if isinstance(ray_masks, np.ndarray):
+            if ray_masks.dtype != np.uint8 or ray_masks.shape != (n,):
+                raise ValueError(f"{who}: ray_masks must be uint8 ({n},), got {ray_masks.dtype} {ray_masks.shape}")
+            rm = torch.from_numpy(np.ascontiguousarray(ray_masks)).to(dev)
+        elif isinstance(ray_masks, torch.Tensor):
+            if ray_masks.dtype != torch.uint8 or tuple(ray_masks.shape) != (n,) or ray_masks.device != dev or not ray_masks.is_contiguous():
+                raise ValueError(f"{who}: ray_masks must be a contiguous uint8 ({n},) tensor on {dev}")
+            rm = ray_masks
+        else:
+            raise ValueError(f"{who}: ray_masks must be a torch tensor or a numpy array, got {type(ray_masks).__name__}")
+    return rm, cm
+
+
+def trace_rays(scene, rays, any_hit=False, opaque=False, collect_stats=False, ctx=None, asynchronous=False, cull_mask=None, ray_masks=None):
     """rtr_trace_rays: rays is a contiguous float32 (N, 8) tensor on the context's device — rows are RtrRay (origin, tmin, direction,
     tmax) — whose results come back as device tensors without a copy, or a numpy array, which is copied to the device and whose results
     come back as numpy.  any_hit: occlusion only (RTR_QUERY_ANY); opaque: no opacity-map test (RTR_QUERY_OPAQUE).  ctx: the context whose
     stream carries the work (default: the scene's).  asynchronous: enqueue and return (rtr_trace_rays_async); the context must then be
     on torch's current stream (ctx.set_stream), so that the results are ordered for torch without a join.  collect_stats: the counting
-    form, synchronous.  Wrong shape, dtype, device or layout raises ValueError before anything is launched."""
+    form, synchronous.  Wrong shape, dtype, device or layout raises ValueError before anything is launched.
+    cull_mask (8 bits) and ray_masks (one uint8 per ray: a device tensor, or a numpy array that is uploaded): traceRayEXT's cullMask —
+    ray k sees the instances whose mask (Scene.set_instance_masks) meets cull_mask & ray_masks[k]; with either given the call is
+    rtr_trace_rays_masked, with both None it is rtr_trace_rays exactly as before."""
     torch = _torch()
     ctx = ctx or scene.ctx
     dev = torch.device("cuda", ctx.device)
@@ -320,7 +359,17 @@ def trace_rays(scene, rays, any_hit=False, opaque=False, collect_stats=False, ct
     op = A.VP(occ.data_ptr()) if occ is not None and n else None
     rp = A.VP(r.data_ptr()) if n else None
     out = QueryResult()
-    if asynchronous:
+    rm = None
+    if cull_mask is not None or ray_masks is not None:
+        rm, cm = _cull_mask_args(torch, "trace_rays", cull_mask, ray_masks, n, dev)
+        mp = A.VP(rm.data_ptr()) if rm is not None and n else None
+        if asynchronous:
+            _check(ctx.lib.rtr_trace_rays_masked_async(ctx.h, scene.h, rp, mp, n, flags, cm, hp, op), "rtr_trace_rays_masked_async")
+        else:
+            st = A.rtr_query_stats() if collect_stats else None
+            _check(ctx.lib.rtr_trace_rays_masked(ctx.h, scene.h, rp, mp, n, flags, cm, hp, op, C.byref(st) if st is not None else None), "rtr_trace_rays_masked")
+            out.stats = st
+    elif asynchronous:
         _check(ctx.lib.rtr_trace_rays_async(ctx.h, scene.h, rp, n, flags, hp, op), "rtr_trace_rays_async")
     else:
         st = A.rtr_query_stats() if collect_stats else None
@@ -338,7 +387,7 @@ def trace_rays(scene, rays, any_hit=False, opaque=False, collect_stats=False, ct
             x = getattr(out, k)
             if x is not None:
                 setattr(out, k, x.cpu().numpy())
-    out._keep = (r, hits, occ)           # an asynchronous query's buffers stay alive with its result
+    out._keep = (r, hits, occ, rm)       # an asynchronous query's buffers stay alive with its result
     return out
 
 
@@ -349,13 +398,15 @@ def occlusion_scratch_bytes(lib, n):
     return int(b.value)
 
 
-def trace_occlusion(scene, rays, opaque=False, collect_stats=False, ctx=None, asynchronous=False, start_leaves=None):
+def trace_occlusion(scene, rays, opaque=False, collect_stats=False, ctx=None, asynchronous=False, start_leaves=None, cull_mask=None, ray_masks=None):
     """rtr_trace_occlusion: the queued occlusion query — the same bytes as trace_rays(any_hit=True), answered by the renderer's any-hit
     machinery (rays binned by direction octant, persistent waves over the 4-wide tree).  rays, opaque, ctx, asynchronous, collect_stats
     and the QueryResult (occluded, stats) as in trace_rays.  The query's scratch is a uint8 device tensor kept on the context and grown
     when a longer ray array comes; queries on one context are ordered on its stream, so they share it.
     start_leaves (rtr_trace_occlusion_hinted): one int32 start hint per ray — light_rays(hints=True)'s or hit_leaves' — as an (N,) int32
-    device tensor or numpy array like the rays; any value is safe and none changes a byte, only the work.  None: the unhinted query."""
+    device tensor or numpy array like the rays; any value is safe and none changes a byte, only the work.  None: the unhinted query.
+    cull_mask, ray_masks: as in trace_rays; with either given the call is rtr_trace_occlusion_masked (hinted or not), with both None the
+    entry points called before."""
     torch = _torch()
     ctx = ctx or scene.ctx
     dev = torch.device("cuda", ctx.device)
@@ -402,7 +453,19 @@ def trace_occlusion(scene, rays, opaque=False, collect_stats=False, ctx=None, as
     args = (n, flags, A.VP(scratch.data_ptr()), scratch.numel(), A.VP(occ.data_ptr())) if n else (0, flags, None, 0, None)
     rp = A.VP(r.data_ptr()) if n else None
     out = QueryResult()
-    if sl is not None:
+    rm = None
+    if cull_mask is not None or ray_masks is not None:
+        rm, cm = _cull_mask_args(torch, "trace_occlusion", cull_mask, ray_masks, n, dev)
+        hp = A.VP(sl.data_ptr()) if sl is not None and n else None
+        mp = A.VP(rm.data_ptr()) if rm is not None and n else None
+        margs = (n, flags, cm) + args[2:]
+        if asynchronous:
+            _check(ctx.lib.rtr_trace_occlusion_masked_async(ctx.h, scene.h, rp, hp, mp, *margs), "rtr_trace_occlusion_masked_async")
+        else:
+            st = A.rtr_query_stats() if collect_stats else None
+            _check(ctx.lib.rtr_trace_occlusion_masked(ctx.h, scene.h, rp, hp, mp, *margs, C.byref(st) if st is not None else None), "rtr_trace_occlusion_masked")
+            out.stats = st
+    elif sl is not None:
         hp = A.VP(sl.data_ptr()) if n else None
         if asynchronous:
             _check(ctx.lib.rtr_trace_occlusion_hinted_async(ctx.h, scene.h, rp, hp, *args), "rtr_trace_occlusion_hinted_async")
@@ -417,7 +480,7 @@ def trace_occlusion(scene, rays, opaque=False, collect_stats=False, ctx=None, as
         _check(ctx.lib.rtr_trace_occlusion(ctx.h, scene.h, rp, *args, C.byref(st) if st is not None else None), "rtr_trace_occlusion")
         out.stats = st
     out.occluded = occ.cpu().numpy() if as_numpy else occ
-    out._keep = (r, sl, occ, scratch)    # an asynchronous query's buffers stay alive with its result
+    out._keep = (r, sl, occ, scratch, rm)    # an asynchronous query's buffers stay alive with its result
     return out
 
 
@@ -683,12 +746,13 @@ def tonemap_pack(ctx, radiance, asynchronous=False):
     return out
 
 
-def direct_light(scene, rays, hits=None, params=None, seeds=None, ctx=None, max_ray_bytes=256 << 20, occlusion="dense"):
+def direct_light(scene, rays, hits=None, params=None, seeds=None, ctx=None, max_ray_bytes=256 << 20, occlusion="dense", shadow_cull_mask=None):
     """The composed stage: closest hit (when hits is None) -> light_rays -> trace_rays(any_hit=True) -> shade_hits, in chunks of hits
     so that a chunk's light rays (n * Q * 32 bytes) stay within max_ray_bytes — a 1080p frame at Q = 7 would be 464 MB of rays at once.
     Chunks do not change the result.  occlusion: "dense" (trace_rays, the default), "queued" (trace_occlusion) or "queued_own_leaf"
     (light_rays(hints=True) and trace_occlusion(start_leaves=...): the renderer's own walk, own-leaf rule included): the same bytes.  rays: a float32 (N, 8) device tensor; hits: a QueryResult, (N, 8) int32 records, or None;
-    params: make_light_params(...).  Returns a RadianceResult on the device."""
+    params: make_light_params(...).  shadow_cull_mask: the cull mask of the shadow rays (instances whose mask does not meet it cast no
+    shadow), passed to whichever occlusion route is selected; None: the unmasked calls, as before.  Returns a RadianceResult on the device."""
     if occlusion not in ("dense", "queued", "queued_own_leaf"):
         raise ValueError(f"direct_light: occlusion must be 'dense', 'queued' or 'queued_own_leaf', got {occlusion!r}")
     if params is None:
@@ -713,9 +777,10 @@ def direct_light(scene, rays, hits=None, params=None, seeds=None, ctx=None, max_
         r, h = rays[a:b], hits[a:b]
         if occlusion == "queued_own_leaf":
             lr, leaves = light_rays(scene, r, h, params, seeds=sd, ctx=ctx, hints=True)
-            occ = trace_occlusion(scene, lr, ctx=ctx, start_leaves=leaves).occluded
+            occ = trace_occlusion(scene, lr, ctx=ctx, start_leaves=leaves, cull_mask=shadow_cull_mask).occluded
         else:
             lr = light_rays(scene, r, h, params, seeds=sd, ctx=ctx)
-            occ = (trace_occlusion(scene, lr, ctx=ctx) if occlusion == "queued" else trace_rays(scene, lr, any_hit=True, ctx=ctx)).occluded
+            occ = (trace_occlusion(scene, lr, ctx=ctx, cull_mask=shadow_cull_mask) if occlusion == "queued"
+                   else trace_rays(scene, lr, any_hit=True, ctx=ctx, cull_mask=shadow_cull_mask)).occluded
         out[a:b] = shade_hits(scene, r, h, params, occ, seeds=sd, ctx=ctx).raw
     return _radiance_result(out, False, torch)

@@ -243,10 +243,15 @@ __device__ __forceinline__ uint32_t ray_octant(const DeviceScene& sc, rtr_v3 o, 
  * FLAT_TAKE: the closest-hit rule written without short-circuit branches.  In the ray-query kernels the branchy form was miscompiled on
  * exact ties in t: a candidate that won on (customIndex, primitiveId) got its t, u, v stored but the ids of the hit it replaced stayed
  * (the compiler merged the two ids into one 64-bit value and carried the old pair along the tie path).  The renderer's kernels are
- * compiled correctly with the branchy form and keep it. */
-template <bool ANY, bool STATS, int BLOCK, int LIMIT = 0, int OCT = 8, bool ALPHA = true, bool FLAT_TAKE = false>
+ * compiled correctly with the branchy form and keep it.
+ * MASKED (the ray queries' cull mask, traceRayEXT's cullMask): rayMask8 is the ray's 8-bit mask in bits 8..15, where a record's flags
+ * word holds the COMPLEMENT of its instance's mask (kTriMaskShift): a fetched record none of whose mask bits meets the ray's is skipped
+ * before the intersection test — one and-not on a word the lane already holds.  It was fetched, so it is counted.  The forms without
+ * MASKED compile to what they were. */
+constexpr uint32_t kTriMaskShift = RTR_TRI_MASK_SHIFT, kTriMaskBits = RTR_TRI_MASK_BITS;
+template <bool ANY, bool STATS, int BLOCK, int LIMIT = 0, int OCT = 8, bool ALPHA = true, bool FLAT_TAKE = false, bool MASKED = false>
 __device__ __forceinline__ bool trace(const DeviceScene& sc, int32_t* __restrict__ stack,
-                                      rtr_v3 o, rtr_v3 d, float tmin, float tmax, HitRec& best, LocalStats& st) {
+                                      rtr_v3 o, rtr_v3 d, float tmin, float tmax, HitRec& best, LocalStats& st, const uint32_t rayMask8 = 0u) {
     if (STATS) { st.rays++; if (ANY) st.shadow++; else st.primary++; }
     best.custom = RTR_MISS; best.prim = RTR_MISS; best.t = tmax; best.u = 0.f; best.v = 0.f; best.leaf = 0;
     if (!(tmax > tmin)) return false;
@@ -302,6 +307,7 @@ __device__ __forceinline__ bool trace(const DeviceScene& sc, int32_t* __restrict
                 const float4 q1 = make_float4(__uint_as_float(r1.x), __uint_as_float(r1.y), __uint_as_float(r1.z), __uint_as_float(r1.w));
                 const float4 q2 = make_float4(__uint_as_float(r2.x), __uint_as_float(r2.y), __uint_as_float(r2.z), __uint_as_float(r2.w));
                 if (STATS) { st.tris++; if (ANY) st.shadowTris++; }
+                if (MASKED && (rayMask8 & ~r2.w) == 0u) continue;      /* the instance does not exist for this ray */
                 float t, u, v;
                 if (rtr_mt_intersect(o, d, f4xyz(q0), f4xyz(q1), f4xyz(q2), tmin, &t, &u, &v)) {
                     if (t < tmax) {

@@ -45,6 +45,9 @@ constexpr size_t kSpillInts = (size_t)64 * 64 * 256;     /* full-depth stacks of
  * visibility byte; that index also names the pixel-sample (slot & slotMask: the planes of the visibility array are slotStride =
  * a power of two apart).  32-B records with the origin in every ray made the queue 0.79 GB per 1080p frame, written by a kernel that
  * is bound by exactly those writes. */
+/* k_shadow_trace4's CALLER forms (launch_occlusion_walk) read these fields differently — dt: the caller's rays, slot: ray indices, origin /
+ * slotMask: the start hints and the scene's record count (HINTS), slotStride: the call's cull mask (MASKED) — so that the renderer's own
+ * instantiations keep their parameter list.  Whoever gives a field a new use in the kernel checks those forms (static_asserts there). */
 struct RayQueue {
     float4*   dt = nullptr;          /* per ray: direction xyz, tmax */
     uint32_t* slot = nullptr;        /* per ray: visibility index = query * slotStride + pixel-sample */
@@ -134,7 +137,17 @@ struct OcclusionArgs {
     const int32_t* startLeaves;
     uint32_t numTris;
 };
-hipError_t launch_occlusion_walk(const DeviceScene& sc, const OcclusionArgs& oa, const Tunables& tun, bool alpha, Counters* stats, hipStream_t stream, uint32_t numCus);
+/* The cull mask of a masked ray query (rtr_trace_rays_masked, rtr_trace_occlusion_masked): ray k's effective mask is
+ * cullMask & (rayMasks ? rayMasks[k] : 0xff).  masked != 0 selects the MASKED forms of the kernels, which take this struct as their LAST
+ * argument — behind everything the unmasked forms read, whose argument structs and instructions are therefore what they were (their
+ * kernel-argument segment is 16 B longer). */
+struct RayMaskArgs {
+    const uint8_t* rayMasks = nullptr;     /* one byte per ray, or null */
+    uint32_t cullMask = 0xffu;             /* 8 bits */
+    uint32_t masked = 0;
+};
+hipError_t launch_occlusion_walk(const DeviceScene& sc, const OcclusionArgs& oa, const Tunables& tun, bool alpha, Counters* stats, hipStream_t stream, uint32_t numCus,
+                                 const RayMaskArgs& rm = RayMaskArgs());
 
 /* fills DeviceScene::lightTris (4 x float4 per light triangle, light l from first[l]); after create and after light transforms change */
 hipError_t launch_light_tris(const RtrAreaLightInfo* lights, const RtrVertex* vertices, const uint32_t* indices, const uint32_t* first,

@@ -841,10 +841,11 @@ __global__ __launch_bounds__(kBlock) void k_shadow_trace(DeviceScene sc, const R
 /* The inner-node loop of k_shadow_trace4, compiled per direction octant (OCT 0..7; 8 = any signs, see slab_oct). */
 /* One any-hit triangle test of the persistent 4-wide kernel: 48-B record through the buffer resource, Moeller-Trumbore, t < tmax,
  * and opacity.rahit on alpha-tested geometry.  MAY_SKIP_ALPHA (the caller-ray form only): `opaque` — wave-uniform, RTR_QUERY_OPAQUE —
- * accepts every candidate without that test. */
-template <bool STATS, bool MAY_SKIP_ALPHA = false>
+ * accepts every candidate without that test.  MASKED (the caller-ray form with a cull mask): rayMask8 as in trace() — a record whose
+ * instance's mask does not meet the ray's is no candidate. */
+template <bool STATS, bool MAY_SKIP_ALPHA = false, bool MASKED = false>
 __device__ __forceinline__ bool tri_any(const DeviceScene& sc, const __amdgpu_buffer_rsrc_t triBuf, const uint32_t tri, const rtr_v3 o, const rtr_v3 d,
-                                        const float tmin, const float tmax, LocalStats& st, const bool opaque = false) {
+                                        const float tmin, const float tmax, LocalStats& st, const bool opaque = false, const uint32_t rayMask8 = 0u) {
     typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
     const int32_t triOff = (int32_t)(tri * 48u);
     const u32x4 r0 = __builtin_amdgcn_raw_buffer_load_b128(triBuf, triOff, 0, RTR_TRI_AUX);
@@ -853,6 +854,7 @@ __device__ __forceinline__ bool tri_any(const DeviceScene& sc, const __amdgpu_bu
     const float4 q0 = make_float4(__uint_as_float(r0.x), __uint_as_float(r0.y), __uint_as_float(r0.z), __uint_as_float(r0.w));
     const float4 q1 = make_float4(__uint_as_float(r1.x), __uint_as_float(r1.y), __uint_as_float(r1.z), __uint_as_float(r1.w));
     const float4 q2 = make_float4(__uint_as_float(r2.x), __uint_as_float(r2.y), __uint_as_float(r2.z), __uint_as_float(r2.w));
+    if (MASKED && (rayMask8 & ~r2.w) == 0u) return false;      /* the instance does not exist for this ray */
     float t, u, v;
     if (!(rtr_mt_intersect(o, d, f4xyz(q0), f4xyz(q1), f4xyz(q2), tmin, &t, &u, &v) && t < tmax)) return false;
     if ((__float_as_uint(q2.w) & 1u) && !(MAY_SKIP_ALPHA && opaque)) return alpha_pass<STATS>(sc, __float_as_uint(q0.w), __float_as_uint(q1.w), u, v, st);
@@ -979,14 +981,23 @@ __device__ __forceinline__ void inner_nodes4(const __amdgpu_buffer_rsrc_t nodeBu
  * the scene's triangle records), the code of the leaf the walk starts at — the renderer's own-leaf rule for rays that are not its own.
  * The refill loads it beside the ray and takes it as (into, ownLeaf) when it is a leaf code whose triangles all lie inside the record
  * array; anything else (0, a positive value, kDone, a code past the records) starts at the root.  An any-hit answer does not depend on
- * where the walk starts, so a hint changes the work, never a byte.  The forms without HINTS compile to what they were. */
-template <int STACK, bool LISTS, bool STATS, bool CALLER = false, bool HINTS = false>
+ * where the walk starts, so a hint changes the work, never a byte.  The forms without HINTS compile to what they were.
+ * MASKED (CALLER only; rtr_trace_occlusion_masked): every ray has an 8-bit cull mask — queue.slotStride: the call's cullMask; count, which
+ * the LISTS forms do not read: one byte per ray, or null — gathered at the refill beside the ray and its hint and kept in bits 8..15 of one
+ * register; tri_any skips the records of instances whose mask does not meet it, in the leaf phase of a walk from the root and of an own-leaf
+ * start alike (a hinted leaf whose triangles are all masked out does not stop the ray).  Rays whose mask is 0 never reach the queue
+ * (k_occlusion_gen).  The forms without MASKED, the renderer's among them, compile to what they were. */
+template <int STACK, bool LISTS, bool STATS, bool CALLER = false, bool HINTS = false, bool MASKED = false>
 __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_shadow_trace4(DeviceScene sc, const RayQueue queue,
                                                               const uint32_t* __restrict__ count, uint32_t* nextBatch,
                                                               uint8_t* __restrict__ vis, uint32_t visFill, uint32_t kBatch, uint32_t kRefill,
                                                               uint32_t kInnerMin, uint32_t* overflow, uint32_t overflowCap, uint32_t octForms, uint32_t topCount,
                                                               const uint2* __restrict__ lists, uint32_t listStride, Counters* stats,
                                                               unsigned long long* __restrict__ clk) {
+    /* MASKED reads its two values through parameters the CALLER + LISTS forms leave unread (count, queue.slotStride: launch_occlusion_walk),
+     * so that the parameter list — and with it the kernel-argument segment and the code of the renderer's own instantiations — stays what it was */
+    static_assert(!MASKED || (CALLER && LISTS), "the cull mask travels in `count` and queue.slotStride, which only the CALLER forms over the batch lists leave unread");
+    static_assert(!HINTS || CALLER, "start hints travel in queue.origin and queue.slotMask, which only the CALLER forms leave unread");
     __shared__ int32_t s_stack[(STACK + 1) * kTraceBlock];    /* slot 0, below the stack, holds kDone for good */
     __shared__ uint4 s_top[kTopNodes * 4];                    /* the first topCount (<= kTopNodes) four-wide entries */
 #if RTR_REFILL_LDS
@@ -1051,6 +1062,7 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(8, 
     float tmax = 0.f;
     uint32_t slot = 0, rayIndex = 0, res = kResNone, occ = 0;
     float tmin = 0.001f;                     /* the renderer's rays all start there; a caller's ray brings its own (CALLER) */
+    uint32_t rayMask8 = 0;                   /* MASKED: the ray's cull mask, where the records keep theirs (tri_any) */
     /* nodes and triangles through buffer resources: the address of a visit is one 32-bit shift, not 64-bit lane arithmetic
      * (2.28 -> 2.17 ms, and 62 -> 47 VGPRs) */
     const __amdgpu_buffer_rsrc_t nodeBuf = __builtin_amdgcn_make_buffer_rsrc((void*)sc.nodes4, 0, 0xffffffff, 0x00020000);
@@ -1155,6 +1167,12 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(8, 
                                 const uint32_t code = (uint32_t)~ownLeaf;
                                 into = ownLeaf < 0 && (code >> 3) + (code & 7u) + 1u <= numTris;
                             }
+                            if (MASKED) {      /* cullMask & the ray's own byte, if the call brought any (wave-uniform branch) */
+                                const uint8_t* __restrict__ qmask = reinterpret_cast<const uint8_t*>(count);
+                                uint32_t m = queue.slotStride;
+                                if (qmask) m &= (uint32_t)qmask[slot];
+                                rayMask8 = m << kTriMaskShift;
+                            }
                         } else
 #if RTR_REFILL_LDS
                         {   /* queue_load() through the addresses kept in LDS */
@@ -1243,7 +1261,7 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(8, 
 #if !RTR_STATS_LEAF_PHASE
                 ws.triIters++; ws.triLanes += (uint32_t)__popcll(m);
 #endif
-                if (go) { st.tris++; st.shadowTris++; hit = tri_any<true, CALLER>(sc, triBuf, first + i, o, d, tmin, tmax, st, (octForms & 4u) != 0u); }
+                if (go) { st.tris++; st.shadowTris++; hit = tri_any<true, CALLER, MASKED>(sc, triBuf, first + i, o, d, tmin, tmax, st, (octForms & 4u) != 0u, rayMask8); }
             }
             if (atLeaf) {
                 if (hit) { res = 1u; cur = kDone; }
@@ -1253,7 +1271,7 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(8, 
             const uint32_t code = (uint32_t)~cur;
             const uint32_t first = code >> 3, cnt = (code & 7u) + 1u;
             bool hit = false;
-            for (uint32_t i = 0; i < cnt && !hit; ++i) hit = tri_any<false, CALLER>(sc, triBuf, first + i, o, d, tmin, tmax, st, (octForms & 4u) != 0u);
+            for (uint32_t i = 0; i < cnt && !hit; ++i) hit = tri_any<false, CALLER, MASKED>(sc, triBuf, first + i, o, d, tmin, tmax, st, (octForms & 4u) != 0u, rayMask8);
             if (hit) { res = 1u; cur = kDone; }
             else { cur = *sp; sp -= kTraceBlock; }                        /* slot 0 holds kDone: an empty stack ends the ray (visible) */
         }
@@ -2057,7 +2075,8 @@ hipError_t launch_wavefront(const DeviceScene& sc, const FrameBatch& fb, const W
 /* The any-hit walk over a caller's rays (rtr_trace_occlusion): k_shadow_trace4 in its CALLER form over the index queue and batch lists
  * k_occlusion_gen built.  Launch shape and tunables are the renderer's: persistent workgroups by the length of the queue, the context's
  * refill / inner-loop thresholds, octant forms, top of the tree in LDS. */
-hipError_t launch_occlusion_walk(const DeviceScene& sc, const OcclusionArgs& oa, const Tunables& tun, bool alpha, Counters* stats, hipStream_t s, uint32_t numCus) {
+hipError_t launch_occlusion_walk(const DeviceScene& sc, const OcclusionArgs& oa, const Tunables& tun, bool alpha, Counters* stats, hipStream_t s, uint32_t numCus,
+                                 const RayMaskArgs& rm) {
     if (numCus == 0) numCus = 256;
     if (!sc.nodes4) return hipErrorInvalidValue;
     RayQueue rq;
@@ -2072,10 +2091,18 @@ hipError_t launch_occlusion_walk(const DeviceScene& sc, const OcclusionArgs& oa,
     const uint32_t kTop = tun.trace_top_nodes < kTopNodes ? tun.trace_top_nodes : kTopNodes;
     const uint32_t top = kTop < sc.numNodes4 ? kTop : sc.numNodes4;
     uint32_t* const ctrl = oa.ctrl;
-#define RTR_OCC_WALK(STATS, HINTS) hipLaunchKernelGGL((k_shadow_trace4<RTR_SHADOW_STACK, true, STATS, true, HINTS>), dim3(tblocks), dim3(kTraceBlock), 0, s, sc, rq, ctrl, ctrl + kBatchCursorWord, \
+    /* the MASKED form's reading of two values the CALLER forms do not use: the queue's slot stride is the call's cull mask, and `count`
+     * (the plain queue's length; these forms walk the lists) the per-ray mask bytes, or null */
+    const bool masked = rm.masked != 0u;
+    if (masked) rq.slotStride = rm.cullMask & 0xffu;
+    const uint32_t* const cnt = masked ? reinterpret_cast<const uint32_t*>(rm.rayMasks) : ctrl;
+#define RTR_OCC_WALK(STATS, HINTS, MASKED) hipLaunchKernelGGL((k_shadow_trace4<RTR_SHADOW_STACK, true, STATS, true, HINTS, MASKED>), dim3(tblocks), dim3(kTraceBlock), 0, s, sc, rq, cnt, ctrl + kBatchCursorWord, \
         oa.occluded, 0u, oa.batch, tun.trace_refill, tun.trace_inner_min, oa.overflow, oa.overflowCap, kOct, top, oa.lists, oa.listStride, stats, (unsigned long long*)nullptr)
-    if (hinted) { if (stats) RTR_OCC_WALK(true, true); else RTR_OCC_WALK(false, true); }
-    else { if (stats) RTR_OCC_WALK(true, false); else RTR_OCC_WALK(false, false); }
+    if (masked) {
+        if (hinted) { if (stats) RTR_OCC_WALK(true, true, true); else RTR_OCC_WALK(false, true, true); }
+        else { if (stats) RTR_OCC_WALK(true, false, true); else RTR_OCC_WALK(false, false, true); }
+    } else if (hinted) { if (stats) RTR_OCC_WALK(true, true, false); else RTR_OCC_WALK(false, true, false); }
+    else { if (stats) RTR_OCC_WALK(true, false, false); else RTR_OCC_WALK(false, false, false); }
 #undef RTR_OCC_WALK
     return hipGetLastError();
 }

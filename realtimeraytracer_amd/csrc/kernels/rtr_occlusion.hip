@@ -34,9 +34,11 @@ __device__ __forceinline__ uint32_t occlusion_code(const float4* __restrict__ ra
 }
 
 /* STATS: the well-formed rays that are not queued (an empty interval) are counted here; the walk counts the ones it takes, so the
- * query's numRays is what the renderer's counters call shadow rays — every ray that was sent, null slots excluded. */
-template <bool STATS>
-__global__ __launch_bounds__(kOccGenBlock) void k_occlusion_gen(OcclusionArgs oa, Counters* stats) {
+ * query's numRays is what the renderer's counters call shadow rays — every ray that was sent, null slots excluded.
+ * MASKED (rtr_trace_occlusion_masked): a ray whose effective cull mask — rm.cullMask & its byte of rm.rayMasks — is 0 sees no instance:
+ * it is "not occluded" now, is not queued, and is counted as a ray with an empty interval is. */
+template <bool STATS, bool MASKED = false>
+__global__ __launch_bounds__(kOccGenBlock) void k_occlusion_gen(OcclusionArgs oa, Counters* stats, RayMaskArgs rm) {
     constexpr uint32_t kWaves = kOccGenBlock / 64;
     __shared__ uint32_t s_tot[kWaves][8], s_run[kWaves][8];
     const uint32_t wave = threadIdx.x >> 6;
@@ -50,6 +52,7 @@ __global__ __launch_bounds__(kOccGenBlock) void k_occlusion_gen(OcclusionArgs oa
         if (k < oa.n) {
             bool wellFormed;
             code = occlusion_code(oa.rays, k, wellFormed);
+            if (MASKED && (rm.cullMask & (rm.rayMasks ? (uint32_t)rm.rayMasks[k] : 0xffu)) == 0u) code = kOccNoWalk;
             if (STATS && wellFormed && code == kOccNoWalk) ++unqueued;
         }
         codes |= code << (4u * j);
@@ -125,17 +128,20 @@ __global__ __launch_bounds__(kOccGenBlock) void k_occlusion_gen(OcclusionArgs oa
 }
 
 hipError_t launch_occlusion(const DeviceScene& sc, const OcclusionArgs& oa, const Tunables& tun, bool alpha, int32_t* spill, Counters* stats,
-                            hipStream_t s, uint32_t numCus) {
+                            hipStream_t s, uint32_t numCus, const RayMaskArgs& rm) {
     const uint32_t genBlocks = (uint32_t)(((uint64_t)oa.n + kOcclusionGenRays - 1) / kOcclusionGenRays);
-    if (stats) hipLaunchKernelGGL(k_occlusion_gen<true>, dim3(genBlocks), dim3(kOccGenBlock), 0, s, oa, stats);
-    else hipLaunchKernelGGL(k_occlusion_gen<false>, dim3(genBlocks), dim3(kOccGenBlock), 0, s, oa, stats);
-    hipError_t e = launch_occlusion_walk(sc, oa, tun, alpha, stats, s, numCus);
+    if (rm.masked) {
+        if (stats) hipLaunchKernelGGL((k_occlusion_gen<true, true>), dim3(genBlocks), dim3(kOccGenBlock), 0, s, oa, stats, rm);
+        else hipLaunchKernelGGL((k_occlusion_gen<false, true>), dim3(genBlocks), dim3(kOccGenBlock), 0, s, oa, stats, rm);
+    } else if (stats) hipLaunchKernelGGL(k_occlusion_gen<true>, dim3(genBlocks), dim3(kOccGenBlock), 0, s, oa, stats, rm);
+    else hipLaunchKernelGGL(k_occlusion_gen<false>, dim3(genBlocks), dim3(kOccGenBlock), 0, s, oa, stats, rm);
+    hipError_t e = launch_occlusion_walk(sc, oa, tun, alpha, stats, s, numCus, rm);
     if (e != hipSuccess) return e;
     QueryArgs qa{};
     qa.rays = oa.rays; qa.occluded = oa.occluded; qa.n = oa.n;
     qa.redoCap = oa.overflowCap; qa.ctrl = oa.overflow; qa.redoList = oa.overflow + 1; qa.spill = spill;
     static_assert(kQueryRedoWord == 0, "the walk's overflow count is the tail's redo count");
-    return launch_query_tail_any(sc, qa, alpha, stats, s);
+    return launch_query_tail_any(sc, qa, alpha, stats, s, rm);
 }
 
 }  // namespace rtrdev

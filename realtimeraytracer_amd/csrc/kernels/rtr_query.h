@@ -69,18 +69,23 @@ struct LeafArgs {
 /* fills the table (zeroed by the caller) from the BVH2: nodes as 2 x uint4 apiece, tris as 3 x float4 apiece */
 hipError_t launch_leaf_table(const uint4* nodes, uint32_t numNodes, const float4* tris, uint32_t numTris, const uint32_t* triCount,
                              const uint32_t* base, uint32_t numInstances, int32_t* table, hipStream_t stream);
+/* rtr_scene_set_instance_masks: rewrites bits 8..15 of every record's flags word from maskBits[customIndex] (the complement of the
+ * instance's mask, already shifted); records whose customIndex is past the table (the dummy record of an empty scene) are left alone */
+hipError_t launch_set_instance_masks(float4* tris, uint32_t numTris, const uint32_t* maskBits, uint32_t numInstances, hipStream_t stream);
 /* leaves[k] = the table entry of hits[k]; 0 for a miss or ids out of range, which read nothing */
 hipError_t launch_hit_leaves(const LeafArgs& a, hipStream_t stream);
 
-/* flags: RTR_QUERY_ANY | RTR_QUERY_OPAQUE (validated by the caller).  stats: the counting form, counters added there (zeroed by the caller). */
-hipError_t launch_query(const DeviceScene& sc, const QueryArgs& qa, uint32_t flags, Counters* stats, hipStream_t stream);
+/* flags: RTR_QUERY_ANY | RTR_QUERY_OPAQUE (validated by the caller).  stats: the counting form, counters added there (zeroed by the caller).
+ * rm.masked: the MASKED forms of the two kernels, which read the rays' cull masks (RayMaskArgs) and skip the records of instances whose mask
+ * does not meet the ray's; a ray whose effective mask is 0 walks nothing. */
+hipError_t launch_query(const DeviceScene& sc, const QueryArgs& qa, uint32_t flags, Counters* stats, hipStream_t stream, const RayMaskArgs& rm = RayMaskArgs());
 /* k_query_tail alone, any-hit form: finishes the rays another walk abandoned — qa.ctrl[kQueryRedoWord] of them, their indices in
  * qa.redoList (or, past qa.redoCap, found by the sentinel in qa.occluded) — over the BVH2 (the queued occlusion query's third stage) */
-hipError_t launch_query_tail_any(const DeviceScene& sc, const QueryArgs& qa, bool alpha, Counters* stats, hipStream_t stream);
+hipError_t launch_query_tail_any(const DeviceScene& sc, const QueryArgs& qa, bool alpha, Counters* stats, hipStream_t stream, const RayMaskArgs& rm = RayMaskArgs());
 /* The queued occlusion query (rtr_trace_occlusion; kernels/rtr_occlusion.hip): queue build over the rays -> k_shadow_trace4's walk over the
  * 4-wide tree (launch_occlusion_walk) -> k_query_tail.  spill: kSpillInts. */
 hipError_t launch_occlusion(const DeviceScene& sc, const OcclusionArgs& oa, const Tunables& tun, bool alpha, int32_t* spill, Counters* stats,
-                            hipStream_t stream, uint32_t numCus);
+                            hipStream_t stream, uint32_t numCus, const RayMaskArgs& rm = RayMaskArgs());
 /* rays one workgroup of the queue build bins: what bounds the batches a launch can append to one list (occlusion_list_stride) */
 constexpr uint32_t kOcclusionGenRays = 4096;
 constexpr uint32_t occlusion_batch(uint32_t n) { return (size_t)n >= ((size_t)100 << 20) ? 512u : 256u; }

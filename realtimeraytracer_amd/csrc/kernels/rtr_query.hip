@@ -46,8 +46,18 @@ __device__ __forceinline__ void query_store_hit(float4* __restrict__ hits, uint3
     hits[2 * (size_t)k + 1] = make_float4(__uint_as_float(h.prim), 0.0f, 0.0f, 0.0f);
 }
 
-template <bool ANY, bool ALPHA, bool STATS>
-__global__ __launch_bounds__(kQueryBlock) void k_query(DeviceScene sc, QueryArgs qa, Counters* stats) {
+/* ray k's effective cull mask, in the bits the records keep theirs in (trace()'s rayMask8); 0: nothing exists for the ray */
+__device__ __forceinline__ uint32_t query_ray_mask8(const RayMaskArgs& rm, uint32_t k) {
+    return (rm.cullMask & (rm.rayMasks ? (uint32_t)rm.rayMasks[k] : 0xffu)) << kTriMaskShift;
+}
+
+/* MASKED (rtr_trace_rays_masked): the ray's mask byte is read beside the ray; a ray whose effective mask is 0 is a miss that walks nothing,
+ * like a degenerate ray.  The masks are the LAST kernel argument, behind everything the forms without MASKED read: those compile to the
+ * instructions they had (compared function by function in the disassembly); only their kernel-argument segment is 16 B longer, which moves
+ * the offset of the one hidden argument k_query_tail loads (the grid size).  Giving the MASKED forms kernels of their own instead kept the
+ * segment and lost that: the inlined bodies were register-allocated differently (k_query 9 instructions longer). */
+template <bool ANY, bool ALPHA, bool STATS, bool MASKED = false>
+__global__ __launch_bounds__(kQueryBlock) void k_query(DeviceScene sc, QueryArgs qa, Counters* stats, RayMaskArgs rm) {
     __shared__ int32_t s_stack[16 * kQueryBlock];
     int32_t* stack = s_stack + threadIdx.x;
     const uint32_t k = blockIdx.x * kQueryBlock + threadIdx.x;
@@ -55,24 +65,25 @@ __global__ __launch_bounds__(kQueryBlock) void k_query(DeviceScene sc, QueryArgs
     LocalStats st;
     rtr_v3 o, d;
     float tmin, tmax;
-    const bool ok = query_ray(qa.rays, k, o, d, tmin, tmax);
+    const uint32_t rm8 = MASKED ? query_ray_mask8(rm, k) : 0u;
+    const bool ok = query_ray(qa.rays, k, o, d, tmin, tmax) && (!MASKED || rm8 != 0u);
     const float limit = ok ? tmax : tmin;                 /* a degenerate ray walks nothing (!(limit > tmin)) but is counted like any other */
     HitRec h;
-    if (STATS) trace<ANY, true, kQueryBlock, 16, 8, ALPHA, true>(sc, stack, o, d, tmin, limit, h, st);
+    if (STATS) trace<ANY, true, kQueryBlock, 16, 8, ALPHA, true, MASKED>(sc, stack, o, d, tmin, limit, h, st, rm8);
     else {
         /* as in k_primary: the traversal compiled for the wave's direction signs when all its rays share them */
         const uint32_t oct = ray_octant(sc, o, d);
         const uint32_t woct = (uint32_t)__builtin_amdgcn_readfirstlane((int)oct);
         switch (__ballot(oct != woct) != 0ull ? 8u : woct) {
-            case 0: trace<ANY, false, kQueryBlock, 16, 0, ALPHA, true>(sc, stack, o, d, tmin, limit, h, st); break;
-            case 1: trace<ANY, false, kQueryBlock, 16, 1, ALPHA, true>(sc, stack, o, d, tmin, limit, h, st); break;
-            case 2: trace<ANY, false, kQueryBlock, 16, 2, ALPHA, true>(sc, stack, o, d, tmin, limit, h, st); break;
-            case 3: trace<ANY, false, kQueryBlock, 16, 3, ALPHA, true>(sc, stack, o, d, tmin, limit, h, st); break;
-            case 4: trace<ANY, false, kQueryBlock, 16, 4, ALPHA, true>(sc, stack, o, d, tmin, limit, h, st); break;
-            case 5: trace<ANY, false, kQueryBlock, 16, 5, ALPHA, true>(sc, stack, o, d, tmin, limit, h, st); break;
-            case 6: trace<ANY, false, kQueryBlock, 16, 6, ALPHA, true>(sc, stack, o, d, tmin, limit, h, st); break;
-            case 7: trace<ANY, false, kQueryBlock, 16, 7, ALPHA, true>(sc, stack, o, d, tmin, limit, h, st); break;
-            default: trace<ANY, false, kQueryBlock, 16, 8, ALPHA, true>(sc, stack, o, d, tmin, limit, h, st); break;
+            case 0: trace<ANY, false, kQueryBlock, 16, 0, ALPHA, true, MASKED>(sc, stack, o, d, tmin, limit, h, st, rm8); break;
+            case 1: trace<ANY, false, kQueryBlock, 16, 1, ALPHA, true, MASKED>(sc, stack, o, d, tmin, limit, h, st, rm8); break;
+            case 2: trace<ANY, false, kQueryBlock, 16, 2, ALPHA, true, MASKED>(sc, stack, o, d, tmin, limit, h, st, rm8); break;
+            case 3: trace<ANY, false, kQueryBlock, 16, 3, ALPHA, true, MASKED>(sc, stack, o, d, tmin, limit, h, st, rm8); break;
+            case 4: trace<ANY, false, kQueryBlock, 16, 4, ALPHA, true, MASKED>(sc, stack, o, d, tmin, limit, h, st, rm8); break;
+            case 5: trace<ANY, false, kQueryBlock, 16, 5, ALPHA, true, MASKED>(sc, stack, o, d, tmin, limit, h, st, rm8); break;
+            case 6: trace<ANY, false, kQueryBlock, 16, 6, ALPHA, true, MASKED>(sc, stack, o, d, tmin, limit, h, st, rm8); break;
+            case 7: trace<ANY, false, kQueryBlock, 16, 7, ALPHA, true, MASKED>(sc, stack, o, d, tmin, limit, h, st, rm8); break;
+            default: trace<ANY, false, kQueryBlock, 16, 8, ALPHA, true, MASKED>(sc, stack, o, d, tmin, limit, h, st, rm8); break;
         }
     }
     /* the walk's outcome is read from the record alone (as k_primary reads it), not from trace()'s return value */
@@ -95,8 +106,8 @@ __global__ __launch_bounds__(kQueryBlock) void k_query(DeviceScene sc, QueryArgs
 /* The rays k_query abandoned, walked from the root with a full-depth stack in global memory (no LDS, so it can always run).  From the
  * redo list, or — when more rays were abandoned than the list holds — from a scan of the outputs for their sentinel.  STATS: the
  * counting form (the ray itself was counted by k_query; this walk's visits and tests are added to it). */
-template <bool ANY, bool ALPHA, bool STATS>
-__global__ __launch_bounds__(kQueryTailBlock) void k_query_tail(DeviceScene sc, QueryArgs qa, Counters* stats) {
+template <bool ANY, bool ALPHA, bool STATS, bool MASKED = false>
+__global__ __launch_bounds__(kQueryTailBlock) void k_query_tail(DeviceScene sc, QueryArgs qa, Counters* stats, RayMaskArgs rm) {
     const uint32_t count = qa.ctrl[kQueryRedoWord];
     if (count == 0u) return;
     const bool scan = count > qa.redoCap;
@@ -110,8 +121,9 @@ __global__ __launch_bounds__(kQueryTailBlock) void k_query_tail(DeviceScene sc, 
         rtr_v3 o, d;
         float tmin, tmax;
         query_ray(qa.rays, k, o, d, tmin, tmax);          /* an abandoned ray is never degenerate: it walked past 16 stacked nodes */
+        const uint32_t rm8 = MASKED ? query_ray_mask8(rm, k) : 0u;      /* re-read like the ray: never 0 here, such a ray walked nothing */
         HitRec h;
-        trace<ANY, STATS, kQueryTailBlocks * kQueryTailBlock, 0, 8, ALPHA, true>(sc, stack, o, d, tmin, tmax, h, st);
+        trace<ANY, STATS, kQueryTailBlocks * kQueryTailBlock, 0, 8, ALPHA, true, MASKED>(sc, stack, o, d, tmin, tmax, h, st, rm8);
         const bool found = h.custom != RTR_MISS;
         if (STATS) { st.rays--; if (ANY) st.shadow--; else st.primary--; }
         if (ANY) qa.occluded[k] = found ? 1u : 0u;
@@ -120,34 +132,44 @@ __global__ __launch_bounds__(kQueryTailBlock) void k_query_tail(DeviceScene sc, 
     if (STATS) st.flush(stats);
 }
 
-template <bool ANY, bool ALPHA, bool STATS>
-static hipError_t query_t(const DeviceScene& sc, const QueryArgs& qa, Counters* stats, hipStream_t s) {
+template <bool ANY, bool ALPHA, bool STATS, bool MASKED>
+static hipError_t query_t(const DeviceScene& sc, const QueryArgs& qa, Counters* stats, hipStream_t s, const RayMaskArgs& rm) {
     const uint32_t blocks = (uint32_t)(((uint64_t)qa.n + kQueryBlock - 1) / kQueryBlock);
-    hipLaunchKernelGGL((k_query<ANY, ALPHA, STATS>), dim3(blocks), dim3(kQueryBlock), 0, s, sc, qa, stats);
-    hipLaunchKernelGGL((k_query_tail<ANY, ALPHA, STATS>), dim3(kQueryTailBlocks), dim3(kQueryTailBlock), 0, s, sc, qa, stats);
+    hipLaunchKernelGGL((k_query<ANY, ALPHA, STATS, MASKED>), dim3(blocks), dim3(kQueryBlock), 0, s, sc, qa, stats, rm);
+    hipLaunchKernelGGL((k_query_tail<ANY, ALPHA, STATS, MASKED>), dim3(kQueryTailBlocks), dim3(kQueryTailBlock), 0, s, sc, qa, stats, rm);
     return hipGetLastError();
 }
 
-template <bool ANY, bool ALPHA>
-static hipError_t query_s(const DeviceScene& sc, const QueryArgs& qa, Counters* stats, hipStream_t s) {
-    return stats ? query_t<ANY, ALPHA, true>(sc, qa, stats, s) : query_t<ANY, ALPHA, false>(sc, qa, stats, s);
+template <bool ANY, bool ALPHA, bool MASKED>
+static hipError_t query_s(const DeviceScene& sc, const QueryArgs& qa, Counters* stats, hipStream_t s, const RayMaskArgs& rm) {
+    return stats ? query_t<ANY, ALPHA, true, MASKED>(sc, qa, stats, s, rm) : query_t<ANY, ALPHA, false, MASKED>(sc, qa, stats, s, rm);
 }
 
-hipError_t launch_query(const DeviceScene& sc, const QueryArgs& qa, uint32_t flags, Counters* stats, hipStream_t s) {
+template <bool MASKED>
+static hipError_t query_f(const DeviceScene& sc, const QueryArgs& qa, uint32_t flags, Counters* stats, hipStream_t s, const RayMaskArgs& rm) {
     const bool any = (flags & RTR_QUERY_ANY) != 0u, alpha = (flags & RTR_QUERY_OPAQUE) == 0u;
-    if (any) return alpha ? query_s<true, true>(sc, qa, stats, s) : query_s<true, false>(sc, qa, stats, s);
-    return alpha ? query_s<false, true>(sc, qa, stats, s) : query_s<false, false>(sc, qa, stats, s);
+    if (any) return alpha ? query_s<true, true, MASKED>(sc, qa, stats, s, rm) : query_s<true, false, MASKED>(sc, qa, stats, s, rm);
+    return alpha ? query_s<false, true, MASKED>(sc, qa, stats, s, rm) : query_s<false, false, MASKED>(sc, qa, stats, s, rm);
 }
 
-hipError_t launch_query_tail_any(const DeviceScene& sc, const QueryArgs& qa, bool alpha, Counters* stats, hipStream_t s) {
+hipError_t launch_query(const DeviceScene& sc, const QueryArgs& qa, uint32_t flags, Counters* stats, hipStream_t s, const RayMaskArgs& rm) {
+    return rm.masked ? query_f<true>(sc, qa, flags, stats, s, rm) : query_f<false>(sc, qa, flags, stats, s, rm);
+}
+
+template <bool MASKED>
+static hipError_t query_tail_any(const DeviceScene& sc, const QueryArgs& qa, bool alpha, Counters* stats, hipStream_t s, const RayMaskArgs& rm) {
     if (alpha) {
-        if (stats) hipLaunchKernelGGL((k_query_tail<true, true, true>), dim3(kQueryTailBlocks), dim3(kQueryTailBlock), 0, s, sc, qa, stats);
-        else hipLaunchKernelGGL((k_query_tail<true, true, false>), dim3(kQueryTailBlocks), dim3(kQueryTailBlock), 0, s, sc, qa, stats);
+        if (stats) hipLaunchKernelGGL((k_query_tail<true, true, true, MASKED>), dim3(kQueryTailBlocks), dim3(kQueryTailBlock), 0, s, sc, qa, stats, rm);
+        else hipLaunchKernelGGL((k_query_tail<true, true, false, MASKED>), dim3(kQueryTailBlocks), dim3(kQueryTailBlock), 0, s, sc, qa, stats, rm);
     } else {
-        if (stats) hipLaunchKernelGGL((k_query_tail<true, false, true>), dim3(kQueryTailBlocks), dim3(kQueryTailBlock), 0, s, sc, qa, stats);
-        else hipLaunchKernelGGL((k_query_tail<true, false, false>), dim3(kQueryTailBlocks), dim3(kQueryTailBlock), 0, s, sc, qa, stats);
+        if (stats) hipLaunchKernelGGL((k_query_tail<true, false, true, MASKED>), dim3(kQueryTailBlocks), dim3(kQueryTailBlock), 0, s, sc, qa, stats, rm);
+        else hipLaunchKernelGGL((k_query_tail<true, false, false, MASKED>), dim3(kQueryTailBlocks), dim3(kQueryTailBlock), 0, s, sc, qa, stats, rm);
     }
     return hipGetLastError();
+}
+
+hipError_t launch_query_tail_any(const DeviceScene& sc, const QueryArgs& qa, bool alpha, Counters* stats, hipStream_t s, const RayMaskArgs& rm) {
+    return rm.masked ? query_tail_any<true>(sc, qa, alpha, stats, s, rm) : query_tail_any<false>(sc, qa, alpha, stats, s, rm);
 }
 
 /* one lane per pixel-sample: the camera ray k_primary traces for it (primary_dir, tmin 0.001, tmax 10000) */
@@ -268,6 +290,27 @@ hipError_t launch_leaf_table(const uint4* nodes, uint32_t numNodes, const float4
     if (numNodes == 0) return hipSuccess;
     hipLaunchKernelGGL(k_leaf_table, dim3((numNodes + kLeafTableBlock - 1) / kLeafTableBlock), dim3(kLeafTableBlock), 0, s, nodes, numNodes, tris, numTris,
                        triCount, base, numInstances, table);
+    return hipGetLastError();
+}
+
+/* ---- instance cull masks (rtr_scene_set_instance_masks) ---------------------------------------------------------------------------------
+ * One lane per record of the leaf-ordered triangle array: bits 8..15 of its flags word (kTriMaskBits) become maskBits[customIndex] — the
+ * complement of its instance's mask, so the default 0xff is the zero the builders write — by one 4-byte store; bit 0 (alpha-tested) and
+ * every other byte of the record stay.  A customIndex past the table (the dummy record of an empty scene) is left alone. */
+constexpr int kSetMasksBlock = 256;
+__global__ __launch_bounds__(kSetMasksBlock) void k_set_instance_masks(float4* __restrict__ tris, uint32_t numTris, const uint32_t* __restrict__ maskBits,
+                                                                       uint32_t numInstances) {
+    const uint32_t j = blockIdx.x * kSetMasksBlock + threadIdx.x;
+    if (j >= numTris) return;
+    const uint32_t custom = __float_as_uint(tris[3 * (size_t)j].w);
+    if (custom >= numInstances) return;
+    uint32_t* const flags = reinterpret_cast<uint32_t*>(&tris[3 * (size_t)j + 2].w);
+    *flags = (*flags & ~kTriMaskBits) | (maskBits[custom] & kTriMaskBits);
+}
+
+hipError_t launch_set_instance_masks(float4* tris, uint32_t numTris, const uint32_t* maskBits, uint32_t numInstances, hipStream_t s) {
+    if (numTris == 0 || numInstances == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_set_instance_masks, dim3((numTris + kSetMasksBlock - 1) / kSetMasksBlock), dim3(kSetMasksBlock), 0, s, tris, numTris, maskBits, numInstances);
     return hipGetLastError();
 }
 

@@ -122,6 +122,10 @@ struct rtr_scene {
     DevBuf<uint32_t> lightTriFirst;      /* first record of light l */
     DevBuf<uint32_t> triCount;           /* per customIndex: triangles of the light or of the instance's mesh (rtr_hit_surfaces' range check) */
     uint32_t numInstances = 0;
+    /* instance cull masks (rtr_scene_set_instance_masks): one byte per instance, in instance order; empty = never set, every mask 0xff.
+     * The records carry them (bits 8..15 of flags, complemented); this table is what the getter returns and what a refit re-applies */
+    std::vector<uint8_t> hostMasks;
+    DevBuf<uint32_t> maskBits;           /* per customIndex: (~mask & 0xff) << 8, the setter kernel's table */
     /* the triangle -> leaf table (rtr_hit_leaves, rtr_light_rays_hinted): made by the first call that asks for it (ensure_leaf_table), kept
      * through refits, which keep topology and leaf order.  mutable: the query calls take the scene const */
     std::vector<uint32_t> hostTriCount;
@@ -606,6 +610,7 @@ static int scene_create_impl(rtr_ctx* ctx, const rtr_scene_desc* d, const rtr_sc
         if (like->stats.numTriangles != totalPrims || like->hostNodes.empty() || like->hostTris.empty())
             return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_scene_create_like: the built scene has %u triangles, this description %zu", like->stats.numTriangles, totalPrims);
         bvh.nodes = like->hostNodes; bvh.tris = like->hostTris; bvh.grid = like->stats.grid; bvh.wideShape = like->hostWideShape;
+        if (!like->hostMasks.empty()) for (RtrBvhTri& t : bvh.tris) t.flags &= ~RTR_TRI_MASK_BITS;      /* a new scene's instance masks are 0xff, whatever `like` has set */
         bvh.maxDepth = like->stats.maxDepth; bvh.maxLeafSize = like->stats.maxLeafSize; bvh.sahCost = like->stats.sahCost; bvh.boxPad = like->stats.boxPad;
         for (int k = 0; k < 3; ++k) { bvh.boundsMin[k] = like->stats.boundsMin[k]; bvh.boundsMax[k] = like->stats.boundsMax[k]; }
         bvh.buildMs = 0.f;                                   /* nothing was built here */
@@ -749,6 +754,42 @@ static int ensure_refit_ready(rtr_scene* s) {
     return RTR_OK;
 }
 
+/* per customIndex: the complement of the instance's mask where the records keep it (RtrBvhTri::flags, RTR_TRI_MASK_SHIFT) */
+static std::vector<uint32_t> instance_mask_bits(const rtr_scene* s, const uint8_t* masks) {
+    std::vector<uint32_t> bits(s->hostInstances.size(), 0u);
+    for (size_t i = 0; i < s->hostInstances.size(); ++i) bits[s->hostInstances[i].customIndex] = ((uint32_t)(uint8_t)~masks[i]) << RTR_TRI_MASK_SHIFT;
+    return bits;
+}
+
+int rtr_scene_set_instance_masks(rtr_scene* s, const uint8_t* masks, uint32_t numInstances) {
+    if (!s || (!masks && numInstances)) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_scene_set_instance_masks: null argument");
+    if (numInstances != s->hostInstances.size()) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_scene_set_instance_masks: %u masks given, scene has %zu instances", numInstances, s->hostInstances.size());
+    if (numInstances == 0) return RTR_OK;
+    const std::vector<uint32_t> bits = instance_mask_bits(s, masks);
+    HIP_TRY(hipSetDevice(s->ctx->device));
+    /* queries of OTHER contexts (other streams) may be walking these records: everything enqueued on the device so far is joined before
+     * they are rewritten (contract in rtr.h, as rtr_scene_update_instances) */
+    HIP_TRY(hipDeviceSynchronize());
+    hipStream_t st = s->ctx->stream;
+    const uint32_t numTris = (uint32_t)(s->tris.n / 3);
+    HIP_TRY(s->maskBits.upload(bits.data(), bits.size(), st));
+    const hipError_t e = rtrdev::launch_set_instance_masks(s->tris.p, numTris, s->maskBits.p, numInstances, st);
+    if (e != hipSuccess) return fail(RTR_ERR_HIP, "rtr_scene_set_instance_masks: kernel launch: %s", hipGetErrorString(e));
+    HIP_TRY(hipStreamSynchronize(st));
+    /* the host mirror (rtr_scene_export_bvh, rtr_scene_create_like) in step: the same rule as the kernel's */
+    for (RtrBvhTri& t : s->hostTris)
+        if (t.customIndex < numInstances) t.flags = (t.flags & ~RTR_TRI_MASK_BITS) | bits[t.customIndex];
+    s->hostMasks.assign(masks, masks + numInstances);
+    return RTR_OK;
+}
+
+int rtr_scene_get_instance_masks(const rtr_scene* s, uint8_t* masks, uint32_t numInstances) {
+    if (!s || (!masks && numInstances)) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_scene_get_instance_masks: null argument");
+    if (numInstances != s->hostInstances.size()) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_scene_get_instance_masks: room for %u masks, scene has %zu instances", numInstances, s->hostInstances.size());
+    for (uint32_t i = 0; i < numInstances; ++i) masks[i] = s->hostMasks.empty() ? 0xffu : s->hostMasks[i];
+    return RTR_OK;
+}
+
 int rtr_scene_update_instances(rtr_scene* s, const RtrInstance* instances, uint32_t numInstances, const RtrAreaLightInfo* lights, uint32_t numLights) {
     if (!s || (!instances && numInstances)) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_scene_update_instances: null argument");
     if (numInstances != s->hostInstances.size()) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_scene_update_instances: %u instances given, scene has %zu", numInstances, s->hostInstances.size());
@@ -779,6 +820,10 @@ int rtr_scene_update_instances(rtr_scene* s, const RtrInstance* instances, uint3
     view.numLights = s->numLights;
     std::vector<rtrdev::PrimRef> prims; std::vector<rtrdev::InstanceRef> refs;
     make_prim_tables(&view, instances, prims, refs);
+    if (!s->hostMasks.empty()) {      /* the refit rewrites the records from this table: the instance masks go with it */
+        const std::vector<uint32_t> bits = instance_mask_bits(s, s->hostMasks.data());
+        for (rtrdev::PrimRef& pr : prims) pr.flags |= bits[pr.customIndex];
+    }
     HIP_TRY(s->prims.upload(prims.data(), prims.size(), st));
     HIP_TRY(s->instRefs.upload(refs.data(), refs.size(), st));
     std::vector<float> xforms, nmats;
@@ -1435,9 +1480,14 @@ static int query_scratch(rtr_ctx* c) {
 }
 
 /* the checks and launches of rtr_trace_rays[_async], enqueued on the context's stream; count: the counting form */
+/* the cull mask of the masked calls: NoMask for the unmasked ones, which launch the kernels' unmasked forms */
+struct CullMask { bool masked; const uint8_t* rayMasks; uint32_t cullMask; };
+static const CullMask NoMask{false, nullptr, 0xffu};
+
 static int enqueue_query(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, uint32_t n, uint32_t flags, RtrHit* hits, uint8_t* occluded,
-                         bool count, const char* who) {
+                         bool count, const char* who, const CullMask& cm = NoMask) {
     if (!c || !s) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: null context or scene", who);
+    if (cm.masked && (cm.cullMask & ~0xffu)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: cullMask 0x%x has bits above the low 8 (an instance mask is 8 bits)", who, cm.cullMask);
     if (flags & ~(RTR_QUERY_ANY | RTR_QUERY_OPAQUE)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: unknown flag bits 0x%x", who, flags & ~(RTR_QUERY_ANY | RTR_QUERY_OPAQUE));
     if (s->ctx->device != c->device) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: the scene lives on device %d, the context on device %d", who, s->ctx->device, c->device);
     if (n == 0) return RTR_OK;
@@ -1464,7 +1514,9 @@ static int enqueue_query(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, uin
     rtrdev::QueryArgs qa{};
     qa.rays = reinterpret_cast<const float4*>(rays); qa.hits = reinterpret_cast<float4*>(hits); qa.occluded = occluded; qa.n = n;
     qa.redoCap = redoCap; qa.ctrl = c->qCtrl.p; qa.redoList = c->qRedo.p; qa.spill = c->qSpill.p;
-    const hipError_t e = rtrdev::launch_query(s->dev, qa, flags, count ? c->qCounters.p : nullptr, st);
+    rtrdev::RayMaskArgs rm;
+    rm.rayMasks = cm.rayMasks; rm.cullMask = cm.cullMask; rm.masked = cm.masked ? 1u : 0u;
+    const hipError_t e = rtrdev::launch_query(s->dev, qa, flags, count ? c->qCounters.p : nullptr, st, rm);
     if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: kernel launch: %s", who, hipGetErrorString(e));
     HIP_TRY(hipEventRecord(c->qEv[1], st));
     c->qLastStream = st;
@@ -1475,8 +1527,26 @@ int rtr_trace_rays_async(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, uin
     return enqueue_query(c, s, rays, n, flags, hits, occluded, false, "rtr_trace_rays_async");
 }
 
+static int query_sync(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, uint32_t n, uint32_t flags, RtrHit* hits, uint8_t* occluded, rtr_query_stats* stats,
+                      const char* who, const CullMask& cm);
+
 int rtr_trace_rays(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, uint32_t n, uint32_t flags, RtrHit* hits, uint8_t* occluded, rtr_query_stats* stats) {
-    const int rc = enqueue_query(c, s, rays, n, flags, hits, occluded, stats != nullptr, "rtr_trace_rays");
+    return query_sync(c, s, rays, n, flags, hits, occluded, stats, "rtr_trace_rays", NoMask);
+}
+
+int rtr_trace_rays_masked_async(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const uint8_t* rayMasks, uint32_t n, uint32_t flags, uint32_t cullMask,
+                                RtrHit* hits, uint8_t* occluded) {
+    return enqueue_query(c, s, rays, n, flags, hits, occluded, false, "rtr_trace_rays_masked_async", CullMask{true, rayMasks, cullMask});
+}
+
+int rtr_trace_rays_masked(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const uint8_t* rayMasks, uint32_t n, uint32_t flags, uint32_t cullMask,
+                          RtrHit* hits, uint8_t* occluded, rtr_query_stats* stats) {
+    return query_sync(c, s, rays, n, flags, hits, occluded, stats, "rtr_trace_rays_masked", CullMask{true, rayMasks, cullMask});
+}
+
+static int query_sync(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, uint32_t n, uint32_t flags, RtrHit* hits, uint8_t* occluded, rtr_query_stats* stats,
+                      const char* who, const CullMask& cm) {
+    const int rc = enqueue_query(c, s, rays, n, flags, hits, occluded, stats != nullptr, who, cm);
     if (rc != RTR_OK) return rc;
     if (stats) memset(stats, 0, sizeof *stats);
     if (n == 0) return RTR_OK;
@@ -1524,9 +1594,10 @@ static bool aligned4(const void* p) { return ((uintptr_t)p & 3u) == 0; }
 
 /* startLeaves: the hints of rtr_trace_occlusion_hinted (null: none; the unhinted calls pass null) */
 static int enqueue_occlusion(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const int32_t* startLeaves, uint32_t n, uint32_t flags, void* scratch,
-                             size_t scratchBytes, uint8_t* occluded, bool count, const char* who) {
+                             size_t scratchBytes, uint8_t* occluded, bool count, const char* who, const CullMask& cm = NoMask) {
     if (n && !aligned4(startLeaves)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: startLeaves is not 4-B aligned", who);
     if (!c || !s) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: null context or scene", who);
+    if (cm.masked && (cm.cullMask & ~0xffu)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: cullMask 0x%x has bits above the low 8 (an instance mask is 8 bits)", who, cm.cullMask);
     if (flags & ~(RTR_QUERY_ANY | RTR_QUERY_OPAQUE)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: unknown flag bits 0x%x", who, flags & ~(RTR_QUERY_ANY | RTR_QUERY_OPAQUE));
     if (s->ctx->device != c->device) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: the scene lives on device %d, the context on device %d", who, s->ctx->device, c->device);
     if (n == 0) return RTR_OK;
@@ -1554,8 +1625,10 @@ static int enqueue_occlusion(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays,
     oa.ctrl = reinterpret_cast<uint32_t*>(base + l.ctrl); oa.overflow = reinterpret_cast<uint32_t*>(base + l.overflow); oa.overflowCap = overflowCap;
     oa.queue = reinterpret_cast<uint32_t*>(base + l.queue); oa.lists = reinterpret_cast<uint2*>(base + l.lists); oa.listStride = l.listStride;
     oa.startLeaves = startLeaves; oa.numTris = (uint32_t)(s->tris.n / 3);          /* a hint is checked against the records the scene holds */
+    rtrdev::RayMaskArgs rm;
+    rm.rayMasks = cm.rayMasks; rm.cullMask = cm.cullMask; rm.masked = cm.masked ? 1u : 0u;
     const hipError_t e = rtrdev::launch_occlusion(s->dev, oa, c->tun, (flags & RTR_QUERY_OPAQUE) == 0u, c->qSpill.p, count ? c->qCounters.p : nullptr, st,
-                                                  (uint32_t)c->prop.multiProcessorCount);
+                                                  (uint32_t)c->prop.multiProcessorCount, rm);
     if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: kernel launch: %s", who, hipGetErrorString(e));
     HIP_TRY(hipEventRecord(c->qEv[1], st));
     c->qLastStream = st;
@@ -1572,7 +1645,17 @@ int rtr_trace_occlusion_hinted_async(rtr_ctx* c, const rtr_scene* s, const RtrRa
 }
 
 static int occlusion_sync(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const int32_t* startLeaves, uint32_t n, uint32_t flags, void* scratch,
-                          size_t scratchBytes, uint8_t* occluded, rtr_query_stats* stats, const char* who);
+                          size_t scratchBytes, uint8_t* occluded, rtr_query_stats* stats, const char* who, const CullMask& cm = NoMask);
+
+int rtr_trace_occlusion_masked_async(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const int32_t* startLeaves, const uint8_t* rayMasks, uint32_t n,
+                                     uint32_t flags, uint32_t cullMask, void* scratch, size_t scratchBytes, uint8_t* occluded) {
+    return enqueue_occlusion(c, s, rays, startLeaves, n, flags, scratch, scratchBytes, occluded, false, "rtr_trace_occlusion_masked_async", CullMask{true, rayMasks, cullMask});
+}
+
+int rtr_trace_occlusion_masked(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const int32_t* startLeaves, const uint8_t* rayMasks, uint32_t n,
+                               uint32_t flags, uint32_t cullMask, void* scratch, size_t scratchBytes, uint8_t* occluded, rtr_query_stats* stats) {
+    return occlusion_sync(c, s, rays, startLeaves, n, flags, scratch, scratchBytes, occluded, stats, "rtr_trace_occlusion_masked", CullMask{true, rayMasks, cullMask});
+}
 
 int rtr_trace_occlusion(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, uint32_t n, uint32_t flags, void* scratch, size_t scratchBytes, uint8_t* occluded,
                         rtr_query_stats* stats) {
@@ -1585,8 +1668,8 @@ int rtr_trace_occlusion_hinted(rtr_ctx* c, const rtr_scene* s, const RtrRay* ray
 }
 
 static int occlusion_sync(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const int32_t* startLeaves, uint32_t n, uint32_t flags, void* scratch,
-                          size_t scratchBytes, uint8_t* occluded, rtr_query_stats* stats, const char* who) {
-    const int rc = enqueue_occlusion(c, s, rays, startLeaves, n, flags, scratch, scratchBytes, occluded, stats != nullptr, who);
+                          size_t scratchBytes, uint8_t* occluded, rtr_query_stats* stats, const char* who, const CullMask& cm) {
+    const int rc = enqueue_occlusion(c, s, rays, startLeaves, n, flags, scratch, scratchBytes, occluded, stats != nullptr, who, cm);
     if (rc != RTR_OK) return rc;
     if (stats) memset(stats, 0, sizeof *stats);
     if (n == 0) return RTR_OK;

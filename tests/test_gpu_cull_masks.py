@@ -1,0 +1,583 @@
+"""Instance cull masks on the device (rtr_scene_set_instance_masks, rtr_trace_rays_masked, rtr_trace_occlusion_masked): Vulkan's rule —
+an instance's triangles exist for a ray iff (instanceMask & rayMask) != 0 — against a brute force of the test's own: oracle_mt (the
+kernels' Moeller-Trumbore) over the exported triangle records, filtered by masks[customIndex] & rayMask, closest = the minimum over
+(t, customIndex, primitiveId), occluded = a filtered hit exists in (tmin, tmax).  Every ray is compared, bit for bit for hits and byte
+for byte for occlusion.  Scenes with alpha-tested geometry are queried with RTR_QUERY_OPAQUE where the brute force is the reference, as
+tests/test_gpu_query.py does.
+
+The brute force keeps Python out of the (ray, triangle) loop: a float64 restatement of the test with generous slack picks, per ray, the
+records that could possibly be accepted (barycentrics within 1e-3 of the triangle, t within a relative 1e-3 of the interval, or a
+determinant too small to judge), and oracle_mt decides every one of those."""
+import numpy as np
+import pytest
+import torch
+
+from realtimeraytracer_amd import _abi as A
+from realtimeraytracer_amd import api, host, scenes
+
+from test_gpu_occlusion import assert_same_bytes, camera_light_rays, mixed_rays
+from test_gpu_query import MISS, _deep_scene, _features_setup, assert_hits
+
+pytestmark = pytest.mark.gpu
+
+F3 = A.f32 * 3
+INVALID = -1
+
+
+def _np(x):
+    return x.cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+
+
+def _records(bvh):
+    raw = np.frombuffer(bvh[1], dtype=np.uint32).reshape(-1, 12).copy()
+    return raw, raw.view(np.float32)
+
+
+def all_hits(oracle, bvh, rays):
+    """per ray: (t, u, v, customIndex, primitiveId) arrays of EVERY record oracle_mt accepts with t < tmax, whatever its mask"""
+    raw, flt = _records(bvh)
+    v0, e1, e2 = flt[:, 0:3].astype(np.float64), flt[:, 4:7].astype(np.float64), flt[:, 8:11].astype(np.float64)
+    n1 = np.linalg.norm(e1, axis=1)
+    L = oracle.lib()
+    tuv = (A.f32 * 3)()
+    out = []
+    for r in rays:
+        tmin, tmax = r[3], r[7]
+        got = ([], [], [], [], [])
+        if tmax > tmin and np.isfinite(r[[0, 1, 2, 4, 5, 6]]).all() and r[4:7].any():
+            o, d = r[0:3].astype(np.float64), r[4:7].astype(np.float64)
+            h = np.cross(d, e2)
+            a = np.einsum("ij,ij->i", e1, h)
+            small = np.abs(a) <= 1e-4 * n1 * np.linalg.norm(h, axis=1) + 1e-300
+            with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+                f = 1.0 / a
+                s = o - v0
+                u = f * np.einsum("ij,ij->i", s, h)
+                q = np.cross(s, e1)
+                v = f * (q @ d)
+                t = f * np.einsum("ij,ij->i", e2, q)
+                inside = (u >= -1e-3) & (v >= -1e-3) & (u + v <= 1.0 + 1e-3) & (t > tmin - 1e-3 * (abs(tmin) + 1.0)) & ~(t > tmax + 1e-3 * (abs(tmax) + 1.0))
+            o32, d32 = F3(*r[0:3]), F3(*r[4:7])
+            for j in np.nonzero(small | inside | ~np.isfinite(t))[0]:
+                if L.oracle_mt(o32, d32, F3(*flt[j, 0:3]), F3(*flt[j, 4:7]), F3(*flt[j, 8:11]), float(tmin), tuv) and np.float32(tuv[0]) < tmax:
+                    for lst, x in zip(got, (np.float32(tuv[0]), np.float32(tuv[1]), np.float32(tuv[2]), int(raw[j, 3]), int(raw[j, 7]))):
+                        lst.append(x)
+        out.append(got)
+    return out
+
+
+def by_custom(desc, masks):
+    """instance-order masks -> a table indexed by customIndex"""
+    t = np.zeros(desc.numInstances, np.int64)
+    for i in range(desc.numInstances):
+        t[desc.instances[i].customIndex] = int(masks[i])
+    return t
+
+
+def filtered(cands, rays, custom_masks, ray_masks):
+    """the expected closest hit and occlusion byte of every ray under the masks"""
+    n = len(rays)
+    t = rays[:, 7].copy(); u = np.zeros(n, np.float32); v = np.zeros(n, np.float32)
+    cu = np.full(n, MISS, np.int64); pr = np.full(n, MISS, np.int64)
+    occ = np.zeros(n, np.uint8)
+    ray_masks = np.broadcast_to(np.asarray(ray_masks, np.int64), (n,))
+    for k, (ts, us, vs, cs, ps) in enumerate(cands):
+        best = None
+        for tt, uu, vv, c, p in zip(ts, us, vs, cs, ps):
+            if custom_masks[c] & ray_masks[k]:
+                if best is None or (tt, c, p) < best[0]:
+                    best = ((tt, c, p), uu, vv)
+        if best is not None:
+            (t[k], cu[k], pr[k]), u[k], v[k] = best[0], best[1], best[2]
+            occ[k] = 1
+    return (t, u, v, cu, pr), occ
+
+
+def seeded_masks(n, seed):
+    """0, single bits and mixed values"""
+    rng = np.random.default_rng(seed)
+    kind = rng.integers(0, 10, n)
+    m = rng.integers(1, 256, n)
+    m = np.where(kind < 5, 1 << rng.integers(0, 8, n), m)
+    m = np.where(kind == 9, 0, m)
+    return m.astype(np.uint8)
+
+
+def counters(st):
+    return (st.numRays, st.numNodeVisits, st.numTriTests, st.numAlphaTests, st.tailRays)
+
+
+def scene_of(name, gpu_ctx, tmp_path, build=A.BUILD_HOST_SAH, size=(160, 100)):
+    if name == "features":
+        hs = _features_setup(tmp_path)
+        desc, keep, s = hs.desc, hs, None
+    else:
+        s = getattr(scenes, name)(*size)
+        desc, keep = s.desc, s
+    old = desc.buildFlags
+    desc.buildFlags = build
+    try:
+        scene = api.Scene(gpu_ctx, desc)
+    finally:
+        desc.buildFlags = old
+    return scene, desc, keep, s
+
+
+def leaves_of(scene, rays_t):
+    """valid start hints for arbitrary rays: the leaves of their unmasked closest hits (0 at a miss)"""
+    return api.hit_leaves(scene, api.trace_rays(scene, rays_t, opaque=True).hits)
+
+
+# ---- 1. defaults change nothing ------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("case", ["sponza_mixed", "textured_room"])
+def test_defaults_change_nothing(gpu_ctx, scene_cache, tmp_path, case):
+    scene, desc, keep, s = scene_of(case, gpu_ctx, tmp_path)
+    st = scene.stats()
+    rays, hits, lp, lr = camera_light_rays(gpu_ctx, scene, s, 160, 100, 0)
+    diag = float(np.linalg.norm(np.array(st.boundsMax[:]) - np.array(st.boundsMin[:])))
+    rnd = torch.from_numpy(mixed_rays(st, 50000, 3, diag)).cuda()
+    for name, r in (("camera", rays), ("light", lr), ("random", rnd)):
+        for opaque in (False, True):
+            a = api.trace_rays(scene, r, opaque=opaque, collect_stats=True)
+            b = api.trace_rays(scene, r, opaque=opaque, collect_stats=True, cull_mask=0xff)
+            assert torch.equal(a.hits, b.hits), f"{case} {name}: dense closest"
+            assert counters(a.stats) == counters(b.stats), f"{case} {name}: dense closest counters"
+            a = api.trace_rays(scene, r, any_hit=True, opaque=opaque, collect_stats=True)
+            b = api.trace_rays(scene, r, any_hit=True, opaque=opaque, collect_stats=True, cull_mask=0xff)
+            assert_same_bytes(b.occluded, a.occluded, f"{case} {name}: dense any")
+            assert counters(a.stats) == counters(b.stats), f"{case} {name}: dense any counters"
+            dense = a.occluded
+            a = api.trace_occlusion(scene, r, opaque=opaque, collect_stats=True)
+            b = api.trace_occlusion(scene, r, opaque=opaque, collect_stats=True, cull_mask=0xff)
+            assert_same_bytes(b.occluded, a.occluded, f"{case} {name}: queued")
+            assert_same_bytes(b.occluded, dense, f"{case} {name}: queued against dense")
+            assert counters(a.stats) == counters(b.stats), f"{case} {name}: queued counters"
+            timed = api.trace_occlusion(scene, r, opaque=opaque, cull_mask=0xff)
+            assert_same_bytes(timed.occluded, dense, f"{case} {name}: queued, timed form")
+    lrh, leaves = api.light_rays(scene, rays, hits, lp, hints=True)
+    assert int((leaves != 0).sum()) > 0
+    a = api.trace_occlusion(scene, lrh, collect_stats=True, start_leaves=leaves)
+    b = api.trace_occlusion(scene, lrh, collect_stats=True, start_leaves=leaves, cull_mask=0xff)
+    assert_same_bytes(b.occluded, a.occluded, f"{case}: queued hinted")
+    assert counters(a.stats) == counters(b.stats), f"{case}: queued hinted counters"
+    ones = torch.full((lrh.shape[0],), 0xff, dtype=torch.uint8, device=lrh.device)
+    c = api.trace_occlusion(scene, lrh, collect_stats=True, start_leaves=leaves, ray_masks=ones)
+    assert_same_bytes(c.occluded, a.occluded, f"{case}: queued hinted, per-ray 0xff")
+    assert counters(a.stats) == counters(c.stats)
+    assert (scene.instance_masks() == 0xff).all()
+
+
+# ---- 2. random instance masks x random cull masks ---------------------------------------------------------------------------------
+@pytest.mark.parametrize("build", [A.BUILD_HOST_SAH, A.BUILD_DEVICE_LBVH], ids=["host_sah", "device_lbvh"])
+@pytest.mark.parametrize("case", ["features", "textured_room", "sponza_mixed"])
+def test_random_masks_equal_the_filtered_brute_force(gpu_ctx, oracle, scene_cache, tmp_path, case, build):
+    scene, desc, keep, s = scene_of(case, gpu_ctx, tmp_path, build)
+    st = scene.stats()
+    diag = float(np.linalg.norm(np.array(st.boundsMax[:]) - np.array(st.boundsMin[:])))
+    n = 300 if case == "sponza_mixed" else 1500
+    rays = mixed_rays(st, n, 31, diag)
+    if case == "sponza_mixed":          # rays that meet more of the scene: camera rays of a coarse frame
+        cam = _np(api.camera_rays(gpu_ctx, s.camera, 16, 9, 1))
+        rays = np.concatenate([rays, cam]).astype(np.float32)
+        n = len(rays)
+    rt = torch.from_numpy(rays).cuda()
+    cands = all_hits(oracle, scene.export_bvh(), rays)
+    assert 0.05 < np.mean([len(c[0]) > 0 for c in cands]) < 0.99
+    hints = leaves_of(scene, rt)
+    assert int((hints != 0).sum()) > 0
+    culls = [0xff, 0x01, 0x80, 0x5a, 0x00, 0xa5]
+    some_masked_out = False
+    for round_, seed in enumerate((101, 202)):
+        masks = seeded_masks(desc.numInstances, seed)
+        scene.set_instance_masks(masks)
+        assert (scene.instance_masks() == masks).all()
+        cm = by_custom(desc, masks)
+        raw = _records(scene.export_bvh())[0]
+        assert ((raw[:, 11] >> 8) == (~cm[raw[:, 3]] & 0xff)).all() and not (raw[:, 11] >> 16).any()
+        for cull in culls:
+            what = f"{case} masks {seed} cull {cull:#x}"
+            exp, occ = filtered(cands, rays, cm, cull)
+            unm, _ = filtered(cands, rays, np.full(len(cm), 0xff, np.int64), 0xff)
+            some_masked_out |= bool((exp[3] != unm[3]).any())
+            assert_hits(api.trace_rays(scene, rt, opaque=True, cull_mask=cull), exp, what)
+            forms = {"dense any": api.trace_rays(scene, rt, any_hit=True, opaque=True, cull_mask=cull),
+                     "queued": api.trace_occlusion(scene, rt, opaque=True, cull_mask=cull),
+                     "queued hinted": api.trace_occlusion(scene, rt, opaque=True, cull_mask=cull, start_leaves=hints),
+                     "queued hinted, counting": api.trace_occlusion(scene, rt, opaque=True, cull_mask=cull, start_leaves=hints, collect_stats=True)}
+            for name, res in forms.items():
+                assert_same_bytes(res.occluded, occ, f"{what}: {name}")
+    assert some_masked_out, "the masks must change some closest hits"
+
+
+# ---- 3. per-ray masks ------------------------------------------------------------------------------------------------------------
+def test_per_ray_masks_equal_one_launch_per_mask(gpu_ctx, oracle, scene_cache, tmp_path):
+    scene, desc, keep, s = scene_of("features", gpu_ctx, tmp_path)
+    st = scene.stats()
+    diag = float(np.linalg.norm(np.array(st.boundsMax[:]) - np.array(st.boundsMin[:])))
+    rays = mixed_rays(st, 4000, 77, diag)
+    rt = torch.from_numpy(rays).cuda()
+    masks = seeded_masks(desc.numInstances, 5)
+    masks[masks == 0] = 0x10
+    scene.set_instance_masks(masks)
+    cm = by_custom(desc, masks)
+    values = np.array([0x00, 0x01, 0x10, 0x0f, 0xf0, 0xff, 0x81], np.uint8)
+    rm = values[np.random.default_rng(9).integers(0, len(values), len(rays))]
+    rmt = torch.from_numpy(rm).cuda()
+    hints = leaves_of(scene, rt)
+    cands = all_hits(oracle, scene.export_bvh(), rays)
+    for cull in (0xff, 0x3c):
+        one = api.trace_rays(scene, rt, opaque=True, cull_mask=cull, ray_masks=rmt)
+        one_any = api.trace_rays(scene, rt, any_hit=True, opaque=True, cull_mask=cull, ray_masks=rmt)
+        one_q = api.trace_occlusion(scene, rt, opaque=True, cull_mask=cull, ray_masks=rmt, start_leaves=hints)
+        exp, occ = filtered(cands, rays, cm, rm.astype(np.int64) & cull)           # ray_masks & cull_mask composes
+        assert_hits(one, exp, f"per-ray masks, cull {cull:#x}")
+        assert_same_bytes(one_any.occluded, occ, "per-ray masks: dense any")
+        assert_same_bytes(one_q.occluded, occ, "per-ray masks: queued hinted")
+        for val in values:                                                          # k launches with cull_mask, each restricted to its rays
+            idx = torch.from_numpy(np.nonzero(rm == val)[0]).cuda()
+            part = api.trace_rays(scene, rt[idx].contiguous(), opaque=True, cull_mask=int(val) & cull)
+            assert torch.equal(part.hits, one.hits[idx]), f"value {val:#x}"
+            part_q = api.trace_occlusion(scene, rt[idx].contiguous(), opaque=True, cull_mask=int(val) & cull)
+            assert torch.equal(part_q.occluded, one_q.occluded[idx]), f"value {val:#x}, queued"
+    # numpy masks are uploaded; a zero effective mask gives misses and no visits are counted for those rays
+    res = api.trace_rays(scene, rt, opaque=True, ray_masks=rm)
+    assert torch.equal(res.hits, api.trace_rays(scene, rt, opaque=True, ray_masks=rmt).hits)
+    zero = np.zeros(len(rays), np.uint8)
+    for kw in ({"cull_mask": 0}, {"ray_masks": zero}, {"cull_mask": 0xf0, "ray_masks": np.full(len(rays), 0x0f, np.uint8)}):
+        r = api.trace_rays(scene, rt, collect_stats=True, **kw)
+        assert (_np(r.custom_index) == -1).all() and (_np(r.primitive_id) == -1).all()
+        assert (_np(r.t).view(np.uint32) == rays[:, 7].view(np.uint32)).all()       # a miss reports the ray's own tmax
+        assert r.stats.numRays == len(rays) and r.stats.numNodeVisits == 0 and r.stats.numTriTests == 0
+        a = api.trace_rays(scene, rt, any_hit=True, collect_stats=True, **kw)
+        assert not _np(a.occluded).any() and a.stats.numNodeVisits == 0 and a.stats.numTriTests == 0
+        q = api.trace_occlusion(scene, rt, collect_stats=True, start_leaves=hints, **kw)
+        assert not _np(q.occluded).any() and q.stats.numNodeVisits == 0 and q.stats.numTriTests == 0
+        assert q.stats.numRays == api.trace_occlusion(scene, rt, collect_stats=True).stats.numRays      # counted as an empty interval is
+    # half the rays see nothing: only the other half's visits are counted
+    half = np.where(np.arange(len(rays)) % 2 == 0, 0, 0xff).astype(np.uint8)
+    odd = torch.from_numpy(np.nonzero(half)[0]).cuda()
+    for any_hit in (False, True):
+        both = api.trace_rays(scene, rt, any_hit=any_hit, collect_stats=True, ray_masks=half).stats
+        only = api.trace_rays(scene, rt[odd].contiguous(), any_hit=any_hit, collect_stats=True, cull_mask=0xff).stats
+        assert (both.numNodeVisits, both.numTriTests) == (only.numNodeVisits, only.numTriTests)
+    both = api.trace_occlusion(scene, rt, collect_stats=True, ray_masks=half).stats
+    only = api.trace_occlusion(scene, rt[odd].contiguous(), collect_stats=True, cull_mask=0xff).stats
+    assert (both.numNodeVisits, both.numTriTests) == (only.numNodeVisits, only.numTriTests)
+
+
+# ---- 4. lights out of a bounce ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("case", ["textured_room", "sponza_mixed"])
+def test_lights_masked_out_of_closest_hits(gpu_ctx, oracle, scene_cache, tmp_path, case):
+    scene, desc, keep, s = scene_of(case, gpu_ctx, tmp_path)
+    nl = s.num_lights
+    assert nl > 0
+    # rays aimed at seeded points of the light triangles, from seeded points of the scene: many meet a light first
+    raw, flt = _records(scene.export_bvh())
+    lt = flt[raw[:, 3] < nl]
+    st = scene.stats()
+    rng = np.random.default_rng(41)
+    n = 400
+    lo, hi = np.array(st.boundsMin[:]), np.array(st.boundsMax[:])
+    o = lo + (hi - lo) * rng.uniform(0.05, 0.95, (n, 3))
+    pick = rng.integers(0, len(lt), n)
+    b = rng.uniform(0.05, 0.45, (n, 2))
+    tgt = lt[pick, 0:3] + lt[pick, 4:7] * b[:, :1] + lt[pick, 8:11] * b[:, 1:]
+    rays = np.zeros((n, 8), np.float32)
+    rays[:, 0:3], rays[:, 3], rays[:, 4:7], rays[:, 7] = o, 0.001, tgt - o, 10000.0
+    rt = torch.from_numpy(rays).cuda()
+    before = api.trace_rays(scene, rt, opaque=True)
+    on_light = _np(before.custom_index) < nl
+    on_light &= _np(before.custom_index) >= 0
+    assert on_light.sum() > n // 10, "the rays must meet the lights"
+    masks = np.full(desc.numInstances, 0xff, np.uint8)
+    for i in range(desc.numInstances):
+        if desc.instances[i].customIndex < nl:
+            masks[i] = 0xfe                                   # bit 0 cleared on the emitters
+    scene.set_instance_masks(masks)
+    after = api.trace_rays(scene, rt, opaque=True, cull_mask=0x01)
+    cands = all_hits(oracle, scene.export_bvh(), rays)
+    exp, occ = filtered(cands, rays, by_custom(desc, masks), 0x01)
+    assert_hits(after, exp, f"{case}: bounce rays off the emitters")
+    ci = _np(after.custom_index)
+    assert not ((ci >= 0) & (ci < nl)).any(), "a light customIndex came back"
+    assert (ci[on_light] != _np(before.custom_index)[on_light]).all()
+    assert (_np(after.t)[on_light] > _np(before.t)[on_light]).all(), "what lies behind the light"
+    assert torch.equal(api.trace_rays(scene, rt, opaque=True).hits, before.hits), "the unmasked query ignores the masks"
+    assert torch.equal(api.trace_rays(scene, rt, opaque=True, cull_mask=0xfe).hits, before.hits), "a mask that meets the lights' other bits sees them"
+
+
+# ---- 5. hints over masked leaves -----------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("case", ["textured_room", "sponza_mixed"])
+def test_hinted_light_rays_with_the_hits_own_instance_masked_out(gpu_ctx, scene_cache, tmp_path, case):
+    scene, desc, keep, s = scene_of(case, gpu_ctx, tmp_path)
+    W, H = 160, 100
+    rays = api.camera_rays(gpu_ctx, s.camera, W, H, 1)
+    hits = api.trace_rays(scene, rays)
+    lp = api.make_light_params(s.num_lights, 3, 0, W, 1)
+    Q = api.light_slots(scene, lp)
+    lr, leaves = api.light_rays(scene, rays, hits, lp, hints=True)
+    assert int((leaves != 0).sum()) > 0
+    masks = (1 << (np.arange(desc.numInstances) % 8)).astype(np.uint8)      # instance i owns bit i mod 8
+    scene.set_instance_masks(masks)
+    cm = by_custom(desc, masks)
+    ci = _np(hits.custom_index).astype(np.int64)
+    own = np.where(ci >= 0, cm[np.clip(ci, 0, len(cm) - 1)], 0)
+    rm = np.repeat((0xff & ~own).astype(np.uint8), Q)                         # a shadow ray does not see the instance it starts on
+    rmt = torch.from_numpy(rm).cuda()
+    for opaque in (False, True):
+        dense = api.trace_rays(scene, lr, any_hit=True, opaque=opaque, ray_masks=rmt, collect_stats=True)
+        plain = api.trace_occlusion(scene, lr, opaque=opaque, ray_masks=rmt)
+        hinted = api.trace_occlusion(scene, lr, opaque=opaque, ray_masks=rmt, start_leaves=leaves)
+        counted = api.trace_occlusion(scene, lr, opaque=opaque, ray_masks=rmt, start_leaves=leaves, collect_stats=True)
+        assert_same_bytes(plain.occluded, dense.occluded, f"{case}: queued")
+        assert_same_bytes(hinted.occluded, dense.occluded, f"{case}: queued hinted, own leaf masked out")
+        assert_same_bytes(counted.occluded, dense.occluded, f"{case}: queued hinted, counting form")
+        unmasked = api.trace_rays(scene, lr, any_hit=True, opaque=opaque).occluded
+        assert int((unmasked != dense.occluded).sum()) > 0, "masking the own instance must change some bytes"
+        assert (_np(dense.occluded) <= _np(unmasked)).all()
+        assert counted.stats.numTriTests > 0
+
+
+# ---- 6. deep rays ----------------------------------------------------------------------------------------------------------------
+def test_deep_rays_honour_the_masks_in_both_tails(gpu_ctx, oracle):
+    """the scene of test_deep_rays_take_the_tail_kernel.  From the head its camera rays outgrow k_query's LDS stack (closest hit, nearest
+    child first); from the wall end, looking back, they graze the whole row and outgrow the any-hit walk's (tests/test_gpu_occlusion.py).
+    Rays that graze 2^19 coplanar triangles are what no float64 prefilter can be conservative about, so the brute force here is the one
+    those two tests use for this scene — the oracle's O(N) loop over every triangle (bvh=None: rtr_mt_intersect, the function oracle_mt
+    calls) — run on the scene with the masked-out instances moved out of every ray's reach: the filter, applied to the geometry."""
+    d, keep, scene, cam = _deep_scene(gpu_ctx)
+    inst = keep[3]
+    W, H, S = 16, 8, 1
+    end = float(1 << 19) * 0.01
+    back = host.Camera(0.004, (end + 0.5, -0.995, 0.0), (0.2 * end, -1.0, 0.0), (0.0, 1.0, 0.0), W, H).getGPUData()
+    rays = torch.cat([api.camera_rays(gpu_ctx, c, W, H, S) for c in (cam, back)])
+    masks = [0x02, 0x01]                                                    # the wall, the row of 2^19 triangles
+    scene.set_instance_masks(np.array(masks, np.uint8))
+    p = api.make_params(W, H, spp=S)
+    seen = set()
+    for cull in (0x01, 0x02, 0x03):
+        for i in range(2):
+            inst[i].transform[7] = 0.0 if masks[i] & cull else 1.0e7      # y translation: far beyond tmax = 10000
+        try:
+            parts = [oracle.primary_hits(d, c, p, bvh=None, threads=16) for c in (cam, back)]
+        finally:
+            for i in range(2):
+                inst[i].transform[7] = 0.0
+        t, u, v, cu, pr = (np.concatenate([x[k] for x in parts]) for k in range(5))
+        exp = (np.where(cu == MISS, np.float32(10000.0), t), u, v, cu.astype(np.int64), pr.astype(np.int64))
+        occ = (cu != MISS).astype(np.uint8)
+        seen |= set(np.unique(exp[3]).tolist())
+        r = api.trace_rays(scene, rays, collect_stats=True, cull_mask=cull)
+        assert r.stats.tailRays > 0, "the rays must go through k_query_tail"
+        assert_hits(r, exp, f"deep rays, cull {cull:#x}")
+        assert_hits(api.trace_rays(scene, rays, cull_mask=cull), exp, f"deep rays, cull {cull:#x}, timed form")
+        a = api.trace_rays(scene, rays, any_hit=True, collect_stats=True, cull_mask=cull)
+        assert_same_bytes(a.occluded, occ, f"deep rays, dense any, cull {cull:#x}")
+        assert_same_bytes(api.trace_rays(scene, rays, any_hit=True, cull_mask=cull).occluded, occ, f"deep rays, dense any, timed, cull {cull:#x}")
+        q = api.trace_occlusion(scene, rays, collect_stats=True, cull_mask=cull)
+        assert q.stats.tailRays > 0, "the rays must go through the queued route's tail"
+        assert_same_bytes(q.occluded, occ, f"deep rays, queued, cull {cull:#x}")
+        assert_same_bytes(api.trace_occlusion(scene, rays, cull_mask=cull).occluded, occ, f"deep rays, queued, timed, cull {cull:#x}")
+        if cull == 0x01:
+            assert not (exp[3] == 0).any(), "the wall is masked out"
+        else:
+            assert (exp[3] == 0).any(), "rays end on the wall"
+    assert {0, MISS} <= seen
+
+
+# ---- 7. persistence and isolation ----------------------------------------------------------------------------------------------
+def test_masks_survive_refits_and_nothing_else_sees_them(gpu_ctx, oracle, scene_cache, tmp_path):
+    s = scenes.cornell_box(96, 64, ltc=scenes.shipped_ltc())
+    scene = api.Scene(gpu_ctx, s.desc)
+    st = scene.stats()
+    frame = api.Frame(gpu_ctx, 96, 64, 0xff)
+    p = api.make_params(96, 64, spp=2, shadow_rays=3, images=A.IMAGES_RAYGEN5)
+    rays = mixed_rays(st, 1500, 21, 1500.0)
+    rt = torch.from_numpy(rays).cuda()
+
+    def snapshot():
+        api.render(scene, s.camera, s.scene_info(0), p, frame)
+        imgs = [frame.download(k).copy() for k in (0, 1, 2, 6, 7)]
+        lrays = camera_light_rays(gpu_ctx, scene, s, 96, 64, 0)[3]
+        return imgs, api.trace_rays(scene, rt).hits.clone(), api.trace_rays(scene, rt, any_hit=True).occluded.clone(), \
+            api.trace_occlusion(scene, lrays).occluded.clone(), lrays.clone()
+
+    before = snapshot()
+    flags0 = _records(scene.export_bvh())[0][:, 11].copy()
+    assert (scene.instance_masks() == 0xff).all()
+    masks = seeded_masks(s.desc.numInstances, 8)
+    scene.set_instance_masks(masks)
+    assert (scene.instance_masks() == masks).all()
+    after = snapshot()
+    for a, b in zip(before[0], after[0]):
+        assert (a == b).all(), "rtr_render must ignore the masks"
+    for a, b in zip(before[1:], after[1:]):
+        assert torch.equal(a, b), "the unmasked queries must ignore the masks"
+    raw = _records(scene.export_bvh())[0]
+    cm = by_custom(s.desc, masks)
+    assert ((raw[:, 11] & 1) == (flags0 & 1)).all() and ((raw[:, 11] >> 8) == (~cm[raw[:, 3]] & 0xff)).all()
+    # a scene made like this one starts at 0xff, records included
+    twin = api.Scene(gpu_ctx, s.desc, like=scene)
+    assert (twin.instance_masks() == 0xff).all()
+    assert not (_records(twin.export_bvh())[0][:, 11] & ~np.uint32(1)).any()
+    assert torch.equal(api.trace_rays(twin, rt, cull_mask=0x01).hits, before[1])
+    # after a refit the masks still hold
+    inst = [A.RtrInstance.from_buffer_copy(s.desc.instances[i]) for i in range(s.desc.numInstances)]
+    for k, i in enumerate(inst):
+        if i.customIndex >= s.num_lights:
+            i.transform[3] += 40.0 * (k % 3)
+            i.transform[7] -= 25.0 * (k % 2)
+    scene.update_instances(inst)
+    assert (scene.instance_masks() == masks).all()
+    # the refit carried the mask bits into the records it rewrote: the renderer still reads bit 0 alone
+    api.render(scene, s.camera, s.scene_info(0), p, frame)
+    moved = [frame.download(k).copy() for k in (0, 1, 2, 6, 7)]
+    plain = api.Scene(gpu_ctx, s.desc)
+    plain.update_instances(inst)
+    api.render(plain, s.camera, s.scene_info(0), p, frame)
+    for k, img in zip((0, 1, 2, 6, 7), moved):
+        assert (frame.download(k) == img).all(), "rtr_render must ignore the masks a refit carried over"
+    bvh = scene.export_bvh()
+    raw = _records(bvh)[0]
+    assert ((raw[:, 11] >> 8) == (~cm[raw[:, 3]] & 0xff)).all() and ((raw[:, 11] & 1) == 0).all()
+    cands = all_hits(oracle, bvh, rays)
+    for cull in (0xff, 0x0f, 0x40):
+        exp, occ = filtered(cands, rays, cm, cull)
+        assert_hits(api.trace_rays(scene, rt, cull_mask=cull), exp, f"after update_instances, cull {cull:#x}")
+        assert_same_bytes(api.trace_occlusion(scene, rt, cull_mask=cull).occluded, occ, f"after update_instances, queued, cull {cull:#x}")
+    unm, _ = filtered(cands, rays, np.full(len(cm), 0xff, np.int64), 0xff)
+    assert_hits(api.trace_rays(scene, rt), unm, "after update_instances, unmasked")
+    # setting 0xff everywhere gives the records a new scene has
+    scene.set_instance_masks(np.full(s.desc.numInstances, 0xff, np.uint8))
+    assert not (_records(scene.export_bvh())[0][:, 11] & ~np.uint32(1)).any()
+
+
+def test_masks_on_a_device_built_scene_survive_a_refit(gpu_ctx, oracle, scene_cache, tmp_path):
+    scene, desc, keep, s = scene_of("textured_room", gpu_ctx, tmp_path, A.BUILD_DEVICE_LBVH)
+    st = scene.stats()
+    masks = seeded_masks(desc.numInstances, 12)
+    scene.set_instance_masks(masks)
+    inst = [A.RtrInstance.from_buffer_copy(desc.instances[i]) for i in range(desc.numInstances)]
+    for k, i in enumerate(inst):
+        i.transform[3] += 0.25 * (k % 3)
+    scene.update_instances(inst)
+    cm = by_custom(desc, masks)
+    bvh = scene.export_bvh()
+    raw = _records(bvh)[0]
+    assert ((raw[:, 11] >> 8) == (~cm[raw[:, 3]] & 0xff)).all() and (raw[:, 11] & 1).any()
+    diag = float(np.linalg.norm(np.array(st.boundsMax[:]) - np.array(st.boundsMin[:])))
+    rays = mixed_rays(st, 1000, 4, diag)
+    cands = all_hits(oracle, bvh, rays)
+    exp, occ = filtered(cands, rays, cm, 0x33)
+    rt = torch.from_numpy(rays).cuda()
+    assert_hits(api.trace_rays(scene, rt, opaque=True, cull_mask=0x33), exp, "device-built, refitted")
+    assert_same_bytes(api.trace_occlusion(scene, rt, opaque=True, cull_mask=0x33).occluded, occ, "device-built, refitted, queued")
+
+
+# ---- 8. alpha-tested geometry ---------------------------------------------------------------------------------------------------
+def test_a_masked_out_alpha_tested_layer_counts_no_alpha_tests(gpu_ctx, scene_cache, tmp_path):
+    scene, desc, keep, s = scene_of("textured_room", gpu_ctx, tmp_path)
+    raw = _records(scene.export_bvh())[0]
+    alpha_customs = set(np.unique(raw[(raw[:, 11] & 1) != 0, 3]).tolist())
+    assert alpha_customs
+    masks = np.array([0x02 if desc.instances[i].customIndex in alpha_customs else 0x01 for i in range(desc.numInstances)], np.uint8)
+    rays = api.camera_rays(gpu_ctx, s.camera, 160, 100, 1)
+    lr = camera_light_rays(gpu_ctx, scene, s, 160, 100, 0)[3]
+    scene.set_instance_masks(masks)
+    for r in (rays, lr):
+        for route in ("closest", "dense any", "queued"):
+            def run(**kw):
+                if route == "queued":
+                    return api.trace_occlusion(scene, r, collect_stats=True, **kw)
+                return api.trace_rays(scene, r, any_hit=route == "dense any", collect_stats=True, **kw)
+            assert run().stats.numAlphaTests > 0, f"{route}: the unmasked query runs the opacity test"
+            off = run(cull_mask=0x01)
+            assert off.stats.numAlphaTests == 0, f"{route}: a masked-out record must not be alpha-tested"
+            assert off.stats.numTriTests > 0
+            assert run(cull_mask=0x02).stats.numAlphaTests > 0
+
+
+# ---- 9. invalid arguments ---------------------------------------------------------------------------------------------------------
+def test_invalid_arguments(gpu_ctx, scene_cache):
+    s = scenes.cornell_box(64, 64)
+    scene = api.Scene(gpu_ctx, s.desc)
+    lib, ctx = gpu_ctx.lib, gpu_ctx.h
+    ni = s.desc.numInstances
+    m = np.full(ni, 0xff, np.uint8)
+    mp = m.ctypes.data_as(A.VP)
+    assert lib.rtr_scene_set_instance_masks(scene.h, None, ni) == INVALID and b"null" in lib.rtr_last_error()
+    assert lib.rtr_scene_set_instance_masks(scene.h, mp, ni + 1) == INVALID and b"instances" in lib.rtr_last_error()
+    assert lib.rtr_scene_set_instance_masks(scene.h, mp, ni - 1) == INVALID
+    assert lib.rtr_scene_get_instance_masks(scene.h, None, ni) == INVALID and b"null" in lib.rtr_last_error()
+    assert lib.rtr_scene_get_instance_masks(scene.h, mp, ni + 1) == INVALID and b"instances" in lib.rtr_last_error()
+    assert lib.rtr_scene_set_instance_masks(scene.h, mp, ni) == 0
+    rays = api.camera_rays(gpu_ctx, s.camera, 8, 8, 1)
+    hits = torch.empty((64, 8), dtype=torch.int32, device="cuda")
+    occ = torch.empty(64 + 16, dtype=torch.uint8, device="cuda")
+    rm = torch.full((64 + 1,), 0xff, dtype=torch.uint8, device="cuda")
+    need = api.occlusion_scratch_bytes(lib, 64)
+    scratch = torch.empty(need + 16, dtype=torch.uint8, device="cuda")
+    rp, hp, op, sp = A.VP(rays.data_ptr()), A.VP(hits.data_ptr()), A.VP(occ.data_ptr()), A.VP(scratch.data_ptr())
+    # the cull mask has 8 bits
+    assert lib.rtr_trace_rays_masked(ctx, scene.h, rp, None, 64, 0, 0x100, hp, None, None) == INVALID
+    assert b"cullMask" in lib.rtr_last_error() and b"rtr_trace_rays_masked" in lib.rtr_last_error()
+    assert lib.rtr_trace_rays_masked_async(ctx, scene.h, rp, None, 64, 0, 0x80000000, hp, None) == INVALID and b"cullMask" in lib.rtr_last_error()
+    assert lib.rtr_trace_occlusion_masked(ctx, scene.h, rp, None, None, 64, 0, 0x1ff, sp, need, op, None) == INVALID
+    assert b"cullMask" in lib.rtr_last_error() and b"rtr_trace_occlusion_masked" in lib.rtr_last_error()
+    assert lib.rtr_trace_occlusion_masked_async(ctx, scene.h, rp, None, None, 64, 0, 0x100, sp, need, op) == INVALID and b"cullMask" in lib.rtr_last_error()
+    # the rules of the unmasked calls
+    assert lib.rtr_trace_rays_masked(ctx, scene.h, None, None, 64, 0, 0xff, hp, None, None) == INVALID and b"rays is null" in lib.rtr_last_error()
+    assert lib.rtr_trace_rays_masked(ctx, scene.h, rp, None, 64, 0, 0xff, None, op, None) == INVALID and b"hits" in lib.rtr_last_error()
+    assert lib.rtr_trace_rays_masked(ctx, scene.h, rp, None, 64, A.QUERY_ANY, 0xff, hp, None, None) == INVALID and b"occluded" in lib.rtr_last_error()
+    assert lib.rtr_trace_rays_masked(ctx, scene.h, A.VP(rays.data_ptr() + 4), None, 64, 0, 0xff, hp, None, None) == INVALID and b"aligned" in lib.rtr_last_error()
+    assert lib.rtr_trace_rays_masked(ctx, scene.h, rp, None, 64, 4, 0xff, hp, None, None) == INVALID and b"flag" in lib.rtr_last_error()
+    assert lib.rtr_trace_rays_masked(None, scene.h, rp, None, 64, 0, 0xff, hp, None, None) == INVALID
+    assert lib.rtr_trace_occlusion_masked(ctx, scene.h, None, None, None, 64, 0, 0xff, sp, need, op, None) == INVALID and b"rays is null" in lib.rtr_last_error()
+    assert lib.rtr_trace_occlusion_masked(ctx, scene.h, rp, None, None, 64, 0, 0xff, None, need, op, None) == INVALID and b"scratch is null" in lib.rtr_last_error()
+    assert lib.rtr_trace_occlusion_masked(ctx, scene.h, rp, None, None, 64, 0, 0xff, sp, need - 16, op, None) == INVALID and b"scratch" in lib.rtr_last_error()
+    assert lib.rtr_trace_occlusion_masked(ctx, scene.h, rp, None, None, 64, 0, 0xff, sp, need, A.VP(occ.data_ptr() + 1), None) == INVALID and b"aligned" in lib.rtr_last_error()
+    assert lib.rtr_trace_occlusion_masked(ctx, scene.h, rp, A.VP(hits.data_ptr() + 2), None, 64, 0, 0xff, sp, need, op, None) == INVALID and b"startLeaves" in lib.rtr_last_error()
+    assert lib.rtr_trace_occlusion_masked(ctx, scene.h, rp, None, None, 64, 8, 0xff, sp, need, op, None) == INVALID and b"flag" in lib.rtr_last_error()
+    # no rays: nothing to do; ray masks need no alignment
+    assert lib.rtr_trace_rays_masked(ctx, scene.h, None, None, 0, 0, 0xff, None, None, None) == 0
+    assert lib.rtr_trace_occlusion_masked(ctx, scene.h, None, None, None, 0, 0, 0xff, None, 0, None, None) == 0
+    ref = api.trace_rays(scene, rays)
+    assert lib.rtr_trace_rays_masked(ctx, scene.h, rp, A.VP(rm.data_ptr() + 1), 64, 0, 0xff, hp, None, None) == 0
+    assert torch.equal(hits, ref.hits)
+    assert lib.rtr_trace_occlusion_masked(ctx, scene.h, rp, None, A.VP(rm.data_ptr() + 1), 64, 0, 0xff, sp, need, op, None) == 0
+    assert torch.equal(occ[:64], api.trace_rays(scene, rays, any_hit=True).occluded)
+    if torch.cuda.device_count() > 1:
+        other = api.Context(1)
+        assert lib.rtr_trace_rays_masked(other.h, scene.h, rp, None, 64, 0, 0xff, hp, None, None) == INVALID
+        other.close()
+    # the Python layer refuses before anything is launched
+    for bad in (rm[:64].to(torch.int32), rm[:63], rm[:64].cpu(), torch.zeros((64, 2), dtype=torch.uint8, device="cuda")[:, 0]):
+        with pytest.raises(ValueError):
+            api.trace_rays(scene, rays, ray_masks=bad)
+        with pytest.raises(ValueError):
+            api.trace_occlusion(scene, rays, ray_masks=bad)
+    for bad in (np.zeros(ni + 1, np.float32), np.full(ni, 256), np.zeros((ni, 1), np.uint8)):
+        with pytest.raises(ValueError):
+            scene.set_instance_masks(bad)
+    with pytest.raises(api.RtrError):
+        scene.set_instance_masks(np.zeros(ni + 1, np.uint8))
+
+
+# ---- the composed stage -----------------------------------------------------------------------------------------------------------
+def test_direct_light_passes_the_shadow_cull_mask_to_every_route(gpu_ctx, scene_cache):
+    s = scenes.cornell_box(96, 64)
+    scene = api.Scene(gpu_ctx, s.desc)
+    rays = api.camera_rays(gpu_ctx, s.camera, 96, 64, 1)
+    lp = api.make_light_params(s.num_lights, 3, 0, 96, 1)
+    base = api.direct_light(scene, rays, params=lp).raw
+    masks = np.full(s.desc.numInstances, 0xff, np.uint8)
+    masks[s.num_lights + 2:] = 0xfe                       # some objects cast no shadow for rays with mask 0x01
+    scene.set_instance_masks(masks)
+    out = {}
+    for route in ("dense", "queued", "queued_own_leaf"):
+        assert torch.equal(api.direct_light(scene, rays, params=lp, occlusion=route).raw, base), f"{route}: None is the unmasked call"
+        assert torch.equal(api.direct_light(scene, rays, params=lp, occlusion=route, shadow_cull_mask=0xff).raw, base)
+        out[route] = api.direct_light(scene, rays, params=lp, occlusion=route, shadow_cull_mask=0x01).raw
+    assert torch.equal(out["dense"], out["queued"]) and torch.equal(out["dense"], out["queued_own_leaf"])
+    assert not torch.equal(out["dense"], base), "non-casters must brighten some pixels"
+    assert bool((out["dense"][:, 0:3] >= base[:, 0:3]).all())

@@ -360,10 +360,39 @@ int  rtr_deinterleave_images(rtr_ctx* ctx, const void* gathered, uint32_t numIma
  *                      gl_RayFlagsTerminateOnFirstHitEXT | gl_RayFlagsSkipClosestHitShaderEXT (raygen.rgen:226-231, :299-303, the
  *                      shadow rays).  Which triangle the walk meets first depends on the walk, so no hit record is defined.
  *   RTR_QUERY_OPAQUE   skip the opacity-map test (opacity.rahit:31-64) as gl_RayFlagsOpaqueEXT does; without it alpha-tested
- *                      geometry is treated exactly as the renderer treats it. */
+ *                      geometry is treated exactly as the renderer treats it.
+ * Culling flags, with Vulkan's own bit values (bit values 4, 8 and everything above 0x80 are refused).  They are per launch and are
+ * taken by every query entry point that has `flags`: rtr_trace_rays[_masked][_async], rtr_trace_occlusion[_hinted|_masked][_async].
+ *   RTR_QUERY_CULL_BACK_FACING / RTR_QUERY_CULL_FRONT_FACING   gl_RayFlagsCullBackFacingTrianglesEXT / ...CullFrontFacing...: a triangle
+ *                      is FRONT-facing for a ray iff the ray arrives on the side its as-wound geometric normal points to — the normal
+ *                      rtr_hit_surfaces reports as RtrSurface::geomNormal = normalize(nmat * cross(p1 - p0, p2 - p0)).  Facing is decided
+ *                      in object space, as in Vulkan, so a mirrored instance (negative determinant of its 3x3 transform) does not change
+ *                      it.  In the kernels' arithmetic: with a = rtr_dot(e1, rtr_cross(d, e2)), the fp32 determinant rtr_mt_intersect
+ *                      computes on the world-space record, front = (a > 0) XOR mirrored(instance).  An accepted hit has
+ *                      |a| >= RTR_MT_EPSILON, so the sign is never ambiguous and every walk gives the same answer.  mirrored() is
+ *                      evaluated on the host, in double, by rtr_scene_create, rtr_scene_create_like and rtr_scene_update_instances (it
+ *                      follows a refit) and kept in a per-customIndex device table beside the transforms, NOT in the triangle records:
+ *                      their bytes are what they were.  Light instances follow the same rule (so a one-sided emitter,
+ *                      RtrAreaLightInfo::isTwoSided == 0, can be passed through from behind).
+ *   RTR_QUERY_CULL_OPAQUE / RTR_QUERY_CULL_NO_OPAQUE   gl_RayFlagsCullOpaqueEXT / gl_RayFlagsCullNoOpaqueEXT: a record is NON-OPAQUE iff
+ *                      its flags bit 0 (alpha-tested) is set and RTR_QUERY_OPAQUE is not given, otherwise opaque; CULL_OPAQUE drops the
+ *                      opaque records, CULL_NO_OPAQUE the non-opaque ones: a caller traces only the alpha-tested layer, or only the rest.
+ * Refused (RTR_ERR_INVALID_ARGUMENT, the message names the flags), as Vulkan forbids them: both face flags together; more than one of
+ * RTR_QUERY_OPAQUE, RTR_QUERY_CULL_OPAQUE and RTR_QUERY_CULL_NO_OPAQUE.
+ * Order, as in Vulkan: culling comes before the any-hit shader — a culled record runs no opacity-map test and adds nothing to
+ * numAlphaTests; it was fetched, so it counts in numTriTests (as a record the cull mask drops does).  The closest hit is the
+ * (t, customIndex, primitiveId)-minimal hit among the records that survive the cull mask, the facing cull, the opacity cull and the
+ * opacity-map test; an occlusion byte is 1 iff such a record exists, the same byte on every route (dense any-hit, queued, queued with
+ * hints: a hinted leaf whose hits are all culled does not stop the ray), and the rays finished over the BVH2 honour the flags too.
+ * Without these bits every entry point launches the kernels it launched before, with the same results and counters; a call that has
+ * them launches the filtered (cull-mask) forms of the kernels, with mask 0xff where the call brings none.  rtr_render ignores all of it. */
 #define RTR_QUERY_CLOSEST 0u
 #define RTR_QUERY_ANY     1u
 #define RTR_QUERY_OPAQUE  2u
+#define RTR_QUERY_CULL_BACK_FACING  0x10u   /* gl_RayFlagsCullBackFacingTrianglesEXT  */
+#define RTR_QUERY_CULL_FRONT_FACING 0x20u   /* gl_RayFlagsCullFrontFacingTrianglesEXT */
+#define RTR_QUERY_CULL_OPAQUE       0x40u   /* gl_RayFlagsCullOpaqueEXT               */
+#define RTR_QUERY_CULL_NO_OPAQUE    0x80u   /* gl_RayFlagsCullNoOpaqueEXT             */
 
 typedef struct rtr_query_stats {
     /* exact work counters of the query (the counting form of the kernels), counted as rtr_frame_stats counts the renderer's camera

@@ -153,6 +153,8 @@ IMAGES_RAYGEN5 = IMG_BIT(0) | IMG_BIT(1) | IMG_BIT(2) | IMG_BIT(6) | IMG_BIT(7)
 IMAGES_DENOISE = IMG_BIT(3) | IMG_BIT(4) | IMG_BIT(5)
 BUILD_HOST_SAH, BUILD_DEVICE_LBVH = 0, 1
 QUERY_CLOSEST, QUERY_ANY, QUERY_OPAQUE = 0, 1, 2
+# the culling ray flags of the queries, at Vulkan's bit values (include/rtr.h RTR_QUERY_CULL_*)
+QUERY_CULL_BACK_FACING, QUERY_CULL_FRONT_FACING, QUERY_CULL_OPAQUE, QUERY_CULL_NO_OPAQUE = 0x10, 0x20, 0x40, 0x80
 SURFACE_MISS, SURFACE_OBJECT, SURFACE_LIGHT, SURFACE_INVALID = 0, 1, 2, 3
 LIGHT_SHADOWED, LIGHT_UNSHADOWED, LIGHT_ANALYTIC = 1, 2, 4
 

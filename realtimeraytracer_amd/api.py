@@ -314,7 +314,23 @@ def _cull_mask_args(torch, who, cull_mask, ray_masks, n, dev):
     return rm, cm
 
 
-def trace_rays(scene, rays, any_hit=False, opaque=False, collect_stats=False, ctx=None, asynchronous=False, cull_mask=None, ray_masks=None):
+def _ray_flags(who, ray_flags, opaque):
+    """the extra flag bits of a query (A.QUERY_CULL_*), checked for the combinations the interface refuses — both face flags; more than
+    one of opaque, QUERY_CULL_OPAQUE and QUERY_CULL_NO_OPAQUE — before anything is launched.  Unknown bits are left to the library, which
+    refuses them.  QUERY_ANY is not taken here: trace_rays has any_hit for it."""
+    f = int(ray_flags)
+    if f < 0 or f > 0xffffffff:
+        raise ValueError(f"{who}: ray_flags must be a 32-bit mask, got {ray_flags!r}")
+    if f & A.QUERY_ANY:
+        raise ValueError(f"{who}: QUERY_ANY is not a ray flag here (trace_rays(any_hit=True) or trace_occlusion)")
+    if (f & A.QUERY_CULL_BACK_FACING) and (f & A.QUERY_CULL_FRONT_FACING):
+        raise ValueError(f"{who}: QUERY_CULL_BACK_FACING and QUERY_CULL_FRONT_FACING exclude each other")
+    if (1 if opaque or f & A.QUERY_OPAQUE else 0) + (1 if f & A.QUERY_CULL_OPAQUE else 0) + (1 if f & A.QUERY_CULL_NO_OPAQUE else 0) > 1:
+        raise ValueError(f"{who}: at most one of opaque (QUERY_OPAQUE), QUERY_CULL_OPAQUE and QUERY_CULL_NO_OPAQUE")
+    return f
+
+
+def trace_rays(scene, rays, any_hit=False, opaque=False, collect_stats=False, ctx=None, asynchronous=False, cull_mask=None, ray_masks=None, ray_flags=0):
     """rtr_trace_rays: rays is a contiguous float32 (N, 8) tensor on the context's device — rows are RtrRay (origin, tmin, direction,
     tmax) — whose results come back as device tensors without a copy, or a numpy array, which is copied to the device and whose results
     come back as numpy.  any_hit: occlusion only (RTR_QUERY_ANY); opaque: no opacity-map test (RTR_QUERY_OPAQUE).  ctx: the context whose
@@ -323,7 +339,11 @@ def trace_rays(scene, rays, any_hit=False, opaque=False, collect_stats=False, ct
     form, synchronous.  Wrong shape, dtype, device or layout raises ValueError before anything is launched.
     cull_mask (8 bits) and ray_masks (one uint8 per ray: a device tensor, or a numpy array that is uploaded): traceRayEXT's cullMask —
     ray k sees the instances whose mask (Scene.set_instance_masks) meets cull_mask & ray_masks[k]; with either given the call is
-    rtr_trace_rays_masked, with both None it is rtr_trace_rays exactly as before."""
+    rtr_trace_rays_masked, with both None it is rtr_trace_rays exactly as before.
+    ray_flags: the culling flags of traceRayEXT's rayFlags, or-ed — A.QUERY_CULL_BACK_FACING or A.QUERY_CULL_FRONT_FACING (facing by the
+    as-wound object-space normal, RtrSurface.geom_normal's side), A.QUERY_CULL_OPAQUE or A.QUERY_CULL_NO_OPAQUE (only the alpha-tested
+    layer / only the rest) — for the whole launch; ValueError for the combinations Vulkan forbids.  0: the call as before."""
+    ray_flags = _ray_flags("trace_rays", ray_flags, opaque)
     torch = _torch()
     ctx = ctx or scene.ctx
     dev = torch.device("cuda", ctx.device)
@@ -347,7 +367,7 @@ def trace_rays(scene, rays, any_hit=False, opaque=False, collect_stats=False, ct
     if asynchronous and ctx.get_stream() != torch.cuda.current_stream(dev).cuda_stream:
         raise ValueError("trace_rays: an asynchronous query needs the context on torch's current stream (ctx.set_stream)")
     n = int(r.shape[0])
-    flags = (A.QUERY_ANY if any_hit else A.QUERY_CLOSEST) | (A.QUERY_OPAQUE if opaque else 0)
+    flags = (A.QUERY_ANY if any_hit else A.QUERY_CLOSEST) | (A.QUERY_OPAQUE if opaque else 0) | ray_flags
     hits = occ = None
     if any_hit:
         occ = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)[:n]
@@ -398,7 +418,7 @@ def occlusion_scratch_bytes(lib, n):
     return int(b.value)
 
 
-def trace_occlusion(scene, rays, opaque=False, collect_stats=False, ctx=None, asynchronous=False, start_leaves=None, cull_mask=None, ray_masks=None):
+def trace_occlusion(scene, rays, opaque=False, collect_stats=False, ctx=None, asynchronous=False, start_leaves=None, cull_mask=None, ray_masks=None, ray_flags=0):
     """rtr_trace_occlusion: the queued occlusion query — the same bytes as trace_rays(any_hit=True), answered by the renderer's any-hit
     machinery (rays binned by direction octant, persistent waves over the 4-wide tree).  rays, opaque, ctx, asynchronous, collect_stats
     and the QueryResult (occluded, stats) as in trace_rays.  The query's scratch is a uint8 device tensor kept on the context and grown
@@ -406,7 +426,9 @@ def trace_occlusion(scene, rays, opaque=False, collect_stats=False, ctx=None, as
     start_leaves (rtr_trace_occlusion_hinted): one int32 start hint per ray — light_rays(hints=True)'s or hit_leaves' — as an (N,) int32
     device tensor or numpy array like the rays; any value is safe and none changes a byte, only the work.  None: the unhinted query.
     cull_mask, ray_masks: as in trace_rays; with either given the call is rtr_trace_occlusion_masked (hinted or not), with both None the
-    entry points called before."""
+    entry points called before.  ray_flags: the culling flags, as in trace_rays; every route writes the same bytes, and a hinted leaf
+    whose hits are all culled does not stop its ray."""
+    ray_flags = _ray_flags("trace_occlusion", ray_flags, opaque)
     torch = _torch()
     ctx = ctx or scene.ctx
     dev = torch.device("cuda", ctx.device)
@@ -449,7 +471,7 @@ def trace_occlusion(scene, rays, opaque=False, collect_stats=False, ctx=None, as
     occ = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)[:n]
     if not asynchronous and ctx.get_stream() != torch.cuda.current_stream(dev).cuda_stream:
         torch.cuda.current_stream(dev).synchronize()        # the rays (and the outputs' memory) are ready for the context's stream
-    flags = A.QUERY_OPAQUE if opaque else 0
+    flags = (A.QUERY_OPAQUE if opaque else 0) | ray_flags
     args = (n, flags, A.VP(scratch.data_ptr()), scratch.numel(), A.VP(occ.data_ptr())) if n else (0, flags, None, 0, None)
     rp = A.VP(r.data_ptr()) if n else None
     out = QueryResult()
@@ -746,13 +768,16 @@ def tonemap_pack(ctx, radiance, asynchronous=False):
     return out
 
 
-def direct_light(scene, rays, hits=None, params=None, seeds=None, ctx=None, max_ray_bytes=256 << 20, occlusion="dense", shadow_cull_mask=None):
+def direct_light(scene, rays, hits=None, params=None, seeds=None, ctx=None, max_ray_bytes=256 << 20, occlusion="dense", shadow_cull_mask=None, shadow_ray_flags=0):
     """The composed stage: closest hit (when hits is None) -> light_rays -> trace_rays(any_hit=True) -> shade_hits, in chunks of hits
     so that a chunk's light rays (n * Q * 32 bytes) stay within max_ray_bytes — a 1080p frame at Q = 7 would be 464 MB of rays at once.
     Chunks do not change the result.  occlusion: "dense" (trace_rays, the default), "queued" (trace_occlusion) or "queued_own_leaf"
     (light_rays(hints=True) and trace_occlusion(start_leaves=...): the renderer's own walk, own-leaf rule included): the same bytes.  rays: a float32 (N, 8) device tensor; hits: a QueryResult, (N, 8) int32 records, or None;
     params: make_light_params(...).  shadow_cull_mask: the cull mask of the shadow rays (instances whose mask does not meet it cast no
-    shadow), passed to whichever occlusion route is selected; None: the unmasked calls, as before.  Returns a RadianceResult on the device."""
+    shadow), passed to whichever occlusion route is selected; None: the unmasked calls, as before.  shadow_ray_flags: the culling flags
+    (A.QUERY_CULL_*, as trace_rays' ray_flags) of the shadow rays, passed to that route likewise; 0: as before.  Returns a RadianceResult
+    on the device."""
+    shadow_ray_flags = _ray_flags("direct_light", shadow_ray_flags, False)
     if occlusion not in ("dense", "queued", "queued_own_leaf"):
         raise ValueError(f"direct_light: occlusion must be 'dense', 'queued' or 'queued_own_leaf', got {occlusion!r}")
     if params is None:
@@ -777,10 +802,10 @@ def direct_light(scene, rays, hits=None, params=None, seeds=None, ctx=None, max_
         r, h = rays[a:b], hits[a:b]
         if occlusion == "queued_own_leaf":
             lr, leaves = light_rays(scene, r, h, params, seeds=sd, ctx=ctx, hints=True)
-            occ = trace_occlusion(scene, lr, ctx=ctx, start_leaves=leaves, cull_mask=shadow_cull_mask).occluded
+            occ = trace_occlusion(scene, lr, ctx=ctx, start_leaves=leaves, cull_mask=shadow_cull_mask, ray_flags=shadow_ray_flags).occluded
         else:
             lr = light_rays(scene, r, h, params, seeds=sd, ctx=ctx)
-            occ = (trace_occlusion(scene, lr, ctx=ctx, cull_mask=shadow_cull_mask) if occlusion == "queued"
-                   else trace_rays(scene, lr, any_hit=True, ctx=ctx, cull_mask=shadow_cull_mask)).occluded
+            occ = (trace_occlusion(scene, lr, ctx=ctx, cull_mask=shadow_cull_mask, ray_flags=shadow_ray_flags) if occlusion == "queued"
+                   else trace_rays(scene, lr, any_hit=True, ctx=ctx, cull_mask=shadow_cull_mask, ray_flags=shadow_ray_flags)).occluded
         out[a:b] = shade_hits(scene, r, h, params, occ, seeds=sd, ctx=ctx).raw
     return _radiance_result(out, False, torch)

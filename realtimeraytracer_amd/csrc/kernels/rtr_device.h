@@ -39,7 +39,9 @@ struct DeviceScene {
     const float4* lightTris;         /* per light triangle, kLightTriRecord x float4: {P0, area} {P1, pdf} {P2, -} {unit normal, -} in world space (k_light_tris) */
     const uint32_t* lightTriFirst;   /* first record of light l */
     const float* xforms;             /* 12 floats (3x4 row-major object->world) per customIndex */
-    const float* nmats;              /* 12 floats (9 used: transpose(inverse(mat3))) per customIndex */
+    const float* nmats;              /* 12 words per customIndex: 0..8 the floats of transpose(inverse(mat3)); word 9 (kMirroredWord) an INTEGER, 1 iff the
+                                      * instance's 3x3 has a negative determinant (the ray queries' face culling reads it: cull_by_facing; the host writes it
+                                      * with the matrix: rtr_api.cpp set_mirrored_word); 10, 11 unused.  Whoever writes this table keeps word 9. */
     const float* ltc1;               /* 64x64x4 or null */
     const float* ltc2;
     float skyLinear[3];
@@ -247,11 +249,38 @@ __device__ __forceinline__ uint32_t ray_octant(const DeviceScene& sc, rtr_v3 o, 
  * MASKED (the ray queries' cull mask, traceRayEXT's cullMask): rayMask8 is the ray's 8-bit mask in bits 8..15, where a record's flags
  * word holds the COMPLEMENT of its instance's mask (kTriMaskShift): a fetched record none of whose mask bits meets the ray's is skipped
  * before the intersection test — one and-not on a word the lane already holds.  It was fetched, so it is counted.  The forms without
- * MASKED compile to what they were. */
+ * MASKED compile to what they were.
+ * cull (MASKED forms only; the ray queries' RTR_QUERY_CULL_* flags, wave-uniform, 0 for a call that has none): the same kind of filter
+ * in the leaf, see cull_by_opacity / cull_by_facing below.  The flags ride on the MASKED forms — a call with flags and no cull mask
+ * launches them with mask 0xff — so the forms without MASKED are not touched by them either. */
 constexpr uint32_t kTriMaskShift = RTR_TRI_MASK_SHIFT, kTriMaskBits = RTR_TRI_MASK_BITS;
+/* The culling ray flags of the ray queries, at Vulkan's bit values (include/rtr.h RTR_QUERY_CULL_*; rtr_query.hip asserts the match). */
+constexpr uint32_t kCullBackFacing = 0x10u, kCullFrontFacing = 0x20u, kCullOpaque = 0x40u, kCullNoOpaque = 0x80u;
+constexpr uint32_t kCullFacing = kCullBackFacing | kCullFrontFacing, kCullOpacity = kCullOpaque | kCullNoOpaque, kCullAll = kCullFacing | kCullOpacity;
+/* Word 9 of an instance's 12-float slot of DeviceScene::nmats (the matrix fills 0..8): 1 iff the instance's 3x3 transform has a negative
+ * determinant (decided on the host, in double; uploaded with the transforms at create and at every instance update).  Only
+ * cull_by_facing reads it. */
+constexpr uint32_t kMirroredWord = 9u;
+/* gl_RayFlagsCullOpaqueEXT / CullNoOpaqueEXT: a record is non-opaque iff it is alpha-tested (flags bit 0) and the query runs the
+ * opacity-map test (alpha: RTR_QUERY_OPAQUE not given).  Decided from the flags word alone, before the intersection test. */
+__device__ __forceinline__ bool cull_by_opacity(const uint32_t cull, const uint32_t recFlags, const bool alpha) {
+    return (cull & (((recFlags & 1u) != 0u && alpha) ? kCullNoOpaque : kCullOpaque)) != 0u;
+}
+/* gl_RayFlagsCullBackFacingTrianglesEXT / CullFrontFacing, for a candidate that has passed rtr_mt_intersect: the sign of the
+ * determinant that test computed (the same fp32 operations on the same operands: the same value, never within RTR_MT_EPSILON of 0 for an
+ * accepted candidate), turned over for a mirrored instance — front = (a > 0) XOR mirrored: the side the as-wound OBJECT-space normal
+ * points to, Vulkan's rule. */
+__device__ __forceinline__ bool cull_by_facing(const DeviceScene& sc, const uint32_t cull, const rtr_v3 d, const rtr_v3 e1, const rtr_v3 e2, const uint32_t custom) {
+    if ((cull & kCullFacing) == 0u) return false;
+    const float a = rtr_dot(e1, rtr_cross(d, e2));
+    const bool mirrored = (__float_as_uint(sc.nmats[12u * custom + kMirroredWord]) & 1u) != 0u;
+    const bool front = (a > 0.0f) != mirrored;
+    return (cull & (front ? kCullFrontFacing : kCullBackFacing)) != 0u;
+}
 template <bool ANY, bool STATS, int BLOCK, int LIMIT = 0, int OCT = 8, bool ALPHA = true, bool FLAT_TAKE = false, bool MASKED = false>
 __device__ __forceinline__ bool trace(const DeviceScene& sc, int32_t* __restrict__ stack,
-                                      rtr_v3 o, rtr_v3 d, float tmin, float tmax, HitRec& best, LocalStats& st, const uint32_t rayMask8 = 0u) {
+                                      rtr_v3 o, rtr_v3 d, float tmin, float tmax, HitRec& best, LocalStats& st, const uint32_t rayMask8 = 0u,
+                                      const uint32_t cull = 0u) {
     if (STATS) { st.rays++; if (ANY) st.shadow++; else st.primary++; }
     best.custom = RTR_MISS; best.prim = RTR_MISS; best.t = tmax; best.u = 0.f; best.v = 0.f; best.leaf = 0;
     if (!(tmax > tmin)) return false;
@@ -308,10 +337,12 @@ __device__ __forceinline__ bool trace(const DeviceScene& sc, int32_t* __restrict
                 const float4 q2 = make_float4(__uint_as_float(r2.x), __uint_as_float(r2.y), __uint_as_float(r2.z), __uint_as_float(r2.w));
                 if (STATS) { st.tris++; if (ANY) st.shadowTris++; }
                 if (MASKED && (rayMask8 & ~r2.w) == 0u) continue;      /* the instance does not exist for this ray */
+                if (MASKED && cull != 0u && cull_by_opacity(cull, r2.w, ALPHA)) continue;      /* culled before the any-hit test, as in Vulkan */
                 float t, u, v;
                 if (rtr_mt_intersect(o, d, f4xyz(q0), f4xyz(q1), f4xyz(q2), tmin, &t, &u, &v)) {
                     if (t < tmax) {
                         const uint32_t cu = __float_as_uint(q0.w), pr = __float_as_uint(q1.w);
+                        if (MASKED && cull != 0u && cull_by_facing(sc, cull, d, f4xyz(q1), f4xyz(q2), cu)) continue;
                         if (ALPHA && (__float_as_uint(q2.w) & 1u) && !alpha_pass<STATS>(sc, cu, pr, u, v, st)) continue;
                         bool take;
                         if (FLAT_TAKE) {

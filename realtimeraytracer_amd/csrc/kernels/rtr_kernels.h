@@ -46,7 +46,8 @@ constexpr size_t kSpillInts = (size_t)64 * 64 * 256;     /* full-depth stacks of
  * a power of two apart).  32-B records with the origin in every ray made the queue 0.79 GB per 1080p frame, written by a kernel that
  * is bound by exactly those writes. */
 /* k_shadow_trace4's CALLER forms (launch_occlusion_walk) read these fields differently — dt: the caller's rays, slot: ray indices, origin /
- * slotMask: the start hints and the scene's record count (HINTS), slotStride: the call's cull mask (MASKED) — so that the renderer's own
+ * slotMask: the start hints and the scene's record count (HINTS), slotStride: the call's cull mask and, above it, its culling ray flags
+ * (MASKED) — so that the renderer's own
  * instantiations keep their parameter list.  Whoever gives a field a new use in the kernel checks those forms (static_asserts there). */
 struct RayQueue {
     float4*   dt = nullptr;          /* per ray: direction xyz, tmax */
@@ -144,7 +145,8 @@ struct OcclusionArgs {
 struct RayMaskArgs {
     const uint8_t* rayMasks = nullptr;     /* one byte per ray, or null */
     uint32_t cullMask = 0xffu;             /* 8 bits */
-    uint32_t masked = 0;
+    uint32_t masked = 0;                   /* bit 0: the MASKED forms; bits 4..7: the call's RTR_QUERY_CULL_* ray flags (kCullAll), which only those forms read —
+                                            * a call with such flags and no cull mask sets bit 0 and leaves the mask at 0xff.  The struct keeps its 16 bytes. */
 };
 hipError_t launch_occlusion_walk(const DeviceScene& sc, const OcclusionArgs& oa, const Tunables& tun, bool alpha, Counters* stats, hipStream_t stream, uint32_t numCus,
                                  const RayMaskArgs& rm = RayMaskArgs());

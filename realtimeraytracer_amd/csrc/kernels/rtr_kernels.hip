@@ -842,10 +842,11 @@ __global__ __launch_bounds__(kBlock) void k_shadow_trace(DeviceScene sc, const R
 /* One any-hit triangle test of the persistent 4-wide kernel: 48-B record through the buffer resource, Moeller-Trumbore, t < tmax,
  * and opacity.rahit on alpha-tested geometry.  MAY_SKIP_ALPHA (the caller-ray form only): `opaque` — wave-uniform, RTR_QUERY_OPAQUE —
  * accepts every candidate without that test.  MASKED (the caller-ray form with a cull mask): rayMask8 as in trace() — a record whose
- * instance's mask does not meet the ray's is no candidate. */
+ * instance's mask does not meet the ray's is no candidate, and neither is one the call's culling ray flags (cull; rtr_device.h) drop. */
 template <bool STATS, bool MAY_SKIP_ALPHA = false, bool MASKED = false>
 __device__ __forceinline__ bool tri_any(const DeviceScene& sc, const __amdgpu_buffer_rsrc_t triBuf, const uint32_t tri, const rtr_v3 o, const rtr_v3 d,
-                                        const float tmin, const float tmax, LocalStats& st, const bool opaque = false, const uint32_t rayMask8 = 0u) {
+                                        const float tmin, const float tmax, LocalStats& st, const bool opaque = false, const uint32_t rayMask8 = 0u,
+                                        const uint32_t cull = 0u) {
     typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
     const int32_t triOff = (int32_t)(tri * 48u);
     const u32x4 r0 = __builtin_amdgcn_raw_buffer_load_b128(triBuf, triOff, 0, RTR_TRI_AUX);
@@ -855,8 +856,10 @@ __device__ __forceinline__ bool tri_any(const DeviceScene& sc, const __amdgpu_bu
     const float4 q1 = make_float4(__uint_as_float(r1.x), __uint_as_float(r1.y), __uint_as_float(r1.z), __uint_as_float(r1.w));
     const float4 q2 = make_float4(__uint_as_float(r2.x), __uint_as_float(r2.y), __uint_as_float(r2.z), __uint_as_float(r2.w));
     if (MASKED && (rayMask8 & ~r2.w) == 0u) return false;      /* the instance does not exist for this ray */
+    if (MASKED && cull != 0u && cull_by_opacity(cull, r2.w, !opaque)) return false;      /* the RTR_QUERY_CULL_* flags (wave-uniform): culled before the any-hit test */
     float t, u, v;
     if (!(rtr_mt_intersect(o, d, f4xyz(q0), f4xyz(q1), f4xyz(q2), tmin, &t, &u, &v) && t < tmax)) return false;
+    if (MASKED && cull != 0u && cull_by_facing(sc, cull, d, f4xyz(q1), f4xyz(q2), __float_as_uint(q0.w))) return false;
     if ((__float_as_uint(q2.w) & 1u) && !(MAY_SKIP_ALPHA && opaque)) return alpha_pass<STATS>(sc, __float_as_uint(q0.w), __float_as_uint(q1.w), u, v, st);
     return true;
 }
@@ -986,7 +989,9 @@ __device__ __forceinline__ void inner_nodes4(const __amdgpu_buffer_rsrc_t nodeBu
  * the LISTS forms do not read: one byte per ray, or null — gathered at the refill beside the ray and its hint and kept in bits 8..15 of one
  * register; tri_any skips the records of instances whose mask does not meet it, in the leaf phase of a walk from the root and of an own-leaf
  * start alike (a hinted leaf whose triangles are all masked out does not stop the ray).  Rays whose mask is 0 never reach the queue
- * (k_occlusion_gen).  The forms without MASKED, the renderer's among them, compile to what they were. */
+ * (k_occlusion_gen).  The call's culling ray flags (RTR_QUERY_CULL_*) sit above the mask in queue.slotStride and go to tri_any as one
+ * wave-uniform value: a hinted leaf whose hits are all culled does not stop the ray either.  The forms without MASKED, the renderer's
+ * among them, compile to what they were. */
 template <int STACK, bool LISTS, bool STATS, bool CALLER = false, bool HINTS = false, bool MASKED = false>
 __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_shadow_trace4(DeviceScene sc, const RayQueue queue,
                                                               const uint32_t* __restrict__ count, uint32_t* nextBatch,
@@ -1063,6 +1068,7 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(8, 
     uint32_t slot = 0, rayIndex = 0, res = kResNone, occ = 0;
     float tmin = 0.001f;                     /* the renderer's rays all start there; a caller's ray brings its own (CALLER) */
     uint32_t rayMask8 = 0;                   /* MASKED: the ray's cull mask, where the records keep theirs (tri_any) */
+    const uint32_t cull = MASKED ? (queue.slotStride >> 4) & kCullAll : 0u;      /* MASKED: the call's RTR_QUERY_CULL_* flags, above the mask (launch_occlusion_walk) */
     /* nodes and triangles through buffer resources: the address of a visit is one 32-bit shift, not 64-bit lane arithmetic
      * (2.28 -> 2.17 ms, and 62 -> 47 VGPRs) */
     const __amdgpu_buffer_rsrc_t nodeBuf = __builtin_amdgcn_make_buffer_rsrc((void*)sc.nodes4, 0, 0xffffffff, 0x00020000);
@@ -1169,7 +1175,7 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(8, 
                             }
                             if (MASKED) {      /* cullMask & the ray's own byte, if the call brought any (wave-uniform branch) */
                                 const uint8_t* __restrict__ qmask = reinterpret_cast<const uint8_t*>(count);
-                                uint32_t m = queue.slotStride;
+                                uint32_t m = queue.slotStride & 0xffu;
                                 if (qmask) m &= (uint32_t)qmask[slot];
                                 rayMask8 = m << kTriMaskShift;
                             }
@@ -1261,7 +1267,7 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(8, 
 #if !RTR_STATS_LEAF_PHASE
                 ws.triIters++; ws.triLanes += (uint32_t)__popcll(m);
 #endif
-                if (go) { st.tris++; st.shadowTris++; hit = tri_any<true, CALLER, MASKED>(sc, triBuf, first + i, o, d, tmin, tmax, st, (octForms & 4u) != 0u, rayMask8); }
+                if (go) { st.tris++; st.shadowTris++; hit = tri_any<true, CALLER, MASKED>(sc, triBuf, first + i, o, d, tmin, tmax, st, (octForms & 4u) != 0u, rayMask8, cull); }
             }
             if (atLeaf) {
                 if (hit) { res = 1u; cur = kDone; }
@@ -1271,7 +1277,7 @@ __global__ __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(8, 
             const uint32_t code = (uint32_t)~cur;
             const uint32_t first = code >> 3, cnt = (code & 7u) + 1u;
             bool hit = false;
-            for (uint32_t i = 0; i < cnt && !hit; ++i) hit = tri_any<false, CALLER, MASKED>(sc, triBuf, first + i, o, d, tmin, tmax, st, (octForms & 4u) != 0u, rayMask8);
+            for (uint32_t i = 0; i < cnt && !hit; ++i) hit = tri_any<false, CALLER, MASKED>(sc, triBuf, first + i, o, d, tmin, tmax, st, (octForms & 4u) != 0u, rayMask8, cull);
             if (hit) { res = 1u; cur = kDone; }
             else { cur = *sp; sp -= kTraceBlock; }                        /* slot 0 holds kDone: an empty stack ends the ray (visible) */
         }
@@ -2094,7 +2100,7 @@ hipError_t launch_occlusion_walk(const DeviceScene& sc, const OcclusionArgs& oa,
     /* the MASKED form's reading of two values the CALLER forms do not use: the queue's slot stride is the call's cull mask, and `count`
      * (the plain queue's length; these forms walk the lists) the per-ray mask bytes, or null */
     const bool masked = rm.masked != 0u;
-    if (masked) rq.slotStride = rm.cullMask & 0xffu;
+    if (masked) rq.slotStride = (rm.cullMask & 0xffu) | ((rm.masked & kCullAll) << 4);      /* the culling ray flags ride above the mask */
     const uint32_t* const cnt = masked ? reinterpret_cast<const uint32_t*>(rm.rayMasks) : ctrl;
 #define RTR_OCC_WALK(STATS, HINTS, MASKED) hipLaunchKernelGGL((k_shadow_trace4<RTR_SHADOW_STACK, true, STATS, true, HINTS, MASKED>), dim3(tblocks), dim3(kTraceBlock), 0, s, sc, rq, cnt, ctrl + kBatchCursorWord, \
         oa.occluded, 0u, oa.batch, tun.trace_refill, tun.trace_inner_min, oa.overflow, oa.overflowCap, kOct, top, oa.lists, oa.listStride, stats, (unsigned long long*)nullptr)

@@ -51,6 +51,11 @@ __device__ __forceinline__ uint32_t query_ray_mask8(const RayMaskArgs& rm, uint3
     return (rm.cullMask & (rm.rayMasks ? (uint32_t)rm.rayMasks[k] : 0xffu)) << kTriMaskShift;
 }
 
+/* the call's RTR_QUERY_CULL_* flags (wave-uniform; 0: none), which travel in RayMaskArgs::masked beside the bit that selects these forms */
+__device__ __forceinline__ uint32_t query_cull(const RayMaskArgs& rm) { return rm.masked & kCullAll; }
+static_assert(kCullBackFacing == RTR_QUERY_CULL_BACK_FACING && kCullFrontFacing == RTR_QUERY_CULL_FRONT_FACING && kCullOpaque == RTR_QUERY_CULL_OPAQUE &&
+              kCullNoOpaque == RTR_QUERY_CULL_NO_OPAQUE && (kCullAll & 1u) == 0u, "the kernels' cull bits are the interface's");
+
 /* MASKED (rtr_trace_rays_masked): the ray's mask byte is read beside the ray; a ray whose effective mask is 0 is a miss that walks nothing,
  * like a degenerate ray.  The masks are the LAST kernel argument, behind everything the forms without MASKED read: those compile to the
  * instructions they had (compared function by function in the disassembly); only their kernel-argument segment is 16 B longer, which moves
@@ -66,24 +71,25 @@ __global__ __launch_bounds__(kQueryBlock) void k_query(DeviceScene sc, QueryArgs
     rtr_v3 o, d;
     float tmin, tmax;
     const uint32_t rm8 = MASKED ? query_ray_mask8(rm, k) : 0u;
+    const uint32_t cull = MASKED ? query_cull(rm) : 0u;
     const bool ok = query_ray(qa.rays, k, o, d, tmin, tmax) && (!MASKED || rm8 != 0u);
     const float limit = ok ? tmax : tmin;                 /* a degenerate ray walks nothing (!(limit > tmin)) but is counted like any other */
     HitRec h;
-    if (STATS) trace<ANY, true, kQueryBlock, 16, 8, ALPHA, true, MASKED>(sc, stack, o, d, tmin, limit, h, st, rm8);
+    if (STATS) trace<ANY, true, kQueryBlock, 16, 8, ALPHA, true, MASKED>(sc, stack, o, d, tmin, limit, h, st, rm8, cull);
     else {
         /* as in k_primary: the traversal compiled for the wave's direction signs when all its rays share them */
         const uint32_t oct = ray_octant(sc, o, d);
         const uint32_t woct = (uint32_t)__builtin_amdgcn_readfirstlane((int)oct);
         switch (__ballot(oct != woct) != 0ull ? 8u : woct) {
-            case 0: trace<ANY, false, kQueryBlock, 16, 0, ALPHA, true, MASKED>(sc, stack, o, d, tmin, limit, h, st, rm8); break;
-            case 1: trace<ANY, false, kQueryBlock, 16, 1, ALPHA, true, MASKED>(sc, stack, o, d, tmin, limit, h, st, rm8); break;
-            case 2: trace<ANY, false, kQueryBlock, 16, 2, ALPHA, true, MASKED>(sc, stack, o, d, tmin, limit, h, st, rm8); break;
-            case 3: trace<ANY, false, kQueryBlock, 16, 3, ALPHA, true, MASKED>(sc, stack, o, d, tmin, limit, h, st, rm8); break;
-            case 4: trace<ANY, false, kQueryBlock, 16, 4, ALPHA, true, MASKED>(sc, stack, o, d, tmin, limit, h, st, rm8); break;
-            case 5: trace<ANY, false, kQueryBlock, 16, 5, ALPHA, true, MASKED>(sc, stack, o, d, tmin, limit, h, st, rm8); break;
-            case 6: trace<ANY, false, kQueryBlock, 16, 6, ALPHA, true, MASKED>(sc, stack, o, d, tmin, limit, h, st, rm8); break;
-            case 7: trace<ANY, false, kQueryBlock, 16, 7, ALPHA, true, MASKED>(sc, stack, o, d, tmin, limit, h, st, rm8); break;
-            default: trace<ANY, false, kQueryBlock, 16, 8, ALPHA, true, MASKED>(sc, stack, o, d, tmin, limit, h, st, rm8); break;
+            case 0: trace<ANY, false, kQueryBlock, 16, 0, ALPHA, true, MASKED>(sc, stack, o, d, tmin, limit, h, st, rm8, cull); break;
+            case 1: trace<ANY, false, kQueryBlock, 16, 1, ALPHA, true, MASKED>(sc, stack, o, d, tmin, limit, h, st, rm8, cull); break;
+            case 2: trace<ANY, false, kQueryBlock, 16, 2, ALPHA, true, MASKED>(sc, stack, o, d, tmin, limit, h, st, rm8, cull); break;
+            case 3: trace<ANY, false, kQueryBlock, 16, 3, ALPHA, true, MASKED>(sc, stack, o, d, tmin, limit, h, st, rm8, cull); break;
+            case 4: trace<ANY, false, kQueryBlock, 16, 4, ALPHA, true, MASKED>(sc, stack, o, d, tmin, limit, h, st, rm8, cull); break;
+            case 5: trace<ANY, false, kQueryBlock, 16, 5, ALPHA, true, MASKED>(sc, stack, o, d, tmin, limit, h, st, rm8, cull); break;
+            case 6: trace<ANY, false, kQueryBlock, 16, 6, ALPHA, true, MASKED>(sc, stack, o, d, tmin, limit, h, st, rm8, cull); break;
+            case 7: trace<ANY, false, kQueryBlock, 16, 7, ALPHA, true, MASKED>(sc, stack, o, d, tmin, limit, h, st, rm8, cull); break;
+            default: trace<ANY, false, kQueryBlock, 16, 8, ALPHA, true, MASKED>(sc, stack, o, d, tmin, limit, h, st, rm8, cull); break;
         }
     }
     /* the walk's outcome is read from the record alone (as k_primary reads it), not from trace()'s return value */
@@ -123,7 +129,7 @@ __global__ __launch_bounds__(kQueryTailBlock) void k_query_tail(DeviceScene sc, 
         query_ray(qa.rays, k, o, d, tmin, tmax);          /* an abandoned ray is never degenerate: it walked past 16 stacked nodes */
         const uint32_t rm8 = MASKED ? query_ray_mask8(rm, k) : 0u;      /* re-read like the ray: never 0 here, such a ray walked nothing */
         HitRec h;
-        trace<ANY, STATS, kQueryTailBlocks * kQueryTailBlock, 0, 8, ALPHA, true, MASKED>(sc, stack, o, d, tmin, tmax, h, st, rm8);
+        trace<ANY, STATS, kQueryTailBlocks * kQueryTailBlock, 0, 8, ALPHA, true, MASKED>(sc, stack, o, d, tmin, tmax, h, st, rm8, MASKED ? query_cull(rm) : 0u);
         const bool found = h.custom != RTR_MISS;
         if (STATS) { st.rays--; if (ANY) st.shadow--; else st.primary--; }
         if (ANY) qa.occluded[k] = found ? 1u : 0u;

@@ -372,6 +372,18 @@ static int validate_desc(const rtr_scene_desc* d) {
     return RTR_OK;
 }
 
+/* The mirrored bit of an instance (the ray queries' face culling, RTR_QUERY_CULL_BACK/FRONT_FACING): 1 iff the determinant of its 3x3
+ * transform, evaluated in double, is negative — the instance turns the winding of its triangles over, and Vulkan decides facing in object
+ * space.  It lives in word kMirroredWord of the instance's 12-float slot of the normal-matrix table, which the matrix does not use: a
+ * per-customIndex table that is uploaded with the transforms by create, create_like and update_instances, and that no triangle record
+ * and no kernel argument had to change for. */
+static void set_mirrored_word(const float* m, float* nmatSlot) {
+    const double det = (double)m[0] * ((double)m[5] * m[10] - (double)m[6] * m[9]) - (double)m[1] * ((double)m[4] * m[10] - (double)m[6] * m[8]) +
+                       (double)m[2] * ((double)m[4] * m[9] - (double)m[5] * m[8]);
+    const uint32_t bit = det < 0.0 ? 1u : 0u;
+    memcpy(&nmatSlot[rtrdev::kMirroredWord], &bit, sizeof bit);
+}
+
 /* flatten TLAS instances to one world-space triangle soup (instance order, then primitive order),
  * fill the per-customIndex transform tables, build the BVH */
 static int flatten_and_build(const rtr_scene_desc* d, rtr::BvhResult& bvh, std::vector<float>& xforms, std::vector<float>& nmats,
@@ -387,6 +399,7 @@ static int flatten_and_build(const rtr_scene_desc* d, rtr::BvhResult& bvh, std::
         const RtrMesh& me = d->meshes[in.meshIndex];
         memcpy(&xforms[12 * (size_t)in.customIndex], in.transform, 12 * sizeof(float));
         rtr_normal_matrix(in.transform, &nmats[12 * (size_t)in.customIndex]);
+        set_mirrored_word(in.transform, &nmats[12 * (size_t)in.customIndex]);
         for (uint32_t t = 0; t < me.indexCount / 3u; ++t) {
             rtr::WorldTriangle w;
             for (int k = 0; k < 3; ++k) {
@@ -577,6 +590,7 @@ static void instance_tables(uint32_t numInstances, const RtrInstance* instances,
     for (uint32_t i = 0; i < numInstances; ++i) {
         memcpy(&xforms[12 * (size_t)instances[i].customIndex], instances[i].transform, 12 * sizeof(float));
         rtr_normal_matrix(instances[i].transform, &nmats[12 * (size_t)instances[i].customIndex]);
+        set_mirrored_word(instances[i].transform, &nmats[12 * (size_t)instances[i].customIndex]);
     }
 }
 
@@ -1484,11 +1498,36 @@ static int query_scratch(rtr_ctx* c) {
 struct CullMask { bool masked; const uint8_t* rayMasks; uint32_t cullMask; };
 static const CullMask NoMask{false, nullptr, 0xffu};
 
+/* the flags argument of every query entry point: the known bits, and the combinations Vulkan forbids (VUID-RayFlags: one face flag at
+ * most; one of Opaque, CullOpaque, CullNoOpaque at most) */
+static const uint32_t kQueryCullFlags = RTR_QUERY_CULL_BACK_FACING | RTR_QUERY_CULL_FRONT_FACING | RTR_QUERY_CULL_OPAQUE | RTR_QUERY_CULL_NO_OPAQUE;
+static int check_query_flags(uint32_t flags, const char* who) {
+    const uint32_t known = RTR_QUERY_ANY | RTR_QUERY_OPAQUE | kQueryCullFlags;
+    if (flags & ~known) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: unknown flag bits 0x%x", who, flags & ~known);
+    if ((flags & RTR_QUERY_CULL_BACK_FACING) && (flags & RTR_QUERY_CULL_FRONT_FACING))
+        return fail(RTR_ERR_INVALID_ARGUMENT, "%s: flags RTR_QUERY_CULL_BACK_FACING and RTR_QUERY_CULL_FRONT_FACING exclude each other", who);
+    const uint32_t op = flags & (RTR_QUERY_OPAQUE | RTR_QUERY_CULL_OPAQUE | RTR_QUERY_CULL_NO_OPAQUE);
+    if (op & (op - 1u))
+        return fail(RTR_ERR_INVALID_ARGUMENT, "%s: flags%s%s%s exclude each other (at most one of RTR_QUERY_OPAQUE, RTR_QUERY_CULL_OPAQUE, RTR_QUERY_CULL_NO_OPAQUE)", who,
+                    (op & RTR_QUERY_OPAQUE) ? " RTR_QUERY_OPAQUE" : "", (op & RTR_QUERY_CULL_OPAQUE) ? " RTR_QUERY_CULL_OPAQUE" : "",
+                    (op & RTR_QUERY_CULL_NO_OPAQUE) ? " RTR_QUERY_CULL_NO_OPAQUE" : "");
+    return RTR_OK;
+}
+/* what the kernels get: a call with culling flags launches the MASKED forms — with the mask 0xff and no per-ray bytes when it brought no
+ * cull mask — and hands them the flags beside the selecting bit; a call without launches what it always did */
+static rtrdev::RayMaskArgs ray_mask_args(const CullMask& cm, uint32_t flags) {
+    rtrdev::RayMaskArgs rm;
+    const uint32_t cull = flags & kQueryCullFlags;
+    rm.rayMasks = cm.masked ? cm.rayMasks : nullptr; rm.cullMask = cm.masked ? cm.cullMask : 0xffu;
+    rm.masked = (cm.masked || cull) ? (1u | cull) : 0u;
+    return rm;
+}
+
 static int enqueue_query(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, uint32_t n, uint32_t flags, RtrHit* hits, uint8_t* occluded,
                          bool count, const char* who, const CullMask& cm = NoMask) {
     if (!c || !s) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: null context or scene", who);
     if (cm.masked && (cm.cullMask & ~0xffu)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: cullMask 0x%x has bits above the low 8 (an instance mask is 8 bits)", who, cm.cullMask);
-    if (flags & ~(RTR_QUERY_ANY | RTR_QUERY_OPAQUE)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: unknown flag bits 0x%x", who, flags & ~(RTR_QUERY_ANY | RTR_QUERY_OPAQUE));
+    if (const int frc = check_query_flags(flags, who)) return frc;
     if (s->ctx->device != c->device) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: the scene lives on device %d, the context on device %d", who, s->ctx->device, c->device);
     if (n == 0) return RTR_OK;
     const bool any = (flags & RTR_QUERY_ANY) != 0u;
@@ -1514,9 +1553,8 @@ static int enqueue_query(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, uin
     rtrdev::QueryArgs qa{};
     qa.rays = reinterpret_cast<const float4*>(rays); qa.hits = reinterpret_cast<float4*>(hits); qa.occluded = occluded; qa.n = n;
     qa.redoCap = redoCap; qa.ctrl = c->qCtrl.p; qa.redoList = c->qRedo.p; qa.spill = c->qSpill.p;
-    rtrdev::RayMaskArgs rm;
-    rm.rayMasks = cm.rayMasks; rm.cullMask = cm.cullMask; rm.masked = cm.masked ? 1u : 0u;
-    const hipError_t e = rtrdev::launch_query(s->dev, qa, flags, count ? c->qCounters.p : nullptr, st, rm);
+    const rtrdev::RayMaskArgs rm = ray_mask_args(cm, flags);
+    const hipError_t e = rtrdev::launch_query(s->dev, qa, flags & (RTR_QUERY_ANY | RTR_QUERY_OPAQUE), count ? c->qCounters.p : nullptr, st, rm);
     if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: kernel launch: %s", who, hipGetErrorString(e));
     HIP_TRY(hipEventRecord(c->qEv[1], st));
     c->qLastStream = st;
@@ -1598,7 +1636,7 @@ static int enqueue_occlusion(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays,
     if (n && !aligned4(startLeaves)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: startLeaves is not 4-B aligned", who);
     if (!c || !s) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: null context or scene", who);
     if (cm.masked && (cm.cullMask & ~0xffu)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: cullMask 0x%x has bits above the low 8 (an instance mask is 8 bits)", who, cm.cullMask);
-    if (flags & ~(RTR_QUERY_ANY | RTR_QUERY_OPAQUE)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: unknown flag bits 0x%x", who, flags & ~(RTR_QUERY_ANY | RTR_QUERY_OPAQUE));
+    if (const int frc = check_query_flags(flags, who)) return frc;
     if (s->ctx->device != c->device) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: the scene lives on device %d, the context on device %d", who, s->ctx->device, c->device);
     if (n == 0) return RTR_OK;
     if (!rays || !occluded || !scratch) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: %s is null", who, !rays ? "rays" : (!occluded ? "occluded" : "scratch"));
@@ -1625,8 +1663,7 @@ static int enqueue_occlusion(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays,
     oa.ctrl = reinterpret_cast<uint32_t*>(base + l.ctrl); oa.overflow = reinterpret_cast<uint32_t*>(base + l.overflow); oa.overflowCap = overflowCap;
     oa.queue = reinterpret_cast<uint32_t*>(base + l.queue); oa.lists = reinterpret_cast<uint2*>(base + l.lists); oa.listStride = l.listStride;
     oa.startLeaves = startLeaves; oa.numTris = (uint32_t)(s->tris.n / 3);          /* a hint is checked against the records the scene holds */
-    rtrdev::RayMaskArgs rm;
-    rm.rayMasks = cm.rayMasks; rm.cullMask = cm.cullMask; rm.masked = cm.masked ? 1u : 0u;
+    const rtrdev::RayMaskArgs rm = ray_mask_args(cm, flags);
     const hipError_t e = rtrdev::launch_occlusion(s->dev, oa, c->tun, (flags & RTR_QUERY_OPAQUE) == 0u, c->qSpill.p, count ? c->qCounters.p : nullptr, st,
                                                   (uint32_t)c->prop.multiProcessorCount, rm);
     if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: kernel launch: %s", who, hipGetErrorString(e));

@@ -211,7 +211,8 @@ int  rtr_scene_create(rtr_ctx* ctx, const rtr_scene_desc* desc, rtr_scene** out)
  * made from the same `desc` (same arrays, same buildFlags) whose host-side copy of the tree is uploaded as it is.  What
  * librtr_mgpu.so replicates the scene with: one build per node instead of one per GPU.  The reference builds its acceleration
  * structure once, on its one device (src/vulkan/raytracing/blas.cppm:75-167); this is that build shared by N devices.
- * RTR_ERR_INVALID_ARGUMENT if `built` does not match `desc` (triangle count). */
+ * RTR_ERR_INVALID_ARGUMENT if `built` does not match `desc` (triangle count).  After rtr_scene_update_vertices on `built`, `desc` must
+ * carry the vertices `built` currently has (rtr_scene_export_vertices): its tree was fitted to those, and nothing here can check it. */
 int  rtr_scene_create_like(rtr_ctx* ctx, const rtr_scene_desc* desc, const rtr_scene* built, rtr_scene** out);
 void rtr_scene_destroy(rtr_scene* scene);
 int  rtr_scene_get_stats(const rtr_scene* scene, rtr_scene_stats* out);
@@ -250,6 +251,48 @@ int  rtr_check_scene_limits(uint64_t numTriangles, uint64_t numNodes);
  * other threads or processes must itself keep those from enqueueing new frames of this scene until the call has returned. */
 int  rtr_scene_update_instances(rtr_scene* scene, const RtrInstance* instances, uint32_t numInstances,
                                 const RtrAreaLightInfo* lights, uint32_t numLights);
+/* Deforming meshes: new vertex positions (and, optionally, normals) for parts of the scene's vertex array, then ONE refit — what Vulkan
+ * does with a BLAS built with ALLOW_UPDATE and rebuilt in MODE_UPDATE (the reference sets eAllowUpdate on its TLAS and leaves the rest
+ * as a TODO, src/vulkan/raytracing/tlas.cppm:20,106,176-178).  Skinned characters, cloth, morph targets, a simulation that lives in a
+ * torch tensor: the topology (indices, meshes, instances) stays, the vertices move.
+ * ranges[r] names numVertices vertices from firstVertex of the scene's CONCATENATED vertex array (rtr_scene_desc::vertices; a range may
+ * span meshes) and where their new data is: three floats per vertex, positionStride / normalStride bytes apart — 12 is packed float3,
+ * 16 a float4 column, 48 an RtrVertex array with normals = base + 16.  A stride is a multiple of 4 and at least 12 (normalStride is only
+ * looked at when a range brings normals).  flags: RTR_VERTICES_HOST — the pointers are host pointers — or RTR_VERTICES_DEVICE — they
+ * are DEVICE pointers on the scene's device (torch tensors, hipMalloc), 4-B aligned; one call is one kind.
+ * Written: position[0..2] of the named vertices, and normal[0..2] where the range's normals is not NULL.  uv and the pad words keep their
+ * bytes; vertices outside the ranges are untouched.  Then comes exactly one refit, rtr_scene_update_instances' own, with `instances`
+ * and `lights`, or with the current ones where they are NULL (numInstances / numLights are then ignored): world-space records, boxes,
+ * grid, 4-wide view, host mirrors, boxPad; the light-triangle table is ALWAYS remade (a light's mesh may be among the vertices).
+ * Instance masks and the triangle -> leaf table survive; the mirrored bits are recomputed only when instances are given.
+ * Everything is validated BEFORE anything is written, and a refused call leaves the scene byte for byte as it was:
+ * RTR_ERR_INVALID_ARGUMENT (with a message) for a null scene or ranges, numRanges == 0, a null positions in a range with vertices,
+ * a bad stride, a range that leaves the vertex array or overlaps another (checked on the host), unknown flag bits, a device pointer
+ * that is not 4-B aligned, everything rtr_scene_update_instances refuses in instances / lights, and a position that rtr_scene_create
+ * would refuse — not finite, or beyond +-3.0e38 — anywhere in any range: the message names the range and the vertex (the first in range
+ * order).  Host data is checked by a host loop; device data by a kernel that reduces the first bad (range, vertex) into a word the host
+ * reads before the writing kernel is launched.  Normals are NOT validated: they are shading data.  An empty scene returns RTR_OK and
+ * does nothing, as rtr_scene_update_instances.
+ * Synchronisation: as the other update calls (above): the call joins the whole device, rewrites, and returns when the new state is
+ * complete.  With RTR_VERTICES_DEVICE the caller's data must be complete before the call: the device join guarantees that for work
+ * ALREADY ENQUEUED on any stream of this process when the call is made; work of other processes, or work enqueued from another thread
+ * during the call, is the caller's to order.  The data is read during the call only; the library keeps no pointer to it.
+ * rtr_scene_create_like afterwards: `desc` must carry the vertices the `built` scene has NOW (rtr_scene_export_vertices gives them),
+ * since the tree that is copied was fitted to those. */
+#define RTR_VERTICES_HOST   0u   /* positions / normals of the ranges are host pointers */
+#define RTR_VERTICES_DEVICE 1u   /* ... are DEVICE pointers on the scene's device (torch tensors, hipMalloc), 4-B aligned */
+typedef struct rtr_vertex_range {
+    uint32_t    firstVertex, numVertices;  /* into the scene's concatenated vertex array (rtr_scene_desc::vertices) */
+    const void* positions;                 /* numVertices x 3 floats, positionStride bytes apart */
+    const void* normals;                   /* the same with normalStride, or NULL: normals are kept */
+} rtr_vertex_range;                        /* 24 bytes */
+int  rtr_scene_update_vertices(rtr_scene* scene, const rtr_vertex_range* ranges, uint32_t numRanges,
+                               uint32_t positionStride, uint32_t normalStride, uint32_t flags,
+                               const RtrInstance* instances, uint32_t numInstances,
+                               const RtrAreaLightInfo* lights, uint32_t numLights);
+/* Copy out the device vertex array as it is now (test / oracle hook like rtr_scene_export_bvh, and what rtr_scene_create_like needs
+ * after a deformation): numVertices records; RTR_ERR_INVALID_ARGUMENT for a null pointer or a `bytes` that is not numVertices * 48. */
+int  rtr_scene_export_vertices(const rtr_scene* scene, RtrVertex* out, size_t bytes);
 /* Instance cull masks: VkAccelerationStructureInstanceKHR::mask (reference src/vulkan/raytracing/tlas.cppm:63, instance.setMask(0xFF): the
  * only value the reference uses).  masks: a HOST array, one byte per instance, in instance order (rtr_scene_desc::instances); every new
  * scene — one made by rtr_scene_create_like too — starts with 0xff everywhere.  Only the MASKED ray queries (rtr_trace_rays_masked,

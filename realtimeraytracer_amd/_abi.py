@@ -85,6 +85,11 @@ class rtr_light_params(C.Structure):
                 ("_pad", u32 * 2)]
 
 
+class rtr_vertex_range(C.Structure):
+    """one range of rtr_scene_update_vertices: vertices firstVertex ... + numVertices of the scene's concatenated vertex array"""
+    _fields_ = [("firstVertex", u32), ("numVertices", u32), ("positions", C.c_void_p), ("normals", C.c_void_p)]
+
+
 class rtr_texture(C.Structure):
     _fields_ = [("pixels", C.POINTER(C.c_uint8)), ("width", u32), ("height", u32), ("channels", u32), ("_pad", u32)]
 
@@ -137,6 +142,7 @@ assert C.sizeof(RtrBvhNode) == 32 and C.sizeof(RtrBvhGrid) == 32 and C.sizeof(Rt
 assert C.sizeof(RtrRay) == 32 and C.sizeof(RtrHit) == 32 and C.sizeof(rtr_query_stats) == 48
 assert C.sizeof(RtrSurface) == 80
 assert C.sizeof(RtrRadiance) == 48 and C.sizeof(rtr_light_params) == 32
+assert C.sizeof(rtr_vertex_range) == 24
 
 # enum rtr_image
 IMAGE_ANALYTIC, IMAGE_SHADOWED, IMAGE_UNSHADOWED = 0, 1, 2
@@ -157,6 +163,7 @@ QUERY_CLOSEST, QUERY_ANY, QUERY_OPAQUE = 0, 1, 2
 QUERY_CULL_BACK_FACING, QUERY_CULL_FRONT_FACING, QUERY_CULL_OPAQUE, QUERY_CULL_NO_OPAQUE = 0x10, 0x20, 0x40, 0x80
 SURFACE_MISS, SURFACE_OBJECT, SURFACE_LIGHT, SURFACE_INVALID = 0, 1, 2, 3
 LIGHT_SHADOWED, LIGHT_UNSHADOWED, LIGHT_ANALYTIC = 1, 2, 4
+VERTICES_HOST, VERTICES_DEVICE = 0, 1
 
 P = C.POINTER
 VP = C.c_void_p
@@ -180,6 +187,8 @@ RTR_SYMBOLS = {
     "rtr_host_build_bvh_wide": (C.c_int, [P(rtr_scene_desc), P(rtr_scene_stats), VP, C.c_size_t, VP, C.c_size_t, VP, C.c_size_t]),
     "rtr_scene_update_lights": (C.c_int, [VP, P(RtrAreaLightInfo), u32]),
     "rtr_scene_update_instances": (C.c_int, [VP, P(RtrInstance), u32, P(RtrAreaLightInfo), u32]),
+    "rtr_scene_update_vertices": (C.c_int, [VP, P(rtr_vertex_range), u32, u32, u32, u32, P(RtrInstance), u32, P(RtrAreaLightInfo), u32]),
+    "rtr_scene_export_vertices": (C.c_int, [VP, VP, C.c_size_t]),
     "rtr_scene_set_instance_masks": (C.c_int, [VP, VP, u32]),
     "rtr_scene_get_instance_masks": (C.c_int, [VP, VP, u32]),
     "rtr_frame_create": (C.c_int, [VP, u32, u32, u32, P(VP)]),

@@ -75,6 +75,7 @@ class Scene:
         self.ctx, self.lib = ctx, ctx.lib
         self.h = A.VP()
         self._num_instances = int(desc.numInstances)
+        self._num_vertices = int(desc.numVertices)
         if like is None:
             _check(self.lib.rtr_scene_create(ctx.h, C.byref(desc), C.byref(self.h)), "rtr_scene_create")
         else:
@@ -107,6 +108,93 @@ class Scene:
         else:
             larr = (A.RtrAreaLightInfo * len(lights))(*lights)
             _check(self.lib.rtr_scene_update_instances(self.h, arr, len(instances), larr, len(lights)), "rtr_scene_update_instances")
+
+    def update_vertices(self, ranges, instances=None, lights=None):
+        """rtr_scene_update_vertices: deform meshes — new positions (and normals) for ranges of the scene's vertex array, then ONE refit
+        that also carries `instances` / `lights` when they are given (as update_instances takes them; None keeps the current ones).
+        ranges: a list of (first_vertex, positions) or (first_vertex, positions, normals); first_vertex indexes the scene's concatenated
+        vertex array (desc.vertices), a range may span meshes, ranges must not overlap.  The arrays are float32 (n, 3) or (n, 4) — the
+        first three columns are used — and either ALL numpy arrays (the host route) or ALL torch tensors on the scene's device (the
+        device route: the data never leaves the device); mixing the kinds is refused.  A strided view is taken as it is when its row
+        stride is a multiple of 4 bytes and its columns are adjacent: a (n, 4)[:, :3] column view, rows of an (n, 12) RtrVertex array.
+        One call passes one position stride and one normal stride, so arrays whose strides differ (or that do not qualify) are made
+        contiguous first.  uv and the vertices outside the ranges keep their bytes.  A position that is not finite refuses the whole
+        call (RtrError, RTR_ERR_INVALID_ARGUMENT) and leaves the scene as it was.  With tensors, torch's current stream is joined first
+        when the context works on another one, as in the query calls."""
+        who = "update_vertices"
+        rows = []
+        for k, r in enumerate(ranges):
+            if not isinstance(r, (tuple, list)) or len(r) not in (2, 3):
+                raise ValueError(f"{who}: range {k} must be (first_vertex, positions[, normals])")
+            rows.append((int(r[0]), r[1], r[2] if len(r) == 3 else None))
+        if not rows:
+            raise ValueError(f"{who}: no ranges")
+        arrays = [a for _, p, n in rows for a in (p, n) if a is not None]
+        if any(p is None for _, p, _ in rows):
+            raise ValueError(f"{who}: a range without positions")
+        as_numpy = all(isinstance(a, np.ndarray) for a in arrays)
+        if not as_numpy:
+            torch = _torch()
+            if not all(isinstance(a, torch.Tensor) for a in arrays):
+                raise ValueError(f"{who}: the arrays must be all numpy arrays or all torch tensors on the scene's device, not a mixture")
+            dev = torch.device("cuda", self.ctx.device)
+        for k, (first, p, n) in enumerate(rows):
+            for name, a in (("positions", p), ("normals", n)):
+                if a is None:
+                    continue
+                ok = (a.dtype == np.float32) if as_numpy else (a.dtype == torch.float32)
+                if not ok or len(a.shape) != 2 or a.shape[1] not in (3, 4):
+                    raise ValueError(f"{who}: range {k}: {name} must be float32 (n, 3) or (n, 4), got {a.dtype} {tuple(a.shape)}")
+                if not as_numpy and a.device != dev:
+                    raise ValueError(f"{who}: range {k}: {name} live on {a.device}, the scene on {dev}")
+            if n is not None and n.shape[0] != p.shape[0]:
+                raise ValueError(f"{who}: range {k}: {p.shape[0]} positions but {n.shape[0]} normals")
+            if first < 0 or first + p.shape[0] > 0xffffffff:
+                raise ValueError(f"{who}: range {k}: first_vertex {first} with {p.shape[0]} vertices does not fit 32 bits")
+
+        def pack(a):
+            return np.ascontiguousarray(a[:, :3]) if as_numpy else a[:, :3].contiguous()
+
+        def unify(which):        # one stride per call: every array of this kind as it is, or all of them packed (stride 12)
+            seen = set()
+            for a in (r[which] for r in rows if r[which] is not None and r[which].shape[0]):
+                sb, sc = (a.strides[0], a.strides[1]) if as_numpy else (4 * a.stride(0), 4 * a.stride(1))
+                if sc != 4 or (a.shape[0] > 1 and (sb % 4 or sb < 12)):
+                    return 12, pack
+                if a.shape[0] > 1:
+                    seen.add(sb)
+            if len(seen) > 1:
+                return 12, pack
+            return (seen.pop() if seen else 12), (lambda a: a)
+
+        pstride, pfix = unify(1)
+        nstride, nfix = unify(2)
+        keep, table = [], (A.rtr_vertex_range * len(rows))()
+        for k, (first, p, n) in enumerate(rows):
+            p = pfix(p)
+            n = nfix(n) if n is not None else None
+            keep += [p, n]
+            ptr = (lambda a: a.ctypes.data) if as_numpy else (lambda a: a.data_ptr())
+            cnt = int(p.shape[0])
+            table[k] = A.rtr_vertex_range(first, cnt, ptr(p) if cnt else None, ptr(n) if n is not None and cnt else None)
+        if not as_numpy and self.ctx.get_stream() != torch.cuda.current_stream(dev).cuda_stream:
+            torch.cuda.current_stream(dev).synchronize()        # the tensors are complete for the context's stream
+        iarr = (A.RtrInstance * len(instances))(*instances) if instances is not None else None
+        larr = (A.RtrAreaLightInfo * len(lights))(*lights) if lights is not None else None
+        _check(self.lib.rtr_scene_update_vertices(self.h, table, len(rows), pstride, nstride, A.VERTICES_HOST if as_numpy else A.VERTICES_DEVICE,
+                                                  iarr, len(instances) if instances is not None else 0,
+                                                  larr, len(lights) if lights is not None else 0), "rtr_scene_update_vertices")
+        del keep
+
+    VERTEX_DTYPE = np.dtype([("position", np.float32, 3), ("pad0", np.float32), ("normal", np.float32, 3), ("pad1", np.float32),
+                             ("uv", np.float32, 2), ("pad2", np.float32, 2)])
+
+    def export_vertices(self, raw=False):
+        """rtr_scene_export_vertices: the device vertex array as it is now — a numpy structured array of RtrVertex records (position,
+        pad0, normal, pad1, uv, pad2), or with raw=True its (n, 12) float32 view"""
+        out = np.zeros(self._num_vertices, self.VERTEX_DTYPE)
+        _check(self.lib.rtr_scene_export_vertices(self.h, out.ctypes.data_as(A.VP) if out.size else None, out.nbytes), "rtr_scene_export_vertices")
+        return out.view(np.float32).reshape(-1, 12) if raw else out
 
     def set_instance_masks(self, masks):
         """rtr_scene_set_instance_masks: one 8-bit cull mask per instance, in instance order (array-like of uint8; default 0xff).  Only

@@ -42,6 +42,22 @@ hipError_t bvh_build_lbvh(const BvhInputs& in, uint32_t numPrims, const BvhDevic
  * from the new root bounds and re-quantise. */
 hipError_t bvh_refit(const BvhInputs& in, uint32_t numPrims, uint32_t numNodes, const BvhDeviceArrays& a, hipStream_t s);
 
+/* ---- vertex updates (rtr_scene_update_vertices): new positions / normals for ranges of the scene's vertex array -------------------
+ * One entry of the device table of ranges.  positions / normals point at DEVICE memory (the caller's, or the scene's staging buffer
+ * for host data), three 32-bit words per vertex, a launch-wide stride apart; normals may be null: the range keeps its normals. */
+struct VertexRange { const uint32_t* positions; const uint32_t* normals; uint32_t firstVertex; uint32_t _pad; };   /* 24 B */
+constexpr uint32_t kVertexRangesPerLaunch = 1024;     /* prefix counts of one launch live in LDS (4 KB + 1 word) */
+/* One lane per vertex of the concatenation of numRanges (<= kVertexRangesPerLaunch) ranges; prefix: numRanges + 1 words, prefix[r] = the
+ * vertices of the ranges before r, prefix[numRanges] = all of them (< 2^32).  Strides in 32-bit words (>= 3).
+ * check: atomicMin(firstBad, concatBase + i) for every lane i whose position rtr_scene_create would refuse (not inside +-3.0e38);
+ * nothing is written but that word, which the host sets to 0xffffffff first and reads before it launches the write.
+ * write: words 0..2 (position) and, where the range has normals, words 4..6 (normal) of vertices[firstVertex + v]; the other six words
+ * of the 48-B vertex are not touched.  The caller guarantees firstVertex + count <= the array's length for every range. */
+hipError_t launch_check_vertices(const VertexRange* ranges, const uint32_t* prefix, uint32_t numRanges, uint32_t total, uint32_t positionStrideWords,
+                                 uint32_t concatBase, uint32_t* firstBad, hipStream_t s);
+hipError_t launch_write_vertices(const VertexRange* ranges, const uint32_t* prefix, uint32_t numRanges, uint32_t total, uint32_t positionStrideWords,
+                                 uint32_t normalStrideWords, RtrVertex* vertices, hipStream_t s);
+
 /* The 4-wide view of a finished (quantised) tree that the any-hit kernel walks: numNodes x 4 uint4, see k_wide_nodes.
  * parentOrNull: the refit parent array (entries outside the tree are skipped) or null. */
 /* sets grid->wideCentreXY / Z (k_wide_centre_*; sums4 = bvh_wide_scratch_words() x u64 of scratch) and writes the 4-wide records about it */

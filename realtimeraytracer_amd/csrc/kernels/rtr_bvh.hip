@@ -498,8 +498,79 @@ __global__ __launch_bounds__(kB) void k_permute_wide(uint32_t numNodes, const ui
     out[dst + 3] = c;
 }
 
+/* ---- vertex updates (rtr_scene_update_vertices) ---------------------------------------------------------------------
+ * Lane i of the launch is vertex i of the concatenation of the ranges.  Its range is the last r with prefix[r] <= i (empty ranges
+ * repeat a count and are skipped by that rule), found by bisection over the prefix counts, which every block first copies to LDS.
+ * The source is read as strided dwords — whatever the caller's layout is: packed float3, a float4 column, RtrVertex records — and the
+ * destination written as dword stores into the 48-B vertex, so uv and the pad words keep their bytes. */
+static_assert(sizeof(RtrVertex) == 48 && sizeof(VertexRange) == 24, "layout");
+
+__device__ __forceinline__ uint32_t vertex_range_of(const uint32_t* sPrefix, uint32_t numRanges, uint32_t i) {
+    uint32_t lo = 0, hi = numRanges;                     /* sPrefix[lo] <= i < sPrefix[hi] */
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (sPrefix[mid] <= i) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(kB) void k_check_vertices(const VertexRange* __restrict__ ranges, const uint32_t* __restrict__ prefix, uint32_t numRanges,
+                                                       uint32_t strideWords, uint32_t concatBase, uint32_t* __restrict__ firstBad) {
+    __shared__ uint32_t sPrefix[kVertexRangesPerLaunch + 1];
+    for (uint32_t j = threadIdx.x; j <= numRanges; j += kB) sPrefix[j] = prefix[j];
+    __syncthreads();
+    const uint32_t i = blockIdx.x * kB + threadIdx.x;
+    if (i >= sPrefix[numRanges]) return;
+    const uint32_t r = vertex_range_of(sPrefix, numRanges, i);
+    const uint32_t* src = ranges[r].positions + (size_t)(i - sPrefix[r]) * strideWords;
+    bool ok = true;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float x = __uint_as_float(src[k]);
+        ok = ok && (x > -3.0e38f && x < 3.0e38f);        /* the rule of the scene builders: NaN fails both comparisons */
+    }
+    if (!ok) atomicMin(firstBad, concatBase + i);        /* rare: no wave reduction in front of it */
+}
+
+__global__ __launch_bounds__(kB) void k_write_vertices(const VertexRange* __restrict__ ranges, const uint32_t* __restrict__ prefix, uint32_t numRanges,
+                                                       uint32_t positionStrideWords, uint32_t normalStrideWords, RtrVertex* __restrict__ vertices) {
+    __shared__ uint32_t sPrefix[kVertexRangesPerLaunch + 1];
+    for (uint32_t j = threadIdx.x; j <= numRanges; j += kB) sPrefix[j] = prefix[j];
+    __syncthreads();
+    const uint32_t i = blockIdx.x * kB + threadIdx.x;
+    if (i >= sPrefix[numRanges]) return;
+    const uint32_t r = vertex_range_of(sPrefix, numRanges, i);
+    const uint32_t v = i - sPrefix[r];
+    const VertexRange vr = ranges[r];
+    uint32_t* dst = reinterpret_cast<uint32_t*>(vertices + ((size_t)vr.firstVertex + v));
+    const uint32_t* p = vr.positions + (size_t)v * positionStrideWords;
+    const uint32_t p0 = p[0], p1 = p[1], p2 = p[2];
+    dst[0] = p0; dst[1] = p1; dst[2] = p2;
+    if (vr.normals) {
+        const uint32_t* q = vr.normals + (size_t)v * normalStrideWords;
+        const uint32_t n0 = q[0], n1 = q[1], n2 = q[2];
+        dst[4] = n0; dst[5] = n1; dst[6] = n2;
+    }
+}
+
 /* ---- host-side drivers ------------------------------------------------------------------------------ */
 #define BV_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return e_; } while (0)
+
+hipError_t launch_check_vertices(const VertexRange* ranges, const uint32_t* prefix, uint32_t numRanges, uint32_t total, uint32_t positionStrideWords,
+                                 uint32_t concatBase, uint32_t* firstBad, hipStream_t s) {
+    if (total == 0 || numRanges == 0) return hipSuccess;
+    if (numRanges > kVertexRangesPerLaunch) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_check_vertices, dim3((uint32_t)(((uint64_t)total + kB - 1) / kB)), dim3(kB), 0, s, ranges, prefix, numRanges, positionStrideWords, concatBase, firstBad);
+    return hipGetLastError();
+}
+
+hipError_t launch_write_vertices(const VertexRange* ranges, const uint32_t* prefix, uint32_t numRanges, uint32_t total, uint32_t positionStrideWords,
+                                 uint32_t normalStrideWords, RtrVertex* vertices, hipStream_t s) {
+    if (total == 0 || numRanges == 0) return hipSuccess;
+    if (numRanges > kVertexRangesPerLaunch) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_write_vertices, dim3((uint32_t)(((uint64_t)total + kB - 1) / kB)), dim3(kB), 0, s, ranges, prefix, numRanges, positionStrideWords, normalStrideWords, vertices);
+    return hipGetLastError();
+}
 
 hipError_t bvh_refit(const BvhInputs& in, uint32_t numPrims, uint32_t numNodes, const BvhDeviceArrays& a, hipStream_t s) {
     BV_TRY(hipMemsetAsync(a.counters, 0, (size_t)numNodes * sizeof(uint32_t), s));

@@ -57,6 +57,8 @@ struct DevBuf {
         if (e == hipSuccess) n = count;
         return e;
     }
+    /* a buffer that is reused from call to call and grows on demand (its old contents are not kept) */
+    hipError_t grow(size_t count) { return (p && n >= count) ? hipSuccess : alloc(count + count / 2); }
     hipError_t upload(const T* src, size_t count, hipStream_t s) {
         hipError_t e = alloc(count);
         if (e != hipSuccess) return e;
@@ -150,6 +152,11 @@ struct rtr_scene {
     DevBuf<uint32_t> counters, depth, slotOfPrim, red;
     uint32_t numPrims = 0, numNodeSlots = 0;
     bool refitReady = false;
+    /* rtr_scene_update_vertices: the device table of ranges, their prefix counts (+ the "first bad vertex" word), and the staging
+     * buffer host data is packed into (vtxHost) and copied to (vtxStage); they grow on demand and are reused by every call */
+    DevBuf<rtrdev::VertexRange> vtxRanges;
+    DevBuf<uint32_t> vtxPrefix, vtxStage;
+    std::vector<uint32_t> vtxHost;
     rtr_scene_stats stats{};
     DeviceScene dev{};
     uint32_t numLights = 0, numObjects = 0, numVertices = 0, numIndices = 0;
@@ -804,46 +811,56 @@ int rtr_scene_get_instance_masks(const rtr_scene* s, uint8_t* masks, uint32_t nu
     return RTR_OK;
 }
 
-int rtr_scene_update_instances(rtr_scene* s, const RtrInstance* instances, uint32_t numInstances, const RtrAreaLightInfo* lights, uint32_t numLights) {
-    if (!s || (!instances && numInstances)) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_scene_update_instances: null argument");
-    if (numInstances != s->hostInstances.size()) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_scene_update_instances: %u instances given, scene has %zu", numInstances, s->hostInstances.size());
-    if (lights && numLights != s->numLights) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_scene_update_instances: %u lights given, scene has %u", numLights, s->numLights);
-    for (uint32_t i = 0; i < numInstances; ++i) {
-        if (instances[i].meshIndex != s->hostInstances[i].meshIndex || instances[i].customIndex != s->hostInstances[i].customIndex)
-            return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_scene_update_instances: instance %u changed mesh or customIndex; only transforms may change (a refit keeps the topology)", i);
-        for (int k = 0; k < 12; ++k)
-            if (!(instances[i].transform[k] > -3.0e38f && instances[i].transform[k] < 3.0e38f))
-                return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_scene_update_instances: instance %u has a non-finite transform", i);
+/* The argument checks the two refitting calls share (rtr_scene_update_instances, rtr_scene_update_vertices); `who` names the caller in
+ * the message.  instances == NULL (rtr_scene_update_vertices only): the current transforms are kept and nothing is checked for them. */
+static int check_refit_args(const rtr_scene* s, const RtrInstance* instances, uint32_t numInstances, const RtrAreaLightInfo* lights, uint32_t numLights,
+                            const char* who) {
+    if (instances) {
+        if (numInstances != s->hostInstances.size()) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: %u instances given, scene has %zu", who, numInstances, s->hostInstances.size());
+        for (uint32_t i = 0; i < numInstances; ++i) {
+            if (instances[i].meshIndex != s->hostInstances[i].meshIndex || instances[i].customIndex != s->hostInstances[i].customIndex)
+                return fail(RTR_ERR_INVALID_ARGUMENT, "%s: instance %u changed mesh or customIndex; only transforms may change (a refit keeps the topology)", who, i);
+            for (int k = 0; k < 12; ++k)
+                if (!(instances[i].transform[k] > -3.0e38f && instances[i].transform[k] < 3.0e38f))
+                    return fail(RTR_ERR_INVALID_ARGUMENT, "%s: instance %u has a non-finite transform", who, i);
+        }
     }
-    if (lights)
+    if (lights) {
+        if (numLights != s->numLights) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: %u lights given, scene has %u", who, numLights, s->numLights);
         for (uint32_t l = 0; l < numLights; ++l)
             if (lights[l].vertexOffset != s->hostLights[l].vertexOffset || lights[l].indexOffset != s->hostLights[l].indexOffset ||
                 lights[l].numTriangles != s->hostLights[l].numTriangles)
-                return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_scene_update_instances: light %u changed its mesh", l);
-    if (s->hostTris.empty() || s->hostTris[0].customIndex == 0xffffffffu) return RTR_OK;     /* empty scene: nothing to refit */
-    HIP_TRY(hipSetDevice(s->ctx->device));
-    int rc = ensure_refit_ready(s);
-    if (rc != RTR_OK) return rc;
-    /* frames of OTHER contexts (other streams) may be rendering this scene: everything enqueued on the device so far is joined
-     * before the nodes, records and light tables are rewritten (contract in rtr.h) */
-    HIP_TRY(hipDeviceSynchronize());
+                return fail(RTR_ERR_INVALID_ARGUMENT, "%s: light %u changed its mesh", who, l);
+    }
+    return RTR_OK;
+}
+
+/* The refit both calls end in, on a scene that is refit-ready and a device that has been joined: world-space records from the device
+ * vertex array, boxes, grid, 4-wide view, host mirrors, boxPad.  instances == NULL keeps the current transforms (and with them the
+ * transform, normal-matrix and mirrored tables); lights == NULL keeps the light infos.  lightTris: remake the light-triangle table even
+ * when no lights are given (the vertices of a light's mesh may have changed). */
+static int refit_scene(rtr_scene* s, const RtrInstance* instances, const RtrAreaLightInfo* lights, bool lightTris) {
     hipStream_t st = s->ctx->stream;
+    const uint32_t numInstances = (uint32_t)s->hostInstances.size(), numLights = s->numLights;
+    const RtrInstance* inst = instances ? instances : s->hostInstances.data();
     rtr_scene_desc view{};
     view.meshes = s->hostMeshes.data(); view.numMeshes = (uint32_t)s->hostMeshes.size();
     view.numInstances = numInstances; view.objects = s->hostObjects.data(); view.numObjects = (uint32_t)s->hostObjects.size();
     view.numLights = s->numLights;
     std::vector<rtrdev::PrimRef> prims; std::vector<rtrdev::InstanceRef> refs;
-    make_prim_tables(&view, instances, prims, refs);
+    make_prim_tables(&view, inst, prims, refs);
     if (!s->hostMasks.empty()) {      /* the refit rewrites the records from this table: the instance masks go with it */
         const std::vector<uint32_t> bits = instance_mask_bits(s, s->hostMasks.data());
         for (rtrdev::PrimRef& pr : prims) pr.flags |= bits[pr.customIndex];
     }
     HIP_TRY(s->prims.upload(prims.data(), prims.size(), st));
     HIP_TRY(s->instRefs.upload(refs.data(), refs.size(), st));
-    std::vector<float> xforms, nmats;
-    instance_tables(numInstances, instances, xforms, nmats);
-    HIP_TRY(hipMemcpyAsync(s->xforms.p, xforms.data(), xforms.size() * sizeof(float), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(s->nmats.p, nmats.data(), nmats.size() * sizeof(float), hipMemcpyHostToDevice, st));
+    std::vector<float> xforms, nmats;      /* outlive the asynchronous copies: the stream is joined below */
+    if (instances) {
+        instance_tables(numInstances, instances, xforms, nmats);
+        HIP_TRY(hipMemcpyAsync(s->xforms.p, xforms.data(), xforms.size() * sizeof(float), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(s->nmats.p, nmats.data(), nmats.size() * sizeof(float), hipMemcpyHostToDevice, st));
+    }
     if (lights && numLights) HIP_TRY(hipMemcpyAsync(s->lights.p, lights, numLights * sizeof(RtrAreaLightInfo), hipMemcpyHostToDevice, st));
     rtrdev::BvhInputs in{s->prims.p, s->instRefs.p, s->vertices.p, s->indices.p};
     hipError_t e = rtrdev::bvh_refit(in, s->numPrims, s->numNodeSlots, device_arrays(s), st);
@@ -855,12 +872,162 @@ int rtr_scene_update_instances(rtr_scene* s, const RtrInstance* instances, uint3
     HIP_TRY(hipMemcpy(s->hostTris.data(), s->tris.p, s->hostTris.size() * 48, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(&s->stats.grid, s->grid.p, sizeof(RtrBvhGrid), hipMemcpyDeviceToHost));
     { const int rc4 = make_wide_nodes(s); if (rc4 != RTR_OK) return rc4; }
-    if (lights && numLights) { const int rcl = make_light_tris(s); if (rcl != RTR_OK) return rcl; }
+    if (lightTris || (lights && numLights)) { const int rcl = make_light_tris(s); if (rcl != RTR_OK) return rcl; }
     HIP_TRY(hipMemcpy(red, s->red.p, sizeof red, hipMemcpyDeviceToHost));
     float mabs; memcpy(&mabs, &red[6], 4);
     s->stats.boxPad = (mabs > 1e-6f ? mabs : 1e-6f) * 3.814697265625e-06f;
-    s->hostInstances.assign(instances, instances + numInstances);
+    if (instances) s->hostInstances.assign(instances, instances + numInstances);
     if (lights && numLights) s->hostLights.assign(lights, lights + numLights);
+    return RTR_OK;
+}
+
+int rtr_scene_update_instances(rtr_scene* s, const RtrInstance* instances, uint32_t numInstances, const RtrAreaLightInfo* lights, uint32_t numLights) {
+    if (!s || (!instances && numInstances)) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_scene_update_instances: null argument");
+    if (numInstances != s->hostInstances.size()) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_scene_update_instances: %u instances given, scene has %zu", numInstances, s->hostInstances.size());
+    int rc = check_refit_args(s, instances, numInstances, lights, numLights, "rtr_scene_update_instances");
+    if (rc != RTR_OK) return rc;
+    if (s->hostTris.empty() || s->hostTris[0].customIndex == 0xffffffffu) return RTR_OK;     /* empty scene: nothing to refit */
+    HIP_TRY(hipSetDevice(s->ctx->device));
+    rc = ensure_refit_ready(s);
+    if (rc != RTR_OK) return rc;
+    /* frames of OTHER contexts (other streams) may be rendering this scene: everything enqueued on the device so far is joined
+     * before the nodes, records and light tables are rewritten (contract in rtr.h) */
+    HIP_TRY(hipDeviceSynchronize());
+    return refit_scene(s, instances, lights, false);
+}
+
+int rtr_scene_update_vertices(rtr_scene* s, const rtr_vertex_range* ranges, uint32_t numRanges, uint32_t positionStride, uint32_t normalStride, uint32_t flags,
+                              const RtrInstance* instances, uint32_t numInstances, const RtrAreaLightInfo* lights, uint32_t numLights) {
+    static const char* who = "rtr_scene_update_vertices";
+    static_assert(sizeof(rtr_vertex_range) == 24, "layout");
+    if (!s) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: null scene", who);
+    if (!ranges || numRanges == 0) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: null ranges (or numRanges == 0): nothing to update", who);
+    if (flags > RTR_VERTICES_DEVICE) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: unknown flag bits 0x%x", who, flags & ~RTR_VERTICES_DEVICE);
+    const bool device = flags == RTR_VERTICES_DEVICE;
+    if ((positionStride & 3u) || positionStride < 12u) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: positionStride %u must be a multiple of 4 and at least 12", who, positionStride);
+    bool anyNormals = false;
+    for (uint32_t r = 0; r < numRanges; ++r) {
+        const rtr_vertex_range& vr = ranges[r];
+        if ((uint64_t)vr.firstVertex + vr.numVertices > s->numVertices)
+            return fail(RTR_ERR_INVALID_ARGUMENT, "%s: range %u (vertices %u .. %llu) leaves the scene's %u vertices", who, r, vr.firstVertex,
+                        (unsigned long long)vr.firstVertex + vr.numVertices, s->numVertices);
+        if (vr.numVertices && !vr.positions) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: range %u has %u vertices and null positions", who, r, vr.numVertices);
+        if (device && ((((uintptr_t)vr.positions) | ((uintptr_t)vr.normals)) & 3u))
+            return fail(RTR_ERR_INVALID_ARGUMENT, "%s: range %u: device pointers must be 4-byte aligned", who, r);
+        anyNormals = anyNormals || (vr.normals && vr.numVertices);
+    }
+    if (anyNormals && ((normalStride & 3u) || normalStride < 12u)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: normalStride %u must be a multiple of 4 and at least 12", who, normalStride);
+    {   /* no two ranges may name a vertex twice: the result would depend on the order the lanes run in */
+        std::vector<uint32_t> order;
+        for (uint32_t r = 0; r < numRanges; ++r) if (ranges[r].numVertices) order.push_back(r);
+        std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return ranges[a].firstVertex < ranges[b].firstVertex; });
+        for (size_t k = 1; k < order.size(); ++k) {
+            const rtr_vertex_range& a = ranges[order[k - 1]]; const rtr_vertex_range& b = ranges[order[k]];
+            if ((uint64_t)a.firstVertex + a.numVertices > b.firstVertex)
+                return fail(RTR_ERR_INVALID_ARGUMENT, "%s: ranges %u and %u overlap (vertex %u)", who, order[k - 1], order[k], b.firstVertex);
+        }
+    }
+    int rc = check_refit_args(s, instances, numInstances, lights, numLights, who);
+    if (rc != RTR_OK) return rc;
+    if (s->hostTris.empty() || s->hostTris[0].customIndex == 0xffffffffu) return RTR_OK;     /* empty scene: nothing to refit */
+
+    /* the device tables of the launches: the ranges in chunks of kVertexRangesPerLaunch, each with its own prefix counts */
+    const uint32_t kChunk = rtrdev::kVertexRangesPerLaunch;
+    const uint32_t numChunks = (numRanges + kChunk - 1) / kChunk;
+    std::vector<rtrdev::VertexRange> table(numRanges);
+    std::vector<uint32_t> prefix((size_t)numRanges + numChunks), chunkBase(numChunks + 1, 0u);
+    for (uint32_t c = 0; c < numChunks; ++c) {
+        uint32_t acc = 0;
+        const uint32_t r0 = c * kChunk, r1 = std::min(numRanges, r0 + kChunk);
+        for (uint32_t r = r0; r < r1; ++r) { prefix[(size_t)r + c] = acc; acc += ranges[r].numVertices; }      /* non-overlapping ranges inside a 32-bit array: no wrap */
+        prefix[(size_t)r1 + c] = acc;
+        chunkBase[c + 1] = chunkBase[c] + acc;
+    }
+    auto name_bad = [&](uint64_t concat, uint32_t* range, uint32_t* vertex) {      /* concatenated index -> (range, vertex in it) */
+        uint32_t r = 0; uint64_t before = 0;
+        while (before + ranges[r].numVertices <= concat) before += ranges[r++].numVertices;
+        *range = r; *vertex = (uint32_t)(concat - before);
+    };
+
+    HIP_TRY(hipSetDevice(s->ctx->device));
+    hipStream_t st = s->ctx->stream;
+    const uint32_t posWords = device ? positionStride / 4u : 3u, nrmWords = device ? normalStride / 4u : 3u;
+    if (!device) {
+        /* host data: checked here, then packed (three words per vertex: all positions, then the normals of the ranges that bring them)
+         * and staged in a device buffer of the scene, from where it takes the path of device data */
+        size_t words = 0;
+        for (uint32_t r = 0; r < numRanges; ++r) words += (size_t)ranges[r].numVertices * (ranges[r].normals ? 6u : 3u);
+        s->vtxHost.resize(words);
+        size_t at = 0;
+        for (uint32_t r = 0; r < numRanges; ++r) {
+            const char* src = static_cast<const char*>(ranges[r].positions);
+            for (uint32_t v = 0; v < ranges[r].numVertices; ++v, at += 3) {
+                float p[3];
+                memcpy(p, src + (size_t)v * positionStride, sizeof p);
+                for (int k = 0; k < 3; ++k)
+                    if (!(p[k] > -3.0e38f && p[k] < 3.0e38f))
+                        return fail(RTR_ERR_INVALID_ARGUMENT, "%s: range %u, vertex %u (scene vertex %u): non-finite position", who, r, v, ranges[r].firstVertex + v);
+                memcpy(&s->vtxHost[at], p, sizeof p);
+            }
+        }
+        HIP_TRY(s->vtxStage.grow(words));
+        size_t pos = 0;
+        for (uint32_t r = 0; r < numRanges; ++r) {
+            table[r] = rtrdev::VertexRange{s->vtxStage.p + pos, nullptr, ranges[r].firstVertex, 0u};
+            pos += (size_t)ranges[r].numVertices * 3u;
+        }
+        for (uint32_t r = 0; r < numRanges; ++r) {
+            if (!ranges[r].normals || !ranges[r].numVertices) continue;
+            const char* src = static_cast<const char*>(ranges[r].normals);
+            table[r].normals = s->vtxStage.p + at;
+            for (uint32_t v = 0; v < ranges[r].numVertices; ++v, at += 3) memcpy(&s->vtxHost[at], src + (size_t)v * normalStride, 12);
+        }
+    } else {
+        for (uint32_t r = 0; r < numRanges; ++r)
+            table[r] = rtrdev::VertexRange{static_cast<const uint32_t*>(ranges[r].positions), ranges[r].numVertices ? static_cast<const uint32_t*>(ranges[r].normals) : nullptr,
+                                           ranges[r].firstVertex, 0u};
+    }
+    /* renders and queries of other streams read the vertices, and with RTR_VERTICES_DEVICE the caller's data may still be in the
+     * making on one of them: everything enqueued on the device so far is joined (contract in rtr.h) */
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(s->vtxRanges.grow(table.size()));
+    HIP_TRY(s->vtxPrefix.grow(prefix.size() + 1));        /* the last word: first bad vertex */
+    uint32_t* firstBad = s->vtxPrefix.p + prefix.size();
+    const uint32_t none = 0xffffffffu;
+    HIP_TRY(hipMemcpyAsync(s->vtxRanges.p, table.data(), table.size() * sizeof(rtrdev::VertexRange), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(s->vtxPrefix.p, prefix.data(), prefix.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(firstBad, &none, sizeof none, hipMemcpyHostToDevice, st));
+    if (!device && !s->vtxHost.empty()) HIP_TRY(hipMemcpyAsync(s->vtxStage.p, s->vtxHost.data(), s->vtxHost.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    for (uint32_t c = 0; c < numChunks; ++c) {
+        const uint32_t r0 = c * kChunk, n = std::min(numRanges, r0 + kChunk) - r0;
+        const hipError_t e = rtrdev::launch_check_vertices(s->vtxRanges.p + r0, s->vtxPrefix.p + r0 + c, n, chunkBase[c + 1] - chunkBase[c], posWords, chunkBase[c], firstBad, st);
+        if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: checking kernel: %s", who, hipGetErrorString(e));
+    }
+    uint32_t bad = none;
+    HIP_TRY(hipMemcpyAsync(&bad, firstBad, sizeof bad, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (bad != none) {
+        uint32_t r = 0, v = 0;
+        name_bad(bad, &r, &v);
+        return fail(RTR_ERR_INVALID_ARGUMENT, "%s: range %u, vertex %u (scene vertex %u): non-finite position", who, r, v, ranges[r].firstVertex + v);
+    }
+    /* nothing of the scene has been touched up to here */
+    rc = ensure_refit_ready(s);
+    if (rc != RTR_OK) return rc;
+    for (uint32_t c = 0; c < numChunks; ++c) {
+        const uint32_t r0 = c * kChunk, n = std::min(numRanges, r0 + kChunk) - r0;
+        const hipError_t e = rtrdev::launch_write_vertices(s->vtxRanges.p + r0, s->vtxPrefix.p + r0 + c, n, chunkBase[c + 1] - chunkBase[c], posWords, nrmWords, s->vertices.p, st);
+        if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: writing kernel: %s", who, hipGetErrorString(e));
+    }
+    return refit_scene(s, instances, lights, true);
+}
+
+int rtr_scene_export_vertices(const rtr_scene* s, RtrVertex* out, size_t bytes) {
+    if (!s || (!out && bytes)) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_scene_export_vertices: null argument");
+    if (bytes != (size_t)s->numVertices * sizeof(RtrVertex)) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_scene_export_vertices: bytes %zu != %zu", bytes, (size_t)s->numVertices * sizeof(RtrVertex));
+    if (!bytes) return RTR_OK;
+    HIP_TRY(hipSetDevice(s->ctx->device));
+    HIP_TRY(hipMemcpy(out, s->vertices.p, bytes, hipMemcpyDeviceToHost));
     return RTR_OK;
 }
 

@@ -293,6 +293,60 @@ int  rtr_scene_update_vertices(rtr_scene* scene, const rtr_vertex_range* ranges,
 /* Copy out the device vertex array as it is now (test / oracle hook like rtr_scene_export_bvh, and what rtr_scene_create_like needs
  * after a deformation): numVertices records; RTR_ERR_INVALID_ARGUMENT for a null pointer or a `bytes` that is not numVertices * 48. */
 int  rtr_scene_export_vertices(const rtr_scene* scene, RtrVertex* out, size_t bytes);
+/* The SAH cost of the tree the kernels walk NOW: what a refit did to the tree's quality, and what a rebuild would win back.  A refit
+ * keeps the split decisions made for the old shape, and rtr_scene_stats::sahCost is the host builder's number at creation (0 for a device
+ * build), which no update ever touches; this is the measure a caller decides with (rtr_scene_rebuild below).
+ * Defined on the quantised BVH2 (RtrBvhNode on RtrBvhGrid, what rtr_scene_export_bvh shows), in integers: for a child box,
+ * d[a] = max(0, qmax[a] - qmin[a]) in grid steps and its area triple is (d.x d.y, d.y d.z, d.z d.x).  Over the nodes that are part of the
+ * tree (a device build leaves slots of its node array unused; they are skipped):
+ *   innerArea   every child slot that holds an inner node adds its triple; the root's own box — the union of its two child boxes in grid
+ *               coordinates — adds its triple too
+ *   leafArea    every child slot that holds a leaf adds count * triple, count = (code & 7) + 1
+ *   rootArea    the root box's triple
+ *   numInner    the inner nodes of the tree (the root included)      numLeafRefs    the child slots that hold a leaf
+ * d <= 65535, count <= 8 and at most 2^25 nodes keep every sum below 2^61: the sums are exact and identical from run to run.  Then, in
+ * double, in exactly this order, with (sx, sy, sz) = grid.scale and W(a) = a[0]*sx*sy + a[1]*sy*sz + a[2]*sz*sx:
+ *   sah = (W(innerArea) * 1.0 + W(leafArea) * 1.0) / W(rootArea)        (0 where W(rootArea) is 0)
+ * — the unit costs are the host builder's defaults, costTraverse = costIntersect = 1.  A scene of a single leaf stores it as both
+ * children of the root, and it counts twice, as the formula says (the empty scene's one degenerate triangle is such a leaf: its box is
+ * padded like every box, has an area on its own grid, and prices as 3).  The number prices the BVH2; the any-hit kernel walks the 4-wide view
+ * made from it, and how well one predicts the other's frame time is a measurement (profiles/rebuild/rebuild_rate.json), not a promise.
+ * rtr_scene_tree_cost: a device kernel (kernels/rtr_bvh.hip, k_tree_cost) over the scene's node array, enqueued on the scene's
+ * context stream and joined before the words are read; it writes nothing a render reads, so it does not join the whole device, and it is
+ * ordered behind the update calls, which return complete.  rtr_host_tree_cost: the host restatement, a walk from the root over `nodes`
+ * (nodeBytes = a multiple of 32, at least one node; rtr_host_build_bvh or rtr_scene_export_bvh output) — the same integers, no device:
+ * tree experiments price a refit on the CPU.  RTR_ERR_INVALID_ARGUMENT (with a message) for a null pointer, a nodeBytes that is 0 or
+ * not a multiple of sizeof(RtrBvhNode), or a child index outside the array. */
+typedef struct rtr_tree_cost {
+    uint64_t innerArea[3], leafArea[3], rootArea[3];
+    uint64_t numInner, numLeafRefs;
+    double   sah;
+} rtr_tree_cost;                           /* 96 bytes */
+#ifdef __cplusplus
+static_assert(sizeof(rtr_tree_cost) == 96 && alignof(rtr_tree_cost) == 8, "rtr_tree_cost is 96 B, 8-byte aligned");
+#endif
+int  rtr_scene_tree_cost(const rtr_scene* scene, rtr_tree_cost* out);
+int  rtr_host_tree_cost(const RtrBvhNode* nodes, size_t nodeBytes, const RtrBvhGrid* grid, rtr_tree_cost* out);
+/* Build the tree AGAIN, in place, from the vertices and transforms the scene has now — Vulkan's MODE_BUILD on a live acceleration
+ * structure, where the update calls above are MODE_UPDATE.  buildFlags: RTR_BUILD_DEVICE_LBVH — the device build of rtr_scene_create,
+ * fed from the scene's own device vertex and index arrays and its current instances (nothing goes through the host but the mirrors and
+ * stats creation also reads back; its scratch is kept by the scene after the first such call and reused) — or RTR_BUILD_HOST_SAH —
+ * vertices and indices are read back, the host builder runs as at creation and the result is uploaded: "the pose changed once, now trace
+ * fast".  A scene of fewer than 16 triangles takes the host builder whatever the flag, as in rtr_scene_create.  The result is the tree
+ * (nodes, records, 4-wide view, grid, stats) rtr_scene_create would make from rtr_scene_export_vertices' array with that flag, byte for
+ * byte (tested); stats.sahCost is the host builder's number, or 0 after a device build, as at creation.
+ * Everything else stays: textures, HDRI, LTC tables, vertices, indices, objects, light tables, the transform, normal-matrix and
+ * mirrored tables, the instance masks (the new records carry them; the getter returns what was set), and every pointer a caller holds.
+ * Frames created before the call render the new tree afterwards with no further step.  The triangle -> leaf table is DROPPED (the leaf
+ * order changed) and remade by the next rtr_hit_leaves / rtr_light_rays_hinted under the first-use rule above; start hints a caller
+ * made BEFORE the rebuild are stale, and, by the contract of the hinted calls, still safe: they change no byte of any answer, only the
+ * work saved.  After a host rebuild the next update call prepares its refit arrays for the new tree, as after a host creation.
+ * Synchronisation: as the other update calls (above): the call joins the whole device, rewrites, and returns when the new state is
+ * complete.  The new tree is built into arrays of its own and swapped in only on success: a refused or failed build —
+ * RTR_ERR_INVALID_ARGUMENT (with a message) for a null scene or a buildFlags above RTR_BUILD_DEVICE_LBVH, RTR_ERR_BVH_TOO_DEEP from a
+ * build's depth check — leaves the scene as it was (HIP runtime errors excepted).  An empty scene returns RTR_OK and does nothing.
+ * Scenes replicated by librtr_mgpu have no rebuild path, as they have no update path. */
+int  rtr_scene_rebuild(rtr_scene* scene, uint32_t buildFlags);
 /* Instance cull masks: VkAccelerationStructureInstanceKHR::mask (reference src/vulkan/raytracing/tlas.cppm:63, instance.setMask(0xFF): the
  * only value the reference uses).  masks: a HOST array, one byte per instance, in instance order (rtr_scene_desc::instances); every new
  * scene — one made by rtr_scene_create_like too — starts with 0xff everywhere.  Only the MASKED ray queries (rtr_trace_rays_masked,

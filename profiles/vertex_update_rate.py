@@ -59,6 +59,23 @@ def frame_ms(ctx, scene, s, p):
     return {"ms_min": min(ms[2:]), "ms_all": ms[2:]}
 
 
+def deformed(d, strength):
+    """(the description's vertices as (n, 12) float32, the same with every object vertex moved along its normal by `strength` x the
+    scene's diagonal x a sine of its position, [(first vertex, count) of the object meshes]); profiles/rebuild_rate.py sweeps strength"""
+    n = d.numVertices
+    old = np.ctypeslib.as_array(C.cast(d.vertices, C.POINTER(C.c_float)), (n, 12)).copy()
+    light_meshes = {d.instances[i].meshIndex for i in range(d.numInstances) if d.instances[i].customIndex < d.numLights}
+    diag = float(np.linalg.norm(old[:, 0:3].max(0).astype(np.float64) - old[:, 0:3].min(0)))
+    new = old.copy()
+    meshes = [(int(d.meshes[m].vertexOffset), int(d.meshes[m].vertexCount)) for m in range(d.numMeshes) if m not in light_meshes]
+    for first, count in meshes:
+        p, nrm = old[first:first + count, 0:3].astype(np.float64), old[first:first + count, 4:7].astype(np.float64)
+        phase = p @ np.array([1.0, 1.7, 0.6]) * (2 * np.pi * 4 / diag)
+        new[first:first + count, 0:3] = (p + strength * diag * np.sin(phase)[:, None] * nrm).astype(np.float32)
+    assert (new[:, 0:3] != old[:, 0:3]).any(), "the scene stores no normals to deform along"
+    return old, new, meshes
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--width", type=int, default=1920)
@@ -71,16 +88,7 @@ def main():
     s = scenes.sponza_class(W, H)
     d = s.desc
     n = d.numVertices
-    old = np.ctypeslib.as_array(C.cast(d.vertices, C.POINTER(C.c_float)), (n, 12)).copy()
-    light_meshes = {d.instances[i].meshIndex for i in range(d.numInstances) if d.instances[i].customIndex < d.numLights}
-    diag = float(np.linalg.norm(old[:, 0:3].max(0).astype(np.float64) - old[:, 0:3].min(0)))
-    new = old.copy()
-    meshes = [(int(d.meshes[m].vertexOffset), int(d.meshes[m].vertexCount)) for m in range(d.numMeshes) if m not in light_meshes]
-    for first, count in meshes:
-        p, nrm = old[first:first + count, 0:3].astype(np.float64), old[first:first + count, 4:7].astype(np.float64)
-        phase = p @ np.array([1.0, 1.7, 0.6]) * (2 * np.pi * 4 / diag)
-        new[first:first + count, 0:3] = (p + 0.01 * diag * np.sin(phase)[:, None] * nrm).astype(np.float32)
-    assert (new[:, 0:3] != old[:, 0:3]).any(), "the scene stores no normals to deform along"
+    old, new, meshes = deformed(d, 0.01)
     big_first, big_count = max(meshes, key=lambda m: m[1])
 
     scene = api.Scene(ctx, d)

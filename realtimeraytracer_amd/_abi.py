@@ -90,6 +90,12 @@ class rtr_vertex_range(C.Structure):
     _fields_ = [("firstVertex", u32), ("numVertices", u32), ("positions", C.c_void_p), ("normals", C.c_void_p)]
 
 
+class rtr_tree_cost(C.Structure):
+    """rtr_scene_tree_cost / rtr_host_tree_cost: the integer area sums of the quantised BVH2 (x*y, y*z, z*x in grid steps), the two counts,
+    and the SAH cost made from them with the grid's scale"""
+    _fields_ = [("innerArea", u64 * 3), ("leafArea", u64 * 3), ("rootArea", u64 * 3), ("numInner", u64), ("numLeafRefs", u64), ("sah", C.c_double)]
+
+
 class rtr_texture(C.Structure):
     _fields_ = [("pixels", C.POINTER(C.c_uint8)), ("width", u32), ("height", u32), ("channels", u32), ("_pad", u32)]
 
@@ -143,6 +149,7 @@ assert C.sizeof(RtrRay) == 32 and C.sizeof(RtrHit) == 32 and C.sizeof(rtr_query_
 assert C.sizeof(RtrSurface) == 80
 assert C.sizeof(RtrRadiance) == 48 and C.sizeof(rtr_light_params) == 32
 assert C.sizeof(rtr_vertex_range) == 24
+assert C.sizeof(rtr_tree_cost) == 96 and C.alignment(rtr_tree_cost) == 8
 
 # enum rtr_image
 IMAGE_ANALYTIC, IMAGE_SHADOWED, IMAGE_UNSHADOWED = 0, 1, 2
@@ -189,6 +196,9 @@ RTR_SYMBOLS = {
     "rtr_scene_update_instances": (C.c_int, [VP, P(RtrInstance), u32, P(RtrAreaLightInfo), u32]),
     "rtr_scene_update_vertices": (C.c_int, [VP, P(rtr_vertex_range), u32, u32, u32, u32, P(RtrInstance), u32, P(RtrAreaLightInfo), u32]),
     "rtr_scene_export_vertices": (C.c_int, [VP, VP, C.c_size_t]),
+    "rtr_scene_tree_cost": (C.c_int, [VP, P(rtr_tree_cost)]),
+    "rtr_host_tree_cost": (C.c_int, [VP, C.c_size_t, P(RtrBvhGrid), P(rtr_tree_cost)]),
+    "rtr_scene_rebuild": (C.c_int, [VP, u32]),
     "rtr_scene_set_instance_masks": (C.c_int, [VP, VP, u32]),
     "rtr_scene_get_instance_masks": (C.c_int, [VP, VP, u32]),
     "rtr_frame_create": (C.c_int, [VP, u32, u32, u32, P(VP)]),

@@ -69,10 +69,34 @@ class BvhExport(tuple):
     stats = None
 
 
+class TreeCost:
+    """What Scene.tree_cost and host_tree_cost give back: the integer area sums of the quantised BVH2 as Python ints — inner_area,
+    leaf_area, root_area, each (x*y, y*z, z*x) in grid steps — the counts num_inner and num_leaf_refs, and sah, the cost made from the
+    sums with the grid's scale (include/rtr.h, rtr_tree_cost)."""
+
+    def __init__(self, c):
+        self.inner_area = tuple(int(x) for x in c.innerArea)
+        self.leaf_area = tuple(int(x) for x in c.leafArea)
+        self.root_area = tuple(int(x) for x in c.rootArea)
+        self.num_inner, self.num_leaf_refs = int(c.numInner), int(c.numLeafRefs)
+        self.sah = float(c.sah)
+        self.raw = bytes(c)
+
+    def integers(self):
+        return self.inner_area + self.leaf_area + self.root_area + (self.num_inner, self.num_leaf_refs)
+
+    def __eq__(self, other):
+        return isinstance(other, TreeCost) and self.raw == other.raw
+
+    def __repr__(self):
+        return f"TreeCost(sah={self.sah!r}, num_inner={self.num_inner}, num_leaf_refs={self.num_leaf_refs}, root_area={self.root_area})"
+
+
 class Scene:
     def __init__(self, ctx, desc, like=None):
         """like: a Scene made from the same description whose tree is uploaded instead of built again (rtr_scene_create_like)"""
         self.ctx, self.lib = ctx, ctx.lib
+        self._built_sah = None        # tree_cost().sah right after the last build or rebuild: taken on first use (update_vertices' policy)
         self.h = A.VP()
         self._num_instances = int(desc.numInstances)
         self._num_vertices = int(desc.numVertices)
@@ -108,6 +132,43 @@ class Scene:
         else:
             larr = (A.RtrAreaLightInfo * len(lights))(*lights)
             _check(self.lib.rtr_scene_update_instances(self.h, arr, len(instances), larr, len(lights)), "rtr_scene_update_instances")
+
+    def tree_cost(self):
+        """rtr_scene_tree_cost: the SAH cost of the tree the kernels walk now (a device kernel over the quantised BVH2) -> TreeCost"""
+        c = A.rtr_tree_cost()
+        _check(self.lib.rtr_scene_tree_cost(self.h, C.byref(c)), "rtr_scene_tree_cost")
+        return TreeCost(c)
+
+    def rebuild(self, build="device"):
+        """rtr_scene_rebuild: build the tree again, in place, from the vertices and transforms the scene has now.  build: "device" (the
+        LBVH build on the device) or "host" (the SAH builder; vertices are read back).  Everything else of the scene stays; the hints of
+        hit_leaves made before are stale (and still safe)."""
+        flags = {"device": A.BUILD_DEVICE_LBVH, "host": A.BUILD_HOST_SAH}.get(build)
+        if flags is None:
+            raise ValueError(f"rebuild: build must be 'device' or 'host', got {build!r}")
+        _check(self.lib.rtr_scene_rebuild(self.h, flags), "rtr_scene_rebuild")
+        self._built_sah = self.tree_cost().sah
+
+    def update_vertices_or_rebuild(self, ranges, instances=None, lights=None, rebuild_above=None, rebuild_build="device"):
+        """update_vertices with a rebuild policy on top; the arguments before rebuild_above are update_vertices' own.
+        rebuild_above: None (the default) — update_vertices and nothing else, no cost kernel runs — or a number: after the refit, if
+        tree_cost().sah > rebuild_above * (the sah right after the last build or rebuild of this scene), rebuild(rebuild_build).  The
+        build-time sah is taken on first use — before this call's refit — and refreshed by rebuild.  Returns whether it rebuilt.  No
+        ratio is recommended: profiles/rebuild/ is where the relation between sah and frame time is written down."""
+        who = "update_vertices_or_rebuild"
+        if rebuild_above is None:
+            self.update_vertices(ranges, instances, lights)
+            return False
+        rebuild_above = float(rebuild_above)
+        if rebuild_build not in ("device", "host"):
+            raise ValueError(f"{who}: rebuild_build must be 'device' or 'host', got {rebuild_build!r}")
+        if self._built_sah is None:
+            self._built_sah = self.tree_cost().sah
+        self.update_vertices(ranges, instances, lights)
+        if self.tree_cost().sah > rebuild_above * self._built_sah:
+            self.rebuild(rebuild_build)
+            return True
+        return False
 
     def update_vertices(self, ranges, instances=None, lights=None):
         """rtr_scene_update_vertices: deform meshes — new positions (and normals) for ranges of the scene's vertex array, then ONE refit
@@ -344,6 +405,21 @@ def host_build_bvh(desc):
     tris = (A.RtrBvhTri * max(st.numTriangles, 1))()
     _check(lib.rtr_host_build_bvh(C.byref(desc), C.byref(st), nodes, C.sizeof(nodes), tris, C.sizeof(tris)), "rtr_host_build_bvh")
     return st, nodes, tris
+
+
+def host_tree_cost(nodes, grid):
+    """rtr_host_tree_cost: the host restatement of Scene.tree_cost, no device -> TreeCost.  nodes: a ctypes RtrBvhNode array (what
+    host_build_bvh or export_bvh return) or a C-contiguous numpy array of its bytes; grid: the RtrBvhGrid its planes live on (stats.grid /
+    the export's third element)."""
+    lib = A.hip_lib()
+    c = A.rtr_tree_cost()
+    if isinstance(nodes, np.ndarray):
+        nodes = np.ascontiguousarray(nodes)
+        ptr, nbytes = nodes.ctypes.data_as(A.VP), nodes.nbytes
+    else:
+        ptr, nbytes = C.cast(nodes, A.VP), C.sizeof(nodes)
+    _check(lib.rtr_host_tree_cost(ptr, nbytes, C.byref(grid), C.byref(c)), "rtr_host_tree_cost")
+    return TreeCost(c)
 
 
 def host_build_bvh_wide(desc):

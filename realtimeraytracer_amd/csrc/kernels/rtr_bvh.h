@@ -67,4 +67,10 @@ hipError_t bvh_make_wide(const uint4* nodes, uint32_t numNodes, const int32_t* p
 /* out[remap[i]] = in[i] with inner child codes renumbered through remap (a permutation of 0..numNodes-1, remap[0] == 0) */
 hipError_t bvh_permute_wide(const uint4* in, uint32_t numNodes, const uint32_t* remap, uint4* out, hipStream_t stream);
 
+/* The SAH cost sums of a finished (quantised) tree, rtr_scene_tree_cost: words = bvh_tree_cost_words() x u64, zeroed here and filled by
+ * k_tree_cost as innerArea[3], leafArea[3], rootArea[3], numInner, numLeafRefs (rtr_tree_cost's integers, in that order).
+ * parentOrNull: as bvh_make_wide — the refit parent array (slots outside the tree are skipped) or null when every slot is in the tree. */
+size_t bvh_tree_cost_words();
+hipError_t bvh_tree_cost(const uint4* nodes, uint32_t numNodes, const int32_t* parentOrNull, unsigned long long* words, hipStream_t s);
+
 }  // namespace rtrdev

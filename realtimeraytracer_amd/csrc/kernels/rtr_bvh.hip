@@ -410,6 +410,55 @@ __global__ void k_wide_centre_set(const unsigned long long* __restrict__ w, RtrB
     grid->wideCentreZ = c[2];
 }
 
+/* ---- the SAH cost of the tree the kernels walk (rtr_scene_tree_cost) -------------------------------------------------
+ * Integer sums over the quantised BVH2, one lane per node slot; slots that are not part of the tree (parent == -2) are skipped.
+ * A child box's extents d = max(0, qmax - qmin) in grid steps give the area triple (dx dy, dy dz, dz dx); the scale factors are
+ * applied once, on the host, to the finished sums (rtr_api.cpp, finish_tree_cost), so the words are exact and the same bytes on every
+ * run: d <= 65535, count <= 8 and at most 2^25 nodes keep every sum below 2^61.
+ *   w[0..2] innerArea : every child slot that holds an inner node, plus the root's own box (the union of its two child boxes)
+ *   w[3..5] leafArea  : every child slot that holds a leaf, times its triangle count
+ *   w[6..8] rootArea  : the root's box (written by lane 0 of block 0: the root is node 0)
+ *   w[9] numInner (the root included)   w[10] numLeafRefs (child slots that hold a leaf)
+ * The words are zero on entry.  rtr_host_tree_cost restates the sums on the host. */
+constexpr uint32_t kTreeCostWords = 11;
+__device__ __forceinline__ void area_triple(const uint32_t lo[3], const uint32_t hi[3], unsigned long long t[3]) {
+    unsigned long long d[3];
+    for (int k = 0; k < 3; ++k) d[k] = hi[k] > lo[k] ? (unsigned long long)(hi[k] - lo[k]) : 0ull;
+    t[0] = d[0] * d[1]; t[1] = d[1] * d[2]; t[2] = d[2] * d[0];
+}
+__global__ __launch_bounds__(kB) void k_tree_cost(uint32_t numNodes, const uint4* __restrict__ nodes, const int32_t* __restrict__ parent,
+                                                  unsigned long long* __restrict__ w) {
+    const uint32_t i = blockIdx.x * kB + threadIdx.x;
+    unsigned long long s[8] = {0, 0, 0, 0, 0, 0, 0, 0};      /* inner[3], leaf[3], numInner, numLeafRefs */
+    if (i < numNodes && (!parent || parent[i] != -2)) {
+        const uint4 a = nodes[(size_t)i * 2], b = nodes[(size_t)i * 2 + 1];      /* the 32-byte node: two 16-byte loads */
+        const uint32_t lo[2][3] = {{a.x & 0xffffu, a.x >> 16, b.x & 0xffffu}, {a.z & 0xffffu, a.z >> 16, b.y & 0xffffu}};
+        const uint32_t hi[2][3] = {{a.y & 0xffffu, a.y >> 16, b.x >> 16}, {a.w & 0xffffu, a.w >> 16, b.y >> 16}};
+        const int32_t code[2] = {(int32_t)b.z, (int32_t)b.w};
+        unsigned long long t[3];
+#pragma unroll
+        for (int sd = 0; sd < 2; ++sd) {
+            area_triple(lo[sd], hi[sd], t);
+            if (code[sd] >= 0) { s[0] += t[0]; s[1] += t[1]; s[2] += t[2]; s[6] += 1ull; }
+            else {
+                const unsigned long long cnt = ((uint32_t)~code[sd] & 7u) + 1u;
+                s[3] += cnt * t[0]; s[4] += cnt * t[1]; s[5] += cnt * t[2]; s[7] += 1ull;
+            }
+        }
+        if (i == 0) {
+            uint32_t rlo[3], rhi[3];
+            for (int k = 0; k < 3; ++k) { rlo[k] = lo[0][k] < lo[1][k] ? lo[0][k] : lo[1][k]; rhi[k] = hi[0][k] > hi[1][k] ? hi[0][k] : hi[1][k]; }
+            area_triple(rlo, rhi, t);
+            s[0] += t[0]; s[1] += t[1]; s[2] += t[2]; s[6] += 1ull;
+            w[6] = t[0]; w[7] = t[1]; w[8] = t[2];               /* no other lane writes these words */
+        }
+    }
+    for (int q = 0; q < 8; ++q) {
+        const unsigned long long tot = wave_total(s[q]);
+        if ((threadIdx.x & 63u) == 0 && tot) atomicAdd(w + (q < 6 ? q : q + 3), tot);
+    }
+}
+
 /* 4-wide view of the tree for the any-hit kernel (rtr_kernels.hip, k_shadow_trace4): entry n starts from the two children of
  * BVH2 node n and, while a slot is free, opens the inner entry with the largest box into its own two children; boxes are
  * copied from the BVH2 nodes that own them and child codes keep BVH2 node ids, so entry 0 roots a complete 4-wide tree.
@@ -622,6 +671,15 @@ hipError_t bvh_permute_wide(const uint4* in, uint32_t numNodes, const uint32_t* 
 }
 
 size_t bvh_wide_scratch_words() { return kCentreWords; }
+
+size_t bvh_tree_cost_words() { return kTreeCostWords; }
+
+hipError_t bvh_tree_cost(const uint4* nodes, uint32_t numNodes, const int32_t* parentOrNull, unsigned long long* words, hipStream_t s) {
+    BV_TRY(hipMemsetAsync(words, 0, kTreeCostWords * sizeof(unsigned long long), s));
+    if (numNodes == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_tree_cost, dim3((numNodes + kB - 1) / kB), dim3(kB), 0, s, numNodes, nodes, parentOrNull, words);
+    return hipGetLastError();
+}
 
 size_t bvh_sort_temp_bytes(uint32_t numPrims) {
     size_t bytes = 0;

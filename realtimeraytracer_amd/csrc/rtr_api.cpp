@@ -59,6 +59,9 @@ struct DevBuf {
     }
     /* a buffer that is reused from call to call and grows on demand (its old contents are not kept) */
     hipError_t grow(size_t count) { return (p && n >= count) ? hipSuccess : alloc(count + count / 2); }
+    /* a buffer whose size is fixed by its owner and that is kept from call to call: allocated on first use */
+    hipError_t ensure(size_t count) { return (p && n >= count) ? hipSuccess : alloc(count); }
+    void swap(DevBuf& o) { std::swap(p, o.p); std::swap(n, o.n); }
     hipError_t upload(const T* src, size_t count, hipStream_t s) {
         hipError_t e = alloc(count);
         if (e != hipSuccess) return e;
@@ -102,6 +105,15 @@ static void ctx_free(rtr_ctx* c) {
 static void ctx_release_child(rtr_ctx* c) {
     if (--c->children == 0 && c->destroyed) ctx_free(c);
 }
+
+/* what the device LBVH build needs while it runs (rtrdev::BvhScratch): rtr_scene_create frees it with the call, a scene that has been
+ * rebuilt on the device keeps it for the next rebuild (sizes depend on the triangle count alone, which no call changes) */
+struct BuildScratch {
+    DevBuf<float4> trisCanon, minCanon, maxCanon;
+    DevBuf<unsigned long long> keysIn, keysOut;
+    DevBuf<int2> range, rawChild;
+    DevBuf<uint8_t> sortTemp;
+};
 
 struct rtr_scene {
     rtr_ctx* ctx = nullptr;
@@ -157,6 +169,13 @@ struct rtr_scene {
     DevBuf<rtrdev::VertexRange> vtxRanges;
     DevBuf<uint32_t> vtxPrefix, vtxStage;
     std::vector<uint32_t> vtxHost;
+    BuildScratch buildScratch;           /* rtr_scene_rebuild with RTR_BUILD_DEVICE_LBVH: empty until the first one */
+    /* rtr_scene_tree_cost: the kernel's words, and for a tree without refit arrays whose slots are not all reachable, a parent array of
+     * its own (costParentState: 0 not looked at yet, 1 every slot is in the tree, 2 costParent holds it).  mutable: the call takes the
+     * scene const, like the leaf table */
+    mutable DevBuf<unsigned long long> costWords;
+    mutable DevBuf<int32_t> costParent;
+    mutable int costParentState = 0;
     rtr_scene_stats stats{};
     DeviceScene dev{};
     uint32_t numLights = 0, numObjects = 0, numVertices = 0, numIndices = 0;
@@ -540,16 +559,13 @@ static rtrdev::BvhDeviceArrays device_arrays(rtr_scene* s) {
     return a;
 }
 
-/* Device LBVH build into s->nodes / s->tris (+ refit arrays); fills hostNodes/hostTris and the stats. */
-static int build_on_device(rtr_scene* s, const rtr_scene_desc* d, size_t numPrims) {
+/* Device LBVH build into s->nodes / s->tris (+ refit arrays) from the primitive tables and the DEVICE vertex / index arrays given;
+ * fills hostNodes/hostTris and the stats.  The core rtr_scene_create (build_on_device) and rtr_scene_rebuild share: `s` is the scene
+ * that receives the tree, `sc` the scratch (the caller's to keep or free). */
+static int build_on_device_core(rtr_scene* s, const std::vector<rtrdev::PrimRef>& prims, const std::vector<rtrdev::InstanceRef>& refs,
+                                const RtrVertex* vertices, const uint32_t* indices, BuildScratch& bs, size_t numPrims) {
     hipStream_t st = s->ctx->stream;
-    std::vector<rtrdev::PrimRef> prims; std::vector<rtrdev::InstanceRef> refs;
-    make_prim_tables(d, d->instances, prims, refs);
     const uint32_t n = (uint32_t)numPrims, numNodes = n - 1;
-    for (uint32_t v = 0; v < d->numVertices; ++v)
-        for (int k = 0; k < 3; ++k)
-            if (!(d->vertices[v].position[k] > -3.0e38f && d->vertices[v].position[k] < 3.0e38f))
-                return fail(RTR_ERR_INVALID_ARGUMENT, "BVH build: non-finite vertex position in vertex %u", v);
     auto t0 = std::chrono::steady_clock::now();
     HIP_TRY(s->prims.upload(prims.data(), prims.size(), st));
     HIP_TRY(s->instRefs.upload(refs.data(), refs.size(), st));
@@ -557,16 +573,15 @@ static int build_on_device(rtr_scene* s, const rtr_scene_desc* d, size_t numPrim
     HIP_TRY(s->tris.alloc((size_t)n * 3));
     HIP_TRY(s->boxMin.alloc(n)); HIP_TRY(s->boxMax.alloc(n)); HIP_TRY(s->parent.alloc(numNodes));
     HIP_TRY(s->counters.alloc(numNodes)); HIP_TRY(s->depth.alloc(numNodes)); HIP_TRY(s->slotOfPrim.alloc(n)); HIP_TRY(s->red.alloc(8));
-    DevBuf<float4> trisCanon, minCanon, maxCanon; DevBuf<unsigned long long> keysIn, keysOut; DevBuf<int2> range, rawChild; DevBuf<uint8_t> sortTemp;
-    HIP_TRY(trisCanon.alloc((size_t)n * 3)); HIP_TRY(minCanon.alloc(n)); HIP_TRY(maxCanon.alloc(n));
-    HIP_TRY(keysIn.alloc(n)); HIP_TRY(keysOut.alloc(n)); HIP_TRY(range.alloc(numNodes)); HIP_TRY(rawChild.alloc(numNodes));
+    HIP_TRY(bs.trisCanon.ensure((size_t)n * 3)); HIP_TRY(bs.minCanon.ensure(n)); HIP_TRY(bs.maxCanon.ensure(n));
+    HIP_TRY(bs.keysIn.ensure(n)); HIP_TRY(bs.keysOut.ensure(n)); HIP_TRY(bs.range.ensure(numNodes)); HIP_TRY(bs.rawChild.ensure(numNodes));
     rtrdev::BvhScratch sc{};
     sc.sortTempBytes = rtrdev::bvh_sort_temp_bytes(n);
-    HIP_TRY(sortTemp.alloc(sc.sortTempBytes));
-    sc.trisCanon = trisCanon.p; sc.minCanon = minCanon.p; sc.maxCanon = maxCanon.p; sc.keysIn = keysIn.p; sc.keysOut = keysOut.p;
-    sc.range = range.p; sc.rawChild = rawChild.p; sc.sortTemp = sortTemp.p;
+    HIP_TRY(bs.sortTemp.ensure(sc.sortTempBytes));
+    sc.trisCanon = bs.trisCanon.p; sc.minCanon = bs.minCanon.p; sc.maxCanon = bs.maxCanon.p; sc.keysIn = bs.keysIn.p; sc.keysOut = bs.keysOut.p;
+    sc.range = bs.range.p; sc.rawChild = bs.rawChild.p; sc.sortTemp = bs.sortTemp.p;
     HIP_TRY(hipMemsetAsync(s->nodesF.p, 0, (size_t)numNodes * 64, st));
-    rtrdev::BvhInputs in{s->prims.p, s->instRefs.p, s->vertices.p, s->indices.p};
+    rtrdev::BvhInputs in{s->prims.p, s->instRefs.p, vertices, indices};
     hipError_t e = rtrdev::bvh_build_lbvh(in, n, device_arrays(s), sc, st);
     if (e != hipSuccess) return fail(RTR_ERR_HIP, "device BVH build: %s", hipGetErrorString(e));
     HIP_TRY(hipStreamSynchronize(st));
@@ -589,6 +604,18 @@ static int build_on_device(rtr_scene* s, const rtr_scene_desc* d, size_t numPrim
     s->stats.boxPad = (mabs > 1e-6f ? mabs : 1e-6f) * 3.814697265625e-06f;
     s->numPrims = n; s->numNodeSlots = numNodes; s->refitReady = true;
     return RTR_OK;
+}
+
+/* rtr_scene_create's device build: the tables from the description, the vertices it uploaded; the scratch goes with the call */
+static int build_on_device(rtr_scene* s, const rtr_scene_desc* d, size_t numPrims) {
+    std::vector<rtrdev::PrimRef> prims; std::vector<rtrdev::InstanceRef> refs;
+    make_prim_tables(d, d->instances, prims, refs);
+    for (uint32_t v = 0; v < d->numVertices; ++v)
+        for (int k = 0; k < 3; ++k)
+            if (!(d->vertices[v].position[k] > -3.0e38f && d->vertices[v].position[k] < 3.0e38f))
+                return fail(RTR_ERR_INVALID_ARGUMENT, "BVH build: non-finite vertex position in vertex %u", v);
+    BuildScratch scratch;
+    return build_on_device_core(s, prims, refs, s->vertices.p, s->indices.p, scratch, numPrims);
 }
 
 static void instance_tables(uint32_t numInstances, const RtrInstance* instances, std::vector<float>& xforms, std::vector<float>& nmats) {
@@ -736,6 +763,24 @@ static int scene_create_impl(rtr_ctx* ctx, const rtr_scene_desc* d, const rtr_sc
     return RTR_OK;
 }
 
+/* parent links of a node array, as the refit keeps them: (parentIndex << 1) | slot, -1 for the root, -2 for a slot the root does not
+ * reach; returns how many slots it reaches */
+static size_t host_parent_array(const std::vector<RtrBvhNode>& nodes, std::vector<int32_t>& parent) {
+    parent.assign(nodes.size(), -2);
+    if (nodes.empty()) return 0;
+    parent[0] = -1;
+    size_t reached = 1;
+    std::vector<uint32_t> stack{0};
+    while (!stack.empty()) {
+        const uint32_t i = stack.back(); stack.pop_back();
+        for (int sl = 0; sl < 2; ++sl) {
+            const int32_t c = nodes[i].child[sl];
+            if (c >= 0 && parent[(size_t)c] == -2) { parent[(size_t)c] = (int32_t)((i << 1) | (uint32_t)sl); stack.push_back((uint32_t)c); ++reached; }
+        }
+    }
+    return reached;
+}
+
 /* A host-built tree gets its refit arrays on the first update: parent links from the node array, the
  * canonical-primitive -> leaf-slot map from the ids stored in the triangle records. */
 static int ensure_refit_ready(rtr_scene* s) {
@@ -743,16 +788,8 @@ static int ensure_refit_ready(rtr_scene* s) {
     if (s->hostInstances.empty()) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_scene_update_instances: the scene has no instances");
     hipStream_t st = s->ctx->stream;
     const uint32_t numNodes = (uint32_t)s->hostNodes.size(), n = (uint32_t)s->hostTris.size();
-    std::vector<int32_t> parent(numNodes, -2);
-    parent[0] = -1;
-    std::vector<uint32_t> stack{0};
-    while (!stack.empty()) {
-        const uint32_t i = stack.back(); stack.pop_back();
-        for (int sl = 0; sl < 2; ++sl) {
-            const int32_t c = s->hostNodes[i].child[sl];
-            if (c >= 0 && parent[(size_t)c] == -2) { parent[(size_t)c] = (int32_t)((i << 1) | (uint32_t)sl); stack.push_back((uint32_t)c); }
-        }
-    }
+    std::vector<int32_t> parent;
+    host_parent_array(s->hostNodes, parent);
     /* canonical order = instances in creation order, primitives in mesh order */
     std::vector<uint32_t> base(s->hostInstances.size(), 0);       /* by customIndex */
     uint32_t acc = 0;
@@ -1029,6 +1066,161 @@ int rtr_scene_export_vertices(const rtr_scene* s, RtrVertex* out, size_t bytes) 
     HIP_TRY(hipSetDevice(s->ctx->device));
     HIP_TRY(hipMemcpy(out, s->vertices.p, bytes, hipMemcpyDeviceToHost));
     return RTR_OK;
+}
+
+/* ---- the cost of the tree, and the rebuild (contracts in rtr.h) ---- */
+/* the integer sums are complete: sah from them in double, in the order rtr.h states (-ffp-contract=off: no fused step) */
+static void finish_tree_cost(rtr_tree_cost* c, const RtrBvhGrid& grid) {
+    const double sx = grid.scale[0], sy = grid.scale[1], sz = grid.scale[2];
+    auto W = [&](const uint64_t* a) { return (double)a[0] * sx * sy + (double)a[1] * sy * sz + (double)a[2] * sz * sx; };
+    const double root = W(c->rootArea);
+    c->sah = root > 0.0 ? (W(c->innerArea) * 1.0 + W(c->leafArea) * 1.0) / root : 0.0;
+}
+
+int rtr_host_tree_cost(const RtrBvhNode* nodes, size_t nodeBytes, const RtrBvhGrid* grid, rtr_tree_cost* out) {
+    if (!nodes || !grid || !out) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_host_tree_cost: null argument");
+    if (nodeBytes == 0 || nodeBytes % sizeof(RtrBvhNode)) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_host_tree_cost: nodeBytes %zu is not a positive multiple of %zu", nodeBytes, sizeof(RtrBvhNode));
+    const size_t n = nodeBytes / sizeof(RtrBvhNode);
+    rtr_tree_cost c{};
+    auto triple = [](const uint32_t lo[3], const uint32_t hi[3], uint64_t t[3]) {
+        uint64_t d[3];
+        for (int k = 0; k < 3; ++k) d[k] = hi[k] > lo[k] ? (uint64_t)(hi[k] - lo[k]) : 0u;
+        t[0] = d[0] * d[1]; t[1] = d[1] * d[2]; t[2] = d[2] * d[0];
+    };
+    /* the walk from the root: every node it reaches is counted once, whichever slots name it */
+    std::vector<uint8_t> seen(n, 0);
+    std::vector<uint32_t> stack{0};
+    seen[0] = 1;
+    while (!stack.empty()) {
+        const uint32_t i = stack.back(); stack.pop_back();
+        const RtrBvhNode& nd = nodes[i];
+        uint32_t lo[2][3], hi[2][3];
+        uint64_t t[3];
+        for (int sd = 0; sd < 2; ++sd) {
+            for (int a = 0; a < 3; ++a) { lo[sd][a] = nd.q[RTR_BVH_QSLOT(sd, 0, a)]; hi[sd][a] = nd.q[RTR_BVH_QSLOT(sd, 1, a)]; }
+            triple(lo[sd], hi[sd], t);
+            const int32_t code = nd.child[sd];
+            if (code >= 0) {
+                if ((size_t)code >= n) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_host_tree_cost: node %u names child %d, the array has %zu nodes", i, code, n);
+                for (int k = 0; k < 3; ++k) c.innerArea[k] += t[k];
+                ++c.numInner;
+                if (!seen[(size_t)code]) { seen[(size_t)code] = 1; stack.push_back((uint32_t)code); }
+            } else {
+                const uint64_t cnt = ((uint32_t)~code & 7u) + 1u;
+                for (int k = 0; k < 3; ++k) c.leafArea[k] += cnt * t[k];
+                ++c.numLeafRefs;
+            }
+        }
+        if (i == 0) {
+            uint32_t rlo[3], rhi[3];
+            for (int a = 0; a < 3; ++a) { rlo[a] = std::min(lo[0][a], lo[1][a]); rhi[a] = std::max(hi[0][a], hi[1][a]); }
+            triple(rlo, rhi, t);
+            for (int k = 0; k < 3; ++k) { c.innerArea[k] += t[k]; c.rootArea[k] = t[k]; }
+            ++c.numInner;
+        }
+    }
+    finish_tree_cost(&c, *grid);
+    *out = c;
+    return RTR_OK;
+}
+
+int rtr_scene_tree_cost(const rtr_scene* s, rtr_tree_cost* out) {
+    if (!s || !out) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_scene_tree_cost: null argument");
+    HIP_TRY(hipSetDevice(s->ctx->device));
+    hipStream_t st = s->ctx->stream;
+    const uint32_t numNodes = (uint32_t)s->hostNodes.size();
+    /* which slots are part of the tree: the refit's parent array where the scene has one (a device build leaves slots unused); a host
+     * tree without one is looked at once, and gets a parent array of its own only if the root does not reach every slot */
+    const int32_t* parent = s->refitReady ? s->parent.p : nullptr;
+    if (!s->refitReady && s->costParentState == 0) {
+        std::vector<int32_t> par;
+        if (host_parent_array(s->hostNodes, par) == s->hostNodes.size()) s->costParentState = 1;
+        else { HIP_TRY(s->costParent.upload(par.data(), par.size(), st)); s->costParentState = 2; }
+    }
+    if (!s->refitReady && s->costParentState == 2) parent = s->costParent.p;
+    const size_t words = rtrdev::bvh_tree_cost_words();
+    HIP_TRY(s->costWords.ensure(words));
+    const hipError_t e = rtrdev::bvh_tree_cost(s->nodes.p, numNodes, parent, s->costWords.p, st);
+    if (e != hipSuccess) return fail(RTR_ERR_HIP, "rtr_scene_tree_cost: kernel launch: %s", hipGetErrorString(e));
+    uint64_t w[11];
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "layout");
+    if (words != 11) return fail(RTR_ERR_HIP, "rtr_scene_tree_cost: the kernel has %zu words, the host expects 11", words);
+    HIP_TRY(hipMemcpyAsync(w, s->costWords.p, sizeof w, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    rtr_tree_cost c{};
+    for (int k = 0; k < 3; ++k) { c.innerArea[k] = w[k]; c.leafArea[k] = w[3 + k]; c.rootArea[k] = w[6 + k]; }
+    c.numInner = w[9]; c.numLeafRefs = w[10];
+    finish_tree_cost(&c, s->stats.grid);
+    *out = c;
+    return RTR_OK;
+}
+
+/* the new tree moves from the scene it was built in (`t`) into `s`; `t` takes the old one away with it */
+static void swap_tree(rtr_scene* s, rtr_scene* t) {
+    s->nodes.swap(t->nodes); s->nodesF.swap(t->nodesF); s->grid.swap(t->grid); s->wideSums.swap(t->wideSums); s->nodes4tmp.swap(t->nodes4tmp);
+    s->wideRemap.swap(t->wideRemap); s->wideShape.swap(t->wideShape); s->hostWideShape.swap(t->hostWideShape); std::swap(s->wideReached, t->wideReached);
+    s->nodes4.swap(t->nodes4); s->tris.swap(t->tris); s->hostNodes.swap(t->hostNodes); s->hostTris.swap(t->hostTris);
+    s->prims.swap(t->prims); s->instRefs.swap(t->instRefs); s->boxMin.swap(t->boxMin); s->boxMax.swap(t->boxMax); s->parent.swap(t->parent);
+    s->counters.swap(t->counters); s->depth.swap(t->depth); s->slotOfPrim.swap(t->slotOfPrim); s->red.swap(t->red);
+    std::swap(s->numPrims, t->numPrims); std::swap(s->numNodeSlots, t->numNodeSlots); std::swap(s->refitReady, t->refitReady);
+    std::swap(s->stats, t->stats);
+}
+
+int rtr_scene_rebuild(rtr_scene* s, uint32_t buildFlags) {
+    static const char* who = "rtr_scene_rebuild";
+    if (!s) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: null scene", who);
+    if (buildFlags > RTR_BUILD_DEVICE_LBVH) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: unknown buildFlags %u", who, buildFlags);
+    if (s->hostTris.empty() || s->hostTris[0].customIndex == 0xffffffffu) return RTR_OK;     /* empty scene: nothing to build */
+    HIP_TRY(hipSetDevice(s->ctx->device));
+    /* frames and queries of OTHER contexts (other streams) may be walking this tree: everything enqueued on the device so far is joined
+     * before it is replaced (contract in rtr.h, as the update calls) */
+    HIP_TRY(hipDeviceSynchronize());
+    hipStream_t st = s->ctx->stream;
+    const size_t totalPrims = s->hostTris.size();
+    const bool deviceBuild = buildFlags == RTR_BUILD_DEVICE_LBVH && totalPrims >= 16;     /* tiny scenes: the host builder, as at creation */
+    rtr_scene_desc view{};
+    view.meshes = s->hostMeshes.data(); view.numMeshes = (uint32_t)s->hostMeshes.size();
+    view.instances = s->hostInstances.data(); view.numInstances = (uint32_t)s->hostInstances.size();
+    view.objects = s->hostObjects.data(); view.numObjects = (uint32_t)s->hostObjects.size();
+    view.lights = s->hostLights.data(); view.numLights = s->numLights;
+    std::vector<uint32_t> maskBits;       /* the new records carry the instance masks, as a refit's do */
+    if (!s->hostMasks.empty()) maskBits = instance_mask_bits(s, s->hostMasks.data());
+    /* the new tree is built in a scene of its own that shares nothing with `s` but the context: whatever fails, `s` is as it was */
+    struct Temp { rtr_scene* p; ~Temp() { delete p; } } tmp{new rtr_scene()};
+    rtr_scene* t = tmp.p;
+    t->ctx = s->ctx;
+    int rc = RTR_OK;
+    if (deviceBuild) {
+        std::vector<rtrdev::PrimRef> prims; std::vector<rtrdev::InstanceRef> refs;
+        make_prim_tables(&view, s->hostInstances.data(), prims, refs);
+        if (!maskBits.empty()) for (rtrdev::PrimRef& pr : prims) pr.flags |= maskBits[pr.customIndex];
+        rc = build_on_device_core(t, prims, refs, s->vertices.p, s->indices.p, s->buildScratch, totalPrims);
+        if (rc != RTR_OK) return rc;
+    } else {
+        std::vector<RtrVertex> vertices(s->numVertices); std::vector<uint32_t> indices(s->numIndices);
+        if (s->numVertices) HIP_TRY(hipMemcpy(vertices.data(), s->vertices.p, vertices.size() * sizeof(RtrVertex), hipMemcpyDeviceToHost));
+        if (s->numIndices) HIP_TRY(hipMemcpy(indices.data(), s->indices.p, indices.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        view.vertices = vertices.data(); view.numVertices = s->numVertices; view.indices = indices.data(); view.numIndices = s->numIndices;
+        rtr::BvhResult bvh; std::vector<float> xforms, nmats; uint32_t stackEntries = 0; size_t numTris = 0;
+        rc = flatten_and_build(&view, bvh, xforms, nmats, &stackEntries, &numTris);      /* the transform tables it fills are the scene's own already */
+        if (rc != RTR_OK) return rc;
+        if (!maskBits.empty()) for (RtrBvhTri& tr : bvh.tris) if (tr.customIndex < maskBits.size()) tr.flags |= maskBits[tr.customIndex];
+        HIP_TRY(t->nodes.upload(reinterpret_cast<const uint4*>(bvh.nodes.data()), bvh.nodes.size() * 2, st));
+        HIP_TRY(t->grid.upload(&bvh.grid, 1, st));
+        HIP_TRY(t->tris.upload(reinterpret_cast<const float4*>(bvh.tris.data()), bvh.tris.size() * 3, st));
+        fill_stats(t->stats, bvh, stackEntries, numTris);
+        t->hostNodes.swap(bvh.nodes); t->hostTris.swap(bvh.tris); t->hostWideShape.swap(bvh.wideShape);
+        t->numPrims = (uint32_t)t->hostTris.size(); t->numNodeSlots = (uint32_t)t->hostNodes.size();
+    }
+    rc = make_wide_nodes(t);
+    if (rc != RTR_OK) return rc;
+    swap_tree(s, t);
+    DeviceScene& dv = s->dev;
+    dv.nodes = s->nodes.p; dv.nodes4 = s->nodes4.p; dv.numNodes4 = (uint32_t)s->hostNodes.size(); dv.grid = s->grid.p; dv.tris = s->tris.p;
+    /* the leaf order changed: the triangle -> leaf table goes, and the next call that needs it makes it again (ensure_leaf_table) */
+    s->leafTable.release(); s->leafReady = false;
+    s->costParent.release(); s->costParentState = 0;
+    return RTR_OK;      /* ~Temp frees the old tree: the device was joined, and nothing has been enqueued against it since */
 }
 
 void rtr_scene_destroy(rtr_scene* s) {

@@ -293,6 +293,57 @@ int  rtr_scene_update_vertices(rtr_scene* scene, const rtr_vertex_range* ranges,
 /* Copy out the device vertex array as it is now (test / oracle hook like rtr_scene_export_bvh, and what rtr_scene_create_like needs
  * after a deformation): numVertices records; RTR_ERR_INVALID_ARGUMENT for a null pointer or a `bytes` that is not numVertices * 48. */
 int  rtr_scene_export_vertices(const rtr_scene* scene, RtrVertex* out, size_t bytes);
+/* The ENQUEUED vertex update: rtr_scene_update_vertices as stream-ordered work.  The synchronous call joins the device, remakes tables on
+ * the host, reads the tree back and renumbers the 4-wide view in a host loop; this form touches the host for argument checks and kernel
+ * launches only: check kernel -> predicated write kernel -> refit -> 4-wide view -> its breadth-first order ON THE DEVICE (kernels/
+ * rtr_bvh.hip, k_wide_order) -> permutation -> light triangles, all enqueued on the stream of the scene's context (rtr_ctx_set_stream
+ * makes that a caller's stream, torch's for one).  The result is the synchronous call's, byte for byte (tested).
+ * rtr_scene_prepare_async_updates: ONCE per scene, synchronous — everything the enqueued form must not do later.  It may join and
+ * allocate: the refit arrays of a host-built tree, the order kernel's scratch, the status words, and the device tables a refit flattens
+ * from (primitives and instances, the current instance masks in the flags).  Afterwards rtr_scene_set_instance_masks,
+ * rtr_scene_update_instances, rtr_scene_update_vertices and rtr_scene_rebuild keep those tables current (a rebuild prepares the new tree
+ * again by itself), so an enqueued update after any of them writes records with the right masks and leaf slots.  Idempotent; an empty
+ * scene returns RTR_OK.
+ * rtr_scene_update_vertices_async: ranges, strides and rules of RTR_VERTICES_DEVICE (device pointers, 4-B aligned; stride a multiple of
+ * 4, at least 12; normals optional).  No instances and no lights: their tables are made on the host, in double, and stay with the
+ * synchronous calls.  The call returns without joining the device, the stream or the host to anything; inside it there is no allocation,
+ * no synchronisation, no device -> host copy and no copy from host memory that could be reused before the copy runs — the table of
+ * ranges travels as kernel arguments, 64 ranges per launch, and the caller's `ranges` array is free when the call returns (the DEVICE
+ * memory it points at is read when the stream gets there).  Refused BEFORE anything is enqueued, with the synchronous call's messages:
+ * a null scene or ranges, numRanges == 0, a bad stride, a range that leaves the vertex array or overlaps another, null positions in a
+ * range with vertices, a misaligned pointer; and a scene that has not been prepared (RTR_ERR_INVALID_ARGUMENT; the message names
+ * rtr_scene_prepare_async_updates).
+ * ORDERING.  Work enqueued on that stream before the call sees the old scene; work enqueued after it sees the new one; the caller's
+ * kernels that produce the positions on that stream come before it without any event.  Work on OTHER streams or contexts that reads the
+ * scene — renders of frames of other contexts, queries — is the caller's to order with events (rtr_ctx_get_stream), as a Vulkan
+ * application barriers an acceleration-structure update.  The refit scratch is the scene's and shared: two updates of one scene are
+ * ordered by being on one stream, so the context's stream must not be changed while updates of its scenes are pending.
+ * BAD DATA.  An enqueued call cannot refuse.  The checking kernel (the rule of rtr_scene_create: inside +-3.0e38) reduces the smallest
+ * offending SCENE vertex index into a device word; the writing kernel writes NOTHING for that update when the word is set — all ranges
+ * land or none does — and the refit runs on the vertices as they are: after a refused update the vertex array keeps its bytes and every
+ * query and render answers as before it (tested).  A one-lane kernel folds the word into the sticky status below.
+ * rtr_scene_update_status: joins the scene's context stream (only that stream) and reports: `enqueued` — calls that returned RTR_OK, the
+ * serial numbers of the updates counting from 1; `refused` — how many of them the device refused, since preparation; firstRefusedUpdate
+ * / firstBadVertex — the serial (its low 32 bits) of the first refused update SINCE THE LAST STATUS CALL and the smallest scene vertex
+ * index it refused, 0xffffffff each when there was none.  A scene never prepared reports zeros.
+ * HOST MIRRORS.  After an enqueued update the library's host copies (nodes, records, grid, boxPad, the count of reached 4-wide
+ * records) are stale and marked so; rtr_scene_export_bvh / _export_wide, rtr_scene_get_stats, rtr_scene_create_like,
+ * rtr_scene_tree_cost, rtr_scene_set_instance_masks, the synchronous update calls, rtr_scene_rebuild and the first rtr_hit_leaves /
+ * rtr_light_rays_hinted (the leaf-table build) first join the scene's stream and read them back, once.  Renders and queries need none
+ * of them.  The triangle -> leaf table and the instance masks survive, as in the synchronous call; the light-triangle table is always
+ * remade.  Scenes replicated by librtr_mgpu have no enqueued update, as they have no update path. */
+typedef struct rtr_update_status {
+    uint64_t enqueued, refused;
+    uint32_t firstRefusedUpdate, firstBadVertex;
+    uint32_t _pad[2];
+} rtr_update_status;                       /* 32 bytes */
+#ifdef __cplusplus
+static_assert(sizeof(rtr_update_status) == 32, "rtr_update_status is 32 B");
+#endif
+int  rtr_scene_prepare_async_updates(rtr_scene* scene);
+int  rtr_scene_update_vertices_async(rtr_scene* scene, const rtr_vertex_range* ranges, uint32_t numRanges,
+                                     uint32_t positionStride, uint32_t normalStride);
+int  rtr_scene_update_status(rtr_scene* scene, rtr_update_status* out);
 /* The SAH cost of the tree the kernels walk NOW: what a refit did to the tree's quality, and what a rebuild would win back.  A refit
  * keeps the split decisions made for the old shape, and rtr_scene_stats::sahCost is the host builder's number at creation (0 for a device
  * build), which no update ever touches; this is the measure a caller decides with (rtr_scene_rebuild below).

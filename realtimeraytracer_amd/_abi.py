@@ -90,6 +90,12 @@ class rtr_vertex_range(C.Structure):
     _fields_ = [("firstVertex", u32), ("numVertices", u32), ("positions", C.c_void_p), ("normals", C.c_void_p)]
 
 
+class rtr_update_status(C.Structure):
+    """rtr_scene_update_status: updates enqueued so far, how many of them the device refused (bad data), and the serial (1-based) of the
+    first refused one since the last status call with its first bad scene vertex (0xffffffff each where there is none)"""
+    _fields_ = [("enqueued", u64), ("refused", u64), ("firstRefusedUpdate", u32), ("firstBadVertex", u32), ("_pad", u32 * 2)]
+
+
 class rtr_tree_cost(C.Structure):
     """rtr_scene_tree_cost / rtr_host_tree_cost: the integer area sums of the quantised BVH2 (x*y, y*z, z*x in grid steps), the two counts,
     and the SAH cost made from them with the grid's scale"""
@@ -150,6 +156,7 @@ assert C.sizeof(RtrSurface) == 80
 assert C.sizeof(RtrRadiance) == 48 and C.sizeof(rtr_light_params) == 32
 assert C.sizeof(rtr_vertex_range) == 24
 assert C.sizeof(rtr_tree_cost) == 96 and C.alignment(rtr_tree_cost) == 8
+assert C.sizeof(rtr_update_status) == 32
 
 # enum rtr_image
 IMAGE_ANALYTIC, IMAGE_SHADOWED, IMAGE_UNSHADOWED = 0, 1, 2
@@ -196,6 +203,9 @@ RTR_SYMBOLS = {
     "rtr_scene_update_instances": (C.c_int, [VP, P(RtrInstance), u32, P(RtrAreaLightInfo), u32]),
     "rtr_scene_update_vertices": (C.c_int, [VP, P(rtr_vertex_range), u32, u32, u32, u32, P(RtrInstance), u32, P(RtrAreaLightInfo), u32]),
     "rtr_scene_export_vertices": (C.c_int, [VP, VP, C.c_size_t]),
+    "rtr_scene_prepare_async_updates": (C.c_int, [VP]),
+    "rtr_scene_update_vertices_async": (C.c_int, [VP, P(rtr_vertex_range), u32, u32, u32]),
+    "rtr_scene_update_status": (C.c_int, [VP, P(rtr_update_status)]),
     "rtr_scene_tree_cost": (C.c_int, [VP, P(rtr_tree_cost)]),
     "rtr_host_tree_cost": (C.c_int, [VP, C.c_size_t, P(RtrBvhGrid), P(rtr_tree_cost)]),
     "rtr_scene_rebuild": (C.c_int, [VP, u32]),

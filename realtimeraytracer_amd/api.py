@@ -2,6 +2,7 @@
 Every non-zero status becomes RtrError carrying rtr_last_error() — the same convention as the C++
 shim csrc/host/renderer.hpp (reference: exceptions caught once in main, src/main.cpp:12-15)."""
 import ctypes as C
+import dataclasses
 
 import numpy as np
 
@@ -92,10 +93,22 @@ class TreeCost:
         return f"TreeCost(sah={self.sah!r}, num_inner={self.num_inner}, num_leaf_refs={self.num_leaf_refs}, root_area={self.root_area})"
 
 
+@dataclasses.dataclass(frozen=True)
+class UpdateStatus:
+    """Scene.update_status(): enqueued — update_vertices_async calls accepted so far, whose serials count from 1; refused —
+    how many of them the device refused for bad data; first_refused_update / first_bad_vertex — the serial of the first refused update
+    since the last status call and the smallest scene vertex index it refused, None where there was none."""
+    enqueued: int
+    refused: int
+    first_refused_update: "int | None"
+    first_bad_vertex: "int | None"
+
+
 class Scene:
     def __init__(self, ctx, desc, like=None):
         """like: a Scene made from the same description whose tree is uploaded instead of built again (rtr_scene_create_like)"""
         self.ctx, self.lib = ctx, ctx.lib
+        self._async_keep = []         # tensors of enqueued vertex updates: referenced until the next update_status (or the scene's end)
         self._built_sah = None        # tree_cost().sah right after the last build or rebuild: taken on first use (update_vertices' policy)
         self.h = A.VP()
         self._num_instances = int(desc.numInstances)
@@ -170,6 +183,29 @@ class Scene:
             return True
         return False
 
+    def prepare_async_updates(self):
+        """rtr_scene_prepare_async_updates: once, synchronously, everything update_vertices_async must not do later"""
+        _check(self.lib.rtr_scene_prepare_async_updates(self.h), "rtr_scene_prepare_async_updates")
+
+    def update_status(self):
+        """rtr_scene_update_status: joins the context's stream and reports the enqueued updates -> UpdateStatus.  The tensors of the
+        updates enqueued so far are released."""
+        st = A.rtr_update_status()
+        _check(self.lib.rtr_scene_update_status(self.h, C.byref(st)), "rtr_scene_update_status")
+        self._async_keep = []
+        none = 0xffffffff
+        return UpdateStatus(int(st.enqueued), int(st.refused), None if st.firstRefusedUpdate == none else int(st.firstRefusedUpdate),
+                            None if st.firstBadVertex == none else int(st.firstBadVertex))
+
+    def update_vertices_async(self, ranges, instances=None, lights=None):
+        """rtr_scene_update_vertices_async: update_vertices as stream-ordered work.  The update is ENQUEUED on the context's stream
+        (Context.set_stream makes that torch's) and the call returns at once: nothing is joined, so the tensors must be produced on that
+        stream (or ordered before it by the caller).  ranges as in update_vertices, torch tensors on the scene's device only, strided
+        views as they are; numpy arrays, instances= and lights= raise ValueError (they stay with the synchronous call).  The scene needs
+        prepare_async_updates() once.  Bad data cannot raise here: update_status() reports it, and a refused update changes nothing.
+        The tensors stay referenced until the next update_status() or the scene's end."""
+        self._update_vertices(ranges, instances, lights, True)
+
     def update_vertices(self, ranges, instances=None, lights=None):
         """rtr_scene_update_vertices: deform meshes — new positions (and normals) for ranges of the scene's vertex array, then ONE refit
         that also carries `instances` / `lights` when they are given (as update_instances takes them; None keeps the current ones).
@@ -181,8 +217,13 @@ class Scene:
         One call passes one position stride and one normal stride, so arrays whose strides differ (or that do not qualify) are made
         contiguous first.  uv and the vertices outside the ranges keep their bytes.  A position that is not finite refuses the whole
         call (RtrError, RTR_ERR_INVALID_ARGUMENT) and leaves the scene as it was.  With tensors, torch's current stream is joined first
-        when the context works on another one, as in the query calls."""
-        who = "update_vertices"
+        when the context works on another one, as in the query calls.  update_vertices_async is the enqueued form."""
+        self._update_vertices(ranges, instances, lights, False)
+
+    def _update_vertices(self, ranges, instances, lights, asynchronous):
+        who = "update_vertices_async" if asynchronous else "update_vertices"
+        if asynchronous and (instances is not None or lights is not None):
+            raise ValueError(f"{who}: takes no instances= and no lights=: they stay with the synchronous call")
         rows = []
         for k, r in enumerate(ranges):
             if not isinstance(r, (tuple, list)) or len(r) not in (2, 3):
@@ -194,6 +235,8 @@ class Scene:
         if any(p is None for _, p, _ in rows):
             raise ValueError(f"{who}: a range without positions")
         as_numpy = all(isinstance(a, np.ndarray) for a in arrays)
+        if asynchronous and (as_numpy or any(isinstance(a, np.ndarray) for a in arrays)):
+            raise ValueError(f"{who}: takes torch tensors on the scene's device, not numpy arrays")
         if not as_numpy:
             torch = _torch()
             if not all(isinstance(a, torch.Tensor) for a in arrays):
@@ -238,6 +281,10 @@ class Scene:
             ptr = (lambda a: a.ctypes.data) if as_numpy else (lambda a: a.data_ptr())
             cnt = int(p.shape[0])
             table[k] = A.rtr_vertex_range(first, cnt, ptr(p) if cnt else None, ptr(n) if n is not None and cnt else None)
+        if asynchronous:
+            _check(self.lib.rtr_scene_update_vertices_async(self.h, table, len(rows), pstride, nstride), "rtr_scene_update_vertices_async")
+            self._async_keep += keep
+            return
         if not as_numpy and self.ctx.get_stream() != torch.cuda.current_stream(dev).cuda_stream:
             torch.cuda.current_stream(dev).synchronize()        # the tensors are complete for the context's stream
         iarr = (A.RtrInstance * len(instances))(*instances) if instances is not None else None

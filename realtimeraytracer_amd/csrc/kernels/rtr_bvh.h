@@ -58,6 +58,20 @@ hipError_t launch_check_vertices(const VertexRange* ranges, const uint32_t* pref
 hipError_t launch_write_vertices(const VertexRange* ranges, const uint32_t* prefix, uint32_t numRanges, uint32_t total, uint32_t positionStrideWords,
                                  uint32_t normalStrideWords, RtrVertex* vertices, hipStream_t s);
 
+/* The enqueued form (rtr_scene_update_vertices_async): up to kVertexRangesPerArgs ranges and their prefix counts as ONE kernel argument
+ * (1 800 B of the 4 KB a launch may carry), copied when the launch is enqueued.  check reduces the smallest offending SCENE vertex index
+ * (firstVertex + v) into *firstBad (0xffffffff on entry: a memset on the stream); write does nothing at all when the word is set.
+ * launch_fold_update_status: one lane adds a set word to status[0..2] = refused count, serial of the first refused update since the
+ * host last reset it (0xffffffff: none), its first bad scene vertex. */
+constexpr uint32_t kVertexRangesPerArgs = 64;
+struct VertexRangeArgs { VertexRange ranges[kVertexRangesPerArgs]; uint32_t prefix[kVertexRangesPerArgs + 1]; uint32_t numRanges; };
+hipError_t launch_check_vertices_args(const VertexRangeArgs& t, uint32_t positionStrideWords, uint32_t* firstBad, hipStream_t s);
+hipError_t launch_write_vertices_args(const VertexRangeArgs& t, uint32_t positionStrideWords, uint32_t normalStrideWords, RtrVertex* vertices,
+                                      const uint32_t* firstBad, hipStream_t s);
+hipError_t launch_fold_update_status(const uint32_t* firstBad, uint32_t* status, uint32_t serial, hipStream_t s);
+/* bvh_refit with the reduction words set by a kernel: no host memory is read after the call returns */
+hipError_t bvh_refit_enqueued(const BvhInputs& in, uint32_t numPrims, uint32_t numNodes, const BvhDeviceArrays& a, hipStream_t s);
+
 /* The 4-wide view of a finished (quantised) tree that the any-hit kernel walks: numNodes x 4 uint4, see k_wide_nodes.
  * parentOrNull: the refit parent array (entries outside the tree are skipped) or null. */
 /* sets grid->wideCentreXY / Z (k_wide_centre_*; sums4 = bvh_wide_scratch_words() x u64 of scratch) and writes the 4-wide records about it */
@@ -66,6 +80,11 @@ size_t bvh_wide_scratch_words();
 hipError_t bvh_make_wide(const uint4* nodes, uint32_t numNodes, const int32_t* parentOrNull, RtrBvhGrid* grid, const uint8_t* shapeOrNull, uint4* wide, unsigned long long* sums4, hipStream_t s);
 /* out[remap[i]] = in[i] with inner child codes renumbered through remap (a permutation of 0..numNodes-1, remap[0] == 0) */
 hipError_t bvh_permute_wide(const uint4* in, uint32_t numNodes, const uint32_t* remap, uint4* out, hipStream_t stream);
+
+/* The permutation bvh_permute_wide takes, made on the device (k_wide_order): the breadth-first order of the 4-wide entries `wide`
+ * (un-permuted, child codes in words 12..15), bit for bit what rtr_api.cpp's host loop computes; *reached = the entries the tree reaches.
+ * scratch: 2 x numNodes words.  One launch of one workgroup; nothing is read back. */
+hipError_t bvh_wide_order(const uint4* wide, uint32_t numNodes, uint32_t* remap, uint32_t* scratch, uint32_t* reached, hipStream_t s);
 
 /* The SAH cost sums of a finished (quantised) tree, rtr_scene_tree_cost: words = bvh_tree_cost_words() x u64, zeroed here and filled by
  * k_tree_cost as innerArea[3], leafArea[3], rootArea[3], numInner, numLeafRefs (rtr_tree_cost's integers, in that order).

@@ -602,6 +602,199 @@ __global__ __launch_bounds__(kB) void k_write_vertices(const VertexRange* __rest
     }
 }
 
+/* ---- the enqueued vertex update (rtr_scene_update_vertices_async) ----------------------------------------------------
+ * The same two kernels with nothing between them and the host: the table of ranges and its prefix counts travel as KERNEL ARGUMENTS
+ * (a launch copies them when it is enqueued, so no host buffer has to outlive the call), the check reduces the smallest offending
+ * SCENE vertex index into *firstBad, and the write is predicated on that word: set, no lane writes anything — all ranges of the update
+ * land or none does.  Ranges do not overlap (checked on the host), so the smallest scene index is one fixed vertex. */
+__device__ __forceinline__ uint32_t arg_range_of(const VertexRangeArgs& t, uint32_t i) {
+    uint32_t lo = 0, hi = t.numRanges;                   /* t.prefix[lo] <= i < t.prefix[hi] */
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (t.prefix[mid] <= i) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(kB) void k_check_vertices_args(VertexRangeArgs t, uint32_t strideWords, uint32_t* __restrict__ firstBad) {
+    const uint32_t i = blockIdx.x * kB + threadIdx.x;
+    if (i >= t.prefix[t.numRanges]) return;
+    const uint32_t r = arg_range_of(t, i);
+    const uint32_t v = i - t.prefix[r];
+    const uint32_t* src = t.ranges[r].positions + (size_t)v * strideWords;
+    bool ok = true;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float x = __uint_as_float(src[k]);
+        ok = ok && (x > -3.0e38f && x < 3.0e38f);
+    }
+    if (!ok) atomicMin(firstBad, t.ranges[r].firstVertex + v);
+}
+
+__global__ __launch_bounds__(kB) void k_write_vertices_args(VertexRangeArgs t, uint32_t positionStrideWords, uint32_t normalStrideWords,
+                                                            RtrVertex* __restrict__ vertices, const uint32_t* __restrict__ firstBad) {
+    if (*firstBad != 0xffffffffu) return;                /* a refused update: the vertex array keeps its bytes */
+    const uint32_t i = blockIdx.x * kB + threadIdx.x;
+    if (i >= t.prefix[t.numRanges]) return;
+    const uint32_t r = arg_range_of(t, i);
+    const uint32_t v = i - t.prefix[r];
+    const VertexRange vr = t.ranges[r];
+    uint32_t* dst = reinterpret_cast<uint32_t*>(vertices + ((size_t)vr.firstVertex + v));
+    const uint32_t* p = vr.positions + (size_t)v * positionStrideWords;
+    const uint32_t p0 = p[0], p1 = p[1], p2 = p[2];
+    dst[0] = p0; dst[1] = p1; dst[2] = p2;
+    if (vr.normals) {
+        const uint32_t* q = vr.normals + (size_t)v * normalStrideWords;
+        const uint32_t n0 = q[0], n1 = q[1], n2 = q[2];
+        dst[4] = n0; dst[5] = n1; dst[6] = n2;
+    }
+}
+
+/* folds the update's word into the scene's sticky status: st[0] refused updates so far, st[1] the serial of the first refused update
+ * since the host last looked (0xffffffff: none), st[2] its first bad scene vertex */
+__global__ void k_fold_update_status(const uint32_t* __restrict__ firstBad, uint32_t* __restrict__ st, uint32_t serial) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    const uint32_t bad = *firstBad;
+    if (bad == 0xffffffffu) return;
+    st[0] += 1u;
+    if (st[1] == 0xffffffffu) { st[1] = serial; st[2] = bad; }
+}
+
+/* the reduction words of a refit as bvh_refit's host array sets them, without a host array */
+__global__ void k_refit_init(uint32_t* __restrict__ red) {
+    const uint32_t i = threadIdx.x;
+    if (blockIdx.x == 0 && i < 8u) red[i] = i < 3u ? 0xffffffffu : 0u;
+}
+
+/* ---- the breadth-first order of the 4-wide view, on the device (rtr_api.cpp, make_wide_nodes' host loop restated) ----------------
+ * remap[] of k_permute_wide and the number of entries the tree reaches, bit for bit what the host loop gives: entry 0 gets id 0; the
+ * entries are numbered in queue order — level by level, inside a level by their parent's new id, then by child slot; a code counts when
+ * it is in 0 .. numNodes-1; an entry is numbered ONCE, where it first appears in that order; what the tree does not reach takes the ids
+ * after them in ascending index order.
+ * ONE workgroup of 1024 lanes walks the levels.  Why one: a level depends on the scan of the one before it, so a grid would need a
+ * device-wide join per level — either a launch per level and phase (the refit keeps the topology, so stats.maxDepth bounds them: some
+ * sixty launches of mostly idle grids, each as long as this kernel's whole step) or a grid sync, which the project does not use.  One
+ * workgroup joins with s_barrier, keeps the level bounds in registers and LDS, needs no bound on the depth, and nothing is read back.
+ * Its price is one CU's memory rate: profiles/refit_async_rate.py measures it on the bench scene.
+ * A step takes kOrderE x 1024 queue entries, lane-consecutive (entry j = base + e * 1024 + tid: four independent loads in flight per
+ * lane):
+ *   claim : every inner code c of entry j (whose new id IS j: order[j] is the entry with id j) does atomicMin(claim[c], 4 j + slot + 1).
+ *           Keys grow in queue order, so the minimum over all time is the first appearance: the host loop's `remap[c] == none` guard.
+ *           claim[0] = 0 keeps the root from ever being numbered again.
+ *   scan  : after a barrier the (entry, slot) pairs that hold their child's claim are counted — ballot + mbcnt inside a wave, one LDS
+ *           word per (e, wave), which wave 0 scans (64 words: one per lane) — and the children take ids `next + rank` in that order.
+ * What a lane reads back of the words this kernel wrote — claim[] (written by atomics, which work in L2), order[] and remap[] (stores of
+ * other waves, one barrier earlier) — it reads with agent-scope loads, from L2: a line of order[] is read while its tail is still being
+ * written, and nothing here depends on what the CU's L1 does with such a line. */
+constexpr uint32_t kOrderB = 1024, kOrderE = 4, kOrderWaves = kOrderB / 64;
+static_assert(kOrderE * kOrderWaves == 64, "wave 0 scans one (e, wave) total per lane");
+
+__device__ __forceinline__ uint32_t lanes_before(unsigned long long m) {
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+}
+
+__global__ __launch_bounds__(kOrderB) void k_wide_order(const uint4* __restrict__ wide, uint32_t numNodes, uint32_t* __restrict__ remap,
+                                                        uint32_t* __restrict__ claim, uint32_t* __restrict__ order, uint32_t* __restrict__ reachedOut) {
+    __shared__ uint32_t sTot[64];
+    __shared__ uint32_t sAll;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    if (blockIdx.x != 0 || numNodes == 0) return;
+    for (uint32_t i = tid; i < numNodes; i += kOrderB) { remap[i] = i ? 0xffffffffu : 0u; claim[i] = i ? 0xffffffffu : 0u; }
+    if (tid == 0) order[0] = 0;
+    __syncthreads();
+    uint32_t begin = 0, end = 1;                          /* the level in order[]: the same in every lane */
+    while (begin < end) {
+        uint32_t next = end;                              /* ids handed out so far */
+        for (uint32_t base = begin; base < end; base += kOrderB * kOrderE) {
+            /* every load below is unconditional (a lane past the level's end reads entry `begin` and drops it): the loads of a lane's
+             * four entries, and later of its sixteen claim words, are in flight together instead of one after the other */
+            uint32_t code[kOrderE][4];                    /* inner codes; 0xffffffff: not one */
+            uint32_t node[kOrderE];
+#pragma unroll
+            for (uint32_t e = 0; e < kOrderE; ++e) {
+                const uint32_t j = base + e * kOrderB + tid;
+                node[e] = __hip_atomic_load(&order[j < end ? j : begin], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+#pragma unroll
+            for (uint32_t e = 0; e < kOrderE; ++e) {
+                const uint32_t j = base + e * kOrderB + tid;
+                const uint4 c = wide[(size_t)node[e] * 4 + 3];
+                code[e][0] = j < end ? c.x : 0xffffffffu; code[e][1] = j < end ? c.y : 0xffffffffu;
+                code[e][2] = j < end ? c.z : 0xffffffffu; code[e][3] = j < end ? c.w : 0xffffffffu;
+            }
+#pragma unroll
+            for (uint32_t e = 0; e < kOrderE; ++e) {
+                const uint32_t j = base + e * kOrderB + tid;
+#pragma unroll
+                for (uint32_t k = 0; k < 4; ++k) {
+                    if (code[e][k] < numNodes) atomicMin(&claim[code[e][k]], 4u * j + k + 1u);      /* (int32_t)code < 0 is >= numNodes as unsigned */
+                    else code[e][k] = 0xffffffffu;
+                }
+            }
+            __syncthreads();
+            uint32_t won[kOrderE], before[kOrderE], seen[kOrderE][4];
+#pragma unroll
+            for (uint32_t e = 0; e < kOrderE; ++e)
+#pragma unroll
+                for (uint32_t k = 0; k < 4; ++k)
+                    seen[e][k] = __hip_atomic_load(&claim[code[e][k] != 0xffffffffu ? code[e][k] : 0u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+            for (uint32_t e = 0; e < kOrderE; ++e) {
+                const uint32_t j = base + e * kOrderB + tid;
+                won[e] = 0; before[e] = 0;
+                uint32_t total = 0;
+#pragma unroll
+                for (uint32_t k = 0; k < 4; ++k) {
+                    const bool w = code[e][k] != 0xffffffffu && seen[e][k] == 4u * j + k + 1u;
+                    const unsigned long long m = __ballot(w);
+                    won[e] |= (w ? 1u : 0u) << k;
+                    before[e] += lanes_before(m);
+                    total += (uint32_t)__popcll(m);
+                }
+                if (lane == 0) sTot[e * kOrderWaves + wave] = total;
+            }
+            __syncthreads();
+            if (wave == 0) {                              /* exclusive scan of the 64 totals, in (e, wave) order = queue order */
+                const uint32_t v = sTot[lane];
+                uint32_t incl = v;
+#pragma unroll
+                for (int o = 1; o < 64; o <<= 1) { const uint32_t up = __shfl_up(incl, o); if ((int)lane >= o) incl += up; }
+                sTot[lane] = incl - v;
+                if (lane == 63u) sAll = incl;
+            }
+            __syncthreads();
+#pragma unroll
+            for (uint32_t e = 0; e < kOrderE; ++e) {
+                uint32_t id = next + sTot[e * kOrderWaves + wave] + before[e];
+#pragma unroll
+                for (uint32_t k = 0; k < 4; ++k)
+                    if (won[e] & (1u << k)) { remap[code[e][k]] = id; order[id] = code[e][k]; ++id; }
+            }
+            next += sAll;
+            __syncthreads();                              /* sTot / sAll are free again; order[] of the next level is written */
+        }
+        begin = end; end = next;
+    }
+    const uint32_t reached = end;
+    if (tid == 0) *reachedOut = reached;
+    if (reached == numNodes) return;
+    /* the rest, in ascending index order */
+    uint32_t run = reached;
+    for (uint32_t base = 0; base < numNodes; base += kOrderB) {
+        const uint32_t i = base + tid;
+        const bool un = i < numNodes && __hip_atomic_load(&remap[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0xffffffffu;
+        const unsigned long long m = __ballot(un);
+        if (lane == 0) sTot[wave] = (uint32_t)__popcll(m);
+        __syncthreads();
+        uint32_t pre = 0, all = 0;
+#pragma unroll
+        for (uint32_t w = 0; w < kOrderWaves; ++w) { const uint32_t t = sTot[w]; if (w < wave) pre += t; all += t; }
+        if (un) remap[i] = run + pre + lanes_before(m);
+        run += all;
+        __syncthreads();
+    }
+}
+
 /* ---- host-side drivers ------------------------------------------------------------------------------ */
 #define BV_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return e_; } while (0)
 
@@ -630,6 +823,46 @@ hipError_t bvh_refit(const BvhInputs& in, uint32_t numPrims, uint32_t numNodes, 
     hipLaunchKernelGGL(k_fit, dim3((numNodes + kB - 1) / kB), dim3(kB), 0, s, numNodes, a.nodesF, a.boxMin, a.boxMax, a.parent, a.counters, a.depth, a.red, a.red + 7);
     hipLaunchKernelGGL(k_grid, dim3(1), dim3(64), 0, s, a.nodesF, a.grid);
     hipLaunchKernelGGL(k_quantize, dim3((numNodes + kB - 1) / kB), dim3(kB), 0, s, numNodes, a.nodesF, a.parent, a.grid, a.nodes);
+    return hipGetLastError();
+}
+
+/* the enqueued forms: nothing here waits, allocates or copies from host memory */
+hipError_t launch_check_vertices_args(const VertexRangeArgs& t, uint32_t positionStrideWords, uint32_t* firstBad, hipStream_t s) {
+    const uint32_t total = t.prefix[t.numRanges];
+    if (total == 0 || t.numRanges == 0) return hipSuccess;
+    if (t.numRanges > kVertexRangesPerArgs) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_check_vertices_args, dim3((uint32_t)(((uint64_t)total + kB - 1) / kB)), dim3(kB), 0, s, t, positionStrideWords, firstBad);
+    return hipGetLastError();
+}
+
+hipError_t launch_write_vertices_args(const VertexRangeArgs& t, uint32_t positionStrideWords, uint32_t normalStrideWords, RtrVertex* vertices,
+                                      const uint32_t* firstBad, hipStream_t s) {
+    const uint32_t total = t.prefix[t.numRanges];
+    if (total == 0 || t.numRanges == 0) return hipSuccess;
+    if (t.numRanges > kVertexRangesPerArgs) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_write_vertices_args, dim3((uint32_t)(((uint64_t)total + kB - 1) / kB)), dim3(kB), 0, s, t, positionStrideWords, normalStrideWords, vertices, firstBad);
+    return hipGetLastError();
+}
+
+hipError_t launch_fold_update_status(const uint32_t* firstBad, uint32_t* status, uint32_t serial, hipStream_t s) {
+    hipLaunchKernelGGL(k_fold_update_status, dim3(1), dim3(64), 0, s, firstBad, status, serial);
+    return hipGetLastError();
+}
+
+hipError_t bvh_refit_enqueued(const BvhInputs& in, uint32_t numPrims, uint32_t numNodes, const BvhDeviceArrays& a, hipStream_t s) {
+    BV_TRY(hipMemsetAsync(a.counters, 0, (size_t)numNodes * sizeof(uint32_t), s));
+    BV_TRY(hipMemsetAsync(a.depth, 0, (size_t)numNodes * sizeof(uint32_t), s));
+    hipLaunchKernelGGL(k_refit_init, dim3(1), dim3(64), 0, s, a.red);
+    hipLaunchKernelGGL(k_world_prims, dim3((numPrims + kB - 1) / kB), dim3(kB), 0, s, in, numPrims, a.slotOfPrim, a.tris, a.boxMin, a.boxMax, a.red);
+    hipLaunchKernelGGL(k_fit, dim3((numNodes + kB - 1) / kB), dim3(kB), 0, s, numNodes, a.nodesF, a.boxMin, a.boxMax, a.parent, a.counters, a.depth, a.red, a.red + 7);
+    hipLaunchKernelGGL(k_grid, dim3(1), dim3(64), 0, s, a.nodesF, a.grid);
+    hipLaunchKernelGGL(k_quantize, dim3((numNodes + kB - 1) / kB), dim3(kB), 0, s, numNodes, a.nodesF, a.parent, a.grid, a.nodes);
+    return hipGetLastError();
+}
+
+hipError_t bvh_wide_order(const uint4* wide, uint32_t numNodes, uint32_t* remap, uint32_t* scratch, uint32_t* reached, hipStream_t s) {
+    if (numNodes == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_wide_order, dim3(1), dim3(kOrderB), 0, s, wide, numNodes, remap, scratch, scratch + numNodes, reached);
     return hipGetLastError();
 }
 

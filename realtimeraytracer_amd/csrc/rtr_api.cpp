@@ -170,6 +170,15 @@ struct rtr_scene {
     DevBuf<uint32_t> vtxPrefix, vtxStage;
     std::vector<uint32_t> vtxHost;
     BuildScratch buildScratch;           /* rtr_scene_rebuild with RTR_BUILD_DEVICE_LBVH: empty until the first one */
+    /* rtr_scene_update_vertices_async (made by rtr_scene_prepare_async_updates): k_wide_order's scratch (2 x numNodes words) and the
+     * words of the enqueued chain — [0] the first bad vertex of the update in flight, [1] the entries the 4-wide tree reaches,
+     * [4..6] the sticky status (refused count, serial of the first refused update since the last status call, its first bad vertex).
+     * mirrorsStale: an enqueued update has run (or will) since hostNodes, hostTris, stats.grid, stats.boxPad and wideReached were
+     * read back; refresh_mirrors joins the stream and reads them again.  mutable: the export calls take the scene const */
+    DevBuf<uint32_t> orderScratch, asyncWords;
+    bool asyncReady = false;
+    mutable bool mirrorsStale = false;
+    uint64_t asyncEnqueued = 0;
     /* rtr_scene_tree_cost: the kernel's words, and for a tree without refit arrays whose slots are not all reachable, a parent array of
      * its own (costParentState: 0 not looked at yet, 1 every slot is in the tree, 2 costParent holds it).  mutable: the call takes the
      * scene const, like the leaf table */
@@ -511,6 +520,27 @@ static void make_prim_tables(const rtr_scene_desc* d, const RtrInstance* instanc
     }
 }
 
+/* The host mirrors after enqueued updates (rtr_scene_update_vertices_async leaves them stale): joins the scene's stream and reads back
+ * what the synchronous refit reads back — nodes, records, grid, boxPad — and the count of reached 4-wide entries k_wide_order left on
+ * the device.  Every call that looks at a mirror comes through here first; it costs nothing while no update has been enqueued. */
+static int refresh_mirrors(const rtr_scene* cs) {
+    if (!cs->mirrorsStale) return RTR_OK;
+    rtr_scene* s = const_cast<rtr_scene*>(cs);
+    HIP_TRY(hipSetDevice(s->ctx->device));
+    HIP_TRY(hipStreamSynchronize(s->ctx->stream));
+    uint32_t red[8], reached = 0;
+    HIP_TRY(hipMemcpy(s->hostNodes.data(), s->nodes.p, s->hostNodes.size() * sizeof(RtrBvhNode), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(s->hostTris.data(), s->tris.p, s->hostTris.size() * 48, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&s->stats.grid, s->grid.p, sizeof(RtrBvhGrid), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(red, s->red.p, sizeof red, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&reached, s->asyncWords.p + 1, sizeof reached, hipMemcpyDeviceToHost));
+    float mabs; memcpy(&mabs, &red[6], 4);
+    s->stats.boxPad = (mabs > 1e-6f ? mabs : 1e-6f) * 3.814697265625e-06f;
+    s->wideReached = reached; s->stats.numWideNodes = reached;
+    s->mirrorsStale = false;
+    return RTR_OK;
+}
+
 /* (re)builds the 4-wide view of the tree the any-hit kernel walks, on the device, from the quantised BVH2 nodes */
 /* (re)computes the per-light-triangle records light_loops reads; the light transforms live in s->lights on the device */
 static int make_light_tris(rtr_scene* s) {
@@ -654,6 +684,8 @@ static int scene_create_impl(rtr_ctx* ctx, const rtr_scene_desc* d, const rtr_sc
     const bool deviceBuild = !like && d->buildFlags == RTR_BUILD_DEVICE_LBVH && totalPrims >= 16;
     rtr::BvhResult bvh; std::vector<float> xforms, nmats; uint32_t stackEntries = 0; size_t numTris = 0;
     if (like) {
+        rc = refresh_mirrors(like);
+        if (rc != RTR_OK) return rc;
         /* the tree of `like`, as its host copy holds it (nodes and records are kept in step with the device by every update) */
         if (like->stats.numTriangles != totalPrims || like->hostNodes.empty() || like->hostTris.empty())
             return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_scene_create_like: the built scene has %u triangles, this description %zu", like->stats.numTriangles, totalPrims);
@@ -819,12 +851,15 @@ static std::vector<uint32_t> instance_mask_bits(const rtr_scene* s, const uint8_
     return bits;
 }
 
+static int upload_prim_tables(rtr_scene* s, const RtrInstance* inst);
+
 int rtr_scene_set_instance_masks(rtr_scene* s, const uint8_t* masks, uint32_t numInstances) {
     if (!s || (!masks && numInstances)) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_scene_set_instance_masks: null argument");
     if (numInstances != s->hostInstances.size()) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_scene_set_instance_masks: %u masks given, scene has %zu instances", numInstances, s->hostInstances.size());
     if (numInstances == 0) return RTR_OK;
     const std::vector<uint32_t> bits = instance_mask_bits(s, masks);
     HIP_TRY(hipSetDevice(s->ctx->device));
+    { const int rcm = refresh_mirrors(s); if (rcm != RTR_OK) return rcm; }
     /* queries of OTHER contexts (other streams) may be walking these records: everything enqueued on the device so far is joined before
      * they are rewritten (contract in rtr.h, as rtr_scene_update_instances) */
     HIP_TRY(hipDeviceSynchronize());
@@ -838,6 +873,8 @@ int rtr_scene_set_instance_masks(rtr_scene* s, const uint8_t* masks, uint32_t nu
     for (RtrBvhTri& t : s->hostTris)
         if (t.customIndex < numInstances) t.flags = (t.flags & ~RTR_TRI_MASK_BITS) | bits[t.customIndex];
     s->hostMasks.assign(masks, masks + numInstances);
+    /* an enqueued refit writes its records from the device tables: they carry the new masks from here on */
+    if (s->asyncReady) return upload_prim_tables(s, s->hostInstances.data());
     return RTR_OK;
 }
 
@@ -872,14 +909,10 @@ static int check_refit_args(const rtr_scene* s, const RtrInstance* instances, ui
     return RTR_OK;
 }
 
-/* The refit both calls end in, on a scene that is refit-ready and a device that has been joined: world-space records from the device
- * vertex array, boxes, grid, 4-wide view, host mirrors, boxPad.  instances == NULL keeps the current transforms (and with them the
- * transform, normal-matrix and mirrored tables); lights == NULL keeps the light infos.  lightTris: remake the light-triangle table even
- * when no lights are given (the vertices of a light's mesh may have changed). */
-static int refit_scene(rtr_scene* s, const RtrInstance* instances, const RtrAreaLightInfo* lights, bool lightTris) {
+/* the device tables a refit flattens from (PrimRef / InstanceRef) for the transforms given, with the instance masks in the flags */
+static int upload_prim_tables(rtr_scene* s, const RtrInstance* inst) {
     hipStream_t st = s->ctx->stream;
-    const uint32_t numInstances = (uint32_t)s->hostInstances.size(), numLights = s->numLights;
-    const RtrInstance* inst = instances ? instances : s->hostInstances.data();
+    const uint32_t numInstances = (uint32_t)s->hostInstances.size();
     rtr_scene_desc view{};
     view.meshes = s->hostMeshes.data(); view.numMeshes = (uint32_t)s->hostMeshes.size();
     view.numInstances = numInstances; view.objects = s->hostObjects.data(); view.numObjects = (uint32_t)s->hostObjects.size();
@@ -892,6 +925,17 @@ static int refit_scene(rtr_scene* s, const RtrInstance* instances, const RtrArea
     }
     HIP_TRY(s->prims.upload(prims.data(), prims.size(), st));
     HIP_TRY(s->instRefs.upload(refs.data(), refs.size(), st));
+    return RTR_OK;
+}
+
+/* The refit both calls end in, on a scene that is refit-ready and a device that has been joined: world-space records from the device
+ * vertex array, boxes, grid, 4-wide view, host mirrors, boxPad.  instances == NULL keeps the current transforms (and with them the
+ * transform, normal-matrix and mirrored tables); lights == NULL keeps the light infos.  lightTris: remake the light-triangle table even
+ * when no lights are given (the vertices of a light's mesh may have changed). */
+static int refit_scene(rtr_scene* s, const RtrInstance* instances, const RtrAreaLightInfo* lights, bool lightTris) {
+    hipStream_t st = s->ctx->stream;
+    const uint32_t numInstances = (uint32_t)s->hostInstances.size(), numLights = s->numLights;
+    { const int rct = upload_prim_tables(s, instances ? instances : s->hostInstances.data()); if (rct != RTR_OK) return rct; }
     std::vector<float> xforms, nmats;      /* outlive the asynchronous copies: the stream is joined below */
     if (instances) {
         instance_tables(numInstances, instances, xforms, nmats);
@@ -923,6 +967,8 @@ int rtr_scene_update_instances(rtr_scene* s, const RtrInstance* instances, uint3
     if (numInstances != s->hostInstances.size()) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_scene_update_instances: %u instances given, scene has %zu", numInstances, s->hostInstances.size());
     int rc = check_refit_args(s, instances, numInstances, lights, numLights, "rtr_scene_update_instances");
     if (rc != RTR_OK) return rc;
+    rc = refresh_mirrors(s);
+    if (rc != RTR_OK) return rc;
     if (s->hostTris.empty() || s->hostTris[0].customIndex == 0xffffffffu) return RTR_OK;     /* empty scene: nothing to refit */
     HIP_TRY(hipSetDevice(s->ctx->device));
     rc = ensure_refit_ready(s);
@@ -933,14 +979,10 @@ int rtr_scene_update_instances(rtr_scene* s, const RtrInstance* instances, uint3
     return refit_scene(s, instances, lights, false);
 }
 
-int rtr_scene_update_vertices(rtr_scene* s, const rtr_vertex_range* ranges, uint32_t numRanges, uint32_t positionStride, uint32_t normalStride, uint32_t flags,
-                              const RtrInstance* instances, uint32_t numInstances, const RtrAreaLightInfo* lights, uint32_t numLights) {
-    static const char* who = "rtr_scene_update_vertices";
-    static_assert(sizeof(rtr_vertex_range) == 24, "layout");
-    if (!s) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: null scene", who);
-    if (!ranges || numRanges == 0) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: null ranges (or numRanges == 0): nothing to update", who);
-    if (flags > RTR_VERTICES_DEVICE) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: unknown flag bits 0x%x", who, flags & ~RTR_VERTICES_DEVICE);
-    const bool device = flags == RTR_VERTICES_DEVICE;
+/* The checks of the ranges that the synchronous and the enqueued vertex update share, with the same messages (`who` names the caller):
+ * strides, ranges inside the vertex array, null positions, device-pointer alignment, overlaps. */
+static int check_vertex_ranges(const rtr_scene* s, const rtr_vertex_range* ranges, uint32_t numRanges, uint32_t positionStride, uint32_t normalStride,
+                               bool device, const char* who) {
     if ((positionStride & 3u) || positionStride < 12u) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: positionStride %u must be a multiple of 4 and at least 12", who, positionStride);
     bool anyNormals = false;
     for (uint32_t r = 0; r < numRanges; ++r) {
@@ -964,7 +1006,22 @@ int rtr_scene_update_vertices(rtr_scene* s, const rtr_vertex_range* ranges, uint
                 return fail(RTR_ERR_INVALID_ARGUMENT, "%s: ranges %u and %u overlap (vertex %u)", who, order[k - 1], order[k], b.firstVertex);
         }
     }
-    int rc = check_refit_args(s, instances, numInstances, lights, numLights, who);
+    return RTR_OK;
+}
+
+int rtr_scene_update_vertices(rtr_scene* s, const rtr_vertex_range* ranges, uint32_t numRanges, uint32_t positionStride, uint32_t normalStride, uint32_t flags,
+                              const RtrInstance* instances, uint32_t numInstances, const RtrAreaLightInfo* lights, uint32_t numLights) {
+    static const char* who = "rtr_scene_update_vertices";
+    static_assert(sizeof(rtr_vertex_range) == 24, "layout");
+    if (!s) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: null scene", who);
+    if (!ranges || numRanges == 0) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: null ranges (or numRanges == 0): nothing to update", who);
+    if (flags > RTR_VERTICES_DEVICE) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: unknown flag bits 0x%x", who, flags & ~RTR_VERTICES_DEVICE);
+    const bool device = flags == RTR_VERTICES_DEVICE;
+    int rc = check_vertex_ranges(s, ranges, numRanges, positionStride, normalStride, device, who);
+    if (rc != RTR_OK) return rc;
+    rc = check_refit_args(s, instances, numInstances, lights, numLights, who);
+    if (rc != RTR_OK) return rc;
+    rc = refresh_mirrors(s);
     if (rc != RTR_OK) return rc;
     if (s->hostTris.empty() || s->hostTris[0].customIndex == 0xffffffffu) return RTR_OK;     /* empty scene: nothing to refit */
 
@@ -1068,6 +1125,99 @@ int rtr_scene_export_vertices(const rtr_scene* s, RtrVertex* out, size_t bytes) 
     return RTR_OK;
 }
 
+/* ---- the enqueued vertex update (contract in rtr.h) ---- */
+static bool scene_is_empty(const rtr_scene* s) { return s->hostTris.empty() || s->hostTris[0].customIndex == 0xffffffffu; }
+
+int rtr_scene_prepare_async_updates(rtr_scene* s) {
+    if (!s) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_scene_prepare_async_updates: null scene");
+    HIP_TRY(hipSetDevice(s->ctx->device));
+    int rc = refresh_mirrors(s);
+    if (rc != RTR_OK) return rc;
+    if (s->asyncReady) return RTR_OK;
+    if (!scene_is_empty(s)) {
+        rc = ensure_refit_ready(s);
+        if (rc != RTR_OK) return rc;
+        rc = upload_prim_tables(s, s->hostInstances.data());
+        if (rc != RTR_OK) return rc;
+        HIP_TRY(s->orderScratch.ensure(2 * s->hostNodes.size()));
+    }
+    if (!s->asyncWords.p) {      /* kept through a rebuild: the status is the scene's, not the tree's */
+        const uint32_t none = 0xffffffffu, init[8] = {none, 0u, 0u, 0u, 0u, none, none, 0u};
+        HIP_TRY(s->asyncWords.upload(init, 8, s->ctx->stream));
+    }
+    s->asyncReady = true;
+    return RTR_OK;
+}
+
+int rtr_scene_update_vertices_async(rtr_scene* s, const rtr_vertex_range* ranges, uint32_t numRanges, uint32_t positionStride, uint32_t normalStride) {
+    static const char* who = "rtr_scene_update_vertices_async";
+    if (!s) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: null scene", who);
+    if (!ranges || numRanges == 0) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: null ranges (or numRanges == 0): nothing to update", who);
+    int rc = check_vertex_ranges(s, ranges, numRanges, positionStride, normalStride, true, who);
+    if (rc != RTR_OK) return rc;
+    if (!s->asyncReady) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: the scene has not been prepared: call rtr_scene_prepare_async_updates once first", who);
+    const uint32_t serial = (uint32_t)(s->asyncEnqueued + 1);
+    if (scene_is_empty(s)) { ++s->asyncEnqueued; return RTR_OK; }      /* nothing to refit, as the synchronous call */
+    HIP_TRY(hipSetDevice(s->ctx->device));
+    hipStream_t st = s->ctx->stream;
+    uint32_t* firstBad = s->asyncWords.p;
+    HIP_TRY(hipMemsetAsync(firstBad, 0xff, sizeof(uint32_t), st));
+    const uint32_t posWords = positionStride / 4u, nrmWords = normalStride / 4u;
+    const uint32_t kChunk = rtrdev::kVertexRangesPerArgs;
+    /* the ranges reach the kernels as kernel arguments, a chunk per launch: first every check, then every (predicated) write */
+    for (int pass = 0; pass < 2; ++pass)
+        for (uint32_t r0 = 0; r0 < numRanges; r0 += kChunk) {
+            rtrdev::VertexRangeArgs t;
+            t.numRanges = std::min(numRanges - r0, kChunk);
+            uint32_t acc = 0;
+            for (uint32_t k = 0; k < t.numRanges; ++k) {
+                const rtr_vertex_range& vr = ranges[r0 + k];
+                t.ranges[k] = rtrdev::VertexRange{static_cast<const uint32_t*>(vr.positions), vr.numVertices ? static_cast<const uint32_t*>(vr.normals) : nullptr, vr.firstVertex, 0u};
+                t.prefix[k] = acc; acc += vr.numVertices;
+            }
+            t.prefix[t.numRanges] = acc;
+            const hipError_t e = pass == 0 ? rtrdev::launch_check_vertices_args(t, posWords, firstBad, st)
+                                           : rtrdev::launch_write_vertices_args(t, posWords, nrmWords, s->vertices.p, firstBad, st);
+            if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: %s kernel: %s", who, pass == 0 ? "checking" : "writing", hipGetErrorString(e));
+        }
+    /* the refit on the vertices as they are now, the 4-wide view, its breadth-first order made on the device, the light triangles */
+    const uint32_t n = (uint32_t)s->hostNodes.size();
+    rtrdev::BvhInputs in{s->prims.p, s->instRefs.p, s->vertices.p, s->indices.p};
+    hipError_t e = rtrdev::bvh_refit_enqueued(in, s->numPrims, s->numNodeSlots, device_arrays(s), st);
+    if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: device BVH refit: %s", who, hipGetErrorString(e));
+    s->mirrorsStale = true;
+    e = rtrdev::bvh_make_wide(s->nodes.p, n, s->parent.p, s->grid.p, s->hostWideShape.size() == n ? s->wideShape.p : nullptr, s->nodes4tmp.p, s->wideSums.p, st);
+    if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: 4-wide node build: %s", who, hipGetErrorString(e));
+    e = rtrdev::bvh_wide_order(s->nodes4tmp.p, n, s->wideRemap.p, s->orderScratch.p, s->asyncWords.p + 1, st);
+    if (e == hipSuccess) e = rtrdev::bvh_permute_wide(s->nodes4tmp.p, n, s->wideRemap.p, s->nodes4.p, st);
+    if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: 4-wide node order: %s", who, hipGetErrorString(e));
+    if (s->numLights) {
+        e = rtrdev::launch_light_tris(s->lights.p, s->vertices.p, s->indices.p, s->lightTriFirst.p, s->numLights, s->lightTris.p, st);
+        if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: light-triangle records: %s", who, hipGetErrorString(e));
+    }
+    e = rtrdev::launch_fold_update_status(firstBad, s->asyncWords.p + 4, serial, st);
+    if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: status kernel: %s", who, hipGetErrorString(e));
+    ++s->asyncEnqueued;
+    return RTR_OK;
+}
+
+int rtr_scene_update_status(rtr_scene* s, rtr_update_status* out) {
+    static_assert(sizeof(rtr_update_status) == 32, "layout");
+    if (!s || !out) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_scene_update_status: null argument");
+    memset(out, 0, sizeof *out);
+    out->enqueued = s->asyncEnqueued;
+    out->firstRefusedUpdate = out->firstBadVertex = 0xffffffffu;
+    if (!s->asyncWords.p) return RTR_OK;      /* never prepared: nothing was enqueued */
+    HIP_TRY(hipSetDevice(s->ctx->device));
+    hipStream_t st = s->ctx->stream;
+    uint32_t w[3];
+    HIP_TRY(hipMemcpyAsync(w, s->asyncWords.p + 4, sizeof w, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    out->refused = w[0]; out->firstRefusedUpdate = w[1]; out->firstBadVertex = w[2];
+    if (w[1] != 0xffffffffu) HIP_TRY(hipMemsetAsync(s->asyncWords.p + 5, 0xff, 2 * sizeof(uint32_t), st));      /* "first since the last status call" starts again */
+    return RTR_OK;
+}
+
 /* ---- the cost of the tree, and the rebuild (contracts in rtr.h) ---- */
 /* the integer sums are complete: sah from them in double, in the order rtr.h states (-ffp-contract=off: no fused step) */
 static void finish_tree_cost(rtr_tree_cost* c, const RtrBvhGrid& grid) {
@@ -1127,6 +1277,7 @@ int rtr_host_tree_cost(const RtrBvhNode* nodes, size_t nodeBytes, const RtrBvhGr
 int rtr_scene_tree_cost(const rtr_scene* s, rtr_tree_cost* out) {
     if (!s || !out) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_scene_tree_cost: null argument");
     HIP_TRY(hipSetDevice(s->ctx->device));
+    { const int rcm = refresh_mirrors(s); if (rcm != RTR_OK) return rcm; }      /* the grid the sums are scaled with */
     hipStream_t st = s->ctx->stream;
     const uint32_t numNodes = (uint32_t)s->hostNodes.size();
     /* which slots are part of the tree: the refit's parent array where the scene has one (a device build leaves slots unused); a host
@@ -1170,6 +1321,7 @@ int rtr_scene_rebuild(rtr_scene* s, uint32_t buildFlags) {
     static const char* who = "rtr_scene_rebuild";
     if (!s) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: null scene", who);
     if (buildFlags > RTR_BUILD_DEVICE_LBVH) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: unknown buildFlags %u", who, buildFlags);
+    { const int rcm = refresh_mirrors(s); if (rcm != RTR_OK) return rcm; }
     if (s->hostTris.empty() || s->hostTris[0].customIndex == 0xffffffffu) return RTR_OK;     /* empty scene: nothing to build */
     HIP_TRY(hipSetDevice(s->ctx->device));
     /* frames and queries of OTHER contexts (other streams) may be walking this tree: everything enqueued on the device so far is joined
@@ -1220,6 +1372,8 @@ int rtr_scene_rebuild(rtr_scene* s, uint32_t buildFlags) {
     /* the leaf order changed: the triangle -> leaf table goes, and the next call that needs it makes it again (ensure_leaf_table) */
     s->leafTable.release(); s->leafReady = false;
     s->costParent.release(); s->costParentState = 0;
+    /* the enqueued update's tables and scratch belong to a tree: made again for the new one (its node count, its leaf slots) */
+    if (s->asyncReady) { s->asyncReady = false; return rtr_scene_prepare_async_updates(s); }
     return RTR_OK;      /* ~Temp frees the old tree: the device was joined, and nothing has been enqueued against it since */
 }
 
@@ -1234,12 +1388,14 @@ void rtr_scene_destroy(rtr_scene* s) {
 
 int rtr_scene_get_stats(const rtr_scene* s, rtr_scene_stats* out) {
     if (!s || !out) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_scene_get_stats: null argument");
+    { const int rcm = refresh_mirrors(s); if (rcm != RTR_OK) return rcm; }
     *out = s->stats;
     return RTR_OK;
 }
 
 int rtr_scene_export_bvh(const rtr_scene* s, RtrBvhNode* nodes, size_t nodeBytes, RtrBvhTri* tris, size_t triBytes) {
     if (!s) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_scene_export_bvh: null scene");
+    { const int rcm = refresh_mirrors(s); if (rcm != RTR_OK) return rcm; }
     if (nodes) {
         if (nodeBytes != s->hostNodes.size() * sizeof(RtrBvhNode)) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_scene_export_bvh: nodeBytes %zu != %zu", nodeBytes, s->hostNodes.size() * sizeof(RtrBvhNode));
         memcpy(nodes, s->hostNodes.data(), nodeBytes);
@@ -1253,6 +1409,7 @@ int rtr_scene_export_bvh(const rtr_scene* s, RtrBvhNode* nodes, size_t nodeBytes
 
 int rtr_scene_export_wide(const rtr_scene* s, RtrWideNode* nodes, size_t nodeBytes) {
     if (!s || !nodes) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_scene_export_wide: null argument");
+    { const int rcm = refresh_mirrors(s); if (rcm != RTR_OK) return rcm; }
     if (nodeBytes != (size_t)s->wideReached * sizeof(RtrWideNode)) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_scene_export_wide: nodeBytes %zu != %zu", nodeBytes, (size_t)s->wideReached * sizeof(RtrWideNode));
     HIP_TRY(hipSetDevice(s->ctx->device));
     HIP_TRY(hipMemcpy(nodes, s->nodes4.p, nodeBytes, hipMemcpyDeviceToHost));      /* the records the tree reaches come first */
@@ -2119,6 +2276,7 @@ int rtr_hit_surfaces(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const R
  * keeps it (a refit moves boxes and records, not the leaves they sit in). */
 static int ensure_leaf_table(rtr_ctx* c, const rtr_scene* s, const char* who) {
     if (s->leafReady) return RTR_OK;
+    { const int rcm = refresh_mirrors(s); if (rcm != RTR_OK) return rcm; }      /* joins an enqueued refit: this kernel may run on another stream */
     std::vector<uint32_t> base(s->hostTriCount.size() + 1, 0u);
     uint64_t total = 0;
     for (size_t i = 0; i < s->hostTriCount.size(); ++i) { base[i] = (uint32_t)total; total += s->hostTriCount[i]; }

@@ -9,7 +9,9 @@
  *
  * pow/exp2/log2 are our own polynomial forms (libm and ocml differ by ULPs, and
  * pow(x,1/2.2) feeds the 8-bit quantiser); they are pinned against libm in
- * tests/test_math.py with a stated ULP tolerance.
+ * tests/test_math.py with a stated ULP tolerance.  That the device compile of this header means the host compile's bits is held
+ * directly, function by function over whole domains, by tests/test_gpu_math_contract.py (tests/math_probe/ compiles every function
+ * below with both compile lines); tests/test_math_contract.py holds the host compile to float64 references.
  *
  * Used by: the HIP kernels (device), the host scene layer, and the CPU oracle.
  */
@@ -191,7 +193,8 @@ RTR_HD float rtr_pow(float x, float y) {
 }
 
 /* ---- atan2 / acos (miss.rmiss:19-22 equirect lookup) ------------------------------------------ */
-/* atan on [0, tan(pi/8)]: odd degree-9 polynomial (the classic single-precision form; |err| < 2e-7) */
+/* atan on [0, tan(pi/8)]: odd degree-9 polynomial (the classic single-precision form; |err| < 2e-7; measured 2.6e-8,
+ * tests/test_math_contract.py) */
 RTR_HD float rtr_atan_small(float x) {
     float z = x * x;
     float p = 8.05374449538e-2f;
@@ -201,7 +204,8 @@ RTR_HD float rtr_atan_small(float x) {
     return rtr_fma(p * z, x, x);
 }
 /* atan2(y, x) in (-pi, pi]; atan2(0,0) = 0.  Range reduction: t = min/max in [0,1], pi/8 split,
- * then octant / quadrant / sign fix-ups. */
+ * then octant / quadrant / sign fix-ups.  Measured against float64 over a 4096 x 4096 lattice of directions, the axes and the
+ * diagonals: |err| <= 2.8e-7 rad (4.4e-8 of a turn); tests/test_math_contract.py asserts 6e-7. */
 RTR_HD float rtr_atan2(float y, float x) {
     const float ax = rtr_abs(x), ay = rtr_abs(y);
     const float mx = ax > ay ? ax : ay, mn = ax > ay ? ay : ax;
@@ -214,7 +218,8 @@ RTR_HD float rtr_atan2(float y, float x) {
     if (x < 0.0f) r = 3.14159265359f - r;
     return y < 0.0f ? -r : r;
 }
-/* acos(x), x in [-1,1]: 2*atan2(sqrt(1-x), sqrt(1+x)) — accurate at both ends */
+/* acos(x), x in [-1,1]: 2*atan2(sqrt(1-x), sqrt(1+x)) — accurate at both ends.  Measured against float64 over [-1, 1]:
+ * |err| <= 3.5e-7 rad; tests/test_math_contract.py asserts 7e-7. */
 RTR_HD float rtr_acos(float x) {
     return 2.0f * rtr_atan2(rtr_sqrt(1.0f - x), rtr_sqrt(1.0f + x));
 }
@@ -285,15 +290,17 @@ RTR_HD void rtr_grid_from_bounds(const float* bmin, const float* bmax, float* or
  * the real quotient, so floor/ceil can be off by one only when v sits within ~1e-11 grid steps of a grid plane — a
  * slip far inside the builder's padding.  (A whole guard step on either side, as a float evaluation needs, made flat
  * boxes thick enough that every shadow ray started inside its own wall's leaves: +14 % triangle tests.)  floor/ceil
- * are exact and the division is IEEE: host and device agree bit for bit. */
+ * are exact and the division is IEEE: host and device agree bit for bit.  A quotient that is NaN (a world-space box that overflowed to
+ * inf: inf - inf, inf / inf) clamps to 0 like every q <= 0, so the float-to-int conversion, undefined for NaN and different between
+ * x86 and gfx950 where it is undefined, always gets a value of [0, 65535]. */
 RTR_HD uint32_t rtr_quant_lo(float v, float origin, float scale) {
     double q = __builtin_floor(((double)v - (double)origin) / (double)scale);
-    q = q < 0.0 ? 0.0 : (q > 65535.0 ? 65535.0 : q);
+    q = !(q > 0.0) ? 0.0 : (q > 65535.0 ? 65535.0 : q);      /* NaN -> 0 as well: the conversion below never sees one */
     return (uint32_t)q;
 }
 RTR_HD uint32_t rtr_quant_hi(float v, float origin, float scale) {
     double q = __builtin_ceil(((double)v - (double)origin) / (double)scale);
-    q = q < 0.0 ? 0.0 : (q > 65535.0 ? 65535.0 : q);
+    q = !(q > 0.0) ? 0.0 : (q > 65535.0 ? 65535.0 : q);      /* NaN -> 0 as well: the conversion below never sees one */
     return (uint32_t)q;
 }
 /* Per-ray constants of the quantised slab test: t(q) = q * ga + gb with ga = scale * idir, gb = (origin - o) * idir.
@@ -357,8 +364,10 @@ RTR_HD int rtr_mt_intersect(rtr_v3 o, rtr_v3 d, rtr_v3 v0, rtr_v3 e1, rtr_v3 e2,
 }
 
 /* ---- tone map: reference src/shaders/raygen.rgen:45-59 ----------------------------------- */
+/* Measured against the clamped float64 curve over [0, FLT_MAX]: |err| <= 2.4e-7; tests/test_math_contract.py asserts 5e-7. */
 RTR_HD float rtr_aces(float x) {
     const float a = 2.51f, b = 0.03f, c = 2.43f, d = 0.59f, e = 0.14f;
+    x = x > 1.0e18f ? 1.0e18f : x;             /* the curve is 1 from x = 7.3 on; beyond 1.2e19 x * x overflows: inf / inf, then NaN -> 0 */
     float num = x * rtr_fma(a, x, b);
     float den = rtr_fma(x, rtr_fma(c, x, d), e);
     return rtr_clamp(num / den, 0.0f, 1.0f);

@@ -82,7 +82,7 @@ class Expect:
                 hu = np.arctan2(dd[:, 2], dd[:, 0]) / (2 * 3.14159265) + 0.5
                 hv = 1.0 - np.arccos(np.clip(dd[:, 1], -1, 1)) / 3.14159265
                 sky = np.power(w.sample(w.hdri, hu, hv)[:, :3], 2.2)
-                slack = 2.2 * _tex_slack(w.hdri, 1e-6)                   # rtr_atan2 / rtr_acos are polynomial: ~1e-6 of a turn
+                slack = 2.2 * _tex_slack(w.hdri, 1e-6)                   # rtr_atan2 <= 6e-7 rad = 1e-7 turn, rtr_acos <= 7e-7 rad = 2.3e-7 of pi (test_math_contract.py): inside 1e-6
             else:
                 sky, slack = np.broadcast_to(w.sky, (len(m), 3)), 0.0
             self.val["color"][m] = sky

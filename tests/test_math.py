@@ -1,5 +1,7 @@
 """The numerical contract (include/rtr_math.h), exercised through the oracle's exported helpers:
-known-answer tests that are implementation independent + accuracy pins vs libm."""
+known-answer tests that are implementation independent + accuracy pins vs libm.
+The rest of the contract's pins: tests/test_math_contract.py (every function of the header against float64 references, host compile)
+and tests/test_gpu_math_contract.py (the device compile equals the host compile, bit for bit, over whole domains)."""
 import ctypes as C
 
 import numpy as np

@@ -305,8 +305,8 @@ int  rtr_scene_export_vertices(const rtr_scene* scene, RtrVertex* out, size_t by
  * again by itself), so an enqueued update after any of them writes records with the right masks and leaf slots.  Idempotent; an empty
  * scene returns RTR_OK.
  * rtr_scene_update_vertices_async: ranges, strides and rules of RTR_VERTICES_DEVICE (device pointers, 4-B aligned; stride a multiple of
- * 4, at least 12; normals optional).  No instances and no lights: their tables are made on the host, in double, and stay with the
- * synchronous calls.  The call returns without joining the device, the stream or the host to anything; inside it there is no allocation,
+ * 4, at least 12; normals optional).  No instances and no lights: they have an enqueued call of their own,
+ * rtr_scene_update_instances_async below.  The call returns without joining the device, the stream or the host to anything; inside it there is no allocation,
  * no synchronisation, no device -> host copy and no copy from host memory that could be reused before the copy runs — the table of
  * ranges travels as kernel arguments, 64 ranges per launch, and the caller's `ranges` array is free when the call returns (the DEVICE
  * memory it points at is read when the stream gets there).  Refused BEFORE anything is enqueued, with the synchronous call's messages:
@@ -332,6 +332,10 @@ int  rtr_scene_export_vertices(const rtr_scene* scene, RtrVertex* out, size_t by
  * rtr_light_rays_hinted (the leaf-table build) first join the scene's stream and read them back, once.  Renders and queries need none
  * of them.  The triangle -> leaf table and the instance masks survive, as in the synchronous call; the light-triangle table is always
  * remade.  Scenes replicated by librtr_mgpu have no enqueued update, as they have no update path. */
+/* Both enqueued updates — rtr_scene_update_vertices_async and rtr_scene_update_instances_async (below) — count on ONE serial sequence:
+ * `enqueued`, `refused` and firstRefusedUpdate speak of updates of either kind.  For a refused INSTANCE update firstBadVertex carries the
+ * smallest offending ELEMENT INDEX of that update instead of a vertex: i < numInstances(scene) is instance i (instance order),
+ * numInstances(scene) + l is light l.  The caller knows which call had which serial. */
 typedef struct rtr_update_status {
     uint64_t enqueued, refused;
     uint32_t firstRefusedUpdate, firstBadVertex;
@@ -344,6 +348,51 @@ int  rtr_scene_prepare_async_updates(rtr_scene* scene);
 int  rtr_scene_update_vertices_async(rtr_scene* scene, const rtr_vertex_range* ranges, uint32_t numRanges,
                                      uint32_t positionStride, uint32_t normalStride);
 int  rtr_scene_update_status(rtr_scene* scene, rtr_update_status* out);
+/* The ENQUEUED instance update: rtr_scene_update_instances as stream-ordered work — rigid bodies moved every frame from transforms that
+ * live on the device (a torch tensor, a physics kernel's output), the TLAS update of the reference (TLAS::updateTransform + TLAS::refit,
+ * src/vulkan/raytracing/tlas.cppm:151-207).  The synchronous call joins the whole device and makes the transform, normal-matrix,
+ * mirrored-bit and InstanceRef tables in host loops; this form makes them ON THE DEVICE and ends in the chain of
+ * rtr_scene_update_vertices_async.  The result is the synchronous call's, byte for byte (tested).
+ * transforms: a DEVICE pointer on the scene's device, 4-B aligned, or NULL (below): 12 floats per instance, a row-major 3x4 as
+ * RtrInstance::transform, transformStride bytes apart.  The stride is a multiple of 4 and at least 48: 48 is a packed (n,3,4) array, 64
+ * the top three rows of an (n,4,4) row-major matrix array, or an RtrInstance array entered at +16.  The records are for the instances
+ * firstInstance .. firstInstance + numInstances - 1 in INSTANCE ORDER (rtr_scene_desc::instances: lights first, then objects); the other
+ * instances keep their transforms.  Meshes and customIndex cannot change: there is nothing to pass them with.
+ * lights: a DEVICE array of numLights RtrAreaLightInfo (96 B each, 4-B aligned), or NULL to keep the light infos; numLights must be the
+ * scene's.  transforms == NULL with numInstances == 0 and a non-NULL lights is a lights-only update.  A light instance's transform and
+ * its RtrAreaLightInfo::transform must agree: as in the synchronous call, that is the caller's business.
+ * The scene must have been prepared (rtr_scene_prepare_async_updates, which also makes the instance-order -> customIndex device table
+ * this call needs; rtr_scene_rebuild prepares again by itself).  The call itself does no allocation, no synchronisation, no device ->
+ * host copy and no copy from reusable host memory: argument checks and launches only, everything enqueued on the scene's context
+ * stream — ORDERING as documented for rtr_scene_update_vertices_async.  The chain:
+ *   check kernel   one lane per element; reduces the smallest offending ELEMENT INDEX of this update into a device word.  Element
+ *                  i < numInstances(scene) is instance i: bad when one of its 12 floats is not inside +-3.0e38 (the synchronous call's
+ *                  rule).  Element numInstances(scene) + l is light l: bad when its vertexOffset, indexOffset or numTriangles differ
+ *                  from the scene's current device light table.  No other light field is validated, as in the synchronous call.
+ *   write kernel   nothing at all when the word is set: all of the update lands or none of it.  Otherwise, for each named instance at
+ *                  its customIndex slot: the transform table (12 floats), words 0..8 of the normal-matrix slot (rtr_normal_matrix),
+ *                  the mirrored word (1 iff the 3x3 determinant, in double, is negative — the host's expression and operation order;
+ *                  the other words of the slot keep their bytes) and the transform of the refit's instance table; and the light infos.
+ *   the refit chain of rtr_scene_update_vertices_async: refit -> 4-wide view -> its breadth-first order -> permutation -> light
+ *                  triangles (always remade) -> the status fold with this call's serial.  After a refused update the chain runs on
+ *                  unchanged tables: every byte and every answer stays.
+ * Refused BEFORE anything is enqueued (RTR_ERR_INVALID_ARGUMENT, the message names the function): a null scene; transforms and lights
+ * both NULL; transforms == NULL with numInstances != 0, or the reverse; a stride that is not a multiple of 4 or below 48; a misaligned
+ * pointer; firstInstance + numInstances (in 64 bits) past the scene's instances; a numLights that is not the scene's when lights is
+ * given; a scene that has not been prepared (the message names rtr_scene_prepare_async_updates).  An empty scene returns RTR_OK, counts
+ * as enqueued and does nothing.
+ * STATUS: rtr_scene_update_status, one serial sequence with the vertex updates (see rtr_update_status above).
+ * HOST MIRRORS.  After this call the library's host copies of the instance transforms and the light infos are stale too, and marked so:
+ * every call that reads them — rtr_scene_update_vertices with instances == NULL, rtr_scene_set_instance_masks, rtr_scene_rebuild,
+ * rtr_scene_update_lights, rtr_scene_update_instances, rtr_scene_create_like, rtr_scene_export_instances — first joins the scene's
+ * stream and reads them back from the device (transforms from the refit's instance table, lights from the light table), once. */
+int  rtr_scene_update_instances_async(rtr_scene* scene, const void* transforms, uint32_t transformStride,
+                                      uint32_t firstInstance, uint32_t numInstances,
+                                      const RtrAreaLightInfo* lights, uint32_t numLights);
+/* Copy out the instances as they are now, in instance order (test hook like rtr_scene_export_vertices, and what rtr_scene_create_like
+ * needs after a device-side animation): numInstances records; RTR_ERR_INVALID_ARGUMENT for a null pointer or a `bytes` that is not
+ * numInstances * 64.  Joins only the scene's stream, and only when an enqueued update has left the host copies stale. */
+int  rtr_scene_export_instances(const rtr_scene* scene, RtrInstance* out, size_t bytes);
 /* The SAH cost of the tree the kernels walk NOW: what a refit did to the tree's quality, and what a rebuild would win back.  A refit
  * keeps the split decisions made for the old shape, and rtr_scene_stats::sahCost is the host builder's number at creation (0 for a device
  * build), which no update ever touches; this is the measure a caller decides with (rtr_scene_rebuild below).

@@ -95,9 +95,11 @@ class TreeCost:
 
 @dataclasses.dataclass(frozen=True)
 class UpdateStatus:
-    """Scene.update_status(): enqueued — update_vertices_async calls accepted so far, whose serials count from 1; refused —
-    how many of them the device refused for bad data; first_refused_update / first_bad_vertex — the serial of the first refused update
-    since the last status call and the smallest scene vertex index it refused, None where there was none."""
+    """Scene.update_status(): enqueued — update_vertices_async and update_instances_async calls accepted so far, whose serials count
+    from 1 on one sequence; refused — how many of them the device refused for bad data; first_refused_update / first_bad_vertex — the
+    serial of the first refused update since the last status call and the smallest scene vertex index it refused, None where there
+    was none.  For a refused instance update first_bad_vertex is its smallest bad element: an instance index (instance order), or
+    the number of instances plus a light index."""
     enqueued: int
     refused: int
     first_refused_update: "int | None"
@@ -108,7 +110,8 @@ class Scene:
     def __init__(self, ctx, desc, like=None):
         """like: a Scene made from the same description whose tree is uploaded instead of built again (rtr_scene_create_like)"""
         self.ctx, self.lib = ctx, ctx.lib
-        self._async_keep = []         # tensors of enqueued vertex updates: referenced until the next update_status (or the scene's end)
+        self._async_keep = []         # tensors of enqueued updates: referenced until the next update_status (or the scene's end)
+        self._num_lights = int(desc.numLights)
         self._built_sah = None        # tree_cost().sah right after the last build or rebuild: taken on first use (update_vertices' policy)
         self.h = A.VP()
         self._num_instances = int(desc.numInstances)
@@ -293,6 +296,86 @@ class Scene:
                                                   iarr, len(instances) if instances is not None else 0,
                                                   larr, len(lights) if lights is not None else 0), "rtr_scene_update_vertices")
         del keep
+
+    def update_instances_async(self, transforms, first_instance=0, lights=None):
+        """rtr_scene_update_instances_async: update_instances as stream-ordered work — rigid bodies moved from transforms that live on
+        the device.  The update is ENQUEUED on the context's stream and the call returns at once, as update_vertices_async.
+        transforms: a float32 torch tensor on the scene's device of shape (n, 3, 4), (n, 12), (n, 4, 4) or (n, 16) — row-major
+        matrices, the top three rows are used — for the instances first_instance .. first_instance + n - 1 in instance order (lights
+        first, then objects); the others keep their transforms.  A strided row view is taken as it is when its rows qualify (stride a
+        multiple of 4 bytes and at least 48, 12 adjacent floats), else it is made contiguous.  None: a lights-only update.
+        lights: None keeps the light infos; a torch uint8 or float32 tensor of numLights * 96 bytes on the device; or a sequence of
+        A.RtrAreaLightInfo, staged once into a device tensor on the context's stream (a non-blocking copy from pinned memory the Scene
+        keeps referenced).  numpy arrays raise ValueError: host data stays with update_instances.  The scene needs
+        prepare_async_updates() once.  Bad data cannot raise here: update_status() reports it (first_bad_vertex: the instance index, or
+        the number of instances plus the light index), and a refused update changes nothing.  The tensors stay referenced until the
+        next update_status() or the scene's end."""
+        who = "update_instances_async"
+        torch = _torch()
+        dev = torch.device("cuda", self.ctx.device)
+        if isinstance(transforms, np.ndarray) or isinstance(lights, np.ndarray):
+            raise ValueError(f"{who}: takes torch tensors on the scene's device, not numpy arrays: host data stays with update_instances")
+        if transforms is None and lights is None:
+            raise ValueError(f"{who}: no transforms and no lights: nothing to update")
+        keep, tptr, stride, count = [], None, 48, 0
+        if transforms is not None:
+            t = transforms
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+                raise ValueError(f"{who}: transforms must be a float32 torch tensor on the scene's device, got {type(t).__name__}")
+            if t.device != dev:
+                raise ValueError(f"{who}: transforms live on {t.device}, the scene on {dev}")
+            shape = tuple(t.shape)
+            if len(shape) == 3 and shape[1:] in ((3, 4), (4, 4)):
+                inner_ok = t.stride(2) == 1 and t.stride(1) == 4
+            elif len(shape) == 2 and shape[1] in (12, 16):
+                inner_ok = t.stride(1) == 1
+            else:
+                raise ValueError(f"{who}: transforms must be (n, 3, 4), (n, 12), (n, 4, 4) or (n, 16), got {shape}")
+            count = int(shape[0])
+            if count == 0:
+                raise ValueError(f"{who}: transforms without rows (pass None for a lights-only update)")
+            row = 4 * t.stride(0)
+            if not inner_ok or (count > 1 and (row % 4 or row < 48)):
+                t = t.contiguous()
+                row = 4 * t.stride(0)
+            stride = row if count > 1 else 48
+            if first_instance < 0 or first_instance + count > 0xffffffff:
+                raise ValueError(f"{who}: first_instance {first_instance} with {count} instances does not fit 32 bits")
+            keep.append(t)
+            tptr = t.data_ptr()
+        lptr, nl = None, 0
+        if lights is not None:
+            if isinstance(lights, torch.Tensor):
+                lt = lights
+                if lt.dtype not in (torch.uint8, torch.float32):
+                    raise ValueError(f"{who}: a lights tensor must be uint8 or float32, got {lt.dtype}")
+                if lt.device != dev:
+                    raise ValueError(f"{who}: lights live on {lt.device}, the scene on {dev}")
+                lt = lt.contiguous()
+                nbytes = lt.numel() * lt.element_size()
+                if nbytes % 96:
+                    raise ValueError(f"{who}: a lights tensor holds whole RtrAreaLightInfo records of 96 bytes, got {nbytes} bytes")
+                nl = nbytes // 96
+                keep.append(lt)
+            else:
+                seq = list(lights)
+                nl = len(seq)
+                raw = bytes((A.RtrAreaLightInfo * nl)(*seq))
+                pinned = torch.frombuffer(bytearray(raw), dtype=torch.uint8).pin_memory() if nl else torch.zeros(0, dtype=torch.uint8)
+                with torch.cuda.stream(torch.cuda.ExternalStream(self.ctx.get_stream(), device=dev)):      # staged on the context's stream, once
+                    lt = pinned.to(dev, non_blocking=True) if nl else torch.zeros(1, dtype=torch.uint8, device=dev)
+                keep += [pinned, lt]
+            lptr = lt.data_ptr()
+        _check(self.lib.rtr_scene_update_instances_async(self.h, A.VP(tptr) if tptr else None, stride, int(first_instance) if tptr else 0, count,
+                                                         C.cast(A.VP(lptr), C.POINTER(A.RtrAreaLightInfo)) if lptr else None, nl),
+               "rtr_scene_update_instances_async")
+        self._async_keep += keep
+
+    def export_instances(self):
+        """rtr_scene_export_instances: the instances as they are now, in instance order — a ctypes array of A.RtrInstance"""
+        out = (A.RtrInstance * self._num_instances)()
+        _check(self.lib.rtr_scene_export_instances(self.h, out if self._num_instances else None, C.sizeof(out)), "rtr_scene_export_instances")
+        return out
 
     VERTEX_DTYPE = np.dtype([("position", np.float32, 3), ("pad0", np.float32), ("normal", np.float32, 3), ("pad1", np.float32),
                              ("uv", np.float32, 2), ("pad2", np.float32, 2)])

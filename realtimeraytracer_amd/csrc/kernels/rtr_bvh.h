@@ -69,6 +69,18 @@ hipError_t launch_check_vertices_args(const VertexRangeArgs& t, uint32_t positio
 hipError_t launch_write_vertices_args(const VertexRangeArgs& t, uint32_t positionStrideWords, uint32_t normalStrideWords, RtrVertex* vertices,
                                       const uint32_t* firstBad, hipStream_t s);
 hipError_t launch_fold_update_status(const uint32_t* firstBad, uint32_t* status, uint32_t serial, hipStream_t s);
+/* The enqueued instance update (rtr_scene_update_instances_async): the instance and light tables of a refit made on the device.  One
+ * lane per element of the update — numInstances records of 12 words (a row-major 3x4), strideWords apart, for the instances
+ * firstInstance .. in INSTANCE ORDER, then the numLights light infos (24 words each; lights null: no light lanes).
+ * check: atomicMin(firstBad, e) for the smallest offending element e — instance index i when one of its 12 floats is not inside
+ * +-3.0e38, sceneInstances + l when light l names another vertexOffset / indexOffset / numTriangles than sceneLights[l] holds.
+ * write: nothing at all when *firstBad is set; else, at the slot customOf[instance] of every named instance, xforms (12 words), nmats
+ * words 0..8 (rtr_normal_matrix) and word mirroredWord (rtr_mirrored.h), refs[].transform; and the light infos into sceneLights. */
+hipError_t launch_check_instances(const void* transforms, uint32_t strideWords, uint32_t firstInstance, uint32_t numInstances, const void* lights,
+                                  uint32_t numLights, uint32_t sceneInstances, const RtrAreaLightInfo* sceneLights, uint32_t* firstBad, hipStream_t s);
+hipError_t launch_write_instances(const void* transforms, uint32_t strideWords, uint32_t firstInstance, uint32_t numInstances, const void* lights,
+                                  uint32_t numLights, const uint32_t* customOf, uint32_t mirroredWord, float* xforms, float* nmats, InstanceRef* refs,
+                                  RtrAreaLightInfo* sceneLights, const uint32_t* firstBad, hipStream_t s);
 /* bvh_refit with the reduction words set by a kernel: no host memory is read after the call returns */
 hipError_t bvh_refit_enqueued(const BvhInputs& in, uint32_t numPrims, uint32_t numNodes, const BvhDeviceArrays& a, hipStream_t s);
 

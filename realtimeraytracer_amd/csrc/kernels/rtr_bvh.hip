@@ -26,6 +26,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include "../../../include/rtr_math.h"
+#include "rtr_mirrored.h"
 
 namespace rtrdev {
 
@@ -660,6 +661,66 @@ __global__ void k_fold_update_status(const uint32_t* __restrict__ firstBad, uint
     if (st[1] == 0xffffffffu) { st[1] = serial; st[2] = bad; }
 }
 
+/* ---- the enqueued instance update (rtr_scene_update_instances_async) -------------------------------------------------
+ * The instance and light tables of a refit made ON THE DEVICE from the caller's device arrays.  One lane per ELEMENT of the update:
+ * lanes 0 .. numInstances-1 are the records (instance firstInstance + lane, in instance order), the numLights lanes after them the
+ * light infos.  The check reduces the smallest offending element index — instance index, or sceneInstances + light — into *firstBad;
+ * the write is predicated on that word, as the vertex update's: set, no lane writes anything. */
+struct InstanceUpdateArgs {
+    const uint32_t* transforms;          /* numInstances records of 12 words, strideWords apart; null with numInstances == 0 */
+    const uint32_t* lights;              /* numLights x 24 words (RtrAreaLightInfo), or null: no light lanes */
+    uint32_t strideWords, firstInstance, numInstances, numLights, sceneInstances;
+};
+
+__global__ __launch_bounds__(kB) void k_check_instances(InstanceUpdateArgs a, const RtrAreaLightInfo* __restrict__ sceneLights, uint32_t* __restrict__ firstBad) {
+    const uint32_t i = blockIdx.x * kB + threadIdx.x;
+    if (i < a.numInstances) {
+        const uint32_t* src = a.transforms + (size_t)i * a.strideWords;
+        bool ok = true;
+#pragma unroll
+        for (int k = 0; k < 12; ++k) {
+            const float x = __uint_as_float(src[k]);
+            ok = ok && (x > -3.0e38f && x < 3.0e38f);        /* the rule of rtr_scene_update_instances: NaN fails both comparisons */
+        }
+        if (!ok) atomicMin(firstBad, a.firstInstance + i);
+    } else if (i - a.numInstances < a.numLights) {
+        const uint32_t l = i - a.numInstances;
+        const uint32_t* mine = a.lights + (size_t)l * 24u;
+        const RtrAreaLightInfo& cur = sceneLights[l];
+        if (mine[4] != cur.vertexOffset || mine[5] != cur.indexOffset || mine[6] != cur.numTriangles) atomicMin(firstBad, a.sceneInstances + l);
+    }
+}
+
+__global__ __launch_bounds__(kB) void k_write_instances(InstanceUpdateArgs a, const uint32_t* __restrict__ customOf, uint32_t mirroredWord,
+                                                        uint32_t* __restrict__ xforms, uint32_t* __restrict__ nmats, InstanceRef* __restrict__ refs,
+                                                        uint32_t* __restrict__ sceneLights, const uint32_t* __restrict__ firstBad) {
+    if (*firstBad != 0xffffffffu) return;                /* a refused update: every table keeps its bytes */
+    const uint32_t i = blockIdx.x * kB + threadIdx.x;
+    if (i < a.numInstances) {
+        const uint32_t* src = a.transforms + (size_t)i * a.strideWords;
+        const uint32_t ci = customOf[a.firstInstance + i];
+        float m[12], nm[9];
+#pragma unroll
+        for (int k = 0; k < 12; ++k) m[k] = __uint_as_float(src[k]);
+        rtr_normal_matrix(m, nm);
+        const uint32_t bit = rtr_mirrored_bit(m);
+        uint32_t* xf = xforms + 12u * (size_t)ci;
+        uint32_t* nd = nmats + 12u * (size_t)ci;
+        uint32_t* rf = reinterpret_cast<uint32_t*>(refs[ci].transform);
+#pragma unroll
+        for (int k = 0; k < 12; ++k) { const uint32_t w = __float_as_uint(m[k]); xf[k] = w; rf[k] = w; }
+#pragma unroll
+        for (int k = 0; k < 9; ++k) nd[k] = __float_as_uint(nm[k]);
+        nd[mirroredWord] = bit;                          /* the other words of the slot keep their bytes */
+    } else if (i - a.numInstances < a.numLights) {
+        const uint32_t l = i - a.numInstances;
+        const uint32_t* mine = a.lights + (size_t)l * 24u;
+        uint32_t* dst = sceneLights + (size_t)l * 24u;
+#pragma unroll
+        for (int k = 0; k < 24; ++k) dst[k] = mine[k];
+    }
+}
+
 /* the reduction words of a refit as bvh_refit's host array sets them, without a host array */
 __global__ void k_refit_init(uint32_t* __restrict__ red) {
     const uint32_t i = threadIdx.x;
@@ -846,6 +907,29 @@ hipError_t launch_write_vertices_args(const VertexRangeArgs& t, uint32_t positio
 
 hipError_t launch_fold_update_status(const uint32_t* firstBad, uint32_t* status, uint32_t serial, hipStream_t s) {
     hipLaunchKernelGGL(k_fold_update_status, dim3(1), dim3(64), 0, s, firstBad, status, serial);
+    return hipGetLastError();
+}
+
+hipError_t launch_check_instances(const void* transforms, uint32_t strideWords, uint32_t firstInstance, uint32_t numInstances, const void* lights,
+                                  uint32_t numLights, uint32_t sceneInstances, const RtrAreaLightInfo* sceneLights, uint32_t* firstBad, hipStream_t s) {
+    const InstanceUpdateArgs a{static_cast<const uint32_t*>(transforms), static_cast<const uint32_t*>(lights), strideWords, firstInstance, numInstances,
+                               lights ? numLights : 0u, sceneInstances};
+    const uint64_t total = (uint64_t)a.numInstances + a.numLights;
+    if (total == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_check_instances, dim3((uint32_t)((total + kB - 1) / kB)), dim3(kB), 0, s, a, sceneLights, firstBad);
+    return hipGetLastError();
+}
+
+hipError_t launch_write_instances(const void* transforms, uint32_t strideWords, uint32_t firstInstance, uint32_t numInstances, const void* lights,
+                                  uint32_t numLights, const uint32_t* customOf, uint32_t mirroredWord, float* xforms, float* nmats, InstanceRef* refs,
+                                  RtrAreaLightInfo* sceneLights, const uint32_t* firstBad, hipStream_t s) {
+    const InstanceUpdateArgs a{static_cast<const uint32_t*>(transforms), static_cast<const uint32_t*>(lights), strideWords, firstInstance, numInstances,
+                               lights ? numLights : 0u, 0u};
+    const uint64_t total = (uint64_t)a.numInstances + a.numLights;
+    if (total == 0) return hipSuccess;
+    if (mirroredWord < 9u || mirroredWord > 11u) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_write_instances, dim3((uint32_t)((total + kB - 1) / kB)), dim3(kB), 0, s, a, customOf, mirroredWord, reinterpret_cast<uint32_t*>(xforms),
+                       reinterpret_cast<uint32_t*>(nmats), refs, reinterpret_cast<uint32_t*>(sceneLights), firstBad);
     return hipGetLastError();
 }
 

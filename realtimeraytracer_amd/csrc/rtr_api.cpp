@@ -8,6 +8,7 @@
 #include "kernels/rtr_kernels.h"
 #include "kernels/rtr_post.h"
 #include "kernels/rtr_bvh.h"
+#include "kernels/rtr_mirrored.h"
 #include "kernels/rtr_query.h"
 
 #include <hip/hip_runtime.h>
@@ -178,6 +179,11 @@ struct rtr_scene {
     DevBuf<uint32_t> orderScratch, asyncWords;
     bool asyncReady = false;
     mutable bool mirrorsStale = false;
+    /* rtr_scene_update_instances_async: per instance, in instance order, its customIndex (fixed for the scene's life; made by
+     * rtr_scene_prepare_async_updates).  instancesStale: an enqueued instance update has run (or will) since hostInstances' transforms
+     * and hostLights were current; set together with mirrorsStale, refresh_mirrors reads them back from instRefs and lights */
+    DevBuf<uint32_t> instCustom;
+    mutable bool instancesStale = false;
     uint64_t asyncEnqueued = 0;
     /* rtr_scene_tree_cost: the kernel's words, and for a tree without refit arrays whose slots are not all reachable, a parent array of
      * its own (costParentState: 0 not looked at yet, 1 every slot is in the tree, 2 costParent holds it).  mutable: the call takes the
@@ -411,11 +417,9 @@ static int validate_desc(const rtr_scene_desc* d) {
  * transform, evaluated in double, is negative — the instance turns the winding of its triangles over, and Vulkan decides facing in object
  * space.  It lives in word kMirroredWord of the instance's 12-float slot of the normal-matrix table, which the matrix does not use: a
  * per-customIndex table that is uploaded with the transforms by create, create_like and update_instances, and that no triangle record
- * and no kernel argument had to change for. */
+ * and no kernel argument had to change for.  The determinant is rtr_mirrored_bit (kernels/rtr_mirrored.h), which the enqueued instance update's kernel evaluates too. */
 static void set_mirrored_word(const float* m, float* nmatSlot) {
-    const double det = (double)m[0] * ((double)m[5] * m[10] - (double)m[6] * m[9]) - (double)m[1] * ((double)m[4] * m[10] - (double)m[6] * m[8]) +
-                       (double)m[2] * ((double)m[4] * m[9] - (double)m[5] * m[8]);
-    const uint32_t bit = det < 0.0 ? 1u : 0u;
+    const uint32_t bit = rtr_mirrored_bit(m);
     memcpy(&nmatSlot[rtrdev::kMirroredWord], &bit, sizeof bit);
 }
 
@@ -520,9 +524,11 @@ static void make_prim_tables(const rtr_scene_desc* d, const RtrInstance* instanc
     }
 }
 
-/* The host mirrors after enqueued updates (rtr_scene_update_vertices_async leaves them stale): joins the scene's stream and reads back
- * what the synchronous refit reads back — nodes, records, grid, boxPad — and the count of reached 4-wide entries k_wide_order left on
- * the device.  Every call that looks at a mirror comes through here first; it costs nothing while no update has been enqueued. */
+/* The host mirrors after enqueued updates (rtr_scene_update_vertices_async and rtr_scene_update_instances_async leave them stale):
+ * joins the scene's stream and reads back what the synchronous refit reads back — nodes, records, grid, boxPad — and the count of
+ * reached 4-wide entries k_wide_order left on the device; after an enqueued INSTANCE update also the transforms of hostInstances (from
+ * the InstanceRef table, through customIndex) and hostLights.  Every call that looks at a mirror comes through here first; it costs
+ * nothing while no update has been enqueued. */
 static int refresh_mirrors(const rtr_scene* cs) {
     if (!cs->mirrorsStale) return RTR_OK;
     rtr_scene* s = const_cast<rtr_scene*>(cs);
@@ -537,6 +543,14 @@ static int refresh_mirrors(const rtr_scene* cs) {
     float mabs; memcpy(&mabs, &red[6], 4);
     s->stats.boxPad = (mabs > 1e-6f ? mabs : 1e-6f) * 3.814697265625e-06f;
     s->wideReached = reached; s->stats.numWideNodes = reached;
+    if (s->instancesStale) {
+        static_assert(sizeof(rtrdev::InstanceRef) == 64 && sizeof(RtrInstance) == 64, "layout");
+        std::vector<rtrdev::InstanceRef> refs(s->hostInstances.size());
+        if (!refs.empty()) HIP_TRY(hipMemcpy(refs.data(), s->instRefs.p, refs.size() * sizeof(rtrdev::InstanceRef), hipMemcpyDeviceToHost));
+        for (RtrInstance& in : s->hostInstances) memcpy(in.transform, refs[in.customIndex].transform, sizeof in.transform);
+        if (s->numLights) HIP_TRY(hipMemcpy(s->hostLights.data(), s->lights.p, s->numLights * sizeof(RtrAreaLightInfo), hipMemcpyDeviceToHost));
+        s->instancesStale = false;
+    }
     s->mirrorsStale = false;
     return RTR_OK;
 }
@@ -1140,12 +1154,43 @@ int rtr_scene_prepare_async_updates(rtr_scene* s) {
         rc = upload_prim_tables(s, s->hostInstances.data());
         if (rc != RTR_OK) return rc;
         HIP_TRY(s->orderScratch.ensure(2 * s->hostNodes.size()));
+        if (!s->instCustom.p) {      /* kept through a rebuild: the instances are the scene's, not the tree's */
+            std::vector<uint32_t> custom(s->hostInstances.size());
+            for (size_t i = 0; i < custom.size(); ++i) custom[i] = s->hostInstances[i].customIndex;
+            HIP_TRY(s->instCustom.upload(custom.data(), custom.size(), s->ctx->stream));
+        }
     }
     if (!s->asyncWords.p) {      /* kept through a rebuild: the status is the scene's, not the tree's */
         const uint32_t none = 0xffffffffu, init[8] = {none, 0u, 0u, 0u, 0u, none, none, 0u};
         HIP_TRY(s->asyncWords.upload(init, 8, s->ctx->stream));
     }
     s->asyncReady = true;
+    return RTR_OK;
+}
+
+/* What both enqueued updates end in, on the tables and vertices as they are when the stream gets there: the refit, the 4-wide view, its
+ * breadth-first order made on the device, the permutation, the light triangles (always remade), and the fold of the update's word
+ * (asyncWords[0]) into the sticky status under this call's serial.  Counts the update as enqueued. */
+static int enqueue_refit_tail(rtr_scene* s, uint32_t serial, const char* who) {
+    hipStream_t st = s->ctx->stream;
+    uint32_t* firstBad = s->asyncWords.p;
+    const uint32_t n = (uint32_t)s->hostNodes.size();
+    rtrdev::BvhInputs in{s->prims.p, s->instRefs.p, s->vertices.p, s->indices.p};
+    hipError_t e = rtrdev::bvh_refit_enqueued(in, s->numPrims, s->numNodeSlots, device_arrays(s), st);
+    if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: device BVH refit: %s", who, hipGetErrorString(e));
+    s->mirrorsStale = true;
+    e = rtrdev::bvh_make_wide(s->nodes.p, n, s->parent.p, s->grid.p, s->hostWideShape.size() == n ? s->wideShape.p : nullptr, s->nodes4tmp.p, s->wideSums.p, st);
+    if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: 4-wide node build: %s", who, hipGetErrorString(e));
+    e = rtrdev::bvh_wide_order(s->nodes4tmp.p, n, s->wideRemap.p, s->orderScratch.p, s->asyncWords.p + 1, st);
+    if (e == hipSuccess) e = rtrdev::bvh_permute_wide(s->nodes4tmp.p, n, s->wideRemap.p, s->nodes4.p, st);
+    if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: 4-wide node order: %s", who, hipGetErrorString(e));
+    if (s->numLights) {
+        e = rtrdev::launch_light_tris(s->lights.p, s->vertices.p, s->indices.p, s->lightTriFirst.p, s->numLights, s->lightTris.p, st);
+        if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: light-triangle records: %s", who, hipGetErrorString(e));
+    }
+    e = rtrdev::launch_fold_update_status(firstBad, s->asyncWords.p + 4, serial, st);
+    if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: status kernel: %s", who, hipGetErrorString(e));
+    ++s->asyncEnqueued;
     return RTR_OK;
 }
 
@@ -1180,24 +1225,48 @@ int rtr_scene_update_vertices_async(rtr_scene* s, const rtr_vertex_range* ranges
                                            : rtrdev::launch_write_vertices_args(t, posWords, nrmWords, s->vertices.p, firstBad, st);
             if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: %s kernel: %s", who, pass == 0 ? "checking" : "writing", hipGetErrorString(e));
         }
-    /* the refit on the vertices as they are now, the 4-wide view, its breadth-first order made on the device, the light triangles */
-    const uint32_t n = (uint32_t)s->hostNodes.size();
-    rtrdev::BvhInputs in{s->prims.p, s->instRefs.p, s->vertices.p, s->indices.p};
-    hipError_t e = rtrdev::bvh_refit_enqueued(in, s->numPrims, s->numNodeSlots, device_arrays(s), st);
-    if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: device BVH refit: %s", who, hipGetErrorString(e));
+    return enqueue_refit_tail(s, serial, who);
+}
+
+int rtr_scene_update_instances_async(rtr_scene* s, const void* transforms, uint32_t transformStride, uint32_t firstInstance, uint32_t numInstances,
+                                     const RtrAreaLightInfo* lights, uint32_t numLights) {
+    static const char* who = "rtr_scene_update_instances_async";
+    if (!s) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: null scene", who);
+    if (!transforms && !lights) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: null transforms and null lights: nothing to update", who);
+    if (!transforms && numInstances) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: null transforms with numInstances %u", who, numInstances);
+    if (transforms && !numInstances) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: transforms given with numInstances 0", who);
+    if (transforms && ((transformStride & 3u) || transformStride < 48u))
+        return fail(RTR_ERR_INVALID_ARGUMENT, "%s: transformStride %u must be a multiple of 4 and at least 48", who, transformStride);
+    if ((((uintptr_t)transforms) | ((uintptr_t)lights)) & 3u) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: device pointers must be 4-byte aligned", who);
+    /* nothing of the scene has been read up to here */
+    if ((uint64_t)firstInstance + numInstances > s->hostInstances.size())
+        return fail(RTR_ERR_INVALID_ARGUMENT, "%s: instances %u .. %llu leave the scene's %zu instances", who, firstInstance,
+                    (unsigned long long)firstInstance + numInstances, s->hostInstances.size());
+    if (lights && numLights != s->numLights) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: %u lights given, scene has %u", who, numLights, s->numLights);
+    if (!s->asyncReady) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: the scene has not been prepared: call rtr_scene_prepare_async_updates once first", who);
+    const uint32_t serial = (uint32_t)(s->asyncEnqueued + 1);
+    if (scene_is_empty(s)) { ++s->asyncEnqueued; return RTR_OK; }      /* nothing to refit, as the synchronous call */
+    HIP_TRY(hipSetDevice(s->ctx->device));
+    hipStream_t st = s->ctx->stream;
+    uint32_t* firstBad = s->asyncWords.p;
+    HIP_TRY(hipMemsetAsync(firstBad, 0xff, sizeof(uint32_t), st));
+    const uint32_t strideWords = transforms ? transformStride / 4u : 12u, sceneInstances = (uint32_t)s->hostInstances.size();
+    hipError_t e = rtrdev::launch_check_instances(transforms, strideWords, firstInstance, numInstances, lights, numLights, sceneInstances, s->lights.p, firstBad, st);
+    if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: checking kernel: %s", who, hipGetErrorString(e));
+    e = rtrdev::launch_write_instances(transforms, strideWords, firstInstance, numInstances, lights, numLights, s->instCustom.p, rtrdev::kMirroredWord,
+                                       s->xforms.p, s->nmats.p, s->instRefs.p, s->lights.p, firstBad, st);
+    if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: writing kernel: %s", who, hipGetErrorString(e));
+    s->instancesStale = true;      /* with mirrorsStale, which the tail sets: refresh_mirrors reads the transforms and lights back */
     s->mirrorsStale = true;
-    e = rtrdev::bvh_make_wide(s->nodes.p, n, s->parent.p, s->grid.p, s->hostWideShape.size() == n ? s->wideShape.p : nullptr, s->nodes4tmp.p, s->wideSums.p, st);
-    if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: 4-wide node build: %s", who, hipGetErrorString(e));
-    e = rtrdev::bvh_wide_order(s->nodes4tmp.p, n, s->wideRemap.p, s->orderScratch.p, s->asyncWords.p + 1, st);
-    if (e == hipSuccess) e = rtrdev::bvh_permute_wide(s->nodes4tmp.p, n, s->wideRemap.p, s->nodes4.p, st);
-    if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: 4-wide node order: %s", who, hipGetErrorString(e));
-    if (s->numLights) {
-        e = rtrdev::launch_light_tris(s->lights.p, s->vertices.p, s->indices.p, s->lightTriFirst.p, s->numLights, s->lightTris.p, st);
-        if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: light-triangle records: %s", who, hipGetErrorString(e));
-    }
-    e = rtrdev::launch_fold_update_status(firstBad, s->asyncWords.p + 4, serial, st);
-    if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: status kernel: %s", who, hipGetErrorString(e));
-    ++s->asyncEnqueued;
+    return enqueue_refit_tail(s, serial, who);
+}
+
+int rtr_scene_export_instances(const rtr_scene* s, RtrInstance* out, size_t bytes) {
+    if (!s || (!out && bytes)) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_scene_export_instances: null argument");
+    if (bytes != s->hostInstances.size() * sizeof(RtrInstance))
+        return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_scene_export_instances: bytes %zu != %zu", bytes, s->hostInstances.size() * sizeof(RtrInstance));
+    { const int rcm = refresh_mirrors(s); if (rcm != RTR_OK) return rcm; }
+    if (bytes) memcpy(out, s->hostInstances.data(), bytes);
     return RTR_OK;
 }
 
@@ -1419,6 +1488,7 @@ int rtr_scene_export_wide(const rtr_scene* s, RtrWideNode* nodes, size_t nodeByt
 int rtr_scene_update_lights(rtr_scene* s, const RtrAreaLightInfo* lights, uint32_t n) {
     if (!s || (!lights && n)) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_scene_update_lights: null argument");
     if (n != s->numLights) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_scene_update_lights: %u lights given, scene has %u (light geometry is part of the BVH)", n, s->numLights);
+    { const int rcm = refresh_mirrors(s); if (rcm != RTR_OK) return rcm; }      /* the transforms compared below: an enqueued instance update may have moved the lights */
     for (uint32_t l = 0; l < n; ++l) {
         if (lights[l].vertexOffset != s->hostLights[l].vertexOffset || lights[l].indexOffset != s->hostLights[l].indexOffset ||
             lights[l].numTriangles != s->hostLights[l].numTriangles || memcmp(lights[l].transform, s->hostLights[l].transform, sizeof lights[l].transform))

@@ -49,6 +49,9 @@ int fail(int code, const char* fmt, ...) {
 template <class T>
 struct DevBuf {
     T* p = nullptr; size_t n = 0;
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), n(o.n) { o.p = nullptr; o.n = 0; }      /* owns its memory: moved, never copied */
+    DevBuf& operator=(DevBuf&& o) noexcept { std::swap(p, o.p); std::swap(n, o.n); return *this; }
     ~DevBuf() { release(); }
     void release() { if (p) { (void)hipFree(p); p = nullptr; n = 0; } }
     hipError_t alloc(size_t count) {
@@ -62,7 +65,6 @@ struct DevBuf {
     hipError_t grow(size_t count) { return (p && n >= count) ? hipSuccess : alloc(count + count / 2); }
     /* a buffer whose size is fixed by its owner and that is kept from call to call: allocated on first use */
     hipError_t ensure(size_t count) { return (p && n >= count) ? hipSuccess : alloc(count); }
-    void swap(DevBuf& o) { std::swap(p, o.p); std::swap(n, o.n); }
     hipError_t upload(const T* src, size_t count, hipStream_t s) {
         hipError_t e = alloc(count);
         if (e != hipSuccess) return e;
@@ -116,8 +118,12 @@ struct BuildScratch {
     DevBuf<uint8_t> sortTemp;
 };
 
-struct rtr_scene {
-    rtr_ctx* ctx = nullptr;
+/* The tree of a scene.  A member is here if and only if it must not outlive the tree: its content or its size is a function of the node
+ * count, the leaf order or the boxes.  rtr_scene_rebuild builds a fresh SceneTree and swaps it in whole, so whatever is here starts
+ * empty with a new tree and is made again by the call that needs it; what is per customIndex, per instance or per vertex, and the
+ * status of the enqueued updates, stays on rtr_scene and is kept through a rebuild. */
+namespace {
+struct SceneTree {
     DevBuf<uint4> nodes;                 /* RtrBvhNode, 2 x uint4 each */
     DevBuf<float4> nodesF;               /* rtr::BvhNodeF, 4 x float4 each: device build / refit only */
     DevBuf<RtrBvhGrid> grid;
@@ -129,6 +135,35 @@ struct rtr_scene {
     uint32_t wideReached = 0;            /* entries the 4-wide tree reaches (they come first in nodes4) */
     DevBuf<uint4> nodes4;                /* RtrWideNode: 4-wide view of the tree for the any-hit kernel, breadth-first order (kernels/rtr_bvh.hip) */
     DevBuf<float4> tris;
+    std::vector<RtrBvhNode> hostNodes;
+    std::vector<RtrBvhTri> hostTris;
+    /* device build / refit state (kernels/rtr_bvh.hip) */
+    DevBuf<rtrdev::PrimRef> prims;
+    DevBuf<rtrdev::InstanceRef> instRefs;
+    DevBuf<float4> boxMin, boxMax;
+    DevBuf<int32_t> parent;
+    DevBuf<uint32_t> counters, depth, slotOfPrim, red;
+    uint32_t numPrims = 0, numNodeSlots = 0;
+    bool refitReady = false;
+    /* the triangle -> leaf table (rtr_hit_leaves, rtr_light_rays_hinted): made by the first call that asks for it (ensure_leaf_table), kept
+     * through refits, which keep topology and leaf order.  mutable: the query calls take the scene const */
+    mutable DevBuf<int32_t> leafTable;
+    mutable bool leafReady = false;
+    /* rtr_scene_tree_cost: for a tree without refit arrays whose slots are not all reachable, a parent array of its own (costParentState:
+     * 0 not looked at yet, 1 every slot is in the tree, 2 costParent holds it).  mutable: the call takes the scene const, like the leaf table */
+    mutable DevBuf<int32_t> costParent;
+    mutable int costParentState = 0;
+    /* the enqueued updates (rtr_scene_prepare_async_updates): k_wide_order's scratch (2 x numNodes words).  asyncReady: prims and instRefs
+     * are on the device for this tree, it is refit-ready, and the scratch and the scene's asyncWords and instCustom exist */
+    DevBuf<uint32_t> orderScratch;
+    bool asyncReady = false;
+    rtr_scene_stats stats{};
+};
+}  // namespace
+
+struct rtr_scene {
+    rtr_ctx* ctx = nullptr;
+    SceneTree tree;
     DevBuf<RtrVertex> vertices;
     DevBuf<uint32_t> indices;
     DevBuf<RtrObjectInfo> objects;
@@ -141,43 +176,28 @@ struct rtr_scene {
      * The records carry them (bits 8..15 of flags, complemented); this table is what the getter returns and what a refit re-applies */
     std::vector<uint8_t> hostMasks;
     DevBuf<uint32_t> maskBits;           /* per customIndex: (~mask & 0xff) << 8, the setter kernel's table */
-    /* the triangle -> leaf table (rtr_hit_leaves, rtr_light_rays_hinted): made by the first call that asks for it (ensure_leaf_table), kept
-     * through refits, which keep topology and leaf order.  mutable: the query calls take the scene const */
     std::vector<uint32_t> hostTriCount;
-    mutable DevBuf<uint32_t> leafBase;   /* per customIndex: prefix sum of triCount */
-    mutable DevBuf<int32_t> leafTable;
-    mutable bool leafReady = false;
+    mutable DevBuf<uint32_t> leafBase;   /* per customIndex: prefix sum of triCount (made with the tree's leaf table) */
     DevBuf<float> xforms, nmats, ltc1, ltc2;
     std::vector<DevBuf<uint8_t>> texPixels;
     DevBuf<uint8_t> hdriPixels;
     DevBuf<rtrdev::DeviceTexture> texTable;
-    std::vector<RtrBvhNode> hostNodes;
-    std::vector<RtrBvhTri> hostTris;
     std::vector<RtrAreaLightInfo> hostLights;
-    /* device build / refit state (kernels/rtr_bvh.hip) */
     std::vector<RtrInstance> hostInstances;
     std::vector<RtrMesh> hostMeshes;
     std::vector<RtrObjectInfo> hostObjects;
-    DevBuf<rtrdev::PrimRef> prims;
-    DevBuf<rtrdev::InstanceRef> instRefs;
-    DevBuf<float4> boxMin, boxMax;
-    DevBuf<int32_t> parent;
-    DevBuf<uint32_t> counters, depth, slotOfPrim, red;
-    uint32_t numPrims = 0, numNodeSlots = 0;
-    bool refitReady = false;
     /* rtr_scene_update_vertices: the device table of ranges, their prefix counts (+ the "first bad vertex" word), and the staging
      * buffer host data is packed into (vtxHost) and copied to (vtxStage); they grow on demand and are reused by every call */
     DevBuf<rtrdev::VertexRange> vtxRanges;
     DevBuf<uint32_t> vtxPrefix, vtxStage;
     std::vector<uint32_t> vtxHost;
     BuildScratch buildScratch;           /* rtr_scene_rebuild with RTR_BUILD_DEVICE_LBVH: empty until the first one */
-    /* rtr_scene_update_vertices_async (made by rtr_scene_prepare_async_updates): k_wide_order's scratch (2 x numNodes words) and the
-     * words of the enqueued chain — [0] the first bad vertex of the update in flight, [1] the entries the 4-wide tree reaches,
-     * [4..6] the sticky status (refused count, serial of the first refused update since the last status call, its first bad vertex).
-     * mirrorsStale: an enqueued update has run (or will) since hostNodes, hostTris, stats.grid, stats.boxPad and wideReached were
-     * read back; refresh_mirrors joins the stream and reads them again.  mutable: the export calls take the scene const */
-    DevBuf<uint32_t> orderScratch, asyncWords;
-    bool asyncReady = false;
+    /* the enqueued updates (made by rtr_scene_prepare_async_updates): the words of the enqueued chain — [0] the first bad vertex of the
+     * update in flight, [1] the entries the 4-wide tree reaches, [4..6] the sticky status (refused count, serial of the first refused
+     * update since the last status call, its first bad vertex).
+     * mirrorsStale: an enqueued update has run (or will) since the tree's hostNodes, hostTris, stats.grid, stats.boxPad and wideReached
+     * were read back; refresh_mirrors joins the stream and reads them again.  mutable: the export calls take the scene const */
+    DevBuf<uint32_t> asyncWords;
     mutable bool mirrorsStale = false;
     /* rtr_scene_update_instances_async: per instance, in instance order, its customIndex (fixed for the scene's life; made by
      * rtr_scene_prepare_async_updates).  instancesStale: an enqueued instance update has run (or will) since hostInstances' transforms
@@ -185,17 +205,14 @@ struct rtr_scene {
     DevBuf<uint32_t> instCustom;
     mutable bool instancesStale = false;
     uint64_t asyncEnqueued = 0;
-    /* rtr_scene_tree_cost: the kernel's words, and for a tree without refit arrays whose slots are not all reachable, a parent array of
-     * its own (costParentState: 0 not looked at yet, 1 every slot is in the tree, 2 costParent holds it).  mutable: the call takes the
-     * scene const, like the leaf table */
-    mutable DevBuf<unsigned long long> costWords;
-    mutable DevBuf<int32_t> costParent;
-    mutable int costParentState = 0;
-    rtr_scene_stats stats{};
+    mutable DevBuf<unsigned long long> costWords;      /* rtr_scene_tree_cost: the kernel's words */
     DeviceScene dev{};
     uint32_t numLights = 0, numObjects = 0, numVertices = 0, numIndices = 0;
     bool hasLtc = false;
 };
+
+/* no geometry: the host builder's tree of such a scene is one node over one placeholder record */
+static bool scene_is_empty(const rtr_scene* s) { return s->tree.hostTris.empty() || s->tree.hostTris[0].customIndex == 0xffffffffu; }
 
 struct rtr_frame {
     rtr_ctx* ctx = nullptr;
@@ -275,10 +292,6 @@ uint32_t rtr_shard_rows(uint32_t height, uint32_t bandRows, uint32_t shardCount)
 }
 
 /* ---- context ------------------------------------------------------------------------------ */
-static int ctx_create_prio(int ordinal, int priorityRank, rtr_ctx** out);
-
-int rtr_ctx_create(int ordinal, rtr_ctx** out) { return ctx_create_prio(ordinal, -1, out); }
-
 /* priorityRank < 0: a stream of default priority.  >= 0: rank 0 gets the device's highest stream priority, rank 1 the next ... (the
  * parts of a split render: the dispatcher then prefers the workgroups of an earlier part wherever two parts compete for a slot) */
 static int ctx_create_prio(int ordinal, int priorityRank, rtr_ctx** out) {
@@ -309,6 +322,8 @@ static int ctx_create_prio(int ordinal, int priorityRank, rtr_ctx** out) {
     *out = c;
     return RTR_OK;
 }
+
+int rtr_ctx_create(int ordinal, rtr_ctx** out) { return ctx_create_prio(ordinal, -1, out); }
 
 int rtr_ctx_set_tunable(rtr_ctx* c, const char* name, uint32_t value) {
     if (!c || !name) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_ctx_set_tunable: null argument");
@@ -423,6 +438,17 @@ static void set_mirrored_word(const float* m, float* nmatSlot) {
     memcpy(&nmatSlot[rtrdev::kMirroredWord], &bit, sizeof bit);
 }
 
+/* the per-customIndex transform tables: the 3x4 transforms, and the normal matrices with the mirrored word */
+static void instance_tables(uint32_t numInstances, const RtrInstance* instances, std::vector<float>& xforms, std::vector<float>& nmats) {
+    xforms.assign(12 * (size_t)numInstances, 0.f);
+    nmats.assign(12 * (size_t)numInstances, 0.f);
+    for (uint32_t i = 0; i < numInstances; ++i) {
+        memcpy(&xforms[12 * (size_t)instances[i].customIndex], instances[i].transform, 12 * sizeof(float));
+        rtr_normal_matrix(instances[i].transform, &nmats[12 * (size_t)instances[i].customIndex]);
+        set_mirrored_word(instances[i].transform, &nmats[12 * (size_t)instances[i].customIndex]);
+    }
+}
+
 /* flatten TLAS instances to one world-space triangle soup (instance order, then primitive order),
  * fill the per-customIndex transform tables, build the BVH */
 static int flatten_and_build(const rtr_scene_desc* d, rtr::BvhResult& bvh, std::vector<float>& xforms, std::vector<float>& nmats,
@@ -431,14 +457,10 @@ static int flatten_and_build(const rtr_scene_desc* d, rtr::BvhResult& bvh, std::
     size_t total = 0;
     for (uint32_t i = 0; i < d->numInstances; ++i) total += d->meshes[d->instances[i].meshIndex].indexCount / 3u;
     soup.reserve(total);
-    xforms.assign(12 * (size_t)d->numInstances, 0.f);
-    nmats.assign(12 * (size_t)d->numInstances, 0.f);
+    instance_tables(d->numInstances, d->instances, xforms, nmats);
     for (uint32_t i = 0; i < d->numInstances; ++i) {
         const RtrInstance& in = d->instances[i];
         const RtrMesh& me = d->meshes[in.meshIndex];
-        memcpy(&xforms[12 * (size_t)in.customIndex], in.transform, 12 * sizeof(float));
-        rtr_normal_matrix(in.transform, &nmats[12 * (size_t)in.customIndex]);
-        set_mirrored_word(in.transform, &nmats[12 * (size_t)in.customIndex]);
         for (uint32_t t = 0; t < me.indexCount / 3u; ++t) {
             rtr::WorldTriangle w;
             for (int k = 0; k < 3; ++k) {
@@ -524,6 +546,18 @@ static void make_prim_tables(const rtr_scene_desc* d, const RtrInstance* instanc
     }
 }
 
+/* The host mirrors of a tree the device has (re)written, behind a join of the stream that did it: nodes, records, grid, and the
+ * reduction words (`red`, handed back: [6] the largest |coordinate|, which gives boxPad, [7] the tree's depth). */
+static int read_back_tree(SceneTree& t, uint32_t (&red)[8]) {
+    HIP_TRY(hipMemcpy(t.hostNodes.data(), t.nodes.p, t.hostNodes.size() * sizeof(RtrBvhNode), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(t.hostTris.data(), t.tris.p, t.hostTris.size() * sizeof(RtrBvhTri), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&t.stats.grid, t.grid.p, sizeof(RtrBvhGrid), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(red, t.red.p, sizeof red, hipMemcpyDeviceToHost));
+    float mabs; memcpy(&mabs, &red[6], 4);
+    t.stats.boxPad = (mabs > 1e-6f ? mabs : 1e-6f) * 3.814697265625e-06f;
+    return RTR_OK;
+}
+
 /* The host mirrors after enqueued updates (rtr_scene_update_vertices_async and rtr_scene_update_instances_async leave them stale):
  * joins the scene's stream and reads back what the synchronous refit reads back — nodes, records, grid, boxPad — and the count of
  * reached 4-wide entries k_wide_order left on the device; after an enqueued INSTANCE update also the transforms of hostInstances (from
@@ -535,18 +569,13 @@ static int refresh_mirrors(const rtr_scene* cs) {
     HIP_TRY(hipSetDevice(s->ctx->device));
     HIP_TRY(hipStreamSynchronize(s->ctx->stream));
     uint32_t red[8], reached = 0;
-    HIP_TRY(hipMemcpy(s->hostNodes.data(), s->nodes.p, s->hostNodes.size() * sizeof(RtrBvhNode), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(s->hostTris.data(), s->tris.p, s->hostTris.size() * 48, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(&s->stats.grid, s->grid.p, sizeof(RtrBvhGrid), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(red, s->red.p, sizeof red, hipMemcpyDeviceToHost));
+    { const int rc = read_back_tree(s->tree, red); if (rc != RTR_OK) return rc; }
     HIP_TRY(hipMemcpy(&reached, s->asyncWords.p + 1, sizeof reached, hipMemcpyDeviceToHost));
-    float mabs; memcpy(&mabs, &red[6], 4);
-    s->stats.boxPad = (mabs > 1e-6f ? mabs : 1e-6f) * 3.814697265625e-06f;
-    s->wideReached = reached; s->stats.numWideNodes = reached;
+    s->tree.wideReached = reached; s->tree.stats.numWideNodes = reached;
     if (s->instancesStale) {
         static_assert(sizeof(rtrdev::InstanceRef) == 64 && sizeof(RtrInstance) == 64, "layout");
         std::vector<rtrdev::InstanceRef> refs(s->hostInstances.size());
-        if (!refs.empty()) HIP_TRY(hipMemcpy(refs.data(), s->instRefs.p, refs.size() * sizeof(rtrdev::InstanceRef), hipMemcpyDeviceToHost));
+        if (!refs.empty()) HIP_TRY(hipMemcpy(refs.data(), s->tree.instRefs.p, refs.size() * sizeof(rtrdev::InstanceRef), hipMemcpyDeviceToHost));
         for (RtrInstance& in : s->hostInstances) memcpy(in.transform, refs[in.customIndex].transform, sizeof in.transform);
         if (s->numLights) HIP_TRY(hipMemcpy(s->hostLights.data(), s->lights.p, s->numLights * sizeof(RtrAreaLightInfo), hipMemcpyDeviceToHost));
         s->instancesStale = false;
@@ -555,7 +584,6 @@ static int refresh_mirrors(const rtr_scene* cs) {
     return RTR_OK;
 }
 
-/* (re)builds the 4-wide view of the tree the any-hit kernel walks, on the device, from the quantised BVH2 nodes */
 /* (re)computes the per-light-triangle records light_loops reads; the light transforms live in s->lights on the device */
 static int make_light_tris(rtr_scene* s) {
     if (s->numLights == 0) return RTR_OK;
@@ -565,17 +593,17 @@ static int make_light_tris(rtr_scene* s) {
     return RTR_OK;
 }
 
-static int make_wide_nodes(rtr_scene* s) {
-    const uint32_t n = (uint32_t)s->hostNodes.size();
-    if (!s->nodes4.p) { HIP_TRY(s->nodes4.alloc((size_t)n * 4)); HIP_TRY(s->nodes4tmp.alloc((size_t)n * 4)); HIP_TRY(s->wideRemap.alloc(n)); HIP_TRY(s->wideSums.alloc(rtrdev::bvh_wide_scratch_words())); }
-    hipStream_t st = s->ctx->stream;
-    if (!s->hostWideShape.empty() && !s->wideShape.p) HIP_TRY(s->wideShape.upload(s->hostWideShape.data(), s->hostWideShape.size(), st));
-    hipError_t e = rtrdev::bvh_make_wide(s->nodes.p, n, s->refitReady ? s->parent.p : nullptr, s->grid.p, s->hostWideShape.size() == n ? s->wideShape.p : nullptr, s->nodes4tmp.p, s->wideSums.p, st);
+/* (re)builds the 4-wide view of the tree the any-hit kernel walks, on the device, from the quantised BVH2 nodes */
+static int make_wide_nodes(SceneTree& t, hipStream_t st) {
+    const uint32_t n = (uint32_t)t.hostNodes.size();
+    if (!t.nodes4.p) { HIP_TRY(t.nodes4.alloc((size_t)n * 4)); HIP_TRY(t.nodes4tmp.alloc((size_t)n * 4)); HIP_TRY(t.wideRemap.alloc(n)); HIP_TRY(t.wideSums.alloc(rtrdev::bvh_wide_scratch_words())); }
+    if (!t.hostWideShape.empty() && !t.wideShape.p) HIP_TRY(t.wideShape.upload(t.hostWideShape.data(), t.hostWideShape.size(), st));
+    hipError_t e = rtrdev::bvh_make_wide(t.nodes.p, n, t.refitReady ? t.parent.p : nullptr, t.grid.p, t.hostWideShape.size() == n ? t.wideShape.p : nullptr, t.nodes4tmp.p, t.wideSums.p, st);
     if (e != hipSuccess) return fail(RTR_ERR_HIP, "4-wide node build: %s", hipGetErrorString(e));
     /* breadth-first order of the 4-wide tree (child codes = the 4th 16 bytes of every entry), so its top levels are the first
      * entries: k_shadow_trace4 keeps those in LDS.  Entries the 4-wide tree does not reach keep the ids after them. */
     std::vector<uint32_t> codes((size_t)n * 4), remap(n, 0xffffffffu), order;
-    HIP_TRY(hipMemcpy2DAsync(codes.data(), 16, reinterpret_cast<const char*>(s->nodes4tmp.p) + 48, 64, 16, n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpy2DAsync(codes.data(), 16, reinterpret_cast<const char*>(t.nodes4tmp.p) + 48, 64, 16, n, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     order.reserve(n);
     order.push_back(0); remap[0] = 0;
@@ -586,37 +614,36 @@ static int make_wide_nodes(rtr_scene* s) {
         }
     uint32_t next = (uint32_t)order.size();
     for (uint32_t i = 0; i < n; ++i) if (remap[i] == 0xffffffffu) remap[i] = next++;
-    HIP_TRY(hipMemcpyAsync(s->wideRemap.p, remap.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    e = rtrdev::bvh_permute_wide(s->nodes4tmp.p, n, s->wideRemap.p, s->nodes4.p, st);
+    HIP_TRY(hipMemcpyAsync(t.wideRemap.p, remap.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    e = rtrdev::bvh_permute_wide(t.nodes4tmp.p, n, t.wideRemap.p, t.nodes4.p, st);
     if (e != hipSuccess) return fail(RTR_ERR_HIP, "4-wide node order: %s", hipGetErrorString(e));
     HIP_TRY(hipStreamSynchronize(st));
-    s->wideReached = (uint32_t)order.size();
-    HIP_TRY(hipMemcpy(&s->stats.grid, s->grid.p, sizeof(RtrBvhGrid), hipMemcpyDeviceToHost));     /* the wide centre was set on the device */
-    s->stats.numWideNodes = s->wideReached; s->stats.wideLayoutVersion = RTR_WIDE_LAYOUT_VERSION;
+    t.wideReached = (uint32_t)order.size();
+    HIP_TRY(hipMemcpy(&t.stats.grid, t.grid.p, sizeof(RtrBvhGrid), hipMemcpyDeviceToHost));     /* the wide centre was set on the device */
+    t.stats.numWideNodes = t.wideReached; t.stats.wideLayoutVersion = RTR_WIDE_LAYOUT_VERSION;
     return RTR_OK;
 }
 
-static rtrdev::BvhDeviceArrays device_arrays(rtr_scene* s) {
+static rtrdev::BvhDeviceArrays device_arrays(SceneTree& t) {
     rtrdev::BvhDeviceArrays a{};
-    a.nodes = s->nodes.p; a.nodesF = s->nodesF.p; a.grid = s->grid.p; a.tris = s->tris.p; a.boxMin = s->boxMin.p; a.boxMax = s->boxMax.p; a.parent = s->parent.p;
-    a.counters = s->counters.p; a.depth = s->depth.p; a.slotOfPrim = s->slotOfPrim.p; a.red = s->red.p;
+    a.nodes = t.nodes.p; a.nodesF = t.nodesF.p; a.grid = t.grid.p; a.tris = t.tris.p; a.boxMin = t.boxMin.p; a.boxMax = t.boxMax.p; a.parent = t.parent.p;
+    a.counters = t.counters.p; a.depth = t.depth.p; a.slotOfPrim = t.slotOfPrim.p; a.red = t.red.p;
     return a;
 }
 
-/* Device LBVH build into s->nodes / s->tris (+ refit arrays) from the primitive tables and the DEVICE vertex / index arrays given;
- * fills hostNodes/hostTris and the stats.  The core rtr_scene_create (build_on_device) and rtr_scene_rebuild share: `s` is the scene
- * that receives the tree, `sc` the scratch (the caller's to keep or free). */
-static int build_on_device_core(rtr_scene* s, const std::vector<rtrdev::PrimRef>& prims, const std::vector<rtrdev::InstanceRef>& refs,
+/* Device LBVH build into t.nodes / t.tris (+ refit arrays) from the primitive tables and the DEVICE vertex / index arrays given;
+ * fills hostNodes/hostTris and the stats.  The core rtr_scene_create (build_on_device) and rtr_scene_rebuild share: `t` is the fresh
+ * tree that is built, `bs` the scratch (the caller's to keep or free). */
+static int build_on_device_core(SceneTree& t, hipStream_t st, const std::vector<rtrdev::PrimRef>& prims, const std::vector<rtrdev::InstanceRef>& refs,
                                 const RtrVertex* vertices, const uint32_t* indices, BuildScratch& bs, size_t numPrims) {
-    hipStream_t st = s->ctx->stream;
     const uint32_t n = (uint32_t)numPrims, numNodes = n - 1;
     auto t0 = std::chrono::steady_clock::now();
-    HIP_TRY(s->prims.upload(prims.data(), prims.size(), st));
-    HIP_TRY(s->instRefs.upload(refs.data(), refs.size(), st));
-    HIP_TRY(s->nodes.alloc((size_t)numNodes * 2)); HIP_TRY(s->nodesF.alloc((size_t)numNodes * 4)); HIP_TRY(s->grid.alloc(1));
-    HIP_TRY(s->tris.alloc((size_t)n * 3));
-    HIP_TRY(s->boxMin.alloc(n)); HIP_TRY(s->boxMax.alloc(n)); HIP_TRY(s->parent.alloc(numNodes));
-    HIP_TRY(s->counters.alloc(numNodes)); HIP_TRY(s->depth.alloc(numNodes)); HIP_TRY(s->slotOfPrim.alloc(n)); HIP_TRY(s->red.alloc(8));
+    HIP_TRY(t.prims.upload(prims.data(), prims.size(), st));
+    HIP_TRY(t.instRefs.upload(refs.data(), refs.size(), st));
+    HIP_TRY(t.nodes.alloc((size_t)numNodes * 2)); HIP_TRY(t.nodesF.alloc((size_t)numNodes * 4)); HIP_TRY(t.grid.alloc(1));
+    HIP_TRY(t.tris.alloc((size_t)n * 3));
+    HIP_TRY(t.boxMin.alloc(n)); HIP_TRY(t.boxMax.alloc(n)); HIP_TRY(t.parent.alloc(numNodes));
+    HIP_TRY(t.counters.alloc(numNodes)); HIP_TRY(t.depth.alloc(numNodes)); HIP_TRY(t.slotOfPrim.alloc(n)); HIP_TRY(t.red.alloc(8));
     HIP_TRY(bs.trisCanon.ensure((size_t)n * 3)); HIP_TRY(bs.minCanon.ensure(n)); HIP_TRY(bs.maxCanon.ensure(n));
     HIP_TRY(bs.keysIn.ensure(n)); HIP_TRY(bs.keysOut.ensure(n)); HIP_TRY(bs.range.ensure(numNodes)); HIP_TRY(bs.rawChild.ensure(numNodes));
     rtrdev::BvhScratch sc{};
@@ -624,29 +651,22 @@ static int build_on_device_core(rtr_scene* s, const std::vector<rtrdev::PrimRef>
     HIP_TRY(bs.sortTemp.ensure(sc.sortTempBytes));
     sc.trisCanon = bs.trisCanon.p; sc.minCanon = bs.minCanon.p; sc.maxCanon = bs.maxCanon.p; sc.keysIn = bs.keysIn.p; sc.keysOut = bs.keysOut.p;
     sc.range = bs.range.p; sc.rawChild = bs.rawChild.p; sc.sortTemp = bs.sortTemp.p;
-    HIP_TRY(hipMemsetAsync(s->nodesF.p, 0, (size_t)numNodes * 64, st));
-    rtrdev::BvhInputs in{s->prims.p, s->instRefs.p, vertices, indices};
-    hipError_t e = rtrdev::bvh_build_lbvh(in, n, device_arrays(s), sc, st);
+    HIP_TRY(hipMemsetAsync(t.nodesF.p, 0, (size_t)numNodes * 64, st));
+    rtrdev::BvhInputs in{t.prims.p, t.instRefs.p, vertices, indices};
+    hipError_t e = rtrdev::bvh_build_lbvh(in, n, device_arrays(t), sc, st);
     if (e != hipSuccess) return fail(RTR_ERR_HIP, "device BVH build: %s", hipGetErrorString(e));
     HIP_TRY(hipStreamSynchronize(st));
-    s->hostNodes.resize(numNodes); s->hostTris.resize(n);
+    t.hostNodes.resize(numNodes); t.hostTris.resize(n);
+    memset(&t.stats, 0, sizeof t.stats);
     uint32_t red[8];
-    HIP_TRY(hipMemcpy(s->hostNodes.data(), s->nodes.p, (size_t)numNodes * sizeof(RtrBvhNode), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(s->hostTris.data(), s->tris.p, (size_t)n * 48, hipMemcpyDeviceToHost));
-    RtrBvhGrid grid;
-    HIP_TRY(hipMemcpy(&grid, s->grid.p, sizeof grid, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(red, s->red.p, sizeof red, hipMemcpyDeviceToHost));
+    { const int rc = read_back_tree(t, red); if (rc != RTR_OK) return rc; }
     const float buildMs = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     if (red[7] > 64) return fail(RTR_ERR_BVH_TOO_DEEP, "device-built BVH depth %u exceeds the 64-entry LDS traversal stack", red[7]);
-    memset(&s->stats, 0, sizeof s->stats);
-    s->stats.numTriangles = n; s->stats.numNodes = numNodes; s->stats.maxDepth = red[7]; s->stats.maxLeafSize = 4;
-    s->stats.bvhLayoutVersion = RTR_BVH_LAYOUT_VERSION;
-    s->stats.stackEntries = red[7] <= 16 ? 16 : (red[7] <= 32 ? 32 : 64);
-    s->stats.buildMs = buildMs;
-    s->stats.grid = grid;
-    float mabs; memcpy(&mabs, &red[6], 4);
-    s->stats.boxPad = (mabs > 1e-6f ? mabs : 1e-6f) * 3.814697265625e-06f;
-    s->numPrims = n; s->numNodeSlots = numNodes; s->refitReady = true;
+    t.stats.numTriangles = n; t.stats.numNodes = numNodes; t.stats.maxDepth = red[7]; t.stats.maxLeafSize = 4;
+    t.stats.bvhLayoutVersion = RTR_BVH_LAYOUT_VERSION;
+    t.stats.stackEntries = red[7] <= 16 ? 16 : (red[7] <= 32 ? 32 : 64);
+    t.stats.buildMs = buildMs;
+    t.numPrims = n; t.numNodeSlots = numNodes; t.refitReady = true;
     return RTR_OK;
 }
 
@@ -659,26 +679,12 @@ static int build_on_device(rtr_scene* s, const rtr_scene_desc* d, size_t numPrim
             if (!(d->vertices[v].position[k] > -3.0e38f && d->vertices[v].position[k] < 3.0e38f))
                 return fail(RTR_ERR_INVALID_ARGUMENT, "BVH build: non-finite vertex position in vertex %u", v);
     BuildScratch scratch;
-    return build_on_device_core(s, prims, refs, s->vertices.p, s->indices.p, scratch, numPrims);
+    return build_on_device_core(s->tree, s->ctx->stream, prims, refs, s->vertices.p, s->indices.p, scratch, numPrims);
 }
 
-static void instance_tables(uint32_t numInstances, const RtrInstance* instances, std::vector<float>& xforms, std::vector<float>& nmats) {
-    xforms.assign(12 * (size_t)numInstances, 0.f);
-    nmats.assign(12 * (size_t)numInstances, 0.f);
-    for (uint32_t i = 0; i < numInstances; ++i) {
-        memcpy(&xforms[12 * (size_t)instances[i].customIndex], instances[i].transform, 12 * sizeof(float));
-        rtr_normal_matrix(instances[i].transform, &nmats[12 * (size_t)instances[i].customIndex]);
-        set_mirrored_word(instances[i].transform, &nmats[12 * (size_t)instances[i].customIndex]);
-    }
-}
-
-static int scene_create_impl(rtr_ctx* ctx, const rtr_scene_desc* d, const rtr_scene* like, rtr_scene** out);
-
-int rtr_scene_create(rtr_ctx* ctx, const rtr_scene_desc* d, rtr_scene** out) { return scene_create_impl(ctx, d, nullptr, out); }
-
-int rtr_scene_create_like(rtr_ctx* ctx, const rtr_scene_desc* d, const rtr_scene* built, rtr_scene** out) {
-    if (!built) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_scene_create_like: null scene to copy the tree from");
-    return scene_create_impl(ctx, d, built, out);
+/* DeviceScene's view of the tree: what the kernels walk */
+static void point_at_tree(DeviceScene& dv, const SceneTree& t) {
+    dv.nodes = t.nodes.p; dv.nodes4 = t.nodes4.p; dv.numNodes4 = (uint32_t)t.hostNodes.size(); dv.grid = t.grid.p; dv.tris = t.tris.p;
 }
 
 static int scene_create_impl(rtr_ctx* ctx, const rtr_scene_desc* d, const rtr_scene* like, rtr_scene** out) {
@@ -701,14 +707,15 @@ static int scene_create_impl(rtr_ctx* ctx, const rtr_scene_desc* d, const rtr_sc
         rc = refresh_mirrors(like);
         if (rc != RTR_OK) return rc;
         /* the tree of `like`, as its host copy holds it (nodes and records are kept in step with the device by every update) */
-        if (like->stats.numTriangles != totalPrims || like->hostNodes.empty() || like->hostTris.empty())
-            return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_scene_create_like: the built scene has %u triangles, this description %zu", like->stats.numTriangles, totalPrims);
-        bvh.nodes = like->hostNodes; bvh.tris = like->hostTris; bvh.grid = like->stats.grid; bvh.wideShape = like->hostWideShape;
+        const SceneTree& lt = like->tree;
+        if (lt.stats.numTriangles != totalPrims || lt.hostNodes.empty() || lt.hostTris.empty())
+            return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_scene_create_like: the built scene has %u triangles, this description %zu", lt.stats.numTriangles, totalPrims);
+        bvh.nodes = lt.hostNodes; bvh.tris = lt.hostTris; bvh.grid = lt.stats.grid; bvh.wideShape = lt.hostWideShape;
         if (!like->hostMasks.empty()) for (RtrBvhTri& t : bvh.tris) t.flags &= ~RTR_TRI_MASK_BITS;      /* a new scene's instance masks are 0xff, whatever `like` has set */
-        bvh.maxDepth = like->stats.maxDepth; bvh.maxLeafSize = like->stats.maxLeafSize; bvh.sahCost = like->stats.sahCost; bvh.boxPad = like->stats.boxPad;
-        for (int k = 0; k < 3; ++k) { bvh.boundsMin[k] = like->stats.boundsMin[k]; bvh.boundsMax[k] = like->stats.boundsMax[k]; }
+        bvh.maxDepth = lt.stats.maxDepth; bvh.maxLeafSize = lt.stats.maxLeafSize; bvh.sahCost = lt.stats.sahCost; bvh.boxPad = lt.stats.boxPad;
+        for (int k = 0; k < 3; ++k) { bvh.boundsMin[k] = lt.stats.boundsMin[k]; bvh.boundsMax[k] = lt.stats.boundsMax[k]; }
         bvh.buildMs = 0.f;                                   /* nothing was built here */
-        stackEntries = like->stats.stackEntries; numTris = like->stats.numTriangles;
+        stackEntries = lt.stats.stackEntries; numTris = lt.stats.numTriangles;
         instance_tables(d->numInstances, d->instances, xforms, nmats);
     } else if (!deviceBuild) {
         rc = flatten_and_build(d, bvh, xforms, nmats, &stackEntries, &numTris);
@@ -719,14 +726,15 @@ static int scene_create_impl(rtr_ctx* ctx, const rtr_scene_desc* d, const rtr_sc
 
     rtr_scene* s = new rtr_scene();
     s->ctx = ctx; ++ctx->children;
+    SceneTree& tree = s->tree;
     hipStream_t st = ctx->stream;
     hipError_t e = hipSuccess;
     auto chk = [&](hipError_t r) { if (e == hipSuccess) e = r; };
     static_assert(sizeof(RtrBvhNode) == 2 * sizeof(uint4) && sizeof(RtrBvhTri) == 3 * sizeof(float4), "layout");
     if (!deviceBuild) {
-        chk(s->nodes.upload(reinterpret_cast<const uint4*>(bvh.nodes.data()), bvh.nodes.size() * 2, st));
-        chk(s->grid.upload(&bvh.grid, 1, st));
-        chk(s->tris.upload(reinterpret_cast<const float4*>(bvh.tris.data()), bvh.tris.size() * 3, st));
+        chk(tree.nodes.upload(reinterpret_cast<const uint4*>(bvh.nodes.data()), bvh.nodes.size() * 2, st));
+        chk(tree.grid.upload(&bvh.grid, 1, st));
+        chk(tree.tris.upload(reinterpret_cast<const float4*>(bvh.tris.data()), bvh.tris.size() * 3, st));
     }
     chk(s->vertices.upload(d->vertices, d->numVertices, st));
     chk(s->indices.upload(d->indices, d->numIndices, st));
@@ -782,18 +790,18 @@ static int scene_create_impl(rtr_ctx* ctx, const rtr_scene_desc* d, const rtr_sc
         rc = build_on_device(s, d, totalPrims);
         if (rc != RTR_OK) { delete s; ctx_release_child(ctx); return rc; }
     } else {
-        fill_stats(s->stats, bvh, stackEntries, numTris);
-        s->hostNodes.swap(bvh.nodes);
-        s->hostTris.swap(bvh.tris);
-        s->hostWideShape.swap(bvh.wideShape);
-        s->numPrims = (uint32_t)s->hostTris.size(); s->numNodeSlots = (uint32_t)s->hostNodes.size();
+        fill_stats(tree.stats, bvh, stackEntries, numTris);
+        tree.hostNodes.swap(bvh.nodes);
+        tree.hostTris.swap(bvh.tris);
+        tree.hostWideShape.swap(bvh.wideShape);
+        tree.numPrims = (uint32_t)tree.hostTris.size(); tree.numNodeSlots = (uint32_t)tree.hostNodes.size();
     }
 
-    rc = make_wide_nodes(s);
+    rc = make_wide_nodes(tree, st);
     if (rc == RTR_OK) rc = make_light_tris(s);
     if (rc != RTR_OK) { delete s; ctx_release_child(ctx); return rc; }
     DeviceScene& dv = s->dev;
-    dv.nodes = s->nodes.p; dv.nodes4 = s->nodes4.p; dv.numNodes4 = (uint32_t)s->hostNodes.size(); dv.grid = s->grid.p; dv.tris = s->tris.p;
+    point_at_tree(dv, tree);
     dv.vertices = s->vertices.p; dv.indices = s->indices.p;
     dv.objects = s->objects.p; dv.lights = s->lights.p;
     dv.lightTris = s->lightTris.p; dv.lightTriFirst = s->lightTriFirst.p;
@@ -807,6 +815,13 @@ static int scene_create_impl(rtr_ctx* ctx, const rtr_scene_desc* d, const rtr_sc
     dv.hdri = hdri;
     *out = s;
     return RTR_OK;
+}
+
+int rtr_scene_create(rtr_ctx* ctx, const rtr_scene_desc* d, rtr_scene** out) { return scene_create_impl(ctx, d, nullptr, out); }
+
+int rtr_scene_create_like(rtr_ctx* ctx, const rtr_scene_desc* d, const rtr_scene* built, rtr_scene** out) {
+    if (!built) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_scene_create_like: null scene to copy the tree from");
+    return scene_create_impl(ctx, d, built, out);
 }
 
 /* parent links of a node array, as the refit keeps them: (parentIndex << 1) | slot, -1 for the root, -2 for a slot the root does not
@@ -830,31 +845,32 @@ static size_t host_parent_array(const std::vector<RtrBvhNode>& nodes, std::vecto
 /* A host-built tree gets its refit arrays on the first update: parent links from the node array, the
  * canonical-primitive -> leaf-slot map from the ids stored in the triangle records. */
 static int ensure_refit_ready(rtr_scene* s) {
-    if (s->refitReady) return RTR_OK;
+    SceneTree& t = s->tree;
+    if (t.refitReady) return RTR_OK;
     if (s->hostInstances.empty()) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_scene_update_instances: the scene has no instances");
     hipStream_t st = s->ctx->stream;
-    const uint32_t numNodes = (uint32_t)s->hostNodes.size(), n = (uint32_t)s->hostTris.size();
+    const uint32_t numNodes = (uint32_t)t.hostNodes.size(), n = (uint32_t)t.hostTris.size();
     std::vector<int32_t> parent;
-    host_parent_array(s->hostNodes, parent);
+    host_parent_array(t.hostNodes, parent);
     /* canonical order = instances in creation order, primitives in mesh order */
     std::vector<uint32_t> base(s->hostInstances.size(), 0);       /* by customIndex */
     uint32_t acc = 0;
     for (const RtrInstance& in : s->hostInstances) { base[in.customIndex] = acc; acc += s->hostMeshes[in.meshIndex].indexCount / 3u; }
     if (acc != n) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_scene_update_instances: scene has no geometry to refit");
     std::vector<uint32_t> slotOfPrim(n, 0);
-    for (uint32_t slot = 0; slot < n; ++slot) slotOfPrim[base[s->hostTris[slot].customIndex] + s->hostTris[slot].primitiveId] = slot;
+    for (uint32_t slot = 0; slot < n; ++slot) slotOfPrim[base[t.hostTris[slot].customIndex] + t.hostTris[slot].primitiveId] = slot;
     /* the fit works on fp32 planes: child codes from the host tree, boxes recomputed by the refit */
     std::vector<rtr::BvhNodeF> nf(numNodes);
     for (uint32_t i = 0; i < numNodes; ++i) {
         memset(&nf[i], 0, sizeof nf[i]);
-        nf[i].child[0] = s->hostNodes[i].child[0]; nf[i].child[1] = s->hostNodes[i].child[1];
+        nf[i].child[0] = t.hostNodes[i].child[0]; nf[i].child[1] = t.hostNodes[i].child[1];
     }
-    HIP_TRY(s->nodesF.upload(reinterpret_cast<const float4*>(nf.data()), (size_t)numNodes * 4, st));
-    HIP_TRY(s->parent.upload(parent.data(), parent.size(), st));
-    HIP_TRY(s->slotOfPrim.upload(slotOfPrim.data(), slotOfPrim.size(), st));
-    HIP_TRY(s->boxMin.alloc(n)); HIP_TRY(s->boxMax.alloc(n));
-    HIP_TRY(s->counters.alloc(numNodes)); HIP_TRY(s->depth.alloc(numNodes)); HIP_TRY(s->red.alloc(8));
-    s->numPrims = n; s->numNodeSlots = numNodes; s->refitReady = true;
+    HIP_TRY(t.nodesF.upload(reinterpret_cast<const float4*>(nf.data()), (size_t)numNodes * 4, st));
+    HIP_TRY(t.parent.upload(parent.data(), parent.size(), st));
+    HIP_TRY(t.slotOfPrim.upload(slotOfPrim.data(), slotOfPrim.size(), st));
+    HIP_TRY(t.boxMin.alloc(n)); HIP_TRY(t.boxMax.alloc(n));
+    HIP_TRY(t.counters.alloc(numNodes)); HIP_TRY(t.depth.alloc(numNodes)); HIP_TRY(t.red.alloc(8));
+    t.numPrims = n; t.numNodeSlots = numNodes; t.refitReady = true;
     return RTR_OK;
 }
 
@@ -865,7 +881,34 @@ static std::vector<uint32_t> instance_mask_bits(const rtr_scene* s, const uint8_
     return bits;
 }
 
-static int upload_prim_tables(rtr_scene* s, const RtrInstance* inst);
+/* the description a scene's host mirrors make (no vertices, no indices: the device holds those) */
+static rtr_scene_desc host_view(const rtr_scene* s) {
+    rtr_scene_desc view{};
+    view.meshes = s->hostMeshes.data(); view.numMeshes = (uint32_t)s->hostMeshes.size();
+    view.instances = s->hostInstances.data(); view.numInstances = (uint32_t)s->hostInstances.size();
+    view.objects = s->hostObjects.data(); view.numObjects = (uint32_t)s->hostObjects.size();
+    view.lights = s->hostLights.data(); view.numLights = s->numLights;
+    return view;
+}
+
+/* the tables a refit or a device build flattens from (PrimRef / InstanceRef) for the transforms given, with the instance masks in the
+ * flags: both write the records from this table */
+static void scene_prim_tables(const rtr_scene* s, const RtrInstance* inst, std::vector<rtrdev::PrimRef>& prims, std::vector<rtrdev::InstanceRef>& refs) {
+    const rtr_scene_desc view = host_view(s);
+    make_prim_tables(&view, inst, prims, refs);
+    if (s->hostMasks.empty()) return;
+    const std::vector<uint32_t> bits = instance_mask_bits(s, s->hostMasks.data());
+    for (rtrdev::PrimRef& pr : prims) pr.flags |= bits[pr.customIndex];
+}
+
+/* those tables on the device, for the scene's tree */
+static int upload_prim_tables(rtr_scene* s, const RtrInstance* inst) {
+    std::vector<rtrdev::PrimRef> prims; std::vector<rtrdev::InstanceRef> refs;
+    scene_prim_tables(s, inst, prims, refs);
+    HIP_TRY(s->tree.prims.upload(prims.data(), prims.size(), s->ctx->stream));
+    HIP_TRY(s->tree.instRefs.upload(refs.data(), refs.size(), s->ctx->stream));
+    return RTR_OK;
+}
 
 int rtr_scene_set_instance_masks(rtr_scene* s, const uint8_t* masks, uint32_t numInstances) {
     if (!s || (!masks && numInstances)) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_scene_set_instance_masks: null argument");
@@ -878,17 +921,17 @@ int rtr_scene_set_instance_masks(rtr_scene* s, const uint8_t* masks, uint32_t nu
      * they are rewritten (contract in rtr.h, as rtr_scene_update_instances) */
     HIP_TRY(hipDeviceSynchronize());
     hipStream_t st = s->ctx->stream;
-    const uint32_t numTris = (uint32_t)(s->tris.n / 3);
+    const uint32_t numTris = (uint32_t)(s->tree.tris.n / 3);
     HIP_TRY(s->maskBits.upload(bits.data(), bits.size(), st));
-    const hipError_t e = rtrdev::launch_set_instance_masks(s->tris.p, numTris, s->maskBits.p, numInstances, st);
+    const hipError_t e = rtrdev::launch_set_instance_masks(s->tree.tris.p, numTris, s->maskBits.p, numInstances, st);
     if (e != hipSuccess) return fail(RTR_ERR_HIP, "rtr_scene_set_instance_masks: kernel launch: %s", hipGetErrorString(e));
     HIP_TRY(hipStreamSynchronize(st));
     /* the host mirror (rtr_scene_export_bvh, rtr_scene_create_like) in step: the same rule as the kernel's */
-    for (RtrBvhTri& t : s->hostTris)
+    for (RtrBvhTri& t : s->tree.hostTris)
         if (t.customIndex < numInstances) t.flags = (t.flags & ~RTR_TRI_MASK_BITS) | bits[t.customIndex];
     s->hostMasks.assign(masks, masks + numInstances);
     /* an enqueued refit writes its records from the device tables: they carry the new masks from here on */
-    if (s->asyncReady) return upload_prim_tables(s, s->hostInstances.data());
+    if (s->tree.asyncReady) return upload_prim_tables(s, s->hostInstances.data());
     return RTR_OK;
 }
 
@@ -923,25 +966,6 @@ static int check_refit_args(const rtr_scene* s, const RtrInstance* instances, ui
     return RTR_OK;
 }
 
-/* the device tables a refit flattens from (PrimRef / InstanceRef) for the transforms given, with the instance masks in the flags */
-static int upload_prim_tables(rtr_scene* s, const RtrInstance* inst) {
-    hipStream_t st = s->ctx->stream;
-    const uint32_t numInstances = (uint32_t)s->hostInstances.size();
-    rtr_scene_desc view{};
-    view.meshes = s->hostMeshes.data(); view.numMeshes = (uint32_t)s->hostMeshes.size();
-    view.numInstances = numInstances; view.objects = s->hostObjects.data(); view.numObjects = (uint32_t)s->hostObjects.size();
-    view.numLights = s->numLights;
-    std::vector<rtrdev::PrimRef> prims; std::vector<rtrdev::InstanceRef> refs;
-    make_prim_tables(&view, inst, prims, refs);
-    if (!s->hostMasks.empty()) {      /* the refit rewrites the records from this table: the instance masks go with it */
-        const std::vector<uint32_t> bits = instance_mask_bits(s, s->hostMasks.data());
-        for (rtrdev::PrimRef& pr : prims) pr.flags |= bits[pr.customIndex];
-    }
-    HIP_TRY(s->prims.upload(prims.data(), prims.size(), st));
-    HIP_TRY(s->instRefs.upload(refs.data(), refs.size(), st));
-    return RTR_OK;
-}
-
 /* The refit both calls end in, on a scene that is refit-ready and a device that has been joined: world-space records from the device
  * vertex array, boxes, grid, 4-wide view, host mirrors, boxPad.  instances == NULL keeps the current transforms (and with them the
  * transform, normal-matrix and mirrored tables); lights == NULL keeps the light infos.  lightTris: remake the light-triangle table even
@@ -957,20 +981,16 @@ static int refit_scene(rtr_scene* s, const RtrInstance* instances, const RtrArea
         HIP_TRY(hipMemcpyAsync(s->nmats.p, nmats.data(), nmats.size() * sizeof(float), hipMemcpyHostToDevice, st));
     }
     if (lights && numLights) HIP_TRY(hipMemcpyAsync(s->lights.p, lights, numLights * sizeof(RtrAreaLightInfo), hipMemcpyHostToDevice, st));
-    rtrdev::BvhInputs in{s->prims.p, s->instRefs.p, s->vertices.p, s->indices.p};
-    hipError_t e = rtrdev::bvh_refit(in, s->numPrims, s->numNodeSlots, device_arrays(s), st);
+    SceneTree& t = s->tree;
+    rtrdev::BvhInputs in{t.prims.p, t.instRefs.p, s->vertices.p, s->indices.p};
+    hipError_t e = rtrdev::bvh_refit(in, t.numPrims, t.numNodeSlots, device_arrays(t), st);
     if (e != hipSuccess) return fail(RTR_ERR_HIP, "device BVH refit: %s", hipGetErrorString(e));
     HIP_TRY(hipStreamSynchronize(st));
     /* keep the host mirror (rtr_scene_export_bvh) and the stats in step */
     uint32_t red[8];
-    HIP_TRY(hipMemcpy(s->hostNodes.data(), s->nodes.p, s->hostNodes.size() * sizeof(RtrBvhNode), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(s->hostTris.data(), s->tris.p, s->hostTris.size() * 48, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(&s->stats.grid, s->grid.p, sizeof(RtrBvhGrid), hipMemcpyDeviceToHost));
-    { const int rc4 = make_wide_nodes(s); if (rc4 != RTR_OK) return rc4; }
+    { const int rcb = read_back_tree(t, red); if (rcb != RTR_OK) return rcb; }
+    { const int rc4 = make_wide_nodes(t, st); if (rc4 != RTR_OK) return rc4; }
     if (lightTris || (lights && numLights)) { const int rcl = make_light_tris(s); if (rcl != RTR_OK) return rcl; }
-    HIP_TRY(hipMemcpy(red, s->red.p, sizeof red, hipMemcpyDeviceToHost));
-    float mabs; memcpy(&mabs, &red[6], 4);
-    s->stats.boxPad = (mabs > 1e-6f ? mabs : 1e-6f) * 3.814697265625e-06f;
     if (instances) s->hostInstances.assign(instances, instances + numInstances);
     if (lights && numLights) s->hostLights.assign(lights, lights + numLights);
     return RTR_OK;
@@ -983,7 +1003,7 @@ int rtr_scene_update_instances(rtr_scene* s, const RtrInstance* instances, uint3
     if (rc != RTR_OK) return rc;
     rc = refresh_mirrors(s);
     if (rc != RTR_OK) return rc;
-    if (s->hostTris.empty() || s->hostTris[0].customIndex == 0xffffffffu) return RTR_OK;     /* empty scene: nothing to refit */
+    if (scene_is_empty(s)) return RTR_OK;     /* nothing to refit */
     HIP_TRY(hipSetDevice(s->ctx->device));
     rc = ensure_refit_ready(s);
     if (rc != RTR_OK) return rc;
@@ -1037,7 +1057,7 @@ int rtr_scene_update_vertices(rtr_scene* s, const rtr_vertex_range* ranges, uint
     if (rc != RTR_OK) return rc;
     rc = refresh_mirrors(s);
     if (rc != RTR_OK) return rc;
-    if (s->hostTris.empty() || s->hostTris[0].customIndex == 0xffffffffu) return RTR_OK;     /* empty scene: nothing to refit */
+    if (scene_is_empty(s)) return RTR_OK;     /* nothing to refit */
 
     /* the device tables of the launches: the ranges in chunks of kVertexRangesPerLaunch, each with its own prefix counts */
     const uint32_t kChunk = rtrdev::kVertexRangesPerLaunch;
@@ -1140,20 +1160,18 @@ int rtr_scene_export_vertices(const rtr_scene* s, RtrVertex* out, size_t bytes) 
 }
 
 /* ---- the enqueued vertex update (contract in rtr.h) ---- */
-static bool scene_is_empty(const rtr_scene* s) { return s->hostTris.empty() || s->hostTris[0].customIndex == 0xffffffffu; }
-
 int rtr_scene_prepare_async_updates(rtr_scene* s) {
     if (!s) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_scene_prepare_async_updates: null scene");
     HIP_TRY(hipSetDevice(s->ctx->device));
     int rc = refresh_mirrors(s);
     if (rc != RTR_OK) return rc;
-    if (s->asyncReady) return RTR_OK;
+    if (s->tree.asyncReady) return RTR_OK;
     if (!scene_is_empty(s)) {
         rc = ensure_refit_ready(s);
         if (rc != RTR_OK) return rc;
         rc = upload_prim_tables(s, s->hostInstances.data());
         if (rc != RTR_OK) return rc;
-        HIP_TRY(s->orderScratch.ensure(2 * s->hostNodes.size()));
+        HIP_TRY(s->tree.orderScratch.ensure(2 * s->tree.hostNodes.size()));
         if (!s->instCustom.p) {      /* kept through a rebuild: the instances are the scene's, not the tree's */
             std::vector<uint32_t> custom(s->hostInstances.size());
             for (size_t i = 0; i < custom.size(); ++i) custom[i] = s->hostInstances[i].customIndex;
@@ -1164,7 +1182,7 @@ int rtr_scene_prepare_async_updates(rtr_scene* s) {
         const uint32_t none = 0xffffffffu, init[8] = {none, 0u, 0u, 0u, 0u, none, none, 0u};
         HIP_TRY(s->asyncWords.upload(init, 8, s->ctx->stream));
     }
-    s->asyncReady = true;
+    s->tree.asyncReady = true;
     return RTR_OK;
 }
 
@@ -1174,15 +1192,16 @@ int rtr_scene_prepare_async_updates(rtr_scene* s) {
 static int enqueue_refit_tail(rtr_scene* s, uint32_t serial, const char* who) {
     hipStream_t st = s->ctx->stream;
     uint32_t* firstBad = s->asyncWords.p;
-    const uint32_t n = (uint32_t)s->hostNodes.size();
-    rtrdev::BvhInputs in{s->prims.p, s->instRefs.p, s->vertices.p, s->indices.p};
-    hipError_t e = rtrdev::bvh_refit_enqueued(in, s->numPrims, s->numNodeSlots, device_arrays(s), st);
+    SceneTree& t = s->tree;
+    const uint32_t n = (uint32_t)t.hostNodes.size();
+    rtrdev::BvhInputs in{t.prims.p, t.instRefs.p, s->vertices.p, s->indices.p};
+    hipError_t e = rtrdev::bvh_refit_enqueued(in, t.numPrims, t.numNodeSlots, device_arrays(t), st);
     if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: device BVH refit: %s", who, hipGetErrorString(e));
     s->mirrorsStale = true;
-    e = rtrdev::bvh_make_wide(s->nodes.p, n, s->parent.p, s->grid.p, s->hostWideShape.size() == n ? s->wideShape.p : nullptr, s->nodes4tmp.p, s->wideSums.p, st);
+    e = rtrdev::bvh_make_wide(t.nodes.p, n, t.parent.p, t.grid.p, t.hostWideShape.size() == n ? t.wideShape.p : nullptr, t.nodes4tmp.p, t.wideSums.p, st);
     if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: 4-wide node build: %s", who, hipGetErrorString(e));
-    e = rtrdev::bvh_wide_order(s->nodes4tmp.p, n, s->wideRemap.p, s->orderScratch.p, s->asyncWords.p + 1, st);
-    if (e == hipSuccess) e = rtrdev::bvh_permute_wide(s->nodes4tmp.p, n, s->wideRemap.p, s->nodes4.p, st);
+    e = rtrdev::bvh_wide_order(t.nodes4tmp.p, n, t.wideRemap.p, t.orderScratch.p, s->asyncWords.p + 1, st);
+    if (e == hipSuccess) e = rtrdev::bvh_permute_wide(t.nodes4tmp.p, n, t.wideRemap.p, t.nodes4.p, st);
     if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: 4-wide node order: %s", who, hipGetErrorString(e));
     if (s->numLights) {
         e = rtrdev::launch_light_tris(s->lights.p, s->vertices.p, s->indices.p, s->lightTriFirst.p, s->numLights, s->lightTris.p, st);
@@ -1200,7 +1219,7 @@ int rtr_scene_update_vertices_async(rtr_scene* s, const rtr_vertex_range* ranges
     if (!ranges || numRanges == 0) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: null ranges (or numRanges == 0): nothing to update", who);
     int rc = check_vertex_ranges(s, ranges, numRanges, positionStride, normalStride, true, who);
     if (rc != RTR_OK) return rc;
-    if (!s->asyncReady) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: the scene has not been prepared: call rtr_scene_prepare_async_updates once first", who);
+    if (!s->tree.asyncReady) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: the scene has not been prepared: call rtr_scene_prepare_async_updates once first", who);
     const uint32_t serial = (uint32_t)(s->asyncEnqueued + 1);
     if (scene_is_empty(s)) { ++s->asyncEnqueued; return RTR_OK; }      /* nothing to refit, as the synchronous call */
     HIP_TRY(hipSetDevice(s->ctx->device));
@@ -1243,7 +1262,7 @@ int rtr_scene_update_instances_async(rtr_scene* s, const void* transforms, uint3
         return fail(RTR_ERR_INVALID_ARGUMENT, "%s: instances %u .. %llu leave the scene's %zu instances", who, firstInstance,
                     (unsigned long long)firstInstance + numInstances, s->hostInstances.size());
     if (lights && numLights != s->numLights) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: %u lights given, scene has %u", who, numLights, s->numLights);
-    if (!s->asyncReady) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: the scene has not been prepared: call rtr_scene_prepare_async_updates once first", who);
+    if (!s->tree.asyncReady) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: the scene has not been prepared: call rtr_scene_prepare_async_updates once first", who);
     const uint32_t serial = (uint32_t)(s->asyncEnqueued + 1);
     if (scene_is_empty(s)) { ++s->asyncEnqueued; return RTR_OK; }      /* nothing to refit, as the synchronous call */
     HIP_TRY(hipSetDevice(s->ctx->device));
@@ -1254,7 +1273,7 @@ int rtr_scene_update_instances_async(rtr_scene* s, const void* transforms, uint3
     hipError_t e = rtrdev::launch_check_instances(transforms, strideWords, firstInstance, numInstances, lights, numLights, sceneInstances, s->lights.p, firstBad, st);
     if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: checking kernel: %s", who, hipGetErrorString(e));
     e = rtrdev::launch_write_instances(transforms, strideWords, firstInstance, numInstances, lights, numLights, s->instCustom.p, rtrdev::kMirroredWord,
-                                       s->xforms.p, s->nmats.p, s->instRefs.p, s->lights.p, firstBad, st);
+                                       s->xforms.p, s->nmats.p, s->tree.instRefs.p, s->lights.p, firstBad, st);
     if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: writing kernel: %s", who, hipGetErrorString(e));
     s->instancesStale = true;      /* with mirrorsStale, which the tail sets: refresh_mirrors reads the transforms and lights back */
     s->mirrorsStale = true;
@@ -1348,19 +1367,20 @@ int rtr_scene_tree_cost(const rtr_scene* s, rtr_tree_cost* out) {
     HIP_TRY(hipSetDevice(s->ctx->device));
     { const int rcm = refresh_mirrors(s); if (rcm != RTR_OK) return rcm; }      /* the grid the sums are scaled with */
     hipStream_t st = s->ctx->stream;
-    const uint32_t numNodes = (uint32_t)s->hostNodes.size();
+    const SceneTree& t = s->tree;
+    const uint32_t numNodes = (uint32_t)t.hostNodes.size();
     /* which slots are part of the tree: the refit's parent array where the scene has one (a device build leaves slots unused); a host
      * tree without one is looked at once, and gets a parent array of its own only if the root does not reach every slot */
-    const int32_t* parent = s->refitReady ? s->parent.p : nullptr;
-    if (!s->refitReady && s->costParentState == 0) {
+    const int32_t* parent = t.refitReady ? t.parent.p : nullptr;
+    if (!t.refitReady && t.costParentState == 0) {
         std::vector<int32_t> par;
-        if (host_parent_array(s->hostNodes, par) == s->hostNodes.size()) s->costParentState = 1;
-        else { HIP_TRY(s->costParent.upload(par.data(), par.size(), st)); s->costParentState = 2; }
+        if (host_parent_array(t.hostNodes, par) == t.hostNodes.size()) t.costParentState = 1;
+        else { HIP_TRY(t.costParent.upload(par.data(), par.size(), st)); t.costParentState = 2; }
     }
-    if (!s->refitReady && s->costParentState == 2) parent = s->costParent.p;
+    if (!t.refitReady && t.costParentState == 2) parent = t.costParent.p;
     const size_t words = rtrdev::bvh_tree_cost_words();
     HIP_TRY(s->costWords.ensure(words));
-    const hipError_t e = rtrdev::bvh_tree_cost(s->nodes.p, numNodes, parent, s->costWords.p, st);
+    const hipError_t e = rtrdev::bvh_tree_cost(t.nodes.p, numNodes, parent, s->costWords.p, st);
     if (e != hipSuccess) return fail(RTR_ERR_HIP, "rtr_scene_tree_cost: kernel launch: %s", hipGetErrorString(e));
     uint64_t w[11];
     static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "layout");
@@ -1370,20 +1390,9 @@ int rtr_scene_tree_cost(const rtr_scene* s, rtr_tree_cost* out) {
     rtr_tree_cost c{};
     for (int k = 0; k < 3; ++k) { c.innerArea[k] = w[k]; c.leafArea[k] = w[3 + k]; c.rootArea[k] = w[6 + k]; }
     c.numInner = w[9]; c.numLeafRefs = w[10];
-    finish_tree_cost(&c, s->stats.grid);
+    finish_tree_cost(&c, t.stats.grid);
     *out = c;
     return RTR_OK;
-}
-
-/* the new tree moves from the scene it was built in (`t`) into `s`; `t` takes the old one away with it */
-static void swap_tree(rtr_scene* s, rtr_scene* t) {
-    s->nodes.swap(t->nodes); s->nodesF.swap(t->nodesF); s->grid.swap(t->grid); s->wideSums.swap(t->wideSums); s->nodes4tmp.swap(t->nodes4tmp);
-    s->wideRemap.swap(t->wideRemap); s->wideShape.swap(t->wideShape); s->hostWideShape.swap(t->hostWideShape); std::swap(s->wideReached, t->wideReached);
-    s->nodes4.swap(t->nodes4); s->tris.swap(t->tris); s->hostNodes.swap(t->hostNodes); s->hostTris.swap(t->hostTris);
-    s->prims.swap(t->prims); s->instRefs.swap(t->instRefs); s->boxMin.swap(t->boxMin); s->boxMax.swap(t->boxMax); s->parent.swap(t->parent);
-    s->counters.swap(t->counters); s->depth.swap(t->depth); s->slotOfPrim.swap(t->slotOfPrim); s->red.swap(t->red);
-    std::swap(s->numPrims, t->numPrims); std::swap(s->numNodeSlots, t->numNodeSlots); std::swap(s->refitReady, t->refitReady);
-    std::swap(s->stats, t->stats);
 }
 
 int rtr_scene_rebuild(rtr_scene* s, uint32_t buildFlags) {
@@ -1391,59 +1400,49 @@ int rtr_scene_rebuild(rtr_scene* s, uint32_t buildFlags) {
     if (!s) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: null scene", who);
     if (buildFlags > RTR_BUILD_DEVICE_LBVH) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: unknown buildFlags %u", who, buildFlags);
     { const int rcm = refresh_mirrors(s); if (rcm != RTR_OK) return rcm; }
-    if (s->hostTris.empty() || s->hostTris[0].customIndex == 0xffffffffu) return RTR_OK;     /* empty scene: nothing to build */
+    if (scene_is_empty(s)) return RTR_OK;     /* nothing to build */
     HIP_TRY(hipSetDevice(s->ctx->device));
     /* frames and queries of OTHER contexts (other streams) may be walking this tree: everything enqueued on the device so far is joined
      * before it is replaced (contract in rtr.h, as the update calls) */
     HIP_TRY(hipDeviceSynchronize());
     hipStream_t st = s->ctx->stream;
-    const size_t totalPrims = s->hostTris.size();
+    const size_t totalPrims = s->tree.hostTris.size();
     const bool deviceBuild = buildFlags == RTR_BUILD_DEVICE_LBVH && totalPrims >= 16;     /* tiny scenes: the host builder, as at creation */
-    rtr_scene_desc view{};
-    view.meshes = s->hostMeshes.data(); view.numMeshes = (uint32_t)s->hostMeshes.size();
-    view.instances = s->hostInstances.data(); view.numInstances = (uint32_t)s->hostInstances.size();
-    view.objects = s->hostObjects.data(); view.numObjects = (uint32_t)s->hostObjects.size();
-    view.lights = s->hostLights.data(); view.numLights = s->numLights;
-    std::vector<uint32_t> maskBits;       /* the new records carry the instance masks, as a refit's do */
-    if (!s->hostMasks.empty()) maskBits = instance_mask_bits(s, s->hostMasks.data());
-    /* the new tree is built in a scene of its own that shares nothing with `s` but the context: whatever fails, `s` is as it was */
-    struct Temp { rtr_scene* p; ~Temp() { delete p; } } tmp{new rtr_scene()};
-    rtr_scene* t = tmp.p;
-    t->ctx = s->ctx;
+    /* the new tree is built apart from the scene, from its vertices and host mirrors: whatever fails, `s` is as it was */
+    SceneTree fresh;
     int rc = RTR_OK;
     if (deviceBuild) {
         std::vector<rtrdev::PrimRef> prims; std::vector<rtrdev::InstanceRef> refs;
-        make_prim_tables(&view, s->hostInstances.data(), prims, refs);
-        if (!maskBits.empty()) for (rtrdev::PrimRef& pr : prims) pr.flags |= maskBits[pr.customIndex];
-        rc = build_on_device_core(t, prims, refs, s->vertices.p, s->indices.p, s->buildScratch, totalPrims);
+        scene_prim_tables(s, s->hostInstances.data(), prims, refs);
+        rc = build_on_device_core(fresh, st, prims, refs, s->vertices.p, s->indices.p, s->buildScratch, totalPrims);
         if (rc != RTR_OK) return rc;
     } else {
         std::vector<RtrVertex> vertices(s->numVertices); std::vector<uint32_t> indices(s->numIndices);
         if (s->numVertices) HIP_TRY(hipMemcpy(vertices.data(), s->vertices.p, vertices.size() * sizeof(RtrVertex), hipMemcpyDeviceToHost));
         if (s->numIndices) HIP_TRY(hipMemcpy(indices.data(), s->indices.p, indices.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        rtr_scene_desc view = host_view(s);
         view.vertices = vertices.data(); view.numVertices = s->numVertices; view.indices = indices.data(); view.numIndices = s->numIndices;
         rtr::BvhResult bvh; std::vector<float> xforms, nmats; uint32_t stackEntries = 0; size_t numTris = 0;
         rc = flatten_and_build(&view, bvh, xforms, nmats, &stackEntries, &numTris);      /* the transform tables it fills are the scene's own already */
         if (rc != RTR_OK) return rc;
-        if (!maskBits.empty()) for (RtrBvhTri& tr : bvh.tris) if (tr.customIndex < maskBits.size()) tr.flags |= maskBits[tr.customIndex];
-        HIP_TRY(t->nodes.upload(reinterpret_cast<const uint4*>(bvh.nodes.data()), bvh.nodes.size() * 2, st));
-        HIP_TRY(t->grid.upload(&bvh.grid, 1, st));
-        HIP_TRY(t->tris.upload(reinterpret_cast<const float4*>(bvh.tris.data()), bvh.tris.size() * 3, st));
-        fill_stats(t->stats, bvh, stackEntries, numTris);
-        t->hostNodes.swap(bvh.nodes); t->hostTris.swap(bvh.tris); t->hostWideShape.swap(bvh.wideShape);
-        t->numPrims = (uint32_t)t->hostTris.size(); t->numNodeSlots = (uint32_t)t->hostNodes.size();
+        if (!s->hostMasks.empty()) {      /* the new records carry the instance masks, as a refit's do */
+            const std::vector<uint32_t> maskBits = instance_mask_bits(s, s->hostMasks.data());
+            for (RtrBvhTri& tr : bvh.tris) if (tr.customIndex < maskBits.size()) tr.flags |= maskBits[tr.customIndex];
+        }
+        HIP_TRY(fresh.nodes.upload(reinterpret_cast<const uint4*>(bvh.nodes.data()), bvh.nodes.size() * 2, st));
+        HIP_TRY(fresh.grid.upload(&bvh.grid, 1, st));
+        HIP_TRY(fresh.tris.upload(reinterpret_cast<const float4*>(bvh.tris.data()), bvh.tris.size() * 3, st));
+        fill_stats(fresh.stats, bvh, stackEntries, numTris);
+        fresh.hostNodes.swap(bvh.nodes); fresh.hostTris.swap(bvh.tris); fresh.hostWideShape.swap(bvh.wideShape);
+        fresh.numPrims = (uint32_t)fresh.hostTris.size(); fresh.numNodeSlots = (uint32_t)fresh.hostNodes.size();
     }
-    rc = make_wide_nodes(t);
+    rc = make_wide_nodes(fresh, st);
     if (rc != RTR_OK) return rc;
-    swap_tree(s, t);
-    DeviceScene& dv = s->dev;
-    dv.nodes = s->nodes.p; dv.nodes4 = s->nodes4.p; dv.numNodes4 = (uint32_t)s->hostNodes.size(); dv.grid = s->grid.p; dv.tris = s->tris.p;
-    /* the leaf order changed: the triangle -> leaf table goes, and the next call that needs it makes it again (ensure_leaf_table) */
-    s->leafTable.release(); s->leafReady = false;
-    s->costParent.release(); s->costParentState = 0;
+    const bool prepared = s->tree.asyncReady;
+    std::swap(s->tree, fresh);      /* `fresh` takes the old tree away: freed on return — the device was joined, and nothing has been enqueued against it since */
+    point_at_tree(s->dev, s->tree);
     /* the enqueued update's tables and scratch belong to a tree: made again for the new one (its node count, its leaf slots) */
-    if (s->asyncReady) { s->asyncReady = false; return rtr_scene_prepare_async_updates(s); }
-    return RTR_OK;      /* ~Temp frees the old tree: the device was joined, and nothing has been enqueued against it since */
+    return prepared ? rtr_scene_prepare_async_updates(s) : RTR_OK;
 }
 
 void rtr_scene_destroy(rtr_scene* s) {
@@ -1458,7 +1457,7 @@ void rtr_scene_destroy(rtr_scene* s) {
 int rtr_scene_get_stats(const rtr_scene* s, rtr_scene_stats* out) {
     if (!s || !out) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_scene_get_stats: null argument");
     { const int rcm = refresh_mirrors(s); if (rcm != RTR_OK) return rcm; }
-    *out = s->stats;
+    *out = s->tree.stats;
     return RTR_OK;
 }
 
@@ -1466,12 +1465,12 @@ int rtr_scene_export_bvh(const rtr_scene* s, RtrBvhNode* nodes, size_t nodeBytes
     if (!s) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_scene_export_bvh: null scene");
     { const int rcm = refresh_mirrors(s); if (rcm != RTR_OK) return rcm; }
     if (nodes) {
-        if (nodeBytes != s->hostNodes.size() * sizeof(RtrBvhNode)) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_scene_export_bvh: nodeBytes %zu != %zu", nodeBytes, s->hostNodes.size() * sizeof(RtrBvhNode));
-        memcpy(nodes, s->hostNodes.data(), nodeBytes);
+        if (nodeBytes != s->tree.hostNodes.size() * sizeof(RtrBvhNode)) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_scene_export_bvh: nodeBytes %zu != %zu", nodeBytes, s->tree.hostNodes.size() * sizeof(RtrBvhNode));
+        memcpy(nodes, s->tree.hostNodes.data(), nodeBytes);
     }
     if (tris) {
-        if (triBytes != s->hostTris.size() * sizeof(RtrBvhTri)) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_scene_export_bvh: triBytes %zu != %zu", triBytes, s->hostTris.size() * sizeof(RtrBvhTri));
-        memcpy(tris, s->hostTris.data(), triBytes);
+        if (triBytes != s->tree.hostTris.size() * sizeof(RtrBvhTri)) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_scene_export_bvh: triBytes %zu != %zu", triBytes, s->tree.hostTris.size() * sizeof(RtrBvhTri));
+        memcpy(tris, s->tree.hostTris.data(), triBytes);
     }
     return RTR_OK;
 }
@@ -1479,9 +1478,9 @@ int rtr_scene_export_bvh(const rtr_scene* s, RtrBvhNode* nodes, size_t nodeBytes
 int rtr_scene_export_wide(const rtr_scene* s, RtrWideNode* nodes, size_t nodeBytes) {
     if (!s || !nodes) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_scene_export_wide: null argument");
     { const int rcm = refresh_mirrors(s); if (rcm != RTR_OK) return rcm; }
-    if (nodeBytes != (size_t)s->wideReached * sizeof(RtrWideNode)) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_scene_export_wide: nodeBytes %zu != %zu", nodeBytes, (size_t)s->wideReached * sizeof(RtrWideNode));
+    if (nodeBytes != (size_t)s->tree.wideReached * sizeof(RtrWideNode)) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_scene_export_wide: nodeBytes %zu != %zu", nodeBytes, (size_t)s->tree.wideReached * sizeof(RtrWideNode));
     HIP_TRY(hipSetDevice(s->ctx->device));
-    HIP_TRY(hipMemcpy(nodes, s->nodes4.p, nodeBytes, hipMemcpyDeviceToHost));      /* the records the tree reaches come first */
+    HIP_TRY(hipMemcpy(nodes, s->tree.nodes4.p, nodeBytes, hipMemcpyDeviceToHost));      /* the records the tree reaches come first */
     return RTR_OK;
 }
 
@@ -1520,12 +1519,6 @@ int rtr_check_scene_limits(uint64_t numTriangles, uint64_t numNodes) {
 }
 
 /* ---- frame -------------------------------------------------------------------------------- */
-static int frame_new(rtr_ctx* ctx, uint32_t width, uint32_t rows, uint32_t images, bool ownImages, rtr_frame** out);
-
-int rtr_frame_create(rtr_ctx* ctx, uint32_t width, uint32_t rows, uint32_t images, rtr_frame** out) {
-    return frame_new(ctx, width, rows, images, true, out);
-}
-
 /* ownImages == false: a part of a split render (no images of its own, see rtr_frame::parts) */
 static int frame_new(rtr_ctx* ctx, uint32_t width, uint32_t rows, uint32_t images, bool ownImages, rtr_frame** out) {
     if (!ctx || !out) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_frame_create: null ctx/out");
@@ -1550,6 +1543,10 @@ static int frame_new(rtr_ctx* ctx, uint32_t width, uint32_t rows, uint32_t image
     if (e != hipSuccess) { rtr_frame_destroy(f); return fail(e == hipErrorOutOfMemory ? RTR_ERR_OUT_OF_MEMORY : RTR_ERR_HIP, "rtr_frame_create: %s", hipGetErrorString(e)); }
     *out = f;
     return RTR_OK;
+}
+
+int rtr_frame_create(rtr_ctx* ctx, uint32_t width, uint32_t rows, uint32_t images, rtr_frame** out) {
+    return frame_new(ctx, width, rows, images, true, out);
 }
 
 void rtr_frame_destroy(rtr_frame* f) {
@@ -1761,10 +1758,10 @@ static int enqueue_render(rtr_scene* s, const RtrCameraData* cams, const RtrScen
 #endif
         ws.rayQueue.dt = f->rayDT.p; ws.rayQueue.slot = f->raySlot.p; ws.rayQueue.origin = f->rayOrigin.p; ws.rayQueue.slotStride = f->slotStride; ws.rayQueue.slotMask = f->slotStride - 1u;
         ws.queueCount = f->queueCount.p; ws.capPixelSamples = nPS; ws.capRays = nRays; ws.spill = f->spill.p; ws.overflow = f->overflow.p; ws.overflowCap = f->overflowCap; ws.batchLists = f->batchLists.p; ws.listStride = f->listStride; ws.clk = f->clk.p;
-        e = rtrdev::launch_wavefront(s->dev, fb, ws, f->ctx->tun, (int)s->stats.stackEntries, dstats, st, f->ev, (uint32_t)f->ctx->prop.multiProcessorCount);
+        e = rtrdev::launch_wavefront(s->dev, fb, ws, f->ctx->tun, (int)s->tree.stats.stackEntries, dstats, st, f->ev, (uint32_t)f->ctx->prop.multiProcessorCount);
     } else {
         (void)hipEventRecord(f->evMega[0], st);
-        e = rtrdev::launch_megakernel(s->dev, ra, fo, (int)s->stats.stackEntries, dstats, st);
+        e = rtrdev::launch_megakernel(s->dev, ra, fo, (int)s->tree.stats.stackEntries, dstats, st);
         (void)hipEventRecord(f->evMega[1], st);
     }
     if (e != hipSuccess) return fail(RTR_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
@@ -2248,7 +2245,7 @@ static int enqueue_occlusion(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays,
     oa.rays = reinterpret_cast<const float4*>(rays); oa.occluded = occluded; oa.n = n; oa.batch = rtrdev::occlusion_batch(n);
     oa.ctrl = reinterpret_cast<uint32_t*>(base + l.ctrl); oa.overflow = reinterpret_cast<uint32_t*>(base + l.overflow); oa.overflowCap = overflowCap;
     oa.queue = reinterpret_cast<uint32_t*>(base + l.queue); oa.lists = reinterpret_cast<uint2*>(base + l.lists); oa.listStride = l.listStride;
-    oa.startLeaves = startLeaves; oa.numTris = (uint32_t)(s->tris.n / 3);          /* a hint is checked against the records the scene holds */
+    oa.startLeaves = startLeaves; oa.numTris = (uint32_t)(s->tree.tris.n / 3);          /* a hint is checked against the records the scene holds */
     const rtrdev::RayMaskArgs rm = ray_mask_args(cm, flags);
     const hipError_t e = rtrdev::launch_occlusion(s->dev, oa, c->tun, (flags & RTR_QUERY_OPAQUE) == 0u, c->qSpill.p, count ? c->qCounters.p : nullptr, st,
                                                   (uint32_t)c->prop.multiProcessorCount, rm);
@@ -2345,7 +2342,8 @@ int rtr_hit_surfaces(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const R
  * goes on: whichever context of the device asks next finds it complete, without an event to wait for.  rtr_scene_update_instances
  * keeps it (a refit moves boxes and records, not the leaves they sit in). */
 static int ensure_leaf_table(rtr_ctx* c, const rtr_scene* s, const char* who) {
-    if (s->leafReady) return RTR_OK;
+    const SceneTree& t = s->tree;
+    if (t.leafReady) return RTR_OK;
     { const int rcm = refresh_mirrors(s); if (rcm != RTR_OK) return rcm; }      /* joins an enqueued refit: this kernel may run on another stream */
     std::vector<uint32_t> base(s->hostTriCount.size() + 1, 0u);
     uint64_t total = 0;
@@ -2353,13 +2351,13 @@ static int ensure_leaf_table(rtr_ctx* c, const rtr_scene* s, const char* who) {
     if (total > 0xffffffffull) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: %llu (customIndex, primitiveId) pairs do not fit the leaf table's 32-bit index", who, (unsigned long long)total);
     hipStream_t st = c->stream;
     HIP_TRY(s->leafBase.upload(base.data(), base.size(), st));
-    HIP_TRY(s->leafTable.alloc((size_t)total));
-    HIP_TRY(hipMemsetAsync(s->leafTable.p, 0, s->leafTable.n * sizeof(int32_t), st));
-    const hipError_t e = rtrdev::launch_leaf_table(s->nodes.p, (uint32_t)(s->nodes.n / 2), s->tris.p, (uint32_t)(s->tris.n / 3), s->triCount.p, s->leafBase.p,
-                                                   s->numInstances, s->leafTable.p, st);
+    HIP_TRY(t.leafTable.alloc((size_t)total));
+    HIP_TRY(hipMemsetAsync(t.leafTable.p, 0, t.leafTable.n * sizeof(int32_t), st));
+    const hipError_t e = rtrdev::launch_leaf_table(t.nodes.p, (uint32_t)(t.nodes.n / 2), t.tris.p, (uint32_t)(t.tris.n / 3), s->triCount.p, s->leafBase.p,
+                                                   s->numInstances, t.leafTable.p, st);
     if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: leaf table: %s", who, hipGetErrorString(e));
     HIP_TRY(hipStreamSynchronize(st));
-    s->leafReady = true;
+    t.leafReady = true;
     return RTR_OK;
 }
 
@@ -2377,7 +2375,7 @@ static int enqueue_hit_leaves(rtr_ctx* c, const rtr_scene* s, const RtrHit* hits
     const int rc = ensure_leaf_table(c, s, who);
     if (rc != RTR_OK) return rc;
     rtrdev::LeafArgs a{};
-    a.hits = reinterpret_cast<const float4*>(hits); a.leaves = leaves; a.triCount = s->triCount.p; a.base = s->leafBase.p; a.table = s->leafTable.p;
+    a.hits = reinterpret_cast<const float4*>(hits); a.leaves = leaves; a.triCount = s->triCount.p; a.base = s->leafBase.p; a.table = s->tree.leafTable.p;
     a.numInstances = s->numInstances; a.n = n;
     const hipError_t e = rtrdev::launch_hit_leaves(a, c->stream);
     if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: kernel launch: %s", who, hipGetErrorString(e));
@@ -2453,7 +2451,7 @@ static int enqueue_light(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, con
     HIP_TRY(hipSetDevice(c->device));
     if (hinted) { const int rct = ensure_leaf_table(c, s, who); if (rct != RTR_OK) return rct; }
     rtrdev::LightArgs la{};
-    if (hinted) { la.outLeaves = outLeaves; la.leafTable = s->leafTable.p; la.leafBase = s->leafBase.p; }
+    if (hinted) { la.outLeaves = outLeaves; la.leafTable = s->tree.leafTable.p; la.leafBase = s->leafBase.p; }
     la.rays = reinterpret_cast<const float4*>(rays); la.hits = reinterpret_cast<const float4*>(hits); la.seeds = seeds;
     la.triCount = s->triCount.p; la.numInstances = s->numInstances; la.n = n; la.slots = slots;
     la.numAreaLights = p->numAreaLights; la.numShadowRays = p->numShadowRays; la.frame = p->frame; la.width = p->width; la.spp = p->spp;

@@ -335,7 +335,8 @@ int  rtr_scene_export_vertices(const rtr_scene* scene, RtrVertex* out, size_t by
 /* Both enqueued updates — rtr_scene_update_vertices_async and rtr_scene_update_instances_async (below) — count on ONE serial sequence:
  * `enqueued`, `refused` and firstRefusedUpdate speak of updates of either kind.  For a refused INSTANCE update firstBadVertex carries the
  * smallest offending ELEMENT INDEX of that update instead of a vertex: i < numInstances(scene) is instance i (instance order),
- * numInstances(scene) + l is light l.  The caller knows which call had which serial. */
+ * numInstances(scene) + l is light l.  An enqueued REBUILD (rtr_scene_rebuild_async, below) counts on the same sequence; for a refused
+ * rebuild firstBadVertex carries the DEPTH of the tree that was refused.  The caller knows which call had which serial. */
 typedef struct rtr_update_status {
     uint64_t enqueued, refused;
     uint32_t firstRefusedUpdate, firstBadVertex;
@@ -447,6 +448,47 @@ int  rtr_host_tree_cost(const RtrBvhNode* nodes, size_t nodeBytes, const RtrBvhG
  * build's depth check — leaves the scene as it was (HIP runtime errors excepted).  An empty scene returns RTR_OK and does nothing.
  * Scenes replicated by librtr_mgpu have no rebuild path, as they have no update path. */
 int  rtr_scene_rebuild(rtr_scene* scene, uint32_t buildFlags);
+/* The ENQUEUED rebuild: rtr_scene_rebuild with RTR_BUILD_DEVICE_LBVH as stream-ordered work, so that a frame loop that animates on the
+ * device gets a good tree back every few frames without stopping.  The synchronous call joins the whole device, makes the primitive
+ * tables in host loops, allocates a new tree, orders the 4-wide view in a host loop and reads the tree back; this form builds into a
+ * STAGE — a second set of the build's arrays that nothing else reads — and lets the device decide the commit.
+ * rtr_scene_prepare_async_rebuild: ONCE per scene, synchronous; may join and allocate.  It implies (and calls)
+ * rtr_scene_prepare_async_updates, and allocates the stage (nodes, fp32 nodes, grid, records, leaf boxes, parent links, the primitive ->
+ * slot map, the reduction words: 184 B per triangle) and the device build's scratch (112 B per triangle and the sort's temporary
+ * storage; the scratch the first synchronous device rebuild allocates, and shared with it) — some 300 B per triangle, kept for the
+ * scene's life.  The commit copies into the live arrays IN PLACE, so they must have a device build's sizes: the scene's current tree must
+ * have been made by RTR_BUILD_DEVICE_LBVH (at creation or by rtr_scene_rebuild) from at least 16 triangles; otherwise
+ * RTR_ERR_INVALID_ARGUMENT, and the message names rtr_scene_rebuild(scene, RTR_BUILD_DEVICE_LBVH) as the way to get there.  Idempotent; an
+ * empty scene returns RTR_OK.  A synchronous rtr_scene_rebuild of a prepared scene prepares the new tree by itself when that is a device
+ * tree; after a HOST rebuild the readiness is gone and the enqueued call is refused until a synchronous device rebuild gives the scene a
+ * device tree again (which prepares it, without a call).
+ * rtr_scene_rebuild_async: buildFlags must be RTR_BUILD_DEVICE_LBVH (RTR_BUILD_HOST_SAH — the host builder is host code — and anything
+ * above are refused).  Argument checks and launches only: no allocation, no synchronisation, no device -> host copy, no copy from
+ * reusable host memory, everything on the scene's context stream — ORDERING as documented for rtr_scene_update_vertices_async.  Refused
+ * BEFORE anything is enqueued (RTR_ERR_INVALID_ARGUMENT, the message names the function): a null scene, bad flags (checked before the
+ * scene is looked at), a scene not prepared for it.  An empty scene returns RTR_OK, counts as enqueued and does nothing.  The chain:
+ *   the device build  rtr_scene_create's kernels in their order, into the stage, from the LIVE device tables (primitives, instances with
+ *                     their current transforms, the instance masks in the flags: current after enqueued instance updates and after
+ *                     rtr_scene_set_instance_masks) and the scene's vertex and index arrays.  It writes nothing a render or query reads.
+ *   the commit        one kernel (k_commit_tree) reads the staged tree's depth.  THE ONE REFUSAL RULE: the scene's render kernels are
+ *                     specialised on the host for a traversal-stack class — 16, 32 or 64 entries, stats.stackEntries — and the host
+ *                     cannot learn a new depth without a join; so a tree DEEPER than stats.stackEntries at the time of the call is
+ *                     refused: the depth goes into the update word and nothing is copied.  Otherwise every staged array is copied over
+ *                     its live twin, all of it or none.  A tree that fits a SMALLER class is committed and stats.stackEntries keeps its
+ *                     value: a larger stack is always correct and changes no byte of any answer; an enqueued rebuild never lowers it
+ *                     (the next synchronous rtr_scene_rebuild does).  A device tree is never deeper than 64.
+ *   the 4-wide view   of the live arrays, its breadth-first order on the device, the permutation; the triangle -> leaf table, if the
+ *                     scene has one, is made again in place (it stays ready and current; a scene that never asked for it gets it on
+ *                     first use, as always); the status fold with this call's serial.  After a refused commit these run on the
+ *                     unchanged tree and reproduce its bytes, as after a refused update.
+ * The result is the synchronous call's, byte for byte (tested) — tree, records, grid, 4-wide view, tree cost, stats.maxDepth at the next
+ * read-back — except stats.stackEntries as said, and stats.buildMs, which keeps its old value: nobody timed the build.  The contract of
+ * rtr_scene_rebuild otherwise holds: textures, tables, vertices, masks, frames made before the call; every pointer a caller holds stays
+ * literally the same, because nothing is swapped.  Start hints made before the call are stale and, by the hinted calls' contract, change
+ * no byte.  STATUS and HOST MIRRORS: as the enqueued updates (rtr_update_status above; for a refused rebuild firstBadVertex is the
+ * refused tree's depth).  Scenes replicated by librtr_mgpu have no enqueued rebuild, as they have no update path. */
+int  rtr_scene_prepare_async_rebuild(rtr_scene* scene);
+int  rtr_scene_rebuild_async(rtr_scene* scene, uint32_t buildFlags);
 /* Instance cull masks: VkAccelerationStructureInstanceKHR::mask (reference src/vulkan/raytracing/tlas.cppm:63, instance.setMask(0xFF): the
  * only value the reference uses).  masks: a HOST array, one byte per instance, in instance order (rtr_scene_desc::instances); every new
  * scene — one made by rtr_scene_create_like too — starts with 0xff everywhere.  Only the MASKED ray queries (rtr_trace_rays_masked,

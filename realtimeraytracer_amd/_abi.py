@@ -94,7 +94,7 @@ class rtr_update_status(C.Structure):
     """rtr_scene_update_status: updates enqueued so far, how many of them the device refused (bad data), and the serial (1-based) of the
     first refused one since the last status call with its first bad scene vertex (0xffffffff each where there is none).  Vertex and
     instance updates share the serials; for a refused instance update firstBadVertex is its first bad element (instance index, or
-    numInstances + light index)"""
+    numInstances + light index); enqueued rebuilds count too, and a refused one reports the refused tree's depth there"""
     _fields_ = [("enqueued", u64), ("refused", u64), ("firstRefusedUpdate", u32), ("firstBadVertex", u32), ("_pad", u32 * 2)]
 
 
@@ -213,6 +213,8 @@ RTR_SYMBOLS = {
     "rtr_scene_tree_cost": (C.c_int, [VP, P(rtr_tree_cost)]),
     "rtr_host_tree_cost": (C.c_int, [VP, C.c_size_t, P(RtrBvhGrid), P(rtr_tree_cost)]),
     "rtr_scene_rebuild": (C.c_int, [VP, u32]),
+    "rtr_scene_prepare_async_rebuild": (C.c_int, [VP]),
+    "rtr_scene_rebuild_async": (C.c_int, [VP, u32]),
     "rtr_scene_set_instance_masks": (C.c_int, [VP, VP, u32]),
     "rtr_scene_get_instance_masks": (C.c_int, [VP, VP, u32]),
     "rtr_frame_create": (C.c_int, [VP, u32, u32, u32, P(VP)]),

@@ -190,9 +190,24 @@ class Scene:
         """rtr_scene_prepare_async_updates: once, synchronously, everything update_vertices_async must not do later"""
         _check(self.lib.rtr_scene_prepare_async_updates(self.h), "rtr_scene_prepare_async_updates")
 
+    def prepare_async_rebuild(self):
+        """rtr_scene_prepare_async_rebuild: once, synchronously, everything rebuild_async must not do later — prepare_async_updates, the
+        stage the device build writes and the build's scratch (some 300 B per triangle, kept).  The scene's tree must be a device
+        tree of at least 16 triangles (rebuild("device") makes one)."""
+        _check(self.lib.rtr_scene_prepare_async_rebuild(self.h), "rtr_scene_prepare_async_rebuild")
+
+    def rebuild_async(self, build="device"):
+        """rtr_scene_rebuild_async: rebuild("device") as stream-ordered work on the context's stream; returns at once, joins nothing.
+        Only build="device" can be enqueued.  The device refuses a tree deeper than the stack class the scene renders with
+        (stats().stackEntries): update_status() reports it, and the refused rebuild changes nothing.  _built_sah is not refreshed: the
+        cost is not known without a join."""
+        if build != "device":
+            raise ValueError(f"rebuild_async: only build='device' can be enqueued, got {build!r}")
+        _check(self.lib.rtr_scene_rebuild_async(self.h, A.BUILD_DEVICE_LBVH), "rtr_scene_rebuild_async")
+
     def update_status(self):
         """rtr_scene_update_status: joins the context's stream and reports the enqueued updates -> UpdateStatus.  The tensors of the
-        updates enqueued so far are released."""
+        updates enqueued so far are released.  For a refused rebuild_async, first_bad_vertex is the depth of the tree that was refused."""
         st = A.rtr_update_status()
         _check(self.lib.rtr_scene_update_status(self.h, C.byref(st)), "rtr_scene_update_status")
         self._async_keep = []

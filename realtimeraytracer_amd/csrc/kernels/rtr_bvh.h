@@ -84,6 +84,19 @@ hipError_t launch_write_instances(const void* transforms, uint32_t strideWords, 
 /* bvh_refit with the reduction words set by a kernel: no host memory is read after the call returns */
 hipError_t bvh_refit_enqueued(const BvhInputs& in, uint32_t numPrims, uint32_t numNodes, const BvhDeviceArrays& a, hipStream_t s);
 
+/* The enqueued rebuild (rtr_scene_rebuild_async).  bvh_build_lbvh_enqueued: bvh_build_lbvh — the same kernels in the same order — with the
+ * reduction words set by k_refit_init and the nodesF memset inside: launches only (the hipcub sort runs in the caller's temp storage), no
+ * host memory is read after the call returns.  `a` is the STAGE (counters and depth may be the live tree's: scratch of the same stream).
+ * bvh_commit_tree: k_commit_tree — when the staged depth stagedRed[7] is above `limit`, the depth goes into *word and nothing is copied;
+ * otherwise every (src, dst, bytes) of the table is copied, 16 bytes per lane and trip, word-wise after an array's last whole 16 bytes.
+ * bytes: multiples of 4; src, dst: 16-B aligned.  One launch of at most kCommitMaxBlocks workgroups of 256 lanes, grid-strided: 4 MiB
+ * per trip — four workgroups (16 waves) per CU of a 256-CU part, which a copy does not need more of. */
+constexpr uint32_t kCommitArrays = 12;
+constexpr uint32_t kCommitMaxBlocks = 1024;
+struct CommitTable { struct { const void* src; void* dst; uint64_t bytes; } a[kCommitArrays]; uint32_t count; };
+hipError_t bvh_build_lbvh_enqueued(const BvhInputs& in, uint32_t numPrims, const BvhDeviceArrays& a, const BvhScratch& t, hipStream_t s);
+hipError_t bvh_commit_tree(const CommitTable& t, const uint32_t* stagedRed, uint32_t limit, uint32_t* word, hipStream_t s);
+
 /* The 4-wide view of a finished (quantised) tree that the any-hit kernel walks: numNodes x 4 uint4, see k_wide_nodes.
  * parentOrNull: the refit parent array (entries outside the tree are skipped) or null. */
 /* sets grid->wideCentreXY / Z (k_wide_centre_*; sums4 = bvh_wide_scratch_words() x u64 of scratch) and writes the 4-wide records about it */

@@ -856,6 +856,33 @@ __global__ __launch_bounds__(kOrderB) void k_wide_order(const uint4* __restrict_
     }
 }
 
+/* ---- the commit of an enqueued rebuild (rtr_scene_rebuild_async) ------------------------------------------------------------------
+ * The device build wrote a STAGE, a second set of the tree's arrays nothing else reads; this kernel decides, on the device, whether the
+ * staged tree replaces the live one.  The decision is one word every lane reads before anything else: the staged depth (red[7] of the
+ * stage).  Above `limit` — the stack class the scene's render kernels are specialised for, which the host cannot raise without a join —
+ * lane 0 writes the depth into *word (the update word the status fold reads) and NO lane copies anything; otherwise every array of the
+ * table is copied over its live twin: all of it lands or none of it does.
+ * One launch over all arrays: the table travels as a kernel argument; a lane moves 16 bytes per trip, the grid is capped
+ * (kCommitMaxBlocks) and strides over an array's 16-byte chunks; the up to three words after an array's last whole chunk (4 (n - 1)-byte
+ * arrays) are moved by the first lanes of the grid.  Every base is a hipMalloc'd one (256-B aligned), every size a multiple of 4. */
+__global__ __launch_bounds__(kB) void k_commit_tree(CommitTable t, const uint32_t* __restrict__ stagedRed, uint32_t limit, uint32_t* __restrict__ word) {
+    const uint32_t depth = stagedRed[7];
+    const uint32_t g = blockIdx.x * kB + threadIdx.x;
+    if (depth > limit) {                                 /* the class would have to rise: refused, and the live tree keeps its bytes */
+        if (g == 0) *word = depth;
+        return;
+    }
+    const uint32_t stride = gridDim.x * kB;
+    for (uint32_t k = 0; k < t.count; ++k) {
+        const uint4* __restrict__ src = static_cast<const uint4*>(t.a[k].src);
+        uint4* __restrict__ dst = static_cast<uint4*>(t.a[k].dst);
+        const uint64_t chunks = t.a[k].bytes >> 4;
+        for (uint64_t i = g; i < chunks; i += stride) dst[i] = src[i];
+        const uint32_t tailWords = (uint32_t)(t.a[k].bytes & 15u) >> 2;
+        if (g < tailWords) reinterpret_cast<uint32_t*>(dst + chunks)[g] = reinterpret_cast<const uint32_t*>(src + chunks)[g];
+    }
+}
+
 /* ---- host-side drivers ------------------------------------------------------------------------------ */
 #define BV_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return e_; } while (0)
 
@@ -941,6 +968,40 @@ hipError_t bvh_refit_enqueued(const BvhInputs& in, uint32_t numPrims, uint32_t n
     hipLaunchKernelGGL(k_fit, dim3((numNodes + kB - 1) / kB), dim3(kB), 0, s, numNodes, a.nodesF, a.boxMin, a.boxMax, a.parent, a.counters, a.depth, a.red, a.red + 7);
     hipLaunchKernelGGL(k_grid, dim3(1), dim3(64), 0, s, a.nodesF, a.grid);
     hipLaunchKernelGGL(k_quantize, dim3((numNodes + kB - 1) / kB), dim3(kB), 0, s, numNodes, a.nodesF, a.parent, a.grid, a.nodes);
+    return hipGetLastError();
+}
+
+/* bvh_build_lbvh without its host array and with the nodesF memset inside: the same kernels in the same order */
+hipError_t bvh_build_lbvh_enqueued(const BvhInputs& in, uint32_t numPrims, const BvhDeviceArrays& a, const BvhScratch& t, hipStream_t s) {
+    const uint32_t n = numPrims, numNodes = n - 1;
+    BV_TRY(hipMemsetAsync(a.nodesF, 0, (size_t)numNodes * 64, s));
+    hipLaunchKernelGGL(k_refit_init, dim3(1), dim3(64), 0, s, a.red);
+    BV_TRY(hipMemsetAsync(a.counters, 0, (size_t)numNodes * sizeof(uint32_t), s));
+    BV_TRY(hipMemsetAsync(a.depth, 0, (size_t)numNodes * sizeof(uint32_t), s));
+    const dim3 gp((n + kB - 1) / kB), gn((numNodes + kB - 1) / kB);
+    hipLaunchKernelGGL(k_world_prims, gp, dim3(kB), 0, s, in, n, (const uint32_t*)nullptr, t.trisCanon, t.minCanon, t.maxCanon, a.red);
+    hipLaunchKernelGGL(k_morton, gp, dim3(kB), 0, s, n, t.minCanon, t.maxCanon, a.red, t.keysIn);
+    size_t tempBytes = t.sortTempBytes;
+    BV_TRY(hipcub::DeviceRadixSort::SortKeys(t.sortTemp, tempBytes, t.keysIn, t.keysOut, (int)n, 0, 64, s));
+    hipLaunchKernelGGL(k_gather, gp, dim3(kB), 0, s, n, t.keysOut, t.trisCanon, t.minCanon, t.maxCanon, a.tris, a.boxMin, a.boxMax, a.slotOfPrim);
+    hipLaunchKernelGGL(k_karras, gn, dim3(kB), 0, s, (int)n, t.keysOut, t.range, t.rawChild);
+    hipLaunchKernelGGL(k_mark_unused, gn, dim3(kB), 0, s, numNodes, a.parent);
+    hipLaunchKernelGGL(k_emit, gn, dim3(kB), 0, s, (int)n, t.range, t.rawChild, a.nodesF, a.parent);
+    hipLaunchKernelGGL(k_fit, gn, dim3(kB), 0, s, numNodes, a.nodesF, a.boxMin, a.boxMax, a.parent, a.counters, a.depth, a.red, a.red + 7);
+    hipLaunchKernelGGL(k_grid, dim3(1), dim3(64), 0, s, a.nodesF, a.grid);
+    hipLaunchKernelGGL(k_quantize, gn, dim3(kB), 0, s, numNodes, a.nodesF, a.parent, a.grid, a.nodes);
+    return hipGetLastError();
+}
+
+hipError_t bvh_commit_tree(const CommitTable& t, const uint32_t* stagedRed, uint32_t limit, uint32_t* word, hipStream_t s) {
+    if (t.count > kCommitArrays) return hipErrorInvalidValue;
+    uint64_t chunks = 1;
+    for (uint32_t k = 0; k < t.count; ++k) {
+        if ((t.a[k].bytes & 3u) || ((uintptr_t)t.a[k].src & 15u) || ((uintptr_t)t.a[k].dst & 15u)) return hipErrorInvalidValue;
+        chunks = t.a[k].bytes >> 4 > chunks ? t.a[k].bytes >> 4 : chunks;
+    }
+    const uint64_t blocks = (chunks + kB - 1) / kB;
+    hipLaunchKernelGGL(k_commit_tree, dim3((uint32_t)(blocks < kCommitMaxBlocks ? blocks : kCommitMaxBlocks)), dim3(kB), 0, s, t, stagedRed, limit, word);
     return hipGetLastError();
 }
 

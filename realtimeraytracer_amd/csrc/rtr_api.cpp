@@ -116,6 +116,18 @@ struct BuildScratch {
     DevBuf<unsigned long long> keysIn, keysOut;
     DevBuf<int2> range, rawChild;
     DevBuf<uint8_t> sortTemp;
+    size_t sortTempBytes = 0;            /* what hipcub asked for (sortTemp may be larger) */
+};
+
+/* rtr_scene_rebuild_async's stage: a second set of the arrays a device build writes, which nothing else reads.  The enqueued build fills
+ * it, k_commit_tree copies it over the live arrays — or does not.  Sizes depend on the triangle count alone; counters and depth are not
+ * staged: they are scratch of whatever fit runs next on the scene's stream, and the build uses the live tree's. */
+struct TreeStage {
+    DevBuf<uint4> nodes;
+    DevBuf<float4> nodesF, tris, boxMin, boxMax;
+    DevBuf<RtrBvhGrid> grid;
+    DevBuf<int32_t> parent;
+    DevBuf<uint32_t> slotOfPrim, red;
 };
 
 /* The tree of a scene.  A member is here if and only if it must not outlive the tree: its content or its size is a function of the node
@@ -157,6 +169,9 @@ struct SceneTree {
      * are on the device for this tree, it is refit-ready, and the scratch and the scene's asyncWords and instCustom exist */
     DevBuf<uint32_t> orderScratch;
     bool asyncReady = false;
+    /* the enqueued rebuild (rtr_scene_prepare_async_rebuild): this tree has a device build's array sizes, and the scene's stage and
+     * build scratch exist.  Here and not on the scene: a new tree starts unprepared (a host rebuild's has other sizes) */
+    bool rebuildReady = false;
     rtr_scene_stats stats{};
 };
 }  // namespace
@@ -192,6 +207,9 @@ struct rtr_scene {
     DevBuf<uint32_t> vtxPrefix, vtxStage;
     std::vector<uint32_t> vtxHost;
     BuildScratch buildScratch;           /* rtr_scene_rebuild with RTR_BUILD_DEVICE_LBVH: empty until the first one */
+    TreeStage stage;                     /* rtr_scene_prepare_async_rebuild: kept through synchronous rebuilds, like the scratch */
+    /* an enqueued rebuild has run (or will) since stats.maxDepth was read back: refresh_mirrors takes it from the live red[7] */
+    mutable bool depthStale = false;
     /* the enqueued updates (made by rtr_scene_prepare_async_updates): the words of the enqueued chain — [0] the first bad vertex of the
      * update in flight, [1] the entries the 4-wide tree reaches, [4..6] the sticky status (refused count, serial of the first refused
      * update since the last status call, its first bad vertex).
@@ -572,6 +590,9 @@ static int refresh_mirrors(const rtr_scene* cs) {
     { const int rc = read_back_tree(s->tree, red); if (rc != RTR_OK) return rc; }
     HIP_TRY(hipMemcpy(&reached, s->asyncWords.p + 1, sizeof reached, hipMemcpyDeviceToHost));
     s->tree.wideReached = reached; s->tree.stats.numWideNodes = reached;
+    /* after an enqueued rebuild the depth is the new tree's (or, refused, still the old one's: a refit keeps it); stackEntries stays — an
+     * enqueued rebuild never lowers the class, and the device refused one that would raise it */
+    if (s->depthStale) { s->tree.stats.maxDepth = red[7]; s->depthStale = false; }
     if (s->instancesStale) {
         static_assert(sizeof(rtrdev::InstanceRef) == 64 && sizeof(RtrInstance) == 64, "layout");
         std::vector<rtrdev::InstanceRef> refs(s->hostInstances.size());
@@ -631,6 +652,22 @@ static rtrdev::BvhDeviceArrays device_arrays(SceneTree& t) {
     return a;
 }
 
+/* the build scratch for n triangles, allocated on first use and kept */
+static int ensure_build_scratch(BuildScratch& bs, uint32_t n) {
+    const uint32_t numNodes = n - 1;
+    HIP_TRY(bs.trisCanon.ensure((size_t)n * 3)); HIP_TRY(bs.minCanon.ensure(n)); HIP_TRY(bs.maxCanon.ensure(n));
+    HIP_TRY(bs.keysIn.ensure(n)); HIP_TRY(bs.keysOut.ensure(n)); HIP_TRY(bs.range.ensure(numNodes)); HIP_TRY(bs.rawChild.ensure(numNodes));
+    bs.sortTempBytes = rtrdev::bvh_sort_temp_bytes(n);
+    HIP_TRY(bs.sortTemp.ensure(bs.sortTempBytes));
+    return RTR_OK;
+}
+static rtrdev::BvhScratch scratch_view(const BuildScratch& bs) {
+    rtrdev::BvhScratch sc{};
+    sc.trisCanon = bs.trisCanon.p; sc.minCanon = bs.minCanon.p; sc.maxCanon = bs.maxCanon.p; sc.keysIn = bs.keysIn.p; sc.keysOut = bs.keysOut.p;
+    sc.range = bs.range.p; sc.rawChild = bs.rawChild.p; sc.sortTemp = bs.sortTemp.p; sc.sortTempBytes = bs.sortTempBytes;
+    return sc;
+}
+
 /* Device LBVH build into t.nodes / t.tris (+ refit arrays) from the primitive tables and the DEVICE vertex / index arrays given;
  * fills hostNodes/hostTris and the stats.  The core rtr_scene_create (build_on_device) and rtr_scene_rebuild share: `t` is the fresh
  * tree that is built, `bs` the scratch (the caller's to keep or free). */
@@ -644,13 +681,8 @@ static int build_on_device_core(SceneTree& t, hipStream_t st, const std::vector<
     HIP_TRY(t.tris.alloc((size_t)n * 3));
     HIP_TRY(t.boxMin.alloc(n)); HIP_TRY(t.boxMax.alloc(n)); HIP_TRY(t.parent.alloc(numNodes));
     HIP_TRY(t.counters.alloc(numNodes)); HIP_TRY(t.depth.alloc(numNodes)); HIP_TRY(t.slotOfPrim.alloc(n)); HIP_TRY(t.red.alloc(8));
-    HIP_TRY(bs.trisCanon.ensure((size_t)n * 3)); HIP_TRY(bs.minCanon.ensure(n)); HIP_TRY(bs.maxCanon.ensure(n));
-    HIP_TRY(bs.keysIn.ensure(n)); HIP_TRY(bs.keysOut.ensure(n)); HIP_TRY(bs.range.ensure(numNodes)); HIP_TRY(bs.rawChild.ensure(numNodes));
-    rtrdev::BvhScratch sc{};
-    sc.sortTempBytes = rtrdev::bvh_sort_temp_bytes(n);
-    HIP_TRY(bs.sortTemp.ensure(sc.sortTempBytes));
-    sc.trisCanon = bs.trisCanon.p; sc.minCanon = bs.minCanon.p; sc.maxCanon = bs.maxCanon.p; sc.keysIn = bs.keysIn.p; sc.keysOut = bs.keysOut.p;
-    sc.range = bs.range.p; sc.rawChild = bs.rawChild.p; sc.sortTemp = bs.sortTemp.p;
+    { const int rcs = ensure_build_scratch(bs, n); if (rcs != RTR_OK) return rcs; }
+    const rtrdev::BvhScratch sc = scratch_view(bs);
     HIP_TRY(hipMemsetAsync(t.nodesF.p, 0, (size_t)numNodes * 64, st));
     rtrdev::BvhInputs in{t.prims.p, t.instRefs.p, vertices, indices};
     hipError_t e = rtrdev::bvh_build_lbvh(in, n, device_arrays(t), sc, st);
@@ -1306,6 +1338,91 @@ int rtr_scene_update_status(rtr_scene* s, rtr_update_status* out) {
     return RTR_OK;
 }
 
+/* ---- the enqueued rebuild (contract in rtr.h) ---- */
+int rtr_scene_prepare_async_rebuild(rtr_scene* s) {
+    static const char* who = "rtr_scene_prepare_async_rebuild";
+    if (!s) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: null scene", who);
+    HIP_TRY(hipSetDevice(s->ctx->device));
+    int rc = refresh_mirrors(s);
+    if (rc != RTR_OK) return rc;
+    SceneTree& t = s->tree;
+    if (t.rebuildReady) return RTR_OK;
+    if (scene_is_empty(s)) {
+        rc = rtr_scene_prepare_async_updates(s);
+        if (rc == RTR_OK) t.rebuildReady = true;
+        return rc;
+    }
+    /* the commit copies a device build over the live arrays IN PLACE: they must have a device build's sizes already */
+    const size_t n = t.hostTris.size();
+    if (n < 16 || t.hostNodes.size() != n - 1 || !t.hostWideShape.empty())
+        return fail(RTR_ERR_INVALID_ARGUMENT, "%s: the scene's tree (%zu triangles, %zu node slots%s) was not made by the device builder, whose arrays an enqueued "
+                    "rebuild commits into: call rtr_scene_rebuild(scene, RTR_BUILD_DEVICE_LBVH) first%s", who, n, t.hostNodes.size(),
+                    t.hostWideShape.empty() ? "" : ", a cost-driven 4-wide shape", n < 16 ? " (a scene of fewer than 16 triangles always takes the host builder: it has no enqueued rebuild)" : "");
+    rc = rtr_scene_prepare_async_updates(s);
+    if (rc != RTR_OK) return rc;
+    const size_t numNodes = n - 1;
+    if (!t.refitReady || t.numPrims != n || t.numNodeSlots != numNodes || t.nodes.n < numNodes * 2 || t.nodesF.n < numNodes * 4 || t.tris.n < n * 3 || t.boxMin.n < n ||
+        t.boxMax.n < n || t.parent.n < numNodes || t.counters.n < numNodes || t.depth.n < numNodes || t.slotOfPrim.n < n || t.red.n < 8)
+        return fail(RTR_ERR_INVALID_ARGUMENT, "%s: the live arrays do not have a device build's sizes: call rtr_scene_rebuild(scene, RTR_BUILD_DEVICE_LBVH) first", who);
+    TreeStage& g = s->stage;
+    HIP_TRY(g.nodes.ensure(numNodes * 2)); HIP_TRY(g.nodesF.ensure(numNodes * 4)); HIP_TRY(g.grid.ensure(1)); HIP_TRY(g.tris.ensure(n * 3));
+    HIP_TRY(g.boxMin.ensure(n)); HIP_TRY(g.boxMax.ensure(n)); HIP_TRY(g.parent.ensure(numNodes)); HIP_TRY(g.slotOfPrim.ensure(n)); HIP_TRY(g.red.ensure(8));
+    rc = ensure_build_scratch(s->buildScratch, (uint32_t)n);
+    if (rc != RTR_OK) return rc;
+    t.rebuildReady = true;
+    return RTR_OK;
+}
+
+int rtr_scene_rebuild_async(rtr_scene* s, uint32_t buildFlags) {
+    static const char* who = "rtr_scene_rebuild_async";
+    if (!s) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: null scene", who);
+    if (buildFlags == RTR_BUILD_HOST_SAH) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: buildFlags RTR_BUILD_HOST_SAH: the host builder is host code and cannot be enqueued; only RTR_BUILD_DEVICE_LBVH can", who);
+    if (buildFlags != RTR_BUILD_DEVICE_LBVH) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: unknown buildFlags %u", who, buildFlags);
+    /* nothing of the scene has been read up to here */
+    if (!s->tree.rebuildReady)
+        return fail(RTR_ERR_INVALID_ARGUMENT, "%s: the scene is not prepared for an enqueued rebuild: call rtr_scene_prepare_async_rebuild first (once per scene, and again after a host rebuild)", who);
+    const uint32_t serial = (uint32_t)(s->asyncEnqueued + 1);
+    if (scene_is_empty(s)) { ++s->asyncEnqueued; return RTR_OK; }      /* nothing to build, as the synchronous call */
+    HIP_TRY(hipSetDevice(s->ctx->device));
+    hipStream_t st = s->ctx->stream;
+    SceneTree& t = s->tree;
+    TreeStage& g = s->stage;
+    uint32_t* word = s->asyncWords.p;
+    HIP_TRY(hipMemsetAsync(word, 0xff, sizeof(uint32_t), st));
+    /* the build, into the stage, from the LIVE tables (current after enqueued instance updates and mask changes) and the scene's vertices */
+    const uint32_t n = t.numPrims, numNodes = t.numNodeSlots;
+    rtrdev::BvhDeviceArrays a{};
+    a.nodes = g.nodes.p; a.nodesF = g.nodesF.p; a.grid = g.grid.p; a.tris = g.tris.p; a.boxMin = g.boxMin.p; a.boxMax = g.boxMax.p; a.parent = g.parent.p;
+    a.counters = t.counters.p; a.depth = t.depth.p; a.slotOfPrim = g.slotOfPrim.p; a.red = g.red.p;
+    rtrdev::BvhInputs in{t.prims.p, t.instRefs.p, s->vertices.p, s->indices.p};
+    hipError_t e = rtrdev::bvh_build_lbvh_enqueued(in, n, a, scratch_view(s->buildScratch), st);
+    if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: device BVH build: %s", who, hipGetErrorString(e));
+    /* the commit: all staged arrays over their live twins, unless the stack class would have to rise */
+    rtrdev::CommitTable ct{};
+    auto add = [&](const void* src, void* dst, size_t bytes) { ct.a[ct.count].src = src; ct.a[ct.count].dst = dst; ct.a[ct.count].bytes = bytes; ++ct.count; };
+    add(g.nodesF.p, t.nodesF.p, (size_t)numNodes * 64); add(g.tris.p, t.tris.p, (size_t)n * 48); add(g.nodes.p, t.nodes.p, (size_t)numNodes * 32);
+    add(g.boxMin.p, t.boxMin.p, (size_t)n * 16); add(g.boxMax.p, t.boxMax.p, (size_t)n * 16); add(g.parent.p, t.parent.p, (size_t)numNodes * 4);
+    add(g.slotOfPrim.p, t.slotOfPrim.p, (size_t)n * 4); add(g.grid.p, t.grid.p, sizeof(RtrBvhGrid)); add(g.red.p, t.red.p, 8 * sizeof(uint32_t));
+    e = rtrdev::bvh_commit_tree(ct, g.red.p, t.stats.stackEntries, word, st);
+    if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: commit kernel: %s", who, hipGetErrorString(e));
+    s->mirrorsStale = true; s->depthStale = true;
+    /* the 4-wide view of whatever tree is live now (after a refused commit: the unchanged one, whose bytes these launches reproduce) */
+    e = rtrdev::bvh_make_wide(t.nodes.p, numNodes, t.parent.p, t.grid.p, nullptr, t.nodes4tmp.p, t.wideSums.p, st);
+    if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: 4-wide node build: %s", who, hipGetErrorString(e));
+    e = rtrdev::bvh_wide_order(t.nodes4tmp.p, numNodes, t.wideRemap.p, t.orderScratch.p, s->asyncWords.p + 1, st);
+    if (e == hipSuccess) e = rtrdev::bvh_permute_wide(t.nodes4tmp.p, numNodes, t.wideRemap.p, t.nodes4.p, st);
+    if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: 4-wide node order: %s", who, hipGetErrorString(e));
+    if (t.leafReady) {      /* the leaf order changed: the table is made again where it is (4 B per triangle, nothing to allocate) */
+        HIP_TRY(hipMemsetAsync(t.leafTable.p, 0, t.leafTable.n * sizeof(int32_t), st));
+        e = rtrdev::launch_leaf_table(t.nodes.p, (uint32_t)(t.nodes.n / 2), t.tris.p, (uint32_t)(t.tris.n / 3), s->triCount.p, s->leafBase.p, s->numInstances, t.leafTable.p, st);
+        if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: leaf table: %s", who, hipGetErrorString(e));
+    }
+    e = rtrdev::launch_fold_update_status(word, s->asyncWords.p + 4, serial, st);
+    if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: status kernel: %s", who, hipGetErrorString(e));
+    ++s->asyncEnqueued;
+    return RTR_OK;
+}
+
 /* ---- the cost of the tree, and the rebuild (contracts in rtr.h) ---- */
 /* the integer sums are complete: sah from them in double, in the order rtr.h states (-ffp-contract=off: no fused step) */
 static void finish_tree_cost(rtr_tree_cost* c, const RtrBvhGrid& grid) {
@@ -1438,11 +1555,15 @@ int rtr_scene_rebuild(rtr_scene* s, uint32_t buildFlags) {
     }
     rc = make_wide_nodes(fresh, st);
     if (rc != RTR_OK) return rc;
-    const bool prepared = s->tree.asyncReady;
+    /* the stage outlives a host rebuild, which drops the readiness: a scene that was EVER prepared for the enqueued rebuild is prepared
+     * again by the next rebuild that gives it a device tree */
+    const bool prepared = s->tree.asyncReady, preparedRebuild = s->tree.rebuildReady || s->stage.red.p != nullptr;
     std::swap(s->tree, fresh);      /* `fresh` takes the old tree away: freed on return — the device was joined, and nothing has been enqueued against it since */
     point_at_tree(s->dev, s->tree);
     /* the enqueued update's tables and scratch belong to a tree: made again for the new one (its node count, its leaf slots) */
-    return prepared ? rtr_scene_prepare_async_updates(s) : RTR_OK;
+    if (prepared) { rc = rtr_scene_prepare_async_updates(s); if (rc != RTR_OK) return rc; }
+    /* and the enqueued rebuild's readiness, where the new tree can take a commit: a host tree has other sizes, and stays unprepared */
+    return preparedRebuild && deviceBuild ? rtr_scene_prepare_async_rebuild(s) : RTR_OK;
 }
 
 void rtr_scene_destroy(rtr_scene* s) {

@@ -489,6 +489,52 @@ int  rtr_scene_rebuild(rtr_scene* scene, uint32_t buildFlags);
  * refused tree's depth).  Scenes replicated by librtr_mgpu have no enqueued rebuild, as they have no update path. */
 int  rtr_scene_prepare_async_rebuild(rtr_scene* scene);
 int  rtr_scene_rebuild_async(rtr_scene* scene, uint32_t buildFlags);
+/* The REBUILD POLICY on the device: rtr_scene_rebuild_async behind a decision the device makes, so that a frame loop on a stream neither
+ * rebuilds blindly every N frames nor stops once a frame to look at rtr_scene_tree_cost.  The device evaluates the cost of the live tree,
+ * compares it with the cost right after the last build, and builds only when the comparison says so.
+ * rtr_scene_prepare_async_rebuild_if: ONCE per scene, synchronous; may join and allocate.  It implies (and calls)
+ * rtr_scene_prepare_async_rebuild — the same refusals, the same messages — and allocates the policy's device memory: the eleven words of
+ * the cost kernel and one record of the fields below with the decision word.  builtSah, the BASELINE, is set to the cost of the tree as
+ * it is at this call: exactly rtr_scene_tree_cost's sah.  Idempotent: a second call does not move the baseline.  An empty scene returns
+ * RTR_OK.
+ * rtr_scene_rebuild_if_async: argument checks and launches only — no allocation, no synchronisation, no device -> host copy, no copy from
+ * reusable host memory, everything on the scene's context stream; ORDERING as documented for rtr_scene_update_vertices_async.  Refused
+ * BEFORE anything is enqueued (RTR_ERR_INVALID_ARGUMENT, the message names the function), in this order: a null scene; buildFlags, as
+ * rtr_scene_rebuild_async checks it (before the scene is looked at); a rebuildAbove that is NaN or negative (likewise; +inf is allowed and
+ * means "never", 0.0 means "whenever the cost is positive"); a scene not prepared (the message names
+ * rtr_scene_prepare_async_rebuild_if).  An empty scene returns RTR_OK, counts as enqueued and does nothing.  The call takes the next serial
+ * of the one sequence of rtr_update_status: a skipped rebuild is an enqueued update that was not refused.  The chain:
+ *   cost      the sums of rtr_scene_tree_cost over the live tree, into the policy's words.
+ *   decide    one lane: sah from the words and the live grid's scale, by the very function the host uses (bit for bit rtr_scene_tree_cost's
+ *             sah at that point of the stream); lastSah = sah, evaluated += 1, lastDecision = go = sah > rebuildAbove * builtSah, in double.
+ *   the build, the commit, the 4-wide view and the leaf table of rtr_scene_rebuild_async, every kernel of them GATED by the decision
+ *             word: with go == 0 each returns at once, and no byte a render, a query or a hint reads is written (the build's sort,
+ *             which runs regardless, touches scratch only).  With go == 1 they are rtr_scene_rebuild_async's, with its
+ *             one refusal rule: a staged tree deeper than stats.stackEntries puts its depth into the update word, copies nothing and counts
+ *             as a refused update; the tail then runs on the unchanged tree.
+ *   close     when the commit copied: the cost of the new live tree, builtSah = its sah, rebuilt += 1.  Then the status fold.
+ * THE BASELINE FOLLOWS EVERY BUILD of a prepared scene: rtr_scene_rebuild_async gets the close (without counting in `rebuilt`), predicated on
+ * its own commit; a synchronous rtr_scene_rebuild that gives the scene a device tree prepares the policy again by itself, builtSah being
+ * the new tree's cost, while evaluated and rebuilt keep counting.  After a HOST rebuild the readiness is gone, as for
+ * rtr_scene_rebuild_async, and comes back with the next synchronous device rebuild.  HOST MIRRORS: stale after the call, exactly as after
+ * rtr_scene_rebuild_async — the host cannot know whether the tree changed.
+ * rtr_scene_rebuild_if_status: joins the scene's context stream (only that) and copies the record out.  A scene never prepared reports
+ * zeros and lastDecision = 0xffffffff.  It does not touch rtr_update_status's "first since the last status call" words.
+ * Scenes replicated by librtr_mgpu have no such call, as they have no update path. */
+typedef struct rtr_rebuild_if_status {
+    uint64_t evaluated;     /* rtr_scene_rebuild_if_async calls whose decision kernel has run, since preparation */
+    uint64_t rebuilt;       /* of those, how many built AND committed a new tree */
+    double   builtSah;      /* the baseline: sah of the tree right after its last build */
+    double   lastSah;       /* the sah the last decision looked at (the refitted tree's); 0 before the first */
+    uint32_t lastDecision;  /* 1: the last call built, 0: it skipped, 0xffffffff: none yet */
+    uint32_t _pad[3];
+} rtr_rebuild_if_status;                   /* 48 bytes */
+#ifdef __cplusplus
+static_assert(sizeof(rtr_rebuild_if_status) == 48, "rtr_rebuild_if_status is 48 B");
+#endif
+int  rtr_scene_prepare_async_rebuild_if(rtr_scene* scene);
+int  rtr_scene_rebuild_if_async(rtr_scene* scene, uint32_t buildFlags, double rebuildAbove);
+int  rtr_scene_rebuild_if_status(rtr_scene* scene, rtr_rebuild_if_status* out);
 /* Instance cull masks: VkAccelerationStructureInstanceKHR::mask (reference src/vulkan/raytracing/tlas.cppm:63, instance.setMask(0xFF): the
  * only value the reference uses).  masks: a HOST array, one byte per instance, in instance order (rtr_scene_desc::instances); every new
  * scene — one made by rtr_scene_create_like too — starts with 0xff everywhere.  Only the MASKED ray queries (rtr_trace_rays_masked,

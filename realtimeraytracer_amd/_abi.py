@@ -98,6 +98,13 @@ class rtr_update_status(C.Structure):
     _fields_ = [("enqueued", u64), ("refused", u64), ("firstRefusedUpdate", u32), ("firstBadVertex", u32), ("_pad", u32 * 2)]
 
 
+class rtr_rebuild_if_status(C.Structure):
+    """rtr_scene_rebuild_if_status: rebuild_if_async calls whose decision has run, how many of them built and committed, the baseline
+    (sah of the tree right after its last build), the sah the last decision looked at, and that decision (1 built, 0 skipped,
+    0xffffffff none yet)"""
+    _fields_ = [("evaluated", u64), ("rebuilt", u64), ("builtSah", C.c_double), ("lastSah", C.c_double), ("lastDecision", u32), ("_pad", u32 * 3)]
+
+
 class rtr_tree_cost(C.Structure):
     """rtr_scene_tree_cost / rtr_host_tree_cost: the integer area sums of the quantised BVH2 (x*y, y*z, z*x in grid steps), the two counts,
     and the SAH cost made from them with the grid's scale"""
@@ -159,6 +166,7 @@ assert C.sizeof(RtrRadiance) == 48 and C.sizeof(rtr_light_params) == 32
 assert C.sizeof(rtr_vertex_range) == 24
 assert C.sizeof(rtr_tree_cost) == 96 and C.alignment(rtr_tree_cost) == 8
 assert C.sizeof(rtr_update_status) == 32
+assert C.sizeof(rtr_rebuild_if_status) == 48
 
 # enum rtr_image
 IMAGE_ANALYTIC, IMAGE_SHADOWED, IMAGE_UNSHADOWED = 0, 1, 2
@@ -215,6 +223,9 @@ RTR_SYMBOLS = {
     "rtr_scene_rebuild": (C.c_int, [VP, u32]),
     "rtr_scene_prepare_async_rebuild": (C.c_int, [VP]),
     "rtr_scene_rebuild_async": (C.c_int, [VP, u32]),
+    "rtr_scene_prepare_async_rebuild_if": (C.c_int, [VP]),
+    "rtr_scene_rebuild_if_async": (C.c_int, [VP, u32, C.c_double]),
+    "rtr_scene_rebuild_if_status": (C.c_int, [VP, P(rtr_rebuild_if_status)]),
     "rtr_scene_set_instance_masks": (C.c_int, [VP, VP, u32]),
     "rtr_scene_get_instance_masks": (C.c_int, [VP, VP, u32]),
     "rtr_frame_create": (C.c_int, [VP, u32, u32, u32, P(VP)]),

@@ -106,6 +106,18 @@ class UpdateStatus:
     first_bad_vertex: "int | None"
 
 
+@dataclasses.dataclass(frozen=True)
+class RebuildIfStatus:
+    """Scene.rebuild_if_status(): evaluated — rebuild_if_async calls whose decision has run; rebuilt — how many of them built and
+    committed a new tree; built_sah — the baseline, the sah of the tree right after its last build; last_sah — the sah the last
+    decision looked at (0.0 before the first); last_decision — True: it built, False: it skipped, None: none yet."""
+    evaluated: int
+    rebuilt: int
+    built_sah: float
+    last_sah: float
+    last_decision: "bool | None"
+
+
 class Scene:
     def __init__(self, ctx, desc, like=None):
         """like: a Scene made from the same description whose tree is uploaded instead of built again (rtr_scene_create_like)"""
@@ -113,6 +125,8 @@ class Scene:
         self._async_keep = []         # tensors of enqueued updates: referenced until the next update_status (or the scene's end)
         self._num_lights = int(desc.numLights)
         self._built_sah = None        # tree_cost().sah right after the last build or rebuild: taken on first use (update_vertices' policy)
+        self._policy_ever = False     # prepare_async_rebuild_if succeeded once: a device rebuild prepares the policy again by itself
+        self._policy_ready = False    # ... and no host rebuild has dropped the readiness since: the baseline lives on the device
         self.h = A.VP()
         self._num_instances = int(desc.numInstances)
         self._num_vertices = int(desc.numVertices)
@@ -164,6 +178,7 @@ class Scene:
             raise ValueError(f"rebuild: build must be 'device' or 'host', got {build!r}")
         _check(self.lib.rtr_scene_rebuild(self.h, flags), "rtr_scene_rebuild")
         self._built_sah = self.tree_cost().sah
+        self._policy_ready = self._policy_ever and build == "device"
 
     def update_vertices_or_rebuild(self, ranges, instances=None, lights=None, rebuild_above=None, rebuild_build="device"):
         """update_vertices with a rebuild policy on top; the arguments before rebuild_above are update_vertices' own.
@@ -178,6 +193,8 @@ class Scene:
         rebuild_above = float(rebuild_above)
         if rebuild_build not in ("device", "host"):
             raise ValueError(f"{who}: rebuild_build must be 'device' or 'host', got {rebuild_build!r}")
+        if self._policy_ready:        # the device keeps the baseline, through rebuild_async and rebuild_if_async too: the policies mix
+            self._built_sah = self.rebuild_if_status().built_sah
         if self._built_sah is None:
             self._built_sah = self.tree_cost().sah
         self.update_vertices(ranges, instances, lights)
@@ -200,10 +217,40 @@ class Scene:
         """rtr_scene_rebuild_async: rebuild("device") as stream-ordered work on the context's stream; returns at once, joins nothing.
         Only build="device" can be enqueued.  The device refuses a tree deeper than the stack class the scene renders with
         (stats().stackEntries): update_status() reports it, and the refused rebuild changes nothing.  _built_sah is not refreshed: the
-        cost is not known without a join."""
+        cost is not known without a join.  On a scene prepared with prepare_async_rebuild_if the DEVICE refreshes the baseline
+        (rebuild_if_status().built_sah), which update_vertices_or_rebuild then uses."""
         if build != "device":
             raise ValueError(f"rebuild_async: only build='device' can be enqueued, got {build!r}")
         _check(self.lib.rtr_scene_rebuild_async(self.h, A.BUILD_DEVICE_LBVH), "rtr_scene_rebuild_async")
+
+    def prepare_async_rebuild_if(self):
+        """rtr_scene_prepare_async_rebuild_if: once, synchronously, everything rebuild_if_async must not do later —
+        prepare_async_rebuild, the policy's words on the device, and the baseline: tree_cost().sah of the tree as it is now."""
+        _check(self.lib.rtr_scene_prepare_async_rebuild_if(self.h), "rtr_scene_prepare_async_rebuild_if")
+        self._policy_ever = self._policy_ready = True
+
+    def rebuild_if_async(self, rebuild_above, build="device"):
+        """rtr_scene_rebuild_if_async: the policy of update_vertices_or_rebuild decided ON THE DEVICE, as stream-ordered work; returns at
+        once, joins nothing.  The stream evaluates the tree's sah, and rebuilds — rebuild_async's chain — when it is above
+        rebuild_above * (the sah right after the last build); otherwise the chain's kernels return at once and no byte changes.
+        rebuild_above: a number >= 0; inf never rebuilds, 0.0 rebuilds whenever the cost is positive.  rebuild_if_status() tells
+        what was decided."""
+        if build != "device":
+            raise ValueError(f"rebuild_if_async: only build='device' can be enqueued, got {build!r}")
+        _check(self.lib.rtr_scene_rebuild_if_async(self.h, A.BUILD_DEVICE_LBVH, float(rebuild_above)), "rtr_scene_rebuild_if_async")
+
+    def rebuild_if_status(self):
+        """rtr_scene_rebuild_if_status: joins the context's stream and reports the policy's record -> RebuildIfStatus"""
+        st = A.rtr_rebuild_if_status()
+        _check(self.lib.rtr_scene_rebuild_if_status(self.h, C.byref(st)), "rtr_scene_rebuild_if_status")
+        return RebuildIfStatus(int(st.evaluated), int(st.rebuilt), float(st.builtSah), float(st.lastSah),
+                               None if st.lastDecision == 0xffffffff else bool(st.lastDecision))
+
+    def update_vertices_or_rebuild_async(self, ranges, rebuild_above):
+        """update_vertices_async(ranges), then rebuild_if_async(rebuild_above): update_vertices_or_rebuild with build="device" as
+        stream-ordered work.  Returns nothing: rebuild_if_status() tells what the device decided."""
+        self.update_vertices_async(ranges)
+        self.rebuild_if_async(rebuild_above)
 
     def update_status(self):
         """rtr_scene_update_status: joins the context's stream and reports the enqueued updates -> UpdateStatus.  The tensors of the

@@ -94,27 +94,43 @@ hipError_t bvh_refit_enqueued(const BvhInputs& in, uint32_t numPrims, uint32_t n
 constexpr uint32_t kCommitArrays = 12;
 constexpr uint32_t kCommitMaxBlocks = 1024;
 struct CommitTable { struct { const void* src; void* dst; uint64_t bytes; } a[kCommitArrays]; uint32_t count; };
-hipError_t bvh_build_lbvh_enqueued(const BvhInputs& in, uint32_t numPrims, const BvhDeviceArrays& a, const BvhScratch& t, hipStream_t s);
-hipError_t bvh_commit_tree(const CommitTable& t, const uint32_t* stagedRed, uint32_t limit, uint32_t* word, hipStream_t s);
+hipError_t bvh_build_lbvh_enqueued(const BvhInputs& in, uint32_t numPrims, const BvhDeviceArrays& a, const BvhScratch& t, hipStream_t s, const uint32_t* go = nullptr);
+hipError_t bvh_commit_tree(const CommitTable& t, const uint32_t* stagedRed, uint32_t limit, uint32_t* word, hipStream_t s, const uint32_t* go = nullptr,
+                           uint32_t* committed = nullptr);
+
+/* The rebuild policy on the device (rtr_scene_rebuild_if_async).  THE GATE: the functions above and below that end in `const uint32_t* go`
+ * take a device word the launch is predicated on — null: always (every launch that existed before the policy passes null and gives the
+ * bytes it gave); else every kernel of the function reads *go first and returns at once when it is 0.  The gated build clears its
+ * arrays with gated kernels; the sort and the small memsets of sum words are not gated.  bvh_commit_tree's `committed`, where given, gets 1 when the stage was copied, 0 when not (gate 0, or depth refused).
+ * RebuildIfRecord: rtr_rebuild_if_status's fields in its order; the first two pad words are the chain's two gates.
+ * bvh_rebuild_if_decide (one lane): sah = rtr_tree_sah(words, grid->scale); lastSah = sah, ++evaluated,
+ *   go = lastDecision = sah > rebuildAbove * builtSah, committed = 0.
+ * bvh_rebuild_if_close (one lane): when rec->committed, builtSah = rtr_tree_sah(words, grid->scale) and rebuilt += countRebuilt.
+ * bvh_clear_words: n 32-bit words to zero, gated — a hipMemsetAsync that a skip can switch off. */
+struct RebuildIfRecord { uint64_t evaluated, rebuilt; double builtSah, lastSah; uint32_t lastDecision, go, committed, _pad; };
+hipError_t bvh_rebuild_if_decide(const unsigned long long* words, const RtrBvhGrid* grid, RebuildIfRecord* rec, double rebuildAbove, hipStream_t s);
+hipError_t bvh_rebuild_if_close(const unsigned long long* words, const RtrBvhGrid* grid, RebuildIfRecord* rec, uint32_t countRebuilt, hipStream_t s);
+hipError_t bvh_clear_words(uint32_t* p, uint64_t n, hipStream_t s, const uint32_t* go = nullptr);
 
 /* The 4-wide view of a finished (quantised) tree that the any-hit kernel walks: numNodes x 4 uint4, see k_wide_nodes.
  * parentOrNull: the refit parent array (entries outside the tree are skipped) or null. */
 /* sets grid->wideCentreXY / Z (k_wide_centre_*; sums4 = bvh_wide_scratch_words() x u64 of scratch) and writes the 4-wide records about it */
 size_t bvh_wide_scratch_words();
 /* shapeOrNull: per BVH2 node, which entries its wide record opens (bvh_build.h collapse_wide); null = the greedy rule */
-hipError_t bvh_make_wide(const uint4* nodes, uint32_t numNodes, const int32_t* parentOrNull, RtrBvhGrid* grid, const uint8_t* shapeOrNull, uint4* wide, unsigned long long* sums4, hipStream_t s);
+hipError_t bvh_make_wide(const uint4* nodes, uint32_t numNodes, const int32_t* parentOrNull, RtrBvhGrid* grid, const uint8_t* shapeOrNull, uint4* wide, unsigned long long* sums4, hipStream_t s,
+                         const uint32_t* go = nullptr);
 /* out[remap[i]] = in[i] with inner child codes renumbered through remap (a permutation of 0..numNodes-1, remap[0] == 0) */
-hipError_t bvh_permute_wide(const uint4* in, uint32_t numNodes, const uint32_t* remap, uint4* out, hipStream_t stream);
+hipError_t bvh_permute_wide(const uint4* in, uint32_t numNodes, const uint32_t* remap, uint4* out, hipStream_t stream, const uint32_t* go = nullptr);
 
 /* The permutation bvh_permute_wide takes, made on the device (k_wide_order): the breadth-first order of the 4-wide entries `wide`
  * (un-permuted, child codes in words 12..15), bit for bit what rtr_api.cpp's host loop computes; *reached = the entries the tree reaches.
  * scratch: 2 x numNodes words.  One launch of one workgroup; nothing is read back. */
-hipError_t bvh_wide_order(const uint4* wide, uint32_t numNodes, uint32_t* remap, uint32_t* scratch, uint32_t* reached, hipStream_t s);
+hipError_t bvh_wide_order(const uint4* wide, uint32_t numNodes, uint32_t* remap, uint32_t* scratch, uint32_t* reached, hipStream_t s, const uint32_t* go = nullptr);
 
 /* The SAH cost sums of a finished (quantised) tree, rtr_scene_tree_cost: words = bvh_tree_cost_words() x u64, zeroed here and filled by
  * k_tree_cost as innerArea[3], leafArea[3], rootArea[3], numInner, numLeafRefs (rtr_tree_cost's integers, in that order).
  * parentOrNull: as bvh_make_wide — the refit parent array (slots outside the tree are skipped) or null when every slot is in the tree. */
 size_t bvh_tree_cost_words();
-hipError_t bvh_tree_cost(const uint4* nodes, uint32_t numNodes, const int32_t* parentOrNull, unsigned long long* words, hipStream_t s);
+hipError_t bvh_tree_cost(const uint4* nodes, uint32_t numNodes, const int32_t* parentOrNull, unsigned long long* words, hipStream_t s, const uint32_t* go = nullptr);
 
 }  // namespace rtrdev

@@ -27,6 +27,7 @@
 
 #include "../../../include/rtr_math.h"
 #include "rtr_mirrored.h"
+#include "rtr_tree_sah.h"
 
 namespace rtrdev {
 
@@ -42,7 +43,8 @@ __host__ __device__ inline float ord2f(uint32_t u) {
 /* scene reduction words: [0..2] centroid min (ordered uint), [3..5] centroid max, [6] max |coordinate| (float bits, >= 0) */
 __global__ __launch_bounds__(kB) void k_world_prims(BvhInputs in, uint32_t n, const uint32_t* __restrict__ slotOfPrim,
                                                     float4* __restrict__ triOut, float4* __restrict__ boxMin, float4* __restrict__ boxMax,
-                                                    uint32_t* __restrict__ red) {
+                                                    uint32_t* __restrict__ red, const uint32_t* __restrict__ go) {
+    if (go && *go == 0u) return;                         /* a gated launch whose decision word says no: nothing is read or written */
     const uint32_t p = blockIdx.x * kB + threadIdx.x;
     float cmin[3] = {3.0e38f, 3.0e38f, 3.0e38f}, cmax[3] = {-3.0e38f, -3.0e38f, -3.0e38f}, mabs = 0.f;
     if (p < n) {
@@ -93,7 +95,8 @@ __device__ __forceinline__ uint32_t expand10(uint32_t v) {
 }
 
 __global__ __launch_bounds__(kB) void k_morton(uint32_t n, const float4* __restrict__ boxMin, const float4* __restrict__ boxMax,
-                                               const uint32_t* __restrict__ red, unsigned long long* __restrict__ keys) {
+                                               const uint32_t* __restrict__ red, unsigned long long* __restrict__ keys, const uint32_t* __restrict__ go) {
+    if (go && *go == 0u) return;
     const uint32_t p = blockIdx.x * kB + threadIdx.x;
     if (p >= n) return;
     const float4 a = boxMin[p], b = boxMax[p];
@@ -115,7 +118,8 @@ __global__ __launch_bounds__(kB) void k_morton(uint32_t n, const float4* __restr
 __global__ __launch_bounds__(kB) void k_gather(uint32_t n, const unsigned long long* __restrict__ keys,
                                                const float4* __restrict__ triIn, const float4* __restrict__ minIn, const float4* __restrict__ maxIn,
                                                float4* __restrict__ triOut, float4* __restrict__ minOut, float4* __restrict__ maxOut,
-                                               uint32_t* __restrict__ slotOfPrim) {
+                                               uint32_t* __restrict__ slotOfPrim, const uint32_t* __restrict__ go) {
+    if (go && *go == 0u) return;
     const uint32_t i = blockIdx.x * kB + threadIdx.x;
     if (i >= n) return;
     const uint32_t p = (uint32_t)(keys[i] & 0xffffffffull);
@@ -136,7 +140,8 @@ __device__ __forceinline__ int32_t leaf_code(uint32_t first, uint32_t count) { r
 
 /* one lane per internal node: range, split, children; child codes with <=4-primitive subtrees collapsed to leaves */
 __global__ __launch_bounds__(kB) void k_karras(int n, const unsigned long long* __restrict__ keys, int2* __restrict__ range,
-                                               int2* __restrict__ rawChild /* index, with bit 31 = primitive leaf */) {
+                                               int2* __restrict__ rawChild /* index, with bit 31 = primitive leaf */, const uint32_t* __restrict__ go) {
+    if (go && *go == 0u) return;
     const int i = blockIdx.x * kB + threadIdx.x;
     if (i >= n - 1) return;
     const int d = (lcp(keys, n, i, i + 1) - lcp(keys, n, i, i - 1)) >= 0 ? 1 : -1;
@@ -159,14 +164,16 @@ __global__ __launch_bounds__(kB) void k_karras(int n, const unsigned long long* 
     rawChild[i] = make_int2(lo == gamma ? (gamma | (int)0x80000000) : gamma, hi == gamma + 1 ? ((gamma + 1) | (int)0x80000000) : gamma + 1);
 }
 
-__global__ __launch_bounds__(kB) void k_mark_unused(uint32_t numNodes, int32_t* __restrict__ parent) {
+__global__ __launch_bounds__(kB) void k_mark_unused(uint32_t numNodes, int32_t* __restrict__ parent, const uint32_t* __restrict__ go) {
+    if (go && *go == 0u) return;
     const uint32_t i = blockIdx.x * kB + threadIdx.x;
     if (i < numNodes) parent[i] = -2;
 }
 
 /* child codes in the final node array + parent links for the climb */
 __global__ __launch_bounds__(kB) void k_emit(int n, const int2* __restrict__ range, const int2* __restrict__ rawChild,
-                                             float4* __restrict__ nodes, int32_t* __restrict__ parent) {
+                                             float4* __restrict__ nodes, int32_t* __restrict__ parent, const uint32_t* __restrict__ go) {
+    if (go && *go == 0u) return;
     const int i = blockIdx.x * kB + threadIdx.x;
     if (i >= n - 1) return;
     const int2 r = range[i];
@@ -192,7 +199,8 @@ __global__ __launch_bounds__(kB) void k_emit(int n, const int2* __restrict__ ran
 /* bottom-up fit (build and refit).  counters must be zero on entry; depth[] gets the inner-node height. */
 __global__ __launch_bounds__(kB) void k_fit(uint32_t numNodes, float4* nodes, const float4* __restrict__ boxMin, const float4* __restrict__ boxMax,
                                             const int32_t* __restrict__ parent, uint32_t* counters, uint32_t* depth, const uint32_t* __restrict__ red,
-                                            uint32_t* maxDepthOut) {
+                                            uint32_t* maxDepthOut, const uint32_t* __restrict__ go) {
+    if (go && *go == 0u) return;
     const uint32_t i = blockIdx.x * kB + threadIdx.x;
     if (i >= numNodes) return;
     const int32_t par0 = parent[i];
@@ -250,8 +258,9 @@ __global__ __launch_bounds__(kB) void k_fit(uint32_t numNodes, float4* nodes, co
 }
 
 /* scene grid from the root's two child boxes (one lane) */
-__global__ void k_grid(const float4* __restrict__ nodesF, RtrBvhGrid* grid) {
+__global__ void k_grid(const float4* __restrict__ nodesF, RtrBvhGrid* grid, const uint32_t* __restrict__ go) {
     if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    if (go && *go == 0u) return;
     const float* f = reinterpret_cast<const float*>(nodesF);
     float mn[3], mx[3];
     for (int k = 0; k < 3; ++k) { mn[k] = fminf(f[k], f[6 + k]); mx[k] = fmaxf(f[3 + k], f[9 + k]); }
@@ -262,7 +271,8 @@ __global__ void k_grid(const float4* __restrict__ nodesF, RtrBvhGrid* grid) {
 
 /* fp32 planes -> 16-bit grid coordinates, rounded outward (same arithmetic as rtr::quantize_nodes on the host) */
 __global__ __launch_bounds__(kB) void k_quantize(uint32_t numNodes, const float4* __restrict__ nodesF, const int32_t* __restrict__ parent,
-                                                 const RtrBvhGrid* __restrict__ grid, uint4* __restrict__ nodes) {
+                                                 const RtrBvhGrid* __restrict__ grid, uint4* __restrict__ nodes, const uint32_t* __restrict__ go) {
+    if (go && *go == 0u) return;
     const uint32_t i = blockIdx.x * kB + threadIdx.x;
     if (i >= numNodes) return;
     uint4 w0 = make_uint4(0, 0, 0, 0), w1 = make_uint4(0, 0, 0, 0);
@@ -341,7 +351,8 @@ __device__ __forceinline__ unsigned long long wave_total(unsigned long long v) {
 }
 
 __global__ __launch_bounds__(kB) void k_wide_centre_sum(uint32_t numNodes, const uint4* __restrict__ nodes, const int32_t* __restrict__ parent,
-                                                        unsigned long long* __restrict__ w) {
+                                                        unsigned long long* __restrict__ w, const uint32_t* __restrict__ go) {
+    if (go && *go == 0u) return;
     const uint32_t i = blockIdx.x * kB + threadIdx.x;
     LeafBox lb[2];
     const int nl = leaf_boxes(i, numNodes, nodes, parent, lb);
@@ -360,7 +371,8 @@ __global__ __launch_bounds__(kB) void k_wide_centre_sum(uint32_t numNodes, const
     }
     for (int k = 0; k < 4; ++k) { const unsigned long long t = wave_total(s[k]); if ((threadIdx.x & 63u) == 0 && t) atomicAdd(w + k, t); }
 }
-__global__ void k_wide_centre_candidates(unsigned long long* __restrict__ w) {
+__global__ void k_wide_centre_candidates(unsigned long long* __restrict__ w, const uint32_t* __restrict__ go) {
+    if (go && *go == 0u) return;
     const unsigned long long n = w[3];
     unsigned long long* cand = w + 4 + 3 * kCentreBins;
     for (int k = 0; k < 3; ++k) {
@@ -381,7 +393,8 @@ __global__ void k_wide_centre_candidates(unsigned long long* __restrict__ w) {
 __device__ __forceinline__ uint32_t plane_slack_lo(uint32_t q, uint32_t c) { const int32_t v = (int32_t)q - (int32_t)c; return v >= 0 ? (uint32_t)v - rtr_f16_mag_down((uint32_t)v) : rtr_f16_mag_up((uint32_t)(-v)) - (uint32_t)(-v); }
 __device__ __forceinline__ uint32_t plane_slack_hi(uint32_t q, uint32_t c) { const int32_t v = (int32_t)q - (int32_t)c; return v >= 0 ? rtr_f16_mag_up((uint32_t)v) - (uint32_t)v : (uint32_t)(-v) - rtr_f16_mag_down((uint32_t)(-v)); }
 __global__ __launch_bounds__(kB) void k_wide_centre_cost(uint32_t numNodes, const uint4* __restrict__ nodes, const int32_t* __restrict__ parent,
-                                                         unsigned long long* __restrict__ w) {
+                                                         unsigned long long* __restrict__ w, const uint32_t* __restrict__ go) {
+    if (go && *go == 0u) return;
     const uint32_t i = blockIdx.x * kB + threadIdx.x;
     const unsigned long long* cand = w + 4 + 3 * kCentreBins;
     LeafBox lb[2];
@@ -402,7 +415,8 @@ __global__ __launch_bounds__(kB) void k_wide_centre_cost(uint32_t numNodes, cons
         }
     for (int q = 0; q < 6; ++q) { const unsigned long long t = wave_total(cost[q]); if ((threadIdx.x & 63u) == 0 && t) atomicAdd(w + 4 + 3 * kCentreBins + 6 + q, t); }
 }
-__global__ void k_wide_centre_set(const unsigned long long* __restrict__ w, RtrBvhGrid* grid) {
+__global__ void k_wide_centre_set(const unsigned long long* __restrict__ w, RtrBvhGrid* grid, const uint32_t* __restrict__ go) {
+    if (go && *go == 0u) return;
     const unsigned long long* cand = w + 4 + 3 * kCentreBins;
     const unsigned long long* cost = cand + 6;
     uint32_t c[3];
@@ -428,7 +442,8 @@ __device__ __forceinline__ void area_triple(const uint32_t lo[3], const uint32_t
     t[0] = d[0] * d[1]; t[1] = d[1] * d[2]; t[2] = d[2] * d[0];
 }
 __global__ __launch_bounds__(kB) void k_tree_cost(uint32_t numNodes, const uint4* __restrict__ nodes, const int32_t* __restrict__ parent,
-                                                  unsigned long long* __restrict__ w) {
+                                                  unsigned long long* __restrict__ w, const uint32_t* __restrict__ go) {
+    if (go && *go == 0u) return;
     const uint32_t i = blockIdx.x * kB + threadIdx.x;
     unsigned long long s[8] = {0, 0, 0, 0, 0, 0, 0, 0};      /* inner[3], leaf[3], numInner, numLeafRefs */
     if (i < numNodes && (!parent || parent[i] != -2)) {
@@ -466,7 +481,8 @@ __global__ __launch_bounds__(kB) void k_tree_cost(uint32_t numNodes, const uint4
  * Word layout (16 words = RtrWideNode): per child (xmin|ymin<<16) (xmax|ymax<<16) (zmin|zmax<<16) as half floats about the scene's wide centre (RtrBvhGrid::wideCentreXY / Z),
  * then the four child codes; an empty slot has the code 0x80000000 and an inside-out infinite box. */
 __global__ __launch_bounds__(kB) void k_wide_nodes(uint32_t numNodes, const uint4* __restrict__ nodes, const int32_t* __restrict__ parent,
-                                                   const RtrBvhGrid* __restrict__ grid, const uint8_t* __restrict__ shape, uint4* __restrict__ wide) {
+                                                   const RtrBvhGrid* __restrict__ grid, const uint8_t* __restrict__ shape, uint4* __restrict__ wide, const uint32_t* __restrict__ go) {
+    if (go && *go == 0u) return;
     const uint32_t i = blockIdx.x * kB + threadIdx.x;
     if (i >= numNodes) return;
     uint32_t o[16];
@@ -535,7 +551,8 @@ __global__ __launch_bounds__(kB) void k_wide_nodes(uint32_t numNodes, const uint
 /* Moves the 4-wide entries into the order the host chose (breadth-first from the root: rtr_api.cpp, make_wide_nodes), so the
  * top of the tree is entries 0..K-1 — the part k_shadow_trace4 keeps in LDS.  Inner child codes are renumbered with it. */
 __global__ __launch_bounds__(kB) void k_permute_wide(uint32_t numNodes, const uint4* __restrict__ in, const uint32_t* __restrict__ remap,
-                                                     uint4* __restrict__ out) {
+                                                     uint4* __restrict__ out, const uint32_t* __restrict__ go) {
+    if (go && *go == 0u) return;
     const uint32_t i = blockIdx.x * kB + threadIdx.x;
     if (i >= numNodes) return;
     const size_t dst = (size_t)remap[i] * 4;
@@ -755,11 +772,12 @@ __device__ __forceinline__ uint32_t lanes_before(unsigned long long m) {
 }
 
 __global__ __launch_bounds__(kOrderB) void k_wide_order(const uint4* __restrict__ wide, uint32_t numNodes, uint32_t* __restrict__ remap,
-                                                        uint32_t* __restrict__ claim, uint32_t* __restrict__ order, uint32_t* __restrict__ reachedOut) {
+                                                        uint32_t* __restrict__ claim, uint32_t* __restrict__ order, uint32_t* __restrict__ reachedOut, const uint32_t* __restrict__ go) {
     __shared__ uint32_t sTot[64];
     __shared__ uint32_t sAll;
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     if (blockIdx.x != 0 || numNodes == 0) return;
+    if (go && *go == 0u) return;                         /* the same word in every lane: the whole workgroup leaves before any barrier */
     for (uint32_t i = tid; i < numNodes; i += kOrderB) { remap[i] = i ? 0xffffffffu : 0u; claim[i] = i ? 0xffffffffu : 0u; }
     if (tid == 0) order[0] = 0;
     __syncthreads();
@@ -864,10 +882,18 @@ __global__ __launch_bounds__(kOrderB) void k_wide_order(const uint4* __restrict_
  * table is copied over its live twin: all of it lands or none of it does.
  * One launch over all arrays: the table travels as a kernel argument; a lane moves 16 bytes per trip, the grid is capped
  * (kCommitMaxBlocks) and strides over an array's 16-byte chunks; the up to three words after an array's last whole chunk (4 (n - 1)-byte
- * arrays) are moved by the first lanes of the grid.  Every base is a hipMalloc'd one (256-B aligned), every size a multiple of 4. */
-__global__ __launch_bounds__(kB) void k_commit_tree(CommitTable t, const uint32_t* __restrict__ stagedRed, uint32_t limit, uint32_t* __restrict__ word) {
-    const uint32_t depth = stagedRed[7];
+ * arrays) are moved by the first lanes of the grid.  Every base is a hipMalloc'd one (256-B aligned), every size a multiple of 4.
+ * The gated form (rtr_scene_rebuild_if_async): with *go == 0 nothing was staged, so nothing is copied and nothing is set.  committed, where
+ * given, gets 1 when the arrays are copied and 0 when they are not (skipped or refused): the word the close of the policy is gated by. */
+__global__ __launch_bounds__(kB) void k_commit_tree(CommitTable t, const uint32_t* __restrict__ stagedRed, uint32_t limit, uint32_t* __restrict__ word,
+                                                    const uint32_t* __restrict__ go, uint32_t* __restrict__ committed) {
     const uint32_t g = blockIdx.x * kB + threadIdx.x;
+    if (go && *go == 0u) {
+        if (g == 0 && committed) *committed = 0u;
+        return;
+    }
+    const uint32_t depth = stagedRed[7];
+    if (g == 0 && committed) *committed = depth > limit ? 0u : 1u;
     if (depth > limit) {                                 /* the class would have to rise: refused, and the live tree keeps its bytes */
         if (g == 0) *word = depth;
         return;
@@ -883,8 +909,51 @@ __global__ __launch_bounds__(kB) void k_commit_tree(CommitTable t, const uint32_
     }
 }
 
+/* ---- the rebuild policy on the device (rtr_scene_rebuild_if_async) -----------------------------------------------------------------
+ * The record the policy keeps on the device: the fields of rtr_rebuild_if_status in its order, with the two words the chain is gated by
+ * in the first two pad words.  go: this call builds (the gate of the build, the commit and the tail); committed: its commit copied the
+ * stage (the gate of the close).  One lane each: the kernels between them are ordered by the stream. */
+static_assert(sizeof(RebuildIfRecord) == 48, "layout");
+
+/* decide: sah of the LIVE tree from the words k_tree_cost just summed and the live grid's scale, by the host's function; the comparison
+ * is Scene.update_vertices_or_rebuild's, in double (rebuildAbove = +inf against a zero baseline is NaN, which compares false: never) */
+__global__ void k_rebuild_if_decide(const unsigned long long* __restrict__ words, const RtrBvhGrid* __restrict__ grid, RebuildIfRecord* __restrict__ rec,
+                                    double rebuildAbove) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "layout");
+    uint64_t w[kTreeCostWords];
+    for (uint32_t k = 0; k < kTreeCostWords; ++k) w[k] = words[k];
+    const double sah = rtr_tree_sah(w, grid->scale[0], grid->scale[1], grid->scale[2]);
+    const uint32_t go = sah > rebuildAbove * rec->builtSah ? 1u : 0u;
+    rec->lastSah = sah;
+    rec->evaluated += 1ull;
+    rec->lastDecision = go;
+    rec->go = go;
+    rec->committed = 0u;
+}
+
+/* close: after a commit that copied, the words hold the sums of the NEW live tree (k_tree_cost gated by the same word): its sah is the
+ * baseline from here on.  countRebuilt: 1 for rtr_scene_rebuild_if_async; 0 for rtr_scene_rebuild_async, which moves the baseline only. */
+__global__ void k_rebuild_if_close(const unsigned long long* __restrict__ words, const RtrBvhGrid* __restrict__ grid, RebuildIfRecord* __restrict__ rec,
+                                   uint32_t countRebuilt) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    if (rec->committed == 0u) return;
+    uint64_t w[kTreeCostWords];
+    for (uint32_t k = 0; k < kTreeCostWords; ++k) w[k] = words[k];
+    rec->builtSah = rtr_tree_sah(w, grid->scale[0], grid->scale[1], grid->scale[2]);
+    rec->rebuilt += countRebuilt;
+}
+
+/* a memset that a decision word can switch off (the leaf table's clearing: it must not run without the kernel that refills the table) */
+__global__ __launch_bounds__(kB) void k_clear_words(uint32_t* __restrict__ p, uint64_t n, const uint32_t* __restrict__ go) {
+    if (go && *go == 0u) return;
+    const uint64_t stride = (uint64_t)gridDim.x * kB;
+    for (uint64_t i = (uint64_t)blockIdx.x * kB + threadIdx.x; i < n; i += stride) p[i] = 0u;
+}
+
 /* ---- host-side drivers ------------------------------------------------------------------------------ */
 #define BV_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return e_; } while (0)
+static constexpr const uint32_t* kAlways = nullptr;      /* the gate of a launch that is not gated */
 
 hipError_t launch_check_vertices(const VertexRange* ranges, const uint32_t* prefix, uint32_t numRanges, uint32_t total, uint32_t positionStrideWords,
                                  uint32_t concatBase, uint32_t* firstBad, hipStream_t s) {
@@ -907,10 +976,10 @@ hipError_t bvh_refit(const BvhInputs& in, uint32_t numPrims, uint32_t numNodes, 
     BV_TRY(hipMemsetAsync(a.depth, 0, (size_t)numNodes * sizeof(uint32_t), s));
     uint32_t init[8] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u, 0u, 0u};
     BV_TRY(hipMemcpyAsync(a.red, init, sizeof init, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_world_prims, dim3((numPrims + kB - 1) / kB), dim3(kB), 0, s, in, numPrims, a.slotOfPrim, a.tris, a.boxMin, a.boxMax, a.red);
-    hipLaunchKernelGGL(k_fit, dim3((numNodes + kB - 1) / kB), dim3(kB), 0, s, numNodes, a.nodesF, a.boxMin, a.boxMax, a.parent, a.counters, a.depth, a.red, a.red + 7);
-    hipLaunchKernelGGL(k_grid, dim3(1), dim3(64), 0, s, a.nodesF, a.grid);
-    hipLaunchKernelGGL(k_quantize, dim3((numNodes + kB - 1) / kB), dim3(kB), 0, s, numNodes, a.nodesF, a.parent, a.grid, a.nodes);
+    hipLaunchKernelGGL(k_world_prims, dim3((numPrims + kB - 1) / kB), dim3(kB), 0, s, in, numPrims, a.slotOfPrim, a.tris, a.boxMin, a.boxMax, a.red, kAlways);
+    hipLaunchKernelGGL(k_fit, dim3((numNodes + kB - 1) / kB), dim3(kB), 0, s, numNodes, a.nodesF, a.boxMin, a.boxMax, a.parent, a.counters, a.depth, a.red, a.red + 7, kAlways);
+    hipLaunchKernelGGL(k_grid, dim3(1), dim3(64), 0, s, a.nodesF, a.grid, kAlways);
+    hipLaunchKernelGGL(k_quantize, dim3((numNodes + kB - 1) / kB), dim3(kB), 0, s, numNodes, a.nodesF, a.parent, a.grid, a.nodes, kAlways);
     return hipGetLastError();
 }
 
@@ -964,36 +1033,46 @@ hipError_t bvh_refit_enqueued(const BvhInputs& in, uint32_t numPrims, uint32_t n
     BV_TRY(hipMemsetAsync(a.counters, 0, (size_t)numNodes * sizeof(uint32_t), s));
     BV_TRY(hipMemsetAsync(a.depth, 0, (size_t)numNodes * sizeof(uint32_t), s));
     hipLaunchKernelGGL(k_refit_init, dim3(1), dim3(64), 0, s, a.red);
-    hipLaunchKernelGGL(k_world_prims, dim3((numPrims + kB - 1) / kB), dim3(kB), 0, s, in, numPrims, a.slotOfPrim, a.tris, a.boxMin, a.boxMax, a.red);
-    hipLaunchKernelGGL(k_fit, dim3((numNodes + kB - 1) / kB), dim3(kB), 0, s, numNodes, a.nodesF, a.boxMin, a.boxMax, a.parent, a.counters, a.depth, a.red, a.red + 7);
-    hipLaunchKernelGGL(k_grid, dim3(1), dim3(64), 0, s, a.nodesF, a.grid);
-    hipLaunchKernelGGL(k_quantize, dim3((numNodes + kB - 1) / kB), dim3(kB), 0, s, numNodes, a.nodesF, a.parent, a.grid, a.nodes);
+    hipLaunchKernelGGL(k_world_prims, dim3((numPrims + kB - 1) / kB), dim3(kB), 0, s, in, numPrims, a.slotOfPrim, a.tris, a.boxMin, a.boxMax, a.red, kAlways);
+    hipLaunchKernelGGL(k_fit, dim3((numNodes + kB - 1) / kB), dim3(kB), 0, s, numNodes, a.nodesF, a.boxMin, a.boxMax, a.parent, a.counters, a.depth, a.red, a.red + 7, kAlways);
+    hipLaunchKernelGGL(k_grid, dim3(1), dim3(64), 0, s, a.nodesF, a.grid, kAlways);
+    hipLaunchKernelGGL(k_quantize, dim3((numNodes + kB - 1) / kB), dim3(kB), 0, s, numNodes, a.nodesF, a.parent, a.grid, a.nodes, kAlways);
     return hipGetLastError();
 }
 
-/* bvh_build_lbvh without its host array and with the nodesF memset inside: the same kernels in the same order */
-hipError_t bvh_build_lbvh_enqueued(const BvhInputs& in, uint32_t numPrims, const BvhDeviceArrays& a, const BvhScratch& t, hipStream_t s) {
+/* bvh_build_lbvh without its host array and with the nodesF memset inside: the same kernels in the same order.  go: every kernel of its
+ * own returns at once when the word is 0, and the three clearings (stage and fit scratch) are gated kernels instead of memsets; the sort
+ * (a library's twenty launches over the build scratch, which a device word cannot switch off) runs regardless: nothing else reads what
+ * it writes */
+hipError_t bvh_build_lbvh_enqueued(const BvhInputs& in, uint32_t numPrims, const BvhDeviceArrays& a, const BvhScratch& t, hipStream_t s, const uint32_t* go) {
     const uint32_t n = numPrims, numNodes = n - 1;
-    BV_TRY(hipMemsetAsync(a.nodesF, 0, (size_t)numNodes * 64, s));
-    hipLaunchKernelGGL(k_refit_init, dim3(1), dim3(64), 0, s, a.red);
-    BV_TRY(hipMemsetAsync(a.counters, 0, (size_t)numNodes * sizeof(uint32_t), s));
-    BV_TRY(hipMemsetAsync(a.depth, 0, (size_t)numNodes * sizeof(uint32_t), s));
+    if (go) {      /* gated, the three clearings are kernels too: 18 MB of memsets were a tenth of a skipped chain on the bench scene */
+        BV_TRY(bvh_clear_words(reinterpret_cast<uint32_t*>(a.nodesF), (uint64_t)numNodes * 16, s, go));
+        hipLaunchKernelGGL(k_refit_init, dim3(1), dim3(64), 0, s, a.red);
+        BV_TRY(bvh_clear_words(a.counters, numNodes, s, go));
+        BV_TRY(bvh_clear_words(a.depth, numNodes, s, go));
+    } else {
+        BV_TRY(hipMemsetAsync(a.nodesF, 0, (size_t)numNodes * 64, s));
+        hipLaunchKernelGGL(k_refit_init, dim3(1), dim3(64), 0, s, a.red);
+        BV_TRY(hipMemsetAsync(a.counters, 0, (size_t)numNodes * sizeof(uint32_t), s));
+        BV_TRY(hipMemsetAsync(a.depth, 0, (size_t)numNodes * sizeof(uint32_t), s));
+    }
     const dim3 gp((n + kB - 1) / kB), gn((numNodes + kB - 1) / kB);
-    hipLaunchKernelGGL(k_world_prims, gp, dim3(kB), 0, s, in, n, (const uint32_t*)nullptr, t.trisCanon, t.minCanon, t.maxCanon, a.red);
-    hipLaunchKernelGGL(k_morton, gp, dim3(kB), 0, s, n, t.minCanon, t.maxCanon, a.red, t.keysIn);
+    hipLaunchKernelGGL(k_world_prims, gp, dim3(kB), 0, s, in, n, (const uint32_t*)nullptr, t.trisCanon, t.minCanon, t.maxCanon, a.red, go);
+    hipLaunchKernelGGL(k_morton, gp, dim3(kB), 0, s, n, t.minCanon, t.maxCanon, a.red, t.keysIn, go);
     size_t tempBytes = t.sortTempBytes;
     BV_TRY(hipcub::DeviceRadixSort::SortKeys(t.sortTemp, tempBytes, t.keysIn, t.keysOut, (int)n, 0, 64, s));
-    hipLaunchKernelGGL(k_gather, gp, dim3(kB), 0, s, n, t.keysOut, t.trisCanon, t.minCanon, t.maxCanon, a.tris, a.boxMin, a.boxMax, a.slotOfPrim);
-    hipLaunchKernelGGL(k_karras, gn, dim3(kB), 0, s, (int)n, t.keysOut, t.range, t.rawChild);
-    hipLaunchKernelGGL(k_mark_unused, gn, dim3(kB), 0, s, numNodes, a.parent);
-    hipLaunchKernelGGL(k_emit, gn, dim3(kB), 0, s, (int)n, t.range, t.rawChild, a.nodesF, a.parent);
-    hipLaunchKernelGGL(k_fit, gn, dim3(kB), 0, s, numNodes, a.nodesF, a.boxMin, a.boxMax, a.parent, a.counters, a.depth, a.red, a.red + 7);
-    hipLaunchKernelGGL(k_grid, dim3(1), dim3(64), 0, s, a.nodesF, a.grid);
-    hipLaunchKernelGGL(k_quantize, gn, dim3(kB), 0, s, numNodes, a.nodesF, a.parent, a.grid, a.nodes);
+    hipLaunchKernelGGL(k_gather, gp, dim3(kB), 0, s, n, t.keysOut, t.trisCanon, t.minCanon, t.maxCanon, a.tris, a.boxMin, a.boxMax, a.slotOfPrim, go);
+    hipLaunchKernelGGL(k_karras, gn, dim3(kB), 0, s, (int)n, t.keysOut, t.range, t.rawChild, go);
+    hipLaunchKernelGGL(k_mark_unused, gn, dim3(kB), 0, s, numNodes, a.parent, go);
+    hipLaunchKernelGGL(k_emit, gn, dim3(kB), 0, s, (int)n, t.range, t.rawChild, a.nodesF, a.parent, go);
+    hipLaunchKernelGGL(k_fit, gn, dim3(kB), 0, s, numNodes, a.nodesF, a.boxMin, a.boxMax, a.parent, a.counters, a.depth, a.red, a.red + 7, go);
+    hipLaunchKernelGGL(k_grid, dim3(1), dim3(64), 0, s, a.nodesF, a.grid, go);
+    hipLaunchKernelGGL(k_quantize, gn, dim3(kB), 0, s, numNodes, a.nodesF, a.parent, a.grid, a.nodes, go);
     return hipGetLastError();
 }
 
-hipError_t bvh_commit_tree(const CommitTable& t, const uint32_t* stagedRed, uint32_t limit, uint32_t* word, hipStream_t s) {
+hipError_t bvh_commit_tree(const CommitTable& t, const uint32_t* stagedRed, uint32_t limit, uint32_t* word, hipStream_t s, const uint32_t* go, uint32_t* committed) {
     if (t.count > kCommitArrays) return hipErrorInvalidValue;
     uint64_t chunks = 1;
     for (uint32_t k = 0; k < t.count; ++k) {
@@ -1001,50 +1080,51 @@ hipError_t bvh_commit_tree(const CommitTable& t, const uint32_t* stagedRed, uint
         chunks = t.a[k].bytes >> 4 > chunks ? t.a[k].bytes >> 4 : chunks;
     }
     const uint64_t blocks = (chunks + kB - 1) / kB;
-    hipLaunchKernelGGL(k_commit_tree, dim3((uint32_t)(blocks < kCommitMaxBlocks ? blocks : kCommitMaxBlocks)), dim3(kB), 0, s, t, stagedRed, limit, word);
+    hipLaunchKernelGGL(k_commit_tree, dim3((uint32_t)(blocks < kCommitMaxBlocks ? blocks : kCommitMaxBlocks)), dim3(kB), 0, s, t, stagedRed, limit, word, go, committed);
     return hipGetLastError();
 }
 
-hipError_t bvh_wide_order(const uint4* wide, uint32_t numNodes, uint32_t* remap, uint32_t* scratch, uint32_t* reached, hipStream_t s) {
+hipError_t bvh_wide_order(const uint4* wide, uint32_t numNodes, uint32_t* remap, uint32_t* scratch, uint32_t* reached, hipStream_t s, const uint32_t* go) {
     if (numNodes == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_wide_order, dim3(1), dim3(kOrderB), 0, s, wide, numNodes, remap, scratch, scratch + numNodes, reached);
+    hipLaunchKernelGGL(k_wide_order, dim3(1), dim3(kOrderB), 0, s, wide, numNodes, remap, scratch, scratch + numNodes, reached, go);
     return hipGetLastError();
 }
 
 hipError_t bvh_build_lbvh(const BvhInputs& in, uint32_t numPrims, const BvhDeviceArrays& a, const BvhScratch& t, hipStream_t s) {
+    const uint32_t* const go = kAlways;
     const uint32_t n = numPrims, numNodes = n - 1;
     uint32_t init[8] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u, 0u, 0u};
     BV_TRY(hipMemcpyAsync(a.red, init, sizeof init, hipMemcpyHostToDevice, s));
     BV_TRY(hipMemsetAsync(a.counters, 0, (size_t)numNodes * sizeof(uint32_t), s));
     BV_TRY(hipMemsetAsync(a.depth, 0, (size_t)numNodes * sizeof(uint32_t), s));
     const dim3 gp((n + kB - 1) / kB), gn((numNodes + kB - 1) / kB);
-    hipLaunchKernelGGL(k_world_prims, gp, dim3(kB), 0, s, in, n, (const uint32_t*)nullptr, t.trisCanon, t.minCanon, t.maxCanon, a.red);
-    hipLaunchKernelGGL(k_morton, gp, dim3(kB), 0, s, n, t.minCanon, t.maxCanon, a.red, t.keysIn);
+    hipLaunchKernelGGL(k_world_prims, gp, dim3(kB), 0, s, in, n, (const uint32_t*)nullptr, t.trisCanon, t.minCanon, t.maxCanon, a.red, go);
+    hipLaunchKernelGGL(k_morton, gp, dim3(kB), 0, s, n, t.minCanon, t.maxCanon, a.red, t.keysIn, go);
     size_t tempBytes = t.sortTempBytes;
     BV_TRY(hipcub::DeviceRadixSort::SortKeys(t.sortTemp, tempBytes, t.keysIn, t.keysOut, (int)n, 0, 64, s));
-    hipLaunchKernelGGL(k_gather, gp, dim3(kB), 0, s, n, t.keysOut, t.trisCanon, t.minCanon, t.maxCanon, a.tris, a.boxMin, a.boxMax, a.slotOfPrim);
-    hipLaunchKernelGGL(k_karras, gn, dim3(kB), 0, s, (int)n, t.keysOut, t.range, t.rawChild);
-    hipLaunchKernelGGL(k_mark_unused, gn, dim3(kB), 0, s, numNodes, a.parent);
-    hipLaunchKernelGGL(k_emit, gn, dim3(kB), 0, s, (int)n, t.range, t.rawChild, a.nodesF, a.parent);
-    hipLaunchKernelGGL(k_fit, gn, dim3(kB), 0, s, numNodes, a.nodesF, a.boxMin, a.boxMax, a.parent, a.counters, a.depth, a.red, a.red + 7);
-    hipLaunchKernelGGL(k_grid, dim3(1), dim3(64), 0, s, a.nodesF, a.grid);
-    hipLaunchKernelGGL(k_quantize, gn, dim3(kB), 0, s, numNodes, a.nodesF, a.parent, a.grid, a.nodes);
+    hipLaunchKernelGGL(k_gather, gp, dim3(kB), 0, s, n, t.keysOut, t.trisCanon, t.minCanon, t.maxCanon, a.tris, a.boxMin, a.boxMax, a.slotOfPrim, go);
+    hipLaunchKernelGGL(k_karras, gn, dim3(kB), 0, s, (int)n, t.keysOut, t.range, t.rawChild, go);
+    hipLaunchKernelGGL(k_mark_unused, gn, dim3(kB), 0, s, numNodes, a.parent, go);
+    hipLaunchKernelGGL(k_emit, gn, dim3(kB), 0, s, (int)n, t.range, t.rawChild, a.nodesF, a.parent, go);
+    hipLaunchKernelGGL(k_fit, gn, dim3(kB), 0, s, numNodes, a.nodesF, a.boxMin, a.boxMax, a.parent, a.counters, a.depth, a.red, a.red + 7, go);
+    hipLaunchKernelGGL(k_grid, dim3(1), dim3(64), 0, s, a.nodesF, a.grid, go);
+    hipLaunchKernelGGL(k_quantize, gn, dim3(kB), 0, s, numNodes, a.nodesF, a.parent, a.grid, a.nodes, go);
     return hipGetLastError();
 }
 
-hipError_t bvh_make_wide(const uint4* nodes, uint32_t numNodes, const int32_t* parentOrNull, RtrBvhGrid* grid, const uint8_t* shapeOrNull, uint4* wide, unsigned long long* sums4, hipStream_t s) {
+hipError_t bvh_make_wide(const uint4* nodes, uint32_t numNodes, const int32_t* parentOrNull, RtrBvhGrid* grid, const uint8_t* shapeOrNull, uint4* wide, unsigned long long* sums4, hipStream_t s, const uint32_t* go) {
     BV_TRY(hipMemsetAsync(sums4, 0, kCentreWords * sizeof(unsigned long long), s));
     const dim3 gn((numNodes + kB - 1) / kB);
-    hipLaunchKernelGGL(k_wide_centre_sum, gn, dim3(kB), 0, s, numNodes, nodes, parentOrNull, sums4);
-    hipLaunchKernelGGL(k_wide_centre_candidates, dim3(1), dim3(1), 0, s, sums4);
-    hipLaunchKernelGGL(k_wide_centre_cost, gn, dim3(kB), 0, s, numNodes, nodes, parentOrNull, sums4);
-    hipLaunchKernelGGL(k_wide_centre_set, dim3(1), dim3(1), 0, s, sums4, grid);
-    hipLaunchKernelGGL(k_wide_nodes, dim3((numNodes + kB - 1) / kB), dim3(kB), 0, s, numNodes, nodes, parentOrNull, grid, shapeOrNull, wide);
+    hipLaunchKernelGGL(k_wide_centre_sum, gn, dim3(kB), 0, s, numNodes, nodes, parentOrNull, sums4, go);
+    hipLaunchKernelGGL(k_wide_centre_candidates, dim3(1), dim3(1), 0, s, sums4, go);
+    hipLaunchKernelGGL(k_wide_centre_cost, gn, dim3(kB), 0, s, numNodes, nodes, parentOrNull, sums4, go);
+    hipLaunchKernelGGL(k_wide_centre_set, dim3(1), dim3(1), 0, s, sums4, grid, go);
+    hipLaunchKernelGGL(k_wide_nodes, dim3((numNodes + kB - 1) / kB), dim3(kB), 0, s, numNodes, nodes, parentOrNull, grid, shapeOrNull, wide, go);
     return hipGetLastError();
 }
 
-hipError_t bvh_permute_wide(const uint4* in, uint32_t numNodes, const uint32_t* remap, uint4* out, hipStream_t s) {
-    hipLaunchKernelGGL(k_permute_wide, dim3((numNodes + kB - 1) / kB), dim3(kB), 0, s, numNodes, in, remap, out);
+hipError_t bvh_permute_wide(const uint4* in, uint32_t numNodes, const uint32_t* remap, uint4* out, hipStream_t s, const uint32_t* go) {
+    hipLaunchKernelGGL(k_permute_wide, dim3((numNodes + kB - 1) / kB), dim3(kB), 0, s, numNodes, in, remap, out, go);
     return hipGetLastError();
 }
 
@@ -1052,10 +1132,27 @@ size_t bvh_wide_scratch_words() { return kCentreWords; }
 
 size_t bvh_tree_cost_words() { return kTreeCostWords; }
 
-hipError_t bvh_tree_cost(const uint4* nodes, uint32_t numNodes, const int32_t* parentOrNull, unsigned long long* words, hipStream_t s) {
+hipError_t bvh_tree_cost(const uint4* nodes, uint32_t numNodes, const int32_t* parentOrNull, unsigned long long* words, hipStream_t s, const uint32_t* go) {
     BV_TRY(hipMemsetAsync(words, 0, kTreeCostWords * sizeof(unsigned long long), s));
     if (numNodes == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_tree_cost, dim3((numNodes + kB - 1) / kB), dim3(kB), 0, s, numNodes, nodes, parentOrNull, words);
+    hipLaunchKernelGGL(k_tree_cost, dim3((numNodes + kB - 1) / kB), dim3(kB), 0, s, numNodes, nodes, parentOrNull, words, go);
+    return hipGetLastError();
+}
+
+hipError_t bvh_rebuild_if_decide(const unsigned long long* words, const RtrBvhGrid* grid, RebuildIfRecord* rec, double rebuildAbove, hipStream_t s) {
+    hipLaunchKernelGGL(k_rebuild_if_decide, dim3(1), dim3(64), 0, s, words, grid, rec, rebuildAbove);
+    return hipGetLastError();
+}
+
+hipError_t bvh_rebuild_if_close(const unsigned long long* words, const RtrBvhGrid* grid, RebuildIfRecord* rec, uint32_t countRebuilt, hipStream_t s) {
+    hipLaunchKernelGGL(k_rebuild_if_close, dim3(1), dim3(64), 0, s, words, grid, rec, countRebuilt);
+    return hipGetLastError();
+}
+
+hipError_t bvh_clear_words(uint32_t* p, uint64_t n, hipStream_t s, const uint32_t* go) {
+    if (n == 0) return hipSuccess;
+    const uint64_t blocks = (n + kB - 1) / kB;
+    hipLaunchKernelGGL(k_clear_words, dim3((uint32_t)(blocks < kCommitMaxBlocks ? blocks : kCommitMaxBlocks)), dim3(kB), 0, s, p, n, go);
     return hipGetLastError();
 }
 

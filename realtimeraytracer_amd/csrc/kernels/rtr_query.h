@@ -66,9 +66,10 @@ struct LeafArgs {
     uint32_t numInstances;
     uint32_t n;
 };
-/* fills the table (zeroed by the caller) from the BVH2: nodes as 2 x uint4 apiece, tris as 3 x float4 apiece */
+/* fills the table (zeroed by the caller) from the BVH2: nodes as 2 x uint4 apiece, tris as 3 x float4 apiece.  go: the gate of
+ * rtr_bvh.h — null: always; else a device word, and the kernel does nothing when it is 0 */
 hipError_t launch_leaf_table(const uint4* nodes, uint32_t numNodes, const float4* tris, uint32_t numTris, const uint32_t* triCount,
-                             const uint32_t* base, uint32_t numInstances, int32_t* table, hipStream_t stream);
+                             const uint32_t* base, uint32_t numInstances, int32_t* table, hipStream_t stream, const uint32_t* go = nullptr);
 /* rtr_scene_set_instance_masks: rewrites bits 8..15 of every record's flags word from maskBits[customIndex] (the complement of the
  * instance's mask, already shifted); records whose customIndex is past the table (the dummy record of an empty scene) are left alone */
 hipError_t launch_set_instance_masks(float4* tris, uint32_t numTris, const uint32_t* maskBits, uint32_t numInstances, hipStream_t stream);

@@ -273,7 +273,8 @@ hipError_t launch_hit_surfaces(const DeviceScene& sc, const SurfaceArgs& sa, hip
 constexpr int kLeafTableBlock = 256;
 __global__ __launch_bounds__(kLeafTableBlock) void k_leaf_table(const uint4* __restrict__ nodes, uint32_t numNodes, const float4* __restrict__ tris,
                                                                 uint32_t numTris, const uint32_t* __restrict__ triCount, const uint32_t* __restrict__ base,
-                                                                uint32_t numInstances, int32_t* __restrict__ table) {
+                                                                uint32_t numInstances, int32_t* __restrict__ table, const uint32_t* __restrict__ go) {
+    if (go && *go == 0u) return;                               /* a gated launch (rtr_scene_rebuild_if_async) whose decision word says no */
     const uint32_t i = blockIdx.x * kLeafTableBlock + threadIdx.x;
     if (i >= numNodes) return;
     const uint4 w = nodes[2 * (size_t)i + 1];                  /* {z planes, child[0], child[1]} */
@@ -292,10 +293,10 @@ __global__ __launch_bounds__(kLeafTableBlock) void k_leaf_table(const uint4* __r
 }
 
 hipError_t launch_leaf_table(const uint4* nodes, uint32_t numNodes, const float4* tris, uint32_t numTris, const uint32_t* triCount,
-                             const uint32_t* base, uint32_t numInstances, int32_t* table, hipStream_t s) {
+                             const uint32_t* base, uint32_t numInstances, int32_t* table, hipStream_t s, const uint32_t* go) {
     if (numNodes == 0) return hipSuccess;
     hipLaunchKernelGGL(k_leaf_table, dim3((numNodes + kLeafTableBlock - 1) / kLeafTableBlock), dim3(kLeafTableBlock), 0, s, nodes, numNodes, tris, numTris,
-                       triCount, base, numInstances, table);
+                       triCount, base, numInstances, table, go);
     return hipGetLastError();
 }
 

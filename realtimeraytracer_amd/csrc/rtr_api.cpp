@@ -9,6 +9,7 @@
 #include "kernels/rtr_post.h"
 #include "kernels/rtr_bvh.h"
 #include "kernels/rtr_mirrored.h"
+#include "kernels/rtr_tree_sah.h"
 #include "kernels/rtr_query.h"
 
 #include <hip/hip_runtime.h>
@@ -172,6 +173,9 @@ struct SceneTree {
     /* the enqueued rebuild (rtr_scene_prepare_async_rebuild): this tree has a device build's array sizes, and the scene's stage and
      * build scratch exist.  Here and not on the scene: a new tree starts unprepared (a host rebuild's has other sizes) */
     bool rebuildReady = false;
+    /* the rebuild policy (rtr_scene_prepare_async_rebuild_if): rebuildReady, the scene's policy words exist, and their baseline is the
+     * cost of THIS tree right after it was built */
+    bool rebuildIfReady = false;
     rtr_scene_stats stats{};
 };
 }  // namespace
@@ -210,6 +214,9 @@ struct rtr_scene {
     TreeStage stage;                     /* rtr_scene_prepare_async_rebuild: kept through synchronous rebuilds, like the scratch */
     /* an enqueued rebuild has run (or will) since stats.maxDepth was read back: refresh_mirrors takes it from the live red[7] */
     mutable bool depthStale = false;
+    /* the rebuild policy's device memory (rtr_scene_prepare_async_rebuild_if), the scene's and not the tree's — the counts go on through
+     * a synchronous rebuild: k_tree_cost's eleven words, a pad word, then one rtrdev::RebuildIfRecord (kPolicyRecordAt) */
+    DevBuf<unsigned long long> policy;
     /* the enqueued updates (made by rtr_scene_prepare_async_updates): the words of the enqueued chain — [0] the first bad vertex of the
      * update in flight, [1] the entries the 4-wide tree reaches, [4..6] the sticky status (refused count, serial of the first refused
      * update since the last status call, its first bad vertex).
@@ -228,6 +235,9 @@ struct rtr_scene {
     uint32_t numLights = 0, numObjects = 0, numVertices = 0, numIndices = 0;
     bool hasLtc = false;
 };
+
+constexpr size_t kPolicyRecordAt = 12, kPolicyWords = kPolicyRecordAt + sizeof(rtrdev::RebuildIfRecord) / sizeof(unsigned long long);
+static rtrdev::RebuildIfRecord* policy_record(const rtr_scene* s) { return reinterpret_cast<rtrdev::RebuildIfRecord*>(s->policy.p + kPolicyRecordAt); }
 
 /* no geometry: the host builder's tree of such a scene is one node over one placeholder record */
 static bool scene_is_empty(const rtr_scene* s) { return s->tree.hostTris.empty() || s->tree.hostTris[0].customIndex == 0xffffffffu; }
@@ -1373,6 +1383,60 @@ int rtr_scene_prepare_async_rebuild(rtr_scene* s) {
     return RTR_OK;
 }
 
+/* The chain of an enqueued rebuild, counted as enqueued under `serial`.  go: null — rtr_scene_rebuild_async, every launch as it always
+ * was — or the policy's decision word (rtr_scene_rebuild_if_async): the build's kernels, the commit and the tail do nothing when it is 0.
+ * On a scene prepared for the policy the chain closes with the baseline: the cost of the live tree again, predicated on this chain's own
+ * commit, and the one lane that takes it as builtSah. */
+static int enqueue_rebuild_chain(rtr_scene* s, uint32_t serial, const char* who, const uint32_t* go) {
+    hipStream_t st = s->ctx->stream;
+    SceneTree& t = s->tree;
+    TreeStage& g = s->stage;
+    uint32_t* word = s->asyncWords.p;
+    rtrdev::RebuildIfRecord* rec = t.rebuildIfReady ? policy_record(s) : nullptr;
+    uint32_t* committed = rec ? &rec->committed : nullptr;
+    HIP_TRY(hipMemsetAsync(word, 0xff, sizeof(uint32_t), st));
+    /* the build, into the stage, from the LIVE tables (current after enqueued instance updates and mask changes) and the scene's vertices */
+    const uint32_t n = t.numPrims, numNodes = t.numNodeSlots;
+    rtrdev::BvhDeviceArrays a{};
+    a.nodes = g.nodes.p; a.nodesF = g.nodesF.p; a.grid = g.grid.p; a.tris = g.tris.p; a.boxMin = g.boxMin.p; a.boxMax = g.boxMax.p; a.parent = g.parent.p;
+    a.counters = t.counters.p; a.depth = t.depth.p; a.slotOfPrim = g.slotOfPrim.p; a.red = g.red.p;
+    rtrdev::BvhInputs in{t.prims.p, t.instRefs.p, s->vertices.p, s->indices.p};
+    hipError_t e = rtrdev::bvh_build_lbvh_enqueued(in, n, a, scratch_view(s->buildScratch), st, go);
+    if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: device BVH build: %s", who, hipGetErrorString(e));
+    /* the commit: all staged arrays over their live twins, unless the stack class would have to rise */
+    rtrdev::CommitTable ct{};
+    auto add = [&](const void* src, void* dst, size_t bytes) { ct.a[ct.count].src = src; ct.a[ct.count].dst = dst; ct.a[ct.count].bytes = bytes; ++ct.count; };
+    add(g.nodesF.p, t.nodesF.p, (size_t)numNodes * 64); add(g.tris.p, t.tris.p, (size_t)n * 48); add(g.nodes.p, t.nodes.p, (size_t)numNodes * 32);
+    add(g.boxMin.p, t.boxMin.p, (size_t)n * 16); add(g.boxMax.p, t.boxMax.p, (size_t)n * 16); add(g.parent.p, t.parent.p, (size_t)numNodes * 4);
+    add(g.slotOfPrim.p, t.slotOfPrim.p, (size_t)n * 4); add(g.grid.p, t.grid.p, sizeof(RtrBvhGrid)); add(g.red.p, t.red.p, 8 * sizeof(uint32_t));
+    e = rtrdev::bvh_commit_tree(ct, g.red.p, t.stats.stackEntries, word, st, go, committed);
+    if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: commit kernel: %s", who, hipGetErrorString(e));
+    s->mirrorsStale = true; s->depthStale = true;
+    /* the 4-wide view of whatever tree is live now (after a refused commit: the unchanged one, whose bytes these launches reproduce) */
+    e = rtrdev::bvh_make_wide(t.nodes.p, numNodes, t.parent.p, t.grid.p, nullptr, t.nodes4tmp.p, t.wideSums.p, st, go);
+    if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: 4-wide node build: %s", who, hipGetErrorString(e));
+    e = rtrdev::bvh_wide_order(t.nodes4tmp.p, numNodes, t.wideRemap.p, t.orderScratch.p, s->asyncWords.p + 1, st, go);
+    if (e == hipSuccess) e = rtrdev::bvh_permute_wide(t.nodes4tmp.p, numNodes, t.wideRemap.p, t.nodes4.p, st, go);
+    if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: 4-wide node order: %s", who, hipGetErrorString(e));
+    if (t.leafReady) {      /* the leaf order changed: the table is made again where it is (4 B per triangle, nothing to allocate) */
+        /* gated, the clearing is a kernel: a skip must not clear the table without the launch that fills it again */
+        if (go) e = rtrdev::bvh_clear_words(reinterpret_cast<uint32_t*>(t.leafTable.p), t.leafTable.n, st, go);
+        else HIP_TRY(hipMemsetAsync(t.leafTable.p, 0, t.leafTable.n * sizeof(int32_t), st));
+        if (e == hipSuccess)
+            e = rtrdev::launch_leaf_table(t.nodes.p, (uint32_t)(t.nodes.n / 2), t.tris.p, (uint32_t)(t.tris.n / 3), s->triCount.p, s->leafBase.p, s->numInstances, t.leafTable.p, st, go);
+        if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: leaf table: %s", who, hipGetErrorString(e));
+    }
+    if (rec) {      /* the baseline follows the build: sums of the new live tree and builtSah from them, when this chain's commit copied */
+        e = rtrdev::bvh_tree_cost(t.nodes.p, numNodes, t.parent.p, s->policy.p, st, committed);
+        if (e == hipSuccess) e = rtrdev::bvh_rebuild_if_close(s->policy.p, t.grid.p, rec, go ? 1u : 0u, st);
+        if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: baseline kernels: %s", who, hipGetErrorString(e));
+    }
+    e = rtrdev::launch_fold_update_status(word, s->asyncWords.p + 4, serial, st);
+    if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: status kernel: %s", who, hipGetErrorString(e));
+    ++s->asyncEnqueued;
+    return RTR_OK;
+}
+
 int rtr_scene_rebuild_async(rtr_scene* s, uint32_t buildFlags) {
     static const char* who = "rtr_scene_rebuild_async";
     if (!s) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: null scene", who);
@@ -1384,52 +1448,87 @@ int rtr_scene_rebuild_async(rtr_scene* s, uint32_t buildFlags) {
     const uint32_t serial = (uint32_t)(s->asyncEnqueued + 1);
     if (scene_is_empty(s)) { ++s->asyncEnqueued; return RTR_OK; }      /* nothing to build, as the synchronous call */
     HIP_TRY(hipSetDevice(s->ctx->device));
+    return enqueue_rebuild_chain(s, serial, who, nullptr);
+}
+
+/* ---- the rebuild policy on the device (contract in rtr.h) ---- */
+/* sets the baseline to the cost of the tree as it is now; the counts of a scene that was prepared before go on */
+static int prepare_rebuild_if(rtr_scene* s, const char* who) {
+    int rc = rtr_scene_prepare_async_rebuild(s);
+    if (rc != RTR_OK) return rc;
+    SceneTree& t = s->tree;
+    if (t.rebuildIfReady) return RTR_OK;
+    if (scene_is_empty(s)) { t.rebuildIfReady = true; return RTR_OK; }
+    if (rtrdev::bvh_tree_cost_words() + 1 != kPolicyRecordAt) return fail(RTR_ERR_HIP, "%s: the cost kernel has %zu words, the policy expects 11", who, rtrdev::bvh_tree_cost_words());
+    rtr_tree_cost c{};
+    rc = rtr_scene_tree_cost(s, &c);      /* joins the scene's stream */
+    if (rc != RTR_OK) return rc;
+    hipStream_t st = s->ctx->stream;
+    if (!s->policy.p) {
+        HIP_TRY(s->policy.alloc(kPolicyWords));
+        HIP_TRY(hipMemsetAsync(s->policy.p, 0, kPolicyWords * sizeof(unsigned long long), st));
+        rtrdev::RebuildIfRecord r{};
+        r.builtSah = c.sah; r.lastDecision = 0xffffffffu;
+        HIP_TRY(hipMemcpyAsync(policy_record(s), &r, sizeof r, hipMemcpyHostToDevice, st));
+    } else
+        HIP_TRY(hipMemcpyAsync(&policy_record(s)->builtSah, &c.sah, sizeof c.sah, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));      /* the copies read this frame's variables */
+    t.rebuildIfReady = true;
+    return RTR_OK;
+}
+
+int rtr_scene_prepare_async_rebuild_if(rtr_scene* s) {
+    static const char* who = "rtr_scene_prepare_async_rebuild_if";
+    if (!s) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: null scene", who);
+    return prepare_rebuild_if(s, who);
+}
+
+int rtr_scene_rebuild_if_async(rtr_scene* s, uint32_t buildFlags, double rebuildAbove) {
+    static const char* who = "rtr_scene_rebuild_if_async";
+    if (!s) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: null scene", who);
+    if (buildFlags == RTR_BUILD_HOST_SAH) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: buildFlags RTR_BUILD_HOST_SAH: the host builder is host code and cannot be enqueued; only RTR_BUILD_DEVICE_LBVH can", who);
+    if (buildFlags != RTR_BUILD_DEVICE_LBVH) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: unknown buildFlags %u", who, buildFlags);
+    if (!(rebuildAbove >= 0.0)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: rebuildAbove %g must be a number >= 0 (+inf: never rebuild)", who, rebuildAbove);
+    /* nothing of the scene has been read up to here */
+    if (!s->tree.rebuildIfReady)
+        return fail(RTR_ERR_INVALID_ARGUMENT, "%s: the scene is not prepared for the rebuild policy: call rtr_scene_prepare_async_rebuild_if first (once per scene, and again after a host rebuild)", who);
+    const uint32_t serial = (uint32_t)(s->asyncEnqueued + 1);
+    if (scene_is_empty(s)) { ++s->asyncEnqueued; return RTR_OK; }      /* nothing to look at */
+    HIP_TRY(hipSetDevice(s->ctx->device));
     hipStream_t st = s->ctx->stream;
     SceneTree& t = s->tree;
-    TreeStage& g = s->stage;
-    uint32_t* word = s->asyncWords.p;
-    HIP_TRY(hipMemsetAsync(word, 0xff, sizeof(uint32_t), st));
-    /* the build, into the stage, from the LIVE tables (current after enqueued instance updates and mask changes) and the scene's vertices */
-    const uint32_t n = t.numPrims, numNodes = t.numNodeSlots;
-    rtrdev::BvhDeviceArrays a{};
-    a.nodes = g.nodes.p; a.nodesF = g.nodesF.p; a.grid = g.grid.p; a.tris = g.tris.p; a.boxMin = g.boxMin.p; a.boxMax = g.boxMax.p; a.parent = g.parent.p;
-    a.counters = t.counters.p; a.depth = t.depth.p; a.slotOfPrim = g.slotOfPrim.p; a.red = g.red.p;
-    rtrdev::BvhInputs in{t.prims.p, t.instRefs.p, s->vertices.p, s->indices.p};
-    hipError_t e = rtrdev::bvh_build_lbvh_enqueued(in, n, a, scratch_view(s->buildScratch), st);
-    if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: device BVH build: %s", who, hipGetErrorString(e));
-    /* the commit: all staged arrays over their live twins, unless the stack class would have to rise */
-    rtrdev::CommitTable ct{};
-    auto add = [&](const void* src, void* dst, size_t bytes) { ct.a[ct.count].src = src; ct.a[ct.count].dst = dst; ct.a[ct.count].bytes = bytes; ++ct.count; };
-    add(g.nodesF.p, t.nodesF.p, (size_t)numNodes * 64); add(g.tris.p, t.tris.p, (size_t)n * 48); add(g.nodes.p, t.nodes.p, (size_t)numNodes * 32);
-    add(g.boxMin.p, t.boxMin.p, (size_t)n * 16); add(g.boxMax.p, t.boxMax.p, (size_t)n * 16); add(g.parent.p, t.parent.p, (size_t)numNodes * 4);
-    add(g.slotOfPrim.p, t.slotOfPrim.p, (size_t)n * 4); add(g.grid.p, t.grid.p, sizeof(RtrBvhGrid)); add(g.red.p, t.red.p, 8 * sizeof(uint32_t));
-    e = rtrdev::bvh_commit_tree(ct, g.red.p, t.stats.stackEntries, word, st);
-    if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: commit kernel: %s", who, hipGetErrorString(e));
-    s->mirrorsStale = true; s->depthStale = true;
-    /* the 4-wide view of whatever tree is live now (after a refused commit: the unchanged one, whose bytes these launches reproduce) */
-    e = rtrdev::bvh_make_wide(t.nodes.p, numNodes, t.parent.p, t.grid.p, nullptr, t.nodes4tmp.p, t.wideSums.p, st);
-    if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: 4-wide node build: %s", who, hipGetErrorString(e));
-    e = rtrdev::bvh_wide_order(t.nodes4tmp.p, numNodes, t.wideRemap.p, t.orderScratch.p, s->asyncWords.p + 1, st);
-    if (e == hipSuccess) e = rtrdev::bvh_permute_wide(t.nodes4tmp.p, numNodes, t.wideRemap.p, t.nodes4.p, st);
-    if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: 4-wide node order: %s", who, hipGetErrorString(e));
-    if (t.leafReady) {      /* the leaf order changed: the table is made again where it is (4 B per triangle, nothing to allocate) */
-        HIP_TRY(hipMemsetAsync(t.leafTable.p, 0, t.leafTable.n * sizeof(int32_t), st));
-        e = rtrdev::launch_leaf_table(t.nodes.p, (uint32_t)(t.nodes.n / 2), t.tris.p, (uint32_t)(t.tris.n / 3), s->triCount.p, s->leafBase.p, s->numInstances, t.leafTable.p, st);
-        if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: leaf table: %s", who, hipGetErrorString(e));
-    }
-    e = rtrdev::launch_fold_update_status(word, s->asyncWords.p + 4, serial, st);
-    if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: status kernel: %s", who, hipGetErrorString(e));
-    ++s->asyncEnqueued;
+    rtrdev::RebuildIfRecord* rec = policy_record(s);
+    /* the cost of the live tree and the decision, both on the device */
+    hipError_t e = rtrdev::bvh_tree_cost(t.nodes.p, t.numNodeSlots, t.parent.p, s->policy.p, st);
+    if (e == hipSuccess) e = rtrdev::bvh_rebuild_if_decide(s->policy.p, t.grid.p, rec, rebuildAbove, st);
+    if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: cost and decision kernels: %s", who, hipGetErrorString(e));
+    return enqueue_rebuild_chain(s, serial, who, &rec->go);
+}
+
+int rtr_scene_rebuild_if_status(rtr_scene* s, rtr_rebuild_if_status* out) {
+    static const char* who = "rtr_scene_rebuild_if_status";
+    static_assert(sizeof(rtr_rebuild_if_status) == sizeof(rtrdev::RebuildIfRecord), "layout");
+    if (!s) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: null scene", who);
+    if (!out) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: null out", who);
+    memset(out, 0, sizeof *out);
+    out->lastDecision = 0xffffffffu;
+    if (!s->policy.p) return RTR_OK;      /* never prepared (or empty): nothing was evaluated */
+    HIP_TRY(hipSetDevice(s->ctx->device));
+    hipStream_t st = s->ctx->stream;
+    rtrdev::RebuildIfRecord r{};
+    HIP_TRY(hipMemcpyAsync(&r, policy_record(s), sizeof r, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    out->evaluated = r.evaluated; out->rebuilt = r.rebuilt; out->builtSah = r.builtSah; out->lastSah = r.lastSah; out->lastDecision = r.lastDecision;
     return RTR_OK;
 }
 
 /* ---- the cost of the tree, and the rebuild (contracts in rtr.h) ---- */
 /* the integer sums are complete: sah from them in double, in the order rtr.h states (-ffp-contract=off: no fused step) */
 static void finish_tree_cost(rtr_tree_cost* c, const RtrBvhGrid& grid) {
-    const double sx = grid.scale[0], sy = grid.scale[1], sz = grid.scale[2];
-    auto W = [&](const uint64_t* a) { return (double)a[0] * sx * sy + (double)a[1] * sy * sz + (double)a[2] * sz * sx; };
-    const double root = W(c->rootArea);
-    c->sah = root > 0.0 ? (W(c->innerArea) * 1.0 + W(c->leafArea) * 1.0) / root : 0.0;
+    uint64_t w[11];
+    for (int k = 0; k < 3; ++k) { w[k] = c->innerArea[k]; w[3 + k] = c->leafArea[k]; w[6 + k] = c->rootArea[k]; }
+    w[9] = c->numInner; w[10] = c->numLeafRefs;
+    c->sah = rtr_tree_sah(w, grid.scale[0], grid.scale[1], grid.scale[2]);      /* the device's function too (kernels/rtr_tree_sah.h) */
 }
 
 int rtr_host_tree_cost(const RtrBvhNode* nodes, size_t nodeBytes, const RtrBvhGrid* grid, rtr_tree_cost* out) {
@@ -1558,12 +1657,14 @@ int rtr_scene_rebuild(rtr_scene* s, uint32_t buildFlags) {
     /* the stage outlives a host rebuild, which drops the readiness: a scene that was EVER prepared for the enqueued rebuild is prepared
      * again by the next rebuild that gives it a device tree */
     const bool prepared = s->tree.asyncReady, preparedRebuild = s->tree.rebuildReady || s->stage.red.p != nullptr;
+    const bool preparedPolicy = s->tree.rebuildIfReady || s->policy.p != nullptr;      /* likewise; its baseline becomes the new tree's cost */
     std::swap(s->tree, fresh);      /* `fresh` takes the old tree away: freed on return — the device was joined, and nothing has been enqueued against it since */
     point_at_tree(s->dev, s->tree);
     /* the enqueued update's tables and scratch belong to a tree: made again for the new one (its node count, its leaf slots) */
     if (prepared) { rc = rtr_scene_prepare_async_updates(s); if (rc != RTR_OK) return rc; }
     /* and the enqueued rebuild's readiness, where the new tree can take a commit: a host tree has other sizes, and stays unprepared */
-    return preparedRebuild && deviceBuild ? rtr_scene_prepare_async_rebuild(s) : RTR_OK;
+    if (preparedRebuild && deviceBuild) { rc = rtr_scene_prepare_async_rebuild(s); if (rc != RTR_OK) return rc; }
+    return preparedPolicy && deviceBuild ? prepare_rebuild_if(s, who) : RTR_OK;
 }
 
 void rtr_scene_destroy(rtr_scene* s) {

@@ -719,6 +719,45 @@ int  rtr_trace_rays_masked_async(rtr_ctx* ctx, const rtr_scene* scene, const Rtr
                                  uint32_t flags, uint32_t cullMask, RtrHit* hits, uint8_t* occluded);
 int  rtr_trace_rays_masked(rtr_ctx* ctx, const rtr_scene* scene, const RtrRay* rays, const uint8_t* rayMasks, uint32_t numRays,
                            uint32_t flags, uint32_t cullMask, RtrHit* hits, uint8_t* occluded, rtr_query_stats* stats);
+/* ---- multi-hit queries: the first K hits along a ray, in order, resumable ----
+ * What a Vulkan caller builds from an any-hit shader that records a hit and ignores it: MORE than the nearest surface along a ray —
+ * transmission through layers, thickness and exit-face probes, X-ray and CSG picking, inside/outside by crossing parity, a robust way past
+ * a coincident surface.  One dense route: one ray per lane over the BVH2, the sibling of rtr_trace_rays_masked(RTR_QUERY_CLOSEST).
+ * ACCEPTED SET.  The set of ray k is exactly the records rtr_trace_rays_masked(RTR_QUERY_CLOSEST, the same flags, cullMask and rayMasks)
+ * would consider: those that pass the cull mask, the opacity cull, rtr_mt_intersect with the ray's tmin, t < tmax, the facing cull and the
+ * opacity-map test (unless RTR_QUERY_OPAQUE) — in that order, counted the same way.  A degenerate ray (as in rtr_trace_rays) and a ray
+ * whose effective mask is 0 have an empty set and walk nothing.
+ * RESULT.  hits has numRays * maxHits records, ray-major: ray k's j-th hit is hits[k * maxHits + j].  The count = min(maxHits, |set|)
+ * smallest members by (t, customIndex, primitiveId) — t as float, the ids unsigned: the total order of the closest-hit rule — go,
+ * ascending, into slots 0 .. count-1.  Every slot j >= count is the miss record rtr_trace_rays writes for that ray: t = the ray's own tmax
+ * bits, u = v = 0, both ids 0xffffffff, pad words 0.  counts[k] = count where counts is given.  EVERY slot of every ray is written.
+ * K = 1.  With maxHits == 1 and after == NULL the bytes of hits are those of rtr_trace_rays_masked(..., RTR_QUERY_CLOSEST, ...), and so
+ * are the work counters (numRays, numNodeVisits, numTriTests, numAlphaTests, tailRays): the walk is the closest-hit walk whose far limit
+ * stays tmax until maxHits hits are held and is then the t of the LAST of them, which at 1 is the closest-hit walk itself.
+ * RESUME.  after (may be NULL): one RtrHit per ray.  If after[k].customIndex is 0xffffffff ray k is EXHAUSTED: count 0, all slots miss
+ * records, no walk.  Otherwise only members whose key is STRICTLY greater than after[k]'s (t, customIndex, primitiveId) are reported; tmin
+ * applies unchanged.  A caller passes the previous call's LAST slot of every ray, hits[k * maxHits + maxHits - 1] (gathered into an array of
+ * its own: after must not overlap hits): a miss record there says the ray has no more, a hit says where to go on.  Chained calls then
+ * enumerate a ray's hits exactly once each — exact ties in t included, which re-tracing from t + epsilon skips or repeats — for any
+ * maxHits.  The scene must not change between the calls of a chain (no update, refit, rebuild or mask change): the keys are compared
+ * bit for bit.
+ * FLAGS.  RTR_QUERY_OPAQUE and the four RTR_QUERY_CULL_* bits, with the refusals of every query (both face flags; more than one of
+ * OPAQUE / CULL_OPAQUE / CULL_NO_OPAQUE; bit values 4, 8 and above 0x80).  RTR_QUERY_ANY is refused: an any-hit walk has no order.
+ * cullMask above 8 bits is refused; maxHits == 0 and maxHits > RTR_MULTIHIT_MAX are refused.
+ * POINTERS.  rays, rayMasks, after, hits and counts are DEVICE pointers; rays, after and hits 16-B aligned, counts 4-B aligned; rayMasks,
+ * after and counts may be NULL.  Null, misaligned or other-device arguments are refused as in rtr_trace_rays (RTR_ERR_INVALID_ARGUMENT,
+ * with a message); numRays == 0 does nothing.  A refused call writes nothing.
+ * STREAM ORDER.  Enqueued on ctx's stream; uses the context's fixed query scratch (redo list, control words, spill stacks: a ray that
+ * outgrows the 16-entry stack is walked again from scratch by a tail kernel, and counts in tailRays).  Apart from that scratch's first
+ * use there is no allocation, no join and no copy back, so a chain can be enqueued whole.  rtr_render and every other query are
+ * untouched: they launch the kernels they launched. */
+#define RTR_MULTIHIT_MAX 8u
+int  rtr_trace_rays_multi_async(rtr_ctx* ctx, const rtr_scene* scene, const RtrRay* rays, const uint8_t* rayMasks, uint32_t numRays,
+                                uint32_t maxHits, uint32_t flags, uint32_t cullMask, const RtrHit* after, RtrHit* hits, uint32_t* counts);
+/* The same, then joins ctx's stream (only that stream).  stats (may be NULL): run the counting form of the kernels and fill it. */
+int  rtr_trace_rays_multi(rtr_ctx* ctx, const rtr_scene* scene, const RtrRay* rays, const uint8_t* rayMasks, uint32_t numRays,
+                          uint32_t maxHits, uint32_t flags, uint32_t cullMask, const RtrHit* after, RtrHit* hits, uint32_t* counts,
+                          rtr_query_stats* stats);
 /* ---- queued occlusion queries ----
  * A second way to answer occlusion rays, with the renderer's own any-hit machinery: the rays are binned by direction octant into a
  * queue of ray indices, persistent waves walk the 4-wide tree and refill their finished lanes from it, and the few rays that need a

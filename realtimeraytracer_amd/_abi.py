@@ -185,6 +185,7 @@ BUILD_HOST_SAH, BUILD_DEVICE_LBVH = 0, 1
 QUERY_CLOSEST, QUERY_ANY, QUERY_OPAQUE = 0, 1, 2
 # the culling ray flags of the queries, at Vulkan's bit values (include/rtr.h RTR_QUERY_CULL_*)
 QUERY_CULL_BACK_FACING, QUERY_CULL_FRONT_FACING, QUERY_CULL_OPAQUE, QUERY_CULL_NO_OPAQUE = 0x10, 0x20, 0x40, 0x80
+MULTIHIT_MAX = 8        # RTR_MULTIHIT_MAX: the most hits per ray one rtr_trace_rays_multi call reports
 SURFACE_MISS, SURFACE_OBJECT, SURFACE_LIGHT, SURFACE_INVALID = 0, 1, 2, 3
 LIGHT_SHADOWED, LIGHT_UNSHADOWED, LIGHT_ANALYTIC = 1, 2, 4
 VERTICES_HOST, VERTICES_DEVICE = 0, 1
@@ -256,6 +257,8 @@ RTR_SYMBOLS = {
     "rtr_trace_rays": (C.c_int, [VP, VP, VP, u32, u32, VP, VP, P(rtr_query_stats)]),
     "rtr_trace_rays_masked_async": (C.c_int, [VP, VP, VP, VP, u32, u32, u32, VP, VP]),
     "rtr_trace_rays_masked": (C.c_int, [VP, VP, VP, VP, u32, u32, u32, VP, VP, P(rtr_query_stats)]),
+    "rtr_trace_rays_multi_async": (C.c_int, [VP, VP, VP, VP, u32, u32, u32, u32, VP, VP, VP]),
+    "rtr_trace_rays_multi": (C.c_int, [VP, VP, VP, VP, u32, u32, u32, u32, VP, VP, VP, P(rtr_query_stats)]),
     "rtr_trace_occlusion_masked_async": (C.c_int, [VP, VP, VP, VP, VP, u32, u32, u32, VP, C.c_size_t, VP]),
     "rtr_trace_occlusion_masked": (C.c_int, [VP, VP, VP, VP, VP, u32, u32, u32, VP, C.c_size_t, VP, P(rtr_query_stats)]),
     "rtr_occlusion_scratch_bytes": (C.c_int, [u32, P(C.c_size_t)]),

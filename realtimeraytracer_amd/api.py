@@ -767,6 +767,85 @@ def trace_rays(scene, rays, any_hit=False, opaque=False, collect_stats=False, ct
     return out
 
 
+class MultiHitResult:
+    """What trace_rays_multi gives back.  hits: the (N, K, 8) int32 array of RtrHit records, ray-major — slot j of ray k is its j-th hit by
+    (t, customIndex, primitiveId), slots past counts[k] are the ray's miss record (t = its tmax, ids -1).  counts: (N,) int32.
+    t, u, v (float32) and custom_index, primitive_id (int32) are (N, K) views of hits.  last: the (N, 8) last-slot records, a contiguous
+    copy made on first use — what the next call of a chain takes as `after`.  stats: rtr_query_stats of the counting form, or None."""
+    hits = counts = t = u = v = custom_index = primitive_id = stats = None
+    _last = None
+
+    @property
+    def last(self):
+        if self._last is None:
+            x = self.hits[:, -1, :]
+            self._last = np.ascontiguousarray(x) if isinstance(x, np.ndarray) else x.contiguous()
+        return self._last
+
+
+def trace_rays_multi(scene, rays, max_hits, after=None, opaque=False, ray_flags=0, cull_mask=None, ray_masks=None, collect_stats=False, ctx=None,
+                     asynchronous=False):
+    """rtr_trace_rays_multi: the first max_hits (1 .. A.MULTIHIT_MAX) hits along every ray, in order — the members of the set the
+    closest-hit trace_rays would consider under the same opaque, ray_flags, cull_mask and ray_masks, smallest first by
+    (t, customIndex, primitiveId).  rays, opaque, ray_flags, cull_mask, ray_masks, collect_stats, ctx and asynchronous are trace_rays';
+    numpy rays give numpy results.  With max_hits=1 and no `after` the records are trace_rays(..., cull_mask=0xff)'s, bit for bit.
+    after: None, a MultiHitResult (its .last is taken) or (N, 8) int32 RtrHit records: ray k reports only hits whose key is strictly
+    greater than after[k]'s, and nothing once after[k] is a miss record — so
+        r = trace_rays_multi(scene, rays, 2)
+        while int(r.counts.sum()):
+            ...                                   # r.hits[:, :, :], r.counts
+            r = trace_rays_multi(scene, rays, 2, after=r)
+    enumerates every hit of every ray exactly once, ties in t included.  The scene must not change inside a chain.
+    The hits compose with hit_surfaces as K rays apiece: hit_surfaces(scene, rays.repeat_interleave(K, 0), r.hits.view(-1, 8)) gives the
+    surface of every slot (a miss record gives the sky), ray-major.
+    ValueError before any device work for max_hits outside 1 .. 8, A.QUERY_ANY among ray_flags and the flag combinations Vulkan forbids."""
+    k_hits = int(max_hits)
+    if k_hits < 1 or k_hits > A.MULTIHIT_MAX:
+        raise ValueError(f"trace_rays_multi: max_hits must be 1 .. {A.MULTIHIT_MAX}, got {max_hits!r}")
+    ray_flags = _ray_flags("trace_rays_multi", ray_flags, opaque)
+    torch = _torch()
+    ctx = ctx or scene.ctx
+    dev = torch.device("cuda", ctx.device)
+    r, as_numpy = _device_array(torch, rays, torch.float32, np.float32, "rays", dev, "trace_rays_multi")
+    n = int(r.shape[0])
+    a = None
+    if after is not None:
+        if isinstance(after, MultiHitResult):
+            after = after.last
+        a, an = _device_array(torch, after, torch.int32, np.int32, "after", dev, "trace_rays_multi")
+        if an != as_numpy:
+            raise ValueError("trace_rays_multi: rays and after must both be numpy arrays or both be tensors")
+        if a.shape[0] != n:
+            raise ValueError(f"trace_rays_multi: {n} rays but {a.shape[0]} after records")
+    if asynchronous and collect_stats:
+        raise ValueError("trace_rays_multi: collect_stats needs the synchronous form")
+    if asynchronous and ctx.get_stream() != torch.cuda.current_stream(dev).cuda_stream:
+        raise ValueError("trace_rays_multi: an asynchronous query needs the context on torch's current stream (ctx.set_stream)")
+    rm, cm = _cull_mask_args(torch, "trace_rays_multi", cull_mask, ray_masks, n, dev)
+    flags = (A.QUERY_OPAQUE if opaque else 0) | ray_flags
+    hits = torch.empty((n, k_hits, 8), dtype=torch.int32, device=dev)
+    counts = torch.empty(max(n, 1), dtype=torch.int32, device=dev)[:n]
+    if not asynchronous and ctx.get_stream() != torch.cuda.current_stream(dev).cuda_stream:
+        torch.cuda.current_stream(dev).synchronize()        # the rays (and the outputs' memory) are ready for the context's stream
+    rp, hp, cp = (A.VP(r.data_ptr()), A.VP(hits.data_ptr()), A.VP(counts.data_ptr())) if n else (None, None, None)
+    mp = A.VP(rm.data_ptr()) if rm is not None and n else None
+    ap = A.VP(a.data_ptr()) if a is not None and n else None
+    out = MultiHitResult()
+    if asynchronous:
+        _check(ctx.lib.rtr_trace_rays_multi_async(ctx.h, scene.h, rp, mp, n, k_hits, flags, cm, ap, hp, cp), "rtr_trace_rays_multi_async")
+    else:
+        st = A.rtr_query_stats() if collect_stats else None
+        _check(ctx.lib.rtr_trace_rays_multi(ctx.h, scene.h, rp, mp, n, k_hits, flags, cm, ap, hp, cp, C.byref(st) if st is not None else None),
+               "rtr_trace_rays_multi")
+        out.stats = st
+    out.hits, out.counts = (hits.cpu().numpy(), counts.cpu().numpy()) if as_numpy else (hits, counts)
+    f = out.hits.view(np.float32) if as_numpy else out.hits.view(torch.float32)
+    out.t, out.u, out.v = f[:, :, 0], f[:, :, 1], f[:, :, 2]
+    out.custom_index, out.primitive_id = out.hits[:, :, 3], out.hits[:, :, 4]
+    out._keep = (r, a, rm, hits, counts)     # an asynchronous query's buffers stay alive with its result
+    return out
+
+
 def occlusion_scratch_bytes(lib, n):
     """rtr_occlusion_scratch_bytes: device scratch a queued occlusion query of n rays needs"""
     b = C.c_size_t(0)

@@ -83,6 +83,24 @@ hipError_t launch_query(const DeviceScene& sc, const QueryArgs& qa, uint32_t fla
 /* k_query_tail alone, any-hit form: finishes the rays another walk abandoned — qa.ctrl[kQueryRedoWord] of them, their indices in
  * qa.redoList (or, past qa.redoCap, found by the sentinel in qa.occluded) — over the BVH2 (the queued occlusion query's third stage) */
 hipError_t launch_query_tail_any(const DeviceScene& sc, const QueryArgs& qa, bool alpha, Counters* stats, hipStream_t stream, const RayMaskArgs& rm = RayMaskArgs());
+/* Arguments of the multi-hit query (rtr_trace_rays_multi; kernels/rtr_multihit.hip).  The redo list, the control words and the spill stacks
+ * are the context's query scratch, as in QueryArgs. */
+struct MultiHitArgs {
+    const float4* rays;          /* RtrRay as 2 x float4 */
+    const float4* after;         /* per ray: the RtrHit to resume behind (2 x float4), or null */
+    float4* hits;                /* n * maxHits RtrHit as 2 x float4, ray-major */
+    uint32_t* counts;            /* per ray: hits found, or null */
+    uint32_t n;
+    uint32_t maxHits;            /* K: 1 .. RTR_MULTIHIT_MAX */
+    uint32_t redoCap;            /* entries of redoList the query may use */
+    uint32_t* ctrl;              /* kQueryCtrlWords words, zeroed before the launch */
+    uint32_t* redoList;
+    int32_t* spill;              /* kSpillInts: the tail kernel's full-depth stacks */
+};
+/* k_multihit + k_multihit_tail: the first maxHits members of every ray's accepted set by (t, customIndex, primitiveId), miss records behind
+ * them.  alpha: run the opacity-map test (RTR_QUERY_OPAQUE not given).  rm: the cull mask and the culling flags, always read (the kernels
+ * have the filtered form only; rm.masked bit 0 is not looked at).  stats: the counting form.  hipErrorInvalidValue for a maxHits out of range. */
+hipError_t launch_multihit(const DeviceScene& sc, const MultiHitArgs& ma, bool alpha, Counters* stats, hipStream_t stream, const RayMaskArgs& rm);
 /* The queued occlusion query (rtr_trace_occlusion; kernels/rtr_occlusion.hip): queue build over the rays -> k_shadow_trace4's walk over the
  * 4-wide tree (launch_occlusion_walk) -> k_query_tail.  spill: kSpillInts. */
 hipError_t launch_occlusion(const DeviceScene& sc, const OcclusionArgs& oa, const Tunables& tun, bool alpha, int32_t* spill, Counters* stats,

@@ -2435,6 +2435,74 @@ int rtr_occlusion_scratch_bytes(uint32_t numRays, size_t* bytes) {
 
 static bool aligned4(const void* p) { return ((uintptr_t)p & 3u) == 0; }
 
+/* ---- multi-hit queries (kernels/rtr_multihit.hip) ---- */
+/* the checks and launches of rtr_trace_rays_multi[_async], enqueued on the context's stream; count: the counting form.  The flag and mask
+ * validation is the masked query's; the kernels have the filtered form only, so the call always brings a cull mask. */
+static int enqueue_multihit(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const uint8_t* rayMasks, uint32_t n, uint32_t maxHits, uint32_t flags,
+                            uint32_t cullMask, const RtrHit* after, RtrHit* hits, uint32_t* counts, bool count, const char* who) {
+    if (!c || !s) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: null context or scene", who);
+    if (cullMask & ~0xffu) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: cullMask 0x%x has bits above the low 8 (an instance mask is 8 bits)", who, cullMask);
+    if (const int frc = check_query_flags(flags, who)) return frc;
+    if (flags & RTR_QUERY_ANY) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: RTR_QUERY_ANY is refused: an any-hit walk has no order to report hits in", who);
+    if (maxHits == 0u || maxHits > RTR_MULTIHIT_MAX) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: maxHits %u, 1 to %u", who, maxHits, RTR_MULTIHIT_MAX);
+    if (s->ctx->device != c->device) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: the scene lives on device %d, the context on device %d", who, s->ctx->device, c->device);
+    if (n == 0) return RTR_OK;
+    if (!rays || !hits) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: %s is null", who, !rays ? "rays" : "hits");
+    if (!aligned16(rays) || !aligned16(hits) || !aligned16(after))
+        return fail(RTR_ERR_INVALID_ARGUMENT, "%s: %s is not 16-B aligned", who, !aligned16(rays) ? "rays" : (!aligned16(hits) ? "hits" : "after"));
+    if (!aligned4(counts)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: counts is not 4-B aligned", who);
+    HIP_TRY(hipSetDevice(c->device));
+    const int src = query_scratch(c);
+    if (src != RTR_OK) return src;
+    uint32_t redoCap = rtrdev::kQueryRedoCap;
+#ifdef RTR_TEST_HOOKS
+    if (const char* e = getenv("RTR_QUERY_REDO_CAP")) { const uint64_t v = strtoull(e, nullptr, 10); if (v >= 1 && v < redoCap) redoCap = (uint32_t)v; }   /* a list short enough to overflow */
+#endif
+    hipStream_t st = c->stream;
+    /* the scratch is the context's: a query enqueued on another stream than the last one (rtr_ctx_set_stream) comes behind it */
+    if (c->qLastStream && c->qLastStream != st) HIP_TRY(hipStreamWaitEvent(st, c->qEv[1], 0));
+    HIP_TRY(hipMemsetAsync(c->qCtrl.p, 0, rtrdev::kQueryCtrlWords * sizeof(uint32_t), st));
+    if (count) HIP_TRY(hipMemsetAsync(c->qCounters.p, 0, sizeof(Counters), st));
+    HIP_TRY(hipEventRecord(c->qEv[0], st));
+    rtrdev::MultiHitArgs ma{};
+    ma.rays = reinterpret_cast<const float4*>(rays); ma.after = reinterpret_cast<const float4*>(after); ma.hits = reinterpret_cast<float4*>(hits);
+    ma.counts = counts; ma.n = n; ma.maxHits = maxHits;
+    ma.redoCap = redoCap; ma.ctrl = c->qCtrl.p; ma.redoList = c->qRedo.p; ma.spill = c->qSpill.p;
+    const rtrdev::RayMaskArgs rm = ray_mask_args(CullMask{true, rayMasks, cullMask}, flags);
+    const hipError_t e = rtrdev::launch_multihit(s->dev, ma, (flags & RTR_QUERY_OPAQUE) == 0u, count ? c->qCounters.p : nullptr, st, rm);
+    if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: kernel launch: %s", who, hipGetErrorString(e));
+    HIP_TRY(hipEventRecord(c->qEv[1], st));
+    c->qLastStream = st;
+    return RTR_OK;
+}
+
+int rtr_trace_rays_multi_async(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const uint8_t* rayMasks, uint32_t n, uint32_t maxHits, uint32_t flags,
+                               uint32_t cullMask, const RtrHit* after, RtrHit* hits, uint32_t* counts) {
+    return enqueue_multihit(c, s, rays, rayMasks, n, maxHits, flags, cullMask, after, hits, counts, false, "rtr_trace_rays_multi_async");
+}
+
+int rtr_trace_rays_multi(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const uint8_t* rayMasks, uint32_t n, uint32_t maxHits, uint32_t flags,
+                         uint32_t cullMask, const RtrHit* after, RtrHit* hits, uint32_t* counts, rtr_query_stats* stats) {
+    const int rc = enqueue_multihit(c, s, rays, rayMasks, n, maxHits, flags, cullMask, after, hits, counts, stats != nullptr, "rtr_trace_rays_multi");
+    if (rc != RTR_OK) return rc;
+    if (stats) memset(stats, 0, sizeof *stats);
+    if (n == 0) return RTR_OK;
+    hipStream_t st = c->stream;
+    if (stats) {      /* copies on the context's stream: the call joins that stream only */
+        Counters h;
+        uint32_t ctrl[rtrdev::kQueryCtrlWords];
+        HIP_TRY(hipMemcpyAsync(&h, c->qCounters.p, sizeof h, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(ctrl, c->qCtrl.p, sizeof ctrl, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        stats->numRays = h.rays; stats->numNodeVisits = h.nodes; stats->numTriTests = h.tris; stats->numAlphaTests = h.alphaTests;
+        stats->tailRays = ctrl[rtrdev::kQueryRedoWord];
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, c->qEv[0], c->qEv[1]));
+        stats->ms = ms;
+    } else HIP_TRY(hipStreamSynchronize(st));
+    return RTR_OK;
+}
+
 /* startLeaves: the hints of rtr_trace_occlusion_hinted (null: none; the unhinted calls pass null) */
 static int enqueue_occlusion(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const int32_t* startLeaves, uint32_t n, uint32_t flags, void* scratch,
                              size_t scratchBytes, uint8_t* occluded, bool count, const char* who, const CullMask& cm = NoMask) {

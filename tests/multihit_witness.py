@@ -11,7 +11,12 @@
                         every accepted record of a ray by the float32 restatement of rtr_mt_intersect (ray_flags_witness.mt32, held to
                         oracle_mt's bits by test_ray_flags_abi.py), vectorised over the records: for the rays that graze the 2^19
                         coplanar triangles of test_gpu_query._deep_scene, where no float64 prefilter is conservative and one ctypes
-                        call per (ray, record) pair is out of reach"""
+                        call per (ray, record) pair is out of reach
+  tie_stack_scene, tie_stack_rays, tiny_scenes, tiny_rays
+                        the constructions of tests/test_gpu_multihit_edges.py, held to their design by tests/test_multihit_edges_abi.py:
+                        ties of 20 and 40 records on one t (more than any K), rays for each of the nine compiled walks, windows whose
+                        tmin / tmax sit on a layer, and trees of 1, 2, 8 and 9 triangles
+  tail_rays             which rays of a launch k_multihit abandoned to k_multihit_tail"""
 import ctypes as C
 
 import numpy as np
@@ -59,16 +64,17 @@ def after_key(rec):
     return (w[0:1].view(F32)[0], int(w[3]), int(w[4]))
 
 
-def first_k(cands, classes, rays, k, flags, custom_masks=None, ray_masks=0xff, after=None):
+def first_k(cands, classes, rays, k, flags, custom_masks=None, ray_masks=0xff, after=None, lists=None):
     """the expected (N, k, 8) uint32 RtrHit records and (N,) counts of rtr_trace_rays_multi(maxHits = k): the k smallest accepted
-    members whose key is strictly greater than after[ray]'s (after: (N, 8) records or None), then the ray's miss record"""
+    members whose key is strictly greater than after[ray]'s (after: (N, 8) records or None), then the ray's miss record.
+    lists: accepted(cands, classes, rays, flags, custom_masks, ray_masks) where the caller has it already (a chain asks once per link)"""
     n = len(rays)
     hits = np.zeros((n, k, 8), np.uint32)
     hits[:, :, 0] = np.ascontiguousarray(rays[:, 7]).view(np.uint32)[:, None]
     hits[:, :, 3] = MISS
     hits[:, :, 4] = MISS
     counts = np.zeros(n, np.int64)
-    for r, lst in enumerate(accepted(cands, classes, rays, flags, custom_masks, ray_masks)):
+    for r, lst in enumerate(accepted(cands, classes, rays, flags, custom_masks, ray_masks) if lists is None else lists):
         if after is not None:
             key = after_key(after[r])
             lst = [] if key is None else [e for e in lst if e[0] > key]
@@ -88,23 +94,21 @@ def trivial_classes(cands):
 LAYERS, COPIES, FIRST_COPIED = 12, 4, 3
 
 
-def layered_scene():
-    """(desc, keep): 16 instances of one quad in z = 0 over [-0.5, 0.5]^2 (triangles (0, 1, 2), (0, 2, 3): the shared edge is the
-    diagonal y = x).  Instance i < 12 is translated to z = 0.25 i; instance 12 + j carries the transform of instance 3 + j bit for bit.
-    customIndex = the instance's number; 32 triangles in all."""
-    V = np.zeros((4, 12), F32)
-    V[:, 0:3] = [[-0.5, -0.5, 0.0], [0.5, -0.5, 0.0], [0.5, 0.5, 0.0], [-0.5, 0.5, 0.0]]
+def _instanced_scene(positions, idx, zs, customs):
+    """(desc, keep): one mesh in z = 0 (positions (n, 3), triangles idx), one instance per entry of zs translated to that z — instances of
+    equal z carry one transform bit for bit — under the customIndices given"""
+    V = np.zeros((len(positions), 12), F32)
+    V[:, 0:3] = positions
     V[:, 6] = 1.0                       # the normal: floats 4..6 of the 48-B vertex
     V[:, 8:10] = V[:, 0:2] + F32(0.5)
-    idx = np.array([0, 1, 2, 0, 2, 3], np.uint32)
-    n = LAYERS + COPIES
+    idx = np.array(idx, np.uint32)
+    n = len(zs)
     meshes = (A.RtrMesh * 1)()
-    meshes[0].vertexOffset, meshes[0].indexOffset, meshes[0].vertexCount, meshes[0].indexCount, meshes[0].isOpaque = 0, 0, 4, 6, 1
+    meshes[0].vertexOffset, meshes[0].indexOffset, meshes[0].vertexCount, meshes[0].indexCount, meshes[0].isOpaque = 0, 0, len(V), len(idx), 1
     inst = (A.RtrInstance * n)()
     for i in range(n):
-        inst[i].meshIndex, inst[i].customIndex = 0, i
-        layer = i if i < LAYERS else FIRST_COPIED + (i - LAYERS)
-        for k, val in enumerate((1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0.25 * layer)):
+        inst[i].meshIndex, inst[i].customIndex = 0, int(customs[i])
+        for k, val in enumerate((1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, zs[i])):
             inst[i].transform[k] = float(val)
     objs = (A.RtrObjectInfo * n)()
     for o in objs:
@@ -118,6 +122,17 @@ def layered_scene():
     d.objects, d.numObjects = objs, n
     d.skyColor[0] = d.skyColor[1] = d.skyColor[2] = 0.5
     return d, (V, idx, meshes, inst, objs)
+
+
+QUAD = ([[-0.5, -0.5, 0.0], [0.5, -0.5, 0.0], [0.5, 0.5, 0.0], [-0.5, 0.5, 0.0]], [0, 1, 2, 0, 2, 3])
+
+
+def layered_scene():
+    """(desc, keep): 16 instances of one quad in z = 0 over [-0.5, 0.5]^2 (triangles (0, 1, 2), (0, 2, 3): the shared edge is the
+    diagonal y = x).  Instance i < 12 is translated to z = 0.25 i; instance 12 + j carries the transform of instance 3 + j bit for bit.
+    customIndex = the instance's number; 32 triangles in all."""
+    n = LAYERS + COPIES
+    return _instanced_scene(*QUAD, [0.25 * (i if i < LAYERS else FIRST_COPIED + (i - LAYERS)) for i in range(n)], range(n))
 
 
 GRID = 16
@@ -209,3 +224,132 @@ def all_hits32(bvh, rays, threads=8):
 
     with ThreadPoolExecutor(max(1, int(threads))) as pool:
         return list(pool.map(one, rays))
+
+
+# ---- the tie stack: more than K records on one t -------------------------------------------------------------------------------------
+TIE_DEPTH = 20
+TIE_Z, SINGLE_Z = (0.5, 1.0), (0.0, 0.25, 0.75, 1.25)
+TIE_STACK_Z = [0.0, 0.25] + [0.5] * TIE_DEPTH + [0.75] + [1.0] * TIE_DEPTH + [1.25]      # per instance, in instance order
+UP_Z, DOWN_Z = -1.0, 4.0              # where the grid rays start: t = z - UP_Z going up, DOWN_Z - z coming down, exact in float32
+KIND_UP, KIND_DOWN, KIND_DIAG, KIND_SIGNS, KIND_WINDOW = range(5)
+SIGNS_FIRST = 2 * GRID * GRID + 64    # group (c) starts on a multiple of 64: each of its nine runs of 64 rays is one wave of a launch
+# group (d): (tmin, tmax) as the z of the layer the bound sits on, None: the bound of the grid ray
+WINDOWS = [(0.5, None), (1.0, None), (None, 0.5), (None, 1.0), (0.5, 1.0), (0.25, 1.25), (0.5, 0.5), (0.75, 0.75)]
+WINDOW_PICK = slice(3, None, 8)       # 32 rays of each grid: columns 3 and 11 (inside in x), every row (four of them outside in y)
+
+
+def tie_stack_scene():
+    """(desc, keep): the layered scene's quad in 44 instances — 20 carry one transform bit for bit at z = 0.5, 20 more at z = 1.0,
+    single layers at z = 0, 0.25, 0.75, 1.25.  Every customIndex is distinct: a fixed seeded permutation of the instance order, so
+    storage order and id order disagree.  88 triangles: enough for both builders."""
+    return _instanced_scene(*QUAD, TIE_STACK_Z, np.random.default_rng(20).permutation(len(TIE_STACK_Z)))
+
+
+def sign_pattern(rays):
+    """bit 0, 1, 2: the x, y, z component of the direction is negative (the octant the timed kernels dispatch on)"""
+    return (rays[:, 4] < 0) * 1 + (rays[:, 5] < 0) * 2 + (rays[:, 6] < 0) * 4
+
+
+def tie_stack_rays():
+    """(rays, kinds) for the tie stack:
+      KIND_UP, KIND_DOWN  (a) layered_rays' 16 x 16 grid over [-0.6, 0.6]^2 from z = -1 looking up and from z = 4 looking down;
+      KIND_DIAG           (b) 64 +z rays through points ON the shared diagonal, exact in float32;
+      KIND_SIGNS          (c) from ray SIGNS_FIRST on: for each of the eight direction-sign patterns p = 0 .. 7 (sign_pattern) 64 oblique
+                          rays of that pattern, no component zero, then 64 rays of patterns k mod 8; all through the quads' interior;
+      KIND_WINDOW         (d) for each of WINDOWS, the WINDOW_PICK rays of the up grid and of the down grid with tmin, tmax on layers"""
+    g = np.linspace(-0.6, 0.6, GRID).astype(F32)
+    gx, gy = np.meshgrid(g, g)
+    up = np.zeros((GRID * GRID, 8), F32)
+    up[:, 0], up[:, 1], up[:, 2], up[:, 6], up[:, 7] = gx.ravel(), gy.ravel(), UP_Z, 1.0, 100.0
+    down = up.copy()
+    down[:, 2], down[:, 6] = DOWN_Z, -1.0
+    x = (np.arange(64, dtype=np.float64) + 0.5) / 64.0 - 0.5            # multiples of 2^-7: exact
+    diag = np.zeros((64, 8), F32)
+    diag[:, 0], diag[:, 1], diag[:, 2], diag[:, 6], diag[:, 7] = x, x, UP_Z, 1.0, 100.0
+    rng = np.random.default_rng(77)
+    pattern = np.concatenate([np.repeat(np.arange(8), 64), np.arange(64) % 8])
+    n = len(pattern)
+    target = np.concatenate([rng.uniform(-0.3, 0.3, (n, 2)), np.full((n, 1), 0.625)], 1)      # mid-way through the stack
+    d = np.concatenate([rng.uniform(0.02, 0.12, (n, 2)), np.ones((n, 1))], 1)                 # at most 0.075 sideways on the way out
+    d *= np.where((pattern[:, None] >> np.arange(3)) & 1, -1.0, 1.0)
+    signs = np.zeros((n, 8), F32)
+    signs[:, 0:3], signs[:, 4:7], signs[:, 7] = target - 2.0 * d, d, 100.0
+    wins = []
+    for zmin, zmax in WINDOWS:
+        for src, t_of in ((up, lambda z: z - UP_Z), (down, lambda z: DOWN_Z - z)):
+            w = src[WINDOW_PICK].copy()
+            lo, hi = (zmin, zmax) if src is up else (zmax, zmin)         # coming down, the far layer is the lower one
+            if lo is not None:
+                w[:, 3] = t_of(lo)
+            if hi is not None:
+                w[:, 7] = t_of(hi)
+            wins.append(w)
+    parts = [up, down, diag, signs, np.concatenate(wins)]
+    assert len(up) + len(down) + len(diag) == SIGNS_FIRST and SIGNS_FIRST % 64 == 0
+    return np.concatenate(parts).astype(F32), np.repeat(np.arange(5), [len(p) for p in parts])
+
+
+# ---- tiny trees ----------------------------------------------------------------------------------------------------------------------
+TRIANGLE = ([[-0.5, -0.5, 0.0], [0.5, -0.5, 0.0], [0.0, 0.5, 0.0]], [0, 1, 2])
+TINY_Z, TINY_BEHIND_Z = 1.0, 1.5
+
+
+def tiny_scenes():
+    """{number of triangles: (desc, keep)} for 1, 2, 8 and 9 triangles: bit copies of one triangle in z = 1 under distinct customIndices
+    (a seeded permutation: storage order is not id order), all tied in t; the 9-triangle scene adds one triangle behind the tie, in
+    z = 1.5, under the SMALLEST customIndex.  Up to 8 records fit one leaf; 9 do not."""
+    out = {}
+    for n in (1, 2, 8, 9):
+        tied = min(n, 8)
+        customs = (np.random.default_rng(n).permutation(tied) + (n - tied)).tolist() + [0] * (n - tied)
+        out[n] = _instanced_scene(*TRIANGLE, [TINY_Z] * tied + [TINY_BEHIND_Z] * (n - tied), customs)
+    return out
+
+
+def tiny_rays():
+    """rays for the tiny scenes: a 7 x 7 grid over [-0.6, 0.6]^2 looking up from z = -1 and down from z = 3 (through the triangle and
+    past it), +z rays through points ON each of the three edges and on the three corners (exact in float32), rays that run ALONG the
+    bottom edge inside the triangles' planes (parallel: no hit, but the leaf is reached), and rays far outside the bounds"""
+    g = np.linspace(-0.6, 0.6, 7).astype(F32)
+    gx, gy = np.meshgrid(g, g)
+    up = np.zeros((49, 8), F32)
+    up[:, 0], up[:, 1], up[:, 2], up[:, 6], up[:, 7] = gx.ravel(), gy.ravel(), -1.0, 1.0, 100.0
+    down = up.copy()
+    down[:, 2], down[:, 6] = 3.0, -1.0
+    s = np.arange(9, dtype=np.float64) / 8.0                             # 0 .. 1 in eighths: the corners included
+    a, b, c = (np.array(v[:2]) for v in TRIANGLE[0])
+    pts = np.concatenate([a + s[:, None] * (b - a), b + s[:, None] * (c - b), c + s[:, None] * (a - c)])
+    edge = np.zeros((len(pts), 8), F32)
+    edge[:, 0:2], edge[:, 2], edge[:, 6], edge[:, 7] = pts, -1.0, 1.0, 100.0
+    along = np.zeros((4, 8), F32)
+    along[:, 7] = 100.0
+    along[0, 0:3], along[0, 4] = (-2.0, -0.5, TINY_Z), 1.0
+    along[1, 0:3], along[1, 4] = (2.0, -0.5, TINY_Z), -1.0
+    along[2, 0:3], along[2, 4] = (-2.0, -0.5, TINY_BEHIND_Z), 1.0
+    along[3, 0:3], along[3, 4:6] = (1.5, -2.5, TINY_Z), (-0.5, 1.0)        # the edge (0.5, -0.5) -> (0, 0.5), from two edge lengths before it
+    away = np.zeros((4, 8), F32)
+    away[:, 7] = 100.0
+    away[:, 0:3] = [[5.0, 5.0, -1.0], [-5.0, 0.0, -1.0], [0.0, 0.0, 5.0], [0.0, 0.0, -1.0]]
+    away[:, 4:7] = [[0.0, 0.0, 1.0], [0.0, 0.0, 1.0], [0.0, 0.0, 1.0], [0.0, 0.0, -1.0]]      # beside, beside, behind looking away, in front looking away
+    return np.concatenate([up, down, edge, along, away]).astype(F32)
+
+
+# ---- which rays of a launch took the tail kernel -------------------------------------------------------------------------------------
+def tail_rays(tail_count, n, cap=64, first_groups=32):
+    """indices of up to `cap` rays that k_multihit abandoned.  tail_count(idx) launches the rays idx alone, counting form, and returns
+    stats.tailRays: a group whose tailRays equals its size holds only such rays (a lone deep ray walks for a tenth of a second, so the
+    groups are halved, not the rays asked one by one)"""
+    tail = []
+
+    def collect(idx):
+        if len(tail) >= cap or not len(idx):
+            return
+        c = tail_count(idx)
+        if c == len(idx):
+            tail.extend(int(i) for i in idx)
+        elif c:
+            collect(idx[:len(idx) // 2]); collect(idx[len(idx) // 2:])
+
+    for first in range(0, n, first_groups):
+        collect(np.arange(first, min(first + first_groups, n)))
+    return tail[:cap]

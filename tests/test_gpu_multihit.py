@@ -191,20 +191,11 @@ def test_deep_rays_take_the_tail_kernel(gpu_ctx):
     assert torch.equal(r4.hits[:, 0, :], closest.hits), "slot 0 of K = 4 is the closest hit"
     # which rays were abandoned: a group of rays launched alone whose tailRays equals its size holds only such rays (a lone deep ray
     # walks for a tenth of a second, so the groups are halved, not the rays asked one by one)
-    tail = []
+    def tail_count(idx):
+        sub = rays[torch.from_numpy(idx).to(rays.device)].contiguous()
+        return api.trace_rays_multi(scene, sub, 4, collect_stats=True).stats.tailRays
 
-    def collect(idx):
-        if len(tail) >= 64 or not len(idx):
-            return
-        c = api.trace_rays_multi(scene, rays[idx].contiguous(), 4, collect_stats=True).stats.tailRays
-        if c == len(idx):
-            tail.extend(idx.tolist())
-        elif c:
-            collect(idx[:len(idx) // 2]); collect(idx[len(idx) // 2:])
-
-    for first in range(0, n, 32):
-        collect(torch.arange(first, min(first + 32, n), device=rays.device))
-    tail = tail[:64]
+    tail = M.tail_rays(tail_count, n)
     assert tail and len(tail) <= r4.stats.tailRays
     sub = _np(rays)[tail]
     cands = M.all_hits32(scene.export_bvh(), sub)

@@ -651,23 +651,72 @@ def _join_ctx_stream(ctx, torch, dev):
         torch.cuda.ExternalStream(cs, device=dev).synchronize()
 
 
+def _check_async(ctx, torch, dev, who, asynchronous, collect_stats=False):
+    """what an asynchronous call needs: the context on torch's current stream, so that its results are ordered for torch without a
+    join, and no counting form, which reads back"""
+    if asynchronous and collect_stats:
+        raise ValueError(f"{who}: collect_stats needs the synchronous form")
+    if asynchronous and ctx.get_stream() != torch.cuda.current_stream(dev).cuda_stream:
+        raise ValueError(f"{who}: an asynchronous call needs the context on torch's current stream (ctx.set_stream)")
+
+
+def _join_torchs_stream(ctx, torch, dev, asynchronous=False):
+    """before a synchronous call: the inputs (and the outputs' memory) are ready for the context's stream"""
+    if not asynchronous and ctx.get_stream() != torch.cuda.current_stream(dev).cuda_stream:
+        torch.cuda.current_stream(dev).synchronize()
+
+
+def _ptr(x, n=1):
+    """tensor x's address for the library; null for None and for a call of n = 0 elements"""
+    return A.VP(x.data_ptr()) if x is not None and n else None
+
+
+def _call_query(ctx, name, asynchronous, collect_stats, *args):
+    """lib.<name>_async(*args), or lib.<name>(*args, stats or null) -> the rtr_query_stats of the counting form, else None"""
+    if asynchronous:
+        _check(getattr(ctx.lib, name + "_async")(*args), name + "_async")
+        return None
+    st = A.rtr_query_stats() if collect_stats else None
+    _check(getattr(ctx.lib, name)(*args, C.byref(st) if st is not None else None), name)
+    return st
+
+
+def _device_array(torch, x, dtype, np_dtype, name, dev, who):
+    """an (N, 8) array of 32-bit words on dev: a device tensor as it is (checked), a numpy array copied there"""
+    if isinstance(x, np.ndarray):
+        if x.dtype != np_dtype or x.ndim != 2 or x.shape[1] != 8:
+            raise ValueError(f"{who}: {name} must be {np.dtype(np_dtype)} (N, 8), got {x.dtype} {x.shape}")
+        return torch.from_numpy(np.ascontiguousarray(x)).to(dev), True
+    if isinstance(x, torch.Tensor):
+        if x.dtype != dtype or x.dim() != 2 or x.shape[1] != 8:
+            raise ValueError(f"{who}: {name} must be {dtype} (N, 8), got {x.dtype} {tuple(x.shape)}")
+        if x.device != dev:
+            raise ValueError(f"{who}: {name} live on {x.device}, the context on {dev}")
+        if not x.is_contiguous():
+            raise ValueError(f"{who}: {name} must be contiguous")
+        return x, False
+    raise ValueError(f"{who}: {name} must be a torch tensor or a numpy array, got {type(x).__name__}")
+
+
+def _device_vector(torch, x, dtype, np_dtypes, n, name, dev, who, as_numpy=None):
+    """an (n,) vector of 8- or 32-bit words on dev, or None for None: a device tensor of dtype as it is (checked), a numpy array of one
+    of np_dtypes copied there as the first of them.  as_numpy: whether the rays came as numpy, which x must then do too (None: either)"""
+    if x is None:
+        return None
+    if not isinstance(x, (np.ndarray, torch.Tensor)):
+        raise ValueError(f"{who}: {name} must be a torch tensor or a numpy array, got {type(x).__name__}")
+    is_numpy = isinstance(x, np.ndarray)
+    ok = (x.dtype in np_dtypes) if is_numpy else (x.dtype == dtype and x.device == dev and x.is_contiguous())
+    if not ok or tuple(x.shape) != (n,) or (as_numpy is not None and is_numpy != as_numpy):
+        like = "" if as_numpy is None else ", numpy or tensor as the rays are"
+        raise ValueError(f"{who}: {name} must be {dtype} ({n},), a numpy array or a contiguous tensor on {dev}{like}; got {x.dtype} {tuple(x.shape)}")
+    return torch.from_numpy(np.ascontiguousarray(x).view(np_dtypes[0])).to(dev) if is_numpy else x
+
+
 def _cull_mask_args(torch, who, cull_mask, ray_masks, n, dev):
     """(ray-mask tensor or None, cull mask) of a masked query; cull_mask None -> 0xff.  ray_masks: a contiguous uint8 (N,) tensor on
     dev, or a numpy array, which is uploaded."""
-    cm = 0xff if cull_mask is None else int(cull_mask)
-    rm = None
-    if ray_masks is not None:
-        if isinstance(ray_masks, np.ndarray):
-            if ray_masks.dtype != np.uint8 or ray_masks.shape != (n,):
-                raise ValueError(f"{who}: ray_masks must be uint8 ({n},), got {ray_masks.dtype} {ray_masks.shape}")
-            rm = torch.from_numpy(np.ascontiguousarray(ray_masks)).to(dev)
-        elif isinstance(ray_masks, torch.Tensor):
-            if ray_masks.dtype != torch.uint8 or tuple(ray_masks.shape) != (n,) or ray_masks.device != dev or not ray_masks.is_contiguous():
-                raise ValueError(f"{who}: ray_masks must be a contiguous uint8 ({n},) tensor on {dev}")
-            rm = ray_masks
-        else:
-            raise ValueError(f"{who}: ray_masks must be a torch tensor or a numpy array, got {type(ray_masks).__name__}")
-    return rm, cm
+    return _device_vector(torch, ray_masks, torch.uint8, (np.uint8,), n, "ray_masks", dev, who), 0xff if cull_mask is None else int(cull_mask)
 
 
 def _ray_flags(who, ray_flags, opaque):
@@ -703,25 +752,8 @@ def trace_rays(scene, rays, any_hit=False, opaque=False, collect_stats=False, ct
     torch = _torch()
     ctx = ctx or scene.ctx
     dev = torch.device("cuda", ctx.device)
-    as_numpy = isinstance(rays, np.ndarray)
-    if as_numpy:
-        if rays.dtype != np.float32 or rays.ndim != 2 or rays.shape[1] != 8:
-            raise ValueError(f"trace_rays: rays must be float32 (N, 8), got {rays.dtype} {rays.shape}")
-        r = torch.from_numpy(np.ascontiguousarray(rays)).to(dev)
-    elif isinstance(rays, torch.Tensor):
-        if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8:
-            raise ValueError(f"trace_rays: rays must be float32 (N, 8), got {rays.dtype} {tuple(rays.shape)}")
-        if rays.device != dev:
-            raise ValueError(f"trace_rays: rays live on {rays.device}, the context on {dev}")
-        if not rays.is_contiguous():
-            raise ValueError("trace_rays: rays must be contiguous")
-        r = rays
-    else:
-        raise ValueError(f"trace_rays: rays must be a torch tensor or a numpy array, got {type(rays).__name__}")
-    if asynchronous and collect_stats:
-        raise ValueError("trace_rays: collect_stats needs the synchronous form")
-    if asynchronous and ctx.get_stream() != torch.cuda.current_stream(dev).cuda_stream:
-        raise ValueError("trace_rays: an asynchronous query needs the context on torch's current stream (ctx.set_stream)")
+    r, as_numpy = _device_array(torch, rays, torch.float32, np.float32, "rays", dev, "trace_rays")
+    _check_async(ctx, torch, dev, "trace_rays", asynchronous, collect_stats)
     n = int(r.shape[0])
     flags = (A.QUERY_ANY if any_hit else A.QUERY_CLOSEST) | (A.QUERY_OPAQUE if opaque else 0) | ray_flags
     hits = occ = None
@@ -729,28 +761,15 @@ def trace_rays(scene, rays, any_hit=False, opaque=False, collect_stats=False, ct
         occ = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)[:n]
     else:
         hits = torch.empty((n, 8), dtype=torch.int32, device=dev)
-    if not asynchronous and ctx.get_stream() != torch.cuda.current_stream(dev).cuda_stream:
-        torch.cuda.current_stream(dev).synchronize()        # the rays (and the outputs' memory) are ready for the context's stream
-    hp = A.VP(hits.data_ptr()) if hits is not None and n else None
-    op = A.VP(occ.data_ptr()) if occ is not None and n else None
-    rp = A.VP(r.data_ptr()) if n else None
+    _join_torchs_stream(ctx, torch, dev, asynchronous)
     out = QueryResult()
     rm = None
     if cull_mask is not None or ray_masks is not None:
         rm, cm = _cull_mask_args(torch, "trace_rays", cull_mask, ray_masks, n, dev)
-        mp = A.VP(rm.data_ptr()) if rm is not None and n else None
-        if asynchronous:
-            _check(ctx.lib.rtr_trace_rays_masked_async(ctx.h, scene.h, rp, mp, n, flags, cm, hp, op), "rtr_trace_rays_masked_async")
-        else:
-            st = A.rtr_query_stats() if collect_stats else None
-            _check(ctx.lib.rtr_trace_rays_masked(ctx.h, scene.h, rp, mp, n, flags, cm, hp, op, C.byref(st) if st is not None else None), "rtr_trace_rays_masked")
-            out.stats = st
-    elif asynchronous:
-        _check(ctx.lib.rtr_trace_rays_async(ctx.h, scene.h, rp, n, flags, hp, op), "rtr_trace_rays_async")
+        name, args = "rtr_trace_rays_masked", (_ptr(r, n), _ptr(rm, n), n, flags, cm, _ptr(hits, n), _ptr(occ, n))
     else:
-        st = A.rtr_query_stats() if collect_stats else None
-        _check(ctx.lib.rtr_trace_rays(ctx.h, scene.h, rp, n, flags, hp, op, C.byref(st) if st is not None else None), "rtr_trace_rays")
-        out.stats = st
+        name, args = "rtr_trace_rays", (_ptr(r, n), n, flags, _ptr(hits, n), _ptr(occ, n))
+    out.stats = _call_query(ctx, name, asynchronous, collect_stats, ctx.h, scene.h, *args)
     if any_hit:
         out.occluded = occ
     else:
@@ -817,27 +836,15 @@ def trace_rays_multi(scene, rays, max_hits, after=None, opaque=False, ray_flags=
             raise ValueError("trace_rays_multi: rays and after must both be numpy arrays or both be tensors")
         if a.shape[0] != n:
             raise ValueError(f"trace_rays_multi: {n} rays but {a.shape[0]} after records")
-    if asynchronous and collect_stats:
-        raise ValueError("trace_rays_multi: collect_stats needs the synchronous form")
-    if asynchronous and ctx.get_stream() != torch.cuda.current_stream(dev).cuda_stream:
-        raise ValueError("trace_rays_multi: an asynchronous query needs the context on torch's current stream (ctx.set_stream)")
+    _check_async(ctx, torch, dev, "trace_rays_multi", asynchronous, collect_stats)
     rm, cm = _cull_mask_args(torch, "trace_rays_multi", cull_mask, ray_masks, n, dev)
     flags = (A.QUERY_OPAQUE if opaque else 0) | ray_flags
     hits = torch.empty((n, k_hits, 8), dtype=torch.int32, device=dev)
     counts = torch.empty(max(n, 1), dtype=torch.int32, device=dev)[:n]
-    if not asynchronous and ctx.get_stream() != torch.cuda.current_stream(dev).cuda_stream:
-        torch.cuda.current_stream(dev).synchronize()        # the rays (and the outputs' memory) are ready for the context's stream
-    rp, hp, cp = (A.VP(r.data_ptr()), A.VP(hits.data_ptr()), A.VP(counts.data_ptr())) if n else (None, None, None)
-    mp = A.VP(rm.data_ptr()) if rm is not None and n else None
-    ap = A.VP(a.data_ptr()) if a is not None and n else None
+    _join_torchs_stream(ctx, torch, dev, asynchronous)
     out = MultiHitResult()
-    if asynchronous:
-        _check(ctx.lib.rtr_trace_rays_multi_async(ctx.h, scene.h, rp, mp, n, k_hits, flags, cm, ap, hp, cp), "rtr_trace_rays_multi_async")
-    else:
-        st = A.rtr_query_stats() if collect_stats else None
-        _check(ctx.lib.rtr_trace_rays_multi(ctx.h, scene.h, rp, mp, n, k_hits, flags, cm, ap, hp, cp, C.byref(st) if st is not None else None),
-               "rtr_trace_rays_multi")
-        out.stats = st
+    out.stats = _call_query(ctx, "rtr_trace_rays_multi", asynchronous, collect_stats, ctx.h, scene.h, _ptr(r, n), _ptr(rm, n), n, k_hits, flags, cm, _ptr(a, n),
+                            _ptr(hits, n), _ptr(counts, n))
     out.hits, out.counts = (hits.cpu().numpy(), counts.cpu().numpy()) if as_numpy else (hits, counts)
     f = out.hits.view(np.float32) if as_numpy else out.hits.view(torch.float32)
     out.t, out.u, out.v = f[:, :, 0], f[:, :, 1], f[:, :, 2]
@@ -867,75 +874,28 @@ def trace_occlusion(scene, rays, opaque=False, collect_stats=False, ctx=None, as
     torch = _torch()
     ctx = ctx or scene.ctx
     dev = torch.device("cuda", ctx.device)
-    as_numpy = isinstance(rays, np.ndarray)
-    if as_numpy:
-        if rays.dtype != np.float32 or rays.ndim != 2 or rays.shape[1] != 8:
-            raise ValueError(f"trace_occlusion: rays must be float32 (N, 8), got {rays.dtype} {rays.shape}")
-        r = torch.from_numpy(np.ascontiguousarray(rays)).to(dev)
-    elif isinstance(rays, torch.Tensor):
-        if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8:
-            raise ValueError(f"trace_occlusion: rays must be float32 (N, 8), got {rays.dtype} {tuple(rays.shape)}")
-        if rays.device != dev:
-            raise ValueError(f"trace_occlusion: rays live on {rays.device}, the context on {dev}")
-        if not rays.is_contiguous():
-            raise ValueError("trace_occlusion: rays must be contiguous")
-        r = rays
-    else:
-        raise ValueError(f"trace_occlusion: rays must be a torch tensor or a numpy array, got {type(rays).__name__}")
-    if asynchronous and collect_stats:
-        raise ValueError("trace_occlusion: collect_stats needs the synchronous form")
-    if asynchronous and ctx.get_stream() != torch.cuda.current_stream(dev).cuda_stream:
-        raise ValueError("trace_occlusion: an asynchronous query needs the context on torch's current stream (ctx.set_stream)")
+    r, as_numpy = _device_array(torch, rays, torch.float32, np.float32, "rays", dev, "trace_occlusion")
+    _check_async(ctx, torch, dev, "trace_occlusion", asynchronous, collect_stats)
     n = int(r.shape[0])
-    sl = None
-    if start_leaves is not None:
-        if isinstance(start_leaves, np.ndarray):
-            if not as_numpy or start_leaves.dtype != np.int32 or start_leaves.shape != (n,):
-                raise ValueError(f"trace_occlusion: start_leaves must be int32 ({n},), numpy like the rays; got {start_leaves.dtype} {start_leaves.shape}")
-            sl = torch.from_numpy(np.ascontiguousarray(start_leaves)).to(dev)
-        elif isinstance(start_leaves, torch.Tensor):
-            if as_numpy or start_leaves.dtype != torch.int32 or tuple(start_leaves.shape) != (n,) or start_leaves.device != dev or not start_leaves.is_contiguous():
-                raise ValueError(f"trace_occlusion: start_leaves must be a contiguous int32 ({n},) tensor on {dev}, like the rays")
-            sl = start_leaves
-        else:
-            raise ValueError(f"trace_occlusion: start_leaves must be a torch tensor or a numpy array, got {type(start_leaves).__name__}")
+    sl = _device_vector(torch, start_leaves, torch.int32, (np.int32,), n, "start_leaves", dev, "trace_occlusion", as_numpy)
     need = occlusion_scratch_bytes(ctx.lib, n)
     scratch = getattr(ctx, "_occlusion_scratch", None)
     if scratch is None or scratch.numel() < need:
         scratch = ctx._occlusion_scratch = torch.empty(need, dtype=torch.uint8, device=dev)
     occ = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)[:n]
-    if not asynchronous and ctx.get_stream() != torch.cuda.current_stream(dev).cuda_stream:
-        torch.cuda.current_stream(dev).synchronize()        # the rays (and the outputs' memory) are ready for the context's stream
+    _join_torchs_stream(ctx, torch, dev, asynchronous)
     flags = (A.QUERY_OPAQUE if opaque else 0) | ray_flags
-    args = (n, flags, A.VP(scratch.data_ptr()), scratch.numel(), A.VP(occ.data_ptr())) if n else (0, flags, None, 0, None)
-    rp = A.VP(r.data_ptr()) if n else None
+    tail = (_ptr(scratch, n), scratch.numel() if n else 0, _ptr(occ, n))
     out = QueryResult()
     rm = None
     if cull_mask is not None or ray_masks is not None:
         rm, cm = _cull_mask_args(torch, "trace_occlusion", cull_mask, ray_masks, n, dev)
-        hp = A.VP(sl.data_ptr()) if sl is not None and n else None
-        mp = A.VP(rm.data_ptr()) if rm is not None and n else None
-        margs = (n, flags, cm) + args[2:]
-        if asynchronous:
-            _check(ctx.lib.rtr_trace_occlusion_masked_async(ctx.h, scene.h, rp, hp, mp, *margs), "rtr_trace_occlusion_masked_async")
-        else:
-            st = A.rtr_query_stats() if collect_stats else None
-            _check(ctx.lib.rtr_trace_occlusion_masked(ctx.h, scene.h, rp, hp, mp, *margs, C.byref(st) if st is not None else None), "rtr_trace_occlusion_masked")
-            out.stats = st
+        name, args = "rtr_trace_occlusion_masked", (_ptr(r, n), _ptr(sl, n), _ptr(rm, n), n, flags, cm) + tail
     elif sl is not None:
-        hp = A.VP(sl.data_ptr()) if n else None
-        if asynchronous:
-            _check(ctx.lib.rtr_trace_occlusion_hinted_async(ctx.h, scene.h, rp, hp, *args), "rtr_trace_occlusion_hinted_async")
-        else:
-            st = A.rtr_query_stats() if collect_stats else None
-            _check(ctx.lib.rtr_trace_occlusion_hinted(ctx.h, scene.h, rp, hp, *args, C.byref(st) if st is not None else None), "rtr_trace_occlusion_hinted")
-            out.stats = st
-    elif asynchronous:
-        _check(ctx.lib.rtr_trace_occlusion_async(ctx.h, scene.h, rp, *args), "rtr_trace_occlusion_async")
+        name, args = "rtr_trace_occlusion_hinted", (_ptr(r, n), _ptr(sl, n), n, flags) + tail
     else:
-        st = A.rtr_query_stats() if collect_stats else None
-        _check(ctx.lib.rtr_trace_occlusion(ctx.h, scene.h, rp, *args, C.byref(st) if st is not None else None), "rtr_trace_occlusion")
-        out.stats = st
+        name, args = "rtr_trace_occlusion", (_ptr(r, n), n, flags) + tail
+    out.stats = _call_query(ctx, name, asynchronous, collect_stats, ctx.h, scene.h, *args)
     out.occluded = occ.cpu().numpy() if as_numpy else occ
     out._keep = (r, sl, occ, scratch, rm)    # an asynchronous query's buffers stay alive with its result
     return out
@@ -948,8 +908,7 @@ def camera_rays(ctx, camera, width, height, spp=1):
     dev = torch.device("cuda", ctx.device)
     n = int(width) * int(height) * int(spp)
     out = torch.empty((max(n, 1), 8), dtype=torch.float32, device=dev)[:n]
-    if ctx.get_stream() != torch.cuda.current_stream(dev).cuda_stream:
-        torch.cuda.current_stream(dev).synchronize()        # the tensor's memory is free for the context's stream
+    _join_torchs_stream(ctx, torch, dev)                    # the tensor's memory is free for the context's stream
     _check(ctx.lib.rtr_camera_rays_async(ctx.h, C.byref(camera), int(width), int(height), int(spp), A.VP(out.data_ptr()) if n else None),
            "rtr_camera_rays_async")
     _join_ctx_stream(ctx, torch, dev)
@@ -961,23 +920,6 @@ class SurfaceResult:
     color (N, 3) and roughness, metallic (N,) and uv (N, 2) are float32; kind (A.SURFACE_*) and object_index (the ObjectInfo row of an
     object, the light index of a light, -1 otherwise) are int32."""
     raw = position = normal = geom_normal = color = roughness = metallic = uv = kind = object_index = None
-
-
-def _device_array(torch, x, dtype, np_dtype, name, dev, who):
-    """an (N, 8) array of 32-bit words on dev: a device tensor as it is (checked), a numpy array copied there"""
-    if isinstance(x, np.ndarray):
-        if x.dtype != np_dtype or x.ndim != 2 or x.shape[1] != 8:
-            raise ValueError(f"{who}: {name} must be {np.dtype(np_dtype)} (N, 8), got {x.dtype} {x.shape}")
-        return torch.from_numpy(np.ascontiguousarray(x)).to(dev), True
-    if isinstance(x, torch.Tensor):
-        if x.dtype != dtype or x.dim() != 2 or x.shape[1] != 8:
-            raise ValueError(f"{who}: {name} must be {dtype} (N, 8), got {x.dtype} {tuple(x.shape)}")
-        if x.device != dev:
-            raise ValueError(f"{who}: {name} live on {x.device}, the context on {dev}")
-        if not x.is_contiguous():
-            raise ValueError(f"{who}: {name} must be contiguous")
-        return x, False
-    raise ValueError(f"{who}: {name} must be a torch tensor or a numpy array, got {type(x).__name__}")
 
 
 def hit_surfaces(scene, rays, hits, ctx=None, asynchronous=False):
@@ -998,12 +940,10 @@ def hit_surfaces(scene, rays, hits, ctx=None, asynchronous=False):
         raise ValueError("hit_surfaces: rays and hits must both be numpy arrays or both be tensors")
     if r.shape[0] != h.shape[0]:
         raise ValueError(f"hit_surfaces: {r.shape[0]} rays but {h.shape[0]} hits")
-    if asynchronous and ctx.get_stream() != torch.cuda.current_stream(dev).cuda_stream:
-        raise ValueError("hit_surfaces: an asynchronous call needs the context on torch's current stream (ctx.set_stream)")
+    _check_async(ctx, torch, dev, "hit_surfaces", asynchronous)
     n = int(r.shape[0])
     out = torch.empty((n, 20), dtype=torch.float32, device=dev)
-    if not asynchronous and ctx.get_stream() != torch.cuda.current_stream(dev).cuda_stream:
-        torch.cuda.current_stream(dev).synchronize()        # the inputs (and the output's memory) are ready for the context's stream
+    _join_torchs_stream(ctx, torch, dev, asynchronous)
     args = (A.VP(r.data_ptr()), A.VP(h.data_ptr()), n, A.VP(out.data_ptr())) if n else (None, None, 0, None)
     if asynchronous:
         _check(ctx.lib.rtr_hit_surfaces_async(ctx.h, scene.h, *args), "rtr_hit_surfaces_async")
@@ -1033,12 +973,10 @@ def hit_leaves(scene, hits, ctx=None, asynchronous=False):
             raise ValueError("hit_leaves: the QueryResult holds no hit records (an any-hit query)")
         hits = hits.hits
     h, as_numpy = _device_array(torch, hits, torch.int32, np.int32, "hits", dev, "hit_leaves")
-    if asynchronous and ctx.get_stream() != torch.cuda.current_stream(dev).cuda_stream:
-        raise ValueError("hit_leaves: an asynchronous call needs the context on torch's current stream (ctx.set_stream)")
+    _check_async(ctx, torch, dev, "hit_leaves", asynchronous)
     n = int(h.shape[0])
     out = torch.empty(n, dtype=torch.int32, device=dev)
-    if not asynchronous and ctx.get_stream() != torch.cuda.current_stream(dev).cuda_stream:
-        torch.cuda.current_stream(dev).synchronize()        # the hits (and the output's memory) are ready for the context's stream
+    _join_torchs_stream(ctx, torch, dev, asynchronous)
     fn = ctx.lib.rtr_hit_leaves_async if asynchronous else ctx.lib.rtr_hit_leaves
     _check(fn(ctx.h, scene.h, A.VP(h.data_ptr()) if n else None, n, A.VP(out.data_ptr()) if n else None), "rtr_hit_leaves")
     if as_numpy:
@@ -1079,22 +1017,8 @@ def _light_inputs(torch, scene, rays, hits, seeds, ctx, who, asynchronous):
         raise ValueError(f"{who}: rays and hits must both be numpy arrays or both be tensors")
     if r.shape[0] != h.shape[0]:
         raise ValueError(f"{who}: {r.shape[0]} rays but {h.shape[0]} hits")
-    sd = None
-    if seeds is not None:
-        if isinstance(seeds, np.ndarray):
-            if seeds.dtype not in (np.uint32, np.int32) or seeds.ndim != 1:
-                raise ValueError(f"{who}: seeds must be 32-bit integers (N,), got {seeds.dtype} {seeds.shape}")
-            sd = torch.from_numpy(np.ascontiguousarray(seeds).view(np.int32)).to(dev)
-        elif isinstance(seeds, torch.Tensor):
-            if seeds.dtype != torch.int32 or seeds.dim() != 1 or seeds.device != dev or not seeds.is_contiguous():
-                raise ValueError(f"{who}: seeds must be a contiguous int32 (N,) tensor on {dev}")
-            sd = seeds
-        else:
-            raise ValueError(f"{who}: seeds must be a torch tensor or a numpy array, got {type(seeds).__name__}")
-        if sd.shape[0] != r.shape[0]:
-            raise ValueError(f"{who}: {r.shape[0]} rays but {sd.shape[0]} seeds")
-    if asynchronous and ctx.get_stream() != torch.cuda.current_stream(dev).cuda_stream:
-        raise ValueError(f"{who}: an asynchronous call needs the context on torch's current stream (ctx.set_stream)")
+    sd = _device_vector(torch, seeds, torch.int32, (np.int32, np.uint32), int(r.shape[0]), "seeds", dev, who)
+    _check_async(ctx, torch, dev, who, asynchronous)
     return r, h, sd, rn
 
 
@@ -1114,8 +1038,7 @@ def light_rays(scene, rays, hits, params, seeds=None, ctx=None, asynchronous=Fal
         raise ValueError(f"light_rays: {n} hits x {q} slots do not fit 32 bits")
     out = torch.empty((n * q, 8), dtype=torch.float32, device=dev)
     leaves = torch.empty(n * q, dtype=torch.int32, device=dev) if hints else None
-    if not asynchronous and ctx.get_stream() != torch.cuda.current_stream(dev).cuda_stream:
-        torch.cuda.current_stream(dev).synchronize()        # the inputs (and the output's memory) are ready for the context's stream
+    _join_torchs_stream(ctx, torch, dev, asynchronous)
     if hints:
         fn, who = (ctx.lib.rtr_light_rays_hinted_async if asynchronous else ctx.lib.rtr_light_rays_hinted), "rtr_light_rays_hinted"
         extra = (A.VP(leaves.data_ptr()) if n else None,)
@@ -1144,19 +1067,11 @@ def shade_hits(scene, rays, hits, params, occluded, seeds=None, ctx=None, asynch
             raise ValueError("shade_hits: the QueryResult holds no visibility bytes (a closest-hit query)")
         occluded = occluded.occluded
     n, q = int(r.shape[0]), light_slots(scene, params)
-    if isinstance(occluded, np.ndarray):
-        if not as_numpy or occluded.dtype != np.uint8 or occluded.shape != (n * q,):
-            raise ValueError(f"shade_hits: occluded must be uint8 ({n * q},), numpy like the rays; got {occluded.dtype} {occluded.shape}")
-        oc = torch.from_numpy(np.ascontiguousarray(occluded)).to(dev)
-    elif isinstance(occluded, torch.Tensor):
-        if as_numpy or occluded.dtype != torch.uint8 or tuple(occluded.shape) != (n * q,) or occluded.device != dev or not occluded.is_contiguous():
-            raise ValueError(f"shade_hits: occluded must be a contiguous uint8 ({n * q},) tensor on {dev}, like the rays")
-        oc = occluded
-    else:
-        raise ValueError(f"shade_hits: occluded must be a torch tensor or a numpy array, got {type(occluded).__name__}")
+    if occluded is None:
+        raise ValueError("shade_hits: occluded must be a torch tensor or a numpy array, got NoneType")
+    oc = _device_vector(torch, occluded, torch.uint8, (np.uint8,), n * q, "occluded", dev, "shade_hits", as_numpy)
     out = torch.empty((n, 12), dtype=torch.float32, device=dev)
-    if not asynchronous and ctx.get_stream() != torch.cuda.current_stream(dev).cuda_stream:
-        torch.cuda.current_stream(dev).synchronize()
+    _join_torchs_stream(ctx, torch, dev, asynchronous)
     fn = ctx.lib.rtr_shade_hits_async if asynchronous else ctx.lib.rtr_shade_hits
     if n:
         _check(fn(ctx.h, scene.h, A.VP(r.data_ptr()), A.VP(h.data_ptr()), n, C.byref(params), A.VP(sd.data_ptr()) if sd is not None else None,
@@ -1189,11 +1104,9 @@ def tonemap_pack(ctx, radiance, asynchronous=False):
     n = int(x.shape[0])
     if n and (x.stride(1) != 1 or x.stride(0) < 3):
         raise ValueError("tonemap_pack: the three floats of a row must be adjacent")
-    if asynchronous and ctx.get_stream() != torch.cuda.current_stream(dev).cuda_stream:
-        raise ValueError("tonemap_pack: an asynchronous call needs the context on torch's current stream (ctx.set_stream)")
+    _check_async(ctx, torch, dev, "tonemap_pack", asynchronous)
     out = torch.empty(n, dtype=torch.int32, device=dev)
-    if not asynchronous and ctx.get_stream() != torch.cuda.current_stream(dev).cuda_stream:
-        torch.cuda.current_stream(dev).synchronize()
+    _join_torchs_stream(ctx, torch, dev, asynchronous)
     fn = ctx.lib.rtr_tonemap_pack_async if asynchronous else ctx.lib.rtr_tonemap_pack
     if n:
         _check(fn(ctx.h, A.VP(x.data_ptr()), 4 * int(x.stride(0)), n, A.VP(out.data_ptr())), "rtr_tonemap_pack")

@@ -19,7 +19,7 @@
  * Resume: only candidates whose key is strictly greater than after[k]'s enter the list (one comparison, ahead of the opacity-map test).
  * Compiled with the library's flags (-ffp-contract=off): the numerical contract of include/rtr_math.h.
  */
-#include "rtr_query.h"
+#include "rtr_query_device.h"
 #include "../../../include/rtr.h"
 
 namespace rtrdev {
@@ -38,16 +38,6 @@ typedef __attribute__((address_space(3))) int32_t* lds_i32;
 
 __host__ __device__ constexpr uint32_t multihit_lds_bytes(uint32_t maxHits) {
     return (uint32_t)kMultiBlock * ((uint32_t)kMultiStack + kMultiFields * maxHits) * 4u;
-}
-
-/* ray k as rtr_query.hip reads it: two 16-B loads.  false: a degenerate ray (origin or direction not finite, or a zero direction) */
-__device__ __forceinline__ bool multi_ray(const float4* __restrict__ rays, uint32_t k, rtr_v3& o, rtr_v3& d, float& tmin, float& tmax) {
-    const float4 a = rays[2 * (size_t)k], b = rays[2 * (size_t)k + 1];
-    o = rtr_mk(a.x, a.y, a.z); tmin = a.w;
-    d = rtr_mk(b.x, b.y, b.z); tmax = b.w;
-    const bool finite = __builtin_isfinite(a.x) && __builtin_isfinite(a.y) && __builtin_isfinite(a.z) &&
-                        __builtin_isfinite(b.x) && __builtin_isfinite(b.y) && __builtin_isfinite(b.z);
-    return finite && (b.x != 0.0f || b.y != 0.0f || b.z != 0.0f);
 }
 
 /* (t, customIndex, primitiveId) < (et, ec, ep), evaluated without short-circuit branches */
@@ -183,11 +173,6 @@ __device__ __forceinline__ void multi_store(const MultiHitArgs& ma, lds_u32 list
     if (ma.counts) ma.counts[k] = cnt;
 }
 
-/* the ray's effective cull mask in the records' bits and the call's culling flags, as rtr_query.hip forms them */
-__device__ __forceinline__ uint32_t multi_ray_mask8(const RayMaskArgs& rm, uint32_t k) {
-    return (rm.cullMask & (rm.rayMasks ? (uint32_t)rm.rayMasks[k] : 0xffu)) << kTriMaskShift;
-}
-
 template <bool ALPHA, bool STATS>
 __global__ __launch_bounds__(kMultiBlock) void k_multihit(DeviceScene sc, MultiHitArgs ma, Counters* stats, RayMaskArgs rm) {
     extern __shared__ uint32_t s_multi[];
@@ -199,8 +184,8 @@ __global__ __launch_bounds__(kMultiBlock) void k_multihit(DeviceScene sc, MultiH
     rtr_v3 o, d;
     float tmin, tmax, at;
     uint32_t ac, ap;
-    const uint32_t rm8 = multi_ray_mask8(rm, k), cull = rm.masked & kCullAll;
-    bool ok = multi_ray(ma.rays, k, o, d, tmin, tmax) && rm8 != 0u;
+    const uint32_t rm8 = query_ray_mask8(rm, k), cull = rm.masked & kCullAll;
+    bool ok = query_ray(ma.rays, k, o, d, tmin, tmax) && rm8 != 0u;
     ok = multi_after(ma.after, k, at, ac, ap) && ok;
     const float tfar = ok ? tmax : tmin;                   /* a degenerate, masked-out or exhausted ray walks nothing but is counted like any other */
     if (STATS) { st.rays++; st.primary++; }
@@ -224,15 +209,7 @@ __global__ __launch_bounds__(kMultiBlock) void k_multihit(DeviceScene sc, MultiH
         }
     }
     multi_store(ma, list, k, cnt, tmax, over);            /* a miss reports the ray's own tmax */
-    /* the abandoned rays of the wave take consecutive entries of the redo list: one atomic per wave */
-    const unsigned long long m = __ballot(over);
-    if (m != 0ull) {
-        const uint32_t prefix = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-        uint32_t base = 0;
-        if (over && prefix == 0u) base = atomicAdd(ma.ctrl + kQueryRedoWord, (uint32_t)__popcll(m));
-        base = (uint32_t)__builtin_amdgcn_readlane((int)base, __ffsll((long long)m) - 1);
-        if (over && base + prefix < ma.redoCap) ma.redoList[base + prefix] = k;
-    }
+    redo_append(ma.ctrl, ma.redoList, ma.redoCap, over, k);
     if (STATS) st.flush(stats);
 }
 
@@ -256,10 +233,10 @@ __global__ __launch_bounds__(kMultiBlock) void k_multihit_tail(DeviceScene sc, M
         rtr_v3 o, d;
         float tmin, tmax, at;
         uint32_t ac, ap;
-        multi_ray(ma.rays, k, o, d, tmin, tmax);          /* an abandoned ray is never degenerate, masked out or exhausted: it walked past 16 stacked nodes */
+        query_ray(ma.rays, k, o, d, tmin, tmax);          /* an abandoned ray is never degenerate, masked out or exhausted: it walked past 16 stacked nodes */
         multi_after(ma.after, k, at, ac, ap);
         uint32_t cnt = 0u;
-        multihit_walk<STATS, kMultiTailBlocks * kMultiBlock, 0, 8, ALPHA>(sc, stack, list, ma.maxHits, o, d, tmin, tmax, at, ac, ap, multi_ray_mask8(rm, k),
+        multihit_walk<STATS, kMultiTailBlocks * kMultiBlock, 0, 8, ALPHA>(sc, stack, list, ma.maxHits, o, d, tmin, tmax, at, ac, ap, query_ray_mask8(rm, k),
                                                                            rm.masked & kCullAll, cnt, st);
         multi_store(ma, list, k, cnt, tmax, false);
     }

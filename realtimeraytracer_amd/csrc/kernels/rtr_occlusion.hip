@@ -24,7 +24,7 @@ static_assert(kOccGenPerLane == 8 && kOccGenPerLane * kOccGenBlock == kOcclusion
 constexpr uint32_t kOccNoWalk = 8u;                                        /* code of a ray that is not queued (octants are 0..7) */
 
 /* ray k's code: its direction octant (signs of the direction as given: the octant only sorts the queue, the walk takes its own from the
- * ray it loads), or kOccNoWalk.  wellFormed: origin and direction finite, direction not zero — query_ray()'s rule (rtr_query.hip). */
+ * ray it loads), or kOccNoWalk.  wellFormed: origin and direction finite, direction not zero — query_ray()'s rule (rtr_query_device.h). */
 __device__ __forceinline__ uint32_t occlusion_code(const float4* __restrict__ rays, uint64_t k, bool& wellFormed) {
     const float4 a = rays[2 * k], b = rays[2 * k + 1];
     wellFormed = __builtin_isfinite(a.x) && __builtin_isfinite(a.y) && __builtin_isfinite(a.z) &&

@@ -7,7 +7,7 @@
  *   k_query       one ray per lane, one-wave workgroups (RTR_PRIMARY_BLOCK, what k_primary measured best), 16-entry interleaved
  *                 LDS stack; a wave whose rays share their direction signs runs the octant form of the slab test.  A ray that
  *                 needs more stack is abandoned: its output gets a sentinel and it is appended to a bounded redo list, one atomic
- *                 per wave (ballot + mbcnt prefix);
+ *                 per wave (ballot + mbcnt prefix: redo_append() of rtr_query_device.h, which k_multihit shares);
  *   k_query_tail  walks those rays again with a full-depth stack in global memory (as k_primary_tail does); if the redo list
  *                 overflowed it finds them by their sentinel in the outputs.
  * k_hit_surfaces (rtr_hit_surfaces) takes the hits further: the surface the closest-hit shader computes for each, by fetch_surface().
@@ -15,7 +15,7 @@
  * ray-gen shader does after the closest hit, by the renderer's own light_loops() with every query at a fixed slot of its hit.
  * Compiled with the library's flags (-ffp-contract=off): the numerical contract of include/rtr_math.h.
  */
-#include "rtr_query.h"
+#include "rtr_query_device.h"
 #include "../../../include/rtr.h"
 
 namespace rtrdev {
@@ -30,25 +30,10 @@ constexpr int kQueryTailBlocks = 64;         /* the spill area holds 64 entries 
 static_assert((size_t)64 * kQueryTailBlocks * kQueryTailBlock == kSpillInts, "the tail kernel's stacks fill the spill area");
 constexpr uint8_t kOccludedRedo = 0xffu;     /* sentinel of an abandoned any-hit ray (its hit record's sentinel: customIndex = RTR_STACK_OVERFLOW) */
 
-/* ray k: two 16-B loads.  false: a degenerate ray (origin or direction not finite, or a zero direction), which is a miss */
-__device__ __forceinline__ bool query_ray(const float4* __restrict__ rays, uint32_t k, rtr_v3& o, rtr_v3& d, float& tmin, float& tmax) {
-    const float4 a = rays[2 * (size_t)k], b = rays[2 * (size_t)k + 1];
-    o = rtr_mk(a.x, a.y, a.z); tmin = a.w;
-    d = rtr_mk(b.x, b.y, b.z); tmax = b.w;
-    const bool finite = __builtin_isfinite(a.x) && __builtin_isfinite(a.y) && __builtin_isfinite(a.z) &&
-                        __builtin_isfinite(b.x) && __builtin_isfinite(b.y) && __builtin_isfinite(b.z);
-    return finite && (b.x != 0.0f || b.y != 0.0f || b.z != 0.0f);
-}
-
 /* RtrHit as two 16-B stores: {t, u, v, customIndex} {primitiveId, 0, 0, 0} */
 __device__ __forceinline__ void query_store_hit(float4* __restrict__ hits, uint32_t k, const HitRec& h) {
     hits[2 * (size_t)k] = make_float4(h.t, h.u, h.v, __uint_as_float(h.custom));
     hits[2 * (size_t)k + 1] = make_float4(__uint_as_float(h.prim), 0.0f, 0.0f, 0.0f);
-}
-
-/* ray k's effective cull mask, in the bits the records keep theirs in (trace()'s rayMask8); 0: nothing exists for the ray */
-__device__ __forceinline__ uint32_t query_ray_mask8(const RayMaskArgs& rm, uint32_t k) {
-    return (rm.cullMask & (rm.rayMasks ? (uint32_t)rm.rayMasks[k] : 0xffu)) << kTriMaskShift;
 }
 
 /* the call's RTR_QUERY_CULL_* flags (wave-uniform; 0: none), which travel in RayMaskArgs::masked beside the bit that selects these forms */
@@ -97,15 +82,7 @@ __global__ __launch_bounds__(kQueryBlock) void k_query(DeviceScene sc, QueryArgs
     if (!ok) h.t = tmax;                                  /* a miss reports the ray's own tmax */
     if (ANY) qa.occluded[k] = over ? kOccludedRedo : (found ? 1u : 0u);
     else query_store_hit(qa.hits, k, h);                  /* an abandoned ray's record carries customIndex = RTR_STACK_OVERFLOW */
-    /* the abandoned rays of the wave take consecutive entries of the redo list: one atomic per wave */
-    const unsigned long long m = __ballot(over);
-    if (m != 0ull) {
-        const uint32_t prefix = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-        uint32_t base = 0;
-        if (over && prefix == 0u) base = atomicAdd(qa.ctrl + kQueryRedoWord, (uint32_t)__popcll(m));
-        base = (uint32_t)__builtin_amdgcn_readlane((int)base, __ffsll((long long)m) - 1);
-        if (over && base + prefix < qa.redoCap) qa.redoList[base + prefix] = k;
-    }
+    redo_append(qa.ctrl, qa.redoList, qa.redoCap, over, k);
     if (STATS) st.flush(stats);
 }
 

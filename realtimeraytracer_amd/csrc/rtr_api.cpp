@@ -2286,6 +2286,23 @@ int rtr_deinterleave_images(rtr_ctx* ctx, const void* gathered, uint32_t numImag
 
 /* ---- ray queries ---------------------------------------------------------------------------- */
 static bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+static bool aligned4(const void* p) { return ((uintptr_t)p & 3u) == 0; }
+
+/* the handles every call of this section takes, and the device they must share */
+static int check_handles(const rtr_ctx* c, const rtr_scene* s, const char* who) {
+    if (!c || !s) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: null context or scene", who);
+    return RTR_OK;
+}
+static int check_same_device(const rtr_ctx* c, const rtr_scene* s, const char* who) {
+    if (s->ctx->device != c->device) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: the scene lives on device %d, the context on device %d", who, s->ctx->device, c->device);
+    return RTR_OK;
+}
+/* a synchronous call joins the context's stream when its asynchronous form (rc) enqueued something */
+static int join_if_enqueued(rtr_ctx* c, int rc, uint32_t n) {
+    if (rc != RTR_OK || n == 0) return rc;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return RTR_OK;
+}
 
 /* the context's query scratch, allocated by its first query (the current device is the context's) */
 static int query_scratch(rtr_ctx* c) {
@@ -2298,7 +2315,37 @@ static int query_scratch(rtr_ctx* c) {
     return RTR_OK;
 }
 
-/* the checks and launches of rtr_trace_rays[_async], enqueued on the context's stream; count: the counting form */
+/* Every query that walks rays (rtr_trace_rays, rtr_trace_rays_multi, rtr_trace_occlusion and their forms) goes through that scratch the
+ * same way: scratch_open, its own memsets, qEv[0], its launches, scratch_close; the counting form reads back in query_join. */
+
+/* entries of a redo list of cap entries the query may use: all of them, or in the test build a list short enough to overflow */
+static uint32_t redo_cap(uint32_t cap) {
+#ifdef RTR_TEST_HOOKS
+    if (const char* e = getenv("RTR_QUERY_REDO_CAP")) { const uint64_t v = strtoull(e, nullptr, 10); if (v >= 1 && v < cap) cap = (uint32_t)v; }
+#endif
+    return cap;
+}
+
+/* The scratch is the context's — redo list, deep stacks, counters, events — so a query enqueued on another stream than the last one
+ * (rtr_ctx_set_stream) comes behind it.  count: the counting form, whose counters start at zero. */
+static int scratch_open(rtr_ctx* c, bool count) {
+    HIP_TRY(hipSetDevice(c->device));
+    if (const int rc = query_scratch(c)) return rc;
+    hipStream_t st = c->stream;
+    if (c->qLastStream && c->qLastStream != st) HIP_TRY(hipStreamWaitEvent(st, c->qEv[1], 0));
+    if (count) HIP_TRY(hipMemsetAsync(c->qCounters.p, 0, sizeof(Counters), st));
+    return RTR_OK;
+}
+
+/* launch: what the query's launcher returned */
+static int scratch_close(rtr_ctx* c, hipError_t launch, const char* who) {
+    if (launch != hipSuccess) return fail(RTR_ERR_HIP, "%s: kernel launch: %s", who, hipGetErrorString(launch));
+    hipStream_t st = c->stream;
+    HIP_TRY(hipEventRecord(c->qEv[1], st));
+    c->qLastStream = st;
+    return RTR_OK;
+}
+
 /* the cull mask of the masked calls: NoMask for the unmasked ones, which launch the kernels' unmasked forms */
 struct CullMask { bool masked; const uint8_t* rayMasks; uint32_t cullMask; };
 static const CullMask NoMask{false, nullptr, 0xffu};
@@ -2328,12 +2375,18 @@ static rtrdev::RayMaskArgs ray_mask_args(const CullMask& cm, uint32_t flags) {
     return rm;
 }
 
+/* what the three kinds of query check first, in this order: the handles, the cull mask's range, the flags */
+static int check_query(const rtr_ctx* c, const rtr_scene* s, const CullMask& cm, uint32_t flags, const char* who) {
+    if (const int rc = check_handles(c, s, who)) return rc;
+    if (cm.masked && (cm.cullMask & ~0xffu)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: cullMask 0x%x has bits above the low 8 (an instance mask is 8 bits)", who, cm.cullMask);
+    return check_query_flags(flags, who);
+}
+
+/* the checks and launches of rtr_trace_rays[_async], enqueued on the context's stream; count: the counting form */
 static int enqueue_query(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, uint32_t n, uint32_t flags, RtrHit* hits, uint8_t* occluded,
                          bool count, const char* who, const CullMask& cm = NoMask) {
-    if (!c || !s) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: null context or scene", who);
-    if (cm.masked && (cm.cullMask & ~0xffu)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: cullMask 0x%x has bits above the low 8 (an instance mask is 8 bits)", who, cm.cullMask);
-    if (const int frc = check_query_flags(flags, who)) return frc;
-    if (s->ctx->device != c->device) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: the scene lives on device %d, the context on device %d", who, s->ctx->device, c->device);
+    if (const int rc = check_query(c, s, cm, flags, who)) return rc;
+    if (const int rc = check_same_device(c, s, who)) return rc;
     if (n == 0) return RTR_OK;
     const bool any = (flags & RTR_QUERY_ANY) != 0u;
     if (!rays) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: rays is null", who);
@@ -2342,74 +2395,18 @@ static int enqueue_query(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, uin
     if (!any && !aligned16(hits)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: hits is not 16-B aligned", who);
     if (any && !occluded) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: an any-hit query (RTR_QUERY_ANY) needs occluded", who);
     if (any && !aligned16(occluded)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: occluded is not 16-B aligned", who);
-    HIP_TRY(hipSetDevice(c->device));
-    const int src = query_scratch(c);
-    if (src != RTR_OK) return src;
-    uint32_t redoCap = rtrdev::kQueryRedoCap;
-#ifdef RTR_TEST_HOOKS
-    if (const char* e = getenv("RTR_QUERY_REDO_CAP")) { const uint64_t v = strtoull(e, nullptr, 10); if (v >= 1 && v < redoCap) redoCap = (uint32_t)v; }   /* a list short enough to overflow */
-#endif
+    if (const int rc = scratch_open(c, count)) return rc;
     hipStream_t st = c->stream;
-    /* the scratch is the context's: a query enqueued on another stream than the last one (rtr_ctx_set_stream) comes behind it */
-    if (c->qLastStream && c->qLastStream != st) HIP_TRY(hipStreamWaitEvent(st, c->qEv[1], 0));
     HIP_TRY(hipMemsetAsync(c->qCtrl.p, 0, rtrdev::kQueryCtrlWords * sizeof(uint32_t), st));
-    if (count) HIP_TRY(hipMemsetAsync(c->qCounters.p, 0, sizeof(Counters), st));
     HIP_TRY(hipEventRecord(c->qEv[0], st));
     rtrdev::QueryArgs qa{};
     qa.rays = reinterpret_cast<const float4*>(rays); qa.hits = reinterpret_cast<float4*>(hits); qa.occluded = occluded; qa.n = n;
-    qa.redoCap = redoCap; qa.ctrl = c->qCtrl.p; qa.redoList = c->qRedo.p; qa.spill = c->qSpill.p;
+    qa.redoCap = redo_cap(rtrdev::kQueryRedoCap); qa.ctrl = c->qCtrl.p; qa.redoList = c->qRedo.p; qa.spill = c->qSpill.p;
     const rtrdev::RayMaskArgs rm = ray_mask_args(cm, flags);
-    const hipError_t e = rtrdev::launch_query(s->dev, qa, flags & (RTR_QUERY_ANY | RTR_QUERY_OPAQUE), count ? c->qCounters.p : nullptr, st, rm);
-    if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: kernel launch: %s", who, hipGetErrorString(e));
-    HIP_TRY(hipEventRecord(c->qEv[1], st));
-    c->qLastStream = st;
-    return RTR_OK;
+    return scratch_close(c, rtrdev::launch_query(s->dev, qa, flags & (RTR_QUERY_ANY | RTR_QUERY_OPAQUE), count ? c->qCounters.p : nullptr, st, rm), who);
 }
 
-int rtr_trace_rays_async(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, uint32_t n, uint32_t flags, RtrHit* hits, uint8_t* occluded) {
-    return enqueue_query(c, s, rays, n, flags, hits, occluded, false, "rtr_trace_rays_async");
-}
-
-static int query_sync(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, uint32_t n, uint32_t flags, RtrHit* hits, uint8_t* occluded, rtr_query_stats* stats,
-                      const char* who, const CullMask& cm);
-
-int rtr_trace_rays(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, uint32_t n, uint32_t flags, RtrHit* hits, uint8_t* occluded, rtr_query_stats* stats) {
-    return query_sync(c, s, rays, n, flags, hits, occluded, stats, "rtr_trace_rays", NoMask);
-}
-
-int rtr_trace_rays_masked_async(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const uint8_t* rayMasks, uint32_t n, uint32_t flags, uint32_t cullMask,
-                                RtrHit* hits, uint8_t* occluded) {
-    return enqueue_query(c, s, rays, n, flags, hits, occluded, false, "rtr_trace_rays_masked_async", CullMask{true, rayMasks, cullMask});
-}
-
-int rtr_trace_rays_masked(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const uint8_t* rayMasks, uint32_t n, uint32_t flags, uint32_t cullMask,
-                          RtrHit* hits, uint8_t* occluded, rtr_query_stats* stats) {
-    return query_sync(c, s, rays, n, flags, hits, occluded, stats, "rtr_trace_rays_masked", CullMask{true, rayMasks, cullMask});
-}
-
-static int query_sync(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, uint32_t n, uint32_t flags, RtrHit* hits, uint8_t* occluded, rtr_query_stats* stats,
-                      const char* who, const CullMask& cm) {
-    const int rc = enqueue_query(c, s, rays, n, flags, hits, occluded, stats != nullptr, who, cm);
-    if (rc != RTR_OK) return rc;
-    if (stats) memset(stats, 0, sizeof *stats);
-    if (n == 0) return RTR_OK;
-    hipStream_t st = c->stream;
-    if (stats) {      /* copies on the context's stream: the call joins that stream only */
-        Counters h;
-        uint32_t ctrl[rtrdev::kQueryCtrlWords];
-        HIP_TRY(hipMemcpyAsync(&h, c->qCounters.p, sizeof h, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(ctrl, c->qCtrl.p, sizeof ctrl, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        stats->numRays = h.rays; stats->numNodeVisits = h.nodes; stats->numTriTests = h.tris; stats->numAlphaTests = h.alphaTests;
-        stats->tailRays = ctrl[rtrdev::kQueryRedoWord];
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, c->qEv[0], c->qEv[1]));
-        stats->ms = ms;
-    } else HIP_TRY(hipStreamSynchronize(st));
-    return RTR_OK;
-}
-
-/* ---- queued occlusion queries (kernels/rtr_occlusion.hip) ---- */
+/* ---- queued occlusion queries (kernels/rtr_occlusion.hip): the layout of the caller's scratch ---- */
 namespace {
 /* the caller's scratch: control block (zeroed with the count of abandoned rays behind it) | abandoned rays' list | index queue | batch lists */
 struct OcclusionLayout { size_t ctrl, overflow, queue, lists, bytes; uint32_t overflowCap, listStride; };
@@ -2427,53 +2424,75 @@ OcclusionLayout occlusion_layout(uint32_t n) {
 }
 }  // namespace
 
-int rtr_occlusion_scratch_bytes(uint32_t numRays, size_t* bytes) {
-    if (!bytes) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_occlusion_scratch_bytes: bytes is null");
-    *bytes = occlusion_layout(numRays).bytes;
+/* What a synchronous query does behind its asynchronous form (rc: what that returned): it joins the context's stream, and the counting
+ * form reads back the counters, the count of abandoned rays and the time between the two events — copies on the context's stream, so the
+ * call joins that stream only.  occlusionScratch: the caller's scratch of a queued occlusion query, which keeps that count behind its
+ * control block; null: the count is the context's control word. */
+static int query_join(rtr_ctx* c, int rc, uint32_t n, rtr_query_stats* stats, const void* occlusionScratch = nullptr) {
+    if (rc != RTR_OK) return rc;
+    if (stats) memset(stats, 0, sizeof *stats);
+    if (n == 0) return RTR_OK;
+    hipStream_t st = c->stream;
+    if (stats) {
+        Counters h;
+        uint32_t tail = 0;
+        const void* tailWord = c->qCtrl.p + rtrdev::kQueryRedoWord;
+        if (occlusionScratch) tailWord = static_cast<const char*>(occlusionScratch) + occlusion_layout(n).overflow;
+        HIP_TRY(hipMemcpyAsync(&h, c->qCounters.p, sizeof h, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(&tail, tailWord, sizeof tail, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        stats->numRays = h.rays; stats->numNodeVisits = h.nodes; stats->numTriTests = h.tris; stats->numAlphaTests = h.alphaTests;
+        stats->tailRays = tail;
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, c->qEv[0], c->qEv[1]));
+        stats->ms = ms;
+    } else HIP_TRY(hipStreamSynchronize(st));
     return RTR_OK;
 }
 
-static bool aligned4(const void* p) { return ((uintptr_t)p & 3u) == 0; }
+int rtr_trace_rays_async(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, uint32_t n, uint32_t flags, RtrHit* hits, uint8_t* occluded) {
+    return enqueue_query(c, s, rays, n, flags, hits, occluded, false, "rtr_trace_rays_async");
+}
+
+int rtr_trace_rays(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, uint32_t n, uint32_t flags, RtrHit* hits, uint8_t* occluded, rtr_query_stats* stats) {
+    return query_join(c, enqueue_query(c, s, rays, n, flags, hits, occluded, stats != nullptr, "rtr_trace_rays"), n, stats);
+}
+
+int rtr_trace_rays_masked_async(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const uint8_t* rayMasks, uint32_t n, uint32_t flags, uint32_t cullMask,
+                                RtrHit* hits, uint8_t* occluded) {
+    return enqueue_query(c, s, rays, n, flags, hits, occluded, false, "rtr_trace_rays_masked_async", CullMask{true, rayMasks, cullMask});
+}
+
+int rtr_trace_rays_masked(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const uint8_t* rayMasks, uint32_t n, uint32_t flags, uint32_t cullMask,
+                          RtrHit* hits, uint8_t* occluded, rtr_query_stats* stats) {
+    return query_join(c, enqueue_query(c, s, rays, n, flags, hits, occluded, stats != nullptr, "rtr_trace_rays_masked", CullMask{true, rayMasks, cullMask}), n, stats);
+}
 
 /* ---- multi-hit queries (kernels/rtr_multihit.hip) ---- */
 /* the checks and launches of rtr_trace_rays_multi[_async], enqueued on the context's stream; count: the counting form.  The flag and mask
  * validation is the masked query's; the kernels have the filtered form only, so the call always brings a cull mask. */
 static int enqueue_multihit(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const uint8_t* rayMasks, uint32_t n, uint32_t maxHits, uint32_t flags,
                             uint32_t cullMask, const RtrHit* after, RtrHit* hits, uint32_t* counts, bool count, const char* who) {
-    if (!c || !s) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: null context or scene", who);
-    if (cullMask & ~0xffu) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: cullMask 0x%x has bits above the low 8 (an instance mask is 8 bits)", who, cullMask);
-    if (const int frc = check_query_flags(flags, who)) return frc;
+    const CullMask cm{true, rayMasks, cullMask};
+    if (const int rc = check_query(c, s, cm, flags, who)) return rc;
     if (flags & RTR_QUERY_ANY) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: RTR_QUERY_ANY is refused: an any-hit walk has no order to report hits in", who);
     if (maxHits == 0u || maxHits > RTR_MULTIHIT_MAX) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: maxHits %u, 1 to %u", who, maxHits, RTR_MULTIHIT_MAX);
-    if (s->ctx->device != c->device) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: the scene lives on device %d, the context on device %d", who, s->ctx->device, c->device);
+    if (const int rc = check_same_device(c, s, who)) return rc;
     if (n == 0) return RTR_OK;
     if (!rays || !hits) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: %s is null", who, !rays ? "rays" : "hits");
     if (!aligned16(rays) || !aligned16(hits) || !aligned16(after))
         return fail(RTR_ERR_INVALID_ARGUMENT, "%s: %s is not 16-B aligned", who, !aligned16(rays) ? "rays" : (!aligned16(hits) ? "hits" : "after"));
     if (!aligned4(counts)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: counts is not 4-B aligned", who);
-    HIP_TRY(hipSetDevice(c->device));
-    const int src = query_scratch(c);
-    if (src != RTR_OK) return src;
-    uint32_t redoCap = rtrdev::kQueryRedoCap;
-#ifdef RTR_TEST_HOOKS
-    if (const char* e = getenv("RTR_QUERY_REDO_CAP")) { const uint64_t v = strtoull(e, nullptr, 10); if (v >= 1 && v < redoCap) redoCap = (uint32_t)v; }   /* a list short enough to overflow */
-#endif
+    if (const int rc = scratch_open(c, count)) return rc;
     hipStream_t st = c->stream;
-    /* the scratch is the context's: a query enqueued on another stream than the last one (rtr_ctx_set_stream) comes behind it */
-    if (c->qLastStream && c->qLastStream != st) HIP_TRY(hipStreamWaitEvent(st, c->qEv[1], 0));
     HIP_TRY(hipMemsetAsync(c->qCtrl.p, 0, rtrdev::kQueryCtrlWords * sizeof(uint32_t), st));
-    if (count) HIP_TRY(hipMemsetAsync(c->qCounters.p, 0, sizeof(Counters), st));
     HIP_TRY(hipEventRecord(c->qEv[0], st));
     rtrdev::MultiHitArgs ma{};
     ma.rays = reinterpret_cast<const float4*>(rays); ma.after = reinterpret_cast<const float4*>(after); ma.hits = reinterpret_cast<float4*>(hits);
     ma.counts = counts; ma.n = n; ma.maxHits = maxHits;
-    ma.redoCap = redoCap; ma.ctrl = c->qCtrl.p; ma.redoList = c->qRedo.p; ma.spill = c->qSpill.p;
-    const rtrdev::RayMaskArgs rm = ray_mask_args(CullMask{true, rayMasks, cullMask}, flags);
-    const hipError_t e = rtrdev::launch_multihit(s->dev, ma, (flags & RTR_QUERY_OPAQUE) == 0u, count ? c->qCounters.p : nullptr, st, rm);
-    if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: kernel launch: %s", who, hipGetErrorString(e));
-    HIP_TRY(hipEventRecord(c->qEv[1], st));
-    c->qLastStream = st;
-    return RTR_OK;
+    ma.redoCap = redo_cap(rtrdev::kQueryRedoCap); ma.ctrl = c->qCtrl.p; ma.redoList = c->qRedo.p; ma.spill = c->qSpill.p;
+    const rtrdev::RayMaskArgs rm = ray_mask_args(cm, flags);
+    return scratch_close(c, rtrdev::launch_multihit(s->dev, ma, (flags & RTR_QUERY_OPAQUE) == 0u, count ? c->qCounters.p : nullptr, st, rm), who);
 }
 
 int rtr_trace_rays_multi_async(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const uint8_t* rayMasks, uint32_t n, uint32_t maxHits, uint32_t flags,
@@ -2483,23 +2502,13 @@ int rtr_trace_rays_multi_async(rtr_ctx* c, const rtr_scene* s, const RtrRay* ray
 
 int rtr_trace_rays_multi(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const uint8_t* rayMasks, uint32_t n, uint32_t maxHits, uint32_t flags,
                          uint32_t cullMask, const RtrHit* after, RtrHit* hits, uint32_t* counts, rtr_query_stats* stats) {
-    const int rc = enqueue_multihit(c, s, rays, rayMasks, n, maxHits, flags, cullMask, after, hits, counts, stats != nullptr, "rtr_trace_rays_multi");
-    if (rc != RTR_OK) return rc;
-    if (stats) memset(stats, 0, sizeof *stats);
-    if (n == 0) return RTR_OK;
-    hipStream_t st = c->stream;
-    if (stats) {      /* copies on the context's stream: the call joins that stream only */
-        Counters h;
-        uint32_t ctrl[rtrdev::kQueryCtrlWords];
-        HIP_TRY(hipMemcpyAsync(&h, c->qCounters.p, sizeof h, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(ctrl, c->qCtrl.p, sizeof ctrl, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        stats->numRays = h.rays; stats->numNodeVisits = h.nodes; stats->numTriTests = h.tris; stats->numAlphaTests = h.alphaTests;
-        stats->tailRays = ctrl[rtrdev::kQueryRedoWord];
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, c->qEv[0], c->qEv[1]));
-        stats->ms = ms;
-    } else HIP_TRY(hipStreamSynchronize(st));
+    return query_join(c, enqueue_multihit(c, s, rays, rayMasks, n, maxHits, flags, cullMask, after, hits, counts, stats != nullptr, "rtr_trace_rays_multi"), n, stats);
+}
+
+/* ---- queued occlusion queries (kernels/rtr_occlusion.hip) ---- */
+int rtr_occlusion_scratch_bytes(uint32_t numRays, size_t* bytes) {
+    if (!bytes) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_occlusion_scratch_bytes: bytes is null");
+    *bytes = occlusion_layout(numRays).bytes;
     return RTR_OK;
 }
 
@@ -2507,42 +2516,28 @@ int rtr_trace_rays_multi(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, con
 static int enqueue_occlusion(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const int32_t* startLeaves, uint32_t n, uint32_t flags, void* scratch,
                              size_t scratchBytes, uint8_t* occluded, bool count, const char* who, const CullMask& cm = NoMask) {
     if (n && !aligned4(startLeaves)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: startLeaves is not 4-B aligned", who);
-    if (!c || !s) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: null context or scene", who);
-    if (cm.masked && (cm.cullMask & ~0xffu)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: cullMask 0x%x has bits above the low 8 (an instance mask is 8 bits)", who, cm.cullMask);
-    if (const int frc = check_query_flags(flags, who)) return frc;
-    if (s->ctx->device != c->device) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: the scene lives on device %d, the context on device %d", who, s->ctx->device, c->device);
+    if (const int rc = check_query(c, s, cm, flags, who)) return rc;
+    if (const int rc = check_same_device(c, s, who)) return rc;
     if (n == 0) return RTR_OK;
     if (!rays || !occluded || !scratch) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: %s is null", who, !rays ? "rays" : (!occluded ? "occluded" : "scratch"));
     if (!aligned16(rays) || !aligned16(occluded) || !aligned16(scratch))
         return fail(RTR_ERR_INVALID_ARGUMENT, "%s: %s is not 16-B aligned", who, !aligned16(rays) ? "rays" : (!aligned16(occluded) ? "occluded" : "scratch"));
     const OcclusionLayout l = occlusion_layout(n);
     if (scratchBytes < l.bytes) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: %zu bytes of scratch, %u rays need %zu (rtr_occlusion_scratch_bytes)", who, scratchBytes, n, l.bytes);
-    HIP_TRY(hipSetDevice(c->device));
-    const int rc = query_scratch(c);
-    if (rc != RTR_OK) return rc;
-    uint32_t overflowCap = l.overflowCap;
-#ifdef RTR_TEST_HOOKS
-    if (const char* e = getenv("RTR_QUERY_REDO_CAP")) { const uint64_t v = strtoull(e, nullptr, 10); if (v >= 1 && v < overflowCap) overflowCap = (uint32_t)v; }   /* a list short enough to overflow */
-#endif
+    if (const int rc = scratch_open(c, count)) return rc;      /* the deep stacks and the counters are the context's */
     hipStream_t st = c->stream;
-    if (c->qLastStream && c->qLastStream != st) HIP_TRY(hipStreamWaitEvent(st, c->qEv[1], 0));      /* the deep stacks and the counters are the context's */
     char* const base = static_cast<char*>(scratch);
     HIP_TRY(hipMemsetAsync(base + l.ctrl, 0, l.overflow + 16u, st));       /* the control block and the count of abandoned rays */
     HIP_TRY(hipMemsetAsync(occluded, 0, n, st));                           /* the walk stores the occluded rays' bytes only */
-    if (count) HIP_TRY(hipMemsetAsync(c->qCounters.p, 0, sizeof(Counters), st));
     HIP_TRY(hipEventRecord(c->qEv[0], st));
     rtrdev::OcclusionArgs oa{};
     oa.rays = reinterpret_cast<const float4*>(rays); oa.occluded = occluded; oa.n = n; oa.batch = rtrdev::occlusion_batch(n);
-    oa.ctrl = reinterpret_cast<uint32_t*>(base + l.ctrl); oa.overflow = reinterpret_cast<uint32_t*>(base + l.overflow); oa.overflowCap = overflowCap;
+    oa.ctrl = reinterpret_cast<uint32_t*>(base + l.ctrl); oa.overflow = reinterpret_cast<uint32_t*>(base + l.overflow); oa.overflowCap = redo_cap(l.overflowCap);
     oa.queue = reinterpret_cast<uint32_t*>(base + l.queue); oa.lists = reinterpret_cast<uint2*>(base + l.lists); oa.listStride = l.listStride;
     oa.startLeaves = startLeaves; oa.numTris = (uint32_t)(s->tree.tris.n / 3);          /* a hint is checked against the records the scene holds */
     const rtrdev::RayMaskArgs rm = ray_mask_args(cm, flags);
-    const hipError_t e = rtrdev::launch_occlusion(s->dev, oa, c->tun, (flags & RTR_QUERY_OPAQUE) == 0u, c->qSpill.p, count ? c->qCounters.p : nullptr, st,
-                                                  (uint32_t)c->prop.multiProcessorCount, rm);
-    if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: kernel launch: %s", who, hipGetErrorString(e));
-    HIP_TRY(hipEventRecord(c->qEv[1], st));
-    c->qLastStream = st;
-    return RTR_OK;
+    return scratch_close(c, rtrdev::launch_occlusion(s->dev, oa, c->tun, (flags & RTR_QUERY_OPAQUE) == 0u, c->qSpill.p, count ? c->qCounters.p : nullptr, st,
+                                                     (uint32_t)c->prop.multiProcessorCount, rm), who);
 }
 
 int rtr_trace_occlusion_async(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, uint32_t n, uint32_t flags, void* scratch, size_t scratchBytes, uint8_t* occluded) {
@@ -2554,9 +2549,6 @@ int rtr_trace_occlusion_hinted_async(rtr_ctx* c, const rtr_scene* s, const RtrRa
     return enqueue_occlusion(c, s, rays, startLeaves, n, flags, scratch, scratchBytes, occluded, false, "rtr_trace_occlusion_hinted_async");
 }
 
-static int occlusion_sync(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const int32_t* startLeaves, uint32_t n, uint32_t flags, void* scratch,
-                          size_t scratchBytes, uint8_t* occluded, rtr_query_stats* stats, const char* who, const CullMask& cm = NoMask);
-
 int rtr_trace_occlusion_masked_async(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const int32_t* startLeaves, const uint8_t* rayMasks, uint32_t n,
                                      uint32_t flags, uint32_t cullMask, void* scratch, size_t scratchBytes, uint8_t* occluded) {
     return enqueue_occlusion(c, s, rays, startLeaves, n, flags, scratch, scratchBytes, occluded, false, "rtr_trace_occlusion_masked_async", CullMask{true, rayMasks, cullMask});
@@ -2564,45 +2556,24 @@ int rtr_trace_occlusion_masked_async(rtr_ctx* c, const rtr_scene* s, const RtrRa
 
 int rtr_trace_occlusion_masked(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const int32_t* startLeaves, const uint8_t* rayMasks, uint32_t n,
                                uint32_t flags, uint32_t cullMask, void* scratch, size_t scratchBytes, uint8_t* occluded, rtr_query_stats* stats) {
-    return occlusion_sync(c, s, rays, startLeaves, n, flags, scratch, scratchBytes, occluded, stats, "rtr_trace_occlusion_masked", CullMask{true, rayMasks, cullMask});
+    return query_join(c, enqueue_occlusion(c, s, rays, startLeaves, n, flags, scratch, scratchBytes, occluded, stats != nullptr, "rtr_trace_occlusion_masked",
+                                           CullMask{true, rayMasks, cullMask}), n, stats, scratch);
 }
 
 int rtr_trace_occlusion(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, uint32_t n, uint32_t flags, void* scratch, size_t scratchBytes, uint8_t* occluded,
                         rtr_query_stats* stats) {
-    return occlusion_sync(c, s, rays, nullptr, n, flags, scratch, scratchBytes, occluded, stats, "rtr_trace_occlusion");
+    return query_join(c, enqueue_occlusion(c, s, rays, nullptr, n, flags, scratch, scratchBytes, occluded, stats != nullptr, "rtr_trace_occlusion"), n, stats, scratch);
 }
 
 int rtr_trace_occlusion_hinted(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const int32_t* startLeaves, uint32_t n, uint32_t flags, void* scratch,
                                size_t scratchBytes, uint8_t* occluded, rtr_query_stats* stats) {
-    return occlusion_sync(c, s, rays, startLeaves, n, flags, scratch, scratchBytes, occluded, stats, "rtr_trace_occlusion_hinted");
-}
-
-static int occlusion_sync(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const int32_t* startLeaves, uint32_t n, uint32_t flags, void* scratch,
-                          size_t scratchBytes, uint8_t* occluded, rtr_query_stats* stats, const char* who, const CullMask& cm) {
-    const int rc = enqueue_occlusion(c, s, rays, startLeaves, n, flags, scratch, scratchBytes, occluded, stats != nullptr, who, cm);
-    if (rc != RTR_OK) return rc;
-    if (stats) memset(stats, 0, sizeof *stats);
-    if (n == 0) return RTR_OK;
-    hipStream_t st = c->stream;
-    if (stats) {      /* copies on the context's stream: the call joins that stream only */
-        Counters h;
-        uint32_t tail = 0;
-        HIP_TRY(hipMemcpyAsync(&h, c->qCounters.p, sizeof h, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(&tail, static_cast<char*>(scratch) + occlusion_layout(n).overflow, sizeof tail, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        stats->numRays = h.rays; stats->numNodeVisits = h.nodes; stats->numTriTests = h.tris; stats->numAlphaTests = h.alphaTests;
-        stats->tailRays = tail;
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, c->qEv[0], c->qEv[1]));
-        stats->ms = ms;
-    } else HIP_TRY(hipStreamSynchronize(st));
-    return RTR_OK;
+    return query_join(c, enqueue_occlusion(c, s, rays, startLeaves, n, flags, scratch, scratchBytes, occluded, stats != nullptr, "rtr_trace_occlusion_hinted"), n, stats, scratch);
 }
 
 /* the checks and the launch of rtr_hit_surfaces[_async], enqueued on the context's stream */
 static int enqueue_surfaces(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, uint32_t n, RtrSurface* out, const char* who) {
-    if (!c || !s) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: null context or scene", who);
-    if (s->ctx->device != c->device) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: the scene lives on device %d, the context on device %d", who, s->ctx->device, c->device);
+    if (const int rc = check_handles(c, s, who)) return rc;
+    if (const int rc = check_same_device(c, s, who)) return rc;
     if (n == 0) return RTR_OK;
     if (!rays || !hits || !out) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: %s is null", who, !rays ? "rays" : (!hits ? "hits" : "out"));
     if (!aligned16(rays) || !aligned16(hits) || !aligned16(out))
@@ -2621,10 +2592,7 @@ int rtr_hit_surfaces_async(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, c
 }
 
 int rtr_hit_surfaces(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, uint32_t n, RtrSurface* out) {
-    const int rc = enqueue_surfaces(c, s, rays, hits, n, out, "rtr_hit_surfaces");
-    if (rc != RTR_OK || n == 0) return rc;
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return RTR_OK;
+    return join_if_enqueued(c, enqueue_surfaces(c, s, rays, hits, n, out, "rtr_hit_surfaces"), n);
 }
 
 /* ---- start hints: the triangle -> leaf table (kernels/rtr_query.hip: k_leaf_table) ---- */
@@ -2658,8 +2626,8 @@ static int enqueue_hit_leaves(rtr_ctx* c, const rtr_scene* s, const RtrHit* hits
         if (!aligned16(hits)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: hits is not 16-B aligned", who);
         if (!aligned4(leaves)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: leaves is not 4-B aligned", who);
     }
-    if (!c || !s) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: null context or scene", who);
-    if (s->ctx->device != c->device) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: the scene lives on device %d, the context on device %d", who, s->ctx->device, c->device);
+    if (const int hrc = check_handles(c, s, who)) return hrc;
+    if (const int drc = check_same_device(c, s, who)) return drc;
     if (n == 0) return RTR_OK;
     HIP_TRY(hipSetDevice(c->device));
     const int rc = ensure_leaf_table(c, s, who);
@@ -2677,10 +2645,7 @@ int rtr_hit_leaves_async(rtr_ctx* c, const rtr_scene* s, const RtrHit* hits, uin
 }
 
 int rtr_hit_leaves(rtr_ctx* c, const rtr_scene* s, const RtrHit* hits, uint32_t n, int32_t* leaves) {
-    const int rc = enqueue_hit_leaves(c, s, hits, n, leaves, "rtr_hit_leaves");
-    if (rc != RTR_OK || n == 0) return rc;
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return RTR_OK;
+    return join_if_enqueued(c, enqueue_hit_leaves(c, s, hits, n, leaves, "rtr_hit_leaves"), n);
 }
 
 int rtr_camera_rays_async(rtr_ctx* c, const RtrCameraData* cam, uint32_t width, uint32_t height, uint32_t spp, RtrRay* out) {
@@ -2723,7 +2688,7 @@ static int enqueue_light(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, con
         if (!aligned4(outLeaves)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: outLeaves is not 4-B aligned", who);
     }
     if (!c || !s || !p) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: null context, scene or params", who);
-    if (s->ctx->device != c->device) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: the scene lives on device %d, the context on device %d", who, s->ctx->device, c->device);
+    if (const int drc = check_same_device(c, s, who)) return drc;
     uint32_t slots = 0;
     const int rc = light_slots(s, p, &slots, who);
     if (rc != RTR_OK) return rc;
@@ -2762,10 +2727,7 @@ int rtr_light_rays_async(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, con
 
 int rtr_light_rays(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, uint32_t n, const rtr_light_params* p,
                    const uint32_t* seeds, RtrRay* outRays) {
-    const int rc = enqueue_light(c, s, rays, hits, n, p, seeds, outRays, nullptr, nullptr, false, "rtr_light_rays");
-    if (rc != RTR_OK || n == 0) return rc;
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return RTR_OK;
+    return join_if_enqueued(c, enqueue_light(c, s, rays, hits, n, p, seeds, outRays, nullptr, nullptr, false, "rtr_light_rays"), n);
 }
 
 int rtr_light_rays_hinted_async(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, uint32_t n, const rtr_light_params* p,
@@ -2775,10 +2737,7 @@ int rtr_light_rays_hinted_async(rtr_ctx* c, const rtr_scene* s, const RtrRay* ra
 
 int rtr_light_rays_hinted(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, uint32_t n, const rtr_light_params* p,
                           const uint32_t* seeds, RtrRay* outRays, int32_t* outLeaves) {
-    const int rc = enqueue_light(c, s, rays, hits, n, p, seeds, outRays, nullptr, nullptr, false, "rtr_light_rays_hinted", outLeaves, true);
-    if (rc != RTR_OK || n == 0) return rc;
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return RTR_OK;
+    return join_if_enqueued(c, enqueue_light(c, s, rays, hits, n, p, seeds, outRays, nullptr, nullptr, false, "rtr_light_rays_hinted", outLeaves, true), n);
 }
 
 int rtr_shade_hits_async(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, uint32_t n, const rtr_light_params* p,
@@ -2788,10 +2747,7 @@ int rtr_shade_hits_async(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, con
 
 int rtr_shade_hits(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, uint32_t n, const rtr_light_params* p,
                    const uint32_t* seeds, const uint8_t* occluded, RtrRadiance* out) {
-    const int rc = enqueue_light(c, s, rays, hits, n, p, seeds, nullptr, occluded, out, true, "rtr_shade_hits");
-    if (rc != RTR_OK || n == 0) return rc;
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return RTR_OK;
+    return join_if_enqueued(c, enqueue_light(c, s, rays, hits, n, p, seeds, nullptr, occluded, out, true, "rtr_shade_hits"), n);
 }
 
 int rtr_tonemap_pack_async(rtr_ctx* c, const float* radiance, uint32_t strideBytes, uint32_t n, uint32_t* out) {
@@ -2807,10 +2763,7 @@ int rtr_tonemap_pack_async(rtr_ctx* c, const float* radiance, uint32_t strideByt
 }
 
 int rtr_tonemap_pack(rtr_ctx* c, const float* radiance, uint32_t strideBytes, uint32_t n, uint32_t* out) {
-    const int rc = rtr_tonemap_pack_async(c, radiance, strideBytes, n, out);
-    if (rc != RTR_OK || n == 0) return rc;
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return RTR_OK;
+    return join_if_enqueued(c, rtr_tonemap_pack_async(c, radiance, strideBytes, n, out), n);
 }
 
 }  // extern "C"

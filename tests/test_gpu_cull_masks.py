@@ -16,7 +16,8 @@ from realtimeraytracer_amd import _abi as A
 from realtimeraytracer_amd import api, host, scenes
 
 from test_gpu_occlusion import assert_same_bytes, camera_light_rays, mixed_rays
-from test_gpu_query import MISS, _deep_scene, _features_setup, assert_hits
+from deep_scene import _deep_scene
+from test_gpu_query import MISS, _features_setup, assert_hits
 
 pytestmark = pytest.mark.gpu
 

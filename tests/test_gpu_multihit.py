@@ -15,7 +15,7 @@ import multihit_witness as M
 import ray_flags_witness as W
 from test_gpu_cull_masks import all_hits, by_custom, counters, scene_of, seeded_masks
 from test_gpu_occlusion import mixed_rays
-from test_gpu_query import _deep_scene
+from deep_scene import _deep_scene
 
 pytestmark = pytest.mark.gpu
 

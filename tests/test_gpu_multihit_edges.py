@@ -17,7 +17,7 @@ from test_gpu_bvh import _with_flags
 from test_gpu_cull_masks import by_custom, counters, seeded_masks
 from test_gpu_multihit import BUILDS, assert_slots
 from test_gpu_occlusion import mixed_rays
-from test_gpu_query import _deep_scene
+from deep_scene import _deep_scene
 from test_gpu_rebuild_async import device_scene, prepared, status
 from test_gpu_rebuild_if import policy_scene
 from test_gpu_update_async import _filler, async_twin, on_device

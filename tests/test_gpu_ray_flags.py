@@ -17,7 +17,8 @@ from realtimeraytracer_amd import api, host, scenes
 import ray_flags_witness as W
 from test_gpu_cull_masks import all_hits, by_custom, counters, leaves_of, scene_of, seeded_masks
 from test_gpu_occlusion import assert_same_bytes, camera_light_rays, mixed_rays
-from test_gpu_query import GOLD, MISS, _deep_scene, assert_hits
+from deep_scene import _deep_scene
+from test_gpu_query import GOLD, MISS, assert_hits
 
 pytestmark = pytest.mark.gpu
 

@@ -915,6 +915,34 @@ int  rtr_shade_hits(rtr_ctx* ctx, const rtr_scene* scene, const RtrRay* rays, co
                     const rtr_light_params* params, const uint32_t* seeds, const uint8_t* occluded, RtrRadiance* out);
 int  rtr_tonemap_pack(rtr_ctx* ctx, const float* radiance, uint32_t strideBytes, uint32_t numValues, uint32_t* outBGRA8);
 
+/* ---- continuation rays for ray-query hits ----------------------------------------------------------------------------------
+ * The second path vertex: for hit k, outRays[k] is ONE direction drawn from the renderer's material at surfaces[k] and outBounce[k] its
+ * throughput weight BRDF * cos / pdf (RtrBounce, include/rtr_types.h), by rtr_bounce_sample of include/rtr_bounce.h — a cosine lobe and
+ * the GGX lobe of alpha = roughness mixed by the one-sample balance heuristic, the BRDF the light loops evaluate.
+ * surfaces are RtrSurface records, rtr_hit_surfaces' output or the caller's edit of it: the call reads NO scene memory and takes no
+ * scene.  rays[k] is the ray that found the hit: its origin gives the view vector normalize(origin - position), rtr_light_rays'
+ * convention.  The random numbers of hit k are rtr_random(s0), (s0 + 100), (s0 + 200), s0 = base_k + frame + 7919 * (depth + 1) in
+ * 32-bit words, base_k = seeds[k], or px * 733 + py * 1933 of the pixel params->width / spp give: rtr_light_rays' rule.
+ * A hit without a continuation (RtrBounce's comment) gets the NULL RAY, which every query answers without a walk, and 32 zero bytes;
+ * every slot of every hit is written, and no output word is a NaN or an infinity.
+ * rays, surfaces, outRays, outBounce: DEVICE pointers, 16-B aligned; seeds 4-B aligned; the outputs must not overlap the inputs.
+ * ENQUEUED on ctx's stream: no allocation, no join, no copy back.  numHits == 0 does nothing.  RTR_ERR_INVALID_ARGUMENT (with a message
+ * that names the function and the argument, and nothing written) for a null or misaligned pointer, lobes == 0 or unknown lobe bits,
+ * width or spp == 0 with seeds == NULL, a normalOffset, tmin or tmax that is not finite, or !(tmax > tmin). */
+int  rtr_bounce_rays_async(rtr_ctx* ctx, const RtrRay* rays, const RtrSurface* surfaces, uint32_t numHits, const rtr_bounce_params* params,
+                           const uint32_t* seeds, RtrRay* outRays, RtrBounce* outBounce);
+/* The same, then joins ctx's stream (only that stream). */
+int  rtr_bounce_rays(rtr_ctx* ctx, const RtrRay* rays, const RtrSurface* surfaces, uint32_t numHits, const rtr_bounce_params* params,
+                     const uint32_t* seeds, RtrRay* outRays, RtrBounce* outBounce);
+/* The host restatement: the same function of the same bytes on HOST pointers, no device (as rtr_host_tree_cost).  The same header
+ * compiled for the host cores; the device's records equal these bit for bit. */
+int  rtr_host_bounce_rays(const RtrRay* rays, const RtrSurface* surfaces, uint32_t numHits, const rtr_bounce_params* params,
+                          const uint32_t* seeds, RtrRay* outRays, RtrBounce* outBounce);
+/* outSin[k], outCos[k] = rtr_sincos_turn(u[k]) of include/rtr_bounce.h, u in [0, 1]: the one function of the sampling contract that is
+ * a polynomial of this library's own, on HOST pointers, so that it can be held to float64 by itself (tests/test_bounce_host.py).
+ * RTR_ERR_INVALID_ARGUMENT for a null pointer with n > 0. */
+int  rtr_host_sincos_turn(const float* u, uint32_t n, float* outSin, float* outCos);
+
 /* ---- errors --------------------------------------------------------------------------- */
 const char* rtr_last_error(void);
 const char* rtr_status_string(int status);

@@ -226,6 +226,25 @@ typedef struct RtrRadiance {
     float    analytic[3];   uint32_t _r1;
 } RtrRadiance;
 
+/* ---- continuation rays (rtr_bounce_rays): one BRDF-sampled direction per hit and its throughput weight ------------------------
+ * What a path tracer multiplies its throughput by when it follows RtrRay next from the hit: weight = BRDF * cos / pdf per channel, the
+ * renderer's Cook-Torrance BRDF (include/rtr_bounce.h), pdf = the mixture density the direction was drawn from.  32 B, two 16-B stores.
+ * A DEAD record — no continuation: not an object, a direction below the surface, a non-finite input — is 32 zero bytes beside the null
+ * ray.  lobe: the RTR_BOUNCE_* lobe the direction was drawn from, 0 when dead; pSpecular: the probability the specular lobe had. */
+#define RTR_BOUNCE_DIFFUSE  1u
+#define RTR_BOUNCE_SPECULAR 2u
+typedef struct RtrBounce {
+    float    weight[3]; float pdf;
+    uint32_t lobe;      float pSpecular; uint32_t _reserved[2];
+} RtrBounce;
+
+typedef struct rtr_bounce_params {
+    uint32_t frame, depth;    /* enter every seed: s0 = seedBase + frame + 7919 * (depth + 1) */
+    uint32_t width, spp;      /* hit k belongs to pixel ((k / spp) % width, (k / spp) / width), as in rtr_light_params.  Used when seeds == NULL */
+    uint32_t lobes;           /* RTR_BOUNCE_DIFFUSE | RTR_BOUNCE_SPECULAR: the lobes that may be sampled */
+    float    normalOffset, tmin, tmax;   /* the next ray: origin position + normalOffset * normal, [tmin, tmax].  The shader's shadow rays: 0.01, 0.001, 10000 */
+} rtr_bounce_params;          /* 32 bytes */
+
 #ifdef __cplusplus
 }
 #endif
@@ -245,6 +264,8 @@ static_assert(sizeof(RtrRay) == 32, "ray must be 32 B");
 static_assert(sizeof(RtrHit) == 32, "hit must be 32 B");
 static_assert(sizeof(RtrSurface) == 80, "surface must be 80 B");
 static_assert(sizeof(RtrRadiance) == 48, "radiance must be 48 B");
+static_assert(sizeof(RtrBounce) == 32, "bounce record must be 32 B");
+static_assert(sizeof(rtr_bounce_params) == 32, "bounce params must be 32 B");
 #endif
 
 #endif /* RTR_TYPES_H */

@@ -85,6 +85,14 @@ class rtr_light_params(C.Structure):
                 ("_pad", u32 * 2)]
 
 
+class RtrBounce(C.Structure):
+    _fields_ = [("weight", f32 * 3), ("pdf", f32), ("lobe", u32), ("pSpecular", f32), ("_reserved", u32 * 2)]
+
+
+class rtr_bounce_params(C.Structure):
+    _fields_ = [("frame", u32), ("depth", u32), ("width", u32), ("spp", u32), ("lobes", u32), ("normalOffset", f32), ("tmin", f32), ("tmax", f32)]
+
+
 class rtr_vertex_range(C.Structure):
     """one range of rtr_scene_update_vertices: vertices firstVertex ... + numVertices of the scene's concatenated vertex array"""
     _fields_ = [("firstVertex", u32), ("numVertices", u32), ("positions", C.c_void_p), ("normals", C.c_void_p)]
@@ -163,6 +171,7 @@ assert C.sizeof(RtrBvhNode) == 32 and C.sizeof(RtrBvhGrid) == 32 and C.sizeof(Rt
 assert C.sizeof(RtrRay) == 32 and C.sizeof(RtrHit) == 32 and C.sizeof(rtr_query_stats) == 48
 assert C.sizeof(RtrSurface) == 80
 assert C.sizeof(RtrRadiance) == 48 and C.sizeof(rtr_light_params) == 32
+assert C.sizeof(RtrBounce) == 32 and C.sizeof(rtr_bounce_params) == 32
 assert C.sizeof(rtr_vertex_range) == 24
 assert C.sizeof(rtr_tree_cost) == 96 and C.alignment(rtr_tree_cost) == 8
 assert C.sizeof(rtr_update_status) == 32
@@ -188,6 +197,7 @@ QUERY_CULL_BACK_FACING, QUERY_CULL_FRONT_FACING, QUERY_CULL_OPAQUE, QUERY_CULL_N
 MULTIHIT_MAX = 8        # RTR_MULTIHIT_MAX: the most hits per ray one rtr_trace_rays_multi call reports
 SURFACE_MISS, SURFACE_OBJECT, SURFACE_LIGHT, SURFACE_INVALID = 0, 1, 2, 3
 LIGHT_SHADOWED, LIGHT_UNSHADOWED, LIGHT_ANALYTIC = 1, 2, 4
+BOUNCE_DIFFUSE, BOUNCE_SPECULAR = 1, 2
 VERTICES_HOST, VERTICES_DEVICE = 0, 1
 
 P = C.POINTER
@@ -280,6 +290,10 @@ RTR_SYMBOLS = {
     "rtr_shade_hits": (C.c_int, [VP, VP, VP, VP, u32, P(rtr_light_params), VP, VP, VP]),
     "rtr_tonemap_pack_async": (C.c_int, [VP, VP, u32, u32, VP]),
     "rtr_tonemap_pack": (C.c_int, [VP, VP, u32, u32, VP]),
+    "rtr_bounce_rays_async": (C.c_int, [VP, VP, VP, u32, P(rtr_bounce_params), VP, VP, VP]),
+    "rtr_bounce_rays": (C.c_int, [VP, VP, VP, u32, P(rtr_bounce_params), VP, VP, VP]),
+    "rtr_host_bounce_rays": (C.c_int, [VP, VP, u32, P(rtr_bounce_params), VP, VP, VP]),
+    "rtr_host_sincos_turn": (C.c_int, [VP, u32, VP, VP]),
 }
 
 RTRH_SYMBOLS = {

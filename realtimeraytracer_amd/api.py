@@ -1157,3 +1157,157 @@ def direct_light(scene, rays, hits=None, params=None, seeds=None, ctx=None, max_
                    else trace_rays(scene, lr, any_hit=True, ctx=ctx, cull_mask=shadow_cull_mask, ray_flags=shadow_ray_flags)).occluded
         out[a:b] = shade_hits(scene, r, h, params, occ, seeds=sd, ctx=ctx).raw
     return _radiance_result(out, False, torch)
+
+
+# ---- continuation rays for ray-query hits (rtr_bounce_rays) and the path they make (path_trace) ------------------------------------
+class BounceResult:
+    """What bounce_rays and host_bounce_rays give back.  rays: the (N, 8) float32 RtrRay of the continuation (eight zeros: no
+    continuation).  raw: the (N, 8) float32 array of RtrBounce records, of which weight (N, 3) and pdf, p_specular (N,) are float32
+    views and lobe (A.BOUNCE_*, 0 = dead) an int32 view."""
+    rays = raw = weight = pdf = lobe = p_specular = None
+
+
+def _bounce_result(rays, raw, as_numpy, torch):
+    res = BounceResult()
+    words = raw.view(np.int32) if as_numpy else raw.view(torch.int32)
+    res.rays, res.raw = rays, raw
+    res.weight, res.pdf, res.lobe, res.p_specular = raw[:, 0:3], raw[:, 3], words[:, 4], raw[:, 5]
+    return res
+
+
+def make_bounce_params(frame=0, depth=0, width=0, spp=1, lobes=A.BOUNCE_DIFFUSE | A.BOUNCE_SPECULAR, normal_offset=0.01, tmin=0.001, tmax=10000.0):
+    """rtr_bounce_params.  frame and depth enter every seed; width / spp say which pixel a hit belongs to (camera_rays' order) and matter
+    only without explicit seeds; normal_offset, tmin, tmax: the continuation ray (the defaults are the shader's shadow-ray numbers)"""
+    return A.rtr_bounce_params(int(frame) & 0xffffffff, int(depth) & 0xffffffff, int(width), int(spp), int(lobes), float(normal_offset), float(tmin), float(tmax))
+
+
+def bounce_rays(ctx, rays, surfaces, params, seeds=None, asynchronous=False):
+    """rtr_bounce_rays: one BRDF-sampled continuation ray per hit and its throughput weight -> BounceResult.  rays: the float32 (N, 8)
+    rays that found the hits; surfaces: hit_surfaces' SurfaceResult or its (N, 20) float32 raw records (edited or not: no scene is read);
+    seeds: int32 (N,) seed bases, default the pixel's (params.width, params.spp).  Device tensors in give device tensors out, numpy in
+    gives numpy out; asynchronous as in trace_rays: the context must then be on torch's current stream."""
+    torch = _torch()
+    dev = torch.device("cuda", ctx.device)
+    if isinstance(surfaces, SurfaceResult):
+        surfaces = surfaces.raw
+    r, rn = _device_array(torch, rays, torch.float32, np.float32, "rays", dev, "bounce_rays")
+    sn = isinstance(surfaces, np.ndarray)
+    if sn != rn:
+        raise ValueError("bounce_rays: rays and surfaces must both be numpy arrays or both be tensors")
+    if sn:
+        if surfaces.dtype != np.float32 or surfaces.ndim != 2 or surfaces.shape[1] != 20:
+            raise ValueError(f"bounce_rays: surfaces must be float32 (N, 20), got {surfaces.dtype} {surfaces.shape}")
+        s = torch.from_numpy(np.ascontiguousarray(surfaces)).to(dev)
+    else:
+        s = surfaces
+        if not isinstance(s, torch.Tensor) or s.dtype != torch.float32 or s.dim() != 2 or s.shape[1] != 20 or s.device != dev or not s.is_contiguous():
+            raise ValueError(f"bounce_rays: surfaces must be a contiguous float32 (N, 20) tensor on {dev}")
+    if r.shape[0] != s.shape[0]:
+        raise ValueError(f"bounce_rays: {r.shape[0]} rays but {s.shape[0]} surfaces")
+    n = int(r.shape[0])
+    sd = _device_vector(torch, seeds, torch.int32, (np.int32, np.uint32), n, "seeds", dev, "bounce_rays")
+    _check_async(ctx, torch, dev, "bounce_rays", asynchronous)
+    out_rays = torch.empty((n, 8), dtype=torch.float32, device=dev)
+    out_b = torch.empty((n, 8), dtype=torch.float32, device=dev)
+    _join_torchs_stream(ctx, torch, dev, asynchronous)
+    fn, who = (ctx.lib.rtr_bounce_rays_async, "rtr_bounce_rays_async") if asynchronous else (ctx.lib.rtr_bounce_rays, "rtr_bounce_rays")
+    if n:
+        _check(fn(ctx.h, A.VP(r.data_ptr()), A.VP(s.data_ptr()), n, C.byref(params), A.VP(sd.data_ptr()) if sd is not None else None,
+                  A.VP(out_rays.data_ptr()), A.VP(out_b.data_ptr())), who)
+    else:
+        _check(fn(ctx.h, None, None, 0, C.byref(params), None, None, None), who)
+    res = _bounce_result(out_rays.cpu().numpy(), out_b.cpu().numpy(), True, torch) if rn else _bounce_result(out_rays, out_b, False, torch)
+    res._keep = (r, s, sd)               # an asynchronous call's inputs stay alive with its result
+    return res
+
+
+def host_bounce_rays(rays, surfaces, params, seeds=None):
+    """rtr_host_bounce_rays: the host restatement of bounce_rays on numpy arrays, no device -> BounceResult of numpy arrays.  rays float32
+    (N, 8), surfaces float32 (N, 20) (or 32-bit words of that shape), seeds int32 / uint32 (N,) or None."""
+    lib = A.hip_lib()
+    r = np.ascontiguousarray(rays)
+    s = np.ascontiguousarray(surfaces)
+    if r.dtype != np.float32 or r.ndim != 2 or r.shape[1] != 8:
+        raise ValueError(f"host_bounce_rays: rays must be float32 (N, 8), got {r.dtype} {r.shape}")
+    if s.dtype.itemsize != 4 or s.ndim != 2 or s.shape[1] != 20 or s.shape[0] != r.shape[0]:
+        raise ValueError(f"host_bounce_rays: surfaces must be 32-bit words ({r.shape[0]}, 20), got {s.dtype} {s.shape}")
+    n = int(r.shape[0])
+    sd = None
+    if seeds is not None:
+        sd = np.ascontiguousarray(seeds)
+        if sd.dtype not in (np.int32, np.uint32) or sd.shape != (n,):
+            raise ValueError(f"host_bounce_rays: seeds must be int32 or uint32 ({n},), got {sd.dtype} {sd.shape}")
+    out_rays = np.zeros((n, 8), np.float32)
+    out_b = np.zeros((n, 8), np.float32)
+    if n:
+        _check(lib.rtr_host_bounce_rays(r.ctypes.data_as(A.VP), s.ctypes.data_as(A.VP), n, C.byref(params), sd.ctypes.data_as(A.VP) if sd is not None else None,
+                                        out_rays.ctypes.data_as(A.VP), out_b.ctypes.data_as(A.VP)), "rtr_host_bounce_rays")
+    return _bounce_result(out_rays, out_b, True, None)
+
+
+class PathResult:
+    """What path_trace gives back: radiance (N, 3) float32, the sum of per_depth, a list of bounces + 1 (N, 3) tensors — entry d is what
+    the path's vertex d contributes, already multiplied by the throughput up to it."""
+    radiance = per_depth = None
+
+
+PATH_SEED_STEP = 0x9E3779B1      # the direct-light seeds of vertex d are the bases + d * this (32-bit words)
+
+
+def _wrap32(x):
+    """an int64 tensor's low 32 bits as int32 (the two's-complement word), without leaning on an out-of-range conversion"""
+    x = x & 0xffffffff
+    return (x - ((x >> 31) << 32)).to(_torch().int32)
+
+
+def path_trace(scene, rays, light_params, bounces, seeds=None, occlusion="dense", bounce_cull_mask=None, bounce_ray_flags=0, max_ray_bytes=256 << 20, ctx=None):
+    """N-bounce global illumination from the public parts, all on the device:
+
+        T = 1, L = 0, r = rays
+        for d in 0 ... bounces:
+            q    = trace_rays(scene, r)                      (from d = 1 on with cull_mask=bounce_cull_mask, ray_flags=bounce_ray_flags)
+            rad  = direct_light(scene, r, q, light_params, seeds = seeds if d == 0 else base + d * PATH_SEED_STEP).shadowed
+            rad  = 0 where d >= 1 and the hit is a light     (next-event estimation counted that light at the vertex before)
+            L   += T * rad;  per_depth.append(T * rad)
+            if d == bounces: break
+            b    = bounce_rays(ctx, r, hit_surfaces(scene, r, q), make_bounce_params(light_params.frame, d, width, spp), seeds)
+            T   *= b.weight;  r = b.rays                      (a dead path carries the null ray and T = 0 from here on)
+
+    base: the explicit seeds, or, with seeds=None, the pixels' px * 733 + py * 1933 from light_params.width / spp, built once.  rays: a
+    float32 (N, 8) device tensor; light_params: make_light_params(...); occlusion, max_ray_bytes as direct_light takes them.
+    bounce_cull_mask: e.g. the complement of the emitters' mask bit keeps bounce rays off the lights.  No Russian roulette and no
+    compaction of dead paths: their null rays cost no walk.  -> PathResult."""
+    torch = _torch()
+    ctx = ctx or scene.ctx
+    bounces = int(bounces)
+    if bounces < 0:
+        raise ValueError(f"path_trace: bounces must be >= 0, got {bounces}")
+    if not isinstance(rays, torch.Tensor):
+        raise ValueError("path_trace: rays must be a device tensor")
+    n = int(rays.shape[0])
+    base = seeds
+    if base is None and bounces > 0:
+        k = torch.arange(n, device=rays.device, dtype=torch.int64) // int(light_params.spp)
+        base = _wrap32((k % int(light_params.width)) * 733 + (k // int(light_params.width)) * 1933)      # 32-bit words, as the kernel's
+    res = PathResult()
+    res.per_depth = []
+    res.radiance = torch.zeros((n, 3), dtype=torch.float32, device=rays.device)
+    T = torch.ones((n, 3), dtype=torch.float32, device=rays.device)
+    r = rays
+    for d in range(bounces + 1):
+        q = trace_rays(scene, r, ctx=ctx) if d == 0 else trace_rays(scene, r, ctx=ctx, cull_mask=bounce_cull_mask, ray_flags=bounce_ray_flags)
+        sd = seeds if d == 0 else _wrap32(base.to(torch.int64) + d * PATH_SEED_STEP)
+        lit = direct_light(scene, r, q, light_params, seeds=sd, ctx=ctx, max_ray_bytes=max_ray_bytes, occlusion=occlusion)
+        rad = lit.shadowed
+        if d >= 1:
+            rad = torch.where((lit.kind == A.SURFACE_LIGHT).unsqueeze(1), torch.zeros_like(rad), rad)
+        term = T * rad
+        res.per_depth.append(term)
+        res.radiance = res.radiance + term
+        if d == bounces:
+            break
+        b = bounce_rays(ctx, r, hit_surfaces(scene, r, q, ctx=ctx),
+                        make_bounce_params(frame=light_params.frame, depth=d, width=light_params.width, spp=light_params.spp), seeds=seeds)
+        T = T * b.weight
+        r = b.rays
+    return res

@@ -11,6 +11,8 @@
 #include "kernels/rtr_mirrored.h"
 #include "kernels/rtr_tree_sah.h"
 #include "kernels/rtr_query.h"
+#include "kernels/rtr_bounce_launch.h"
+#include "rtr_bounce_host.h"
 
 #include <hip/hip_runtime.h>
 
@@ -288,6 +290,9 @@ struct rtr_frame {
     uint32_t* image_ptr(int which) const { return ext[which] ? ext[which] : img[which].p; }
     float4* hdr_ptr() const { return extHdr ? extHdr : hdr.p; }
 };
+
+/* rtr_bounce_host.cpp's way to this thread's error text */
+void rtrdev::set_last_error(const char* msg) { g_err = msg; }
 
 extern "C" {
 
@@ -2764,6 +2769,32 @@ int rtr_tonemap_pack_async(rtr_ctx* c, const float* radiance, uint32_t strideByt
 
 int rtr_tonemap_pack(rtr_ctx* c, const float* radiance, uint32_t strideBytes, uint32_t n, uint32_t* out) {
     return join_if_enqueued(c, rtr_tonemap_pack_async(c, radiance, strideBytes, n, out), n);
+}
+
+/* ---- continuation rays for ray-query hits (kernels/rtr_bounce.hip; the host form is rtr_bounce_host.cpp) -------------------------- */
+static int enqueue_bounce(rtr_ctx* c, const RtrRay* rays, const RtrSurface* surfaces, uint32_t n, const rtr_bounce_params* p, const uint32_t* seeds,
+                          RtrRay* outRays, RtrBounce* outBounce, const char* who) {
+    char msg[256];       /* the arrays and the params are checked first, which needs nothing of the handle */
+    if (n && !rtrdev::bounce_check_args(who, rays, surfaces, n, p, seeds, outRays, outBounce, msg, sizeof msg)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s", msg);
+    if (!c) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: ctx is null", who);
+    if (n == 0) return RTR_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    rtrdev::BounceArgs a{};
+    a.rays = reinterpret_cast<const float4*>(rays); a.surfaces = reinterpret_cast<const float4*>(surfaces); a.seeds = seeds;
+    a.outRays = reinterpret_cast<float4*>(outRays); a.outBounce = reinterpret_cast<float4*>(outBounce); a.params = *p; a.n = n;
+    const hipError_t e = rtrdev::launch_bounce_rays(a, c->stream);
+    if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: kernel launch: %s", who, hipGetErrorString(e));
+    return RTR_OK;
+}
+
+int rtr_bounce_rays_async(rtr_ctx* c, const RtrRay* rays, const RtrSurface* surfaces, uint32_t n, const rtr_bounce_params* p, const uint32_t* seeds,
+                          RtrRay* outRays, RtrBounce* outBounce) {
+    return enqueue_bounce(c, rays, surfaces, n, p, seeds, outRays, outBounce, "rtr_bounce_rays_async");
+}
+
+int rtr_bounce_rays(rtr_ctx* c, const RtrRay* rays, const RtrSurface* surfaces, uint32_t n, const rtr_bounce_params* p, const uint32_t* seeds,
+                    RtrRay* outRays, RtrBounce* outBounce) {
+    return join_if_enqueued(c, enqueue_bounce(c, rays, surfaces, n, p, seeds, outRays, outBounce, "rtr_bounce_rays"), n);
 }
 
 }  // extern "C"

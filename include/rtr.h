@@ -943,6 +943,43 @@ int  rtr_host_bounce_rays(const RtrRay* rays, const RtrSurface* surfaces, uint32
  * RTR_ERR_INVALID_ARGUMENT for a null pointer with n > 0. */
 int  rtr_host_sincos_turn(const float* u, uint32_t n, float* outSin, float* outCos);
 
+/* ---- compaction of live paths, with Russian roulette -------------------------------------------------------------------------
+ * Between two vertices of a path tracer's wavefront: the paths that go on are gathered to the front of every array IN THEIR ORDER
+ * (a stable compaction), the rest of every array is cleared.  Which paths go on is rtr_path_survive of include/rtr_paths.h: a path is
+ * LIVE when its ray would cost a walk (origin and direction finite, direction not zero, tmax > tmin), every channel of its throughput
+ * is finite and >= 0 and one is > 0; with RTR_COMPACT_ROULETTE a live path of p = max(max3(T), survivalFloor) < 1 goes on with
+ * probability p — iff rtr_random(seeds[k] + frame + 7919 * (depth + 1) + 300) < p, the fourth random number of the vertex whose
+ * rtr_bounce_rays took the first three — and with throughput T / p.
+ * Inputs, DEVICE pointers: rays (16-B aligned); throughput: path k's three floats are at (char*)throughput + k * throughputStrideBytes
+ * (a multiple of 4, at least 12; 4-B aligned — an RtrBounce array is passed as it is with stride 32); seeds (4-B aligned) or NULL:
+ * then outSeeds must be NULL too and the roulette is refused; pathIds or NULL: path k has id k.
+ * Outputs: ALL numPaths slots of each are written.  With count survivors, slot j < count holds the j-th survivor in input order: its
+ * ray's 32 bytes, its throughput as PACKED floats (stride 12), its seed and its id; slot j >= count holds the null ray, zero
+ * throughput, seed 0 and id RTR_PATH_NONE; *outCount = count, a DEVICE word.  A caller that never joins keeps launching numPaths wide,
+ * its dead lanes gathered into whole dead waves at the end; one that reads the count shrinks every later launch.  Chained calls
+ * compose the ids: the second call's ids index the first call's input.
+ * scratch: rtr_compact_scratch_bytes(numPaths) bytes of device memory the CALLER owns (a multiple of 16, monotone in numPaths; pure
+ * arithmetic), 16-B aligned; it need not be initialised and nothing is kept in it between calls.
+ * ENQUEUED on ctx's stream, three launches: no allocation, no join, no copy back.  numPaths == 0 writes *outCount = 0 when outCount
+ * is not NULL, and nothing else.  RTR_ERR_INVALID_ARGUMENT (with a message that names the function and the argument, and nothing
+ * written) for a null or misaligned pointer the call needs (outSeeds exactly when seeds; outCount), a scratch that is too small, a
+ * stride that is not a multiple of 4 or below 12, unknown flag bits, the roulette without seeds, a survivalFloor outside (0, 1] with
+ * the roulette, non-zero _reserved words, or an output range (the scratch and the count included) that overlaps an input range or
+ * another output. */
+int  rtr_compact_scratch_bytes(uint32_t numPaths, size_t* bytes);
+int  rtr_compact_paths_async(rtr_ctx* ctx, const RtrRay* rays, const float* throughput, const uint32_t* seeds, const uint32_t* pathIds,
+                             uint32_t numPaths, const rtr_compact_params* params, void* scratch, size_t scratchBytes,
+                             RtrRay* outRays, float* outThroughput, uint32_t* outSeeds, uint32_t* outPathIds, uint32_t* outCount);
+/* The same, then joins ctx's stream (only that stream).  hostCount: NULL, or where one 4-byte copy after the join puts the count. */
+int  rtr_compact_paths(rtr_ctx* ctx, const RtrRay* rays, const float* throughput, const uint32_t* seeds, const uint32_t* pathIds,
+                       uint32_t numPaths, const rtr_compact_params* params, void* scratch, size_t scratchBytes,
+                       RtrRay* outRays, float* outThroughput, uint32_t* outSeeds, uint32_t* outPathIds, uint32_t* outCount, uint32_t* hostCount);
+/* The host restatement: the same function of the same bytes on HOST pointers, no device, no scratch; outCount is a host word.  The same
+ * header in a plain loop; the device's words equal these bit for bit. */
+int  rtr_host_compact_paths(const RtrRay* rays, const float* throughput, const uint32_t* seeds, const uint32_t* pathIds,
+                            uint32_t numPaths, const rtr_compact_params* params,
+                            RtrRay* outRays, float* outThroughput, uint32_t* outSeeds, uint32_t* outPathIds, uint32_t* outCount);
+
 /* ---- errors --------------------------------------------------------------------------- */
 const char* rtr_last_error(void);
 const char* rtr_status_string(int status);

@@ -245,6 +245,21 @@ typedef struct rtr_bounce_params {
     float    normalOffset, tmin, tmax;   /* the next ray: origin position + normalOffset * normal, [tmin, tmax].  The shader's shadow rays: 0.01, 0.001, 10000 */
 } rtr_bounce_params;          /* 32 bytes */
 
+/* ---- path compaction (rtr_compact_paths): the live paths of a wavefront, gathered to the front in their order ------------------
+ * frame and depth enter the roulette's seed: u = rtr_random(seed + frame + 7919 * (depth + 1) + 300), the fourth random number of the
+ * vertex whose rtr_bounce_rays took + 0, + 100 and + 200.  flags: RTR_COMPACT_ROULETTE or 0.  survivalFloor: the least survival
+ * probability of the roulette, in (0, 1] (read only with the flag).  throughputStrideBytes: the distance between two paths' throughputs
+ * in the INPUT, a multiple of 4 and at least 12 (32: the weight column of RtrBounce records as they are).  _reserved must be 0.
+ * RTR_PATH_NONE is the path id of an output slot behind the survivors.  The rule itself is include/rtr_paths.h. */
+#define RTR_COMPACT_ROULETTE 1u
+#define RTR_PATH_NONE 0xffffffffu
+typedef struct rtr_compact_params {
+    uint32_t frame, depth, flags;
+    float    survivalFloor;
+    uint32_t throughputStrideBytes;
+    uint32_t _reserved[3];
+} rtr_compact_params;         /* 32 bytes */
+
 #ifdef __cplusplus
 }
 #endif
@@ -266,6 +281,7 @@ static_assert(sizeof(RtrSurface) == 80, "surface must be 80 B");
 static_assert(sizeof(RtrRadiance) == 48, "radiance must be 48 B");
 static_assert(sizeof(RtrBounce) == 32, "bounce record must be 32 B");
 static_assert(sizeof(rtr_bounce_params) == 32, "bounce params must be 32 B");
+static_assert(sizeof(rtr_compact_params) == 32, "compact params must be 32 B");
 #endif
 
 #endif /* RTR_TYPES_H */

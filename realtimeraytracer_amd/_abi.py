@@ -93,6 +93,10 @@ class rtr_bounce_params(C.Structure):
     _fields_ = [("frame", u32), ("depth", u32), ("width", u32), ("spp", u32), ("lobes", u32), ("normalOffset", f32), ("tmin", f32), ("tmax", f32)]
 
 
+class rtr_compact_params(C.Structure):
+    _fields_ = [("frame", u32), ("depth", u32), ("flags", u32), ("survivalFloor", f32), ("throughputStrideBytes", u32), ("_reserved", u32 * 3)]
+
+
 class rtr_vertex_range(C.Structure):
     """one range of rtr_scene_update_vertices: vertices firstVertex ... + numVertices of the scene's concatenated vertex array"""
     _fields_ = [("firstVertex", u32), ("numVertices", u32), ("positions", C.c_void_p), ("normals", C.c_void_p)]
@@ -172,6 +176,7 @@ assert C.sizeof(RtrRay) == 32 and C.sizeof(RtrHit) == 32 and C.sizeof(rtr_query_
 assert C.sizeof(RtrSurface) == 80
 assert C.sizeof(RtrRadiance) == 48 and C.sizeof(rtr_light_params) == 32
 assert C.sizeof(RtrBounce) == 32 and C.sizeof(rtr_bounce_params) == 32
+assert C.sizeof(rtr_compact_params) == 32
 assert C.sizeof(rtr_vertex_range) == 24
 assert C.sizeof(rtr_tree_cost) == 96 and C.alignment(rtr_tree_cost) == 8
 assert C.sizeof(rtr_update_status) == 32
@@ -198,6 +203,8 @@ MULTIHIT_MAX = 8        # RTR_MULTIHIT_MAX: the most hits per ray one rtr_trace_
 SURFACE_MISS, SURFACE_OBJECT, SURFACE_LIGHT, SURFACE_INVALID = 0, 1, 2, 3
 LIGHT_SHADOWED, LIGHT_UNSHADOWED, LIGHT_ANALYTIC = 1, 2, 4
 BOUNCE_DIFFUSE, BOUNCE_SPECULAR = 1, 2
+COMPACT_ROULETTE = 1            # RTR_COMPACT_ROULETTE
+PATH_NONE = 0xffffffff          # RTR_PATH_NONE: the path id of a slot behind the survivors
 VERTICES_HOST, VERTICES_DEVICE = 0, 1
 
 P = C.POINTER
@@ -293,6 +300,10 @@ RTR_SYMBOLS = {
     "rtr_bounce_rays_async": (C.c_int, [VP, VP, VP, u32, P(rtr_bounce_params), VP, VP, VP]),
     "rtr_bounce_rays": (C.c_int, [VP, VP, VP, u32, P(rtr_bounce_params), VP, VP, VP]),
     "rtr_host_bounce_rays": (C.c_int, [VP, VP, u32, P(rtr_bounce_params), VP, VP, VP]),
+    "rtr_compact_scratch_bytes": (C.c_int, [u32, P(C.c_size_t)]),
+    "rtr_compact_paths_async": (C.c_int, [VP, VP, VP, VP, VP, u32, P(rtr_compact_params), VP, C.c_size_t, VP, VP, VP, VP, VP]),
+    "rtr_compact_paths": (C.c_int, [VP, VP, VP, VP, VP, u32, P(rtr_compact_params), VP, C.c_size_t, VP, VP, VP, VP, VP, P(u32)]),
+    "rtr_host_compact_paths": (C.c_int, [VP, VP, VP, VP, u32, P(rtr_compact_params), VP, VP, VP, VP, P(u32)]),
     "rtr_host_sincos_turn": (C.c_int, [VP, u32, VP, VP]),
 }
 

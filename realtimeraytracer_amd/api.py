@@ -1245,10 +1245,139 @@ def host_bounce_rays(rays, surfaces, params, seeds=None):
     return _bounce_result(out_rays, out_b, True, None)
 
 
+# ---- compaction of live paths, with Russian roulette (rtr_compact_paths) -------------------------------------------------------------
+class CompactResult:
+    """What compact_paths and host_compact_paths give back, every array N long: rays (N, 8) float32, throughput (N, 3) float32, seeds
+    (N,) int32 or None (no seeds went in), path_ids (N,) int32 (-1 = A.PATH_NONE behind the survivors).  The first count rows are the
+    survivors in input order; the rest are the null ray, zero throughput, seed 0.  count_tensor: the 1-element int32 device tensor the
+    count was written to; count: that number as an int, read on first use — the only join (numpy results carry it already)."""
+    rays = throughput = seeds = path_ids = count_tensor = None
+    _count = None
+
+    @property
+    def count(self):
+        if self._count is None:
+            self._count = int(self.count_tensor.item()) & 0xffffffff
+        return self._count
+
+
+def make_compact_params(frame=0, depth=0, roulette=False, survival_floor=0.05, throughput_stride=12):
+    """rtr_compact_params.  frame and depth enter the roulette's seed and are those of the bounce before (make_bounce_params); roulette:
+    RTR_COMPACT_ROULETTE; survival_floor: the least survival probability, in (0, 1]; throughput_stride: bytes between two paths'
+    throughputs in the input (compact_paths sets it from the array it is given)"""
+    return A.rtr_compact_params(int(frame) & 0xffffffff, int(depth) & 0xffffffff, A.COMPACT_ROULETTE if roulette else 0, float(survival_floor),
+                                int(throughput_stride), (A.u32 * 3)(0, 0, 0))
+
+
+def _with_stride(params, stride):
+    return A.rtr_compact_params(params.frame, params.depth, params.flags, params.survivalFloor, int(stride), params._reserved)
+
+
+def compact_scratch_bytes(lib, n):
+    """rtr_compact_scratch_bytes(n)"""
+    b = C.c_size_t(0)
+    _check(lib.rtr_compact_scratch_bytes(int(n), C.byref(b)), "rtr_compact_scratch_bytes")
+    return int(b.value)
+
+
+def compact_paths(ctx, rays, throughput, seeds=None, path_ids=None, params=None, asynchronous=False):
+    """rtr_compact_paths: the live paths gathered to the front in their order, the rest cleared -> CompactResult (the rule: include/rtr.h,
+    include/rtr_paths.h).  rays: float32 (N, 8); throughput: float32 (N, 3) — contiguous, or a view of the first three columns of wider
+    rows, as BounceResult.weight is — or the (N, 8) raw RtrBounce records themselves (stride 32 either way); seeds, path_ids: int32 (N,)
+    or None (no roulette without seeds; None ids: path k is k); params: make_compact_params(...), default no roulette — its
+    throughput_stride is replaced by the array's.  Device tensors in give device tensors out and NO join: the count stays on the device
+    until CompactResult.count is read; numpy in gives numpy out.  The scratch is a tensor of this call's own, kept alive with the
+    result.  asynchronous as in trace_rays: the context must then be on torch's current stream."""
+    torch = _torch()
+    dev = torch.device("cuda", ctx.device)
+    who = "compact_paths"
+    params = params if params is not None else make_compact_params()
+    r, rn = _device_array(torch, rays, torch.float32, np.float32, "rays", dev, who)
+    n = int(r.shape[0])
+    t = throughput
+    if isinstance(t, np.ndarray) != rn:
+        raise ValueError(f"{who}: rays and throughput must both be numpy arrays or both be tensors")
+    if rn:
+        if t.dtype != np.float32 or t.ndim != 2 or t.shape[0] != n or t.shape[1] not in (3, 8):
+            raise ValueError(f"{who}: throughput must be float32 ({n}, 3) or ({n}, 8), got {t.dtype} {t.shape}")
+        t = torch.from_numpy(np.ascontiguousarray(t)).to(dev)
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 2 or t.shape[0] != n or t.shape[1] not in (3, 8) or t.device != dev:
+        raise ValueError(f"{who}: throughput must be a float32 ({n}, 3) or ({n}, 8) tensor on {dev}")
+    if n and (t.stride(1) != 1 or (n > 1 and t.stride(0) < 3)):
+        raise ValueError(f"{who}: the three floats of a throughput row must be adjacent and the rows apart")
+    stride = 4 * int(t.stride(0)) if n > 1 else 4 * int(t.shape[1])
+    sd = _device_vector(torch, seeds, torch.int32, (np.int32, np.uint32), n, "seeds", dev, who, as_numpy=rn)
+    ids = _device_vector(torch, path_ids, torch.int32, (np.int32, np.uint32), n, "path_ids", dev, who, as_numpy=rn)
+    _check_async(ctx, torch, dev, who, asynchronous)
+    out_rays = torch.empty((n, 8), dtype=torch.float32, device=dev)
+    out_t = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    out_seeds = torch.empty(n, dtype=torch.int32, device=dev) if sd is not None else None
+    out_ids = torch.empty(n, dtype=torch.int32, device=dev)
+    count = torch.empty(1, dtype=torch.int32, device=dev)
+    nbytes = compact_scratch_bytes(ctx.lib, n)
+    scratch = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev)
+    _join_torchs_stream(ctx, torch, dev, asynchronous)
+    p = _with_stride(params, stride)
+    args = (ctx.h, _ptr(r, n), _ptr(t, n), _ptr(sd, n), _ptr(ids, n), n, C.byref(p), A.VP(scratch.data_ptr()), nbytes,
+            _ptr(out_rays, n), _ptr(out_t, n), _ptr(out_seeds, n), _ptr(out_ids, n), A.VP(count.data_ptr()))
+    if asynchronous:
+        _check(ctx.lib.rtr_compact_paths_async(*args), "rtr_compact_paths_async")
+    else:
+        _check(ctx.lib.rtr_compact_paths(*args, None), "rtr_compact_paths")
+    res = CompactResult()
+    if rn:
+        res.rays, res.throughput, res.path_ids = out_rays.cpu().numpy(), out_t.cpu().numpy(), out_ids.cpu().numpy()
+        res.seeds = out_seeds.cpu().numpy() if out_seeds is not None else None
+        res.count_tensor = count
+        res._count = int(count.item()) & 0xffffffff
+    else:
+        res.rays, res.throughput, res.seeds, res.path_ids, res.count_tensor = out_rays, out_t, out_seeds, out_ids, count
+    res._keep = (r, t, sd, ids, scratch)      # an asynchronous call's inputs and its scratch stay alive with its result
+    return res
+
+
+def host_compact_paths(rays, throughput, seeds=None, path_ids=None, params=None):
+    """rtr_host_compact_paths: the host restatement of compact_paths on numpy arrays, no device -> CompactResult of numpy arrays (count
+    is set; count_tensor is None).  rays float32 (N, 8) (or 32-bit words of that shape); throughput float32 (N, 3), or (N, 8) RtrBounce
+    records (stride 32); seeds, path_ids int32 / uint32 (N,) or None."""
+    lib = A.hip_lib()
+    params = params if params is not None else make_compact_params()
+    r = np.ascontiguousarray(rays)
+    if r.dtype.itemsize != 4 or r.ndim != 2 or r.shape[1] != 8:
+        raise ValueError(f"host_compact_paths: rays must be 32-bit words (N, 8), got {r.dtype} {r.shape}")
+    n = int(r.shape[0])
+    t = np.ascontiguousarray(throughput)
+    if t.dtype.itemsize != 4 or t.ndim != 2 or t.shape[0] != n or t.shape[1] not in (3, 8):
+        raise ValueError(f"host_compact_paths: throughput must be 32-bit words ({n}, 3) or ({n}, 8), got {t.dtype} {t.shape}")
+    vec = []
+    for name, x in (("seeds", seeds), ("path_ids", path_ids)):
+        if x is not None:
+            x = np.ascontiguousarray(x)
+            if x.dtype not in (np.int32, np.uint32) or x.shape != (n,):
+                raise ValueError(f"host_compact_paths: {name} must be int32 or uint32 ({n},), got {x.dtype} {x.shape}")
+        vec.append(x)
+    sd, ids = vec
+    out_rays = np.zeros((n, 8), np.float32)
+    out_t = np.zeros((n, 3), np.float32)
+    out_seeds = np.zeros(n, np.int32) if sd is not None else None
+    out_ids = np.zeros(n, np.int32)
+    count = A.u32(0)
+    p = _with_stride(params, 4 * t.shape[1])
+
+    def ptr(x):
+        return x.ctypes.data_as(A.VP) if x is not None and n else None
+    _check(lib.rtr_host_compact_paths(ptr(r), ptr(t), ptr(sd), ptr(ids), n, C.byref(p), ptr(out_rays), ptr(out_t), ptr(out_seeds), ptr(out_ids),
+                                      C.byref(count)), "rtr_host_compact_paths")
+    res = CompactResult()
+    res.rays, res.throughput, res.seeds, res.path_ids, res._count = out_rays, out_t, out_seeds, out_ids, int(count.value)
+    return res
+
+
 class PathResult:
     """What path_trace gives back: radiance (N, 3) float32, the sum of per_depth, a list of bounces + 1 (N, 3) tensors — entry d is what
-    the path's vertex d contributes, already multiplied by the throughput up to it."""
-    radiance = per_depth = None
+    the path's vertex d contributes, already multiplied by the throughput up to it.  live: with compact=True the number of paths that
+    reached vertex d, a list of bounces + 1 ints (live[0] = N); None without."""
+    radiance = per_depth = live = None
 
 
 PATH_SEED_STEP = 0x9E3779B1      # the direct-light seeds of vertex d are the bases + d * this (32-bit words)
@@ -1260,7 +1389,8 @@ def _wrap32(x):
     return (x - ((x >> 31) << 32)).to(_torch().int32)
 
 
-def path_trace(scene, rays, light_params, bounces, seeds=None, occlusion="dense", bounce_cull_mask=None, bounce_ray_flags=0, max_ray_bytes=256 << 20, ctx=None):
+def path_trace(scene, rays, light_params, bounces, seeds=None, occlusion="dense", bounce_cull_mask=None, bounce_ray_flags=0, max_ray_bytes=256 << 20, ctx=None,
+               compact=False, roulette_from=None, survival_floor=0.05):
     """N-bounce global illumination from the public parts, all on the device:
 
         T = 1, L = 0, r = rays
@@ -1275,8 +1405,27 @@ def path_trace(scene, rays, light_params, bounces, seeds=None, occlusion="dense"
 
     base: the explicit seeds, or, with seeds=None, the pixels' px * 733 + py * 1933 from light_params.width / spp, built once.  rays: a
     float32 (N, 8) device tensor; light_params: make_light_params(...); occlusion, max_ray_bytes as direct_light takes them.
-    bounce_cull_mask: e.g. the complement of the emitters' mask bit keeps bounce rays off the lights.  No Russian roulette and no
-    compaction of dead paths: their null rays cost no walk.  -> PathResult."""
+    bounce_cull_mask: e.g. the complement of the emitters' mask bit keeps bounce rays off the lights.  By default no Russian roulette
+    and no compaction of dead paths: their null rays cost no walk, but they keep their lanes.
+
+    compact=True: the same sum over the LIVE paths only.  r, T, base and ids (ids = 0 ... N - 1 at the start) are arrays of live[d] rows,
+    and after the last line of the loop above
+
+            c    = compact_paths(ctx, r, T, base, ids, make_compact_params(light_params.frame, d, roulette, survival_floor))
+            n    = c.count                                   (the one join of the vertex);  live.append(n)
+            r, T, base, ids = the first n rows of c.rays, c.throughput, c.seeds, c.path_ids        (n = 0 ends the loop: every later term is zeros)
+
+    with roulette = roulette_from is not None and d >= roulette_from.  From the first compaction on every seed is explicit: direct_light
+    takes base + d * PATH_SEED_STEP and bounce_rays takes base, the gathered words, which are what the plain loop gives those paths.
+    per_depth[d] is zeros (N, 3) with the live terms written at their ids (ids are unique: no atomics).  Without roulette the result
+    is the plain loop's: a path compact_paths drops has T = 0 or the null ray, so all its later terms are 0 there too (one difference,
+    outside what bounce_rays produces: a throughput that is negative or not finite is dead here).  With roulette a live path of
+    p = max(max3(T), survival_floor) < 1 goes on with probability p and T / p (include/rtr_paths.h): the same mean, fewer paths, more
+    variance.  roulette_from without compact raises ValueError.  -> PathResult."""
+    if roulette_from is not None and not compact:
+        raise ValueError("path_trace: roulette_from needs compact=True (a path the roulette kills saves nothing while it keeps its lane)")
+    if roulette_from is not None and int(roulette_from) < 0:
+        raise ValueError(f"path_trace: roulette_from must be >= 0, got {roulette_from}")
     torch = _torch()
     ctx = ctx or scene.ctx
     bounces = int(bounces)
@@ -1294,6 +1443,10 @@ def path_trace(scene, rays, light_params, bounces, seeds=None, occlusion="dense"
     res.radiance = torch.zeros((n, 3), dtype=torch.float32, device=rays.device)
     T = torch.ones((n, 3), dtype=torch.float32, device=rays.device)
     r = rays
+    ids = None                           # compact: the original slot of each row, from the first compaction on
+    bounce_seeds = seeds
+    if compact:
+        res.live = [n]
     for d in range(bounces + 1):
         q = trace_rays(scene, r, ctx=ctx) if d == 0 else trace_rays(scene, r, ctx=ctx, cull_mask=bounce_cull_mask, ray_flags=bounce_ray_flags)
         sd = seeds if d == 0 else _wrap32(base.to(torch.int64) + d * PATH_SEED_STEP)
@@ -1302,12 +1455,29 @@ def path_trace(scene, rays, light_params, bounces, seeds=None, occlusion="dense"
         if d >= 1:
             rad = torch.where((lit.kind == A.SURFACE_LIGHT).unsqueeze(1), torch.zeros_like(rad), rad)
         term = T * rad
+        if ids is not None:
+            full = torch.zeros((n, 3), dtype=torch.float32, device=rays.device)
+            full[ids.to(torch.int64)] = term
+            term = full
         res.per_depth.append(term)
         res.radiance = res.radiance + term
         if d == bounces:
             break
         b = bounce_rays(ctx, r, hit_surfaces(scene, r, q, ctx=ctx),
-                        make_bounce_params(frame=light_params.frame, depth=d, width=light_params.width, spp=light_params.spp), seeds=seeds)
+                        make_bounce_params(frame=light_params.frame, depth=d, width=light_params.width, spp=light_params.spp), seeds=bounce_seeds)
         T = T * b.weight
         r = b.rays
+        if compact:
+            c = compact_paths(ctx, r, T, seeds=base, path_ids=ids,
+                              params=make_compact_params(frame=light_params.frame, depth=d, roulette=roulette_from is not None and d >= int(roulette_from),
+                                                         survival_floor=survival_floor))
+            m = c.count
+            res.live.append(m)
+            if m == 0:                   # nothing goes on: every later term is zero
+                for _ in range(d + 1, bounces + 1):
+                    res.per_depth.append(torch.zeros((n, 3), dtype=torch.float32, device=rays.device))
+                res.live += [0] * (bounces - d - 1)
+                break
+            r, T, base, ids = c.rays[:m], c.throughput[:m], c.seeds[:m], c.path_ids[:m]
+            bounce_seeds = base
     return res

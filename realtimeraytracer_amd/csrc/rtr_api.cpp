@@ -13,6 +13,8 @@
 #include "kernels/rtr_query.h"
 #include "kernels/rtr_bounce_launch.h"
 #include "rtr_bounce_host.h"
+#include "kernels/rtr_paths_launch.h"
+#include "rtr_paths_host.h"
 
 #include <hip/hip_runtime.h>
 
@@ -2795,6 +2797,60 @@ int rtr_bounce_rays_async(rtr_ctx* c, const RtrRay* rays, const RtrSurface* surf
 int rtr_bounce_rays(rtr_ctx* c, const RtrRay* rays, const RtrSurface* surfaces, uint32_t n, const rtr_bounce_params* p, const uint32_t* seeds,
                     RtrRay* outRays, RtrBounce* outBounce) {
     return join_if_enqueued(c, enqueue_bounce(c, rays, surfaces, n, p, seeds, outRays, outBounce, "rtr_bounce_rays"), n);
+}
+
+/* ---- compaction of live paths (kernels/rtr_paths.hip; the host form and the argument checks are rtr_paths_host.cpp) ----------------- */
+static int enqueue_compact(rtr_ctx* c, const RtrRay* rays, const float* throughput, const uint32_t* seeds, const uint32_t* pathIds, uint32_t n,
+                           const rtr_compact_params* p, void* scratch, size_t scratchBytes, RtrRay* outRays, float* outThroughput,
+                           uint32_t* outSeeds, uint32_t* outPathIds, uint32_t* outCount, const char* who) {
+    char msg[256];       /* the arrays and the params are checked first, which needs nothing of the handle */
+    const rtrdev::CompactCall call{rays, throughput, seeds, pathIds, n, p, scratch, scratchBytes, rtrdev::compact_scratch_bytes(n), true,
+                                   outRays, outThroughput, outSeeds, outPathIds, outCount};
+    if (n && !rtrdev::compact_check_args(who, call, msg, sizeof msg)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s", msg);
+    if (!c) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: ctx is null", who);
+    if (n == 0 && !outCount) return RTR_OK;
+    if (n == 0 && !aligned4(outCount)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: outCount is not 4-B aligned", who);
+    HIP_TRY(hipSetDevice(c->device));
+    if (n == 0) {
+        HIP_TRY(hipMemsetAsync(outCount, 0, sizeof(uint32_t), c->stream));
+        return RTR_OK;
+    }
+    const size_t groups = ((size_t)n + 255u) / 256u;
+    rtrdev::CompactArgs a{};
+    a.rays = reinterpret_cast<const float4*>(rays); a.throughput = reinterpret_cast<const char*>(throughput); a.seeds = seeds; a.pathIds = pathIds;
+    a.ballots = static_cast<unsigned long long*>(scratch);
+    a.groupTotals = reinterpret_cast<uint32_t*>(static_cast<char*>(scratch) + groups * 32u);
+    a.outRays = reinterpret_cast<float4*>(outRays); a.outThroughput = outThroughput; a.outSeeds = outSeeds; a.outPathIds = outPathIds;
+    a.outCount = outCount; a.params = *p; a.n = n;
+    const hipError_t e = rtrdev::launch_compact_paths(a, c->stream);
+    if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: kernel launch: %s", who, hipGetErrorString(e));
+    return RTR_OK;
+}
+
+int rtr_compact_paths_async(rtr_ctx* c, const RtrRay* rays, const float* throughput, const uint32_t* seeds, const uint32_t* pathIds, uint32_t n,
+                            const rtr_compact_params* p, void* scratch, size_t scratchBytes, RtrRay* outRays, float* outThroughput,
+                            uint32_t* outSeeds, uint32_t* outPathIds, uint32_t* outCount) {
+    return enqueue_compact(c, rays, throughput, seeds, pathIds, n, p, scratch, scratchBytes, outRays, outThroughput, outSeeds, outPathIds, outCount,
+                           "rtr_compact_paths_async");
+}
+
+int rtr_compact_paths(rtr_ctx* c, const RtrRay* rays, const float* throughput, const uint32_t* seeds, const uint32_t* pathIds, uint32_t n,
+                      const rtr_compact_params* p, void* scratch, size_t scratchBytes, RtrRay* outRays, float* outThroughput,
+                      uint32_t* outSeeds, uint32_t* outPathIds, uint32_t* outCount, uint32_t* hostCount) {
+    const int rc = enqueue_compact(c, rays, throughput, seeds, pathIds, n, p, scratch, scratchBytes, outRays, outThroughput, outSeeds, outPathIds,
+                                   outCount, "rtr_compact_paths");
+    if (rc != RTR_OK) return rc;
+    if (n == 0) {                        /* nothing was launched; the count's memset, when there is one, is joined like a launch */
+        if (hostCount) *hostCount = 0u;
+        if (outCount) HIP_TRY(hipStreamSynchronize(c->stream));
+        return RTR_OK;
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (hostCount) {                     /* on the context's stream, so that no other stream is joined */
+        HIP_TRY(hipMemcpyAsync(hostCount, outCount, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    return RTR_OK;
 }
 
 }  // extern "C"

@@ -980,6 +980,45 @@ int  rtr_host_compact_paths(const RtrRay* rays, const float* throughput, const u
                             uint32_t numPaths, const rtr_compact_params* params,
                             RtrRay* outRays, float* outThroughput, uint32_t* outSeeds, uint32_t* outPathIds, uint32_t* outCount);
 
+/* ---- picked light samples: one-sample direct lighting for path vertices ------------------------------------------------------
+ * rtr_light_rays sends all Q shadow rays of a hit; these send P picked area-light samples and the directional light.  With Ttot the
+ * triangles of the first numAreaLights lights and ns = numShadowRays a hit has A = Ttot * ns = Q - 1 AREA SLOTS, rtr_light_slots' first
+ * Q - 1 under the same numbers, and owns R = P + 1 slots here: pick p at slot p, the directional light at slot R - 1.  Which area slot a
+ * pick takes is the rule of include/rtr_pick.h (rtr_pick_params, include/rtr_types.h), or the caller's choice (slotsIn).  Each pick
+ * weighted Ttot / P, the picks' sum is an unbiased estimate of the light loops' area sum.
+ *
+ * rtr_light_rays_picked: outSlots[k * P + p] = the area slot of pick p of hit k — slotsIn[k * P + p] as it is, or drawn — written for
+ * every hit; outRays[k * R + p] = byte for byte the ray rtr_light_rays writes at outRays[k * Q + that slot] for the same hit, params and
+ * seeds, the null ray where that is null and for a slot >= A (RTR_PICK_NONE included); outRays[k * R + R - 1] = rtr_light_rays' slot
+ * Q - 1.  A hit that is a miss, a light or invalid gets R null rays.  slotsIn: NULL or numHits * P words, 4-B aligned; outSlots
+ * likewise, required; the others as rtr_light_rays_async.
+ * rtr_shade_hits_picked: out[k] as rtr_shade_hits' — kind, the sky at a miss and the colour at a light hit unchanged — with, at an
+ * object, shadowed = sum over the picks in order of contrib_p * (occluded[k * R + p] ? 0 : w_p), then the directional term as the light
+ * loops add it; unshadowed the same with every sample visible, when asked for; analytic zeros.  contrib_p: the light loops' BRDF * L / pdf
+ * of slots[k * P + p] (a null slot contributes nothing).  slots: rtr_light_rays_picked's outSlots; occluded: the numHits * R bytes of an
+ * RTR_QUERY_ANY query of its rays; weights: NULL (w_p = (float)Ttot / (float)P) or numHits * P floats — 1 / (P * pdf_slot * ns) for slots
+ * drawn with probability pdf_slot each.  RTR_LIGHT_ANALYTIC: RTR_ERR_UNSUPPORTED, the LTC term integrates whole lights.
+ * Both are ENQUEUED on ctx's stream.  Refused before anything is written (RTR_ERR_INVALID_ARGUMENT, the message names the function and
+ * the argument): a null or misaligned pointer, numPicks 0 or above RTR_PICK_MAX, non-zero _reserved words, numHits * R past 32 bits,
+ * A above RTR_PICK_MAX_SLOTS, width or spp == 0 with seeds == NULL, params rtr_light_slots refuses, a scene on another device. */
+int  rtr_light_rays_picked_async(rtr_ctx* ctx, const rtr_scene* scene, const RtrRay* rays, const RtrHit* hits, uint32_t numHits,
+                                 const rtr_light_params* params, const rtr_pick_params* pick, const uint32_t* seeds, const uint32_t* slotsIn,
+                                 RtrRay* outRays, uint32_t* outSlots);
+int  rtr_shade_hits_picked_async(rtr_ctx* ctx, const rtr_scene* scene, const RtrRay* rays, const RtrHit* hits, uint32_t numHits,
+                                 const rtr_light_params* params, const rtr_pick_params* pick, const uint32_t* seeds, const uint32_t* slots,
+                                 const float* weights, const uint8_t* occluded, RtrRadiance* out);
+/* The same two, then join ctx's stream (only that stream). */
+int  rtr_light_rays_picked(rtr_ctx* ctx, const rtr_scene* scene, const RtrRay* rays, const RtrHit* hits, uint32_t numHits,
+                           const rtr_light_params* params, const rtr_pick_params* pick, const uint32_t* seeds, const uint32_t* slotsIn,
+                           RtrRay* outRays, uint32_t* outSlots);
+int  rtr_shade_hits_picked(rtr_ctx* ctx, const rtr_scene* scene, const RtrRay* rays, const RtrHit* hits, uint32_t numHits,
+                           const rtr_light_params* params, const rtr_pick_params* pick, const uint32_t* seeds, const uint32_t* slots,
+                           const float* weights, const uint8_t* occluded, RtrRadiance* out);
+/* The drawn slots on the host: outSlots[k * P + p] for numHits hits by the rule of include/rtr_pick.h in a plain loop, HOST pointers, no
+ * device.  frame, width, spp: rtr_light_params' (width, spp used when seeds == NULL); areaSlots: A.  The device's words equal these. */
+int  rtr_host_pick_slots(const uint32_t* seeds, uint32_t numHits, uint32_t frame, uint32_t width, uint32_t spp, const rtr_pick_params* pick,
+                         uint32_t areaSlots, uint32_t* outSlots);
+
 /* ---- errors --------------------------------------------------------------------------- */
 const char* rtr_last_error(void);
 const char* rtr_status_string(int status);

@@ -260,6 +260,21 @@ typedef struct rtr_compact_params {
     uint32_t _reserved[3];
 } rtr_compact_params;         /* 32 bytes */
 
+/* ---- picked light samples (rtr_light_rays_picked, rtr_shade_hits_picked): numPicks of a hit's area-light slots instead of all ---
+ * A hit's AREA SLOTS are the first A = Q - 1 slots of rtr_light_slots, numbered the same way: slot j is sample j % numShadowRays of
+ * light triangle j / numShadowRays.  numPicks (P, 1 ... RTR_PICK_MAX) of them are drawn per hit — pick p by
+ * u = rtr_random(seedBase + frame + 7919 * (depth + 1) + 400 + 100 * p), slot (uint32_t)(u * A) clamped to A - 1 — or handed in by the
+ * caller; the directional light is never picked, it keeps a ray of its own.  depth enters the seed as in rtr_bounce_params; _reserved
+ * must be 0.  RTR_PICK_NONE: no slot (what is drawn when A == 0; a caller's way to leave a pick out).  A may be at most
+ * RTR_PICK_MAX_SLOTS, so that every slot can be drawn from a float.  The rule itself is include/rtr_pick.h. */
+#define RTR_PICK_MAX       30u
+#define RTR_PICK_NONE      0xffffffffu
+#define RTR_PICK_MAX_SLOTS (1u << 24)
+typedef struct rtr_pick_params {
+    uint32_t numPicks, depth;
+    uint32_t _reserved[6];
+} rtr_pick_params;            /* 32 bytes */
+
 #ifdef __cplusplus
 }
 #endif
@@ -282,6 +297,7 @@ static_assert(sizeof(RtrRadiance) == 48, "radiance must be 48 B");
 static_assert(sizeof(RtrBounce) == 32, "bounce record must be 32 B");
 static_assert(sizeof(rtr_bounce_params) == 32, "bounce params must be 32 B");
 static_assert(sizeof(rtr_compact_params) == 32, "compact params must be 32 B");
+static_assert(sizeof(rtr_pick_params) == 32, "pick params must be 32 B");
 #endif
 
 #endif /* RTR_TYPES_H */

@@ -97,6 +97,10 @@ class rtr_compact_params(C.Structure):
     _fields_ = [("frame", u32), ("depth", u32), ("flags", u32), ("survivalFloor", f32), ("throughputStrideBytes", u32), ("_reserved", u32 * 3)]
 
 
+class rtr_pick_params(C.Structure):
+    _fields_ = [("numPicks", u32), ("depth", u32), ("_reserved", u32 * 6)]
+
+
 class rtr_vertex_range(C.Structure):
     """one range of rtr_scene_update_vertices: vertices firstVertex ... + numVertices of the scene's concatenated vertex array"""
     _fields_ = [("firstVertex", u32), ("numVertices", u32), ("positions", C.c_void_p), ("normals", C.c_void_p)]
@@ -177,6 +181,7 @@ assert C.sizeof(RtrSurface) == 80
 assert C.sizeof(RtrRadiance) == 48 and C.sizeof(rtr_light_params) == 32
 assert C.sizeof(RtrBounce) == 32 and C.sizeof(rtr_bounce_params) == 32
 assert C.sizeof(rtr_compact_params) == 32
+assert C.sizeof(rtr_pick_params) == 32
 assert C.sizeof(rtr_vertex_range) == 24
 assert C.sizeof(rtr_tree_cost) == 96 and C.alignment(rtr_tree_cost) == 8
 assert C.sizeof(rtr_update_status) == 32
@@ -205,6 +210,9 @@ LIGHT_SHADOWED, LIGHT_UNSHADOWED, LIGHT_ANALYTIC = 1, 2, 4
 BOUNCE_DIFFUSE, BOUNCE_SPECULAR = 1, 2
 COMPACT_ROULETTE = 1            # RTR_COMPACT_ROULETTE
 PATH_NONE = 0xffffffff          # RTR_PATH_NONE: the path id of a slot behind the survivors
+PICK_MAX = 30                   # RTR_PICK_MAX: the most picked light samples per hit
+PICK_NONE = 0xffffffff          # RTR_PICK_NONE: no area slot
+PICK_MAX_SLOTS = 1 << 24        # RTR_PICK_MAX_SLOTS: the most area slots a pick can be drawn from
 VERTICES_HOST, VERTICES_DEVICE = 0, 1
 
 P = C.POINTER
@@ -304,6 +312,11 @@ RTR_SYMBOLS = {
     "rtr_compact_paths_async": (C.c_int, [VP, VP, VP, VP, VP, u32, P(rtr_compact_params), VP, C.c_size_t, VP, VP, VP, VP, VP]),
     "rtr_compact_paths": (C.c_int, [VP, VP, VP, VP, VP, u32, P(rtr_compact_params), VP, C.c_size_t, VP, VP, VP, VP, VP, P(u32)]),
     "rtr_host_compact_paths": (C.c_int, [VP, VP, VP, VP, u32, P(rtr_compact_params), VP, VP, VP, VP, P(u32)]),
+    "rtr_light_rays_picked_async": (C.c_int, [VP, VP, VP, VP, u32, P(rtr_light_params), P(rtr_pick_params), VP, VP, VP, VP]),
+    "rtr_light_rays_picked": (C.c_int, [VP, VP, VP, VP, u32, P(rtr_light_params), P(rtr_pick_params), VP, VP, VP, VP]),
+    "rtr_shade_hits_picked_async": (C.c_int, [VP, VP, VP, VP, u32, P(rtr_light_params), P(rtr_pick_params), VP, VP, VP, VP, VP]),
+    "rtr_shade_hits_picked": (C.c_int, [VP, VP, VP, VP, u32, P(rtr_light_params), P(rtr_pick_params), VP, VP, VP, VP, VP]),
+    "rtr_host_pick_slots": (C.c_int, [VP, u32, u32, u32, u32, P(rtr_pick_params), u32, VP]),
     "rtr_host_sincos_turn": (C.c_int, [VP, u32, VP, VP]),
 }
 

@@ -1091,6 +1091,88 @@ def _radiance_result(raw, as_numpy, torch):
     return res
 
 
+# ---- picked light samples (rtr_light_rays_picked, rtr_shade_hits_picked): P area-light samples per hit instead of all ----------------
+def make_pick_params(picks=1, depth=0):
+    """rtr_pick_params: picks (P, 1 ... A.PICK_MAX) area-light samples per hit; depth enters their seeds as it enters bounce_rays'"""
+    return A.rtr_pick_params(int(picks), int(depth) & 0xffffffff)
+
+
+def host_pick_slots(seeds, n, params, pick, area_slots):
+    """rtr_host_pick_slots: the slots light_rays_picked draws for n hits, on the host -> uint32 (n, P).  seeds: int32 / uint32 (n,) or
+    None (then the pixels' of params.width / spp); params: the rtr_light_params (frame, width, spp); area_slots: A = light_slots - 1"""
+    lib = A.hip_lib()
+    n = int(n)
+    sd = None
+    if seeds is not None:
+        sd = np.ascontiguousarray(seeds)
+        if sd.dtype not in (np.int32, np.uint32) or sd.shape != (n,):
+            raise ValueError(f"host_pick_slots: seeds must be int32 or uint32 ({n},), got {sd.dtype} {sd.shape}")
+    out = np.zeros((n, int(pick.numPicks)), np.uint32)
+    _check(lib.rtr_host_pick_slots(sd.ctypes.data_as(A.VP) if sd is not None and n else None, n, int(params.frame), int(params.width), int(params.spp),
+                                   C.byref(pick), int(area_slots), out.ctypes.data_as(A.VP) if out.size else None), "rtr_host_pick_slots")
+    return out
+
+
+def _pick_vector(torch, x, dtype, np_dtypes, n, p, name, dev, who, as_numpy):
+    """_device_vector for an (n, p) or (n * p,) array of per-pick words, flattened"""
+    if x is not None and isinstance(x, (np.ndarray, torch.Tensor)) and tuple(x.shape) == (n, p):
+        x = x.reshape(-1)
+    return _device_vector(torch, x, dtype, np_dtypes, n * p, name, dev, who, as_numpy)
+
+
+def light_rays_picked(scene, rays, hits, params, pick, seeds=None, slots=None, ctx=None, asynchronous=False):
+    """rtr_light_rays_picked: per hit the shadow rays of pick.numPicks (P) of its area-light slots and of the directional light ->
+    (rays, slots): an (N * R, 8) float32 array of RtrRay, R = P + 1, hit k's at rows k * R ... k * R + R — pick p at row k * R + p, the
+    directional light last — each the ray light_rays writes for that slot (eight zeros where that is null); and the (N, P) area slots
+    used (int32 words on the device, uint32 for numpy; A.PICK_NONE: no slot).  slots: None (drawn by include/rtr_pick.h's rule, what
+    host_pick_slots restates) or the caller's (N, P) choice, e.g. stratified or power-proportional.  The other arguments as light_rays."""
+    torch = _torch()
+    ctx = ctx or scene.ctx
+    dev = torch.device("cuda", ctx.device)
+    r, h, sd, as_numpy = _light_inputs(torch, scene, rays, hits, seeds, ctx, "light_rays_picked", asynchronous)
+    n, p = int(r.shape[0]), int(pick.numPicks)
+    sl = _pick_vector(torch, slots, torch.int32, (np.int32, np.uint32), n, p, "slots", dev, "light_rays_picked", as_numpy)
+    out = torch.empty((n * (p + 1), 8), dtype=torch.float32, device=dev)
+    out_slots = torch.empty((n, p), dtype=torch.int32, device=dev)
+    _join_torchs_stream(ctx, torch, dev, asynchronous)
+    fn = ctx.lib.rtr_light_rays_picked_async if asynchronous else ctx.lib.rtr_light_rays_picked
+    _check(fn(ctx.h, scene.h, _ptr(r, n), _ptr(h, n), n, C.byref(params), C.byref(pick), _ptr(sd, n), _ptr(sl, n), _ptr(out, n), _ptr(out_slots, n)),
+           "rtr_light_rays_picked")
+    if as_numpy:
+        return out.cpu().numpy(), out_slots.cpu().numpy().view(np.uint32)
+    out._keep = (r, h, sd, sl)           # an asynchronous call's inputs stay alive with its result
+    return out, out_slots
+
+
+def shade_hits_picked(scene, rays, hits, params, pick, slots, occluded, weights=None, seeds=None, ctx=None, asynchronous=False):
+    """rtr_shade_hits_picked: shade_hits' RadianceResult from the picks.  slots: light_rays_picked's (N, P); occluded: the (N * R,) uint8
+    answers of trace_rays(any_hit=True) for its rays (or the QueryResult); weights: None — each pick counts (light triangles) / P, which
+    makes the picks' sum an unbiased estimate of the light loops' area sum for uniformly drawn slots — or float32 (N, P),
+    1 / (P * pdf * shadow_rays) for slots drawn with probability pdf each.  The analytic sum cannot be asked for."""
+    torch = _torch()
+    ctx = ctx or scene.ctx
+    dev = torch.device("cuda", ctx.device)
+    r, h, sd, as_numpy = _light_inputs(torch, scene, rays, hits, seeds, ctx, "shade_hits_picked", asynchronous)
+    if isinstance(occluded, QueryResult):
+        if occluded.occluded is None:
+            raise ValueError("shade_hits_picked: the QueryResult holds no visibility bytes (a closest-hit query)")
+        occluded = occluded.occluded
+    n, p = int(r.shape[0]), int(pick.numPicks)
+    if occluded is None or slots is None:
+        raise ValueError("shade_hits_picked: slots and occluded must be torch tensors or numpy arrays")
+    sl = _pick_vector(torch, slots, torch.int32, (np.int32, np.uint32), n, p, "slots", dev, "shade_hits_picked", as_numpy)
+    wt = _pick_vector(torch, weights, torch.float32, (np.float32,), n, p, "weights", dev, "shade_hits_picked", as_numpy)
+    oc = _device_vector(torch, occluded, torch.uint8, (np.uint8,), n * (p + 1), "occluded", dev, "shade_hits_picked", as_numpy)
+    out = torch.empty((n, 12), dtype=torch.float32, device=dev)
+    _join_torchs_stream(ctx, torch, dev, asynchronous)
+    fn = ctx.lib.rtr_shade_hits_picked_async if asynchronous else ctx.lib.rtr_shade_hits_picked
+    _check(fn(ctx.h, scene.h, _ptr(r, n), _ptr(h, n), n, C.byref(params), C.byref(pick), _ptr(sd, n), _ptr(sl, n), _ptr(wt, n), _ptr(oc, n), _ptr(out, n)),
+           "rtr_shade_hits_picked")
+    res = _radiance_result(out.cpu().numpy() if as_numpy else out, as_numpy, torch)
+    res._keep = (r, h, sd, sl, wt, oc)
+    return res
+
+
 def tonemap_pack(ctx, radiance, asynchronous=False):
     """rtr_tonemap_pack: the tone-mapped BGRA8 pixel (ACES, sRGB; uint32 as Frame.download gives them, here int32 (N,) on the device) of
     each row of radiance, a float32 (N, >= 3) array whose first three columns are used and whose rows may be a view into wider records
@@ -1116,7 +1198,8 @@ def tonemap_pack(ctx, radiance, asynchronous=False):
     return out
 
 
-def direct_light(scene, rays, hits=None, params=None, seeds=None, ctx=None, max_ray_bytes=256 << 20, occlusion="dense", shadow_cull_mask=None, shadow_ray_flags=0):
+def direct_light(scene, rays, hits=None, params=None, seeds=None, ctx=None, max_ray_bytes=256 << 20, occlusion="dense", shadow_cull_mask=None, shadow_ray_flags=0,
+                 picks=None, pick_depth=0):
     """The composed stage: closest hit (when hits is None) -> light_rays -> trace_rays(any_hit=True) -> shade_hits, in chunks of hits
     so that a chunk's light rays (n * Q * 32 bytes) stay within max_ray_bytes — a 1080p frame at Q = 7 would be 464 MB of rays at once.
     Chunks do not change the result.  occlusion: "dense" (trace_rays, the default), "queued" (trace_occlusion) or "queued_own_leaf"
@@ -1124,7 +1207,10 @@ def direct_light(scene, rays, hits=None, params=None, seeds=None, ctx=None, max_
     params: make_light_params(...).  shadow_cull_mask: the cull mask of the shadow rays (instances whose mask does not meet it cast no
     shadow), passed to whichever occlusion route is selected; None: the unmasked calls, as before.  shadow_ray_flags: the culling flags
     (A.QUERY_CULL_*, as trace_rays' ray_flags) of the shadow rays, passed to that route likewise; 0: as before.  Returns a RadianceResult
-    on the device."""
+    on the device.
+    picks=P: the picked route — light_rays_picked(make_pick_params(P, pick_depth)) -> the same occlusion query -> shade_hits_picked with
+    the default weights: P + 1 rays per hit instead of Q, an unbiased estimate of the same shadowed (and unshadowed) sum; the analytic sum
+    is refused.  "queued_own_leaf" raises ValueError with picks: the picked rays have no start hints.  None: the full loops, as before."""
     shadow_ray_flags = _ray_flags("direct_light", shadow_ray_flags, False)
     if occlusion not in ("dense", "queued", "queued_own_leaf"):
         raise ValueError(f"direct_light: occlusion must be 'dense', 'queued' or 'queued_own_leaf', got {occlusion!r}")
@@ -1139,6 +1225,12 @@ def direct_light(scene, rays, hits=None, params=None, seeds=None, ctx=None, max_
     if isinstance(hits, QueryResult):
         hits = hits.hits
     n, q = int(rays.shape[0]), light_slots(scene, params)
+    pick = None
+    if picks is not None:
+        if occlusion == "queued_own_leaf":
+            raise ValueError("direct_light: occlusion='queued_own_leaf' needs start hints, which the picked rays do not have (picks must be None)")
+        pick = make_pick_params(picks, pick_depth)
+        q = int(pick.numPicks) + 1
     chunk = max(1, int(max_ray_bytes) // (32 * q))
     out =torch.empty((n, 12), dtype=torch.float32, device=rays.device)
     for a in range(0, n, chunk):
@@ -1148,6 +1240,12 @@ def direct_light(scene, rays, hits=None, params=None, seeds=None, ctx=None, max_
             k = torch.arange(a, b, device=rays.device, dtype=torch.int64) // int(params.spp)
             sd = ((k % int(params.width)) * 733 + (k // int(params.width)) * 1933).to(torch.int32)      # wraps to 32 bits as the kernel's words do
         r, h = rays[a:b], hits[a:b]
+        if pick is not None:
+            lr, sl = light_rays_picked(scene, r, h, params, pick, seeds=sd, ctx=ctx)
+            occ = (trace_occlusion(scene, lr, ctx=ctx, cull_mask=shadow_cull_mask, ray_flags=shadow_ray_flags) if occlusion == "queued"
+                   else trace_rays(scene, lr, any_hit=True, ctx=ctx, cull_mask=shadow_cull_mask, ray_flags=shadow_ray_flags)).occluded
+            out[a:b] = shade_hits_picked(scene, r, h, params, pick, sl, occ, seeds=sd, ctx=ctx).raw
+            continue
         if occlusion == "queued_own_leaf":
             lr, leaves = light_rays(scene, r, h, params, seeds=sd, ctx=ctx, hints=True)
             occ = trace_occlusion(scene, lr, ctx=ctx, start_leaves=leaves, cull_mask=shadow_cull_mask, ray_flags=shadow_ray_flags).occluded
@@ -1421,11 +1519,35 @@ def path_trace(scene, rays, light_params, bounces, seeds=None, occlusion="dense"
     is the plain loop's: a path compact_paths drops has T = 0 or the null ray, so all its later terms are 0 there too (one difference,
     outside what bounce_rays produces: a throughput that is negative or not finite is dead here).  With roulette a live path of
     p = max(max3(T), survival_floor) < 1 goes on with probability p and T / p (include/rtr_paths.h): the same mean, fewer paths, more
-    variance.  roulette_from without compact raises ValueError.  -> PathResult."""
+    variance.  roulette_from without compact raises ValueError.  Every vertex takes the full light loops; path_trace_picked is this
+    loop with picked light samples at the later vertices.  -> PathResult."""
+    return _path_trace(scene, rays, light_params, bounces, seeds, occlusion, bounce_cull_mask, bounce_ray_flags, max_ray_bytes, ctx, compact, roulette_from,
+                       survival_floor, None, 1)
+
+
+def path_trace_picked(scene, rays, light_params, bounces, light_picks=None, pick_from=1, seeds=None, occlusion="dense", bounce_cull_mask=None, bounce_ray_flags=0,
+                      max_ray_bytes=256 << 20, ctx=None, compact=False, roulette_from=None, survival_floor=0.05):
+    """path_trace with one-sample direct lighting at the path vertices: the same loop, the same arguments, and
+    light_picks=P: the vertices d >= pick_from take direct_light(..., picks=P, pick_depth=d) with the seeds path_trace gives them: P picked
+    area-light samples and the directional light instead of all Q shadow rays, the same mean (include/rtr_pick.h).  The camera hits keep
+    the renderer's full loops by default (pick_from=1).  The picks read other random numbers than the bounce and the roulette, so which
+    paths live does not depend on them.  light_picks with light_params.outputs asking for the analytic sum raises ValueError; None: every
+    vertex takes the full loops, path_trace's calls and bytes.  -> PathResult."""
+    return _path_trace(scene, rays, light_params, bounces, seeds, occlusion, bounce_cull_mask, bounce_ray_flags, max_ray_bytes, ctx, compact, roulette_from,
+                       survival_floor, light_picks, pick_from)
+
+
+def _path_trace(scene, rays, light_params, bounces, seeds, occlusion, bounce_cull_mask, bounce_ray_flags, max_ray_bytes, ctx, compact, roulette_from, survival_floor,
+                light_picks, pick_from):
+    """the loop of path_trace and path_trace_picked"""
     if roulette_from is not None and not compact:
         raise ValueError("path_trace: roulette_from needs compact=True (a path the roulette kills saves nothing while it keeps its lane)")
     if roulette_from is not None and int(roulette_from) < 0:
         raise ValueError(f"path_trace: roulette_from must be >= 0, got {roulette_from}")
+    if light_picks is not None and int(light_params.outputs) & A.LIGHT_ANALYTIC:
+        raise ValueError("path_trace_picked: light_picks cannot give the analytic sum (light_params.outputs has LIGHT_ANALYTIC): the LTC term has no per-sample form")
+    if light_picks is not None and int(pick_from) < 0:
+        raise ValueError(f"path_trace_picked: pick_from must be >= 0, got {pick_from}")
     torch = _torch()
     ctx = ctx or scene.ctx
     bounces = int(bounces)
@@ -1450,7 +1572,10 @@ def path_trace(scene, rays, light_params, bounces, seeds=None, occlusion="dense"
     for d in range(bounces + 1):
         q = trace_rays(scene, r, ctx=ctx) if d == 0 else trace_rays(scene, r, ctx=ctx, cull_mask=bounce_cull_mask, ray_flags=bounce_ray_flags)
         sd = seeds if d == 0 else _wrap32(base.to(torch.int64) + d * PATH_SEED_STEP)
-        lit = direct_light(scene, r, q, light_params, seeds=sd, ctx=ctx, max_ray_bytes=max_ray_bytes, occlusion=occlusion)
+        if light_picks is not None and d >= int(pick_from):
+            lit = direct_light(scene, r, q, light_params, seeds=sd, ctx=ctx, max_ray_bytes=max_ray_bytes, occlusion=occlusion, picks=light_picks, pick_depth=d)
+        else:
+            lit = direct_light(scene, r, q, light_params, seeds=sd, ctx=ctx, max_ray_bytes=max_ray_bytes, occlusion=occlusion)
         rad = lit.shadowed
         if d >= 1:
             rad = torch.where((lit.kind == A.SURFACE_LIGHT).unsqueeze(1), torch.zeros_like(rad), rad)

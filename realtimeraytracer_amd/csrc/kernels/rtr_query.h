@@ -54,6 +54,19 @@ struct LightArgs {
     float4* out;                 /* shade: RtrRadiance as 3 x float4 */
 };
 
+/* Arguments of the picked direct-lighting kernels (rtr_light_rays_picked, rtr_shade_hits_picked): LightArgs as those of the full forms,
+ * with la.slots = R = picks + 1 (the picks, then the directional light), and what include/rtr_pick.h needs. */
+struct PickArgs {
+    LightArgs la;
+    uint32_t picks;              /* P: 1 ... RTR_PICK_MAX */
+    uint32_t depth;              /* enters the picks' seeds */
+    uint32_t areaSlots;          /* A: numShadowRays x the triangles of the first numAreaLights lights (la.numAreaLights > 0 whenever A > 0) */
+    float defaultWeight;         /* shade: (float)triangles / (float)P */
+    const uint32_t* slotsIn;     /* rays: n * P slots of the caller's choosing, or null (drawn by the rule); shade: the slots the rays were made for */
+    uint32_t* outSlots;          /* rays: n * P slots used */
+    const float* weights;        /* shade: n * P weights, or null (defaultWeight) */
+};
+
 /* The per-scene triangle -> leaf table (rtr_hit_leaves, rtr_light_rays_hinted): entry base[customIndex] + primitiveId, base = the prefix
  * sum of triCount, is the child code of the BVH2 leaf that holds that world-space record (RtrBvhNode::child: negative); an entry no leaf
  * wrote stays 0.  A start hint of the queued occlusion query (include/rtr.h). */
@@ -120,6 +133,9 @@ hipError_t launch_hit_surfaces(const DeviceScene& sc, const SurfaceArgs& sa, hip
 hipError_t launch_light_rays(const DeviceScene& sc, const LightArgs& la, hipStream_t stream);
 /* one RtrRadiance per hit: shade_sample with the visibility bytes of those slots */
 hipError_t launch_shade_hits(const DeviceScene& sc, const LightArgs& la, hipStream_t stream);
+/* the picked forms: per hit the shadow rays of pa.picks area slots and of the directional light, and the slots; the sums over them */
+hipError_t launch_light_rays_picked(const DeviceScene& sc, const PickArgs& pa, hipStream_t stream);
+hipError_t launch_shade_hits_picked(const DeviceScene& sc, const PickArgs& pa, hipStream_t stream);
 /* tonemap_pack of n float3 read strideWords floats apart */
 hipError_t launch_tonemap_pack(const float* radiance, uint32_t strideWords, uint32_t n, uint32_t* out, hipStream_t stream);
 

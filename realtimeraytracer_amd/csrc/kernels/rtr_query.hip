@@ -13,10 +13,13 @@
  * k_hit_surfaces (rtr_hit_surfaces) takes the hits further: the surface the closest-hit shader computes for each, by fetch_surface().
  * k_light_rays / k_shade_hits / k_tonemap_pack (rtr_light_rays, rtr_shade_hits, rtr_tonemap_pack) take them to the framebuffer: what the
  * ray-gen shader does after the closest hit, by the renderer's own light_loops() with every query at a fixed slot of its hit.
+ * k_light_rays_picked / k_shade_hits_picked (rtr_light_rays_picked, rtr_shade_hits_picked) do the same for a few picked area-light slots
+ * of each hit (include/rtr_pick.h) and the directional light: the light loops' sample functions, called per picked slot.
  * Compiled with the library's flags (-ffp-contract=off): the numerical contract of include/rtr_math.h.
  */
 #include "rtr_query_device.h"
 #include "../../../include/rtr.h"
+#include "../../../include/rtr_pick.h"
 
 namespace rtrdev {
 
@@ -537,6 +540,168 @@ __global__ __launch_bounds__(kTonemapBlock) void k_tonemap_pack(const float* __r
 
 hipError_t launch_tonemap_pack(const float* radiance, uint32_t strideWords, uint32_t n, uint32_t* out, hipStream_t s) {
     hipLaunchKernelGGL(k_tonemap_pack, dim3((uint32_t)(((uint64_t)n + kTonemapBlock - 1) / kTonemapBlock)), dim3(kTonemapBlock), 0, s, radiance, strideWords, n, out);
+    return hipGetLastError();
+}
+
+/* ---- picked light samples (rtr_light_rays_picked, rtr_shade_hits_picked) -----------------------------------------------------------
+ * The same rays and the same sums for P of a hit's A area slots (include/rtr_pick.h) and the directional light: hit k owns R = P + 1
+ * slots, the picks first.  Slot j is sample j % ns of light triangle t = j / ns, and t differs from lane to lane: where light_loops reads
+ * a triangle's record and its light's colour, intensity and sidedness through wave-uniform addresses (scalar loads), these are per-lane
+ * gathers from the same small tables — four 16-B pieces of sc.lightTris, 32 B of sc.lights.  The light of t is found in sc.lightTriFirst
+ * by a binary search over the first numAreaLights entries: the last l with lightTriFirst[l] <= t, at most ceil(log2(numAreaLights))
+ * steps (a light without triangles shares its entry with the next one and is passed over).  The sample's point, the cull of a one-sided
+ * triangle, direction, distance and BRDF are light_sample_pos, the test of light_loops and area_sample_contrib: called, not restated. */
+struct PickedSample { rtr_v3 dir; float dist; rtr_v3 lcol; float lintensity, pdf; };
+
+/* what light_loops computes for area slot j < A of a surface point; false where it sends no ray (a one-sided triangle facing away) */
+__device__ __forceinline__ bool picked_sample(const DeviceScene& sc, const PickArgs& pa, const RenderArgs& ra, rtr_v3 hitPoint, uint32_t j, PickedSample& ps) {
+    const uint32_t t = j / pa.la.numShadowRays, s = j - t * pa.la.numShadowRays;
+    uint32_t lo = 0u, hi = pa.la.numAreaLights;
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (sc.lightTriFirst[mid] <= t) lo = mid; else hi = mid;
+    }
+    const RtrAreaLightInfo* L = sc.lights + lo;
+    const float4* rec = sc.lightTris + (size_t)t * kLightTriRecord;
+    const float4 r0 = rec[0], r1 = rec[1], r2 = rec[2], r3 = rec[3];
+    rtr_v3 P[3];
+    P[0] = rtr_mk(r0.x, r0.y, r0.z); P[1] = rtr_mk(r1.x, r1.y, r1.z); P[2] = rtr_mk(r2.x, r2.y, r2.z);
+    if (L->isTwoSided == 0u) {
+        if (rtr_dot(rtr_mk(r3.x, r3.y, r3.z), rtr_sub(hitPoint, P[0])) < 0.0f) return false;
+    }
+    const rtr_v3 lightVec = rtr_sub(light_sample_pos(P, s, 0u, 0u, ra.info.frame), hitPoint);
+    ps.dir = rtr_normalize(lightVec);
+    ps.dist = rtr_length(lightVec);
+    ps.lcol = rtr_ld3(L->color); ps.lintensity = L->intensity; ps.pdf = r1.w;
+    return true;
+}
+
+/* One lane per hit, one wave per workgroup, as k_light_rays<STAGED>: the wave's 64 * R rays are made in LDS at the odd pitch 2 R + 1
+ * pieces over zeros — the null rays of every slot without a ray — and stored as one contiguous block, lane i on the i-th 16-B piece.
+ * R <= RTR_PICK_MAX + 1 = 31 always fits the stage (63 KiB), so there is no unstaged form.  The slots go out as the lane draws them,
+ * P words at the 4 P-byte lane stride: 8 B per hit beside 64 B of rays at P = 1. */
+__global__ __launch_bounds__(kLightRaysBlock) void k_light_rays_picked(DeviceScene sc, PickArgs pa) {
+    extern __shared__ rtr_q4 s_pick_stage[];
+    typedef __attribute__((address_space(3))) rtr_q4* lds_q4;
+    const lds_q4 stage = (lds_q4)s_pick_stage;
+    const LightArgs& la = pa.la;
+    const uint32_t lane = threadIdx.x;
+    const uint64_t k0 = (uint64_t)blockIdx.x * kLightRaysBlock;
+    const bool live = k0 + lane < la.n;
+    const uint32_t k = (uint32_t)(k0 + lane);
+    const uint32_t P = pa.picks, R = P + 1u, pieces = 2u * R, pitch = pieces + 1u;
+    rtr_q4* __restrict__ out = reinterpret_cast<rtr_q4*>(la.outRays) + k0 * pieces;          /* the wave's block */
+    const rtr_q4 zero = {0.0f, 0.0f, 0.0f, 0.0f};
+    for (uint32_t i = lane; i < kLightRaysBlock * pitch; i += kLightRaysBlock) stage[i] = zero;
+    __syncthreads();
+    if (live) {
+        HitRec h;
+        rtr_v3 dir;
+        RenderArgs ra{};
+        const bool object = light_hit(sc, la, k, h, dir, ra) == RTR_SURFACE_OBJECT;
+        Accum acc;
+        Surface sf;
+        LocalStats st;
+        rtr_v3 shadowOrigin = rtr_mk(0, 0, 0);
+        if (object) {
+            fetch_surface<false, false>(sc, ra, h, dir, false, acc, sf, st);
+            shadowOrigin = rtr_madd(sf.hitPoint, sf.hitNormal, 0.01f);
+        }
+        const lds_q4 row = stage + lane * pitch;
+        for (uint32_t p = 0; p < P; ++p) {
+            const size_t at = (size_t)k * P + p;
+            /* ra.info.frame is la.frame + the hit's seed base (light_hit) */
+            const uint32_t j = pa.slotsIn ? pa.slotsIn[at] : rtr_pick_slot(ra.info.frame, pa.depth, p, pa.areaSlots);
+            pa.outSlots[at] = j;
+            PickedSample ps;
+            if (object && j < pa.areaSlots && picked_sample(sc, pa, ra, sf.hitPoint, j, ps)) {
+                row[2u * p] = rtr_q4{shadowOrigin.x, shadowOrigin.y, shadowOrigin.z, 0.001f};
+                row[2u * p + 1u] = rtr_q4{ps.dir.x, ps.dir.y, ps.dir.z, ps.dist - 0.5f};
+            }
+        }
+        const rtr_v3 directLightDir = directional_light_dir();
+        if (object && !(rtr_dot(sf.hitNormal, directLightDir) <= 0.0f)) {
+            row[2u * P] = rtr_q4{shadowOrigin.x, shadowOrigin.y, shadowOrigin.z, 0.001f};
+            row[2u * P + 1u] = rtr_q4{directLightDir.x, directLightDir.y, directLightDir.z, 10000.0f};
+        }
+    }
+    __syncthreads();
+    const uint64_t left = la.n - k0;
+    const uint32_t total = (uint32_t)(left < (uint64_t)kLightRaysBlock ? left : (uint64_t)kLightRaysBlock) * pieces;
+    /* piece p of the block belongs to row p / pieces: kept as (row, rest) and stepped by 64 pieces, one division per lane */
+    const uint32_t stepRow = (uint32_t)kLightRaysBlock / pieces, stepRest = (uint32_t)kLightRaysBlock % pieces;
+    uint32_t row = lane / pieces, rest = lane % pieces;
+    for (uint32_t p = lane; p < total; p += kLightRaysBlock) {
+        out[p] = stage[row * pitch + rest];
+        row += stepRow; rest += stepRest;
+        if (rest >= pieces) { rest -= pieces; ++row; }
+    }
+}
+
+hipError_t launch_light_rays_picked(const DeviceScene& sc, const PickArgs& pa, hipStream_t s) {
+    const uint32_t blocks = (uint32_t)(((uint64_t)pa.la.n + kLightRaysBlock - 1) / kLightRaysBlock);
+    const size_t lds = (size_t)kLightRaysBlock * (2u * (pa.picks + 1u) + 1u) * sizeof(rtr_q4);
+    if (pa.picks == 0u || pa.picks + 1u > kLightStagedSlots || lds > kLightStagedLds) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_light_rays_picked, dim3(blocks), dim3(kLightRaysBlock), lds, s, sc, pa);
+    return hipGetLastError();
+}
+
+/* One lane per hit: k_shade_hits' record from the picks.  The sky, a light's colour and kind are fetch_surface<true>'s; at an object
+ * acc = 0, then acc = fma(contrib_p, occluded ? 0 : w_p, acc) for p = 0 ... P - 1 in order, then the directional term as light_loops adds
+ * it.  An occluded sample's BRDF is skipped unless the unshadowed sum is wanted (light_loops' rule, divergence D6).  With one light
+ * triangle, one sample and one pick of weight 1 every operation is the full loops' (x * 1, x / 1 and 0 + x give x back). */
+__global__ __launch_bounds__(kShadeBlock) void k_shade_hits_picked(DeviceScene sc, PickArgs pa) {
+    const LightArgs& la = pa.la;
+    const uint32_t k = blockIdx.x * kShadeBlock + threadIdx.x;
+    if (k >= la.n) return;
+    HitRec h;
+    rtr_v3 dir;
+    RenderArgs ra{};
+    const uint32_t kind = light_hit(sc, la, k, h, dir, ra);
+    const bool wantUnshadowed = (la.outputs & RTR_LIGHT_UNSHADOWED) != 0u;
+    const rtr_v3 zero = rtr_mk(0, 0, 0);
+    const uint32_t P = pa.picks, R = P + 1u;
+    Accum acc;
+    acc.analytic = acc.shadowed = acc.unshadowed = acc.avgNormal = acc.avgPosition = zero;
+    Surface sf;
+    LocalStats st;
+    if (kind != RTR_SURFACE_INVALID && fetch_surface<true, false>(sc, ra, h, dir, false, acc, sf, st)) {
+        const rtr_v3 currDiffuse = surface_diffuse(sf.om, sf.color);
+        const uint8_t* occ = la.occluded + (size_t)k * R;
+        rtr_v3 sumShadowed = zero, sumUnshadowed = zero;
+        for (uint32_t p = 0; p < P; ++p) {
+            const size_t at = (size_t)k * P + p;
+            const uint32_t j = pa.slotsIn[at];
+            PickedSample ps;
+            if (j >= pa.areaSlots || !picked_sample(sc, pa, ra, sf.hitPoint, j, ps)) continue;
+            const bool occluded = occ[p] != 0;
+            if (wantUnshadowed || !occluded) {
+                const float w = pa.weights ? pa.weights[at] : pa.defaultWeight;
+                const rtr_v3 contrib = area_sample_contrib(sf.hitNormal, sf.viewDir, sf.roughness, sf.mSpecular, currDiffuse, ps.lcol, ps.lintensity, ps.pdf, ps.dir, ps.dist);
+                sumShadowed = rtr_madd(sumShadowed, contrib, occluded ? 0.0f : w);
+                sumUnshadowed = rtr_madd(sumUnshadowed, contrib, w);
+            }
+        }
+        acc.shadowed = rtr_add(acc.shadowed, sumShadowed);
+        acc.unshadowed = rtr_add(acc.unshadowed, sumUnshadowed);
+        if (!(rtr_dot(sf.hitNormal, directional_light_dir()) <= 0.0f)) {      /* raygen.rgen:289-338, as light_loops */
+            const bool occluded = occ[P] != 0;
+            if (wantUnshadowed || !occluded) {
+                const rtr_v3 contrib = directional_contrib(sf.hitNormal, sf.viewDir, sf.roughness, sf.mSpecular, currDiffuse);
+                acc.shadowed = rtr_madd(acc.shadowed, contrib, occluded ? 0.0f : 1.0f);
+                acc.unshadowed = rtr_add(acc.unshadowed, contrib);
+            }
+        }
+    }
+    if (!wantUnshadowed) acc.unshadowed = zero;
+    float4* o = la.out + 3 * (size_t)k;
+    o[0] = make_float4(acc.shadowed.x, acc.shadowed.y, acc.shadowed.z, __uint_as_float(kind));
+    o[1] = make_float4(acc.unshadowed.x, acc.unshadowed.y, acc.unshadowed.z, 0.0f);
+    o[2] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+}
+
+hipError_t launch_shade_hits_picked(const DeviceScene& sc, const PickArgs& pa, hipStream_t s) {
+    hipLaunchKernelGGL(k_shade_hits_picked, dim3((uint32_t)(((uint64_t)pa.la.n + kShadeBlock - 1) / kShadeBlock)), dim3(kShadeBlock), 0, s, sc, pa);
     return hipGetLastError();
 }
 

@@ -15,6 +15,7 @@
 #include "rtr_bounce_host.h"
 #include "kernels/rtr_paths_launch.h"
 #include "rtr_paths_host.h"
+#include "rtr_pick_host.h"
 
 #include <hip/hip_runtime.h>
 
@@ -2851,6 +2852,63 @@ int rtr_compact_paths(rtr_ctx* c, const RtrRay* rays, const float* throughput, c
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
     return RTR_OK;
+}
+
+/* ---- picked light samples (kernels/rtr_query.hip; the rule is include/rtr_pick.h, the host form and the argument checks rtr_pick_host.cpp) -- */
+static int enqueue_light_picked(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, uint32_t n, const rtr_light_params* p,
+                                const rtr_pick_params* pick, const uint32_t* seeds, const uint32_t* slots, RtrRay* outRays, uint32_t* outSlots,
+                                const float* weights, const uint8_t* occluded, RtrRadiance* out, bool shade, const char* who) {
+    char msg[256];       /* the params and the arrays are checked first, which needs nothing of the handles */
+    int prc = RTR_ERR_INVALID_ARGUMENT;
+    if (!rtrdev::pick_check_params(who, p, pick, shade, msg, sizeof msg, &prc)) return fail(prc, "%s", msg);
+    const rtrdev::PickCall call{rays, hits, n, p, pick, seeds, shade, slots, outRays, outSlots, weights, occluded, out};
+    if (n && !rtrdev::pick_check_arrays(who, call, msg, sizeof msg)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s", msg);
+    if (!c || !s) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: null context or scene", who);
+    if (const int drc = check_same_device(c, s, who)) return drc;
+    uint32_t q = 0;
+    const int rc = light_slots(s, p, &q, who);
+    if (rc != RTR_OK) return rc;
+    const uint32_t areaSlots = q - 1u, tris = areaSlots / p->numShadowRays;
+    if (!rtrdev::pick_check_area(who, areaSlots, msg, sizeof msg)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s", msg);
+    if (n == 0) return RTR_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    rtrdev::PickArgs pa{};
+    rtrdev::LightArgs& la = pa.la;
+    la.rays = reinterpret_cast<const float4*>(rays); la.hits = reinterpret_cast<const float4*>(hits); la.seeds = seeds;
+    la.triCount = s->triCount.p; la.numInstances = s->numInstances; la.n = n; la.slots = pick->numPicks + 1u;
+    la.numAreaLights = p->numAreaLights; la.numShadowRays = p->numShadowRays; la.frame = p->frame; la.width = p->width; la.spp = p->spp;
+    la.outputs = p->outputs;
+    la.outRays = reinterpret_cast<float4*>(outRays); la.occluded = occluded; la.out = reinterpret_cast<float4*>(out);
+    pa.picks = pick->numPicks; pa.depth = pick->depth; pa.areaSlots = areaSlots;
+    pa.defaultWeight = (float)tris / (float)pick->numPicks;
+    pa.slotsIn = slots; pa.outSlots = outSlots; pa.weights = weights;
+    const hipError_t e = shade ? rtrdev::launch_shade_hits_picked(s->dev, pa, c->stream) : rtrdev::launch_light_rays_picked(s->dev, pa, c->stream);
+    if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: kernel launch: %s", who, hipGetErrorString(e));
+    return RTR_OK;
+}
+
+int rtr_light_rays_picked_async(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, uint32_t n, const rtr_light_params* p,
+                                const rtr_pick_params* pick, const uint32_t* seeds, const uint32_t* slotsIn, RtrRay* outRays, uint32_t* outSlots) {
+    return enqueue_light_picked(c, s, rays, hits, n, p, pick, seeds, slotsIn, outRays, outSlots, nullptr, nullptr, nullptr, false, "rtr_light_rays_picked_async");
+}
+
+int rtr_light_rays_picked(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, uint32_t n, const rtr_light_params* p,
+                          const rtr_pick_params* pick, const uint32_t* seeds, const uint32_t* slotsIn, RtrRay* outRays, uint32_t* outSlots) {
+    return join_if_enqueued(c, enqueue_light_picked(c, s, rays, hits, n, p, pick, seeds, slotsIn, outRays, outSlots, nullptr, nullptr, nullptr, false,
+                                                    "rtr_light_rays_picked"), n);
+}
+
+int rtr_shade_hits_picked_async(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, uint32_t n, const rtr_light_params* p,
+                                const rtr_pick_params* pick, const uint32_t* seeds, const uint32_t* slots, const float* weights,
+                                const uint8_t* occluded, RtrRadiance* out) {
+    return enqueue_light_picked(c, s, rays, hits, n, p, pick, seeds, slots, nullptr, nullptr, weights, occluded, out, true, "rtr_shade_hits_picked_async");
+}
+
+int rtr_shade_hits_picked(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, uint32_t n, const rtr_light_params* p,
+                          const rtr_pick_params* pick, const uint32_t* seeds, const uint32_t* slots, const float* weights,
+                          const uint8_t* occluded, RtrRadiance* out) {
+    return join_if_enqueued(c, enqueue_light_picked(c, s, rays, hits, n, p, pick, seeds, slots, nullptr, nullptr, weights, occluded, out, true,
+                                                    "rtr_shade_hits_picked"), n);
 }
 
 }  // extern "C"

@@ -1019,6 +1019,57 @@ int  rtr_shade_hits_picked(rtr_ctx* ctx, const rtr_scene* scene, const RtrRay* r
 int  rtr_host_pick_slots(const uint32_t* seeds, uint32_t numHits, uint32_t frame, uint32_t width, uint32_t spp, const rtr_pick_params* pick,
                          uint32_t areaSlots, uint32_t* outSlots);
 
+/* ---- multiple importance sampling at a path vertex: the picks and the bounce under the balance heuristic ------------------------
+ * With the picked samples alone a light reaches a path vertex only through its shadow rays, and a bounce ray that lands on a light counts
+ * for nothing.  These two calls let both count: rtr_mis_pick_weights gives the P picks of a vertex the weights rtr_shade_hits_picked is
+ * to apply, and rtr_emitter_hits gives what the vertex's bounce ray adds when its closest hit is a light.  The rule is include/rtr_mis.h
+ * (rtr_mis_params, RtrMisSample, RtrEmitter: include/rtr_types.h); DESIGN.md section 3 has the estimator.
+ *
+ * rtr_mis_pick_weights: outWeights[k * P + p] = ((float)Ttot / (float)P) * wPick of pick p of hit k, 0 for a pick that sends no ray
+ * (RTR_PICK_NONE, a slot >= A, a one-sided triangle facing away), for a hit that is not an object and where a value is not finite;
+ * outSamples (NULL, or numHits * P records, 16-B aligned): what each weight was made from, zeros beside a zero weight.  rays, hits,
+ * params, pick, seeds as rtr_shade_hits_picked takes them; slots: the numHits * P words rtr_light_rays_picked wrote, or NULL — then the
+ * slots it draws with slotsIn == NULL for the same params, pick and seeds.  mis: numPicks, numAreaLights and numShadowRays repeat pick's
+ * and params' (a difference is refused); lobes: the lobes the vertex's rtr_bounce_rays call samples.
+ * rtr_emitter_hits: out[k] for bounce ray rays[k] with closest hit hits[k], having left the vertex whose RtrSurface is prevSurfaces[k]
+ * and whose RtrBounce is bounces[k]: where the hit is a triangle of a light, radiance (to be multiplied by the throughput after the
+ * bounce), wBounce, the pick density lightPdf, the distance and the light-triangle record, kind = RTR_SURFACE_LIGHT; 32 zero bytes for a
+ * miss, an object, ids out of range, a dead bounce (pdf <= 0), a one-sided light met from behind, and where a value is not finite.  A
+ * light with index >= mis->numAreaLights is sampled by the bounce alone: wBounce = 1.  All arrays numRays records, 16-B aligned.
+ * Both are ENQUEUED on ctx's stream: no allocation, no join, no copy back.  Refused before anything is written
+ * (RTR_ERR_INVALID_ARGUMENT, the message names the function and the argument): a null or misaligned pointer, numPicks 0 or above
+ * RTR_PICK_MAX, lobes 0 or unknown, non-zero _reserved words, what rtr_shade_hits_picked refuses of params and pick, numAreaLights above
+ * the scene's lights, a scene on another device. */
+int  rtr_mis_pick_weights_async(rtr_ctx* ctx, const rtr_scene* scene, const RtrRay* rays, const RtrHit* hits, uint32_t numHits,
+                                const rtr_light_params* params, const rtr_pick_params* pick, const rtr_mis_params* mis, const uint32_t* seeds,
+                                const uint32_t* slots, float* outWeights, RtrMisSample* outSamples);
+int  rtr_emitter_hits_async(rtr_ctx* ctx, const rtr_scene* scene, const RtrRay* rays, const RtrHit* hits, const RtrSurface* prevSurfaces,
+                            const RtrBounce* bounces, uint32_t numRays, const rtr_mis_params* mis, RtrEmitter* out);
+/* The same two, then join ctx's stream (only that stream). */
+int  rtr_mis_pick_weights(rtr_ctx* ctx, const rtr_scene* scene, const RtrRay* rays, const RtrHit* hits, uint32_t numHits,
+                          const rtr_light_params* params, const rtr_pick_params* pick, const rtr_mis_params* mis, const uint32_t* seeds,
+                          const uint32_t* slots, float* outWeights, RtrMisSample* outSamples);
+int  rtr_emitter_hits(rtr_ctx* ctx, const rtr_scene* scene, const RtrRay* rays, const RtrHit* hits, const RtrSurface* prevSurfaces,
+                      const RtrBounce* bounces, uint32_t numRays, const rtr_mis_params* mis, RtrEmitter* out);
+/* A read-back of the scene's light-triangle table, current after updates: outRecords gets 16 floats per light triangle of ALL the
+ * scene's lights — {P0, area} {P1, pdfrec} {P2, -} {unit normal, -} in world space — and outFirst (NULL, or one word per light) the first
+ * record of each light; *outCount the number of triangles.  capacityTris < that count (or outRecords == NULL) copies nothing, reports the
+ * count and is refused with RTR_ERR_INVALID_ARGUMENT.  Joins the scene's stream and copies: HOST pointers. */
+int  rtr_scene_export_light_tris(const rtr_scene* scene, float* outRecords, uint32_t capacityTris, uint32_t* outFirst, uint32_t* outCount);
+/* The host forms of include/rtr_mis.h in plain loops, HOST pointers, no device; the device's words equal these.
+ * rtr_host_bounce_pdf: outPdf[k] = the density rtr_bounce_rays divides by at surfaces[k] (found by rays[k]) for the UNIT direction
+ * dirs[3k ... 3k + 2] and the lobes given: RtrBounce::pdf bit for bit for the direction it drew.
+ * rtr_host_mis_weights: outSamples[k] = {lightPdf, pb[k], wPick, cosLight[k], dist[k], area[k], 0, 0} and, with outWBounce != NULL,
+ * outWBounce[k] = wBounce.  P may be 0 here (nobody picks).
+ * rtr_host_emitter_hits: rtr_emitter_hits for a light table handed in (lightTris, lightTriFirst: rtr_scene_export_light_tris';
+ * lights: the scene's light infos). */
+int  rtr_host_bounce_pdf(const RtrRay* rays, const RtrSurface* surfaces, const float* dirs, uint32_t n, uint32_t lobes, float* outPdf);
+int  rtr_host_mis_weights(uint32_t n, const float* pb, const float* dist, const float* cosLight, const float* area, uint32_t Ttot, uint32_t P,
+                          RtrMisSample* outSamples, float* outWBounce);
+int  rtr_host_emitter_hits(const RtrRay* rays, const RtrHit* hits, const RtrSurface* prevSurfaces, const RtrBounce* bounces, uint32_t n,
+                           const float* lightTris, const uint32_t* lightTriFirst, const RtrAreaLightInfo* lights, uint32_t numLights,
+                           const rtr_mis_params* mis, RtrEmitter* out);
+
 /* ---- errors --------------------------------------------------------------------------- */
 const char* rtr_last_error(void);
 const char* rtr_status_string(int status);

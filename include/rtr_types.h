@@ -275,6 +275,30 @@ typedef struct rtr_pick_params {
     uint32_t _reserved[6];
 } rtr_pick_params;            /* 32 bytes */
 
+/* ---- multiple importance sampling at a path vertex (rtr_mis_pick_weights, rtr_emitter_hits; the rule is include/rtr_mis.h) -----------
+ * The balance heuristic over the numPicks (P) picked light samples of a vertex and its one bounce sample.  numAreaLights, numShadowRays:
+ * rtr_light_params' of the picks (Ttot = the triangles of the first numAreaLights lights; slot j belongs to light triangle
+ * j / numShadowRays); lobes: rtr_bounce_params::lobes of the bounce.  _reserved must be 0.
+ * RtrMisSample: what the pick side used for one pick — the solid-angle density of the pick (lightPdf, 0 where it is not finite) and of
+ * the bounce (bouncePdf) for the pick's direction, the MIS weight wPick, cosLight = dot(n_t, -dir), the distance, the light triangle's
+ * area and its record (lightTri); 32 zero bytes for a pick without a ray.
+ * RtrEmitter: what a bounce ray that ends on a light adds, to be multiplied by the throughput after the bounce; kind = RTR_SURFACE_LIGHT
+ * on a record that counts, 32 zero bytes otherwise. */
+typedef struct rtr_mis_params {
+    uint32_t numPicks, numAreaLights, numShadowRays, lobes;
+    uint32_t _reserved[4];
+} rtr_mis_params;             /* 32 bytes */
+
+typedef struct RtrMisSample {
+    float    lightPdf, bouncePdf, wPick, cosLight;
+    float    dist, area; uint32_t lightTri, _r;
+} RtrMisSample;
+
+typedef struct RtrEmitter {
+    float    radiance[3]; float wBounce;
+    float    lightPdf, dist; uint32_t lightTri, kind;
+} RtrEmitter;
+
 #ifdef __cplusplus
 }
 #endif
@@ -298,6 +322,9 @@ static_assert(sizeof(RtrBounce) == 32, "bounce record must be 32 B");
 static_assert(sizeof(rtr_bounce_params) == 32, "bounce params must be 32 B");
 static_assert(sizeof(rtr_compact_params) == 32, "compact params must be 32 B");
 static_assert(sizeof(rtr_pick_params) == 32, "pick params must be 32 B");
+static_assert(sizeof(rtr_mis_params) == 32, "mis params must be 32 B");
+static_assert(sizeof(RtrMisSample) == 32, "mis sample must be 32 B");
+static_assert(sizeof(RtrEmitter) == 32, "emitter record must be 32 B");
 #endif
 
 #endif /* RTR_TYPES_H */

@@ -101,6 +101,18 @@ class rtr_pick_params(C.Structure):
     _fields_ = [("numPicks", u32), ("depth", u32), ("_reserved", u32 * 6)]
 
 
+class rtr_mis_params(C.Structure):
+    _fields_ = [("numPicks", u32), ("numAreaLights", u32), ("numShadowRays", u32), ("lobes", u32), ("_reserved", u32 * 4)]
+
+
+class RtrMisSample(C.Structure):
+    _fields_ = [("lightPdf", f32), ("bouncePdf", f32), ("wPick", f32), ("cosLight", f32), ("dist", f32), ("area", f32), ("lightTri", u32), ("_r", u32)]
+
+
+class RtrEmitter(C.Structure):
+    _fields_ = [("radiance", f32 * 3), ("wBounce", f32), ("lightPdf", f32), ("dist", f32), ("lightTri", u32), ("kind", u32)]
+
+
 class rtr_vertex_range(C.Structure):
     """one range of rtr_scene_update_vertices: vertices firstVertex ... + numVertices of the scene's concatenated vertex array"""
     _fields_ = [("firstVertex", u32), ("numVertices", u32), ("positions", C.c_void_p), ("normals", C.c_void_p)]
@@ -182,6 +194,7 @@ assert C.sizeof(RtrRadiance) == 48 and C.sizeof(rtr_light_params) == 32
 assert C.sizeof(RtrBounce) == 32 and C.sizeof(rtr_bounce_params) == 32
 assert C.sizeof(rtr_compact_params) == 32
 assert C.sizeof(rtr_pick_params) == 32
+assert C.sizeof(rtr_mis_params) == 32 and C.sizeof(RtrMisSample) == 32 and C.sizeof(RtrEmitter) == 32
 assert C.sizeof(rtr_vertex_range) == 24
 assert C.sizeof(rtr_tree_cost) == 96 and C.alignment(rtr_tree_cost) == 8
 assert C.sizeof(rtr_update_status) == 32
@@ -317,6 +330,14 @@ RTR_SYMBOLS = {
     "rtr_shade_hits_picked_async": (C.c_int, [VP, VP, VP, VP, u32, P(rtr_light_params), P(rtr_pick_params), VP, VP, VP, VP, VP]),
     "rtr_shade_hits_picked": (C.c_int, [VP, VP, VP, VP, u32, P(rtr_light_params), P(rtr_pick_params), VP, VP, VP, VP, VP]),
     "rtr_host_pick_slots": (C.c_int, [VP, u32, u32, u32, u32, P(rtr_pick_params), u32, VP]),
+    "rtr_mis_pick_weights_async": (C.c_int, [VP, VP, VP, VP, u32, P(rtr_light_params), P(rtr_pick_params), P(rtr_mis_params), VP, VP, VP, VP]),
+    "rtr_mis_pick_weights": (C.c_int, [VP, VP, VP, VP, u32, P(rtr_light_params), P(rtr_pick_params), P(rtr_mis_params), VP, VP, VP, VP]),
+    "rtr_emitter_hits_async": (C.c_int, [VP, VP, VP, VP, VP, VP, u32, P(rtr_mis_params), VP]),
+    "rtr_emitter_hits": (C.c_int, [VP, VP, VP, VP, VP, VP, u32, P(rtr_mis_params), VP]),
+    "rtr_scene_export_light_tris": (C.c_int, [VP, VP, u32, VP, P(u32)]),
+    "rtr_host_bounce_pdf": (C.c_int, [VP, VP, VP, u32, u32, VP]),
+    "rtr_host_mis_weights": (C.c_int, [u32, VP, VP, VP, VP, u32, u32, VP, VP]),
+    "rtr_host_emitter_hits": (C.c_int, [VP, VP, VP, VP, u32, VP, VP, VP, u32, P(rtr_mis_params), VP]),
     "rtr_host_sincos_turn": (C.c_int, [VP, u32, VP, VP]),
 }
 

@@ -449,6 +449,18 @@ class Scene:
         _check(self.lib.rtr_scene_export_vertices(self.h, out.ctypes.data_as(A.VP) if out.size else None, out.nbytes), "rtr_scene_export_vertices")
         return out.view(np.float32).reshape(-1, 12) if raw else out
 
+    def export_light_tris(self):
+        """rtr_scene_export_light_tris: the light-triangle table as it is now -> (records, first): float32 (T, 16) — per triangle of all
+        the lights {P0, area} {P1, pdfrec} {P2, -} {unit normal, -} in world space — and uint32 (numLights,), the first record of each light"""
+        count = C.c_uint32(0)
+        self.lib.rtr_scene_export_light_tris(self.h, None, 0, None, C.byref(count))      # refused unless there are none: reports the count
+        n = int(count.value)
+        rec = np.zeros((n, 16), np.float32)
+        first = np.zeros(self._num_lights, np.uint32)
+        _check(self.lib.rtr_scene_export_light_tris(self.h, rec.ctypes.data_as(A.VP) if n else None, n, first.ctypes.data_as(A.VP) if first.size else None,
+                                                    C.byref(count)), "rtr_scene_export_light_tris")
+        return rec, first
+
     def set_instance_masks(self, masks):
         """rtr_scene_set_instance_masks: one 8-bit cull mask per instance, in instance order (array-like of uint8; default 0xff).  Only
         the masked queries (trace_rays / trace_occlusion with cull_mask or ray_masks) look at them; renders ignore them."""
@@ -1199,7 +1211,7 @@ def tonemap_pack(ctx, radiance, asynchronous=False):
 
 
 def direct_light(scene, rays, hits=None, params=None, seeds=None, ctx=None, max_ray_bytes=256 << 20, occlusion="dense", shadow_cull_mask=None, shadow_ray_flags=0,
-                 picks=None, pick_depth=0):
+                 pick_weights=None, picks=None, pick_depth=0):
     """The composed stage: closest hit (when hits is None) -> light_rays -> trace_rays(any_hit=True) -> shade_hits, in chunks of hits
     so that a chunk's light rays (n * Q * 32 bytes) stay within max_ray_bytes — a 1080p frame at Q = 7 would be 464 MB of rays at once.
     Chunks do not change the result.  occlusion: "dense" (trace_rays, the default), "queued" (trace_occlusion) or "queued_own_leaf"
@@ -1210,7 +1222,11 @@ def direct_light(scene, rays, hits=None, params=None, seeds=None, ctx=None, max_
     on the device.
     picks=P: the picked route — light_rays_picked(make_pick_params(P, pick_depth)) -> the same occlusion query -> shade_hits_picked with
     the default weights: P + 1 rays per hit instead of Q, an unbiased estimate of the same shadowed (and unshadowed) sum; the analytic sum
-    is refused.  "queued_own_leaf" raises ValueError with picks: the picked rays have no start hints.  None: the full loops, as before."""
+    is refused.  "queued_own_leaf" raises ValueError with picks: the picked rays have no start hints.  None: the full loops, as before.
+    pick_weights: with picks, a float32 (N, P) device tensor handed to shade_hits_picked as its weights (mis_pick_weights' for the slots
+    this call draws); None: the default weights, as before.  Without picks it raises ValueError."""
+    if pick_weights is not None and picks is None:
+        raise ValueError("direct_light: pick_weights are the weights of the picked route (picks must be given)")
     shadow_ray_flags = _ray_flags("direct_light", shadow_ray_flags, False)
     if occlusion not in ("dense", "queued", "queued_own_leaf"):
         raise ValueError(f"direct_light: occlusion must be 'dense', 'queued' or 'queued_own_leaf', got {occlusion!r}")
@@ -1244,6 +1260,9 @@ def direct_light(scene, rays, hits=None, params=None, seeds=None, ctx=None, max_
             lr, sl = light_rays_picked(scene, r, h, params, pick, seeds=sd, ctx=ctx)
             occ = (trace_occlusion(scene, lr, ctx=ctx, cull_mask=shadow_cull_mask, ray_flags=shadow_ray_flags) if occlusion == "queued"
                    else trace_rays(scene, lr, any_hit=True, ctx=ctx, cull_mask=shadow_cull_mask, ray_flags=shadow_ray_flags)).occluded
+            if pick_weights is not None:
+                out[a:b] = shade_hits_picked(scene, r, h, params, pick, sl, occ, weights=pick_weights[a:b], seeds=sd, ctx=ctx).raw
+                continue
             out[a:b] = shade_hits_picked(scene, r, h, params, pick, sl, occ, seeds=sd, ctx=ctx).raw
             continue
         if occlusion == "queued_own_leaf":
@@ -1471,6 +1490,164 @@ def host_compact_paths(rays, throughput, seeds=None, path_ids=None, params=None)
     return res
 
 
+# ---- MIS at a path vertex (rtr_mis_pick_weights, rtr_emitter_hits; include/rtr_mis.h) -------------------------------------------------
+class EmitterResult:
+    """What emitter_hits and host_emitter_hits give back.  raw: the (N, 8) float32 array of RtrEmitter records, of which radiance (N, 3)
+    (to be multiplied by the throughput after the bounce), w_bounce, light_pdf and dist (N,) are float32 views and light_tri, kind
+    (A.SURFACE_LIGHT where the record counts, 0 beside 32 zero bytes) int32 views."""
+    raw = radiance = w_bounce = light_pdf = dist = light_tri = kind = None
+
+
+def _emitter_result(raw, as_numpy, torch):
+    res = EmitterResult()
+    words = raw.view(np.int32) if as_numpy else raw.view(torch.int32)
+    res.raw = raw
+    res.radiance, res.w_bounce, res.light_pdf, res.dist, res.light_tri, res.kind = raw[:, 0:3], raw[:, 3], raw[:, 4], raw[:, 5], words[:, 6], words[:, 7]
+    return res
+
+
+def make_mis_params(picks, num_area_lights, shadow_rays, lobes=A.BOUNCE_DIFFUSE | A.BOUNCE_SPECULAR):
+    """rtr_mis_params: the picks per vertex (P), the light params' numAreaLights and numShadowRays, and the lobes the vertex's bounce samples"""
+    return A.rtr_mis_params(int(picks), int(num_area_lights), int(shadow_rays), int(lobes))
+
+
+def mis_pick_weights(scene, rays, hits, params, pick, mis, slots, seeds=None, samples=False, ctx=None, asynchronous=False):
+    """rtr_mis_pick_weights: the weights shade_hits_picked (weights=) is to give the picks of each hit when the vertex's bounce ray counts
+    the lights it meets (emitter_hits) -> float32 (N, P): (light triangles / P) * wPick of the balance heuristic, 0 for a pick without a
+    ray.  slots: light_rays_picked's (N, P), or None — the slots it draws by itself for the same params, pick and seeds.  samples=True:
+    -> (weights, samples), samples the float32 (N, P, 8) RtrMisSample records (lightPdf, bouncePdf, wPick, cosLight, dist, area and the
+    words lightTri, 0).  The other arguments as shade_hits_picked; numpy in gives numpy out."""
+    torch = _torch()
+    ctx = ctx or scene.ctx
+    dev = torch.device("cuda", ctx.device)
+    r, h, sd, as_numpy = _light_inputs(torch, scene, rays, hits, seeds, ctx, "mis_pick_weights", asynchronous)
+    n, p = int(r.shape[0]), int(pick.numPicks)
+    sl = _pick_vector(torch, slots, torch.int32, (np.int32, np.uint32), n, p, "slots", dev, "mis_pick_weights", as_numpy)
+    out = torch.empty((n, p), dtype=torch.float32, device=dev)
+    rec = torch.empty((n, p, 8), dtype=torch.float32, device=dev) if samples else None
+    _join_torchs_stream(ctx, torch, dev, asynchronous)
+    fn = ctx.lib.rtr_mis_pick_weights_async if asynchronous else ctx.lib.rtr_mis_pick_weights
+    _check(fn(ctx.h, scene.h, _ptr(r, n), _ptr(h, n), n, C.byref(params), C.byref(pick), C.byref(mis), _ptr(sd, n), _ptr(sl, n), _ptr(out, n),
+              _ptr(rec, n) if samples else None), "rtr_mis_pick_weights")
+    if as_numpy:
+        return (out.cpu().numpy(), rec.cpu().numpy()) if samples else out.cpu().numpy()
+    out._keep = (r, h, sd, sl)           # an asynchronous call's inputs stay alive with its result
+    return (out, rec) if samples else out
+
+
+def _records(torch, x, width, name, dev, who, as_numpy):
+    """a float32 (N, width) record array on the device: a tensor as it is, numpy uploaded"""
+    if as_numpy:
+        x = np.ascontiguousarray(x)
+        if x.dtype.itemsize != 4 or x.ndim != 2 or x.shape[1] != width:
+            raise ValueError(f"{who}: {name} must be 32-bit words (N, {width}), got {x.dtype} {x.shape}")
+        return torch.from_numpy(x.view(np.float32)).to(dev)
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.dim() != 2 or x.shape[1] != width or x.device != dev or not x.is_contiguous():
+        raise ValueError(f"{who}: {name} must be a contiguous float32 (N, {width}) tensor on {dev}")
+    return x
+
+
+def emitter_hits(scene, rays, hits, prev_surfaces, bounces, mis, ctx=None, asynchronous=False):
+    """rtr_emitter_hits: what each bounce ray adds where its closest hit is a light -> EmitterResult.  rays: the bounce rays (N, 8);
+    hits: their closest hits (a QueryResult or (N, 8) int32 records); prev_surfaces: the SurfaceResult (or (N, 20) float32 records) of the
+    vertices the rays left; bounces: bounce_rays' BounceResult (or its (N, 8) raw records) at those vertices; mis: make_mis_params(...).
+    Device tensors in give device tensors out, numpy in gives numpy out."""
+    torch = _torch()
+    ctx = ctx or scene.ctx
+    dev = torch.device("cuda", ctx.device)
+    if isinstance(prev_surfaces, SurfaceResult):
+        prev_surfaces = prev_surfaces.raw
+    if isinstance(bounces, BounceResult):
+        bounces = bounces.raw
+    r, h, _, as_numpy = _light_inputs(torch, scene, rays, hits, None, ctx, "emitter_hits", asynchronous)
+    n = int(r.shape[0])
+    if isinstance(prev_surfaces, np.ndarray) != as_numpy or isinstance(bounces, np.ndarray) != as_numpy:
+        raise ValueError("emitter_hits: rays, hits, prev_surfaces and bounces must all be numpy arrays or all be tensors")
+    s = _records(torch, prev_surfaces, 20, "prev_surfaces", dev, "emitter_hits", as_numpy)
+    b = _records(torch, bounces, 8, "bounces", dev, "emitter_hits", as_numpy)
+    if int(s.shape[0]) != n or int(b.shape[0]) != n:
+        raise ValueError(f"emitter_hits: {n} rays but {s.shape[0]} surfaces and {b.shape[0]} bounce records")
+    out = torch.empty((n, 8), dtype=torch.float32, device=dev)
+    _join_torchs_stream(ctx, torch, dev, asynchronous)
+    fn = ctx.lib.rtr_emitter_hits_async if asynchronous else ctx.lib.rtr_emitter_hits
+    _check(fn(ctx.h, scene.h, _ptr(r, n), _ptr(h, n), _ptr(s, n), _ptr(b, n), n, C.byref(mis), _ptr(out, n)), "rtr_emitter_hits")
+    res = _emitter_result(out.cpu().numpy() if as_numpy else out, as_numpy, torch)
+    res._keep = (r, h, s, b)
+    return res
+
+
+def _host_words(x, shape_tail, name, who):
+    x = np.ascontiguousarray(x)
+    if x.dtype.itemsize != 4 or x.ndim != 1 + len(shape_tail) or tuple(x.shape[1:]) != tuple(shape_tail):
+        raise ValueError(f"{who}: {name} must be 32-bit words (N, {', '.join(map(str, shape_tail))}), got {x.dtype} {x.shape}")
+    return x
+
+
+def host_bounce_pdf(rays, surfaces, dirs, lobes=A.BOUNCE_DIFFUSE | A.BOUNCE_SPECULAR):
+    """rtr_host_bounce_pdf: the density bounce_rays divides by, for the unit directions dirs (N, 3) at surfaces (N, 20) found by rays
+    (N, 8) -> float32 (N,).  For the direction host_bounce_rays drew it is BounceResult.pdf bit for bit; 0 below the horizon, for a
+    surface that is not an object and for input that is not finite."""
+    lib = A.hip_lib()
+    r, s, d = _host_words(rays, (8,), "rays", "host_bounce_pdf"), _host_words(surfaces, (20,), "surfaces", "host_bounce_pdf"), _host_words(dirs, (3,), "dirs", "host_bounce_pdf")
+    n = int(r.shape[0])
+    if s.shape[0] != n or d.shape[0] != n:
+        raise ValueError(f"host_bounce_pdf: {n} rays but {s.shape[0]} surfaces and {d.shape[0]} directions")
+    out = np.zeros(n, np.float32)
+    _check(lib.rtr_host_bounce_pdf(r.ctypes.data_as(A.VP) if n else None, s.ctypes.data_as(A.VP) if n else None, d.ctypes.data_as(A.VP) if n else None, n,
+                                   int(lobes), out.ctypes.data_as(A.VP) if n else None), "rtr_host_bounce_pdf")
+    return out
+
+
+def host_mis_weights(pb, dist, cos_light, area, tris, picks):
+    """rtr_host_mis_weights: the balance heuristic of include/rtr_mis.h for N directions -> (samples, w_bounce): the float32 (N, 8)
+    RtrMisSample records (lightPdf, pb, wPick, cosLight, dist, area, 0, 0) and wBounce (N,).  tris: Ttot; picks: P (0: nobody picks)."""
+    lib = A.hip_lib()
+    arrs = [np.ascontiguousarray(x, dtype=np.float32).reshape(-1) for x in (pb, dist, cos_light, area)]
+    n = int(arrs[0].size)
+    if any(a.size != n for a in arrs):
+        raise ValueError("host_mis_weights: pb, dist, cos_light and area must have one length")
+    out = np.zeros((n, 8), np.float32)
+    wb = np.zeros(n, np.float32)
+    ptrs = [a.ctypes.data_as(A.VP) if n else None for a in arrs]
+    _check(lib.rtr_host_mis_weights(n, ptrs[0], ptrs[1], ptrs[2], ptrs[3], int(tris), int(picks), out.ctypes.data_as(A.VP) if n else None,
+                                    wb.ctypes.data_as(A.VP) if n else None), "rtr_host_mis_weights")
+    return out, wb
+
+
+def _aligned_copy(x, align=16):
+    """a C-contiguous copy of x whose data starts at a multiple of align bytes"""
+    buf = np.zeros(x.nbytes + align, np.uint8)
+    off = (-buf.ctypes.data) % align
+    out = buf[off:off + x.nbytes].view(x.dtype).reshape(x.shape)
+    out[...] = x
+    return out
+
+
+def host_emitter_hits(rays, hits, prev_surfaces, bounces, light_tris, light_first, lights, mis):
+    """rtr_host_emitter_hits: emitter_hits on the host, no device -> EmitterResult of numpy arrays.  light_tris, light_first:
+    Scene.export_light_tris(); lights: the scene's A.RtrAreaLightInfo records (a sequence or a ctypes array)."""
+    lib = A.hip_lib()
+    who = "host_emitter_hits"
+    r, h = _aligned_copy(_host_words(rays, (8,), "rays", who)), _aligned_copy(_host_words(hits, (8,), "hits", who))
+    s, b = _aligned_copy(_host_words(prev_surfaces, (20,), "prev_surfaces", who)), _aligned_copy(_host_words(bounces, (8,), "bounces", who))
+    n = int(r.shape[0])
+    if h.shape[0] != n or s.shape[0] != n or b.shape[0] != n:
+        raise ValueError(f"{who}: {n} rays but {h.shape[0]} hits, {s.shape[0]} surfaces and {b.shape[0]} bounce records")
+    lt = np.ascontiguousarray(light_tris, dtype=np.float32).reshape(-1, 16)
+    lf = np.ascontiguousarray(light_first, dtype=np.uint32).reshape(-1)
+    li = (A.RtrAreaLightInfo * len(lights))(*lights)
+    if lf.size != len(lights):
+        raise ValueError(f"{who}: {lf.size} first records but {len(lights)} lights")
+    if any(int(lf[l]) + int(li[l].numTriangles) > lt.shape[0] for l in range(len(lights))):
+        raise ValueError(f"{who}: the lights' triangles reach past the {lt.shape[0]} records of light_tris")
+    out = _aligned_copy(np.zeros((n, 8), np.float32))
+    _check(lib.rtr_host_emitter_hits(r.ctypes.data_as(A.VP) if n else None, h.ctypes.data_as(A.VP) if n else None, s.ctypes.data_as(A.VP) if n else None,
+                                     b.ctypes.data_as(A.VP) if n else None, n, lt.ctypes.data_as(A.VP) if lt.size else None,
+                                     lf.ctypes.data_as(A.VP) if lf.size else None, li if len(lights) else None, len(lights), C.byref(mis),
+                                     out.ctypes.data_as(A.VP) if n else None), who)
+    return _emitter_result(out, True, None)
+
+
 class PathResult:
     """What path_trace gives back: radiance (N, 3) float32, the sum of per_depth, a list of bounces + 1 (N, 3) tensors — entry d is what
     the path's vertex d contributes, already multiplied by the throughput up to it.  live: with compact=True the number of paths that
@@ -1537,9 +1714,30 @@ def path_trace_picked(scene, rays, light_params, bounces, light_picks=None, pick
                        survival_floor, light_picks, pick_from)
 
 
+def path_trace_mis(scene, rays, light_params, bounces, light_picks=1, pick_from=1, seeds=None, occlusion="dense", bounce_cull_mask=None, bounce_ray_flags=0,
+                   max_ray_bytes=256 << 20, ctx=None, compact=False, roulette_from=None, survival_floor=0.05):
+    """path_trace_picked with multiple importance sampling between the picks of a vertex and its bounce ray (include/rtr_mis.h): the
+    same loop, the same arguments (light_picks=P is needed), and with mis = make_mis_params(P, numAreaLights, numShadowRays)
+
+        a vertex d >= pick_from with d < bounces is a MIS VERTEX: its direct_light(..., picks=P, pick_depth=d) takes
+            pick_weights = mis_pick_weights(scene, r, q, light_params, make_pick_params(P, d), mis, None, seeds = that call's seeds)
+        at a vertex d >= 1 whose hit is a light, rad = emitter_hits(scene, r, q, S, B, mis).radiance when vertex d - 1 was a MIS vertex
+            (S, B: the hit_surfaces and the bounce_rays records of vertex d - 1; T already holds that bounce's weight), else 0 as before.
+
+    The last vertex has no bounce after it: its picks keep the default weights.  A vertex that takes the full light loops (d < pick_from)
+    is no MIS vertex, and the bounce ray that leaves it counts no light.  With bounces=0 these are path_trace_picked's calls and bytes.
+    compact=True: S and B follow the survivors — compact_paths is called with path_ids=None, so that its ids are the row indices of that
+    call; S, B and the pixel ids are gathered with them in torch (ids = ids[rows]), which gives the ids compact_paths would have
+    gathered.  Without roulette the result is the plain loop's.  -> PathResult."""
+    if light_picks is None:
+        raise ValueError("path_trace_mis: light_picks must be given (the MIS is between the picks and the bounce)")
+    return _path_trace(scene, rays, light_params, bounces, seeds, occlusion, bounce_cull_mask, bounce_ray_flags, max_ray_bytes, ctx, compact, roulette_from,
+                       survival_floor, light_picks, pick_from, mis=True)
+
+
 def _path_trace(scene, rays, light_params, bounces, seeds, occlusion, bounce_cull_mask, bounce_ray_flags, max_ray_bytes, ctx, compact, roulette_from, survival_floor,
-                light_picks, pick_from):
-    """the loop of path_trace and path_trace_picked"""
+                light_picks, pick_from, mis=False):
+    """the loop of path_trace, path_trace_picked and path_trace_mis"""
     if roulette_from is not None and not compact:
         raise ValueError("path_trace: roulette_from needs compact=True (a path the roulette kills saves nothing while it keeps its lane)")
     if roulette_from is not None and int(roulette_from) < 0:
@@ -1569,16 +1767,24 @@ def _path_trace(scene, rays, light_params, bounces, seeds, occlusion, bounce_cul
     bounce_seeds = seeds
     if compact:
         res.live = [n]
+    mis_params = make_mis_params(light_picks, light_params.numAreaLights, light_params.numShadowRays) if mis else None
+    prev = None                          # mis: (surfaces, bounce records) of the vertex before when it was a MIS vertex
     for d in range(bounces + 1):
         q = trace_rays(scene, r, ctx=ctx) if d == 0 else trace_rays(scene, r, ctx=ctx, cull_mask=bounce_cull_mask, ray_flags=bounce_ray_flags)
         sd = seeds if d == 0 else _wrap32(base.to(torch.int64) + d * PATH_SEED_STEP)
-        if light_picks is not None and d >= int(pick_from):
+        mis_vertex = mis and int(pick_from) <= d < bounces
+        if mis_vertex:
+            w = mis_pick_weights(scene, r, q, light_params, make_pick_params(light_picks, d), mis_params, None, seeds=sd, ctx=ctx)
+            lit = direct_light(scene, r, q, light_params, seeds=sd, ctx=ctx, max_ray_bytes=max_ray_bytes, occlusion=occlusion, picks=light_picks, pick_depth=d,
+                               pick_weights=w)
+        elif light_picks is not None and d >= int(pick_from):
             lit = direct_light(scene, r, q, light_params, seeds=sd, ctx=ctx, max_ray_bytes=max_ray_bytes, occlusion=occlusion, picks=light_picks, pick_depth=d)
         else:
             lit = direct_light(scene, r, q, light_params, seeds=sd, ctx=ctx, max_ray_bytes=max_ray_bytes, occlusion=occlusion)
         rad = lit.shadowed
         if d >= 1:
-            rad = torch.where((lit.kind == A.SURFACE_LIGHT).unsqueeze(1), torch.zeros_like(rad), rad)
+            met = emitter_hits(scene, r, q, prev[0], prev[1], mis_params, ctx=ctx).radiance if prev is not None else torch.zeros_like(rad)
+            rad = torch.where((lit.kind == A.SURFACE_LIGHT).unsqueeze(1), met, rad)
         term = T * rad
         if ids is not None:
             full = torch.zeros((n, 3), dtype=torch.float32, device=rays.device)
@@ -1588,12 +1794,13 @@ def _path_trace(scene, rays, light_params, bounces, seeds, occlusion, bounce_cul
         res.radiance = res.radiance + term
         if d == bounces:
             break
-        b = bounce_rays(ctx, r, hit_surfaces(scene, r, q, ctx=ctx),
-                        make_bounce_params(frame=light_params.frame, depth=d, width=light_params.width, spp=light_params.spp), seeds=bounce_seeds)
+        surf = hit_surfaces(scene, r, q, ctx=ctx)
+        b = bounce_rays(ctx, r, surf, make_bounce_params(frame=light_params.frame, depth=d, width=light_params.width, spp=light_params.spp), seeds=bounce_seeds)
         T = T * b.weight
         r = b.rays
+        prev = (surf.raw, b.raw) if mis_vertex else None
         if compact:
-            c = compact_paths(ctx, r, T, seeds=base, path_ids=ids,
+            c = compact_paths(ctx, r, T, seeds=base, path_ids=None if mis else ids,
                               params=make_compact_params(frame=light_params.frame, depth=d, roulette=roulette_from is not None and d >= int(roulette_from),
                                                          survival_floor=survival_floor))
             m = c.count
@@ -1603,6 +1810,12 @@ def _path_trace(scene, rays, light_params, bounces, seeds, occlusion, bounce_cul
                     res.per_depth.append(torch.zeros((n, 3), dtype=torch.float32, device=rays.device))
                 res.live += [0] * (bounces - d - 1)
                 break
-            r, T, base, ids = c.rays[:m], c.throughput[:m], c.seeds[:m], c.path_ids[:m]
+            r, T, base, rows = c.rays[:m], c.throughput[:m], c.seeds[:m], c.path_ids[:m]
+            if mis:                      # the ids are this call's row indices: the records of the vertex and the pixel ids follow the survivors
+                rows = rows.to(torch.int64)
+                if prev is not None:
+                    prev = (prev[0][rows].contiguous(), prev[1][rows].contiguous())
+                rows = rows.to(torch.int32) if ids is None else ids[rows]
+            ids = rows
             bounce_seeds = base
     return res

@@ -67,6 +67,16 @@ struct PickArgs {
     const float* weights;        /* shade: n * P weights, or null (defaultWeight) */
 };
 
+/* Arguments of the MIS-weight kernel (rtr_mis_pick_weights): PickArgs as rtr_shade_hits_picked's (slotsIn may be null: drawn by the rule;
+ * defaultWeight = (float)tris / (float)P), and what include/rtr_mis.h needs. */
+struct MisPickArgs {
+    PickArgs pa;
+    float* outWeights;           /* n * P weights for rtr_shade_hits_picked */
+    float4* outSamples;          /* n * P RtrMisSample as 2 x float4, or null */
+    uint32_t lobes;              /* rtr_bounce_params::lobes of the vertex's bounce */
+    uint32_t tris;               /* Ttot: the triangles of the first numAreaLights lights */
+};
+
 /* The per-scene triangle -> leaf table (rtr_hit_leaves, rtr_light_rays_hinted): entry base[customIndex] + primitiveId, base = the prefix
  * sum of triCount, is the child code of the BVH2 leaf that holds that world-space record (RtrBvhNode::child: negative); an entry no leaf
  * wrote stays 0.  A start hint of the queued occlusion query (include/rtr.h). */
@@ -136,6 +146,8 @@ hipError_t launch_shade_hits(const DeviceScene& sc, const LightArgs& la, hipStre
 /* the picked forms: per hit the shadow rays of pa.picks area slots and of the directional light, and the slots; the sums over them */
 hipError_t launch_light_rays_picked(const DeviceScene& sc, const PickArgs& pa, hipStream_t stream);
 hipError_t launch_shade_hits_picked(const DeviceScene& sc, const PickArgs& pa, hipStream_t stream);
+/* per pick the weight under the balance heuristic with the vertex's bounce sample, and optionally what it was made from */
+hipError_t launch_mis_pick_weights(const DeviceScene& sc, const MisPickArgs& ma, hipStream_t stream);
 /* tonemap_pack of n float3 read strideWords floats apart */
 hipError_t launch_tonemap_pack(const float* radiance, uint32_t strideWords, uint32_t n, uint32_t* out, hipStream_t stream);
 

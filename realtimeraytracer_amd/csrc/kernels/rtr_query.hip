@@ -15,11 +15,13 @@
  * ray-gen shader does after the closest hit, by the renderer's own light_loops() with every query at a fixed slot of its hit.
  * k_light_rays_picked / k_shade_hits_picked (rtr_light_rays_picked, rtr_shade_hits_picked) do the same for a few picked area-light slots
  * of each hit (include/rtr_pick.h) and the directional light: the light loops' sample functions, called per picked slot.
+ * k_mis_pick_weights (rtr_mis_pick_weights) gives those picks their balance-heuristic weights against the vertex's bounce (include/rtr_mis.h).
  * Compiled with the library's flags (-ffp-contract=off): the numerical contract of include/rtr_math.h.
  */
 #include "rtr_query_device.h"
 #include "../../../include/rtr.h"
 #include "../../../include/rtr_pick.h"
+#include "../../../include/rtr_mis.h"
 
 namespace rtrdev {
 
@@ -702,6 +704,71 @@ __global__ __launch_bounds__(kShadeBlock) void k_shade_hits_picked(DeviceScene s
 
 hipError_t launch_shade_hits_picked(const DeviceScene& sc, const PickArgs& pa, hipStream_t s) {
     hipLaunchKernelGGL(k_shade_hits_picked, dim3((uint32_t)(((uint64_t)pa.la.n + kShadeBlock - 1) / kShadeBlock)), dim3(kShadeBlock), 0, s, sc, pa);
+    return hipGetLastError();
+}
+
+/* ---- MIS weights of the picks (rtr_mis_pick_weights; the rule is include/rtr_mis.h) -------------------------------------------------
+ * One lane per hit: for each pick the weight rtr_shade_hits_picked is to give it when the vertex's bounce ray counts the lights it
+ * meets (rtr_emitter_hits) — the default weight times the balance heuristic's wPick.  The hit, the surface and the sample are
+ * light_hit, fetch_surface and picked_sample, called as k_shade_hits_picked calls them, so the direction and the distance are the ones
+ * its contribution is evaluated at; the triangle's area and normal are words of the record picked_sample reads.  The bounce density of
+ * the pick's direction is rtr_mis_bounce_pdf on the words of the RtrSurface k_hit_surfaces writes for this hit (position, normal,
+ * colour, roughness, metallic) and the ray's origin.  A slot is the caller's (pa.slotsIn) or drawn by the rule k_light_rays_picked
+ * draws by.  Every weight and, when asked for, every RtrMisSample is written: zeros for a pick without a ray. */
+__global__ __launch_bounds__(kShadeBlock) void k_mis_pick_weights(DeviceScene sc, MisPickArgs ma) {
+    const PickArgs& pa = ma.pa;
+    const LightArgs& la = pa.la;
+    const uint32_t k = blockIdx.x * kShadeBlock + threadIdx.x;
+    if (k >= la.n) return;
+    HitRec h;
+    rtr_v3 dir;
+    RenderArgs ra{};
+    const bool object = light_hit(sc, la, k, h, dir, ra) == RTR_SURFACE_OBJECT;
+    const uint32_t P = pa.picks;
+    Accum acc;
+    Surface sf;
+    LocalStats st;
+    RtrRay ray{};
+    RtrSurface rs{};
+    if (object) {
+        /* <true>: with the colour and the material, which the density reads (acc is only written at a miss or a light) */
+        fetch_surface<true, false>(sc, ra, h, dir, false, acc, sf, st);
+        ray.origin[0] = ra.cam.position[0]; ray.origin[1] = ra.cam.position[1]; ray.origin[2] = ra.cam.position[2];
+        rs.position[0] = sf.hitPoint.x; rs.position[1] = sf.hitPoint.y; rs.position[2] = sf.hitPoint.z; rs.kind = RTR_SURFACE_OBJECT;
+        rs.normal[0] = sf.hitNormal.x; rs.normal[1] = sf.hitNormal.y; rs.normal[2] = sf.hitNormal.z;
+        rs.color[0] = sf.color.x; rs.color[1] = sf.color.y; rs.color[2] = sf.color.z;
+        rs.roughness = sf.roughness; rs.metallic = sf.metallic;
+    }
+    for (uint32_t p = 0; p < P; ++p) {
+        const size_t at = (size_t)k * P + p;
+        /* ra.info.frame is la.frame + the hit's seed base (light_hit) */
+        const uint32_t j = pa.slotsIn ? pa.slotsIn[at] : rtr_pick_slot(ra.info.frame, pa.depth, p, pa.areaSlots);
+        float w = 0.0f;
+        float4 m0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), m1 = m0;
+        PickedSample ps;
+        if (object && j < pa.areaSlots && picked_sample(sc, pa, ra, sf.hitPoint, j, ps)) {
+            const uint32_t t = j / la.numShadowRays;
+            const float4* rec = sc.lightTris + (size_t)t * kLightTriRecord;
+            const float area = rec[0].w;
+            const float cosLight = rtr_dot(f4xyz(rec[3]), rtr_neg(ps.dir));
+            const float pb = rtr_mis_bounce_pdf(&ray, &rs, ps.dir, ma.lobes);
+            float lightPdf, wPick, wBounce;
+            rtr_mis_weights(pb, ps.dist, cosLight, area, ma.tris, P, &lightPdf, &wPick, &wBounce);
+            const float wt = pa.defaultWeight * wPick;
+            if (rtr_bounce_finite(wt) & rtr_bounce_finite(ps.dist) & rtr_bounce_finite(cosLight) & rtr_bounce_finite(area) & rtr_bounce_finite3(ps.dir)) {
+                w = wt;
+                m0 = make_float4(lightPdf, pb, wPick, cosLight);
+                m1 = make_float4(ps.dist, area, __uint_as_float(t), 0.0f);
+            }
+        }
+        ma.outWeights[at] = w;
+        if (ma.outSamples) { ma.outSamples[2 * at] = m0; ma.outSamples[2 * at + 1] = m1; }
+    }
+}
+
+hipError_t launch_mis_pick_weights(const DeviceScene& sc, const MisPickArgs& ma, hipStream_t s) {
+    if (ma.pa.picks == 0u || ma.pa.picks > RTR_PICK_MAX) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_mis_pick_weights, dim3((uint32_t)(((uint64_t)ma.pa.la.n + kShadeBlock - 1) / kShadeBlock)), dim3(kShadeBlock), 0, s, sc, ma);
     return hipGetLastError();
 }
 

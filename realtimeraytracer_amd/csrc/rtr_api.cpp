@@ -16,6 +16,8 @@
 #include "kernels/rtr_paths_launch.h"
 #include "rtr_paths_host.h"
 #include "rtr_pick_host.h"
+#include "kernels/rtr_mis_launch.h"
+#include "rtr_mis_host.h"
 
 #include <hip/hip_runtime.h>
 
@@ -2909,6 +2911,104 @@ int rtr_shade_hits_picked(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, co
                           const uint8_t* occluded, RtrRadiance* out) {
     return join_if_enqueued(c, enqueue_light_picked(c, s, rays, hits, n, p, pick, seeds, slots, nullptr, nullptr, weights, occluded, out, true,
                                                     "rtr_shade_hits_picked"), n);
+}
+
+/* ---- MIS at a path vertex (kernels/rtr_query.hip, kernels/rtr_mis.hip; the rule is include/rtr_mis.h, the host forms and the argument checks rtr_mis_host.cpp) -- */
+static int enqueue_mis_pick_weights(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, uint32_t n, const rtr_light_params* p,
+                                    const rtr_pick_params* pick, const rtr_mis_params* mis, const uint32_t* seeds, const uint32_t* slots,
+                                    float* outWeights, RtrMisSample* outSamples, const char* who) {
+    char msg[256];       /* the params and the arrays are checked first, which needs nothing of the handles */
+    int prc = RTR_ERR_INVALID_ARGUMENT;
+    if (!rtrdev::mis_check_params(who, mis, msg, sizeof msg)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s", msg);
+    if (!rtrdev::pick_check_params(who, p, pick, true, msg, sizeof msg, &prc)) return fail(prc, "%s", msg);
+    if (!rtrdev::mis_check_pick_call(who, p, pick, mis, rays, hits, n, seeds, slots, outWeights, outSamples, msg, sizeof msg))
+        return fail(RTR_ERR_INVALID_ARGUMENT, "%s", msg);
+    if (!c || !s) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: null context or scene", who);
+    if (const int drc = check_same_device(c, s, who)) return drc;
+    uint32_t q = 0;
+    const int rc = light_slots(s, p, &q, who);
+    if (rc != RTR_OK) return rc;
+    const uint32_t areaSlots = q - 1u, tris = areaSlots / p->numShadowRays;
+    if (!rtrdev::pick_check_area(who, areaSlots, msg, sizeof msg)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s", msg);
+    if (n == 0) return RTR_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    rtrdev::MisPickArgs ma{};
+    rtrdev::PickArgs& pa = ma.pa;
+    rtrdev::LightArgs& la = pa.la;
+    la.rays = reinterpret_cast<const float4*>(rays); la.hits = reinterpret_cast<const float4*>(hits); la.seeds = seeds;
+    la.triCount = s->triCount.p; la.numInstances = s->numInstances; la.n = n; la.slots = pick->numPicks + 1u;
+    la.numAreaLights = p->numAreaLights; la.numShadowRays = p->numShadowRays; la.frame = p->frame; la.width = p->width; la.spp = p->spp;
+    la.outputs = p->outputs;
+    pa.picks = pick->numPicks; pa.depth = pick->depth; pa.areaSlots = areaSlots;
+    pa.defaultWeight = (float)tris / (float)pick->numPicks;
+    pa.slotsIn = slots;
+    ma.outWeights = outWeights; ma.outSamples = reinterpret_cast<float4*>(outSamples); ma.lobes = mis->lobes; ma.tris = tris;
+    const hipError_t e = rtrdev::launch_mis_pick_weights(s->dev, ma, c->stream);
+    if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: kernel launch: %s", who, hipGetErrorString(e));
+    return RTR_OK;
+}
+
+int rtr_mis_pick_weights_async(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, uint32_t n, const rtr_light_params* p,
+                               const rtr_pick_params* pick, const rtr_mis_params* mis, const uint32_t* seeds, const uint32_t* slots, float* outWeights,
+                               RtrMisSample* outSamples) {
+    return enqueue_mis_pick_weights(c, s, rays, hits, n, p, pick, mis, seeds, slots, outWeights, outSamples, "rtr_mis_pick_weights_async");
+}
+
+int rtr_mis_pick_weights(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, uint32_t n, const rtr_light_params* p,
+                         const rtr_pick_params* pick, const rtr_mis_params* mis, const uint32_t* seeds, const uint32_t* slots, float* outWeights,
+                         RtrMisSample* outSamples) {
+    return join_if_enqueued(c, enqueue_mis_pick_weights(c, s, rays, hits, n, p, pick, mis, seeds, slots, outWeights, outSamples, "rtr_mis_pick_weights"), n);
+}
+
+static int enqueue_emitter_hits(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, const RtrSurface* prevSurfaces,
+                                const RtrBounce* bounces, uint32_t n, const rtr_mis_params* mis, RtrEmitter* out, const char* who) {
+    char msg[256];       /* the params and the arrays are checked first, which needs nothing of the handles */
+    if (!rtrdev::mis_check_params(who, mis, msg, sizeof msg)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s", msg);
+    if (n && !rtrdev::mis_check_emitter_arrays(who, rays, hits, prevSurfaces, bounces, out, msg, sizeof msg)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s", msg);
+    if (!c || !s) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: null context or scene", who);
+    if (const int drc = check_same_device(c, s, who)) return drc;
+    if (mis->numAreaLights > s->numLights) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: numAreaLights %u > scene lights %u", who, mis->numAreaLights, s->numLights);
+    uint64_t tris = 0;
+    for (uint32_t l = 0; l < mis->numAreaLights; ++l) tris += s->hostLights[l].numTriangles;
+    if (tris > RTR_PICK_MAX_SLOTS) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: %llu light triangles are more than 2^24", who, (unsigned long long)tris);
+    if (n == 0) return RTR_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    rtrdev::EmitterArgs a{};
+    a.rays = reinterpret_cast<const float4*>(rays); a.hits = reinterpret_cast<const float4*>(hits);
+    a.prevSurfaces = reinterpret_cast<const float4*>(prevSurfaces); a.bounces = reinterpret_cast<const float4*>(bounces);
+    a.out = reinterpret_cast<float4*>(out);
+    a.lightTris = s->dev.lightTris; a.lightTriFirst = s->dev.lightTriFirst; a.lights = s->dev.lights; a.numLights = s->numLights;
+    a.numAreaLights = mis->numAreaLights; a.tris = (uint32_t)tris; a.picks = mis->numPicks; a.n = n;
+    const hipError_t e = rtrdev::launch_emitter_hits(a, c->stream);
+    if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: kernel launch: %s", who, hipGetErrorString(e));
+    return RTR_OK;
+}
+
+int rtr_emitter_hits_async(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, const RtrSurface* prevSurfaces, const RtrBounce* bounces,
+                           uint32_t n, const rtr_mis_params* mis, RtrEmitter* out) {
+    return enqueue_emitter_hits(c, s, rays, hits, prevSurfaces, bounces, n, mis, out, "rtr_emitter_hits_async");
+}
+
+int rtr_emitter_hits(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, const RtrSurface* prevSurfaces, const RtrBounce* bounces,
+                     uint32_t n, const rtr_mis_params* mis, RtrEmitter* out) {
+    return join_if_enqueued(c, enqueue_emitter_hits(c, s, rays, hits, prevSurfaces, bounces, n, mis, out, "rtr_emitter_hits"), n);
+}
+
+int rtr_scene_export_light_tris(const rtr_scene* s, float* outRecords, uint32_t capacityTris, uint32_t* outFirst, uint32_t* outCount) {
+    static const char* who = "rtr_scene_export_light_tris";
+    if (!s) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: null scene", who);
+    uint32_t total = 0;
+    std::vector<uint32_t> first(s->numLights);
+    for (uint32_t l = 0; l < s->numLights; ++l) { first[l] = total; total += s->hostLights[l].numTriangles; }
+    if (outCount) *outCount = total;
+    if (capacityTris < total || (total && !outRecords))
+        return fail(RTR_ERR_INVALID_ARGUMENT, "%s: capacity %u light triangles, %u are needed", who, outRecords ? capacityTris : 0u, total);
+    HIP_TRY(hipSetDevice(s->ctx->device));
+    hipStream_t st = s->ctx->stream;
+    if (total) HIP_TRY(hipMemcpyAsync(outRecords, s->lightTris.p, (size_t)total * rtrdev::kLightTriRecord * sizeof(float4), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (outFirst) for (uint32_t l = 0; l < s->numLights; ++l) outFirst[l] = first[l];
+    return RTR_OK;
 }
 
 }  // extern "C"

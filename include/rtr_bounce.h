@@ -107,7 +107,8 @@ RTR_HD void rtr_bounce_dead(RtrRay* next, RtrBounce* b) {
 
 /* The whole per-hit function.  ray: the ray that found the hit (its origin gives the view vector, as in rtr_light_rays); sf: the hit's
  * RtrSurface; seedBase: seeds[k] or the pixel's px * 733 + py * 1933.  A record is DEAD (rtr_bounce_dead) when the surface is not an
- * object, a float it uses is not finite, no lobe that was asked for can be sampled, the direction leaves below the surface
+ * object, a float it uses is not finite, no lobe that was asked for can be sampled, the specular lobe drew a half vector on the far side
+ * of the view (dot(V, H) <= 0: DESIGN.md section 3, views from behind the shading normal), the direction leaves below the surface
  * (dot(N, L) <= 0), the mixture pdf is <= 0 or not finite, or a weight channel is negative or not finite.  No output word is ever a
  * NaN or an infinity. */
 RTR_HD void rtr_bounce_sample(const RtrRay* ray, const RtrSurface* sf, uint32_t seedBase, const rtr_bounce_params* p, RtrRay* next, RtrBounce* b) {
@@ -145,7 +146,13 @@ RTR_HD void rtr_bounce_sample(const RtrRay* ray, const RtrSurface* sf, uint32_t 
         const float den = rtr_fma(alpha2, u1, 1.0f - u1);
         const float cosT = rtr_sqrt((1.0f - u1) / den), sinT = rtr_sqrt((alpha2 * u1) / den);
         const rtr_v3 H = rtr_normalize(rtr_madd(rtr_madd(rtr_scale(T, sinT * cs), B, sinT * sn), N, cosT));
-        L = rtr_normalize(rtr_sub(rtr_scale(H, 2.0f * rtr_dot(V, H)), V));
+        /* A half vector on the far side of the view has no specular sample.  Seen from above (dot(N, V) > 0) its reflection leaves below
+         * the surface and was dead already; seen from behind the shading normal it can leave above it, dot(N, L) = 2 VoH NoH - NoV > 0,
+         * in a direction whose evaluated half vector is -H, where the density below has no specular term (its NoH > 0 guard, and the
+         * renderer's chi(NoH)): the record would be live with a density it was not drawn from.  With VoH > 0, normalize(V + L) is H. */
+        const float VoHs = rtr_dot(V, H);
+        if (!(VoHs > 0.0f)) return;
+        L = rtr_normalize(rtr_sub(rtr_scale(H, 2.0f * VoHs), V));
     } else {
         const float r = rtr_sqrt(u1);
         L = rtr_normalize(rtr_madd(rtr_madd(rtr_scale(T, r * cs), B, r * sn), N, rtr_sqrt(rtr_max(1.0f - u1, 0.0f))));
@@ -156,7 +163,15 @@ RTR_HD void rtr_bounce_sample(const RtrRay* ray, const RtrSurface* sf, uint32_t 
     /* the balance heuristic over the lobes that are on; the density of the specular lobe is the UNCLAMPED GGX the directions are drawn
      * from (the max(den, 0.001) of GGX_Distribution belongs to the BRDF) */
     const rtr_v3 Hm = rtr_normalize(rtr_add(V, L));
-    const float NoH = rtr_dot(N, Hm), VoH = rtr_dot(V, Hm);
+    const float NoH = rtr_dot(N, Hm);
+    float VoH = rtr_dot(V, Hm);
+    /* V + L cancels for L near -V, where the specular density has its 1 / VoH singularity: the sum is 2 VoH long and its float32 components
+     * are good to 6e-8 absolute, so that Hm is good to 3e-8 / VoH and dot(V, Hm), nearly at right angles to V, to no more than that
+     * ABSOLUTE: 30 % of a VoH of 3e-4, and no sign left below 2e-4, which used to strike the specular term from a density that is at its
+     * largest there.  |V + L| / 2 is the same number and keeps its digits (3e-8 / VoH RELATIVE).  A view from above keeps the bits of the
+     * dot product: alive, it is never near -V (dot(N, L) = 2 VoH NoH - NoV).  A view from behind or along the surface (dot(N, V) <= 0),
+     * which is, takes the length, and so does any record whose dot product has lost its sign. */
+    if (!(rtr_dot(N, V) > 0.0f) | !(VoH > 0.0f)) VoH = 0.5f * rtr_length(rtr_add(V, L));
     const float pdfD = NoL / RTR_BOUNCE_PI_F;
     float pdfS = 0.0f;
     if (specOn & (NoH > 0.0f) & (VoH > 0.0f)) {

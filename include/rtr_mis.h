@@ -28,8 +28,10 @@
 
 /* The density rtr_bounce_sample divides by, for an arbitrary UNIT direction L: its expressions in its order, so that for the direction it
  * drew this is RtrBounce::pdf bit for bit (a record rtr_bounce_sample declared dead for its weight or origin has pdf 0 there and not
- * here).  0 for a surface that is not an object, a float that is not finite, no lobe to sample, dot(N, L) <= 0, or a density that is
- * not positive and finite. */
+ * here).  The specular term is that of the evaluated half vector Hm = normalize(V + L) where dot(N, Hm) > 0 and nothing elsewhere:
+ * rtr_bounce_sample drops a drawn half vector with dot(V, H) <= 0, so that Hm is the H every live specular sample was drawn with, also
+ * for a view from behind the shading normal.  0 for a surface that is not an object, a float that is not finite,
+ * no lobe to sample, dot(N, L) <= 0, or a density that is not positive and finite. */
 RTR_HD float rtr_mis_bounce_pdf(const RtrRay* ray, const RtrSurface* sf, rtr_v3 L, uint32_t lobes) {
     if (sf->kind != RTR_SURFACE_OBJECT) return 0.0f;
     const rtr_v3 P = rtr_ld3(sf->position), N = rtr_ld3(sf->normal), color = rtr_ld3(sf->color), O = rtr_ld3(ray->origin);
@@ -50,7 +52,9 @@ RTR_HD float rtr_mis_bounce_pdf(const RtrRay* ray, const RtrSurface* sf, rtr_v3 
     const float NoL = rtr_dot(N, L);
     if (!(NoL > 0.0f)) return 0.0f;
     const rtr_v3 Hm = rtr_normalize(rtr_add(V, L));
-    const float NoH = rtr_dot(N, Hm), VoH = rtr_dot(V, Hm);
+    const float NoH = rtr_dot(N, Hm);
+    float VoH = rtr_dot(V, Hm);
+    if (!(rtr_dot(N, V) > 0.0f) | !(VoH > 0.0f)) VoH = 0.5f * rtr_length(rtr_add(V, L));      /* V + L cancels near L = -V: as rtr_bounce_sample */
     const float pdfD = NoL / RTR_BOUNCE_PI_F;
     float pdfS = 0.0f;
     if (specOn & (NoH > 0.0f) & (VoH > 0.0f)) {

@@ -14,7 +14,14 @@ events on the context's stream, which is torch's current stream; three warm-up c
 five repeats of the cases are interleaved, so that a drift of the clock is in all of them alike, and the minimum is reported beside the
 median and all five.  path_trace is timed with a host clock around the call and a device join, five interleaved repeats.
 
-    python profiles/mis_rate.py [--width 1920 --height 1080] [--frames 64] [--out profiles/mis/mis_rate_1080p.json]
+  back_seen    (--back-seen [--label KEY]: this section alone) the share of the hits of vertex 0 and of vertex 1 that are objects seen
+               from behind their shading normal (dot(N, V) < 0), the per-frame differences of the image sums picked - full and MIS -
+               full (full: api.path_trace) over frames 0 ... 63 at 2 bounces with their standard errors, and the wall time of
+               path_trace_mis at 2 bounces.  Merged into the JSON at --out under back_seen[KEY]; the rest of the file is kept.  The
+               committed file holds two builds of one session, which DESIGN.md section 3 compares: the one before the rule for views
+               from behind the shading normal (--label build_before_the_rule, run against that build's libraries) and the one with it.
+
+    python profiles/mis_rate.py [--width 1920 --height 1080] [--frames 64] [--out profiles/mis/mis_rate_1080p.json] [--back-seen [--label KEY]]
 """
 import argparse
 import json
@@ -33,8 +40,50 @@ from realtimeraytracer_amd import _abi as A  # noqa: E402
 from realtimeraytracer_amd import api, scenes  # noqa: E402
 
 
+def back_seen(ctx, scene, s, rays, W, H, frames):
+    def share(r, surf):
+        nov = ((r[:, 0:3] - surf.position) * surf.normal).sum(1)
+        obj = surf.kind == A.SURFACE_OBJECT
+        return float((obj & (nov < 0)).sum()) / max(int(obj.sum()), 1), int(obj.sum())
+
+    hits = api.trace_rays(scene, rays).hits
+    surf = api.hit_surfaces(scene, rays, hits)
+    b = api.bounce_rays(ctx, rays, surf, api.make_bounce_params(frame=0, depth=0, width=W, spp=1))
+    live = (b.rays != 0).any(1)
+    r1 = b.rays[live]
+    surf1 = api.hit_surfaces(scene, r1, api.trace_rays(scene, r1).hits)
+    s0, n0 = share(rays, surf)
+    s1, n1 = share(r1, surf1)
+    out = {"frames": frames, "vertex_0": {"object_hits": n0, "seen_from_behind_share": s0}, "vertex_1": {"object_hits": n1, "seen_from_behind_share": s1}}
+    sums = {"full": [], "picked": [], "mis": []}
+    for f in range(frames):
+        lpf = api.make_light_params(s.num_lights, 3, f, W, 1, A.LIGHT_SHADOWED)
+        sums["full"].append(float(api.path_trace(scene, rays, lpf, 2).radiance.double().sum()))
+        sums["picked"].append(float(api.path_trace_picked(scene, rays, lpf, 2, light_picks=1).radiance.double().sum()))
+        sums["mis"].append(float(api.path_trace_mis(scene, rays, lpf, 2, light_picks=1).radiance.double().sum()))
+    t = {k: torch.tensor(v, dtype=torch.float64) for k, v in sums.items()}
+    out["image_sum_mean"] = {k: float(v.mean()) for k, v in t.items()}
+    for k in ("picked", "mis"):
+        d = t[k] - t["full"]
+        out[f"{k}_minus_full"] = {"mean": float(d.mean()), "se": float(d.std() / frames ** 0.5), "relative": float(d.mean() / t["full"].mean())}
+    lp = api.make_light_params(s.num_lights, 3, 0, W, 1, A.LIGHT_SHADOWED)
+
+    def run():
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        api.path_trace_mis(scene, rays, lp, 2, light_picks=1)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3
+
+    run()
+    out["path_trace_mis_2_bounces_ms"] = five_each({"mis": run})["mis"]
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--back-seen", action="store_true")
+    ap.add_argument("--label", default="build_with_the_rule", help="with --back-seen: the key of this build's figures under back_seen")
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--frames", type=int, default=64)
@@ -54,6 +103,15 @@ def main():
            "device": ctx.device_name(), "kernel_revision": A.hip_lib().rtr_kernel_revision().decode()}
 
     rays = api.camera_rays(ctx, s.camera, W, H, 1)
+    if args.back_seen:
+        # merged into the file that is there under the build's label: the other sections and the other build's figures stay
+        merged = json.load(open(args.out)) if os.path.exists(args.out) else out
+        merged.setdefault("back_seen", {})[args.label] = dict(back_seen(ctx, scene, s, rays, W, H, args.frames), kernel_revision=out["kernel_revision"])
+        ctx.set_stream(None)
+        with open(args.out, "w") as f:
+            f.write(json.dumps(merged, indent=1) + "\n")
+        print(json.dumps({"back_seen": {args.label: merged["back_seen"][args.label]}}))
+        return
     hits = api.trace_rays(scene, rays).hits
     surf = api.hit_surfaces(scene, rays, hits)
     pick, mis = api.make_pick_params(1, 0), api.make_mis_params(1, s.num_lights, 3)

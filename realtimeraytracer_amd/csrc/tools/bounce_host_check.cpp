@@ -1,6 +1,6 @@
 /* bounce_host_check — rtr_host_bounce_rays under the host sanitizers: a stand-alone program around rtr_bounce_host.cpp, built with
  * -fsanitize=address,undefined by `make bounce_host_check` (never part of a library, never loaded into Python).  It runs a few hundred
- * records — live ones over the whole material range, every kind of dead one, seeds whose random number is exactly 1.0, exactly sized
+ * records — live ones over the whole material range, views from behind the shading normal and along the surface, every kind of dead one, seeds whose random number is exactly 1.0, exactly sized
  * heap arrays so that a read or write past a record is caught — and every refusal.  Exit status 0 and "ok" when nothing was reported. */
 #include "../rtr_bounce_host.h"
 
@@ -47,6 +47,11 @@ int main() {
         for (int a = 0; a < 3; ++a) { sf[k].position[a] = unit(s) * 20 - 10; sf[k].color[a] = (k % 11 == 0) ? 0.0f : unit(s); }
         sf[k].roughness = rough[k % 5]; sf[k].metallic = metal[(k / 5) % 3];
         for (int a = 0; a < 3; ++a) rays[k].origin[a] = sf[k].position[a] + sf[k].normal[a] * (0.5f + unit(s)) + (unit(s) - 0.5f);
+        if (k % 7 == 2) for (int a = 0; a < 3; ++a) rays[k].origin[a] = 2.0f * sf[k].position[a] - rays[k].origin[a];      /* seen from behind the normal */
+        if (k % 43 == 5) {                                                  /* dot(N, V) exactly 0 */
+            sf[k].normal[0] = 0; sf[k].normal[1] = 0; sf[k].normal[2] = (k & 1u) ? 1.0f : -1.0f;
+            rays[k].origin[2] = sf[k].position[2];
+        }
         rays[k].tmax = 10000.0f;
         seeds[k] = lcg(s);
         if (k % 13 == 1) seeds[k] = 60418823u - 7919u - 3u - 100u * (k % 3);   /* rtr_random == 1.0 for u1, u2 or uLobe */

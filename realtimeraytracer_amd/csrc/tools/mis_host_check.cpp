@@ -1,7 +1,8 @@
 /* mis_host_check — the host forms of include/rtr_mis.h under the host sanitizers: a stand-alone program around rtr_mis_host.cpp, built
  * with -fsanitize=address,undefined by `make mis_host_check` (never part of a library, never loaded into Python).  It runs
  * rtr_host_bounce_pdf, rtr_host_mis_weights and rtr_host_emitter_hits for 1 ... 20000 records on exactly sized heap arrays, so that a
- * read or write past an array is caught, with inputs that reach every early return (surfaces that are not objects, NaN and infinite
+ * read or write past an array is caught, with inputs that reach every early return (surfaces that are not objects, views from behind
+ * the shading normal and along the surface, the direction -V, NaN and infinite
  * words, zero and denormal densities, distances and areas, ids out of range, one-sided lights from behind); checks that no output word is
  * a NaN or an infinity, that the weights add up to 1 where either is set, and every kind of refusal.  Exit status 0 and "ok" when
  * nothing was reported. */
@@ -69,7 +70,10 @@ int main() {
                 f.normal[2] = 1.0f; f.color[0] = unit(s); f.color[1] = unit(s); f.color[2] = unit(s);
                 f.roughness = (k % 5u) * 0.25f; f.metallic = (k % 3u) * 0.5f;
                 rays[k].origin[0] = f.position[0] + 0.3f; rays[k].origin[1] = f.position[1] - 0.2f; rays[k].origin[2] = 3.0f;
+                if (k % 4u == 1u) rays[k].origin[2] = -3.0f;                     /* seen from behind the shading normal */
+                if (k % 23u == 7u) rays[k].origin[2] = 0.0f;                     /* dot(N, V) exactly 0 */
                 float d[3] = {unit(s) - 0.5f, unit(s) - 0.5f, unit(s) * 1.2f - 0.2f};
+                if (k % 31u == 9u) for (int i = 0; i < 3; ++i) d[i] = f.position[i] - rays[k].origin[i];      /* L = -V: V + L cancels */
                 const float len = sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]) + 1e-20f;
                 for (int i = 0; i < 3; ++i) dirs[3 * (size_t)k + i] = d[i] / len;
                 /* the bounce ray of this vertex: from 0.01 above it along dirs, ending on the plane z = 2 when it goes up */

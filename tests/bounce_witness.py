@@ -81,8 +81,14 @@ def brdf(N, V, L, roughness, F0, om, color):
 
 def sample(rays, surfaces, seed_base, frame=0, depth=0, lobes=DIFFUSE | SPECULAR, normal_offset=0.01, tmin=0.001, tmax=10000.0):
     """rtr_bounce_sample in float64 on (N, 8) float32 rays and (N, 20) float32 RtrSurface records -> dict of float64 arrays:
-    rays (N, 8), weight (N, 3), pdf, p_spec, lobe (0 = dead), and the two margins a discrete decision hangs on: lobe_margin =
-    |uLobe - pSpec| where both lobes are on (inf otherwise), nol = dot(N, L) of the sampled direction (nan where none was sampled)."""
+    rays (N, 8), weight (N, 3), pdf, p_spec, lobe (0 = dead), and the three margins a discrete decision hangs on: lobe_margin =
+    |uLobe - pSpec| where both lobes are on (inf otherwise), nol = dot(N, L) of the sampled direction (nan where none was sampled),
+    voh = dot(V, H) of the half vector the specular lobe drew (inf where the diffuse lobe was taken).
+
+    The rule for a view from behind the shading normal (dot(N, V) < 0), as DESIGN.md section 3 states it: the specular lobe draws H
+    around N and reflects V about it; a draw with dot(V, H) <= 0 is DEAD.  For the draws that remain, normalize(V + L) is H itself, so
+    the density evaluated from L, D(N.H) N.H / (4 V.H) where N.H > 0, is the density L was drawn with; the directions the dropped draws
+    would have reached are left to the cosine lobe."""
     rays = np.asarray(rays, np.float32)
     sf = np.asarray(surfaces).view(np.float32)
     n = len(rays)
@@ -118,7 +124,10 @@ def sample(rays, surfaces, seed_base, frame=0, depth=0, lobes=DIFFUSE | SPECULAR
         den = a2 * u1 + (1.0 - u1)
         cosT, sinT = np.sqrt((1.0 - u1) / den), np.sqrt(a2 * u1 / den)
         H = _normalize((sinT * cs)[:, None] * T + (sinT * sn)[:, None] * B + cosT[:, None] * N)
-        Ls = _normalize(2.0 * _dot(V, H)[:, None] * H - V)
+        VoHs = _dot(V, H)
+        voh = np.where(take_spec, VoHs, np.inf)
+        live &= ~take_spec | (VoHs > 0.0)                   # a half vector on the far side of the view: no specular sample
+        Ls = _normalize(2.0 * VoHs[:, None] * H - V)
         # diffuse
         r = np.sqrt(u1)
         Ld = _normalize((r * cs)[:, None] * T + (r * sn)[:, None] * B + np.sqrt(np.maximum(1.0 - u1, 0.0))[:, None] * N)
@@ -133,7 +142,7 @@ def sample(rays, surfaces, seed_base, frame=0, depth=0, lobes=DIFFUSE | SPECULAR
         Nn = _normalize(N)
         NxH = np.cross(Nn, Hm)
         dn = _dot(Nn, Hm) ** 2 * a2 + _dot(NxH, NxH)
-        pdfS =np.where(spec_on & (NoH > 0.0) & (VoH > 0.0), a2 / (PI_F * dn * dn) * NoH / (4.0 * VoH), 0.0)
+        pdfS = np.where(spec_on & (NoH > 0.0) & (VoH > 0.0), a2 / (PI_F * dn * dn) * NoH / (4.0 * VoH), 0.0)
         pdf = p_spec * pdfS + (1.0 - p_spec) * pdfD
         live &= (pdf > 0.0) & np.isfinite(pdf)
         w = brdf(N, V, L, roughness, F0, om, color) * NoL[:, None] / pdf[:, None]
@@ -144,20 +153,44 @@ def sample(rays, surfaces, seed_base, frame=0, depth=0, lobes=DIFFUSE | SPECULAR
     out[~live] = 0.0
     z = lambda x: np.where(live if np.ndim(x) == 1 else live[:, None], x, 0.0)      # noqa: E731
     return {"rays": out, "weight": z(w), "pdf": z(pdf), "p_spec": z(p_spec), "lobe": z(np.where(take_spec, SPECULAR, DIFFUSE)).astype(np.int64),
-            "lobe_margin": lobe_margin, "nol": NoL}
+            "lobe_margin": lobe_margin, "nol": NoL, "voh": voh}
 
 
-def make_surfaces(n, seed=1234):
-    """About n synthetic hits: (rays (N, 8) float32, surfaces (N, 20) float32, seeds (N,) uint32).  Random unit normals, view directions in
-    the normal's upper hemisphere at distances 0.5 ... 20, roughness of {0, 1e-3, 0.05, 0.3, 1}, metallic of {0, 0.5, 1}, colours random
-    or black or white, random seeds.  Every record is an object with finite floats."""
+GRAZING_BAND = 1e-3          # |dot(N, V)| of the grazing band of make_surfaces(views="sphere")
+
+
+def make_surfaces(n, seed=1234, views="upper"):
+    """About n synthetic hits: (rays (N, 8) float32, surfaces (N, 20) float32, seeds (N,) uint32).  Random unit normals, view directions
+    at distances 0.5 ... 20, roughness of {0, 1e-3, 0.05, 0.3, 1}, metallic of {0, 0.5, 1}, colours random or black or white, random
+    seeds.  Every record is an object with finite floats.
+
+    views="upper": every view vector mirrored into the normal's upper hemisphere.
+    views="sphere": the view vectors as drawn, half of them behind the shading normal, and two bands of grazing views from a random
+    stream of their own: 6 % of the records with dot(N, V) uniform in [-1e-3, 1e-3], and 6 % with dot(N, V) exactly 0 in float32 (the
+    normal is a signed coordinate axis, and the ray's origin and the hit share that coordinate bit for bit)."""
+    if views not in ("upper", "sphere"):
+        raise ValueError(f"views {views!r}: 'upper' or 'sphere'")
     rng = np.random.default_rng(seed)
     N = rng.normal(size=(n, 3))
     N /= np.linalg.norm(N, axis=1)[:, None]
     v = rng.normal(size=(n, 3))
     v /= np.linalg.norm(v, axis=1)[:, None]
     nv = np.sum(v * N, axis=1)
-    v = np.where((nv < 0)[:, None], v - 2.0 * nv[:, None] * N, v)          # mirrored into the upper hemisphere
+    if views == "upper":
+        v = np.where((nv < 0)[:, None], v - 2.0 * nv[:, None] * N, v)      # mirrored into the upper hemisphere
+    else:
+        rb = np.random.default_rng([seed, 1])
+        band = rb.uniform(size=n)
+        near, zero = band < 0.06, (band >= 0.06) & (band < 0.12)
+        axis, sign = rb.integers(0, 3, size=n), rb.choice([-1.0, 1.0], size=n)
+        N[zero] = 0.0
+        N[zero, axis[zero]] = sign[zero]
+        graze = near | zero
+        t = v - np.sum(v * N, axis=1)[:, None] * N                         # the tangential part of the drawn view, exactly 0 along an axis normal
+        t[zero, axis[zero]] = 0.0
+        t /= np.linalg.norm(t, axis=1)[:, None]
+        eps = np.where(near, rb.uniform(-GRAZING_BAND, GRAZING_BAND, size=n), 0.0)
+        v = np.where(graze[:, None], t * np.sqrt(1.0 - eps * eps)[:, None] + eps[:, None] * N, v)
     P = rng.uniform(-10.0, 10.0, size=(n, 3))
     O = P + v * rng.uniform(0.5, 20.0, size=(n, 1))
     color = rng.uniform(0.0, 1.0, size=(n, 3))
@@ -211,7 +244,9 @@ def dead_cases():
 
 
 def albedo_quadrature(roughness, metallic, color, nov, n_theta=1200, n_phi=2400):
-    """integral of BRDF * cos over the hemisphere for N = +z and V at dot(N, V) = nov: midpoint rule in (cos theta, phi) -> (3,)"""
+    """integral of BRDF * cos over the hemisphere of N = +z for V at dot(N, V) = nov: midpoint rule in (cos theta, phi) -> (3,).  nov may
+    be 0 or negative, a view from behind the shading normal: the integral is still over the directions with dot(N, L) > 0, of the BRDF
+    as the renderer evaluates it there (dot(N, V) clamped at 0.1 in the denominator, chi(dot(N, H)) of the evaluated half vector)."""
     N = np.array([0.0, 0.0, 1.0])
     V = np.array([np.sqrt(1.0 - nov * nov), 0.0, nov])
     color = np.asarray(color, np.float64)
@@ -226,3 +261,75 @@ def albedo_quadrature(roughness, metallic, color, nov, n_theta=1200, n_phi=2400)
         f = brdf(N, V, L.reshape(-1, 3), roughness, F0, om, color) * L.reshape(-1, 3)[:, 2:3]
         total += f.sum(0)
     return total * (1.0 / n_theta) * (2.0 * np.pi / n_phi)
+
+
+def _midpoint_rect(density, mu0, mu1, phi0, phi1, sub):
+    mu = mu0 + (np.arange(sub) + 0.5) * ((mu1 - mu0) / sub)
+    phi = phi0 + (np.arange(sub) + 0.5) * ((phi1 - phi0) / sub)
+    st = np.sqrt(1.0 - mu * mu)
+    L = np.stack([st[:, None] * np.cos(phi)[None, :], st[:, None] * np.sin(phi)[None, :], np.broadcast_to(mu[:, None], (sub, sub))], axis=-1)
+    return float(np.asarray(density(L.reshape(-1, 3)), np.float64).sum()) * ((mu1 - mu0) / sub) * ((phi1 - phi0) / sub)
+
+
+def _graded_rect(density, mu0, mu1, phi0, phi1, sub, point, levels):
+    """the midpoint rule on a rectangle that is halved in both directions, level after level, around the point it contains or touches"""
+    tol = 1e-12
+    if levels == 0 or not (mu0 - tol <= point[0] <= mu1 + tol and phi0 - tol <= point[1] <= phi1 + tol):
+        return _midpoint_rect(density, mu0, mu1, phi0, phi1, sub)
+    mm, pm = 0.5 * (mu0 + mu1), 0.5 * (phi0 + phi1)
+    return sum(_graded_rect(density, a, b, c, d, sub, point, levels - 1)
+               for a, b in ((mu0, mm), (mm, mu1)) for c, d in ((phi0, pm), (pm, phi1)))
+
+
+def density_cells(density, n_mu=8, n_phi=16, sub=64, refine_at=None, levels=0):
+    """The integral of density(L) over each cell of a grid of n_mu (cos theta = L.z, 0 ... 1) x n_phi (phi = atan2(L.y, L.x), 0 ... 2 pi)
+    cells of the hemisphere around +z: the midpoint rule on sub x sub points per cell, in float64 -> (n_mu, n_phi).  density takes
+    (M, 3) float64 unit vectors and returns (M,) values per unit solid angle; d omega = d mu d phi.
+
+    refine_at = (mu, phi), 0 < phi < 2 pi: the cells that contain or touch that point are integrated on a graded grid instead, halved
+    `levels` times around it with sub x sub midpoints in every piece.  The density of a reflection about a sampled half vector,
+    D N.H / (4 V.H), has an integrable 1 / r singularity at L = -V (V.H = 0), which lies inside the hemisphere for a view from behind
+    the normal and just below its horizon for a grazing one; there the plain midpoint rule converges with the first power of the
+    spacing only, the graded one loses nothing to it."""
+    mu = (np.arange(n_mu * sub) + 0.5) / (n_mu * sub)
+    phi = (np.arange(n_phi * sub) + 0.5) * (2.0 * np.pi / (n_phi * sub))
+    st = np.sqrt(1.0 - mu * mu)
+    out = np.zeros((n_mu, n_phi))
+    for i in range(n_mu):
+        rows = slice(i * sub, (i + 1) * sub)
+        L = np.stack([st[rows, None] * np.cos(phi)[None, :], st[rows, None] * np.sin(phi)[None, :],
+                      np.broadcast_to(mu[rows, None], (sub, len(phi)))], axis=-1)
+        f = np.asarray(density(L.reshape(-1, 3)), np.float64).reshape(sub, n_phi, sub)
+        out[i] = f.sum(axis=(0, 2))
+    out *= (1.0 / (n_mu * sub)) * (2.0 * np.pi / (n_phi * sub))
+    if refine_at is not None and levels > 0:
+        dm, dp, tol = 1.0 / n_mu, 2.0 * np.pi / n_phi, 1e-12
+        for i in range(n_mu):
+            for j in range(n_phi):
+                if i * dm - tol <= refine_at[0] <= (i + 1) * dm + tol and j * dp - tol <= refine_at[1] <= (j + 1) * dp + tol:
+                    out[i, j] = _graded_rect(density, i * dm, (i + 1) * dm, j * dp, (j + 1) * dp, sub, refine_at, levels)
+    return out
+
+
+def albedo_quadrature_half_vector(roughness, metallic, color, nov, n_theta=900, n_psi=1800):
+    """The integral of albedo_quadrature over the half vector instead of the direction: L = 2 (V.H) H - V, d omega_L = 4 (V.H) d omega_H,
+    H over the half of the sphere with V.H > 0 (which L covers the sphere from once), on a midpoint grid of (theta_h, psi) around N = +z,
+    d omega_H = sin theta_h d theta_h d psi -> (3,).  For a grazing view of a narrow lobe the directions of the lobe lie in a sliver
+    2 alpha wide and 2 alpha (V.H) thick that no uniform grid of directions resolves, while the half vectors fill a round cap of
+    radius alpha.  The integrand is continuous: BRDF * dot(N, L) goes to 0 at the horizon and the Jacobian at V.H = 0."""
+    N = np.array([0.0, 0.0, 1.0])
+    V = np.array([np.sqrt(1.0 - nov * nov), 0.0, nov])
+    color = np.asarray(color, np.float64)
+    om = 1.0 - metallic
+    F0 = color * metallic + 0.04 * om
+    psi = (np.arange(n_psi) + 0.5) * (2.0 * np.pi / n_psi)
+    total = np.zeros(3)
+    for block in np.array_split(np.arange(n_theta), 24):
+        th = (block + 0.5) * (np.pi / n_theta)
+        st, ct = np.sin(th), np.cos(th)
+        H = np.stack([st[:, None] * np.cos(psi)[None, :], st[:, None] * np.sin(psi)[None, :], np.broadcast_to(ct[:, None], (len(th), n_psi))], axis=-1).reshape(-1, 3)
+        voh = H @ V
+        L = 2.0 * voh[:, None] * H - V
+        jac = np.where((voh > 0.0) & (L[:, 2] > 0.0), 4.0 * voh * L[:, 2], 0.0) * np.repeat(st, n_psi)
+        total += (brdf(N, V, L, roughness, F0, om, color) * jac[:, None]).sum(0)
+    return total * (np.pi / n_theta) * (2.0 * np.pi / n_psi)

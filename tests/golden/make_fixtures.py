@@ -14,6 +14,11 @@ place where /root/reference and oracle/_ref exist):  python tests/golden/make_fi
   ref_ltc_tables.bin      the reference's two 64x64 RGBA32F LTC tables (external/LUT/ltc_matrix.h, dumped by
                           oracle/_ref/ltc_dump) as 2 x 16384 little-endian floats: what tests/test_ltc_tables.py
                           and tests/test_host_scene.py compare the shipped tables with
+  bounce_upper_crc.npy    (`make_fixtures.py bounce`) CRC-32 of each record (RtrRay + RtrBounce, 64 bytes) rtr_host_bounce_rays
+                          gives on bounce_witness.make_surfaces(20000, views="upper"), one row per lobe mask (both, diffuse,
+                          specular), recorded with the build BEFORE the rule for views from behind the shading normal
+                           went in: tests/test_bounce_host.py holds every later build to it.  Not to be
+                          regenerated with a build whose upper-hemisphere records are meant to have moved without saying so.
 """
 import hashlib
 import json
@@ -95,7 +100,29 @@ def ltc_tables():
     print("ref_ltc_tables.bin:", len(raw), "bytes")
 
 
+def bounce_record_crcs(lobes):
+    """CRC-32 of the 64 bytes (RtrRay, RtrBounce) of each record of the upper-hemisphere synthetic surfaces -> (20000,) uint32"""
+    import zlib
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import bounce_witness as W
+    from realtimeraytracer_amd import api
+    rays, sf, seeds = W.make_surfaces(20000, views="upper")
+    h = api.host_bounce_rays(rays, sf, api.make_bounce_params(lobes=lobes), seeds)
+    rec = np.concatenate([np.ascontiguousarray(h.rays).view(np.uint32), np.ascontiguousarray(h.raw).view(np.uint32)], axis=1)
+    assert rec.shape == (20000, 16)
+    return np.array([zlib.crc32(r.tobytes()) for r in rec], np.uint32)
+
+
+def bounce_upper():
+    """6) rtr_host_bounce_rays on the upper-hemisphere synthetic surfaces -> tests/golden/bounce_upper_crc.npy"""
+    out = np.stack([bounce_record_crcs(lobes) for lobes in (3, 1, 2)])
+    np.save(os.path.join(HERE, "bounce_upper_crc.npy"), out)
+    print("bounce_upper_crc.npy:", out.shape, out.dtype)
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "bounce":
+        return bounce_upper()
     if len(sys.argv) > 1 and sys.argv[1] == "images":
         return image_hashes()
     if len(sys.argv) > 1 and sys.argv[1] == "ltc":

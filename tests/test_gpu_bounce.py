@@ -60,6 +60,25 @@ def test_device_equals_host_on_synthetic_surfaces(gpu_ctx, lobes):
     _assert_device_is_host(gpu_ctx, rays, sf, None, p, f"lobes {lobes}, pixel seeds")
 
 
+@pytest.mark.parametrize("lobes", LOBES)
+def test_device_equals_host_on_synthetic_surfaces_over_the_sphere_of_views(gpu_ctx, lobes):
+    """the 20 000 records of make_surfaces(views="sphere"): 47 % seen from behind the shading normal, a grazing band, dot(N, V) exactly
+    0.  Rays, RtrBounce words and the dead records' zero bytes are the host's, and the density rtr_host_bounce_pdf gives for the
+    direction drawn is RtrBounce::pdf bit for bit."""
+    rays, sf, seeds = W.make_surfaces(20000, views="sphere")
+    for n in (65, 20000):
+        p = api.make_bounce_params(lobes=lobes)
+        host = _assert_device_is_host(gpu_ctx, rays[:n].copy(), sf[:n].copy(), seeds[:n].copy(), p, f"sphere of views, lobes {lobes}, {n} hits")
+    live = host.lobe != 0
+    nov = np.sum(sf[:, 4:7].astype(np.float64) * (rays[:, 0:3].astype(np.float64) - sf[:, 0:3]), axis=1)
+    assert (live & (nov < 0)).sum() > 500 and (~live & (nov < 0)).sum() > 1000
+    assert not host.rays[~live].any() and not host.raw.view(np.uint32)[~live].any()
+    pdf = api.host_bounce_pdf(rays[live], sf[live], host.rays[live, 4:7], lobes)
+    assert (pdf.view(np.uint32) == host.pdf[live].view(np.uint32)).all()
+    p = api.make_bounce_params(frame=9, depth=2, width=171, spp=2, lobes=lobes, normal_offset=0.002, tmin=0.01, tmax=50.0)
+    _assert_device_is_host(gpu_ctx, rays, sf, None, p, f"sphere of views, lobes {lobes}, pixel seeds")
+
+
 @pytest.mark.parametrize("case", ["cornell_box", "textured_room", "random_rays"])
 def test_device_equals_host_on_real_surfaces(gpu_ctx, scene_cache, case):
     if case == "textured_room":

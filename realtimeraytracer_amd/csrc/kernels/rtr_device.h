@@ -650,27 +650,43 @@ __device__ __forceinline__ rtr_v3 directional_contrib(rtr_v3 hitNormal, rtr_v3 v
                              ((directLightColor.z * directLightIntensity) * NdotL) * 20.0f);
     return rtr_mul(BRDF, Lr);
 }
-/* the point on light triangle P the sample s of pixel (px, py) of frame `frame` aims at (raygen.rgen:206-215) */
-__device__ __forceinline__ rtr_v3 light_sample_pos(const rtr_v3* P, uint32_t s, uint32_t px, uint32_t py, uint32_t frame) {
-    const uint32_t seed = s + px * 733u + py * 1933u + frame;
+/* the point on light triangle P the sample s of pixel (px, py) of frame `frame` aims at (raygen.rgen:206-215), in two parts: the folded
+ * pair of randoms — a function of (s, px, py, frame) only, the same for every light and light triangle of the pixel — and the point the
+ * pair picks on a triangle.  seed0 = px * 733 + py * 1933 + frame; the sample's seed is s + seed0 (unsigned sums: the order is free). */
+struct SamplePair { float r1, r2; };
+__device__ __forceinline__ uint32_t light_sample_seed0(uint32_t px, uint32_t py, uint32_t frame) { return px * 733u + py * 1933u + frame; }
+__device__ __forceinline__ SamplePair light_sample_pair(uint32_t seed) {
     float r1 = rtr_random(seed), r2 = rtr_random(seed + 100u);
     if (r1 + r2 > 1.0f) { r1 = 1.0f - r1; r2 = 1.0f - r2; }
-    return rtr_madd(rtr_madd(P[0], rtr_sub(P[1], P[0]), r1), rtr_sub(P[2], P[0]), r2);
+    return SamplePair{r1, r2};
 }
+__device__ __forceinline__ rtr_v3 light_sample_at(const rtr_v3* P, SamplePair r) {
+    return rtr_madd(rtr_madd(P[0], rtr_sub(P[1], P[0]), r.r1), rtr_sub(P[2], P[0]), r.r2);
+}
+__device__ __forceinline__ rtr_v3 light_sample_pos(const rtr_v3* P, uint32_t s, uint32_t px, uint32_t py, uint32_t frame) {
+    return light_sample_at(P, light_sample_pair(s + light_sample_seed0(px, py, frame)));
+}
+/* Where light_loops takes a sample's pair from.  DrawnSamples, the default, draws it where it is used: once per light triangle.  A
+ * kernel that keeps a pixel's pairs somewhere (k_shadow_gen_oct, k_shadow_gen: ParkedSamples) passes a source of its own. */
+struct DrawnSamples {
+    uint32_t px, py, frame;
+    __device__ __forceinline__ SamplePair pair(uint32_t s) const { return light_sample_pair(s + light_sample_seed0(px, py, frame)); }
+};
 
 /* The light loops of raygen.rgen:165-338 for one shaded surface point.  Policy::occluded(origin, dir, tmax, rawDir, intoSurface) (rawDir: dir before normalisation, only its signs are meaningful; intoSurface: dot(hitNormal, rawDir) < 0) answers the
  * shadow query; Policy::kShade == false (counting / emitting the queries) skips the BRDF arithmetic but keeps the exact
  * sequence of queries.  Policy::slots_at(first) is told, ahead of the queries of a light triangle that is not culled, the FIXED slot of
  * its first sample — (lightTriFirst[li] + ti) * numShadowRays, include/rtr.h: rtr_light_slots — and kDirectionalSlot ahead of the
  * directional light's query.  The renderer's policies number their queries as they come and leave it empty; the ray-query stage
- * (kernels/rtr_query.hip), whose slots do not depend on which triangles were culled, takes its place from it. */
+ * (kernels/rtr_query.hip), whose slots do not depend on which triangles were culled, takes its place from it.  Samples::pair(s) is
+ * sample s's pair of randoms (DrawnSamples above, or a kernel's store of them: the same values either way). */
 constexpr uint32_t kDirectionalSlot = 0xffffffffu;
 #ifndef RTR_INTO_EXPR
 #define RTR_INTO_EXPR (rtr_dot(hitNormal, lightVec) < 0.0f)
 #endif
-template <class Policy, bool STATS>
-__device__ __forceinline__ void light_loops(const DeviceScene& sc, const RenderArgs& ra, uint32_t px, uint32_t py,
-                                            const Surface& sf, uint32_t want, Accum& o, Policy& pol, LocalStats& st) {
+template <class Policy, bool STATS, class Samples>
+__device__ __forceinline__ void light_loops_from(const DeviceScene& sc, const RenderArgs& ra, const Samples& smp,
+                                                 const Surface& sf, uint32_t want, Accum& o, Policy& pol, LocalStats& st) {
     /* want: bit 0 = the analytic (LTC) image is an output, bit 1 = the unshadowed image is.  When the unshadowed image is not
      * asked for, an occluded sample contributes contrib * 0 to the only sum that is kept, so its BRDF is not evaluated here.  The
      * reference (and the oracle) evaluate it and multiply by 0: identical whenever contrib is finite; an occluded sample whose
@@ -706,7 +722,7 @@ __device__ __forceinline__ void light_loops(const DeviceScene& sc, const RenderA
             rtr_v3 shadowedSample = rtr_mk(0, 0, 0), unshadowedSample = rtr_mk(0, 0, 0);
             pol.slots_at((sc.lightTriFirst[li] + ti) * ra.numShadowRays);
             for (uint32_t s = 0; s < ra.numShadowRays; ++s) {                             /* :206 */
-                const rtr_v3 lightSamplePos = light_sample_pos(P, s, px, py, ra.info.frame);
+                const rtr_v3 lightSamplePos = light_sample_at(P, smp.pair(s));
                 const rtr_v3 lightVec = rtr_sub(lightSamplePos, hitPoint);
                 const rtr_v3 sampledLightDir = rtr_normalize(lightVec);
                 const float lightDistance = rtr_length(lightVec);
@@ -752,6 +768,12 @@ __device__ __forceinline__ void light_loops(const DeviceScene& sc, const RenderA
         o.unshadowed = rtr_add(o.unshadowed, contrib);
         o.analytic = rtr_add(o.analytic, contrib);
     }
+}
+/* the light loops with every pair drawn where it is used: the form of every kernel that keeps no pairs */
+template <class Policy, bool STATS>
+__device__ __forceinline__ void light_loops(const DeviceScene& sc, const RenderArgs& ra, uint32_t px, uint32_t py,
+                                            const Surface& sf, uint32_t want, Accum& o, Policy& pol, LocalStats& st) {
+    light_loops_from<Policy, STATS>(sc, ra, DrawnSamples{px, py, ra.info.frame}, sf, want, o, pol, st);
 }
 
 /* The per-light-triangle part of raygen.rgen:174-196, hoisted out of the pixel loops (see light_loops). */

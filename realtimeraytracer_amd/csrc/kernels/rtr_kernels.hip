@@ -440,12 +440,41 @@ __device__ __forceinline__ uint32_t wave_total(uint32_t v) {
     return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
 }
 
+/* A pixel's sample pairs, drawn ONCE and kept in LDS for both passes of the queue build.  A pair depends on (sample, pixel, frame) only
+ * (light_sample_pair), yet the light loops ask for it once per light triangle and the queue build walks them twice: on the bench frame
+ * (2 lights x 2 triangles x 3 samples) twelve draws per pixel and pass where three are distinct, each two PCG hashes, two converts and
+ * the fold.  The area is lane-interleaved — word j of lane t at [j * BLOCK + t], so the 64 lanes of a wave read 64 consecutive words: no
+ * bank conflict — and a lane touches its own column only: no barrier between its stores and its loads, and a padding lane, which
+ * neither draws nor walks the loops, neither writes nor reads.  kParkedPairs pairs per lane; a frame with more shadow rays per light
+ * triangle draws every pair where it is used, as DrawnSamples does (parked is uniform over the frame).  The pairs do not depend on the
+ * sample plane: with spp > 1 they are still drawn once per pixel. */
+constexpr uint32_t kParkedPairs = 4;
+typedef __attribute__((address_space(3))) uint32_t* lds_column;
+template <uint32_t BLOCK>
+struct ParkedSamples {
+    lds_column pairs;            /* this lane's column: r1 of sample s at pairs[2 s BLOCK], r2 at pairs[(2 s + 1) BLOCK] */
+    uint32_t seed0;
+    bool parked;
+    __device__ __forceinline__ void draw(uint32_t ns) const {
+        if (!parked) return;
+        for (uint32_t s = 0; s < ns; ++s) {
+            const SamplePair r = light_sample_pair(s + seed0);
+            pairs[2u * s * BLOCK] = __float_as_uint(r.r1); pairs[(2u * s + 1u) * BLOCK] = __float_as_uint(r.r2);
+        }
+    }
+    __device__ __forceinline__ SamplePair pair(uint32_t s) const {
+        if (parked) return SamplePair{__uint_as_float(pairs[2u * s * BLOCK]), __uint_as_float(pairs[(2u * s + 1u) * BLOCK])};
+        return light_sample_pair(s + seed0);
+    }
+};
+
 /* 1024-thread workgroups (16 waves): the queue is reserved once per workgroup, see below; planeStride = the sample-plane stride
  * of the hit records k_primary wrote (its grid x 256). */
 constexpr uint32_t kGenBlock = 1024;
 __global__ __launch_bounds__(kGenBlock) void k_shadow_gen(DeviceScene sc, FrameBatch fb, const float4* hitTuvp,
                                                           const uint32_t* hitCustom, RayQueue queue, uint32_t* count, uint32_t planeStride) {
     __shared__ uint32_t s_off[kGenBlock / 64], s_tot[kGenBlock / 64], s_base;
+    __shared__ uint32_t s_pairs[2u * kParkedPairs * kGenBlock];       /* 32 KB; the kernel's registers (5 waves per SIMD) hold one 16-wave workgroup per CU */
     uint32_t q;
     const uint32_t frame = batch_frame(blockIdx.x * kGenBlock + threadIdx.x, planeStride, q);
     const RenderArgs& ra = fb.ra[frame < fb.n ? frame : 0u];
@@ -462,15 +491,17 @@ __global__ __launch_bounds__(kGenBlock) void k_shadow_gen(DeviceScene sc, FrameB
     Surface sf0;
     bool surf0 = false;
     uint32_t n = 0;
+    const ParkedSamples<kGenBlock> smp{(lds_column)&s_pairs[threadIdx.x], light_sample_seed0(px, py, ra.info.frame), ra.numShadowRays <= kParkedPairs};
     if (live) {
         CountPolicy cp{0};
+        smp.draw(ra.numShadowRays);
         for (uint32_t i = 0; i < ra.spp; ++i) {
             const size_t k = (plane0 + i) * planeStride + q;
             const float4 r = hitTuvp[k];
             HitRec h; h.t = r.x; h.u = r.y; h.v = r.z; h.prim = __float_as_uint(r.w); h.custom = hitCustom[k];
             Surface sf;
             const bool surf = fetch_surface<false, false>(sc, ra, h, primary_dir(ra, px, py, i), false, acc, sf, st);
-            if (surf) light_loops<CountPolicy, false>(sc, ra, px, py, sf, 0u, acc, cp, st);
+            if (surf) light_loops_from<CountPolicy, false>(sc, ra, smp, sf, 0u, acc, cp, st);
             if (i == 0) { sf0 = sf; surf0 = surf; }
         }
         n = cp.n;
@@ -495,14 +526,14 @@ __global__ __launch_bounds__(kGenBlock) void k_shadow_gen(DeviceScene sc, FrameB
         const size_t k = (plane0 + i) * planeStride + q;
         EmitPolicy pol{queue, (EmitPolicy::lds_word)&s_off[wave], base, (uint32_t)k};
         if (single) {
-            if (surf0) { queue_store_origin(queue, k, sf0.hitPoint, sf0.hitNormal); light_loops<EmitPolicy, false>(sc, ra, px, py, sf0, 0u, acc, pol, st); }
+            if (surf0) { queue_store_origin(queue, k, sf0.hitPoint, sf0.hitNormal); light_loops_from<EmitPolicy, false>(sc, ra, smp, sf0, 0u, acc, pol, st); }
         } else {
             const float4 r = hitTuvp[k];
             HitRec h; h.t = r.x; h.u = r.y; h.v = r.z; h.prim = __float_as_uint(r.w); h.custom = hitCustom[k];
             Surface sf;
             if (fetch_surface<false, false>(sc, ra, h, primary_dir(ra, px, py, i), false, acc, sf, st)) {
                 queue_store_origin(queue, k, sf.hitPoint, sf.hitNormal);
-                light_loops<EmitPolicy, false>(sc, ra, px, py, sf, 0u, acc, pol, st);
+                light_loops_from<EmitPolicy, false>(sc, ra, smp, sf, 0u, acc, pol, st);
             }
         }
     }
@@ -515,13 +546,18 @@ constexpr uint32_t kBinnedMinNodes = 1u << 16;       /* ... and this tree size: 
 #define RTR_GEN_OCT_BLOCK 512
 #endif
 constexpr uint32_t kGenOctBlock = RTR_GEN_OCT_BLOCK;     /* two workgroups per CU, so one's reservation round trips hide under the other's work */
+constexpr uint32_t kParkSurface = 6, kParkWords = kParkSurface + 2u * kParkedPairs;      /* a lane's column of k_shadow_gen_oct's LDS area: hit point, hit normal, its sample pairs */
 /* k_shadow_gen with the queue binned by direction octant (CountOctPolicy / EmitOctPolicy above).  ctrl = Workspace::queueCount:
  * [0] queued rays, [16 + 16 r] / [kQueueListLens + r] cursor / length of batch list r = octant * 8 + xcd; lists: listStride uint2 {first, count} per list. */
 /* Seven waves per SIMD: the kernel is neither issue- nor HBM-bound (its records leave in whole lines: WRITE_SIZE = 1.01 x the algorithmic
  * bytes) but waits — on the hit -> object -> index -> vertex chain of its surface fetch, on its reservation atomics and three barriers — so it
  * wants waves more than registers: at the 88 VGPRs it would take by itself (5 waves per SIMD) 0.171 ms per 1080p frame, capped at 64 (8 waves,
  * 13 dwords spilled) 0.148 (profiles/r04/ab_tri2_gen_waves.log).  Round 5: with the into-the-surface mark of every ray (a dot product and
- * a bit per sample) the cap of 64 spilled 31 dwords and cost 0.010 ms; at 72 (7 waves) the kernel is back at 0.151 (profiles/r05/ab_gen_into.log). */
+ * a bit per sample) the cap of 64 spilled 31 dwords and cost 0.010 ms; at 72 (7 waves) the kernel is back at 0.151 (profiles/r05/ab_gen_into.log).
+ * With the sample pairs and the surface parked in LDS (ParkedSamples, s_park) the kernel takes 68 VGPRs under the cap of 72 and spills nothing
+ * (before: 18 dwords, 68 bytes of scratch per lane): 0.158 -> 0.142 ms per frame in ten-frame launches.  Capped at 64 it still spills one dword,
+ * in the emit pass of spp > 1, and measured 0.133 in the same session (profiles/gen_samples_once/ab.log): the next step once that dword is gone;
+ * a kernel with a private segment is not what this one is meant to be, so 7 stays. */
 #ifndef RTR_GEN_OCT_WAVES
 #define RTR_GEN_OCT_WAVES 7
 #endif
@@ -535,6 +571,7 @@ __global__ __launch_bounds__(kGenOctBlock) RTR_GEN_OCT_ATTR void k_shadow_gen_oc
                                                               uint32_t listStride, uint32_t kBatch, uint32_t nt) {
     constexpr uint32_t kWaves = kGenOctBlock / 64;
     __shared__ uint32_t s_tot[kWaves][8], s_run[kWaves][8];
+    __shared__ uint32_t s_park[kParkWords * kGenOctBlock];      /* 28 KB at 512 threads: the three workgroups per CU of seven waves per SIMD take 84 of the CU's 160 KB, the four of eight waves 112 — LDS does not set the residency */
     uint32_t q;
     const uint32_t frame = batch_frame(blockIdx.x * kGenOctBlock + threadIdx.x, planeStride, q);
     const RenderArgs& ra = fb.ra[frame < fb.n ? frame : 0u];
@@ -545,10 +582,14 @@ __global__ __launch_bounds__(kGenOctBlock) RTR_GEN_OCT_ATTR void k_shadow_gen_oc
     LocalStats st;
     Accum acc = zero_accum();
     const bool single = ra.spp == 1u;                 /* (fetching the surface again in the emit phase instead of keeping it across the reservation: 74 VGPRs instead of 88, and slower — profiles/r04/ab_gen_refetch.log) */
-    Surface sf0;
-    bool surf0 = false;
+    /* What the emit pass needs of the one sample's surface (spp == 1) crosses the reservation in LDS, in the lane's column of s_park
+     * beside its sample pairs (ParkedSamples): hit point and normal, words 0-5; the pairs from word kParkSurface.  Kept in registers it
+     * was spilled to scratch under this kernel's register cap — a vector-memory round trip on the chain the kernel already waits on. */
+    const lds_column park = (lds_column)&s_park[threadIdx.x];
+    const ParkedSamples<kGenOctBlock> smp{park + kParkSurface * kGenOctBlock, light_sample_seed0(px, py, ra.info.frame), ra.numShadowRays <= kParkedPairs};
     CountOctPolicy cp{0ull, 0ull};
     if (live) {
+        smp.draw(ra.numShadowRays);
         for (uint32_t i = 0; i < ra.spp; ++i) {
             const size_t k = (plane0 + i) * planeStride + q;
             const float4 r = hitTuvp[k];
@@ -563,8 +604,13 @@ __global__ __launch_bounds__(kGenOctBlock) RTR_GEN_OCT_ATTR void k_shadow_gen_oc
                 if (fetch_surface<false, false>(sc, ra, h2, primary_dir(ra, px, py, i), false, acc, sf2, st)) sf = sf2;
             }
 #endif
-            if (surf) light_loops<CountOctPolicy, false>(sc, ra, px, py, sf, 0u, acc, cp, st);
-            if (i == 0) { sf0 = sf; surf0 = surf; }
+            if (surf) {
+                if (single) {
+                    park[0u * kGenOctBlock] = __float_as_uint(sf.hitPoint.x); park[1u * kGenOctBlock] = __float_as_uint(sf.hitPoint.y); park[2u * kGenOctBlock] = __float_as_uint(sf.hitPoint.z);
+                    park[3u * kGenOctBlock] = __float_as_uint(sf.hitNormal.x); park[4u * kGenOctBlock] = __float_as_uint(sf.hitNormal.y); park[5u * kGenOctBlock] = __float_as_uint(sf.hitNormal.z);
+                }
+                light_loops_from<CountOctPolicy, false>(sc, ra, smp, sf, 0u, acc, cp, st);
+            }
         }
     }
     uint32_t mine = 0;
@@ -584,14 +630,24 @@ __global__ __launch_bounds__(kGenOctBlock) RTR_GEN_OCT_ATTR void k_shadow_gen_oc
          * itself (64 broadcast LDS reads) instead of waiting for one lane to do it. */
         const uint32_t o = threadIdx.x / kQueueRegions, x = threadIdx.x % kQueueRegions;
         uint32_t before = 0, len = 0, total = 0;                 /* rays of the octants before o, of o, of all */
+        /* the counts of four waves at a time: all 8 x kWaves words fetched at once are 64 registers, which this kernel's cap does not
+         * have beside what the lanes of this wave carry over the reservation — they went to scratch */
+        uint32_t tot[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+#pragma unroll
+        for (uint32_t w0 = 0; w0 < kWaves; w0 += 4u) {
+#pragma unroll
+            for (uint32_t w = w0; w < w0 + 4u && w < kWaves; ++w) {
+#pragma unroll
+                for (uint32_t oo = 0; oo < 8; ++oo) tot[oo] += s_tot[w][oo];
+            }
+            /* the sums so far are made here, and no read of the next four waves' counts starts before */
+            asm volatile("" : "+v"(tot[0]), "+v"(tot[1]), "+v"(tot[2]), "+v"(tot[3]), "+v"(tot[4]), "+v"(tot[5]), "+v"(tot[6]), "+v"(tot[7]) : : "memory");
+        }
 #pragma unroll
         for (uint32_t oo = 0; oo < 8; ++oo) {
-            uint32_t t = 0;
-#pragma unroll
-            for (uint32_t w = 0; w < kWaves; ++w) t += s_tot[w][oo];
-            before += oo < o ? t : 0u;
-            len = oo == o ? t : len;
-            total += t;
+            before += oo < o ? tot[oo] : 0u;
+            len = oo == o ? tot[oo] : len;
+            total += tot[oo];
         }
         /* the run's batches are dealt round-robin to the eight lists of this octant (one per consumer XCD); every lane makes its
          * own reservation */
@@ -617,19 +673,23 @@ __global__ __launch_bounds__(kGenOctBlock) RTR_GEN_OCT_ATTR void k_shadow_gen_oc
         }
     }
     __syncthreads();
-    if (!live || mine == 0) return;
+    if (mine == 0) return;                 /* padding lanes, misses, light hits: a lane that counted a query is live, and with spp == 1 its one sample has a surface, parked above */
     for (uint32_t i = 0; i < ra.spp; ++i) {
         const size_t k = (plane0 + i) * planeStride + q;
         EmitOctPolicy pol{queue, (EmitOctPolicy::lds_word)&s_run[wave][0], (uint32_t)k, nt};
         if (single) {
-            if (surf0) { queue_store_origin(queue, k, sf0.hitPoint, sf0.hitNormal); light_loops<EmitOctPolicy, false>(sc, ra, px, py, sf0, 0u, acc, pol, st); }
+            Surface sf0 = {};              /* of it the emission reads hit point and normal only */
+            sf0.hitPoint = rtr_mk(__uint_as_float(park[0u * kGenOctBlock]), __uint_as_float(park[1u * kGenOctBlock]), __uint_as_float(park[2u * kGenOctBlock]));
+            sf0.hitNormal = rtr_mk(__uint_as_float(park[3u * kGenOctBlock]), __uint_as_float(park[4u * kGenOctBlock]), __uint_as_float(park[5u * kGenOctBlock]));
+            queue_store_origin(queue, k, sf0.hitPoint, sf0.hitNormal);
+            light_loops_from<EmitOctPolicy, false>(sc, ra, smp, sf0, 0u, acc, pol, st);
         } else {
             const float4 r = hitTuvp[k];
             HitRec h; h.t = r.x; h.u = r.y; h.v = r.z; h.prim = __float_as_uint(r.w); h.custom = hitCustom[k];
             Surface sf;
             if (fetch_surface<false, false>(sc, ra, h, primary_dir(ra, px, py, i), false, acc, sf, st)) {
                 queue_store_origin(queue, k, sf.hitPoint, sf.hitNormal);
-                light_loops<EmitOctPolicy, false>(sc, ra, px, py, sf, 0u, acc, pol, st);
+                light_loops_from<EmitOctPolicy, false>(sc, ra, smp, sf, 0u, acc, pol, st);
             }
         }
     }

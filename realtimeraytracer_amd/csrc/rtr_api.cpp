@@ -46,6 +46,12 @@ int fail(int code, const char* fmt, ...) {
     return code;
 }
 
+/* the status of a call whose kernel launcher returned e */
+int launched(hipError_t e, const char* who) {
+    if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: kernel launch: %s", who, hipGetErrorString(e));
+    return RTR_OK;
+}
+
 #define HIP_TRY(expr)                                                                              \
     do {                                                                                           \
         hipError_t e_ = (expr);                                                                    \
@@ -976,7 +982,7 @@ int rtr_scene_set_instance_masks(rtr_scene* s, const uint8_t* masks, uint32_t nu
     const uint32_t numTris = (uint32_t)(s->tree.tris.n / 3);
     HIP_TRY(s->maskBits.upload(bits.data(), bits.size(), st));
     const hipError_t e = rtrdev::launch_set_instance_masks(s->tree.tris.p, numTris, s->maskBits.p, numInstances, st);
-    if (e != hipSuccess) return fail(RTR_ERR_HIP, "rtr_scene_set_instance_masks: kernel launch: %s", hipGetErrorString(e));
+    if (const int rc = launched(e, "rtr_scene_set_instance_masks")) return rc;
     HIP_TRY(hipStreamSynchronize(st));
     /* the host mirror (rtr_scene_export_bvh, rtr_scene_create_like) in step: the same rule as the kernel's */
     for (RtrBvhTri& t : s->tree.hostTris)
@@ -1607,7 +1613,7 @@ int rtr_scene_tree_cost(const rtr_scene* s, rtr_tree_cost* out) {
     const size_t words = rtrdev::bvh_tree_cost_words();
     HIP_TRY(s->costWords.ensure(words));
     const hipError_t e = rtrdev::bvh_tree_cost(t.nodes.p, numNodes, parent, s->costWords.p, st);
-    if (e != hipSuccess) return fail(RTR_ERR_HIP, "rtr_scene_tree_cost: kernel launch: %s", hipGetErrorString(e));
+    if (const int rc = launched(e, "rtr_scene_tree_cost")) return rc;
     uint64_t w[11];
     static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "layout");
     if (words != 11) return fail(RTR_ERR_HIP, "rtr_scene_tree_cost: the kernel has %zu words, the host expects 11", words);
@@ -2297,6 +2303,9 @@ int rtr_deinterleave_images(rtr_ctx* ctx, const void* gathered, uint32_t numImag
 /* ---- ray queries ---------------------------------------------------------------------------- */
 static bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 static bool aligned4(const void* p) { return ((uintptr_t)p & 3u) == 0; }
+/* the pointer tables and the params' rules of rtr_arg_check.h, which the rtr_*_host.cpp share */
+using rtrdev::Arg;
+using rtrdev::check_ptrs;
 
 /* the handles every call of this section takes, and the device they must share */
 static int check_handles(const rtr_ctx* c, const rtr_scene* s, const char* who) {
@@ -2349,7 +2358,7 @@ static int scratch_open(rtr_ctx* c, bool count) {
 
 /* launch: what the query's launcher returned */
 static int scratch_close(rtr_ctx* c, hipError_t launch, const char* who) {
-    if (launch != hipSuccess) return fail(RTR_ERR_HIP, "%s: kernel launch: %s", who, hipGetErrorString(launch));
+    if (const int rc = launched(launch, who)) return rc;
     hipStream_t st = c->stream;
     HIP_TRY(hipEventRecord(c->qEv[1], st));
     c->qLastStream = st;
@@ -2489,10 +2498,8 @@ static int enqueue_multihit(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, 
     if (maxHits == 0u || maxHits > RTR_MULTIHIT_MAX) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: maxHits %u, 1 to %u", who, maxHits, RTR_MULTIHIT_MAX);
     if (const int rc = check_same_device(c, s, who)) return rc;
     if (n == 0) return RTR_OK;
-    if (!rays || !hits) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: %s is null", who, !rays ? "rays" : "hits");
-    if (!aligned16(rays) || !aligned16(hits) || !aligned16(after))
-        return fail(RTR_ERR_INVALID_ARGUMENT, "%s: %s is not 16-B aligned", who, !aligned16(rays) ? "rays" : (!aligned16(hits) ? "hits" : "after"));
-    if (!aligned4(counts)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: counts is not 4-B aligned", who);
+    const Arg args[4] = {{rays, "rays", 16, true}, {hits, "hits", 16, true}, {after, "after", 16, false}, {counts, "counts", 4, false}};
+    if (const int rc = check_ptrs(who, args)) return rc;
     if (const int rc = scratch_open(c, count)) return rc;
     hipStream_t st = c->stream;
     HIP_TRY(hipMemsetAsync(c->qCtrl.p, 0, rtrdev::kQueryCtrlWords * sizeof(uint32_t), st));
@@ -2529,9 +2536,8 @@ static int enqueue_occlusion(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays,
     if (const int rc = check_query(c, s, cm, flags, who)) return rc;
     if (const int rc = check_same_device(c, s, who)) return rc;
     if (n == 0) return RTR_OK;
-    if (!rays || !occluded || !scratch) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: %s is null", who, !rays ? "rays" : (!occluded ? "occluded" : "scratch"));
-    if (!aligned16(rays) || !aligned16(occluded) || !aligned16(scratch))
-        return fail(RTR_ERR_INVALID_ARGUMENT, "%s: %s is not 16-B aligned", who, !aligned16(rays) ? "rays" : (!aligned16(occluded) ? "occluded" : "scratch"));
+    const Arg args[3] = {{rays, "rays", 16, true}, {occluded, "occluded", 16, true}, {scratch, "scratch", 16, true}};
+    if (const int rc = check_ptrs(who, args)) return rc;
     const OcclusionLayout l = occlusion_layout(n);
     if (scratchBytes < l.bytes) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: %zu bytes of scratch, %u rays need %zu (rtr_occlusion_scratch_bytes)", who, scratchBytes, n, l.bytes);
     if (const int rc = scratch_open(c, count)) return rc;      /* the deep stacks and the counters are the context's */
@@ -2585,16 +2591,13 @@ static int enqueue_surfaces(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, 
     if (const int rc = check_handles(c, s, who)) return rc;
     if (const int rc = check_same_device(c, s, who)) return rc;
     if (n == 0) return RTR_OK;
-    if (!rays || !hits || !out) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: %s is null", who, !rays ? "rays" : (!hits ? "hits" : "out"));
-    if (!aligned16(rays) || !aligned16(hits) || !aligned16(out))
-        return fail(RTR_ERR_INVALID_ARGUMENT, "%s: %s is not 16-B aligned", who, !aligned16(rays) ? "rays" : (!aligned16(hits) ? "hits" : "out"));
+    const Arg args[3] = {{rays, "rays", 16, true}, {hits, "hits", 16, true}, {out, "out", 16, true}};
+    if (const int rc = check_ptrs(who, args)) return rc;
     HIP_TRY(hipSetDevice(c->device));
     rtrdev::SurfaceArgs sa{};
     sa.rays = reinterpret_cast<const float4*>(rays); sa.hits = reinterpret_cast<const float4*>(hits); sa.out = reinterpret_cast<float4*>(out);
     sa.triCount = s->triCount.p; sa.numInstances = s->numInstances; sa.n = n;
-    const hipError_t e = rtrdev::launch_hit_surfaces(s->dev, sa, c->stream);
-    if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: kernel launch: %s", who, hipGetErrorString(e));
-    return RTR_OK;
+    return launched(rtrdev::launch_hit_surfaces(s->dev, sa, c->stream), who);
 }
 
 int rtr_hit_surfaces_async(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, uint32_t n, RtrSurface* out) {
@@ -2631,11 +2634,8 @@ static int ensure_leaf_table(rtr_ctx* c, const rtr_scene* s, const char* who) {
 
 /* the checks and the launch of rtr_hit_leaves[_async].  The pointers are checked first: that needs nothing of the handles */
 static int enqueue_hit_leaves(rtr_ctx* c, const rtr_scene* s, const RtrHit* hits, uint32_t n, int32_t* leaves, const char* who) {
-    if (n) {
-        if (!hits || !leaves) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: %s is null", who, !hits ? "hits" : "leaves");
-        if (!aligned16(hits)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: hits is not 16-B aligned", who);
-        if (!aligned4(leaves)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: leaves is not 4-B aligned", who);
-    }
+    const Arg args[2] = {{hits, "hits", 16, true}, {leaves, "leaves", 4, true}};
+    if (const int rc = n ? check_ptrs(who, args) : RTR_OK) return rc;
     if (const int hrc = check_handles(c, s, who)) return hrc;
     if (const int drc = check_same_device(c, s, who)) return drc;
     if (n == 0) return RTR_OK;
@@ -2645,9 +2645,7 @@ static int enqueue_hit_leaves(rtr_ctx* c, const rtr_scene* s, const RtrHit* hits
     rtrdev::LeafArgs a{};
     a.hits = reinterpret_cast<const float4*>(hits); a.leaves = leaves; a.triCount = s->triCount.p; a.base = s->leafBase.p; a.table = s->tree.leafTable.p;
     a.numInstances = s->numInstances; a.n = n;
-    const hipError_t e = rtrdev::launch_hit_leaves(a, c->stream);
-    if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: kernel launch: %s", who, hipGetErrorString(e));
-    return RTR_OK;
+    return launched(rtrdev::launch_hit_leaves(a, c->stream), who);
 }
 
 int rtr_hit_leaves_async(rtr_ctx* c, const rtr_scene* s, const RtrHit* hits, uint32_t n, int32_t* leaves) {
@@ -2664,9 +2662,7 @@ int rtr_camera_rays_async(rtr_ctx* c, const RtrCameraData* cam, uint32_t width, 
     if (width == 0 || height == 0 || spp == 0) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_camera_rays_async: extent %ux%u x %u spp", width, height, spp);
     if ((uint64_t)width * height * spp > 0xffffffffull) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_camera_rays_async: %ux%u x %u spp is more than 2^32 - 1 rays", width, height, spp);
     HIP_TRY(hipSetDevice(c->device));
-    const hipError_t e = rtrdev::launch_camera_rays(*cam, width, height, spp, reinterpret_cast<float4*>(out), c->stream);
-    if (e != hipSuccess) return fail(RTR_ERR_HIP, "rtr_camera_rays_async: kernel launch: %s", hipGetErrorString(e));
-    return RTR_OK;
+    return launched(rtrdev::launch_camera_rays(*cam, width, height, spp, reinterpret_cast<float4*>(out), c->stream), "rtr_camera_rays_async");
 }
 
 /* ---- direct lighting for ray-query hits -------------------------------------------------------------------------------------- */
@@ -2675,8 +2671,8 @@ int rtr_camera_rays_async(rtr_ctx* c, const RtrCameraData* cam, uint32_t width, 
 static int light_slots(const rtr_scene* s, const rtr_light_params* p, uint32_t* q, const char* who) {
     if (!s || !p) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: null scene or params", who);
     if (p->numAreaLights > s->numLights) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: numAreaLights %u > scene lights %u", who, p->numAreaLights, s->numLights);
-    if (p->numShadowRays == 0 || p->numShadowRays > 1024) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: numShadowRays %u (1 ... 1024)", who, p->numShadowRays);
-    if (p->outputs & ~(RTR_LIGHT_SHADOWED | RTR_LIGHT_UNSHADOWED | RTR_LIGHT_ANALYTIC)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: unknown output bits 0x%x", who, p->outputs);
+    if (const int rc = rtrdev::check_shadow_rays(who, p->numShadowRays)) return rc;
+    if (const int rc = rtrdev::check_light_outputs(who, p->outputs)) return rc;
     uint64_t slots = 1;
     for (uint32_t l = 0; l < p->numAreaLights; ++l) slots += (uint64_t)s->hostLights[l].numTriangles * p->numShadowRays;
     if (slots > 0xffffffffull) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: %llu slots per hit do not fit 32 bits", who, (unsigned long long)slots);
@@ -2689,45 +2685,43 @@ int rtr_light_slots(const rtr_scene* s, const rtr_light_params* p, uint32_t* slo
     return light_slots(s, p, slotsPerHit, "rtr_light_slots");
 }
 
+/* what every lighting launch takes of the call alike; slots, the output arrays, the hint fields and the test hook are the caller's */
+static void fill_light_args(rtrdev::LightArgs& la, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, uint32_t n, const rtr_light_params* p,
+                            const uint32_t* seeds) {
+    la.rays = reinterpret_cast<const float4*>(rays); la.hits = reinterpret_cast<const float4*>(hits); la.seeds = seeds;
+    la.triCount = s->triCount.p; la.numInstances = s->numInstances; la.n = n;
+    la.numAreaLights = p->numAreaLights; la.numShadowRays = p->numShadowRays; la.frame = p->frame; la.width = p->width; la.spp = p->spp;
+    la.outputs = p->outputs;
+}
+
 /* the checks and the launch of rtr_light_rays[_async] (shade == false) and rtr_shade_hits[_async], enqueued on the context's stream */
 static int enqueue_light(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, uint32_t n, const rtr_light_params* p,
                          const uint32_t* seeds, RtrRay* outRays, const uint8_t* occluded, RtrRadiance* out, bool shade, const char* who,
                          int32_t* outLeaves = nullptr, bool hinted = false) {
-    if (hinted && n) {       /* rtr_light_rays_hinted: its own array is checked first, which needs nothing of the handles */
-        if (!outLeaves) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: outLeaves is null", who);
-        if (!aligned4(outLeaves)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: outLeaves is not 4-B aligned", who);
-    }
+    const Arg own[1] = {{outLeaves, "outLeaves", 4, true}};       /* rtr_light_rays_hinted: its own array is checked first, which needs nothing of the handles */
+    if (const int rc = hinted && n ? check_ptrs(who, own) : RTR_OK) return rc;
     if (!c || !s || !p) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: null context, scene or params", who);
-    if (const int drc = check_same_device(c, s, who)) return drc;
+    if (const int rc = check_same_device(c, s, who)) return rc;
     uint32_t slots = 0;
-    const int rc = light_slots(s, p, &slots, who);
-    if (rc != RTR_OK) return rc;
+    if (const int rc = light_slots(s, p, &slots, who)) return rc;
     if (shade && (p->outputs & RTR_LIGHT_ANALYTIC) && !s->hasLtc) return fail(RTR_ERR_UNSUPPORTED, "%s: RTR_LIGHT_ANALYTIC needs the LTC tables (rtr_scene_desc.ltc1/ltc2)", who);
     if (n == 0) return RTR_OK;
-    if ((uint64_t)n * slots > 0xffffffffull) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: %u hits x %u slots do not fit 32 bits", who, n, slots);
-    const void* res = shade ? (const void*)out : (const void*)outRays;
-    const char* resName = shade ? "out" : "outRays";
-    if (!rays || !hits || !res) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: %s is null", who, !rays ? "rays" : (!hits ? "hits" : resName));
-    if (shade && !occluded) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: occluded is null", who);
-    if (!aligned16(rays) || !aligned16(hits) || !aligned16(res))
-        return fail(RTR_ERR_INVALID_ARGUMENT, "%s: %s is not 16-B aligned", who, !aligned16(rays) ? "rays" : (!aligned16(hits) ? "hits" : resName));
-    if (seeds && !aligned4(seeds)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: seeds is not 4-B aligned", who);
-    if (!seeds && (p->width == 0 || p->spp == 0)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: width %u, spp %u: without seeds the hits are pixel-samples of a frame", who, p->width, p->spp);
+    if (const int rc = rtrdev::check_fits_32(who, n, "hits", slots, "slots")) return rc;
+    const Arg args[5] = {{rays, "rays", 16, true}, {hits, "hits", 16, true}, shade ? Arg{out, "out", 16, true} : Arg{outRays, "outRays", 16, true},
+                         {occluded, "occluded", 1, shade}, {seeds, "seeds", 4, false}};
+    if (const int rc = check_ptrs(who, args)) return rc;
+    if (const int rc = rtrdev::check_pixel_seeds(who, seeds, p->width, p->spp)) return rc;
     HIP_TRY(hipSetDevice(c->device));
-    if (hinted) { const int rct = ensure_leaf_table(c, s, who); if (rct != RTR_OK) return rct; }
+    if (const int rc = hinted ? ensure_leaf_table(c, s, who) : RTR_OK) return rc;
     rtrdev::LightArgs la{};
     if (hinted) { la.outLeaves = outLeaves; la.leafTable = s->tree.leafTable.p; la.leafBase = s->leafBase.p; }
-    la.rays = reinterpret_cast<const float4*>(rays); la.hits = reinterpret_cast<const float4*>(hits); la.seeds = seeds;
-    la.triCount = s->triCount.p; la.numInstances = s->numInstances; la.n = n; la.slots = slots;
-    la.numAreaLights = p->numAreaLights; la.numShadowRays = p->numShadowRays; la.frame = p->frame; la.width = p->width; la.spp = p->spp;
-    la.outputs = p->outputs;
+    fill_light_args(la, s, rays, hits, n, p, seeds);
+    la.slots = slots;
     la.outRays = reinterpret_cast<float4*>(outRays); la.occluded = occluded; la.out = reinterpret_cast<float4*>(out);
 #ifdef RTR_TEST_HOOKS
     if (const char* e = getenv("RTR_LIGHT_RAYS_DIRECT")) la.direct = atoi(e) != 0 ? 1u : 0u;   /* the kernel's unstaged form for a light table that would be staged */
 #endif
-    const hipError_t e = shade ? rtrdev::launch_shade_hits(s->dev, la, c->stream) : rtrdev::launch_light_rays(s->dev, la, c->stream);
-    if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: kernel launch: %s", who, hipGetErrorString(e));
-    return RTR_OK;
+    return launched(shade ? rtrdev::launch_shade_hits(s->dev, la, c->stream) : rtrdev::launch_light_rays(s->dev, la, c->stream), who);
 }
 
 int rtr_light_rays_async(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, uint32_t n, const rtr_light_params* p,
@@ -2764,12 +2758,10 @@ int rtr_tonemap_pack_async(rtr_ctx* c, const float* radiance, uint32_t strideByt
     if (!c) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_tonemap_pack: null context");
     if (strideBytes < 12 || (strideBytes & 3u)) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_tonemap_pack: strideBytes %u (a multiple of 4, at least 12)", strideBytes);
     if (n == 0) return RTR_OK;
-    if (!radiance || !out) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_tonemap_pack: %s is null", !radiance ? "radiance" : "outBGRA8");
-    if (!aligned4(radiance) || !aligned4(out)) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_tonemap_pack: %s is not 4-B aligned", !aligned4(radiance) ? "radiance" : "outBGRA8");
+    const Arg args[2] = {{radiance, "radiance", 4, true}, {out, "outBGRA8", 4, true}};
+    if (const int rc = check_ptrs("rtr_tonemap_pack", args)) return rc;
     HIP_TRY(hipSetDevice(c->device));
-    const hipError_t e = rtrdev::launch_tonemap_pack(radiance, strideBytes / 4u, n, out, c->stream);
-    if (e != hipSuccess) return fail(RTR_ERR_HIP, "rtr_tonemap_pack: kernel launch: %s", hipGetErrorString(e));
-    return RTR_OK;
+    return launched(rtrdev::launch_tonemap_pack(radiance, strideBytes / 4u, n, out, c->stream), "rtr_tonemap_pack");
 }
 
 int rtr_tonemap_pack(rtr_ctx* c, const float* radiance, uint32_t strideBytes, uint32_t n, uint32_t* out) {
@@ -2779,17 +2771,15 @@ int rtr_tonemap_pack(rtr_ctx* c, const float* radiance, uint32_t strideBytes, ui
 /* ---- continuation rays for ray-query hits (kernels/rtr_bounce.hip; the host form is rtr_bounce_host.cpp) -------------------------- */
 static int enqueue_bounce(rtr_ctx* c, const RtrRay* rays, const RtrSurface* surfaces, uint32_t n, const rtr_bounce_params* p, const uint32_t* seeds,
                           RtrRay* outRays, RtrBounce* outBounce, const char* who) {
-    char msg[256];       /* the arrays and the params are checked first, which needs nothing of the handle */
-    if (n && !rtrdev::bounce_check_args(who, rays, surfaces, n, p, seeds, outRays, outBounce, msg, sizeof msg)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s", msg);
+    /* the arrays and the params are checked first, which needs nothing of the handle */
+    if (const int rc = n ? rtrdev::bounce_check_args(who, rays, surfaces, n, p, seeds, outRays, outBounce) : RTR_OK) return rc;
     if (!c) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: ctx is null", who);
     if (n == 0) return RTR_OK;
     HIP_TRY(hipSetDevice(c->device));
     rtrdev::BounceArgs a{};
     a.rays = reinterpret_cast<const float4*>(rays); a.surfaces = reinterpret_cast<const float4*>(surfaces); a.seeds = seeds;
     a.outRays = reinterpret_cast<float4*>(outRays); a.outBounce = reinterpret_cast<float4*>(outBounce); a.params = *p; a.n = n;
-    const hipError_t e = rtrdev::launch_bounce_rays(a, c->stream);
-    if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: kernel launch: %s", who, hipGetErrorString(e));
-    return RTR_OK;
+    return launched(rtrdev::launch_bounce_rays(a, c->stream), who);
 }
 
 int rtr_bounce_rays_async(rtr_ctx* c, const RtrRay* rays, const RtrSurface* surfaces, uint32_t n, const rtr_bounce_params* p, const uint32_t* seeds,
@@ -2806,10 +2796,10 @@ int rtr_bounce_rays(rtr_ctx* c, const RtrRay* rays, const RtrSurface* surfaces, 
 static int enqueue_compact(rtr_ctx* c, const RtrRay* rays, const float* throughput, const uint32_t* seeds, const uint32_t* pathIds, uint32_t n,
                            const rtr_compact_params* p, void* scratch, size_t scratchBytes, RtrRay* outRays, float* outThroughput,
                            uint32_t* outSeeds, uint32_t* outPathIds, uint32_t* outCount, const char* who) {
-    char msg[256];       /* the arrays and the params are checked first, which needs nothing of the handle */
+    /* the arrays and the params are checked first, which needs nothing of the handle */
     const rtrdev::CompactCall call{rays, throughput, seeds, pathIds, n, p, scratch, scratchBytes, rtrdev::compact_scratch_bytes(n), true,
                                    outRays, outThroughput, outSeeds, outPathIds, outCount};
-    if (n && !rtrdev::compact_check_args(who, call, msg, sizeof msg)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s", msg);
+    if (const int rc = n ? rtrdev::compact_check_args(who, call) : RTR_OK) return rc;
     if (!c) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: ctx is null", who);
     if (n == 0 && !outCount) return RTR_OK;
     if (n == 0 && !aligned4(outCount)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: outCount is not 4-B aligned", who);
@@ -2825,9 +2815,7 @@ static int enqueue_compact(rtr_ctx* c, const RtrRay* rays, const float* throughp
     a.groupTotals = reinterpret_cast<uint32_t*>(static_cast<char*>(scratch) + groups * 32u);
     a.outRays = reinterpret_cast<float4*>(outRays); a.outThroughput = outThroughput; a.outSeeds = outSeeds; a.outPathIds = outPathIds;
     a.outCount = outCount; a.params = *p; a.n = n;
-    const hipError_t e = rtrdev::launch_compact_paths(a, c->stream);
-    if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: kernel launch: %s", who, hipGetErrorString(e));
-    return RTR_OK;
+    return launched(rtrdev::launch_compact_paths(a, c->stream), who);
 }
 
 int rtr_compact_paths_async(rtr_ctx* c, const RtrRay* rays, const float* throughput, const uint32_t* seeds, const uint32_t* pathIds, uint32_t n,
@@ -2857,36 +2845,43 @@ int rtr_compact_paths(rtr_ctx* c, const RtrRay* rays, const float* throughput, c
 }
 
 /* ---- picked light samples (kernels/rtr_query.hip; the rule is include/rtr_pick.h, the host form and the argument checks rtr_pick_host.cpp) -- */
+/* What the picked calls and rtr_mis_pick_weights do between their own argument checks and the launch: the handles, their device, the
+ * scene's lights against the params.  areaSlots: A of include/rtr_pick.h; tris: the light triangles behind it. */
+static int picked_scene_checks(const rtr_ctx* c, const rtr_scene* s, const rtr_light_params* p, const char* who, uint32_t* areaSlots, uint32_t* tris) {
+    if (const int rc = check_handles(c, s, who)) return rc;
+    if (const int rc = check_same_device(c, s, who)) return rc;
+    uint32_t q = 0;
+    if (const int rc = light_slots(s, p, &q, who)) return rc;
+    *areaSlots = q - 1u; *tris = *areaSlots / p->numShadowRays;
+    return rtrdev::pick_check_area(who, *areaSlots);
+}
+
+/* and what their launches take alike; the output arrays and the weights are the caller's */
+static void fill_pick_args(rtrdev::PickArgs& pa, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, uint32_t n, const rtr_light_params* p,
+                           const rtr_pick_params* pick, const uint32_t* seeds, const uint32_t* slots, uint32_t areaSlots, uint32_t tris) {
+    fill_light_args(pa.la, s, rays, hits, n, p, seeds);
+    pa.la.slots = pick->numPicks + 1u;
+    pa.picks = pick->numPicks; pa.depth = pick->depth; pa.areaSlots = areaSlots;
+    pa.defaultWeight = (float)tris / (float)pick->numPicks;
+    pa.slotsIn = slots;
+}
+
 static int enqueue_light_picked(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, uint32_t n, const rtr_light_params* p,
                                 const rtr_pick_params* pick, const uint32_t* seeds, const uint32_t* slots, RtrRay* outRays, uint32_t* outSlots,
                                 const float* weights, const uint8_t* occluded, RtrRadiance* out, bool shade, const char* who) {
-    char msg[256];       /* the params and the arrays are checked first, which needs nothing of the handles */
-    int prc = RTR_ERR_INVALID_ARGUMENT;
-    if (!rtrdev::pick_check_params(who, p, pick, shade, msg, sizeof msg, &prc)) return fail(prc, "%s", msg);
+    /* the params and the arrays are checked first, which needs nothing of the handles */
+    if (const int rc = rtrdev::pick_check_params(who, p, pick, shade)) return rc;
     const rtrdev::PickCall call{rays, hits, n, p, pick, seeds, shade, slots, outRays, outSlots, weights, occluded, out};
-    if (n && !rtrdev::pick_check_arrays(who, call, msg, sizeof msg)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s", msg);
-    if (!c || !s) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: null context or scene", who);
-    if (const int drc = check_same_device(c, s, who)) return drc;
-    uint32_t q = 0;
-    const int rc = light_slots(s, p, &q, who);
-    if (rc != RTR_OK) return rc;
-    const uint32_t areaSlots = q - 1u, tris = areaSlots / p->numShadowRays;
-    if (!rtrdev::pick_check_area(who, areaSlots, msg, sizeof msg)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s", msg);
+    if (const int rc = n ? rtrdev::pick_check_arrays(who, call) : RTR_OK) return rc;
+    uint32_t areaSlots = 0, tris = 0;
+    if (const int rc = picked_scene_checks(c, s, p, who, &areaSlots, &tris)) return rc;
     if (n == 0) return RTR_OK;
     HIP_TRY(hipSetDevice(c->device));
     rtrdev::PickArgs pa{};
-    rtrdev::LightArgs& la = pa.la;
-    la.rays = reinterpret_cast<const float4*>(rays); la.hits = reinterpret_cast<const float4*>(hits); la.seeds = seeds;
-    la.triCount = s->triCount.p; la.numInstances = s->numInstances; la.n = n; la.slots = pick->numPicks + 1u;
-    la.numAreaLights = p->numAreaLights; la.numShadowRays = p->numShadowRays; la.frame = p->frame; la.width = p->width; la.spp = p->spp;
-    la.outputs = p->outputs;
-    la.outRays = reinterpret_cast<float4*>(outRays); la.occluded = occluded; la.out = reinterpret_cast<float4*>(out);
-    pa.picks = pick->numPicks; pa.depth = pick->depth; pa.areaSlots = areaSlots;
-    pa.defaultWeight = (float)tris / (float)pick->numPicks;
-    pa.slotsIn = slots; pa.outSlots = outSlots; pa.weights = weights;
-    const hipError_t e = shade ? rtrdev::launch_shade_hits_picked(s->dev, pa, c->stream) : rtrdev::launch_light_rays_picked(s->dev, pa, c->stream);
-    if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: kernel launch: %s", who, hipGetErrorString(e));
-    return RTR_OK;
+    fill_pick_args(pa, s, rays, hits, n, p, pick, seeds, slots, areaSlots, tris);
+    pa.la.outRays = reinterpret_cast<float4*>(outRays); pa.la.occluded = occluded; pa.la.out = reinterpret_cast<float4*>(out);
+    pa.outSlots = outSlots; pa.weights = weights;
+    return launched(shade ? rtrdev::launch_shade_hits_picked(s->dev, pa, c->stream) : rtrdev::launch_light_rays_picked(s->dev, pa, c->stream), who);
 }
 
 int rtr_light_rays_picked_async(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, uint32_t n, const rtr_light_params* p,
@@ -2917,35 +2912,18 @@ int rtr_shade_hits_picked(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, co
 static int enqueue_mis_pick_weights(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, uint32_t n, const rtr_light_params* p,
                                     const rtr_pick_params* pick, const rtr_mis_params* mis, const uint32_t* seeds, const uint32_t* slots,
                                     float* outWeights, RtrMisSample* outSamples, const char* who) {
-    char msg[256];       /* the params and the arrays are checked first, which needs nothing of the handles */
-    int prc = RTR_ERR_INVALID_ARGUMENT;
-    if (!rtrdev::mis_check_params(who, mis, msg, sizeof msg)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s", msg);
-    if (!rtrdev::pick_check_params(who, p, pick, true, msg, sizeof msg, &prc)) return fail(prc, "%s", msg);
-    if (!rtrdev::mis_check_pick_call(who, p, pick, mis, rays, hits, n, seeds, slots, outWeights, outSamples, msg, sizeof msg))
-        return fail(RTR_ERR_INVALID_ARGUMENT, "%s", msg);
-    if (!c || !s) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: null context or scene", who);
-    if (const int drc = check_same_device(c, s, who)) return drc;
-    uint32_t q = 0;
-    const int rc = light_slots(s, p, &q, who);
-    if (rc != RTR_OK) return rc;
-    const uint32_t areaSlots = q - 1u, tris = areaSlots / p->numShadowRays;
-    if (!rtrdev::pick_check_area(who, areaSlots, msg, sizeof msg)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s", msg);
+    /* the params and the arrays are checked first, which needs nothing of the handles */
+    if (const int rc = rtrdev::mis_check_params(who, mis)) return rc;
+    if (const int rc = rtrdev::pick_check_params(who, p, pick, true)) return rc;
+    if (const int rc = rtrdev::mis_check_pick_call(who, p, pick, mis, rays, hits, n, seeds, slots, outWeights, outSamples)) return rc;
+    uint32_t areaSlots = 0, tris = 0;
+    if (const int rc = picked_scene_checks(c, s, p, who, &areaSlots, &tris)) return rc;
     if (n == 0) return RTR_OK;
     HIP_TRY(hipSetDevice(c->device));
     rtrdev::MisPickArgs ma{};
-    rtrdev::PickArgs& pa = ma.pa;
-    rtrdev::LightArgs& la = pa.la;
-    la.rays = reinterpret_cast<const float4*>(rays); la.hits = reinterpret_cast<const float4*>(hits); la.seeds = seeds;
-    la.triCount = s->triCount.p; la.numInstances = s->numInstances; la.n = n; la.slots = pick->numPicks + 1u;
-    la.numAreaLights = p->numAreaLights; la.numShadowRays = p->numShadowRays; la.frame = p->frame; la.width = p->width; la.spp = p->spp;
-    la.outputs = p->outputs;
-    pa.picks = pick->numPicks; pa.depth = pick->depth; pa.areaSlots = areaSlots;
-    pa.defaultWeight = (float)tris / (float)pick->numPicks;
-    pa.slotsIn = slots;
+    fill_pick_args(ma.pa, s, rays, hits, n, p, pick, seeds, slots, areaSlots, tris);
     ma.outWeights = outWeights; ma.outSamples = reinterpret_cast<float4*>(outSamples); ma.lobes = mis->lobes; ma.tris = tris;
-    const hipError_t e = rtrdev::launch_mis_pick_weights(s->dev, ma, c->stream);
-    if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: kernel launch: %s", who, hipGetErrorString(e));
-    return RTR_OK;
+    return launched(rtrdev::launch_mis_pick_weights(s->dev, ma, c->stream), who);
 }
 
 int rtr_mis_pick_weights_async(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, uint32_t n, const rtr_light_params* p,
@@ -2962,11 +2940,11 @@ int rtr_mis_pick_weights(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, con
 
 static int enqueue_emitter_hits(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, const RtrSurface* prevSurfaces,
                                 const RtrBounce* bounces, uint32_t n, const rtr_mis_params* mis, RtrEmitter* out, const char* who) {
-    char msg[256];       /* the params and the arrays are checked first, which needs nothing of the handles */
-    if (!rtrdev::mis_check_params(who, mis, msg, sizeof msg)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s", msg);
-    if (n && !rtrdev::mis_check_emitter_arrays(who, rays, hits, prevSurfaces, bounces, out, msg, sizeof msg)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s", msg);
-    if (!c || !s) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: null context or scene", who);
-    if (const int drc = check_same_device(c, s, who)) return drc;
+    /* the params and the arrays are checked first, which needs nothing of the handles */
+    if (const int rc = rtrdev::mis_check_params(who, mis)) return rc;
+    if (const int rc = n ? rtrdev::mis_check_emitter_arrays(who, rays, hits, prevSurfaces, bounces, out) : RTR_OK) return rc;
+    if (const int rc = check_handles(c, s, who)) return rc;
+    if (const int rc = check_same_device(c, s, who)) return rc;
     if (mis->numAreaLights > s->numLights) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: numAreaLights %u > scene lights %u", who, mis->numAreaLights, s->numLights);
     uint64_t tris = 0;
     for (uint32_t l = 0; l < mis->numAreaLights; ++l) tris += s->hostLights[l].numTriangles;
@@ -2979,9 +2957,7 @@ static int enqueue_emitter_hits(rtr_ctx* c, const rtr_scene* s, const RtrRay* ra
     a.out = reinterpret_cast<float4*>(out);
     a.lightTris = s->dev.lightTris; a.lightTriFirst = s->dev.lightTriFirst; a.lights = s->dev.lights; a.numLights = s->numLights;
     a.numAreaLights = mis->numAreaLights; a.tris = (uint32_t)tris; a.picks = mis->numPicks; a.n = n;
-    const hipError_t e = rtrdev::launch_emitter_hits(a, c->stream);
-    if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: kernel launch: %s", who, hipGetErrorString(e));
-    return RTR_OK;
+    return launched(rtrdev::launch_emitter_hits(a, c->stream), who);
 }
 
 int rtr_emitter_hits_async(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, const RtrSurface* prevSurfaces, const RtrBounce* bounces,

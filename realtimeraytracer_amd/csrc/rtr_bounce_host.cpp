@@ -6,64 +6,32 @@
 #include "../../include/rtr_bounce.h"
 
 #include <cstdint>
-#include <cstdio>
 
 namespace rtrdev {
 
-static bool overlaps(const void* a, size_t aBytes, const void* b, size_t bBytes) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a0 < b0 + bBytes && b0 < a0 + aBytes;
-}
-
-bool bounce_check_args(const char* who, const RtrRay* rays, const RtrSurface* surfaces, uint32_t n, const rtr_bounce_params* p,
-                       const uint32_t* seeds, const RtrRay* outRays, const RtrBounce* outBounce, char* msg, size_t msgBytes) {
-    if (!p) { snprintf(msg, msgBytes, "%s: params is null", who); return false; }
-    const struct { const void* ptr; const char* name; size_t stride; bool out; } arr[4] = {
-        {rays, "rays", sizeof(RtrRay), false}, {surfaces, "surfaces", sizeof(RtrSurface), false},
-        {outRays, "outRays", sizeof(RtrRay), true}, {outBounce, "outBounce", sizeof(RtrBounce), true}};
-    for (const auto& a : arr)
-        if (!a.ptr) { snprintf(msg, msgBytes, "%s: %s is null", who, a.name); return false; }
-    for (const auto& a : arr)
-        if ((uintptr_t)a.ptr & 15u) { snprintf(msg, msgBytes, "%s: %s is not 16-B aligned", who, a.name); return false; }
-    if (seeds && ((uintptr_t)seeds & 3u)) { snprintf(msg, msgBytes, "%s: seeds is not 4-B aligned", who); return false; }
-    if (p->lobes == 0u || (p->lobes & ~(RTR_BOUNCE_DIFFUSE | RTR_BOUNCE_SPECULAR))) {
-        snprintf(msg, msgBytes, "%s: lobes 0x%x (RTR_BOUNCE_DIFFUSE | RTR_BOUNCE_SPECULAR, at least one)", who, p->lobes);
-        return false;
-    }
-    if (!seeds && (p->width == 0u || p->spp == 0u)) {
-        snprintf(msg, msgBytes, "%s: width %u, spp %u: without seeds the hits are pixel-samples of a frame", who, p->width, p->spp);
-        return false;
-    }
-    if (!rtr_bounce_finite(p->normalOffset)) { snprintf(msg, msgBytes, "%s: normalOffset is not finite", who); return false; }
-    if (!rtr_bounce_finite(p->tmin)) { snprintf(msg, msgBytes, "%s: tmin is not finite", who); return false; }
-    if (!rtr_bounce_finite(p->tmax)) { snprintf(msg, msgBytes, "%s: tmax is not finite", who); return false; }
-    if (!(p->tmax > p->tmin)) { snprintf(msg, msgBytes, "%s: tmax %g is not above tmin %g", who, (double)p->tmax, (double)p->tmin); return false; }
-    for (int o = 2; o < 4; ++o) {
-        for (int i = 0; i < 2; ++i)
-            if (overlaps(arr[o].ptr, arr[o].stride * n, arr[i].ptr, arr[i].stride * n)) {
-                snprintf(msg, msgBytes, "%s: %s overlaps %s", who, arr[o].name, arr[i].name);
-                return false;
-            }
-        if (seeds && overlaps(arr[o].ptr, arr[o].stride * n, seeds, sizeof(uint32_t) * (size_t)n)) {
-            snprintf(msg, msgBytes, "%s: %s overlaps seeds", who, arr[o].name);
-            return false;
-        }
-    }
-    if (overlaps(outRays, sizeof(RtrRay) * (size_t)n, outBounce, sizeof(RtrBounce) * (size_t)n)) {
-        snprintf(msg, msgBytes, "%s: outRays overlaps outBounce", who);
-        return false;
-    }
-    return true;
+int bounce_check_args(const char* who, const RtrRay* rays, const RtrSurface* surfaces, uint32_t n, const rtr_bounce_params* p,
+                      const uint32_t* seeds, const RtrRay* outRays, const RtrBounce* outBounce) {
+    if (!p) return refusef("%s: params is null", who);
+    const Arg a[5] = {{rays, "rays", 16, true, sizeof(RtrRay) * (size_t)n}, {surfaces, "surfaces", 16, true, sizeof(RtrSurface) * (size_t)n},
+                      {outRays, "outRays", 16, true, sizeof(RtrRay) * (size_t)n}, {outBounce, "outBounce", 16, true, sizeof(RtrBounce) * (size_t)n},
+                      {seeds, "seeds", 4, false, sizeof(uint32_t) * (size_t)n}};
+    if (const int rc = check_ptrs(who, a)) return rc;
+    if (const int rc = check_lobes(who, p->lobes)) return rc;
+    if (const int rc = check_pixel_seeds(who, seeds, p->width, p->spp)) return rc;
+    if (!rtr_bounce_finite(p->normalOffset)) return refusef("%s: normalOffset is not finite", who);
+    if (!rtr_bounce_finite(p->tmin)) return refusef("%s: tmin is not finite", who);
+    if (!rtr_bounce_finite(p->tmax)) return refusef("%s: tmax is not finite", who);
+    if (!(p->tmax > p->tmin)) return refusef("%s: tmax %g is not above tmin %g", who, (double)p->tmax, (double)p->tmin);
+    const Arg in[3] = {a[0], a[1], a[4]};
+    return check_overlaps(who, in, 3, a + 2, 2);
 }
 
 }  // namespace rtrdev
 
 extern "C" int rtr_host_sincos_turn(const float* u, uint32_t n, float* outSin, float* outCos) {
     if (n == 0) return RTR_OK;
-    if (!u || !outSin || !outCos) {
-        rtrdev::set_last_error(!u ? "rtr_host_sincos_turn: u is null" : (!outSin ? "rtr_host_sincos_turn: outSin is null" : "rtr_host_sincos_turn: outCos is null"));
-        return RTR_ERR_INVALID_ARGUMENT;
-    }
+    const rtrdev::Arg a[3] = {{u, "u", 1, true}, {outSin, "outSin", 1, true}, {outCos, "outCos", 1, true}};
+    if (const int rc = rtrdev::check_ptrs("rtr_host_sincos_turn", a)) return rc;
     for (uint32_t k = 0; k < n; ++k) rtr_sincos_turn(u[k], &outSin[k], &outCos[k]);
     return RTR_OK;
 }
@@ -71,11 +39,7 @@ extern "C" int rtr_host_sincos_turn(const float* u, uint32_t n, float* outSin, f
 extern "C" int rtr_host_bounce_rays(const RtrRay* rays, const RtrSurface* surfaces, uint32_t n, const rtr_bounce_params* p, const uint32_t* seeds,
                                     RtrRay* outRays, RtrBounce* outBounce) {
     if (n == 0) return RTR_OK;
-    char msg[256];
-    if (!rtrdev::bounce_check_args("rtr_host_bounce_rays", rays, surfaces, n, p, seeds, outRays, outBounce, msg, sizeof msg)) {
-        rtrdev::set_last_error(msg);
-        return RTR_ERR_INVALID_ARGUMENT;
-    }
+    if (const int rc = rtrdev::bounce_check_args("rtr_host_bounce_rays", rays, surfaces, n, p, seeds, outRays, outBounce)) return rc;
     for (uint32_t k = 0; k < n; ++k) {
         const uint32_t base = seeds ? seeds[k] : rtr_bounce_pixel_seed(k, p->width, p->spp);
         rtr_bounce_sample(&rays[k], &surfaces[k], base, p, &outRays[k], &outBounce[k]);

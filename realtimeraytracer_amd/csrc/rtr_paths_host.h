@@ -1,7 +1,6 @@
 /* rtr_paths_host.h — what rtr_compact_paths' device and host entry points share (internal to librtr_hip.so). */
 #pragma once
-#include <stddef.h>
-#include "../../include/rtr.h"
+#include "rtr_arg_check.h"
 
 namespace rtrdev {
 
@@ -13,14 +12,11 @@ struct CompactCall {
     const RtrRay* outRays; const float* outThroughput; const uint32_t* outSeeds; const uint32_t* outPathIds; const uint32_t* outCount;
 };
 
-/* The argument checks of rtr_compact_paths[_async] and rtr_host_compact_paths, which need no device: true when the call may go on,
- * else the refusal's message (it names `who` and the argument) in msg.  Not called for numPaths == 0. */
-bool compact_check_args(const char* who, const CompactCall& c, char* msg, size_t msgBytes);
+/* The argument checks of rtr_compact_paths[_async] and rtr_host_compact_paths, which need no device (as rtr_arg_check.h returns them).
+ * Not called for numPaths == 0. */
+int compact_check_args(const char* who, const CompactCall& c);
 
 /* what rtr_compact_scratch_bytes returns: per 256-path workgroup four 64-bit ballots and one 32-bit total, each array rounded to 16 B */
 size_t compact_scratch_bytes(uint32_t numPaths);
-
-/* rtr_last_error's text for this thread; defined by rtr_api.cpp (a stand-alone program around rtr_paths_host.cpp brings its own) */
-void set_last_error(const char* msg);
 
 }  // namespace rtrdev

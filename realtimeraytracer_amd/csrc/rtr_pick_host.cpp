@@ -6,70 +6,42 @@
 #include "../../include/rtr_pick.h"
 
 #include <cstdint>
-#include <cstdio>
 
 namespace rtrdev {
 
-static bool pick_params_ok(const char* who, const rtr_pick_params* pick, char* msg, size_t msgBytes) {
-    if (!pick) { snprintf(msg, msgBytes, "%s: pick params is null", who); return false; }
-    if (pick->numPicks == 0u || pick->numPicks > RTR_PICK_MAX) {
-        snprintf(msg, msgBytes, "%s: numPicks %u (1 ... %u)", who, pick->numPicks, RTR_PICK_MAX);
-        return false;
-    }
-    uint32_t r = 0;
-    for (int i = 0; i < 6; ++i) r |= pick->_reserved[i];
-    if (r) { snprintf(msg, msgBytes, "%s: _reserved words of pick params are not 0", who); return false; }
-    return true;
+static int pick_params_ok(const char* who, const rtr_pick_params* pick) {
+    if (!pick) return refusef("%s: pick params is null", who);
+    if (const int rc = check_num_picks(who, pick->numPicks)) return rc;
+    return check_reserved(who, pick->_reserved, 6, "pick params");
 }
 
-bool pick_check_params(const char* who, const rtr_light_params* p, const rtr_pick_params* pick, bool shade, char* msg, size_t msgBytes, int* rc) {
-    *rc = RTR_ERR_INVALID_ARGUMENT;
-    if (!p) { snprintf(msg, msgBytes, "%s: params is null", who); return false; }
-    if (!pick_params_ok(who, pick, msg, msgBytes)) return false;
+int pick_check_params(const char* who, const rtr_light_params* p, const rtr_pick_params* pick, bool shade) {
+    if (!p) return refusef("%s: params is null", who);
+    if (const int rc = pick_params_ok(who, pick)) return rc;
     /* what rtr_light_slots refuses of the params alone; numAreaLights is held to the scene's lights once there is a scene */
-    if (p->numShadowRays == 0 || p->numShadowRays > 1024) { snprintf(msg, msgBytes, "%s: numShadowRays %u (1 ... 1024)", who, p->numShadowRays); return false; }
-    if (p->outputs & ~(RTR_LIGHT_SHADOWED | RTR_LIGHT_UNSHADOWED | RTR_LIGHT_ANALYTIC)) {
-        snprintf(msg, msgBytes, "%s: unknown output bits 0x%x", who, p->outputs);
-        return false;
-    }
+    if (const int rc = check_shadow_rays(who, p->numShadowRays)) return rc;
+    if (const int rc = check_light_outputs(who, p->outputs)) return rc;
     if (shade && (p->outputs & RTR_LIGHT_ANALYTIC)) {
-        *rc = RTR_ERR_UNSUPPORTED;
-        snprintf(msg, msgBytes, "%s: RTR_LIGHT_ANALYTIC has no per-sample form (the LTC term integrates whole lights): use rtr_shade_hits", who);
-        return false;
+        refusef("%s: RTR_LIGHT_ANALYTIC has no per-sample form (the LTC term integrates whole lights): use rtr_shade_hits", who);
+        return RTR_ERR_UNSUPPORTED;
     }
-    return true;
+    return RTR_OK;
 }
 
-bool pick_check_arrays(const char* who, const PickCall& c, char* msg, size_t msgBytes) {
-    const uint32_t P = c.pick->numPicks, R = P + 1u;
-    if ((uint64_t)c.n * R > 0xffffffffull) { snprintf(msg, msgBytes, "%s: %u hits x %u slots do not fit 32 bits", who, c.n, R); return false; }
-    struct Arg { const void* ptr; const char* name; unsigned align; bool needed; };
+int pick_check_arrays(const char* who, const PickCall& c) {
+    if (const int rc = check_fits_32(who, c.n, "hits", c.pick->numPicks + 1u, "slots")) return rc;
     const Arg light[6] = {{c.rays, "rays", 16, true}, {c.hits, "hits", 16, true}, {c.seeds, "seeds", 4, false}, {c.slots, "slotsIn", 4, false},
                           {c.outRays, "outRays", 16, true}, {c.outSlots, "outSlots", 4, true}};
     const Arg shade[7] = {{c.rays, "rays", 16, true}, {c.hits, "hits", 16, true}, {c.seeds, "seeds", 4, false}, {c.slots, "slots", 4, true},
                           {c.weights, "weights", 4, false}, {c.occluded, "occluded", 1, true}, {c.out, "out", 16, true}};
-    const Arg* args = c.shade ? shade : light;
-    const int count = c.shade ? 7 : 6;
-    for (int i = 0; i < count; ++i)
-        if (args[i].needed && !args[i].ptr) { snprintf(msg, msgBytes, "%s: %s is null", who, args[i].name); return false; }
-    for (int i = 0; i < count; ++i)
-        if (args[i].ptr && ((uintptr_t)args[i].ptr & (args[i].align - 1u))) {
-            snprintf(msg, msgBytes, "%s: %s is not %u-B aligned", who, args[i].name, args[i].align);
-            return false;
-        }
-    if (!c.seeds && (c.light->width == 0 || c.light->spp == 0)) {
-        snprintf(msg, msgBytes, "%s: width %u, spp %u: without seeds the hits are pixel-samples of a frame", who, c.light->width, c.light->spp);
-        return false;
-    }
-    return true;
+    if (const int rc = c.shade ? check_ptrs(who, shade) : check_ptrs(who, light)) return rc;
+    return check_pixel_seeds(who, c.seeds, c.light->width, c.light->spp);
 }
 
-bool pick_check_area(const char* who, uint64_t areaSlots, char* msg, size_t msgBytes) {
-    if (areaSlots > RTR_PICK_MAX_SLOTS) {
-        snprintf(msg, msgBytes, "%s: %llu area slots per hit are more than RTR_PICK_MAX_SLOTS = 2^24", who, (unsigned long long)areaSlots);
-        return false;
-    }
-    return true;
+int pick_check_area(const char* who, uint64_t areaSlots) {
+    if (areaSlots > RTR_PICK_MAX_SLOTS)
+        return refusef("%s: %llu area slots per hit are more than RTR_PICK_MAX_SLOTS = 2^24", who, (unsigned long long)areaSlots);
+    return RTR_OK;
 }
 
 }  // namespace rtrdev
@@ -77,24 +49,17 @@ bool pick_check_area(const char* who, uint64_t areaSlots, char* msg, size_t msgB
 extern "C" int rtr_host_pick_slots(const uint32_t* seeds, uint32_t n, uint32_t frame, uint32_t width, uint32_t spp, const rtr_pick_params* pick,
                                    uint32_t areaSlots, uint32_t* outSlots) {
     const char* who = "rtr_host_pick_slots";
-    char msg[256];
-    if (!rtrdev::pick_params_ok(who, pick, msg, sizeof msg) || !rtrdev::pick_check_area(who, areaSlots, msg, sizeof msg)) {
-        rtrdev::set_last_error(msg);
-        return RTR_ERR_INVALID_ARGUMENT;
-    }
+    if (const int rc = rtrdev::pick_params_ok(who, pick)) return rc;
+    if (const int rc = rtrdev::pick_check_area(who, areaSlots)) return rc;
     if (n == 0) return RTR_OK;
     const uint32_t P = pick->numPicks;
-    if ((uint64_t)n * P > 0xffffffffull) snprintf(msg, sizeof msg, "%s: %u hits x %u picks do not fit 32 bits", who, n, P);
-    else if (!outSlots) snprintf(msg, sizeof msg, "%s: outSlots is null", who);
-    else if (((uintptr_t)outSlots | (uintptr_t)seeds) & 3u) snprintf(msg, sizeof msg, "%s: %s is not 4-B aligned", who, ((uintptr_t)outSlots & 3u) ? "outSlots" : "seeds");
-    else if (!seeds && (width == 0 || spp == 0)) snprintf(msg, sizeof msg, "%s: width %u, spp %u: without seeds the hits are pixel-samples of a frame", who, width, spp);
-    else {
-        for (uint32_t k = 0; k < n; ++k) {
-            const uint32_t baseFrame = rtr_pick_base(seeds, k, width, spp) + frame;
-            for (uint32_t p = 0; p < P; ++p) outSlots[(size_t)k * P + p] = rtr_pick_slot(baseFrame, pick->depth, p, areaSlots);
-        }
-        return RTR_OK;
+    if (const int rc = rtrdev::check_fits_32(who, n, "hits", P, "picks")) return rc;
+    const rtrdev::Arg a[2] = {{outSlots, "outSlots", 4, true}, {seeds, "seeds", 4, false}};
+    if (const int rc = rtrdev::check_ptrs(who, a)) return rc;
+    if (const int rc = rtrdev::check_pixel_seeds(who, seeds, width, spp)) return rc;
+    for (uint32_t k = 0; k < n; ++k) {
+        const uint32_t baseFrame = rtr_pick_base(seeds, k, width, spp) + frame;
+        for (uint32_t p = 0; p < P; ++p) outSlots[(size_t)k * P + p] = rtr_pick_slot(baseFrame, pick->depth, p, areaSlots);
     }
-    rtrdev::set_last_error(msg);
-    return RTR_ERR_INVALID_ARGUMENT;
+    return RTR_OK;
 }

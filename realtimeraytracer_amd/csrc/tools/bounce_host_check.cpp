@@ -3,28 +3,11 @@
  * records — live ones over the whole material range, views from behind the shading normal and along the surface, every kind of dead one, seeds whose random number is exactly 1.0, exactly sized
  * heap arrays so that a read or write past a record is caught — and every refusal.  Exit status 0 and "ok" when nothing was reported. */
 #include "../rtr_bounce_host.h"
+#include "host_check.h"
 
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
 #include <limits>
-#include <string>
-
-static std::string g_err;
-void rtrdev::set_last_error(const char* msg) { g_err = msg; }
-
-static uint32_t lcg(uint32_t& s) { s = s * 1664525u + 1013904223u; return s; }
-static float unit(uint32_t& s) { return (float)(lcg(s) >> 8) * (1.0f / 16777216.0f); }
-
-template <class T>
-static T* aligned(size_t n) { return static_cast<T*>(aligned_alloc(16, (n * sizeof(T) + 15) / 16 * 16)); }
-
-static int expect_refused(int rc, const char* needle) {
-    if (rc == RTR_ERR_INVALID_ARGUMENT && g_err.find("rtr_host_bounce_rays: ") == 0 && g_err.find(needle) != std::string::npos) return 0;
-    fprintf(stderr, "expected a refusal naming '%s', got %d '%s'\n", needle, rc, g_err.c_str());
-    return 1;
-}
 
 int main() {
     const uint32_t n = 640;
@@ -107,14 +90,15 @@ int main() {
     rtr_bounce_params p{};
     p.width = 8; p.spp = 1; p.lobes = 3; p.normalOffset = 0.01f; p.tmin = 0.001f; p.tmax = 10000.0f;
     rtr_bounce_params q = p;
-    bad += expect_refused(rtr_host_bounce_rays(nullptr, sf, n, &p, seeds, outRays, outBounce), "rays is null");
-    bad += expect_refused(rtr_host_bounce_rays(rays, sf, n, nullptr, seeds, outRays, outBounce), "params is null");
-    bad += expect_refused(rtr_host_bounce_rays(rays, sf, n, &p, seeds, reinterpret_cast<RtrRay*>(reinterpret_cast<char*>(outRays) + 4), outBounce), "outRays is not 16-B aligned");
-    q = p; q.lobes = 0; bad += expect_refused(rtr_host_bounce_rays(rays, sf, n, &q, seeds, outRays, outBounce), "lobes");
-    q = p; q.width = 0; bad += expect_refused(rtr_host_bounce_rays(rays, sf, n, &q, nullptr, outRays, outBounce), "width");
-    q = p; q.tmax = nan; bad += expect_refused(rtr_host_bounce_rays(rays, sf, n, &q, seeds, outRays, outBounce), "tmax");
-    q = p; q.tmin = 5.0f; q.tmax = 5.0f; bad += expect_refused(rtr_host_bounce_rays(rays, sf, n, &q, seeds, outRays, outBounce), "tmax");
-    bad += expect_refused(rtr_host_bounce_rays(rays, sf, n, &p, seeds, rays, outBounce), "outRays overlaps rays");
+    const char* who = "rtr_host_bounce_rays";
+    bad += expect_refused(rtr_host_bounce_rays(nullptr, sf, n, &p, seeds, outRays, outBounce), who, "rays is null");
+    bad += expect_refused(rtr_host_bounce_rays(rays, sf, n, nullptr, seeds, outRays, outBounce), who, "params is null");
+    bad += expect_refused(rtr_host_bounce_rays(rays, sf, n, &p, seeds, reinterpret_cast<RtrRay*>(reinterpret_cast<char*>(outRays) + 4), outBounce), who, "outRays is not 16-B aligned");
+    q = p; q.lobes = 0; bad += expect_refused(rtr_host_bounce_rays(rays, sf, n, &q, seeds, outRays, outBounce), who, "lobes");
+    q = p; q.width = 0; bad += expect_refused(rtr_host_bounce_rays(rays, sf, n, &q, nullptr, outRays, outBounce), who, "width");
+    q = p; q.tmax = nan; bad += expect_refused(rtr_host_bounce_rays(rays, sf, n, &q, seeds, outRays, outBounce), who, "tmax");
+    q = p; q.tmin = 5.0f; q.tmax = 5.0f; bad += expect_refused(rtr_host_bounce_rays(rays, sf, n, &q, seeds, outRays, outBounce), who, "tmax");
+    bad += expect_refused(rtr_host_bounce_rays(rays, sf, n, &p, seeds, rays, outBounce), who, "outRays overlaps rays");
     if (rtr_host_bounce_rays(nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr) != RTR_OK) ++bad;
 
     free(rays); free(sf); free(seeds); free(outRays); free(outBounce);

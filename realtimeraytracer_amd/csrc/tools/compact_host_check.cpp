@@ -5,28 +5,11 @@
  * stride 12 and 32, on exactly sized heap arrays so that a read or write past a record is caught; checks the count, the stable order
  * and the cleared tail; and every kind of refusal.  Exit status 0 and "ok" when nothing was reported. */
 #include "../rtr_paths_host.h"
+#include "host_check.h"
 
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
 #include <limits>
-#include <string>
 #include <vector>
-
-static std::string g_err;
-void rtrdev::set_last_error(const char* msg) { g_err = msg; }
-
-static uint32_t lcg(uint32_t& s) { s = s * 1664525u + 1013904223u; return s; }
-static float unit(uint32_t& s) { return (float)(lcg(s) >> 8) * (1.0f / 16777216.0f); }
-
-template <class T>
-static T* aligned(size_t n) { return static_cast<T*>(aligned_alloc(16, (n * sizeof(T) + 15) / 16 * 16)); }
-
-static int expect_refused(int rc, const char* needle) {
-    if (rc == RTR_ERR_INVALID_ARGUMENT && g_err.find("rtr_host_compact_paths: ") == 0 && g_err.find(needle) != std::string::npos) return 0;
-    fprintf(stderr, "expected a refusal naming '%s', got %d '%s'\n", needle, rc, g_err.c_str());
-    return 1;
-}
 
 static bool wanted_live(int pattern, uint32_t k, uint32_t n, uint32_t& s) {
     switch (pattern) {
@@ -125,22 +108,22 @@ int main() {
     p.throughputStrideBytes = 12; p.survivalFloor = 0.05f;
     rtr_compact_params q = p;
     int refusals = 0;
-#define REFUSED(call, needle) do { bad += expect_refused(call, needle); ++refusals; } while (0)
-    REFUSED(rtr_host_compact_paths(nullptr, thr, seeds, ids, n, &p, outRays, outT, outSeeds, outIds, &count), "rays is null");
-    REFUSED(rtr_host_compact_paths(rays, thr, seeds, ids, n, nullptr, outRays, outT, outSeeds, outIds, &count), "params is null");
-    REFUSED(rtr_host_compact_paths(rays, thr, seeds, ids, n, &p, outRays, outT, outSeeds, outIds, nullptr), "outCount is null");
-    REFUSED(rtr_host_compact_paths(rays, thr, seeds, ids, n, &p, outRays, outT, nullptr, outIds, &count), "outSeeds is null");
-    REFUSED(rtr_host_compact_paths(rays, thr, nullptr, ids, n, &p, outRays, outT, outSeeds, outIds, &count), "outSeeds without seeds");
-    REFUSED(rtr_host_compact_paths(rays, thr, seeds, ids, n, &p, reinterpret_cast<RtrRay*>(reinterpret_cast<char*>(outRays) + 4), outT, outSeeds, outIds, &count), "outRays is not 16-B aligned");
-    q = p; q.throughputStrideBytes = 8; REFUSED(rtr_host_compact_paths(rays, thr, seeds, ids, n, &q, outRays, outT, outSeeds, outIds, &count), "throughputStrideBytes");
-    q = p; q.flags = 2; REFUSED(rtr_host_compact_paths(rays, thr, seeds, ids, n, &q, outRays, outT, outSeeds, outIds, &count), "flags");
-    q = p; q.flags = 1; REFUSED(rtr_host_compact_paths(rays, thr, nullptr, ids, n, &q, outRays, outT, nullptr, outIds, &count), "needs seeds");
-    q = p; q.flags = 1; q.survivalFloor = nan; REFUSED(rtr_host_compact_paths(rays, thr, seeds, ids, n, &q, outRays, outT, outSeeds, outIds, &count), "survivalFloor");
-    q = p; q.flags = 1; q.survivalFloor = 0.0f; REFUSED(rtr_host_compact_paths(rays, thr, seeds, ids, n, &q, outRays, outT, outSeeds, outIds, &count), "survivalFloor");
-    q = p; q._reserved[2] = 1; REFUSED(rtr_host_compact_paths(rays, thr, seeds, ids, n, &q, outRays, outT, outSeeds, outIds, &count), "_reserved");
-    REFUSED(rtr_host_compact_paths(rays, thr, seeds, ids, n, &p, rays, outT, outSeeds, outIds, &count), "outRays overlaps rays");
-    REFUSED(rtr_host_compact_paths(rays, thr, seeds, ids, n, &p, outRays, outT, outSeeds, outSeeds, &count), "outSeeds overlaps outPathIds");
-    REFUSED(rtr_host_compact_paths(rays, thr, seeds, ids, n, &p, outRays, outT, outSeeds, outIds, outIds + 5), "outPathIds overlaps outCount");
+    const char* who = "rtr_host_compact_paths";
+    REFUSED(rtr_host_compact_paths(nullptr, thr, seeds, ids, n, &p, outRays, outT, outSeeds, outIds, &count), who, "rays is null");
+    REFUSED(rtr_host_compact_paths(rays, thr, seeds, ids, n, nullptr, outRays, outT, outSeeds, outIds, &count), who, "params is null");
+    REFUSED(rtr_host_compact_paths(rays, thr, seeds, ids, n, &p, outRays, outT, outSeeds, outIds, nullptr), who, "outCount is null");
+    REFUSED(rtr_host_compact_paths(rays, thr, seeds, ids, n, &p, outRays, outT, nullptr, outIds, &count), who, "outSeeds is null");
+    REFUSED(rtr_host_compact_paths(rays, thr, nullptr, ids, n, &p, outRays, outT, outSeeds, outIds, &count), who, "outSeeds without seeds");
+    REFUSED(rtr_host_compact_paths(rays, thr, seeds, ids, n, &p, reinterpret_cast<RtrRay*>(reinterpret_cast<char*>(outRays) + 4), outT, outSeeds, outIds, &count), who, "outRays is not 16-B aligned");
+    q = p; q.throughputStrideBytes = 8; REFUSED(rtr_host_compact_paths(rays, thr, seeds, ids, n, &q, outRays, outT, outSeeds, outIds, &count), who, "throughputStrideBytes");
+    q = p; q.flags = 2; REFUSED(rtr_host_compact_paths(rays, thr, seeds, ids, n, &q, outRays, outT, outSeeds, outIds, &count), who, "flags");
+    q = p; q.flags = 1; REFUSED(rtr_host_compact_paths(rays, thr, nullptr, ids, n, &q, outRays, outT, nullptr, outIds, &count), who, "needs seeds");
+    q = p; q.flags = 1; q.survivalFloor = nan; REFUSED(rtr_host_compact_paths(rays, thr, seeds, ids, n, &q, outRays, outT, outSeeds, outIds, &count), who, "survivalFloor");
+    q = p; q.flags = 1; q.survivalFloor = 0.0f; REFUSED(rtr_host_compact_paths(rays, thr, seeds, ids, n, &q, outRays, outT, outSeeds, outIds, &count), who, "survivalFloor");
+    q = p; q._reserved[2] = 1; REFUSED(rtr_host_compact_paths(rays, thr, seeds, ids, n, &q, outRays, outT, outSeeds, outIds, &count), who, "_reserved");
+    REFUSED(rtr_host_compact_paths(rays, thr, seeds, ids, n, &p, rays, outT, outSeeds, outIds, &count), who, "outRays overlaps rays");
+    REFUSED(rtr_host_compact_paths(rays, thr, seeds, ids, n, &p, outRays, outT, outSeeds, outSeeds, &count), who, "outSeeds overlaps outPathIds");
+    REFUSED(rtr_host_compact_paths(rays, thr, seeds, ids, n, &p, outRays, outT, outSeeds, outIds, outIds + 5), who, "outPathIds overlaps outCount");
     size_t bytes = 1, last = 0;
     if (rtr_compact_scratch_bytes(7, nullptr) != RTR_ERR_INVALID_ARGUMENT) ++bad;
     for (uint32_t m = 0; m < 5000; ++m) {

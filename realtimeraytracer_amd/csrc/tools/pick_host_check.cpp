@@ -5,23 +5,10 @@
  * equals the header's function of its seed; the argument checks the device entry points share; and every kind of refusal.  Exit
  * status 0 and "ok" when nothing was reported. */
 #include "../rtr_pick_host.h"
+#include "host_check.h"
 #include "../../../include/rtr_pick.h"
 
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
-#include <string>
-
-static std::string g_err;
-void rtrdev::set_last_error(const char* msg) { g_err = msg; }
-
-static uint32_t lcg(uint32_t& s) { s = s * 1664525u + 1013904223u; return s; }
-
-static int expect_refused(int rc, const char* needle) {
-    if (rc == RTR_ERR_INVALID_ARGUMENT && g_err.find("rtr_host_pick_slots: ") == 0 && g_err.find(needle) != std::string::npos) return 0;
-    fprintf(stderr, "expected a refusal naming '%s', got %d '%s'\n", needle, rc, g_err.c_str());
-    return 1;
-}
 
 int main() {
     const uint32_t sizes[7] = {1, 63, 64, 65, 257, 4099, 20000};
@@ -68,49 +55,47 @@ int main() {
     p.numPicks = 2;
     rtr_pick_params q = p;
     int refusals = 0;
-#define REFUSED(call, needle) do { bad += expect_refused(call, needle); ++refusals; } while (0)
-    REFUSED(rtr_host_pick_slots(seeds, 32, 0, 0, 0, nullptr, 6, out), "pick params is null");
-    q = p; q.numPicks = 0; REFUSED(rtr_host_pick_slots(seeds, 32, 0, 0, 0, &q, 6, out), "numPicks 0");
-    q = p; q.numPicks = RTR_PICK_MAX + 1u; REFUSED(rtr_host_pick_slots(seeds, 32, 0, 0, 0, &q, 6, out), "numPicks 31");
-    q = p; q._reserved[5] = 1; REFUSED(rtr_host_pick_slots(seeds, 32, 0, 0, 0, &q, 6, out), "_reserved");
-    REFUSED(rtr_host_pick_slots(seeds, 32, 0, 0, 0, &p, (1u << 24) + 1u, out), "area slots");
-    REFUSED(rtr_host_pick_slots(seeds, 32, 0, 0, 0, &p, 6, nullptr), "outSlots is null");
-    REFUSED(rtr_host_pick_slots(seeds, 32, 0, 0, 0, &p, 6, reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(out) + 2)), "outSlots is not 4-B aligned");
-    REFUSED(rtr_host_pick_slots(reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(seeds) + 1), 31, 0, 0, 0, &p, 6, out), "seeds is not 4-B aligned");
-    REFUSED(rtr_host_pick_slots(nullptr, 32, 0, 0, 1, &p, 6, out), "width 0");
-    REFUSED(rtr_host_pick_slots(nullptr, 32, 0, 8, 0, &p, 6, out), "spp 0");
-    REFUSED(rtr_host_pick_slots(seeds, 0xffffffffu, 0, 0, 0, &p, 6, out), "do not fit 32 bits");
+    const char* who = "rtr_host_pick_slots";
+    REFUSED(rtr_host_pick_slots(seeds, 32, 0, 0, 0, nullptr, 6, out), who, "pick params is null");
+    q = p; q.numPicks = 0; REFUSED(rtr_host_pick_slots(seeds, 32, 0, 0, 0, &q, 6, out), who, "numPicks 0");
+    q = p; q.numPicks = RTR_PICK_MAX + 1u; REFUSED(rtr_host_pick_slots(seeds, 32, 0, 0, 0, &q, 6, out), who, "numPicks 31");
+    q = p; q._reserved[5] = 1; REFUSED(rtr_host_pick_slots(seeds, 32, 0, 0, 0, &q, 6, out), who, "_reserved");
+    REFUSED(rtr_host_pick_slots(seeds, 32, 0, 0, 0, &p, (1u << 24) + 1u, out), who, "area slots");
+    REFUSED(rtr_host_pick_slots(seeds, 32, 0, 0, 0, &p, 6, nullptr), who, "outSlots is null");
+    REFUSED(rtr_host_pick_slots(seeds, 32, 0, 0, 0, &p, 6, reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(out) + 2)), who, "outSlots is not 4-B aligned");
+    REFUSED(rtr_host_pick_slots(reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(seeds) + 1), 31, 0, 0, 0, &p, 6, out), who, "seeds is not 4-B aligned");
+    REFUSED(rtr_host_pick_slots(nullptr, 32, 0, 0, 1, &p, 6, out), who, "width 0");
+    REFUSED(rtr_host_pick_slots(nullptr, 32, 0, 8, 0, &p, 6, out), who, "spp 0");
+    REFUSED(rtr_host_pick_slots(seeds, 0xffffffffu, 0, 0, 0, &p, 6, out), who, "do not fit 32 bits");
     if (rtr_host_pick_slots(nullptr, 0, 0, 0, 0, &p, 6, nullptr) != RTR_OK) ++bad;
 
     /* the checks the device entry points share */
-    char msg[256];
-    int rc = 0;
     rtr_light_params lp{};
     lp.numShadowRays = 3; lp.width = 8; lp.spp = 1; lp.outputs = RTR_LIGHT_SHADOWED;
-    if (!rtrdev::pick_check_params("f", &lp, &p, true, msg, sizeof msg, &rc)) ++bad;
+    if (rtrdev::pick_check_params("f", &lp, &p, true) != RTR_OK) ++bad;
     rtr_light_params lq = lp;
     lq.outputs |= RTR_LIGHT_ANALYTIC;
-    if (rtrdev::pick_check_params("f", &lq, &p, true, msg, sizeof msg, &rc) || rc != RTR_ERR_UNSUPPORTED) ++bad;
-    if (!rtrdev::pick_check_params("f", &lq, &p, false, msg, sizeof msg, &rc)) ++bad;
+    if (rtrdev::pick_check_params("f", &lq, &p, true) != RTR_ERR_UNSUPPORTED) ++bad;
+    if (rtrdev::pick_check_params("f", &lq, &p, false) != RTR_OK) ++bad;
     lq = lp; lq.numShadowRays = 1025;
-    if (rtrdev::pick_check_params("f", &lq, &p, false, msg, sizeof msg, &rc) || rc != RTR_ERR_INVALID_ARGUMENT) ++bad;
+    if (rtrdev::pick_check_params("f", &lq, &p, false) != RTR_ERR_INVALID_ARGUMENT) ++bad;
     alignas(16) static RtrRay rays[2];
     alignas(16) static RtrHit hits[2];
     alignas(16) static RtrRadiance rad[2];
     uint8_t occ[6];
     float w[4];
     rtrdev::PickCall c{rays, hits, 2, &lp, &p, nullptr, false, nullptr, rays, out, nullptr, nullptr, nullptr};
-    if (!rtrdev::pick_check_arrays("f", c, msg, sizeof msg)) ++bad;
+    if (rtrdev::pick_check_arrays("f", c) != RTR_OK) ++bad;
     c.outSlots = nullptr;
-    if (rtrdev::pick_check_arrays("f", c, msg, sizeof msg) || !strstr(msg, "outSlots is null")) ++bad;
+    bad += expect_refused(rtrdev::pick_check_arrays("f", c), "f", "outSlots is null");
     rtrdev::PickCall d{rays, hits, 2, &lp, &p, seeds, true, out, nullptr, nullptr, w, occ, rad};
-    if (!rtrdev::pick_check_arrays("f", d, msg, sizeof msg)) ++bad;
+    if (rtrdev::pick_check_arrays("f", d) != RTR_OK) ++bad;
     d.slots = nullptr;
-    if (rtrdev::pick_check_arrays("f", d, msg, sizeof msg) || !strstr(msg, "slots is null")) ++bad;
+    bad += expect_refused(rtrdev::pick_check_arrays("f", d), "f", "slots is null");
     d.slots = out; d.n = 0x10000000u;
-    if (!rtrdev::pick_check_arrays("f", d, msg, sizeof msg)) ++bad;                /* 2^28 x 3 fits */
+    if (rtrdev::pick_check_arrays("f", d) != RTR_OK) ++bad;                /* 2^28 x 3 fits */
     d.n = 0x60000000u;
-    if (rtrdev::pick_check_arrays("f", d, msg, sizeof msg) || !strstr(msg, "do not fit 32 bits")) ++bad;
+    bad += expect_refused(rtrdev::pick_check_arrays("f", d), "f", "do not fit 32 bits");
 
     if (bad) { fprintf(stderr, "%d problems\n", bad); return 1; }
     printf("ok: %zu runs, %zu slots, %d refusals\n", runs, slots, refusals);

@@ -86,11 +86,12 @@ PATTERN = 0xA5
 
 
 class Buffers:
-    """16-B aligned host arrays of N records, the outputs pre-filled with a pattern"""
+    """16-B aligned host arrays of N records, the outputs pre-filled with a pattern; the outputs have room for 2 N records, so that an
+    output moved to the last record of the other one still ends inside that array and reaches no third one"""
 
     def __init__(self):
         rays, sf, seeds = W.make_surfaces(N, seed=11)
-        self.keep = [np.zeros(len(x.tobytes()) + 64, np.uint8) for x in (rays, sf, seeds)] + [np.full(32 * N + 64, PATTERN, np.uint8) for _ in range(2)]
+        self.keep = [np.zeros(len(x.tobytes()) + 64, np.uint8) for x in (rays, sf, seeds)] + [np.full(64 * N + 64, PATTERN, np.uint8) for _ in range(2)]
         self.addr = []
         for k, buf in enumerate(self.keep):
             a = (buf.ctypes.data + 15) & ~15
@@ -163,6 +164,43 @@ def test_the_device_calls_check_their_arguments_before_the_context(name):
         assert name.encode() + b": " in msg and needle in msg, (kw, msg)
     assert fn(None, *b.args()) == INVALID and b"ctx is null" in lib.rtr_last_error()
     assert b.untouched()
+
+
+def _two_faults(b):
+    """calls with two faults, and the one whose message wins: every null before any misaligned pointer, each in the argument order
+    (seeds' alignment after the 16-B ones), the arrays before the params' values, the params in their order, overlaps last"""
+    mk = api.make_bounce_params
+    return [
+        ({"rays": b.rays + 4, "outBounce": 0}, b"outBounce is null"), ({"surfaces": 0, "outRays": 0}, b"surfaces is null"),
+        ({"surfaces": b.surfaces + 8, "outRays": b.out_rays + 4}, b"surfaces is not 16-B aligned"),
+        ({"outRays": b.out_rays + 4, "seeds": b.seeds + 2}, b"outRays is not 16-B aligned"),
+        ({"params": None, "rays": 0}, b"params is null"), ({"params": mk(lobes=0, width=8), "rays": 0}, b"rays is null"),
+        ({"params": mk(lobes=0, width=8), "seeds": b.seeds + 2}, b"seeds is not 4-B aligned"),
+        ({"params": mk(lobes=0, width=0), "seeds": 0}, b"lobes 0x0"), ({"params": mk(width=0, tmin=float("nan")), "seeds": 0}, b"width 0, spp 1"),
+        ({"params": mk(width=8, tmin=2.0, tmax=1.0), "outRays": b.rays}, b"tmax 1 is not above tmin 2"),
+        ({"outRays": b.rays, "outBounce": b.out_rays}, b"outRays overlaps rays"),
+        ({"outRays": b.surfaces, "outBounce": b.rays}, b"outRays overlaps surfaces"),
+    ]
+
+
+@pytest.mark.parametrize("name", ["rtr_host_bounce_rays", "rtr_bounce_rays", "rtr_bounce_rays_async"])
+def test_which_refusal_wins_under_two_faults(name):
+    lib = A.hip_lib()
+    fn = getattr(lib, name) if "host" in name else (lambda *a: getattr(lib, name)(None, *a))      # a null context: the arrays' faults win
+    b = Buffers()
+    for kw, needle in _two_faults(b):
+        assert fn(*b.args(**kw)) == INVALID, kw
+        msg = lib.rtr_last_error()
+        assert msg.startswith(name.encode() + b": " + needle), (kw, msg)
+
+
+def test_host_sincos_turn_names_its_first_null_array():
+    lib = A.hip_lib()
+    u = np.zeros(4, np.float32)
+    for args, needle in (((None, 4, None, None), b"u is null"), ((VP(u.ctypes.data), 4, None, None), b"outSin is null"),
+                         ((VP(u.ctypes.data), 4, VP(u.ctypes.data), None), b"outCos is null")):
+        assert lib.rtr_host_sincos_turn(*args) == INVALID and lib.rtr_last_error() == b"rtr_host_sincos_turn: " + needle
+    assert lib.rtr_host_sincos_turn(None, 0, None, None) == 0
 
 
 def test_host_bounce_rays_checks_its_arrays():

@@ -254,6 +254,43 @@ def test_the_device_calls_check_their_arguments_before_the_context(name):
     assert b.untouched()
 
 
+def _two_faults(b, device):
+    """calls with two faults, and the one whose message wins: every null before any misaligned pointer, each in the argument order
+    (the scratch last), the arrays before the params' values, the params in their order, overlaps last and per output"""
+    r = [
+        ({"rays": b.rays + 4, "outCount": 0}, b"outCount is null"), ({"throughput": 0, "outRays": 0}, b"throughput is null"),
+        ({"seeds": b.seeds + 2, "outRays": b.out_rays + 8}, b"seeds is not 4-B aligned"),
+        ({"outThroughput": b.out_t + 1, "outCount": b.out_count + 2}, b"outThroughput is not 4-B aligned"),
+        ({"params": None, "rays": 0}, b"params is null"), ({"params": _params(stride=8), "outRays": b.out_rays + 8}, b"outRays is not 16-B aligned"),
+        ({"seeds": 0, "rays": b.rays + 4}, b"rays is not 16-B aligned"), ({"seeds": 0, "params": _params(stride=8)}, b"outSeeds without seeds"),
+        ({"params": _params(stride=8, flags=2)}, b"throughputStrideBytes 8"), ({"params": _params(flags=2, reserved=0)}, b"flags 0x2"),
+        ({"params": _params(roulette=True, survival_floor=0.0, reserved=1)}, b"survivalFloor 0"),
+        ({"params": _params(reserved=0), "outRays": b.rays}, b"_reserved words of params are not 0"),
+        ({"outRays": b.rays, "outPathIds": b.ids}, b"outRays overlaps rays"),
+        ({"outPathIds": b.ids, "outCount": b.out_rays + 16}, b"outPathIds overlaps pathIds"),
+        ({"outThroughput": b.out_rays + 32 * (N - 1) + 28, "outCount": b.seeds}, b"outRays overlaps outThroughput"),
+    ]
+    if device:
+        r += [({"rays": b.rays + 4, "scratch": 0}, b"scratch is null"), ({"outCount": b.out_count + 2, "scratch": b.scratch + 8}, b"outCount is not 4-B aligned"),
+              ({"scratchBytes": 0, "params": _params(stride=8)}, b"scratchBytes 0"), ({"scratchBytes": 0, "seeds": 0}, b"outSeeds without seeds"),
+              ({"scratch": b.rays + 16 * 7, "outCount": b.seeds}, b"outCount overlaps seeds")]
+    return r
+
+
+@pytest.mark.parametrize("name", ["rtr_host_compact_paths", "rtr_compact_paths", "rtr_compact_paths_async"])
+def test_which_refusal_wins_under_two_faults(name):
+    lib = A.hip_lib()
+    device = "host" not in name
+    extra = (None,) if name == "rtr_compact_paths" else ()
+    fn = (lambda *a: getattr(lib, name)(None, *a, *extra)) if device else getattr(lib, name)      # a null context: the arrays' faults win
+    b = Buffers()
+    for kw, needle in _two_faults(b, device):
+        assert fn(*b.args(device, **kw)) == INVALID, kw
+        msg = lib.rtr_last_error()
+        assert msg.startswith(name.encode() + b": " + needle), (kw, msg)
+    assert b.untouched()
+
+
 def test_host_compact_paths_checks_its_arrays():
     rays, thr, seeds, ids, _ = W.make_paths(8, "random_half")
     for bad in ((rays[:, :7], thr, seeds, ids), (rays.astype(np.float64), thr, seeds, ids), (rays, thr[:, :2], seeds, ids), (rays, thr[:4], seeds, ids),

@@ -81,3 +81,23 @@ def test_arguments_are_checked_before_any_device_is_touched():
                  lambda: lib.rtr_tonemap_pack(None, None, 48, 0, None)):
         assert call() == INVALID
         assert b"null" in lib.rtr_last_error()
+
+
+def test_which_refusal_wins_under_two_faults():
+    """the lighting calls look at their handles and params before any array or value; rtr_tonemap_pack at its context, then the stride,
+    then the arrays; rtr_light_slots at its output before the scene"""
+    lib = A.hip_lib()
+    err = lib.rtr_last_error
+    bad = A.rtr_light_params(0, 0, 0, 0, 0, 8)          # numShadowRays 0, width and spp 0, unknown output bits
+    odd = A.VP(0x1002)
+    q = C.c_uint32(0)
+    assert lib.rtr_light_slots(None, None, None) == INVALID and err() == b"rtr_light_slots: slotsPerHit is null"
+    assert lib.rtr_light_slots(None, C.byref(bad), C.byref(q)) == INVALID and err() == b"rtr_light_slots: null scene or params"
+    for name in ("rtr_light_rays_async", "rtr_light_rays"):
+        assert getattr(lib, name)(None, None, odd, None, 4, C.byref(bad), odd, None) == INVALID
+        assert err() == name.encode() + b": null context, scene or params"
+    for name in ("rtr_shade_hits_async", "rtr_shade_hits"):
+        assert getattr(lib, name)(None, None, odd, None, 4, C.byref(bad), odd, None, odd) == INVALID
+        assert err() == name.encode() + b": null context, scene or params"
+    for name in ("rtr_tonemap_pack_async", "rtr_tonemap_pack"):
+        assert getattr(lib, name)(None, odd, 7, 4, None) == INVALID and err() == b"rtr_tonemap_pack: null context"

@@ -154,6 +154,91 @@ def test_refusals_by_message(name):
         assert not buf.any()                 # nothing was written
 
 
+@pytest.mark.parametrize("name", NEW[:4])
+def test_which_refusal_wins_under_two_faults(name):
+    """the mis params and their values in order, (rtr_mis_pick_weights: the light and pick params, what the three must agree on, numHits x
+    picks), every null before any misaligned pointer in the argument order, the pixel-seed rule, and only then the handles"""
+    lib = A.hip_lib()
+    weights = "pick_weights" in name
+    call = (lambda c, **kw: c.weights_call(getattr(lib, name), **kw)) if weights else (lambda c, **kw: c.emitter_call(getattr(lib, name), **kw))
+
+    def wins(needle, c=None, **kw):
+        c = c or Call()
+        assert call(c, **kw) == INVALID, needle
+        msg = lib.rtr_last_error().decode()
+        assert msg.startswith(f"{name}: {needle}"), f"expected '{name}: {needle}', got '{msg}'"
+
+    c = Call()
+    wins("mis params is null", mis=None, rays=None)
+    c.mis.numPicks, c.mis.numShadowRays, c.mis.lobes, c.mis._reserved[0] = 0, 0, 0, 1
+    wins("numPicks 0 (1 ... 30)", c=c)
+    c.mis.numPicks = 2
+    wins("numShadowRays 0 (1 ... 1024)", c=c)
+    c.mis.numShadowRays = 3
+    wins("lobes 0x0", c=c, rays=None)
+    c.mis.lobes = 3
+    wins("_reserved words of mis params are not 0", c=c, rays=None)
+    c = Call()
+    wins("rays is null", rays=None, hits=None)
+    wins("hits is null", hits=None, rays=Call.ptr(c.rays, 2))
+    if weights:
+        wins("outWeights is null", out_weights=None, rays=Call.ptr(c.rays, 2))
+        wins("hits is not 16-B aligned", hits=Call.ptr(c.hits, 2), out_samples=Call.ptr(c.samples, 4))
+        wins("seeds is not 4-B aligned", seeds=Call.ptr(c.seeds, 2), slots=Call.ptr(c.slots, 2), out_weights=Call.ptr(c.weights, 2))
+        wins("params is null", light=None, pick=None)
+        wins("pick params is null", pick=None, rays=None)
+        c = Call()
+        c.mis.lobes, c.light.numShadowRays = 0, 0
+        wins("lobes 0x0", c=c)
+        c = Call()
+        c.pick.numPicks, c.mis.numAreaLights = 3, 2
+        wins("numPicks 2 of the mis params is not the pick params' 3", c=c, rays=None)
+        c = Call()
+        c.mis.numAreaLights = 2
+        wins("numAreaLights 2, numShadowRays 3 of the mis params are not the light params' 1, 3", c=c, n=0x80000000)
+        wins("2147483648 hits x 2 picks do not fit 32 bits", n=0x80000000, rays=None)
+        c = Call()
+        c.light.width = 0
+        wins("rays is not 16-B aligned", c=c, rays=Call.ptr(c.rays, 2))
+        wins("width 0, spp 1", c=c)
+    else:
+        wins("out is null", out=None, rays=Call.ptr(c.rays, 2))
+        wins("prevSurfaces is not 16-B aligned", surf=Call.ptr(c.surf, 2), out=Call.ptr(c.out, 8))
+
+
+def test_the_host_forms_under_two_faults():
+    lib = A.hip_lib()
+    c = Call()
+    p = Call.ptr
+    x, out = np.zeros(3 * N + 1, np.float32), np.zeros(N + 1, np.float32)
+
+    def wins(fn, needle, *args):
+        assert getattr(lib, fn)(*args) == INVALID, needle
+        msg = lib.rtr_last_error().decode()
+        assert msg.startswith(f"{fn}: {needle}"), msg
+
+    wins("rtr_host_bounce_pdf", "lobes 0x0", None, p(c.surf), p(x), N, 0, p(out))
+    wins("rtr_host_bounce_pdf", "outPdf is null", p(c.rays, 2), p(c.surf), p(x), N, 3, None)
+    wins("rtr_host_bounce_pdf", "rays is null", None, None, p(x), N, 3, p(out))
+    wins("rtr_host_bounce_pdf", "dirs is not 4-B aligned", p(c.rays), p(c.surf), p(x, 2), N, 3, p(out, 2))
+    wins("rtr_host_mis_weights", "P 31 (0 ... 30)", N, None, p(x), p(x), p(x), (1 << 24) + 1, 31, p(c.samples), None)
+    wins("rtr_host_mis_weights", "Ttot 16777217", N, None, p(x), p(x), p(x), (1 << 24) + 1, 1, p(c.samples), None)
+    wins("rtr_host_mis_weights", "outSamples is null", N, p(x, 2), p(x), p(x), p(x), 1, 1, None, None)
+    wins("rtr_host_mis_weights", "dist is null", N, p(x), None, p(x), None, 1, 1, p(c.samples), None)
+    wins("rtr_host_mis_weights", "cosLight is not 4-B aligned", N, p(x), p(x), p(x, 2), p(x), 1, 1, p(c.samples), p(out, 2))
+    rec, first = np.zeros((1, 16), np.float32), np.zeros(1, np.uint32)
+    light = (A.RtrAreaLightInfo * 1)()
+    light[0].numTriangles = 1
+    mis = C.byref(c.mis)
+    wins("rtr_host_emitter_hits", "mis params is null", None, p(c.hits), p(c.surf), p(c.bounce), N, None, p(first), light, 1, None, p(c.out))
+    wins("rtr_host_emitter_hits", "numAreaLights 1 > lights 0", None, p(c.hits), p(c.surf), p(c.bounce), N, None, p(first), light, 0, mis, p(c.out))
+    wins("rtr_host_emitter_hits", "lightTris is null", None, p(c.hits), p(c.surf), p(c.bounce), N, None, None, light, 1, mis, p(c.out))
+    wins("rtr_host_emitter_hits", "lightTriFirst is null", None, p(c.hits), p(c.surf), p(c.bounce), N, p(rec), None, None, 1, mis, p(c.out))
+    wins("rtr_host_emitter_hits", "out is null", p(c.rays, 2), p(c.hits), p(c.surf), p(c.bounce), N, p(rec), p(first), light, 1, mis, None)
+    wins("rtr_host_emitter_hits", "hits is not 16-B aligned", p(c.rays), p(c.hits, 2), p(c.surf), p(c.bounce, 2), N, p(rec), p(first), light, 1, mis, p(c.out))
+    assert not c.out.any() and not out.any() and not c.samples.any()
+
+
 def test_export_light_tris_refusals():
     lib = A.hip_lib()
     count = C.c_uint32(7)

@@ -50,6 +50,15 @@ def test_null_context_or_scene_is_refused_with_the_existing_message():
     assert b"rtr_trace_rays_multi_async: null context or scene" in lib.rtr_last_error()
 
 
+def test_the_handles_come_before_every_other_fault():
+    lib = A.hip_lib()
+    odd = A.VP(0x1002)                        # maxHits 0, RTR_QUERY_ANY, a cull mask above 8 bits, null and misaligned arrays beside the null handles
+    assert lib.rtr_trace_rays_multi(None, None, None, None, 64, 0, 1, 0x100, odd, odd, odd, None) == -1
+    assert lib.rtr_last_error() == b"rtr_trace_rays_multi: null context or scene"
+    assert lib.rtr_trace_rays_multi_async(None, None, None, None, 64, 0, 1, 0x100, odd, odd, odd) == -1
+    assert lib.rtr_last_error() == b"rtr_trace_rays_multi_async: null context or scene"
+
+
 def test_python_signature_defaults_and_value_errors():
     sig = inspect.signature(api.trace_rays_multi)
     assert list(sig.parameters) == ["scene", "rays", "max_hits", "after", "opaque", "ray_flags", "cull_mask", "ray_masks", "collect_stats", "ctx",

@@ -83,6 +83,32 @@ def test_argument_errors_that_need_no_device():
     assert b"rtr_trace_occlusion_hinted: null context or scene" in err(), err()
 
 
+def test_which_refusal_wins_under_two_faults():
+    """rtr_hit_leaves checks its arrays before the handles, every null before any misaligned pointer; the hinted calls check their own
+    array first, then the handles, and only then the other arrays"""
+    lib = A.hip_lib()
+    err = lib.rtr_last_error
+    fake, odd16, odd4 = A.VP(0x1000), A.VP(0x1008), A.VP(0x1002)
+    p = api.make_light_params(1, 3, 0, 8, 1)
+    for name in ("rtr_hit_leaves", "rtr_hit_leaves_async"):
+        fn, who = getattr(lib, name), name.encode() + b": "
+        assert fn(None, None, odd16, 64, None) == INVALID and err().startswith(who + b"leaves is null"), err()
+        assert fn(None, None, None, 64, None) == INVALID and err().startswith(who + b"hits is null"), err()
+        assert fn(None, None, odd16, 64, odd4) == INVALID and err().startswith(who + b"hits is not 16-B aligned"), err()
+        assert fn(None, None, None, 0, None) == INVALID and err().startswith(who + b"null context or scene"), err()
+    for name in ("rtr_light_rays_hinted", "rtr_light_rays_hinted_async"):
+        fn, who = getattr(lib, name), name.encode() + b": "
+        assert fn(None, None, None, odd16, 64, None, odd4, None, None) == INVALID and err().startswith(who + b"outLeaves is null"), err()
+        assert fn(None, None, None, odd16, 64, None, odd4, None, odd4) == INVALID and err().startswith(who + b"outLeaves is not 4-B aligned"), err()
+        assert fn(None, None, None, odd16, 64, C.byref(p), odd4, None, fake) == INVALID and err().startswith(who + b"null context, scene or params"), err()
+        assert fn(None, None, None, None, 0, None, None, None, None) == INVALID and err().startswith(who + b"null context, scene or params"), err()
+    for name, tail in (("rtr_trace_occlusion_hinted", (None,)), ("rtr_trace_occlusion_hinted_async", ())):
+        fn, who = getattr(lib, name), name.encode() + b": "
+        assert fn(None, None, None, odd4, 64, 0x100, None, 0, odd16, *tail) == INVALID and err().startswith(who + b"startLeaves is not 4-B aligned"), err()
+        assert fn(None, None, None, fake, 64, 0x100, None, 0, odd16, *tail) == INVALID and err().startswith(who + b"null context or scene"), err()
+        assert fn(None, None, None, odd4, 0, 0x100, None, 0, odd16, *tail) == INVALID and err().startswith(who + b"null context or scene"), err()
+
+
 def test_direct_light_knows_the_own_leaf_route():
     with pytest.raises(ValueError, match="occlusion must be"):
         api.direct_light(None, None, occlusion="sparse")

@@ -157,6 +157,70 @@ def test_refusals_by_message(name):
         assert not buf.any()             # nothing was written
 
 
+@pytest.mark.parametrize("name", NEW[:4])
+def test_which_refusal_wins_under_two_faults(name):
+    """the light params, the pick params, the light params' values, numHits x R, every null before any misaligned pointer in the
+    argument order, the pixel-seed rule, and only then the handles"""
+    lib = A.hip_lib()
+    call = _entry(lib, name)
+    shade = "shade" in name
+    last, last_name = ("out", "out") if shade else ("out_slots", "outSlots")
+
+    def wins(needle, status=INVALID, c=None, **kw):
+        c = c or Call()
+        assert call(c, **kw) == status, needle
+        msg = lib.rtr_last_error().decode()
+        assert msg.startswith(f"{name}: {needle}"), f"expected '{name}: {needle}', got '{msg}'"
+
+    c = Call()
+    wins(f"{last_name} is null", rays=Call.ptr(c.rays, 2), **{last: None})
+    wins("rays is null", rays=None, hits=None)
+    wins("hits is not 16-B aligned", hits=Call.ptr(c.hits, 2), seeds=Call.ptr(c.seeds, 2))
+    wins("seeds is not 4-B aligned", seeds=Call.ptr(c.seeds, 2), slots=Call.ptr(c.slots, 2))
+    wins("params is null", light=None, pick=None)
+    wins("pick params is null", pick=None, rays=None)
+    c = Call()
+    c.pick.numPicks, c.pick._reserved[0], c.light.numShadowRays = 0, 1, 0
+    wins("numPicks 0 (1 ... 30)", c=c)
+    c = Call()
+    c.pick._reserved[3], c.light.numShadowRays, c.light.outputs = 1, 0, 8
+    wins("_reserved words of pick params are not 0", c=c)
+    c = Call()
+    c.light.numShadowRays, c.light.outputs = 0, 8 | A.LIGHT_ANALYTIC
+    wins("numShadowRays 0 (1 ... 1024)", c=c, rays=None)
+    c = Call()
+    c.light.outputs = 8 | A.LIGHT_ANALYTIC
+    wins("unknown output bits 0xc", c=c, n=0x60000000)
+    wins("1610612736 hits x 3 slots do not fit 32 bits", n=0x60000000, rays=None)
+    c = Call()
+    c.light.width = 0
+    wins("rays is not 16-B aligned", c=c, rays=Call.ptr(c.rays, 2))
+    c = Call()
+    c.light.width = 0
+    wins("width 0, spp 1", c=c)                  # before the handles, which are null throughout
+
+
+def test_host_pick_slots_under_two_faults():
+    lib = A.hip_lib()
+    seeds, out = np.zeros(N + 1, np.uint32), np.zeros(2 * N + 1, np.uint32)
+    pick = api.make_pick_params(2)
+    p = Call.ptr
+
+    def wins(needle, seeds_p=p(seeds), n=N, width=2, spp=1, pick_p=C.byref(pick), area=6, out_p=p(out)):
+        assert lib.rtr_host_pick_slots(seeds_p, n, 0, width, spp, pick_p, area, out_p) == INVALID, needle
+        msg = lib.rtr_last_error().decode()
+        assert msg.startswith("rtr_host_pick_slots: " + needle), msg
+
+    wins("pick params is null", pick_p=None, area=(1 << 24) + 1)
+    wins("16777217 area slots", area=(1 << 24) + 1, n=0, out_p=None)
+    wins("4294967295 hits x 2 picks do not fit 32 bits", n=0xffffffff, out_p=None)
+    wins("outSlots is null", out_p=None, seeds_p=p(seeds, 2))
+    wins("outSlots is not 4-B aligned", out_p=p(out, 2), seeds_p=p(seeds, 2))
+    wins("seeds is not 4-B aligned", seeds_p=p(seeds, 2), width=0)
+    wins("width 0, spp 0", seeds_p=None, width=0, spp=0)
+    assert not out.any()
+
+
 def test_the_python_signatures():
     sig = inspect.signature(api.make_pick_params).parameters
     assert [(k, sig[k].default) for k in sig] == [("picks", 1), ("depth", 0)]

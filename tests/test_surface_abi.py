@@ -52,3 +52,10 @@ def test_arguments_are_checked_before_any_device_is_touched():
     assert lib.rtr_hit_surfaces_async(None, None, None, None, 1, None) == -1
     assert b"null" in lib.rtr_last_error()
     assert lib.rtr_hit_surfaces(None, None, None, None, 0, None) == -1
+
+
+def test_the_handles_come_before_the_arrays():
+    lib = A.hip_lib()
+    for name in NEW:                          # a null and a misaligned array beside the null handles: the handles' message wins
+        assert getattr(lib, name)(None, None, None, A.VP(0x1008), 4, A.VP(0x1004)) == -1
+        assert lib.rtr_last_error() == name.encode() + b": null context or scene"

@@ -53,7 +53,8 @@ class World:
             self.refs[key] = out
         return self.refs[key]
 
-    def check(self, mode, shadow_rays=SHADOW_RAYS, spps=(1, 2)):
+    def check(self, mode, shadow_rays=SHADOW_RAYS, spps=(1, 2), all_sky=False):
+        """all_sky: no sample of the frame hits anything, so it sends no shadow ray at all (and the queue build runs on an empty queue)"""
         binned, compact, pipeline = MODES[mode]
         W, H = self.s.width, self.s.height
         c = api.Context(0)
@@ -74,7 +75,7 @@ class World:
                         g = forms[1][1].stats()
                         for fld in COUNTERS:
                             assert getattr(g, fld) == getattr(stats, fld), f"{what}: counter {fld}: gpu {getattr(g, fld)} != oracle {getattr(stats, fld)}"
-                        assert stats.numShadowRays > 0
+                        assert (stats.numShadowRays > 0) != all_sky and (stats.numHits > 0) != all_sky
             for _, frame in forms:
                 frame.close()
         finally:
@@ -100,6 +101,21 @@ def test_cornell_parked_pairs_change_nothing(worlds, mode, size):
     """64x64: whole tiles; 70x50: the last tile column and row are partial, so workgroups hold lanes without a pixel, which neither draw
     pairs nor park a surface nor read either back."""
     worlds("cornell", *size).check(mode)
+
+
+FRAME_EDGES = [(1, 1), (1, 9), (9, 1), (7, 7), (8, 8), (9, 9), (65, 3), (3, 65)]
+# a frame of one row spans the 40 degrees of the field of view with one pixel, whose jitter (a function of the pixel's column alone)
+# throws every sample of these two frames above or below the box: they are all sky, in every frame and sample plane drawn here
+ALL_SKY = {(1, 1), (9, 1)}
+
+
+@pytest.mark.parametrize("size", FRAME_EDGES, ids=[f"{w}x{h}" for w, h in FRAME_EDGES])
+@pytest.mark.parametrize("mode", list(MODES))
+def test_cornell_frame_shape_edges(worlds, mode, size):
+    """Frames around the 8x8 tile: a single pixel, one tile column or row with one more pixel, a tile less one pixel each way, a tile, a
+    tile and one pixel each way, nine tile columns of three rows and the transpose — the last tile of a row or column holds 1 .. 8 pixels
+    each way, and the frame holds fewer pixels than a workgroup, a wave or a batch; two of them send no shadow ray at all."""
+    worlds("cornell", *size).check(mode, shadow_rays=(3, K + 1), spps=(1, 2), all_sky=size in ALL_SKY)
 
 
 def _culling_lights_box(directory, width, height):

@@ -25,6 +25,8 @@ namespace rtrdev {
 struct DeviceTexture { const uint8_t* pixels; uint32_t width, height, channels, _pad; };
 
 constexpr uint32_t kLightTriRecord = 4;     /* float4s per light-triangle record */
+constexpr uint32_t kObjectTermsRecord = 4;  /* float4s per object-terms record: {linear colour, roughness} {mDiffuse, metallic} {mSpecular, 1 - metallic} {diffuse / pi, flag}; flag (an
+                                             * integer word): 1 iff the object has no colour, specular or metallic map, so that the record is its surface's material */
 
 struct DeviceScene {
     const uint4* nodes;              /* RtrBvhNode (layout version 3) as 2 x uint4 */
@@ -35,6 +37,7 @@ struct DeviceScene {
     const RtrVertex* vertices;
     const uint32_t* indices;
     const RtrObjectInfo* objects;
+    const float4* objectTerms;       /* per object, kObjectTermsRecord x float4: what its material alone decides of a surface (k_object_terms, made once with the scene: no call rewrites objects) */
     const RtrAreaLightInfo* lights;
     const float4* lightTris;         /* per light triangle, kLightTriRecord x float4: {P0, area} {P1, pdf} {P2, -} {unit normal, -} in world space (k_light_tris) */
     const uint32_t* lightTriFirst;   /* first record of light l */
@@ -379,10 +382,14 @@ __device__ __forceinline__ float GGX_Distribution(rtr_v3 n, rtr_v3 h, float alph
 }
 __device__ __forceinline__ float GGX_PartialGeometryTerm(rtr_v3 v, rtr_v3 n, rtr_v3 h, float alpha) {
     float VoH2 = rtr_clamp(rtr_dot(v, h), 0.001f, 1.0f);
-    const float chi = chiGGX(VoH2 / rtr_clamp(rtr_dot(v, n), 0.001f, 1.0f));
+    /* The reference's chi = chiGGX(VoH2 / clamp(dot(v, n), 0.001, 1)) is 1.0f for every input, so neither the quotient nor dot(v, n) is
+     * formed: rtr_clamp is select-form (m = x > lo ? x : lo; m < hi ? m : hi) and a NaN operand fails the first test and comes out as lo, so numerator
+     * and denominator both lie in [0.001, 1]; the IEEE quotient of two such floats lies in [0.001, 1000] — 0.001f / 1.0f is 0.001f,
+     * 1.0f / 0.001f is finite, nothing underflows to 0 or turns NaN — and chiGGX of a positive number is 1.  chi * 2.0f is 2.0f.  The
+     * oracle keeps dividing; the bits are the same (tests/test_ggx_chi_constant.py walks the corners in float32). */
     VoH2 = VoH2 * VoH2;
     const float tan2 = (1.0f - VoH2) / VoH2;
-    return (chi * 2.0f) / (1.0f + rtr_sqrt(rtr_fma(alpha * alpha, tan2, 1.0f)));
+    return 2.0f / (1.0f + rtr_sqrt(rtr_fma(alpha * alpha, tan2, 1.0f)));
 }
 __device__ __forceinline__ rtr_v3 Fresnel_Schlick(float cosT, rtr_v3 F0) {
     const float p = rtr_pow(1.0f - cosT, 5.0f);
@@ -502,9 +509,39 @@ struct Accum { rtr_v3 analytic, shadowed, unshadowed, avgNormal, avgPosition; };
 /* What the light loops need to know about a primary hit: closesthit.rchit:53-106 + raygen.rgen:123-163. */
 struct Surface {
     rtr_v3 hitPoint, hitNormal, viewDir, color, mDiffuse, mSpecular;
+    rtr_v3 diffuse;           /* currDiffuse of the light loops: (om * color) / pi per channel */
     float roughness, metallic, om;
     float4 t1, t2;
 };
+
+/* What the material decides of a surface point once colour (linear) and metallic are known (closesthit.rchit:96-106, raygen.rgen:244):
+ * the ONE place these are formed — for a pixel whose object has a map (fetch_surface) and, per object, for the table the others read
+ * (k_object_terms), so that a table entry holds the bits a pixel would compute.  diffuse = (om * color) / pi per channel. */
+__device__ __forceinline__ rtr_v3 surface_diffuse(float om, rtr_v3 color) {
+    return rtr_mk((om * color.x) / RTR_PI_F, (om * color.y) / RTR_PI_F, (om * color.z) / RTR_PI_F);
+}
+__device__ __forceinline__ void material_terms(rtr_v3 color, float metallic, float om, rtr_v3& mDiffuse, rtr_v3& mSpecular, rtr_v3& diffuse) {
+    mDiffuse = rtr_scale(color, om);
+    mSpecular = rtr_mk(rtr_fma(color.x, metallic, 0.04f * om), rtr_fma(color.y, metallic, 0.04f * om),
+                       rtr_fma(color.z, metallic, 0.04f * om));
+    diffuse = surface_diffuse(om, color);
+}
+/* An object's record of the terms table (DeviceScene::objectTerms, kObjectTermsRecord): fetch_surface's material code for an object
+ * without maps, run once per object instead of once per pixel-sample. */
+__device__ __forceinline__ void object_terms_record(const RtrObjectInfo* oi, float4* rec) {
+    const rtr_v3 col = rtr_ld3(oi->color);
+    const rtr_v3 color = rtr_mk(rtr_to_linear(col.x), rtr_to_linear(col.y), rtr_to_linear(col.z));
+    const float metallic = oi->metallic;
+    const float roughness = 1.0f - oi->specular;
+    const float om = 1.0f - metallic;
+    rtr_v3 mDiffuse, mSpecular, diffuse;
+    material_terms(color, metallic, om, mDiffuse, mSpecular, diffuse);
+    const uint32_t plain = (oi->usesColorMap | oi->usesSpecularMap | oi->usesMetallicMap) == 0u ? 1u : 0u;
+    rec[0] = make_float4(color.x, color.y, color.z, roughness);
+    rec[1] = make_float4(mDiffuse.x, mDiffuse.y, mDiffuse.z, metallic);
+    rec[2] = make_float4(mSpecular.x, mSpecular.y, mSpecular.z, om);
+    rec[3] = make_float4(diffuse.x, diffuse.y, diffuse.z, __uint_as_float(plain));
+}
 
 /* Miss / light-hit handling (raygen.rgen:110-121, miss.rmiss:15-27) and the surface fetch.  Returns false when the
  * sample is finished (miss or light).  SHADE == false (shadow-ray generator) skips material and colour work but
@@ -563,31 +600,44 @@ __device__ __forceinline__ bool fetch_surface(const DeviceScene& sc, const Rende
     }
     float metallic = oi->metallic;
     float rough = oi->specular;
-    rtr_v3 color = rtr_mk(0, 0, 0);
+    rtr_v3 color = rtr_mk(0, 0, 0), mDiffuse = rtr_mk(0, 0, 0), mSpecular = rtr_mk(0, 0, 0), diffuse = rtr_mk(0, 0, 0);
+    float roughness = 0.0f, om = 0.0f;
+    bool tabled = false;
     if (SHADE) {
-        rtr_v3 col = rtr_ld3(oi->color);
-        if (oi->usesColorMap | oi->usesSpecularMap | oi->usesMetallicMap) {
+        /* An object without maps: colour -> linear (three pow), mDiffuse, mSpecular and the diffuse term over pi (three divisions) are
+         * functions of its RtrObjectInfo alone — k_object_terms formed them once, with the code of the other branch, and the record is
+         * read in whole 16-B pieces.  The flag is per object: nearly always the same for all lanes of a tile. */
+        const float4* ot = sc.objectTerms + (size_t)kObjectTermsRecord * (h.custom - sc.numLights);
+        const float4 m3 = ot[3];
+        tabled = __float_as_uint(m3.w) != 0u;
+        if (tabled) {
+            const float4 m0 = ot[0], m1 = ot[1], m2 = ot[2];
+            color = rtr_mk(m0.x, m0.y, m0.z); roughness = m0.w;
+            mDiffuse = rtr_mk(m1.x, m1.y, m1.z); metallic = m1.w;
+            mSpecular = rtr_mk(m2.x, m2.y, m2.z); om = m2.w;
+            diffuse = rtr_mk(m3.x, m3.y, m3.z);
+        } else {
+            rtr_v3 col = rtr_ld3(oi->color);
             const float4 ta = va[2], tb = vb[2], tc = vc[2];                             /* uv in floats 8,9 of the 48-B vertex */
             const float uu = rtr_fma(tc.x, b2, rtr_fma(tb.x, b1, ta.x * b0));
             const float vv = rtr_fma(tc.y, b2, rtr_fma(tb.y, b1, ta.y * b0));
             if (oi->usesColorMap != 0u) { const float4 t = sample_tex<STATS>(sc.textures[oi->colorIndex], uu, vv, st); col = rtr_mk(t.x, t.y, t.z); }
             if (oi->usesSpecularMap != 0u) rough = sample_tex<STATS>(sc.textures[oi->specularIndex], uu, vv, st).x;
             if (oi->usesMetallicMap != 0u) metallic = sample_tex<STATS>(sc.textures[oi->metallicIndex], uu, vv, st).x;
+            color = rtr_mk(rtr_to_linear(col.x), rtr_to_linear(col.y), rtr_to_linear(col.z));
         }
-        color = rtr_mk(rtr_to_linear(col.x), rtr_to_linear(col.y), rtr_to_linear(col.z));
     }
-    const float roughness = 1.0f - rough;
+    if (!tabled) {
+        roughness = 1.0f - rough;
+        om = 1.0f - metallic;
+        if (SHADE) material_terms(color, metallic, om, mDiffuse, mSpecular, diffuse);
+    }
 
     const rtr_v3 viewDir = rtr_normalize(rtr_sub(camPos, hitPoint));
-    const float om = 1.0f - metallic;
-    rtr_v3 mDiffuse = rtr_mk(0, 0, 0), mSpecular = rtr_mk(0, 0, 0);
     float4 t1 = make_float4(1, 0, 0, 1), t2 = make_float4(0, 0, 0, 0);
     if (SHADE) {
         o.avgNormal = rtr_add(o.avgNormal, hitNormal);
         o.avgPosition = rtr_add(o.avgPosition, hitPoint);
-        mDiffuse = rtr_scale(color, om);
-        mSpecular = rtr_mk(rtr_fma(color.x, metallic, 0.04f * om), rtr_fma(color.y, metallic, 0.04f * om),
-                           rtr_fma(color.z, metallic, 0.04f * om));
         if (wantAnalytic) {
             const float dotNV = rtr_clamp(rtr_dot(hitNormal, viewDir), 0.0f, 1.0f);
             const float lu = rtr_fma(roughness, RTR_LUT_SCALE, RTR_LUT_BIAS);
@@ -597,7 +647,7 @@ __device__ __forceinline__ bool fetch_surface(const DeviceScene& sc, const Rende
         }
     }
     sf.hitPoint = hitPoint; sf.hitNormal = hitNormal; sf.viewDir = viewDir; sf.color = color;
-    sf.mDiffuse = mDiffuse; sf.mSpecular = mSpecular; sf.roughness = roughness; sf.metallic = metallic; sf.om = om;
+    sf.mDiffuse = mDiffuse; sf.mSpecular = mSpecular; sf.diffuse = diffuse; sf.roughness = roughness; sf.metallic = metallic; sf.om = om;
     sf.t1 = t1; sf.t2 = t2;
     return true;
 }
@@ -605,10 +655,7 @@ __device__ __forceinline__ bool fetch_surface(const DeviceScene& sc, const Rende
 /* One area-light sample's BRDF * L / pdf (raygen.rgen:244-267) and the directional light's BRDF * L (raygen.rgen:316-336): the
  * arithmetic of the light loops, as functions of what a sample needs of its surface point — so that the per-pixel loops (light_loops)
  * and the compacted form of k_resolve_compact (one lane per VISIBLE sample, whichever pixel it belongs to) run the same operations in
- * the same order.  currDiffuse = (om * color) / pi per channel, formed once per surface point. */
-__device__ __forceinline__ rtr_v3 surface_diffuse(float om, rtr_v3 color) {
-    return rtr_mk((om * color.x) / RTR_PI_F, (om * color.y) / RTR_PI_F, (om * color.z) / RTR_PI_F);
-}
+ * the same order.  currDiffuse = (om * color) / pi per channel is the surface's (Surface::diffuse: surface_diffuse above). */
 __device__ __forceinline__ rtr_v3 area_sample_contrib(rtr_v3 hitNormal, rtr_v3 viewDir, float roughness, rtr_v3 mSpecular, rtr_v3 currDiffuse,
                                                       rtr_v3 lcol, float lintensity, float pdf, rtr_v3 sampledLightDir, float lightDistance) {
     const rtr_v3 halfVector = rtr_normalize(rtr_add(viewDir, sampledLightDir));
@@ -692,12 +739,12 @@ __device__ __forceinline__ void light_loops_from(const DeviceScene& sc, const Re
      * reference (and the oracle) evaluate it and multiply by 0: identical whenever contrib is finite; an occluded sample whose
      * contrib overflows poisons the reference's pixel (0 * inf = NaN) and not this one — divergence D6, DESIGN.md §4. */
     const bool wantAnalytic = (want & 1u) != 0u, wantUnshadowed = (want & 2u) != 0u;
-    const rtr_v3 hitPoint = sf.hitPoint, hitNormal = sf.hitNormal, viewDir = sf.viewDir, color = sf.color;
+    const rtr_v3 hitPoint = sf.hitPoint, hitNormal = sf.hitNormal, viewDir = sf.viewDir;
     const rtr_v3 mDiffuse = sf.mDiffuse, mSpecular = sf.mSpecular;
-    const float roughness = sf.roughness, om = sf.om;
+    const float roughness = sf.roughness;
     const float4 t1 = sf.t1, t2 = sf.t2;
     const rtr_v3 shadowOrigin = rtr_madd(hitPoint, hitNormal, 0.01f);
-    const rtr_v3 currDiffuse = surface_diffuse(om, color);
+    const rtr_v3 currDiffuse = sf.diffuse;
 
     for (uint32_t li = 0; li < ra.info.numAreaLights; ++li) {                             /* :165 */
         const RtrAreaLightInfo* L = sc.lights + li;

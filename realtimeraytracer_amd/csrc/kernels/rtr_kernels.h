@@ -154,6 +154,11 @@ hipError_t launch_occlusion_walk(const DeviceScene& sc, const OcclusionArgs& oa,
 /* fills DeviceScene::lightTris (4 x float4 per light triangle, light l from first[l]); after create and after light transforms change */
 hipError_t launch_light_tris(const RtrAreaLightInfo* lights, const RtrVertex* vertices, const uint32_t* indices, const uint32_t* first,
                              uint32_t numLights, float4* out, hipStream_t stream);
+/* the per-object material terms (DeviceScene::objectTerms): kObjectTermsRecord float4 per object */
+hipError_t launch_object_terms(const RtrObjectInfo* objects, uint32_t numObjects, float4* out, hipStream_t stream);
+/* what the loaded code object says of the binned queue build (k_shadow_gen_oct<single>): registers, LDS, private segment.  For the test
+ * build's rtr_test_gen_oct_attributes; nothing of the product calls it. */
+hipError_t gen_oct_attributes(bool single, hipFuncAttributes* out);
 hipError_t launch_deinterleave(const uint32_t* gathered, uint32_t* dst, uint32_t width, uint32_t height,
                                uint32_t bandRows, uint32_t shardCount, uint32_t localRows, hipStream_t stream);
 

@@ -555,33 +555,33 @@ constexpr uint32_t kParkSurface = 6, kParkWords = kParkSurface + 2u * kParkedPai
  * 13 dwords spilled) 0.148 (profiles/r04/ab_tri2_gen_waves.log).  Round 5: with the into-the-surface mark of every ray (a dot product and
  * a bit per sample) the cap of 64 spilled 31 dwords and cost 0.010 ms; at 72 (7 waves) the kernel is back at 0.151 (profiles/r05/ab_gen_into.log).
  * With the sample pairs and the surface parked in LDS (ParkedSamples, s_park) the kernel takes 68 VGPRs under the cap of 72 and spills nothing
- * (before: 18 dwords, 68 bytes of scratch per lane): 0.158 -> 0.142 ms per frame in ten-frame launches.  Capped at 64 it still spills one dword,
- * in the emit pass of spp > 1, and measured 0.133 in the same session (profiles/gen_samples_once/ab.log): the next step once that dword is gone;
- * a kernel with a private segment is not what this one is meant to be, so 7 stays. */
+ * (before: 18 dwords, 68 bytes of scratch per lane): 0.158 -> 0.142 ms per frame in ten-frame launches.  Capped at 64 it still spilled one dword,
+ * in the emit pass of spp > 1 (profiles/gen_samples_once/ab.log), and a kernel with a private segment is not what this one is meant to be.
+ * So spp == 1 is a compile-time property: k_shadow_gen_oct<true> has no second surface fetch and no primary_dir in its emit pass, fits 64
+ * VGPRs with no spill and no private segment and runs at eight waves per SIMD (tests/test_gpu_gen_oct_scratch.py holds it to that);
+ * k_shadow_gen_oct<false>, spp > 1, keeps the cap of RTR_GEN_OCT_WAVES = 7 (profiles/gen_eight_waves_object_terms/ab.log). */
 #ifndef RTR_GEN_OCT_WAVES
 #define RTR_GEN_OCT_WAVES 7
 #endif
-#if RTR_GEN_OCT_WAVES > 0
-#define RTR_GEN_OCT_ATTR __attribute__((amdgpu_waves_per_eu(RTR_GEN_OCT_WAVES, 8)))
-#else
-#define RTR_GEN_OCT_ATTR
-#endif
-__global__ __launch_bounds__(kGenOctBlock) RTR_GEN_OCT_ATTR void k_shadow_gen_oct(DeviceScene sc, FrameBatch fb, const float4* hitTuvp, const uint32_t* hitCustom,
-                                                              RayQueue queue, uint32_t* ctrl, uint32_t planeStride, uint2* lists,
-                                                              uint32_t listStride, uint32_t kBatch, uint32_t nt) {
+template <bool SINGLE>
+__global__ __launch_bounds__(kGenOctBlock) __attribute__((amdgpu_waves_per_eu(SINGLE ? 8 : RTR_GEN_OCT_WAVES, 8)))
+void k_shadow_gen_oct(DeviceScene sc, FrameBatch fb, const float4* hitTuvp, const uint32_t* hitCustom,
+                      RayQueue queue, uint32_t* ctrl, uint32_t planeStride, uint2* lists,
+                      uint32_t listStride, uint32_t kBatch, uint32_t nt) {
     constexpr uint32_t kWaves = kGenOctBlock / 64;
     __shared__ uint32_t s_tot[kWaves][8], s_run[kWaves][8];
     __shared__ uint32_t s_park[kParkWords * kGenOctBlock];      /* 28 KB at 512 threads: the three workgroups per CU of seven waves per SIMD take 84 of the CU's 160 KB, the four of eight waves 112 — LDS does not set the residency */
     uint32_t q;
     const uint32_t frame = batch_frame(blockIdx.x * kGenOctBlock + threadIdx.x, planeStride, q);
     const RenderArgs& ra = fb.ra[frame < fb.n ? frame : 0u];
-    const size_t plane0 = (size_t)frame * ra.spp;
+    const uint32_t spp = SINGLE ? 1u : ra.spp;         /* SINGLE: the launcher chose this instantiation because ra.spp == 1 */
+    const size_t plane0 = (size_t)frame * spp;
     const uint32_t wave = threadIdx.x >> 6;
     uint32_t px = 0, lrow = 0, py = 0;
     const bool live = frame < fb.n && pixel_of(ra, q, px, lrow, py);
     LocalStats st;
     Accum acc = zero_accum();
-    const bool single = ra.spp == 1u;                 /* (fetching the surface again in the emit phase instead of keeping it across the reservation: 74 VGPRs instead of 88, and slower — profiles/r04/ab_gen_refetch.log) */
+    constexpr bool single = SINGLE;                   /* (fetching the surface again in the emit phase instead of keeping it across the reservation: 74 VGPRs instead of 88, and slower — profiles/r04/ab_gen_refetch.log) */
     /* What the emit pass needs of the one sample's surface (spp == 1) crosses the reservation in LDS, in the lane's column of s_park
      * beside its sample pairs (ParkedSamples): hit point and normal, words 0-5; the pairs from word kParkSurface.  Kept in registers it
      * was spilled to scratch under this kernel's register cap — a vector-memory round trip on the chain the kernel already waits on. */
@@ -590,7 +590,7 @@ __global__ __launch_bounds__(kGenOctBlock) RTR_GEN_OCT_ATTR void k_shadow_gen_oc
     CountOctPolicy cp{0ull, 0ull};
     if (live) {
         smp.draw(ra.numShadowRays);
-        for (uint32_t i = 0; i < ra.spp; ++i) {
+        for (uint32_t i = 0; i < spp; ++i) {
             const size_t k = (plane0 + i) * planeStride + q;
             const float4 r = hitTuvp[k];
             HitRec h; h.t = r.x; h.u = r.y; h.v = r.z; h.prim = __float_as_uint(r.w); h.custom = hitCustom[k];
@@ -674,10 +674,10 @@ __global__ __launch_bounds__(kGenOctBlock) RTR_GEN_OCT_ATTR void k_shadow_gen_oc
     }
     __syncthreads();
     if (mine == 0) return;                 /* padding lanes, misses, light hits: a lane that counted a query is live, and with spp == 1 its one sample has a surface, parked above */
-    for (uint32_t i = 0; i < ra.spp; ++i) {
+    for (uint32_t i = 0; i < spp; ++i) {
         const size_t k = (plane0 + i) * planeStride + q;
         EmitOctPolicy pol{queue, (EmitOctPolicy::lds_word)&s_run[wave][0], (uint32_t)k, nt};
-        if (single) {
+        if constexpr (single) {
             Surface sf0 = {};              /* of it the emission reads hit point and normal only */
             sf0.hitPoint = rtr_mk(__uint_as_float(park[0u * kGenOctBlock]), __uint_as_float(park[1u * kGenOctBlock]), __uint_as_float(park[2u * kGenOctBlock]));
             sf0.hitNormal = rtr_mk(__uint_as_float(park[3u * kGenOctBlock]), __uint_as_float(park[4u * kGenOctBlock]), __uint_as_float(park[5u * kGenOctBlock]));
@@ -1778,7 +1778,7 @@ void k_resolve_compact(DeviceScene sc, FrameBatch fb, uint32_t planeStride, cons
         }
         wave_lds_sync();                                 /* the last sample's evaluation has read the surfaces */
         if (has) {
-            const rtr_v3 cd = surface_diffuse(sf.om, sf.color);
+            const rtr_v3 cd = sf.diffuse;
             s_surf[wave][0][lane] = make_float4(sf.hitPoint.x, sf.hitPoint.y, sf.hitPoint.z, sf.roughness);
             s_surf[wave][1][lane] = make_float4(sf.hitNormal.x, sf.hitNormal.y, sf.hitNormal.z, cd.x);
             s_surf[wave][2][lane] = make_float4(sf.viewDir.x, sf.viewDir.y, sf.viewDir.z, cd.y);
@@ -1915,6 +1915,13 @@ __global__ __launch_bounds__(64) void k_light_tris(const RtrAreaLightInfo* __res
     if (l >= numLights) return;
     const RtrAreaLightInfo* L = lights + l;
     for (uint32_t ti = 0; ti < L->numTriangles; ++ti) light_tri_record(L, vertices, indices, ti, out + (size_t)(first[l] + ti) * kLightTriRecord);
+}
+
+/* The per-object material terms fetch_surface<true> reads (DeviceScene::objectTerms), one lane per object: made once, when the scene is. */
+__global__ __launch_bounds__(64) void k_object_terms(const RtrObjectInfo* __restrict__ objects, uint32_t numObjects, float4* __restrict__ out) {
+    const uint32_t o = blockIdx.x * 64u + threadIdx.x;
+    if (o >= numObjects) return;
+    object_terms_record(objects + o, out + (size_t)o * kObjectTermsRecord);
 }
 
 /* Pre-fill of the visibility array: the first planeVec 16-B words of each plane (blockIdx.y), pitchVec words apart — and the launch's
@@ -2069,7 +2076,9 @@ static hipError_t wave_t(const DeviceScene& sc, const FrameBatch& fb, const Work
     const uint32_t kNtQueue = tun.queue_nt;          /* bit 0: any-hit kernel reads the queue past the caches (default); bit 1: the queue-build kernel writes it so (slower, see queue_load) */
     RayQueue rq = ws.rayQueue;
     rq.ownLeaf = (wide && tun.trace_own_leaf) ? 1u : 0u;          /* only the 4-wide any-hit kernel starts a walk at a leaf (the 2-wide comparison kernel takes the mark off) */
-    if (binned) hipLaunchKernelGGL(k_shadow_gen_oct, dim3(genOctBlocks), dim3(kGenOctBlock), 0, s, sc, fb, ws.hitTuvp, ws.hitCustom, rq, ws.queueCount, blocks * kBlock, ws.batchLists, ws.listStride, kBatch, kNtQueue >> 1);
+    /* spp (the same for every frame of the launch) picks the instantiation: one sample per pixel is the form at eight waves per SIMD */
+    if (binned && ra.spp == 1u) hipLaunchKernelGGL(k_shadow_gen_oct<true>, dim3(genOctBlocks), dim3(kGenOctBlock), 0, s, sc, fb, ws.hitTuvp, ws.hitCustom, rq, ws.queueCount, blocks * kBlock, ws.batchLists, ws.listStride, kBatch, kNtQueue >> 1);
+    else if (binned) hipLaunchKernelGGL(k_shadow_gen_oct<false>, dim3(genOctBlocks), dim3(kGenOctBlock), 0, s, sc, fb, ws.hitTuvp, ws.hitCustom, rq, ws.queueCount, blocks * kBlock, ws.batchLists, ws.listStride, kBatch, kNtQueue >> 1);
     else hipLaunchKernelGGL(k_shadow_gen, dim3(genBlocks), dim3(kGenBlock), 0, s, sc, fb, ws.hitTuvp, ws.hitCustom, rq, ws.queueCount, blocks * kBlock);
     if (ev) hipEventRecord(ev[2], s);
     /* persistent waves: as many workgroups as stay resident (17 KiB of LDS stack + 2.5 KiB of tree top per workgroup -> 8 per CU,
@@ -2178,6 +2187,17 @@ hipError_t launch_light_tris(const RtrAreaLightInfo* lights, const RtrVertex* ve
     if (numLights == 0) return hipSuccess;
     hipLaunchKernelGGL(k_light_tris, dim3((numLights + 63u) / 64u), dim3(64), 0, stream, lights, vertices, indices, first, numLights, out);
     return hipGetLastError();
+}
+
+hipError_t launch_object_terms(const RtrObjectInfo* objects, uint32_t numObjects, float4* out, hipStream_t stream) {
+    if (numObjects == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_object_terms, dim3((numObjects + 63u) / 64u), dim3(64), 0, stream, objects, numObjects, out);
+    return hipGetLastError();
+}
+
+hipError_t gen_oct_attributes(bool single, hipFuncAttributes* out) {
+    return single ? hipFuncGetAttributes(out, reinterpret_cast<const void*>(&k_shadow_gen_oct<true>))
+                  : hipFuncGetAttributes(out, reinterpret_cast<const void*>(&k_shadow_gen_oct<false>));
 }
 
 hipError_t launch_deinterleave(const uint32_t* gathered, uint32_t* dst, uint32_t width, uint32_t height,

@@ -668,7 +668,7 @@ __global__ __launch_bounds__(kShadeBlock) void k_shade_hits_picked(DeviceScene s
     Surface sf;
     LocalStats st;
     if (kind != RTR_SURFACE_INVALID && fetch_surface<true, false>(sc, ra, h, dir, false, acc, sf, st)) {
-        const rtr_v3 currDiffuse = surface_diffuse(sf.om, sf.color);
+        const rtr_v3 currDiffuse = sf.diffuse;
         const uint8_t* occ = la.occluded + (size_t)k * R;
         rtr_v3 sumShadowed = zero, sumUnshadowed = zero;
         for (uint32_t p = 0; p < P; ++p) {

@@ -198,7 +198,8 @@ struct rtr_scene {
     SceneTree tree;
     DevBuf<RtrVertex> vertices;
     DevBuf<uint32_t> indices;
-    DevBuf<RtrObjectInfo> objects;
+    DevBuf<RtrObjectInfo> objects;       /* written once, by rtr_scene_create: no update, refit or rebuild call touches it ... */
+    DevBuf<float4> objectTerms;          /* ... so the per-object material terms made from it (rtrdev::launch_object_terms) are made once too */
     DevBuf<RtrAreaLightInfo> lights;
     DevBuf<float4> lightTris;            /* 4 x float4 per light triangle (rtrdev::launch_light_tris) */
     DevBuf<uint32_t> lightTriFirst;      /* first record of light l */
@@ -640,6 +641,16 @@ static int make_light_tris(rtr_scene* s) {
     return RTR_OK;
 }
 
+/* computes the per-object material terms fetch_surface reads, on the device, from s->objects */
+static int make_object_terms(rtr_scene* s) {
+    if (s->numObjects == 0) return RTR_OK;
+    HIP_TRY(s->objectTerms.alloc((size_t)s->numObjects * rtrdev::kObjectTermsRecord));
+    hipError_t e = rtrdev::launch_object_terms(s->objects.p, s->numObjects, s->objectTerms.p, s->ctx->stream);
+    if (e != hipSuccess) return fail(RTR_ERR_HIP, "object terms: %s", hipGetErrorString(e));
+    HIP_TRY(hipStreamSynchronize(s->ctx->stream));     /* frames of other contexts may render this scene next */
+    return RTR_OK;
+}
+
 /* (re)builds the 4-wide view of the tree the any-hit kernel walks, on the device, from the quantised BVH2 nodes */
 static int make_wide_nodes(SceneTree& t, hipStream_t st) {
     const uint32_t n = (uint32_t)t.hostNodes.size();
@@ -857,11 +868,12 @@ static int scene_create_impl(rtr_ctx* ctx, const rtr_scene_desc* d, const rtr_sc
 
     rc = make_wide_nodes(tree, st);
     if (rc == RTR_OK) rc = make_light_tris(s);
+    if (rc == RTR_OK) rc = make_object_terms(s);
     if (rc != RTR_OK) { delete s; ctx_release_child(ctx); return rc; }
     DeviceScene& dv = s->dev;
     point_at_tree(dv, tree);
     dv.vertices = s->vertices.p; dv.indices = s->indices.p;
-    dv.objects = s->objects.p; dv.lights = s->lights.p;
+    dv.objects = s->objects.p; dv.objectTerms = s->objectTerms.p; dv.lights = s->lights.p;
     dv.lightTris = s->lightTris.p; dv.lightTriFirst = s->lightTriFirst.p;
     dv.xforms = s->xforms.p; dv.nmats = s->nmats.p;
     dv.ltc1 = s->hasLtc ? s->ltc1.p : nullptr; dv.ltc2 = s->hasLtc ? s->ltc2.p : nullptr;
@@ -2986,5 +2998,18 @@ int rtr_scene_export_light_tris(const rtr_scene* s, float* outRecords, uint32_t 
     if (outFirst) for (uint32_t l = 0; l < s->numLights; ++l) outFirst[l] = first[l];
     return RTR_OK;
 }
+
+#ifdef RTR_TEST_HOOKS
+/* librtr_hip_test.so only: what the loaded code object says of the binned queue build, k_shadow_gen_oct<single> (spp == 1) or <false> —
+ * out[0] VGPRs, out[1] private-segment bytes per lane, out[2] static LDS bytes, out[3] the launch bound.  Register and scratch figures
+ * only: the spp == 1 form is meant to have no private segment at its eight waves per SIMD (tests/test_gpu_gen_oct_scratch.py). */
+int rtr_test_gen_oct_attributes(int single, uint32_t out[4]) {
+    if (!out) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_test_gen_oct_attributes: null output");
+    hipFuncAttributes a{};
+    HIP_TRY(rtrdev::gen_oct_attributes(single != 0, &a));
+    out[0] = (uint32_t)a.numRegs; out[1] = (uint32_t)a.localSizeBytes; out[2] = (uint32_t)a.sharedSizeBytes; out[3] = (uint32_t)a.maxThreadsPerBlock;
+    return RTR_OK;
+}
+#endif
 
 }  // extern "C"

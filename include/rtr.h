@@ -1070,6 +1070,64 @@ int  rtr_host_emitter_hits(const RtrRay* rays, const RtrHit* hits, const RtrSurf
                            const float* lightTris, const uint32_t* lightTriFirst, const RtrAreaLightInfo* lights, uint32_t numLights,
                            const rtr_mis_params* mis, RtrEmitter* out);
 
+/* ---- sky importance sampling at a path vertex: directions drawn in proportion to the sky, under the balance heuristic ------------------
+ * Without these calls the sky reaches a path vertex only when its bounce ray happens to miss the scene.  rtr_sky_rays draws S directions
+ * per vertex in proportion to the scene's SKY TABLE — a piecewise-constant importance function over the HDRI's texel cells (or over a
+ * 32 x 16 grid for the constant sky), held as integer prefix sums — and gives each its shadow ray and its contribution; rtr_shade_sky
+ * sums the contributions the occlusion query let through; rtr_sky_hits gives what the vertex's bounce ray adds when it misses.  The rule
+ * is include/rtr_sky.h (rtr_sky_params, RtrSkySample, RtrSkyEscape, rtr_sky_table: include/rtr_types.h); DESIGN.md section 3 has the
+ * estimator and the table.
+ *
+ * rtr_scene_prepare_sky: builds the table on the device from the HDRI the scene holds, 4 B per texel and 8 B per row.  SYNCHRONOUS: it
+ * allocates and joins, once per scene (a second call does nothing).  The first rtr_sky_rays / rtr_sky_hits / export of a scene builds
+ * the table the same way, so only a caller that wants a chain without allocation or join has to call this first.  The HDRI and the sky
+ * colour cannot change after rtr_scene_create, so no refit, rebuild, vertex or instance update touches the table.  Refused: an HDRI wider
+ * than 65535 texels (a row's sum would not fit 32 bits).
+ * rtr_scene_export_sky_table: *outWidth, *outHeight of the table; with capacities of at least width * height and height, the row sums and
+ * the marginal sums to HOST pointers; smaller capacities (or NULL arrays) copy nothing, report the extent and are refused with
+ * RTR_ERR_INVALID_ARGUMENT.  Joins and copies.
+ * rtr_host_sky_table: the same table built on the host from a texture (NULL: the constant sky of skyColor, sRGB-encoded as
+ * rtr_scene_desc's), with the same capacity rule.  The device's words equal the host's, all of them.
+ *
+ * rtr_sky_rays: for hit k (found by rays[k], surface surfaces[k]: rtr_hit_surfaces') and sample j < S, outRays[k * S + j] and
+ * outSamples[k * S + j]; every slot of every hit is written, a dead sample as the null ray and 32 zero bytes.  seeds: one word per hit,
+ * or NULL for the pixel rule (params->width, params->spp).
+ * rtr_shade_sky: out[4k ... 4k + 2] = the sum over j, in order, of samples[k * S + j].contrib where occluded[k * S + j] == 0 (the bytes
+ * an RTR_QUERY_ANY query of outRays wrote), out[4k + 3] = 0.  16 B per hit.
+ * rtr_sky_hits: out[k] for bounce ray rays[k] with closest hit hits[k], having left the vertex whose RtrSurface is prevSurfaces[k] and
+ * whose RtrBounce is bounces[k] — read only where the hit is a miss; 32 zero bytes for every hit that is not a miss.  params->numSamples
+ * may be 0 here (the vertex drew no sky sample: wBounce = 1).
+ * The _async forms are ENQUEUED on ctx's stream: on a prepared scene no allocation, no join, no copy back.  The plain forms then join
+ * that stream (only that stream).  Refused before anything is written (RTR_ERR_INVALID_ARGUMENT, the message names the function and the
+ * argument): a null or misaligned pointer, numSamples 0 (rtr_sky_rays, rtr_shade_sky) or above RTR_SKY_MAX_SAMPLES, lobes 0 or unknown,
+ * unknown flag bits, a non-zero _reserved word, width or spp 0 with seeds == NULL, numHits * S past 32 bits, an output that overlaps an
+ * input or another output, a scene on another device. */
+int  rtr_scene_prepare_sky(rtr_scene* scene);
+int  rtr_scene_export_sky_table(const rtr_scene* scene, uint32_t* outWidth, uint32_t* outHeight, uint32_t* outRows, size_t capacityCells,
+                                uint64_t* outMarginal, uint32_t capacityRows);
+int  rtr_sky_rays_async(rtr_ctx* ctx, const rtr_scene* scene, const RtrRay* rays, const RtrSurface* surfaces, uint32_t numHits,
+                        const rtr_sky_params* params, const uint32_t* seeds, RtrRay* outRays, RtrSkySample* outSamples);
+int  rtr_shade_sky_async(rtr_ctx* ctx, const RtrSkySample* samples, const uint8_t* occluded, uint32_t numHits, uint32_t numSamples, float* out);
+int  rtr_sky_hits_async(rtr_ctx* ctx, const rtr_scene* scene, const RtrRay* rays, const RtrHit* hits, const RtrSurface* prevSurfaces,
+                        const RtrBounce* bounces, uint32_t numRays, const rtr_sky_params* params, RtrSkyEscape* out);
+int  rtr_sky_rays(rtr_ctx* ctx, const rtr_scene* scene, const RtrRay* rays, const RtrSurface* surfaces, uint32_t numHits,
+                  const rtr_sky_params* params, const uint32_t* seeds, RtrRay* outRays, RtrSkySample* outSamples);
+int  rtr_shade_sky(rtr_ctx* ctx, const RtrSkySample* samples, const uint8_t* occluded, uint32_t numHits, uint32_t numSamples, float* out);
+int  rtr_sky_hits(rtr_ctx* ctx, const rtr_scene* scene, const RtrRay* rays, const RtrHit* hits, const RtrSurface* prevSurfaces,
+                  const RtrBounce* bounces, uint32_t numRays, const rtr_sky_params* params, RtrSkyEscape* out);
+/* The host forms of include/rtr_sky.h in plain loops, HOST pointers, no device; the device's words equal these.  hdri: the sky's texture
+ * or NULL for the constant sky of skyColor (three floats, sRGB-encoded); table: rtr_host_sky_table's (or an exported one) of that sky.
+ * rtr_host_sky_pdf: outPdf[k] = the solid-angle density of the table for direction dirs[3k ... 3k + 2] (it need not be normalised).
+ * rtr_host_sky_radiance: out[3k ... 3k + 2] = the miss rule's radiance for that direction: RtrSurface::color of a miss, bit for bit. */
+int  rtr_host_sky_table(const rtr_texture* hdri, const float* skyColor, uint32_t* outWidth, uint32_t* outHeight, uint32_t* outRows,
+                        size_t capacityCells, uint64_t* outMarginal, uint32_t capacityRows);
+int  rtr_host_sky_rays(const rtr_texture* hdri, const float* skyColor, const rtr_sky_table* table, const RtrRay* rays, const RtrSurface* surfaces,
+                       uint32_t numHits, const rtr_sky_params* params, const uint32_t* seeds, RtrRay* outRays, RtrSkySample* outSamples);
+int  rtr_host_sky_hits(const rtr_texture* hdri, const float* skyColor, const rtr_sky_table* table, const RtrRay* rays, const RtrHit* hits,
+                       const RtrSurface* prevSurfaces, const RtrBounce* bounces, uint32_t numRays, const rtr_sky_params* params, RtrSkyEscape* out);
+int  rtr_host_sky_pdf(const rtr_sky_table* table, const float* dirs, uint32_t n, float* outPdf);
+int  rtr_host_sky_radiance(const rtr_texture* hdri, const float* skyColor, const float* dirs, uint32_t n, float* out);
+
 /* ---- errors --------------------------------------------------------------------------- */
 const char* rtr_last_error(void);
 const char* rtr_status_string(int status);

@@ -299,6 +299,43 @@ typedef struct RtrEmitter {
     float    lightPdf, dist; uint32_t lightTri, kind;
 } RtrEmitter;
 
+/* ---- sky importance sampling at a path vertex (rtr_sky_rays, rtr_shade_sky, rtr_sky_hits; the rule is include/rtr_sky.h) --------------
+ * numSamples (S, 1 ... RTR_SKY_MAX_SAMPLES) directions per vertex drawn in proportion to the scene's sky table.  depth and frame enter
+ * the seed as in rtr_bounce_params (sample j takes the offsets 3400 + 200 j and 3500 + 200 j); width, spp: the pixel rule, used when
+ * seeds == NULL; lobes: rtr_bounce_params::lobes of the vertex's bounce; flags: RTR_SKY_MIS (the balance heuristic against that bounce)
+ * or 0.  _reserved must be 0.  rtr_sky_hits takes numSamples 0 as well: a vertex that drew no sky sample.
+ * RtrSkySample: contrib = f cos sky / (S skyPdf + bouncePdf) (without the flag: / (S skyPdf)), to be multiplied by the throughput and
+ * added where the sample's ray is not occluded; skyPdf, bouncePdf: the solid-angle densities of the sky table and of the bounce for the
+ * sample's direction; wSky = S skyPdf / (S skyPdf + bouncePdf) (1 without the flag); cell = y * W + x of the table.  A DEAD sample is 32
+ * zero bytes beside the null ray.
+ * RtrSkyEscape: what a bounce ray that MISSED adds, to be multiplied by the throughput after the bounce: radiance = sky * wBounce,
+ * wBounce = bouncePdf / (S skyPdf + bouncePdf) (1 without the flag or with S == 0).  kind = RTR_SURFACE_MISS on a record that counts, 32
+ * zero bytes otherwise. */
+#define RTR_SKY_MAX_SAMPLES 8u
+#define RTR_SKY_MIS         1u
+typedef struct rtr_sky_params {
+    uint32_t numSamples, depth, frame, width;
+    uint32_t spp, lobes, flags, _reserved;
+} rtr_sky_params;             /* 32 bytes */
+
+/* a sky table as the calls that take one read it (rtr_host_sky_table and rtr_scene_export_sky_table fill the two arrays): rows[y *
+ * width + x], the inclusive prefix sums of row y's cell weights; marginal[y], the inclusive prefix sums of the row totals */
+typedef struct rtr_sky_table {
+    const uint32_t* rows;
+    const uint64_t* marginal;
+    uint32_t width, height;
+} rtr_sky_table;
+
+typedef struct RtrSkySample {
+    float    contrib[3]; float skyPdf;
+    float    bouncePdf, wSky; uint32_t cell, _r;
+} RtrSkySample;
+
+typedef struct RtrSkyEscape {
+    float    radiance[3]; float wBounce;
+    float    skyPdf, bouncePdf; uint32_t cell, kind;
+} RtrSkyEscape;
+
 #ifdef __cplusplus
 }
 #endif
@@ -325,6 +362,9 @@ static_assert(sizeof(rtr_pick_params) == 32, "pick params must be 32 B");
 static_assert(sizeof(rtr_mis_params) == 32, "mis params must be 32 B");
 static_assert(sizeof(RtrMisSample) == 32, "mis sample must be 32 B");
 static_assert(sizeof(RtrEmitter) == 32, "emitter record must be 32 B");
+static_assert(sizeof(rtr_sky_params) == 32, "sky params must be 32 B");
+static_assert(sizeof(RtrSkySample) == 32, "sky sample must be 32 B");
+static_assert(sizeof(RtrSkyEscape) == 32, "sky escape record must be 32 B");
 #endif
 
 #endif /* RTR_TYPES_H */

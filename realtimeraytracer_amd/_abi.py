@@ -113,6 +113,23 @@ class RtrEmitter(C.Structure):
     _fields_ = [("radiance", f32 * 3), ("wBounce", f32), ("lightPdf", f32), ("dist", f32), ("lightTri", u32), ("kind", u32)]
 
 
+class rtr_sky_params(C.Structure):
+    _fields_ = [("numSamples", u32), ("depth", u32), ("frame", u32), ("width", u32), ("spp", u32), ("lobes", u32), ("flags", u32), ("_reserved", u32)]
+
+
+class RtrSkySample(C.Structure):
+    _fields_ = [("contrib", f32 * 3), ("skyPdf", f32), ("bouncePdf", f32), ("wSky", f32), ("cell", u32), ("_r", u32)]
+
+
+class RtrSkyEscape(C.Structure):
+    _fields_ = [("radiance", f32 * 3), ("wBounce", f32), ("skyPdf", f32), ("bouncePdf", f32), ("cell", u32), ("kind", u32)]
+
+
+class rtr_sky_table(C.Structure):
+    """a sky table as the host forms read it: the rows' 32-bit inclusive prefix sums (width * height) and the 64-bit marginal sums (height)"""
+    _fields_ = [("rows", C.POINTER(u32)), ("marginal", C.POINTER(u64)), ("width", u32), ("height", u32)]
+
+
 class rtr_vertex_range(C.Structure):
     """one range of rtr_scene_update_vertices: vertices firstVertex ... + numVertices of the scene's concatenated vertex array"""
     _fields_ = [("firstVertex", u32), ("numVertices", u32), ("positions", C.c_void_p), ("normals", C.c_void_p)]
@@ -195,6 +212,7 @@ assert C.sizeof(RtrBounce) == 32 and C.sizeof(rtr_bounce_params) == 32
 assert C.sizeof(rtr_compact_params) == 32
 assert C.sizeof(rtr_pick_params) == 32
 assert C.sizeof(rtr_mis_params) == 32 and C.sizeof(RtrMisSample) == 32 and C.sizeof(RtrEmitter) == 32
+assert C.sizeof(rtr_sky_params) == 32 and C.sizeof(RtrSkySample) == 32 and C.sizeof(RtrSkyEscape) == 32
 assert C.sizeof(rtr_vertex_range) == 24
 assert C.sizeof(rtr_tree_cost) == 96 and C.alignment(rtr_tree_cost) == 8
 assert C.sizeof(rtr_update_status) == 32
@@ -226,6 +244,8 @@ PATH_NONE = 0xffffffff          # RTR_PATH_NONE: the path id of a slot behind th
 PICK_MAX = 30                   # RTR_PICK_MAX: the most picked light samples per hit
 PICK_NONE = 0xffffffff          # RTR_PICK_NONE: no area slot
 PICK_MAX_SLOTS = 1 << 24        # RTR_PICK_MAX_SLOTS: the most area slots a pick can be drawn from
+SKY_MAX_SAMPLES = 8             # RTR_SKY_MAX_SAMPLES: the most sky samples per path vertex
+SKY_MIS = 1                     # RTR_SKY_MIS: the balance heuristic between the sky samples and the bounce
 VERTICES_HOST, VERTICES_DEVICE = 0, 1
 
 P = C.POINTER
@@ -339,6 +359,19 @@ RTR_SYMBOLS = {
     "rtr_host_mis_weights": (C.c_int, [u32, VP, VP, VP, VP, u32, u32, VP, VP]),
     "rtr_host_emitter_hits": (C.c_int, [VP, VP, VP, VP, u32, VP, VP, VP, u32, P(rtr_mis_params), VP]),
     "rtr_host_sincos_turn": (C.c_int, [VP, u32, VP, VP]),
+    "rtr_scene_prepare_sky": (C.c_int, [VP]),
+    "rtr_scene_export_sky_table": (C.c_int, [VP, P(u32), P(u32), VP, C.c_size_t, VP, u32]),
+    "rtr_sky_rays_async": (C.c_int, [VP, VP, VP, VP, u32, P(rtr_sky_params), VP, VP, VP]),
+    "rtr_sky_rays": (C.c_int, [VP, VP, VP, VP, u32, P(rtr_sky_params), VP, VP, VP]),
+    "rtr_shade_sky_async": (C.c_int, [VP, VP, VP, u32, u32, VP]),
+    "rtr_shade_sky": (C.c_int, [VP, VP, VP, u32, u32, VP]),
+    "rtr_sky_hits_async": (C.c_int, [VP, VP, VP, VP, VP, VP, u32, P(rtr_sky_params), VP]),
+    "rtr_sky_hits": (C.c_int, [VP, VP, VP, VP, VP, VP, u32, P(rtr_sky_params), VP]),
+    "rtr_host_sky_table": (C.c_int, [P(rtr_texture), VP, P(u32), P(u32), VP, C.c_size_t, VP, u32]),
+    "rtr_host_sky_rays": (C.c_int, [P(rtr_texture), VP, P(rtr_sky_table), VP, VP, u32, P(rtr_sky_params), VP, VP, VP]),
+    "rtr_host_sky_hits": (C.c_int, [P(rtr_texture), VP, P(rtr_sky_table), VP, VP, VP, VP, u32, P(rtr_sky_params), VP]),
+    "rtr_host_sky_pdf": (C.c_int, [P(rtr_sky_table), VP, u32, VP]),
+    "rtr_host_sky_radiance": (C.c_int, [P(rtr_texture), VP, VP, u32, VP]),
 }
 
 RTRH_SYMBOLS = {

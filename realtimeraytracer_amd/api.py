@@ -461,6 +461,21 @@ class Scene:
                                                     C.byref(count)), "rtr_scene_export_light_tris")
         return rec, first
 
+    def prepare_sky(self):
+        """rtr_scene_prepare_sky: build the sky table on the device now (synchronous; once per scene), so that the enqueued sky calls
+        neither allocate nor join.  The first sky call of a scene that was not prepared builds it the same way."""
+        _check(self.lib.rtr_scene_prepare_sky(self.h), "rtr_scene_prepare_sky")
+
+    def export_sky_table(self):
+        """rtr_scene_export_sky_table: the device's sky table -> SkyTable (width, height, rows uint32 (H, W), marginal uint64 (H,)):
+        the words host_sky_table gives for the scene's HDRI or constant sky"""
+        w, h = C.c_uint32(0), C.c_uint32(0)
+        self.lib.rtr_scene_export_sky_table(self.h, C.byref(w), C.byref(h), None, 0, None, 0)      # refused: reports the extent
+        rows, marginal = np.zeros((h.value, w.value), np.uint32), np.zeros(h.value, np.uint64)
+        _check(self.lib.rtr_scene_export_sky_table(self.h, C.byref(w), C.byref(h), rows.ctypes.data_as(A.VP), rows.size, marginal.ctypes.data_as(A.VP),
+                                                   h.value), "rtr_scene_export_sky_table")
+        return SkyTable(w.value, h.value, rows, marginal)
+
     def set_instance_masks(self, masks):
         """rtr_scene_set_instance_masks: one 8-bit cull mask per instance, in instance order (array-like of uint8; default 0xff).  Only
         the masked queries (trace_rays / trace_occlusion with cull_mask or ray_masks) look at them; renders ignore them."""
@@ -1648,6 +1663,240 @@ def host_emitter_hits(rays, hits, prev_surfaces, bounces, light_tris, light_firs
     return _emitter_result(out, True, None)
 
 
+# ---- sky importance sampling at a path vertex (rtr_sky_rays, rtr_shade_sky, rtr_sky_hits; include/rtr_sky.h) ---------------------------
+class SkyTable:
+    """A sky table on the host: width, height, rows — uint32 (height, width), each row's inclusive prefix sums of its cell weights — and
+    marginal — uint64 (height,), the inclusive prefix sums of the row totals.  total: the sum of all weights (0: a black sky)."""
+    def __init__(self, width, height, rows, marginal):
+        self.width, self.height, self.rows, self.marginal = int(width), int(height), rows, marginal
+
+    @property
+    def total(self):
+        return int(self.marginal[-1])
+
+    def weights(self):
+        """the cell weights, uint32 (height, width)"""
+        return np.diff(self.rows.astype(np.int64), axis=1, prepend=0).astype(np.uint32)
+
+    def _c(self):
+        return A.rtr_sky_table(self.rows.ctypes.data_as(C.POINTER(C.c_uint32)), self.marginal.ctypes.data_as(C.POINTER(C.c_uint64)), self.width, self.height)
+
+
+class SkyResult:
+    """What sky_rays and host_sky_rays give back.  rays: the (N, S, 8) float32 RtrRay of the samples (eight zeros: a dead sample).  raw:
+    the (N, S, 8) float32 array of RtrSkySample records, of which contrib (N, S, 3), sky_pdf, bounce_pdf and w_sky (N, S) are float32
+    views and cell (y * W + x of the table) an int32 view."""
+    rays = raw = contrib = sky_pdf = bounce_pdf = w_sky = cell = None
+
+
+def _sky_result(rays, raw, as_numpy, torch):
+    res = SkyResult()
+    words = raw.view(np.int32) if as_numpy else raw.view(torch.int32)
+    res.rays, res.raw = rays, raw
+    res.contrib, res.sky_pdf, res.bounce_pdf, res.w_sky, res.cell = raw[..., 0:3], raw[..., 3], raw[..., 4], raw[..., 5], words[..., 6]
+    return res
+
+
+class SkyEscapeResult:
+    """What sky_hits and host_sky_hits give back.  raw: the (N, 8) float32 array of RtrSkyEscape records, of which radiance (N, 3) (to be
+    multiplied by the throughput after the bounce), w_bounce, sky_pdf and bounce_pdf (N,) are float32 views and cell, kind int32 views."""
+    raw = radiance = w_bounce = sky_pdf = bounce_pdf = cell = kind = None
+
+
+def _sky_escape_result(raw, as_numpy, torch):
+    res = SkyEscapeResult()
+    words = raw.view(np.int32) if as_numpy else raw.view(torch.int32)
+    res.raw = raw
+    res.radiance, res.w_bounce, res.sky_pdf, res.bounce_pdf, res.cell, res.kind = raw[:, 0:3], raw[:, 3], raw[:, 4], raw[:, 5], words[:, 6], words[:, 7]
+    return res
+
+
+def make_sky_params(samples=1, depth=0, frame=0, width=0, spp=1, lobes=A.BOUNCE_DIFFUSE | A.BOUNCE_SPECULAR, mis=True):
+    """rtr_sky_params: the sky samples per vertex (S), depth and frame of the seeds, width / spp of the pixel rule (used without explicit
+    seeds), the lobes the vertex's bounce samples, and whether the balance heuristic against that bounce applies"""
+    return A.rtr_sky_params(int(samples), int(depth) & 0xffffffff, int(frame) & 0xffffffff, int(width), int(spp), int(lobes), A.SKY_MIS if mis else 0, 0)
+
+
+def sky_rays(scene, rays, surfaces, params, seeds=None, ctx=None, asynchronous=False):
+    """rtr_sky_rays: S directions per hit drawn in proportion to the scene's sky, each with its shadow ray and its contribution ->
+    SkyResult.  rays: the float32 (N, 8) rays that found the hits; surfaces: hit_surfaces' SurfaceResult or its (N, 20) raw records;
+    seeds: int32 (N,) seed bases, default the pixel's (params.width, params.spp).  Device tensors in give device tensors out, numpy in
+    gives numpy out; asynchronous as in trace_rays."""
+    torch = _torch()
+    ctx = ctx or scene.ctx
+    dev = torch.device("cuda", ctx.device)
+    who = "sky_rays"
+    if isinstance(surfaces, SurfaceResult):
+        surfaces = surfaces.raw
+    r, as_numpy = _device_array(torch, rays, torch.float32, np.float32, "rays", dev, who)
+    if isinstance(surfaces, np.ndarray) != as_numpy:
+        raise ValueError(f"{who}: rays and surfaces must both be numpy arrays or both be tensors")
+    s = _records(torch, surfaces, 20, "surfaces", dev, who, as_numpy)
+    n, S = int(r.shape[0]), int(params.numSamples)
+    if int(s.shape[0]) != n:
+        raise ValueError(f"{who}: {n} rays but {s.shape[0]} surfaces")
+    sd = _device_vector(torch, seeds, torch.int32, (np.int32, np.uint32), n, "seeds", dev, who)
+    _check_async(ctx, torch, dev, who, asynchronous)
+    out_rays = torch.empty((n, S, 8), dtype=torch.float32, device=dev)
+    out_s = torch.empty((n, S, 8), dtype=torch.float32, device=dev)
+    _join_torchs_stream(ctx, torch, dev, asynchronous)
+    fn = ctx.lib.rtr_sky_rays_async if asynchronous else ctx.lib.rtr_sky_rays
+    _check(fn(ctx.h, scene.h, _ptr(r, n), _ptr(s, n), n, C.byref(params), _ptr(sd, n), _ptr(out_rays, n * S), _ptr(out_s, n * S)), "rtr_sky_rays")
+    res = _sky_result(out_rays.cpu().numpy(), out_s.cpu().numpy(), True, torch) if as_numpy else _sky_result(out_rays, out_s, False, torch)
+    res._keep = (r, s, sd)               # an asynchronous call's inputs stay alive with its result
+    return res
+
+
+def shade_sky(ctx, samples, occluded, asynchronous=False):
+    """rtr_shade_sky: per hit the sum, over its samples in order, of contrib where the sample's ray is not occluded -> float32 (N, 3).
+    samples: sky_rays' SkyResult or its (N, S, 8) raw records; occluded: uint8 (N, S) or (N * S,), what an any-hit query of the sample
+    rays reported.  Device tensors in give a device tensor out, numpy in gives numpy out."""
+    torch = _torch()
+    dev = torch.device("cuda", ctx.device)
+    who = "shade_sky"
+    if isinstance(samples, SkyResult):
+        samples = samples.raw
+    as_numpy = isinstance(samples, np.ndarray)
+    if samples.ndim != 3 or samples.shape[2] != 8:
+        raise ValueError(f"{who}: samples must be float32 (N, S, 8), got {tuple(samples.shape)}")
+    n, S = int(samples.shape[0]), int(samples.shape[1])
+    rec = _records(torch, samples.reshape(n * S, 8), 8, "samples", dev, who, as_numpy)
+    if isinstance(occluded, np.ndarray) != as_numpy:
+        raise ValueError(f"{who}: samples and occluded must both be numpy arrays or both be tensors")
+    occ = torch.from_numpy(np.ascontiguousarray(occluded)).to(dev) if as_numpy else occluded
+    if occ.dtype != torch.uint8 or occ.numel() != n * S or occ.device != dev or not occ.is_contiguous():
+        raise ValueError(f"{who}: occluded must be contiguous uint8 with {n * S} elements on {dev}")
+    _check_async(ctx, torch, dev, who, asynchronous)
+    out = torch.empty((n, 4), dtype=torch.float32, device=dev)
+    _join_torchs_stream(ctx, torch, dev, asynchronous)
+    fn = ctx.lib.rtr_shade_sky_async if asynchronous else ctx.lib.rtr_shade_sky
+    _check(fn(ctx.h, _ptr(rec, n), _ptr(occ, n), n, S, _ptr(out, n)), "rtr_shade_sky")
+    res = out[:, 0:3]
+    if as_numpy:
+        return res.cpu().numpy()
+    res._keep = (rec, occ)
+    return res
+
+
+def sky_hits(scene, rays, hits, prev_surfaces, bounces, params, ctx=None, asynchronous=False):
+    """rtr_sky_hits: what each bounce ray adds where it misses the scene -> SkyEscapeResult.  rays: the bounce rays (N, 8); hits: their
+    closest hits (a QueryResult or (N, 8) int32 records); prev_surfaces: the SurfaceResult (or (N, 20) float32 records) of the vertices the
+    rays left; bounces: bounce_rays' BounceResult (or its (N, 8) raw records) at those vertices; params: make_sky_params(...), whose
+    samples may be 0 here.  Device tensors in give device tensors out, numpy in gives numpy out."""
+    torch = _torch()
+    ctx = ctx or scene.ctx
+    dev = torch.device("cuda", ctx.device)
+    who = "sky_hits"
+    if isinstance(prev_surfaces, SurfaceResult):
+        prev_surfaces = prev_surfaces.raw
+    if isinstance(bounces, BounceResult):
+        bounces = bounces.raw
+    r, h, _, as_numpy = _light_inputs(torch, scene, rays, hits, None, ctx, who, asynchronous)
+    n = int(r.shape[0])
+    if isinstance(prev_surfaces, np.ndarray) != as_numpy or isinstance(bounces, np.ndarray) != as_numpy:
+        raise ValueError(f"{who}: rays, hits, prev_surfaces and bounces must all be numpy arrays or all be tensors")
+    s = _records(torch, prev_surfaces, 20, "prev_surfaces", dev, who, as_numpy)
+    b = _records(torch, bounces, 8, "bounces", dev, who, as_numpy)
+    if int(s.shape[0]) != n or int(b.shape[0]) != n:
+        raise ValueError(f"{who}: {n} rays but {s.shape[0]} surfaces and {b.shape[0]} bounce records")
+    out = torch.empty((n, 8), dtype=torch.float32, device=dev)
+    _join_torchs_stream(ctx, torch, dev, asynchronous)
+    fn = ctx.lib.rtr_sky_hits_async if asynchronous else ctx.lib.rtr_sky_hits
+    _check(fn(ctx.h, scene.h, _ptr(r, n), _ptr(h, n), _ptr(s, n), _ptr(b, n), n, C.byref(params), _ptr(out, n)), "rtr_sky_hits")
+    res = _sky_escape_result(out.cpu().numpy() if as_numpy else out, as_numpy, torch)
+    res._keep = (r, h, s, b)
+    return res
+
+
+def _host_sky(hdri, sky_color, who):
+    """(texture pointer or None, its keep-alive, the sky colour's pointer) of a host sky: hdri a uint8 (H, W, 4) / (H, W, 1) / (H, W) array or None"""
+    col = np.ascontiguousarray(sky_color if sky_color is not None else (0.0, 0.0, 0.0), dtype=np.float32).reshape(3)
+    if hdri is None:
+        return None, (col,), col.ctypes.data_as(A.VP)
+    px = np.ascontiguousarray(hdri)
+    if px.dtype != np.uint8 or px.ndim not in (2, 3) or (px.ndim == 3 and px.shape[2] not in (1, 4)):
+        raise ValueError(f"{who}: hdri must be uint8 (H, W, 4), (H, W, 1) or (H, W), got {px.dtype} {px.shape}")
+    tex = A.rtr_texture(px.ctypes.data_as(C.POINTER(C.c_uint8)), px.shape[1], px.shape[0], px.shape[2] if px.ndim == 3 else 1, 0)
+    return C.byref(tex), (px, tex, col), col.ctypes.data_as(A.VP)
+
+
+def host_sky_table(hdri=None, sky_color=None):
+    """rtr_host_sky_table: the sky table of an HDRI (uint8 (H, W, 4) RGBA8 or (H, W) / (H, W, 1) R8) or, with hdri None, of the constant
+    sky of sky_color (three sRGB-encoded floats), built on the host -> SkyTable.  Scene.export_sky_table() gives the same words."""
+    lib = A.hip_lib()
+    tex, keep, col = _host_sky(hdri, sky_color, "host_sky_table")
+    w, h = C.c_uint32(0), C.c_uint32(0)
+    lib.rtr_host_sky_table(tex, col, C.byref(w), C.byref(h), None, 0, None, 0)      # refused: reports the extent
+    if w.value == 0:
+        _check(lib.rtr_host_sky_table(tex, col, C.byref(w), C.byref(h), None, 0, None, 0), "rtr_host_sky_table")
+    rows, marginal = np.zeros((h.value, w.value), np.uint32), np.zeros(h.value, np.uint64)
+    _check(lib.rtr_host_sky_table(tex, col, C.byref(w), C.byref(h), rows.ctypes.data_as(A.VP), rows.size, marginal.ctypes.data_as(A.VP), h.value), "rtr_host_sky_table")
+    return SkyTable(w.value, h.value, rows, marginal)
+
+
+def host_sky_rays(table, rays, surfaces, params, seeds=None, hdri=None, sky_color=None):
+    """rtr_host_sky_rays: sky_rays on the host, no device -> SkyResult of numpy arrays.  table: the SkyTable of the sky (hdri, sky_color
+    as host_sky_table takes them)."""
+    lib = A.hip_lib()
+    who = "host_sky_rays"
+    tex, keep, col = _host_sky(hdri, sky_color, who)
+    r, s = _aligned_copy(_host_words(rays, (8,), "rays", who)), _aligned_copy(_host_words(surfaces, (20,), "surfaces", who))
+    n, S = int(r.shape[0]), int(params.numSamples)
+    if s.shape[0] != n:
+        raise ValueError(f"{who}: {n} rays but {s.shape[0]} surfaces")
+    sd = None
+    if seeds is not None:
+        sd = np.ascontiguousarray(seeds)
+        if sd.dtype not in (np.int32, np.uint32) or sd.shape != (n,):
+            raise ValueError(f"{who}: seeds must be int32 or uint32 ({n},), got {sd.dtype} {sd.shape}")
+    out_rays, out_s = _aligned_copy(np.zeros((n, max(S, 1), 8), np.float32)), _aligned_copy(np.zeros((n, max(S, 1), 8), np.float32))
+    t = table._c()
+    _check(lib.rtr_host_sky_rays(tex, col, C.byref(t), r.ctypes.data_as(A.VP) if n else None, s.ctypes.data_as(A.VP) if n else None, n, C.byref(params),
+                                 sd.ctypes.data_as(A.VP) if sd is not None and n else None, out_rays.ctypes.data_as(A.VP) if n else None,
+                                 out_s.ctypes.data_as(A.VP) if n else None), "rtr_host_sky_rays")
+    return _sky_result(out_rays, out_s, True, None)
+
+
+def host_sky_hits(table, rays, hits, prev_surfaces, bounces, params, hdri=None, sky_color=None):
+    """rtr_host_sky_hits: sky_hits on the host, no device -> SkyEscapeResult of numpy arrays"""
+    lib = A.hip_lib()
+    who = "host_sky_hits"
+    tex, keep, col = _host_sky(hdri, sky_color, who)
+    r, h = _aligned_copy(_host_words(rays, (8,), "rays", who)), _aligned_copy(_host_words(hits, (8,), "hits", who))
+    s, b = _aligned_copy(_host_words(prev_surfaces, (20,), "prev_surfaces", who)), _aligned_copy(_host_words(bounces, (8,), "bounces", who))
+    n = int(r.shape[0])
+    if h.shape[0] != n or s.shape[0] != n or b.shape[0] != n:
+        raise ValueError(f"{who}: {n} rays but {h.shape[0]} hits, {s.shape[0]} surfaces and {b.shape[0]} bounce records")
+    out = _aligned_copy(np.zeros((n, 8), np.float32))
+    t = table._c()
+    _check(lib.rtr_host_sky_hits(tex, col, C.byref(t), r.ctypes.data_as(A.VP) if n else None, h.ctypes.data_as(A.VP) if n else None,
+                                 s.ctypes.data_as(A.VP) if n else None, b.ctypes.data_as(A.VP) if n else None, n, C.byref(params),
+                                 out.ctypes.data_as(A.VP) if n else None), "rtr_host_sky_hits")
+    return _sky_escape_result(out, True, None)
+
+
+def host_sky_pdf(table, dirs):
+    """rtr_host_sky_pdf: the solid-angle density of the table for the directions dirs (N, 3) -> float32 (N,)"""
+    lib = A.hip_lib()
+    d = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+    n = int(d.shape[0])
+    out = np.zeros(n, np.float32)
+    t = table._c()
+    _check(lib.rtr_host_sky_pdf(C.byref(t), d.ctypes.data_as(A.VP) if n else None, n, out.ctypes.data_as(A.VP) if n else None), "rtr_host_sky_pdf")
+    return out
+
+
+def host_sky_radiance(dirs, hdri=None, sky_color=None):
+    """rtr_host_sky_radiance: the miss rule's radiance for the directions dirs (N, 3) -> float32 (N, 3): RtrSurface::color of a miss"""
+    lib = A.hip_lib()
+    tex, keep, col = _host_sky(hdri, sky_color, "host_sky_radiance")
+    d = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+    n = int(d.shape[0])
+    out = np.zeros((n, 3), np.float32)
+    _check(lib.rtr_host_sky_radiance(tex, col, d.ctypes.data_as(A.VP) if n else None, n, out.ctypes.data_as(A.VP) if n else None), "rtr_host_sky_radiance")
+    return out
+
+
 class PathResult:
     """What path_trace gives back: radiance (N, 3) float32, the sum of per_depth, a list of bounces + 1 (N, 3) tensors — entry d is what
     the path's vertex d contributes, already multiplied by the throughput up to it.  live: with compact=True the number of paths that
@@ -1735,9 +1984,36 @@ def path_trace_mis(scene, rays, light_params, bounces, light_picks=1, pick_from=
                        survival_floor, light_picks, pick_from, mis=True)
 
 
+def path_trace_sky(scene, rays, light_params, bounces, sky_samples=1, sky_from=0, sky_mis=True, light_picks=1, pick_from=1, seeds=None, occlusion="dense",
+                   bounce_cull_mask=None, bounce_ray_flags=0, max_ray_bytes=256 << 20, ctx=None, compact=False, roulette_from=None, survival_floor=0.05):
+    """path_trace_mis with sky importance sampling at the path vertices (include/rtr_sky.h): the same loop, the same arguments, and with
+    sky = make_sky_params(S = sky_samples, d, light_params.frame, width, spp, mis=sky_mis)
+
+        a vertex d >= sky_from with d < bounces is a SKY VERTEX: it adds T * shade_sky(k, occluded) of its S samples
+            k = sky_rays(scene, r, hit_surfaces(scene, r, q), sky, seeds = the bounce's seeds), traced with RTR_QUERY_ANY by the occlusion=
+            route of the light rays ("queued": trace_occlusion, else the dense query)
+        at a vertex d >= 1 whose hit is a miss, rad = sky_hits(scene, r, q, S', B', sky).radiance when vertex d - 1 was a sky vertex
+            (S', B': the hit_surfaces and bounce_rays records of vertex d - 1), and 0 there with sky_mis=False: that vertex sampled the
+            sky itself, as a picked vertex's light hit counts for nothing.  Every other miss adds T * sky as before, and so does the miss
+            of a camera ray.
+
+    compact=True: the escape records' inputs follow the survivors as the emitter records' do.  sky_samples=0 is path_trace_mis, tensor
+    for tensor.  The samples cover the whole sphere of directions (about half fall below the surface and are dead), and are drawn
+    without regard to the BRDF.  -> PathResult."""
+    if light_picks is None:
+        raise ValueError("path_trace_sky: light_picks must be given (the loop is path_trace_mis's)")
+    sky_samples = int(sky_samples)
+    if not 0 <= sky_samples <= A.SKY_MAX_SAMPLES:
+        raise ValueError(f"path_trace_sky: sky_samples must be 0 ... {A.SKY_MAX_SAMPLES}, got {sky_samples}")
+    if int(sky_from) < 0:
+        raise ValueError(f"path_trace_sky: sky_from must be >= 0, got {sky_from}")
+    return _path_trace(scene, rays, light_params, bounces, seeds, occlusion, bounce_cull_mask, bounce_ray_flags, max_ray_bytes, ctx, compact, roulette_from,
+                       survival_floor, light_picks, pick_from, mis=True, sky=(sky_samples, int(sky_from), bool(sky_mis)) if sky_samples else None)
+
+
 def _path_trace(scene, rays, light_params, bounces, seeds, occlusion, bounce_cull_mask, bounce_ray_flags, max_ray_bytes, ctx, compact, roulette_from, survival_floor,
-                light_picks, pick_from, mis=False):
-    """the loop of path_trace, path_trace_picked and path_trace_mis"""
+                light_picks, pick_from, mis=False, sky=None):
+    """the loop of path_trace, path_trace_picked, path_trace_mis and path_trace_sky (sky: (samples, from, mis) or None)"""
     if roulette_from is not None and not compact:
         raise ValueError("path_trace: roulette_from needs compact=True (a path the roulette kills saves nothing while it keeps its lane)")
     if roulette_from is not None and int(roulette_from) < 0:
@@ -1769,6 +2045,7 @@ def _path_trace(scene, rays, light_params, bounces, seeds, occlusion, bounce_cul
         res.live = [n]
     mis_params = make_mis_params(light_picks, light_params.numAreaLights, light_params.numShadowRays) if mis else None
     prev = None                          # mis: (surfaces, bounce records) of the vertex before when it was a MIS vertex
+    prev_sky = None                      # sky: the same records of the vertex before when it was a sky vertex
     for d in range(bounces + 1):
         q = trace_rays(scene, r, ctx=ctx) if d == 0 else trace_rays(scene, r, ctx=ctx, cull_mask=bounce_cull_mask, ray_flags=bounce_ray_flags)
         sd = seeds if d == 0 else _wrap32(base.to(torch.int64) + d * PATH_SEED_STEP)
@@ -1785,7 +2062,18 @@ def _path_trace(scene, rays, light_params, bounces, seeds, occlusion, bounce_cul
         if d >= 1:
             met = emitter_hits(scene, r, q, prev[0], prev[1], mis_params, ctx=ctx).radiance if prev is not None else torch.zeros_like(rad)
             rad = torch.where((lit.kind == A.SURFACE_LIGHT).unsqueeze(1), met, rad)
+            if prev_sky is not None:
+                esc = (sky_hits(scene, r, q, prev_sky[0], prev_sky[1], make_sky_params(sky[0], d - 1, light_params.frame, light_params.width, light_params.spp,
+                                                                                       mis=True), ctx=ctx).radiance if sky[2] else torch.zeros_like(rad))
+                rad = torch.where((lit.kind == A.SURFACE_MISS).unsqueeze(1), esc, rad)
         term = T * rad
+        sky_vertex = sky is not None and sky[1] <= d < bounces
+        surf = hit_surfaces(scene, r, q, ctx=ctx) if d < bounces else None
+        if sky_vertex:
+            k = sky_rays(scene, r, surf, make_sky_params(sky[0], d, light_params.frame, light_params.width, light_params.spp, mis=sky[2]), seeds=bounce_seeds, ctx=ctx)
+            kr = k.rays.reshape(-1, 8)
+            occ = (trace_occlusion(scene, kr, ctx=ctx) if occlusion == "queued" else trace_rays(scene, kr, any_hit=True, ctx=ctx)).occluded
+            term = term + T * shade_sky(ctx, k, occ)
         if ids is not None:
             full = torch.zeros((n, 3), dtype=torch.float32, device=rays.device)
             full[ids.to(torch.int64)] = term
@@ -1794,11 +2082,11 @@ def _path_trace(scene, rays, light_params, bounces, seeds, occlusion, bounce_cul
         res.radiance = res.radiance + term
         if d == bounces:
             break
-        surf = hit_surfaces(scene, r, q, ctx=ctx)
         b = bounce_rays(ctx, r, surf, make_bounce_params(frame=light_params.frame, depth=d, width=light_params.width, spp=light_params.spp), seeds=bounce_seeds)
         T = T * b.weight
         r = b.rays
         prev = (surf.raw, b.raw) if mis_vertex else None
+        prev_sky = (surf.raw, b.raw) if sky_vertex else None
         if compact:
             c = compact_paths(ctx, r, T, seeds=base, path_ids=None if mis else ids,
                               params=make_compact_params(frame=light_params.frame, depth=d, roulette=roulette_from is not None and d >= int(roulette_from),
@@ -1815,6 +2103,8 @@ def _path_trace(scene, rays, light_params, bounces, seeds, occlusion, bounce_cul
                 rows = rows.to(torch.int64)
                 if prev is not None:
                     prev = (prev[0][rows].contiguous(), prev[1][rows].contiguous())
+                if prev_sky is not None:
+                    prev_sky = (prev_sky[0][rows].contiguous(), prev_sky[1][rows].contiguous())
                 rows = rows.to(torch.int32) if ids is None else ids[rows]
             ids = rows
             bounce_seeds = base

@@ -18,6 +18,8 @@
 #include "rtr_pick_host.h"
 #include "kernels/rtr_mis_launch.h"
 #include "rtr_mis_host.h"
+#include "kernels/rtr_sky_launch.h"
+#include "rtr_sky_host.h"
 
 #include <hip/hip_runtime.h>
 
@@ -214,6 +216,12 @@ struct rtr_scene {
     DevBuf<float> xforms, nmats, ltc1, ltc2;
     std::vector<DevBuf<uint8_t>> texPixels;
     DevBuf<uint8_t> hdriPixels;
+    /* the sky table (rtr_scene_prepare_sky, or the first call that needs it: ensure_sky_table): the rows' 32-bit prefix sums and the 64-bit
+     * marginal sums.  The HDRI and the sky colour are fixed for the scene's life, so nothing ever remakes it.  mutable: the sky calls
+     * take the scene const, like the leaf table */
+    mutable DevBuf<uint32_t> skyRows;
+    mutable DevBuf<uint64_t> skyMarginal;
+    mutable bool skyReady = false;
     DevBuf<rtrdev::DeviceTexture> texTable;
     std::vector<RtrAreaLightInfo> hostLights;
     std::vector<RtrInstance> hostInstances;
@@ -2980,6 +2988,139 @@ int rtr_emitter_hits_async(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, c
 int rtr_emitter_hits(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, const RtrSurface* prevSurfaces, const RtrBounce* bounces,
                      uint32_t n, const rtr_mis_params* mis, RtrEmitter* out) {
     return join_if_enqueued(c, enqueue_emitter_hits(c, s, rays, hits, prevSurfaces, bounces, n, mis, out, "rtr_emitter_hits"), n);
+}
+
+/* ---- sky importance sampling (kernels/rtr_sky.hip; the rule is include/rtr_sky.h, the host forms and the argument checks rtr_sky_host.cpp) -- */
+static rtr_sky_source scene_sky_source(const rtr_scene* s) {
+    rtr_sky_source src{};
+    src.pixels = s->dev.hdri.pixels; src.width = s->dev.hdri.width; src.height = s->dev.hdri.height; src.channels = s->dev.hdri.channels;
+    for (int k = 0; k < 3; ++k) src.skyLinear[k] = s->dev.skyLinear[k];
+    return src;
+}
+
+/* Made by the first call that needs it, on `st` (the current device is the scene's), and JOINED before the call goes on, as the leaf
+ * table is: whichever context of the device asks next finds it complete.  It reads the HDRI's texels and the sky colour alone, which
+ * no update, refit or rebuild writes. */
+static int ensure_sky_table(const rtr_scene* s, hipStream_t st, const char* who) {
+    if (s->skyReady) return RTR_OK;
+    const rtr_sky_source src = scene_sky_source(s);
+    const uint32_t W = rtr_sky_table_width(&src), H = rtr_sky_table_height(&src);
+    if (W > RTR_SKY_MAX_WIDTH) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: the scene's hdri is %u texels wide: a row's sum fits 32 bits up to %u", who, W, RTR_SKY_MAX_WIDTH);
+    HIP_TRY(s->skyRows.alloc((size_t)W * H));
+    HIP_TRY(s->skyMarginal.alloc(H));
+    const hipError_t e = rtrdev::launch_sky_table(src, s->skyRows.p, s->skyMarginal.p, st);
+    if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: sky table: %s", who, hipGetErrorString(e));
+    HIP_TRY(hipStreamSynchronize(st));
+    s->skyReady = true;
+    return RTR_OK;
+}
+
+static rtrdev::SkyDevice scene_sky_device(const rtr_scene* s) {
+    rtrdev::SkyDevice sd{};
+    sd.sky = scene_sky_source(s);
+    sd.table.rows = s->skyRows.p; sd.table.marginal = s->skyMarginal.p;
+    sd.table.width = rtr_sky_table_width(&sd.sky); sd.table.height = rtr_sky_table_height(&sd.sky);
+    return sd;
+}
+
+int rtr_scene_prepare_sky(rtr_scene* s) {
+    static const char* who = "rtr_scene_prepare_sky";
+    if (!s) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: null scene", who);
+    HIP_TRY(hipSetDevice(s->ctx->device));
+    return ensure_sky_table(s, s->ctx->stream, who);
+}
+
+int rtr_scene_export_sky_table(const rtr_scene* s, uint32_t* outWidth, uint32_t* outHeight, uint32_t* outRows, size_t capacityCells, uint64_t* outMarginal,
+                               uint32_t capacityRows) {
+    static const char* who = "rtr_scene_export_sky_table";
+    if (!s) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: null scene", who);
+    const rtr_sky_source src = scene_sky_source(s);
+    const uint32_t W = rtr_sky_table_width(&src), H = rtr_sky_table_height(&src);
+    if (outWidth) *outWidth = W;
+    if (outHeight) *outHeight = H;
+    if (!outRows || !outMarginal || capacityCells < (size_t)W * H || capacityRows < H)
+        return fail(RTR_ERR_INVALID_ARGUMENT, "%s: capacity %zu cells, %u rows; %zu and %u are needed", who, outRows ? capacityCells : (size_t)0,
+                    outMarginal ? capacityRows : 0u, (size_t)W * H, H);
+    HIP_TRY(hipSetDevice(s->ctx->device));
+    if (const int rc = ensure_sky_table(s, s->ctx->stream, who)) return rc;
+    HIP_TRY(hipMemcpy(outRows, s->skyRows.p, (size_t)W * H * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(outMarginal, s->skyMarginal.p, (size_t)H * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return RTR_OK;
+}
+
+static int enqueue_sky_rays(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrSurface* surfaces, uint32_t n, const rtr_sky_params* p,
+                            const uint32_t* seeds, RtrRay* outRays, RtrSkySample* outSamples, const char* who) {
+    /* the params and the arrays are checked first, which needs nothing of the handles */
+    if (const int rc = rtrdev::sky_check_params(who, p, false)) return rc;
+    if (const int rc = rtrdev::sky_check_rays_call(who, p, rays, surfaces, n, seeds, outRays, outSamples)) return rc;
+    if (const int rc = check_handles(c, s, who)) return rc;
+    if (const int rc = check_same_device(c, s, who)) return rc;
+    if (n == 0) return RTR_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    if (const int rc = ensure_sky_table(s, c->stream, who)) return rc;
+    rtrdev::SkyRaysArgs a{};
+    a.sd = scene_sky_device(s);
+    a.rays = reinterpret_cast<const float4*>(rays); a.surfaces = reinterpret_cast<const float4*>(surfaces); a.seeds = seeds;
+    a.outRays = reinterpret_cast<float4*>(outRays); a.outSamples = reinterpret_cast<float4*>(outSamples);
+    a.params = *p; a.n = n;
+    return launched(rtrdev::launch_sky_rays(a, a.sd.table.height <= rtrdev::kSkyLdsRows, c->stream), who);
+}
+
+int rtr_sky_rays_async(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrSurface* surfaces, uint32_t n, const rtr_sky_params* p,
+                       const uint32_t* seeds, RtrRay* outRays, RtrSkySample* outSamples) {
+    return enqueue_sky_rays(c, s, rays, surfaces, n, p, seeds, outRays, outSamples, "rtr_sky_rays_async");
+}
+
+int rtr_sky_rays(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrSurface* surfaces, uint32_t n, const rtr_sky_params* p,
+                 const uint32_t* seeds, RtrRay* outRays, RtrSkySample* outSamples) {
+    return join_if_enqueued(c, enqueue_sky_rays(c, s, rays, surfaces, n, p, seeds, outRays, outSamples, "rtr_sky_rays"), n);
+}
+
+static int enqueue_shade_sky(rtr_ctx* c, const RtrSkySample* samples, const uint8_t* occluded, uint32_t n, uint32_t numSamples, float* out, const char* who) {
+    if (const int rc = rtrdev::sky_check_shade_call(who, samples, occluded, n, numSamples, out)) return rc;
+    if (!c) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: null context", who);
+    if (n == 0) return RTR_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    rtrdev::SkyShadeArgs a{};
+    a.samples = reinterpret_cast<const float4*>(samples); a.occluded = occluded; a.out = reinterpret_cast<float4*>(out);
+    a.numSamples = numSamples; a.n = n;
+    return launched(rtrdev::launch_shade_sky(a, c->stream), who);
+}
+
+int rtr_shade_sky_async(rtr_ctx* c, const RtrSkySample* samples, const uint8_t* occluded, uint32_t n, uint32_t numSamples, float* out) {
+    return enqueue_shade_sky(c, samples, occluded, n, numSamples, out, "rtr_shade_sky_async");
+}
+
+int rtr_shade_sky(rtr_ctx* c, const RtrSkySample* samples, const uint8_t* occluded, uint32_t n, uint32_t numSamples, float* out) {
+    const int rc = enqueue_shade_sky(c, samples, occluded, n, numSamples, out, "rtr_shade_sky");
+    return rc == RTR_OK ? join_if_enqueued(c, rc, n) : rc;
+}
+
+static int enqueue_sky_hits(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, const RtrSurface* prevSurfaces, const RtrBounce* bounces,
+                            uint32_t n, const rtr_sky_params* p, RtrSkyEscape* out, const char* who) {
+    if (const int rc = rtrdev::sky_check_params(who, p, true)) return rc;
+    if (const int rc = n ? rtrdev::sky_check_hits_arrays(who, rays, hits, prevSurfaces, bounces, n, out) : RTR_OK) return rc;
+    if (const int rc = check_handles(c, s, who)) return rc;
+    if (const int rc = check_same_device(c, s, who)) return rc;
+    if (n == 0) return RTR_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    if (const int rc = ensure_sky_table(s, c->stream, who)) return rc;
+    rtrdev::SkyHitsArgs a{};
+    a.sd = scene_sky_device(s);
+    a.rays = reinterpret_cast<const float4*>(rays); a.hits = reinterpret_cast<const float4*>(hits);
+    a.prevSurfaces = reinterpret_cast<const float4*>(prevSurfaces); a.bounces = reinterpret_cast<const float4*>(bounces);
+    a.out = reinterpret_cast<float4*>(out); a.numSamples = p->numSamples; a.flags = p->flags; a.n = n;
+    return launched(rtrdev::launch_sky_hits(a, c->stream), who);
+}
+
+int rtr_sky_hits_async(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, const RtrSurface* prevSurfaces, const RtrBounce* bounces,
+                       uint32_t n, const rtr_sky_params* p, RtrSkyEscape* out) {
+    return enqueue_sky_hits(c, s, rays, hits, prevSurfaces, bounces, n, p, out, "rtr_sky_hits_async");
+}
+
+int rtr_sky_hits(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, const RtrSurface* prevSurfaces, const RtrBounce* bounces,
+                 uint32_t n, const rtr_sky_params* p, RtrSkyEscape* out) {
+    return join_if_enqueued(c, enqueue_sky_hits(c, s, rays, hits, prevSurfaces, bounces, n, p, out, "rtr_sky_hits"), n);
 }
 
 int rtr_scene_export_light_tris(const rtr_scene* s, float* outRecords, uint32_t capacityTris, uint32_t* outFirst, uint32_t* outCount) {

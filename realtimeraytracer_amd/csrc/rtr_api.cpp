@@ -1,4 +1,6 @@
-/* rtr_api.cpp — implementation of the C ABI in include/rtr.h (host side of librtr_hip.so).
+/* rtr_api.cpp — implementation of the C ABI in include/rtr.h (host side of librtr_hip.so): errors, version and status strings, the
+ * context and the scene.  Frames and dispatch are rtr_api_render.cpp, the ray queries rtr_api_query.cpp, lighting and the path-vertex
+ * calls rtr_api_paths.cpp; rtr_api_internal.h has what they share.
  * HIP runtime for device memory / streams / events; kernels in kernels/rtr_kernels.hip.
  * There is NO CPU rendering fallback in this library: without a HIP device every entry point
  * that needs one fails with RTR_ERR_NO_DEVICE / RTR_ERR_HIP. */
@@ -6,20 +8,11 @@
 #include "../../include/rtr_math.h"
 #include "bvh_build.h"
 #include "kernels/rtr_kernels.h"
-#include "kernels/rtr_post.h"
 #include "kernels/rtr_bvh.h"
 #include "kernels/rtr_mirrored.h"
 #include "kernels/rtr_tree_sah.h"
 #include "kernels/rtr_query.h"
-#include "kernels/rtr_bounce_launch.h"
-#include "rtr_bounce_host.h"
-#include "kernels/rtr_paths_launch.h"
-#include "rtr_paths_host.h"
-#include "rtr_pick_host.h"
-#include "kernels/rtr_mis_launch.h"
-#include "rtr_mis_host.h"
-#include "kernels/rtr_sky_launch.h"
-#include "rtr_sky_host.h"
+#include "rtr_api_internal.h"
 
 #include <hip/hip_runtime.h>
 
@@ -31,17 +24,15 @@
 #include <string>
 #include <vector>
 
-using rtrdev::Counters;
-using rtrdev::DeviceScene;
-using rtrdev::FrameOut;
-using rtrdev::RenderArgs;
-using rtrdev::Workspace;
+using namespace rtrapi;
 
 namespace {
 
 thread_local std::string g_err;
 
-int fail(int code, const char* fmt, ...) {
+}  // namespace
+
+int rtrapi::fail(int code, const char* fmt, ...) {
     char buf[1024];
     va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
     g_err = buf;
@@ -49,70 +40,16 @@ int fail(int code, const char* fmt, ...) {
 }
 
 /* the status of a call whose kernel launcher returned e */
-int launched(hipError_t e, const char* who) {
+int rtrapi::launched(hipError_t e, const char* who) {
     if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: kernel launch: %s", who, hipGetErrorString(e));
     return RTR_OK;
 }
 
-#define HIP_TRY(expr)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess)                                                                      \
-            return fail(e_ == hipErrorOutOfMemory ? RTR_ERR_OUT_OF_MEMORY : RTR_ERR_HIP, "%s failed: %s", #expr, \
-                        hipGetErrorString(e_));                                                    \
-    } while (0)
+constexpr size_t kPolicyRecordAt = 12, kPolicyWords = kPolicyRecordAt + sizeof(rtrdev::RebuildIfRecord) / sizeof(unsigned long long);
+static rtrdev::RebuildIfRecord* policy_record(const rtr_scene* s) { return reinterpret_cast<rtrdev::RebuildIfRecord*>(s->policy.p + kPolicyRecordAt); }
 
-template <class T>
-struct DevBuf {
-    T* p = nullptr; size_t n = 0;
-    DevBuf() = default;
-    DevBuf(DevBuf&& o) noexcept : p(o.p), n(o.n) { o.p = nullptr; o.n = 0; }      /* owns its memory: moved, never copied */
-    DevBuf& operator=(DevBuf&& o) noexcept { std::swap(p, o.p); std::swap(n, o.n); return *this; }
-    ~DevBuf() { release(); }
-    void release() { if (p) { (void)hipFree(p); p = nullptr; n = 0; } }
-    hipError_t alloc(size_t count) {
-        release();
-        if (count == 0) count = 1;
-        hipError_t e = hipMalloc((void**)&p, count * sizeof(T));
-        if (e == hipSuccess) n = count;
-        return e;
-    }
-    /* a buffer that is reused from call to call and grows on demand (its old contents are not kept) */
-    hipError_t grow(size_t count) { return (p && n >= count) ? hipSuccess : alloc(count + count / 2); }
-    /* a buffer whose size is fixed by its owner and that is kept from call to call: allocated on first use */
-    hipError_t ensure(size_t count) { return (p && n >= count) ? hipSuccess : alloc(count); }
-    hipError_t upload(const T* src, size_t count, hipStream_t s) {
-        hipError_t e = alloc(count);
-        if (e != hipSuccess) return e;
-        if (count == 0 || !src) return hipSuccess;
-        e = hipMemcpyAsync(p, src, count * sizeof(T), hipMemcpyHostToDevice, s);
-        if (e != hipSuccess) return e;
-        return hipStreamSynchronize(s);
-    }
-};
-
-}  // namespace
-
-struct rtr_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    bool ownStream = false;
-    hipDeviceProp_t prop;
-    int numXccs = 0;                     /* hipDeviceAttributeNumberOfXccs (reported by rtr_ctx_device_name): the kernels' eight batch cursors stay private to one XCD each for 8, 4, 2 or 1 XCDs — kernels/rtr_kernels.h, kQueueRegions */
-    /* scenes and frames keep a pointer to their context: a context destroyed while it still has children lives on,
-     * unusable, until the last child is gone (garbage-collected bindings destroy objects in any order) */
-    int children = 0;
-    bool destroyed = false;
-    rtrdev::Tunables tun;                /* run-time tunables of the staged pipeline: environment at creation, rtr_ctx_set_tunable afterwards */
-    /* ray queries (rtr_trace_rays): the tail kernel's scratch — control block, redo list (kQueryRedoCap entries), full-depth stacks —
-     * and the counters of the counting form.  Allocated by the first query and reused by every later one: its size does not depend on
-     * the number of rays.  qEv: around the query's kernels (timing, and what a query enqueued on another stream waits for). */
-    DevBuf<uint32_t> qCtrl, qRedo;
-    DevBuf<int32_t> qSpill;
-    DevBuf<Counters> qCounters;
-    hipEvent_t qEv[2] = {nullptr, nullptr};
-    hipStream_t qLastStream = nullptr;   /* the stream the last query was enqueued on */
-};
+/* no geometry: the host builder's tree of such a scene is one node over one placeholder record */
+static bool scene_is_empty(const rtr_scene* s) { return s->tree.hostTris.empty() || s->tree.hostTris[0].customIndex == 0xffffffffu; }
 
 static void ctx_free(rtr_ctx* c) {
     (void)hipSetDevice(c->device);
@@ -121,195 +58,9 @@ static void ctx_free(rtr_ctx* c) {
     if (c->ownStream && c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
-static void ctx_release_child(rtr_ctx* c) {
+void rtrapi::ctx_release_child(rtr_ctx* c) {
     if (--c->children == 0 && c->destroyed) ctx_free(c);
 }
-
-/* what the device LBVH build needs while it runs (rtrdev::BvhScratch): rtr_scene_create frees it with the call, a scene that has been
- * rebuilt on the device keeps it for the next rebuild (sizes depend on the triangle count alone, which no call changes) */
-struct BuildScratch {
-    DevBuf<float4> trisCanon, minCanon, maxCanon;
-    DevBuf<unsigned long long> keysIn, keysOut;
-    DevBuf<int2> range, rawChild;
-    DevBuf<uint8_t> sortTemp;
-    size_t sortTempBytes = 0;            /* what hipcub asked for (sortTemp may be larger) */
-};
-
-/* rtr_scene_rebuild_async's stage: a second set of the arrays a device build writes, which nothing else reads.  The enqueued build fills
- * it, k_commit_tree copies it over the live arrays — or does not.  Sizes depend on the triangle count alone; counters and depth are not
- * staged: they are scratch of whatever fit runs next on the scene's stream, and the build uses the live tree's. */
-struct TreeStage {
-    DevBuf<uint4> nodes;
-    DevBuf<float4> nodesF, tris, boxMin, boxMax;
-    DevBuf<RtrBvhGrid> grid;
-    DevBuf<int32_t> parent;
-    DevBuf<uint32_t> slotOfPrim, red;
-};
-
-/* The tree of a scene.  A member is here if and only if it must not outlive the tree: its content or its size is a function of the node
- * count, the leaf order or the boxes.  rtr_scene_rebuild builds a fresh SceneTree and swaps it in whole, so whatever is here starts
- * empty with a new tree and is made again by the call that needs it; what is per customIndex, per instance or per vertex, and the
- * status of the enqueued updates, stays on rtr_scene and is kept through a rebuild. */
-namespace {
-struct SceneTree {
-    DevBuf<uint4> nodes;                 /* RtrBvhNode, 2 x uint4 each */
-    DevBuf<float4> nodesF;               /* rtr::BvhNodeF, 4 x float4 each: device build / refit only */
-    DevBuf<RtrBvhGrid> grid;
-    DevBuf<unsigned long long> wideSums;     /* scratch of bvh_make_wide */
-    DevBuf<uint4> nodes4tmp;             /* the 4-wide entries in BVH2-id order, before the breadth-first permutation */
-    DevBuf<uint32_t> wideRemap;
-    DevBuf<uint8_t> wideShape;           /* per BVH2 node: which entries its 4-wide record opens (host builder's cost-driven collapse); empty = greedy */
-    std::vector<uint8_t> hostWideShape;
-    uint32_t wideReached = 0;            /* entries the 4-wide tree reaches (they come first in nodes4) */
-    DevBuf<uint4> nodes4;                /* RtrWideNode: 4-wide view of the tree for the any-hit kernel, breadth-first order (kernels/rtr_bvh.hip) */
-    DevBuf<float4> tris;
-    std::vector<RtrBvhNode> hostNodes;
-    std::vector<RtrBvhTri> hostTris;
-    /* device build / refit state (kernels/rtr_bvh.hip) */
-    DevBuf<rtrdev::PrimRef> prims;
-    DevBuf<rtrdev::InstanceRef> instRefs;
-    DevBuf<float4> boxMin, boxMax;
-    DevBuf<int32_t> parent;
-    DevBuf<uint32_t> counters, depth, slotOfPrim, red;
-    uint32_t numPrims = 0, numNodeSlots = 0;
-    bool refitReady = false;
-    /* the triangle -> leaf table (rtr_hit_leaves, rtr_light_rays_hinted): made by the first call that asks for it (ensure_leaf_table), kept
-     * through refits, which keep topology and leaf order.  mutable: the query calls take the scene const */
-    mutable DevBuf<int32_t> leafTable;
-    mutable bool leafReady = false;
-    /* rtr_scene_tree_cost: for a tree without refit arrays whose slots are not all reachable, a parent array of its own (costParentState:
-     * 0 not looked at yet, 1 every slot is in the tree, 2 costParent holds it).  mutable: the call takes the scene const, like the leaf table */
-    mutable DevBuf<int32_t> costParent;
-    mutable int costParentState = 0;
-    /* the enqueued updates (rtr_scene_prepare_async_updates): k_wide_order's scratch (2 x numNodes words).  asyncReady: prims and instRefs
-     * are on the device for this tree, it is refit-ready, and the scratch and the scene's asyncWords and instCustom exist */
-    DevBuf<uint32_t> orderScratch;
-    bool asyncReady = false;
-    /* the enqueued rebuild (rtr_scene_prepare_async_rebuild): this tree has a device build's array sizes, and the scene's stage and
-     * build scratch exist.  Here and not on the scene: a new tree starts unprepared (a host rebuild's has other sizes) */
-    bool rebuildReady = false;
-    /* the rebuild policy (rtr_scene_prepare_async_rebuild_if): rebuildReady, the scene's policy words exist, and their baseline is the
-     * cost of THIS tree right after it was built */
-    bool rebuildIfReady = false;
-    rtr_scene_stats stats{};
-};
-}  // namespace
-
-struct rtr_scene {
-    rtr_ctx* ctx = nullptr;
-    SceneTree tree;
-    DevBuf<RtrVertex> vertices;
-    DevBuf<uint32_t> indices;
-    DevBuf<RtrObjectInfo> objects;       /* written once, by rtr_scene_create: no update, refit or rebuild call touches it ... */
-    DevBuf<float4> objectTerms;          /* ... so the per-object material terms made from it (rtrdev::launch_object_terms) are made once too */
-    DevBuf<RtrAreaLightInfo> lights;
-    DevBuf<float4> lightTris;            /* 4 x float4 per light triangle (rtrdev::launch_light_tris) */
-    DevBuf<uint32_t> lightTriFirst;      /* first record of light l */
-    DevBuf<uint32_t> triCount;           /* per customIndex: triangles of the light or of the instance's mesh (rtr_hit_surfaces' range check) */
-    uint32_t numInstances = 0;
-    /* instance cull masks (rtr_scene_set_instance_masks): one byte per instance, in instance order; empty = never set, every mask 0xff.
-     * The records carry them (bits 8..15 of flags, complemented); this table is what the getter returns and what a refit re-applies */
-    std::vector<uint8_t> hostMasks;
-    DevBuf<uint32_t> maskBits;           /* per customIndex: (~mask & 0xff) << 8, the setter kernel's table */
-    std::vector<uint32_t> hostTriCount;
-    mutable DevBuf<uint32_t> leafBase;   /* per customIndex: prefix sum of triCount (made with the tree's leaf table) */
-    DevBuf<float> xforms, nmats, ltc1, ltc2;
-    std::vector<DevBuf<uint8_t>> texPixels;
-    DevBuf<uint8_t> hdriPixels;
-    /* the sky table (rtr_scene_prepare_sky, or the first call that needs it: ensure_sky_table): the rows' 32-bit prefix sums and the 64-bit
-     * marginal sums.  The HDRI and the sky colour are fixed for the scene's life, so nothing ever remakes it.  mutable: the sky calls
-     * take the scene const, like the leaf table */
-    mutable DevBuf<uint32_t> skyRows;
-    mutable DevBuf<uint64_t> skyMarginal;
-    mutable bool skyReady = false;
-    DevBuf<rtrdev::DeviceTexture> texTable;
-    std::vector<RtrAreaLightInfo> hostLights;
-    std::vector<RtrInstance> hostInstances;
-    std::vector<RtrMesh> hostMeshes;
-    std::vector<RtrObjectInfo> hostObjects;
-    /* rtr_scene_update_vertices: the device table of ranges, their prefix counts (+ the "first bad vertex" word), and the staging
-     * buffer host data is packed into (vtxHost) and copied to (vtxStage); they grow on demand and are reused by every call */
-    DevBuf<rtrdev::VertexRange> vtxRanges;
-    DevBuf<uint32_t> vtxPrefix, vtxStage;
-    std::vector<uint32_t> vtxHost;
-    BuildScratch buildScratch;           /* rtr_scene_rebuild with RTR_BUILD_DEVICE_LBVH: empty until the first one */
-    TreeStage stage;                     /* rtr_scene_prepare_async_rebuild: kept through synchronous rebuilds, like the scratch */
-    /* an enqueued rebuild has run (or will) since stats.maxDepth was read back: refresh_mirrors takes it from the live red[7] */
-    mutable bool depthStale = false;
-    /* the rebuild policy's device memory (rtr_scene_prepare_async_rebuild_if), the scene's and not the tree's — the counts go on through
-     * a synchronous rebuild: k_tree_cost's eleven words, a pad word, then one rtrdev::RebuildIfRecord (kPolicyRecordAt) */
-    DevBuf<unsigned long long> policy;
-    /* the enqueued updates (made by rtr_scene_prepare_async_updates): the words of the enqueued chain — [0] the first bad vertex of the
-     * update in flight, [1] the entries the 4-wide tree reaches, [4..6] the sticky status (refused count, serial of the first refused
-     * update since the last status call, its first bad vertex).
-     * mirrorsStale: an enqueued update has run (or will) since the tree's hostNodes, hostTris, stats.grid, stats.boxPad and wideReached
-     * were read back; refresh_mirrors joins the stream and reads them again.  mutable: the export calls take the scene const */
-    DevBuf<uint32_t> asyncWords;
-    mutable bool mirrorsStale = false;
-    /* rtr_scene_update_instances_async: per instance, in instance order, its customIndex (fixed for the scene's life; made by
-     * rtr_scene_prepare_async_updates).  instancesStale: an enqueued instance update has run (or will) since hostInstances' transforms
-     * and hostLights were current; set together with mirrorsStale, refresh_mirrors reads them back from instRefs and lights */
-    DevBuf<uint32_t> instCustom;
-    mutable bool instancesStale = false;
-    uint64_t asyncEnqueued = 0;
-    mutable DevBuf<unsigned long long> costWords;      /* rtr_scene_tree_cost: the kernel's words */
-    DeviceScene dev{};
-    uint32_t numLights = 0, numObjects = 0, numVertices = 0, numIndices = 0;
-    bool hasLtc = false;
-};
-
-constexpr size_t kPolicyRecordAt = 12, kPolicyWords = kPolicyRecordAt + sizeof(rtrdev::RebuildIfRecord) / sizeof(unsigned long long);
-static rtrdev::RebuildIfRecord* policy_record(const rtr_scene* s) { return reinterpret_cast<rtrdev::RebuildIfRecord*>(s->policy.p + kPolicyRecordAt); }
-
-/* no geometry: the host builder's tree of such a scene is one node over one placeholder record */
-static bool scene_is_empty(const rtr_scene* s) { return s->tree.hostTris.empty() || s->tree.hostTris[0].customIndex == 0xffffffffu; }
-
-struct rtr_frame {
-    rtr_ctx* ctx = nullptr;
-    uint32_t width = 0, rows = 0, images = 0;
-    DevBuf<uint32_t> img[8];
-    uint32_t* ext[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    DevBuf<float4> hdr;
-    /* wavefront scratch */
-    DevBuf<float4> hitTuvp, rayDT, rayOrigin;      /* hit records; per ray (direction, tmax); per pixel-sample the shadow rays' origin */
-    DevBuf<uint32_t> raySlot;                      /* per ray: index of its visibility byte */
-    uint32_t slotStride = 0;                       /* distance of the visibility planes: a power of two >= the pixel-sample slots */
-    uint32_t visFill = 1;                          /* pre-fill of the visibility array for the next launch: the commoner outcome of the last one (1 = occluded) */
-    DevBuf<uint32_t> hitCustom, queueCount;
-    DevBuf<uint8_t> vis;
-    DevBuf<int32_t> spill;
-    DevBuf<uint32_t> overflow;
-    uint32_t overflowCap = 0;
-    DevBuf<uint2> batchLists;
-    DevBuf<unsigned long long> clk;
-    uint32_t listStride = 0;
-    DevBuf<Counters> counters;
-    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   /* [5]: between the any-hit kernel and k_shadow_tail */
-    hipEvent_t evMega[2] = {nullptr, nullptr};
-    rtr_frame_stats stats{};
-    bool pendingStats = false, pendingWave = false, pendingCounters = false;
-    uint32_t pendingImagesK = 0; bool pendingHdr = false, pendingAccum = false;
-    hipEvent_t evDone = nullptr;         /* a frame rendered as a later frame of a batch: recorded on the leading frame's stream behind the launch */
-    bool viaBatch = false;
-    /* ordering between a batch launch (on the leading frame's stream) and the other frames' own streams, paid only when it is needed:
-     * batchStream = the stream of the launch that last wrote this frame as a later frame of a batch and has not been joined (evDone
-     * marks its end); ownPending = the frame's own stream may still hold work for it (a launch it led); evOwn orders a later batch
-     * behind that work */
-    hipStream_t batchStream = nullptr;
-    bool ownPending = false;
-    hipEvent_t evOwn = nullptr;
-    /* rtr_render_split_async: the frame as band-shards ("parts") on streams of their own.  A part is an internal frame object — its
-     * own scratch, events, counters and context (= stream) — that owns no image: it is bound to THIS frame's images and writes its
-     * rows where they belong (RenderArgs::directRows) */
-    std::vector<rtr_ctx*> partCtx;
-    std::vector<rtr_frame*> parts;
-    std::vector<hipEvent_t> evPart;      /* part k's launches are done (recorded on its stream, waited for by this frame's) */
-    hipEvent_t evSplit[2] = {nullptr, nullptr};     /* on this frame's stream: the fork, and behind the join — the split render's duration */
-    uint32_t pendingSplit = 0;           /* parts of the split render in flight (0: the last render was not split) */
-    float4* extHdr = nullptr;            /* a part: the HDR image of the frame it belongs to */
-    uint32_t* image_ptr(int which) const { return ext[which] ? ext[which] : img[which].p; }
-    float4* hdr_ptr() const { return extHdr ? extHdr : hdr.p; }
-};
 
 /* rtr_bounce_host.cpp's way to this thread's error text */
 void rtrdev::set_last_error(const char* msg) { g_err = msg; }
@@ -347,7 +98,7 @@ uint32_t rtr_shard_rows(uint32_t height, uint32_t bandRows, uint32_t shardCount)
 /* ---- context ------------------------------------------------------------------------------ */
 /* priorityRank < 0: a stream of default priority.  >= 0: rank 0 gets the device's highest stream priority, rank 1 the next ... (the
  * parts of a split render: the dispatcher then prefers the workgroups of an earlier part wherever two parts compete for a slot) */
-static int ctx_create_prio(int ordinal, int priorityRank, rtr_ctx** out) {
+extern "C++" int rtrapi::ctx_create_prio(int ordinal, int priorityRank, rtr_ctx** out) {
     if (!out) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_ctx_create: out is null");
     *out = nullptr;
     int count = 0;
@@ -616,7 +367,7 @@ static int read_back_tree(SceneTree& t, uint32_t (&red)[8]) {
  * reached 4-wide entries k_wide_order left on the device; after an enqueued INSTANCE update also the transforms of hostInstances (from
  * the InstanceRef table, through customIndex) and hostLights.  Every call that looks at a mirror comes through here first; it costs
  * nothing while no update has been enqueued. */
-static int refresh_mirrors(const rtr_scene* cs) {
+extern "C++" int rtrapi::refresh_mirrors(const rtr_scene* cs) {
     if (!cs->mirrorsStale) return RTR_OK;
     rtr_scene* s = const_cast<rtr_scene*>(cs);
     HIP_TRY(hipSetDevice(s->ctx->device));
@@ -1775,1382 +1526,5 @@ int rtr_check_scene_limits(uint64_t numTriangles, uint64_t numNodes) {
                     (unsigned long long)numNodes, RTR_WIDE_NODE_BYTES, (unsigned long long)((kMaxBytes - 1) / RTR_WIDE_NODE_BYTES));
     return RTR_OK;
 }
-
-/* ---- frame -------------------------------------------------------------------------------- */
-/* ownImages == false: a part of a split render (no images of its own, see rtr_frame::parts) */
-static int frame_new(rtr_ctx* ctx, uint32_t width, uint32_t rows, uint32_t images, bool ownImages, rtr_frame** out) {
-    if (!ctx || !out) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_frame_create: null ctx/out");
-    if (ctx->destroyed) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_frame_create: the context has been destroyed");
-    *out = nullptr;
-    if (width == 0 || rows == 0 || width > 65536 || rows > 65536) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_frame_create: bad extent %ux%u", width, rows);
-    if (images == 0) images = RTR_IMAGES_FRAMEBUFFER;
-    const uint32_t known = 0xffu | RTR_IMG_BIT(RTR_IMAGE_HDR);
-    if (images & ~known) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_frame_create: unknown image bits 0x%x", images & ~known);
-    HIP_TRY(hipSetDevice(ctx->device));
-    rtr_frame* f = new rtr_frame();
-    f->ctx = ctx; ++ctx->children; f->width = width; f->rows = rows; f->images = images;
-    const size_t px = (size_t)width * rows;
-    hipError_t e = hipSuccess;
-    for (int i = 0; i < 8 && e == hipSuccess && ownImages; ++i)
-        if (images & RTR_IMG_BIT(i)) { e = f->img[i].alloc(px); if (e == hipSuccess) e = hipMemsetAsync(f->img[i].p, 0, px * 4, ctx->stream); }
-    if (e == hipSuccess && ownImages && (images & RTR_IMG_BIT(RTR_IMAGE_HDR))) { e = f->hdr.alloc(px); if (e == hipSuccess) e = hipMemsetAsync(f->hdr.p, 0, px * 16, ctx->stream); }
-    if (e == hipSuccess) e = f->counters.alloc(1);
-    for (int i = 0; i < 6 && e == hipSuccess; ++i) e = hipEventCreate(&f->ev[i]);
-    for (int i = 0; i < 2 && e == hipSuccess; ++i) e = hipEventCreate(&f->evMega[i]);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) { rtr_frame_destroy(f); return fail(e == hipErrorOutOfMemory ? RTR_ERR_OUT_OF_MEMORY : RTR_ERR_HIP, "rtr_frame_create: %s", hipGetErrorString(e)); }
-    *out = f;
-    return RTR_OK;
-}
-
-int rtr_frame_create(rtr_ctx* ctx, uint32_t width, uint32_t rows, uint32_t images, rtr_frame** out) {
-    return frame_new(ctx, width, rows, images, true, out);
-}
-
-void rtr_frame_destroy(rtr_frame* f) {
-    if (!f) return;
-    (void)hipSetDevice(f->ctx->device);
-    (void)hipStreamSynchronize(f->ctx->stream);
-    for (auto& e : f->ev) if (e) (void)hipEventDestroy(e);
-    for (auto& e : f->evMega) if (e) (void)hipEventDestroy(e);
-    if (f->evDone) { (void)hipEventSynchronize(f->evDone); (void)hipEventDestroy(f->evDone); }
-    if (f->evOwn) (void)hipEventDestroy(f->evOwn);
-    for (rtr_frame* part : f->parts) rtr_frame_destroy(part);
-    for (rtr_ctx* pc : f->partCtx) rtr_ctx_destroy(pc);
-    for (auto& e : f->evPart) if (e) (void)hipEventDestroy(e);
-    for (auto& e : f->evSplit) if (e) (void)hipEventDestroy(e);
-    rtr_ctx* c = f->ctx;
-    delete f;
-    ctx_release_child(c);
-}
-
-int rtr_frame_bind_external(rtr_frame* f, int which, void* dptr, size_t bytes) {
-    if (!f || which < 0 || which > 7) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_frame_bind_external: bad argument");
-    if (dptr && bytes != (size_t)f->width * f->rows * 4) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_frame_bind_external: %zu bytes given, image is %zu", bytes, (size_t)f->width * f->rows * 4);
-    if (dptr && ((uintptr_t)dptr & 3u)) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_frame_bind_external: pointer not 4-byte aligned");
-    f->ext[which] = (uint32_t*)dptr;
-    if (dptr) f->images |= RTR_IMG_BIT(which);
-    return RTR_OK;
-}
-
-int rtr_frame_device_ptr(const rtr_frame* f, int which, void** dptr, size_t* bytes) {
-    if (!f || !dptr) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_frame_device_ptr: null argument");
-    if (which == RTR_IMAGE_HDR) {
-        if (!f->hdr.p) return fail(RTR_ERR_INVALID_ARGUMENT, "frame has no HDR image");
-        *dptr = f->hdr.p; if (bytes) *bytes = (size_t)f->width * f->rows * 16; return RTR_OK;
-    }
-    if (which < 0 || which > 7 || !f->image_ptr(which)) return fail(RTR_ERR_INVALID_ARGUMENT, "frame has no image %d", which);
-    *dptr = f->image_ptr(which); if (bytes) *bytes = (size_t)f->width * f->rows * 4;
-    return RTR_OK;
-}
-
-int rtr_frame_download(const rtr_frame* f, int which, void* dst, size_t bytes) {
-    if (!f || !dst) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_frame_download: null argument");
-    void* src = nullptr; size_t need = 0;
-    int rc = rtr_frame_device_ptr(f, which, &src, &need);
-    if (rc != RTR_OK) return rc;
-    if (bytes != need) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_frame_download: %zu bytes given, image %d is %zu", bytes, which, need);
-    HIP_TRY(hipSetDevice(f->ctx->device));
-    if (f->viaBatch) HIP_TRY(hipEventSynchronize(f->evDone));          /* its pixels came from another frame's stream */
-    HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, f->ctx->stream));
-    HIP_TRY(hipStreamSynchronize(f->ctx->stream));
-    return RTR_OK;
-}
-
-/* Work about to be enqueued for `f` on its own stream comes behind a batch launch on another stream that wrote it last (the launch
- * runs on its leading frame's stream), and a later batch must come behind this work (ownPending): the ordering contract of
- * rtr_render_batch_async for everything that is not itself a render */
-static int order_on_own_stream(rtr_frame* f) {
-    hipStream_t st = f->ctx->stream;
-    if (f->batchStream && f->batchStream != st) HIP_TRY(hipStreamWaitEvent(st, f->evDone, 0));
-    f->batchStream = nullptr;
-    f->ownPending = true;
-    return RTR_OK;
-}
-
-int rtr_frame_clear(rtr_frame* f) {
-    if (!f) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_frame_clear: null frame");
-    HIP_TRY(hipSetDevice(f->ctx->device));
-    { const int rc = order_on_own_stream(f); if (rc != RTR_OK) return rc; }
-    const size_t px = (size_t)f->width * f->rows;
-    for (int i = 0; i < 8; ++i) if (f->image_ptr(i)) HIP_TRY(hipMemsetAsync(f->image_ptr(i), 0, px * 4, f->ctx->stream));
-    if (f->hdr.p) HIP_TRY(hipMemsetAsync(f->hdr.p, 0, px * 16, f->ctx->stream));
-    HIP_TRY(hipStreamSynchronize(f->ctx->stream));
-    return RTR_OK;
-}
-
-/* ---- dispatch ------------------------------------------------------------------------------ */
-/* Enqueues one launch of the pipeline over n frames (n = 1: rtr_render / rtr_render_async).  frames[0] leads: its context's stream
- * carries the work, its scratch holds the batch, its statistics describe the launch. */
-static_assert(RTR_MAX_BATCH == rtrdev::kMaxBatch, "include/rtr.h and kernels/rtr_device.h disagree on the frames per launch");
-static int enqueue_render(rtr_scene* s, const RtrCameraData* cams, const RtrSceneInfo* infos, const rtr_render_params* pin, rtr_frame* const* frames, uint32_t n, bool direct = false) {
-    if (!s || !cams || !infos || !pin || !frames || n < 1 || !frames[0]) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_render: null argument");
-    if (n > rtrdev::kMaxBatch) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_render_batch_async: %u frames, at most %u per launch", n, rtrdev::kMaxBatch);
-    rtr_frame* f = frames[0];
-    /* work is enqueued on the (leading) FRAME's context stream; the (read-only) scene may belong to another context of the same
-     * device, so two frames on two streams can be in flight against one scene */
-    if (s->ctx->device != f->ctx->device) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_render: scene and frame live on different devices");
-    rtr_render_params p = *pin;
-    if (p.bandRows == 0) p.bandRows = 8;
-    if (p.shardCount == 0) p.shardCount = 1;
-    if (p.images == 0) p.images = RTR_IMAGES_FRAMEBUFFER;
-    if (p.width == 0 || p.height == 0 || p.spp == 0 || p.spp > 1024 || p.numShadowRays > 1024)
-        return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_render: bad width/height/spp/numShadowRays (%u,%u,%u,%u)", p.width, p.height, p.spp, p.numShadowRays);
-    if (p.bandRows % 8u) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_render: bandRows %u must be a multiple of 8 (one wave = one 8x8 tile)", p.bandRows);
-    if (p.shardIndex >= p.shardCount) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_render: shardIndex %u >= shardCount %u", p.shardIndex, p.shardCount);
-    const uint32_t rows = rtr_shard_rows(p.height, p.bandRows, p.shardCount);
-    const uint32_t frameRows = direct ? p.height : rows;     /* direct: the images are the whole frame, this shard writes its own rows of them */
-    if (p.images & RTR_IMAGES_DENOISE) return fail(RTR_ERR_UNSUPPORTED, "rtr_render: denoise/combine images are produced by rtr_denoise_combine, not by the ray-gen dispatch");
-    if ((p.images & RTR_IMG_BIT(RTR_IMAGE_ANALYTIC)) && !s->hasLtc) return fail(RTR_ERR_UNSUPPORTED, "rtr_render: RTR_IMAGE_ANALYTIC needs the LTC tables (rtr_scene_desc.ltc1/ltc2)");
-    const bool wantHdr = (p.images & RTR_IMG_BIT(RTR_IMAGE_HDR)) != 0 || p.accumulate;
-    if (n > 1 && p.pipeline == 1) return fail(RTR_ERR_UNSUPPORTED, "rtr_render_batch_async: the megakernel renders one frame per launch");
-
-    rtrdev::FrameBatch fb{};
-    fb.n = n;
-    uint32_t k = 0;
-    uint64_t maxRays = 1;
-    for (uint32_t b = 0; b < n; ++b) {
-        rtr_frame* fr = frames[b];
-        if (!fr) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_render_batch_async: frame %u is null", b);
-        for (uint32_t c = 0; c < b; ++c) if (frames[c] == fr) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_render_batch_async: frame %u given twice", b);
-        if (fr->ctx->device != f->ctx->device) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_render_batch_async: frame %u lives on another device", b);
-        if (infos[b].numAreaLights > s->numLights) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_render: SceneInfo.numAreaLights %u > scene lights %u", infos[b].numAreaLights, s->numLights);
-        if (infos[b].numAreaLights != infos[0].numAreaLights) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_render_batch_async: the frames of a launch must use the same number of area lights");
-        if (fr->width != p.width || fr->rows != frameRows) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_render: frame is %ux%u, this shard needs %ux%u", fr->width, fr->rows, p.width, frameRows);
-        if (wantHdr && !fr->hdr_ptr()) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_render: HDR accumulation requested but the frame has no RTR_IMAGE_HDR");
-        FrameOut& fo = fb.fo[b];
-        k = 0;
-        for (int i = 0; i < 8; ++i) {
-            fo.img[i] = nullptr;
-            if (p.images & RTR_IMG_BIT(i)) {
-                if (!fr->image_ptr(i)) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_render: image %d requested but not in the frame", i);
-                fo.img[i] = fr->image_ptr(i); ++k;
-            }
-        }
-        fo.hdr = wantHdr ? fr->hdr_ptr() : nullptr;
-        RenderArgs& ra = fb.ra[b];
-        ra.cam = cams[b]; ra.info = infos[b];
-        ra.width = p.width; ra.height = p.height; ra.spp = p.spp; ra.numShadowRays = p.numShadowRays;
-        ra.bandRows = p.bandRows; ra.shardIndex = p.shardIndex; ra.shardCount = p.shardCount;
-        ra.localRows = rows; ra.tilesPerRow = (p.width + 7u) / 8u;
-        ra.images = p.images; ra.accumulate = p.accumulate; ra.accumulatedFrames = p.accumulatedFrames; ra.directRows = direct ? 1u : 0u;
-        if (b == 0) for (uint32_t l = 0; l < infos[0].numAreaLights; ++l) maxRays += (uint64_t)s->hostLights[l].numTriangles * p.numShadowRays;
-        ra.maxRaysPerSample = (uint32_t)maxRays;
-    }
-    const RenderArgs& ra = fb.ra[0];
-    const FrameOut& fo = fb.fo[0];
-
-    HIP_TRY(hipSetDevice(f->ctx->device));
-    hipStream_t st = f->ctx->stream;
-    Counters* dstats = nullptr;
-    if (p.collectStats) { HIP_TRY(hipMemsetAsync(f->counters.p, 0, sizeof(Counters), st)); dstats = f->counters.p; }
-
-    const uint64_t paddedPixels = (uint64_t)((rows + 7u) / 8u) * ra.tilesPerRow * 64u;
-    const uint64_t blocks = (paddedPixels + 255u) / 256u;
-    const uint64_t nPS = blocks * 256u * p.spp * n;          /* pixel-sample slots of the launch */
-    const uint64_t nRays = nPS * maxRays;                    /* queue capacity: every pixel-sample issuing every query */
-    uint64_t slotStride = 256;                                /* the visibility planes are a power of two apart, so a slot names its pixel-sample with a mask */
-    while (slotStride < nPS) slotStride <<= 1;
-    const uint64_t nSlots = slotStride * maxRays;
-    bool wave = p.pipeline != 1;
-    if (wave && (nSlots >= (1ull << 31) || maxRays > 4096)) {
-        if (p.pipeline == 2 || n > 1) return fail(RTR_ERR_UNSUPPORTED, "rtr_render: wavefront scratch would need %llu visibility slots", (unsigned long long)nSlots);
-        wave = false;
-    }
-    if (blocks * n >= (1ull << 31)) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_render: frame too large");
-
-    /* the counting form IS the timed kernel template; the 2-wide comparison kernel has none, and counting another kernel's work
-     * under its name would be a wrong number */
-    if (wave && p.collectStats && f->ctx->tun.trace_bvh4 == 0u)
-        return fail(RTR_ERR_UNSUPPORTED, "rtr_render: collectStats with the tunable trace_bvh4 = 0: the 2-wide comparison kernel has no counting form (set it back to 1, or render with pipeline 1)");
-    f->pendingWave = wave; f->pendingCounters = p.collectStats != 0;
-    f->pendingImagesK = k; f->pendingHdr = wantHdr; f->pendingAccum = p.accumulate != 0;
-    memset(&f->stats, 0, sizeof f->stats);
-    f->stats.localRows = rows; f->stats.localPixels = rows * p.width * n;
-    f->viaBatch = false; f->pendingSplit = 0;
-    /* The launch runs on THIS frame's stream.  What another stream still holds for one of its frames comes first: a launch the frame
-     * led on its own stream (ownPending), or a batch on a third stream that wrote it (batchStream).  In steady state — the same
-     * frames batched behind the same leader, or frames joined between uses — neither is set and nothing is enqueued here (cross-stream
-     * waits on every launch cost 3 % of the frame rate at N = 1 and 25 % on a 1/8 shard: profiles/r03/ab_batch_stream_order.log). */
-    if (f->batchStream && f->batchStream != st) HIP_TRY(hipStreamWaitEvent(st, f->evDone, 0));
-    f->batchStream = nullptr;
-    for (uint32_t b = 1; b < n; ++b) {
-        rtr_frame* fr = frames[b];
-        if (fr->ownPending && fr->ctx->stream != st) {
-            if (!fr->evOwn) HIP_TRY(hipEventCreateWithFlags(&fr->evOwn, hipEventDisableTiming));
-            HIP_TRY(hipEventRecord(fr->evOwn, fr->ctx->stream));
-            HIP_TRY(hipStreamWaitEvent(st, fr->evOwn, 0));
-        }
-        if (fr->batchStream && fr->batchStream != st) HIP_TRY(hipStreamWaitEvent(st, fr->evDone, 0));
-    }
-    hipError_t e;
-    if (wave) {
-        /* the list of rays left to the redo kernels: the camera rays' needs one entry per pixel-sample at most; the any-hit kernel's
-         * gets 1/16 of the queue (at least 2^20 entries) and k_shadow_tail redoes the whole queue should that ever overflow */
-        uint64_t ovCap = std::max<uint64_t>(std::max<uint64_t>(nPS, nRays / 16), 1ull << 20);
-        if (ovCap > nRays) ovCap = std::max<uint64_t>(nRays, nPS);
-        if (f->hitTuvp.n < nPS) { HIP_TRY(f->hitTuvp.alloc(nPS)); HIP_TRY(f->hitCustom.alloc(nPS)); HIP_TRY(f->rayOrigin.alloc(nPS)); }
-        if (f->vis.n < nSlots) HIP_TRY(f->vis.alloc(nSlots));
-        if (f->rayDT.n < nRays) { HIP_TRY(f->rayDT.alloc(nRays)); HIP_TRY(f->raySlot.alloc(nRays)); }
-        /* every array is (re)sized by its OWN need: the redo list is also k_primary's (one entry per pixel-sample at most), and a
-         * launch with fewer queries per sample but more samples than an earlier one needs a longer list with a shorter queue */
-        if (f->overflow.n < ovCap + 1) HIP_TRY(f->overflow.alloc(ovCap + 1));
-        f->overflowCap = (uint32_t)std::min<uint64_t>(ovCap, f->overflow.n - 1);      /* what the any-hit kernel may use of it */
-#ifdef RTR_TEST_HOOKS
-        if (const char* e = getenv("RTR_TRACE_OVERFLOW_CAP")) { const uint64_t v = strtoull(e, nullptr, 10); if (v >= 1 && v < f->overflowCap) f->overflowCap = (uint32_t)v; }   /* a list short enough to overflow */
-#endif
-        {   /* batch lists of the binned queue (octant x consumer XCD): a run's batches are dealt round-robin to the eight lists of
-             * its octant, so a list holds at most 1/8 of one batch per 64 rays (the smallest batch) + one per k_shadow_gen_oct workgroup */
-            const uint64_t ls = nRays / 64 / rtrdev::kQueueRegions + nPS / 256 + 16;
-            if ((uint64_t)f->listStride < ls) { HIP_TRY(f->batchLists.alloc((size_t)ls * rtrdev::kQueueLists)); f->listStride = (uint32_t)ls; }
-        }
-        f->slotStride = (uint32_t)slotStride;
-        if (!f->queueCount.p) HIP_TRY(f->queueCount.alloc(rtrdev::kQueueCtrlWords));
-        if (!f->clk.p) { HIP_TRY(f->clk.alloc(2 * rtrdev::kQueueRegions)); HIP_TRY(hipMemsetAsync(f->clk.p, 0, 2 * rtrdev::kQueueRegions * sizeof(unsigned long long), st)); }
-        if (!f->spill.p) HIP_TRY(f->spill.alloc(rtrdev::kSpillInts));      /* 64 entries x the redo kernels' grid */
-        Workspace ws;
-        ws.hitTuvp = f->hitTuvp.p; ws.hitCustom = f->hitCustom.p; ws.vis = f->vis.p; ws.visFill = f->visFill;
-        ws.visPlaneBytes = (size_t)nPS; ws.visPlanes = (uint32_t)maxRays;      /* what a launch fills: the first nPS bytes of each of the maxRays planes, not the power-of-two pitch between them */
-#ifdef RTR_TEST_HOOKS
-        if (const char* e = getenv("RTR_TRACE_VIS_FILL")) if ((e[0] == '0' || e[0] == '1') && !e[1]) ws.visFill = (uint32_t)(e[0] - '0');      /* force the pre-fill */
-#endif
-        ws.rayQueue.dt = f->rayDT.p; ws.rayQueue.slot = f->raySlot.p; ws.rayQueue.origin = f->rayOrigin.p; ws.rayQueue.slotStride = f->slotStride; ws.rayQueue.slotMask = f->slotStride - 1u;
-        ws.queueCount = f->queueCount.p; ws.capPixelSamples = nPS; ws.capRays = nRays; ws.spill = f->spill.p; ws.overflow = f->overflow.p; ws.overflowCap = f->overflowCap; ws.batchLists = f->batchLists.p; ws.listStride = f->listStride; ws.clk = f->clk.p;
-        e = rtrdev::launch_wavefront(s->dev, fb, ws, f->ctx->tun, (int)s->tree.stats.stackEntries, dstats, st, f->ev, (uint32_t)f->ctx->prop.multiProcessorCount);
-    } else {
-        (void)hipEventRecord(f->evMega[0], st);
-        e = rtrdev::launch_megakernel(s->dev, ra, fo, (int)s->tree.stats.stackEntries, dstats, st);
-        (void)hipEventRecord(f->evMega[1], st);
-    }
-    if (e != hipSuccess) return fail(RTR_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
-    f->pendingStats = true;
-    f->ownPending = true;
-    /* ... and each of the other frames gets an event behind the launch: rtr_frame_wait / rtr_frame_download wait on it, and so does
-     * the stream of whatever launch writes the frame next (above) */
-    for (uint32_t b = 1; b < n; ++b) {
-        rtr_frame* fr = frames[b];
-        if (!fr->evDone) HIP_TRY(hipEventCreateWithFlags(&fr->evDone, hipEventDisableTiming));
-        HIP_TRY(hipEventRecord(fr->evDone, st));
-        fr->batchStream = st;
-        fr->viaBatch = true; fr->pendingStats = false;
-        memset(&fr->stats, 0, sizeof fr->stats);
-    }
-    return RTR_OK;
-}
-
-int rtr_render_batch_limit(const rtr_scene* s, const rtr_render_params* pin, uint32_t numAreaLights, uint32_t* maxFrames) {
-    if (!s || !pin || !maxFrames) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_render_batch_limit: null argument");
-    if (numAreaLights > s->numLights) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_render_batch_limit: %u area lights, the scene has %u", numAreaLights, s->numLights);
-    rtr_render_params p = *pin;
-    if (p.bandRows == 0) p.bandRows = 8;
-    if (p.shardCount == 0) p.shardCount = 1;
-    if (p.width == 0 || p.height == 0 || p.spp == 0 || p.bandRows % 8u) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_render_batch_limit: bad width/height/spp/bandRows");
-    *maxFrames = 1;
-    if (p.pipeline == 1) return RTR_OK;
-    /* the arithmetic of enqueue_render() */
-    uint64_t maxRays = 1;
-    for (uint32_t l = 0; l < numAreaLights; ++l) maxRays += (uint64_t)s->hostLights[l].numTriangles * p.numShadowRays;
-    const uint32_t rows = rtr_shard_rows(p.height, p.bandRows, p.shardCount);
-    const uint64_t blocks = ((uint64_t)((rows + 7u) / 8u) * ((p.width + 7u) / 8u) * 64u + 255u) / 256u;
-    for (uint32_t n = rtrdev::kMaxBatch; n > 1; --n) {
-        const uint64_t nPS = blocks * 256u * p.spp * n;
-        uint64_t slotStride = 256;
-        while (slotStride < nPS) slotStride <<= 1;
-        if (slotStride * maxRays < (1ull << 31) && maxRays <= 4096 && blocks * n < (1ull << 31)) { *maxFrames = n; break; }
-    }
-    return RTR_OK;
-}
-
-/* One frame as `parts` band-shards, each on a stream of its own, all writing their rows of the SAME images: the kernels of one frame
- * are a dependency chain and each ends in a tail, so part k+1's camera rays and queue build run under part k's traversal and its
- * traversal fills the tail of part k's — frames in flight, inside one frame. */
-int rtr_render_split_async(rtr_scene* s, const RtrCameraData* cam, const RtrSceneInfo* info, const rtr_render_params* pin, rtr_frame* f, uint32_t parts) {
-    if (!s || !cam || !info || !pin || !f) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_render_split_async: null argument");
-    if (parts < 1 || parts > RTR_MAX_SPLIT) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_render_split_async: %u parts, 1 to %d", parts, RTR_MAX_SPLIT);
-    if (pin->shardCount > 1) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_render_split_async: the frame must be whole (shardCount %u); a shard of a multi-GPU frame is not split again", pin->shardCount);
-    if (f->extHdr) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_render_split_async: not a frame of the caller's");
-    rtr_render_params p = *pin;
-    if (p.bandRows == 0) p.bandRows = 8;
-    if (p.bandRows % 8u) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_render_split_async: bandRows %u must be a multiple of 8", p.bandRows);
-    if (p.height == 0 || p.width == 0) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_render_split_async: empty frame");
-    const uint32_t bands = (p.height + p.bandRows - 1) / p.bandRows;
-    if (parts > bands) parts = bands;                 /* never a part without a band */
-    if (parts <= 1) { p.shardIndex = 0; p.shardCount = 1; return enqueue_render(s, cam, info, &p, &f, 1); }
-    if (f->width != p.width || f->rows != p.height) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_render_split_async: frame is %ux%u, the whole frame is %ux%u", f->width, f->rows, p.width, p.height);
-    HIP_TRY(hipSetDevice(f->ctx->device));
-    hipStream_t st = f->ctx->stream;
-    /* the parts: internal frame objects (scratch, events, counters; no images) on contexts (streams) of their own */
-    while (f->parts.size() < parts) {
-        rtr_ctx* pc = nullptr; rtr_frame* pf = nullptr;
-        int rc = ctx_create_prio(f->ctx->device, f->ctx->tun.split_priorities ? (int)f->parts.size() : -1, &pc);
-        if (rc != RTR_OK) return rc;
-        rc = frame_new(pc, f->width, f->rows, f->images, false, &pf);
-        if (rc != RTR_OK) { rtr_ctx_destroy(pc); return rc; }
-        hipEvent_t ev = nullptr;
-        hipError_t e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-        if (e != hipSuccess) { rtr_frame_destroy(pf); rtr_ctx_destroy(pc); return fail(RTR_ERR_HIP, "hipEventCreate: %s", hipGetErrorString(e)); }
-        f->partCtx.push_back(pc); f->parts.push_back(pf); f->evPart.push_back(ev);
-    }
-    for (auto& e : f->evSplit) if (!e) HIP_TRY(hipEventCreate(&e));
-    /* what another stream still holds for this frame comes first (enqueue_render's rule) */
-    if (f->batchStream && f->batchStream != st) HIP_TRY(hipStreamWaitEvent(st, f->evDone, 0));
-    f->batchStream = nullptr;
-    HIP_TRY(hipEventRecord(f->evSplit[0], st));          /* the fork */
-    /* A failure inside the loop must not leave the frame's stream un-joined from parts that were already enqueued (a download, clear
-     * or denoise that follows would race them, and rtr_frame_wait would never collect them): the error is kept, every part that WAS
-     * enqueued is joined, the frame is marked pending for exactly those, and then the error is returned. */
-    int rc = RTR_OK;
-    uint32_t started = 0;
-    auto hip_keep = [&](hipError_t e, const char* what) {
-        if (e != hipSuccess && rc == RTR_OK) rc = fail(RTR_ERR_HIP, "rtr_render_split_async: %s: %s", what, hipGetErrorString(e));
-        return e == hipSuccess;
-    };
-    for (uint32_t k = 0; k < parts && rc == RTR_OK; ++k) {
-        rtr_frame* pf = f->parts[k];
-        pf->ctx->tun = f->ctx->tun;
-        pf->images = f->images;
-        for (int i = 0; i < 8; ++i) pf->ext[i] = f->image_ptr(i);
-        pf->extHdr = f->hdr.p;
-        hipStream_t ps = pf->ctx->stream;
-        if (!hip_keep(hipStreamWaitEvent(ps, f->evSplit[0], 0), "hipStreamWaitEvent (fork)")) break;
-        p.shardIndex = k; p.shardCount = parts;
-        const int prc = enqueue_render(s, cam, info, &p, &pf, 1, true);
-        if (prc != RTR_OK) { rc = prc; break; }
-        ++started;                                              /* from here on part k has work on its stream: it must be joined */
-        if (hip_keep(hipEventRecord(f->evPart[k], ps), "hipEventRecord (part)")) hip_keep(hipStreamWaitEvent(st, f->evPart[k], 0), "hipStreamWaitEvent (join)");
-        else hip_keep(hipStreamSynchronize(ps), "hipStreamSynchronize (join of last resort)");      /* no event to order behind: drain the part here */
-    }
-    hip_keep(hipEventRecord(f->evSplit[1], st), "hipEventRecord (join)");
-    f->ownPending = true; f->viaBatch = false;
-    f->pendingSplit = started; f->pendingStats = started != 0;
-    return rc;
-}
-
-int rtr_render_split(rtr_scene* s, const RtrCameraData* cam, const RtrSceneInfo* info, const rtr_render_params* p, rtr_frame* f, uint32_t parts) {
-    int rc = rtr_render_split_async(s, cam, info, p, f, parts);
-    if (rc != RTR_OK) return rc;
-    return rtr_frame_wait(f);
-}
-
-/* joins a split render and makes the frame's statistics out of its parts': counters and per-kernel times are SUMS over the parts (the
- * parts' kernels overlap: the sum of their durations exceeds the frame's), totalMs is the frame's own duration, fork to join */
-static int wait_split(rtr_frame* f) {
-    const uint32_t parts = f->pendingSplit;
-    f->pendingSplit = 0; f->pendingStats = false;
-    rtr_frame_stats t; memset(&t, 0, sizeof t);
-    double clk = 0; uint32_t nclk = 0;
-    for (uint32_t k = 0; k < parts; ++k) {
-        int rc = rtr_frame_wait(f->parts[k]);
-        if (rc != RTR_OK) return rc;
-        const rtr_frame_stats& a = f->parts[k]->stats;
-        t.numRays += a.numRays; t.numPrimaryRays += a.numPrimaryRays; t.numShadowRays += a.numShadowRays; t.numNodeVisits += a.numNodeVisits;
-        t.numTriTests += a.numTriTests; t.numHits += a.numHits; t.numLightFetches += a.numLightFetches; t.numLightTriFetches += a.numLightTriFetches;
-        t.numTexFetches += a.numTexFetches; t.numAlphaTests += a.numAlphaTests; t.algorithmicBytes += a.algorithmicBytes;
-        t.numShadowNodeVisits += a.numShadowNodeVisits; t.numShadowTriTests += a.numShadowTriTests; t.shadowTraceBytes += a.shadowTraceBytes;
-        t.primaryMs += a.primaryMs; t.shadowGenMs += a.shadowGenMs; t.shadowTraceMs += a.shadowTraceMs; t.resolveMs += a.resolveMs; t.shadowTailMs += a.shadowTailMs;
-        t.localRows += a.localRows; t.localPixels += a.localPixels; t.pipelineUsed = a.pipelineUsed;
-        t.shadowInnerIterations += a.shadowInnerIterations; t.shadowInnerActiveLanes += a.shadowInnerActiveLanes;
-        t.shadowTriIterations += a.shadowTriIterations; t.shadowTriActiveLanes += a.shadowTriActiveLanes; t.shadowRefills += a.shadowRefills;
-        t.primaryTailRays += a.primaryTailRays; t.shadowTailRays += a.shadowTailRays;
-        if (a.shadowTraceClockMHz > 0.f) {
-            clk += a.shadowTraceClockMHz; ++nclk;
-            t.shadowTraceClockMinMHz = (t.shadowTraceClockMinMHz == 0.f || a.shadowTraceClockMinMHz < t.shadowTraceClockMinMHz) ? a.shadowTraceClockMinMHz : t.shadowTraceClockMinMHz;
-            t.shadowTraceClockMaxMHz = a.shadowTraceClockMaxMHz > t.shadowTraceClockMaxMHz ? a.shadowTraceClockMaxMHz : t.shadowTraceClockMaxMHz;
-        }
-    }
-    if (nclk) t.shadowTraceClockMHz = (float)(clk / nclk);
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, f->evSplit[0], f->evSplit[1]);
-    t.totalMs = ms;
-    f->stats = t;
-    return RTR_OK;
-}
-
-int rtr_frame_wait(rtr_frame* f) {
-    if (!f) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_frame_wait: null frame");
-    HIP_TRY(hipSetDevice(f->ctx->device));
-    HIP_TRY(hipStreamSynchronize(f->ctx->stream));
-    f->ownPending = false;
-    if (f->pendingSplit) return wait_split(f);
-    if (f->viaBatch) { HIP_TRY(hipEventSynchronize(f->evDone)); f->batchStream = nullptr; return RTR_OK; }      /* rendered in another frame's launch: that launch's times and counters are the leading frame's */
-    if (!f->pendingStats) return RTR_OK;
-    f->pendingStats = false;
-    rtr_frame_stats& s = f->stats;
-    if (f->pendingWave) {
-        float a = 0, b = 0, c = 0, d = 0;
-        (void)hipEventElapsedTime(&a, f->ev[0], f->ev[1]);
-        (void)hipEventElapsedTime(&b, f->ev[1], f->ev[2]);
-        (void)hipEventElapsedTime(&c, f->ev[2], f->ev[5]);
-        float tail = 0;
-        (void)hipEventElapsedTime(&tail, f->ev[5], f->ev[3]);
-        s.shadowTailMs = tail;
-        (void)hipEventElapsedTime(&d, f->ev[3], f->ev[4]);
-        s.primaryMs = a; s.shadowGenMs = b; s.shadowTraceMs = c; s.resolveMs = d; s.totalMs = a + b + c + tail + d;
-        s.pipelineUsed = 2;
-        if (f->clk.p) {      /* shader clock held during the any-hit launch: s_memtime ticks over 100-MHz ticks of one wave per XCD; the MEAN over the XCDs — they clock
-                              * independently (2.25 ... 2.40 GHz within one launch on a warm part) and the launch's vector-issue capacity is the sum of theirs */
-            unsigned long long h[2 * rtrdev::kQueueRegions];
-            HIP_TRY(hipMemcpy(h, f->clk.p, sizeof h, hipMemcpyDeviceToHost));
-            float mhz[rtrdev::kQueueRegions]; int nv = 0;
-            for (uint32_t r = 0; r < rtrdev::kQueueRegions; ++r) if (h[2 * r + 1]) mhz[nv++] = (float)((double)h[2 * r] / (double)h[2 * r + 1] * 100.0);
-            for (int i = 1; i < nv; ++i) for (int j = i; j > 0 && mhz[j] < mhz[j - 1]; --j) { const float t = mhz[j]; mhz[j] = mhz[j - 1]; mhz[j - 1] = t; }
-            double sum = 0; for (int i = 0; i < nv; ++i) sum += mhz[i];
-            s.shadowTraceClockMHz = nv ? (float)(sum / nv) : 0.f;
-            s.shadowTraceClockMinMHz = nv ? mhz[0] : 0.f; s.shadowTraceClockMaxMHz = nv ? mhz[nv - 1] : 0.f;
-        }
-        if (f->queueCount.p) {      /* the next launch pre-fills the visibility array with this one's commoner outcome */
-            uint32_t q[4] = {0, 0, 0, 0};
-            HIP_TRY(hipMemcpy(q, f->queueCount.p, sizeof q, hipMemcpyDeviceToHost));
-            if (q[0]) f->visFill = (2ull * q[3] >= q[0]) ? 1u : 0u;
-        }
-    } else {
-        float a = 0;
-        (void)hipEventElapsedTime(&a, f->evMega[0], f->evMega[1]);
-        s.primaryMs = a; s.totalMs = a;
-        s.pipelineUsed = 1;
-    }
-    if (f->pendingCounters) {
-        Counters h;
-        HIP_TRY(hipMemcpy(&h, f->counters.p, sizeof h, hipMemcpyDeviceToHost));
-        s.numRays = h.rays; s.numPrimaryRays = h.primary; s.numShadowRays = h.shadow;
-        s.numNodeVisits = h.nodes; s.numTriTests = h.tris; s.numHits = h.hits;
-        s.numLightFetches = h.lightFetch; s.numLightTriFetches = h.lightTriFetch;
-        s.numShadowNodeVisits = h.shadowNodes; s.numShadowTriTests = h.shadowTris;
-        s.numTexFetches = h.texFetch; s.numAlphaTests = h.alphaTests;
-        const uint64_t shadowNodeBytes = f->pendingWave ? RTR_WIDE_NODE_BYTES : RTR_BVH_NODE_BYTES;     /* the megakernel walks the BVH2 for its shadow rays too */
-        s.shadowTraceBytes = shadowNodeBytes * h.shadowNodes + 48ull * h.shadowTris + 37ull * h.shadow;      /* per ray: 20 B of queue record + the 16-B origin of its pixel-sample + its visibility byte */
-        s.shadowInnerIterations = h.innerIters; s.shadowInnerActiveLanes = h.innerLanes;
-        s.shadowTriIterations = h.triIters; s.shadowTriActiveLanes = h.triLanes; s.shadowRefills = h.refills;
-        if (f->overflow.p) { uint32_t ov = 0; HIP_TRY(hipMemcpy(&ov, f->overflow.p, sizeof ov, hipMemcpyDeviceToHost)); s.shadowTailRays = ov; }
-        if (f->pendingWave && f->queueCount.p) { uint32_t rd = 0; HIP_TRY(hipMemcpy(&rd, f->queueCount.p + 2, sizeof rd, hipMemcpyDeviceToHost)); s.primaryTailRays = rd; }
-        s.algorithmicBytes = (uint64_t)RTR_BVH_NODE_BYTES * (h.nodes - h.shadowNodes) + shadowNodeBytes * h.shadowNodes + 48ull * h.tris + 236ull * (h.hits + h.alphaTests) + 96ull * h.lightFetch + 156ull * h.lightTriFetch +
-                             16ull * h.texFetch +
-                             4ull * f->pendingImagesK * s.localPixels + (f->pendingHdr ? (f->pendingAccum ? 32ull : 16ull) * s.localPixels : 0ull);
-    }
-    return RTR_OK;
-}
-
-int rtr_render_async(rtr_scene* s, const RtrCameraData* cam, const RtrSceneInfo* info, const rtr_render_params* p, rtr_frame* f) {
-    return enqueue_render(s, cam, info, p, &f, 1);
-}
-
-int rtr_render_batch_async(rtr_scene* s, const RtrCameraData* cams, const RtrSceneInfo* infos, const rtr_render_params* p, rtr_frame* const* frames, uint32_t n) {
-    return enqueue_render(s, cams, infos, p, frames, n);
-}
-
-int rtr_render(rtr_scene* s, const RtrCameraData* cam, const RtrSceneInfo* info, const rtr_render_params* p, rtr_frame* f) {
-    int rc = enqueue_render(s, cam, info, p, &f, 1);
-    if (rc != RTR_OK) return rc;
-    return rtr_frame_wait(f);
-}
-
-int rtr_frame_get_stats(const rtr_frame* f, rtr_frame_stats* out) {
-    if (!f || !out) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_frame_get_stats: null argument");
-    *out = f->stats;
-    return RTR_OK;
-}
-
-/* the checks, launches and ping-pong of rtr_denoise_combine, enqueued on the frame's context stream (behind a batch launch that wrote
- * the frame on another stream, and ahead of a later one: order_on_own_stream) */
-static int enqueue_denoise_combine(rtr_frame* f, int iterations, const char* who) {
-    if (!f) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: null frame", who);
-    if (iterations < 0 || iterations > 64) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: iterations %d", who, iterations);
-    for (int i = 0; i < 8; ++i)
-        if (!f->image_ptr(i)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: the frame lacks image %d (create it with all of images 0-7)", who, i);
-    HIP_TRY(hipSetDevice(f->ctx->device));
-    { const int rc = order_on_own_stream(f); if (rc != RTR_OK) return rc; }
-    hipStream_t st = f->ctx->stream;
-    uint32_t* sh = f->image_ptr(RTR_IMAGE_SHADOWED); uint32_t* un = f->image_ptr(RTR_IMAGE_UNSHADOWED);
-    uint32_t* dsh = f->image_ptr(RTR_IMAGE_DENOISED_SHADOWED); uint32_t* dun = f->image_ptr(RTR_IMAGE_DENOISED_UNSHADOWED);
-    const uint32_t* nrm = f->image_ptr(RTR_IMAGE_NORMAL); const uint32_t* pos = f->image_ptr(RTR_IMAGE_POSITION);
-    int denoisingOutput = 1;                                            /* application.cppm:392 */
-    for (int i = 0; i < iterations; ++i) {
-        const int step = (i + 1) * 1;                                   /* (i + 1) * DENOISING_STRENGTH */
-        hipError_t e;
-        if (denoisingOutput == 1) {
-            e = rtrdev::launch_denoise_pair(un, dun, sh, dsh, nrm, pos, f->width, f->rows, step, 1.0f, 0.001f, 0.001f, st);
-        } else {
-            e = rtrdev::launch_denoise_pair(dun, un, dsh, sh, nrm, pos, f->width, f->rows, step, 1.0f, 0.001f, 0.001f, st);
-        }
-        if (e != hipSuccess) return fail(RTR_ERR_HIP, "denoise launch: %s", hipGetErrorString(e));
-        denoisingOutput = 1 - denoisingOutput;
-    }
-    hipError_t e = rtrdev::launch_combine(f->image_ptr(RTR_IMAGE_ANALYTIC), denoisingOutput == 0 ? sh : dsh, denoisingOutput == 0 ? un : dun,
-                                          f->image_ptr(RTR_IMAGE_FINAL), f->width, f->rows, st);
-    if (e != hipSuccess) return fail(RTR_ERR_HIP, "combine launch: %s", hipGetErrorString(e));
-    return RTR_OK;
-}
-
-int rtr_denoise_combine(rtr_frame* f, int iterations) {
-    const int rc = enqueue_denoise_combine(f, iterations, "rtr_denoise_combine");
-    if (rc != RTR_OK) return rc;
-    HIP_TRY(hipStreamSynchronize(f->ctx->stream));
-    return RTR_OK;
-}
-
-int rtr_denoise_combine_async(rtr_frame* f, int iterations) {
-    return enqueue_denoise_combine(f, iterations, "rtr_denoise_combine_async");     /* rtr_frame_wait joins */
-}
-
-int rtr_deinterleave_bands(rtr_ctx* ctx, const void* gathered, void* dst, uint32_t width, uint32_t height, uint32_t bandRows, uint32_t shardCount) {
-    if (!ctx || !gathered || !dst || width == 0 || height == 0) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_deinterleave_bands: bad argument");
-    if (bandRows == 0) bandRows = 8;
-    if (shardCount == 0) shardCount = 1;
-    HIP_TRY(hipSetDevice(ctx->device));
-    const uint32_t localRows = rtr_shard_rows(height, bandRows, shardCount);
-    hipError_t e = rtrdev::launch_deinterleave((const uint32_t*)gathered, (uint32_t*)dst, width, height, bandRows, shardCount, localRows, ctx->stream);
-    if (e != hipSuccess) return fail(RTR_ERR_HIP, "deinterleave launch: %s", hipGetErrorString(e));
-    return RTR_OK;   /* enqueued on the ctx stream; the caller synchronises (stream order is enough for a following copy) */
-}
-
-int rtr_deinterleave_images(rtr_ctx* ctx, const void* gathered, uint32_t numImages, void* const* dst, uint32_t width, uint32_t height,
-                            uint32_t bandRows, uint32_t shardCount) {
-    if (!ctx || !gathered || !dst || width == 0 || height == 0) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_deinterleave_images: bad argument");
-    if (numImages == 0 || numImages > rtrdev::kMaxDeinterleaveImages) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_deinterleave_images: %u images, 1 to %u", numImages, rtrdev::kMaxDeinterleaveImages);
-    for (uint32_t i = 0; i < numImages; ++i) if (!dst[i]) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_deinterleave_images: destination %u is null", i);
-    if (bandRows == 0) bandRows = 8;
-    if (bandRows % 8u) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_deinterleave_images: bandRows %u is not a multiple of 8", bandRows);
-    if (shardCount == 0) shardCount = 1;
-    HIP_TRY(hipSetDevice(ctx->device));
-    const uint32_t localRows = rtr_shard_rows(height, bandRows, shardCount);
-    uint32_t* d[rtrdev::kMaxDeinterleaveImages];
-    for (uint32_t i = 0; i < numImages; ++i) d[i] = static_cast<uint32_t*>(dst[i]);
-    hipError_t e = rtrdev::launch_deinterleave_images(static_cast<const uint32_t*>(gathered), d, numImages, width, height, bandRows, shardCount, localRows, ctx->stream);
-    if (e != hipSuccess) return fail(RTR_ERR_HIP, "deinterleave launch: %s", hipGetErrorString(e));
-    return RTR_OK;   /* enqueued on the ctx stream, like rtr_deinterleave_bands */
-}
-
-/* ---- ray queries ---------------------------------------------------------------------------- */
-static bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-static bool aligned4(const void* p) { return ((uintptr_t)p & 3u) == 0; }
-/* the pointer tables and the params' rules of rtr_arg_check.h, which the rtr_*_host.cpp share */
-using rtrdev::Arg;
-using rtrdev::check_ptrs;
-
-/* the handles every call of this section takes, and the device they must share */
-static int check_handles(const rtr_ctx* c, const rtr_scene* s, const char* who) {
-    if (!c || !s) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: null context or scene", who);
-    return RTR_OK;
-}
-static int check_same_device(const rtr_ctx* c, const rtr_scene* s, const char* who) {
-    if (s->ctx->device != c->device) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: the scene lives on device %d, the context on device %d", who, s->ctx->device, c->device);
-    return RTR_OK;
-}
-/* a synchronous call joins the context's stream when its asynchronous form (rc) enqueued something */
-static int join_if_enqueued(rtr_ctx* c, int rc, uint32_t n) {
-    if (rc != RTR_OK || n == 0) return rc;
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return RTR_OK;
-}
-
-/* the context's query scratch, allocated by its first query (the current device is the context's) */
-static int query_scratch(rtr_ctx* c) {
-    if (c->qCtrl.p) return RTR_OK;
-    HIP_TRY(c->qRedo.alloc(rtrdev::kQueryRedoCap));
-    HIP_TRY(c->qSpill.alloc(rtrdev::kSpillInts));
-    HIP_TRY(c->qCounters.alloc(1));
-    for (hipEvent_t& e : c->qEv) HIP_TRY(hipEventCreate(&e));
-    HIP_TRY(c->qCtrl.alloc(rtrdev::kQueryCtrlWords));
-    return RTR_OK;
-}
-
-/* Every query that walks rays (rtr_trace_rays, rtr_trace_rays_multi, rtr_trace_occlusion and their forms) goes through that scratch the
- * same way: scratch_open, its own memsets, qEv[0], its launches, scratch_close; the counting form reads back in query_join. */
-
-/* entries of a redo list of cap entries the query may use: all of them, or in the test build a list short enough to overflow */
-static uint32_t redo_cap(uint32_t cap) {
-#ifdef RTR_TEST_HOOKS
-    if (const char* e = getenv("RTR_QUERY_REDO_CAP")) { const uint64_t v = strtoull(e, nullptr, 10); if (v >= 1 && v < cap) cap = (uint32_t)v; }
-#endif
-    return cap;
-}
-
-/* The scratch is the context's — redo list, deep stacks, counters, events — so a query enqueued on another stream than the last one
- * (rtr_ctx_set_stream) comes behind it.  count: the counting form, whose counters start at zero. */
-static int scratch_open(rtr_ctx* c, bool count) {
-    HIP_TRY(hipSetDevice(c->device));
-    if (const int rc = query_scratch(c)) return rc;
-    hipStream_t st = c->stream;
-    if (c->qLastStream && c->qLastStream != st) HIP_TRY(hipStreamWaitEvent(st, c->qEv[1], 0));
-    if (count) HIP_TRY(hipMemsetAsync(c->qCounters.p, 0, sizeof(Counters), st));
-    return RTR_OK;
-}
-
-/* launch: what the query's launcher returned */
-static int scratch_close(rtr_ctx* c, hipError_t launch, const char* who) {
-    if (const int rc = launched(launch, who)) return rc;
-    hipStream_t st = c->stream;
-    HIP_TRY(hipEventRecord(c->qEv[1], st));
-    c->qLastStream = st;
-    return RTR_OK;
-}
-
-/* the cull mask of the masked calls: NoMask for the unmasked ones, which launch the kernels' unmasked forms */
-struct CullMask { bool masked; const uint8_t* rayMasks; uint32_t cullMask; };
-static const CullMask NoMask{false, nullptr, 0xffu};
-
-/* the flags argument of every query entry point: the known bits, and the combinations Vulkan forbids (VUID-RayFlags: one face flag at
- * most; one of Opaque, CullOpaque, CullNoOpaque at most) */
-static const uint32_t kQueryCullFlags = RTR_QUERY_CULL_BACK_FACING | RTR_QUERY_CULL_FRONT_FACING | RTR_QUERY_CULL_OPAQUE | RTR_QUERY_CULL_NO_OPAQUE;
-static int check_query_flags(uint32_t flags, const char* who) {
-    const uint32_t known = RTR_QUERY_ANY | RTR_QUERY_OPAQUE | kQueryCullFlags;
-    if (flags & ~known) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: unknown flag bits 0x%x", who, flags & ~known);
-    if ((flags & RTR_QUERY_CULL_BACK_FACING) && (flags & RTR_QUERY_CULL_FRONT_FACING))
-        return fail(RTR_ERR_INVALID_ARGUMENT, "%s: flags RTR_QUERY_CULL_BACK_FACING and RTR_QUERY_CULL_FRONT_FACING exclude each other", who);
-    const uint32_t op = flags & (RTR_QUERY_OPAQUE | RTR_QUERY_CULL_OPAQUE | RTR_QUERY_CULL_NO_OPAQUE);
-    if (op & (op - 1u))
-        return fail(RTR_ERR_INVALID_ARGUMENT, "%s: flags%s%s%s exclude each other (at most one of RTR_QUERY_OPAQUE, RTR_QUERY_CULL_OPAQUE, RTR_QUERY_CULL_NO_OPAQUE)", who,
-                    (op & RTR_QUERY_OPAQUE) ? " RTR_QUERY_OPAQUE" : "", (op & RTR_QUERY_CULL_OPAQUE) ? " RTR_QUERY_CULL_OPAQUE" : "",
-                    (op & RTR_QUERY_CULL_NO_OPAQUE) ? " RTR_QUERY_CULL_NO_OPAQUE" : "");
-    return RTR_OK;
-}
-/* what the kernels get: a call with culling flags launches the MASKED forms — with the mask 0xff and no per-ray bytes when it brought no
- * cull mask — and hands them the flags beside the selecting bit; a call without launches what it always did */
-static rtrdev::RayMaskArgs ray_mask_args(const CullMask& cm, uint32_t flags) {
-    rtrdev::RayMaskArgs rm;
-    const uint32_t cull = flags & kQueryCullFlags;
-    rm.rayMasks = cm.masked ? cm.rayMasks : nullptr; rm.cullMask = cm.masked ? cm.cullMask : 0xffu;
-    rm.masked = (cm.masked || cull) ? (1u | cull) : 0u;
-    return rm;
-}
-
-/* what the three kinds of query check first, in this order: the handles, the cull mask's range, the flags */
-static int check_query(const rtr_ctx* c, const rtr_scene* s, const CullMask& cm, uint32_t flags, const char* who) {
-    if (const int rc = check_handles(c, s, who)) return rc;
-    if (cm.masked && (cm.cullMask & ~0xffu)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: cullMask 0x%x has bits above the low 8 (an instance mask is 8 bits)", who, cm.cullMask);
-    return check_query_flags(flags, who);
-}
-
-/* the checks and launches of rtr_trace_rays[_async], enqueued on the context's stream; count: the counting form */
-static int enqueue_query(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, uint32_t n, uint32_t flags, RtrHit* hits, uint8_t* occluded,
-                         bool count, const char* who, const CullMask& cm = NoMask) {
-    if (const int rc = check_query(c, s, cm, flags, who)) return rc;
-    if (const int rc = check_same_device(c, s, who)) return rc;
-    if (n == 0) return RTR_OK;
-    const bool any = (flags & RTR_QUERY_ANY) != 0u;
-    if (!rays) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: rays is null", who);
-    if (!aligned16(rays)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: rays is not 16-B aligned", who);
-    if (!any && !hits) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: a closest-hit query needs hits", who);
-    if (!any && !aligned16(hits)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: hits is not 16-B aligned", who);
-    if (any && !occluded) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: an any-hit query (RTR_QUERY_ANY) needs occluded", who);
-    if (any && !aligned16(occluded)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: occluded is not 16-B aligned", who);
-    if (const int rc = scratch_open(c, count)) return rc;
-    hipStream_t st = c->stream;
-    HIP_TRY(hipMemsetAsync(c->qCtrl.p, 0, rtrdev::kQueryCtrlWords * sizeof(uint32_t), st));
-    HIP_TRY(hipEventRecord(c->qEv[0], st));
-    rtrdev::QueryArgs qa{};
-    qa.rays = reinterpret_cast<const float4*>(rays); qa.hits = reinterpret_cast<float4*>(hits); qa.occluded = occluded; qa.n = n;
-    qa.redoCap = redo_cap(rtrdev::kQueryRedoCap); qa.ctrl = c->qCtrl.p; qa.redoList = c->qRedo.p; qa.spill = c->qSpill.p;
-    const rtrdev::RayMaskArgs rm = ray_mask_args(cm, flags);
-    return scratch_close(c, rtrdev::launch_query(s->dev, qa, flags & (RTR_QUERY_ANY | RTR_QUERY_OPAQUE), count ? c->qCounters.p : nullptr, st, rm), who);
-}
-
-/* ---- queued occlusion queries (kernels/rtr_occlusion.hip): the layout of the caller's scratch ---- */
-namespace {
-/* the caller's scratch: control block (zeroed with the count of abandoned rays behind it) | abandoned rays' list | index queue | batch lists */
-struct OcclusionLayout { size_t ctrl, overflow, queue, lists, bytes; uint32_t overflowCap, listStride; };
-size_t up16(size_t x) { return (x + 15u) & ~(size_t)15u; }
-OcclusionLayout occlusion_layout(uint32_t n) {
-    OcclusionLayout l{};
-    l.overflowCap = n < rtrdev::kQueryRedoCap ? n : rtrdev::kQueryRedoCap;
-    l.listStride = rtrdev::occlusion_list_stride(n);
-    l.ctrl = 0;
-    l.overflow = up16(rtrdev::kQueueCtrlWords * sizeof(uint32_t));
-    l.queue = l.overflow + up16(((size_t)l.overflowCap + 1u) * sizeof(uint32_t));
-    l.lists = l.queue + up16((size_t)n * sizeof(uint32_t));
-    l.bytes = l.lists + up16((size_t)rtrdev::kQueueLists * l.listStride * sizeof(uint2));
-    return l;
-}
-}  // namespace
-
-/* What a synchronous query does behind its asynchronous form (rc: what that returned): it joins the context's stream, and the counting
- * form reads back the counters, the count of abandoned rays and the time between the two events — copies on the context's stream, so the
- * call joins that stream only.  occlusionScratch: the caller's scratch of a queued occlusion query, which keeps that count behind its
- * control block; null: the count is the context's control word. */
-static int query_join(rtr_ctx* c, int rc, uint32_t n, rtr_query_stats* stats, const void* occlusionScratch = nullptr) {
-    if (rc != RTR_OK) return rc;
-    if (stats) memset(stats, 0, sizeof *stats);
-    if (n == 0) return RTR_OK;
-    hipStream_t st = c->stream;
-    if (stats) {
-        Counters h;
-        uint32_t tail = 0;
-        const void* tailWord = c->qCtrl.p + rtrdev::kQueryRedoWord;
-        if (occlusionScratch) tailWord = static_cast<const char*>(occlusionScratch) + occlusion_layout(n).overflow;
-        HIP_TRY(hipMemcpyAsync(&h, c->qCounters.p, sizeof h, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(&tail, tailWord, sizeof tail, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        stats->numRays = h.rays; stats->numNodeVisits = h.nodes; stats->numTriTests = h.tris; stats->numAlphaTests = h.alphaTests;
-        stats->tailRays = tail;
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, c->qEv[0], c->qEv[1]));
-        stats->ms = ms;
-    } else HIP_TRY(hipStreamSynchronize(st));
-    return RTR_OK;
-}
-
-int rtr_trace_rays_async(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, uint32_t n, uint32_t flags, RtrHit* hits, uint8_t* occluded) {
-    return enqueue_query(c, s, rays, n, flags, hits, occluded, false, "rtr_trace_rays_async");
-}
-
-int rtr_trace_rays(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, uint32_t n, uint32_t flags, RtrHit* hits, uint8_t* occluded, rtr_query_stats* stats) {
-    return query_join(c, enqueue_query(c, s, rays, n, flags, hits, occluded, stats != nullptr, "rtr_trace_rays"), n, stats);
-}
-
-int rtr_trace_rays_masked_async(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const uint8_t* rayMasks, uint32_t n, uint32_t flags, uint32_t cullMask,
-                                RtrHit* hits, uint8_t* occluded) {
-    return enqueue_query(c, s, rays, n, flags, hits, occluded, false, "rtr_trace_rays_masked_async", CullMask{true, rayMasks, cullMask});
-}
-
-int rtr_trace_rays_masked(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const uint8_t* rayMasks, uint32_t n, uint32_t flags, uint32_t cullMask,
-                          RtrHit* hits, uint8_t* occluded, rtr_query_stats* stats) {
-    return query_join(c, enqueue_query(c, s, rays, n, flags, hits, occluded, stats != nullptr, "rtr_trace_rays_masked", CullMask{true, rayMasks, cullMask}), n, stats);
-}
-
-/* ---- multi-hit queries (kernels/rtr_multihit.hip) ---- */
-/* the checks and launches of rtr_trace_rays_multi[_async], enqueued on the context's stream; count: the counting form.  The flag and mask
- * validation is the masked query's; the kernels have the filtered form only, so the call always brings a cull mask. */
-static int enqueue_multihit(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const uint8_t* rayMasks, uint32_t n, uint32_t maxHits, uint32_t flags,
-                            uint32_t cullMask, const RtrHit* after, RtrHit* hits, uint32_t* counts, bool count, const char* who) {
-    const CullMask cm{true, rayMasks, cullMask};
-    if (const int rc = check_query(c, s, cm, flags, who)) return rc;
-    if (flags & RTR_QUERY_ANY) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: RTR_QUERY_ANY is refused: an any-hit walk has no order to report hits in", who);
-    if (maxHits == 0u || maxHits > RTR_MULTIHIT_MAX) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: maxHits %u, 1 to %u", who, maxHits, RTR_MULTIHIT_MAX);
-    if (const int rc = check_same_device(c, s, who)) return rc;
-    if (n == 0) return RTR_OK;
-    const Arg args[4] = {{rays, "rays", 16, true}, {hits, "hits", 16, true}, {after, "after", 16, false}, {counts, "counts", 4, false}};
-    if (const int rc = check_ptrs(who, args)) return rc;
-    if (const int rc = scratch_open(c, count)) return rc;
-    hipStream_t st = c->stream;
-    HIP_TRY(hipMemsetAsync(c->qCtrl.p, 0, rtrdev::kQueryCtrlWords * sizeof(uint32_t), st));
-    HIP_TRY(hipEventRecord(c->qEv[0], st));
-    rtrdev::MultiHitArgs ma{};
-    ma.rays = reinterpret_cast<const float4*>(rays); ma.after = reinterpret_cast<const float4*>(after); ma.hits = reinterpret_cast<float4*>(hits);
-    ma.counts = counts; ma.n = n; ma.maxHits = maxHits;
-    ma.redoCap = redo_cap(rtrdev::kQueryRedoCap); ma.ctrl = c->qCtrl.p; ma.redoList = c->qRedo.p; ma.spill = c->qSpill.p;
-    const rtrdev::RayMaskArgs rm = ray_mask_args(cm, flags);
-    return scratch_close(c, rtrdev::launch_multihit(s->dev, ma, (flags & RTR_QUERY_OPAQUE) == 0u, count ? c->qCounters.p : nullptr, st, rm), who);
-}
-
-int rtr_trace_rays_multi_async(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const uint8_t* rayMasks, uint32_t n, uint32_t maxHits, uint32_t flags,
-                               uint32_t cullMask, const RtrHit* after, RtrHit* hits, uint32_t* counts) {
-    return enqueue_multihit(c, s, rays, rayMasks, n, maxHits, flags, cullMask, after, hits, counts, false, "rtr_trace_rays_multi_async");
-}
-
-int rtr_trace_rays_multi(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const uint8_t* rayMasks, uint32_t n, uint32_t maxHits, uint32_t flags,
-                         uint32_t cullMask, const RtrHit* after, RtrHit* hits, uint32_t* counts, rtr_query_stats* stats) {
-    return query_join(c, enqueue_multihit(c, s, rays, rayMasks, n, maxHits, flags, cullMask, after, hits, counts, stats != nullptr, "rtr_trace_rays_multi"), n, stats);
-}
-
-/* ---- queued occlusion queries (kernels/rtr_occlusion.hip) ---- */
-int rtr_occlusion_scratch_bytes(uint32_t numRays, size_t* bytes) {
-    if (!bytes) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_occlusion_scratch_bytes: bytes is null");
-    *bytes = occlusion_layout(numRays).bytes;
-    return RTR_OK;
-}
-
-/* startLeaves: the hints of rtr_trace_occlusion_hinted (null: none; the unhinted calls pass null) */
-static int enqueue_occlusion(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const int32_t* startLeaves, uint32_t n, uint32_t flags, void* scratch,
-                             size_t scratchBytes, uint8_t* occluded, bool count, const char* who, const CullMask& cm = NoMask) {
-    if (n && !aligned4(startLeaves)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: startLeaves is not 4-B aligned", who);
-    if (const int rc = check_query(c, s, cm, flags, who)) return rc;
-    if (const int rc = check_same_device(c, s, who)) return rc;
-    if (n == 0) return RTR_OK;
-    const Arg args[3] = {{rays, "rays", 16, true}, {occluded, "occluded", 16, true}, {scratch, "scratch", 16, true}};
-    if (const int rc = check_ptrs(who, args)) return rc;
-    const OcclusionLayout l = occlusion_layout(n);
-    if (scratchBytes < l.bytes) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: %zu bytes of scratch, %u rays need %zu (rtr_occlusion_scratch_bytes)", who, scratchBytes, n, l.bytes);
-    if (const int rc = scratch_open(c, count)) return rc;      /* the deep stacks and the counters are the context's */
-    hipStream_t st = c->stream;
-    char* const base = static_cast<char*>(scratch);
-    HIP_TRY(hipMemsetAsync(base + l.ctrl, 0, l.overflow + 16u, st));       /* the control block and the count of abandoned rays */
-    HIP_TRY(hipMemsetAsync(occluded, 0, n, st));                           /* the walk stores the occluded rays' bytes only */
-    HIP_TRY(hipEventRecord(c->qEv[0], st));
-    rtrdev::OcclusionArgs oa{};
-    oa.rays = reinterpret_cast<const float4*>(rays); oa.occluded = occluded; oa.n = n; oa.batch = rtrdev::occlusion_batch(n);
-    oa.ctrl = reinterpret_cast<uint32_t*>(base + l.ctrl); oa.overflow = reinterpret_cast<uint32_t*>(base + l.overflow); oa.overflowCap = redo_cap(l.overflowCap);
-    oa.queue = reinterpret_cast<uint32_t*>(base + l.queue); oa.lists = reinterpret_cast<uint2*>(base + l.lists); oa.listStride = l.listStride;
-    oa.startLeaves = startLeaves; oa.numTris = (uint32_t)(s->tree.tris.n / 3);          /* a hint is checked against the records the scene holds */
-    const rtrdev::RayMaskArgs rm = ray_mask_args(cm, flags);
-    return scratch_close(c, rtrdev::launch_occlusion(s->dev, oa, c->tun, (flags & RTR_QUERY_OPAQUE) == 0u, c->qSpill.p, count ? c->qCounters.p : nullptr, st,
-                                                     (uint32_t)c->prop.multiProcessorCount, rm), who);
-}
-
-int rtr_trace_occlusion_async(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, uint32_t n, uint32_t flags, void* scratch, size_t scratchBytes, uint8_t* occluded) {
-    return enqueue_occlusion(c, s, rays, nullptr, n, flags, scratch, scratchBytes, occluded, false, "rtr_trace_occlusion_async");
-}
-
-int rtr_trace_occlusion_hinted_async(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const int32_t* startLeaves, uint32_t n, uint32_t flags, void* scratch,
-                                     size_t scratchBytes, uint8_t* occluded) {
-    return enqueue_occlusion(c, s, rays, startLeaves, n, flags, scratch, scratchBytes, occluded, false, "rtr_trace_occlusion_hinted_async");
-}
-
-int rtr_trace_occlusion_masked_async(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const int32_t* startLeaves, const uint8_t* rayMasks, uint32_t n,
-                                     uint32_t flags, uint32_t cullMask, void* scratch, size_t scratchBytes, uint8_t* occluded) {
-    return enqueue_occlusion(c, s, rays, startLeaves, n, flags, scratch, scratchBytes, occluded, false, "rtr_trace_occlusion_masked_async", CullMask{true, rayMasks, cullMask});
-}
-
-int rtr_trace_occlusion_masked(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const int32_t* startLeaves, const uint8_t* rayMasks, uint32_t n,
-                               uint32_t flags, uint32_t cullMask, void* scratch, size_t scratchBytes, uint8_t* occluded, rtr_query_stats* stats) {
-    return query_join(c, enqueue_occlusion(c, s, rays, startLeaves, n, flags, scratch, scratchBytes, occluded, stats != nullptr, "rtr_trace_occlusion_masked",
-                                           CullMask{true, rayMasks, cullMask}), n, stats, scratch);
-}
-
-int rtr_trace_occlusion(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, uint32_t n, uint32_t flags, void* scratch, size_t scratchBytes, uint8_t* occluded,
-                        rtr_query_stats* stats) {
-    return query_join(c, enqueue_occlusion(c, s, rays, nullptr, n, flags, scratch, scratchBytes, occluded, stats != nullptr, "rtr_trace_occlusion"), n, stats, scratch);
-}
-
-int rtr_trace_occlusion_hinted(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const int32_t* startLeaves, uint32_t n, uint32_t flags, void* scratch,
-                               size_t scratchBytes, uint8_t* occluded, rtr_query_stats* stats) {
-    return query_join(c, enqueue_occlusion(c, s, rays, startLeaves, n, flags, scratch, scratchBytes, occluded, stats != nullptr, "rtr_trace_occlusion_hinted"), n, stats, scratch);
-}
-
-/* the checks and the launch of rtr_hit_surfaces[_async], enqueued on the context's stream */
-static int enqueue_surfaces(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, uint32_t n, RtrSurface* out, const char* who) {
-    if (const int rc = check_handles(c, s, who)) return rc;
-    if (const int rc = check_same_device(c, s, who)) return rc;
-    if (n == 0) return RTR_OK;
-    const Arg args[3] = {{rays, "rays", 16, true}, {hits, "hits", 16, true}, {out, "out", 16, true}};
-    if (const int rc = check_ptrs(who, args)) return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    rtrdev::SurfaceArgs sa{};
-    sa.rays = reinterpret_cast<const float4*>(rays); sa.hits = reinterpret_cast<const float4*>(hits); sa.out = reinterpret_cast<float4*>(out);
-    sa.triCount = s->triCount.p; sa.numInstances = s->numInstances; sa.n = n;
-    return launched(rtrdev::launch_hit_surfaces(s->dev, sa, c->stream), who);
-}
-
-int rtr_hit_surfaces_async(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, uint32_t n, RtrSurface* out) {
-    return enqueue_surfaces(c, s, rays, hits, n, out, "rtr_hit_surfaces_async");
-}
-
-int rtr_hit_surfaces(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, uint32_t n, RtrSurface* out) {
-    return join_if_enqueued(c, enqueue_surfaces(c, s, rays, hits, n, out, "rtr_hit_surfaces"), n);
-}
-
-/* ---- start hints: the triangle -> leaf table (kernels/rtr_query.hip: k_leaf_table) ---- */
-/* Made by the first call that needs it, on the calling context's stream (the current device is the scene's), and JOINED before the call
- * goes on: whichever context of the device asks next finds it complete, without an event to wait for.  rtr_scene_update_instances
- * keeps it (a refit moves boxes and records, not the leaves they sit in). */
-static int ensure_leaf_table(rtr_ctx* c, const rtr_scene* s, const char* who) {
-    const SceneTree& t = s->tree;
-    if (t.leafReady) return RTR_OK;
-    { const int rcm = refresh_mirrors(s); if (rcm != RTR_OK) return rcm; }      /* joins an enqueued refit: this kernel may run on another stream */
-    std::vector<uint32_t> base(s->hostTriCount.size() + 1, 0u);
-    uint64_t total = 0;
-    for (size_t i = 0; i < s->hostTriCount.size(); ++i) { base[i] = (uint32_t)total; total += s->hostTriCount[i]; }
-    if (total > 0xffffffffull) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: %llu (customIndex, primitiveId) pairs do not fit the leaf table's 32-bit index", who, (unsigned long long)total);
-    hipStream_t st = c->stream;
-    HIP_TRY(s->leafBase.upload(base.data(), base.size(), st));
-    HIP_TRY(t.leafTable.alloc((size_t)total));
-    HIP_TRY(hipMemsetAsync(t.leafTable.p, 0, t.leafTable.n * sizeof(int32_t), st));
-    const hipError_t e = rtrdev::launch_leaf_table(t.nodes.p, (uint32_t)(t.nodes.n / 2), t.tris.p, (uint32_t)(t.tris.n / 3), s->triCount.p, s->leafBase.p,
-                                                   s->numInstances, t.leafTable.p, st);
-    if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: leaf table: %s", who, hipGetErrorString(e));
-    HIP_TRY(hipStreamSynchronize(st));
-    t.leafReady = true;
-    return RTR_OK;
-}
-
-/* the checks and the launch of rtr_hit_leaves[_async].  The pointers are checked first: that needs nothing of the handles */
-static int enqueue_hit_leaves(rtr_ctx* c, const rtr_scene* s, const RtrHit* hits, uint32_t n, int32_t* leaves, const char* who) {
-    const Arg args[2] = {{hits, "hits", 16, true}, {leaves, "leaves", 4, true}};
-    if (const int rc = n ? check_ptrs(who, args) : RTR_OK) return rc;
-    if (const int hrc = check_handles(c, s, who)) return hrc;
-    if (const int drc = check_same_device(c, s, who)) return drc;
-    if (n == 0) return RTR_OK;
-    HIP_TRY(hipSetDevice(c->device));
-    const int rc = ensure_leaf_table(c, s, who);
-    if (rc != RTR_OK) return rc;
-    rtrdev::LeafArgs a{};
-    a.hits = reinterpret_cast<const float4*>(hits); a.leaves = leaves; a.triCount = s->triCount.p; a.base = s->leafBase.p; a.table = s->tree.leafTable.p;
-    a.numInstances = s->numInstances; a.n = n;
-    return launched(rtrdev::launch_hit_leaves(a, c->stream), who);
-}
-
-int rtr_hit_leaves_async(rtr_ctx* c, const rtr_scene* s, const RtrHit* hits, uint32_t n, int32_t* leaves) {
-    return enqueue_hit_leaves(c, s, hits, n, leaves, "rtr_hit_leaves_async");
-}
-
-int rtr_hit_leaves(rtr_ctx* c, const rtr_scene* s, const RtrHit* hits, uint32_t n, int32_t* leaves) {
-    return join_if_enqueued(c, enqueue_hit_leaves(c, s, hits, n, leaves, "rtr_hit_leaves"), n);
-}
-
-int rtr_camera_rays_async(rtr_ctx* c, const RtrCameraData* cam, uint32_t width, uint32_t height, uint32_t spp, RtrRay* out) {
-    if (!c || !cam || !out) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_camera_rays_async: null argument");
-    if (!aligned16(out)) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_camera_rays_async: out is not 16-B aligned");
-    if (width == 0 || height == 0 || spp == 0) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_camera_rays_async: extent %ux%u x %u spp", width, height, spp);
-    if ((uint64_t)width * height * spp > 0xffffffffull) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_camera_rays_async: %ux%u x %u spp is more than 2^32 - 1 rays", width, height, spp);
-    HIP_TRY(hipSetDevice(c->device));
-    return launched(rtrdev::launch_camera_rays(*cam, width, height, spp, reinterpret_cast<float4*>(out), c->stream), "rtr_camera_rays_async");
-}
-
-/* ---- direct lighting for ray-query hits -------------------------------------------------------------------------------------- */
-
-/* Q of rtr_light_slots, from the host copy of the light table (as enqueue_render counts maxRaysPerSample) */
-static int light_slots(const rtr_scene* s, const rtr_light_params* p, uint32_t* q, const char* who) {
-    if (!s || !p) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: null scene or params", who);
-    if (p->numAreaLights > s->numLights) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: numAreaLights %u > scene lights %u", who, p->numAreaLights, s->numLights);
-    if (const int rc = rtrdev::check_shadow_rays(who, p->numShadowRays)) return rc;
-    if (const int rc = rtrdev::check_light_outputs(who, p->outputs)) return rc;
-    uint64_t slots = 1;
-    for (uint32_t l = 0; l < p->numAreaLights; ++l) slots += (uint64_t)s->hostLights[l].numTriangles * p->numShadowRays;
-    if (slots > 0xffffffffull) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: %llu slots per hit do not fit 32 bits", who, (unsigned long long)slots);
-    *q = (uint32_t)slots;
-    return RTR_OK;
-}
-
-int rtr_light_slots(const rtr_scene* s, const rtr_light_params* p, uint32_t* slotsPerHit) {
-    if (!slotsPerHit) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_light_slots: slotsPerHit is null");
-    return light_slots(s, p, slotsPerHit, "rtr_light_slots");
-}
-
-/* what every lighting launch takes of the call alike; slots, the output arrays, the hint fields and the test hook are the caller's */
-static void fill_light_args(rtrdev::LightArgs& la, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, uint32_t n, const rtr_light_params* p,
-                            const uint32_t* seeds) {
-    la.rays = reinterpret_cast<const float4*>(rays); la.hits = reinterpret_cast<const float4*>(hits); la.seeds = seeds;
-    la.triCount = s->triCount.p; la.numInstances = s->numInstances; la.n = n;
-    la.numAreaLights = p->numAreaLights; la.numShadowRays = p->numShadowRays; la.frame = p->frame; la.width = p->width; la.spp = p->spp;
-    la.outputs = p->outputs;
-}
-
-/* the checks and the launch of rtr_light_rays[_async] (shade == false) and rtr_shade_hits[_async], enqueued on the context's stream */
-static int enqueue_light(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, uint32_t n, const rtr_light_params* p,
-                         const uint32_t* seeds, RtrRay* outRays, const uint8_t* occluded, RtrRadiance* out, bool shade, const char* who,
-                         int32_t* outLeaves = nullptr, bool hinted = false) {
-    const Arg own[1] = {{outLeaves, "outLeaves", 4, true}};       /* rtr_light_rays_hinted: its own array is checked first, which needs nothing of the handles */
-    if (const int rc = hinted && n ? check_ptrs(who, own) : RTR_OK) return rc;
-    if (!c || !s || !p) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: null context, scene or params", who);
-    if (const int rc = check_same_device(c, s, who)) return rc;
-    uint32_t slots = 0;
-    if (const int rc = light_slots(s, p, &slots, who)) return rc;
-    if (shade && (p->outputs & RTR_LIGHT_ANALYTIC) && !s->hasLtc) return fail(RTR_ERR_UNSUPPORTED, "%s: RTR_LIGHT_ANALYTIC needs the LTC tables (rtr_scene_desc.ltc1/ltc2)", who);
-    if (n == 0) return RTR_OK;
-    if (const int rc = rtrdev::check_fits_32(who, n, "hits", slots, "slots")) return rc;
-    const Arg args[5] = {{rays, "rays", 16, true}, {hits, "hits", 16, true}, shade ? Arg{out, "out", 16, true} : Arg{outRays, "outRays", 16, true},
-                         {occluded, "occluded", 1, shade}, {seeds, "seeds", 4, false}};
-    if (const int rc = check_ptrs(who, args)) return rc;
-    if (const int rc = rtrdev::check_pixel_seeds(who, seeds, p->width, p->spp)) return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    if (const int rc = hinted ? ensure_leaf_table(c, s, who) : RTR_OK) return rc;
-    rtrdev::LightArgs la{};
-    if (hinted) { la.outLeaves = outLeaves; la.leafTable = s->tree.leafTable.p; la.leafBase = s->leafBase.p; }
-    fill_light_args(la, s, rays, hits, n, p, seeds);
-    la.slots = slots;
-    la.outRays = reinterpret_cast<float4*>(outRays); la.occluded = occluded; la.out = reinterpret_cast<float4*>(out);
-#ifdef RTR_TEST_HOOKS
-    if (const char* e = getenv("RTR_LIGHT_RAYS_DIRECT")) la.direct = atoi(e) != 0 ? 1u : 0u;   /* the kernel's unstaged form for a light table that would be staged */
-#endif
-    return launched(shade ? rtrdev::launch_shade_hits(s->dev, la, c->stream) : rtrdev::launch_light_rays(s->dev, la, c->stream), who);
-}
-
-int rtr_light_rays_async(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, uint32_t n, const rtr_light_params* p,
-                         const uint32_t* seeds, RtrRay* outRays) {
-    return enqueue_light(c, s, rays, hits, n, p, seeds, outRays, nullptr, nullptr, false, "rtr_light_rays_async");
-}
-
-int rtr_light_rays(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, uint32_t n, const rtr_light_params* p,
-                   const uint32_t* seeds, RtrRay* outRays) {
-    return join_if_enqueued(c, enqueue_light(c, s, rays, hits, n, p, seeds, outRays, nullptr, nullptr, false, "rtr_light_rays"), n);
-}
-
-int rtr_light_rays_hinted_async(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, uint32_t n, const rtr_light_params* p,
-                                const uint32_t* seeds, RtrRay* outRays, int32_t* outLeaves) {
-    return enqueue_light(c, s, rays, hits, n, p, seeds, outRays, nullptr, nullptr, false, "rtr_light_rays_hinted_async", outLeaves, true);
-}
-
-int rtr_light_rays_hinted(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, uint32_t n, const rtr_light_params* p,
-                          const uint32_t* seeds, RtrRay* outRays, int32_t* outLeaves) {
-    return join_if_enqueued(c, enqueue_light(c, s, rays, hits, n, p, seeds, outRays, nullptr, nullptr, false, "rtr_light_rays_hinted", outLeaves, true), n);
-}
-
-int rtr_shade_hits_async(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, uint32_t n, const rtr_light_params* p,
-                         const uint32_t* seeds, const uint8_t* occluded, RtrRadiance* out) {
-    return enqueue_light(c, s, rays, hits, n, p, seeds, nullptr, occluded, out, true, "rtr_shade_hits_async");
-}
-
-int rtr_shade_hits(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, uint32_t n, const rtr_light_params* p,
-                   const uint32_t* seeds, const uint8_t* occluded, RtrRadiance* out) {
-    return join_if_enqueued(c, enqueue_light(c, s, rays, hits, n, p, seeds, nullptr, occluded, out, true, "rtr_shade_hits"), n);
-}
-
-int rtr_tonemap_pack_async(rtr_ctx* c, const float* radiance, uint32_t strideBytes, uint32_t n, uint32_t* out) {
-    if (!c) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_tonemap_pack: null context");
-    if (strideBytes < 12 || (strideBytes & 3u)) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_tonemap_pack: strideBytes %u (a multiple of 4, at least 12)", strideBytes);
-    if (n == 0) return RTR_OK;
-    const Arg args[2] = {{radiance, "radiance", 4, true}, {out, "outBGRA8", 4, true}};
-    if (const int rc = check_ptrs("rtr_tonemap_pack", args)) return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    return launched(rtrdev::launch_tonemap_pack(radiance, strideBytes / 4u, n, out, c->stream), "rtr_tonemap_pack");
-}
-
-int rtr_tonemap_pack(rtr_ctx* c, const float* radiance, uint32_t strideBytes, uint32_t n, uint32_t* out) {
-    return join_if_enqueued(c, rtr_tonemap_pack_async(c, radiance, strideBytes, n, out), n);
-}
-
-/* ---- continuation rays for ray-query hits (kernels/rtr_bounce.hip; the host form is rtr_bounce_host.cpp) -------------------------- */
-static int enqueue_bounce(rtr_ctx* c, const RtrRay* rays, const RtrSurface* surfaces, uint32_t n, const rtr_bounce_params* p, const uint32_t* seeds,
-                          RtrRay* outRays, RtrBounce* outBounce, const char* who) {
-    /* the arrays and the params are checked first, which needs nothing of the handle */
-    if (const int rc = n ? rtrdev::bounce_check_args(who, rays, surfaces, n, p, seeds, outRays, outBounce) : RTR_OK) return rc;
-    if (!c) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: ctx is null", who);
-    if (n == 0) return RTR_OK;
-    HIP_TRY(hipSetDevice(c->device));
-    rtrdev::BounceArgs a{};
-    a.rays = reinterpret_cast<const float4*>(rays); a.surfaces = reinterpret_cast<const float4*>(surfaces); a.seeds = seeds;
-    a.outRays = reinterpret_cast<float4*>(outRays); a.outBounce = reinterpret_cast<float4*>(outBounce); a.params = *p; a.n = n;
-    return launched(rtrdev::launch_bounce_rays(a, c->stream), who);
-}
-
-int rtr_bounce_rays_async(rtr_ctx* c, const RtrRay* rays, const RtrSurface* surfaces, uint32_t n, const rtr_bounce_params* p, const uint32_t* seeds,
-                          RtrRay* outRays, RtrBounce* outBounce) {
-    return enqueue_bounce(c, rays, surfaces, n, p, seeds, outRays, outBounce, "rtr_bounce_rays_async");
-}
-
-int rtr_bounce_rays(rtr_ctx* c, const RtrRay* rays, const RtrSurface* surfaces, uint32_t n, const rtr_bounce_params* p, const uint32_t* seeds,
-                    RtrRay* outRays, RtrBounce* outBounce) {
-    return join_if_enqueued(c, enqueue_bounce(c, rays, surfaces, n, p, seeds, outRays, outBounce, "rtr_bounce_rays"), n);
-}
-
-/* ---- compaction of live paths (kernels/rtr_paths.hip; the host form and the argument checks are rtr_paths_host.cpp) ----------------- */
-static int enqueue_compact(rtr_ctx* c, const RtrRay* rays, const float* throughput, const uint32_t* seeds, const uint32_t* pathIds, uint32_t n,
-                           const rtr_compact_params* p, void* scratch, size_t scratchBytes, RtrRay* outRays, float* outThroughput,
-                           uint32_t* outSeeds, uint32_t* outPathIds, uint32_t* outCount, const char* who) {
-    /* the arrays and the params are checked first, which needs nothing of the handle */
-    const rtrdev::CompactCall call{rays, throughput, seeds, pathIds, n, p, scratch, scratchBytes, rtrdev::compact_scratch_bytes(n), true,
-                                   outRays, outThroughput, outSeeds, outPathIds, outCount};
-    if (const int rc = n ? rtrdev::compact_check_args(who, call) : RTR_OK) return rc;
-    if (!c) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: ctx is null", who);
-    if (n == 0 && !outCount) return RTR_OK;
-    if (n == 0 && !aligned4(outCount)) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: outCount is not 4-B aligned", who);
-    HIP_TRY(hipSetDevice(c->device));
-    if (n == 0) {
-        HIP_TRY(hipMemsetAsync(outCount, 0, sizeof(uint32_t), c->stream));
-        return RTR_OK;
-    }
-    const size_t groups = ((size_t)n + 255u) / 256u;
-    rtrdev::CompactArgs a{};
-    a.rays = reinterpret_cast<const float4*>(rays); a.throughput = reinterpret_cast<const char*>(throughput); a.seeds = seeds; a.pathIds = pathIds;
-    a.ballots = static_cast<unsigned long long*>(scratch);
-    a.groupTotals = reinterpret_cast<uint32_t*>(static_cast<char*>(scratch) + groups * 32u);
-    a.outRays = reinterpret_cast<float4*>(outRays); a.outThroughput = outThroughput; a.outSeeds = outSeeds; a.outPathIds = outPathIds;
-    a.outCount = outCount; a.params = *p; a.n = n;
-    return launched(rtrdev::launch_compact_paths(a, c->stream), who);
-}
-
-int rtr_compact_paths_async(rtr_ctx* c, const RtrRay* rays, const float* throughput, const uint32_t* seeds, const uint32_t* pathIds, uint32_t n,
-                            const rtr_compact_params* p, void* scratch, size_t scratchBytes, RtrRay* outRays, float* outThroughput,
-                            uint32_t* outSeeds, uint32_t* outPathIds, uint32_t* outCount) {
-    return enqueue_compact(c, rays, throughput, seeds, pathIds, n, p, scratch, scratchBytes, outRays, outThroughput, outSeeds, outPathIds, outCount,
-                           "rtr_compact_paths_async");
-}
-
-int rtr_compact_paths(rtr_ctx* c, const RtrRay* rays, const float* throughput, const uint32_t* seeds, const uint32_t* pathIds, uint32_t n,
-                      const rtr_compact_params* p, void* scratch, size_t scratchBytes, RtrRay* outRays, float* outThroughput,
-                      uint32_t* outSeeds, uint32_t* outPathIds, uint32_t* outCount, uint32_t* hostCount) {
-    const int rc = enqueue_compact(c, rays, throughput, seeds, pathIds, n, p, scratch, scratchBytes, outRays, outThroughput, outSeeds, outPathIds,
-                                   outCount, "rtr_compact_paths");
-    if (rc != RTR_OK) return rc;
-    if (n == 0) {                        /* nothing was launched; the count's memset, when there is one, is joined like a launch */
-        if (hostCount) *hostCount = 0u;
-        if (outCount) HIP_TRY(hipStreamSynchronize(c->stream));
-        return RTR_OK;
-    }
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (hostCount) {                     /* on the context's stream, so that no other stream is joined */
-        HIP_TRY(hipMemcpyAsync(hostCount, outCount, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-    }
-    return RTR_OK;
-}
-
-/* ---- picked light samples (kernels/rtr_query.hip; the rule is include/rtr_pick.h, the host form and the argument checks rtr_pick_host.cpp) -- */
-/* What the picked calls and rtr_mis_pick_weights do between their own argument checks and the launch: the handles, their device, the
- * scene's lights against the params.  areaSlots: A of include/rtr_pick.h; tris: the light triangles behind it. */
-static int picked_scene_checks(const rtr_ctx* c, const rtr_scene* s, const rtr_light_params* p, const char* who, uint32_t* areaSlots, uint32_t* tris) {
-    if (const int rc = check_handles(c, s, who)) return rc;
-    if (const int rc = check_same_device(c, s, who)) return rc;
-    uint32_t q = 0;
-    if (const int rc = light_slots(s, p, &q, who)) return rc;
-    *areaSlots = q - 1u; *tris = *areaSlots / p->numShadowRays;
-    return rtrdev::pick_check_area(who, *areaSlots);
-}
-
-/* and what their launches take alike; the output arrays and the weights are the caller's */
-static void fill_pick_args(rtrdev::PickArgs& pa, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, uint32_t n, const rtr_light_params* p,
-                           const rtr_pick_params* pick, const uint32_t* seeds, const uint32_t* slots, uint32_t areaSlots, uint32_t tris) {
-    fill_light_args(pa.la, s, rays, hits, n, p, seeds);
-    pa.la.slots = pick->numPicks + 1u;
-    pa.picks = pick->numPicks; pa.depth = pick->depth; pa.areaSlots = areaSlots;
-    pa.defaultWeight = (float)tris / (float)pick->numPicks;
-    pa.slotsIn = slots;
-}
-
-static int enqueue_light_picked(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, uint32_t n, const rtr_light_params* p,
-                                const rtr_pick_params* pick, const uint32_t* seeds, const uint32_t* slots, RtrRay* outRays, uint32_t* outSlots,
-                                const float* weights, const uint8_t* occluded, RtrRadiance* out, bool shade, const char* who) {
-    /* the params and the arrays are checked first, which needs nothing of the handles */
-    if (const int rc = rtrdev::pick_check_params(who, p, pick, shade)) return rc;
-    const rtrdev::PickCall call{rays, hits, n, p, pick, seeds, shade, slots, outRays, outSlots, weights, occluded, out};
-    if (const int rc = n ? rtrdev::pick_check_arrays(who, call) : RTR_OK) return rc;
-    uint32_t areaSlots = 0, tris = 0;
-    if (const int rc = picked_scene_checks(c, s, p, who, &areaSlots, &tris)) return rc;
-    if (n == 0) return RTR_OK;
-    HIP_TRY(hipSetDevice(c->device));
-    rtrdev::PickArgs pa{};
-    fill_pick_args(pa, s, rays, hits, n, p, pick, seeds, slots, areaSlots, tris);
-    pa.la.outRays = reinterpret_cast<float4*>(outRays); pa.la.occluded = occluded; pa.la.out = reinterpret_cast<float4*>(out);
-    pa.outSlots = outSlots; pa.weights = weights;
-    return launched(shade ? rtrdev::launch_shade_hits_picked(s->dev, pa, c->stream) : rtrdev::launch_light_rays_picked(s->dev, pa, c->stream), who);
-}
-
-int rtr_light_rays_picked_async(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, uint32_t n, const rtr_light_params* p,
-                                const rtr_pick_params* pick, const uint32_t* seeds, const uint32_t* slotsIn, RtrRay* outRays, uint32_t* outSlots) {
-    return enqueue_light_picked(c, s, rays, hits, n, p, pick, seeds, slotsIn, outRays, outSlots, nullptr, nullptr, nullptr, false, "rtr_light_rays_picked_async");
-}
-
-int rtr_light_rays_picked(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, uint32_t n, const rtr_light_params* p,
-                          const rtr_pick_params* pick, const uint32_t* seeds, const uint32_t* slotsIn, RtrRay* outRays, uint32_t* outSlots) {
-    return join_if_enqueued(c, enqueue_light_picked(c, s, rays, hits, n, p, pick, seeds, slotsIn, outRays, outSlots, nullptr, nullptr, nullptr, false,
-                                                    "rtr_light_rays_picked"), n);
-}
-
-int rtr_shade_hits_picked_async(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, uint32_t n, const rtr_light_params* p,
-                                const rtr_pick_params* pick, const uint32_t* seeds, const uint32_t* slots, const float* weights,
-                                const uint8_t* occluded, RtrRadiance* out) {
-    return enqueue_light_picked(c, s, rays, hits, n, p, pick, seeds, slots, nullptr, nullptr, weights, occluded, out, true, "rtr_shade_hits_picked_async");
-}
-
-int rtr_shade_hits_picked(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, uint32_t n, const rtr_light_params* p,
-                          const rtr_pick_params* pick, const uint32_t* seeds, const uint32_t* slots, const float* weights,
-                          const uint8_t* occluded, RtrRadiance* out) {
-    return join_if_enqueued(c, enqueue_light_picked(c, s, rays, hits, n, p, pick, seeds, slots, nullptr, nullptr, weights, occluded, out, true,
-                                                    "rtr_shade_hits_picked"), n);
-}
-
-/* ---- MIS at a path vertex (kernels/rtr_query.hip, kernels/rtr_mis.hip; the rule is include/rtr_mis.h, the host forms and the argument checks rtr_mis_host.cpp) -- */
-static int enqueue_mis_pick_weights(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, uint32_t n, const rtr_light_params* p,
-                                    const rtr_pick_params* pick, const rtr_mis_params* mis, const uint32_t* seeds, const uint32_t* slots,
-                                    float* outWeights, RtrMisSample* outSamples, const char* who) {
-    /* the params and the arrays are checked first, which needs nothing of the handles */
-    if (const int rc = rtrdev::mis_check_params(who, mis)) return rc;
-    if (const int rc = rtrdev::pick_check_params(who, p, pick, true)) return rc;
-    if (const int rc = rtrdev::mis_check_pick_call(who, p, pick, mis, rays, hits, n, seeds, slots, outWeights, outSamples)) return rc;
-    uint32_t areaSlots = 0, tris = 0;
-    if (const int rc = picked_scene_checks(c, s, p, who, &areaSlots, &tris)) return rc;
-    if (n == 0) return RTR_OK;
-    HIP_TRY(hipSetDevice(c->device));
-    rtrdev::MisPickArgs ma{};
-    fill_pick_args(ma.pa, s, rays, hits, n, p, pick, seeds, slots, areaSlots, tris);
-    ma.outWeights = outWeights; ma.outSamples = reinterpret_cast<float4*>(outSamples); ma.lobes = mis->lobes; ma.tris = tris;
-    return launched(rtrdev::launch_mis_pick_weights(s->dev, ma, c->stream), who);
-}
-
-int rtr_mis_pick_weights_async(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, uint32_t n, const rtr_light_params* p,
-                               const rtr_pick_params* pick, const rtr_mis_params* mis, const uint32_t* seeds, const uint32_t* slots, float* outWeights,
-                               RtrMisSample* outSamples) {
-    return enqueue_mis_pick_weights(c, s, rays, hits, n, p, pick, mis, seeds, slots, outWeights, outSamples, "rtr_mis_pick_weights_async");
-}
-
-int rtr_mis_pick_weights(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, uint32_t n, const rtr_light_params* p,
-                         const rtr_pick_params* pick, const rtr_mis_params* mis, const uint32_t* seeds, const uint32_t* slots, float* outWeights,
-                         RtrMisSample* outSamples) {
-    return join_if_enqueued(c, enqueue_mis_pick_weights(c, s, rays, hits, n, p, pick, mis, seeds, slots, outWeights, outSamples, "rtr_mis_pick_weights"), n);
-}
-
-static int enqueue_emitter_hits(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, const RtrSurface* prevSurfaces,
-                                const RtrBounce* bounces, uint32_t n, const rtr_mis_params* mis, RtrEmitter* out, const char* who) {
-    /* the params and the arrays are checked first, which needs nothing of the handles */
-    if (const int rc = rtrdev::mis_check_params(who, mis)) return rc;
-    if (const int rc = n ? rtrdev::mis_check_emitter_arrays(who, rays, hits, prevSurfaces, bounces, out) : RTR_OK) return rc;
-    if (const int rc = check_handles(c, s, who)) return rc;
-    if (const int rc = check_same_device(c, s, who)) return rc;
-    if (mis->numAreaLights > s->numLights) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: numAreaLights %u > scene lights %u", who, mis->numAreaLights, s->numLights);
-    uint64_t tris = 0;
-    for (uint32_t l = 0; l < mis->numAreaLights; ++l) tris += s->hostLights[l].numTriangles;
-    if (tris > RTR_PICK_MAX_SLOTS) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: %llu light triangles are more than 2^24", who, (unsigned long long)tris);
-    if (n == 0) return RTR_OK;
-    HIP_TRY(hipSetDevice(c->device));
-    rtrdev::EmitterArgs a{};
-    a.rays = reinterpret_cast<const float4*>(rays); a.hits = reinterpret_cast<const float4*>(hits);
-    a.prevSurfaces = reinterpret_cast<const float4*>(prevSurfaces); a.bounces = reinterpret_cast<const float4*>(bounces);
-    a.out = reinterpret_cast<float4*>(out);
-    a.lightTris = s->dev.lightTris; a.lightTriFirst = s->dev.lightTriFirst; a.lights = s->dev.lights; a.numLights = s->numLights;
-    a.numAreaLights = mis->numAreaLights; a.tris = (uint32_t)tris; a.picks = mis->numPicks; a.n = n;
-    return launched(rtrdev::launch_emitter_hits(a, c->stream), who);
-}
-
-int rtr_emitter_hits_async(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, const RtrSurface* prevSurfaces, const RtrBounce* bounces,
-                           uint32_t n, const rtr_mis_params* mis, RtrEmitter* out) {
-    return enqueue_emitter_hits(c, s, rays, hits, prevSurfaces, bounces, n, mis, out, "rtr_emitter_hits_async");
-}
-
-int rtr_emitter_hits(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, const RtrSurface* prevSurfaces, const RtrBounce* bounces,
-                     uint32_t n, const rtr_mis_params* mis, RtrEmitter* out) {
-    return join_if_enqueued(c, enqueue_emitter_hits(c, s, rays, hits, prevSurfaces, bounces, n, mis, out, "rtr_emitter_hits"), n);
-}
-
-/* ---- sky importance sampling (kernels/rtr_sky.hip; the rule is include/rtr_sky.h, the host forms and the argument checks rtr_sky_host.cpp) -- */
-static rtr_sky_source scene_sky_source(const rtr_scene* s) {
-    rtr_sky_source src{};
-    src.pixels = s->dev.hdri.pixels; src.width = s->dev.hdri.width; src.height = s->dev.hdri.height; src.channels = s->dev.hdri.channels;
-    for (int k = 0; k < 3; ++k) src.skyLinear[k] = s->dev.skyLinear[k];
-    return src;
-}
-
-/* Made by the first call that needs it, on `st` (the current device is the scene's), and JOINED before the call goes on, as the leaf
- * table is: whichever context of the device asks next finds it complete.  It reads the HDRI's texels and the sky colour alone, which
- * no update, refit or rebuild writes. */
-static int ensure_sky_table(const rtr_scene* s, hipStream_t st, const char* who) {
-    if (s->skyReady) return RTR_OK;
-    const rtr_sky_source src = scene_sky_source(s);
-    const uint32_t W = rtr_sky_table_width(&src), H = rtr_sky_table_height(&src);
-    if (W > RTR_SKY_MAX_WIDTH) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: the scene's hdri is %u texels wide: a row's sum fits 32 bits up to %u", who, W, RTR_SKY_MAX_WIDTH);
-    HIP_TRY(s->skyRows.alloc((size_t)W * H));
-    HIP_TRY(s->skyMarginal.alloc(H));
-    const hipError_t e = rtrdev::launch_sky_table(src, s->skyRows.p, s->skyMarginal.p, st);
-    if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: sky table: %s", who, hipGetErrorString(e));
-    HIP_TRY(hipStreamSynchronize(st));
-    s->skyReady = true;
-    return RTR_OK;
-}
-
-static rtrdev::SkyDevice scene_sky_device(const rtr_scene* s) {
-    rtrdev::SkyDevice sd{};
-    sd.sky = scene_sky_source(s);
-    sd.table.rows = s->skyRows.p; sd.table.marginal = s->skyMarginal.p;
-    sd.table.width = rtr_sky_table_width(&sd.sky); sd.table.height = rtr_sky_table_height(&sd.sky);
-    return sd;
-}
-
-int rtr_scene_prepare_sky(rtr_scene* s) {
-    static const char* who = "rtr_scene_prepare_sky";
-    if (!s) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: null scene", who);
-    HIP_TRY(hipSetDevice(s->ctx->device));
-    return ensure_sky_table(s, s->ctx->stream, who);
-}
-
-int rtr_scene_export_sky_table(const rtr_scene* s, uint32_t* outWidth, uint32_t* outHeight, uint32_t* outRows, size_t capacityCells, uint64_t* outMarginal,
-                               uint32_t capacityRows) {
-    static const char* who = "rtr_scene_export_sky_table";
-    if (!s) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: null scene", who);
-    const rtr_sky_source src = scene_sky_source(s);
-    const uint32_t W = rtr_sky_table_width(&src), H = rtr_sky_table_height(&src);
-    if (outWidth) *outWidth = W;
-    if (outHeight) *outHeight = H;
-    if (!outRows || !outMarginal || capacityCells < (size_t)W * H || capacityRows < H)
-        return fail(RTR_ERR_INVALID_ARGUMENT, "%s: capacity %zu cells, %u rows; %zu and %u are needed", who, outRows ? capacityCells : (size_t)0,
-                    outMarginal ? capacityRows : 0u, (size_t)W * H, H);
-    HIP_TRY(hipSetDevice(s->ctx->device));
-    if (const int rc = ensure_sky_table(s, s->ctx->stream, who)) return rc;
-    HIP_TRY(hipMemcpy(outRows, s->skyRows.p, (size_t)W * H * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(outMarginal, s->skyMarginal.p, (size_t)H * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    return RTR_OK;
-}
-
-static int enqueue_sky_rays(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrSurface* surfaces, uint32_t n, const rtr_sky_params* p,
-                            const uint32_t* seeds, RtrRay* outRays, RtrSkySample* outSamples, const char* who) {
-    /* the params and the arrays are checked first, which needs nothing of the handles */
-    if (const int rc = rtrdev::sky_check_params(who, p, false)) return rc;
-    if (const int rc = rtrdev::sky_check_rays_call(who, p, rays, surfaces, n, seeds, outRays, outSamples)) return rc;
-    if (const int rc = check_handles(c, s, who)) return rc;
-    if (const int rc = check_same_device(c, s, who)) return rc;
-    if (n == 0) return RTR_OK;
-    HIP_TRY(hipSetDevice(c->device));
-    if (const int rc = ensure_sky_table(s, c->stream, who)) return rc;
-    rtrdev::SkyRaysArgs a{};
-    a.sd = scene_sky_device(s);
-    a.rays = reinterpret_cast<const float4*>(rays); a.surfaces = reinterpret_cast<const float4*>(surfaces); a.seeds = seeds;
-    a.outRays = reinterpret_cast<float4*>(outRays); a.outSamples = reinterpret_cast<float4*>(outSamples);
-    a.params = *p; a.n = n;
-    return launched(rtrdev::launch_sky_rays(a, a.sd.table.height <= rtrdev::kSkyLdsRows, c->stream), who);
-}
-
-int rtr_sky_rays_async(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrSurface* surfaces, uint32_t n, const rtr_sky_params* p,
-                       const uint32_t* seeds, RtrRay* outRays, RtrSkySample* outSamples) {
-    return enqueue_sky_rays(c, s, rays, surfaces, n, p, seeds, outRays, outSamples, "rtr_sky_rays_async");
-}
-
-int rtr_sky_rays(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrSurface* surfaces, uint32_t n, const rtr_sky_params* p,
-                 const uint32_t* seeds, RtrRay* outRays, RtrSkySample* outSamples) {
-    return join_if_enqueued(c, enqueue_sky_rays(c, s, rays, surfaces, n, p, seeds, outRays, outSamples, "rtr_sky_rays"), n);
-}
-
-static int enqueue_shade_sky(rtr_ctx* c, const RtrSkySample* samples, const uint8_t* occluded, uint32_t n, uint32_t numSamples, float* out, const char* who) {
-    if (const int rc = rtrdev::sky_check_shade_call(who, samples, occluded, n, numSamples, out)) return rc;
-    if (!c) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: null context", who);
-    if (n == 0) return RTR_OK;
-    HIP_TRY(hipSetDevice(c->device));
-    rtrdev::SkyShadeArgs a{};
-    a.samples = reinterpret_cast<const float4*>(samples); a.occluded = occluded; a.out = reinterpret_cast<float4*>(out);
-    a.numSamples = numSamples; a.n = n;
-    return launched(rtrdev::launch_shade_sky(a, c->stream), who);
-}
-
-int rtr_shade_sky_async(rtr_ctx* c, const RtrSkySample* samples, const uint8_t* occluded, uint32_t n, uint32_t numSamples, float* out) {
-    return enqueue_shade_sky(c, samples, occluded, n, numSamples, out, "rtr_shade_sky_async");
-}
-
-int rtr_shade_sky(rtr_ctx* c, const RtrSkySample* samples, const uint8_t* occluded, uint32_t n, uint32_t numSamples, float* out) {
-    const int rc = enqueue_shade_sky(c, samples, occluded, n, numSamples, out, "rtr_shade_sky");
-    return rc == RTR_OK ? join_if_enqueued(c, rc, n) : rc;
-}
-
-static int enqueue_sky_hits(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, const RtrSurface* prevSurfaces, const RtrBounce* bounces,
-                            uint32_t n, const rtr_sky_params* p, RtrSkyEscape* out, const char* who) {
-    if (const int rc = rtrdev::sky_check_params(who, p, true)) return rc;
-    if (const int rc = n ? rtrdev::sky_check_hits_arrays(who, rays, hits, prevSurfaces, bounces, n, out) : RTR_OK) return rc;
-    if (const int rc = check_handles(c, s, who)) return rc;
-    if (const int rc = check_same_device(c, s, who)) return rc;
-    if (n == 0) return RTR_OK;
-    HIP_TRY(hipSetDevice(c->device));
-    if (const int rc = ensure_sky_table(s, c->stream, who)) return rc;
-    rtrdev::SkyHitsArgs a{};
-    a.sd = scene_sky_device(s);
-    a.rays = reinterpret_cast<const float4*>(rays); a.hits = reinterpret_cast<const float4*>(hits);
-    a.prevSurfaces = reinterpret_cast<const float4*>(prevSurfaces); a.bounces = reinterpret_cast<const float4*>(bounces);
-    a.out = reinterpret_cast<float4*>(out); a.numSamples = p->numSamples; a.flags = p->flags; a.n = n;
-    return launched(rtrdev::launch_sky_hits(a, c->stream), who);
-}
-
-int rtr_sky_hits_async(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, const RtrSurface* prevSurfaces, const RtrBounce* bounces,
-                       uint32_t n, const rtr_sky_params* p, RtrSkyEscape* out) {
-    return enqueue_sky_hits(c, s, rays, hits, prevSurfaces, bounces, n, p, out, "rtr_sky_hits_async");
-}
-
-int rtr_sky_hits(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, const RtrSurface* prevSurfaces, const RtrBounce* bounces,
-                 uint32_t n, const rtr_sky_params* p, RtrSkyEscape* out) {
-    return join_if_enqueued(c, enqueue_sky_hits(c, s, rays, hits, prevSurfaces, bounces, n, p, out, "rtr_sky_hits"), n);
-}
-
-int rtr_scene_export_light_tris(const rtr_scene* s, float* outRecords, uint32_t capacityTris, uint32_t* outFirst, uint32_t* outCount) {
-    static const char* who = "rtr_scene_export_light_tris";
-    if (!s) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: null scene", who);
-    uint32_t total = 0;
-    std::vector<uint32_t> first(s->numLights);
-    for (uint32_t l = 0; l < s->numLights; ++l) { first[l] = total; total += s->hostLights[l].numTriangles; }
-    if (outCount) *outCount = total;
-    if (capacityTris < total || (total && !outRecords))
-        return fail(RTR_ERR_INVALID_ARGUMENT, "%s: capacity %u light triangles, %u are needed", who, outRecords ? capacityTris : 0u, total);
-    HIP_TRY(hipSetDevice(s->ctx->device));
-    hipStream_t st = s->ctx->stream;
-    if (total) HIP_TRY(hipMemcpyAsync(outRecords, s->lightTris.p, (size_t)total * rtrdev::kLightTriRecord * sizeof(float4), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (outFirst) for (uint32_t l = 0; l < s->numLights; ++l) outFirst[l] = first[l];
-    return RTR_OK;
-}
-
-#ifdef RTR_TEST_HOOKS
-/* librtr_hip_test.so only: what the loaded code object says of the binned queue build, k_shadow_gen_oct<single> (spp == 1) or <false> —
- * out[0] VGPRs, out[1] private-segment bytes per lane, out[2] static LDS bytes, out[3] the launch bound.  Register and scratch figures
- * only: the spp == 1 form is meant to have no private segment at its eight waves per SIMD (tests/test_gpu_gen_oct_scratch.py). */
-int rtr_test_gen_oct_attributes(int single, uint32_t out[4]) {
-    if (!out) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_test_gen_oct_attributes: null output");
-    hipFuncAttributes a{};
-    HIP_TRY(rtrdev::gen_oct_attributes(single != 0, &a));
-    out[0] = (uint32_t)a.numRegs; out[1] = (uint32_t)a.localSizeBytes; out[2] = (uint32_t)a.sharedSizeBytes; out[3] = (uint32_t)a.maxThreadsPerBlock;
-    return RTR_OK;
-}
-#endif
 
 }  // extern "C"

@@ -69,6 +69,21 @@ def test_exports_are_c_linkage():
         assert n in exported
 
 
+def test_the_split_of_the_abi_files_shows_in_neither_exports_nor_last_error():
+    """csrc/rtr_api_internal.h: what the rtr_api*.cpp files share lives in namespace rtrapi, which is declared hidden, so splitting the
+    ABI's implementation over several files adds nothing to what the libraries export; and the thread's error text is one object,
+    rtr_api.cpp's, whichever file refuses (scene, render, query, paths: one null-argument refusal each)."""
+    for path, lib in ((A.LIB_HIP_PATH, A.hip_lib()), (A.LIB_HIP_HOOKS_PATH, A.hip_lib_with_hooks())):
+        names = [l.split()[-1] for l in subprocess.check_output(["nm", "-D", "--defined-only", path]).decode().splitlines()]
+        assert "rtr_last_error" in names, f"{os.path.basename(path)}: no dynamic symbols read"
+        leaked = [n for n in names if "rtrapi" in n]
+        assert not leaked, f"{os.path.basename(path)} exports {leaked}"
+        assert lib.rtr_scene_get_stats(None, None) == -1 and lib.rtr_last_error() == b"rtr_scene_get_stats: null argument"
+        assert lib.rtr_frame_download(None, 1, None, 0) == -1 and lib.rtr_last_error() == b"rtr_frame_download: null argument"
+        assert lib.rtr_camera_rays_async(None, None, 1, 1, 1, None) == -1 and lib.rtr_last_error() == b"rtr_camera_rays_async: null argument"
+        assert lib.rtr_light_slots(None, None, None) == -1 and lib.rtr_last_error() == b"rtr_light_slots: slotsPerHit is null"
+
+
 def test_pod_layouts_match_reference():
     # SURVEY Appendix A: Vertex 48, GPUCameraData 64, SceneInfo 32, GPUObjectInfo 80, GPUAreaLightInfo 96, DenoisingInfo 24
     assert C.sizeof(A.RtrVertex) == 48 and A.RtrVertex.normal.offset == 16 and A.RtrVertex.uv.offset == 32

@@ -1128,6 +1128,69 @@ int  rtr_host_sky_hits(const rtr_texture* hdri, const float* skyColor, const rtr
 int  rtr_host_sky_pdf(const rtr_sky_table* table, const float* dirs, uint32_t n, float* outPdf);
 int  rtr_host_sky_radiance(const rtr_texture* hdri, const float* skyColor, const float* dirs, uint32_t n, float* out);
 
+/* ---- power-proportional light picks: a light-power table, its picks and their MIS -------------------------------------------------
+ * rtr_light_rays_picked draws a vertex's picks uniformly over the light triangles.  These calls draw them in proportion to the emitted
+ * power of each triangle — max(colour) * intensity * area — from the scene's LIGHT-POWER TABLE: one integer weight and one 64-bit
+ * inclusive sum per light triangle of ALL lights, in rtr_scene_export_light_tris' order.  The rule is include/rtr_power.h; DESIGN.md
+ * section 3 has the table, the estimator and the unbiasedness argument.  The chain is rtr_pick_slots_power ->
+ * rtr_light_rays_picked(slotsIn) -> an occlusion query -> rtr_shade_hits_picked(weights), with rtr_mis_pick_weights_power between
+ * the first two and rtr_emitter_hits_power on the bounce ray when the bounce is to count the lights it meets.
+ *
+ * rtr_scene_prepare_light_power: builds the table on the device, 12 B per light triangle.  SYNCHRONOUS: it allocates and joins, once per
+ * scene (a second call does nothing).  The first power call or export of a scene builds it the same way, so only a caller that wants a
+ * chain without allocation or join has to call this first.  Once a scene has a table, every call that rewrites its light triangles or
+ * its light infos — rtr_scene_update_lights, rtr_scene_update_instances, rtr_scene_update_vertices, rtr_scene_rebuild's refit and the
+ * _async updates — enqueues the two launches of the build right behind its own, on the same stream: no allocation, no join, the _async
+ * updates keep their contract.  A scene without a table launches what it launched before.
+ * rtr_scene_export_light_power: *outCount = the light triangles of all lights; with capacityTris of at least that, the weights and the
+ * sums to HOST pointers; a smaller capacity (or a NULL array) copies nothing, reports the count and is refused with
+ * RTR_ERR_INVALID_ARGUMENT.  Joins the scene's stream and copies.
+ * rtr_pick_slots_power: for hit k and pick p < P, outSlots[k * P + p] = the area slot drawn (RTR_PICK_NONE when no triangle of the first
+ * numAreaLights lights emits) and outWeights[k * P + p] = total / (P * weight) of its triangle, the weight rtr_shade_hits_picked is to
+ * apply (0 beside RTR_PICK_NONE).  It needs the seeds alone: seeds (one word per hit) or NULL for the pixel rule (params->width,
+ * params->spp); params->frame and pick->depth enter as in rtr_light_rays_picked.
+ * rtr_mis_pick_weights_power: rtr_mis_pick_weights' arguments; slots is REQUIRED (rtr_pick_slots_power's, or the caller's);
+ * outWeights[k * P + p] = wPow * wPick with the table's probability of the slot's triangle; 0 for a triangle of weight 0.
+ * rtr_emitter_hits_power: rtr_emitter_hits' arguments and records with the table's probability of the hit triangle; a triangle of weight
+ * 0, or of a light with index >= mis->numAreaLights, is the bounce's alone (wBounce = 1).
+ * The _async forms are ENQUEUED on ctx's stream: on a prepared scene no allocation, no join, no copy back.  The plain forms then join
+ * that stream (only that stream).  Refused before anything is written (RTR_ERR_INVALID_ARGUMENT, the message names the function and the
+ * argument): a null or misaligned pointer, numPicks 0 or above RTR_PICK_MAX, non-zero _reserved words, A above RTR_PICK_MAX_SLOTS,
+ * numAreaLights above the scene's lights, width or spp 0 with seeds == NULL, a scene on another device. */
+int  rtr_scene_prepare_light_power(rtr_scene* scene);
+int  rtr_scene_export_light_power(const rtr_scene* scene, uint32_t* outWeights, uint64_t* outCdf, uint32_t capacityTris, uint32_t* outCount);
+int  rtr_pick_slots_power_async(rtr_ctx* ctx, const rtr_scene* scene, uint32_t numHits, const rtr_light_params* params, const rtr_pick_params* pick,
+                                const uint32_t* seeds, uint32_t* outSlots, float* outWeights);
+int  rtr_pick_slots_power(rtr_ctx* ctx, const rtr_scene* scene, uint32_t numHits, const rtr_light_params* params, const rtr_pick_params* pick,
+                          const uint32_t* seeds, uint32_t* outSlots, float* outWeights);
+int  rtr_mis_pick_weights_power_async(rtr_ctx* ctx, const rtr_scene* scene, const RtrRay* rays, const RtrHit* hits, uint32_t numHits,
+                                      const rtr_light_params* params, const rtr_pick_params* pick, const rtr_mis_params* mis, const uint32_t* seeds,
+                                      const uint32_t* slots, float* outWeights, RtrMisSample* outSamples);
+int  rtr_mis_pick_weights_power(rtr_ctx* ctx, const rtr_scene* scene, const RtrRay* rays, const RtrHit* hits, uint32_t numHits,
+                                const rtr_light_params* params, const rtr_pick_params* pick, const rtr_mis_params* mis, const uint32_t* seeds,
+                                const uint32_t* slots, float* outWeights, RtrMisSample* outSamples);
+int  rtr_emitter_hits_power_async(rtr_ctx* ctx, const rtr_scene* scene, const RtrRay* rays, const RtrHit* hits, const RtrSurface* prevSurfaces,
+                                  const RtrBounce* bounces, uint32_t numRays, const rtr_mis_params* mis, RtrEmitter* out);
+int  rtr_emitter_hits_power(rtr_ctx* ctx, const rtr_scene* scene, const RtrRay* rays, const RtrHit* hits, const RtrSurface* prevSurfaces,
+                            const RtrBounce* bounces, uint32_t numRays, const rtr_mis_params* mis, RtrEmitter* out);
+/* The host forms of include/rtr_power.h in plain loops, HOST pointers, no device; the device's words equal these.
+ * rtr_host_light_power: the table of a light table handed in (lightTris, lightTriFirst: rtr_scene_export_light_tris'; lights: the scene's
+ * light infos): one weight and one sum per light triangle of all numLights lights.
+ * rtr_host_pick_slots_power: rtr_pick_slots_power for a table handed in; tris: Ttot, the triangles of the first numAreaLights lights.
+ * rtr_host_mis_weights_power: rtr_host_mis_weights with the probability of triangle lightTri[k] in place of 1 / Ttot; outSamples[k] =
+ * {lightPdf, pb[k], wPick, cosLight[k], dist[k], area[k], lightTri[k], 0}; outWBounce (or NULL): wBounce; outWeights (or NULL): the
+ * weight rtr_mis_pick_weights_power gives a pick on that triangle.  P may be 0 here (nobody picks).
+ * rtr_host_emitter_hits_power: rtr_host_emitter_hits with the table. */
+int  rtr_host_light_power(const float* lightTris, const uint32_t* lightTriFirst, const RtrAreaLightInfo* lights, uint32_t numLights,
+                          uint32_t* outWeights, uint64_t* outCdf);
+int  rtr_host_pick_slots_power(const uint64_t* cdf, uint32_t tris, const uint32_t* seeds, uint32_t numHits, const rtr_light_params* params,
+                               const rtr_pick_params* pick, uint32_t* outSlots, float* outWeights);
+int  rtr_host_mis_weights_power(uint32_t n, const float* pb, const float* dist, const float* cosLight, const float* area, const uint32_t* lightTri,
+                                const uint64_t* cdf, uint32_t tris, uint32_t P, RtrMisSample* outSamples, float* outWBounce, float* outWeights);
+int  rtr_host_emitter_hits_power(const RtrRay* rays, const RtrHit* hits, const RtrSurface* prevSurfaces, const RtrBounce* bounces, uint32_t n,
+                                 const float* lightTris, const uint32_t* lightTriFirst, const RtrAreaLightInfo* lights, uint32_t numLights,
+                                 const uint64_t* cdf, const rtr_mis_params* mis, RtrEmitter* out);
+
 /* ---- errors --------------------------------------------------------------------------- */
 const char* rtr_last_error(void);
 const char* rtr_status_string(int status);

@@ -106,49 +106,66 @@ RTR_HD void rtr_mis_emitter_zero(RtrEmitter* e) {
     e->lightPdf = 0.0f; e->dist = 0.0f; e->lightTri = 0u; e->kind = 0u;
 }
 
+/* What the bounce side measures of one ray before any pick density enters: pb (the vertex's bounce density), NL = dot(N, L), d (the
+ * distance from x), cosL = dot(n_t, -L), and the area and pdfrec words of the record.  Shared by rtr_mis_emitter and
+ * rtr_power_mis_emitter (include/rtr_power.h), which differ in the pick term alone. */
+typedef struct rtr_mis_emitter_geom { float pb, NL, d, cosL, area, pdfrec; } rtr_mis_emitter_geom;
+
+/* 0 where the record stays zeros: a previous surface that is not an object, pb <= 0, NL <= 0, d == 0, a one-sided light met from behind
+ * (dot(n_t, x - P0) < 0, the light loops' test), or anything not finite on the way.  d is measured from x, not from the ray's origin
+ * normalOffset above it, and the ray does not stop 0.5 short as a shadow ray does. */
+RTR_HD int rtr_mis_emitter_measure(const RtrRay* ray, float t, const RtrSurface* prev, const RtrBounce* bounce, const float* rec, uint32_t twoSided,
+                                   rtr_mis_emitter_geom* g) {
+    if (prev->kind != RTR_SURFACE_OBJECT) return 0;
+    const float pb = bounce->pdf;
+    if (!(pb > 0.0f) || !rtr_bounce_finite(pb)) return 0;
+    const rtr_v3 o = rtr_ld3(ray->origin), dir = rtr_ld3(ray->direction), x = rtr_ld3(prev->position), N = rtr_ld3(prev->normal);
+    if (!(rtr_bounce_finite3(o) & rtr_bounce_finite3(dir) & rtr_bounce_finite3(x) & rtr_bounce_finite3(N) & rtr_bounce_finite(t))) return 0;
+    const rtr_v3 L = rtr_normalize(dir);
+    if (!rtr_bounce_finite3(L)) return 0;
+    const float NL = rtr_dot(N, L);
+    if (!(NL > 0.0f)) return 0;
+    const rtr_v3 y = rtr_madd(o, dir, t);
+    const float d = rtr_length(rtr_sub(y, x));
+    if (!(d > 0.0f) || !rtr_bounce_finite(d)) return 0;
+    const rtr_v3 P0 = rtr_ld3(rec), nt = rtr_ld3(rec + 12);
+    if (twoSided == 0u) {
+        if (rtr_dot(nt, rtr_sub(x, P0)) < 0.0f) return 0;
+    }
+    g->pb = pb; g->NL = NL; g->d = d; g->cosL = rtr_dot(nt, rtr_neg(L)); g->area = rec[3]; g->pdfrec = rec[7];
+    return 1;
+}
+
+/* The record of a measured ray once the heuristic's terms are known: a, b of the denominator, lightPdf and wBounce of the weights. */
+RTR_HD void rtr_mis_emitter_record(const rtr_mis_emitter_geom* m, float a, float b, float lightPdf, float wBounce, uint32_t lightTri,
+                                   const float* lightColor, float intensity, RtrEmitter* e) {
+    const float sum = a + b;
+    const float g = m->pb / sum;
+    const float k = rtr_max(m->NL, 0.1f) / m->NL;
+    const float den = m->pdfrec * m->area;
+    const rtr_v3 E = rtr_mk(((10.0f * lightColor[0]) * intensity) / den, ((10.0f * lightColor[1]) * intensity) / den, ((10.0f * lightColor[2]) * intensity) / den);
+    const rtr_v3 rad = rtr_mk((k * E.x) * g, (k * E.y) * g, (k * E.z) * g);
+    if (!rtr_bounce_finite3(rad)) return;
+    e->radiance[0] = rad.x; e->radiance[1] = rad.y; e->radiance[2] = rad.z; e->wBounce = wBounce;
+    e->lightPdf = lightPdf; e->dist = m->d; e->lightTri = lightTri; e->kind = RTR_SURFACE_LIGHT;
+}
+
 /* The whole per-ray function of the bounce side.  ray: the bounce ray (its direction need not be normalised; t is in its units); t: its
  * closest hit's parameter; prev: the RtrSurface of the vertex it left (x, N); bounce: that vertex's RtrBounce (pb = pdf); rec: the 16
  * floats of the light triangle's record {P0, area} {P1, pdfrec} {P2, -} {n_t, -}; lightTri: that record's index; lightColor, intensity,
  * twoSided: its light's words; sampled: the light is one of the first numAreaLights (the picks can reach it).  The caller has made sure
- * that the hit is a triangle of a light.  Zeros (rtr_mis_emitter_zero) for a previous surface that is not an object, pb <= 0, NL <= 0,
- * d == 0, a one-sided light met from behind (dot(n_t, x - P0) < 0, the light loops' test), or anything not finite on the way.  d is
- * measured from x, not from the ray's origin normalOffset above it, and the ray does not stop 0.5 short as a shadow ray does
- * (DESIGN.md section 4). */
+ * that the hit is a triangle of a light.  Zeros (rtr_mis_emitter_zero) where rtr_mis_emitter_measure gives 0. */
 RTR_HD void rtr_mis_emitter(const RtrRay* ray, float t, const RtrSurface* prev, const RtrBounce* bounce, const float* rec, uint32_t lightTri,
                             const float* lightColor, float intensity, uint32_t twoSided, int sampled, uint32_t Ttot, uint32_t P, RtrEmitter* e) {
     rtr_mis_emitter_zero(e);
-    if (prev->kind != RTR_SURFACE_OBJECT) return;
-    const float pb = bounce->pdf;
-    if (!(pb > 0.0f) || !rtr_bounce_finite(pb)) return;
-    const rtr_v3 o = rtr_ld3(ray->origin), dir = rtr_ld3(ray->direction), x = rtr_ld3(prev->position), N = rtr_ld3(prev->normal);
-    if (!(rtr_bounce_finite3(o) & rtr_bounce_finite3(dir) & rtr_bounce_finite3(x) & rtr_bounce_finite3(N) & rtr_bounce_finite(t))) return;
-    const rtr_v3 L = rtr_normalize(dir);
-    if (!rtr_bounce_finite3(L)) return;
-    const float NL = rtr_dot(N, L);
-    if (!(NL > 0.0f)) return;
-    const rtr_v3 y = rtr_madd(o, dir, t);
-    const float d = rtr_length(rtr_sub(y, x));
-    if (!(d > 0.0f) || !rtr_bounce_finite(d)) return;
-    const rtr_v3 P0 = rtr_ld3(rec), nt = rtr_ld3(rec + 12);
-    const float area = rec[3], pdfrec = rec[7];
-    if (twoSided == 0u) {
-        if (rtr_dot(nt, rtr_sub(x, P0)) < 0.0f) return;
-    }
-    const float cosL = rtr_dot(nt, rtr_neg(L));
+    rtr_mis_emitter_geom m;
+    if (!rtr_mis_emitter_measure(ray, t, prev, bounce, rec, twoSided, &m)) return;
     const uint32_t tt = sampled ? Ttot : 0u;
     float a, b;
-    rtr_mis_terms(pb, d, cosL, area, tt, P, &a, &b);
-    const float sum = a + b;
-    const float g = pb / sum;
-    const float k = rtr_max(NL, 0.1f) / NL;
-    const float den = pdfrec * area;
-    const rtr_v3 E = rtr_mk(((10.0f * lightColor[0]) * intensity) / den, ((10.0f * lightColor[1]) * intensity) / den, ((10.0f * lightColor[2]) * intensity) / den);
-    const rtr_v3 rad = rtr_mk((k * E.x) * g, (k * E.y) * g, (k * E.z) * g);
+    rtr_mis_terms(m.pb, m.d, m.cosL, m.area, tt, P, &a, &b);
     float lightPdf, wPick, wBounce;
-    rtr_mis_weights(pb, d, cosL, area, tt, P, &lightPdf, &wPick, &wBounce);
-    if (!rtr_bounce_finite3(rad)) return;
-    e->radiance[0] = rad.x; e->radiance[1] = rad.y; e->radiance[2] = rad.z; e->wBounce = wBounce;
-    e->lightPdf = lightPdf; e->dist = d; e->lightTri = lightTri; e->kind = RTR_SURFACE_LIGHT;
+    rtr_mis_weights(m.pb, m.d, m.cosL, m.area, tt, P, &lightPdf, &wPick, &wBounce);
+    rtr_mis_emitter_record(&m, a, b, lightPdf, wBounce, lightTri, lightColor, intensity, e);
 }
 
 #endif /* RTR_MIS_H */

@@ -245,6 +245,8 @@ PICK_MAX = 30                   # RTR_PICK_MAX: the most picked light samples pe
 PICK_NONE = 0xffffffff          # RTR_PICK_NONE: no area slot
 PICK_MAX_SLOTS = 1 << 24        # RTR_PICK_MAX_SLOTS: the most area slots a pick can be drawn from
 SKY_MAX_SAMPLES = 8             # RTR_SKY_MAX_SAMPLES: the most sky samples per path vertex
+POWER_SCALE = 1 << 20           # RTR_POWER_SCALE (include/rtr_power.h): the weight of the strongest light triangle
+POWER_SCAN_CHUNK = 256          # kPowerScanChunk: light triangles one pass of the device's table scan covers
 SKY_MIS = 1                     # RTR_SKY_MIS: the balance heuristic between the sky samples and the bounce
 VERTICES_HOST, VERTICES_DEVICE = 0, 1
 
@@ -372,6 +374,18 @@ RTR_SYMBOLS = {
     "rtr_host_sky_hits": (C.c_int, [P(rtr_texture), VP, P(rtr_sky_table), VP, VP, VP, VP, u32, P(rtr_sky_params), VP]),
     "rtr_host_sky_pdf": (C.c_int, [P(rtr_sky_table), VP, u32, VP]),
     "rtr_host_sky_radiance": (C.c_int, [P(rtr_texture), VP, VP, u32, VP]),
+    "rtr_scene_prepare_light_power": (C.c_int, [VP]),
+    "rtr_scene_export_light_power": (C.c_int, [VP, VP, VP, u32, P(u32)]),
+    "rtr_pick_slots_power_async": (C.c_int, [VP, VP, u32, P(rtr_light_params), P(rtr_pick_params), VP, VP, VP]),
+    "rtr_pick_slots_power": (C.c_int, [VP, VP, u32, P(rtr_light_params), P(rtr_pick_params), VP, VP, VP]),
+    "rtr_mis_pick_weights_power_async": (C.c_int, [VP, VP, VP, VP, u32, P(rtr_light_params), P(rtr_pick_params), P(rtr_mis_params), VP, VP, VP, VP]),
+    "rtr_mis_pick_weights_power": (C.c_int, [VP, VP, VP, VP, u32, P(rtr_light_params), P(rtr_pick_params), P(rtr_mis_params), VP, VP, VP, VP]),
+    "rtr_emitter_hits_power_async": (C.c_int, [VP, VP, VP, VP, VP, VP, u32, P(rtr_mis_params), VP]),
+    "rtr_emitter_hits_power": (C.c_int, [VP, VP, VP, VP, VP, VP, u32, P(rtr_mis_params), VP]),
+    "rtr_host_light_power": (C.c_int, [VP, VP, VP, u32, VP, VP]),
+    "rtr_host_pick_slots_power": (C.c_int, [VP, u32, VP, u32, P(rtr_light_params), P(rtr_pick_params), VP, VP]),
+    "rtr_host_mis_weights_power": (C.c_int, [u32, VP, VP, VP, VP, VP, VP, u32, u32, VP, VP, VP]),
+    "rtr_host_emitter_hits_power": (C.c_int, [VP, VP, VP, VP, u32, VP, VP, VP, u32, VP, P(rtr_mis_params), VP]),
 }
 
 RTRH_SYMBOLS = {

@@ -476,6 +476,24 @@ class Scene:
                                                    h.value), "rtr_scene_export_sky_table")
         return SkyTable(w.value, h.value, rows, marginal)
 
+    def prepare_light_power(self):
+        """rtr_scene_prepare_light_power: build the light-power table on the device now (synchronous; once per scene), so that the enqueued
+        power calls neither allocate nor join.  The first power call of a scene that was not prepared builds it the same way; from then on
+        every update of the lights or of their triangles remakes it on its own stream."""
+        _check(self.lib.rtr_scene_prepare_light_power(self.h), "rtr_scene_prepare_light_power")
+
+    def export_light_power(self):
+        """rtr_scene_export_light_power: the device's light-power table as it is now -> (weights, cdf): uint32 (T,) and uint64 (T,), one
+        integer weight and one inclusive sum per light triangle of all the lights, in export_light_tris' order: the words
+        host_light_power gives for export_light_tris() and the scene's lights"""
+        count = C.c_uint32(0)
+        self.lib.rtr_scene_export_light_power(self.h, None, None, 0, C.byref(count))      # refused unless there are none: reports the count
+        n = int(count.value)
+        w, cdf = np.zeros(n, np.uint32), np.zeros(n, np.uint64)
+        _check(self.lib.rtr_scene_export_light_power(self.h, w.ctypes.data_as(A.VP) if n else None, cdf.ctypes.data_as(A.VP) if n else None, n,
+                                                     C.byref(count)), "rtr_scene_export_light_power")
+        return w, cdf
+
     def set_instance_masks(self, masks):
         """rtr_scene_set_instance_masks: one 8-bit cull mask per instance, in instance order (array-like of uint8; default 0xff).  Only
         the masked queries (trace_rays / trace_occlusion with cull_mask or ray_masks) look at them; renders ignore them."""
@@ -1567,6 +1585,11 @@ def emitter_hits(scene, rays, hits, prev_surfaces, bounces, mis, ctx=None, async
     hits: their closest hits (a QueryResult or (N, 8) int32 records); prev_surfaces: the SurfaceResult (or (N, 20) float32 records) of the
     vertices the rays left; bounces: bounce_rays' BounceResult (or its (N, 8) raw records) at those vertices; mis: make_mis_params(...).
     Device tensors in give device tensors out, numpy in gives numpy out."""
+    return _emitter_hits("rtr_emitter_hits", scene, rays, hits, prev_surfaces, bounces, mis, ctx, asynchronous)
+
+
+def _emitter_hits(name, scene, rays, hits, prev_surfaces, bounces, mis, ctx, asynchronous):
+    """emitter_hits and emitter_hits_power: the same arrays; name: the entry point"""
     torch = _torch()
     ctx = ctx or scene.ctx
     dev = torch.device("cuda", ctx.device)
@@ -1584,8 +1607,8 @@ def emitter_hits(scene, rays, hits, prev_surfaces, bounces, mis, ctx=None, async
         raise ValueError(f"emitter_hits: {n} rays but {s.shape[0]} surfaces and {b.shape[0]} bounce records")
     out = torch.empty((n, 8), dtype=torch.float32, device=dev)
     _join_torchs_stream(ctx, torch, dev, asynchronous)
-    fn = ctx.lib.rtr_emitter_hits_async if asynchronous else ctx.lib.rtr_emitter_hits
-    _check(fn(ctx.h, scene.h, _ptr(r, n), _ptr(h, n), _ptr(s, n), _ptr(b, n), n, C.byref(mis), _ptr(out, n)), "rtr_emitter_hits")
+    fn = getattr(ctx.lib, name + "_async" if asynchronous else name)
+    _check(fn(ctx.h, scene.h, _ptr(r, n), _ptr(h, n), _ptr(s, n), _ptr(b, n), n, C.byref(mis), _ptr(out, n)), name)
     res = _emitter_result(out.cpu().numpy() if as_numpy else out, as_numpy, torch)
     res._keep = (r, h, s, b)
     return res
@@ -1641,6 +1664,11 @@ def _aligned_copy(x, align=16):
 def host_emitter_hits(rays, hits, prev_surfaces, bounces, light_tris, light_first, lights, mis):
     """rtr_host_emitter_hits: emitter_hits on the host, no device -> EmitterResult of numpy arrays.  light_tris, light_first:
     Scene.export_light_tris(); lights: the scene's A.RtrAreaLightInfo records (a sequence or a ctypes array)."""
+    return _host_emitter_hits(rays, hits, prev_surfaces, bounces, light_tris, light_first, lights, mis, None)
+
+
+def _host_emitter_hits(rays, hits, prev_surfaces, bounces, light_tris, light_first, lights, mis, _cdf):
+    """host_emitter_hits (_cdf is None) and host_emitter_hits_power: the same arrays"""
     lib = A.hip_lib()
     who = "host_emitter_hits"
     r, h = _aligned_copy(_host_words(rays, (8,), "rays", who)), _aligned_copy(_host_words(hits, (8,), "hits", who))
@@ -1656,11 +1684,193 @@ def host_emitter_hits(rays, hits, prev_surfaces, bounces, light_tris, light_firs
     if any(int(lf[l]) + int(li[l].numTriangles) > lt.shape[0] for l in range(len(lights))):
         raise ValueError(f"{who}: the lights' triangles reach past the {lt.shape[0]} records of light_tris")
     out = _aligned_copy(np.zeros((n, 8), np.float32))
+    if _cdf is not None:                 # host_emitter_hits_power: the same arrays and the table's sums
+        c = np.ascontiguousarray(_cdf, dtype=np.uint64).reshape(-1)
+        _check(lib.rtr_host_emitter_hits_power(r.ctypes.data_as(A.VP) if n else None, h.ctypes.data_as(A.VP) if n else None, s.ctypes.data_as(A.VP) if n else None,
+                                               b.ctypes.data_as(A.VP) if n else None, n, lt.ctypes.data_as(A.VP) if lt.size else None,
+                                               lf.ctypes.data_as(A.VP) if lf.size else None, li if len(lights) else None, len(lights),
+                                               c.ctypes.data_as(A.VP) if c.size else None, C.byref(mis), out.ctypes.data_as(A.VP) if n else None),
+               "host_emitter_hits_power")
+        return _emitter_result(out, True, None)
     _check(lib.rtr_host_emitter_hits(r.ctypes.data_as(A.VP) if n else None, h.ctypes.data_as(A.VP) if n else None, s.ctypes.data_as(A.VP) if n else None,
                                      b.ctypes.data_as(A.VP) if n else None, n, lt.ctypes.data_as(A.VP) if lt.size else None,
                                      lf.ctypes.data_as(A.VP) if lf.size else None, li if len(lights) else None, len(lights), C.byref(mis),
                                      out.ctypes.data_as(A.VP) if n else None), who)
     return _emitter_result(out, True, None)
+
+
+# ---- power-proportional light picks (rtr_pick_slots_power and the power forms of the MIS calls; include/rtr_power.h) --------------------
+def pick_slots_power(scene, n, params, pick, seeds=None, ctx=None, asynchronous=False):
+    """rtr_pick_slots_power: for n hits the area slots of pick.numPicks (P) picks each, drawn in proportion to the power of the light
+    triangles (the scene's light-power table), and the weights shade_hits_picked is to give them -> (slots, weights): int32 (n, P)
+    (uint32 for numpy; A.PICK_NONE: no triangle emits) and float32 (n, P), total / (P * weight of the slot's triangle).  seeds: int32
+    (n,) on the device (numpy in gives numpy out) or None, then the pixels' of params.width / spp; params: make_light_params(...) —
+    numAreaLights, numShadowRays, frame; pick.depth enters the seeds as in light_rays_picked.  slots go to light_rays_picked(slots=)."""
+    torch = _torch()
+    ctx = ctx or scene.ctx
+    dev = torch.device("cuda", ctx.device)
+    n, p = int(n), int(pick.numPicks)
+    as_numpy = isinstance(seeds, np.ndarray)
+    sd = _device_vector(torch, seeds, torch.int32, (np.int32, np.uint32), n, "seeds", dev, "pick_slots_power")
+    _check_async(ctx, torch, dev, "pick_slots_power", asynchronous)
+    slots = torch.empty((n, p), dtype=torch.int32, device=dev)
+    weights = torch.empty((n, p), dtype=torch.float32, device=dev)
+    _join_torchs_stream(ctx, torch, dev, asynchronous)
+    fn = ctx.lib.rtr_pick_slots_power_async if asynchronous else ctx.lib.rtr_pick_slots_power
+    _check(fn(ctx.h, scene.h, n, C.byref(params), C.byref(pick), _ptr(sd, n), _ptr(slots, n), _ptr(weights, n)), "rtr_pick_slots_power")
+    if as_numpy:
+        return slots.cpu().numpy().view(np.uint32), weights.cpu().numpy()
+    slots._keep = sd                     # an asynchronous call's inputs stay alive with its result
+    return slots, weights
+
+
+def mis_pick_weights_power(scene, rays, hits, params, pick, mis, slots, seeds=None, samples=False, ctx=None, asynchronous=False):
+    """rtr_mis_pick_weights_power: mis_pick_weights for power-proportional picks -> float32 (N, P): wPow * wPick, with the probability
+    of each slot's triangle read from the scene's light-power table; 0 for a pick without a ray and for a triangle of weight 0.
+    slots is needed: pick_slots_power's (N, P), or the caller's.  The other arguments and samples=True as mis_pick_weights."""
+    torch = _torch()
+    ctx = ctx or scene.ctx
+    dev = torch.device("cuda", ctx.device)
+    r, h, sd, as_numpy = _light_inputs(torch, scene, rays, hits, seeds, ctx, "mis_pick_weights_power", asynchronous)
+    n, p = int(r.shape[0]), int(pick.numPicks)
+    if slots is None:
+        raise ValueError("mis_pick_weights_power: slots must be given (pick_slots_power's, or the caller's)")
+    sl = _pick_vector(torch, slots, torch.int32, (np.int32, np.uint32), n, p, "slots", dev, "mis_pick_weights_power", as_numpy)
+    out = torch.empty((n, p), dtype=torch.float32, device=dev)
+    rec = torch.empty((n, p, 8), dtype=torch.float32, device=dev) if samples else None
+    _join_torchs_stream(ctx, torch, dev, asynchronous)
+    fn = ctx.lib.rtr_mis_pick_weights_power_async if asynchronous else ctx.lib.rtr_mis_pick_weights_power
+    _check(fn(ctx.h, scene.h, _ptr(r, n), _ptr(h, n), n, C.byref(params), C.byref(pick), C.byref(mis), _ptr(sd, n), _ptr(sl, n), _ptr(out, n),
+              _ptr(rec, n) if samples else None), "rtr_mis_pick_weights_power")
+    if as_numpy:
+        return (out.cpu().numpy(), rec.cpu().numpy()) if samples else out.cpu().numpy()
+    out._keep = (r, h, sd, sl)           # an asynchronous call's inputs stay alive with its result
+    return (out, rec) if samples else out
+
+
+def emitter_hits_power(scene, rays, hits, prev_surfaces, bounces, mis, ctx=None, asynchronous=False):
+    """rtr_emitter_hits_power: emitter_hits for a vertex whose picks were power-proportional -> EmitterResult; the pick density of the
+    hit triangle comes from the scene's light-power table.  The arguments as emitter_hits."""
+    return _emitter_hits("rtr_emitter_hits_power", scene, rays, hits, prev_surfaces, bounces, mis, ctx, asynchronous)
+
+
+def host_light_power(light_tris, light_first, lights):
+    """rtr_host_light_power: the light-power table on the host, no device -> (weights, cdf): uint32 (T,), uint64 (T,).  light_tris,
+    light_first: Scene.export_light_tris(); lights: the scene's A.RtrAreaLightInfo records (a sequence or a ctypes array)."""
+    lib = A.hip_lib()
+    who = "host_light_power"
+    lt = np.ascontiguousarray(light_tris, dtype=np.float32).reshape(-1, 16)
+    lf = np.ascontiguousarray(light_first, dtype=np.uint32).reshape(-1)
+    li = (A.RtrAreaLightInfo * len(lights))(*lights)
+    if lf.size != len(lights):
+        raise ValueError(f"{who}: {lf.size} first records but {len(lights)} lights")
+    total = sum(int(l.numTriangles) for l in li)
+    if total != lt.shape[0]:
+        raise ValueError(f"{who}: the lights have {total} triangles but light_tris {lt.shape[0]} records")
+    w, cdf = np.zeros(total, np.uint32), np.zeros(total, np.uint64)
+    _check(lib.rtr_host_light_power(lt.ctypes.data_as(A.VP) if lt.size else None, lf.ctypes.data_as(A.VP) if lf.size else None, li if len(lights) else None,
+                                    len(lights), w.ctypes.data_as(A.VP) if total else None, cdf.ctypes.data_as(A.VP) if total else None), who)
+    return w, cdf
+
+
+def _host_cdf(cdf, tris, who):
+    c = np.ascontiguousarray(cdf, dtype=np.uint64).reshape(-1)
+    if int(tris) > c.size:
+        raise ValueError(f"{who}: tris {tris} but the table has {c.size} sums")
+    return c
+
+
+def host_pick_slots_power(cdf, tris, seeds, n, params, pick):
+    """rtr_host_pick_slots_power: the slots and weights pick_slots_power gives n hits, on the host -> (uint32 (n, P), float32 (n, P)).
+    cdf: the table's sums (host_light_power's or an exported table's); tris: Ttot, the triangles of the first params.numAreaLights
+    lights; seeds: int32 / uint32 (n,) or None (the pixels' of params.width / spp)."""
+    lib = A.hip_lib()
+    who = "host_pick_slots_power"
+    n = int(n)
+    c = _host_cdf(cdf, tris, who)
+    sd = None
+    if seeds is not None:
+        sd = np.ascontiguousarray(seeds)
+        if sd.dtype not in (np.int32, np.uint32) or sd.shape != (n,):
+            raise ValueError(f"{who}: seeds must be int32 or uint32 ({n},), got {sd.dtype} {sd.shape}")
+    p = int(pick.numPicks)
+    slots, weights = np.zeros((n, p), np.uint32), np.zeros((n, p), np.float32)
+    _check(lib.rtr_host_pick_slots_power(c.ctypes.data_as(A.VP) if c.size else None, int(tris), sd.ctypes.data_as(A.VP) if sd is not None and n else None, n,
+                                         C.byref(params), C.byref(pick), slots.ctypes.data_as(A.VP) if slots.size else None,
+                                         weights.ctypes.data_as(A.VP) if weights.size else None), who)
+    return slots, weights
+
+
+def host_mis_weights_power(pb, dist, cos_light, area, light_tri, cdf, tris, picks):
+    """rtr_host_mis_weights_power: the balance heuristic of include/rtr_power.h for N directions -> (samples, w_bounce, weights): the
+    float32 (N, 8) RtrMisSample records (lightPdf, pb, wPick, cosLight, dist, area and the words lightTri, 0), wBounce (N,) and the
+    weight mis_pick_weights_power gives a pick on that triangle (N,).  light_tri: the triangle of each direction; cdf, tris: the table
+    and Ttot; picks: P (0: nobody picks)."""
+    lib = A.hip_lib()
+    who = "host_mis_weights_power"
+    arrs = [np.ascontiguousarray(x, dtype=np.float32).reshape(-1) for x in (pb, dist, cos_light, area)]
+    lt = np.ascontiguousarray(light_tri).reshape(-1)
+    if lt.dtype not in (np.int32, np.uint32):
+        lt = lt.astype(np.uint32)
+    n = int(arrs[0].size)
+    if any(a.size != n for a in arrs) or lt.size != n:
+        raise ValueError(f"{who}: pb, dist, cos_light, area and light_tri must have one length")
+    c = _host_cdf(cdf, tris, who)
+    out = np.zeros((n, 8), np.float32)
+    wb, wt = np.zeros(n, np.float32), np.zeros(n, np.float32)
+    ptrs = [a.ctypes.data_as(A.VP) if n else None for a in arrs]
+    _check(lib.rtr_host_mis_weights_power(n, ptrs[0], ptrs[1], ptrs[2], ptrs[3], lt.ctypes.data_as(A.VP) if n else None,
+                                          c.ctypes.data_as(A.VP) if c.size else None, int(tris), int(picks), out.ctypes.data_as(A.VP) if n else None,
+                                          wb.ctypes.data_as(A.VP) if n else None, wt.ctypes.data_as(A.VP) if n else None), who)
+    return out, wb, wt
+
+
+def host_emitter_hits_power(rays, hits, prev_surfaces, bounces, light_tris, light_first, lights, cdf, mis):
+    """rtr_host_emitter_hits_power: emitter_hits_power on the host, no device -> EmitterResult of numpy arrays.  cdf: the table's sums;
+    the other arguments as host_emitter_hits."""
+    return _host_emitter_hits(rays, hits, prev_surfaces, bounces, light_tris, light_first, lights, mis, cdf)
+
+
+def direct_light_power(scene, rays, hits=None, params=None, picks=1, pick_depth=0, seeds=None, mis=None, ctx=None, max_ray_bytes=256 << 20, occlusion="dense",
+                       shadow_cull_mask=None, shadow_ray_flags=0):
+    """direct_light's picked route with power-proportional picks: closest hit (when hits is None) -> pick_slots_power ->
+    light_rays_picked(slots=) -> trace_rays(any_hit=True) ("dense") or trace_occlusion ("queued") -> shade_hits_picked(weights=), in
+    direct_light's chunks: picks + 1 rays per hit, an unbiased estimate of the light loops' shadowed (and unshadowed) sum whose variance
+    does not grow with the spread of the lights' powers.  mis: None — the weights are pick_slots_power's — or make_mis_params(...) of
+    the vertex's bounce: then they are mis_pick_weights_power's for the same slots, and the bounce ray is to count the lights it meets
+    (emitter_hits_power).  The analytic sum is refused.  The other arguments as direct_light.  -> RadianceResult on the device."""
+    shadow_ray_flags = _ray_flags("direct_light_power", shadow_ray_flags, False)
+    if occlusion not in ("dense", "queued"):
+        raise ValueError(f"direct_light_power: occlusion must be 'dense' or 'queued' (the picked rays have no start hints), got {occlusion!r}")
+    if params is None:
+        raise ValueError("direct_light_power: params (make_light_params) are needed")
+    torch = _torch()
+    ctx = ctx or scene.ctx
+    if not isinstance(rays, torch.Tensor):
+        raise ValueError("direct_light_power: rays must be a device tensor")
+    if hits is None:
+        hits = trace_rays(scene, rays, ctx=ctx)
+    if isinstance(hits, QueryResult):
+        hits = hits.hits
+    n = int(rays.shape[0])
+    pick = make_pick_params(picks, pick_depth)
+    chunk = max(1, int(max_ray_bytes) // (32 * (int(pick.numPicks) + 1)))
+    out = torch.empty((n, 12), dtype=torch.float32, device=rays.device)
+    for a in range(0, n, chunk):
+        b = min(n, a + chunk)
+        sd = seeds[a:b] if seeds is not None else None
+        if sd is None and a:             # as direct_light: a later chunk carries its pixels' seeds
+            k = torch.arange(a, b, device=rays.device, dtype=torch.int64) // int(params.spp)
+            sd = ((k % int(params.width)) * 733 + (k // int(params.width)) * 1933).to(torch.int32)
+        r, h = rays[a:b], hits[a:b]
+        sl, w = pick_slots_power(scene, b - a, params, pick, seeds=sd, ctx=ctx)
+        if mis is not None:
+            w = mis_pick_weights_power(scene, r, h, params, pick, mis, sl, seeds=sd, ctx=ctx)
+        lr, sl = light_rays_picked(scene, r, h, params, pick, seeds=sd, slots=sl, ctx=ctx)
+        occ = (trace_occlusion(scene, lr, ctx=ctx, cull_mask=shadow_cull_mask, ray_flags=shadow_ray_flags) if occlusion == "queued"
+               else trace_rays(scene, lr, any_hit=True, ctx=ctx, cull_mask=shadow_cull_mask, ray_flags=shadow_ray_flags)).occluded
+        out[a:b] = shade_hits_picked(scene, r, h, params, pick, sl, occ, weights=w, seeds=sd, ctx=ctx).raw
+    return _radiance_result(out, False, torch)
 
 
 # ---- sky importance sampling at a path vertex (rtr_sky_rays, rtr_shade_sky, rtr_sky_hits; include/rtr_sky.h) ---------------------------
@@ -2011,9 +2221,33 @@ def path_trace_sky(scene, rays, light_params, bounces, sky_samples=1, sky_from=0
                        survival_floor, light_picks, pick_from, mis=True, sky=(sky_samples, int(sky_from), bool(sky_mis)) if sky_samples else None)
 
 
+def path_trace_power(scene, rays, light_params, bounces, sky_samples=1, sky_from=0, sky_mis=True, light_picks=1, pick_from=1, seeds=None, occlusion="dense",
+                     bounce_cull_mask=None, bounce_ray_flags=0, max_ray_bytes=256 << 20, ctx=None, compact=False, roulette_from=None, survival_floor=0.05):
+    """path_trace_sky with power-proportional light picks (include/rtr_power.h): the same loop, the same arguments and defaults, and
+
+        a vertex d >= pick_from takes direct_light_power(..., picks=P, pick_depth=d, mis = the MIS params at a MIS vertex, else None)
+            in place of direct_light(..., picks=P): its slots are pick_slots_power's and its weights that call's or
+            mis_pick_weights_power's
+        at a vertex d >= 1 whose hit is a light, rad = emitter_hits_power(...).radiance when vertex d - 1 was a MIS vertex.
+
+    The picks read the uniform picks' random numbers and one more each, none of them the bounce's or the roulette's, so which paths live
+    does not depend on them.  In a scene whose light triangles all have one power the picks' distribution is the uniform one.
+    occlusion="queued_own_leaf" raises ValueError at the first picked vertex, as with path_trace_picked.  -> PathResult."""
+    if light_picks is None:
+        raise ValueError("path_trace_power: light_picks must be given (the power table is what the picks are drawn from)")
+    sky_samples = int(sky_samples)
+    if not 0 <= sky_samples <= A.SKY_MAX_SAMPLES:
+        raise ValueError(f"path_trace_power: sky_samples must be 0 ... {A.SKY_MAX_SAMPLES}, got {sky_samples}")
+    if int(sky_from) < 0:
+        raise ValueError(f"path_trace_power: sky_from must be >= 0, got {sky_from}")
+    return _path_trace(scene, rays, light_params, bounces, seeds, occlusion, bounce_cull_mask, bounce_ray_flags, max_ray_bytes, ctx, compact, roulette_from,
+                       survival_floor, light_picks, pick_from, mis=True, sky=(sky_samples, int(sky_from), bool(sky_mis)) if sky_samples else None, power=True)
+
+
 def _path_trace(scene, rays, light_params, bounces, seeds, occlusion, bounce_cull_mask, bounce_ray_flags, max_ray_bytes, ctx, compact, roulette_from, survival_floor,
-                light_picks, pick_from, mis=False, sky=None):
-    """the loop of path_trace, path_trace_picked, path_trace_mis and path_trace_sky (sky: (samples, from, mis) or None)"""
+                light_picks, pick_from, mis=False, sky=None, power=False):
+    """the loop of path_trace, path_trace_picked, path_trace_mis, path_trace_sky and path_trace_power (sky: (samples, from, mis) or None;
+    power: the pick vertices take direct_light_power and the light hits emitter_hits_power)"""
     if roulette_from is not None and not compact:
         raise ValueError("path_trace: roulette_from needs compact=True (a path the roulette kills saves nothing while it keeps its lane)")
     if roulette_from is not None and int(roulette_from) < 0:
@@ -2050,7 +2284,10 @@ def _path_trace(scene, rays, light_params, bounces, seeds, occlusion, bounce_cul
         q = trace_rays(scene, r, ctx=ctx) if d == 0 else trace_rays(scene, r, ctx=ctx, cull_mask=bounce_cull_mask, ray_flags=bounce_ray_flags)
         sd = seeds if d == 0 else _wrap32(base.to(torch.int64) + d * PATH_SEED_STEP)
         mis_vertex = mis and int(pick_from) <= d < bounces
-        if mis_vertex:
+        if power and d >= int(pick_from):
+            lit = direct_light_power(scene, r, q, light_params, picks=light_picks, pick_depth=d, seeds=sd, mis=mis_params if mis_vertex else None, ctx=ctx,
+                                     max_ray_bytes=max_ray_bytes, occlusion=occlusion)
+        elif mis_vertex:
             w = mis_pick_weights(scene, r, q, light_params, make_pick_params(light_picks, d), mis_params, None, seeds=sd, ctx=ctx)
             lit = direct_light(scene, r, q, light_params, seeds=sd, ctx=ctx, max_ray_bytes=max_ray_bytes, occlusion=occlusion, picks=light_picks, pick_depth=d,
                                pick_weights=w)
@@ -2060,7 +2297,7 @@ def _path_trace(scene, rays, light_params, bounces, seeds, occlusion, bounce_cul
             lit = direct_light(scene, r, q, light_params, seeds=sd, ctx=ctx, max_ray_bytes=max_ray_bytes, occlusion=occlusion)
         rad = lit.shadowed
         if d >= 1:
-            met = emitter_hits(scene, r, q, prev[0], prev[1], mis_params, ctx=ctx).radiance if prev is not None else torch.zeros_like(rad)
+            met = (emitter_hits_power if power else emitter_hits)(scene, r, q, prev[0], prev[1], mis_params, ctx=ctx).radiance if prev is not None else torch.zeros_like(rad)
             rad = torch.where((lit.kind == A.SURFACE_LIGHT).unsqueeze(1), met, rad)
             if prev_sky is not None:
                 esc = (sky_hits(scene, r, q, prev_sky[0], prev_sky[1], make_sky_params(sky[0], d - 1, light_params.frame, light_params.width, light_params.spp,

@@ -7,15 +7,19 @@
  * gather that triangle's record (four 16-B pieces of the scene's light-triangle table, found at lightTriFirst[customIndex] +
  * primitiveId as k_hit_surfaces finds it) and 32 B of its light's info; the ids are checked against the light table before anything is
  * read there.  Every record is written: a lane without a light hit stores 32 zero bytes.
+ * POWER (rtr_emitter_hits_power; include/rtr_power.h): the pick density of the hit triangle comes from the scene's power table, two
+ * 8-B gathers of a.cdf and its total, read only by a lane that has a light hit.  The uniform instantiation reads nothing of the table.
  */
 #include <hip/hip_runtime.h>
 #include "rtr_mis_launch.h"
 #include "../../../include/rtr_mis.h"
+#include "../../../include/rtr_power.h"
 
 namespace rtrdev {
 
 constexpr int kEmitterBlock = 256;
 
+template <bool POWER>
 __global__ __launch_bounds__(kEmitterBlock) void k_emitter_hits(EmitterArgs a) {
     const uint32_t k = blockIdx.x * kEmitterBlock + threadIdx.x;
     if (k >= a.n) return;
@@ -45,7 +49,8 @@ __global__ __launch_bounds__(kEmitterBlock) void k_emitter_hits(EmitterArgs a) {
             b.pdf = b0.w;
             const float recf[16] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w, c2.x, c2.y, c2.z, c2.w, c3.x, c3.y, c3.z, c3.w};
             const float col[3] = {li->color[0], li->color[1], li->color[2]};
-            rtr_mis_emitter(&ray, h0.x, &sf, &b, recf, t, col, li->intensity, li->isTwoSided, l < a.numAreaLights, a.tris, a.picks, &e);
+            if (POWER) rtr_power_mis_emitter(&ray, h0.x, &sf, &b, recf, t, col, li->intensity, li->isTwoSided, rtr_power_ptri(a.cdf, a.tris, t), a.picks, &e);
+            else rtr_mis_emitter(&ray, h0.x, &sf, &b, recf, t, col, li->intensity, li->isTwoSided, l < a.numAreaLights, a.tris, a.picks, &e);
         }
     }
     float4* __restrict__ o = a.out + 2 * (size_t)k;
@@ -54,7 +59,9 @@ __global__ __launch_bounds__(kEmitterBlock) void k_emitter_hits(EmitterArgs a) {
 }
 
 hipError_t launch_emitter_hits(const EmitterArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL(k_emitter_hits, dim3((uint32_t)(((uint64_t)a.n + kEmitterBlock - 1) / kEmitterBlock)), dim3(kEmitterBlock), 0, s, a);
+    const dim3 grid((uint32_t)(((uint64_t)a.n + kEmitterBlock - 1) / kEmitterBlock));
+    if (a.cdf) hipLaunchKernelGGL(k_emitter_hits<true>, grid, dim3(kEmitterBlock), 0, s, a);
+    else hipLaunchKernelGGL(k_emitter_hits<false>, grid, dim3(kEmitterBlock), 0, s, a);
     return hipGetLastError();
 }
 

@@ -20,9 +20,11 @@ struct EmitterArgs {
     uint32_t tris;                   /* Ttot: their triangles */
     uint32_t picks;                  /* P */
     uint32_t n;
+    const uint64_t* cdf;             /* null: the uniform rule; else the scene's power table (include/rtr_power.h) */
 };
 
-/* one RtrEmitter per ray: rtr_mis_emitter (include/rtr_mis.h) where the hit is a triangle of a light, zeros elsewhere */
+/* one RtrEmitter per ray: rtr_mis_emitter (include/rtr_mis.h) where the hit is a triangle of a light, zeros elsewhere; with a.cdf rtr_power_mis_emitter
+ * (include/rtr_power.h) */
 hipError_t launch_emitter_hits(const EmitterArgs& a, hipStream_t stream);
 
 }  // namespace rtrdev

@@ -75,6 +75,7 @@ struct MisPickArgs {
     float4* outSamples;          /* n * P RtrMisSample as 2 x float4, or null */
     uint32_t lobes;              /* rtr_bounce_params::lobes of the vertex's bounce */
     uint32_t tris;               /* Ttot: the triangles of the first numAreaLights lights */
+    const uint64_t* cdf;         /* null: the uniform rule; else the scene's power table (include/rtr_power.h), and pa.slotsIn is needed */
 };
 
 /* The per-scene triangle -> leaf table (rtr_hit_leaves, rtr_light_rays_hinted): entry base[customIndex] + primitiveId, base = the prefix
@@ -146,7 +147,8 @@ hipError_t launch_shade_hits(const DeviceScene& sc, const LightArgs& la, hipStre
 /* the picked forms: per hit the shadow rays of pa.picks area slots and of the directional light, and the slots; the sums over them */
 hipError_t launch_light_rays_picked(const DeviceScene& sc, const PickArgs& pa, hipStream_t stream);
 hipError_t launch_shade_hits_picked(const DeviceScene& sc, const PickArgs& pa, hipStream_t stream);
-/* per pick the weight under the balance heuristic with the vertex's bounce sample, and optionally what it was made from */
+/* per pick the weight under the balance heuristic with the vertex's bounce sample, and optionally what it was made from; with ma.cdf the
+ * power form (rtr_mis_pick_weights_power) */
 hipError_t launch_mis_pick_weights(const DeviceScene& sc, const MisPickArgs& ma, hipStream_t stream);
 /* tonemap_pack of n float3 read strideWords floats apart */
 hipError_t launch_tonemap_pack(const float* radiance, uint32_t strideWords, uint32_t n, uint32_t* out, hipStream_t stream);

@@ -22,6 +22,7 @@
 #include "../../../include/rtr.h"
 #include "../../../include/rtr_pick.h"
 #include "../../../include/rtr_mis.h"
+#include "../../../include/rtr_power.h"
 
 namespace rtrdev {
 
@@ -714,7 +715,11 @@ hipError_t launch_shade_hits_picked(const DeviceScene& sc, const PickArgs& pa, h
  * its contribution is evaluated at; the triangle's area and normal are words of the record picked_sample reads.  The bounce density of
  * the pick's direction is rtr_mis_bounce_pdf on the words of the RtrSurface k_hit_surfaces writes for this hit (position, normal,
  * colour, roughness, metallic) and the ray's origin.  A slot is the caller's (pa.slotsIn) or drawn by the rule k_light_rays_picked
- * draws by.  Every weight and, when asked for, every RtrMisSample is written: zeros for a pick without a ray. */
+ * draws by.  Every weight and, when asked for, every RtrMisSample is written: zeros for a pick without a ray.
+ * POWER (rtr_mis_pick_weights_power; the rule is include/rtr_power.h): the slots are always the caller's, and the weight is wPow * wPick
+ * with the probability of the slot's triangle read from the scene's power table (ma.cdf, two 8-B gathers per pick).  The uniform
+ * instantiation reads nothing of the table and computes what it computed. */
+template <bool POWER>
 __global__ __launch_bounds__(kShadeBlock) void k_mis_pick_weights(DeviceScene sc, MisPickArgs ma) {
     const PickArgs& pa = ma.pa;
     const LightArgs& la = pa.la;
@@ -752,9 +757,13 @@ __global__ __launch_bounds__(kShadeBlock) void k_mis_pick_weights(DeviceScene sc
             const float area = rec[0].w;
             const float cosLight = rtr_dot(f4xyz(rec[3]), rtr_neg(ps.dir));
             const float pb = rtr_mis_bounce_pdf(&ray, &rs, ps.dir, ma.lobes);
-            float lightPdf, wPick, wBounce;
-            rtr_mis_weights(pb, ps.dist, cosLight, area, ma.tris, P, &lightPdf, &wPick, &wBounce);
-            const float wt = pa.defaultWeight * wPick;
+            float lightPdf, wPick, wBounce, wt;
+            if (POWER) {
+                wt = rtr_power_mis_pick(ma.cdf, ma.tris, t, P, pb, ps.dist, cosLight, area, &lightPdf, &wPick);
+            } else {
+                rtr_mis_weights(pb, ps.dist, cosLight, area, ma.tris, P, &lightPdf, &wPick, &wBounce);
+                wt = pa.defaultWeight * wPick;
+            }
             if (rtr_bounce_finite(wt) & rtr_bounce_finite(ps.dist) & rtr_bounce_finite(cosLight) & rtr_bounce_finite(area) & rtr_bounce_finite3(ps.dir)) {
                 w = wt;
                 m0 = make_float4(lightPdf, pb, wPick, cosLight);
@@ -768,7 +777,13 @@ __global__ __launch_bounds__(kShadeBlock) void k_mis_pick_weights(DeviceScene sc
 
 hipError_t launch_mis_pick_weights(const DeviceScene& sc, const MisPickArgs& ma, hipStream_t s) {
     if (ma.pa.picks == 0u || ma.pa.picks > RTR_PICK_MAX) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_mis_pick_weights, dim3((uint32_t)(((uint64_t)ma.pa.la.n + kShadeBlock - 1) / kShadeBlock)), dim3(kShadeBlock), 0, s, sc, ma);
+    const dim3 grid((uint32_t)(((uint64_t)ma.pa.la.n + kShadeBlock - 1) / kShadeBlock));
+    if (ma.cdf) {
+        if (!ma.pa.slotsIn) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(k_mis_pick_weights<true>, grid, dim3(kShadeBlock), 0, s, sc, ma);
+    } else {
+        hipLaunchKernelGGL(k_mis_pick_weights<false>, grid, dim3(kShadeBlock), 0, s, sc, ma);
+    }
     return hipGetLastError();
 }
 

@@ -396,6 +396,7 @@ static int make_light_tris(rtr_scene* s) {
     if (s->numLights == 0) return RTR_OK;
     hipError_t e = rtrdev::launch_light_tris(s->lights.p, s->vertices.p, s->indices.p, s->lightTriFirst.p, s->numLights, s->lightTris.p, s->ctx->stream);
     if (e != hipSuccess) return fail(RTR_ERR_HIP, "light-triangle records: %s", hipGetErrorString(e));
+    if (const int rc = enqueue_light_power(s, s->ctx->stream, "light-triangle records")) return rc;      /* a power table follows its records */
     HIP_TRY(hipStreamSynchronize(s->ctx->stream));     /* frames of other contexts may render this scene next */
     return RTR_OK;
 }
@@ -1035,6 +1036,8 @@ static int enqueue_refit_tail(rtr_scene* s, uint32_t serial, const char* who) {
     if (s->numLights) {
         e = rtrdev::launch_light_tris(s->lights.p, s->vertices.p, s->indices.p, s->lightTriFirst.p, s->numLights, s->lightTris.p, st);
         if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: light-triangle records: %s", who, hipGetErrorString(e));
+        /* a power table follows its records; a refused update rebuilds the same table from unchanged data */
+        if (const int rc = enqueue_light_power(s, st, who)) return rc;
     }
     e = rtrdev::launch_fold_update_status(firstBad, s->asyncWords.p + 4, serial, st);
     if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: status kernel: %s", who, hipGetErrorString(e));
@@ -1506,6 +1509,7 @@ int rtr_scene_update_lights(rtr_scene* s, const RtrAreaLightInfo* lights, uint32
     if (n) {
         HIP_TRY(hipDeviceSynchronize());       /* frames in flight on other streams read s->lights: joined before the rewrite (contract in rtr.h) */
         HIP_TRY(hipMemcpyAsync(s->lights.p, lights, n * sizeof(RtrAreaLightInfo), hipMemcpyHostToDevice, s->ctx->stream));
+        if (const int rc = enqueue_light_power(s, s->ctx->stream, "rtr_scene_update_lights")) return rc;      /* the powers follow colour and intensity */
         HIP_TRY(hipStreamSynchronize(s->ctx->stream));
         s->hostLights.assign(lights, lights + n);
     }

@@ -3,7 +3,7 @@
  * the helpers that more than one file calls, each under the name of the file that defines it (as rtrapi::name, and extern "C++" where
  * the definition stands inside that file's extern "C" block).  The ABI is split by subsystem —
  * rtr_api.cpp (errors, context, scene), rtr_api_render.cpp (frames and dispatch), rtr_api_query.cpp (ray queries), rtr_api_paths.cpp
- * (lighting and path vertices) — and a new subsystem gets a file of its own, not a section in one of these.  What is shared and is not
+ * (lighting and path vertices), rtr_api_power.cpp (the light-power table and its picks) — and a new subsystem gets a file of its own, not a section in one of these.  What is shared and is not
  * a name of the ABI lives in namespace rtrapi, which is hidden: the library exports nothing of it.  A helper one file uses stays
  * static in that file.  No anonymous namespace, no static or thread_local object and no function definition that is not inline
  * belongs here: every file would get a copy of its own (the text behind rtr_last_error is rtr_api.cpp's alone). */
@@ -191,6 +191,14 @@ struct rtr_scene {
     mutable DevBuf<uint32_t> skyRows;
     mutable DevBuf<uint64_t> skyMarginal;
     mutable bool skyReady = false;
+    /* the light-power table (rtr_scene_prepare_light_power, or the first call that needs it: ensure_light_power): one weight and one
+     * 64-bit inclusive sum per light triangle of all lights, and the word the build's maximum is folded into.  Their sizes are fixed
+     * for the scene's life; their CONTENT follows the light triangles and the light infos: whoever rewrites those enqueues the build
+     * behind the write (enqueue_light_power), once powerReady.  mutable: as the sky table */
+    mutable DevBuf<uint32_t> powerWeights, powerMax;
+    mutable DevBuf<uint64_t> powerCdf;
+    mutable uint32_t powerTris = 0;
+    mutable bool powerReady = false;
     DevBuf<rtrdev::DeviceTexture> texTable;
     std::vector<RtrAreaLightInfo> hostLights;
     std::vector<RtrInstance> hostInstances;
@@ -241,5 +249,15 @@ int check_handles(const rtr_ctx* c, const rtr_scene* s, const char* who);
 int check_same_device(const rtr_ctx* c, const rtr_scene* s, const char* who);
 int join_if_enqueued(rtr_ctx* c, int rc, uint32_t n);
 int ensure_leaf_table(rtr_ctx* c, const rtr_scene* s, const char* who);
+
+/* rtr_api_paths.cpp */
+int picked_scene_checks(const rtr_ctx* c, const rtr_scene* s, const rtr_light_params* p, const char* who, uint32_t* areaSlots, uint32_t* tris);
+
+/* rtr_api_power.cpp */
+/* makes the scene's power table if it has none: allocates, builds on `st` (the current device is the scene's) and JOINS, as the sky table */
+int ensure_light_power(const rtr_scene* s, hipStream_t st, const char* who);
+/* a scene that has a table: the build's launches on `st`, behind whatever rewrote the light triangles or the light infos there; no
+ * allocation, no join.  A scene without one: nothing */
+int enqueue_light_power(const rtr_scene* s, hipStream_t st, const char* who);
 
 }  // namespace rtrapi

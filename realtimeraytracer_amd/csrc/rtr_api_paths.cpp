@@ -206,8 +206,8 @@ int rtr_compact_paths(rtr_ctx* c, const RtrRay* rays, const float* throughput, c
 
 /* ---- picked light samples (kernels/rtr_query.hip; the rule is include/rtr_pick.h, the host form and the argument checks rtr_pick_host.cpp) -- */
 /* What the picked calls and rtr_mis_pick_weights do between their own argument checks and the launch: the handles, their device, the
- * scene's lights against the params.  areaSlots: A of include/rtr_pick.h; tris: the light triangles behind it. */
-static int picked_scene_checks(const rtr_ctx* c, const rtr_scene* s, const rtr_light_params* p, const char* who, uint32_t* areaSlots, uint32_t* tris) {
+ * scene's lights against the params.  areaSlots: A of include/rtr_pick.h; tris: the light triangles behind it.  (rtr_api_power.cpp calls it too.) */
+extern "C++" int rtrapi::picked_scene_checks(const rtr_ctx* c, const rtr_scene* s, const rtr_light_params* p, const char* who, uint32_t* areaSlots, uint32_t* tris) {
     if (const int rc = check_handles(c, s, who)) return rc;
     if (const int rc = check_same_device(c, s, who)) return rc;
     uint32_t q = 0;
@@ -271,11 +271,12 @@ int rtr_shade_hits_picked(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, co
 /* ---- MIS at a path vertex (kernels/rtr_query.hip, kernels/rtr_mis.hip; the rule is include/rtr_mis.h, the host forms and the argument checks rtr_mis_host.cpp) -- */
 static int enqueue_mis_pick_weights(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, uint32_t n, const rtr_light_params* p,
                                     const rtr_pick_params* pick, const rtr_mis_params* mis, const uint32_t* seeds, const uint32_t* slots,
-                                    float* outWeights, RtrMisSample* outSamples, const char* who) {
+                                    float* outWeights, RtrMisSample* outSamples, const char* who, bool power = false) {
     /* the params and the arrays are checked first, which needs nothing of the handles */
     if (const int rc = rtrdev::mis_check_params(who, mis)) return rc;
     if (const int rc = rtrdev::pick_check_params(who, p, pick, true)) return rc;
     if (const int rc = rtrdev::mis_check_pick_call(who, p, pick, mis, rays, hits, n, seeds, slots, outWeights, outSamples)) return rc;
+    if (power && n && !slots) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: slots is null", who);      /* the power form draws none itself */
     uint32_t areaSlots = 0, tris = 0;
     if (const int rc = picked_scene_checks(c, s, p, who, &areaSlots, &tris)) return rc;
     if (n == 0) return RTR_OK;
@@ -283,6 +284,10 @@ static int enqueue_mis_pick_weights(rtr_ctx* c, const rtr_scene* s, const RtrRay
     rtrdev::MisPickArgs ma{};
     fill_pick_args(ma.pa, s, rays, hits, n, p, pick, seeds, slots, areaSlots, tris);
     ma.outWeights = outWeights; ma.outSamples = reinterpret_cast<float4*>(outSamples); ma.lobes = mis->lobes; ma.tris = tris;
+    if (power) {
+        if (const int rc = ensure_light_power(s, c->stream, who)) return rc;
+        ma.cdf = s->powerCdf.p;
+    }
     return launched(rtrdev::launch_mis_pick_weights(s->dev, ma, c->stream), who);
 }
 
@@ -298,8 +303,22 @@ int rtr_mis_pick_weights(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, con
     return join_if_enqueued(c, enqueue_mis_pick_weights(c, s, rays, hits, n, p, pick, mis, seeds, slots, outWeights, outSamples, "rtr_mis_pick_weights"), n);
 }
 
+/* the power forms (include/rtr_power.h): the same checks and the same kernel's other instantiation, with the scene's power table */
+int rtr_mis_pick_weights_power_async(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, uint32_t n, const rtr_light_params* p,
+                                     const rtr_pick_params* pick, const rtr_mis_params* mis, const uint32_t* seeds, const uint32_t* slots,
+                                     float* outWeights, RtrMisSample* outSamples) {
+    return enqueue_mis_pick_weights(c, s, rays, hits, n, p, pick, mis, seeds, slots, outWeights, outSamples, "rtr_mis_pick_weights_power_async", true);
+}
+
+int rtr_mis_pick_weights_power(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, uint32_t n, const rtr_light_params* p,
+                               const rtr_pick_params* pick, const rtr_mis_params* mis, const uint32_t* seeds, const uint32_t* slots, float* outWeights,
+                               RtrMisSample* outSamples) {
+    return join_if_enqueued(c, enqueue_mis_pick_weights(c, s, rays, hits, n, p, pick, mis, seeds, slots, outWeights, outSamples,
+                                                        "rtr_mis_pick_weights_power", true), n);
+}
+
 static int enqueue_emitter_hits(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, const RtrSurface* prevSurfaces,
-                                const RtrBounce* bounces, uint32_t n, const rtr_mis_params* mis, RtrEmitter* out, const char* who) {
+                                const RtrBounce* bounces, uint32_t n, const rtr_mis_params* mis, RtrEmitter* out, const char* who, bool power = false) {
     /* the params and the arrays are checked first, which needs nothing of the handles */
     if (const int rc = rtrdev::mis_check_params(who, mis)) return rc;
     if (const int rc = n ? rtrdev::mis_check_emitter_arrays(who, rays, hits, prevSurfaces, bounces, out) : RTR_OK) return rc;
@@ -317,6 +336,10 @@ static int enqueue_emitter_hits(rtr_ctx* c, const rtr_scene* s, const RtrRay* ra
     a.out = reinterpret_cast<float4*>(out);
     a.lightTris = s->dev.lightTris; a.lightTriFirst = s->dev.lightTriFirst; a.lights = s->dev.lights; a.numLights = s->numLights;
     a.numAreaLights = mis->numAreaLights; a.tris = (uint32_t)tris; a.picks = mis->numPicks; a.n = n;
+    if (power) {
+        if (const int rc = ensure_light_power(s, c->stream, who)) return rc;
+        a.cdf = s->powerCdf.p;
+    }
     return launched(rtrdev::launch_emitter_hits(a, c->stream), who);
 }
 
@@ -328,6 +351,16 @@ int rtr_emitter_hits_async(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, c
 int rtr_emitter_hits(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, const RtrSurface* prevSurfaces, const RtrBounce* bounces,
                      uint32_t n, const rtr_mis_params* mis, RtrEmitter* out) {
     return join_if_enqueued(c, enqueue_emitter_hits(c, s, rays, hits, prevSurfaces, bounces, n, mis, out, "rtr_emitter_hits"), n);
+}
+
+int rtr_emitter_hits_power_async(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, const RtrSurface* prevSurfaces,
+                                 const RtrBounce* bounces, uint32_t n, const rtr_mis_params* mis, RtrEmitter* out) {
+    return enqueue_emitter_hits(c, s, rays, hits, prevSurfaces, bounces, n, mis, out, "rtr_emitter_hits_power_async", true);
+}
+
+int rtr_emitter_hits_power(rtr_ctx* c, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, const RtrSurface* prevSurfaces, const RtrBounce* bounces,
+                           uint32_t n, const rtr_mis_params* mis, RtrEmitter* out) {
+    return join_if_enqueued(c, enqueue_emitter_hits(c, s, rays, hits, prevSurfaces, bounces, n, mis, out, "rtr_emitter_hits_power", true), n);
 }
 
 /* ---- sky importance sampling (kernels/rtr_sky.hip; the rule is include/rtr_sky.h, the host forms and the argument checks rtr_sky_host.cpp) -- */

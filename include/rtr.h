@@ -980,6 +980,49 @@ int  rtr_host_compact_paths(const RtrRay* rays, const float* throughput, const u
                             uint32_t numPaths, const rtr_compact_params* params,
                             RtrRay* outRays, float* outThroughput, uint32_t* outSeeds, uint32_t* outPathIds, uint32_t* outCount);
 
+/* ---- accumulation: a vertex's radiance added to the image, and the throughput after its bounce --------------------------------
+ * What a path tracer does with the records of one vertex, so that a frame is library launches on one stream and nothing else.  The
+ * rule is include/rtr_accum.h, every step one IEEE binary32 operation per channel: for path k < numPaths
+ *     rad  = radiance[k].shadowed; for a light hit with RTR_ACCUM_LIGHTS_FROM_EMITTERS emitters[k].radiance, for a miss with
+ *            RTR_ACCUM_MISSES_FROM_ESCAPES escapes[k].radiance (0 where that array is NULL)
+ *     term = T[k] * rad, then + T[k] * skySums[4k .. 4k + 2] when skySums (rtr_shade_sky's output) is given
+ *     id   = pathIds ? pathIds[k] : k;  with id < params->numSlots: accum[id] += term, and outTerm[id] = term when outTerm is given
+ *     outThroughput[3k ..] = T[k] * bounces[k].weight when bounces and outThroughput are given (both or neither), for every k.
+ * Without the flags a light hit or a miss adds `shadowed`, the camera vertex's rule.  A term of zero is still added.  A path whose id
+ * is not below numSlots — RTR_PATH_NONE, what rtr_compact_paths writes behind the survivors — touches neither image, so a caller
+ * that never joins launches numPaths wide.  The ids below numSlots must be DISTINCT: there are no atomics, and an image row named
+ * twice ends up holding one of the two results.  Rows of outTerm that no path names keep their bytes; the caller clears them.
+ * DEVICE pointers: radiance, emitters, escapes, bounces and skySums 16-B aligned; throughput (path k's three floats at (char*)throughput
+ * + k * throughputStrideBytes), pathIds, accum, outTerm (slot id's three floats at id * imageStrideBytes) and outThroughput (packed,
+ * stride 12) 4-B aligned.  outThroughput == throughput with throughputStrideBytes 12 is allowed (in place); every other overlap of
+ * an output with an input or with another output is refused.
+ * ENQUEUED on ctx's stream, one launch: no allocation, no join, no copy back.  numPaths == 0 is RTR_OK and launches nothing.
+ * RTR_ERR_INVALID_ARGUMENT (with a message that names the function and the argument, and nothing written; the arrays and the params
+ * are checked before the handle) for a null radiance, throughput, accum or params, bounces without outThroughput or the reverse, a
+ * misaligned pointer, a stride that is not a multiple of 4 or below 12, unknown flag bits, non-zero _reserved words, numSlots 0, an
+ * array whose extent does not fit the address space, or such an overlap. */
+int  rtr_accumulate_paths_async(rtr_ctx* ctx, const RtrRadiance* radiance, const float* throughput, const uint32_t* pathIds,
+                                const RtrEmitter* emitters, const RtrSkyEscape* escapes, const float* skySums, const RtrBounce* bounces,
+                                uint32_t numPaths, const rtr_accum_params* params, float* accum, float* outTerm, float* outThroughput);
+/* The same, then joins ctx's stream (only that stream). */
+int  rtr_accumulate_paths(rtr_ctx* ctx, const RtrRadiance* radiance, const float* throughput, const uint32_t* pathIds,
+                          const RtrEmitter* emitters, const RtrSkyEscape* escapes, const float* skySums, const RtrBounce* bounces,
+                          uint32_t numPaths, const rtr_accum_params* params, float* accum, float* outTerm, float* outThroughput);
+/* The host restatement: the same function of the same bytes on HOST pointers, no device.  The same header in a plain loop; the
+ * device's words equal these bit for bit. */
+int  rtr_host_accumulate_paths(const RtrRadiance* radiance, const float* throughput, const uint32_t* pathIds,
+                               const RtrEmitter* emitters, const RtrSkyEscape* escapes, const float* skySums, const RtrBounce* bounces,
+                               uint32_t numPaths, const rtr_accum_params* params, float* accum, float* outTerm, float* outThroughput);
+/* The gather that goes with it: out[j] = src[rows[j]] for j < numRows, records of recordBytes bytes (a multiple of 4, at most 256);
+ * a row that is not below numSrc (RTR_PATH_NONE) gives a record of zero bytes.  With the ids of a rtr_compact_paths call that took
+ * pathIds == NULL as rows, the records of a vertex (RtrSurface, RtrBounce) and the pixel ids follow the survivors.  src, rows and out
+ * 4-B aligned DEVICE pointers (src may be NULL with numSrc == 0); 16-B accesses are used when recordBytes and both record arrays
+ * allow it.  One launch on ctx's stream; numRows == 0 is RTR_OK and launches nothing.  RTR_ERR_INVALID_ARGUMENT for a recordBytes
+ * that is 0, not a multiple of 4 or above 256, a null or misaligned pointer, or out overlapping src or rows. */
+int  rtr_gather_records_async(rtr_ctx* ctx, const void* src, uint32_t recordBytes, uint32_t numSrc, const uint32_t* rows, uint32_t numRows, void* out);
+int  rtr_gather_records(rtr_ctx* ctx, const void* src, uint32_t recordBytes, uint32_t numSrc, const uint32_t* rows, uint32_t numRows, void* out);
+int  rtr_host_gather_records(const void* src, uint32_t recordBytes, uint32_t numSrc, const uint32_t* rows, uint32_t numRows, void* out);
+
 /* ---- picked light samples: one-sample direct lighting for path vertices ------------------------------------------------------
  * rtr_light_rays sends all Q shadow rays of a hit; these send P picked area-light samples and the directional light.  With Ttot the
  * triangles of the first numAreaLights lights and ns = numShadowRays a hit has A = Ttot * ns = Q - 1 AREA SLOTS, rtr_light_slots' first

@@ -260,6 +260,20 @@ typedef struct rtr_compact_params {
     uint32_t _reserved[3];
 } rtr_compact_params;         /* 32 bytes */
 
+/* ---- path accumulation (rtr_accumulate_paths): one vertex's radiance added to the image, and the throughput after its bounce --------
+ * flags: with RTR_ACCUM_LIGHTS_FROM_EMITTERS a path whose hit is a light takes its radiance from the RtrEmitter records (0 without
+ * them) instead of RtrRadiance::shadowed; with RTR_ACCUM_MISSES_FROM_ESCAPES a path that missed takes it from the RtrSkyEscape records
+ * in the same way.  The rule itself is include/rtr_accum.h. */
+#define RTR_ACCUM_LIGHTS_FROM_EMITTERS 1u
+#define RTR_ACCUM_MISSES_FROM_ESCAPES  2u
+typedef struct rtr_accum_params {
+    uint32_t flags;
+    uint32_t numSlots;               /* rows of accum / outTerm; a path whose id is >= numSlots touches neither image */
+    uint32_t throughputStrideBytes;  /* input T: a multiple of 4, at least 12, as in rtr_compact_params */
+    uint32_t imageStrideBytes;       /* accum and outTerm: a multiple of 4, at least 12 (12: an (N,3) tensor; 16: float4) */
+    uint32_t _reserved[4];           /* must be 0 */
+} rtr_accum_params;                  /* 32 bytes */
+
 /* ---- picked light samples (rtr_light_rays_picked, rtr_shade_hits_picked): numPicks of a hit's area-light slots instead of all ---
  * A hit's AREA SLOTS are the first A = Q - 1 slots of rtr_light_slots, numbered the same way: slot j is sample j % numShadowRays of
  * light triangle j / numShadowRays.  numPicks (P, 1 ... RTR_PICK_MAX) of them are drawn per hit — pick p by
@@ -358,6 +372,7 @@ static_assert(sizeof(RtrRadiance) == 48, "radiance must be 48 B");
 static_assert(sizeof(RtrBounce) == 32, "bounce record must be 32 B");
 static_assert(sizeof(rtr_bounce_params) == 32, "bounce params must be 32 B");
 static_assert(sizeof(rtr_compact_params) == 32, "compact params must be 32 B");
+static_assert(sizeof(rtr_accum_params) == 32, "accum params must be 32 B");
 static_assert(sizeof(rtr_pick_params) == 32, "pick params must be 32 B");
 static_assert(sizeof(rtr_mis_params) == 32, "mis params must be 32 B");
 static_assert(sizeof(RtrMisSample) == 32, "mis sample must be 32 B");

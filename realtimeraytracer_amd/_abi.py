@@ -97,6 +97,10 @@ class rtr_compact_params(C.Structure):
     _fields_ = [("frame", u32), ("depth", u32), ("flags", u32), ("survivalFloor", f32), ("throughputStrideBytes", u32), ("_reserved", u32 * 3)]
 
 
+class rtr_accum_params(C.Structure):
+    _fields_ = [("flags", u32), ("numSlots", u32), ("throughputStrideBytes", u32), ("imageStrideBytes", u32), ("_reserved", u32 * 4)]
+
+
 class rtr_pick_params(C.Structure):
     _fields_ = [("numPicks", u32), ("depth", u32), ("_reserved", u32 * 6)]
 
@@ -210,6 +214,7 @@ assert C.sizeof(RtrSurface) == 80
 assert C.sizeof(RtrRadiance) == 48 and C.sizeof(rtr_light_params) == 32
 assert C.sizeof(RtrBounce) == 32 and C.sizeof(rtr_bounce_params) == 32
 assert C.sizeof(rtr_compact_params) == 32
+assert C.sizeof(rtr_accum_params) == 32
 assert C.sizeof(rtr_pick_params) == 32
 assert C.sizeof(rtr_mis_params) == 32 and C.sizeof(RtrMisSample) == 32 and C.sizeof(RtrEmitter) == 32
 assert C.sizeof(rtr_sky_params) == 32 and C.sizeof(RtrSkySample) == 32 and C.sizeof(RtrSkyEscape) == 32
@@ -241,7 +246,8 @@ LIGHT_SHADOWED, LIGHT_UNSHADOWED, LIGHT_ANALYTIC = 1, 2, 4
 BOUNCE_DIFFUSE, BOUNCE_SPECULAR = 1, 2
 COMPACT_ROULETTE = 1            # RTR_COMPACT_ROULETTE
 PATH_NONE = 0xffffffff          # RTR_PATH_NONE: the path id of a slot behind the survivors
-PICK_MAX = 30                   # RTR_PICK_MAX: the most picked light samples per hit
+ACCUM_LIGHTS_FROM_EMITTERS, ACCUM_MISSES_FROM_ESCAPES = 1, 2      # RTR_ACCUM_*: rtr_accum_params.flags
+PICK_MAX = 30                  # RTR_PICK_MAX: the most picked light samples per hit
 PICK_NONE = 0xffffffff          # RTR_PICK_NONE: no area slot
 PICK_MAX_SLOTS = 1 << 24        # RTR_PICK_MAX_SLOTS: the most area slots a pick can be drawn from
 SKY_MAX_SAMPLES = 8             # RTR_SKY_MAX_SAMPLES: the most sky samples per path vertex
@@ -347,6 +353,12 @@ RTR_SYMBOLS = {
     "rtr_compact_paths_async": (C.c_int, [VP, VP, VP, VP, VP, u32, P(rtr_compact_params), VP, C.c_size_t, VP, VP, VP, VP, VP]),
     "rtr_compact_paths": (C.c_int, [VP, VP, VP, VP, VP, u32, P(rtr_compact_params), VP, C.c_size_t, VP, VP, VP, VP, VP, P(u32)]),
     "rtr_host_compact_paths": (C.c_int, [VP, VP, VP, VP, u32, P(rtr_compact_params), VP, VP, VP, VP, P(u32)]),
+    "rtr_accumulate_paths_async": (C.c_int, [VP, VP, VP, VP, VP, VP, VP, VP, u32, P(rtr_accum_params), VP, VP, VP]),
+    "rtr_accumulate_paths": (C.c_int, [VP, VP, VP, VP, VP, VP, VP, VP, u32, P(rtr_accum_params), VP, VP, VP]),
+    "rtr_host_accumulate_paths": (C.c_int, [VP, VP, VP, VP, VP, VP, VP, u32, P(rtr_accum_params), VP, VP, VP]),
+    "rtr_gather_records_async": (C.c_int, [VP, VP, u32, u32, VP, u32, VP]),
+    "rtr_gather_records": (C.c_int, [VP, VP, u32, u32, VP, u32, VP]),
+    "rtr_host_gather_records": (C.c_int, [VP, u32, u32, VP, u32, VP]),
     "rtr_light_rays_picked_async": (C.c_int, [VP, VP, VP, VP, u32, P(rtr_light_params), P(rtr_pick_params), VP, VP, VP, VP]),
     "rtr_light_rays_picked": (C.c_int, [VP, VP, VP, VP, u32, P(rtr_light_params), P(rtr_pick_params), VP, VP, VP, VP]),
     "rtr_shade_hits_picked_async": (C.c_int, [VP, VP, VP, VP, u32, P(rtr_light_params), P(rtr_pick_params), VP, VP, VP, VP, VP]),

@@ -1523,6 +1523,170 @@ def host_compact_paths(rays, throughput, seeds=None, path_ids=None, params=None)
     return res
 
 
+# ---- accumulation of a vertex and the record gather (rtr_accumulate_paths, rtr_gather_records; include/rtr_accum.h) -------------------
+def make_accum_params(num_slots, lights_from_emitters=False, misses_from_escapes=False, throughput_stride=12, image_stride=12):
+    """rtr_accum_params.  num_slots: the rows of the image (a path whose id is not below it touches nothing); lights_from_emitters,
+    misses_from_escapes: RTR_ACCUM_LIGHTS_FROM_EMITTERS, RTR_ACCUM_MISSES_FROM_ESCAPES; throughput_stride, image_stride: bytes between
+    two rows of the input throughput and of the images (accumulate_paths sets both from the arrays it is given)"""
+    flags = (A.ACCUM_LIGHTS_FROM_EMITTERS if lights_from_emitters else 0) | (A.ACCUM_MISSES_FROM_ESCAPES if misses_from_escapes else 0)
+    return A.rtr_accum_params(flags, int(num_slots), int(throughput_stride), int(image_stride), (A.u32 * 4)(0, 0, 0, 0))
+
+
+def _accum_with_strides(params, throughput_stride, image_stride):
+    return A.rtr_accum_params(params.flags, params.numSlots, int(throughput_stride), int(image_stride), params._reserved)
+
+
+def _row_stride_bytes(x):
+    """bytes between two rows of a 2-D tensor or numpy array whose rows hold adjacent floats"""
+    if isinstance(x, np.ndarray):
+        return int(x.strides[0]) if x.shape[0] > 1 else 4 * int(x.shape[1])
+    return 4 * int(x.stride(0)) if x.shape[0] > 1 else 4 * int(x.shape[1])
+
+
+def _accum_rows(torch, x, widths, n, name, dev, who):
+    """a float32 tensor on dev of n rows (None: any number) whose leading three floats are adjacent: contiguous (rows, w) for a w of
+    widths, or a view of the first three columns of such rows"""
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.dim() != 2 or x.device != dev or (n is not None and int(x.shape[0]) != n):
+        raise ValueError(f"{who}: {name} must be a float32 ({'rows' if n is None else n}, 3) tensor on {dev}")
+    rows, w = int(x.shape[0]), int(x.shape[1])
+    view_of_wider = w == 3 and (rows < 2 or int(x.stride(0)) in widths)
+    if rows and ((w not in widths and not view_of_wider) or x.stride(1) != 1 or (rows > 1 and x.stride(0) < 3)):
+        raise ValueError(f"{who}: {name} must have {' or '.join(map(str, widths))} columns (or be the first three of such rows), the floats of a row adjacent")
+    return x
+
+
+def accumulate_paths(ctx, radiance, throughput, accum, params, path_ids=None, emitters=None, escapes=None, sky_sums=None, bounces=None, out_term=None,
+                     asynchronous=False):
+    """rtr_accumulate_paths: one vertex of the paths added to the image, accum[id] += T * rad (+ T * sky_sums), in place, and the
+    throughput after the vertex's bounce -> the new float32 (N, 3) throughput tensor, or None without bounces (the rule: include/rtr.h,
+    include/rtr_accum.h).  radiance: a RadianceResult or its raw (N, 12) tensor; throughput: float32 (N, 3), contiguous or a view of the
+    first three columns of wider rows, or (N, 8) RtrBounce records; accum: float32 (S, 3) or (S, 4), S >= params.numSlots; params:
+    make_accum_params(...) — its two strides are replaced by the arrays'; path_ids: int32 (N,) or None (path k is k); emitters, escapes:
+    an EmitterResult / SkyEscapeResult or their raw (N, 8) tensors; sky_sums: what shade_sky gave, (N, 3) over 16-B rows, or (N, 4);
+    bounces: a BounceResult or its raw (N, 8) tensor; out_term: None, or a tensor laid out as accum that takes the terms at their ids
+    (the caller clears it).  Device tensors only.  asynchronous as in trace_rays: the context must then be on torch's current stream."""
+    torch = _torch()
+    dev = torch.device("cuda", ctx.device)
+    who = "accumulate_paths"
+    unwrap = ((RadianceResult, radiance), (EmitterResult, emitters), (SkyEscapeResult, escapes), (BounceResult, bounces))
+    radiance, emitters, escapes, bounces = (x.raw if isinstance(x, cls) else x for cls, x in unwrap)
+    rad = _records(torch, radiance, 12, "radiance", dev, who, False)
+    n = int(rad.shape[0])
+    t = _accum_rows(torch, throughput, (3, 8), n, "throughput", dev, who)
+    acc = _accum_rows(torch, accum, (3, 4), None, "accum", dev, who)
+    if int(acc.shape[0]) < int(params.numSlots):
+        raise ValueError(f"{who}: accum has {acc.shape[0]} rows, params.numSlots is {params.numSlots}")
+    term = out_term
+    if term is not None:
+        _accum_rows(torch, term, (3, 4), int(acc.shape[0]), "out_term", dev, who)
+        if _row_stride_bytes(term) != _row_stride_bytes(acc):
+            raise ValueError(f"{who}: out_term must be laid out as accum")
+    ids = _device_vector(torch, path_ids, torch.int32, (np.int32, np.uint32), n, "path_ids", dev, who, as_numpy=False)
+    em = _records(torch, emitters, 8, "emitters", dev, who, False) if emitters is not None else None
+    es = _records(torch, escapes, 8, "escapes", dev, who, False) if escapes is not None else None
+    bo = _records(torch, bounces, 8, "bounces", dev, who, False) if bounces is not None else None
+    sk = _accum_rows(torch, sky_sums, (4,), n, "sky_sums", dev, who) if sky_sums is not None else None
+    if sk is not None and n > 1 and int(sk.stride(0)) != 4:
+        raise ValueError(f"{who}: sky_sums must lie in 16-B rows, as shade_sky gives them")
+    for name, x in (("emitters", em), ("escapes", es), ("bounces", bo)):
+        if x is not None and int(x.shape[0]) != n:
+            raise ValueError(f"{who}: {n} paths but {x.shape[0]} {name}")
+    _check_async(ctx, torch, dev, who, asynchronous)
+    out_t = torch.empty((n, 3), dtype=torch.float32, device=dev) if bo is not None else None
+    _join_torchs_stream(ctx, torch, dev, asynchronous)
+    p = _accum_with_strides(params, _row_stride_bytes(t) if n else 12, _row_stride_bytes(acc) if acc.shape[0] else 12)
+    fn = ctx.lib.rtr_accumulate_paths_async if asynchronous else ctx.lib.rtr_accumulate_paths
+    _check(fn(ctx.h, _ptr(rad, n), _ptr(t, n), _ptr(ids, n), _ptr(em, n), _ptr(es, n), _ptr(sk, n), _ptr(bo, n), n, C.byref(p), _ptr(acc, n), _ptr(term, n),
+              _ptr(out_t, n)), "rtr_accumulate_paths")
+    if out_t is not None:
+        out_t._keep = (rad, t, ids, em, es, sk, bo, acc, term)      # an asynchronous call's arrays stay alive with its result
+    return out_t
+
+
+def gather_records(ctx, src, rows, asynchronous=False):
+    """rtr_gather_records: out[j] = src[rows[j]], a zero record where rows[j] is not a row of src (A.PATH_NONE) -> a tensor of
+    src's dtype, (len(rows),) + src.shape[1:].  src: a contiguous device tensor of 32-bit elements whose rows are at most 256 B;
+    rows: int32 (M,) on the device (the words are read as unsigned)."""
+    torch = _torch()
+    dev = torch.device("cuda", ctx.device)
+    who = "gather_records"
+    if not isinstance(src, torch.Tensor) or src.device != dev or not src.is_contiguous() or src.element_size() != 4 or src.dim() < 1:
+        raise ValueError(f"{who}: src must be a contiguous tensor of 32-bit elements on {dev}")
+    num_src = int(src.shape[0])
+    record = 4 * int(np.prod(src.shape[1:], dtype=np.int64))
+    if not 4 <= record <= 256:
+        raise ValueError(f"{who}: a row of src is {record} B (4 ... 256)")
+    if not isinstance(rows, torch.Tensor) or rows.dim() != 1:
+        raise ValueError(f"{who}: rows must be an int32 (M,) tensor on {dev}")
+    m = int(rows.shape[0])
+    rw = _device_vector(torch, rows, torch.int32, (np.int32, np.uint32), m, "rows", dev, who, as_numpy=False)
+    _check_async(ctx, torch, dev, who, asynchronous)
+    out = torch.empty((m,) + tuple(src.shape[1:]), dtype=src.dtype, device=dev)
+    _join_torchs_stream(ctx, torch, dev, asynchronous)
+    fn = ctx.lib.rtr_gather_records_async if asynchronous else ctx.lib.rtr_gather_records
+    _check(fn(ctx.h, _ptr(src, num_src), record, num_src, _ptr(rw, m), m, _ptr(out, m)), "rtr_gather_records")
+    out._keep = (src, rw)
+    return out
+
+
+def host_accumulate_paths(radiance, throughput, accum, params, path_ids=None, emitters=None, escapes=None, sky_sums=None, bounces=None, out_term=None):
+    """rtr_host_accumulate_paths: the host restatement of accumulate_paths on numpy arrays, no device -> the new float32 (N, 3)
+    throughput, or None without bounces.  radiance: 32-bit words (N, 12); throughput: float32 (N, 3) or (N, 8); accum and out_term:
+    C-contiguous float32 (S, 3) or (S, 4), updated in place; path_ids: int32 / uint32 (N,); emitters, escapes, bounces: 32-bit words
+    (N, 8); sky_sums: float32 (N, 4).  params' strides are replaced by the arrays'."""
+    lib = A.hip_lib()
+    who = "host_accumulate_paths"
+    rad = _aligned_copy(_host_words(radiance, (12,), "radiance", who))
+    n = int(rad.shape[0])
+    t = np.ascontiguousarray(throughput)
+    if t.dtype != np.float32 or t.ndim != 2 or t.shape[0] != n or t.shape[1] not in (3, 8):
+        raise ValueError(f"{who}: throughput must be float32 ({n}, 3) or ({n}, 8), got {t.dtype} {t.shape}")
+    for name, x in (("accum", accum), ("out_term", out_term)):
+        if x is not None and (not isinstance(x, np.ndarray) or x.dtype != np.float32 or x.ndim != 2 or x.shape[1] not in (3, 4) or not x.flags.c_contiguous
+                              or not x.flags.writeable or x.shape != accum.shape or x.shape[0] < int(params.numSlots)):
+            raise ValueError(f"{who}: {name} must be a writable C-contiguous float32 (S, 3) or (S, 4) array, S >= numSlots")
+    ids = None
+    if path_ids is not None:
+        ids = np.ascontiguousarray(path_ids)
+        if ids.dtype not in (np.int32, np.uint32) or ids.shape != (n,):
+            raise ValueError(f"{who}: path_ids must be int32 or uint32 ({n},), got {ids.dtype} {ids.shape}")
+    rec = []
+    for name, x, w in (("emitters", emitters, 8), ("escapes", escapes, 8), ("sky_sums", sky_sums, 4), ("bounces", bounces, 8)):
+        if x is not None:
+            x = _aligned_copy(_host_words(x, (w,), name, who))
+            if x.shape[0] != n:
+                raise ValueError(f"{who}: {n} paths but {x.shape[0]} {name}")
+        rec.append(x)
+    em, es, sk, bo = rec
+    out_t = np.zeros((n, 3), np.float32) if bo is not None else None
+    p = _accum_with_strides(params, 4 * t.shape[1], 4 * accum.shape[1])
+
+    def ptr(x):
+        return x.ctypes.data_as(A.VP) if x is not None and n else None
+    _check(lib.rtr_host_accumulate_paths(ptr(rad), ptr(t), ptr(ids), ptr(em), ptr(es), ptr(sk), ptr(bo), n, C.byref(p), ptr(accum), ptr(out_term), ptr(out_t)),
+           "rtr_host_accumulate_paths")
+    return out_t
+
+
+def host_gather_records(src, rows):
+    """rtr_host_gather_records on numpy arrays -> out[j] = src[rows[j]], zeros where rows[j] is not a row of src.  src: 32-bit elements,
+    rows of at most 256 B; rows: int32 / uint32 (M,)."""
+    lib = A.hip_lib()
+    s = np.ascontiguousarray(src)
+    if s.dtype.itemsize != 4 or s.ndim < 1:
+        raise ValueError(f"host_gather_records: src must hold 32-bit elements, got {s.dtype} {s.shape}")
+    record = 4 * int(np.prod(s.shape[1:], dtype=np.int64))
+    if not 4 <= record <= 256:
+        raise ValueError(f"host_gather_records: a row of src is {record} B (4 ... 256)")
+    rw = np.ascontiguousarray(rows)
+    if rw.dtype not in (np.int32, np.uint32) or rw.ndim != 1:
+        raise ValueError(f"host_gather_records: rows must be int32 or uint32 (M,), got {rw.dtype} {rw.shape}")
+    out = np.zeros((rw.shape[0],) + s.shape[1:], s.dtype)
+    _check(lib.rtr_host_gather_records(s.ctypes.data_as(A.VP) if s.shape[0] else None, record, int(s.shape[0]), rw.ctypes.data_as(A.VP) if rw.shape[0] else None,
+                                       int(rw.shape[0]), out.ctypes.data_as(A.VP) if rw.shape[0] else None), "rtr_host_gather_records")
+    return out
+
+
 # ---- MIS at a path vertex (rtr_mis_pick_weights, rtr_emitter_hits; include/rtr_mis.h) -------------------------------------------------
 class EmitterResult:
     """What emitter_hits and host_emitter_hits give back.  raw: the (N, 8) float32 array of RtrEmitter records, of which radiance (N, 3)
@@ -2343,6 +2507,161 @@ def _path_trace(scene, rays, light_params, bounces, seeds, occlusion, bounce_cul
                 if prev_sky is not None:
                     prev_sky = (prev_sky[0][rows].contiguous(), prev_sky[1][rows].contiguous())
                 rows = rows.to(torch.int32) if ids is None else ids[rows]
+            ids = rows
+            bounce_seeds = base
+    return res
+
+
+# ---- the same loops with the per-vertex arithmetic in the library (rtr_accumulate_paths, rtr_gather_records) ---------------------------
+class _LoopDefault:
+    """the default of a path_trace_library keyword: whatever the named loop's own default is"""
+    def __repr__(self):
+        return "LOOP_DEFAULT"
+
+
+LOOP_DEFAULT = _LoopDefault()
+
+# the keywords each loop has beyond path_trace's, with their defaults there
+_LIBRARY_LOOPS = {
+    "plain": {},
+    "picked": {"light_picks": None, "pick_from": 1},
+    "mis": {"light_picks": 1, "pick_from": 1},
+    "sky": {"sky_samples": 1, "sky_from": 0, "sky_mis": True, "light_picks": 1, "pick_from": 1},
+    "power": {"sky_samples": 1, "sky_from": 0, "sky_mis": True, "light_picks": 1, "pick_from": 1},
+}
+
+
+def path_trace_library(scene, rays, light_params, bounces, loop="power", sky_samples=LOOP_DEFAULT, sky_from=LOOP_DEFAULT, sky_mis=LOOP_DEFAULT,
+                       light_picks=LOOP_DEFAULT, pick_from=LOOP_DEFAULT, seeds=None, occlusion="dense", bounce_cull_mask=None, bounce_ray_flags=0,
+                       max_ray_bytes=256 << 20, ctx=None, compact=False, roulette_from=None, survival_floor=0.05):
+    """path_trace ("plain"), path_trace_picked ("picked"), path_trace_mis ("mis"), path_trace_sky ("sky") or path_trace_power ("power")
+    with the arithmetic of a vertex done by the library: the same calls in the same order, but where those loops mask light hits and
+    misses, form T * rad and T * sky, scatter the terms to their ids, add them to the sum and multiply T by the bounce's weight in
+    torch, this one calls accumulate_paths once per vertex, after bounce_rays, so that it makes the next T too — with
+    RTR_ACCUM_LIGHTS_FROM_EMITTERS at every vertex d >= 1 (the emitter records where the vertex before was a MIS vertex, none
+    otherwise) and RTR_ACCUM_MISSES_FROM_ESCAPES where the vertex before was a sky vertex (none with sky_mis=False) — and after a
+    compaction gather_records moves the records of the vertex and the pixel ids to the survivors' rows.  The operations and their
+    order are those loops' (include/rtr_accum.h), so radiance, every per_depth[d] and live equal theirs bit for bit.
+    The keywords after loop are path_trace_power's; LOOP_DEFAULT stands for the named loop's own default, and a keyword that loop does
+    not have raises ValueError when it is given.  -> PathResult."""
+    if loop not in _LIBRARY_LOOPS:
+        raise ValueError(f"path_trace_library: loop must be one of {', '.join(map(repr, _LIBRARY_LOOPS))}, got {loop!r}")
+    own = _LIBRARY_LOOPS[loop]
+    kw = {}
+    for name, value in (("sky_samples", sky_samples), ("sky_from", sky_from), ("sky_mis", sky_mis), ("light_picks", light_picks), ("pick_from", pick_from)):
+        if name not in own and value is not LOOP_DEFAULT:
+            raise ValueError(f"path_trace_library: loop={loop!r} has no {name}")
+        kw[name] = own.get(name) if value is LOOP_DEFAULT else value
+    mis = loop in ("mis", "sky", "power")
+    sky = None
+    if mis and kw["light_picks"] is None:
+        raise ValueError(f"path_trace_library: loop={loop!r} needs light_picks (the MIS is between the picks and the bounce)")
+    if loop in ("sky", "power"):
+        s = int(kw["sky_samples"])
+        if not 0 <= s <= A.SKY_MAX_SAMPLES:
+            raise ValueError(f"path_trace_library: sky_samples must be 0 ... {A.SKY_MAX_SAMPLES}, got {s}")
+        if int(kw["sky_from"]) < 0:
+            raise ValueError(f"path_trace_library: sky_from must be >= 0, got {kw['sky_from']}")
+        sky = (s, int(kw["sky_from"]), bool(kw["sky_mis"])) if s else None
+    return _path_trace_library(scene, rays, light_params, bounces, seeds, occlusion, bounce_cull_mask, bounce_ray_flags, max_ray_bytes, ctx, compact,
+                               roulette_from, survival_floor, kw["light_picks"], 1 if kw["pick_from"] is None else kw["pick_from"], mis, sky, loop == "power")
+
+
+def _path_trace_library(scene, rays, light_params, bounces, seeds, occlusion, bounce_cull_mask, bounce_ray_flags, max_ray_bytes, ctx, compact, roulette_from,
+                        survival_floor, light_picks, pick_from, mis, sky, power):
+    """_path_trace, its arguments and its calls, with accumulate_paths and gather_records in place of the torch arithmetic"""
+    if roulette_from is not None and not compact:
+        raise ValueError("path_trace: roulette_from needs compact=True (a path the roulette kills saves nothing while it keeps its lane)")
+    if roulette_from is not None and int(roulette_from) < 0:
+        raise ValueError(f"path_trace: roulette_from must be >= 0, got {roulette_from}")
+    if light_picks is not None and int(light_params.outputs) & A.LIGHT_ANALYTIC:
+        raise ValueError("path_trace_picked: light_picks cannot give the analytic sum (light_params.outputs has LIGHT_ANALYTIC): the LTC term has no per-sample form")
+    if light_picks is not None and int(pick_from) < 0:
+        raise ValueError(f"path_trace_picked: pick_from must be >= 0, got {pick_from}")
+    torch = _torch()
+    ctx = ctx or scene.ctx
+    bounces = int(bounces)
+    if bounces < 0:
+        raise ValueError(f"path_trace: bounces must be >= 0, got {bounces}")
+    if not isinstance(rays, torch.Tensor):
+        raise ValueError("path_trace: rays must be a device tensor")
+    n = int(rays.shape[0])
+    base = seeds
+    if base is None and bounces > 0:
+        k = torch.arange(n, device=rays.device, dtype=torch.int64) // int(light_params.spp)
+        base = _wrap32((k % int(light_params.width)) * 733 + (k // int(light_params.width)) * 1933)      # 32-bit words, as the kernel's
+    res = PathResult()
+    res.per_depth = []
+    res.radiance = torch.zeros((n, 3), dtype=torch.float32, device=rays.device)      # the image accumulate_paths adds to, in place
+    T = torch.ones((n, 3), dtype=torch.float32, device=rays.device)
+    r = rays
+    ids = None                           # compact: the original slot of each row, from the first compaction on
+    bounce_seeds = seeds
+    if compact:
+        res.live = [n]
+    mis_params = make_mis_params(light_picks, light_params.numAreaLights, light_params.numShadowRays) if mis else None
+    prev = None                          # mis: (surfaces, bounce records) of the vertex before when it was a MIS vertex
+    prev_sky = None                      # sky: the same records of the vertex before when it was a sky vertex
+    for d in range(bounces + 1):
+        q = trace_rays(scene, r, ctx=ctx) if d == 0 else trace_rays(scene, r, ctx=ctx, cull_mask=bounce_cull_mask, ray_flags=bounce_ray_flags)
+        sd = seeds if d == 0 else _wrap32(base.to(torch.int64) + d * PATH_SEED_STEP)
+        mis_vertex = mis and int(pick_from) <= d < bounces
+        if power and d >= int(pick_from):
+            lit = direct_light_power(scene, r, q, light_params, picks=light_picks, pick_depth=d, seeds=sd, mis=mis_params if mis_vertex else None, ctx=ctx,
+                                     max_ray_bytes=max_ray_bytes, occlusion=occlusion)
+        elif mis_vertex:
+            w = mis_pick_weights(scene, r, q, light_params, make_pick_params(light_picks, d), mis_params, None, seeds=sd, ctx=ctx)
+            lit = direct_light(scene, r, q, light_params, seeds=sd, ctx=ctx, max_ray_bytes=max_ray_bytes, occlusion=occlusion, picks=light_picks, pick_depth=d,
+                               pick_weights=w)
+        elif light_picks is not None and d >= int(pick_from):
+            lit = direct_light(scene, r, q, light_params, seeds=sd, ctx=ctx, max_ray_bytes=max_ray_bytes, occlusion=occlusion, picks=light_picks, pick_depth=d)
+        else:
+            lit = direct_light(scene, r, q, light_params, seeds=sd, ctx=ctx, max_ray_bytes=max_ray_bytes, occlusion=occlusion)
+        met = esc = None                 # a light hit (a miss) at d >= 1 takes these records' radiance, 0 without them
+        if d >= 1 and prev is not None:
+            met = (emitter_hits_power if power else emitter_hits)(scene, r, q, prev[0], prev[1], mis_params, ctx=ctx).raw
+        if d >= 1 and prev_sky is not None and sky[2]:
+            esc = sky_hits(scene, r, q, prev_sky[0], prev_sky[1], make_sky_params(sky[0], d - 1, light_params.frame, light_params.width, light_params.spp,
+                                                                                 mis=True), ctx=ctx).raw
+        ap = make_accum_params(n, lights_from_emitters=d >= 1, misses_from_escapes=d >= 1 and prev_sky is not None)
+        sky_vertex = sky is not None and sky[1] <= d < bounces
+        surf = hit_surfaces(scene, r, q, ctx=ctx) if d < bounces else None
+        sums = None
+        if sky_vertex:
+            k = sky_rays(scene, r, surf, make_sky_params(sky[0], d, light_params.frame, light_params.width, light_params.spp, mis=sky[2]), seeds=bounce_seeds, ctx=ctx)
+            kr = k.rays.reshape(-1, 8)
+            occ = (trace_occlusion(scene, kr, ctx=ctx) if occlusion == "queued" else trace_rays(scene, kr, any_hit=True, ctx=ctx)).occluded
+            sums = shade_sky(ctx, k, occ)
+        b = None
+        if d < bounces:
+            b = bounce_rays(ctx, r, surf, make_bounce_params(frame=light_params.frame, depth=d, width=light_params.width, spp=light_params.spp), seeds=bounce_seeds)
+        term = torch.zeros((n, 3), dtype=torch.float32, device=rays.device)
+        T = accumulate_paths(ctx, lit, T, res.radiance, ap, path_ids=ids, emitters=met, escapes=esc, sky_sums=sums, bounces=b, out_term=term)
+        res.per_depth.append(term)
+        if d == bounces:
+            break
+        r = b.rays
+        prev = (surf.raw, b.raw) if mis_vertex else None
+        prev_sky = (surf.raw, b.raw) if sky_vertex else None
+        if compact:
+            c = compact_paths(ctx, r, T, seeds=base, path_ids=None if mis else ids,
+                              params=make_compact_params(frame=light_params.frame, depth=d, roulette=roulette_from is not None and d >= int(roulette_from),
+                                                         survival_floor=survival_floor))
+            m = c.count
+            res.live.append(m)
+            if m == 0:                   # nothing goes on: every later term is zero
+                for _ in range(d + 1, bounces + 1):
+                    res.per_depth.append(torch.zeros((n, 3), dtype=torch.float32, device=rays.device))
+                res.live += [0] * (bounces - d - 1)
+                break
+            r, T, base, rows = c.rays[:m], c.throughput[:m], c.seeds[:m], c.path_ids[:m]
+            if mis:                      # the ids are this call's row indices: the records of the vertex and the pixel ids follow the survivors
+                if prev is not None:
+                    prev = (gather_records(ctx, prev[0], rows), gather_records(ctx, prev[1], rows))
+                if prev_sky is not None:
+                    prev_sky = prev if mis_vertex and sky_vertex else (gather_records(ctx, prev_sky[0], rows), gather_records(ctx, prev_sky[1], rows))
+                if ids is not None:
+                    rows = gather_records(ctx, ids, rows)
             ids = rows
             bounce_seeds = base
     return res

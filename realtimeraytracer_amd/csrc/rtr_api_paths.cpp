@@ -1,5 +1,5 @@
 /* rtr_api_paths.cpp — the path-vertex calls of the C ABI in include/rtr.h: direct lighting and the tone map, continuation rays,
- * compaction, picked light samples, MIS and the sky, and rtr_scene_export_light_tris (rtr_api_internal.h has what the ABI's files
+ * compaction, accumulation and the record gather, picked light samples, MIS and the sky, and rtr_scene_export_light_tris (rtr_api_internal.h has what the ABI's files
  * share).  They read the scene and never write its tree. */
 #include "../../include/rtr.h"
 #include "kernels/rtr_kernels.h"
@@ -8,6 +8,8 @@
 #include "rtr_bounce_host.h"
 #include "kernels/rtr_paths_launch.h"
 #include "rtr_paths_host.h"
+#include "kernels/rtr_accum_launch.h"
+#include "rtr_accum_host.h"
 #include "rtr_pick_host.h"
 #include "kernels/rtr_mis_launch.h"
 #include "rtr_mis_host.h"
@@ -202,6 +204,58 @@ int rtr_compact_paths(rtr_ctx* c, const RtrRay* rays, const float* throughput, c
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
     return RTR_OK;
+}
+
+/* ---- accumulation of a vertex and the record gather (kernels/rtr_accum.hip; the rule is include/rtr_accum.h, the host forms and the argument checks rtr_accum_host.cpp) -- */
+static int enqueue_accumulate(rtr_ctx* c, const RtrRadiance* radiance, const float* throughput, const uint32_t* pathIds, const RtrEmitter* emitters,
+                              const RtrSkyEscape* escapes, const float* skySums, const RtrBounce* bounces, uint32_t n, const rtr_accum_params* p,
+                              float* accum, float* outTerm, float* outThroughput, const char* who) {
+    /* the arrays and the params are checked first, which needs nothing of the handle */
+    const rtrdev::AccumCall call{radiance, throughput, pathIds, emitters, escapes, skySums, bounces, n, p, accum, outTerm, outThroughput};
+    if (const int rc = n ? rtrdev::accum_check_args(who, call) : RTR_OK) return rc;
+    if (!c) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: ctx is null", who);
+    if (n == 0) return RTR_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    rtrdev::AccumArgs a{};
+    a.radiance = reinterpret_cast<const float4*>(radiance); a.throughput = reinterpret_cast<const char*>(throughput); a.pathIds = pathIds;
+    a.emitters = reinterpret_cast<const float4*>(emitters); a.escapes = reinterpret_cast<const float4*>(escapes);
+    a.skySums = reinterpret_cast<const float4*>(skySums); a.bounces = reinterpret_cast<const float4*>(bounces);
+    a.accum = reinterpret_cast<char*>(accum); a.outTerm = reinterpret_cast<char*>(outTerm); a.outThroughput = outThroughput;
+    a.params = *p; a.n = n;
+    return launched(rtrdev::launch_accumulate_paths(a, c->stream), who);
+}
+
+int rtr_accumulate_paths_async(rtr_ctx* c, const RtrRadiance* radiance, const float* throughput, const uint32_t* pathIds, const RtrEmitter* emitters,
+                               const RtrSkyEscape* escapes, const float* skySums, const RtrBounce* bounces, uint32_t n, const rtr_accum_params* p,
+                               float* accum, float* outTerm, float* outThroughput) {
+    return enqueue_accumulate(c, radiance, throughput, pathIds, emitters, escapes, skySums, bounces, n, p, accum, outTerm, outThroughput,
+                              "rtr_accumulate_paths_async");
+}
+
+int rtr_accumulate_paths(rtr_ctx* c, const RtrRadiance* radiance, const float* throughput, const uint32_t* pathIds, const RtrEmitter* emitters,
+                         const RtrSkyEscape* escapes, const float* skySums, const RtrBounce* bounces, uint32_t n, const rtr_accum_params* p,
+                         float* accum, float* outTerm, float* outThroughput) {
+    return join_if_enqueued(c, enqueue_accumulate(c, radiance, throughput, pathIds, emitters, escapes, skySums, bounces, n, p, accum, outTerm,
+                                                  outThroughput, "rtr_accumulate_paths"), n);
+}
+
+static int enqueue_gather(rtr_ctx* c, const void* src, uint32_t recordBytes, uint32_t numSrc, const uint32_t* rows, uint32_t numRows, void* out, const char* who) {
+    if (const int rc = numRows ? rtrdev::gather_check_args(who, src, recordBytes, numSrc, rows, numRows, out) : RTR_OK) return rc;
+    if (!c) return fail(RTR_ERR_INVALID_ARGUMENT, "%s: ctx is null", who);
+    if (numRows == 0) return RTR_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    rtrdev::GatherArgs a{};
+    a.src = static_cast<const char*>(src); a.rows = rows; a.out = static_cast<char*>(out);
+    a.recordBytes = recordBytes; a.numSrc = numSrc; a.numRows = numRows;
+    return launched(rtrdev::launch_gather_records(a, c->stream), who);
+}
+
+int rtr_gather_records_async(rtr_ctx* c, const void* src, uint32_t recordBytes, uint32_t numSrc, const uint32_t* rows, uint32_t numRows, void* out) {
+    return enqueue_gather(c, src, recordBytes, numSrc, rows, numRows, out, "rtr_gather_records_async");
+}
+
+int rtr_gather_records(rtr_ctx* c, const void* src, uint32_t recordBytes, uint32_t numSrc, const uint32_t* rows, uint32_t numRows, void* out) {
+    return join_if_enqueued(c, enqueue_gather(c, src, recordBytes, numSrc, rows, numRows, out, "rtr_gather_records"), numRows);
 }
 
 /* ---- picked light samples (kernels/rtr_query.hip; the rule is include/rtr_pick.h, the host form and the argument checks rtr_pick_host.cpp) -- */

@@ -1263,49 +1263,73 @@ def direct_light(scene, rays, hits=None, params=None, seeds=None, ctx=None, max_
     shadow_ray_flags = _ray_flags("direct_light", shadow_ray_flags, False)
     if occlusion not in ("dense", "queued", "queued_own_leaf"):
         raise ValueError(f"direct_light: occlusion must be 'dense', 'queued' or 'queued_own_leaf', got {occlusion!r}")
+    return _direct_light("direct_light", scene, rays, hits, params, seeds, ctx, max_ray_bytes, occlusion, shadow_cull_mask, shadow_ray_flags, picks, pick_depth,
+                         pick_weights=pick_weights)
+
+
+def _pixel_seeds(torch, params, a, b, device):
+    """the seed words px * 733 + py * 1933 of the pixels of hits a ... b - 1 in camera_rays' order (the pixel of hit k is (k // spp) %
+    width, (k // spp) // width): what the kernels give a hit without explicit seeds, as int32 (b - a,).  For every frame this project
+    allows the sum stays far inside 32 bits, so _wrap32 and the plain conversion to int32 give the same words; the conversion it is,
+    one launch where _wrap32 is five: a chunked direct_light builds these for every later chunk, and a frame's time showed the four."""
+    k = torch.arange(a, b, device=device, dtype=torch.int64) // int(params.spp)
+    return ((k % int(params.width)) * 733 + (k // int(params.width)) * 1933).to(torch.int32)
+
+
+def _occluded(scene, rays, occlusion, ctx, cull_mask=None, ray_flags=0):
+    """the visibility bytes of rays by the occlusion= route: trace_occlusion ("queued"), else the dense any-hit query"""
+    if occlusion == "queued":
+        return trace_occlusion(scene, rays, ctx=ctx, cull_mask=cull_mask, ray_flags=ray_flags).occluded
+    return trace_rays(scene, rays, any_hit=True, ctx=ctx, cull_mask=cull_mask, ray_flags=ray_flags).occluded
+
+
+def _direct_light(who, scene, rays, hits, params, seeds, ctx, max_ray_bytes, occlusion, shadow_cull_mask, shadow_ray_flags, picks, pick_depth, pick_weights=None,
+                  power=False, mis=None):
+    """the chunked stage of direct_light and direct_light_power (who: the one that was called, which has checked occlusion and the flags).
+    A chunk's light rays and its shading come from one of three routes: the full light loops (picks is None; "queued_own_leaf" with
+    their start hints), uniform picks (pick_weights: the caller's weights or None) or power-proportional picks (power; mis: the MIS
+    params of the vertex's bounce or None).  A later chunk without seeds carries its pixels' own."""
     if params is None:
-        raise ValueError("direct_light: params (make_light_params) are needed")
+        raise ValueError(f"{who}: params (make_light_params) are needed")
     torch = _torch()
     ctx = ctx or scene.ctx
     if not isinstance(rays, torch.Tensor):
-        raise ValueError("direct_light: rays must be a device tensor")
+        raise ValueError(f"{who}: rays must be a device tensor")
     if hits is None:
         hits = trace_rays(scene, rays, ctx=ctx)
     if isinstance(hits, QueryResult):
         hits = hits.hits
-    n, q = int(rays.shape[0]), light_slots(scene, params)
-    pick = None
+    n, pick = int(rays.shape[0]), None
+    q = None if power else light_slots(scene, params)      # direct_light asks for Q on its picked route too: the first check of the params
     if picks is not None:
         if occlusion == "queued_own_leaf":
-            raise ValueError("direct_light: occlusion='queued_own_leaf' needs start hints, which the picked rays do not have (picks must be None)")
+            raise ValueError(f"{who}: occlusion='queued_own_leaf' needs start hints, which the picked rays do not have (picks must be None)")
         pick = make_pick_params(picks, pick_depth)
         q = int(pick.numPicks) + 1
     chunk = max(1, int(max_ray_bytes) // (32 * q))
-    out =torch.empty((n, 12), dtype=torch.float32, device=rays.device)
+    out = torch.empty((n, 12), dtype=torch.float32, device=rays.device)
     for a in range(0, n, chunk):
         b = min(n, a + chunk)
-        sd = seeds[a:b] if seeds is not None else None
-        if sd is None and a:             # the pixel of hit k is (k // spp) % width, (k // spp) // width: a later chunk carries its seeds
-            k = torch.arange(a, b, device=rays.device, dtype=torch.int64) // int(params.spp)
-            sd = ((k % int(params.width)) * 733 + (k // int(params.width)) * 1933).to(torch.int32)      # wraps to 32 bits as the kernel's words do
+        sd = seeds[a:b] if seeds is not None else _pixel_seeds(torch, params, a, b, rays.device) if a else None
         r, h = rays[a:b], hits[a:b]
-        if pick is not None:
-            lr, sl = light_rays_picked(scene, r, h, params, pick, seeds=sd, ctx=ctx)
-            occ = (trace_occlusion(scene, lr, ctx=ctx, cull_mask=shadow_cull_mask, ray_flags=shadow_ray_flags) if occlusion == "queued"
-                   else trace_rays(scene, lr, any_hit=True, ctx=ctx, cull_mask=shadow_cull_mask, ray_flags=shadow_ray_flags)).occluded
-            if pick_weights is not None:
-                out[a:b] = shade_hits_picked(scene, r, h, params, pick, sl, occ, weights=pick_weights[a:b], seeds=sd, ctx=ctx).raw
-                continue
-            out[a:b] = shade_hits_picked(scene, r, h, params, pick, sl, occ, seeds=sd, ctx=ctx).raw
+        if pick is None:                 # the full light loops
+            if occlusion == "queued_own_leaf":
+                lr, leaves = light_rays(scene, r, h, params, seeds=sd, ctx=ctx, hints=True)
+                occ = trace_occlusion(scene, lr, ctx=ctx, start_leaves=leaves, cull_mask=shadow_cull_mask, ray_flags=shadow_ray_flags).occluded
+            else:
+                occ = _occluded(scene, light_rays(scene, r, h, params, seeds=sd, ctx=ctx), occlusion, ctx, shadow_cull_mask, shadow_ray_flags)
+            out[a:b] = shade_hits(scene, r, h, params, occ, seeds=sd, ctx=ctx).raw
             continue
-        if occlusion == "queued_own_leaf":
-            lr, leaves = light_rays(scene, r, h, params, seeds=sd, ctx=ctx, hints=True)
-            occ = trace_occlusion(scene, lr, ctx=ctx, start_leaves=leaves, cull_mask=shadow_cull_mask, ray_flags=shadow_ray_flags).occluded
-        else:
-            lr = light_rays(scene, r, h, params, seeds=sd, ctx=ctx)
-            occ = (trace_occlusion(scene, lr, ctx=ctx, cull_mask=shadow_cull_mask, ray_flags=shadow_ray_flags) if occlusion == "queued"
-                   else trace_rays(scene, lr, any_hit=True, ctx=ctx, cull_mask=shadow_cull_mask, ray_flags=shadow_ray_flags)).occluded
-        out[a:b] = shade_hits(scene, r, h, params, occ, seeds=sd, ctx=ctx).raw
+        if power:                        # power-proportional picks: the slots and their weights come first
+            sl, w = pick_slots_power(scene, b - a, params, pick, seeds=sd, ctx=ctx)
+            if mis is not None:
+                w = mis_pick_weights_power(scene, r, h, params, pick, mis, sl, seeds=sd, ctx=ctx)
+            lr, sl = light_rays_picked(scene, r, h, params, pick, seeds=sd, slots=sl, ctx=ctx)
+        else:                            # uniform picks: light_rays_picked draws the slots
+            lr, sl = light_rays_picked(scene, r, h, params, pick, seeds=sd, ctx=ctx)
+            w = None if pick_weights is None else pick_weights[a:b]
+        occ = _occluded(scene, lr, occlusion, ctx, shadow_cull_mask, shadow_ray_flags)
+        out[a:b] = shade_hits_picked(scene, r, h, params, pick, sl, occ, weights=w, seeds=sd, ctx=ctx).raw
     return _radiance_result(out, False, torch)
 
 
@@ -1714,18 +1738,25 @@ def mis_pick_weights(scene, rays, hits, params, pick, mis, slots, seeds=None, sa
     ray.  slots: light_rays_picked's (N, P), or None — the slots it draws by itself for the same params, pick and seeds.  samples=True:
     -> (weights, samples), samples the float32 (N, P, 8) RtrMisSample records (lightPdf, bouncePdf, wPick, cosLight, dist, area and the
     words lightTri, 0).  The other arguments as shade_hits_picked; numpy in gives numpy out."""
+    return _mis_pick_weights("mis_pick_weights", scene, rays, hits, params, pick, mis, slots, seeds, samples, ctx, asynchronous, need_slots=False)
+
+
+def _mis_pick_weights(name, scene, rays, hits, params, pick, mis, slots, seeds, samples, ctx, asynchronous, need_slots):
+    """mis_pick_weights and mis_pick_weights_power: the same arrays; name: the entry point without its rtr_; need_slots: None is refused"""
     torch = _torch()
     ctx = ctx or scene.ctx
     dev = torch.device("cuda", ctx.device)
-    r, h, sd, as_numpy = _light_inputs(torch, scene, rays, hits, seeds, ctx, "mis_pick_weights", asynchronous)
+    r, h, sd, as_numpy = _light_inputs(torch, scene, rays, hits, seeds, ctx, name, asynchronous)
     n, p = int(r.shape[0]), int(pick.numPicks)
-    sl = _pick_vector(torch, slots, torch.int32, (np.int32, np.uint32), n, p, "slots", dev, "mis_pick_weights", as_numpy)
+    if need_slots and slots is None:
+        raise ValueError(f"{name}: slots must be given (pick_slots_power's, or the caller's)")
+    sl = _pick_vector(torch, slots, torch.int32, (np.int32, np.uint32), n, p, "slots", dev, name, as_numpy)
     out = torch.empty((n, p), dtype=torch.float32, device=dev)
     rec = torch.empty((n, p, 8), dtype=torch.float32, device=dev) if samples else None
     _join_torchs_stream(ctx, torch, dev, asynchronous)
-    fn = ctx.lib.rtr_mis_pick_weights_async if asynchronous else ctx.lib.rtr_mis_pick_weights
+    fn = getattr(ctx.lib, f"rtr_{name}_async" if asynchronous else f"rtr_{name}")
     _check(fn(ctx.h, scene.h, _ptr(r, n), _ptr(h, n), n, C.byref(params), C.byref(pick), C.byref(mis), _ptr(sd, n), _ptr(sl, n), _ptr(out, n),
-              _ptr(rec, n) if samples else None), "rtr_mis_pick_weights")
+              _ptr(rec, n) if samples else None), f"rtr_{name}")
     if as_numpy:
         return (out.cpu().numpy(), rec.cpu().numpy()) if samples else out.cpu().numpy()
     out._keep = (r, h, sd, sl)           # an asynchronous call's inputs stay alive with its result
@@ -1892,24 +1923,7 @@ def mis_pick_weights_power(scene, rays, hits, params, pick, mis, slots, seeds=No
     """rtr_mis_pick_weights_power: mis_pick_weights for power-proportional picks -> float32 (N, P): wPow * wPick, with the probability
     of each slot's triangle read from the scene's light-power table; 0 for a pick without a ray and for a triangle of weight 0.
     slots is needed: pick_slots_power's (N, P), or the caller's.  The other arguments and samples=True as mis_pick_weights."""
-    torch = _torch()
-    ctx = ctx or scene.ctx
-    dev = torch.device("cuda", ctx.device)
-    r, h, sd, as_numpy = _light_inputs(torch, scene, rays, hits, seeds, ctx, "mis_pick_weights_power", asynchronous)
-    n, p = int(r.shape[0]), int(pick.numPicks)
-    if slots is None:
-        raise ValueError("mis_pick_weights_power: slots must be given (pick_slots_power's, or the caller's)")
-    sl = _pick_vector(torch, slots, torch.int32, (np.int32, np.uint32), n, p, "slots", dev, "mis_pick_weights_power", as_numpy)
-    out = torch.empty((n, p), dtype=torch.float32, device=dev)
-    rec = torch.empty((n, p, 8), dtype=torch.float32, device=dev) if samples else None
-    _join_torchs_stream(ctx, torch, dev, asynchronous)
-    fn = ctx.lib.rtr_mis_pick_weights_power_async if asynchronous else ctx.lib.rtr_mis_pick_weights_power
-    _check(fn(ctx.h, scene.h, _ptr(r, n), _ptr(h, n), n, C.byref(params), C.byref(pick), C.byref(mis), _ptr(sd, n), _ptr(sl, n), _ptr(out, n),
-              _ptr(rec, n) if samples else None), "rtr_mis_pick_weights_power")
-    if as_numpy:
-        return (out.cpu().numpy(), rec.cpu().numpy()) if samples else out.cpu().numpy()
-    out._keep = (r, h, sd, sl)           # an asynchronous call's inputs stay alive with its result
-    return (out, rec) if samples else out
+    return _mis_pick_weights("mis_pick_weights_power", scene, rays, hits, params, pick, mis, slots, seeds, samples, ctx, asynchronous, need_slots=True)
 
 
 def emitter_hits_power(scene, rays, hits, prev_surfaces, bounces, mis, ctx=None, asynchronous=False):
@@ -2006,35 +2020,8 @@ def direct_light_power(scene, rays, hits=None, params=None, picks=1, pick_depth=
     shadow_ray_flags = _ray_flags("direct_light_power", shadow_ray_flags, False)
     if occlusion not in ("dense", "queued"):
         raise ValueError(f"direct_light_power: occlusion must be 'dense' or 'queued' (the picked rays have no start hints), got {occlusion!r}")
-    if params is None:
-        raise ValueError("direct_light_power: params (make_light_params) are needed")
-    torch = _torch()
-    ctx = ctx or scene.ctx
-    if not isinstance(rays, torch.Tensor):
-        raise ValueError("direct_light_power: rays must be a device tensor")
-    if hits is None:
-        hits = trace_rays(scene, rays, ctx=ctx)
-    if isinstance(hits, QueryResult):
-        hits = hits.hits
-    n = int(rays.shape[0])
-    pick = make_pick_params(picks, pick_depth)
-    chunk = max(1, int(max_ray_bytes) // (32 * (int(pick.numPicks) + 1)))
-    out = torch.empty((n, 12), dtype=torch.float32, device=rays.device)
-    for a in range(0, n, chunk):
-        b = min(n, a + chunk)
-        sd = seeds[a:b] if seeds is not None else None
-        if sd is None and a:             # as direct_light: a later chunk carries its pixels' seeds
-            k = torch.arange(a, b, device=rays.device, dtype=torch.int64) // int(params.spp)
-            sd = ((k % int(params.width)) * 733 + (k // int(params.width)) * 1933).to(torch.int32)
-        r, h = rays[a:b], hits[a:b]
-        sl, w = pick_slots_power(scene, b - a, params, pick, seeds=sd, ctx=ctx)
-        if mis is not None:
-            w = mis_pick_weights_power(scene, r, h, params, pick, mis, sl, seeds=sd, ctx=ctx)
-        lr, sl = light_rays_picked(scene, r, h, params, pick, seeds=sd, slots=sl, ctx=ctx)
-        occ = (trace_occlusion(scene, lr, ctx=ctx, cull_mask=shadow_cull_mask, ray_flags=shadow_ray_flags) if occlusion == "queued"
-               else trace_rays(scene, lr, any_hit=True, ctx=ctx, cull_mask=shadow_cull_mask, ray_flags=shadow_ray_flags)).occluded
-        out[a:b] = shade_hits_picked(scene, r, h, params, pick, sl, occ, weights=w, seeds=sd, ctx=ctx).raw
-    return _radiance_result(out, False, torch)
+    return _direct_light("direct_light_power", scene, rays, hits, params, seeds, ctx, max_ray_bytes, occlusion, shadow_cull_mask, shadow_ray_flags, picks, pick_depth,
+                         power=True, mis=mis)
 
 
 # ---- sky importance sampling at a path vertex (rtr_sky_rays, rtr_shade_sky, rtr_sky_hits; include/rtr_sky.h) ---------------------------
@@ -2321,8 +2308,8 @@ def path_trace(scene, rays, light_params, bounces, seeds=None, occlusion="dense"
     p = max(max3(T), survival_floor) < 1 goes on with probability p and T / p (include/rtr_paths.h): the same mean, fewer paths, more
     variance.  roulette_from without compact raises ValueError.  Every vertex takes the full light loops; path_trace_picked is this
     loop with picked light samples at the later vertices.  -> PathResult."""
-    return _path_trace(scene, rays, light_params, bounces, seeds, occlusion, bounce_cull_mask, bounce_ray_flags, max_ray_bytes, ctx, compact, roulette_from,
-                       survival_floor, None, 1)
+    return _path_trace("path_trace", "plain", False, scene, rays, light_params, bounces, seeds, occlusion, bounce_cull_mask, bounce_ray_flags, max_ray_bytes, ctx,
+                       compact, roulette_from, survival_floor)
 
 
 def path_trace_picked(scene, rays, light_params, bounces, light_picks=None, pick_from=1, seeds=None, occlusion="dense", bounce_cull_mask=None, bounce_ray_flags=0,
@@ -2333,8 +2320,8 @@ def path_trace_picked(scene, rays, light_params, bounces, light_picks=None, pick
     the renderer's full loops by default (pick_from=1).  The picks read other random numbers than the bounce and the roulette, so which
     paths live does not depend on them.  light_picks with light_params.outputs asking for the analytic sum raises ValueError; None: every
     vertex takes the full loops, path_trace's calls and bytes.  -> PathResult."""
-    return _path_trace(scene, rays, light_params, bounces, seeds, occlusion, bounce_cull_mask, bounce_ray_flags, max_ray_bytes, ctx, compact, roulette_from,
-                       survival_floor, light_picks, pick_from)
+    return _path_trace("path_trace_picked", "picked", False, scene, rays, light_params, bounces, seeds, occlusion, bounce_cull_mask, bounce_ray_flags, max_ray_bytes, ctx,
+                       compact, roulette_from, survival_floor, light_picks=light_picks, pick_from=pick_from)
 
 
 def path_trace_mis(scene, rays, light_params, bounces, light_picks=1, pick_from=1, seeds=None, occlusion="dense", bounce_cull_mask=None, bounce_ray_flags=0,
@@ -2352,10 +2339,8 @@ def path_trace_mis(scene, rays, light_params, bounces, light_picks=1, pick_from=
     compact=True: S and B follow the survivors — compact_paths is called with path_ids=None, so that its ids are the row indices of that
     call; S, B and the pixel ids are gathered with them in torch (ids = ids[rows]), which gives the ids compact_paths would have
     gathered.  Without roulette the result is the plain loop's.  -> PathResult."""
-    if light_picks is None:
-        raise ValueError("path_trace_mis: light_picks must be given (the MIS is between the picks and the bounce)")
-    return _path_trace(scene, rays, light_params, bounces, seeds, occlusion, bounce_cull_mask, bounce_ray_flags, max_ray_bytes, ctx, compact, roulette_from,
-                       survival_floor, light_picks, pick_from, mis=True)
+    return _path_trace("path_trace_mis", "mis", False, scene, rays, light_params, bounces, seeds, occlusion, bounce_cull_mask, bounce_ray_flags, max_ray_bytes, ctx,
+                       compact, roulette_from, survival_floor, light_picks=light_picks, pick_from=pick_from)
 
 
 def path_trace_sky(scene, rays, light_params, bounces, sky_samples=1, sky_from=0, sky_mis=True, light_picks=1, pick_from=1, seeds=None, occlusion="dense",
@@ -2374,15 +2359,8 @@ def path_trace_sky(scene, rays, light_params, bounces, sky_samples=1, sky_from=0
     compact=True: the escape records' inputs follow the survivors as the emitter records' do.  sky_samples=0 is path_trace_mis, tensor
     for tensor.  The samples cover the whole sphere of directions (about half fall below the surface and are dead), and are drawn
     without regard to the BRDF.  -> PathResult."""
-    if light_picks is None:
-        raise ValueError("path_trace_sky: light_picks must be given (the loop is path_trace_mis's)")
-    sky_samples = int(sky_samples)
-    if not 0 <= sky_samples <= A.SKY_MAX_SAMPLES:
-        raise ValueError(f"path_trace_sky: sky_samples must be 0 ... {A.SKY_MAX_SAMPLES}, got {sky_samples}")
-    if int(sky_from) < 0:
-        raise ValueError(f"path_trace_sky: sky_from must be >= 0, got {sky_from}")
-    return _path_trace(scene, rays, light_params, bounces, seeds, occlusion, bounce_cull_mask, bounce_ray_flags, max_ray_bytes, ctx, compact, roulette_from,
-                       survival_floor, light_picks, pick_from, mis=True, sky=(sky_samples, int(sky_from), bool(sky_mis)) if sky_samples else None)
+    return _path_trace("path_trace_sky", "sky", False, scene, rays, light_params, bounces, seeds, occlusion, bounce_cull_mask, bounce_ray_flags, max_ray_bytes, ctx,
+                       compact, roulette_from, survival_floor, sky_samples=sky_samples, sky_from=sky_from, sky_mis=sky_mis, light_picks=light_picks, pick_from=pick_from)
 
 
 def path_trace_power(scene, rays, light_params, bounces, sky_samples=1, sky_from=0, sky_mis=True, light_picks=1, pick_from=1, seeds=None, occlusion="dense",
@@ -2397,122 +2375,10 @@ def path_trace_power(scene, rays, light_params, bounces, sky_samples=1, sky_from
     The picks read the uniform picks' random numbers and one more each, none of them the bounce's or the roulette's, so which paths live
     does not depend on them.  In a scene whose light triangles all have one power the picks' distribution is the uniform one.
     occlusion="queued_own_leaf" raises ValueError at the first picked vertex, as with path_trace_picked.  -> PathResult."""
-    if light_picks is None:
-        raise ValueError("path_trace_power: light_picks must be given (the power table is what the picks are drawn from)")
-    sky_samples = int(sky_samples)
-    if not 0 <= sky_samples <= A.SKY_MAX_SAMPLES:
-        raise ValueError(f"path_trace_power: sky_samples must be 0 ... {A.SKY_MAX_SAMPLES}, got {sky_samples}")
-    if int(sky_from) < 0:
-        raise ValueError(f"path_trace_power: sky_from must be >= 0, got {sky_from}")
-    return _path_trace(scene, rays, light_params, bounces, seeds, occlusion, bounce_cull_mask, bounce_ray_flags, max_ray_bytes, ctx, compact, roulette_from,
-                       survival_floor, light_picks, pick_from, mis=True, sky=(sky_samples, int(sky_from), bool(sky_mis)) if sky_samples else None, power=True)
+    return _path_trace("path_trace_power", "power", False, scene, rays, light_params, bounces, seeds, occlusion, bounce_cull_mask, bounce_ray_flags, max_ray_bytes, ctx,
+                       compact, roulette_from, survival_floor, sky_samples=sky_samples, sky_from=sky_from, sky_mis=sky_mis, light_picks=light_picks, pick_from=pick_from)
 
 
-def _path_trace(scene, rays, light_params, bounces, seeds, occlusion, bounce_cull_mask, bounce_ray_flags, max_ray_bytes, ctx, compact, roulette_from, survival_floor,
-                light_picks, pick_from, mis=False, sky=None, power=False):
-    """the loop of path_trace, path_trace_picked, path_trace_mis, path_trace_sky and path_trace_power (sky: (samples, from, mis) or None;
-    power: the pick vertices take direct_light_power and the light hits emitter_hits_power)"""
-    if roulette_from is not None and not compact:
-        raise ValueError("path_trace: roulette_from needs compact=True (a path the roulette kills saves nothing while it keeps its lane)")
-    if roulette_from is not None and int(roulette_from) < 0:
-        raise ValueError(f"path_trace: roulette_from must be >= 0, got {roulette_from}")
-    if light_picks is not None and int(light_params.outputs) & A.LIGHT_ANALYTIC:
-        raise ValueError("path_trace_picked: light_picks cannot give the analytic sum (light_params.outputs has LIGHT_ANALYTIC): the LTC term has no per-sample form")
-    if light_picks is not None and int(pick_from) < 0:
-        raise ValueError(f"path_trace_picked: pick_from must be >= 0, got {pick_from}")
-    torch = _torch()
-    ctx = ctx or scene.ctx
-    bounces = int(bounces)
-    if bounces < 0:
-        raise ValueError(f"path_trace: bounces must be >= 0, got {bounces}")
-    if not isinstance(rays, torch.Tensor):
-        raise ValueError("path_trace: rays must be a device tensor")
-    n = int(rays.shape[0])
-    base = seeds
-    if base is None and bounces > 0:
-        k = torch.arange(n, device=rays.device, dtype=torch.int64) // int(light_params.spp)
-        base = _wrap32((k % int(light_params.width)) * 733 + (k // int(light_params.width)) * 1933)      # 32-bit words, as the kernel's
-    res = PathResult()
-    res.per_depth = []
-    res.radiance = torch.zeros((n, 3), dtype=torch.float32, device=rays.device)
-    T = torch.ones((n, 3), dtype=torch.float32, device=rays.device)
-    r = rays
-    ids = None                           # compact: the original slot of each row, from the first compaction on
-    bounce_seeds = seeds
-    if compact:
-        res.live = [n]
-    mis_params = make_mis_params(light_picks, light_params.numAreaLights, light_params.numShadowRays) if mis else None
-    prev = None                          # mis: (surfaces, bounce records) of the vertex before when it was a MIS vertex
-    prev_sky = None                      # sky: the same records of the vertex before when it was a sky vertex
-    for d in range(bounces + 1):
-        q = trace_rays(scene, r, ctx=ctx) if d == 0 else trace_rays(scene, r, ctx=ctx, cull_mask=bounce_cull_mask, ray_flags=bounce_ray_flags)
-        sd = seeds if d == 0 else _wrap32(base.to(torch.int64) + d * PATH_SEED_STEP)
-        mis_vertex = mis and int(pick_from) <= d < bounces
-        if power and d >= int(pick_from):
-            lit = direct_light_power(scene, r, q, light_params, picks=light_picks, pick_depth=d, seeds=sd, mis=mis_params if mis_vertex else None, ctx=ctx,
-                                     max_ray_bytes=max_ray_bytes, occlusion=occlusion)
-        elif mis_vertex:
-            w = mis_pick_weights(scene, r, q, light_params, make_pick_params(light_picks, d), mis_params, None, seeds=sd, ctx=ctx)
-            lit = direct_light(scene, r, q, light_params, seeds=sd, ctx=ctx, max_ray_bytes=max_ray_bytes, occlusion=occlusion, picks=light_picks, pick_depth=d,
-                               pick_weights=w)
-        elif light_picks is not None and d >= int(pick_from):
-            lit = direct_light(scene, r, q, light_params, seeds=sd, ctx=ctx, max_ray_bytes=max_ray_bytes, occlusion=occlusion, picks=light_picks, pick_depth=d)
-        else:
-            lit = direct_light(scene, r, q, light_params, seeds=sd, ctx=ctx, max_ray_bytes=max_ray_bytes, occlusion=occlusion)
-        rad = lit.shadowed
-        if d >= 1:
-            met = (emitter_hits_power if power else emitter_hits)(scene, r, q, prev[0], prev[1], mis_params, ctx=ctx).radiance if prev is not None else torch.zeros_like(rad)
-            rad = torch.where((lit.kind == A.SURFACE_LIGHT).unsqueeze(1), met, rad)
-            if prev_sky is not None:
-                esc = (sky_hits(scene, r, q, prev_sky[0], prev_sky[1], make_sky_params(sky[0], d - 1, light_params.frame, light_params.width, light_params.spp,
-                                                                                       mis=True), ctx=ctx).radiance if sky[2] else torch.zeros_like(rad))
-                rad = torch.where((lit.kind == A.SURFACE_MISS).unsqueeze(1), esc, rad)
-        term = T * rad
-        sky_vertex = sky is not None and sky[1] <= d < bounces
-        surf = hit_surfaces(scene, r, q, ctx=ctx) if d < bounces else None
-        if sky_vertex:
-            k = sky_rays(scene, r, surf, make_sky_params(sky[0], d, light_params.frame, light_params.width, light_params.spp, mis=sky[2]), seeds=bounce_seeds, ctx=ctx)
-            kr = k.rays.reshape(-1, 8)
-            occ = (trace_occlusion(scene, kr, ctx=ctx) if occlusion == "queued" else trace_rays(scene, kr, any_hit=True, ctx=ctx)).occluded
-            term = term + T * shade_sky(ctx, k, occ)
-        if ids is not None:
-            full = torch.zeros((n, 3), dtype=torch.float32, device=rays.device)
-            full[ids.to(torch.int64)] = term
-            term = full
-        res.per_depth.append(term)
-        res.radiance = res.radiance + term
-        if d == bounces:
-            break
-        b = bounce_rays(ctx, r, surf, make_bounce_params(frame=light_params.frame, depth=d, width=light_params.width, spp=light_params.spp), seeds=bounce_seeds)
-        T = T * b.weight
-        r = b.rays
-        prev = (surf.raw, b.raw) if mis_vertex else None
-        prev_sky = (surf.raw, b.raw) if sky_vertex else None
-        if compact:
-            c = compact_paths(ctx, r, T, seeds=base, path_ids=None if mis else ids,
-                              params=make_compact_params(frame=light_params.frame, depth=d, roulette=roulette_from is not None and d >= int(roulette_from),
-                                                         survival_floor=survival_floor))
-            m = c.count
-            res.live.append(m)
-            if m == 0:                   # nothing goes on: every later term is zero
-                for _ in range(d + 1, bounces + 1):
-                    res.per_depth.append(torch.zeros((n, 3), dtype=torch.float32, device=rays.device))
-                res.live += [0] * (bounces - d - 1)
-                break
-            r, T, base, rows = c.rays[:m], c.throughput[:m], c.seeds[:m], c.path_ids[:m]
-            if mis:                      # the ids are this call's row indices: the records of the vertex and the pixel ids follow the survivors
-                rows = rows.to(torch.int64)
-                if prev is not None:
-                    prev = (prev[0][rows].contiguous(), prev[1][rows].contiguous())
-                if prev_sky is not None:
-                    prev_sky = (prev_sky[0][rows].contiguous(), prev_sky[1][rows].contiguous())
-                rows = rows.to(torch.int32) if ids is None else ids[rows]
-            ids = rows
-            bounce_seeds = base
-    return res
-
-
-# ---- the same loops with the per-vertex arithmetic in the library (rtr_accumulate_paths, rtr_gather_records) ---------------------------
 class _LoopDefault:
     """the default of a path_trace_library keyword: whatever the named loop's own default is"""
     def __repr__(self):
@@ -2522,54 +2388,58 @@ class _LoopDefault:
 LOOP_DEFAULT = _LoopDefault()
 
 # the keywords each loop has beyond path_trace's, with their defaults there
-_LIBRARY_LOOPS = {
+_LOOPS = {
     "plain": {},
     "picked": {"light_picks": None, "pick_from": 1},
     "mis": {"light_picks": 1, "pick_from": 1},
     "sky": {"sky_samples": 1, "sky_from": 0, "sky_mis": True, "light_picks": 1, "pick_from": 1},
     "power": {"sky_samples": 1, "sky_from": 0, "sky_mis": True, "light_picks": 1, "pick_from": 1},
 }
+# the loops with MIS vertices, and why each of them cannot do without light_picks
+_PICKS_NEEDED = {
+    "mis": "the MIS is between the picks and the bounce",
+    "sky": "the loop is path_trace_mis's",
+    "power": "the power table is what the picks are drawn from",
+}
 
 
-def path_trace_library(scene, rays, light_params, bounces, loop="power", sky_samples=LOOP_DEFAULT, sky_from=LOOP_DEFAULT, sky_mis=LOOP_DEFAULT,
-                       light_picks=LOOP_DEFAULT, pick_from=LOOP_DEFAULT, seeds=None, occlusion="dense", bounce_cull_mask=None, bounce_ray_flags=0,
-                       max_ray_bytes=256 << 20, ctx=None, compact=False, roulette_from=None, survival_floor=0.05):
-    """path_trace ("plain"), path_trace_picked ("picked"), path_trace_mis ("mis"), path_trace_sky ("sky") or path_trace_power ("power")
-    with the arithmetic of a vertex done by the library: the same calls in the same order, but where those loops mask light hits and
-    misses, form T * rad and T * sky, scatter the terms to their ids, add them to the sum and multiply T by the bounce's weight in
-    torch, this one calls accumulate_paths once per vertex, after bounce_rays, so that it makes the next T too — with
-    RTR_ACCUM_LIGHTS_FROM_EMITTERS at every vertex d >= 1 (the emitter records where the vertex before was a MIS vertex, none
-    otherwise) and RTR_ACCUM_MISSES_FROM_ESCAPES where the vertex before was a sky vertex (none with sky_mis=False) — and after a
-    compaction gather_records moves the records of the vertex and the pixel ids to the survivors' rows.  The operations and their
-    order are those loops' (include/rtr_accum.h), so radiance, every per_depth[d] and live equal theirs bit for bit.
-    The keywords after loop are path_trace_power's; LOOP_DEFAULT stands for the named loop's own default, and a keyword that loop does
-    not have raises ValueError when it is given.  -> PathResult."""
-    if loop not in _LIBRARY_LOOPS:
-        raise ValueError(f"path_trace_library: loop must be one of {', '.join(map(repr, _LIBRARY_LOOPS))}, got {loop!r}")
-    own = _LIBRARY_LOOPS[loop]
-    kw = {}
-    for name, value in (("sky_samples", sky_samples), ("sky_from", sky_from), ("sky_mis", sky_mis), ("light_picks", light_picks), ("pick_from", pick_from)):
+def _loop_keywords(who, loop, library, given):
+    """the keywords of a loop resolved through _LOOPS and checked -> (light_picks, pick_from, sky), sky: (samples, from, mis) or None.
+    who: the function that was called; given: its keywords (LOOP_DEFAULT or absent: the loop's own default).  Nothing but the keywords
+    is looked at."""
+    if loop not in _LOOPS:
+        raise ValueError(f"{who}: loop must be one of {', '.join(map(repr, _LOOPS))}, got {loop!r}")
+    own, kw = _LOOPS[loop], {}
+    for name in _LOOPS["power"]:
+        value = given.get(name, LOOP_DEFAULT)
         if name not in own and value is not LOOP_DEFAULT:
-            raise ValueError(f"path_trace_library: loop={loop!r} has no {name}")
+            raise ValueError(f"{who}: loop={loop!r} has no {name}")
         kw[name] = own.get(name) if value is LOOP_DEFAULT else value
-    mis = loop in ("mis", "sky", "power")
+    if loop in _PICKS_NEEDED and kw["light_picks"] is None:
+        raise ValueError(f"{who}: loop={loop!r} needs light_picks (the MIS is between the picks and the bounce)" if library
+                         else f"{who}: light_picks must be given ({_PICKS_NEEDED[loop]})")
     sky = None
-    if mis and kw["light_picks"] is None:
-        raise ValueError(f"path_trace_library: loop={loop!r} needs light_picks (the MIS is between the picks and the bounce)")
-    if loop in ("sky", "power"):
+    if "sky_samples" in own:
         s = int(kw["sky_samples"])
         if not 0 <= s <= A.SKY_MAX_SAMPLES:
-            raise ValueError(f"path_trace_library: sky_samples must be 0 ... {A.SKY_MAX_SAMPLES}, got {s}")
+            raise ValueError(f"{who}: sky_samples must be 0 ... {A.SKY_MAX_SAMPLES}, got {s}")
         if int(kw["sky_from"]) < 0:
-            raise ValueError(f"path_trace_library: sky_from must be >= 0, got {kw['sky_from']}")
+            raise ValueError(f"{who}: sky_from must be >= 0, got {kw['sky_from']}")
         sky = (s, int(kw["sky_from"]), bool(kw["sky_mis"])) if s else None
-    return _path_trace_library(scene, rays, light_params, bounces, seeds, occlusion, bounce_cull_mask, bounce_ray_flags, max_ray_bytes, ctx, compact,
-                               roulette_from, survival_floor, kw["light_picks"], 1 if kw["pick_from"] is None else kw["pick_from"], mis, sky, loop == "power")
+    if library and kw["pick_from"] is None:      # path_trace_library reads None as 1; a loop without picks never reads it
+        kw["pick_from"] = 1
+    return kw["light_picks"], kw["pick_from"], sky
 
 
-def _path_trace_library(scene, rays, light_params, bounces, seeds, occlusion, bounce_cull_mask, bounce_ray_flags, max_ray_bytes, ctx, compact, roulette_from,
-                        survival_floor, light_picks, pick_from, mis, sky, power):
-    """_path_trace, its arguments and its calls, with accumulate_paths and gather_records in place of the torch arithmetic"""
+def _path_trace(who, loop, library, scene, rays, light_params, bounces, seeds, occlusion, bounce_cull_mask, bounce_ray_flags, max_ray_bytes, ctx, compact, roulette_from,
+                survival_floor, **given):
+    """the loop of path_trace, path_trace_picked, path_trace_mis, path_trace_sky, path_trace_power and path_trace_library.  loop: its
+    name in _LOOPS ("mis", "sky", "power": with MIS vertices; "power": the pick vertices take direct_light_power and the light hits
+    emitter_hits_power); who, given: as _loop_keywords takes them.  library chooses between the two forms of what differs: step, the
+    arithmetic of a vertex (include/rtr_accum.h) in torch or by accumulate_paths, and take, the records of a compaction's survivors by
+    torch indexing or by gather_records.  Everything else, and its order, is written once, here."""
+    light_picks, pick_from, sky = _loop_keywords(who, loop, library, given)
+    mis, power = loop in _PICKS_NEEDED, loop == "power"
     if roulette_from is not None and not compact:
         raise ValueError("path_trace: roulette_from needs compact=True (a path the roulette kills saves nothing while it keeps its lane)")
     if roulette_from is not None and int(roulette_from) < 0:
@@ -2588,11 +2458,10 @@ def _path_trace_library(scene, rays, light_params, bounces, seeds, occlusion, bo
     n = int(rays.shape[0])
     base = seeds
     if base is None and bounces > 0:
-        k = torch.arange(n, device=rays.device, dtype=torch.int64) // int(light_params.spp)
-        base = _wrap32((k % int(light_params.width)) * 733 + (k // int(light_params.width)) * 1933)      # 32-bit words, as the kernel's
+        base = _pixel_seeds(torch, light_params, 0, n, rays.device)
     res = PathResult()
     res.per_depth = []
-    res.radiance = torch.zeros((n, 3), dtype=torch.float32, device=rays.device)      # the image accumulate_paths adds to, in place
+    res.radiance = torch.zeros((n, 3), dtype=torch.float32, device=rays.device)      # the library's step adds to it in place
     T = torch.ones((n, 3), dtype=torch.float32, device=rays.device)
     r = rays
     ids = None                           # compact: the original slot of each row, from the first compaction on
@@ -2602,6 +2471,35 @@ def _path_trace_library(scene, rays, light_params, bounces, seeds, occlusion, bo
     mis_params = make_mis_params(light_picks, light_params.numAreaLights, light_params.numShadowRays) if mis else None
     prev = None                          # mis: (surfaces, bounce records) of the vertex before when it was a MIS vertex
     prev_sky = None                      # sky: the same records of the vertex before when it was a sky vertex
+
+    # step: the vertex's term, (n, 3) with the live paths' at their ids, added to res.radiance -> (term, the throughput after bounce b or
+    # None).  met, esc: the emitter and the escape records or None; lights_from, misses_from: a light hit / a miss takes their radiance,
+    # 0 without them (RTR_ACCUM_LIGHTS_FROM_EMITTERS, RTR_ACCUM_MISSES_FROM_ESCAPES); sums: shade_sky's or None
+    def step_torch(lit, T, ids, met, esc, lights_from, misses_from, sums, b):
+        rad = lit.shadowed
+        if lights_from:
+            rad = torch.where((lit.kind == A.SURFACE_LIGHT).unsqueeze(1), met.radiance if met is not None else torch.zeros_like(rad), rad)
+        if misses_from:
+            rad = torch.where((lit.kind == A.SURFACE_MISS).unsqueeze(1), esc.radiance if esc is not None else torch.zeros_like(rad), rad)
+        term = T * rad
+        if sums is not None:
+            term = term + T * sums
+        if ids is not None:
+            full = torch.zeros((n, 3), dtype=torch.float32, device=rays.device)
+            full[ids.to(torch.int64)] = term
+            term = full
+        res.radiance = res.radiance + term
+        return term, T * b.weight if b is not None else None
+
+    def step_library(lit, T, ids, met, esc, lights_from, misses_from, sums, b):
+        term = torch.zeros((n, 3), dtype=torch.float32, device=rays.device)
+        ap = make_accum_params(n, lights_from_emitters=lights_from, misses_from_escapes=misses_from)
+        return term, accumulate_paths(ctx, lit, T, res.radiance, ap, path_ids=ids, emitters=met, escapes=esc, sky_sums=sums, bounces=b, out_term=term)
+
+    def take(records, rows):             # the records of the survivors; rows: compact_paths' ids, for torch as int64
+        return gather_records(ctx, records, rows) if library else records[rows].contiguous()
+
+    step = step_library if library else step_torch
     for d in range(bounces + 1):
         q = trace_rays(scene, r, ctx=ctx) if d == 0 else trace_rays(scene, r, ctx=ctx, cull_mask=bounce_cull_mask, ray_flags=bounce_ray_flags)
         sd = seeds if d == 0 else _wrap32(base.to(torch.int64) + d * PATH_SEED_STEP)
@@ -2619,24 +2517,20 @@ def _path_trace_library(scene, rays, light_params, bounces, seeds, occlusion, bo
             lit = direct_light(scene, r, q, light_params, seeds=sd, ctx=ctx, max_ray_bytes=max_ray_bytes, occlusion=occlusion)
         met = esc = None                 # a light hit (a miss) at d >= 1 takes these records' radiance, 0 without them
         if d >= 1 and prev is not None:
-            met = (emitter_hits_power if power else emitter_hits)(scene, r, q, prev[0], prev[1], mis_params, ctx=ctx).raw
+            met = (emitter_hits_power if power else emitter_hits)(scene, r, q, prev[0], prev[1], mis_params, ctx=ctx)
         if d >= 1 and prev_sky is not None and sky[2]:
-            esc = sky_hits(scene, r, q, prev_sky[0], prev_sky[1], make_sky_params(sky[0], d - 1, light_params.frame, light_params.width, light_params.spp,
-                                                                                 mis=True), ctx=ctx).raw
-        ap = make_accum_params(n, lights_from_emitters=d >= 1, misses_from_escapes=d >= 1 and prev_sky is not None)
+            esc = sky_hits(scene, r, q, prev_sky[0], prev_sky[1], make_sky_params(sky[0], d - 1, light_params.frame, light_params.width, light_params.spp, mis=True),
+                           ctx=ctx)
+        misses_from = d >= 1 and prev_sky is not None
         sky_vertex = sky is not None and sky[1] <= d < bounces
         surf = hit_surfaces(scene, r, q, ctx=ctx) if d < bounces else None
-        sums = None
+        sums = b = None
         if sky_vertex:
             k = sky_rays(scene, r, surf, make_sky_params(sky[0], d, light_params.frame, light_params.width, light_params.spp, mis=sky[2]), seeds=bounce_seeds, ctx=ctx)
-            kr = k.rays.reshape(-1, 8)
-            occ = (trace_occlusion(scene, kr, ctx=ctx) if occlusion == "queued" else trace_rays(scene, kr, any_hit=True, ctx=ctx)).occluded
-            sums = shade_sky(ctx, k, occ)
-        b = None
+            sums = shade_sky(ctx, k, _occluded(scene, k.rays.reshape(-1, 8), occlusion, ctx))
         if d < bounces:
             b = bounce_rays(ctx, r, surf, make_bounce_params(frame=light_params.frame, depth=d, width=light_params.width, spp=light_params.spp), seeds=bounce_seeds)
-        term = torch.zeros((n, 3), dtype=torch.float32, device=rays.device)
-        T = accumulate_paths(ctx, lit, T, res.radiance, ap, path_ids=ids, emitters=met, escapes=esc, sky_sums=sums, bounces=b, out_term=term)
+        term, T = step(lit, T, ids, met, esc, d >= 1, misses_from, sums, b)
         res.per_depth.append(term)
         if d == bounces:
             break
@@ -2656,12 +2550,31 @@ def _path_trace_library(scene, rays, light_params, bounces, seeds, occlusion, bo
                 break
             r, T, base, rows = c.rays[:m], c.throughput[:m], c.seeds[:m], c.path_ids[:m]
             if mis:                      # the ids are this call's row indices: the records of the vertex and the pixel ids follow the survivors
+                at = rows if library else rows.to(torch.int64)
                 if prev is not None:
-                    prev = (gather_records(ctx, prev[0], rows), gather_records(ctx, prev[1], rows))
+                    prev = (take(prev[0], at), take(prev[1], at))
                 if prev_sky is not None:
-                    prev_sky = prev if mis_vertex and sky_vertex else (gather_records(ctx, prev_sky[0], rows), gather_records(ctx, prev_sky[1], rows))
+                    prev_sky = prev if mis_vertex and sky_vertex else (take(prev_sky[0], at), take(prev_sky[1], at))
                 if ids is not None:
-                    rows = gather_records(ctx, ids, rows)
+                    rows = take(ids, at)
             ids = rows
             bounce_seeds = base
     return res
+
+
+# ---- the same loops with the per-vertex arithmetic in the library (rtr_accumulate_paths, rtr_gather_records) ---------------------------
+def path_trace_library(scene, rays, light_params, bounces, loop="power", sky_samples=LOOP_DEFAULT, sky_from=LOOP_DEFAULT, sky_mis=LOOP_DEFAULT,
+                       light_picks=LOOP_DEFAULT, pick_from=LOOP_DEFAULT, seeds=None, occlusion="dense", bounce_cull_mask=None, bounce_ray_flags=0,
+                       max_ray_bytes=256 << 20, ctx=None, compact=False, roulette_from=None, survival_floor=0.05):
+    """path_trace ("plain"), path_trace_picked ("picked"), path_trace_mis ("mis"), path_trace_sky ("sky") or path_trace_power ("power")
+    with the arithmetic of a vertex done by the library: the same calls in the same order, but where those loops mask light hits and
+    misses, form T * rad and T * sky, scatter the terms to their ids, add them to the sum and multiply T by the bounce's weight in
+    torch, this one calls accumulate_paths once per vertex, after bounce_rays, so that it makes the next T too — with
+    RTR_ACCUM_LIGHTS_FROM_EMITTERS at every vertex d >= 1 (the emitter records where the vertex before was a MIS vertex, none
+    otherwise) and RTR_ACCUM_MISSES_FROM_ESCAPES where the vertex before was a sky vertex (none with sky_mis=False) — and after a
+    compaction gather_records moves the records of the vertex and the pixel ids to the survivors' rows.  The operations and their
+    order are those loops' (include/rtr_accum.h), so radiance, every per_depth[d] and live equal theirs bit for bit.
+    The keywords after loop are path_trace_power's; LOOP_DEFAULT stands for the named loop's own default, and a keyword that loop does
+    not have raises ValueError when it is given.  -> PathResult."""
+    return _path_trace("path_trace_library", loop, True, scene, rays, light_params, bounces, seeds, occlusion, bounce_cull_mask, bounce_ray_flags, max_ray_bytes, ctx,
+                       compact, roulette_from, survival_floor, sky_samples=sky_samples, sky_from=sky_from, sky_mis=sky_mis, light_picks=light_picks, pick_from=pick_from)

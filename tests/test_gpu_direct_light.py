@@ -430,3 +430,29 @@ def test_direct_light_in_chunks_equals_one_pass(gpu_ctx, scene_cache):
     b = api.direct_light(scene, rays, params=p, seeds=seeds, max_ray_bytes=chunk * Q * 32)
     assert torch.equal(a.raw.view(torch.int32), b.raw.view(torch.int32)) and not torch.equal(a.raw, whole.raw)
     assert a.shadowed.shape == (n, 3) and a.kind.dtype == torch.int32
+
+
+def test_later_chunks_without_seeds_start_mid_row_and_mid_pixel(gpu_ctx, scene_cache):
+    """seeds=None at 2 spp in chunks of 999 hits: 999 is odd, so every other chunk begins with the second sample of a pixel, and no
+    multiple of the 64-pixel row; a later chunk has to carry the seeds of exactly its pixels.  Every route of direct_light and
+    direct_light_power gives the bytes of the same call in one chunk."""
+    w = h = 64
+    s = scenes.cornell_box(w, h)
+    scene = api.Scene(gpu_ctx, s.desc)
+    rays = api.camera_rays(gpu_ctx, s.camera, w, h, 2)
+    assert len(rays) == 8192
+    q = api.trace_rays(scene, rays)
+    p = api.make_light_params(s.num_lights, 3, 2, width=w, spp=2, outputs=A.LIGHT_SHADOWED | A.LIGHT_UNSHADOWED)
+    Q = api.light_slots(scene, p)
+    mis = api.make_mis_params(2, p.numAreaLights, p.numShadowRays)
+    routes = {
+        "full loops": (api.direct_light, {}, Q),
+        "full loops, queued": (api.direct_light, dict(occlusion="queued"), Q),
+        "uniform picks": (api.direct_light, dict(picks=2, pick_depth=1), 3),
+        "power picks": (api.direct_light_power, dict(picks=2, pick_depth=1, mis=None), 3),
+        "power picks with MIS": (api.direct_light_power, dict(picks=2, pick_depth=1, mis=mis), 3),
+    }
+    for name, (fn, kw, per_hit) in routes.items():
+        whole = fn(scene, rays, q, params=p, **kw).raw.view(torch.int32)
+        parts = fn(scene, rays, q, params=p, max_ray_bytes=999 * per_hit * 32, **kw).raw.view(torch.int32)
+        assert bool(whole.any()) and torch.equal(parts, whole), name

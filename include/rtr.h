@@ -1234,6 +1234,44 @@ int  rtr_host_emitter_hits_power(const RtrRay* rays, const RtrHit* hits, const R
                                  const float* lightTris, const uint32_t* lightTriFirst, const RtrAreaLightInfo* lights, uint32_t numLights,
                                  const uint64_t* cdf, const rtr_mis_params* mis, RtrEmitter* out);
 
+/* ---- resampled light picks: candidates from the power table, chosen by what they would contribute at the vertex --------------------
+ * rtr_pick_slots_power looks at the lights and never at the vertex.  rtr_pick_slots_ris takes its place in the chain (-> rtr_light_rays_picked
+ * (slotsIn) -> an occlusion query -> rtr_shade_hits_picked(weights)): for hit k and pick p < P it draws ris->numCandidates (M) slots from the
+ * scene's light-power table, gives each the largest channel of the unshadowed contribution rtr_shade_hits_picked would evaluate there
+ * (the BRDF, both cosines, the distance, the light's colour and its one-sidedness) as its target, keeps one in proportion to target /
+ * table probability, and writes outSlots[k * P + p] and outWeights[k * P + p] = (sum_j target_j / q_j) / (target_y M P): ONE shadow ray
+ * per pick, M BRDFs.  The rule is include/rtr_ris.h (rtr_ris_params: include/rtr_types.h); DESIGN.md section 3 has the estimator and the
+ * unbiasedness argument.  M = 1 is the power pick.  A hit that is not an object, a pick whose candidates all have target 0 (one-sided
+ * triangles facing away, no positive channel) and a table without power give RTR_PICK_NONE and 0.  No output word is ever a NaN or an
+ * infinity.  With RTR_RIS_MIS the target is multiplied by, and the weight carries, the wPick rtr_mis_pick_weights_power computes for
+ * ris->lobes: the outputs replace that call's too, and the bounce ray takes rtr_emitter_hits_power as before.
+ * outCandidates, outTargets (both or neither): [(k * P + p) * M + j] = the slot of candidate j (RTR_PICK_NONE without a table) and its
+ * target as used (0 where it counted as 0, and at a hit that is not an object).
+ * The _async form is ENQUEUED on ctx's stream: on a scene that has its power table (rtr_scene_prepare_light_power) no allocation, no
+ * join, no copy back; the first call of an unprepared scene builds the table as the power calls do.  The plain form then joins that
+ * stream (only that stream).  Refused before anything is written (RTR_ERR_INVALID_ARGUMENT, the message names the function and the
+ * argument): a null or misaligned pointer, numCandidates 0 or above RTR_RIS_MAX_CANDIDATES, unknown flag bits, lobes 0 or unknown with
+ * RTR_RIS_MIS or non-zero without it, non-zero _reserved words, outCandidates without outTargets or the reverse, what
+ * rtr_pick_slots_power and rtr_shade_hits_picked refuse of params and pick, numHits * P * M past 32 bits, an output that overlaps an
+ * input or another output, a scene on another device. */
+int  rtr_pick_slots_ris_async(rtr_ctx* ctx, const rtr_scene* scene, const RtrRay* rays, const RtrHit* hits, uint32_t numHits,
+                              const rtr_light_params* params, const rtr_pick_params* pick, const rtr_ris_params* ris, const uint32_t* seeds,
+                              uint32_t* outSlots, float* outWeights, uint32_t* outCandidates, float* outTargets);
+int  rtr_pick_slots_ris(rtr_ctx* ctx, const rtr_scene* scene, const RtrRay* rays, const RtrHit* hits, uint32_t numHits,
+                        const rtr_light_params* params, const rtr_pick_params* pick, const rtr_ris_params* ris, const uint32_t* seeds,
+                        uint32_t* outSlots, float* outWeights, uint32_t* outCandidates, float* outTargets);
+/* The host forms of include/rtr_ris.h in plain loops, HOST pointers, no device; the device's words equal these.
+ * rtr_host_ris_candidates: outCandidates[(k * P + p) * M + j], the slots rtr_pick_slots_ris draws for a table handed in (cdf, tris: as
+ * rtr_host_pick_slots_power takes them).
+ * rtr_host_ris_select: the reservoir over candidates and targets handed in ([(k * P + p) * M + j]; a candidate that is RTR_PICK_NONE, is
+ * not a slot of the table, lies on a triangle of weight 0 or, with RTR_RIS_MIS, has a wPick that is not finite or not > 0 is passed over) -> outSlots, outWeights [k * P + p].  wPick: with
+ * RTR_RIS_MIS the wPick of every candidate (the targets already contain it; the weight carries the held one), NULL without. */
+int  rtr_host_ris_candidates(const uint64_t* cdf, uint32_t tris, const uint32_t* seeds, uint32_t numHits, const rtr_light_params* params,
+                             const rtr_pick_params* pick, uint32_t numCandidates, uint32_t* outCandidates);
+int  rtr_host_ris_select(const uint64_t* cdf, uint32_t tris, const uint32_t* seeds, uint32_t numHits, const rtr_light_params* params,
+                         const rtr_pick_params* pick, const rtr_ris_params* ris, const uint32_t* candidates, const float* targets,
+                         const float* wPick, uint32_t* outSlots, float* outWeights);
+
 /* ---- errors --------------------------------------------------------------------------- */
 const char* rtr_last_error(void);
 const char* rtr_status_string(int status);

@@ -31,7 +31,10 @@
  * 400 + 100 p for p < 30 (the picks: 400 ... 3300) and 3400 + 200 j, 3500 + 200 j for j < 8 (the sky: 3400 ... 4900): every one a
  * multiple of 100.  The sample numbers take 450 + 100 p (450 ... 3350), 50 modulo 100, so none of them is any of those; all offsets
  * stay below 7919, so the draws of depth + 1 begin behind them.  The light samples of the same hit read offsets 0 ... 1123 from bf
- * (rtr_pick.h), below 7919 + 450, and the sum does not wrap around to them while depth + 1 <= 542 000, as there.
+ * (rtr_pick.h), below 7919 + 450, and the sum does not wrap around to them while depth + 1 <= 542 000, as there.  The resampled picks
+ * (rtr_ris.h) go on behind the sky: candidate j >= 1 of pick p takes 5000 + 48 p + 3 j and that + 1, and the reservoir number of any
+ * candidate 5000 + 48 p + 3 j + 2 — 5002 ... 6439 for p < 30 and j < 16, above 4900 and 3350 and below 7919; candidate 0 is the pick
+ * above, seeds and all.
  * RESOLUTION.  rtr_random gives 24-bit numbers k / 2^24 (and 1.0).  A table whose total is above 2^24 — more than 16 triangles of full
  * weight — has targets no draw can reach: the 2^24 numbers fall total / 2^24 weight units apart, so that a triangle of weight w is met
  * by about w 2^24 / total of them, and a triangle lighter than total / 2^24 by one or none.  The numbers are evenly spaced, so the

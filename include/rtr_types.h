@@ -313,6 +313,18 @@ typedef struct RtrEmitter {
     float    lightPdf, dist; uint32_t lightTri, kind;
 } RtrEmitter;
 
+/* ---- resampled light picks at a path vertex (rtr_pick_slots_ris; the rule is include/rtr_ris.h) --------------------------------------
+ * Each of a vertex's picks is chosen among numCandidates (M, 1 ... RTR_RIS_MAX_CANDIDATES) draws from the light-power table in proportion
+ * to the unshadowed contribution each would make at the vertex.  flags: RTR_RIS_MIS (the picks are weighted against the vertex's bounce,
+ * whose ray then counts the lights it meets: rtr_emitter_hits_power) or 0.  lobes: rtr_bounce_params::lobes of that bounce, required with
+ * the flag and 0 without it.  _reserved must be 0. */
+#define RTR_RIS_MAX_CANDIDATES 16u
+#define RTR_RIS_MIS            1u
+typedef struct rtr_ris_params {
+    uint32_t numCandidates, flags, lobes;
+    uint32_t _reserved[5];
+} rtr_ris_params;             /* 32 bytes */
+
 /* ---- sky importance sampling at a path vertex (rtr_sky_rays, rtr_shade_sky, rtr_sky_hits; the rule is include/rtr_sky.h) --------------
  * numSamples (S, 1 ... RTR_SKY_MAX_SAMPLES) directions per vertex drawn in proportion to the scene's sky table.  depth and frame enter
  * the seed as in rtr_bounce_params (sample j takes the offsets 3400 + 200 j and 3500 + 200 j); width, spp: the pixel rule, used when
@@ -377,6 +389,7 @@ static_assert(sizeof(rtr_pick_params) == 32, "pick params must be 32 B");
 static_assert(sizeof(rtr_mis_params) == 32, "mis params must be 32 B");
 static_assert(sizeof(RtrMisSample) == 32, "mis sample must be 32 B");
 static_assert(sizeof(RtrEmitter) == 32, "emitter record must be 32 B");
+static_assert(sizeof(rtr_ris_params) == 32, "ris params must be 32 B");
 static_assert(sizeof(rtr_sky_params) == 32, "sky params must be 32 B");
 static_assert(sizeof(RtrSkySample) == 32, "sky sample must be 32 B");
 static_assert(sizeof(RtrSkyEscape) == 32, "sky escape record must be 32 B");

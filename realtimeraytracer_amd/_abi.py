@@ -109,6 +109,10 @@ class rtr_mis_params(C.Structure):
     _fields_ = [("numPicks", u32), ("numAreaLights", u32), ("numShadowRays", u32), ("lobes", u32), ("_reserved", u32 * 4)]
 
 
+class rtr_ris_params(C.Structure):
+    _fields_ = [("numCandidates", u32), ("flags", u32), ("lobes", u32), ("_reserved", u32 * 5)]
+
+
 class RtrMisSample(C.Structure):
     _fields_ = [("lightPdf", f32), ("bouncePdf", f32), ("wPick", f32), ("cosLight", f32), ("dist", f32), ("area", f32), ("lightTri", u32), ("_r", u32)]
 
@@ -216,6 +220,7 @@ assert C.sizeof(RtrBounce) == 32 and C.sizeof(rtr_bounce_params) == 32
 assert C.sizeof(rtr_compact_params) == 32
 assert C.sizeof(rtr_accum_params) == 32
 assert C.sizeof(rtr_pick_params) == 32
+assert C.sizeof(rtr_ris_params) == 32
 assert C.sizeof(rtr_mis_params) == 32 and C.sizeof(RtrMisSample) == 32 and C.sizeof(RtrEmitter) == 32
 assert C.sizeof(rtr_sky_params) == 32 and C.sizeof(RtrSkySample) == 32 and C.sizeof(RtrSkyEscape) == 32
 assert C.sizeof(rtr_vertex_range) == 24
@@ -253,6 +258,8 @@ PICK_MAX_SLOTS = 1 << 24        # RTR_PICK_MAX_SLOTS: the most area slots a pick
 SKY_MAX_SAMPLES = 8             # RTR_SKY_MAX_SAMPLES: the most sky samples per path vertex
 POWER_SCALE = 1 << 20           # RTR_POWER_SCALE (include/rtr_power.h): the weight of the strongest light triangle
 POWER_SCAN_CHUNK = 256          # kPowerScanChunk: light triangles one pass of the device's table scan covers
+RIS_MAX_CANDIDATES = 16         # RTR_RIS_MAX_CANDIDATES: the most candidates a resampled pick is chosen among
+RIS_MIS = 1                     # RTR_RIS_MIS: the resampled picks are weighted against the vertex's bounce
 SKY_MIS = 1                     # RTR_SKY_MIS: the balance heuristic between the sky samples and the bounce
 VERTICES_HOST, VERTICES_DEVICE = 0, 1
 
@@ -398,6 +405,10 @@ RTR_SYMBOLS = {
     "rtr_host_pick_slots_power": (C.c_int, [VP, u32, VP, u32, P(rtr_light_params), P(rtr_pick_params), VP, VP]),
     "rtr_host_mis_weights_power": (C.c_int, [u32, VP, VP, VP, VP, VP, VP, u32, u32, VP, VP, VP]),
     "rtr_host_emitter_hits_power": (C.c_int, [VP, VP, VP, VP, u32, VP, VP, VP, u32, VP, P(rtr_mis_params), VP]),
+    "rtr_pick_slots_ris_async": (C.c_int, [VP, VP, VP, VP, u32, P(rtr_light_params), P(rtr_pick_params), P(rtr_ris_params), VP, VP, VP, VP, VP]),
+    "rtr_pick_slots_ris": (C.c_int, [VP, VP, VP, VP, u32, P(rtr_light_params), P(rtr_pick_params), P(rtr_ris_params), VP, VP, VP, VP, VP]),
+    "rtr_host_ris_candidates": (C.c_int, [VP, u32, VP, u32, P(rtr_light_params), P(rtr_pick_params), u32, VP]),
+    "rtr_host_ris_select": (C.c_int, [VP, u32, VP, u32, P(rtr_light_params), P(rtr_pick_params), P(rtr_ris_params), VP, VP, VP, VP, VP]),
 }
 
 RTRH_SYMBOLS = {

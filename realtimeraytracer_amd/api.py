@@ -1284,11 +1284,12 @@ def _occluded(scene, rays, occlusion, ctx, cull_mask=None, ray_flags=0):
 
 
 def _direct_light(who, scene, rays, hits, params, seeds, ctx, max_ray_bytes, occlusion, shadow_cull_mask, shadow_ray_flags, picks, pick_depth, pick_weights=None,
-                  power=False, mis=None):
-    """the chunked stage of direct_light and direct_light_power (who: the one that was called, which has checked occlusion and the flags).
-    A chunk's light rays and its shading come from one of three routes: the full light loops (picks is None; "queued_own_leaf" with
-    their start hints), uniform picks (pick_weights: the caller's weights or None) or power-proportional picks (power; mis: the MIS
-    params of the vertex's bounce or None).  A later chunk without seeds carries its pixels' own."""
+                  power=False, mis=None, ris=None):
+    """the chunked stage of direct_light, direct_light_power and direct_light_ris (who: the one that was called, which has checked
+    occlusion and the flags).  A chunk's light rays and its shading come from one of four routes: the full light loops (picks is None;
+    "queued_own_leaf" with their start hints), uniform picks (pick_weights: the caller's weights or None), power-proportional picks
+    (power; mis: the MIS params of the vertex's bounce or None) or resampled picks (power and ris: the rtr_ris_params, which carry the
+    MIS flag themselves).  A later chunk without seeds carries its pixels' own."""
     if params is None:
         raise ValueError(f"{who}: params (make_light_params) are needed")
     torch = _torch()
@@ -1321,9 +1322,13 @@ def _direct_light(who, scene, rays, hits, params, seeds, ctx, max_ray_bytes, occ
             out[a:b] = shade_hits(scene, r, h, params, occ, seeds=sd, ctx=ctx).raw
             continue
         if power:                        # power-proportional picks: the slots and their weights come first
-            sl, w = pick_slots_power(scene, b - a, params, pick, seeds=sd, ctx=ctx)
-            if mis is not None:
-                w = mis_pick_weights_power(scene, r, h, params, pick, mis, sl, seeds=sd, ctx=ctx)
+            if ris is not None:          # resampled among candidates of the table: one call gives both, MIS or not
+                got = pick_slots_ris(scene, r, h, params, pick, ris, seeds=sd, ctx=ctx)
+                sl, w = got.slots, got.weights
+            else:
+                sl, w = pick_slots_power(scene, b - a, params, pick, seeds=sd, ctx=ctx)
+                if mis is not None:
+                    w = mis_pick_weights_power(scene, r, h, params, pick, mis, sl, seeds=sd, ctx=ctx)
             lr, sl = light_rays_picked(scene, r, h, params, pick, seeds=sd, slots=sl, ctx=ctx)
         else:                            # uniform picks: light_rays_picked draws the slots
             lr, sl = light_rays_picked(scene, r, h, params, pick, seeds=sd, ctx=ctx)
@@ -2024,6 +2029,110 @@ def direct_light_power(scene, rays, hits=None, params=None, picks=1, pick_depth=
                          power=True, mis=mis)
 
 
+# ---- resampled light picks (rtr_pick_slots_ris; include/rtr_ris.h) -----------------------------------------------------------------------
+class RisResult:
+    """What pick_slots_ris gives back: slots int32 (N, P) (uint32 for numpy; A.PICK_NONE: no pick) and weights float32 (N, P) for
+    light_rays_picked(slots=) and shade_hits_picked(weights=); with samples=True candidates (N, P, M), the slots the picks were chosen
+    among, and targets float32 (N, P, M), each candidate's target as used; None without."""
+    slots = weights = candidates = targets = None
+
+
+def make_ris_params(candidates, mis=False, lobes=0):
+    """rtr_ris_params: candidates (M, 1 ... A.RIS_MAX_CANDIDATES) draws from the light-power table per pick; mis: A.RIS_MIS — the picks are
+    weighted against the vertex's bounce, whose lobes (make_bounce_params') are then needed; without it lobes stays 0"""
+    return A.rtr_ris_params(int(candidates), A.RIS_MIS if mis else 0, int(lobes))
+
+
+def pick_slots_ris(scene, rays, hits, params, pick, ris, seeds=None, samples=False, ctx=None, asynchronous=False):
+    """rtr_pick_slots_ris: pick_slots_power with eyes — each of the pick.numPicks (P) picks of a hit is chosen among ris.numCandidates
+    (M) slots drawn from the scene's light-power table, in proportion to the unshadowed contribution shade_hits_picked would evaluate
+    at each (the BRDF, both cosines, the distance, the light's colour and its one-sidedness) -> RisResult, on the device (numpy in gives
+    numpy out).  With ris.flags = A.RIS_MIS the weights carry the wPick of mis_pick_weights_power, whose place the call takes too.
+    rays, hits, params, seeds as shade_hits_picked takes them; samples=True: the candidates and their targets as well."""
+    torch = _torch()
+    ctx = ctx or scene.ctx
+    dev = torch.device("cuda", ctx.device)
+    r, h, sd, as_numpy = _light_inputs(torch, scene, rays, hits, seeds, ctx, "pick_slots_ris", asynchronous)
+    n, p, m = int(r.shape[0]), int(pick.numPicks), int(ris.numCandidates)
+    res = RisResult()
+    res.slots = torch.empty((n, p), dtype=torch.int32, device=dev)
+    res.weights = torch.empty((n, p), dtype=torch.float32, device=dev)
+    if samples:
+        res.candidates = torch.empty((n, p, m), dtype=torch.int32, device=dev)
+        res.targets = torch.empty((n, p, m), dtype=torch.float32, device=dev)
+    _join_torchs_stream(ctx, torch, dev, asynchronous)
+    fn = ctx.lib.rtr_pick_slots_ris_async if asynchronous else ctx.lib.rtr_pick_slots_ris
+    _check(fn(ctx.h, scene.h, _ptr(r, n), _ptr(h, n), n, C.byref(params), C.byref(pick), C.byref(ris), _ptr(sd, n), _ptr(res.slots, n), _ptr(res.weights, n),
+              _ptr(res.candidates, n) if samples else None, _ptr(res.targets, n) if samples else None), "rtr_pick_slots_ris")
+    if as_numpy:
+        res.slots, res.weights = res.slots.cpu().numpy().view(np.uint32), res.weights.cpu().numpy()
+        if samples:
+            res.candidates, res.targets = res.candidates.cpu().numpy().view(np.uint32), res.targets.cpu().numpy()
+    res._keep = (r, h, sd)               # an asynchronous call's inputs stay alive with its result
+    return res
+
+
+def _host_seeds(seeds, n, who):
+    if seeds is None:
+        return None
+    sd = np.ascontiguousarray(seeds)
+    if sd.dtype not in (np.int32, np.uint32) or sd.shape != (n,):
+        raise ValueError(f"{who}: seeds must be int32 or uint32 ({n},), got {sd.dtype} {sd.shape}")
+    return sd
+
+
+def host_ris_candidates(cdf, tris, seeds, n, params, pick, candidates):
+    """rtr_host_ris_candidates: the candidates pick_slots_ris draws for n hits, on the host -> uint32 (n, P, M).  cdf, tris, seeds, params,
+    pick as host_pick_slots_power takes them; candidates: M."""
+    lib = A.hip_lib()
+    who = "host_ris_candidates"
+    n, m = int(n), int(candidates)
+    c = _host_cdf(cdf, tris, who)
+    sd = _host_seeds(seeds, n, who)
+    out = np.zeros((n, int(pick.numPicks), max(m, 0)), np.uint32)
+    _check(lib.rtr_host_ris_candidates(c.ctypes.data_as(A.VP) if c.size else None, int(tris), sd.ctypes.data_as(A.VP) if sd is not None and n else None, n,
+                                       C.byref(params), C.byref(pick), m, out.ctypes.data_as(A.VP) if out.size else None), who)
+    return out
+
+
+def host_ris_select(cdf, tris, seeds, n, params, pick, ris, candidates, targets, w_pick=None):
+    """rtr_host_ris_select: the reservoir of include/rtr_ris.h over candidates uint32 (n, P, M) and targets float32 (n, P, M) handed in, on
+    the host -> (slots uint32 (n, P), weights float32 (n, P)).  w_pick: float32 (n, P, M), the candidates' wPick, with ris.flags =
+    A.RIS_MIS (the targets already contain it); None without.  The other arguments as host_ris_candidates."""
+    lib = A.hip_lib()
+    who = "host_ris_select"
+    n, p, m = int(n), int(pick.numPicks), int(ris.numCandidates)
+    c = _host_cdf(cdf, tris, who)
+    sd = _host_seeds(seeds, n, who)
+    cand = np.ascontiguousarray(candidates)
+    if cand.dtype not in (np.int32, np.uint32) or cand.size != n * p * m:
+        raise ValueError(f"{who}: candidates must be int32 or uint32 ({n}, {p}, {m}), got {cand.dtype} {cand.shape}")
+    tg = np.ascontiguousarray(targets, dtype=np.float32)
+    wp = None if w_pick is None else np.ascontiguousarray(w_pick, dtype=np.float32)
+    if tg.size != n * p * m or (wp is not None and wp.size != n * p * m):
+        raise ValueError(f"{who}: targets and w_pick must be float32 ({n}, {p}, {m})")
+    slots, weights = np.zeros((n, p), np.uint32), np.zeros((n, p), np.float32)
+    ptr = lambda x: x.ctypes.data_as(A.VP) if x is not None and x.size else None
+    _check(lib.rtr_host_ris_select(ptr(c), int(tris), ptr(sd) if n else None, n, C.byref(params), C.byref(pick), C.byref(ris), ptr(cand), ptr(tg), ptr(wp),
+                                   ptr(slots), ptr(weights)), who)
+    return slots, weights
+
+
+def direct_light_ris(scene, rays, hits=None, params=None, picks=1, candidates=4, pick_depth=0, seeds=None, mis=None, ctx=None, max_ray_bytes=256 << 20,
+                     occlusion="dense", shadow_cull_mask=None, shadow_ray_flags=0):
+    """direct_light_power with resampled picks: closest hit (when hits is None) -> pick_slots_ris(make_ris_params(candidates, ...)) ->
+    light_rays_picked(slots=) -> the occlusion query -> shade_hits_picked(weights=), in direct_light's chunks: still picks + 1 rays per
+    hit, each pick chosen among `candidates` draws of the power table by what it would contribute at the hit.  mis: None, or
+    make_mis_params(...) of the vertex's bounce — then the call passes A.RIS_MIS with mis.lobes, and the bounce ray is to count the lights
+    it meets (emitter_hits_power), as with direct_light_power.  The other arguments as direct_light_power.  -> RadianceResult."""
+    shadow_ray_flags = _ray_flags("direct_light_ris", shadow_ray_flags, False)
+    if occlusion not in ("dense", "queued"):
+        raise ValueError(f"direct_light_ris: occlusion must be 'dense' or 'queued' (the picked rays have no start hints), got {occlusion!r}")
+    ris = make_ris_params(candidates, mis is not None, mis.lobes if mis is not None else 0)
+    return _direct_light("direct_light_ris", scene, rays, hits, params, seeds, ctx, max_ray_bytes, occlusion, shadow_cull_mask, shadow_ray_flags, picks, pick_depth,
+                         power=True, mis=mis, ris=ris)
+
+
 # ---- sky importance sampling at a path vertex (rtr_sky_rays, rtr_shade_sky, rtr_sky_hits; include/rtr_sky.h) ---------------------------
 class SkyTable:
     """A sky table on the host: width, height, rows — uint32 (height, width), each row's inclusive prefix sums of its cell weights — and
@@ -2379,6 +2488,23 @@ def path_trace_power(scene, rays, light_params, bounces, sky_samples=1, sky_from
                        compact, roulette_from, survival_floor, sky_samples=sky_samples, sky_from=sky_from, sky_mis=sky_mis, light_picks=light_picks, pick_from=pick_from)
 
 
+def path_trace_ris(scene, rays, light_params, bounces, sky_samples=1, sky_from=0, sky_mis=True, light_picks=1, pick_from=1, ris_candidates=4, seeds=None,
+                   occlusion="dense", bounce_cull_mask=None, bounce_ray_flags=0, max_ray_bytes=256 << 20, ctx=None, compact=False, roulette_from=None,
+                   survival_floor=0.05):
+    """path_trace_power with resampled light picks (include/rtr_ris.h): the same loop, the same arguments and defaults, and
+
+        a vertex d >= pick_from takes direct_light_ris(..., picks=P, candidates=ris_candidates, pick_depth=d, mis = the MIS params at a
+            MIS vertex, else None) in place of direct_light_power: each pick is chosen among ris_candidates draws of the power table by
+            what it would contribute at the vertex; a MIS vertex passes RTR_RIS_MIS
+        at a vertex d >= 1 whose hit is a light, rad = emitter_hits_power(...).radiance when vertex d - 1 was a MIS vertex, as there.
+
+    The candidates read numbers of their own, none of them the bounce's or the roulette's, so which paths live does not depend on them.
+    ris_candidates=1 is path_trace_power's picks.  -> PathResult."""
+    return _path_trace("path_trace_ris", "ris", False, scene, rays, light_params, bounces, seeds, occlusion, bounce_cull_mask, bounce_ray_flags, max_ray_bytes, ctx,
+                       compact, roulette_from, survival_floor, sky_samples=sky_samples, sky_from=sky_from, sky_mis=sky_mis, light_picks=light_picks, pick_from=pick_from,
+                       ris_candidates=ris_candidates)
+
+
 class _LoopDefault:
     """the default of a path_trace_library keyword: whatever the named loop's own default is"""
     def __repr__(self):
@@ -2394,23 +2520,26 @@ _LOOPS = {
     "mis": {"light_picks": 1, "pick_from": 1},
     "sky": {"sky_samples": 1, "sky_from": 0, "sky_mis": True, "light_picks": 1, "pick_from": 1},
     "power": {"sky_samples": 1, "sky_from": 0, "sky_mis": True, "light_picks": 1, "pick_from": 1},
+    "ris": {"sky_samples": 1, "sky_from": 0, "sky_mis": True, "light_picks": 1, "pick_from": 1, "ris_candidates": 4},
 }
 # the loops with MIS vertices, and why each of them cannot do without light_picks
 _PICKS_NEEDED = {
     "mis": "the MIS is between the picks and the bounce",
     "sky": "the loop is path_trace_mis's",
     "power": "the power table is what the picks are drawn from",
+    "ris": "the picks are what is resampled",
 }
 
 
 def _loop_keywords(who, loop, library, given):
-    """the keywords of a loop resolved through _LOOPS and checked -> (light_picks, pick_from, sky), sky: (samples, from, mis) or None.
+    """the keywords of a loop resolved through _LOOPS and checked -> (light_picks, pick_from, sky, ris), sky: (samples, from, mis) or None,
+    ris: the candidates per pick or None.
     who: the function that was called; given: its keywords (LOOP_DEFAULT or absent: the loop's own default).  Nothing but the keywords
     is looked at."""
     if loop not in _LOOPS:
         raise ValueError(f"{who}: loop must be one of {', '.join(map(repr, _LOOPS))}, got {loop!r}")
     own, kw = _LOOPS[loop], {}
-    for name in _LOOPS["power"]:
+    for name in _LOOPS["ris"]:
         value = given.get(name, LOOP_DEFAULT)
         if name not in own and value is not LOOP_DEFAULT:
             raise ValueError(f"{who}: loop={loop!r} has no {name}")
@@ -2428,18 +2557,23 @@ def _loop_keywords(who, loop, library, given):
         sky = (s, int(kw["sky_from"]), bool(kw["sky_mis"])) if s else None
     if library and kw["pick_from"] is None:      # path_trace_library reads None as 1; a loop without picks never reads it
         kw["pick_from"] = 1
-    return kw["light_picks"], kw["pick_from"], sky
+    ris = None
+    if "ris_candidates" in own:
+        ris = int(kw["ris_candidates"])
+        if not 1 <= ris <= A.RIS_MAX_CANDIDATES:
+            raise ValueError(f"{who}: ris_candidates must be 1 ... {A.RIS_MAX_CANDIDATES}, got {ris}")
+    return kw["light_picks"], kw["pick_from"], sky, ris
 
 
 def _path_trace(who, loop, library, scene, rays, light_params, bounces, seeds, occlusion, bounce_cull_mask, bounce_ray_flags, max_ray_bytes, ctx, compact, roulette_from,
                 survival_floor, **given):
-    """the loop of path_trace, path_trace_picked, path_trace_mis, path_trace_sky, path_trace_power and path_trace_library.  loop: its
-    name in _LOOPS ("mis", "sky", "power": with MIS vertices; "power": the pick vertices take direct_light_power and the light hits
-    emitter_hits_power); who, given: as _loop_keywords takes them.  library chooses between the two forms of what differs: step, the
+    """the loop of path_trace, path_trace_picked, path_trace_mis, path_trace_sky, path_trace_power, path_trace_ris and path_trace_library.
+    loop: its name in _LOOPS ("mis", "sky", "power", "ris": with MIS vertices; "power", "ris": the pick vertices take direct_light_power
+    or direct_light_ris and the light hits emitter_hits_power); who, given: as _loop_keywords takes them.  library chooses between the two forms of what differs: step, the
     arithmetic of a vertex (include/rtr_accum.h) in torch or by accumulate_paths, and take, the records of a compaction's survivors by
     torch indexing or by gather_records.  Everything else, and its order, is written once, here."""
-    light_picks, pick_from, sky = _loop_keywords(who, loop, library, given)
-    mis, power = loop in _PICKS_NEEDED, loop == "power"
+    light_picks, pick_from, sky, ris = _loop_keywords(who, loop, library, given)
+    mis, power = loop in _PICKS_NEEDED, loop in ("power", "ris")
     if roulette_from is not None and not compact:
         raise ValueError("path_trace: roulette_from needs compact=True (a path the roulette kills saves nothing while it keeps its lane)")
     if roulette_from is not None and int(roulette_from) < 0:
@@ -2504,7 +2638,10 @@ def _path_trace(who, loop, library, scene, rays, light_params, bounces, seeds, o
         q = trace_rays(scene, r, ctx=ctx) if d == 0 else trace_rays(scene, r, ctx=ctx, cull_mask=bounce_cull_mask, ray_flags=bounce_ray_flags)
         sd = seeds if d == 0 else _wrap32(base.to(torch.int64) + d * PATH_SEED_STEP)
         mis_vertex = mis and int(pick_from) <= d < bounces
-        if power and d >= int(pick_from):
+        if ris is not None and d >= int(pick_from):
+            lit = direct_light_ris(scene, r, q, light_params, picks=light_picks, candidates=ris, pick_depth=d, seeds=sd, mis=mis_params if mis_vertex else None, ctx=ctx,
+                                   max_ray_bytes=max_ray_bytes, occlusion=occlusion)
+        elif power and d >= int(pick_from):
             lit = direct_light_power(scene, r, q, light_params, picks=light_picks, pick_depth=d, seeds=sd, mis=mis_params if mis_vertex else None, ctx=ctx,
                                      max_ray_bytes=max_ray_bytes, occlusion=occlusion)
         elif mis_vertex:
@@ -2566,8 +2703,8 @@ def _path_trace(who, loop, library, scene, rays, light_params, bounces, seeds, o
 def path_trace_library(scene, rays, light_params, bounces, loop="power", sky_samples=LOOP_DEFAULT, sky_from=LOOP_DEFAULT, sky_mis=LOOP_DEFAULT,
                        light_picks=LOOP_DEFAULT, pick_from=LOOP_DEFAULT, seeds=None, occlusion="dense", bounce_cull_mask=None, bounce_ray_flags=0,
                        max_ray_bytes=256 << 20, ctx=None, compact=False, roulette_from=None, survival_floor=0.05):
-    """path_trace ("plain"), path_trace_picked ("picked"), path_trace_mis ("mis"), path_trace_sky ("sky") or path_trace_power ("power")
-    with the arithmetic of a vertex done by the library: the same calls in the same order, but where those loops mask light hits and
+    """path_trace ("plain"), path_trace_picked ("picked"), path_trace_mis ("mis"), path_trace_sky ("sky"), path_trace_power ("power") or
+    path_trace_ris ("ris", with its default ris_candidates) with the arithmetic of a vertex done by the library: the same calls in the same order, but where those loops mask light hits and
     misses, form T * rad and T * sky, scatter the terms to their ids, add them to the sum and multiply T by the bounce's weight in
     torch, this one calls accumulate_paths once per vertex, after bounce_rays, so that it makes the next T too — with
     RTR_ACCUM_LIGHTS_FROM_EMITTERS at every vertex d >= 1 (the emitter records where the vertex before was a MIS vertex, none

@@ -78,6 +78,16 @@ struct MisPickArgs {
     const uint64_t* cdf;         /* null: the uniform rule; else the scene's power table (include/rtr_power.h), and pa.slotsIn is needed */
 };
 
+/* Arguments of the resampled-pick kernel (rtr_pick_slots_ris): MisPickArgs as rtr_mis_pick_weights_power's (ma.cdf is needed; ma.pa.slotsIn
+ * and ma.outSamples are not read; ma.lobes with mis alone), and what include/rtr_ris.h needs. */
+struct RisArgs {
+    MisPickArgs ma;              /* ma.pa.outSlots, ma.outWeights: n * P slots and weights for rtr_light_rays_picked / rtr_shade_hits_picked */
+    uint32_t candidates;         /* M: 1 ... RTR_RIS_MAX_CANDIDATES */
+    uint32_t mis;                /* RTR_RIS_MIS: the targets and the weights carry wPick */
+    uint32_t* outCandidates;     /* n * P * M slots, or null */
+    float* outTargets;           /* n * P * M targets as used; null exactly when outCandidates is */
+};
+
 /* The per-scene triangle -> leaf table (rtr_hit_leaves, rtr_light_rays_hinted): entry base[customIndex] + primitiveId, base = the prefix
  * sum of triCount, is the child code of the BVH2 leaf that holds that world-space record (RtrBvhNode::child: negative); an entry no leaf
  * wrote stays 0.  A start hint of the queued occlusion query (include/rtr.h). */
@@ -150,6 +160,8 @@ hipError_t launch_shade_hits_picked(const DeviceScene& sc, const PickArgs& pa, h
 /* per pick the weight under the balance heuristic with the vertex's bounce sample, and optionally what it was made from; with ma.cdf the
  * power form (rtr_mis_pick_weights_power) */
 hipError_t launch_mis_pick_weights(const DeviceScene& sc, const MisPickArgs& ma, hipStream_t stream);
+/* per pick the slot kept of a.candidates draws from the power table in proportion to their unshadowed contributions, and its weight */
+hipError_t launch_pick_slots_ris(const DeviceScene& sc, const RisArgs& a, hipStream_t stream);
 /* tonemap_pack of n float3 read strideWords floats apart */
 hipError_t launch_tonemap_pack(const float* radiance, uint32_t strideWords, uint32_t n, uint32_t* out, hipStream_t stream);
 

@@ -16,6 +16,7 @@
  * k_light_rays_picked / k_shade_hits_picked (rtr_light_rays_picked, rtr_shade_hits_picked) do the same for a few picked area-light slots
  * of each hit (include/rtr_pick.h) and the directional light: the light loops' sample functions, called per picked slot.
  * k_mis_pick_weights (rtr_mis_pick_weights) gives those picks their balance-heuristic weights against the vertex's bounce (include/rtr_mis.h).
+ * k_pick_slots_ris (rtr_pick_slots_ris) chooses each pick among candidates of the power table by what they would contribute (include/rtr_ris.h).
  * Compiled with the library's flags (-ffp-contract=off): the numerical contract of include/rtr_math.h.
  */
 #include "rtr_query_device.h"
@@ -23,6 +24,7 @@
 #include "../../../include/rtr_pick.h"
 #include "../../../include/rtr_mis.h"
 #include "../../../include/rtr_power.h"
+#include "../../../include/rtr_ris.h"
 
 namespace rtrdev {
 
@@ -783,6 +785,97 @@ hipError_t launch_mis_pick_weights(const DeviceScene& sc, const MisPickArgs& ma,
         hipLaunchKernelGGL(k_mis_pick_weights<true>, grid, dim3(kShadeBlock), 0, s, sc, ma);
     } else {
         hipLaunchKernelGGL(k_mis_pick_weights<false>, grid, dim3(kShadeBlock), 0, s, sc, ma);
+    }
+    return hipGetLastError();
+}
+
+/* ---- resampled light picks (rtr_pick_slots_ris; the rule is include/rtr_ris.h) -------------------------------------------------------
+ * One lane per hit: light_hit and fetch_surface<true> once, then for each of the P picks M candidates from the scene's power table
+ * (ma.cdf: the two searches of k_pick_slots_power), each given its target — picked_sample and area_sample_contrib called as
+ * k_shade_hits_picked calls them, so the target is the largest channel of the very bits the shader multiplies later; MIS: times the
+ * wPick k_mis_pick_weights<true> computes for the slot, by the same calls under the same guard — and passed through the header's
+ * reservoir.  The loop state of a pick is the reservoir's four scalars: nothing is indexed by j, so nothing goes to scratch.  Every
+ * slot and weight of every hit is written: RTR_PICK_NONE and 0 at a hit that is not an object.  SAMPLES: the candidates and their
+ * targets as used go out too, the candidates for every hit (they are functions of the seeds alone), 0 targets where the hit is no
+ * object; the forms without SAMPLES contain none of these stores. */
+template <bool MIS, bool SAMPLES>
+__global__ __launch_bounds__(kShadeBlock) void k_pick_slots_ris(DeviceScene sc, RisArgs a) {
+    const MisPickArgs& ma = a.ma;
+    const PickArgs& pa = ma.pa;
+    const LightArgs& la = pa.la;
+    const uint32_t k = blockIdx.x * kShadeBlock + threadIdx.x;
+    if (k >= la.n) return;
+    HitRec h;
+    rtr_v3 dir;
+    RenderArgs ra{};
+    const bool object = light_hit(sc, la, k, h, dir, ra) == RTR_SURFACE_OBJECT;
+    const uint32_t P = pa.picks, M = a.candidates;
+    const uint64_t* __restrict__ cdf = ma.cdf;
+    Accum acc;
+    Surface sf;
+    LocalStats st;
+    RtrRay ray{};
+    RtrSurface rs{};
+    if (object) {
+        fetch_surface<true, false>(sc, ra, h, dir, false, acc, sf, st);
+        if (MIS) {      /* the words of the RtrSurface k_hit_surfaces writes for this hit, as k_mis_pick_weights fills them */
+            ray.origin[0] = ra.cam.position[0]; ray.origin[1] = ra.cam.position[1]; ray.origin[2] = ra.cam.position[2];
+            rs.position[0] = sf.hitPoint.x; rs.position[1] = sf.hitPoint.y; rs.position[2] = sf.hitPoint.z; rs.kind = RTR_SURFACE_OBJECT;
+            rs.normal[0] = sf.hitNormal.x; rs.normal[1] = sf.hitNormal.y; rs.normal[2] = sf.hitNormal.z;
+            rs.color[0] = sf.color.x; rs.color[1] = sf.color.y; rs.color[2] = sf.color.z;
+            rs.roughness = sf.roughness; rs.metallic = sf.metallic;
+        }
+    }
+    const uint64_t total = rtr_power_total(cdf, ma.tris);
+    for (uint32_t p = 0; p < P; ++p) {
+        const size_t at = (size_t)k * P + p;
+        rtr_ris_reservoir res;
+        rtr_ris_begin(&res);
+        if (object || SAMPLES) {
+            for (uint32_t j = 0; j < M; ++j) {
+                /* ra.info.frame is la.frame + the hit's seed base (light_hit) */
+                uint32_t weightT;
+                const uint32_t slot = rtr_ris_candidate(cdf, ma.tris, la.numShadowRays, ra.info.frame, pa.depth, p, j, &weightT);
+                float target = 0.0f, wPick = 0.0f;
+                PickedSample ps;
+                if (object && slot != RTR_PICK_NONE && picked_sample(sc, pa, ra, sf.hitPoint, slot, ps)) {
+                    const rtr_v3 contrib = area_sample_contrib(sf.hitNormal, sf.viewDir, sf.roughness, sf.mSpecular, sf.diffuse, ps.lcol, ps.lintensity, ps.pdf, ps.dir, ps.dist);
+                    float phat = rtr_bounce_max3(contrib);
+                    if (MIS) {
+                        const uint32_t t = slot / la.numShadowRays;
+                        const float4* rec = sc.lightTris + (size_t)t * kLightTriRecord;
+                        const float area = rec[0].w;
+                        const float cosLight = rtr_dot(f4xyz(rec[3]), rtr_neg(ps.dir));
+                        const float pb = rtr_mis_bounce_pdf(&ray, &rs, ps.dir, ma.lobes);
+                        float lightPdf, wp;
+                        const float wt = rtr_power_mis_pick(cdf, ma.tris, t, P, pb, ps.dist, cosLight, area, &lightPdf, &wp);
+                        if (rtr_bounce_finite(wt) & rtr_bounce_finite(ps.dist) & rtr_bounce_finite(cosLight) & rtr_bounce_finite(area) & rtr_bounce_finite3(ps.dir)) wPick = wp;
+                        phat = phat * wPick;
+                    }
+                    target = rtr_ris_target(phat);
+                    rtr_ris_step(&res, total, weightT, slot, target, wPick, rtr_ris_number(ra.info.frame, pa.depth, p, j));
+                }
+                if (SAMPLES) { a.outCandidates[at * M + j] = slot; a.outTargets[at * M + j] = target; }
+            }
+        }
+        float w;
+        pa.outSlots[at] = rtr_ris_finish(&res, M, P, MIS ? 1u : 0u, &w);
+        ma.outWeights[at] = w;
+    }
+}
+
+hipError_t launch_pick_slots_ris(const DeviceScene& sc, const RisArgs& a, hipStream_t s) {
+    if (a.ma.pa.picks == 0u || a.ma.pa.picks > RTR_PICK_MAX || a.candidates == 0u || a.candidates > RTR_RIS_MAX_CANDIDATES || !a.ma.cdf ||
+        !a.outCandidates != !a.outTargets)
+        return hipErrorInvalidValue;
+    const dim3 grid((uint32_t)(((uint64_t)a.ma.pa.la.n + kShadeBlock - 1) / kShadeBlock));
+    const bool samples = a.outCandidates != nullptr;
+    if (a.mis) {
+        if (samples) hipLaunchKernelGGL((k_pick_slots_ris<true, true>), grid, dim3(kShadeBlock), 0, s, sc, a);
+        else hipLaunchKernelGGL((k_pick_slots_ris<true, false>), grid, dim3(kShadeBlock), 0, s, sc, a);
+    } else {
+        if (samples) hipLaunchKernelGGL((k_pick_slots_ris<false, true>), grid, dim3(kShadeBlock), 0, s, sc, a);
+        else hipLaunchKernelGGL((k_pick_slots_ris<false, false>), grid, dim3(kShadeBlock), 0, s, sc, a);
     }
     return hipGetLastError();
 }

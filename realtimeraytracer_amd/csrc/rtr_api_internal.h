@@ -3,7 +3,7 @@
  * the helpers that more than one file calls, each under the name of the file that defines it (as rtrapi::name, and extern "C++" where
  * the definition stands inside that file's extern "C" block).  The ABI is split by subsystem —
  * rtr_api.cpp (errors, context, scene), rtr_api_render.cpp (frames and dispatch), rtr_api_query.cpp (ray queries), rtr_api_paths.cpp
- * (lighting and path vertices), rtr_api_power.cpp (the light-power table and its picks) — and a new subsystem gets a file of its own, not a section in one of these.  What is shared and is not
+ * (lighting and path vertices), rtr_api_power.cpp (the light-power table and its picks), rtr_api_ris.cpp (the resampled picks) — and a new subsystem gets a file of its own, not a section in one of these.  What is shared and is not
  * a name of the ABI lives in namespace rtrapi, which is hidden: the library exports nothing of it.  A helper one file uses stays
  * static in that file.  No anonymous namespace, no static or thread_local object and no function definition that is not inline
  * belongs here: every file would get a copy of its own (the text behind rtr_last_error is rtr_api.cpp's alone). */
@@ -17,6 +17,8 @@
 
 #include <utility>
 #include <vector>
+
+namespace rtrdev { struct PickArgs; }      /* kernels/rtr_query.h: named by fill_pick_args below */
 
 using rtrdev::Counters;
 using rtrdev::DeviceScene;
@@ -252,6 +254,8 @@ int ensure_leaf_table(rtr_ctx* c, const rtr_scene* s, const char* who);
 
 /* rtr_api_paths.cpp */
 int picked_scene_checks(const rtr_ctx* c, const rtr_scene* s, const rtr_light_params* p, const char* who, uint32_t* areaSlots, uint32_t* tris);
+void fill_pick_args(rtrdev::PickArgs& pa, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, uint32_t n, const rtr_light_params* p,
+                    const rtr_pick_params* pick, const uint32_t* seeds, const uint32_t* slots, uint32_t areaSlots, uint32_t tris);
 
 /* rtr_api_power.cpp */
 /* makes the scene's power table if it has none: allocates, builds on `st` (the current device is the scene's) and JOINS, as the sky table */

@@ -270,8 +270,8 @@ extern "C++" int rtrapi::picked_scene_checks(const rtr_ctx* c, const rtr_scene* 
     return rtrdev::pick_check_area(who, *areaSlots);
 }
 
-/* and what their launches take alike; the output arrays and the weights are the caller's */
-static void fill_pick_args(rtrdev::PickArgs& pa, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, uint32_t n, const rtr_light_params* p,
+/* and what their launches take alike; the output arrays and the weights are the caller's.  (rtr_api_ris.cpp calls it too.) */
+extern "C++" void rtrapi::fill_pick_args(rtrdev::PickArgs& pa, const rtr_scene* s, const RtrRay* rays, const RtrHit* hits, uint32_t n, const rtr_light_params* p,
                            const rtr_pick_params* pick, const uint32_t* seeds, const uint32_t* slots, uint32_t areaSlots, uint32_t tris) {
     fill_light_args(pa.la, s, rays, hits, n, p, seeds);
     pa.la.slots = pick->numPicks + 1u;

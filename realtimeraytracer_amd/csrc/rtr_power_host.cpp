@@ -21,16 +21,12 @@ int power_check_pick_call(const char* who, const rtr_light_params* light, const 
     return check_pixel_seeds(who, seeds, light->width, light->spp);
 }
 
-namespace {
-
-/* a table over `tris` triangles: cdf is needed when there are any, 8-B aligned */
 int power_check_table(const char* who, const uint64_t* cdf, uint32_t tris) {
     if (tris > RTR_PICK_MAX_SLOTS) return refusef("%s: tris %u is more than RTR_PICK_MAX_SLOTS = 2^24", who, tris);
     const Arg args[1] = {{cdf, "cdf", 8, tris != 0u}};
     return check_ptrs(who, args);
 }
 
-}  // namespace
 }  // namespace rtrdev
 
 extern "C" int rtr_host_light_power(const float* lightTris, const uint32_t* lightTriFirst, const RtrAreaLightInfo* lights, uint32_t numLights,

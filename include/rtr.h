@@ -223,6 +223,21 @@ int  rtr_scene_export_bvh(const rtr_scene* scene, RtrBvhNode* nodes, size_t node
  * leaf codes index the triangle array of rtr_scene_export_bvh.  Test / oracle hook: the oracle restates the kernel's walk over
  * it to check the kernel's work counters. */
 int  rtr_scene_export_wide(const rtr_scene* scene, RtrWideNode* nodes, size_t nodeBytes);
+/* The same records in the RESIDENT order, byte for byte what the device holds: a best-first top towards the area lights — what the
+ * any-hit kernel keeps in LDS, rtr_trace_top_nodes() records at the most — then every other record in breadth-first order.  The
+ * top grows from the root: the inner child with the highest priority of any record already in it comes next, ties to the lower
+ * breadth-first index; a record's priority is the sum over the area lights of min(1, box area / (4 pi d^2)), d the distance from the
+ * light's centre (its transform's translation) to the record's box.  Record 0 is the root and a record precedes its children, so
+ * every walk is the one over rtr_scene_export_wide; a scene without area lights is resident in breadth-first order.  Every build,
+ * refit and rebuild, synchronous or enqueued, orders the records it writes this way, from the boxes and lights it finds. */
+int  rtr_scene_export_wide_resident(const rtr_scene* scene, RtrWideNode* nodes, size_t nodeBytes);
+/* The 4-wide records the any-hit kernel of this build keeps in LDS (its kTopNodes): the size of the resident order's top. */
+uint32_t rtr_trace_top_nodes(void);
+/* Host restatement of the resident order, no device: `wide` (wideBytes = a positive multiple of 64) is a breadth-first view
+ * (rtr_host_build_bvh_wide or rtr_scene_export_wide), `grid` its grid with the wide centre, `lights` the scene's area lights;
+ * `out` takes the same records in the order rtr_scene_export_wide_resident shows for them with a top of topNodes records. */
+int  rtr_host_wide_resident(const RtrWideNode* wide, size_t wideBytes, const RtrBvhGrid* grid, const RtrAreaLightInfo* lights, uint32_t numLights,
+                            uint32_t topNodes, RtrWideNode* out);
 /* Host-only BVH build (no device needed): validates `desc`, flattens and builds exactly as
  * rtr_scene_create does and copies the result out.  Call with nodes == tris == NULL to get the counts
  * in `stats`.  Used by the CPU-side tests (BVH invariants, oracle BVH-vs-brute-force). */

@@ -139,8 +139,9 @@ typedef struct RtrBvhGrid {
  * a HALF FLOAT: its offset in grid steps from the scene's WIDE CENTRE c (q - c; RtrBvhGrid::wideCentreXY / Z: per axis the mean midpoint of
  * the tree's leaf boxes, so the half floats are finest where the geometry is), rounded outward to 11 significant bits
  * (exact within 2048 steps of c, 2^-11 of the distance from it beyond; a magnitude above 65504 becomes infinite), so that its parameter on a ray is ONE
- * instruction, t = fma(f16 plane, ga, gbc) with v_fma_mix_f32, no conversion (ga, gbc: rtr_ray_grid_centre).  Records are in breadth-first order (the first ones are the top levels, which the kernel keeps in LDS); record 0 is
- * the root.  Built on the device after every build / refit (kernels/rtr_bvh.hip: k_wide_nodes, k_permute_wide).
+ * instruction, t = fma(f16 plane, ga, gbc) with v_fma_mix_f32, no conversion (ga, gbc: rtr_ray_grid_centre).  Exported records are in breadth-first order; record 0 is
+ * the root.  On the device they are in the resident order (rtr_scene_export_wide_resident: a best-first top towards the lights, which
+ * the kernel keeps in LDS, then breadth-first).  Built on the device after every build / refit (kernels/rtr_bvh.hip: k_wide_nodes, k_permute_wide).
  *   plane[k] : slot k: (xmin | ymin << 16) (xmax | ymax << 16) (zmin | zmax << 16), IEEE binary16 each
  *   child[k] : >= 0 index of a record of this array; < 0 leaf code as in RtrBvhNode (triangles in the same leaf-ordered array);
  *              0x80000000 = empty slot (slots 0 and 1 are never empty); its planes are min = +inf, max = -inf: an inside-out box

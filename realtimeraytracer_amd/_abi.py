@@ -281,6 +281,9 @@ RTR_SYMBOLS = {
     "rtr_scene_get_stats": (C.c_int, [VP, P(rtr_scene_stats)]),
     "rtr_scene_export_bvh": (C.c_int, [VP, VP, C.c_size_t, VP, C.c_size_t]),
     "rtr_scene_export_wide": (C.c_int, [VP, VP, C.c_size_t]),
+    "rtr_scene_export_wide_resident": (C.c_int, [VP, VP, C.c_size_t]),
+    "rtr_trace_top_nodes": (C.c_uint32, []),
+    "rtr_host_wide_resident": (C.c_int, [VP, C.c_size_t, VP, VP, C.c_uint32, C.c_uint32, VP]),
     "rtr_host_build_bvh": (C.c_int, [P(rtr_scene_desc), P(rtr_scene_stats), VP, C.c_size_t, VP, C.c_size_t]),
     "rtr_host_build_bvh_wide": (C.c_int, [P(rtr_scene_desc), P(rtr_scene_stats), VP, C.c_size_t, VP, C.c_size_t, VP, C.c_size_t]),
     "rtr_scene_update_lights": (C.c_int, [VP, P(RtrAreaLightInfo), u32]),

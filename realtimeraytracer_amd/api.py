@@ -154,6 +154,16 @@ class Scene:
             out.wide = wn
         return out
 
+    def export_wide_resident(self):
+        """rtr_scene_export_wide_resident: the 4-wide records in the order the device holds them (a best-first top towards the lights,
+        then breadth-first) -> a ctypes RtrWideNode array, or None for a scene without a wide view"""
+        s = self.stats()
+        if not s.numWideNodes:
+            return None
+        wn = (A.RtrWideNode * s.numWideNodes)()
+        _check(self.lib.rtr_scene_export_wide_resident(self.h, wn, C.sizeof(wn)), "rtr_scene_export_wide_resident")
+        return wn
+
     def update_instances(self, instances, lights=None):
         """rtr_scene_update_instances: new transforms (+ optional light infos) -> device-side re-flatten + BVH refit."""
         arr = (A.RtrInstance * len(instances))(*instances)
@@ -672,6 +682,24 @@ def host_build_bvh_wide(desc):
     out = BvhExport((nodes, tris, st.grid))
     out.wide = wide
     out.stats = st
+    return out
+
+
+def trace_top_nodes():
+    """rtr_trace_top_nodes: the 4-wide records the any-hit kernel of this build keeps in LDS"""
+    return int(A.hip_lib().rtr_trace_top_nodes())
+
+
+def host_wide_resident(wide, grid, lights, top=None):
+    """rtr_host_wide_resident: the resident order of a breadth-first 4-wide view, no device -> a ctypes RtrWideNode array.  wide: what
+    host_build_bvh_wide(...).wide or export_bvh().wide hold; grid: their grid (stats.grid / the export's third element); lights: the
+    scene's A.RtrAreaLightInfo records (a sequence or a ctypes array, may be empty); top: the size of the best-first top
+    (default: trace_top_nodes())."""
+    lib = A.hip_lib()
+    n = len(lights) if lights is not None else 0
+    li = (A.RtrAreaLightInfo * n)(*lights) if n else None
+    out = (A.RtrWideNode * len(wide))()
+    _check(lib.rtr_host_wide_resident(wide, C.sizeof(wide), C.byref(grid), li, n, trace_top_nodes() if top is None else int(top), out), "rtr_host_wide_resident")
     return out
 
 

@@ -4,6 +4,7 @@
  * replaces in the reference. */
 #include "bvh_build.h"
 #include "../../include/rtr_math.h"
+#include "kernels/rtr_hot_top.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -637,8 +638,13 @@ void make_wide_host(const RtrBvhNode* nodes, size_t count, const uint8_t* shape,
             o.child[j] = code_of(j);
         }
     }
+    wide_breadth_first(all.data(), count, wide);
+}
+
+void wide_breadth_first(const RtrWideNode* all, size_t count, std::vector<RtrWideNode>& wide) {
     std::vector<uint32_t> remap(count, 0xffffffffu), order;
     order.reserve(count);
+    if (count == 0) { wide.clear(); return; }
     order.push_back(0); remap[0] = 0;
     for (size_t head = 0; head < order.size(); ++head)
         for (int k = 0; k < 4; ++k) {
@@ -649,6 +655,52 @@ void make_wide_host(const RtrBvhNode* nodes, size_t count, const uint8_t* shape,
     for (size_t j = 0; j < order.size(); ++j) {
         wide[j] = all[order[j]];
         for (int k = 0; k < 4; ++k) if (wide[j].child[k] >= 0) wide[j].child[k] = (int32_t)remap[(size_t)wide[j].child[k]];
+    }
+}
+
+/* ---- the resident order (kernels/rtr_hot_top.h; kernels/rtr_bvh.hip: k_hot_top_select + k_hot_top_apply restated) ---- */
+void hot_top_positions(const RtrWideNode* wide, size_t count, const RtrBvhGrid& grid, const RtrAreaLightInfo* lights, uint32_t numLights, uint32_t top,
+                       std::vector<uint32_t>& pos) {
+    pos.resize(count);
+    for (size_t i = 0; i < count; ++i) pos[i] = (uint32_t)i;
+    if (top > RTR_HOT_TOP_MAX) top = RTR_HOT_TOP_MAX;
+    if (count == 0 || numLights == 0 || top <= 1u) return;
+    struct Cand { uint32_t score, id; };
+    std::vector<Cand> cand;
+    std::vector<uint32_t> sel{0u};
+    const float* centres = reinterpret_cast<const float*>(lights) + 20;      /* transform[12..14] */
+    auto add_children = [&](uint32_t id) {
+        const RtrWideNode& n = wide[id];
+        for (int k = 0; k < 4; ++k) {
+            const int32_t cd = n.child[k];
+            if (cd < 0 || (size_t)cd >= count) continue;
+            cand.push_back(Cand{rtr_f2u(rtr_hot_score(n.plane[k][0], n.plane[k][1], n.plane[k][2], &grid, centres, numLights, 24u)), (uint32_t)cd});
+        }
+    };
+    add_children(0u);
+    while (sel.size() < top && !cand.empty()) {
+        size_t best = 0;                        /* the highest priority, then the lower breadth-first index, then the first in the list */
+        for (size_t i = 1; i < cand.size(); ++i)
+            if (cand[i].score > cand[best].score || (cand[i].score == cand[best].score && cand[i].id < cand[best].id)) best = i;
+        const uint32_t id = cand[best].id;
+        cand[best] = cand.back(); cand.pop_back();
+        if (std::find(sel.begin(), sel.end(), id) != sel.end()) continue;      /* a record met twice (never in a tree) is taken once */
+        sel.push_back(id);
+        add_children(id);
+    }
+    /* the set in the order it grew, then everything else in the order it had */
+    std::vector<uint32_t> sorted(sel);
+    std::sort(sorted.begin(), sorted.end());
+    for (size_t i = 0; i < count; ++i)
+        pos[i] = (uint32_t)(sel.size() + i - (size_t)(std::lower_bound(sorted.begin(), sorted.end(), (uint32_t)i) - sorted.begin()));
+    for (size_t r = 0; r < sel.size(); ++r) pos[sel[r]] = (uint32_t)r;
+}
+
+void permute_wide_host(const RtrWideNode* wide, size_t count, const std::vector<uint32_t>& pos, RtrWideNode* out) {
+    for (size_t i = 0; i < count; ++i) {
+        RtrWideNode n = wide[i];
+        for (int k = 0; k < 4; ++k) if (n.child[k] >= 0 && (size_t)n.child[k] < count) n.child[k] = (int32_t)pos[(size_t)n.child[k]];
+        out[pos[i]] = n;
     }
 }
 

@@ -88,4 +88,16 @@ void collapse_wide(const BvhNodeF* nodes, size_t count, float costTraverse, floa
  * rtr_host_build_bvh (CPU-only tests walk the wide view with the oracle) and checked against the device's records in the GPU tests. */
 void make_wide_host(const RtrBvhNode* nodes, size_t count, const uint8_t* shapeOrNull, RtrBvhGrid& grid, std::vector<RtrWideNode>& wide);
 
+/* The records `all` reaches from record 0 (child codes index `all`), renumbered breadth-first: the order of the EXPORTED view. */
+void wide_breadth_first(const RtrWideNode* all, size_t count, std::vector<RtrWideNode>& wide);
+
+/* The RESIDENT order of a breadth-first view: what the device holds in DeviceScene::nodes4 (kernels/rtr_hot_top.h).  pos[i] is where
+ * record i goes: the best-first top of at most `top` records (grown from the root by the lights' priority, in the order it grew),
+ * then every other record in the order it had.  Host restatement of k_hot_top_select + k_hot_top_apply: the same positions for the
+ * same tree, grid and lights.  No lights, or top <= 1: the identity. */
+void hot_top_positions(const RtrWideNode* wide, size_t count, const RtrBvhGrid& grid, const RtrAreaLightInfo* lights, uint32_t numLights, uint32_t top,
+                       std::vector<uint32_t>& pos);
+/* out[pos[i]] = wide[i], inner child codes renumbered with it */
+void permute_wide_host(const RtrWideNode* wide, size_t count, const std::vector<uint32_t>& pos, RtrWideNode* out);
+
 }  // namespace rtr

@@ -127,6 +127,14 @@ hipError_t bvh_permute_wide(const uint4* in, uint32_t numNodes, const uint32_t* 
  * scratch: 2 x numNodes words.  One launch of one workgroup; nothing is read back. */
 hipError_t bvh_wide_order(const uint4* wide, uint32_t numNodes, uint32_t* remap, uint32_t* scratch, uint32_t* reached, hipStream_t s, const uint32_t* go = nullptr);
 
+/* The resident order (rtr_hot_top.h): turns remap[] — breadth-first ids, from bvh_wide_order or the host loop — into the positions
+ * bvh_permute_wide moves the records to: the best-first top of at most `top` records towards the lights, then every other record in
+ * breadth-first order.  wide: the un-permuted records remap[] was made from.  sel: bvh_hot_top_words() words of scratch.  Two launches
+ * (one wave, then one lane per record); none without lights or with top <= 1: remap[] stays breadth-first. */
+size_t bvh_hot_top_words();
+hipError_t bvh_hot_top(const uint4* wide, uint32_t numNodes, uint32_t* remap, uint32_t* sel, const RtrBvhGrid* grid, const RtrAreaLightInfo* lights, uint32_t numLights,
+                       uint32_t top, hipStream_t s, const uint32_t* go = nullptr);
+
 /* The SAH cost sums of a finished (quantised) tree, rtr_scene_tree_cost: words = bvh_tree_cost_words() x u64, zeroed here and filled by
  * k_tree_cost as innerArea[3], leafArea[3], rootArea[3], numInner, numLeafRefs (rtr_tree_cost's integers, in that order).
  * parentOrNull: as bvh_make_wide — the refit parent array (slots outside the tree are skipped) or null when every slot is in the tree. */

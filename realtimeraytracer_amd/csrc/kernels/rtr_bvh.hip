@@ -28,6 +28,7 @@
 #include "../../../include/rtr_math.h"
 #include "rtr_mirrored.h"
 #include "rtr_tree_sah.h"
+#include "rtr_hot_top.h"
 
 namespace rtrdev {
 
@@ -548,8 +549,8 @@ __global__ __launch_bounds__(kB) void k_wide_nodes(uint32_t numNodes, const uint
     for (int q = 0; q < 4; ++q) wide[(size_t)i * 4 + q] = make_uint4(o[q * 4], o[q * 4 + 1], o[q * 4 + 2], o[q * 4 + 3]);
 }
 
-/* Moves the 4-wide entries into the order the host chose (breadth-first from the root: rtr_api.cpp, make_wide_nodes), so the
- * top of the tree is entries 0..K-1 — the part k_shadow_trace4 keeps in LDS.  Inner child codes are renumbered with it. */
+/* Moves the 4-wide entries into the resident order (breadth-first from the root — rtr_api.cpp make_wide_nodes or k_wide_order — with
+ * the best-first top of bvh_hot_top in front), so entries 0..K-1 are the part k_shadow_trace4 keeps in LDS.  Inner child codes are renumbered with it. */
 __global__ __launch_bounds__(kB) void k_permute_wide(uint32_t numNodes, const uint4* __restrict__ in, const uint32_t* __restrict__ remap,
                                                      uint4* __restrict__ out, const uint32_t* __restrict__ go) {
     if (go && *go == 0u) return;
@@ -874,6 +875,97 @@ __global__ __launch_bounds__(kOrderB) void k_wide_order(const uint4* __restrict_
     }
 }
 
+/* ---- the best-first top of the resident order (rtr_hot_top.h; bvh_build.cpp hot_top_positions restated) ---------------------------
+ * k_hot_top_select: ONE wave grows the set from the root.  wide[] is still in BVH2-id order (child codes are BVH2 ids) and remap[]
+ * holds every record's breadth-first id.  The candidates — the inner children of the records in the set — sit in LDS as (priority
+ * bits, breadth-first id, BVH2 id); a step takes the one with the greatest key (priority << 32 | ~id: the highest priority, then the
+ * lower breadth-first id; of equal keys the first in the list), moves the list's last entry into its place, and appends the taken
+ * record's own inner children, whose priorities lanes 0..3 compute from the record's four child boxes.  A priority is >= 0, so its
+ * bits order as it does.  The list holds at most 3 x set + 1 entries.  sel[0] = the size of the set, sel[1..] = its breadth-first ids
+ * in the order they were taken.
+ * k_hot_top_apply turns remap[] from breadth-first ids into resident positions: a member of the set goes to its rank, every other
+ * record moves up by the number of members after it (breadth-first id b -> size + b - members below b). */
+constexpr uint32_t kHotCand = 3u * RTR_HOT_TOP_MAX + 4u;
+
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t lo = __shfl_xor((uint32_t)v, o), hi = __shfl_xor((uint32_t)(v >> 32), o);
+        const unsigned long long u = ((unsigned long long)hi << 32) | lo;
+        v = u > v ? u : v;
+    }
+    return v;
+}
+__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const uint32_t u = __shfl_xor(v, o); v = u < v ? u : v; }
+    return v;
+}
+
+__global__ __launch_bounds__(64) void k_hot_top_select(const uint4* __restrict__ wide, uint32_t numNodes, const uint32_t* __restrict__ remap,
+                                                       const RtrBvhGrid* __restrict__ grid, const RtrAreaLightInfo* __restrict__ lights, uint32_t numLights,
+                                                       uint32_t top, uint32_t* __restrict__ sel, const uint32_t* __restrict__ go) {
+    __shared__ uint32_t cScore[kHotCand], cId[kHotCand], cNode[kHotCand], sSel[RTR_HOT_TOP_MAX];
+    const uint32_t lane = threadIdx.x;
+    if (blockIdx.x != 0 || numNodes == 0) return;
+    if (go && *go == 0u) return;                         /* the same word in every lane */
+    if (top > RTR_HOT_TOP_MAX) top = RTR_HOT_TOP_MAX;
+    const uint32_t* words = reinterpret_cast<const uint32_t*>(wide);
+    const float* centres = reinterpret_cast<const float*>(lights) + 20;      /* transform[12..14] */
+    uint32_t nc = 0, ns = 1;                              /* the same in every lane */
+    auto add_children = [&](uint32_t node) {              /* entered by all 64 lanes */
+        const uint32_t* w = words + (size_t)node * 16;
+        uint32_t code = 0xffffffffu, score = 0;
+        if (lane < 4u) {
+            code = w[12 + lane];
+            if (code < numNodes) score = rtr_f2u(rtr_hot_score(w[3 * lane], w[3 * lane + 1], w[3 * lane + 2], grid, centres, numLights, 24u));
+        }
+        const bool inner = code < numNodes;               /* (int32_t)code < 0 is >= numNodes as unsigned */
+        const unsigned long long m = __ballot(inner);
+        const uint32_t at = nc + lanes_before(m);
+        if (inner && at < kHotCand) { cScore[at] = score; cId[at] = remap[code]; cNode[at] = code; }
+        nc += (uint32_t)__popcll(m);
+        if (nc > kHotCand) nc = kHotCand;                 /* cannot happen: 3 x set + 1 entries at the most */
+    };
+    if (lane == 0) sSel[0] = 0u;
+    add_children(0u);
+    __syncthreads();
+    while (ns < top && nc > 0u) {
+        unsigned long long best = 0ull; uint32_t bi = 0xffffffffu;
+        for (uint32_t i = lane; i < nc; i += 64u) {
+            const unsigned long long key = ((unsigned long long)cScore[i] << 32) | (0xffffffffu - cId[i]);
+            if (bi == 0xffffffffu || key > best) { best = key; bi = i; }
+        }
+        const unsigned long long all = wave_max_u64(bi == 0xffffffffu ? 0ull : best);
+        const uint32_t win = wave_min_u32(bi != 0xffffffffu && best == all ? bi : 0xffffffffu);      /* < nc: some lane holds the maximum */
+        const uint32_t id = cId[win], node = cNode[win];
+        bool dup = false;
+        for (uint32_t i = lane; i < ns; i += 64u) dup = dup || sSel[i] == id;
+        const bool met = __ballot(dup) != 0ull;           /* a record met twice (never in a tree) is taken once */
+        __syncthreads();
+        --nc;
+        if (lane == 0) { cScore[win] = cScore[nc]; cId[win] = cId[nc]; cNode[win] = cNode[nc]; if (!met) sSel[ns] = id; }
+        __syncthreads();
+        if (!met) { ++ns; add_children(node); __syncthreads(); }
+    }
+    if (lane == 0) sel[0] = ns;
+    for (uint32_t i = lane; i < ns; i += 64u) sel[1 + i] = sSel[i];
+}
+
+__global__ __launch_bounds__(kB) void k_hot_top_apply(uint32_t numNodes, uint32_t* __restrict__ remap, const uint32_t* __restrict__ sel, const uint32_t* __restrict__ go) {
+    __shared__ uint32_t sSel[RTR_HOT_TOP_MAX];
+    if (go && *go == 0u) return;
+    const uint32_t ns = sel[0] < RTR_HOT_TOP_MAX ? sel[0] : RTR_HOT_TOP_MAX;
+    for (uint32_t i = threadIdx.x; i < ns; i += kB) sSel[i] = sel[1 + i];
+    __syncthreads();
+    const uint32_t i = blockIdx.x * kB + threadIdx.x;
+    if (i >= numNodes) return;
+    const uint32_t b = remap[i];
+    uint32_t below = 0, rank = 0xffffffffu;
+    for (uint32_t r = 0; r < ns; ++r) { const uint32_t s = sSel[r]; below += s < b ? 1u : 0u; if (s == b) rank = r; }
+    remap[i] = rank != 0xffffffffu ? rank : ns + b - below;
+}
+
 /* ---- the commit of an enqueued rebuild (rtr_scene_rebuild_async) ------------------------------------------------------------------
  * The device build wrote a STAGE, a second set of the tree's arrays nothing else reads; this kernel decides, on the device, whether the
  * staged tree replaces the live one.  The decision is one word every lane reads before anything else: the staged depth (red[7] of the
@@ -1087,6 +1179,16 @@ hipError_t bvh_commit_tree(const CommitTable& t, const uint32_t* stagedRed, uint
 hipError_t bvh_wide_order(const uint4* wide, uint32_t numNodes, uint32_t* remap, uint32_t* scratch, uint32_t* reached, hipStream_t s, const uint32_t* go) {
     if (numNodes == 0) return hipSuccess;
     hipLaunchKernelGGL(k_wide_order, dim3(1), dim3(kOrderB), 0, s, wide, numNodes, remap, scratch, scratch + numNodes, reached, go);
+    return hipGetLastError();
+}
+
+size_t bvh_hot_top_words() { return RTR_HOT_TOP_MAX + 1u; }
+
+hipError_t bvh_hot_top(const uint4* wide, uint32_t numNodes, uint32_t* remap, uint32_t* sel, const RtrBvhGrid* grid, const RtrAreaLightInfo* lights, uint32_t numLights,
+                       uint32_t top, hipStream_t s, const uint32_t* go) {
+    if (numNodes == 0 || numLights == 0 || !lights || top <= 1u) return hipSuccess;
+    hipLaunchKernelGGL(k_hot_top_select, dim3(1), dim3(64), 0, s, wide, numNodes, remap, grid, lights, numLights, top, sel, go);
+    hipLaunchKernelGGL(k_hot_top_apply, dim3((numNodes + kB - 1) / kB), dim3(kB), 0, s, numNodes, remap, sel, go);
     return hipGetLastError();
 }
 

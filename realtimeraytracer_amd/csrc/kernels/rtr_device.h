@@ -31,7 +31,7 @@ constexpr uint32_t kObjectTermsRecord = 4;  /* float4s per object-terms record: 
 struct DeviceScene {
     const uint4* nodes;              /* RtrBvhNode (layout version 3) as 2 x uint4 */
     const RtrBvhGrid* grid;          /* the grid the 16-bit planes live on; device memory so a refit can rewrite it */
-    const uint4* nodes4;             /* RtrWideNode (layout W4.0): 4-wide view for the any-hit kernel (4 x uint4 per entry, breadth-first order), or null */
+    const uint4* nodes4;             /* RtrWideNode (layout W4.0): 4-wide view for the any-hit kernel (4 x uint4 per entry, resident order: rtr_hot_top.h), or null */
     uint32_t numNodes4;              /* entries in nodes4 (the first wideReached of them are the tree) */
     const float4* tris;              /* RtrBvhTri  as 3 x float4 */
     const RtrVertex* vertices;

@@ -14,9 +14,9 @@ namespace rtrdev {
 #define RTR_SHADOW_FAR_FIRST 1
 #endif
 #if RTR_SHADOW_FAR_FIRST
-#define RTR_ANYHIT_KERNEL_REVISION "r05.3"
+#define RTR_ANYHIT_KERNEL_REVISION "r05.4"
 #else
-#define RTR_ANYHIT_KERNEL_REVISION "r05.3-nearest-first"
+#define RTR_ANYHIT_KERNEL_REVISION "r05.4-nearest-first"
 #endif
 
 /* Batch cursors per queue (and batch lists per octant).  Workgroups are dealt round-robin to the XCDs, and a workgroup starts on
@@ -106,6 +106,8 @@ struct Tunables {
 };
 Tunables tunables_from_env();
 /* name: a field of Tunables (lower case).  false: no such tunable, or a value outside its range. */
+/* kTopNodes of this build: the 4-wide records k_shadow_trace4 can keep in LDS, the size of the resident order's best-first top */
+uint32_t trace_top_capacity();
 bool tunable_set(Tunables& t, const char* name, uint32_t value);
 bool tunable_get(const Tunables& t, const char* name, uint32_t* value);
 

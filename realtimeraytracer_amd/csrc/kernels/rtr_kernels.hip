@@ -952,7 +952,7 @@ __device__ __forceinline__ void inner_nodes4(const __amdgpu_buffer_rsrc_t nodeBu
         if (STATS) { ws.innerIters++; ws.innerLanes += (uint32_t)__popcll(innerMask); }
         if (cur >= 0) {
             if (STATS) { st.nodes++; st.shadowNodes++; }
-            /* one 64-B four-wide node = the whole visit; the first topCount entries (the top levels: breadth-first order) are in
+            /* one 64-B four-wide node = the whole visit; the first topCount entries (the best-first top of the resident order: rtr_hot_top.h) are in
              * LDS, which takes those visits — 35-40 % of all — off the L1's tag look-ups, the busiest unit of this kernel */
             u32x4 q0, q1, q2, q3;
             const bool inLds = __builtin_amdgcn_inverse_ballot_w64(__builtin_amdgcn_ballot_w64((uint32_t)cur < topCount));      /* the mask once: branch and select from one compare */
@@ -1950,6 +1950,8 @@ const TunableField kTunables[] = {
     {"trace_top_nodes", &Tunables::trace_top_nodes, 0u, 0xffffffffu}, {"resolve_row_waves", &Tunables::resolve_row_waves, 0u, 1u}, {"resolve_compact", &Tunables::resolve_compact, 0u, 1u}, {"split_priorities", &Tunables::split_priorities, 0u, 1u},
 };
 }  // namespace
+
+uint32_t trace_top_capacity() { return kTopNodes; }
 
 bool tunable_set(Tunables& t, const char* name, uint32_t value) {
     for (const TunableField& f : kTunables)

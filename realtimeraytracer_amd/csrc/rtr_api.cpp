@@ -412,14 +412,16 @@ static int make_object_terms(rtr_scene* s) {
 }
 
 /* (re)builds the 4-wide view of the tree the any-hit kernel walks, on the device, from the quantised BVH2 nodes */
-static int make_wide_nodes(SceneTree& t, hipStream_t st) {
+static int make_wide_nodes(SceneTree& t, const RtrAreaLightInfo* lights, uint32_t numLights, hipStream_t st) {
     const uint32_t n = (uint32_t)t.hostNodes.size();
-    if (!t.nodes4.p) { HIP_TRY(t.nodes4.alloc((size_t)n * 4)); HIP_TRY(t.nodes4tmp.alloc((size_t)n * 4)); HIP_TRY(t.wideRemap.alloc(n)); HIP_TRY(t.wideSums.alloc(rtrdev::bvh_wide_scratch_words())); }
+    /* wideRemap: the permutation, then bvh_hot_top's scratch */
+    if (!t.nodes4.p) { HIP_TRY(t.nodes4.alloc((size_t)n * 4)); HIP_TRY(t.nodes4tmp.alloc((size_t)n * 4)); HIP_TRY(t.wideRemap.alloc(n + rtrdev::bvh_hot_top_words())); HIP_TRY(t.wideSums.alloc(rtrdev::bvh_wide_scratch_words())); }
     if (!t.hostWideShape.empty() && !t.wideShape.p) HIP_TRY(t.wideShape.upload(t.hostWideShape.data(), t.hostWideShape.size(), st));
     hipError_t e = rtrdev::bvh_make_wide(t.nodes.p, n, t.refitReady ? t.parent.p : nullptr, t.grid.p, t.hostWideShape.size() == n ? t.wideShape.p : nullptr, t.nodes4tmp.p, t.wideSums.p, st);
     if (e != hipSuccess) return fail(RTR_ERR_HIP, "4-wide node build: %s", hipGetErrorString(e));
-    /* breadth-first order of the 4-wide tree (child codes = the 4th 16 bytes of every entry), so its top levels are the first
-     * entries: k_shadow_trace4 keeps those in LDS.  Entries the 4-wide tree does not reach keep the ids after them. */
+    /* breadth-first order of the 4-wide tree (child codes = the 4th 16 bytes of every entry); entries the 4-wide tree does not reach
+     * keep the ids after them.  bvh_hot_top then moves the best-first top towards the lights to the front (kernels/rtr_hot_top.h):
+     * k_shadow_trace4 keeps the first entries in LDS. */
     std::vector<uint32_t> codes((size_t)n * 4), remap(n, 0xffffffffu), order;
     HIP_TRY(hipMemcpy2DAsync(codes.data(), 16, reinterpret_cast<const char*>(t.nodes4tmp.p) + 48, 64, 16, n, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -433,7 +435,8 @@ static int make_wide_nodes(SceneTree& t, hipStream_t st) {
     uint32_t next = (uint32_t)order.size();
     for (uint32_t i = 0; i < n; ++i) if (remap[i] == 0xffffffffu) remap[i] = next++;
     HIP_TRY(hipMemcpyAsync(t.wideRemap.p, remap.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    e = rtrdev::bvh_permute_wide(t.nodes4tmp.p, n, t.wideRemap.p, t.nodes4.p, st);
+    e = rtrdev::bvh_hot_top(t.nodes4tmp.p, n, t.wideRemap.p, t.wideRemap.p + n, t.grid.p, lights, numLights, rtrdev::trace_top_capacity(), st);
+    if (e == hipSuccess) e = rtrdev::bvh_permute_wide(t.nodes4tmp.p, n, t.wideRemap.p, t.nodes4.p, st);
     if (e != hipSuccess) return fail(RTR_ERR_HIP, "4-wide node order: %s", hipGetErrorString(e));
     HIP_TRY(hipStreamSynchronize(st));
     t.wideReached = (uint32_t)order.size();
@@ -626,7 +629,7 @@ static int scene_create_impl(rtr_ctx* ctx, const rtr_scene_desc* d, const rtr_sc
         tree.numPrims = (uint32_t)tree.hostTris.size(); tree.numNodeSlots = (uint32_t)tree.hostNodes.size();
     }
 
-    rc = make_wide_nodes(tree, st);
+    rc = make_wide_nodes(tree, s->lights.p, s->numLights, st);
     if (rc == RTR_OK) rc = make_light_tris(s);
     if (rc == RTR_OK) rc = make_object_terms(s);
     if (rc != RTR_OK) { delete s; ctx_release_child(ctx); return rc; }
@@ -819,7 +822,7 @@ static int refit_scene(rtr_scene* s, const RtrInstance* instances, const RtrArea
     /* keep the host mirror (rtr_scene_export_bvh) and the stats in step */
     uint32_t red[8];
     { const int rcb = read_back_tree(t, red); if (rcb != RTR_OK) return rcb; }
-    { const int rc4 = make_wide_nodes(t, st); if (rc4 != RTR_OK) return rc4; }
+    { const int rc4 = make_wide_nodes(t, s->lights.p, s->numLights, st); if (rc4 != RTR_OK) return rc4; }
     if (lightTris || (lights && numLights)) { const int rcl = make_light_tris(s); if (rcl != RTR_OK) return rcl; }
     if (instances) s->hostInstances.assign(instances, instances + numInstances);
     if (lights && numLights) s->hostLights.assign(lights, lights + numLights);
@@ -1031,6 +1034,7 @@ static int enqueue_refit_tail(rtr_scene* s, uint32_t serial, const char* who) {
     e = rtrdev::bvh_make_wide(t.nodes.p, n, t.parent.p, t.grid.p, t.hostWideShape.size() == n ? t.wideShape.p : nullptr, t.nodes4tmp.p, t.wideSums.p, st);
     if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: 4-wide node build: %s", who, hipGetErrorString(e));
     e = rtrdev::bvh_wide_order(t.nodes4tmp.p, n, t.wideRemap.p, t.orderScratch.p, s->asyncWords.p + 1, st);
+    if (e == hipSuccess) e = rtrdev::bvh_hot_top(t.nodes4tmp.p, n, t.wideRemap.p, t.wideRemap.p + n, t.grid.p, s->lights.p, s->numLights, rtrdev::trace_top_capacity(), st);
     if (e == hipSuccess) e = rtrdev::bvh_permute_wide(t.nodes4tmp.p, n, t.wideRemap.p, t.nodes4.p, st);
     if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: 4-wide node order: %s", who, hipGetErrorString(e));
     if (s->numLights) {
@@ -1206,6 +1210,7 @@ static int enqueue_rebuild_chain(rtr_scene* s, uint32_t serial, const char* who,
     e = rtrdev::bvh_make_wide(t.nodes.p, numNodes, t.parent.p, t.grid.p, nullptr, t.nodes4tmp.p, t.wideSums.p, st, go);
     if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: 4-wide node build: %s", who, hipGetErrorString(e));
     e = rtrdev::bvh_wide_order(t.nodes4tmp.p, numNodes, t.wideRemap.p, t.orderScratch.p, s->asyncWords.p + 1, st, go);
+    if (e == hipSuccess) e = rtrdev::bvh_hot_top(t.nodes4tmp.p, numNodes, t.wideRemap.p, t.wideRemap.p + numNodes, t.grid.p, s->lights.p, s->numLights, rtrdev::trace_top_capacity(), st, go);
     if (e == hipSuccess) e = rtrdev::bvh_permute_wide(t.nodes4tmp.p, numNodes, t.wideRemap.p, t.nodes4.p, st, go);
     if (e != hipSuccess) return fail(RTR_ERR_HIP, "%s: 4-wide node order: %s", who, hipGetErrorString(e));
     if (t.leafReady) {      /* the leaf order changed: the table is made again where it is (4 B per triangle, nothing to allocate) */
@@ -1442,7 +1447,7 @@ int rtr_scene_rebuild(rtr_scene* s, uint32_t buildFlags) {
         fresh.hostNodes.swap(bvh.nodes); fresh.hostTris.swap(bvh.tris); fresh.hostWideShape.swap(bvh.wideShape);
         fresh.numPrims = (uint32_t)fresh.hostTris.size(); fresh.numNodeSlots = (uint32_t)fresh.hostNodes.size();
     }
-    rc = make_wide_nodes(fresh, st);
+    rc = make_wide_nodes(fresh, s->lights.p, s->numLights, st);
     if (rc != RTR_OK) return rc;
     /* the stage outlives a host rebuild, which drops the readiness: a scene that was EVER prepared for the enqueued rebuild is prepared
      * again by the next rebuild that gives it a device tree */
@@ -1492,7 +1497,35 @@ int rtr_scene_export_wide(const rtr_scene* s, RtrWideNode* nodes, size_t nodeByt
     { const int rcm = refresh_mirrors(s); if (rcm != RTR_OK) return rcm; }
     if (nodeBytes != (size_t)s->tree.wideReached * sizeof(RtrWideNode)) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_scene_export_wide: nodeBytes %zu != %zu", nodeBytes, (size_t)s->tree.wideReached * sizeof(RtrWideNode));
     HIP_TRY(hipSetDevice(s->ctx->device));
-    HIP_TRY(hipMemcpy(nodes, s->tree.nodes4.p, nodeBytes, hipMemcpyDeviceToHost));      /* the records the tree reaches come first */
+    /* the device holds the RESIDENT order (best-first top, kernels/rtr_hot_top.h); the export is the same tree numbered breadth-first,
+     * as it always was: a record's walk does not depend on where it is stored */
+    std::vector<RtrWideNode> resident(s->tree.wideReached), bfs;
+    HIP_TRY(hipMemcpy(resident.data(), s->tree.nodes4.p, nodeBytes, hipMemcpyDeviceToHost));      /* the records the tree reaches come first */
+    rtr::wide_breadth_first(resident.data(), resident.size(), bfs);
+    if (bfs.size() != resident.size()) return fail(RTR_ERR_HIP, "rtr_scene_export_wide: the resident records reach %zu of %zu", bfs.size(), resident.size());
+    memcpy(nodes, bfs.data(), nodeBytes);
+    return RTR_OK;
+}
+
+int rtr_scene_export_wide_resident(const rtr_scene* s, RtrWideNode* nodes, size_t nodeBytes) {
+    if (!s || !nodes) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_scene_export_wide_resident: null argument");
+    { const int rcm = refresh_mirrors(s); if (rcm != RTR_OK) return rcm; }
+    if (nodeBytes != (size_t)s->tree.wideReached * sizeof(RtrWideNode)) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_scene_export_wide_resident: nodeBytes %zu != %zu", nodeBytes, (size_t)s->tree.wideReached * sizeof(RtrWideNode));
+    HIP_TRY(hipSetDevice(s->ctx->device));
+    HIP_TRY(hipMemcpy(nodes, s->tree.nodes4.p, nodeBytes, hipMemcpyDeviceToHost));
+    return RTR_OK;
+}
+
+uint32_t rtr_trace_top_nodes(void) { return rtrdev::trace_top_capacity(); }
+
+int rtr_host_wide_resident(const RtrWideNode* wide, size_t wideBytes, const RtrBvhGrid* grid, const RtrAreaLightInfo* lights, uint32_t numLights, uint32_t topNodes,
+                           RtrWideNode* out) {
+    if (!wide || !grid || !out || (!lights && numLights)) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_host_wide_resident: null argument");
+    if (wideBytes == 0 || wideBytes % sizeof(RtrWideNode)) return fail(RTR_ERR_INVALID_ARGUMENT, "rtr_host_wide_resident: wideBytes %zu is not a positive multiple of %zu", wideBytes, sizeof(RtrWideNode));
+    const size_t count = wideBytes / sizeof(RtrWideNode);
+    std::vector<uint32_t> pos;
+    rtr::hot_top_positions(wide, count, *grid, lights, numLights, topNodes, pos);
+    rtr::permute_wide_host(wide, count, pos, out);
     return RTR_OK;
 }
 

@@ -81,12 +81,12 @@ struct SceneTree {
     DevBuf<float4> nodesF;               /* rtr::BvhNodeF, 4 x float4 each: device build / refit only */
     DevBuf<RtrBvhGrid> grid;
     DevBuf<unsigned long long> wideSums;     /* scratch of bvh_make_wide */
-    DevBuf<uint4> nodes4tmp;             /* the 4-wide entries in BVH2-id order, before the breadth-first permutation */
-    DevBuf<uint32_t> wideRemap;
+    DevBuf<uint4> nodes4tmp;             /* the 4-wide entries in BVH2-id order, before the permutation into the resident order */
+    DevBuf<uint32_t> wideRemap;          /* the permutation (numNodes words), then bvh_hot_top's scratch */
     DevBuf<uint8_t> wideShape;           /* per BVH2 node: which entries its 4-wide record opens (host builder's cost-driven collapse); empty = greedy */
     std::vector<uint8_t> hostWideShape;
     uint32_t wideReached = 0;            /* entries the 4-wide tree reaches (they come first in nodes4) */
-    DevBuf<uint4> nodes4;                /* RtrWideNode: 4-wide view of the tree for the any-hit kernel, breadth-first order (kernels/rtr_bvh.hip) */
+    DevBuf<uint4> nodes4;                /* RtrWideNode: 4-wide view of the tree for the any-hit kernel, resident order: best-first top, then breadth-first (kernels/rtr_hot_top.h) */
     DevBuf<float4> tris;
     std::vector<RtrBvhNode> hostNodes;
     std::vector<RtrBvhTri> hostTris;
